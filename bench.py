@@ -12,7 +12,14 @@ simulations, moves and records are exactly those of the lock-step driver, `--dri
 (g*60)/4096 plies into its first game, played untimed by the same searched self-play), so the engine is in the steady state of a
 long-running service: games complete in any window, and games/s, sims/s and expansions/s are all measured.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: set up, stagger, W warm-up steps, the K timed steps, the exchange step, the line.
+--dump-outputs DIR writes what the timed path computed (dump_outputs: the records of the timed steps, every slot's game, the network's
+(pi, v) on the slots' positions) as DIR/<name>.npy; the inputs are seeded, so two runs with the same arguments compare output for output.
+--full adds everything else after the timed region: the device calibration, the secondary legs of bench_legs.run_secondary (kernels,
+the other precisions, 6x6, config5, the live PMC traffic passes, the parity sample, the CPU baseline) and, for N > 1 over RCCL, the
+C ABI's own exchange step.
 
 With N > 1 and no launcher environment (RANK / WORLD_SIZE unset) this process only SPAWNS the N ranks (one child
 process per GPU, RCCL rendezvous on 127.0.0.1) and relays rank 0's JSON line -- it never touches the GPU itself; under
@@ -22,10 +29,11 @@ size different from --gpus is an error (exit 2), never a silent 1-GPU run.
 Prints ONE JSON line of <= 6 KB on rank 0 (strict JSON, contract keys first; bench_legs.compact_line): value = node expansions per second
 over all GPUs (the BASELINE metric; the same line carries games/s and sims/s) in the arithmetic `--precision` names -- default bf16x3: fp32
 values carried exactly as three bf16 planes, six bf16 MFMA products per fp32 product (fp32-class results; exact fp32 on the fp32 matrix cores,
-literally what the reference computes in, Net/NNet.py:85, rides beside it as value_f32 / roofline_f32) -- `roofline` for the dominant kernel (HIP events on the launch
-stream, in the timed region; traffic from two rocprofv3 --pmc child passes of this run) and `cpu_baseline` (the CPU oracle -- the reference
-algorithm with batch-1 leaf evaluation -- timed on this host's cores on a bounded sample), then scalars: the same workload in the library's
-other precisions (value_f16x2, roofline_f16x2, ...), whole_path_frac, config4 / config5 / dropin_config0 figures, the parity sample.
+literally what the reference computes in, Net/NNet.py:85, rides beside it as value_f32 / roofline_f32 with --full) -- `roofline` for the dominant kernel (HIP
+events on the launch stream, in the timed region; traffic from the committed profile, or with --full from two rocprofv3 --pmc child passes of this run),
+whole_path_frac, and with --full `cpu_baseline` (the CPU oracle -- the reference algorithm with batch-1 leaf evaluation -- timed on this host's cores on a
+bounded sample), then scalars: the same workload in the library's other precisions (value_f16x2, roofline_f16x2, ...), config4 / config5 /
+dropin_config0 figures, the parity sample.
 Everything else -- `kernels` (every kernel of a step against its own roof), the nested legs (`precisions`, `config4`, `config5`,
 `other_driver`, `cross_game_dedup`, `eval_cache`, `all_layers_as_gemm`, `dropin_config0`, `parity_sample`), notes, `wall_breakdown` -- is
 written to bench_detail.json next to this file.  In the timed region the network evaluates EVERY expansion (cross-game de-duplication off).
@@ -168,20 +176,28 @@ def main():
                     help="arithmetic of the timed region (top-level value / dtype / roofline): bf16x3 (default) = every fp32 value carried EXACTLY as three bf16 "
                          "planes, six bf16 MFMA products per fp32 product, fp32 accumulate -- fp32-class results (the dropped cross terms are below fp32's own "
                          "rounding of a product) at 2.67x the fp32 matrix roof; f32 = exact fp32 matrix cores, literally what the reference computes in "
-                         "(Net/NNet.py:85); f16x2 = f32 via 2 x fp16 split (22 of 24 significand bits).  Every other mode is measured after the timed region "
-                         "and rides beside it (value_<mode>, roofline_<mode>)")
+                         "(Net/NNet.py:85); f16x2 = f32 via 2 x fp16 split (22 of 24 significand bits).  With --full every other mode is measured after the timed "
+                         "region and rides beside it (value_<mode>, roofline_<mode>)")
     ap.add_argument("--stagger-sims", type=int, default=-1,
                     help="simulations per move of the untimed stagger phase that spreads the slots over the plies of a game "
                          "(-1 = --sims: the staggered plies are ordinary self-play at full strength; 0 = no stagger: all games start "
                          "at ply 0 and none completes for ~60 move rounds)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-live-traffic", action="store_true", help="skip the two rocprofv3 --pmc child runs that measure roofline.traffic in this run")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure and check everything else: the device calibration, the secondary legs (kernels, the other "
+                         "precisions, 6x6, de-duplication on, conv2 as a GEMM, config5, drop-in, parity sample), the CPU baseline, the live "
+                         "roofline.traffic passes and, for N > 1 over RCCL, the C ABI's own exchange step.  Off: the run does only what the "
+                         "headline needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed as DIR/<name>.npy (float32 / float64, < 64 MB in all; "
+                         "see dump_outputs) so that two builds can be compared output for output")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline, the parity sample and the legs that use the oracle")
+    ap.add_argument("--no-live-traffic", action="store_true", help="with --full: skip the two rocprofv3 --pmc child runs that measure roofline.traffic in this run")
     ap.add_argument("--no-dedup-compare", "--no-compare", dest="no_compare", action="store_true",
-                    help="skip the secondary measurements (kernels, exact fp32, 6x6, de-duplication on, conv2 as a GEMM, drop-in, parity sample): profiling runs")
+                    help="with --full: skip the secondary measurements (kernels, exact fp32, 6x6, de-duplication on, conv2 as a GEMM, drop-in, parity sample)")
     ap.add_argument("--dedup", default="off", choices=["off", "on"],
                     help="cross-game leaf de-duplication in the timed region.  off (default for the headline): the network evaluates "
                          "every expansion -- no output is shared or cached; on: the library default (a board reached by several "
-                         "games in the same step is evaluated once).  With off, the on-rate is measured afterwards and reported "
+                         "games in the same step is evaluated once).  With off and --full, the on-rate is measured afterwards and reported "
                          "next to it (N = 1 only)")
     ap.add_argument("--batch-cap", type=int, default=-1,
                     help="free-running driver: leaves per network batch; -1 = the cap at which conv3's grid is a whole number of rounds "
@@ -240,6 +256,59 @@ def write_detail(out):
         except OSError:
             continue
     return None
+
+
+DUMP_MAX_RECORDS = 1 << 18       # --dump-outputs: above this many records (92 bytes each as written) a fixed seeded sample of this many
+DUMP_MAX_SLOTS = 1 << 15         # ... and of slots (~570 bytes each): < 45 MB in all
+
+
+def _dump_rows(count, cap):
+    """the rows --dump-outputs writes out of `count`: all of them, or a fixed seeded sample of `cap` in ascending order"""
+    import numpy as np
+    if count <= cap:
+        return np.arange(count)
+    return np.sort(np.random.default_rng(20240607).choice(count, cap, replace=False))
+
+
+def dump_outputs(out_dir, pooled, eng, net):
+    """--dump-outputs DIR: what the timed path hands its caller, as DIR/<name>.npy, for an output-for-output comparison of two builds.
+    records_*: the move records of the games that ended in the timed steps (the exchange step's pool), sorted by (game_id, ply);
+    slot_*: every slot's game after the last timed step, with the root visit counts of its last move; net_pi / net_v: the timed
+    network's (pi, v) on every slot's position after the last timed step.  Bitboards are split into their exact 32-bit halves
+    [..., (low, high)] as float64; game ids are float64, everything else float32.  At most DUMP_MAX_RECORDS records and DUMP_MAX_SLOTS
+    slots (a fixed seeded sample beyond that).  Returns {name: shape}."""
+    import numpy as np
+    from othellozero_amd.distributed import tensor_to_records
+
+    def halves(b):
+        b = np.asarray(b, dtype=np.uint64)
+        return np.stack([b & np.uint64(0xFFFFFFFF), b >> np.uint64(32)], axis=-1).astype(np.float64)
+
+    rec = tensor_to_records(pooled)
+    rec = rec[np.lexsort((rec["ply"], rec["game_id"]))]
+    rec = rec[_dump_rows(rec.size, DUMP_MAX_RECORDS)]
+    st = eng.state()
+    rows = _dump_rows(st["ply"].size, DUMP_MAX_SLOTS)
+    own = np.where(st["player"] == 1, st["black"], st["white"])[rows]
+    opp = np.where(st["player"] == 1, st["white"], st["black"])[rows]
+    pi, v = net.predict_batch(own, opp)
+    arrays = {
+        "records_game_id": rec["game_id"].astype(np.float64),
+        "records_ply": rec["ply"].astype(np.float32), "records_action": rec["action"].astype(np.float32),
+        "records_player": rec["player"].astype(np.float32), "records_z": rec["z"].astype(np.float32),
+        "records_greedy": rec["greedy"].astype(np.float32),
+        "records_black": halves(rec["black"]), "records_white": halves(rec["white"]),
+        "records_final_black": halves(rec["final_black"]), "records_final_white": halves(rec["final_white"]),
+        "slot_game_id": st["game_id"][rows].astype(np.float64), "slot_ply": st["ply"][rows].astype(np.float32),
+        "slot_player": st["player"][rows].astype(np.float32), "slot_finished": st["finished"][rows].astype(np.float32),
+        "slot_black": halves(st["black"][rows]), "slot_white": halves(st["white"][rows]),
+        "slot_root_counts": eng.last_counts()[rows].astype(np.float32),
+        "net_pi": pi.reshape(len(rows), -1).astype(np.float32), "net_v": v.reshape(-1).astype(np.float32),
+    }
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def run_rank(args, rank, world, local_rank, t_proc):
@@ -474,6 +543,11 @@ def run_rank(args, rank, world, local_rank, t_proc):
                                      "when the tables are on (all_layers_as_gemm is the rate with every layer as a kernel / GEMM)"}
         wall = {"setup_s": round(t_setup, 2), "stagger_s": round(t_stagger, 2), "timed_region_s": round(dt, 2)}      # where this process's wall time goes
         out["wall_breakdown"] = wall
+        if args.dump_outputs:                                    # before anything below advances the engine again
+            t_sec = time.perf_counter()
+            out["dumped_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "arrays": dump_outputs(args.dump_outputs, pooled, eng, net)}
+            wall["dump_outputs_s"] = round(time.perf_counter() - t_sec, 2)
+    if rank == 0 and args.full:
         # what THIS device's matrix pipes sustain right now, measured right after the timed region: a pure-MFMA loop (no LDS, no loads, no barriers) per
         # instruction the two precisions run on.  The GEMM kernels' rate moves with it from box to box (and with a power cap), so a reader can
         # tell a slow box from a regression: roofline.achieved x 3 / device_calibration.f16.tflops is the kernel's share of what the pipe gives HERE.
@@ -501,6 +575,7 @@ def run_rank(args, rank, world, local_rank, t_proc):
             run_secondary(dict(args=args, out=out, wall=wall, world=world, net=net, eng=eng, make_engine=make_engine, measure=measure, advance=advance,
                                layer=layer, n=n, G=G, cap_main=cap_main, d=d, dom_launches=dom_launches, flop_ref=flop_ref, batch_cap=batch_cap))
             del eng
+    if rank == 0:
         # ---- output.  stdout: ONE line of <= 6 KB, contract keys first (bench_legs.compact_line) -- printed LAST, so that it is the tail of this
         # process's output whatever a reader keeps.  Everything else (kernels[], the nested legs, notes, wall_breakdown) goes to bench_detail.json next
         # to bench.py (a temporary directory if that is not writable) and, in a few lines, to stderr BEFORE the line.
@@ -509,7 +584,7 @@ def run_rank(args, rank, world, local_rank, t_proc):
         text = compact_line(out)
         print(f"bench.py: detail -> {detail_path}; wall {json.dumps(wall)}", file=sys.stderr, flush=True)
         print(text, flush=True)
-    if world > 1 and args.backend == "nccl" and not args.no_c_abi_gather:
+    if world > 1 and args.backend == "nccl" and args.full and not args.no_c_abi_gather:
         # AFTER the line is out (nothing here can cost the measurement): the same exchange step through the C ABI's own RCCL communicator
         # (oz_comm_* / oz_selfplay_gather_records), checked against the torch.distributed pool; outcome on stderr.  Guarded by a
         # timeout: a rank that cannot finish it in 60 s says so and the run still ends with exit code 0.

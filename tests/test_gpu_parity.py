@@ -1298,7 +1298,7 @@ def test_bench_single_rank_contract(tmp_path):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--games", "256", "--sims", "16",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=root)
+                        "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1 and r.stdout.rstrip().endswith(lines[0])          # the line is the LAST thing on stdout
@@ -1360,6 +1360,45 @@ def test_bench_single_rank_contract(tmp_path):
         assert k in names, k
     assert all(k["ms_per_step"] > 0 and 0 < k["frac"] < 1.5 and k["bound"] for k in det["kernels"])
     assert abs(sum(k["ms_per_step"] for k in det["kernels"]) / det["ms_per_step"] - 1) < 0.5
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_its_outputs_repeat(tmp_path):
+    """bench.py without --full measures the headline only (no secondary leg, no calibration, no CPU baseline) and honours --steps;
+    --dump-outputs writes what the timed path computed as float32 / float64 .npy files, and two runs with the same arguments write the
+    same arrays bit for bit"""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    outs, dumps = [], []
+    for tag in ("a", "b"):
+        d = tmp_path / tag
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--games", "256", "--sims", "16",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        outs.append(json.loads(lines[0]))
+        dumps.append({f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))})
+    out = outs[0]
+    assert out["metric"] == "mcts_node_expansions_per_sec" and out["unit"] == "node-expansions/s" and out["higher_is_better"] is True
+    assert out["dtype"] == "f32 (3xbf16 split)" and out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["value"] > 0
+    assert out["roofline"]["launches"] == 3 * 16 and 0 < out["roofline"]["frac"] < 1
+    for k in ("cpu_baseline", "value_f32", "value_f16x2", "config4_value", "config5_games_per_s", "device_calibration", "value_other_driver",
+              "value_with_cross_game_dedup", "parity_sample_max_err", "dropin_config0_s"):
+        assert k not in out, k
+    a, b = dumps
+    assert set(a) == set(b) and {"records_game_id", "records_action", "records_black", "slot_root_counts", "net_pi", "net_v"} <= set(a)
+    assert all(x.dtype in (np.float32, np.float64) for x in a.values())
+    assert sum(x.nbytes for x in a.values()) < 64 << 20
+    for name in a:
+        assert np.array_equal(a[name], b[name]), name
+    assert a["records_game_id"].size == out["pooled_records"] and np.all(np.diff(a["records_game_id"]) >= 0)
+    assert a["records_black"].shape == (out["pooled_records"], 2) and np.all(a["records_black"] < 2.0 ** 32)
+    assert a["net_pi"].shape == (256, 64) and a["net_v"].shape == (256,) and a["slot_root_counts"].shape == (256, 64)
+    assert np.all(np.isfinite(a["net_pi"])) and np.allclose(a["net_pi"].sum(axis=1), 1.0, atol=1e-5) and np.all(np.abs(a["net_v"]) <= 1)
 
 
 @pytest.mark.gpu

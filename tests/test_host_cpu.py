@@ -338,6 +338,68 @@ def test_bench_parent_reports_failing_ranks():
     assert r.returncode != 0 and "rank" in r.stderr and not [l for l in r.stdout.splitlines() if l.startswith("{")]
 
 
+def test_bench_dump_outputs_writes_bounded_float_arrays(tmp_path, monkeypatch):
+    """bench.dump_outputs on stand-ins for the engine and the network: records sorted by (game_id, ply), bitboards as exact 32-bit halves,
+    only float32 / float64 files, a fixed seeded sample (the same rows twice) above the row caps, < 64 MB in all at the largest sizes"""
+    import importlib.util
+    import torch
+    from othellozero_amd import _lib
+    monkeypatch.setenv("HSA_ENABLE_IPC_MODE_LEGACY", os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))     # importing bench.py sets a default
+    spec = importlib.util.spec_from_file_location("oz_bench_dump", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+
+    class Eng:
+        def __init__(self, G, rs):
+            self.st = dict(black=rs.randint(0, 2 ** 63, G, dtype=np.uint64) * np.uint64(2) + np.uint64(1), white=rs.randint(0, 2 ** 32, G, dtype=np.uint64),
+                           player=np.where(rs.rand(G) < 0.5, 1, -1).astype(np.int8), finished=np.zeros(G, np.uint8),
+                           ply=rs.randint(0, 60, G).astype(np.int32), game_id=np.arange(G, dtype=np.uint64))
+            self.counts = rs.randint(0, 100, (G, 64)).astype(np.int32)
+
+        def state(self):
+            return self.st
+
+        def last_counts(self):
+            return self.counts
+
+    class Net:
+        def predict_batch(self, own, opp):
+            own = np.asarray(own, np.uint64)
+            return np.full((own.size, 8, 8), 1 / 64, np.float32), ((own & np.uint64(0xFF)).astype(np.float32) / 255)
+
+    def records(R, rs):
+        rec = np.zeros(R, _lib.RECORD_DTYPE)
+        rec["game_id"] = rs.randint(0, 1 << 40, R)
+        rec["ply"] = rs.randint(0, 60, R)
+        rec["action"] = rs.randint(0, 64, R)
+        rec["player"] = np.where(rs.rand(R) < 0.5, 1, -1)
+        rec["z"] = rs.randint(-1, 2, R)
+        rec["black"] = rs.randint(0, 2 ** 63, R, dtype=np.uint64) * np.uint64(2) + np.uint64(1)
+        return rec
+
+    rs = np.random.RandomState(3)
+    rec = records(1000, rs)
+    shapes = bench.dump_outputs(str(tmp_path / "small"), torch.from_numpy(rec.view(np.uint8).reshape(-1, 48).copy()), Eng(96, rs), Net())
+    got = {f[:-4]: np.load(tmp_path / "small" / f) for f in os.listdir(tmp_path / "small")}
+    assert set(got) == set(shapes) and all(x.dtype in (np.float32, np.float64) for x in got.values())
+    want = rec[np.lexsort((rec["ply"], rec["game_id"]))]
+    assert np.array_equal(got["records_game_id"], want["game_id"].astype(np.float64)) and np.array_equal(got["records_action"], want["action"])
+    b = got["records_black"].astype(np.uint64)
+    assert np.array_equal(b[:, 0] | (b[:, 1] << np.uint64(32)), want["black"])
+    assert got["net_pi"].shape == (96, 64) and got["net_v"].shape == (96,) and got["slot_root_counts"].shape == (96, 64)
+
+    big = records(bench.DUMP_MAX_RECORDS + 5000, rs)
+    pooled = torch.from_numpy(big.view(np.uint8).reshape(-1, 48).copy())
+    eng = Eng(bench.DUMP_MAX_SLOTS + 300, rs)
+    for tag in ("b1", "b2"):
+        bench.dump_outputs(str(tmp_path / tag), pooled, eng, Net())
+    b1 = {f[:-4]: np.load(tmp_path / "b1" / f) for f in os.listdir(tmp_path / "b1")}
+    assert b1["records_game_id"].shape == (bench.DUMP_MAX_RECORDS,) and b1["slot_ply"].shape == (bench.DUMP_MAX_SLOTS,)
+    assert sum(x.nbytes for x in b1.values()) < 64 << 20
+    for name, x in b1.items():
+        assert np.array_equal(x, np.load(tmp_path / "b2" / (name + ".npy"))), name
+
+
 def test_preferred_batch_cap_makes_conv3_whole_grid_rounds():
     """the cap bench.py gives the free-running driver: the largest batch whose conv3 grid (256 x 256 tiles, 256 CUs) is a whole number of
     rounds -- 3640 leaves for 4096 8x8 games on 512 or 256 filters; nothing to cap where the games themselves already are (6x6, 8192 games)"""

@@ -1,13 +1,13 @@
 #!/bin/bash
-# Run ON THE GPU BOX through gpurun (GRAFT_REPO_ROOT is set there): the driver's own bench command; the stdout line and bench_detail.json are kept
-# under gpurun_out/r6bench, a digest of the detail is printed.  A missing variable or a failed step ends the script.
+# Run on a GPU machine: bench.py --full (every leg, not only the headline); the stdout line and bench_detail.json are kept in the output
+# folder $O below, a digest of the detail is printed.  A missing variable or a failed step ends the script.
 set -euo pipefail
 : "${GRAFT_REPO_ROOT:?run through gpurun (GRAFT_REPO_ROOT unset)}"
 cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
 O=gpurun_out/r6bench
 mkdir -p $O
-SECONDS=0; timeout -k 10 1000 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.out 2> $O/bench.err || { tail -30 $O/bench.err; exit 1; }
+SECONDS=0; timeout -k 10 1000 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench.out 2> $O/bench.err || { tail -30 $O/bench.err; exit 1; }
 echo "bench wall: $SECONDS s; line bytes $(wc -c < $O/bench.out)"
 cp bench_detail.json $O/bench_detail.json
 cat $O/bench.out
