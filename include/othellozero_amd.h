@@ -388,11 +388,13 @@ int oz_trainer_arena_size(int n, int channels, int in_channels, int64_t* nelem);
 int oz_trainer_create(oz_trainer** out, int n, int channels, int in_channels, int max_batch, float lr, float clipvalue /* <= 0: none */,
                       float dropout, float bn_momentum, uint64_t seed, float* external_grads);
 int oz_trainer_destroy(oz_trainer* t);
-/* arithmetic of the 3x3 layers' forward and data-gradient GEMMs: 0 = fp32 matrix cores (default), 1 = f16x2 -- every fp32 value as two
- * fp16 planes, 3 fp16 MFMA products per fp32 product with fp32 accumulation (the inference kernels of precision f16x2; tensors
- * are moved into the fp16 range by exact powers of two taken from their own maxima on the device, per step).  Weight gradients,
- * dense layers, BN, losses and Adam stay fp32.  Needs channels % 256 == 0; an activation above 65504 raises OZ_ERR_STATE at the
- * next synchronising call (forward_backward, fit_epoch). */
+/* arithmetic of the 3x3 layers (conv2..conv4): 0 = fp32 matrix cores (default); 1 = f16x2 -- forward and data-gradient GEMMs with every
+ * fp32 value as two fp16 planes, 3 fp16 MFMA products per fp32 product with fp32 accumulation (the inference kernels of precision f16x2;
+ * tensors are moved into the fp16 range by exact powers of two taken from their own maxima on the device, per step), an activation above
+ * 65504 raises OZ_ERR_STATE at the next synchronising call (forward_backward, fit_epoch); 2 = bf16x3 -- forward, data gradient AND weight
+ * gradient with every fp32 value exactly as three bf16 planes, 6 bf16 MFMA products per fp32 product with fp32 accumulation, no scaling,
+ * no range flag, nothing to refuse.  conv1, the dense layers, BN, losses and Adam stay fp32.  Modes 1 and 2 need channels % 256 == 0 and
+ * allocate their buffers at first use; a trainer may switch among the modes between steps. */
 int oz_trainer_set_precision(oz_trainer* t, int mode);
 int oz_trainer_set_weight(oz_trainer* t, int index, const float* data, int64_t nelem);
 int oz_trainer_get_weight(oz_trainer* t, int index, float* data, int64_t nelem);

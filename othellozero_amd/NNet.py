@@ -40,7 +40,7 @@ class NNetWrapper(_NetHandle):
     _models_built = 0          # Keras numbers layer names per process (conv2d, ..., conv2d_4, ...); checkpoints keep that
 
     def __init__(self, board_size=(8, 8), batch_size=32, epochs=10, num_channels_1=512, num_channels_2=256,
-                 lr=0.001, dropout=0.3, network=NeuralNets.ONN, max_batch=1, seed=0, weights=None, precision="f32"):
+                 lr=0.001, dropout=0.3, network=NeuralNets.ONN, max_batch=1, seed=0, weights=None, precision="f32", train_precision=None):
         super().__init__()
         self._model_index = NNetWrapper._models_built
         NNetWrapper._models_built += 1
@@ -63,6 +63,10 @@ class NNetWrapper(_NetHandle):
         #  fp16 window by an exact power of two at commit, a commit-time self-check against the exact-fp32 kernels refuses networks that amplify
         #  rounding, and a position whose activations leave the calibrated range raises OzError(OZ_ERR_STATE) instead of returning a degraded answer)
         self.precision = precision
+        # train_precision: the trainer's arithmetic for the 3x3 layers ("f32", "f16x2", "bf16x3"); None = f16x2 for an f16x2 network whose
+        # num_channels_1 % 256 == 0, else f32
+        assert train_precision in (None, "f32", "f16x2", "bf16x3"), train_precision
+        self.train_precision = train_precision
         self.requested_precision = precision          # what the caller asked for: a refused f16x2 commit falls back for THAT set of weights only
         self.f16x2_refusals = 0                       # commits precision f16x2 refused so far (train() reports it in its history)
         _lib.check(lib.oz_net_set_precision(self._h, PRECISION_MODES[precision]))
@@ -139,10 +143,16 @@ class NNetWrapper(_NetHandle):
         pi, v = self.predict_batch(np.array([own], np.uint64), np.array([opp], np.uint64))
         return pi[0], v[0]
 
+    def _train_arithmetic(self):
+        if self.train_precision is not None:
+            return self.train_precision
+        return "f16x2" if self.precision == "f16x2" and self.num_channels % 256 == 0 else "f32"
+
     def train(self, examples, verbose=None, seed=None, allreduce=None):
         """Net/NNet.py:53-68: model.fit(x=boards, y=[pis, vs], batch_size=self.batch_size, epochs=self.epochs) on the GPU
         (oz_trainer_*: MFMA forward / backward in the wrapper's precision -- "f16x2" runs the 3x3 layers' forward and data
-        gradient on the fp16 matrix cores like the inference kernels (needs num_channels % 256 == 0, else fp32) -- Adam
+        gradient on the fp16 matrix cores like the inference kernels (needs num_channels % 256 == 0, else fp32); train_precision="bf16x3"
+        runs their forward and both gradients as three bf16 planes per fp32 value (fp32-class, no scaling, no guard) -- Adam
         lr=self.lr with clipvalue 0.5 for ONN / none for BNN, Dropout self.dropout, BN momentum 0.99).  Returns a History-like object (`.history['loss']`, ...).  The TensorBoard
         callback of the reference is not reproduced.  Optimiser state persists across calls like the compiled Keras model's."""
         from . import trainer as T
@@ -156,7 +166,7 @@ class NNetWrapper(_NetHandle):
                                       clipvalue=0.5 if self.network_type is NeuralNets.ONN else 0.0, dropout=self.dropout,
                                       seed=self._model_index if seed is None else seed,
                                       external_grads_ptr=getattr(allreduce, "ptr", None),
-                                      precision="f16x2" if self.precision == "f16x2" and self.num_channels % 256 == 0 else "f32")
+                                      precision=self._train_arithmetic())
             self._trainer_arena = getattr(allreduce, "ptr", None)
             self._fit_calls = 0
         assert getattr(allreduce, "ptr", None) == self._trainer_arena, "train() must keep using the GradientAllReduce it started with"
@@ -181,6 +191,7 @@ class NNetWrapper(_NetHandle):
                 self.precision = "f32"
                 _lib.check(lib.oz_net_commit(self._h))
         hist.precision = self.precision                     # the arithmetic these weights are evaluated in until the next set_weights
+        hist.train_precision = self._trainer.precision      # the arithmetic the trainer's 3x3 layers ran in
         hist.f16x2_refusals = self.f16x2_refusals           # (attributes, not history entries: Keras' history holds per-epoch number lists only)
         return hist
 
@@ -218,7 +229,7 @@ class NNetWrapper(_NetHandle):
     def copy(self):
         return NNetWrapper((self.board_size_x, self.board_size_y), network=self.network_type,
                            num_channels_1=self.num_channels, max_batch=self.max_batch, weights=self.get_weights(),
-                           precision=self.precision)
+                           precision=self.precision, train_precision=self.train_precision)
 
     # ---- profiling hooks used by bench.py
     def time_forward(self, count, iters=3):

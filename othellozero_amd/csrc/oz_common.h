@@ -155,3 +155,15 @@ void oz_set_error(const char* fmt, ...);
     do {                                                                                  \
         if (!(cond)) { oz_set_error(__VA_ARGS__); return OZ_ERR_ARG; }                    \
     } while (0)
+
+// ---------------------------------------------------------------- bf16x3: an fp32 value as three bf16 planes (oz_net_b3.h, header comment)
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ void b3_split(float x, __bf16& b1, __bf16& b2, __bf16& b3) {
+    b1 = (__bf16)x;
+    // the top 0.4 % of fp32's range (|x| > 0x7F7F8000 = bf16's largest value + half an ulp) would ROUND to infinity: take bf16's largest value instead --
+    // the residual (< 2^120) still fits the other two planes exactly
+    if (__builtin_isinf((float)b1) && !__builtin_isinf(x)) b1 = __builtin_bit_cast(__bf16, (unsigned short)(x < 0.f ? 0xFF7Fu : 0x7F7Fu));
+    const float r1 = x - (float)b1;               // exact
+    b2 = (__bf16)r1;
+    b3 = (__bf16)(r1 - (float)b2);                // exact difference, at most 8 significant bits: the cast is exact
+}

@@ -159,3 +159,10 @@ int oz_gemm_f32_launch(const float* in, const float* Wt, const float* scale, con
 int oz_gemm_h2_launch(const void* in_h2, const void* Wh, const float* scale, const float* shift, float* out, const int* d_count, int max_count,
                       int Hin, int Hout, int pad, int Cin, int taps, int N, hipStream_t s, float* partial, long long partial_floats,
                       const void* zero_line, int* flag);
+// the bf16x3 GEMM (k_gemm_b3, oz_net_b3.h) on b3-layout operands, fp32 rows out (act = relu or identity); zero_line = >= 128 B of zeros;
+// tag 0 / 1: forward / data-gradient symbol in a profile
+int oz_gemm_b3_launch(const void* in_b3, const void* Wb, const float* scale, const float* shift, float* out, const int* d_count, int max_count,
+                      int Hin, int Hout, int pad, int Cin, int taps, int N, int relu, hipStream_t s, float* partial, long long partial_floats,
+                      const void* zero_line, int tag);
+// fp32 rows [*d_count * P][C] -> the b3 layout (k_f32_to_b3)
+int oz_f32_to_b3_launch(const float* x, const int* d_count, int max_count, int P, int C, void* out, hipStream_t s);

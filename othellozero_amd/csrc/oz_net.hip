@@ -555,6 +555,69 @@ int oz_gemm_h2_launch(const void* in_h2, const void* Wh, const float* scale, con
     return OZ_OK;
 }
 
+// k_gemm_b3 for callers outside the network object (the trainer's bf16x3 mode): out[M][N] fp32 rows = act((A . Wb^T) * scale + shift), A and
+// Wb in the b3 layout, relu 0 or 1.  Tile and k-split are chosen from `max_count` (the caller's capacity -- a constant of the trainer, so a row's
+// result does not depend on the size of one call): the 256 x 256 tile for unsplit 'valid' layers whose grid fills the chip on it (the network
+// object's rule), else the 128 x 256 tile with the k loop split until every CU has a block (raw slabs in `partial`, then the fixed-order fp32
+// reduce with scale / shift / act).  `tag` 0 / 1 only names the kernel in a profile (forward / data gradient).  NetObj::launch_gemm_b3 is
+// untouched: the inference forward keeps its own tiles and splits.
+int oz_gemm_b3_launch(const void* in_b3, const void* Wb, const float* scale, const float* shift, float* out, const int* d_count, int max_count,
+                      int Hin, int Hout, int pad, int Cin, int taps, int N, int relu, hipStream_t s, float* partial, long long partial_floats,
+                      const void* zero_line, int tag) {
+    OZ_REQUIRE(N % B3_BN == 0 && Cin % B3_BK == 0, "gemm_b3: N %% 256 and Cin %% 32 must be 0 (N=%d Cin=%d)", N, Cin);
+    static bool attr_set_dev[64] = {};                       // per device: function attributes belong to the device the caller is on
+    int dev_now = 0;
+    OZ_HIP(hipGetDevice(&dev_now));
+    bool& attr_set = attr_set_dev[dev_now & 63];
+    if (!attr_set) {
+        OZ_HIP(hipFuncSetAttribute((const void*)k_gemm_b3<7>, hipFuncAttributeMaxDynamicSharedMemorySize, B3_LDS));
+        OZ_HIP(hipFuncSetAttribute((const void*)k_gemm_b3<8>, hipFuncAttributeMaxDynamicSharedMemorySize, B3_LDS));
+        OZ_HIP(hipFuncSetAttribute((const void*)k_gemm_b3_big<7>, hipFuncAttributeMaxDynamicSharedMemorySize, B3B_LDS));
+        OZ_HIP(hipFuncSetAttribute((const void*)k_gemm_b3_big<8>, hipFuncAttributeMaxDynamicSharedMemorySize, B3B_LDS));
+        attr_set = true;
+    }
+    B3Geom g;
+    g.Hin = Hin; g.Hout = Hout; g.pad = pad; g.Cin = Cin; g.taps = taps; g.N = N; g.K = taps * Cin; g.out_b3 = 0; g.relu = relu;
+    const long long Mmax = (long long)max_count * Hout * Hout;
+    g.slab = Mmax * N;
+    auto paid = [&](int bm) { return (double)(((((Mmax + bm - 1) / bm) * (N / B3_BN)) + 255) / 256) * bm; };
+    const long long big_blocks = ((Mmax + B3B_BM - 1) / B3B_BM) * (N / B3B_BN);
+    const bool big = pad == 0 && big_blocks >= 192 && 0.96 * paid(B3B_BM) <= paid(B3_BM);
+    const int BMt = big ? B3B_BM : B3_BM;
+    const int num_mt = (int)((Mmax + BMt - 1) / BMt);
+    int ksplit = 1;
+    if (!big && partial) {
+        const long long blocks = (long long)num_mt * (N / B3_BN);
+        const int nk = g.K / B3_BK;
+        // the largest split <= 16 that keeps the grid within one round of the 256 CUs (one 144 KB block per CU), >= 8 k-tiles per slice
+        while (ksplit < 16 && blocks * (ksplit + 1) <= 256 && nk / (ksplit + 1) >= 8 && (long long)(ksplit + 1) * Mmax * N <= partial_floats) ++ksplit;
+    }
+    g.ksplit = ksplit;
+    const int per_mt = (N / B3_BN) * ksplit;
+    const int grid = num_mt < 8 ? ((per_mt + 7) / 8) * 8 * num_mt : ((num_mt + 7) / 8) * 8 * per_mt;       // (the kernels' two block mappings)
+    void* dst = ksplit > 1 ? (void*)partial : (void*)out;
+    const uint4 *a = (const uint4*)in_b3, *w = (const uint4*)Wb, *z = (const uint4*)zero_line;
+    if (big && tag) hipLaunchKernelGGL(k_gemm_b3_big<8>, dim3(grid), dim3(B3_NT), B3B_LDS, s, a, w, scale, shift, dst, d_count, g, num_mt, z);
+    else if (big) hipLaunchKernelGGL(k_gemm_b3_big<7>, dim3(grid), dim3(B3_NT), B3B_LDS, s, a, w, scale, shift, dst, d_count, g, num_mt, z);
+    else if (tag) hipLaunchKernelGGL(k_gemm_b3<8>, dim3(grid), dim3(B3_NT), B3_LDS, s, a, w, scale, shift, dst, d_count, g, num_mt, z);
+    else hipLaunchKernelGGL(k_gemm_b3<7>, dim3(grid), dim3(B3_NT), B3_LDS, s, a, w, scale, shift, dst, d_count, g, num_mt, z);
+    if (ksplit > 1) {
+        const long long quads = (Mmax * N + 3) / 4;
+        hipLaunchKernelGGL(k_splitk_reduce_f32, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, s, (const float*)partial, g.slab, ksplit, N,
+                           Hout * Hout, d_count, scale, shift, relu, out);
+    }
+    OZ_HIP(hipGetLastError());
+    return OZ_OK;
+}
+// k_f32_to_b3 for callers outside the network object: fp32 rows [*d_count * P][C] -> the b3 layout (grid sized for max_count boards)
+int oz_f32_to_b3_launch(const float* x, const int* d_count, int max_count, int P, int C, void* out, hipStream_t s) {
+    OZ_REQUIRE(C % 32 == 0, "f32_to_b3: C %% 32 must be 0 (C=%d)", C);
+    const long long threads = (long long)max_count * P * (C / 8);
+    hipLaunchKernelGGL(k_f32_to_b3, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, x, d_count, P, C, (uint4*)out);
+    OZ_HIP(hipGetLastError());
+    return OZ_OK;
+}
+
 // ---------------------------------------------------------------- heads
 // one 256-thread block per LP positions whose f2 rows (2 KB each) are staged in LDS once: wave w accumulates k in [128w, 128w+128) of
 // logits[a] = f2 . Wpi[:,a] (one policy column per lane, every coalesced Wpi row load feeds LP positions through LDS broadcasts) and of

@@ -35,8 +35,6 @@
 // a position's result does not depend on its place in the batch or on the batch size.
 #pragma once
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 #define B3_BK 32
 #define B3_BM 128
 #define B3_BN 256
@@ -58,15 +56,7 @@ struct B3Geom {
     long long slab;                               // floats between two partial slabs
 };
 
-__device__ __forceinline__ void b3_split(float x, __bf16& b1, __bf16& b2, __bf16& b3) {
-    b1 = (__bf16)x;
-    // the top 0.4 % of fp32's range (|x| > 0x7F7F8000 = bf16's largest value + half an ulp) would ROUND to infinity: take bf16's largest value instead --
-    // the residual (< 2^120) still fits the other two planes exactly
-    if (__builtin_isinf((float)b1) && !__builtin_isinf(x)) b1 = __builtin_bit_cast(__bf16, (unsigned short)(x < 0.f ? 0xFF7Fu : 0x7F7Fu));
-    const float r1 = x - (float)b1;               // exact
-    b2 = (__bf16)r1;
-    b3 = (__bf16)(r1 - (float)b2);                // exact difference, at most 8 significant bits: the cast is exact
-}
+// b3_split (the three-plane split of one fp32 value) and bf16x8 live in oz_common.h: the trainer converts its operands with the same function
 
 // fp32 rows [rows][C] -> the b3 layout; rows = *d_count * P.  One thread per (row, 8 channels): two 16-byte loads, three 16-byte stores.
 __global__ __launch_bounds__(256) void k_f32_to_b3(const float* __restrict__ x, const int* __restrict__ d_count, int P, int C, uint4* __restrict__ out) {

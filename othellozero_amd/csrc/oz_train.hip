@@ -870,6 +870,214 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_h2(const uint4* __restrict__ X
             }
 }
 
+// ---------------------------------------------------------------- bf16x3 mode of the 3x3 layers (oz_trainer_set_precision 2)
+// Every fp32 operand travels EXACTLY as three bf16 planes (oz_net_b3.h: b3_split, the b3 layout, six products per fp32 product in the order
+// a3 b1 + a1 b3 + a2 b2 + a2 b1 + a1 b2 + a1 b1, fp32 accumulation).  bf16 has fp32's exponent range: no scaling, no maxima, no range flag.
+// Forward and data gradient of conv2..conv4 run on k_gemm_b3 (oz_gemm_b3_launch), their weight gradients on k_wgrad_b3 below; conv1, the
+// dense layers, the heads, BN and Adam stay exact fp32.  The operands are converted per step from the fp32 masters / tensors.
+// Fallback rule: none.  Every trainer capacity (Bmax) takes these kernels: the GEMMs split their k loop until the grid fills the chip (keyed on
+// Bmax), the weight gradient splits its board range; at the reference's batch of 32 both already beat the exact-fp32 kernels they replace.
+//
+// Keras kernel W[9][Cin][Cout] fp32 -> a k_gemm_b3 weight operand, k order k' = (slice * 9 + tap) * 32 + c32 (as k_t_w_to_h2, unscaled):
+//   DGRAD = 0  forward operand:       row n = co, channel of k' = ci:  W[tap][ci][co]
+//   DGRAD = 1  data-gradient operand: row n = ci, channel of k' = co:  W[8 - tap][ci][co]   (reversed, channel-swapped taps)
+template <int DGRAD>
+__global__ __launch_bounds__(256) void k_t_w_to_b3(const float* __restrict__ W, int Cin, int Cout, uint4* __restrict__ out) {
+    const int N = DGRAD ? Cin : Cout, Cch = DGRAD ? Cout : Cin, ng = 9 * Cch / 8;
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    int nrow, grp;
+    if (DGRAD) { grp = (int)(idx % ng); nrow = (int)(idx / ng); }
+    else { nrow = (int)(idx % N); grp = (int)(idx / N); }
+    if (idx >= (long long)N * ng) return;
+    const int kp = grp * 8, tile = kp >> 5, c32 = kp & 31, slice = tile / 9, tap = tile - slice * 9, ch = slice * 32 + c32;
+    bf16x8 p0, p1, p2;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const float v = DGRAD ? W[((size_t)(8 - tap) * Cin + nrow) * Cout + ch + j] : W[((size_t)tap * Cin + ch + j) * Cout + nrow];
+        __bf16 a, b, c;
+        b3_split(v, a, b, c);
+        p0[j] = a; p1[j] = b; p2[j] = c;
+    }
+    uint4* dst = out + (size_t)nrow * (size_t)(9 * Cch / 32 * 12) + (grp >> 2) * 12 + (grp & 3);
+    dst[0] = *reinterpret_cast<uint4*>(&p0);
+    dst[4] = *reinterpret_cast<uint4*>(&p1);
+    dst[8] = *reinterpret_cast<uint4*>(&p2);
+}
+// dz (zero-bordered [B][Hz][Hz][C] fp32, interior Hout^2 at offset zoff) -> the same geometry in the b3 layout; only the interior is written
+// (the b3 buffer is zeroed once at allocation, so its border stays zero).  One thread per (row, 8 channels).
+__global__ __launch_bounds__(256) void k_t_dz_to_b3(const float* __restrict__ dz, const int* __restrict__ d_count, int Hout, int Hz, int zoff, int C,
+                                                    uint4* __restrict__ out) {
+    const int cg = C >> 3, P = Hout * Hout;
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x, m = idx / cg;
+    if (m >= (long long)(*d_count) * P) return;
+    const int g8 = (int)(idx % cg), b = (int)(m / P), pix = (int)(m % P);
+    const size_t row = ((size_t)b * Hz + pix / Hout + zoff) * Hz + pix % Hout + zoff;
+    const f32x4 lo = *reinterpret_cast<const f32x4*>(dz + row * C + g8 * 8), hi = *reinterpret_cast<const f32x4*>(dz + row * C + g8 * 8 + 4);
+    bf16x8 p0, p1, p2;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        __bf16 a, bb, c;
+        b3_split(j < 4 ? lo[j] : hi[j - 4], a, bb, c);
+        p0[j] = a; p1[j] = bb; p2[j] = c;
+    }
+    uint4* dst = out + row * (size_t)(C / 32 * 12) + (g8 >> 2) * 12 + (g8 & 3);
+    dst[0] = *reinterpret_cast<uint4*>(&p0);
+    dst[4] = *reinterpret_cast<uint4*>(&p1);
+    dst[8] = *reinterpret_cast<uint4*>(&p2);
+}
+// octet images in three planes: [octet][row][pixel slot][plane 0 | 1 | 2][C] x 16 B (8 boards of bf16) -- k_t_x_octets / k_t_z_octets with
+// a third plane and no scaling.  4 channels x 3 planes = twelve 16-byte stores per thread.
+__device__ __forceinline__ void t_store_octet4_b3(uint4* __restrict__ dst, int C, const f32x4* v) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        bf16x8 h1, h2, h3;
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            __bf16 a, bb, c;
+            b3_split(v[b][q], a, bb, c);
+            h1[b] = a; h2[b] = bb; h3[b] = c;
+        }
+        dst[q] = *reinterpret_cast<uint4*>(&h1);
+        dst[C + q] = *reinterpret_cast<uint4*>(&h2);
+        dst[2 * C + q] = *reinterpret_cast<uint4*>(&h3);
+    }
+}
+// X octet image of a[l - 1] ([B][Hin][Hin][C] fp32): out[octet][row < Hin + 2 pad][slot < WH_XW][plane][C] (zero border, zero columns, zero boards >= B)
+__global__ __launch_bounds__(256) void k_t_x_octets_b3(const float* __restrict__ a, const int* __restrict__ d_count, int Hin, int pad, int C, uint4* __restrict__ out) {
+    const int B = *d_count, XR = Hin + 2 * pad, noct = (B + 7) >> 3, C4 = C >> 2;
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long long)noct * XR * WH_XW * C4) return;
+    const int ch = (int)(idx % C4) * 4;
+    const long long cell = idx / C4;
+    const int c = (int)(cell % WH_XW), r = (int)((cell / WH_XW) % XR), oct = (int)(cell / ((long long)WH_XW * XR));
+    const int iy = r - pad, ix = c - pad;
+    const bool inside = iy >= 0 && iy < Hin && ix >= 0 && ix < Hin;
+    f32x4 v[8];
+#pragma unroll
+    for (int b = 0; b < 8; ++b) {
+        const int bb = oct * 8 + b;
+        v[b] = (inside && bb < B) ? *reinterpret_cast<const f32x4*>(a + (((size_t)bb * Hin + iy) * Hin + ix) * C + ch) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    t_store_octet4_b3(out + (size_t)cell * 3 * C + ch, C, v);
+}
+// dZ octet image of dz[l] (zero-bordered [B][Hz][Hz][C] fp32, interior Hout^2 at offset zoff): out[octet][row < Hout][slot < WH_ZW][plane][C]
+__global__ __launch_bounds__(256) void k_t_z_octets_b3(const float* __restrict__ dz, const int* __restrict__ d_count, int Hout, int Hz, int zoff, int C,
+                                                       uint4* __restrict__ out) {
+    const int B = *d_count, noct = (B + 7) >> 3, C4 = C >> 2;
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long long)noct * Hout * WH_ZW * C4) return;
+    const int ch = (int)(idx % C4) * 4;
+    const long long cell = idx / C4;
+    const int c = (int)(cell % WH_ZW), r = (int)((cell / WH_ZW) % Hout), oct = (int)(cell / ((long long)WH_ZW * Hout));
+    f32x4 v[8];
+#pragma unroll
+    for (int b = 0; b < 8; ++b) {
+        const int bb = oct * 8 + b;
+        v[b] = (c < Hout && bb < B) ? *reinterpret_cast<const f32x4*>(dz + (((size_t)bb * Hz + r + zoff) * Hz + c + zoff) * C + ch) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    t_store_octet4_b3(out + (size_t)cell * 3 * C + ch, C, v);
+}
+// k_wgrad_b3: the weight gradient of conv2..conv4 on v_mfma_f32_16x16x32_bf16, k_wgrad_h2's scheme (octet images, a block owns a ci x co tile
+// for all nine taps, walks the output rows of each octet with a 4-slot X row ring and two dZ row buffers, every tap reads the same staged rows
+// at a shifted pixel slot) with three planes per value and six products per fp32 product (the order above).
+// LDS plan: with three planes k_wgrad_h2's 64 ci x 128 co tile would need 4 X rows of 30 KB + 2 dZ rows of 48 KB = 216 KB, more than a CU's
+// 160 KB.  This kernel uses 32 ci x 128 co: 4 x 15 KB + 2 x 48 KB = 156 KB (one block per CU), which keeps the ring's one-row prefetch; a
+// 64 x 64 tile would fit only with a 3-row X ring (138 KB), which cannot stream the next row in beside the MFMAs of the current one, and was not built.
+// 8 waves = 2 (16 ci) x 4 (32 co): 9 taps x 2 accumulator tiles of 16 x 16 per wave; per pixel quad a wave reads 6 dZ + 27 X fragments
+// (ds_read_b128) for 108 MFMAs.  Octet ranges split over blockIdx.y (raw slabs + k_t_sum_partials, fixed order).
+// Measured in the training step (8x8, 512 filters, rocprofv3): 56 us per layer at batch 32, 406 us at batch 256 -- bound by the operand stream
+// (every dZ row is staged by C / 32 blocks), not the matrix pipe (profiles/r7_train_b{32,256}_bf16x3_kernel_stats.csv, docs/HISTORY.md round 7).
+#define WB_CI 32
+#define WB_CO 128
+#define WB_XROW (3 * WH_XW * WB_CI * 16)        // bytes of one staged X row: [plane][slot][ci] x 16 B = 15 KB
+#define WB_ZROW (3 * WH_ZW * WB_CO * 16)        // bytes of one staged dZ row: [plane][slot][co] x 16 B = 48 KB
+#define WB_LDS (4 * WB_XROW + 2 * WB_ZROW)      // 156 KB
+__global__ __launch_bounds__(512) void k_wgrad_b3(const uint4* __restrict__ Xt, const uint4* __restrict__ Zt, const int* __restrict__ d_count, WhGeom g,
+                                                  float* __restrict__ dW, int msplit, float* __restrict__ partial, long long slab) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char wb_lds[];
+    unsigned char* const Xring = wb_lds;
+    unsigned char* const Zbuf = wb_lds + 4 * WB_XROW;
+    const int nco = g.Cout / WB_CO;
+    const int ci0 = (blockIdx.x / nco) * WB_CI, co0 = (blockIdx.x % nco) * WB_CO;
+    const int noct = (*d_count + 7) >> 3;
+    const int per = (noct + msplit - 1) / msplit, o0 = blockIdx.y * per, o1 = o0 + per < noct ? o0 + per : noct;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int wm = wave >> 2, wn = wave & 3, r16 = lane & 15, g4 = lane >> 4;
+
+    // LDS-DMA: one instruction = 64 consecutive 16-byte entries.  X row = 15 instructions, instruction q = the (plane, slot) pairs 2q and 2q + 1
+    // (WH_XW is even: both in one plane), lanes = 2 slots x the 32 ci of the tile; dZ row = 48 instructions q = (plane, slot, half), lanes = 64
+    // of the tile's 128 co.  Wave w issues q = w, w + 8, ...
+    auto dma_x = [&](int oct, int row, int slot) {
+        const uint4* src = Xt + (((size_t)oct * g.XR + row) * WH_XW) * 3 * g.Cin + ci0 + (lane & 31);
+        for (int q = wave; q < 3 * WH_XW / 2; q += 8) {
+            const int pc = 2 * q + (lane >> 5), p = pc / WH_XW, c = pc - p * WH_XW;
+            __builtin_amdgcn_global_load_lds((t_gptr)(src + ((size_t)c * 3 + p) * g.Cin), (t_lptr)(Xring + slot * WB_XROW + q * 1024), 16, 0, 0);
+        }
+    };
+    auto dma_z = [&](int oct, int row, int buf) {
+        const uint4* src = Zt + (((size_t)oct * g.Hout + row) * WH_ZW) * 3 * g.Cout + co0 + lane;
+        for (int q = wave; q < 6 * WH_ZW; q += 8) {
+            const int h = q & 1, pc = q >> 1, p = pc / WH_ZW, c = pc - p * WH_ZW;
+            __builtin_amdgcn_global_load_lds((t_gptr)(src + ((size_t)c * 3 + p) * g.Cout + h * 64), (t_lptr)(Zbuf + buf * WB_ZROW + q * 1024), 16, 0, 0);
+        }
+    };
+
+    t_f32x4 acc[9][2];
+#pragma unroll
+    for (int t = 0; t < 9; ++t)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[t][j] = t_f32x4{0.f, 0.f, 0.f, 0.f};
+
+    for (int oct = o0; oct < o1; ++oct) {
+        // the three X rows and the dZ row of output row 0 (the previous octet's last step ended with a barrier: every slot is free)
+        dma_x(oct, 0, 0); dma_x(oct, 1, 1); dma_x(oct, 2, 2); dma_z(oct, 0, 0);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        for (int oy = 0; oy < g.Hout; ++oy) {
+            if (oy + 1 < g.Hout) { dma_x(oct, oy + 3, (oy + 3) & 3); dma_z(oct, oy + 1, (oy + 1) & 1); }     // slots last read in step oy - 1
+            const unsigned char* Zr = Zbuf + (oy & 1) * WB_ZROW + (wn * 32 + r16) * 16;
+#pragma unroll
+            for (int quad = 0; quad < 2; ++quad) {
+                const int px = quad * 4 + g4;
+                bf16x8 z[3][2];
+#pragma unroll
+                for (int p = 0; p < 3; ++p)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) z[p][j] = *reinterpret_cast<const bf16x8*>(Zr + ((p * WH_ZW + px) * WB_CO + j * 16) * 16);
+#pragma unroll
+                for (int t = 0; t < 9; ++t) {
+                    const int dy = t / 3, dx = t - 3 * dy;
+                    const unsigned char* Xr = Xring + ((oy + dy) & 3) * WB_XROW + (wm * 16 + r16) * 16;
+                    bf16x8 x[3];
+#pragma unroll
+                    for (int p = 0; p < 3; ++p) x[p] = *reinterpret_cast<const bf16x8*>(Xr + ((p * WH_XW + px + dx) * WB_CI) * 16);
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) {
+#pragma unroll
+                        for (int q = 0; q < 6; ++q) {      // small terms first: x3 z1, x1 z3, x2 z2, x2 z1, x1 z2, x1 z1
+                            constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
+                            acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x[PA[q]], z[PB[q]][j], acc[t][j], 0, 0, 0);
+                        }
+                    }
+                }
+            }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the next step's rows have landed (this wave's pieces) ...
+            __syncthreads();                                       // ... everybody's, and everybody is done reading this step's
+        }
+    }
+    // C/D layout of the 16 x 16 MFMA: col = lane & 15 (co), row = (lane >> 4) * 4 + reg (ci)
+    float* __restrict__ outp = msplit > 1 ? partial + (size_t)blockIdx.y * slab : dW;
+#pragma unroll
+    for (int t = 0; t < 9; ++t)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int ci = ci0 + wm * 16 + g4 * 4 + r, co = co0 + wn * 32 + j * 16 + r16;
+                outp[((size_t)t * g.Cin + ci) * g.Cout + co] = acc[t][j][r];
+            }
+}
+
 // ---------------------------------------------------------------- Adam (tf.keras formulation) with clipvalue
 __global__ __launch_bounds__(256) void k_t_adam(float* __restrict__ P, const float* __restrict__ G, float* __restrict__ M1, float* __restrict__ V2,
                                                 long long count, float lr_t, float clip) {
@@ -922,6 +1130,11 @@ struct oz_trainer {
     long long gpartial_floats = 40LL << 20;      // 160 MB each: 16 row-split slabs of a 3x3 x 512 x 512 weight gradient
     bool wconv_attr = false, wh_attr = false;
     uint4 *xt_oct[4] = {}, *zt_oct[4] = {};     // f16x2 weight gradient: octet images of a[l - 1] / dz[l] (k_t_x_octets / k_t_z_octets)
+    // bf16x3 mode (oz_trainer_set_precision 2): conv2..4 forward, data gradient and weight gradient on the bf16 matrix cores
+    int b3 = 0;
+    bool wb3_attr = false;
+    uint4 *Wb3[4] = {}, *Wb3d[4] = {}, *a_b3[3] = {}, *dz_b3[4] = {};
+    uint4 *xt_b3[4] = {}, *zt_b3[4] = {};     // octet images in three planes (k_t_x_octets_b3 / k_t_z_octets_b3)
     // HBM-resident data set of a fit (oz_trainer_set_dataset / oz_trainer_fit_epoch)
     uint64_t *ds_own = nullptr, *ds_opp = nullptr;
     float *ds_pi = nullptr, *ds_z = nullptr;
@@ -1068,9 +1281,9 @@ static int t_check_range(oz_trainer* t) {
 }
 
 OZ_API int oz_trainer_set_precision(oz_trainer* t, int mode) {
-    OZ_REQUIRE(t && (mode == 0 || mode == 1), "oz_trainer_set_precision: mode 0 (f32) or 1 (f16x2)");
+    OZ_REQUIRE(t && (mode == 0 || mode == 1 || mode == 2), "oz_trainer_set_precision: mode 0 (f32), 1 (f16x2) or 2 (bf16x3)");
     T_LOCK(t);
-    OZ_REQUIRE(t->C % 256 == 0 || mode == 0, "oz_trainer_set_precision: f16x2 needs channels %% 256 == 0 (got %d)", t->C);
+    OZ_REQUIRE(t->C % 256 == 0 || mode == 0, "oz_trainer_set_precision: %s needs channels %% 256 == 0 (got %d)", mode == 1 ? "f16x2" : "bf16x3", t->C);
     OZ_HIP(hipSetDevice(t->device));
     OZ_HIP(hipStreamSynchronize(t->s));
     if (mode == 1 && !t->wmax) {
@@ -1088,7 +1301,21 @@ OZ_API int oz_trainer_set_precision(oz_trainer* t, int mode) {
         T_ALLOC(t->wmax, 4); T_ALLOC(t->dzmax, 8); T_ALLOC(t->h2flag, 1);
         OZ_HIP(hipStreamSynchronize(t->s));
     }
-    t->h2 = mode;
+    if (mode == 2 && !t->Wb3[1]) {
+        const int C = t->C;
+        const size_t wq = (size_t)C * 9 * C * 3 / 8;         // uint4 units of a 3x3 kernel in the b3 layout (6 B per value)
+        const size_t noct = (size_t)(t->Bmax + 7) / 8;
+        for (int l = 1; l < 4; ++l) {
+            T_ALLOC(t->Wb3[l], wq); T_ALLOC(t->Wb3d[l], wq);
+            T_ALLOC(t->a_b3[l - 1], (size_t)t->Bmax * t->P_[l - 1] * C * 3 / 8);
+            T_ALLOC(t->dz_b3[l], (size_t)t->Bmax * t->Hz[l] * t->Hz[l] * C * 3 / 8);      // zeroed: the border stays zero
+            T_ALLOC(t->xt_b3[l], noct * (t->Hout[l] + 2) * WH_XW * 3 * C);
+            T_ALLOC(t->zt_b3[l], noct * t->Hout[l] * WH_ZW * 3 * C);
+        }
+        OZ_HIP(hipStreamSynchronize(t->s));
+    }
+    t->h2 = mode == 1;
+    t->b3 = mode == 2;
     t->dirty = true;
     return OZ_OK;
 }
@@ -1172,7 +1399,14 @@ static int t_refresh(oz_trainer* t) {
         }                                                                                          // for all five forward operands, 64 us of an idle main stream per step)
         OZ_HIP(hipGetLastError());
     }
-    for (int l = t->h2 ? 4 : 1; l < 6; ++l) {      // fp32 forward operands (the dense layers; the 3x3 layers too in f32 mode)
+    if (t->b3) {         // bf16x3: the b3 forward operands, straight from the masters (no scaling)
+        for (int l = 1; l < 4; ++l) {
+            hipLaunchKernelGGL(k_t_w_to_b3<0>, dim3(h2_blocks), dim3(256), 0, r, t->param(6 * l), C, C, t->Wb3[l]);
+            if (t->overlap) { OZ_HIP(hipEventRecord(t->ev_wl[l], r)); t->wait_wl[l] = true; }
+        }
+        OZ_HIP(hipGetLastError());
+    }
+    for (int l = (t->h2 || t->b3) ? 4 : 1; l < 6; ++l) {      // fp32 forward operands (the dense layers; the 3x3 layers too in f32 mode)
         hipLaunchKernelGGL(k_t_transpose, dim3((Ns[l] + 31) / 32, (Ks[l] + 31) / 32), dim3(256), 0, r, t->param(6 * l), Ks[l], Ns[l], t->Wt[l]);
         OZ_HIP(hipGetLastError());
     }
@@ -1180,6 +1414,8 @@ static int t_refresh(oz_trainer* t) {
     for (int l = 1; l < 4; ++l) {
         if (t->h2)
             hipLaunchKernelGGL(k_t_w_to_h2<1>, dim3(h2_blocks), dim3(256), 0, r, t->param(6 * l), C, C, t->wmax + (l - 1), t->Whd[l], (float*)nullptr, t->h2flag);
+        else if (t->b3)
+            hipLaunchKernelGGL(k_t_w_to_b3<1>, dim3(h2_blocks), dim3(256), 0, r, t->param(6 * l), C, C, t->Wb3d[l]);
         else {
             const long long cnt = 9LL * C * C;
             hipLaunchKernelGGL(k_t_dgrad_operand, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, r, t->param(6 * l), C, C, t->Wd[l]);
@@ -1242,9 +1478,15 @@ static int t_forward_backward_async(oz_trainer* t, int B) {
       OZ_HIP(hipGetLastError()); }
     if (int rc = t_bn_forward(t, 0, B)) return rc;
     const int Hin[6] = {n, n, n, n - 2, 1, 1}, pad[6] = {1, 1, 0, 0, 0, 0}, Cin[6] = {t->cin, C, C, C, F, 1024}, taps[6] = {9, 9, 9, 9, 1, 1};
-    if (t->wait_wt && !t->h2) { OZ_HIP(hipStreamWaitEvent(s, t->ev_wt, 0)); t->wait_wt = false; }
+    if (t->wait_wt && !t->h2 && !t->b3) { OZ_HIP(hipStreamWaitEvent(s, t->ev_wt, 0)); t->wait_wt = false; }
     for (int l = 1; l < 6; ++l) {
-        if (t->wait_wt && l == 4) { OZ_HIP(hipStreamWaitEvent(s, t->ev_wt, 0)); t->wait_wt = false; }      // f16x2: the fp32 operands of the dense layers
+        if (t->wait_wt && l == 4) { OZ_HIP(hipStreamWaitEvent(s, t->ev_wt, 0)); t->wait_wt = false; }      // f16x2 / bf16x3: the fp32 operands of the dense layers
+        if (t->b3 && l < 4) {      // bf16x3: the previous layer's activation in the b3 layout, then the GEMM on the bf16 matrix cores (z is pre-BN: no ReLU)
+            if (int rc = oz_f32_to_b3_launch(t->a[l - 1], t->d_count, t->Bmax, t->P_[l - 1], C, t->a_b3[l - 1], s)) return rc;
+            if (t->wait_wl[l]) { OZ_HIP(hipStreamWaitEvent(s, t->ev_wl[l], 0)); t->wait_wl[l] = false; }
+            if (int rc = oz_gemm_b3_launch(t->a_b3[l - 1], t->Wb3[l], t->ones, t->param(6 * l + 1), t->z[l], t->d_count, t->Bmax, Hin[l], t->Hout[l], pad[l],
+                                           Cin[l], 9, t->Co[l], 0, s, t->gpartial, t->gpartial_floats, t->zeros, 0)) return rc;
+        } else
         if (t->h2 && l < 4) {      // f16x2: the previous layer's activation in the h2 layout, then the GEMM on the fp16 matrix cores
             const long long thr = (long long)B * t->P_[l - 1] * (C / 8);
             hipLaunchKernelGGL(k_t_act_to_h2, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, s, t->a[l - 1], t->d_count, t->P_[l - 1], C, t->a_h2[l - 1], t->h2flag);
@@ -1340,7 +1582,23 @@ static int t_forward_backward_async(oz_trainer* t, int B) {
             }
             // (measured on one MI355X, 8x8 / 512 filters: the board-resident kernel wins from batch 256 on -- 6.01 vs 6.36 ms per step, 17.0 vs
             //  19.9 at 1024 -- and loses 3-4 % at 32 .. 128, where the tap-per-block kernel's 144 x 4 short blocks finish sooner)
-            if (taps[l] == 9 && t->h2 && have_dzmax && l >= 1 && B >= WH_MIN_BATCH && Cin[l] % WH_CI == 0 && Cc % WH_CO == 0) {
+            if (taps[l] == 9 && t->b3) {
+                // bf16x3: octet images of a[l - 1] and dz[l] in three planes, then the MFMA kernel on the bf16 matrix cores (six products per fp32 product)
+                const int noct = (B + 7) / 8, XR = t->Hout[l] + 2;
+                const int tiles = (Cin[l] / WB_CI) * (Cc / WB_CO);
+                msplit = 1;
+                while (msplit < 32 && tiles * msplit < 256 && msplit * 2 <= noct && wcount * msplit * 2 <= t->gpartial_floats) msplit *= 2;
+                const long long xthr = (long long)noct * XR * WH_XW * (Cin[l] / 4), zthr = (long long)noct * t->Hout[l] * WH_ZW * (Cc / 4);
+                hipLaunchKernelGGL(k_t_x_octets_b3, dim3((unsigned)((xthr + 255) / 256)), dim3(256), 0, sw, t->a[l - 1], t->d_count, Hin[l], pad[l], Cin[l], t->xt_b3[l]);
+                hipLaunchKernelGGL(k_t_z_octets_b3, dim3((unsigned)((zthr + 255) / 256)), dim3(256), 0, sw, t->dz[l], t->d_count, t->Hout[l], t->Hz[l], t->zoff[l], Cc,
+                                   t->zt_b3[l]);
+                if (!t->wb3_attr) {
+                    OZ_HIP(hipFuncSetAttribute((const void*)k_wgrad_b3, hipFuncAttributeMaxDynamicSharedMemorySize, WB_LDS));
+                    t->wb3_attr = true;
+                }
+                WhGeom wg; wg.XR = XR; wg.Hout = t->Hout[l]; wg.Cin = Cin[l]; wg.Cout = Cc;
+                hipLaunchKernelGGL(k_wgrad_b3, dim3(tiles, msplit), dim3(512), WB_LDS, sw, t->xt_b3[l], t->zt_b3[l], t->d_count, wg, t->grad(6 * l), msplit, wp, wcount);
+            } else if (taps[l] == 9 && t->h2 && have_dzmax && l >= 1 && B >= WH_MIN_BATCH && Cin[l] % WH_CI == 0 && Cc % WH_CO == 0) {
                 // f16x2: octet images of a[l - 1] and of the scaled dz[l], then the MFMA kernel on the fp16 matrix cores (three products per fp32 product)
                 const int noct = (B + 7) / 8, XR = t->Hout[l] + 2;
                 const int tiles = (Cin[l] / WH_CI) * (Cc / WH_CO);
@@ -1384,7 +1642,13 @@ static int t_forward_backward_async(oz_trainer* t, int B) {
             } else {               // 3x3 conv: conv of dz (zero-bordered for 'valid' layers) with the reversed, channel-swapped taps
                 const int same = pad[l];
                 if (t->wait_wd) { OZ_HIP(hipStreamWaitEvent(s, t->ev_wd, 0)); t->wait_wd = false; }
-                if (have_dzmax) {  // f16x2: dz scaled into the fp16 range by its own maximum, h2 layout, same zero-bordered geometry
+                if (t->b3) {       // bf16x3: dz in the b3 layout, same zero-bordered geometry, unscaled
+                    const long long thr = (long long)B * P * (Cc / 8);
+                    hipLaunchKernelGGL(k_t_dz_to_b3, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, s, t->dz[l], t->d_count, t->Hout[l], t->Hz[l], t->zoff[l], Cc,
+                                       t->dz_b3[l]);
+                    if (int rc = oz_gemm_b3_launch(t->dz_b3[l], t->Wb3d[l], t->ones, t->zeros, t->dA[cur ^ 1], t->d_count, t->Bmax, t->Hz[l], Hin[l], same ? 1 : 0, Cc, 9,
+                                                   Cin[l], 0, s, t->gpartial, t->gpartial_floats, t->zeros, 1)) return rc;
+                } else if (have_dzmax) {  // f16x2: dz scaled into the fp16 range by its own maximum, h2 layout, same zero-bordered geometry
                     long long thr = (long long)B * P * (Cc / 8);
                     if (thr < Cin[l]) thr = Cin[l];
                     hipLaunchKernelGGL(k_t_dz_to_h2, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, s, t->dz[l], t->d_count, t->Hout[l], t->Hz[l], t->zoff[l], Cc,

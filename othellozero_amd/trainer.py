@@ -13,6 +13,7 @@ from . import _lib
 from .weights import onn_shapes
 
 TRAINABLE = [i for i in range(40) if i >= 36 or i % 6 not in (4, 5)]
+PRECISION_MODES = {"f32": 0, "f16x2": 1, "bf16x3": 2}      # oz_trainer_set_precision
 
 
 class History:
@@ -26,9 +27,11 @@ class History:
 class Trainer:
     def __init__(self, board_size=8, channels=512, in_channels=2, max_batch=32, lr=1e-3, clipvalue=0.5, dropout=0.3,
                  bn_momentum=0.99, seed=0, external_grads_ptr=None, precision="f32"):
-        """precision: arithmetic of the 3x3 layers' forward / data-gradient GEMMs -- "f32" (fp32 matrix cores) or "f16x2"
-        (fp32 values as two fp16 planes on the fp16 matrix cores, the inference kernels' arithmetic; channels % 256 == 0)"""
-        assert precision in ("f32", "f16x2"), precision
+        """precision: arithmetic of the 3x3 layers -- "f32" (fp32 matrix cores), "f16x2" (forward / data-gradient GEMMs: fp32 values
+        as two fp16 planes on the fp16 matrix cores, per-step power-of-two scaling and a range guard; channels % 256 == 0) or "bf16x3"
+        (forward, data gradient and weight gradient: every fp32 value exactly as three bf16 planes on the bf16 matrix cores, no scaling,
+        no guard; channels % 256 == 0)"""
+        assert precision in PRECISION_MODES, precision
         lib = _lib.require_gpu()
         self.n, self.channels, self.in_channels, self.max_batch = board_size, channels, in_channels, int(max_batch)
         self._h = C.c_void_p()
@@ -37,8 +40,8 @@ class Trainer:
                                          C.c_void_p(external_grads_ptr) if external_grads_ptr else None))
         self.shapes = onn_shapes(board_size, channels, in_channels)
         self.precision = precision
-        if precision == "f16x2":
-            _lib.check(lib.oz_trainer_set_precision(self._h, 1))
+        if precision != "f32":
+            _lib.check(lib.oz_trainer_set_precision(self._h, PRECISION_MODES[precision]))
 
     def __del__(self):
         try:

@@ -24,7 +24,7 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--precision", default="f32", choices=("f32", "f16x2"), help="arithmetic of the 3x3 layers' forward / data-gradient GEMMs")
+    ap.add_argument("--precision", default="f32", choices=("f32", "f16x2", "bf16x3"), help="arithmetic of the 3x3 layers")
     ap.add_argument("--fit-examples", type=int, default=0,
                     help="also time trainer.fit over this many examples (2 epochs) both ways: step-wise host loop vs HBM-resident data set")
     args = ap.parse_args()
@@ -80,7 +80,10 @@ def main():
                                    "frac": flop * args.steps / dt / 1e12 / 157.3, "traffic": None,
                                    "note": ("fp32 matrix roof; precision f16x2 runs the 3x3 layers' forward and data gradient as 3 fp16 MFMA products per "
                                             "fp32 product (roof 2500 / 3 = 833 TFLOP/s for that share of the FLOP), the weight gradients and dense layers "
-                                            "on the fp32 matrix cores -- frac may exceed 1") if args.precision == "f16x2" else "fp32 matrix roof"},
+                                            "on the fp32 matrix cores -- frac may exceed 1") if args.precision == "f16x2" else
+                                           ("fp32 matrix roof; precision bf16x3 runs the 3x3 layers' forward, data gradient AND weight gradient as 6 bf16 "
+                                            "MFMA products per fp32 product (roof 2500 / 6 = 417 TFLOP/s for that share of the FLOP), conv1 and the dense "
+                                            "layers on the fp32 matrix cores -- frac may exceed 1") if args.precision == "bf16x3" else "fp32 matrix roof"},
                       "adam_bytes_per_step": params * 4 * 7, "last_loss": loss[0], "dtype": args.precision, "data": "synthetic"}))
 
 
