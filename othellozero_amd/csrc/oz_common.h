@@ -156,8 +156,24 @@ void oz_set_error(const char* fmt, ...);
         if (!(cond)) { oz_set_error(__VA_ARGS__); return OZ_ERR_ARG; }                    \
     } while (0)
 
-// ---------------------------------------------------------------- bf16x3: an fp32 value as three bf16 planes (oz_net_b3.h, header comment)
+// ---------------------------------------------------------------- device vector types
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));           // one 16-byte store
+typedef const __attribute__((address_space(1))) void* oz_gptr;        // global source of an LDS-DMA (global_load_lds)
+typedef __attribute__((address_space(3))) void* oz_lptr;              // its LDS destination
+
+// ---------------------------------------------------------------- split-plane operand formats
+// An fp32 value as the sum of two fp16 planes (precision f16x2, oz_net_h2.h header) or of three bf16 planes (precision bf16x3, oz_net_b3.h header).
+__device__ __forceinline__ void h2_split(float x, _Float16& h1, _Float16& h2) {
+    h1 = (_Float16)x;
+    h2 = (_Float16)(x - (float)h1);
+}
+// x = b1 + b2 + b3 exactly for 2^-100 <= |x| <= FLT_MAX (round to nearest: |x - b1| <= 2^-8 |x|, |x - b1 - b2| <= 2^-17 |x|, and the third residual
+// has at most 8 significant bits); below 2^-100 the last residual can fall under bf16's subnormal step: absolute error < 2^-120.  Inf and NaN give
+// NaN planes.
 __device__ __forceinline__ void b3_split(float x, __bf16& b1, __bf16& b2, __bf16& b3) {
     b1 = (__bf16)x;
     // the top 0.4 % of fp32's range (|x| > 0x7F7F8000 = bf16's largest value + half an ulp) would ROUND to infinity: take bf16's largest value instead --
@@ -166,4 +182,49 @@ __device__ __forceinline__ void b3_split(float x, __bf16& b1, __bf16& b2, __bf16
     const float r1 = x - (float)b1;               // exact
     b2 = (__bf16)r1;
     b3 = (__bf16)(r1 - (float)b2);                // exact difference, at most 8 significant bits: the cast is exact
+}
+// Eight values split into PLANES planes (2: h2_split, 3: b3_split), plane p stored as one 16-byte chunk at dst[p * pstride];
+// NT = non-temporal stores (an output that would otherwise evict data the kernel re-reads from L2).
+template <bool NT> __device__ __forceinline__ void oz_store16(uint4* dst, u32x4 v) {
+    if constexpr (NT) __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(dst));
+    else *reinterpret_cast<u32x4*>(dst) = v;
+}
+template <int PLANES, bool NT = false>
+__device__ __forceinline__ void oz_split8_store(uint4* dst, size_t pstride, const float (&v)[8]) {
+    static_assert(PLANES == 2 || PLANES == 3, "f16x2 or bf16x3");
+    if constexpr (PLANES == 2) {
+        f16x8 h1, h2;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            _Float16 a, b;
+            h2_split(v[j], a, b);
+            h1[j] = a; h2[j] = b;
+        }
+        oz_store16<NT>(dst, __builtin_bit_cast(u32x4, h1));
+        oz_store16<NT>(dst + pstride, __builtin_bit_cast(u32x4, h2));
+    } else {
+        bf16x8 p0, p1, p2;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            __bf16 a, b, c;
+            b3_split(v[j], a, b, c);
+            p0[j] = a; p1[j] = b; p2[j] = c;
+        }
+        oz_store16<NT>(dst, __builtin_bit_cast(u32x4, p0));
+        oz_store16<NT>(dst + pstride, __builtin_bit_cast(u32x4, p1));
+        oz_store16<NT>(dst + 2 * pstride, __builtin_bit_cast(u32x4, p2));
+    }
+}
+// The h2 layout: a row of K values (a pixel's channels or a weight row's k) is K / 8 groups of 32 bytes, group g = [h1 x 8][h2 x 8] at chunks
+// 2 g, 2 g + 1 of the row; rows follow each other.  Stores the group of k .. k + 7 (k % 8 == 0) of row `row`.
+template <bool NT = false>
+__device__ __forceinline__ void h2_store8(uint4* out, size_t row, int K, int k, const float (&v)[8]) {
+    oz_split8_store<2, NT>(out + (row * (size_t)(K >> 3) + (k >> 3)) * 2, 1, v);
+}
+// The b3 layout: a row of K values is K / 32 k-tiles of 192 bytes = 12 chunks [plane 0: 32 bf16][plane 1: 32 bf16][plane 2: 32 bf16]; the chunk
+// of plane p and 8-group kg = (k / 8) % 4 of k-tile k / 32 sits at 12 (k / 32) + 4 p + kg of the row; rows follow each other.  Stores the group of
+// k .. k + 7 (k % 8 == 0) of row `row`.
+template <bool NT = false>
+__device__ __forceinline__ void b3_store8(uint4* out, size_t row, int K, int k, const float (&v)[8]) {
+    oz_split8_store<3, NT>(out + row * (size_t)(K / 32 * 12) + (k >> 5) * 12 + ((k >> 3) & 3), 4, v);
 }

@@ -166,3 +166,5 @@ int oz_gemm_b3_launch(const void* in_b3, const void* Wb, const float* scale, con
                       const void* zero_line, int tag);
 // fp32 rows [*d_count * P][C] -> the b3 layout (k_f32_to_b3)
 int oz_f32_to_b3_launch(const float* x, const int* d_count, int max_count, int P, int C, void* out, hipStream_t s);
+// Keras weights [K][N] with k = tap * Cin + ci -> b3 rows [N][K] in the GEMM's tap-inner k order (k_w_to_b3)
+int oz_w_to_b3_launch(const float* W, int K, int N, int taps, void* out, hipStream_t s);

@@ -26,9 +26,6 @@
 
 #include "oz_internal.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 // ---------------------------------------------------------------- conv1 (+ plane unpack)
 // out[m][co] = relu(scale[co] * sum_{tap,ch} x[b][y+ky-1][x+kx-1][ch] * W[tap][ch][co] + shift[co])
 // one thread per (row m, 4 consecutive output channels)
@@ -71,8 +68,6 @@ __global__ __launch_bounds__(256) void k_conv1(const uint64_t* __restrict__ own,
 #define GM_BK 32
 #define GM_LDS_STRIDE 32   // floats per staged row: 128 B, no padding -- rows arrive by LDS-DMA (8 rows = 1 KB per wave instruction) and the 16-byte
                            // chunks of a row are XOR-swizzled with row & 7 on the SOURCE side and on the read side (conflict-free, see k_gemm_f32)
-typedef const __attribute__((address_space(1))) void* gm_gptr;
-typedef __attribute__((address_space(3))) void* gm_lptr;
 __device__ float g_gm_zero_line[32];          // 128 B of zeros: the source of taps outside the image / rows beyond M
 
 
@@ -192,11 +187,11 @@ __global__ __launch_bounds__(CF::NT, CF::OCC) void k_gemm_f32(const float* __res
 #pragma unroll
         for (int i = 0; i < IA; ++i) {
             const float* ga = ((amask[i] >> tap) & 1) ? in + abase[i] + toff : zsrc;
-            __builtin_amdgcn_global_load_lds((gm_gptr)ga, (gm_lptr)(la + (wave_u * 8 + RPP * i) * GM_LDS_STRIDE), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((oz_gptr)ga, (oz_lptr)(la + (wave_u * 8 + RPP * i) * GM_LDS_STRIDE), 16, 0, 0);
         }
 #pragma unroll
         for (int i = 0; i < IB; ++i)
-            __builtin_amdgcn_global_load_lds((gm_gptr)(brow[i] + k0), (gm_lptr)(lb + (wave_u * 8 + RPP * i) * GM_LDS_STRIDE), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((oz_gptr)(brow[i] + k0), (oz_lptr)(lb + (wave_u * 8 + RPP * i) * GM_LDS_STRIDE), 16, 0, 0);
     };
 
     f32x16 acc[TI][TJ];
@@ -617,6 +612,14 @@ int oz_f32_to_b3_launch(const float* x, const int* d_count, int max_count, int P
     OZ_HIP(hipGetLastError());
     return OZ_OK;
 }
+// k_w_to_b3 for callers outside the network object: Keras weights [K][N] (k = tap * Cin + ci) -> b3 rows [N][K] in the GEMM's k order
+int oz_w_to_b3_launch(const float* W, int K, int N, int taps, void* out, hipStream_t s) {
+    OZ_REQUIRE(K % (32 * taps) == 0, "w_to_b3: K / taps %% 32 must be 0 (K=%d, taps=%d)", K, taps);
+    const long long threads = (long long)N * (K / 8);
+    hipLaunchKernelGGL(k_w_to_b3, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, W, K, N, taps, (uint4*)out);
+    OZ_HIP(hipGetLastError());
+    return OZ_OK;
+}
 
 // ---------------------------------------------------------------- heads
 // one 256-thread block per LP positions whose f2 rows (2 KB each) are staged in LDS once: wave w accumulates k in [128w, 128w+128) of
@@ -892,7 +895,8 @@ struct OnnNet : oz_net {
     int cal_total = 0;
 
     // precision 2 ("f32 via 3 x bf16 split", oz_net_b3.h): conv3, conv4 and fc1 on k_gemm_b3 (weights and activations in the b3 layout, 6 B per
-    // element); conv1 + conv2 from the exact-fp32 pattern tables, fc2 and the heads on the exact-fp32 kernels.  Networks below B3_MIN_BATCH
+    // element); fc2 on k_gemm_b3 too (b3 operands in, fp32 rows out); conv1 + conv2 from the exact-fp32 pattern tables, the heads on the exact-fp32
+    // kernels.  Networks below B3_MIN_BATCH
     // positions of capacity run the exact-fp32 forward as it is (their layers are weight streams / split-K launches: latency, not matrix rate) --
     // a per-network constant, so a position's result does not depend on the size of the call it sits in.
     uint4* d_wb[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // conv2 (the all-GEMM form only), conv3, conv4, fc1, fc2
@@ -1946,8 +1950,7 @@ OZ_API int oz_net_commit(oz_net* net) {
             }
             if (o->use_b3()) {                         // conv2 .. fc2 once more in the b3 layout (three bf16 planes, the GEMM's tap-inner k order)
                 if (!o->d_wb[i]) { if (int rc = o->alloc(&o->d_wb[i], (size_t)N * (K / 32) * 12)) return rc; }
-                const long long threads = (long long)N * (K / 8);
-                hipLaunchKernelGGL(k_w_to_b3, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, 0, o->d_raw, K, N, i < 3 ? 9 : 1, o->d_wb[i]);
+                if (int rc = oz_w_to_b3_launch(o->d_raw, K, N, i < 3 ? 9 : 1, o->d_wb[i], 0)) return rc;
             }
             OZ_HIP(hipGetLastError());
             OZ_HIP(hipDeviceSynchronize());                       // d_raw is reused by the next layer

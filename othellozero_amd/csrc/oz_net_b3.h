@@ -2,21 +2,18 @@
 //
 // Why: the fp32 matrix cores peak at 157 TFLOP/s, 1/16 of the 16-bit MFMA rate, and k_gemm_f32 sits at 0.85 of that roof.  The
 // f16x2 mode (oz_net_h2.h) reaches the 16-bit pipes but carries 22 of fp32's 24 significand bits in fp16's narrow exponent range,
-// which is what its commit-time placement, guards and self-check are for.  This mode carries an fp32 value EXACTLY:
+// which is what its commit-time placement, guards and self-check are for.  This mode carries an fp32 value as three bf16 planes,
 //     x = b1 + b2 + b3,   b1 = bf16(x), b2 = bf16(x - b1), b3 = bf16(x - b1 - b2)
-// bf16 has fp32's exponent range and 8 significand bits, so three planes hold all 24 bits of every normal fp32 value (round to
-// nearest: |x - b1| <= 2^-8 |x|, |x - b1 - b2| <= 2^-17 |x|, the third residual is exact; the only loss is a residual below the smallest
-// normal fp32 / bf16's subnormal step, i.e. for |x| < 2^-100: absolute error < 2^-120) -- no scaling, no calibration, no guards, no refusal path.  A product keeps six of
-// the nine cross terms,
+// bf16 has fp32's exponent range and 8 significand bits: the split is exact for 2^-100 <= |x| <= FLT_MAX (oz_common.h, b3_split, states
+// the bounds) -- no scaling, no calibration, no guards, no refusal path.  A product keeps six of the nine cross terms,
 //     a b ~= a3 b1 + a1 b3 + a2 b2 + a2 b1 + a1 b2 + a1 b1          (dropped: a2 b3, a3 b2 <= 2^-25 |a b| each, a3 b3 <= 2^-34 |a b|)
 // each an exact bf16 x bf16 product accumulated in fp32 on v_mfma_f32_16x16x32_bf16, small terms first.  Per product the dropped
 // terms stay within fp32's own rounding of that product (half an ulp, 2^-24, in the worst case; a quarter of it typically); what remains is the fp32
 // accumulation order, as in k_gemm_f32.
 // Cost: 6 MFMAs at 16x the fp32 rate = 2.67x the fp32 matrix roof (cap 2500 / 6 = 417 TFLOP/s fp32-equivalent).
 //
-// Storage ("b3 layout"): a row (pixel or output channel) is cut into k-tiles of 32 channels; a k-tile is 192 bytes =
-// [plane 0: 32 bf16][plane 1: 32 bf16][plane 2: 32 bf16] = 12 chunks of 16 B, chunk (plane p, group kg of 8 channels) at index 4 p + kg.
-// A row of K values is K / 32 * 192 = 6 K bytes.  Weight rows [N][K'] use the GEMM's tap-inner k order of oz_net_h2.h:
+// Storage: the "b3 layout" of oz_common.h (b3_store8): a row (pixel or output channel) is cut into k-tiles of 32 channels of 192 bytes,
+// 12 chunks of 16 B, three planes of four chunks.  Weight rows [N][K'] use the GEMM's tap-inner k order of oz_net_h2.h:
 // k' = (slice * taps + tap) * 32 + c32 for input channel 32 * slice + c32.
 //
 // Kernel k_gemm_b3: implicit GEMM, block tile 128 x 256 x 32, 8 waves (2 x 4, wave tile 64 x 64 = 4 x 4 MFMA tiles of 16 x 16),
@@ -56,7 +53,7 @@ struct B3Geom {
     long long slab;                               // floats between two partial slabs
 };
 
-// b3_split (the three-plane split of one fp32 value) and bf16x8 live in oz_common.h: the trainer converts its operands with the same function
+// b3_split, b3_store8 and the layout's definition live in oz_common.h: the trainer converts its operands with the same functions
 
 // fp32 rows [rows][C] -> the b3 layout; rows = *d_count * P.  One thread per (row, 8 channels): two 16-byte loads, three 16-byte stores.
 __global__ __launch_bounds__(256) void k_f32_to_b3(const float* __restrict__ x, const int* __restrict__ d_count, int P, int C, uint4* __restrict__ out) {
@@ -66,17 +63,8 @@ __global__ __launch_bounds__(256) void k_f32_to_b3(const float* __restrict__ x, 
     if (row >= (long long)(*d_count) * P) return;
     const int c8 = (int)(idx % cg) * 8;
     const f32x4 lo = *reinterpret_cast<const f32x4*>(x + (size_t)row * C + c8), hi = *reinterpret_cast<const f32x4*>(x + (size_t)row * C + c8 + 4);
-    bf16x8 p0, p1, p2;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        __bf16 a, b, c;
-        b3_split(j < 4 ? lo[j] : hi[j - 4], a, b, c);
-        p0[j] = a; p1[j] = b; p2[j] = c;
-    }
-    uint4* dst = out + (size_t)row * (size_t)(C / 32 * 12) + (c8 >> 5) * 12 + ((c8 >> 3) & 3);
-    dst[0] = *reinterpret_cast<uint4*>(&p0);
-    dst[4] = *reinterpret_cast<uint4*>(&p1);
-    dst[8] = *reinterpret_cast<uint4*>(&p2);
+    const float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    b3_store8(out, row, C, c8, v);
 }
 
 // finishes a split-K layer whose consumer reads the b3 layout: out[m][n] = relu((sum_s slab[s][m][n]) * scale[n] + shift[n]), the slices added in a
@@ -95,18 +83,10 @@ __global__ __launch_bounds__(256) void k_splitk_reduce_b3(const float* __restric
         lo += *reinterpret_cast<const f32x4*>(p + (size_t)s * slab);
         hi += *reinterpret_cast<const f32x4*>(p + (size_t)s * slab + 4);
     }
-    bf16x8 p0, p1, p2;
+    float v[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float v = fmaxf(fmaf(j < 4 ? lo[j] : hi[j - 4], scale[c8 + j], shift[c8 + j]), 0.f);
-        __bf16 a, b, c;
-        b3_split(v, a, b, c);
-        p0[j] = a; p1[j] = b; p2[j] = c;
-    }
-    uint4* dst = out + (size_t)m * (size_t)(N / 32 * 12) + (c8 >> 5) * 12 + ((c8 >> 3) & 3);
-    dst[0] = *reinterpret_cast<uint4*>(&p0);
-    dst[4] = *reinterpret_cast<uint4*>(&p1);
-    dst[8] = *reinterpret_cast<uint4*>(&p2);
+    for (int j = 0; j < 8; ++j) v[j] = fmaxf(fmaf(j < 4 ? lo[j] : hi[j - 4], scale[c8 + j], shift[c8 + j]), 0.f);
+    b3_store8(out, m, N, c8, v);
 }
 
 // weights as stored by Keras, [K][N] with k = tap * Cin + ci  ->  b3 rows [N][K / 32][3 planes][32] in the GEMM's k order
@@ -117,19 +97,14 @@ __global__ __launch_bounds__(256) void k_w_to_b3(const float* __restrict__ src, 
     const int grp = (int)(idx / N);
     if (grp >= (K >> 3)) return;
     const int Cin = K / taps;
-    bf16x8 p0, p1, p2;
+    float v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const int kp = grp * 8 + j, tile = kp >> 5, c32 = kp & 31, slice = tile / taps, tap = tile - slice * taps;
         const int k = tap * Cin + slice * 32 + c32;
-        __bf16 a, b, cc;
-        b3_split(src[(size_t)k * N + c], a, b, cc);
-        p0[j] = a; p1[j] = b; p2[j] = cc;
+        v[j] = src[(size_t)k * N + c];
     }
-    uint4* dst = out + (size_t)c * (size_t)(K / 32 * 12) + (grp >> 2) * 12 + (grp & 3);
-    dst[0] = *reinterpret_cast<uint4*>(&p0);
-    dst[4] = *reinterpret_cast<uint4*>(&p1);
-    dst[8] = *reinterpret_cast<uint4*>(&p2);
+    b3_store8(out, c, K, grp * 8, v);
 }
 
 // out[M][N] = act((A[M][K] . W[N][K]^T) * scale + shift); A and W in the b3 layout; M = *d_count * Hout^2.
@@ -201,21 +176,21 @@ __global__ __launch_bounds__(B3_NT, 2) void k_gemm_b3(const uint4* __restrict__ 
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
             const uint4* ga = ((amask[i] >> tap) & 1) ? in + (aidx[i] + toff) : zsrc;
-            __builtin_amdgcn_global_load_lds((h2_gptr)ga, (h2_lptr)(la + wave * B3_BLK + i * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((oz_gptr)ga, (oz_lptr)(la + wave * B3_BLK + i * 1024), 16, 0, 0);
         }
     };
     auto put_be = [&](int ktc, unsigned char* lbp) {
 #pragma unroll
         for (int i = 0; i < 3; ++i)
-            __builtin_amdgcn_global_load_lds((h2_gptr)(Wb + bidx_e[i] + ktc * 12), (h2_lptr)(lbp + eb * B3_BLK + i * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((oz_gptr)(Wb + bidx_e[i] + ktc * 12), (oz_lptr)(lbp + eb * B3_BLK + i * 1024), 16, 0, 0);
     };
     auto put_bl = [&](int ktc, unsigned char* lbp) {
 #pragma unroll
         for (int i = 0; i < 3; ++i)
-            __builtin_amdgcn_global_load_lds((h2_gptr)(Wb + bidx_l[i] + ktc * 12), (h2_lptr)(lbp + lb * B3_BLK + i * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((oz_gptr)(Wb + bidx_l[i] + ktc * 12), (oz_lptr)(lbp + lb * B3_BLK + i * 1024), 16, 0, 0);
     };
 
-    f32x4v acc[RI][RJ];
+    f32x4 acc[RI][RJ];
 #pragma unroll
     for (int i = 0; i < RI; ++i)
 #pragma unroll
@@ -279,7 +254,7 @@ __global__ __launch_bounds__(B3_NT, 2) void k_gemm_b3(const uint4* __restrict__ 
                 for (int i = 0; i < RI; ++i)
 #pragma unroll
                     for (int j = 0; j < 2; ++j) {
-                        f32x4v& c = acc[i][nh * 2 + j];
+                        f32x4& c = acc[i][nh * 2 + j];
                         c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[PA[q]][i], fb[PB[q]][nh * 2 + j], c, 0, 0, 0);
                     }
             }
@@ -466,16 +441,16 @@ __global__ __launch_bounds__(B3_NT, 2) void k_gemm_b3_big(const uint4* __restric
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
             const uint4* ga = aoff[h][i] != ~0u ? in + (aoff[h][i] + toff) : zsrc;
-            __builtin_amdgcn_global_load_lds((h2_gptr)ga, (h2_lptr)(reg + wave * B3_BLK + i * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((oz_gptr)ga, (oz_lptr)(reg + wave * B3_BLK + i * 1024), 16, 0, 0);
         }
     };
     auto put_b = [&](int h, int ktc, unsigned char* reg) {
 #pragma unroll
         for (int i = 0; i < 3; ++i)
-            __builtin_amdgcn_global_load_lds((h2_gptr)(Wb + (boff[i] + (h ? bhalf : 0u) + (unsigned)ktc * 12u)), (h2_lptr)(reg + wave * B3_BLK + i * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((oz_gptr)(Wb + (boff[i] + (h ? bhalf : 0u) + (unsigned)ktc * 12u)), (oz_lptr)(reg + wave * B3_BLK + i * 1024), 16, 0, 0);
     };
 
-    f32x4v acc[2 * HA][RJ];
+    f32x4 acc[2 * HA][RJ];
 #pragma unroll
     for (int i = 0; i < 2 * HA; ++i)
 #pragma unroll
@@ -532,7 +507,7 @@ __global__ __launch_bounds__(B3_NT, 2) void k_gemm_b3_big(const uint4* __restric
                 for (int i = 0; i < HA; ++i)
 #pragma unroll
                     for (int j = 0; j < 2; ++j) {
-                        f32x4v& c = acc[mh * HA + i][nh * 2 + j];
+                        f32x4& c = acc[mh * HA + i][nh * 2 + j];
                         c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[PA[q]][i], fb[PB[q]][j], c, 0, 0, 0);
                     }
             }

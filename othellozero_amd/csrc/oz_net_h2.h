@@ -39,7 +39,7 @@
 // Measured: |d pi|, |d v| <= 1e-5 vs float64 on every tested network incl. small-activation, wide-weight-range and badly scaled BN
 // cases (tests/test_gpu_parity.py::test_f16x2_scaling_*), like the fp32 path; 5e-8 on the bench's network.
 //
-// Storage ("h2 layout"): for a row (pixel or output channel) every 8 consecutive k are one 32-byte
+// Storage: the "h2 layout" of oz_common.h (h2_store8): for a row (pixel or output channel) every 8 consecutive k are one 32-byte
 // group  [h1 x 8][h2 x 8]; a row of K values is K/8 groups = 4*K bytes (same footprint as fp32).
 // Weight rows are stored in the kernel's k-tile order: k' = (slice*taps + tap)*32 + c  for channel 32*slice + c,
 // i.e. the 9 taps of one 32-channel slice are consecutive k-tiles, so the 9 shifted re-reads of the same
@@ -92,9 +92,6 @@
 // GEMM is conv3.  The GEMM kernel still serves conv2 when the tables are switched off and builds the tables at commit.
 #pragma once
 #include <type_traits>
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
 
 #define H2_BK 32
 #define H2_F16_MAX 65504.0f
@@ -215,11 +212,11 @@ __global__ __launch_bounds__(256) void k_splitk_reduce_h2(const float* __restric
     for (int j = 0; j < 8; ++j) acc[j] = p[j];
     // added in order s = 1, 2, ... (bit-reproducible), fetched four slices (8 x 16 B per thread) at a time: see k_splitk_reduce_f32
     for (int s0 = 1; s0 < ksplit; s0 += 4) {
-        f32x4v b[4][2];
+        f32x4 b[4][2];
 #pragma unroll
         for (int q = 0; q < 4; ++q)
             if (s0 + q < ksplit) {
-                const f32x4v* src = reinterpret_cast<const f32x4v*>(p + (size_t)(s0 + q) * slab);
+                const f32x4* src = reinterpret_cast<const f32x4*>(p + (size_t)(s0 + q) * slab);
                 b[q][0] = src[0]; b[q][1] = src[1];
             }
 #pragma unroll
@@ -229,32 +226,22 @@ __global__ __launch_bounds__(256) void k_splitk_reduce_h2(const float* __restric
                 for (int j = 0; j < 4; ++j) { acc[j] += b[q][0][j]; acc[j + 4] += b[q][1][j]; }
             }
     }
-    f16x8 h1, h2;
+    float v[8];
     bool over = false;
     float vmax = 0.f;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-        float v = fmaf(acc[j], scale[c8 + j], shift[c8 + j]);
-        if (relu) v = fmaxf(v, 0.f);
-        over |= fabsf(v) > H2_F16_MAX;
-        vmax = fmaxf(vmax, fabsf(v));
-        const _Float16 a = (_Float16)v;
-        h1[j] = a;
-        h2[j] = (_Float16)(v - (float)a);
+        v[j] = fmaf(acc[j], scale[c8 + j], shift[c8 + j]);
+        if (relu) v[j] = fmaxf(v[j], 0.f);
+        over |= fabsf(v[j]) > H2_F16_MAX;
+        vmax = fmaxf(vmax, fabsf(v[j]));
     }
+    h2_store8(out, m, N, c8, v);
     if (over) atomicOr(flag, H2_FLAG_OVER);
     if (low.cnt) {                                       // 8 adjacent threads = one 64-channel slice of row m (ng % 8 == 0: whole octets pass the row test together)
         vmax = h2_octet_max(vmax);
         if ((threadIdx.x & 7) == 0 && vmax > 0.f && vmax < low.thr) h2_low_report(low, m, N >> 6);
     }
-    uint4* dst = out + ((size_t)m * ng + (c8 >> 3)) * 2;
-    dst[0] = *reinterpret_cast<uint4*>(&h1);
-    dst[1] = *reinterpret_cast<uint4*>(&h2);
-}
-
-__device__ __forceinline__ void h2_split(float x, _Float16& h1, _Float16& h2) {
-    h1 = (_Float16)x;
-    h2 = (_Float16)(x - (float)h1);
 }
 
 // XOR key of LDS row `row` (applied to the 16-byte chunk index, on the DMA source side and on the read side).
@@ -264,9 +251,6 @@ __device__ __forceinline__ void h2_split(float x, _Float16& h1, _Float16& h2) {
 // {2 ^ key(r)} for r in {4-11}  cover all eight chunk slots of each row parity: key = bit1(r) | 6*bit3(r).
 // (the natural (row>>1)&7 key is conflict-free only for the 32x32x16 map: measured 50 % conflict cycles here)
 __device__ __forceinline__ int h2_swz(int row) { return ((row >> 1) & 1) | (((row >> 3) & 1) * 6); }
-
-typedef const __attribute__((address_space(1))) void* h2_gptr;
-typedef __attribute__((address_space(3))) void* h2_lptr;
 
 // conv1 + plane unpack, output in the h2 layout.  One thread = one board row (n pixels) x 8 channels: the 18
 // weight vectors are loaded once per thread and applied to the row's pixels (input bits tested in registers).
@@ -323,24 +307,19 @@ __global__ __launch_bounds__(256) void k_conv1_h2(const uint64_t* __restrict__ o
 #pragma unroll
     for (int x = 0; x < 8; ++x) {
         if (x >= n) continue;
-        f16x8 h1, h2;
+        float v[8];
         float vmax = 0.f;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const float v = fmaxf(fmaf(acc[x][j], sc[j], sh[j]), 0.f);
-            over |= v > H2_F16_MAX;
-            vmax = fmaxf(vmax, v);
-            _Float16 a, bb;
-            h2_split(v, a, bb);
-            h1[j] = a; h2[j] = bb;
+            v[j] = fmaxf(fmaf(acc[x][j], sc[j], sh[j]), 0.f);
+            over |= v[j] > H2_F16_MAX;
+            vmax = fmaxf(vmax, v[j]);
         }
         if (low.cnt) {                                   // cg % 8 == 0: the 8 threads of a 64-channel slice sit in one lane octet, same board row
             vmax = h2_octet_max(vmax);
             if ((threadIdx.x & 7) == 0 && vmax > 0.f && vmax < low.thr) h2_low_report(low, br * n + x, C >> 6);
         }
-        uint4* dst = out + ((size_t)(br * n + x) * cg + (c8 >> 3)) * 2;
-        dst[0] = *reinterpret_cast<uint4*>(&h1);
-        dst[1] = *reinterpret_cast<uint4*>(&h2);
+        h2_store8(out, br * n + x, C, c8, v);
     }
     if (over) atomicOr(flag, H2_FLAG_OVER);
 }
@@ -368,18 +347,14 @@ __global__ __launch_bounds__(256) void k_w_to_h2(const float* __restrict__ src, 
     if (grp >= (K >> 3)) return;
     const int Cin = K / taps;
     const int ce = colexp[c];
-    f16x8 h1, h2;
+    float v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const int kp = grp * 8 + j, tile = kp >> 5, c32 = kp & 31, slice = tile / taps, tap = tile - slice * taps;
         const int k = tap * Cin + slice * 32 + c32;
-        const float x = ldexpf(src[(size_t)k * N + c], ce - inexp[k % Cmod]);
-        const _Float16 a = (_Float16)x;
-        h1[j] = a; h2[j] = (_Float16)(x - (float)a);
+        v[j] = ldexpf(src[(size_t)k * N + c], ce - inexp[k % Cmod]);
     }
-    uint4* dst = out + ((size_t)c * (K >> 3) + grp) * 2;
-    dst[0] = *reinterpret_cast<uint4*>(&h1);
-    dst[1] = *reinterpret_cast<uint4*>(&h2);
+    h2_store8(out, c, K, grp * 8, v);
 }
 // colmax[c] = max over k of |w[k][c]| * 2^-inexp[k % Cmod]  (bit pattern of a non-negative float: atomicMax on unsigned orders them)
 __global__ __launch_bounds__(256) void k_w_colmax(const float* __restrict__ src, int K, int N, const int* __restrict__ inexp, int Cmod,
@@ -498,19 +473,14 @@ __global__ __launch_bounds__(256) void k_lut_build(int C, const float* __restric
 #pragma unroll
         for (int j = 0; j < 8; ++j) acc[j] = fmaf(a1, w1[j], acc[j]);
     }
-    f16x8 h1, h2;
+    float v[8];
     bool over = false;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-        const float v = fmaxf(fmaf(acc[j], scale[c8 + j], shift[c8 + j]), 0.f);
-        over |= v > H2_F16_MAX;
-        _Float16 a, bb;
-        h2_split(v, a, bb);
-        h1[j] = a; h2[j] = bb;
+        v[j] = fmaxf(fmaf(acc[j], scale[c8 + j], shift[c8 + j]), 0.f);
+        over |= v[j] > H2_F16_MAX;
     }
-    uint4* dst = table + ((size_t)id * cg + (c8 >> 3)) * 2;
-    dst[0] = *reinterpret_cast<uint4*>(&h1);
-    dst[1] = *reinterpret_cast<uint4*>(&h2);
+    h2_store8(table, id, C, c8, v);
     if (over) atomicOr(flag, H2_FLAG_OVER);
 }
 
@@ -556,9 +526,8 @@ __global__ __launch_bounds__(256) void k_lut_build(int C, const float* __restric
 __device__ __forceinline__ size_t t2_record(int slice, int t, unsigned id) {          // float index of record (slice, tap, id)
     return (((size_t)slice * 9 + t) * OZ_LUT_ROWS + id) * OZ_C2L_SLICE;
 }
-// one output row piece: BN + ReLU of 8 channel sums, then the h2 split (two 16-byte streaming stores) or fp32 (two 16-byte stores)
-// OUT: 0 = fp32 rows, 1 = the h2 layout, 2 = the b3 layout (three bf16 planes, oz_net_b3.h)
-__device__ __forceinline__ void b3_split(float x, __bf16& b1, __bf16& b2, __bf16& b3);
+// one output row piece: BN + ReLU of 8 channel sums, then fp32 or the split planes, in streaming stores (the 0.5 GB of output would
+// otherwise evict table records from L2 / Infinity Cache).  OUT: 0 = fp32 rows, 1 = the h2 layout, 2 = the b3 layout
 template <int OUT>
 __device__ __forceinline__ bool c2l_finish(const f32x4& lo, const f32x4& hi, const float* __restrict__ scale, const float* __restrict__ shift, int c8,
                                            void* __restrict__ out, size_t pixel, int C, float& vmax, float relu_floor) {
@@ -573,35 +542,13 @@ __device__ __forceinline__ bool c2l_finish(const f32x4& lo, const f32x4& hi, con
     vmax = 0.f;
 #pragma unroll
     for (int j = 0; j < 8; ++j) vmax = fmaxf(vmax, v[j]);
-    typedef unsigned v4u __attribute__((ext_vector_type(4)));
     bool over = false;
-    constexpr bool OUT_H2 = OUT == 1;
     if constexpr (OUT == 2) {
-        typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-        bf16x8_t p0, p1, p2;
+        b3_store8<true>(reinterpret_cast<uint4*>(out), pixel, C, c8, v);
+    } else if constexpr (OUT == 1) {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            __bf16 a, b, c;
-            b3_split(v[j], a, b, c);
-            p0[j] = a; p1[j] = b; p2[j] = c;
-        }
-        v4u* dst = reinterpret_cast<v4u*>(reinterpret_cast<uint4*>(out) + pixel * (size_t)(C / 32 * 12) + (c8 >> 5) * 12 + ((c8 >> 3) & 3));
-        __builtin_nontemporal_store(*reinterpret_cast<v4u*>(&p0), dst);
-        __builtin_nontemporal_store(*reinterpret_cast<v4u*>(&p1), dst + 4);
-        __builtin_nontemporal_store(*reinterpret_cast<v4u*>(&p2), dst + 8);
-    } else if constexpr (OUT_H2) {
-        f16x8 h1, h2;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            over |= v[j] > H2_F16_MAX;
-            _Float16 a, bb;
-            h2_split(v[j], a, bb);
-            h1[j] = a; h2[j] = bb;
-        }
-        // streaming stores: the 0.5 GB of output would otherwise evict table records from L2 / Infinity Cache
-        v4u* dst = reinterpret_cast<v4u*>(reinterpret_cast<uint4*>(out) + (pixel * (size_t)(C >> 3) + (c8 >> 3)) * 2);
-        __builtin_nontemporal_store(*reinterpret_cast<v4u*>(&h1), dst);
-        __builtin_nontemporal_store(*reinterpret_cast<v4u*>(&h2), dst + 1);
+        for (int j = 0; j < 8; ++j) over |= v[j] > H2_F16_MAX;
+        h2_store8<true>(reinterpret_cast<uint4*>(out), pixel, C, c8, v);
     } else {
         float* dst = reinterpret_cast<float*>(out) + pixel * (size_t)C + c8;
         const f32x4 r0 = {v[0], v[1], v[2], v[3]}, r1 = {v[4], v[5], v[6], v[7]};
@@ -684,7 +631,6 @@ __global__ __launch_bounds__(256) void k_conv2_lut_xcd(const unsigned* __restric
             va[q] = fmaxf(fmaf(lo[q], sca[q], sha[q]), relu_floor);
             vb[q] = fmaxf(fmaf(hi[q], scb[q], shb[q]), relu_floor);
         }
-        typedef unsigned v4u __attribute__((ext_vector_type(4)));
         if constexpr (OUT_H2) {
             // group g = j >> 1 of line 0 (and of line 1): lane 2 g holds channels 8 g .. 8 g + 3, lane 2 g + 1 channels 8 g + 4 .. + 7.  The h2
             // layout wants [h1 x 8][h2 x 8] per group: the even lane sends its h2 halves and receives the partner's h1 halves, so that the even lane
@@ -709,11 +655,11 @@ __global__ __launch_bounds__(256) void k_conv2_lut_xcd(const unsigned* __restric
             unsigned got[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q) got[q] = (unsigned)__shfl_xor((int)give[q], 1, 64);
-            v4u c0, c1;       // even lane: [own h1 | partner's h1];  odd lane: [partner's h2 | own h2]
+            u32x4 c0, c1;     // even lane: [own h1 | partner's h1];  odd lane: [partner's h2 | own h2]
             c0[0] = even ? h1a.u[0] : got[0]; c0[1] = even ? h1a.u[1] : got[1]; c0[2] = even ? got[0] : h2a.u[0]; c0[3] = even ? got[1] : h2a.u[1];
             c1[0] = even ? h1b.u[0] : got[2]; c1[1] = even ? h1b.u[1] : got[3]; c1[2] = even ? got[2] : h2b.u[0]; c1[3] = even ? got[3] : h2b.u[1];
             // streaming stores: the 0.5 GB of output would otherwise evict table records from L2 / Infinity Cache
-            v4u* dst = reinterpret_cast<v4u*>(reinterpret_cast<unsigned char*>(out) + (size_t)pixel * (C * 4) + slice * 256 + j * 16);
+            u32x4* dst = reinterpret_cast<u32x4*>(reinterpret_cast<unsigned char*>(out) + (size_t)pixel * (C * 4) + slice * 256 + j * 16);
             __builtin_nontemporal_store(c0, dst);
             __builtin_nontemporal_store(c1, dst + 8);
         } else if constexpr (OUT_B3) {
@@ -742,8 +688,8 @@ __global__ __launch_bounds__(256) void k_conv2_lut_xcd(const unsigned* __restric
             unsigned char* base = reinterpret_cast<unsigned char*>(out) + (size_t)pixel * (C * 6) + slice * 384 + j * 16;
 #pragma unroll
             for (int k3 = 0; k3 < 3; ++k3) {
-                const v4u c = *reinterpret_cast<const v4u*>(img + k3 * 128 + j * 16);
-                __builtin_nontemporal_store(c, reinterpret_cast<v4u*>(base + k3 * 128));
+                const u32x4 c = *reinterpret_cast<const u32x4*>(img + k3 * 128 + j * 16);
+                __builtin_nontemporal_store(c, reinterpret_cast<u32x4*>(base + k3 * 128));
             }
             __builtin_amdgcn_wave_barrier();
         } else {
@@ -943,16 +889,16 @@ __global__ __launch_bounds__(CF::NT, 2) void k_gemm_h2(const uint4* __restrict__
             const uint4* ga;
             if constexpr (CF::LUT) ga = lut_src(i, lut[tap * BM + a_row0(i) + l8], slice);
             else ga = ((amask[i] >> tap) & 1) ? in + (aidx[i] + toff) : zsrc;
-            __builtin_amdgcn_global_load_lds((h2_gptr)ga, (h2_lptr)(la + a_row0(i) * 128), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((oz_gptr)ga, (oz_lptr)(la + a_row0(i) * 128), 16, 0, 0);
         }
 #pragma unroll
         for (int i = 0; i < IB; ++i) {
             const uint4* gb = Wh + bidx[i] + kt * 8;
-            __builtin_amdgcn_global_load_lds((h2_gptr)gb, (h2_lptr)(lb + b_row0(i) * 128), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((oz_gptr)gb, (oz_lptr)(lb + b_row0(i) * 128), 16, 0, 0);
         }
     };
 
-    f32x4v acc[RI][RJ];
+    f32x4 acc[RI][RJ];
 #pragma unroll
     for (int i = 0; i < RI; ++i)
 #pragma unroll
@@ -979,11 +925,11 @@ __global__ __launch_bounds__(CF::NT, 2) void k_gemm_h2(const uint4* __restrict__
 #pragma unroll
             for (int i = 0; i < IA; ++i) {
                 const uint4* ga = ((amask[i] >> tap) & 1) ? in + (aidx[i] + toff) : zsrc;
-                __builtin_amdgcn_global_load_lds((h2_gptr)ga, (h2_lptr)(st + a_row0(i) * 128), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds((oz_gptr)ga, (oz_lptr)(st + a_row0(i) * 128), 16, 0, 0);
             }
 #pragma unroll
             for (int i = 0; i < IB; ++i)
-                __builtin_amdgcn_global_load_lds((h2_gptr)(Wh + bidx[i] + ktc * 8), (h2_lptr)(st + CF::TILEA + b_row0(i) * 128), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds((oz_gptr)(Wh + bidx[i] + ktc * 8), (oz_lptr)(st + CF::TILEA + b_row0(i) * 128), 16, 0, 0);
         };
         int k2 = kbeg + 2 < nk ? kbeg + 2 : nk - 1, slice2 = k2 / g.taps, tap2 = k2 - slice2 * g.taps;      // tile kt + 2 (past the end: the last again)
         stage(kbeg, 0);
@@ -1053,10 +999,10 @@ __global__ __launch_bounds__(CF::NT, 2) void k_gemm_h2(const uint4* __restrict__
         auto put_a = [&](int i, int slice, int tap, unsigned char* la) {
             const int dy = (tap * 11) >> 5, dx = tap - 3 * dy;                                      // tap / 3, tap % 3 for tap < 9
             const uint4* ga = ((amask[i] >> tap) & 1) ? in + (aidx[i] + ((long long)dy * g.Hin + dx) * rowq + slice * 8) : zsrc;
-            __builtin_amdgcn_global_load_lds((h2_gptr)ga, (h2_lptr)(la + a_row0(i) * 128), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((oz_gptr)ga, (oz_lptr)(la + a_row0(i) * 128), 16, 0, 0);
         };
         auto put_b = [&](int i, int ktc, unsigned char* lb) {
-            __builtin_amdgcn_global_load_lds((h2_gptr)(Wh + bidx[i] + ktc * 8), (h2_lptr)(lb + b_row0(i) * 128), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((oz_gptr)(Wh + bidx[i] + ktc * 8), (oz_lptr)(lb + b_row0(i) * 128), 16, 0, 0);
         };
         int k1 = kbeg + 1 < nk ? kbeg + 1 : nk - 1, slice1 = k1 / g.taps, tap1 = k1 - slice1 * g.taps;      // tile kt + 1, kt + 2 (past the end: the last again)
         int k2 = kbeg + 2 < nk ? kbeg + 2 : nk - 1, slice2 = k2 / g.taps, tap2 = k2 - slice2 * g.taps;
@@ -1114,7 +1060,7 @@ __global__ __launch_bounds__(CF::NT, 2) void k_gemm_h2(const uint4* __restrict__
                     for (int i = 0; i < RI; ++i)
 #pragma unroll
                         for (int j = 0; j < 2; ++j) {
-                            f32x4v& c = acc[i][nh * 2 + j];
+                            f32x4& c = acc[i][nh * 2 + j];
                             c = __builtin_amdgcn_mfma_f32_16x16x32_f16(p == 0 ? fa2[i] : fa1[i], p == 1 ? fb2[nh * 2 + j] : fb1[nh * 2 + j], c, 0, 0, 0);
                         }
                 __builtin_amdgcn_sched_barrier(0);
@@ -1197,7 +1143,7 @@ __global__ __launch_bounds__(CF::NT, 2) void k_gemm_h2(const uint4* __restrict__
                 const uint4* ga;
                 if constexpr (CF::LUT) ga = lut_src(i, aid[i], slice);
                 else ga = ((amask[i] >> tap) & 1) ? in + (aidx[i] + toff) : zsrc;
-                __builtin_amdgcn_global_load_lds((h2_gptr)ga, (h2_lptr)(la + a_row0(i) * 128), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds((oz_gptr)ga, (oz_lptr)(la + a_row0(i) * 128), 16, 0, 0);
             };
             // LUT: the table rows of the tile being staged, read in phase 1 (retired by its lgkmcnt(0)), used in phases 2 and 4
             auto ld_ids = [&]() {
@@ -1207,7 +1153,7 @@ __global__ __launch_bounds__(CF::NT, 2) void k_gemm_h2(const uint4* __restrict__
                 }
             };
             auto dma_b = [&](int i) {
-                __builtin_amdgcn_global_load_lds((h2_gptr)(Wh + bidx[i] + ktc * 8), (h2_lptr)(lb + b_row0(i) * 128), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds((oz_gptr)(Wh + bidx[i] + ktc * 8), (oz_lptr)(lb + b_row0(i) * 128), 16, 0, 0);
             };
             auto lda = [&](int half) {
 #pragma unroll
@@ -1246,7 +1192,7 @@ __global__ __launch_bounds__(CF::NT, 2) void k_gemm_h2(const uint4* __restrict__
                     for (int i = 0; i < HA; ++i)
 #pragma unroll
                         for (int j = 0; j < 2; ++j) {
-                            f32x4v& c = acc[mh * HA + i][nh * 2 + j];
+                            f32x4& c = acc[mh * HA + i][nh * 2 + j];
                             c = __builtin_amdgcn_mfma_f32_16x16x32_f16(p == 0 ? fa2[i] : fa1[i], p == 1 ? fb2[nh * 2 + j] : fb1[nh * 2 + j], c, 0, 0, 0);
                         }
                 __builtin_amdgcn_sched_barrier(0);

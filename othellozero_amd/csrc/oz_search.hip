@@ -2035,11 +2035,8 @@ OZ_API int oz_selftest_arith(const double* a, const double* b, int count, double
 // `device_calibration`, so that a reader can tell a slow box (or a power-capped one) from a regression: the GEMM kernels' own rate moves
 // with this one.  tflops = FLOP of the issued MFMAs / HIP-event time; clock_ghz = the clock at which back-to-back issue (64 / 16 cycles per
 // MFMA and SIMD) gives that rate.
-typedef float dg_f32x16 __attribute__((ext_vector_type(16)));
-typedef float dg_f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 dg_f16x8 __attribute__((ext_vector_type(8)));
 __global__ __launch_bounds__(256) void k_diag_mfma_f32(float* out, int iters, float a0, float b0) {
-    dg_f32x16 acc[4];
+    f32x16 acc[4];
     for (int i = 0; i < 4; ++i) for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
     const float a = a0 + threadIdx.x * 1.0009765625e-3f, b = b0 + threadIdx.x * 2.001953125e-3f;
     for (int it = 0; it < iters; ++it) {
@@ -2053,9 +2050,9 @@ __global__ __launch_bounds__(256) void k_diag_mfma_f32(float* out, int iters, fl
     out[blockIdx.x * blockDim.x + threadIdx.x] = s;
 }
 __global__ __launch_bounds__(256) void k_diag_mfma_f16(float* out, int iters, unsigned seed) {
-    dg_f32x4 acc[4];
+    f32x4 acc[4];
     for (int i = 0; i < 4; ++i) for (int r = 0; r < 4; ++r) acc[i][r] = 0.f;
-    dg_f16x8 a, b;
+    f16x8 a, b;
     uint64_t r = oz_sm64(seed + 977u * (blockIdx.x * blockDim.x + threadIdx.x));
     for (int j = 0; j < 8; ++j) {                            // values in [2^-3, 2^-2) with random mantissas and signs: the window the network's tensors sit in
         r = oz_sm64(r);
@@ -2073,11 +2070,10 @@ __global__ __launch_bounds__(256) void k_diag_mfma_f16(float* out, int iters, un
     for (int i = 0; i < 4; ++i) for (int r2 = 0; r2 < 4; ++r2) s += acc[i][r2];
     out[blockIdx.x * blockDim.x + threadIdx.x] = s;
 }
-typedef __bf16 dg_bf16x8 __attribute__((ext_vector_type(8)));
 __global__ __launch_bounds__(256) void k_diag_mfma_bf16(float* out, int iters, unsigned seed) {
-    dg_f32x4 acc[4];
+    f32x4 acc[4];
     for (int i = 0; i < 4; ++i) for (int r = 0; r < 4; ++r) acc[i][r] = 0.f;
-    dg_bf16x8 a, b;
+    bf16x8 a, b;
     uint64_t r = oz_sm64(seed + 977u * (blockIdx.x * blockDim.x + threadIdx.x));
     for (int j = 0; j < 8; ++j) {                            // values in [2^-3, 2^-2) with random 7-bit mantissas and signs: what the planes of precision bf16x3 hold
         r = oz_sm64(r);

@@ -23,9 +23,6 @@
 
 #include "oz_internal.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 #define BN_EPS 1e-3f
 #define RED_S 256         // row splits of the column reductions (2048 waves of 1 KB loads at 512 channels: the passes are HBM streams)
 
@@ -591,7 +588,6 @@ __global__ __launch_bounds__(256) void k_t_dgrad_operand(const float* __restrict
 // would keep 13 bits, at 2^13 it keeps all 22.
 #define T_W_TARGET 1000.0f
 #define T_DZ_TARGET 8192.0f
-typedef _Float16 t_f16x8 __attribute__((ext_vector_type(8)));
 struct AbsMaxArgs { const float* p[3]; long long n[3]; };
 // out[l] = bits of max |p[l][i]| (non-negative floats order like their bit patterns); out is zeroed by the caller
 __global__ __launch_bounds__(256) void k_t_absmax(AbsMaxArgs a, unsigned* __restrict__ out) {
@@ -627,13 +623,6 @@ __device__ __forceinline__ int t_exp_for(unsigned max_bits, float target) {
     const int e = (int)floorf(log2f(target / mx));
     return e < -120 ? -120 : e > 120 ? 120 : e;
 }
-__device__ __forceinline__ void t_store_h2(uint4* dst, const float* v) {
-    t_f16x8 h1, h2;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { const _Float16 a = (_Float16)v[j]; h1[j] = a; h2[j] = (_Float16)(v[j] - (float)a); }
-    dst[0] = *reinterpret_cast<uint4*>(&h1);
-    dst[1] = *reinterpret_cast<uint4*>(&h2);
-}
 // Keras kernel W[9][Cin][Cout] fp32 -> a k_gemm_h2 weight operand in the h2 layout, k order k' = (slice * 9 + tap) * 32 + c32,
 // scaled by 2^kexp (kexp from the tensor's maximum), straight from the master weights (no fp32 intermediate):
 //   DGRAD = 0  forward operand:       row n = co, channel of k' = ci:  W[tap][ci][co]        (threads adjacent in co: coalesced reads)
@@ -661,7 +650,7 @@ __global__ __launch_bounds__(256) void k_t_w_to_h2(const float* __restrict__ W, 
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = ldexpf(W[((size_t)tap * Cin + ch + j) * Cout + nrow], kexp);
     }
-    t_store_h2(out + ((size_t)nrow * ng + grp) * 2, v);
+    h2_store8(out, nrow, ng * 8, kp, v);
     if (!DGRAD && grp == 0) scale_out[nrow] = ldexpf(1.0f, -kexp);
 }
 // activation rows [M][C] fp32 -> h2 layout (the next layer's A operand)
@@ -676,7 +665,7 @@ __global__ __launch_bounds__(256) void k_t_act_to_h2(const float* __restrict__ a
     bool over = false;
 #pragma unroll
     for (int j = 0; j < 8; ++j) { v[j] = q[j]; over |= fabsf(v[j]) > 65504.0f; }
-    t_store_h2(out + ((size_t)m * cg + g8) * 2, v);
+    h2_store8(out, m, C, g8 * 8, v);
     if (over) atomicOr(flag, 1);
 }
 // dz (zero-bordered [B][Hz][Hz][C] fp32, interior Hout^2 at offset zoff) -> the same geometry in the h2 layout, scaled by 2^ez with ez
@@ -696,7 +685,7 @@ __global__ __launch_bounds__(256) void k_t_dz_to_h2(const float* __restrict__ dz
     float v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = ldexpf(q[j], ez);
-    t_store_h2(out + (row * cg + g8) * 2, v);
+    h2_store8(out, row, C, g8 * 8, v);
 }
 
 // ---------------------------------------------------------------- f16x2 weight gradient of the 3x3 layers (round 3)
@@ -724,21 +713,21 @@ __global__ __launch_bounds__(256) void k_t_dz_to_h2(const float* __restrict__ dz
 #define WH_XROW (2 * WH_XW * WH_CI * 16)        // bytes of one staged X row: [plane][slot][ci] x 16 B = 20 KB
 #define WH_ZROW (2 * WH_ZW * WH_CO * 16)        // bytes of one staged dZ row: [plane][slot][co] x 16 B = 32 KB
 #define WH_LDS (4 * WH_XROW + 2 * WH_ZROW)      // 144 KB
-// X octet image of a[l - 1] ([B][Hin][Hin][C] fp32): out[octet][row < Hin + 2 pad][slot < WH_XW][plane][C] x 16 B.
-// One thread per (cell, 4 channels): eight 16-byte loads (one per board), eight 16-byte stores (4 channels x 2 planes).
+// Octet images, PLANES = 2 (f16x2: h1 | h2 in fp16, dZ scaled) or 3 (bf16x3: the three bf16 planes, unscaled); a 16-byte entry holds one
+// (pixel, plane, channel) of 8 boards, split by oz_split8_store.
+// X octet image of a[l - 1] ([B][Hin][Hin][C] fp32): out[octet][row < Hin + 2 pad][slot < WH_XW][plane][C] x 16 B (zero border, zero columns,
+// zero boards >= B).  One thread per (cell, 4 channels): eight 16-byte loads (one per board), 4 x PLANES 16-byte stores.
+template <int PLANES>
 __device__ __forceinline__ void t_store_octet4(uint4* __restrict__ dst, int C, const f32x4* v) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-        t_f16x8 h1, h2;
+        float x[8];
 #pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            const _Float16 x = (_Float16)v[b][q];
-            h1[b] = x; h2[b] = (_Float16)(v[b][q] - (float)x);
-        }
-        dst[q] = *reinterpret_cast<uint4*>(&h1);
-        dst[C + q] = *reinterpret_cast<uint4*>(&h2);
+        for (int b = 0; b < 8; ++b) x[b] = v[b][q];
+        oz_split8_store<PLANES>(dst + q, C, x);
     }
 }
+template <int PLANES>
 __global__ __launch_bounds__(256) void k_t_x_octets(const float* __restrict__ a, const int* __restrict__ d_count, int Hin, int pad, int C, uint4* __restrict__ out) {
     const int B = *d_count, XR = Hin + 2 * pad, noct = (B + 7) >> 3, C4 = C >> 2;
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -754,17 +743,20 @@ __global__ __launch_bounds__(256) void k_t_x_octets(const float* __restrict__ a,
         const int bb = oct * 8 + b;
         v[b] = (inside && bb < B) ? *reinterpret_cast<const f32x4*>(a + (((size_t)bb * Hin + iy) * Hin + ix) * C + ch) : f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    t_store_octet4(out + (size_t)cell * 2 * C + ch, C, v);
+    t_store_octet4<PLANES>(out + (size_t)cell * PLANES * C + ch, C, v);
 }
-// dZ octet image of dz[l] (zero-bordered [B][Hz][Hz][C] fp32, interior Hout^2 at offset zoff), scaled by 2^ez (ez from the tensor's maximum):
-// out[octet][row < Hout][slot < WH_ZW][plane][C] x 16 B
+// dZ octet image of dz[l] (zero-bordered [B][Hz][Hz][C] fp32, interior Hout^2 at offset zoff): out[octet][row < Hout][slot < WH_ZW][plane][C] x 16 B;
+// f16x2 only: scaled by 2^ez (ez from the tensor's maximum dzmax), a non-finite maximum raises flag bit 2
+template <int PLANES>
 __global__ __launch_bounds__(256) void k_t_z_octets(const float* __restrict__ dz, const int* __restrict__ d_count, int Hout, int Hz, int zoff, int C,
                                                     const unsigned* __restrict__ dzmax, uint4* __restrict__ out, int* __restrict__ flag) {
     const int B = *d_count, noct = (B + 7) >> 3, C4 = C >> 2;
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx == 0 && t_bad_max(*dzmax)) atomicOr(flag, 2);
+    if constexpr (PLANES == 2) {
+        if (idx == 0 && t_bad_max(*dzmax)) atomicOr(flag, 2);
+    }
     if (idx >= (long long)noct * Hout * WH_ZW * C4) return;
-    const int ez = t_exp_for(*dzmax, T_DZ_TARGET);
+    const int ez = PLANES == 2 ? t_exp_for(*dzmax, T_DZ_TARGET) : 0;
     const int ch = (int)(idx % C4) * 4;
     const long long cell = idx / C4;
     const int c = (int)(cell % WH_ZW), r = (int)((cell / WH_ZW) % Hout), oct = (int)(cell / ((long long)WH_ZW * Hout));
@@ -774,16 +766,15 @@ __global__ __launch_bounds__(256) void k_t_z_octets(const float* __restrict__ dz
         const int bb = oct * 8 + b;
         v[b] = f32x4{0.f, 0.f, 0.f, 0.f};
         if (c < Hout && bb < B) {
-            const f32x4 x = *reinterpret_cast<const f32x4*>(dz + (((size_t)bb * Hz + r + zoff) * Hz + c + zoff) * C + ch);
+            v[b] = *reinterpret_cast<const f32x4*>(dz + (((size_t)bb * Hz + r + zoff) * Hz + c + zoff) * C + ch);
+            if constexpr (PLANES == 2) {
 #pragma unroll
-            for (int q = 0; q < 4; ++q) v[b][q] = ldexpf(x[q], ez);
+                for (int q = 0; q < 4; ++q) v[b][q] = ldexpf(v[b][q], ez);
+            }
         }
     }
-    t_store_octet4(out + (size_t)cell * 2 * C + ch, C, v);
+    t_store_octet4<PLANES>(out + (size_t)cell * PLANES * C + ch, C, v);
 }
-typedef float t_f32x4 __attribute__((ext_vector_type(4)));
-typedef const __attribute__((address_space(1))) void* t_gptr;
-typedef __attribute__((address_space(3))) void* t_lptr;
 struct WhGeom { int XR, Hout, Cin, Cout; };
 __global__ __launch_bounds__(512, 2) void k_wgrad_h2(const uint4* __restrict__ Xt, const uint4* __restrict__ Zt, const int* __restrict__ d_count, WhGeom g,
                                                      const unsigned* __restrict__ dzmax, float* __restrict__ dW, int msplit, float* __restrict__ partial,
@@ -804,22 +795,22 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_h2(const uint4* __restrict__ X
         const uint4* src = Xt + (((size_t)oct * g.XR + row) * WH_XW) * 2 * g.Cin + ci0 + lane;
         for (int q = wave; q < 2 * WH_XW; q += 8) {
             const int p = q / WH_XW, c = q - p * WH_XW;
-            __builtin_amdgcn_global_load_lds((t_gptr)(src + ((size_t)c * 2 + p) * g.Cin), (t_lptr)(Xring + slot * WH_XROW + q * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((oz_gptr)(src + ((size_t)c * 2 + p) * g.Cin), (oz_lptr)(Xring + slot * WH_XROW + q * 1024), 16, 0, 0);
         }
     };
     auto dma_z = [&](int oct, int row, int buf) {
         const uint4* src = Zt + (((size_t)oct * g.Hout + row) * WH_ZW) * 2 * g.Cout + co0 + lane;
         for (int q = wave; q < 4 * WH_ZW; q += 8) {
             const int h = q & 1, c = (q >> 1) % WH_ZW, p = q / (2 * WH_ZW);
-            __builtin_amdgcn_global_load_lds((t_gptr)(src + ((size_t)c * 2 + p) * g.Cout + h * 64), (t_lptr)(Zbuf + buf * WH_ZROW + ((p * WH_ZW + c) * 2 + h) * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((oz_gptr)(src + ((size_t)c * 2 + p) * g.Cout + h * 64), (oz_lptr)(Zbuf + buf * WH_ZROW + ((p * WH_ZW + c) * 2 + h) * 1024), 16, 0, 0);
         }
     };
 
-    t_f32x4 acc[9][4];
+    f32x4 acc[9][4];
 #pragma unroll
     for (int t = 0; t < 9; ++t)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[t][j] = t_f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < 4; ++j) acc[t][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     for (int oct = o0; oct < o1; ++oct) {
         // the three X rows and the dZ row of output row 0 (the previous octet's last step ended with a barrier: every slot is free)
@@ -832,18 +823,18 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_h2(const uint4* __restrict__ X
 #pragma unroll
             for (int quad = 0; quad < 2; ++quad) {
                 const int px = quad * 4 + g4;
-                t_f16x8 z1[4], z2[4];
+                f16x8 z1[4], z2[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    z1[j] = *reinterpret_cast<const t_f16x8*>(Zr + ((0 * WH_ZW + px) * WH_CO + j * 16) * 16);
-                    z2[j] = *reinterpret_cast<const t_f16x8*>(Zr + ((1 * WH_ZW + px) * WH_CO + j * 16) * 16);
+                    z1[j] = *reinterpret_cast<const f16x8*>(Zr + ((0 * WH_ZW + px) * WH_CO + j * 16) * 16);
+                    z2[j] = *reinterpret_cast<const f16x8*>(Zr + ((1 * WH_ZW + px) * WH_CO + j * 16) * 16);
                 }
 #pragma unroll
                 for (int t = 0; t < 9; ++t) {
                     const int dy = t / 3, dx = t - 3 * dy;
                     const unsigned char* Xr = Xring + ((oy + dy) & 3) * WH_XROW + (wm * 16 + r16) * 16;
-                    const t_f16x8 x1 = *reinterpret_cast<const t_f16x8*>(Xr + ((0 * WH_XW + px + dx) * WH_CI) * 16);
-                    const t_f16x8 x2 = *reinterpret_cast<const t_f16x8*>(Xr + ((1 * WH_XW + px + dx) * WH_CI) * 16);
+                    const f16x8 x1 = *reinterpret_cast<const f16x8*>(Xr + ((0 * WH_XW + px + dx) * WH_CI) * 16);
+                    const f16x8 x2 = *reinterpret_cast<const f16x8*>(Xr + ((1 * WH_XW + px + dx) * WH_CI) * 16);
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(x2, z1[j], acc[t][j], 0, 0, 0);
@@ -878,30 +869,20 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_h2(const uint4* __restrict__ X
 // Fallback rule: none.  Every trainer capacity (Bmax) takes these kernels: the GEMMs split their k loop until the grid fills the chip (keyed on
 // Bmax), the weight gradient splits its board range; at the reference's batch of 32 both already beat the exact-fp32 kernels they replace.
 //
-// Keras kernel W[9][Cin][Cout] fp32 -> a k_gemm_b3 weight operand, k order k' = (slice * 9 + tap) * 32 + c32 (as k_t_w_to_h2, unscaled):
-//   DGRAD = 0  forward operand:       row n = co, channel of k' = ci:  W[tap][ci][co]
-//   DGRAD = 1  data-gradient operand: row n = ci, channel of k' = co:  W[8 - tap][ci][co]   (reversed, channel-swapped taps)
-template <int DGRAD>
+// The forward weight operand is k_w_to_b3's (oz_w_to_b3_launch, taps = 9).  The data-gradient operand: Keras kernel W[9][Cin][Cout] fp32 -> row
+// n = ci, channel of k' = co: W[8 - tap][ci][co] (the reversed, channel-swapped taps) in k order k' = (slice * 9 + tap) * 32 + c32, as k_t_w_to_h2<1>
+// unscaled.  One thread per (row, group of 8 k'): a thread's 8 values are 8 consecutive co = one 32-byte read.
 __global__ __launch_bounds__(256) void k_t_w_to_b3(const float* __restrict__ W, int Cin, int Cout, uint4* __restrict__ out) {
-    const int N = DGRAD ? Cin : Cout, Cch = DGRAD ? Cout : Cin, ng = 9 * Cch / 8;
+    const int ng = 9 * Cout / 8;
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    int nrow, grp;
-    if (DGRAD) { grp = (int)(idx % ng); nrow = (int)(idx / ng); }
-    else { nrow = (int)(idx % N); grp = (int)(idx / N); }
-    if (idx >= (long long)N * ng) return;
+    const int grp = (int)(idx % ng), nrow = (int)(idx / ng);
+    if (idx >= (long long)Cin * ng) return;
     const int kp = grp * 8, tile = kp >> 5, c32 = kp & 31, slice = tile / 9, tap = tile - slice * 9, ch = slice * 32 + c32;
-    bf16x8 p0, p1, p2;
+    const float* q = W + ((size_t)(8 - tap) * Cin + nrow) * Cout + ch;
+    float v[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float v = DGRAD ? W[((size_t)(8 - tap) * Cin + nrow) * Cout + ch + j] : W[((size_t)tap * Cin + ch + j) * Cout + nrow];
-        __bf16 a, b, c;
-        b3_split(v, a, b, c);
-        p0[j] = a; p1[j] = b; p2[j] = c;
-    }
-    uint4* dst = out + (size_t)nrow * (size_t)(9 * Cch / 32 * 12) + (grp >> 2) * 12 + (grp & 3);
-    dst[0] = *reinterpret_cast<uint4*>(&p0);
-    dst[4] = *reinterpret_cast<uint4*>(&p1);
-    dst[8] = *reinterpret_cast<uint4*>(&p2);
+    for (int j = 0; j < 8; ++j) v[j] = q[j];
+    b3_store8(out, nrow, 9 * Cout, kp, v);
 }
 // dz (zero-bordered [B][Hz][Hz][C] fp32, interior Hout^2 at offset zoff) -> the same geometry in the b3 layout; only the interior is written
 // (the b3 buffer is zeroed once at allocation, so its border stays zero).  One thread per (row, 8 channels).
@@ -913,69 +894,8 @@ __global__ __launch_bounds__(256) void k_t_dz_to_b3(const float* __restrict__ dz
     const int g8 = (int)(idx % cg), b = (int)(m / P), pix = (int)(m % P);
     const size_t row = ((size_t)b * Hz + pix / Hout + zoff) * Hz + pix % Hout + zoff;
     const f32x4 lo = *reinterpret_cast<const f32x4*>(dz + row * C + g8 * 8), hi = *reinterpret_cast<const f32x4*>(dz + row * C + g8 * 8 + 4);
-    bf16x8 p0, p1, p2;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        __bf16 a, bb, c;
-        b3_split(j < 4 ? lo[j] : hi[j - 4], a, bb, c);
-        p0[j] = a; p1[j] = bb; p2[j] = c;
-    }
-    uint4* dst = out + row * (size_t)(C / 32 * 12) + (g8 >> 2) * 12 + (g8 & 3);
-    dst[0] = *reinterpret_cast<uint4*>(&p0);
-    dst[4] = *reinterpret_cast<uint4*>(&p1);
-    dst[8] = *reinterpret_cast<uint4*>(&p2);
-}
-// octet images in three planes: [octet][row][pixel slot][plane 0 | 1 | 2][C] x 16 B (8 boards of bf16) -- k_t_x_octets / k_t_z_octets with
-// a third plane and no scaling.  4 channels x 3 planes = twelve 16-byte stores per thread.
-__device__ __forceinline__ void t_store_octet4_b3(uint4* __restrict__ dst, int C, const f32x4* v) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        bf16x8 h1, h2, h3;
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            __bf16 a, bb, c;
-            b3_split(v[b][q], a, bb, c);
-            h1[b] = a; h2[b] = bb; h3[b] = c;
-        }
-        dst[q] = *reinterpret_cast<uint4*>(&h1);
-        dst[C + q] = *reinterpret_cast<uint4*>(&h2);
-        dst[2 * C + q] = *reinterpret_cast<uint4*>(&h3);
-    }
-}
-// X octet image of a[l - 1] ([B][Hin][Hin][C] fp32): out[octet][row < Hin + 2 pad][slot < WH_XW][plane][C] (zero border, zero columns, zero boards >= B)
-__global__ __launch_bounds__(256) void k_t_x_octets_b3(const float* __restrict__ a, const int* __restrict__ d_count, int Hin, int pad, int C, uint4* __restrict__ out) {
-    const int B = *d_count, XR = Hin + 2 * pad, noct = (B + 7) >> 3, C4 = C >> 2;
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (long long)noct * XR * WH_XW * C4) return;
-    const int ch = (int)(idx % C4) * 4;
-    const long long cell = idx / C4;
-    const int c = (int)(cell % WH_XW), r = (int)((cell / WH_XW) % XR), oct = (int)(cell / ((long long)WH_XW * XR));
-    const int iy = r - pad, ix = c - pad;
-    const bool inside = iy >= 0 && iy < Hin && ix >= 0 && ix < Hin;
-    f32x4 v[8];
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-        const int bb = oct * 8 + b;
-        v[b] = (inside && bb < B) ? *reinterpret_cast<const f32x4*>(a + (((size_t)bb * Hin + iy) * Hin + ix) * C + ch) : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    t_store_octet4_b3(out + (size_t)cell * 3 * C + ch, C, v);
-}
-// dZ octet image of dz[l] (zero-bordered [B][Hz][Hz][C] fp32, interior Hout^2 at offset zoff): out[octet][row < Hout][slot < WH_ZW][plane][C]
-__global__ __launch_bounds__(256) void k_t_z_octets_b3(const float* __restrict__ dz, const int* __restrict__ d_count, int Hout, int Hz, int zoff, int C,
-                                                       uint4* __restrict__ out) {
-    const int B = *d_count, noct = (B + 7) >> 3, C4 = C >> 2;
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (long long)noct * Hout * WH_ZW * C4) return;
-    const int ch = (int)(idx % C4) * 4;
-    const long long cell = idx / C4;
-    const int c = (int)(cell % WH_ZW), r = (int)((cell / WH_ZW) % Hout), oct = (int)(cell / ((long long)WH_ZW * Hout));
-    f32x4 v[8];
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-        const int bb = oct * 8 + b;
-        v[b] = (c < Hout && bb < B) ? *reinterpret_cast<const f32x4*>(dz + (((size_t)bb * Hz + r + zoff) * Hz + c + zoff) * C + ch) : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    t_store_octet4_b3(out + (size_t)cell * 3 * C + ch, C, v);
+    const float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    b3_store8(out, row, C, g8 * 8, v);
 }
 // k_wgrad_b3: the weight gradient of conv2..conv4 on v_mfma_f32_16x16x32_bf16, k_wgrad_h2's scheme (octet images, a block owns a ci x co tile
 // for all nine taps, walks the output rows of each octet with a 4-slot X row ring and two dZ row buffers, every tap reads the same staged rows
@@ -1011,22 +931,22 @@ __global__ __launch_bounds__(512) void k_wgrad_b3(const uint4* __restrict__ Xt, 
         const uint4* src = Xt + (((size_t)oct * g.XR + row) * WH_XW) * 3 * g.Cin + ci0 + (lane & 31);
         for (int q = wave; q < 3 * WH_XW / 2; q += 8) {
             const int pc = 2 * q + (lane >> 5), p = pc / WH_XW, c = pc - p * WH_XW;
-            __builtin_amdgcn_global_load_lds((t_gptr)(src + ((size_t)c * 3 + p) * g.Cin), (t_lptr)(Xring + slot * WB_XROW + q * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((oz_gptr)(src + ((size_t)c * 3 + p) * g.Cin), (oz_lptr)(Xring + slot * WB_XROW + q * 1024), 16, 0, 0);
         }
     };
     auto dma_z = [&](int oct, int row, int buf) {
         const uint4* src = Zt + (((size_t)oct * g.Hout + row) * WH_ZW) * 3 * g.Cout + co0 + lane;
         for (int q = wave; q < 6 * WH_ZW; q += 8) {
             const int h = q & 1, pc = q >> 1, p = pc / WH_ZW, c = pc - p * WH_ZW;
-            __builtin_amdgcn_global_load_lds((t_gptr)(src + ((size_t)c * 3 + p) * g.Cout + h * 64), (t_lptr)(Zbuf + buf * WB_ZROW + q * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((oz_gptr)(src + ((size_t)c * 3 + p) * g.Cout + h * 64), (oz_lptr)(Zbuf + buf * WB_ZROW + q * 1024), 16, 0, 0);
         }
     };
 
-    t_f32x4 acc[9][2];
+    f32x4 acc[9][2];
 #pragma unroll
     for (int t = 0; t < 9; ++t)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) acc[t][j] = t_f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < 2; ++j) acc[t][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     for (int oct = o0; oct < o1; ++oct) {
         // the three X rows and the dZ row of output row 0 (the previous octet's last step ended with a barrier: every slot is free)
@@ -1129,12 +1049,12 @@ struct oz_trainer {
     bool overlap = true;                 // weight gradients on the second stream beside the data-gradient chain (false: all on the main stream)
     long long gpartial_floats = 40LL << 20;      // 160 MB each: 16 row-split slabs of a 3x3 x 512 x 512 weight gradient
     bool wconv_attr = false, wh_attr = false;
-    uint4 *xt_oct[4] = {}, *zt_oct[4] = {};     // f16x2 weight gradient: octet images of a[l - 1] / dz[l] (k_t_x_octets / k_t_z_octets)
+    uint4 *xt_oct[4] = {}, *zt_oct[4] = {};     // f16x2 weight gradient: octet images of a[l - 1] / dz[l] (k_t_x_octets<2> / k_t_z_octets<2>)
     // bf16x3 mode (oz_trainer_set_precision 2): conv2..4 forward, data gradient and weight gradient on the bf16 matrix cores
     int b3 = 0;
     bool wb3_attr = false;
     uint4 *Wb3[4] = {}, *Wb3d[4] = {}, *a_b3[3] = {}, *dz_b3[4] = {};
-    uint4 *xt_b3[4] = {}, *zt_b3[4] = {};     // octet images in three planes (k_t_x_octets_b3 / k_t_z_octets_b3)
+    uint4 *xt_b3[4] = {}, *zt_b3[4] = {};     // octet images in three planes (k_t_x_octets<3> / k_t_z_octets<3>)
     // HBM-resident data set of a fit (oz_trainer_set_dataset / oz_trainer_fit_epoch)
     uint64_t *ds_own = nullptr, *ds_opp = nullptr;
     float *ds_pi = nullptr, *ds_z = nullptr;
@@ -1401,7 +1321,7 @@ static int t_refresh(oz_trainer* t) {
     }
     if (t->b3) {         // bf16x3: the b3 forward operands, straight from the masters (no scaling)
         for (int l = 1; l < 4; ++l) {
-            hipLaunchKernelGGL(k_t_w_to_b3<0>, dim3(h2_blocks), dim3(256), 0, r, t->param(6 * l), C, C, t->Wb3[l]);
+            if (int rc = oz_w_to_b3_launch(t->param(6 * l), 9 * C, C, 9, t->Wb3[l], r)) return rc;
             if (t->overlap) { OZ_HIP(hipEventRecord(t->ev_wl[l], r)); t->wait_wl[l] = true; }
         }
         OZ_HIP(hipGetLastError());
@@ -1415,7 +1335,7 @@ static int t_refresh(oz_trainer* t) {
         if (t->h2)
             hipLaunchKernelGGL(k_t_w_to_h2<1>, dim3(h2_blocks), dim3(256), 0, r, t->param(6 * l), C, C, t->wmax + (l - 1), t->Whd[l], (float*)nullptr, t->h2flag);
         else if (t->b3)
-            hipLaunchKernelGGL(k_t_w_to_b3<1>, dim3(h2_blocks), dim3(256), 0, r, t->param(6 * l), C, C, t->Wb3d[l]);
+            hipLaunchKernelGGL(k_t_w_to_b3, dim3(h2_blocks), dim3(256), 0, r, t->param(6 * l), C, C, t->Wb3d[l]);
         else {
             const long long cnt = 9LL * C * C;
             hipLaunchKernelGGL(k_t_dgrad_operand, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, r, t->param(6 * l), C, C, t->Wd[l]);
@@ -1582,39 +1502,38 @@ static int t_forward_backward_async(oz_trainer* t, int B) {
             }
             // (measured on one MI355X, 8x8 / 512 filters: the board-resident kernel wins from batch 256 on -- 6.01 vs 6.36 ms per step, 17.0 vs
             //  19.9 at 1024 -- and loses 3-4 % at 32 .. 128, where the tap-per-block kernel's 144 x 4 short blocks finish sooner)
-            if (taps[l] == 9 && t->b3) {
-                // bf16x3: octet images of a[l - 1] and dz[l] in three planes, then the MFMA kernel on the bf16 matrix cores (six products per fp32 product)
+            const bool wgrad_b3 = taps[l] == 9 && t->b3;
+            const bool wgrad_h2 = taps[l] == 9 && t->h2 && have_dzmax && l >= 1 && B >= WH_MIN_BATCH && Cin[l] % WH_CI == 0 && Cc % WH_CO == 0;
+            if (wgrad_b3 || wgrad_h2) {
+                // octet images of a[l - 1] and dz[l], then the MFMA kernel: bf16x3 three planes on the bf16 matrix cores (six products per fp32
+                // product), f16x2 two planes of the scaled dz on the fp16 matrix cores (three products per fp32 product)
                 const int noct = (B + 7) / 8, XR = t->Hout[l] + 2;
-                const int tiles = (Cin[l] / WB_CI) * (Cc / WB_CO);
+                const int tiles = (Cin[l] / (wgrad_b3 ? WB_CI : WH_CI)) * (Cc / (wgrad_b3 ? WB_CO : WH_CO));
                 msplit = 1;
                 while (msplit < 32 && tiles * msplit < 256 && msplit * 2 <= noct && wcount * msplit * 2 <= t->gpartial_floats) msplit *= 2;
                 const long long xthr = (long long)noct * XR * WH_XW * (Cin[l] / 4), zthr = (long long)noct * t->Hout[l] * WH_ZW * (Cc / 4);
-                hipLaunchKernelGGL(k_t_x_octets_b3, dim3((unsigned)((xthr + 255) / 256)), dim3(256), 0, sw, t->a[l - 1], t->d_count, Hin[l], pad[l], Cin[l], t->xt_b3[l]);
-                hipLaunchKernelGGL(k_t_z_octets_b3, dim3((unsigned)((zthr + 255) / 256)), dim3(256), 0, sw, t->dz[l], t->d_count, t->Hout[l], t->Hz[l], t->zoff[l], Cc,
-                                   t->zt_b3[l]);
-                if (!t->wb3_attr) {
-                    OZ_HIP(hipFuncSetAttribute((const void*)k_wgrad_b3, hipFuncAttributeMaxDynamicSharedMemorySize, WB_LDS));
-                    t->wb3_attr = true;
-                }
+                const dim3 xgrid((unsigned)((xthr + 255) / 256)), zgrid((unsigned)((zthr + 255) / 256));
                 WhGeom wg; wg.XR = XR; wg.Hout = t->Hout[l]; wg.Cin = Cin[l]; wg.Cout = Cc;
-                hipLaunchKernelGGL(k_wgrad_b3, dim3(tiles, msplit), dim3(512), WB_LDS, sw, t->xt_b3[l], t->zt_b3[l], t->d_count, wg, t->grad(6 * l), msplit, wp, wcount);
-            } else if (taps[l] == 9 && t->h2 && have_dzmax && l >= 1 && B >= WH_MIN_BATCH && Cin[l] % WH_CI == 0 && Cc % WH_CO == 0) {
-                // f16x2: octet images of a[l - 1] and of the scaled dz[l], then the MFMA kernel on the fp16 matrix cores (three products per fp32 product)
-                const int noct = (B + 7) / 8, XR = t->Hout[l] + 2;
-                const int tiles = (Cin[l] / WH_CI) * (Cc / WH_CO);
-                msplit = 1;
-                while (msplit < 32 && tiles * msplit < 256 && msplit * 2 <= noct && wcount * msplit * 2 <= t->gpartial_floats) msplit *= 2;
-                const long long xthr = (long long)noct * XR * WH_XW * (Cin[l] / 4), zthr = (long long)noct * t->Hout[l] * WH_ZW * (Cc / 4);
-                hipLaunchKernelGGL(k_t_x_octets, dim3((unsigned)((xthr + 255) / 256)), dim3(256), 0, sw, t->a[l - 1], t->d_count, Hin[l], pad[l], Cin[l], t->xt_oct[l]);
-                hipLaunchKernelGGL(k_t_z_octets, dim3((unsigned)((zthr + 255) / 256)), dim3(256), 0, sw, t->dz[l], t->d_count, t->Hout[l], t->Hz[l], t->zoff[l], Cc,
-                                   t->dzmax + l, t->zt_oct[l], t->h2flag);
-                if (!t->wh_attr) {
-                    OZ_HIP(hipFuncSetAttribute((const void*)k_wgrad_h2, hipFuncAttributeMaxDynamicSharedMemorySize, WH_LDS));
-                    t->wh_attr = true;
+                if (wgrad_b3) {
+                    hipLaunchKernelGGL(k_t_x_octets<3>, xgrid, dim3(256), 0, sw, t->a[l - 1], t->d_count, Hin[l], pad[l], Cin[l], t->xt_b3[l]);
+                    hipLaunchKernelGGL(k_t_z_octets<3>, zgrid, dim3(256), 0, sw, t->dz[l], t->d_count, t->Hout[l], t->Hz[l], t->zoff[l], Cc,
+                                       (const unsigned*)nullptr, t->zt_b3[l], (int*)nullptr);
+                    if (!t->wb3_attr) {
+                        OZ_HIP(hipFuncSetAttribute((const void*)k_wgrad_b3, hipFuncAttributeMaxDynamicSharedMemorySize, WB_LDS));
+                        t->wb3_attr = true;
+                    }
+                    hipLaunchKernelGGL(k_wgrad_b3, dim3(tiles, msplit), dim3(512), WB_LDS, sw, t->xt_b3[l], t->zt_b3[l], t->d_count, wg, t->grad(6 * l), msplit, wp, wcount);
+                } else {
+                    hipLaunchKernelGGL(k_t_x_octets<2>, xgrid, dim3(256), 0, sw, t->a[l - 1], t->d_count, Hin[l], pad[l], Cin[l], t->xt_oct[l]);
+                    hipLaunchKernelGGL(k_t_z_octets<2>, zgrid, dim3(256), 0, sw, t->dz[l], t->d_count, t->Hout[l], t->Hz[l], t->zoff[l], Cc,
+                                       t->dzmax + l, t->zt_oct[l], t->h2flag);
+                    if (!t->wh_attr) {
+                        OZ_HIP(hipFuncSetAttribute((const void*)k_wgrad_h2, hipFuncAttributeMaxDynamicSharedMemorySize, WH_LDS));
+                        t->wh_attr = true;
+                    }
+                    hipLaunchKernelGGL(k_wgrad_h2, dim3(tiles, msplit), dim3(512), WH_LDS, sw, t->xt_oct[l], t->zt_oct[l], t->d_count, wg, t->dzmax + l, t->grad(6 * l),
+                                       msplit, wp, wcount);
                 }
-                WhGeom wg; wg.XR = XR; wg.Hout = t->Hout[l]; wg.Cin = Cin[l]; wg.Cout = Cc;
-                hipLaunchKernelGGL(k_wgrad_h2, dim3(tiles, msplit), dim3(512), WH_LDS, sw, t->xt_oct[l], t->zt_oct[l], t->d_count, wg, t->dzmax + l, t->grad(6 * l),
-                                   msplit, wp, wcount);
             } else if (taps[l] == 9 && B >= 192 && Cin[l] % WC_CI == 0 && Cc % WC_CO == 0) {
                 // board-resident kernel: (Cin / 64) x (Cout / 128) tiles, boards split over blockIdx.y until every CU has a block
                 WconvGeom cg; cg.Hin = Hin[l]; cg.Hout = t->Hout[l]; cg.pad = pad[l]; cg.Cin = Cin[l]; cg.Cout = Cc; cg.Hz = t->Hz[l]; cg.zoff = t->zoff[l];
