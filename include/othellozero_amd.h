@@ -248,7 +248,9 @@ typedef struct {
     int32_t batch_cap;      /* free-running driver: leaves per network batch (0 = none), see oz_selfplay_set_batch_cap */
     int32_t eval_cache;     /* 1: leaves whose board is in the network's evaluation cache (oz_net_set_eval_cache) take their (pi, v) from it and
                              * need no batch slot; evaluated leaves are inserted.  0 (default): every leaf is evaluated by the network */
-    int32_t reserved;
+    int32_t record_visits;  /* 1: keep every move's root visit counts N(s, a) next to its record (oz_selfplay_visits) -- the search's
+                             * visit distribution pi, the AlphaZero policy target; 16 KB per slot + 256 B per record of device memory.
+                             * 0 (default): nothing is kept or allocated */
 } oz_selfplay_config;
 #define OZ_DEDUP_DEFAULT 0  /* = on */
 #define OZ_DEDUP_ON 1
@@ -312,6 +314,13 @@ int oz_selfplay_state(oz_selfplay* sp, uint64_t* black, uint64_t* white, int8_t*
 int oz_selfplay_records(oz_selfplay* sp, oz_record* out, int64_t max_records, int64_t* written);
 /* same, device to device, for the RCCL all-gather (dst = device pointer, e.g. a torch tensor) */
 int oz_selfplay_records_device(oz_selfplay* sp, void* dst_device, int64_t max_records, int64_t* written);
+/* root visit counts of every recorded move (oz_selfplay_config.record_visits = 1; OZ_ERR_ARG otherwise): row i belongs to record i of
+ * oz_selfplay_records -- the same ring order, so one permutation sorts both.  A row holds the N(state, action) the move's search left at
+ * its root, visits earlier moves' searches left in the same tree included, at square row*8+col, 0 off the legal set: exactly what
+ * get_policy_action_probabilities (othelo_mcts.py:51-67) reads.  int32, exact.  A row is kept where its record is (record_cap). */
+int oz_selfplay_visits(oz_selfplay* sp, int32_t* out /* [max_records][64] */, int64_t max_records, int64_t* written);
+/* same, device to device */
+int oz_selfplay_visits_device(oz_selfplay* sp, void* dst_device, int64_t max_records, int64_t* written);
 /* root visit counts of the last move round, counts[num_games][64] (parity tests) */
 int oz_selfplay_last_counts(oz_selfplay* sp, int32_t* counts);
 /* HIP-event time of the evaluator (NN) launches since creation, and their count */
@@ -334,6 +343,11 @@ int oz_comm_destroy(oz_comm* comm);
  * (OZ_ERR_ARG), never on one rank alone.  out == NULL and max_records == 0 on every rank: the counts only (*written = the pooled number). */
 int oz_selfplay_gather_records(oz_selfplay* sp, oz_comm* comm, int64_t first_record, oz_record* out, int64_t max_records, int64_t* written,
                                int64_t* per_rank);
+/* COLLECTIVE, the same protocol for the visit-count rows of oz_selfplay_visits (every engine created with record_visits = 1; a rank
+ * without them fails the call on every rank together): the rows come back in the order oz_selfplay_gather_records returns the records
+ * for the same first_record. */
+int oz_selfplay_gather_visits(oz_selfplay* sp, oz_comm* comm, int64_t first_record, int32_t* out /* [max_records][64] */, int64_t max_records,
+                              int64_t* written, int64_t* per_rank);
 
 /* ------------------------------------------------------------------ arena
  * duel_between_agents with two NeuralNetworkOthelloAgent (agents.py:44-84): net_a = BLACK, net_b = WHITE,
@@ -373,6 +387,14 @@ int oz_arena_results(oz_arena* a, int8_t* winner /* +1 net_a */, int32_t* points
 int oz_examples_expand(const oz_record* records, int64_t count, int n, int alias_final, uint8_t* boards,
                        int32_t* policy_index, int8_t* z);
 int oz_symmetry_table(int n, int32_t* perm /* [8][n*n] source index of every output cell */);
+/* the same expansion with the search's visit distribution as the policy target (the AlphaZero pi) instead of the one-hot of the move:
+ * counts[count][64] = the rows of oz_selfplay_visits.  pi[count*8][n*n] float64 = get_policy_action_probabilities(root, temperature)
+ * (othelo_mcts.py:51-67) of the record's root, then the record's 8 symmetries in training_example_symmetries' order (the identity is
+ * example 7): N ** (1 / temperature) on the legal squares divided by np.sum of the (n, n) array in NumPy's pairwise order, or by 1 if
+ * that is 0.  Bit-exact against that formula on the host whenever 1 / temperature is an integer; otherwise within 1 ulp of the
+ * device's pow per element.  temperature <= 0: OZ_ERR_ARG.  boards and z as in oz_examples_expand. */
+int oz_examples_expand_visits(const oz_record* records, const int32_t* counts, int64_t count, int n, int alias_final, double temperature,
+                              uint8_t* boards, double* pi, int8_t* z);
 
 /* ------------------------------------------------------------------ training step
  * NNetWrapper.train (Net/NNet.py:53-68) = keras Model.fit on Net/OthelloNN.py:42-56 / Net/BaseNN.py:41-57:
@@ -396,6 +418,14 @@ int oz_trainer_destroy(oz_trainer* t);
  * no range flag, nothing to refuse.  conv1, the dense layers, BN, losses and Adam stay fp32.  Modes 1 and 2 need channels % 256 == 0 and
  * allocate their buffers at first use; a trainer may switch among the modes between steps. */
 int oz_trainer_set_precision(oz_trainer* t, int mode);
+/* the policy loss.  OZ_POLICY_LOSS_ROWS (default): the reference's categorical_crossentropy on the (n, n)-reshaped softmax, i.e. every
+ * board row renormalised on its own and the loss averaged over rows -- trains only ratios within a row.  OZ_POLICY_LOSS_FLAT: keras'
+ * categorical_crossentropy on the (B, n*n) softmax -- q = p / sum(p), clipped to [1e-7, 1 - 1e-7], -sum_i t_i log q_i, batch mean: the
+ * loss for dense visit-distribution targets (oz_examples_expand_visits).  Every precision, the step-wise and the resident paths;
+ * losses3[1] reports the loss of the mode. */
+#define OZ_POLICY_LOSS_ROWS 0
+#define OZ_POLICY_LOSS_FLAT 1
+int oz_trainer_set_policy_loss(oz_trainer* t, int mode);
 int oz_trainer_set_weight(oz_trainer* t, int index, const float* data, int64_t nelem);
 int oz_trainer_get_weight(oz_trainer* t, int index, float* data, int64_t nelem);
 int oz_trainer_get_grad(oz_trainer* t, int index, float* data, int64_t nelem);      /* trainable arrays only */

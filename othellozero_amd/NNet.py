@@ -40,7 +40,8 @@ class NNetWrapper(_NetHandle):
     _models_built = 0          # Keras numbers layer names per process (conv2d, ..., conv2d_4, ...); checkpoints keep that
 
     def __init__(self, board_size=(8, 8), batch_size=32, epochs=10, num_channels_1=512, num_channels_2=256,
-                 lr=0.001, dropout=0.3, network=NeuralNets.ONN, max_batch=1, seed=0, weights=None, precision="f32", train_precision=None):
+                 lr=0.001, dropout=0.3, network=NeuralNets.ONN, max_batch=1, seed=0, weights=None, precision="f32", train_precision=None,
+                 policy_loss="rows"):
         super().__init__()
         self._model_index = NNetWrapper._models_built
         NNetWrapper._models_built += 1
@@ -67,6 +68,10 @@ class NNetWrapper(_NetHandle):
         # num_channels_1 % 256 == 0, else f32
         assert train_precision in (None, "f32", "f16x2", "bf16x3"), train_precision
         self.train_precision = train_precision
+        # policy_loss: "rows" = the reference's cross entropy on the (n, n)-reshaped policy (rows renormalised one by one); "flat" = on the
+        # whole n*n softmax, what dense visit-distribution targets need (loop.training(policy_target="visits"))
+        assert policy_loss in ("rows", "flat"), policy_loss
+        self.policy_loss = policy_loss
         self.requested_precision = precision          # what the caller asked for: a refused f16x2 commit falls back for THAT set of weights only
         self.f16x2_refusals = 0                       # commits precision f16x2 refused so far (train() reports it in its history)
         _lib.check(lib.oz_net_set_precision(self._h, PRECISION_MODES[precision]))
@@ -166,7 +171,7 @@ class NNetWrapper(_NetHandle):
                                       clipvalue=0.5 if self.network_type is NeuralNets.ONN else 0.0, dropout=self.dropout,
                                       seed=self._model_index if seed is None else seed,
                                       external_grads_ptr=getattr(allreduce, "ptr", None),
-                                      precision=self._train_arithmetic())
+                                      precision=self._train_arithmetic(), policy_loss=self.policy_loss)
             self._trainer_arena = getattr(allreduce, "ptr", None)
             self._fit_calls = 0
         assert getattr(allreduce, "ptr", None) == self._trainer_arena, "train() must keep using the GradientAllReduce it started with"
@@ -229,7 +234,7 @@ class NNetWrapper(_NetHandle):
     def copy(self):
         return NNetWrapper((self.board_size_x, self.board_size_y), network=self.network_type,
                            num_channels_1=self.num_channels, max_batch=self.max_batch, weights=self.get_weights(),
-                           precision=self.precision, train_precision=self.train_precision)
+                           precision=self.precision, train_precision=self.train_precision, policy_loss=self.policy_loss)
 
     # ---- profiling hooks used by bench.py
     def time_forward(self, count, iters=3):

@@ -22,6 +22,7 @@ NET_OPT_B3_TILE = 10
 NET_INFO_CONV3_TILE_ROWS, NET_INFO_SELF_CHECK_GUARD, NET_INFO_ARITHMETIC = 1, 2, 3                                                          # oz_net_get_info
 LEAF_IDLE, LEAF_TERMINAL, LEAF_EVAL = 0, 1, 2
 VT_INT, VT_F32, VT_F64 = 0, 1, 2
+POLICY_LOSS_ROWS, POLICY_LOSS_FLAT = 0, 1                                            # oz_trainer_set_policy_loss
 NET_KERNELS = ("input", "conv2", "conv3", "conv4", "fc1", "fc2", "heads")           # OZ_NET_KERNELS slots
 TREE_KERNELS = ("select", "compact", "network", "expand_backup", "roots_move")       # OZ_TREE_KERNELS slots
 
@@ -42,7 +43,7 @@ class SelfplayConfig(C.Structure):
         ("c", C.c_double), ("temperature", C.c_double), ("e_greedy", C.c_double),
         ("seed", C.c_uint64), ("first_game_id", C.c_uint64), ("game_id_stride", C.c_uint64),
         ("refill", C.c_int32), ("node_cap", C.c_int32), ("reserved0", C.c_int32), ("record_cap", C.c_int32),
-        ("dedup", C.c_int32), ("batch_cap", C.c_int32), ("eval_cache", C.c_int32), ("reserved", C.c_int32),
+        ("dedup", C.c_int32), ("batch_cap", C.c_int32), ("eval_cache", C.c_int32), ("record_visits", C.c_int32),
     ]
 
 
@@ -113,15 +114,19 @@ SIGNATURES = {
     "oz_selfplay_state": [_vp, _u64p, _u64p, _i8p, _u8p, _i32p, _u64p],
     "oz_selfplay_records": [_vp, _vp, C.c_int64, _i64p],
     "oz_selfplay_records_device": [_vp, _vp, C.c_int64, _i64p],
+    "oz_selfplay_visits": [_vp, _i32p, C.c_int64, _i64p],
+    "oz_selfplay_visits_device": [_vp, _vp, C.c_int64, _i64p],
     "oz_selfplay_last_counts": [_vp, _i32p],
     "oz_selfplay_eval_time": [_vp, _f64p, _i64p, _i64p],
     "oz_comm_unique_id": [_u8p], "oz_comm_create": [C.POINTER(_vp), _u8p, C.c_int, C.c_int], "oz_comm_destroy": [_vp],
     "oz_selfplay_gather_records": [_vp, _vp, C.c_int64, _vp, C.c_int64, _i64p, _i64p],
+    "oz_selfplay_gather_visits": [_vp, _vp, C.c_int64, _i32p, C.c_int64, _i64p, _i64p],
     "oz_arena_create": [C.POINTER(_vp), C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_uint64, C.c_uint64, _vp, _vp, C.c_int],
     "oz_arena_destroy": [_vp], "oz_arena_run": [_vp], "oz_arena_run_rounds": [_vp, C.c_int], "oz_arena_stats": [_vp, _i64p, _i64p],
     "oz_arena_set_dedup": [_vp, C.c_int], "oz_arena_set_eval_cache": [_vp, C.c_int], "oz_arena_profile": [_vp, C.c_int], "oz_arena_profile_read": [_vp, _f64p, _i64p, C.c_int], "oz_arena_leaves_evaluated": [_vp, _i64p, _i64p],
     "oz_arena_results": [_vp, _i8p, _i32p, _i32p, _u8p, _i8p, _u64p, _u64p],
     "oz_examples_expand": [_vp, C.c_int64, C.c_int, C.c_int, _u8p, _i32p, _i8p],
+    "oz_examples_expand_visits": [_vp, _i32p, C.c_int64, C.c_int, C.c_int, C.c_double, _u8p, _f64p, _i8p],
     "oz_symmetry_table": [C.c_int, _i32p],
     "oz_selftest_arith": [_f64p, _f64p, C.c_int, _f64p, _f64p, _f32p, _f32p],
     "oz_selftest_mfma_rate": [C.c_int, C.c_double, _f64p, _f64p, _f64p],
@@ -142,6 +147,7 @@ SIGNATURES = {
     "oz_trainer_get_activation": [_vp, C.c_int, C.c_int, _f32p, C.c_int64],
     "oz_trainer_sync": [_vp],
     "oz_trainer_set_precision": [_vp, C.c_int],
+    "oz_trainer_set_policy_loss": [_vp, C.c_int],
     "oz_trainer_step_count": [_vp, C.POINTER(C.c_int64)],
 }
 

@@ -139,6 +139,19 @@ OZ_HD int oz_kth_bit(uint64_t m, int k) {
     return oz_ctz(m);
 }
 
+// NumPy pairwise sum of a contiguous float64 vector, 8 <= len <= 128 (np.sum at MCTS/__init__.py:49-51)
+__host__ __device__ inline double pairwise_sum(const double* a, int len) {
+    double r0 = a[0], r1 = a[1], r2 = a[2], r3 = a[3], r4 = a[4], r5 = a[5], r6 = a[6], r7 = a[7];
+    int i;
+    for (i = 8; i < len - (len % 8); i += 8) {
+        r0 += a[i]; r1 += a[i + 1]; r2 += a[i + 2]; r3 += a[i + 3];
+        r4 += a[i + 4]; r5 += a[i + 5]; r6 += a[i + 6]; r7 += a[i + 7];
+    }
+    double res = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
+    for (; i < len; ++i) res += a[i];
+    return res;
+}
+
 // ---------------------------------------------------------------- error plumbing (host)
 #include <stdio.h>
 void oz_set_error(const char* fmt, ...);

@@ -17,7 +17,8 @@ void oz_set_error(const char* fmt, ...) {
     va_end(ap);
 }
 OZ_API const char* oz_last_error(void) { return g_err; }
-OZ_API int oz_version(void) { return 200; }     // 200 (round 4): edge_cap left oz_mcts_create / oz_arena_create / oz_selfplay_config
+OZ_API int oz_version(void) { return 201; }     // 201: visit-count policy targets (record_visits, oz_examples_expand_visits, flat policy loss)
+                                                // 200 (round 4): edge_cap left oz_mcts_create / oz_arena_create / oz_selfplay_config
 OZ_API int oz_device_count(void) {
     int c = 0;
     if (hipGetDeviceCount(&c) != hipSuccess) return 0;
@@ -251,6 +252,77 @@ OZ_API int oz_examples_expand(const oz_record* records, int64_t count, int n, in
     OZ_HIP(hipGetLastError());
     OZ_HIP(hipMemcpy(boards, b.p, cells * 2, hipMemcpyDeviceToHost));
     OZ_HIP(hipMemcpy(policy_index, p.p, 4 * nex, hipMemcpyDeviceToHost));
+    OZ_HIP(hipMemcpy(z, zz.p, nex, hipMemcpyDeviceToHost));
+    return OZ_OK;
+}
+
+// N ** (1 / T) of get_policy_action_probabilities (othelo_mcts.py:59-60) for a visit count.  k = 1 / T where that is an integer (else 0):
+// the product of k factors is exact while it stays <= 2^53 (every partial product is then an integer below it), so it equals the
+// correctly rounded power the host computes; beyond that, and for any other exponent, the device's pow.
+__device__ __forceinline__ double oz_count_pow(int cnt, double inv, int k) {
+    const double x = (double)cnt;
+    if (k > 0) {
+        double r = x;
+        for (int i = 1; i < k; ++i) r *= x;
+        if (r <= 9007199254740992.0) return r;
+    }
+    return pow(x, inv);
+}
+
+// one 64-lane block per record, lane = cell r*n+c of the record's own (n, n) view: pi of the root (pairwise np.sum by lane 0, as on the
+// host), then for each of the 8 symmetries the output cell `lane` takes its source cell's value -- boards, pi and z of the 8 examples
+__global__ __launch_bounds__(64) void k_expand_visits(const oz_record* __restrict__ recs, const int32_t* __restrict__ counts, int n, int alias_final,
+                                                      double inv, int k, uint8_t* __restrict__ boards, double* __restrict__ pi, int8_t* __restrict__ z) {
+    __shared__ double arr[64];
+    __shared__ double divisor;
+    const int64_t rix = blockIdx.x;
+    const int lane = threadIdx.x, n2 = n * n;
+    const int r = lane / n, c = lane % n;
+    arr[lane] = lane < n2 ? oz_count_pow(counts[rix * 64 + r * 8 + c], inv, k) : 0.0;     // counts are 0 off the legal set
+    __syncthreads();
+    if (lane == 0) {
+        const double sum = pairwise_sum(arr, n2);
+        divisor = sum == 0 ? 1.0 : sum;
+    }
+    __syncthreads();
+    const double q = arr[lane] / divisor;
+    __syncthreads();
+    arr[lane] = q;
+    __syncthreads();
+    if (lane >= n2) return;
+    const oz_record rec = recs[rix];
+    const uint64_t b = alias_final ? rec.final_black : rec.black, w = alias_final ? rec.final_white : rec.white;
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+        const int64_t ex = rix * 8 + t;
+        const int src = oz_sym_src(t, n, r, c), sq = (src / n) * 8 + src % n;
+        pi[ex * n2 + lane] = arr[src];
+        uchar2 o;
+        o.x = (uint8_t)((b >> sq) & 1); o.y = (uint8_t)((w >> sq) & 1);
+        reinterpret_cast<uchar2*>(boards)[ex * n2 + lane] = o;
+        if (lane == 0) z[ex] = rec.z;
+    }
+}
+
+OZ_API int oz_examples_expand_visits(const oz_record* records, const int32_t* counts, int64_t count, int n, int alias_final, double temperature,
+                                     uint8_t* boards, double* pi, int8_t* z) {
+    if (int rc = check_n(n)) return rc;
+    OZ_REQUIRE(temperature > 0, "oz_examples_expand_visits: temperature %g (the visit distribution needs T > 0)", temperature);
+    if (count <= 0) return OZ_OK;
+    OZ_REQUIRE(records && counts && boards && pi && z, "null argument");
+    OZ_REQUIRE(count < (1ll << 31), "too many records in one call");
+    oz_current_device();
+    const int64_t nex = count * 8, cells = nex * n * n;
+    DevBuf<oz_record> r; DevBuf<int32_t> cn; DevBuf<uint8_t> b; DevBuf<double> p; DevBuf<int8_t> zz;
+    OZ_HIP(r.alloc(count)); OZ_HIP(cn.alloc(count * 64)); OZ_HIP(b.alloc(cells * 2)); OZ_HIP(p.alloc(cells)); OZ_HIP(zz.alloc(nex));
+    OZ_HIP(hipMemcpy(r.p, records, sizeof(oz_record) * count, hipMemcpyHostToDevice));
+    OZ_HIP(hipMemcpy(cn.p, counts, sizeof(int32_t) * 64 * count, hipMemcpyHostToDevice));
+    const double inv = 1.0 / temperature;
+    const int k = (inv == floor(inv) && inv <= 64.0) ? (int)inv : 0;
+    hipLaunchKernelGGL(k_expand_visits, dim3((unsigned)count), dim3(64), 0, 0, r.p, cn.p, n, alias_final, inv, k, b.p, p.p, zz.p);
+    OZ_HIP(hipGetLastError());
+    OZ_HIP(hipMemcpy(boards, b.p, cells * 2, hipMemcpyDeviceToHost));
+    OZ_HIP(hipMemcpy(pi, p.p, sizeof(double) * cells, hipMemcpyDeviceToHost));
     OZ_HIP(hipMemcpy(z, zz.p, nex, hipMemcpyDeviceToHost));
     return OZ_OK;
 }

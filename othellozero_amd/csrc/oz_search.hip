@@ -173,19 +173,6 @@ __device__ __forceinline__ uint32_t ht_entry(uint64_t own, uint64_t opp, int nod
     return ((uint32_t)(key_hash64(own, opp) >> 52) << OZ_HT_IDX_BITS) | (uint32_t)(node + 1);
 }
 
-// NumPy pairwise sum of a contiguous float64 vector, 8 <= len <= 128 (np.sum at MCTS/__init__.py:49-51)
-__host__ __device__ inline double pairwise_sum(const double* a, int len) {
-    double r0 = a[0], r1 = a[1], r2 = a[2], r3 = a[3], r4 = a[4], r5 = a[5], r6 = a[6], r7 = a[7];
-    int i;
-    for (i = 8; i < len - (len % 8); i += 8) {
-        r0 += a[i]; r1 += a[i + 1]; r2 += a[i + 2]; r3 += a[i + 3];
-        r4 += a[i + 4]; r5 += a[i + 5]; r6 += a[i + 6]; r7 += a[i + 7];
-    }
-    double res = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
-    for (; i < len; ++i) res += a[i];
-    return res;
-}
-
 // ---------------------------------------------------------------- K4: select / descend
 // MCTS.simulate down to the first terminal or unexpanded state (MCTS/__init__.py:39-44,58-67),
 // get_next_state (othelo_mcts.py:43-49).  One wave per game; per level ONE wave-wide load stages the node's record in LDS.
@@ -1007,8 +994,12 @@ struct GamesDev {
     int8_t* log_player;                   // [G][64]
     int32_t* last_counts;                 // [G][64]
     oz_record* records;
+    // oz_selfplay_config.record_visits: root visit counts of every move of the game in progress, and of every record (same ring index)
+    int32_t* log_counts;                  // [G][64 plies][64 squares], or null
+    int32_t* visits;                      // [record_cap][64], or null
     unsigned long long* counters;         // [0] records [1] games completed [2] moves
     long long record_cap;
+    int record_visits;
     uint64_t seed, id_stride;
     double temperature, e_greedy;
     int refill, init_black_set;
@@ -1060,6 +1051,7 @@ __device__ __forceinline__ void sp_move_body(const GamesDev& gm, const MctsDev& 
     if (is_legal) cnt = (int)(rec_edge(t, g, node, oz_popc(legal & ((1ULL << lane) - 1ULL)))->n_tag & ~OZ_TAG_F32);
     gm.last_counts[(size_t)g * 64 + lane] = cnt;
     const int ply = unii(gm.ply[g]);
+    const size_t lb = (size_t)g * 64;
     const uint64_t gid = uni64(gm.game_id[g]);
     const int mx = unii(wave_max_i32(cnt));                      // >= 1 once the root has been selected from
     int action, greedy = 1;
@@ -1081,7 +1073,6 @@ __device__ __forceinline__ void sp_move_body(const GamesDev& gm, const MctsDev& 
     }
     uint64_t black = uni64(gm.black[g]), white = uni64(gm.white[g]);
     int player = unii(gm.player[g]), fin = 0;
-    const size_t lb = (size_t)g * 64;
     if (lane == 0 && ply < 64) {
         gm.log_black[lb + ply] = black; gm.log_white[lb + ply] = white;
         gm.log_action[lb + ply] = (uint8_t)action; gm.log_player[lb + ply] = (int8_t)player;
@@ -1113,6 +1104,15 @@ __device__ __forceinline__ void sp_move_body(const GamesDev& gm, const MctsDev& 
                 gm.records[base + lane] = r;
             } else atomicOr(t.error_flag, EF_RECORDS);
         }
+        if (gm.record_visits) {
+            // row i of the game's counts next to record i, one coalesced 256-byte row per ply; a row is written where its record is
+            // (the loop above has flagged EF_RECORDS for the rest).  This ply's row is still in registers.
+            const long long room = gm.record_cap - (long long)base;
+            for (int i = 0; i < nply && i < room; ++i)
+                gm.visits[(size_t)(base + i) * 64 + lane] = i == ply ? cnt : gm.log_counts[(lb + i) * 64 + lane];
+        }
+    } else if (gm.record_visits && ply < 64) {
+        gm.log_counts[(lb + ply) * 64 + lane] = cnt;
     }
     if (lane == 0) atomicAdd(&gm.counters[2], 1ULL);
     if (fin && gm.refill) {
@@ -1243,16 +1243,17 @@ struct oz_selfplay {
     }
 };
 
-static int games_alloc(oz_selfplay* sp, int G, int n, long long record_cap) {
+static int games_alloc(oz_selfplay* sp, int G, int n, long long record_cap, int record_visits) {
     GamesDev& gm = sp->gm;
     memset(&gm, 0, sizeof gm);
-    gm.G = G; gm.n = n; gm.valid = oz_valid_mask(n); gm.record_cap = record_cap;
+    gm.G = G; gm.n = n; gm.valid = oz_valid_mask(n); gm.record_cap = record_cap; gm.record_visits = record_visits;
     int rc = OZ_OK;
 #define A(ptr, cnt) if (!rc) rc = sp->alloc(&gm.ptr, cnt)
     A(black, G); A(white, G); A(game_id, G); A(player, G); A(finished, G); A(ply, G);
     A(log_black, (size_t)G * 64); A(log_white, (size_t)G * 64); A(log_action, (size_t)G * 64);
     A(log_greedy, (size_t)G * 64); A(log_player, (size_t)G * 64); A(last_counts, (size_t)G * 64);
     A(records, (size_t)record_cap); A(counters, 4);
+    if (record_visits) { A(log_counts, (size_t)G * 64 * 64); A(visits, (size_t)record_cap * 64); }      // 16 KB per slot, 256 B per record
 #undef A
     return rc;
 }
@@ -1287,13 +1288,14 @@ OZ_API int oz_selfplay_create(oz_selfplay** out, const oz_selfplay_config* cfg, 
     OZ_REQUIRE(cfg->dedup == OZ_DEDUP_DEFAULT || cfg->dedup == OZ_DEDUP_ON || cfg->dedup == OZ_DEDUP_OFF, "oz_selfplay_config.dedup = %d", cfg->dedup);
     OZ_REQUIRE(cfg->eval_cache == 0 || cfg->eval_cache == 1, "oz_selfplay_config.eval_cache = %d", cfg->eval_cache);
     OZ_REQUIRE(cfg->batch_cap == 0 || cfg->batch_cap >= 8, "oz_selfplay_config.batch_cap = %d (0 = none, else >= 8 leaves)", cfg->batch_cap);
+    OZ_REQUIRE(cfg->record_visits == 0 || cfg->record_visits == 1, "oz_selfplay_config.record_visits = %d", cfg->record_visits);
     oz_selfplay* sp = new oz_selfplay();
     sp->cfg = *cfg; sp->net = net;
     const int max_plies = cfg->n * cfg->n - 4;
     const int node_cap = cfg->node_cap > 0 ? cfg->node_cap : cfg->sims * (max_plies + 1) + 64;
     const long long rcap = cfg->record_cap > 0 ? cfg->record_cap : (long long)cfg->num_games * 64 * 4;
     int rc = mcts_create(&sp->m, cfg->n, cfg->num_games, node_cap, cfg->c, cfg->q_mode);
-    if (!rc) rc = games_alloc(sp, cfg->num_games, cfg->n, rcap);
+    if (!rc) rc = games_alloc(sp, cfg->num_games, cfg->n, rcap, cfg->record_visits);
     if (!rc) sp->m->d.dedup = cfg->dedup == OZ_DEDUP_OFF ? 0 : 1;
     if (!rc) sp->batch_cap = cfg->batch_cap;
     if (!rc) rc = sp->alloc(&sp->d_sims_done, cfg->num_games);
@@ -1513,7 +1515,8 @@ OZ_API int oz_selfplay_state(oz_selfplay* sp, uint64_t* black, uint64_t* white, 
     return OZ_OK;
 }
 
-static int selfplay_records(oz_selfplay* sp, void* dst, int64_t max_records, int64_t* written, hipMemcpyKind kind) {
+// rows of `src` (`width` bytes each, ring index = record index): the records or the visit-count rows
+static int selfplay_rows(oz_selfplay* sp, const void* src, size_t width, void* dst, int64_t max_records, int64_t* written, hipMemcpyKind kind) {
     OZ_REQUIRE(sp && written, "null argument");
     std::lock_guard<std::mutex> lk(sp->mu);
     hipSetDevice(sp->m->device);
@@ -1525,16 +1528,29 @@ static int selfplay_records(oz_selfplay* sp, void* dst, int64_t max_records, int
     if (n > max_records) n = max_records;
     if (n > 0) {
         OZ_REQUIRE(dst, "null destination");
-        OZ_HIP(hipMemcpy(dst, sp->gm.records, sizeof(oz_record) * (size_t)n, kind));
+        OZ_HIP(hipMemcpy(dst, src, width * (size_t)n, kind));
     }
     *written = n;
     return OZ_OK;
 }
 OZ_API int oz_selfplay_records(oz_selfplay* sp, oz_record* out, int64_t max_records, int64_t* written) {
-    return selfplay_records(sp, out, max_records, written, hipMemcpyDeviceToHost);
+    OZ_REQUIRE(sp, "null selfplay");
+    return selfplay_rows(sp, sp->gm.records, sizeof(oz_record), out, max_records, written, hipMemcpyDeviceToHost);
 }
 OZ_API int oz_selfplay_records_device(oz_selfplay* sp, void* dst_device, int64_t max_records, int64_t* written) {
-    return selfplay_records(sp, dst_device, max_records, written, hipMemcpyDeviceToDevice);
+    OZ_REQUIRE(sp, "null selfplay");
+    return selfplay_rows(sp, sp->gm.records, sizeof(oz_record), dst_device, max_records, written, hipMemcpyDeviceToDevice);
+}
+#define OZ_REQUIRE_VISITS(sp) OZ_REQUIRE((sp)->gm.record_visits, "this engine does not record visit counts: create it with oz_selfplay_config.record_visits = 1")
+OZ_API int oz_selfplay_visits(oz_selfplay* sp, int32_t* out, int64_t max_records, int64_t* written) {
+    OZ_REQUIRE(sp, "null selfplay");
+    OZ_REQUIRE_VISITS(sp);
+    return selfplay_rows(sp, sp->gm.visits, 64 * sizeof(int32_t), out, max_records, written, hipMemcpyDeviceToHost);
+}
+OZ_API int oz_selfplay_visits_device(oz_selfplay* sp, void* dst_device, int64_t max_records, int64_t* written) {
+    OZ_REQUIRE(sp, "null selfplay");
+    OZ_REQUIRE_VISITS(sp);
+    return selfplay_rows(sp, sp->gm.visits, 64 * sizeof(int32_t), dst_device, max_records, written, hipMemcpyDeviceToDevice);
 }
 
 OZ_API int oz_selfplay_last_counts(oz_selfplay* sp, int32_t* counts) {
@@ -1614,7 +1630,7 @@ OZ_API int oz_arena_create(oz_arena** out, int n, int num_games, int sims, doubl
     sp->cfg.n = n; sp->cfg.num_games = num_games; sp->cfg.sims = sims; sp->cfg.c = c; sp->cfg.q_mode = q_mode; sp->cfg.seed = seed;
     int rc = mcts_create(&sp->m, n, num_games, ncap, c, q_mode);
     if (!rc) rc = mcts_create(&a->mb, n, num_games, ncap, c, q_mode);
-    if (!rc) rc = games_alloc(sp, num_games, n, (long long)num_games * 64);
+    if (!rc) rc = games_alloc(sp, num_games, n, (long long)num_games * 64, 0);      // the arena keeps no visit counts
     if (!rc) {
         sp->gm.seed = seed; sp->gm.id_stride = 0; sp->gm.temperature = 0; sp->gm.e_greedy = 1.0; sp->gm.refill = 0;
         rc = games_init(sp, first_game_id, sp->m->stream);
@@ -1868,7 +1884,7 @@ struct oz_comm {
     hipStream_t stream = nullptr;
     long long* d_counts = nullptr;        // [2 + 2 * world]: this rank's (count, room), then every rank's pair
     unsigned char *d_send = nullptr, *d_recv = nullptr;
-    long long cap = 0;                    // records per rank the two buffers hold
+    long long cap = 0;                    // bytes per rank the two buffers hold
     std::mutex mu;
 };
 
@@ -1913,7 +1929,7 @@ OZ_API int oz_comm_destroy(oz_comm* c) {
 
 // COLLECTIVE: every rank of `comm` calls it with its own engine.  The records [first_record, records completed so far) of every rank's
 // engine, concatenated in rank order, into `out` (host, caller-owned, max_records long; per_rank[world] gets every rank's count).
-// A (count, room) pair all-gather (16 bytes per rank) + ONE padded all-gather of 48-byte records, device to device out of the engines' HBM
+// A (count, room) pair all-gather (16 bytes per rank) + ONE padded all-gather of the rows, device to device out of the engines' HBM
 // buffers.  Every decision that could end the call on one rank is taken from the GATHERED pairs, i.e. identically on every rank (a
 // rank-local capacity check let one rank leave while its peers entered the payload all-gather; ADVICE r4: so did a rank-local argument or HIP
 // error BEFORE the first all-gather): a rank whose own arguments are bad (first_record < 0, a null buffer with room, the communicator on
@@ -1922,14 +1938,21 @@ OZ_API int oz_comm_destroy(oz_comm* c) {
 // moves; a failed buffer allocation is agreed on by one more 8-byte all-gather.  What stays rank-local: null sp / comm / written (there is no
 // communicator to say so with) and an RCCL / HIP failure of the collectives themselves (the communicator is then broken for everybody).
 // out == NULL with max_records == 0 on every rank = the counts only (*written = the pooled number, per_rank filled): size the buffer, call again.
-OZ_API int oz_selfplay_gather_records(oz_selfplay* sp, oz_comm* c, int64_t first_record, oz_record* out, int64_t max_records, int64_t* written,
-                                      int64_t* per_rank) {
+// The protocol is the same for any per-record payload: gather_rows moves `width`-byte rows of the engine buffer `src` (ring index = record
+// index), so the records and the visit-count rows of oz_selfplay_gather_visits come back in the same order for the same first_record.
+// visits != 0: the rows are the visit counts, which an engine without record_visits does not have -- a local argument error like the others.
+static int gather_rows(oz_selfplay* sp, oz_comm* c, int visits, int64_t first_record, void* out_, int64_t max_records, int64_t* written,
+                       int64_t* per_rank, const char* fn) {
     OZ_REQUIRE(sp && c && written, "null argument");
     std::lock_guard<std::mutex> lk(sp->mu);
     std::lock_guard<std::mutex> lkc(c->mu);
     hipSetDevice(c->device);
+    unsigned char* out = (unsigned char*)out_;
+    const size_t width = visits ? 64 * sizeof(int32_t) : sizeof(oz_record);
+    const unsigned char* src = visits ? (const unsigned char*)sp->gm.visits : (const unsigned char*)sp->gm.records;
     char local_bad[256] = "";
-    if (first_record < 0) snprintf(local_bad, sizeof local_bad, "first_record %lld", (long long)first_record);
+    if (visits && !sp->gm.record_visits) snprintf(local_bad, sizeof local_bad, "the engine does not record visit counts (oz_selfplay_config.record_visits = 0)");
+    else if (first_record < 0) snprintf(local_bad, sizeof local_bad, "first_record %lld", (long long)first_record);
     else if (!out && max_records != 0) snprintf(local_bad, sizeof local_bad, "null output buffer with room for %lld records", (long long)max_records);
     else if (c->device != sp->m->device) snprintf(local_bad, sizeof local_bad, "the communicator lives on device %d, the engine on device %d", c->device, sp->m->device);
     unsigned long long total = 0;
@@ -1950,9 +1973,9 @@ OZ_API int oz_selfplay_gather_records(oz_selfplay* sp, oz_comm* c, int64_t first
     OZ_HIP(hipMemcpyAsync(pairs.data(), c->d_counts + 2, sizeof(long long) * 2 * W, hipMemcpyDeviceToHost, c->stream));
     OZ_HIP(hipStreamSynchronize(c->stream));
     *written = 0;
-    if (local_bad[0]) { oz_set_error("oz_selfplay_gather_records: %s (every rank fails together)", local_bad); return OZ_ERR_ARG; }
+    if (local_bad[0]) { oz_set_error("%s: %s (every rank fails together)", fn, local_bad); return OZ_ERR_ARG; }
     for (int r = 0; r < W; ++r)
-        if (pairs[2 * r + 1] == -2) { oz_set_error("oz_selfplay_gather_records: rank %d could not take part (bad arguments or a local error there): every rank fails together", r); return OZ_ERR_STATE; }
+        if (pairs[2 * r + 1] == -2) { oz_set_error("%s: rank %d could not take part (bad arguments or a local error there): every rank fails together", fn, r); return OZ_ERR_STATE; }
     long long mx = 0, sum = 0;
     int counts_only = 0, short_rank = -1;
     for (int r = 0; r < W; ++r) {
@@ -1963,16 +1986,16 @@ OZ_API int oz_selfplay_gather_records(oz_selfplay* sp, oz_comm* c, int64_t first
     }
     for (int r = 0; r < W && short_rank < 0; ++r) if (pairs[2 * r + 1] >= 0 && pairs[2 * r + 1] < sum) short_rank = r;
     if (counts_only == W) { *written = sum; return OZ_OK; }
-    OZ_REQUIRE(counts_only == 0, "oz_selfplay_gather_records: %d of %d ranks asked for the counts only (out == NULL), the others for the records", counts_only, W);
-    OZ_REQUIRE(short_rank < 0, "oz_selfplay_gather_records: %lld pooled records, rank %d has room for %lld (every rank fails together)", sum, short_rank,
+    OZ_REQUIRE(counts_only == 0, "%s: %d of %d ranks asked for the counts only (out == NULL), the others for the rows", fn, counts_only, W);
+    OZ_REQUIRE(short_rank < 0, "%s: %lld pooled records, rank %d has room for %lld (every rank fails together)", fn, sum, short_rank,
                pairs[2 * short_rank + 1]);
     if (mx == 0) return OZ_OK;
-    if (mx > c->cap) {                                        // grow the padded send / receive buffers (kept with the communicator); every rank's cap
-        hipFree(c->d_send); hipFree(c->d_recv);               // has followed the same mx history, so all of them are here together
+    if (mx * (long long)width > c->cap) {                     // grow the padded send / receive buffers (kept with the communicator); every rank's cap
+        hipFree(c->d_send); hipFree(c->d_recv);               // has followed the same (mx, width) history, so all of them are here together
         c->d_send = c->d_recv = nullptr; c->cap = 0;
-        const long long cap = mx + mx / 4 + 1024;
-        long long failed = hipMalloc((void**)&c->d_send, (size_t)cap * sizeof(oz_record)) != hipSuccess ||
-                           hipMalloc((void**)&c->d_recv, (size_t)cap * sizeof(oz_record) * W) != hipSuccess;
+        const long long cap = (mx + mx / 4 + 1024) * (long long)width;
+        long long failed = hipMalloc((void**)&c->d_send, (size_t)cap) != hipSuccess ||
+                           hipMalloc((void**)&c->d_recv, (size_t)cap * W) != hipSuccess;
         if (!failed) c->cap = cap;
         else { hipFree(c->d_send); hipFree(c->d_recv); c->d_send = c->d_recv = nullptr; (void)hipGetLastError(); }
         OZ_HIP(hipMemcpyAsync(c->d_counts, &failed, sizeof failed, hipMemcpyHostToDevice, c->stream));
@@ -1981,21 +2004,29 @@ OZ_API int oz_selfplay_gather_records(oz_selfplay* sp, oz_comm* c, int64_t first
         OZ_HIP(hipMemcpyAsync(st.data(), c->d_counts + 2, sizeof(long long) * W, hipMemcpyDeviceToHost, c->stream));
         OZ_HIP(hipStreamSynchronize(c->stream));
         for (int r = 0; r < W; ++r)
-            if (st[r]) { oz_set_error("oz_selfplay_gather_records: rank %d could not allocate its exchange buffers (%lld records x %d ranks)", r, cap, W); return OZ_ERR_HIP; }
+            if (st[r]) { oz_set_error("%s: rank %d could not allocate its exchange buffers (%lld bytes x %d ranks)", fn, r, cap, W); return OZ_ERR_HIP; }
     }
-    if (mine) OZ_HIP(hipMemcpyAsync(c->d_send, sp->gm.records + first_record, (size_t)mine * sizeof(oz_record), hipMemcpyDeviceToDevice, c->stream));
-    if (mine < mx) OZ_HIP(hipMemsetAsync(c->d_send + (size_t)mine * sizeof(oz_record), 0, (size_t)(mx - mine) * sizeof(oz_record), c->stream));
-    OZ_NCCL(g_rccl.AllGather(c->d_send, c->d_recv, (size_t)mx * sizeof(oz_record), OZ_NCCL_UINT8, c->comm, c->stream));
+    if (mine) OZ_HIP(hipMemcpyAsync(c->d_send, src + (size_t)first_record * width, (size_t)mine * width, hipMemcpyDeviceToDevice, c->stream));
+    if (mine < mx) OZ_HIP(hipMemsetAsync(c->d_send + (size_t)mine * width, 0, (size_t)(mx - mine) * width, c->stream));
+    OZ_NCCL(g_rccl.AllGather(c->d_send, c->d_recv, (size_t)mx * width, OZ_NCCL_UINT8, c->comm, c->stream));
     long long pos = 0;
     for (int r = 0; r < W; ++r) {
         const long long cnt = pairs[2 * r];
-        if (cnt) OZ_HIP(hipMemcpyAsync(out + pos, c->d_recv + (size_t)r * mx * sizeof(oz_record), (size_t)cnt * sizeof(oz_record),
+        if (cnt) OZ_HIP(hipMemcpyAsync(out + (size_t)pos * width, c->d_recv + (size_t)r * mx * width, (size_t)cnt * width,
                                        hipMemcpyDeviceToHost, c->stream));
         pos += cnt;
     }
     OZ_HIP(hipStreamSynchronize(c->stream));
     *written = sum;
     return OZ_OK;
+}
+OZ_API int oz_selfplay_gather_records(oz_selfplay* sp, oz_comm* c, int64_t first_record, oz_record* out, int64_t max_records, int64_t* written,
+                                      int64_t* per_rank) {
+    return gather_rows(sp, c, 0, first_record, out, max_records, written, per_rank, "oz_selfplay_gather_records");
+}
+OZ_API int oz_selfplay_gather_visits(oz_selfplay* sp, oz_comm* c, int64_t first_record, int32_t* out, int64_t max_records, int64_t* written,
+                                     int64_t* per_rank) {
+    return gather_rows(sp, c, 1, first_record, out, max_records, written, per_rank, "oz_selfplay_gather_visits");
 }
 
 // ================================================================ diagnostics

@@ -277,7 +277,9 @@ __global__ __launch_bounds__(256) void k_t_bn_bwd(const float* __restrict__ dA, 
 
 // ---------------------------------------------------------------- heads: forward, losses, gradient wrt f2
 // one 64-thread block per sample (A = n*n <= 64 policy outputs, lane = action)
-__global__ __launch_bounds__(64) void k_t_heads(const float* __restrict__ f2 /*[B][512]*/, const int* __restrict__ d_count, int n,
+// flat = 0 (OZ_POLICY_LOSS_ROWS): the reference's loss on the (n, n) view, every row renormalised and the rows averaged;
+// flat = 1 (OZ_POLICY_LOSS_FLAT): the same clipped cross entropy with ONE group of A lanes -- whole-board sums, no mean over rows
+__global__ __launch_bounds__(64) void k_t_heads(const float* __restrict__ f2 /*[B][512]*/, const int* __restrict__ d_count, int n, int flat,
                                                 const float* __restrict__ Wpi /*[512][A]*/, const float* __restrict__ bpi,
                                                 const float* __restrict__ Wv /*[512]*/, const float* __restrict__ bv,
                                                 const float* __restrict__ pit /*[B][A]*/, const float* __restrict__ zt /*[B]*/,
@@ -314,11 +316,11 @@ __global__ __launch_bounds__(64) void k_t_heads(const float* __restrict__ f2 /*[
     const float p = e / se;
     const float v = tanhf(vacc + bv[0]);
     // row-normalised, clipped cross entropy on the (n, n) view; the lanes of one board row are n consecutive lanes
-    // (every lane runs the shuffles; lanes >= A read a clamped source and their results are unused)
-    const int row = lane / n;
+    // (every lane runs the shuffles; lanes >= A read a clamped source and their results are unused).  flat: one group of A lanes
+    const int row = flat ? 0 : lane / n, width = flat ? A : n;
     const float t = lane < A ? pit[(size_t)b * A + lane] : 0.f;
     float S = 0.f;
-    for (int c = 0; c < n; ++c) { const int src = row * n + c; S += __shfl(p, src < 63 ? src : 63); }
+    for (int c = 0; c < width; ++c) { const int src = row * n + c; S += __shfl(p, src < 63 ? src : 63); }
     const float q = lane < A ? p / S : 0.5f;
     const bool inside = q >= 1e-7f && q <= 1.0f - 1e-7f;
     const float qc = fminf(fmaxf(q, 1e-7f), 1.0f - 1e-7f);
@@ -328,8 +330,8 @@ __global__ __launch_bounds__(64) void k_t_heads(const float* __restrict__ f2 /*[
     const float gq = (lane < A && inside) ? -t / q : 0.f;
     const float gqq = gq * q;
     float rowdot = 0.f;
-    for (int c = 0; c < n; ++c) { const int src = row * n + c; rowdot += __shfl(gqq, src < 63 ? src : 63); }
-    const float normp = 1.0f / ((float)B * (float)n);
+    for (int c = 0; c < width; ++c) { const int src = row * n + c; rowdot += __shfl(gqq, src < 63 ? src : 63); }
+    const float normp = flat ? 1.0f / (float)B : 1.0f / ((float)B * (float)n);
     const float gp = lane < A ? (gq - rowdot) / S * normp : 0.f;
     // softmax backward: dlogit_j = p_j (gp_j - sum_k gp_k p_k)
     float dot = gp * p;
@@ -342,7 +344,7 @@ __global__ __launch_bounds__(64) void k_t_heads(const float* __restrict__ f2 /*[
         const float d = v - zt[b];
         v_out[b] = v;
         dvpre[b] = 2.0f * d / (float)B * (1.0f - v * v);
-        loss[2 * b] = lpi / (float)n;          // per-sample mean over rows
+        loss[2 * b] = flat ? lpi : lpi / (float)n;          // per-sample mean over rows (ROWS)
         loss[2 * b + 1] = d * d;
     }
 }
@@ -1017,6 +1019,7 @@ struct oz_trainer {
     float lr = 1e-3f, clip = 0.5f, rate = 0.3f, mom = 0.99f;
     uint64_t seed = 0;
     int64_t step = 0;
+    int policy_loss = OZ_POLICY_LOSS_ROWS;   // oz_trainer_set_policy_loss
     hipStream_t s = nullptr;
     int64_t size[40], toff[40];          // element counts; offset in the trainable arena (-1: moving statistic)
     int64_t total = 0;
@@ -1197,6 +1200,13 @@ static int t_check_range(oz_trainer* t) {
         else oz_set_error("an activation exceeded the fp16 range (65504) in the trainer's f16x2 mode: the step is invalid; use precision 0 (f32)");
         return OZ_ERR_STATE;
     }
+    return OZ_OK;
+}
+
+OZ_API int oz_trainer_set_policy_loss(oz_trainer* t, int mode) {
+    OZ_REQUIRE(t && (mode == OZ_POLICY_LOSS_ROWS || mode == OZ_POLICY_LOSS_FLAT), "oz_trainer_set_policy_loss: mode 0 (rows) or 1 (flat)");
+    T_LOCK(t);
+    t->policy_loss = mode;              // read at the next launch of the heads kernel (stream order)
     return OZ_OK;
 }
 
@@ -1418,7 +1428,7 @@ static int t_forward_backward_async(oz_trainer* t, int B) {
                                         Cin[l], taps[l], t->Co[l], 0, s, t->gpartial, (t->split_mask & 1) ? t->gpartial_floats : 0)) return rc;
         if (int rc = t_bn_forward(t, l, B)) return rc;
     }
-    hipLaunchKernelGGL(k_t_heads, dim3(B), dim3(64), 0, s, t->a[5], t->d_count, n, t->param(36), t->param(37), t->param(38), t->param(39),
+    hipLaunchKernelGGL(k_t_heads, dim3(B), dim3(64), 0, s, t->a[5], t->d_count, n, t->policy_loss, t->param(36), t->param(37), t->param(38), t->param(39),
                        t->d_pit, t->d_zt, t->p, t->v, t->dlogit, t->dvpre, t->loss);
     OZ_HIP(hipGetLastError());
 

@@ -14,6 +14,7 @@ import torch.distributed as dist
 from ._lib import RECORD_DTYPE
 
 RECORD_BYTES = RECORD_DTYPE.itemsize
+VISITS_BYTES = 64 * 4                  # one record's root visit counts, int32 by square row*8+col
 
 
 def shard_games(total_games, rank, world_size):
@@ -80,10 +81,34 @@ def engine_records_tensor(engine, device):
     return t[:written]
 
 
-def pooled_selfplay_records(engine, device, group=None):
-    """records of every rank's completed games, identical on all ranks, sorted by (game_id, ply)"""
-    allrec = tensor_to_records(gather_records(engine_records_tensor(engine, device), group))
-    return allrec[np.lexsort((allrec["ply"], allrec["game_id"]))]
+def engine_visits_tensor(engine, device, count):
+    """the first `count` visit-count rows of the engine (record_visits=True) as a uint8 [count, 256] tensor on `device` -- the int32 [64]
+    row of each record, in the ring order of engine_records_tensor; device to device"""
+    t = torch.empty((max(count, 1), VISITS_BYTES), dtype=torch.uint8, device=device)
+    written = engine.visits_to_device(t.data_ptr(), count) if count else 0
+    assert written == count, (written, count)
+    return t[:count]
+
+
+def pooled_selfplay_records(engine, device, group=None, with_visits=False):
+    """records of every rank's completed games, identical on all ranks, sorted by (game_id, ply).
+    with_visits=True (engines created with record_visits=True): (records, counts int32 [R, 64]) -- each rank's rows travel as
+    record || counts (48 + 256 bytes) in the same all-gather and are split after the sort"""
+    local = engine_records_tensor(engine, device)
+    if not with_visits:
+        allrec = tensor_to_records(gather_records(local, group))
+        return allrec[np.lexsort((allrec["ply"], allrec["game_id"]))]
+    rows = gather_records(torch.cat([local, engine_visits_tensor(engine, device, local.shape[0])], dim=1), group)
+    return split_record_rows(rows)
+
+
+def split_record_rows(rows):
+    """uint8 [R, 48 + 256] rows (record || int32 [64] visit counts) -> (records, counts) sorted by (game_id, ply)"""
+    a = rows.detach().cpu().contiguous().numpy().reshape(-1, RECORD_BYTES + VISITS_BYTES)
+    rec = np.ascontiguousarray(a[:, :RECORD_BYTES]).view(RECORD_DTYPE).reshape(-1)
+    counts = np.ascontiguousarray(a[:, RECORD_BYTES:]).view("<i4").reshape(-1, 64)
+    order = np.lexsort((rec["ply"], rec["game_id"]))
+    return rec[order], counts[order]
 
 
 # ---------------------------------------------------------------- arena games sharded over the ranks (SURVEY.md 8(e): all-gather of (winner, points))
@@ -148,8 +173,10 @@ class Comm:
         self.rank, self.world = rank, world
         _lib.check(lib.oz_comm_create(C.byref(self._h), ident, rank, world))
 
-    def gather_records(self, engine, first_record=0, max_records=None):
-        """COLLECTIVE: the records [first_record, ...) of every rank's engine in rank order -> (records, per-rank counts).
+    def gather_records(self, engine, first_record=0, max_records=None, with_visits=False):
+        """COLLECTIVE: the records [first_record, ...) of every rank's engine in rank order -> (records, per-rank counts);
+        with_visits=True (engines created with record_visits=True): (records, visit counts int32 [R, 64], per-rank counts), the
+        rows gathered by oz_selfplay_gather_visits with the same protocol, in the same order.
         Two collective calls: the counts alone (out = NULL), then the records into a buffer sized from the pooled count -- the same
         number on every rank, so no rank can come up short while its peers wait in the payload all-gather.  max_records, if
         given, is this rank's room: the library fails the call on every rank together when it is too small on any."""
@@ -165,7 +192,13 @@ class Comm:
         out = np.zeros(cap, dtype=RECORD_DTYPE)
         _lib.check(lib.oz_selfplay_gather_records(engine._h, self._h, int(first_record), out.ctypes.data_as(C.c_void_p), cap,
                                                   C.byref(written), _lib.p_i64(per)))
-        return out[:written.value], per
+        if not with_visits:
+            return out[:written.value], per
+        counts, got, per2 = np.zeros((cap, 64), np.int32), C.c_int64(), np.zeros(self.world, np.int64)
+        _lib.check(lib.oz_selfplay_gather_visits(engine._h, self._h, int(first_record), _lib.p_i32(counts), cap, C.byref(got),
+                                                 _lib.p_i64(per2)))
+        assert got.value == written.value and np.array_equal(per, per2), (got.value, written.value)
+        return out[:written.value], counts[:got.value], per
 
     def close(self):
         if self._h:

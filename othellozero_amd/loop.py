@@ -73,7 +73,7 @@ class CircularArray:
         return f'{type(self).__name__}({len(self._list)!r})'
 
 
-def examples_from_records(records, board_size, alias_final=True, in_channels=2):
+def examples_from_records(records, board_size, alias_final=True, in_channels=2, visits=None, target_temperature=1.0):
     """move records of finished games -> the reference's example tuples [(board, one-hot policy (n,n), z)], 8 per move in
     training.py:13-23's order.
 
@@ -82,14 +82,19 @@ def examples_from_records(records, board_size, alias_final=True, in_channels=2):
     position at the move.
     in_channels=1 (BaseNN): board (n,n) with +1 BLACK / -1 WHITE, the position AT THE MOVE whatever alias_final says -- the
     reference builds a fresh one-channel array per round for BNN (training.py:34-37, Othello/__init__.py:79-84,266-270), so
-    those examples are never aliased."""
+    those examples are never aliased.
+    visits (int32 (R, 64), the records' root visit counts): the policy of every example is the search's visit distribution at
+    target_temperature (expand_examples) instead of the one-hot of the move played."""
     one_channel = in_channels == 1
-    boards, pol, z = expand_examples(records, board_size, alias_final=alias_final and not one_channel)
+    boards, pol, z = expand_examples(records, board_size, alias_final=alias_final and not one_channel, visits=visits,
+                                     target_temperature=target_temperature)
     n = board_size
     if one_channel:
         boards = boards[..., 0].astype(np.int64) - boards[..., 1].astype(np.int64)      # convert_to_one_channel_board
     else:
         boards = boards.astype(bool)
+    if visits is not None:
+        return [(b, p, int(zz)) for b, p, zz in zip(boards, pol, z)]
     out = []
     for b, p, zz in zip(boards, pol, z):
         policy = np.zeros((n, n))
@@ -164,7 +169,7 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
              e_greedy, evaluation_interval, evaluation_iterations, temperature_threshold, self_play_training,
              self_play_interval, self_play_total_games, self_play_threshold, checkpoint_filepath, training_buffer_size,
              seed=1234, reference_aliasing=True, alias_final_boards=True, dump_examples=False, q_mode=_lib.QMODE_F64,
-             distributed=False, batched_evaluation=False):
+             distributed=False, batched_evaluation=False, policy_target="onehot", target_temperature=1.0):
     """main.py:56-259 on the GPU engines; returns `historic` = [(episodes done, win rate vs random), ...]
 
     batched_evaluation=True plays the evaluation games against RandomOthelloAgent in lock step on the GPU
@@ -174,7 +179,23 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
     the ranks by global game id and pooled with one all-gather of move records, every rank then holds the same replay
     buffer (same `random` stream, seeded here), trains on its 1/world slice of it with one gradient all-reduce per step,
     and plays the (deterministic) matches / evaluations redundantly, so all ranks take the same promotion decisions
-    without further communication; rank 0 writes the files."""
+    without further communication; rank 0 writes the files.
+
+    policy_target="visits" trains the policy on the search's visit distribution (the AlphaZero pi, from the root visit counts the
+    engines record, at target_temperature) instead of the one-hot of the move played.  It needs alias_final_boards=False (pi belongs
+    to the position of the move, not the game's final one) and a network whose policy_loss is "flat" (the reference's row-wise loss
+    cannot learn how pi's mass splits between board rows)."""
+    if policy_target not in ("onehot", "visits"):
+        raise ValueError(f"policy_target must be 'onehot' or 'visits' (got {policy_target!r})")
+    visits = policy_target == "visits"
+    if visits and alias_final_boards:
+        raise ValueError("policy_target='visits' needs alias_final_boards=False: a visit distribution belongs to the position of its "
+                         "move, not to the game's final position")
+    if visits and getattr(neural_network, "policy_loss", "rows") != "flat":
+        raise ValueError("policy_target='visits' needs a network trained with the flat policy loss: create it with "
+                         "NNetWrapper(..., policy_loss='flat') (the row-wise loss renormalises every board row on its own)")
+    if visits and not target_temperature > 0:
+        raise ValueError(f"target_temperature must be > 0 (got {target_temperature})")
     if self_play_training:
         assert self_play_threshold <= self_play_total_games, 'Self-play threshold must be less than self-play games'
 
@@ -210,16 +231,20 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
         if distributed:
             first, count = shard_games(num_episodes, rank, world)
             eng = SelfPlayEngine(neural_network, board_size, count, num_simulations, degree_exploration, temperature, e_greedy,
-                                 seed=seed, first_game_id=total_episodes_done + first, q_mode=q_mode)
+                                 seed=seed, first_game_id=total_episodes_done + first, q_mode=q_mode, record_visits=visits)
             eng.play_to_end()
-            records = pooled_selfplay_records(eng, device)          # the only exchange of the self-play phase
+            records = pooled_selfplay_records(eng, device, with_visits=visits)      # the only exchange of the self-play phase
             del eng
         else:
             records = selfplay_batch(neural_network, board_size, num_games=num_episodes, num_simulations=num_simulations,
                                      degree_exploration=degree_exploration, policy_temperature=temperature, e_greedy=e_greedy,
-                                     seed=seed, first_game_id=total_episodes_done, q_mode=q_mode)
+                                     seed=seed, first_game_id=total_episodes_done, q_mode=q_mode, record_visits=visits)
+        counts = None
+        if visits:
+            records, counts = records
         training_examples.extend(examples_from_records(records, board_size, alias_final=alias_final_boards,
-                                                       in_channels=getattr(neural_network, "in_channels", 2)))
+                                                       in_channels=getattr(neural_network, "in_channels", 2), visits=counts,
+                                                       target_temperature=target_temperature))
         total_episodes_done += num_episodes
         logging.info('[%d/%d] self-play done: %d records, buffer holds %d examples', i, num_iterations, len(records), len(training_examples))
 

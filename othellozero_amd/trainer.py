@@ -14,6 +14,7 @@ from .weights import onn_shapes
 
 TRAINABLE = [i for i in range(40) if i >= 36 or i % 6 not in (4, 5)]
 PRECISION_MODES = {"f32": 0, "f16x2": 1, "bf16x3": 2}      # oz_trainer_set_precision
+POLICY_LOSSES = {"rows": _lib.POLICY_LOSS_ROWS, "flat": _lib.POLICY_LOSS_FLAT}      # oz_trainer_set_policy_loss
 
 
 class History:
@@ -26,12 +27,15 @@ class History:
 
 class Trainer:
     def __init__(self, board_size=8, channels=512, in_channels=2, max_batch=32, lr=1e-3, clipvalue=0.5, dropout=0.3,
-                 bn_momentum=0.99, seed=0, external_grads_ptr=None, precision="f32"):
+                 bn_momentum=0.99, seed=0, external_grads_ptr=None, precision="f32", policy_loss="rows"):
         """precision: arithmetic of the 3x3 layers -- "f32" (fp32 matrix cores), "f16x2" (forward / data-gradient GEMMs: fp32 values
         as two fp16 planes on the fp16 matrix cores, per-step power-of-two scaling and a range guard; channels % 256 == 0) or "bf16x3"
         (forward, data gradient and weight gradient: every fp32 value exactly as three bf16 planes on the bf16 matrix cores, no scaling,
-        no guard; channels % 256 == 0)"""
+        no guard; channels % 256 == 0)
+        policy_loss: "rows" -- the reference's categorical cross entropy on the (n, n)-reshaped softmax (each board row renormalised, rows
+        averaged); "flat" -- on the whole (n*n,) softmax, the loss for dense visit-distribution targets"""
         assert precision in PRECISION_MODES, precision
+        assert policy_loss in POLICY_LOSSES, policy_loss
         lib = _lib.require_gpu()
         self.n, self.channels, self.in_channels, self.max_batch = board_size, channels, in_channels, int(max_batch)
         self._h = C.c_void_p()
@@ -42,6 +46,9 @@ class Trainer:
         self.precision = precision
         if precision != "f32":
             _lib.check(lib.oz_trainer_set_precision(self._h, PRECISION_MODES[precision]))
+        self.policy_loss = policy_loss
+        if policy_loss != "rows":
+            _lib.check(lib.oz_trainer_set_policy_loss(self._h, POLICY_LOSSES[policy_loss]))
 
     def __del__(self):
         try:

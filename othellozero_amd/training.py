@@ -31,12 +31,19 @@ def training_example_symmetries(board, policy):
 
 
 def execute_episode(board_size, neural_network, degree_exploration, num_simulations, policy_temperature, e_greedy,
-                    q_mode=_lib.QMODE_F64, snapshot_boards=False):
+                    q_mode=_lib.QMODE_F64, snapshot_boards=False, policy_target="onehot", target_temperature=1.0):
     """training.py:26-72.  Returns [(board (n,n,2) bool, one-hot policy (n,n) float64, z int), ...], 8 per move.
 
     snapshot_boards=False reproduces the reference exactly, including its aliasing quirk: the
     returned boards are views of the live game array, so every example shows the FINAL position.  Pass
-    snapshot_boards=True to store the position at the time of the move instead (what training wants)."""
+    snapshot_boards=True to store the position at the time of the move instead (what training wants).
+
+    policy_target="visits" stores the search's visit distribution instead of the one-hot of the move played (the AlphaZero
+    pi): mcts.get_policy_action_probabilities(state, target_temperature) at every move.  With target_temperature > 0 that
+    call draws no random number, so moves and random streams are those of the default "onehot"."""
+    assert policy_target in ("onehot", "visits"), policy_target
+    if policy_target == "visits" and not target_temperature > 0:
+        raise ValueError(f"target_temperature must be > 0 for visit-count targets (got {target_temperature})")
     examples = []
     game = OthelloGame(board_size)
     mcts = OthelloMCTS(board_size, neural_network, degree_exploration, q_mode=q_mode,
@@ -60,6 +67,8 @@ def execute_episode(board_size, neural_network, degree_exploration, num_simulati
 
         action_choosed = np.zeros((board_size, board_size))
         action_choosed[action[0]][action[1]] = 1
+        if policy_target == "visits":
+            action_choosed = mcts.get_policy_action_probabilities(state, target_temperature)
         board_now = game.board(board_view_type)
         if snapshot_boards:
             board_now = np.copy(board_now)
@@ -114,11 +123,14 @@ class SelfPlayEngine:
 
     def __init__(self, neural_network, board_size=8, num_games=4096, num_simulations=100, degree_exploration=1.0,
                  policy_temperature=1.0, e_greedy=0.9, seed=1234, first_game_id=0, game_id_stride=0,
-                 q_mode=_lib.QMODE_F64, refill=False, node_cap=0, record_cap=0, dedup=True, batch_cap=0, eval_cache=False):
+                 q_mode=_lib.QMODE_F64, refill=False, node_cap=0, record_cap=0, dedup=True, batch_cap=0, eval_cache=False,
+                 record_visits=False):
         """dedup: cross-game leaf de-duplication (a board several games reach in one batch is evaluated once; no record changes);
         batch_cap: leaves per network batch of the free-running driver (0 = none; see preferred_batch_cap);
         eval_cache: take (pi, v) of boards the network has evaluated before from its persistent cache (NNetWrapper.set_eval_cache) --
-        the reference's per-search _predict_cache (othelo_mcts.py:82-88) across batches, games and refilled slots; no record changes"""
+        the reference's per-search _predict_cache (othelo_mcts.py:82-88) across batches, games and refilled slots; no record changes;
+        record_visits: keep every recorded move's root visit counts (records(with_visits=True)) -- the policy targets of
+        expand_examples(visits=...); 16 KB per slot + 256 B per record of device memory, no record changes"""
         lib = _lib.require_gpu()
         assert getattr(neural_network, "_h", None) is not None, "SelfPlayEngine needs a native NNetWrapper / StubNetWrapper"
         self.net = neural_network
@@ -127,7 +139,7 @@ class SelfPlayEngine:
             temperature=float(policy_temperature), e_greedy=float(e_greedy), seed=seed, first_game_id=first_game_id,
             game_id_stride=game_id_stride, refill=1 if refill else 0, node_cap=node_cap,
             record_cap=record_cap, dedup=_lib.DEDUP_ON if dedup else _lib.DEDUP_OFF, batch_cap=int(batch_cap),
-            eval_cache=1 if eval_cache else 0)
+            eval_cache=1 if eval_cache else 0, record_visits=1 if record_visits else 0)
         self._h = C.c_void_p()
         _lib.check(lib.oz_selfplay_create(C.byref(self._h), C.byref(self.cfg), neural_network._h))
         self.n, self.num_games = board_size, num_games
@@ -204,19 +216,33 @@ class SelfPlayEngine:
         _lib.check(_lib.load().oz_selfplay_last_counts(self._h, _lib.p_i32(c)))
         return c
 
-    def records(self):
+    def records(self, with_visits=False):
         """move records of the games completed so far (numpy structured array, _lib.RECORD_DTYPE),
-        sorted by (game_id, ply)."""
+        sorted by (game_id, ply).  with_visits=True (engine created with record_visits=True): (records, counts), counts =
+        int32 (R, 64) root visit counts of each record's move by square row*8+col, in the same order."""
         total = self.stats()["records"]
         out = np.zeros(max(total, 1), dtype=_lib.RECORD_DTYPE)
         written = C.c_int64()
         _lib.check(_lib.load().oz_selfplay_records(self._h, out.ctypes.data_as(C.c_void_p), total, C.byref(written)))
         out = out[:written.value]
-        return out[np.lexsort((out["ply"], out["game_id"]))]
+        order = np.lexsort((out["ply"], out["game_id"]))
+        if not with_visits:
+            return out[order]
+        counts = np.zeros((max(out.size, 1), 64), np.int32)
+        got = C.c_int64()
+        _lib.check(_lib.load().oz_selfplay_visits(self._h, _lib.p_i32(counts), out.size, C.byref(got)))
+        assert got.value == out.size, (got.value, out.size)
+        return out[order], counts[:out.size][order]
 
     def records_to_device(self, device_ptr, max_records):
         written = C.c_int64()
         _lib.check(_lib.load().oz_selfplay_records_device(self._h, C.c_void_p(device_ptr), max_records, C.byref(written)))
+        return written.value
+
+    def visits_to_device(self, device_ptr, max_records):
+        """the visit-count rows (int32 [max_records][64]) in the ring order of records_to_device, device to device"""
+        written = C.c_int64()
+        _lib.check(_lib.load().oz_selfplay_visits_device(self._h, C.c_void_p(device_ptr), max_records, C.byref(written)))
         return written.value
 
     def eval_time(self):
@@ -224,13 +250,13 @@ class SelfPlayEngine:
         _lib.check(_lib.load().oz_selfplay_eval_time(self._h, C.byref(ms), C.byref(launches), C.byref(leaves)))
         return dict(ms=ms.value, launches=launches.value, leaves=leaves.value)
 
-    def play_to_end(self, max_rounds=None):
+    def play_to_end(self, max_rounds=None, with_visits=False):
         max_rounds = max_rounds or self.n * self.n
         for _ in range(max_rounds):
             self.run(4)
             if self.stats()["live_games"] == 0:
                 break
-        return self.records()
+        return self.records(with_visits=with_visits)
 
 
 def preferred_batch_cap(board_size, num_games, channels=512, precision="f16x2"):
@@ -249,11 +275,26 @@ def preferred_batch_cap(board_size, num_games, channels=512, precision="f16x2"):
     return 0 if cap >= num_games else int(cap)
 
 
-def expand_examples(records, board_size, alias_final=False):
+def expand_examples(records, board_size, alias_final=False, visits=None, target_temperature=1.0):
     """8-fold symmetry expansion of move records on the GPU (training.py:13-23,58-65).
-    Returns boards (R*8, n, n, 2) uint8, policy_index (R*8,) int32 (position of the one-hot), z (R*8,) int8."""
+    Returns boards (R*8, n, n, 2) uint8, policy_index (R*8,) int32 (position of the one-hot), z (R*8,) int8.
+
+    visits = the records' root visit counts (int32 (R, 64), SelfPlayEngine.records(with_visits=True)): the policy is the search's
+    visit distribution get_policy_action_probabilities(root, target_temperature) (othelo_mcts.py:51-67) in place of the one-hot,
+    and the second array returned is pi (R*8, n, n) float64 (target_temperature > 0)."""
     rec = np.ascontiguousarray(records, dtype=_lib.RECORD_DTYPE)
     R, n = rec.size, board_size
+    if visits is not None:
+        cnt = np.ascontiguousarray(visits, dtype=np.int32).reshape(-1, 64)
+        assert cnt.shape[0] == R, f"{cnt.shape[0]} visit-count rows for {R} records"
+        if not target_temperature > 0:
+            raise ValueError(f"target_temperature must be > 0 for visit-count targets (got {target_temperature})")
+        boards, pi, z = np.zeros((R * 8, n, n, 2), np.uint8), np.zeros((R * 8, n, n), np.float64), np.zeros(R * 8, np.int8)
+        if R:
+            _lib.check(_lib.require_gpu().oz_examples_expand_visits(rec.ctypes.data_as(C.c_void_p), _lib.p_i32(cnt), R, n,
+                                                                    1 if alias_final else 0, float(target_temperature),
+                                                                    _lib.p_u8(boards), _lib.p_f64(pi), _lib.p_i8(z)))
+        return boards, pi, z
     boards = np.zeros((R * 8, n, n, 2), np.uint8)
     pol, z = np.zeros(R * 8, np.int32), np.zeros(R * 8, np.int8)
     if R:
@@ -264,9 +305,13 @@ def expand_examples(records, board_size, alias_final=False):
 
 def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations=100, degree_exploration=1.0,
                    policy_temperature=1.0, e_greedy=0.9, seed=1234, first_game_id=0, q_mode=_lib.QMODE_F64,
-                   expand=False, alias_final=False):
-    """Play num_games complete games; returns the move records (or the expanded examples)."""
+                   expand=False, alias_final=False, record_visits=False, target_temperature=1.0):
+    """Play num_games complete games; returns the move records (or the expanded examples).
+    record_visits=True: (records, visit counts) -- or, with expand, the examples with visit-distribution targets at target_temperature."""
     eng = SelfPlayEngine(neural_network, board_size, num_games, num_simulations, degree_exploration, policy_temperature,
-                         e_greedy, seed, first_game_id, q_mode=q_mode)
+                         e_greedy, seed, first_game_id, q_mode=q_mode, record_visits=record_visits)
+    if record_visits:
+        rec, counts = eng.play_to_end(with_visits=True)
+        return expand_examples(rec, board_size, alias_final, visits=counts, target_temperature=target_temperature) if expand else (rec, counts)
     rec = eng.play_to_end()
     return expand_examples(rec, board_size, alias_final) if expand else rec
