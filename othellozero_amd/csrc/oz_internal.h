@@ -134,6 +134,30 @@ struct oz_net {
 int oz_net_forward_device(oz_net* net, const uint64_t* d_own, const uint64_t* d_opp, const int* d_count,
                           int max_count, float* d_pi, float* d_v, hipStream_t s);
 
+// One GEMM layer of the network as data: a 3x3 convolution (taps = 9) over Hin x Hin pixels of Cin channels, or a dense layer (taps = 1,
+// Hin = Hout = 1, pad = 0, Cin = its inputs); N output channels on Hout x Hout pixels.  The leading fields of GemmGeom / H2Geom / B3Geom
+// are filled from it (oz_geom_set_shape): the kernels' argument layouts stay their own.
+struct OzLayerShape {
+    int Hin, Hout, pad, Cin, taps, N;
+    int K() const { return taps * Cin; }
+    int pixels() const { return Hout * Hout; }
+};
+template <typename Geom> inline void oz_geom_set_shape(Geom& g, const OzLayerShape& L) {
+    g.Hin = L.Hin; g.Hout = L.Hout; g.pad = L.pad; g.Cin = L.Cin; g.taps = L.taps; g.N = L.N; g.K = L.K();
+}
+// OthelloNN's five GEMM layers (Net/OthelloNN.py:42-56) on an n x n board with C filters: [0] conv2 'same', [1] conv3 'valid', [2] conv4 'valid',
+// [3] fc1 (Flatten (h, w, c) -> 1024), [4] fc2 (1024 -> 512).  conv1 (K = 18) is no GEMM.  The one statement of these shapes: the three forwards,
+// oz_net_commit's buffers and weight images, and the trainer's per-layer set-up read it.
+struct OzLayers {
+    OzLayerShape l[5];
+    const OzLayerShape& operator[](int i) const { return l[i]; }
+    const OzLayerShape* begin() const { return l; }
+    const OzLayerShape* end() const { return l + 5; }
+};
+inline OzLayers oz_onn_layers(int n, int C) {
+    return {{{n, n, 1, C, 9, C}, {n, n - 2, 0, C, 9, C}, {n - 2, n - 4, 0, C, 9, C}, {1, 1, 0, (n - 4) * (n - 4) * C, 1, 1024}, {1, 1, 0, 1024, 1, 512}}};
+}
+
 // implicit-GEMM geometry of k_gemm_f32 (oz_net.hip): out[M][N] = act((A[M][K] . Wt[N][K]^T) * scale + shift),
 // M = *d_count * Hout^2 rows (b, oy, ox); A rows are gathered per 3x3 tap with zero fill
 struct GemmGeom {

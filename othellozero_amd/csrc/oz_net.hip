@@ -22,6 +22,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 #include "oz_internal.h"
@@ -377,6 +378,32 @@ __global__ __launch_bounds__(256) void k_splitk_reduce_f32(const float* __restri
     *reinterpret_cast<f32x4*>(out + i) = r;
 }
 
+// ---------------------------------------------------------------- launch helpers shared by every GEMM launcher of this file
+// The grid of the h2 / b3 GEMM kernels' two block mappings: num_mt row tiles x per_mt (column tiles x k-slices) blocks, the minor dimension
+// padded to a multiple of the 8 XCDs (few row tiles: the blocks of one row tile go round the XCDs; otherwise the row tiles do).
+static inline int gemm_grid(int num_mt, int per_mt) { return num_mt < 8 ? ((per_mt + 7) / 8) * 8 * num_mt : ((num_mt + 7) / 8) * 8 * per_mt; }
+
+// The dynamic-LDS limit of ONE kernel instantiation, set once per device (function attributes belong to the device the caller is on)
+template <auto Kernel> static int set_max_lds_once(int bytes) {
+    static bool attr_done[64] = {};
+    int dev_now = 0;
+    OZ_HIP(hipGetDevice(&dev_now));
+    if (!attr_done[dev_now & 63]) {
+        OZ_HIP(hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+        attr_done[dev_now & 63] = true;
+    }
+    return OZ_OK;
+}
+
+// Finishes a split-K launch whose consumer reads fp32 rows: out[rows][N] = act(sum of the k-slices (fixed order) * scale + shift), rows = boards x P
+// (round 5, measured and removed: one output per thread with all 72 slices in flight -- 6.1 against 6.6 us: a kernel of this kind is
+//  launch + count + one round trip to the slabs + store ~ 5 us whatever the loop looks like; fewer launches is what is left)
+static void launch_splitk_reduce_f32(const float* partial, long long slab, int ksplit, int N, int P, int max_count, const int* d_count,
+                                     const float* scale, const float* shift, int relu, float* out, hipStream_t s) {
+    const long long quads = ((long long)max_count * P * N + 3) / 4;
+    hipLaunchKernelGGL(k_splitk_reduce_f32, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, s, partial, slab, ksplit, N, P, d_count, scale, shift, relu, out);
+}
+
 // shared launcher (inference f32 path and the training step, oz_train.hip).  `partial` (optional, `partial_floats`
 // long): when the launch would have fewer blocks than the chip has CUs, the k loop is split over blockIdx.y and reduced
 // in a fixed order by k_splitk_reduce_f32 -- same result for every batch position, different rounding than ksplit = 1.
@@ -392,8 +419,8 @@ int oz_gemm_f32_launch(const float* in, const float* Wt, const float* scale, con
     int& tile_rows = tile_rows_out ? *tile_rows_out : tile_rows_dummy;
     OZ_REQUIRE(N % GM_BN == 0 && Cin % GM_BK == 0, "gemm_f32: N %% 128 and Cin %% 32 must be 0 (N=%d Cin=%d)", N, Cin);
     GemmGeom g;
-    g.Hin = Hin; g.Hout = Hout; g.pad = pad; g.Cin = Cin; g.taps = taps; g.N = N; g.K = taps * Cin; g.relu = relu;
-    g.core_lo = core_lo; g.core_hi = core_hi;
+    oz_geom_set_shape(g, OzLayerShape{Hin, Hout, pad, Cin, taps, N});
+    g.relu = relu; g.core_lo = core_lo; g.core_hi = core_hi;
     const long long Mmax = (long long)max_count * Hout * Hout;
     // pixel-major tiles skip the k-tiles of taps that only read zeros; they pay when the boards fill the 128-row tiles
     // (keyed on the call's capacity `max_count` / `sizing_count`, like the split-K choice: per-network constants)
@@ -417,11 +444,7 @@ int oz_gemm_f32_launch(const float* in, const float* Wt, const float* scale, con
             tile_rows = 64;
             hipLaunchKernelGGL(k_gemm_f32_skinny, dim3(N / SK_COLS, ks), dim3(256), 0, s, in, Wt, d_count, g.K, N, kb, partial, slab, g);
             if (defer && relu) { defer->partial = partial; defer->slab = slab; defer->ksplit = ks; defer->scale = scale; defer->shift = shift; OZ_HIP(hipGetLastError()); return OZ_OK; }
-            const long long quads = (slab + 3) / 4;
-            // (round 5, measured and removed: one output per thread with all 72 slices in flight -- 6.1 against 6.6 us: a kernel of this kind is
-            //  launch + count + one round trip to the slabs + store ~ 5 us whatever the loop looks like; fewer launches is what is left)
-            hipLaunchKernelGGL(k_splitk_reduce_f32, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, s, partial, slab, ks, N, Pout, d_count, scale,
-                               shift, relu, out);
+            launch_splitk_reduce_f32(partial, slab, ks, N, Pout, max_count, d_count, scale, shift, relu, out, s);
             OZ_HIP(hipGetLastError());
             return OZ_OK;
         }
@@ -438,16 +461,6 @@ int oz_gemm_f32_launch(const float* in, const float* Wt, const float* scale, con
         while (ksplit < 16 && grid_s * ksplit < split_blocks && nk / (ksplit * 2) >= 8 && (long long)(ksplit * 2) * (Ms > Mmax ? Ms : Mmax) * N <= partial_floats) ksplit *= 2;
     }
     g.ksplit = ksplit; g.slab = Mmax * N;
-    {   // the dynamic-LDS limits of the two instantiations, once per device
-        static bool attr_done[64] = {};
-        int dev_now = 0;
-        OZ_HIP(hipGetDevice(&dev_now));
-        if (!attr_done[dev_now & 63]) {
-            OZ_HIP(hipFuncSetAttribute((const void*)k_gemm_f32<GmStd>, hipFuncAttributeMaxDynamicSharedMemorySize, GmStd::LDS_BYTES));
-            OZ_HIP(hipFuncSetAttribute((const void*)k_gemm_f32<GmBig>, hipFuncAttributeMaxDynamicSharedMemorySize, GmBig::LDS_BYTES));
-            attr_done[dev_now & 63] = true;
-        }
-    }
     // 3x3 convolutions that fill the chip with 256 x 256 tiles (no pixel-major skipping, no k split): the big tile -- every output element's
     // products are added in the same order as on the standard tile (bit-identical), keyed on the call's capacity like the other choices
     const long long big_blocks = ((Mmax + GmBig::BM - 1) / GmBig::BM) * (N / GmBig::BN);
@@ -455,18 +468,18 @@ int oz_gemm_f32_launch(const float* in, const float* Wt, const float* scale, con
         tile_rows = GmBig::BM;
         const int num_mt_big = (int)((Mmax + GmBig::BM - 1) / GmBig::BM);
         const int grid_big = ((num_mt_big + 7) / 8) * 8 * (N / GmBig::BN);
+        if (int rc = set_max_lds_once<k_gemm_f32<GmBig>>(GmBig::LDS_BYTES)) return rc;
         hipLaunchKernelGGL(k_gemm_f32<GmBig>, dim3(grid_big, 1), dim3(GmBig::NT), GmBig::LDS_BYTES, s, in, Wt, scale, shift, out, d_count, g, num_mt_big, partial);
         OZ_HIP(hipGetLastError());
         return OZ_OK;
     }
     tile_rows = GmStd::BM;
+    if (int rc = set_max_lds_once<k_gemm_f32<GmStd>>(GmStd::LDS_BYTES)) return rc;
     hipLaunchKernelGGL(k_gemm_f32<GmStd>, dim3(grid, ksplit), dim3(GmStd::NT), GmStd::LDS_BYTES, s, in, Wt, scale, shift, out, d_count, g, num_mt, partial);
     OZ_HIP(hipGetLastError());
     if (ksplit > 1 && defer && relu) { defer->partial = partial; defer->slab = g.slab; defer->ksplit = ksplit; defer->scale = scale; defer->shift = shift; }
     else if (ksplit > 1) {
-        const long long quads = (Mmax * N + 3) / 4;
-        hipLaunchKernelGGL(k_splitk_reduce_f32, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, s, partial, g.slab, ksplit, N, Hout * Hout,
-                           d_count, scale, shift, relu, out);
+        launch_splitk_reduce_f32(partial, g.slab, ksplit, N, Pout, max_count, d_count, scale, shift, relu, out, s);
         OZ_HIP(hipGetLastError());
     }
     return OZ_OK;
@@ -478,131 +491,142 @@ int oz_gemm_f32_launch(const float* in, const float* Wt, const float* scale, con
                                // layers are weight streams / 16-way split-K launches -- latency, not matrix rate -- and the exact-fp32 kernels serve them
 #define CONV3_LOW_COST 1.30     // a round of 128-row conv3 tiles against 128/192 of a 192-row round (forward_h2's tile choice)
 
+// ---------------------------------------------------------------- one launcher per GEMM kernel family
+// launch_h2 / launch_b3 own the MECHANICS of a launch: geometry, grid, the LDS attribute, the kernel, and the finish of a split-K launch.
+// The POLICY -- which tile (CF / big), how many k-slices, how far apart the slabs sit -- is decided by the caller and differs between the
+// network object (keyed on max_batch, OnnNet below) and the trainer (keyed on its capacity, oz_gemm_h2_launch / oz_gemm_b3_launch).
+// Where the result goes:
+//   packed = 1  `out` in the kernel family's own operand layout (h2 / b3), BN + act applied -- by the kernel, or by the fixed-order reduce of a split launch
+//   packed = 0  `out` as fp32 rows, likewise; but a split launch with `defer` given writes only the raw slabs and fills *defer: the consumer
+//               of the rows adds the slices (the heads kernel, OzDeferredReduce)
+// `slabs` (ksplit > 1 only) holds ksplit slabs `slab` floats apart.
+
+// the trainer's k-split for a launch of `blocks` unsplit blocks and nk k-tiles: the largest split <= 16 that keeps the grid within one round of
+// the 256 CUs (any number of slices: the k range is divided proportionally), >= 8 k-tiles per slice, slabs of slab_floats within the buffer
+static int trainer_ksplit(long long blocks, int nk, long long slab_floats, long long partial_floats) {
+    int ksplit = 1;
+    while (ksplit < 16 && blocks * (ksplit + 1) <= 256 && nk / (ksplit + 1) >= 8 && (long long)(ksplit + 1) * slab_floats <= partial_floats) ++ksplit;
+    return ksplit;
+}
+
+// what a grid of bm-row tiles (256 columns each) pays for `rows` x N outputs: rounds of the 256 CUs x tile height.  Between tiles that add every
+// output's products in the same order, the cheaper one: 1024 boards of conv3 = 36864 rows -> 256-row tiles 288 blocks = 2 rounds x 256, 192-row
+// tiles 384 blocks = 2 x 192.
+static long long tile_cost(long long rows, int N, int bm) { return ((((rows + bm - 1) / bm) * (N / 256) + 255) / 256) * bm; }
+
+// low / lut_ids / relu = 0: the f16x2-only extras -- the low-side guard of a packed output, conv1 as a lookup inside the operand gather (H2BigPPLut),
+// the BN output before the ReLU (calibration passes, the table GEMMs)
+template <typename CF, int TAG = 0>
+static int launch_h2(const OzLayerShape& L, const void* in, const uint4* W, const float* scale, const float* shift, void* out, int packed, OzDeferredReduce* defer,
+                     const int* d_count, int max_count, int ksplit, float* slabs, long long slab, const uint4* zero_line, int* flag, hipStream_t s,
+                     int relu = 1, H2Low low = H2Low(), const unsigned* lut_ids = nullptr) {
+    if (defer) *defer = OzDeferredReduce();
+    H2Geom g;
+    oz_geom_set_shape(g, L);
+    g.out_h2 = packed; g.relu = relu; g.ksplit = ksplit; g.slab = slab;
+    if (packed && ksplit == 1) g.low = low;                   // (a split launch: the reduce below guards the rows it writes)
+    const int P = L.pixels(), N = L.N;
+    const int num_mt = (int)(((long long)max_count * P + CF::BM - 1) / CF::BM);
+    constexpr int LDS = CF::LDS + (CF::LUT ? 9 * CF::BM * 2 : 0);
+    if (int rc = set_max_lds_once<k_gemm_h2<CF, TAG>>(LDS)) return rc;
+    hipLaunchKernelGGL((k_gemm_h2<CF, TAG>), dim3(gemm_grid(num_mt, (N / CF::BN) * ksplit)), dim3(CF::NT), LDS, s, (const uint4*)in, W, scale, shift,
+                       ksplit > 1 ? (void*)slabs : out, d_count, g, num_mt, zero_line, flag, lut_ids);
+    if (ksplit > 1 && packed) {
+        const long long threads = (long long)max_count * P * (N / 8);
+        hipLaunchKernelGGL(k_splitk_reduce_h2, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, (const float*)slabs, slab, ksplit, N, P, d_count,
+                           scale, shift, relu, (uint4*)out, flag, low);
+    } else if (ksplit > 1 && defer && relu) *defer = OzDeferredReduce{slabs, slab, ksplit, scale, shift};
+    else if (ksplit > 1) launch_splitk_reduce_f32(slabs, slab, ksplit, N, P, max_count, d_count, scale, shift, relu, (float*)out, s);
+    OZ_HIP(hipGetLastError());
+    return OZ_OK;
+}
+
+// big: the 256 x 256 tile (k_gemm_b3_big; ksplit must be 1), else the 128 x 256 tile
+template <int TAG>
+static int launch_b3(const OzLayerShape& L, const uint4* in, const uint4* W, const float* scale, const float* shift, void* out, int packed, OzDeferredReduce* defer,
+                     const int* d_count, int max_count, bool big, int ksplit, float* slabs, long long slab, const uint4* zero_line, hipStream_t s, int relu = 1) {
+    OZ_REQUIRE(L.N % B3_BN == 0 && L.Cin % B3_BK == 0, "gemm_b3: N %% 256 and Cin %% 32 must be 0 (N=%d Cin=%d)", L.N, L.Cin);
+    if (defer) *defer = OzDeferredReduce();
+    B3Geom g;
+    oz_geom_set_shape(g, L);
+    g.out_b3 = packed; g.relu = relu; g.ksplit = ksplit; g.slab = slab;
+    const int P = L.pixels(), N = L.N, BM = big ? B3B_BM : B3_BM;
+    const int num_mt = (int)(((long long)max_count * P + BM - 1) / BM);
+    const dim3 grid(gemm_grid(num_mt, (N / B3_BN) * ksplit));
+    void* dst = ksplit > 1 ? (void*)slabs : out;
+    if (big) {
+        if (int rc = set_max_lds_once<k_gemm_b3_big<TAG>>(B3B_LDS)) return rc;
+        hipLaunchKernelGGL((k_gemm_b3_big<TAG>), grid, dim3(B3_NT), B3B_LDS, s, in, W, scale, shift, dst, d_count, g, num_mt, zero_line);
+    } else {
+        if (int rc = set_max_lds_once<k_gemm_b3<TAG>>(B3_LDS)) return rc;
+        hipLaunchKernelGGL((k_gemm_b3<TAG>), grid, dim3(B3_NT), B3_LDS, s, in, W, scale, shift, dst, d_count, g, num_mt, zero_line);
+    }
+    if (ksplit > 1 && packed) {                               // the consumer reads the b3 layout: fixed-order reduce + BN + ReLU + split
+        const long long threads = (long long)max_count * P * (N / 8);
+        hipLaunchKernelGGL(k_splitk_reduce_b3, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, (const float*)slabs, slab, ksplit, N, P, d_count,
+                           scale, shift, (uint4*)out);
+    } else if (ksplit > 1 && defer && relu) *defer = OzDeferredReduce{slabs, slab, ksplit, scale, shift};
+    else if (ksplit > 1) launch_splitk_reduce_f32(slabs, slab, ksplit, N, P, max_count, d_count, scale, shift, relu, (float*)out, s);
+    OZ_HIP(hipGetLastError());
+    return OZ_OK;
+}
+
+// the price of the two b3 tiles for `rows` x N outputs (tile_cost), the 256-row tile at 0.96 of its rows (measured at equal fill: 3.59 us per k-tile
+// against 2 x 1.87): true when a grid of 256 x 256 tiles fills the chip and pays no more than one of 128 x 256 tiles.  Callers add their own
+// conditions ('valid' padding, no k split, the screen option).
+static bool b3_big_tile_pays(long long rows, int N) {
+    auto paid = [&](int bm) { return (double)tile_cost(rows, N, bm); };
+    const long long big_blocks = ((rows + B3B_BM - 1) / B3B_BM) * (N / B3B_BN);
+    return big_blocks >= 192 && 0.96 * paid(B3B_BM) <= paid(B3_BM);
+}
+
 // k_gemm_h2 for callers outside the network object (the trainer's f16x2 mode): out[M][N] fp32 rows = (A . Wh^T) * scale + shift, A and Wh
 // in the h2 layout.  Tile and k-split are chosen from `max_count` (the caller's capacity -- a constant of the trainer, so a
 // row's result does not depend on the size of one call): the 256 x 256 ping-pong tile once it fills the chip, else
-// 128 x 128 tiles with the k loop split until every CU has a block (raw slabs + the fixed-order fp32 reduce).
+// 128 x 256 tiles with the k loop split until every CU has a block (raw slabs + the fixed-order fp32 reduce).
 int oz_gemm_h2_launch(const void* in_h2, const void* Wh, const float* scale, const float* shift, float* out, const int* d_count, int max_count,
                       int Hin, int Hout, int pad, int Cin, int taps, int N, hipStream_t s, float* partial, long long partial_floats,
                       const void* zero_line, int* flag) {
     OZ_REQUIRE(N % 256 == 0 && Cin % 32 == 0, "gemm_h2: N %% 256 and Cin %% 32 must be 0 (N=%d Cin=%d)", N, Cin);
-    static bool attr_set_dev[64] = {};                       // per device: function attributes belong to the device the caller is on
-    int dev_now = 0;
-    OZ_HIP(hipGetDevice(&dev_now));
-    bool& attr_set = attr_set_dev[dev_now & 63];
-    if (!attr_set) {
-        OZ_HIP(hipFuncSetAttribute((const void*)k_gemm_h2<H2BigPP>, hipFuncAttributeMaxDynamicSharedMemorySize, H2BigPP::LDS));
-        OZ_HIP(hipFuncSetAttribute((const void*)k_gemm_h2<H2MidPP>, hipFuncAttributeMaxDynamicSharedMemorySize, H2MidPP::LDS));
-        OZ_HIP(hipFuncSetAttribute((const void*)k_gemm_h2<H2LowPP>, hipFuncAttributeMaxDynamicSharedMemorySize, H2LowPP::LDS));
-        OZ_HIP(hipFuncSetAttribute((const void*)k_gemm_h2<H2Small>, hipFuncAttributeMaxDynamicSharedMemorySize, H2Small::LDS));
-        OZ_HIP(hipFuncSetAttribute((const void*)k_gemm_h2<H2Small2>, hipFuncAttributeMaxDynamicSharedMemorySize, H2Small2::LDS));
-        attr_set = true;
-    }
-    H2Geom g;
-    g.Hin = Hin; g.Hout = Hout; g.pad = pad; g.Cin = Cin; g.taps = taps; g.N = N; g.K = taps * Cin; g.out_h2 = 0; g.relu = 0;
-    const long long Mmax = (long long)max_count * Hout * Hout;
-    g.slab = Mmax * N;
-    const long long big_blocks = ((Mmax + 255) / 256) * (N / 256);
-    const bool big = big_blocks >= 192;
-    // between the two ping-pong tiles, the one whose grid pays fewer tile-rows (rounds of 256 CUs x tile height), as the inference forward
-    // picks conv3's: 1024 boards of conv3 = 36864 rows -> 256-row tiles 288 blocks = 2 rounds x 256, 192-row tiles 384 blocks = 2 x 192.
-    // Both add every output's products in the same order.
-    auto tile_cost = [&](int bm) { return ((((Mmax + bm - 1) / bm) * (N / 256) + 255) / 256) * bm; };
-    const bool mid = big && tile_cost(192) < tile_cost(256);
+    const OzLayerShape L = {Hin, Hout, pad, Cin, taps, N};
+    const long long Mmax = (long long)max_count * L.pixels();
+    const bool big = ((Mmax + 255) / 256) * (N / 256) >= 192;
+    // between the two ping-pong tiles, the one whose grid pays fewer tile-rows, as the inference forward picks conv3's
+    const bool mid = big && tile_cost(Mmax, N, 192) < tile_cost(Mmax, N, 256);
     // (round 5, measured and removed: a few 256 x 256 tiles with an 8 .. 16-way k split for launches of 8 .. 96 big tiles -- the trainer's GEMMs at the
     //  reference's batch -- 45 us + a larger reduce against 40 us on the 128 x 128 tiles: 0.99 -> 1.04 ms per step)
     // launches too small for those: the 128 x 256 tile of the 2-phase ping-pong loop (8 waves, 24 MFMAs per M section) with the k loop split until
     // every CU has a block -- twice the 128 x 128 tile's work per k-tile in about the same time (1.0 against 1.06 us).  Needs a k-slice of >= 8 tiles.
     const bool low = !big && partial != nullptr;
-    const int BM = mid ? 192 : big ? 256 : 128, BN = (big || low) ? 256 : 128;
-    const int num_mt = (int)((Mmax + BM - 1) / BM);
-    int ksplit = 1;
-    if (!big && partial) {
-        const long long blocks = (long long)num_mt * (N / BN);
-        const int nk = g.K / H2_BK;
-        // the largest split <= 16 that keeps the grid within one round of the 256 CUs (any number of slices: the k range is divided proportionally)
-        while (ksplit < 16 && blocks * (ksplit + 1) <= 256 && nk / (ksplit + 1) >= 8 && (long long)(ksplit + 1) * Mmax * N <= partial_floats) ++ksplit;
-    }
-    g.ksplit = ksplit;
-    const int per_mt = (N / BN) * ksplit;
-    const int grid = num_mt < 8 ? ((per_mt + 7) / 8) * 8 * num_mt : ((num_mt + 7) / 8) * 8 * per_mt;       // (the kernel's two block mappings)
-    void* dst = ksplit > 1 ? (void*)partial : (void*)out;
-    if (mid)
-        hipLaunchKernelGGL(k_gemm_h2<H2MidPP>, dim3(grid), dim3(H2MidPP::NT), H2MidPP::LDS, s, (const uint4*)in_h2, (const uint4*)Wh, scale, shift, dst,
-                           d_count, g, num_mt, (const uint4*)zero_line, flag, (const unsigned*)nullptr);
-    else if (big)
-        hipLaunchKernelGGL(k_gemm_h2<H2BigPP>, dim3(grid), dim3(H2BigPP::NT), H2BigPP::LDS, s, (const uint4*)in_h2, (const uint4*)Wh, scale, shift, dst,
-                           d_count, g, num_mt, (const uint4*)zero_line, flag, (const unsigned*)nullptr);
-    else if (low)
-        // (round 6: the 1-phase / 3-stage loop of this tile, H2LowPP1, measured SLOWER here -- 1.00 against 0.93-0.96 ms per step at the reference's batch: the
-        //  trainer's k-slices are 8 .. 36 tiles and the deeper prologue, two tiles staged before the first MFMA, costs more than the halved barriers return)
-        hipLaunchKernelGGL(k_gemm_h2<H2LowPP>, dim3(grid), dim3(H2LowPP::NT), H2LowPP::LDS, s, (const uint4*)in_h2, (const uint4*)Wh, scale, shift, dst,
-                           d_count, g, num_mt, (const uint4*)zero_line, flag, (const unsigned*)nullptr);
-    else
-        hipLaunchKernelGGL(k_gemm_h2<H2Small>, dim3(grid), dim3(H2Small::NT), H2Small::LDS, s, (const uint4*)in_h2, (const uint4*)Wh, scale, shift, dst,
-                           d_count, g, num_mt, (const uint4*)zero_line, flag, (const unsigned*)nullptr);
-    if (ksplit > 1) {
-        const long long quads = (Mmax * N + 3) / 4;
-        hipLaunchKernelGGL(k_splitk_reduce_f32, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, s, (const float*)partial, g.slab, ksplit, N,
-                           Hout * Hout, d_count, scale, shift, 0, out);
-    }
-    OZ_HIP(hipGetLastError());
-    return OZ_OK;
+    const int ksplit = low ? trainer_ksplit(((Mmax + 127) / 128) * (N / 256), L.K() / H2_BK, Mmax * N, partial_floats) : 1;
+    auto go = [&](auto cf) {
+        return launch_h2<decltype(cf)>(L, in_h2, (const uint4*)Wh, scale, shift, out, 0, nullptr, d_count, max_count, ksplit, partial, Mmax * N,
+                                       (const uint4*)zero_line, flag, s, 0);
+    };
+    // (round 6: the 1-phase / 3-stage loop of the 128 x 256 tile, H2LowPP1, measured SLOWER here -- 1.00 against 0.93-0.96 ms per step at the reference's batch: the
+    //  trainer's k-slices are 8 .. 36 tiles and the deeper prologue, two tiles staged before the first MFMA, costs more than the halved barriers return)
+    return mid ? go(H2MidPP()) : big ? go(H2BigPP()) : low ? go(H2LowPP()) : go(H2Small());
 }
 
 // k_gemm_b3 for callers outside the network object (the trainer's bf16x3 mode): out[M][N] fp32 rows = act((A . Wb^T) * scale + shift), A and
 // Wb in the b3 layout, relu 0 or 1.  Tile and k-split are chosen from `max_count` (the caller's capacity -- a constant of the trainer, so a row's
 // result does not depend on the size of one call): the 256 x 256 tile for unsplit 'valid' layers whose grid fills the chip on it (the network
-// object's rule), else the 128 x 256 tile with the k loop split until every CU has a block (raw slabs in `partial`, then the fixed-order fp32
-// reduce with scale / shift / act).  `tag` 0 / 1 only names the kernel in a profile (forward / data gradient).  NetObj::launch_gemm_b3 is
-// untouched: the inference forward keeps its own tiles and splits.
+// object's pricing, b3_big_tile_pays), else the 128 x 256 tile with the k loop split until every CU has a block (raw slabs in `partial`, then the
+// fixed-order fp32 reduce with scale / shift / act).  `tag` 0 / 1 only names the kernel in a profile (forward / data gradient).  The inference
+// forward launches through the same launch_b3 with its own tiles and splits (OnnNet::launch_gemm_b3).
 int oz_gemm_b3_launch(const void* in_b3, const void* Wb, const float* scale, const float* shift, float* out, const int* d_count, int max_count,
                       int Hin, int Hout, int pad, int Cin, int taps, int N, int relu, hipStream_t s, float* partial, long long partial_floats,
                       const void* zero_line, int tag) {
-    OZ_REQUIRE(N % B3_BN == 0 && Cin % B3_BK == 0, "gemm_b3: N %% 256 and Cin %% 32 must be 0 (N=%d Cin=%d)", N, Cin);
-    static bool attr_set_dev[64] = {};                       // per device: function attributes belong to the device the caller is on
-    int dev_now = 0;
-    OZ_HIP(hipGetDevice(&dev_now));
-    bool& attr_set = attr_set_dev[dev_now & 63];
-    if (!attr_set) {
-        OZ_HIP(hipFuncSetAttribute((const void*)k_gemm_b3<7>, hipFuncAttributeMaxDynamicSharedMemorySize, B3_LDS));
-        OZ_HIP(hipFuncSetAttribute((const void*)k_gemm_b3<8>, hipFuncAttributeMaxDynamicSharedMemorySize, B3_LDS));
-        OZ_HIP(hipFuncSetAttribute((const void*)k_gemm_b3_big<7>, hipFuncAttributeMaxDynamicSharedMemorySize, B3B_LDS));
-        OZ_HIP(hipFuncSetAttribute((const void*)k_gemm_b3_big<8>, hipFuncAttributeMaxDynamicSharedMemorySize, B3B_LDS));
-        attr_set = true;
-    }
-    B3Geom g;
-    g.Hin = Hin; g.Hout = Hout; g.pad = pad; g.Cin = Cin; g.taps = taps; g.N = N; g.K = taps * Cin; g.out_b3 = 0; g.relu = relu;
-    const long long Mmax = (long long)max_count * Hout * Hout;
-    g.slab = Mmax * N;
-    auto paid = [&](int bm) { return (double)(((((Mmax + bm - 1) / bm) * (N / B3_BN)) + 255) / 256) * bm; };
-    const long long big_blocks = ((Mmax + B3B_BM - 1) / B3B_BM) * (N / B3B_BN);
-    const bool big = pad == 0 && big_blocks >= 192 && 0.96 * paid(B3B_BM) <= paid(B3_BM);
-    const int BMt = big ? B3B_BM : B3_BM;
-    const int num_mt = (int)((Mmax + BMt - 1) / BMt);
-    int ksplit = 1;
-    if (!big && partial) {
-        const long long blocks = (long long)num_mt * (N / B3_BN);
-        const int nk = g.K / B3_BK;
-        // the largest split <= 16 that keeps the grid within one round of the 256 CUs (one 144 KB block per CU), >= 8 k-tiles per slice
-        while (ksplit < 16 && blocks * (ksplit + 1) <= 256 && nk / (ksplit + 1) >= 8 && (long long)(ksplit + 1) * Mmax * N <= partial_floats) ++ksplit;
-    }
-    g.ksplit = ksplit;
-    const int per_mt = (N / B3_BN) * ksplit;
-    const int grid = num_mt < 8 ? ((per_mt + 7) / 8) * 8 * num_mt : ((num_mt + 7) / 8) * 8 * per_mt;       // (the kernels' two block mappings)
-    void* dst = ksplit > 1 ? (void*)partial : (void*)out;
-    const uint4 *a = (const uint4*)in_b3, *w = (const uint4*)Wb, *z = (const uint4*)zero_line;
-    if (big && tag) hipLaunchKernelGGL(k_gemm_b3_big<8>, dim3(grid), dim3(B3_NT), B3B_LDS, s, a, w, scale, shift, dst, d_count, g, num_mt, z);
-    else if (big) hipLaunchKernelGGL(k_gemm_b3_big<7>, dim3(grid), dim3(B3_NT), B3B_LDS, s, a, w, scale, shift, dst, d_count, g, num_mt, z);
-    else if (tag) hipLaunchKernelGGL(k_gemm_b3<8>, dim3(grid), dim3(B3_NT), B3_LDS, s, a, w, scale, shift, dst, d_count, g, num_mt, z);
-    else hipLaunchKernelGGL(k_gemm_b3<7>, dim3(grid), dim3(B3_NT), B3_LDS, s, a, w, scale, shift, dst, d_count, g, num_mt, z);
-    if (ksplit > 1) {
-        const long long quads = (Mmax * N + 3) / 4;
-        hipLaunchKernelGGL(k_splitk_reduce_f32, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, s, (const float*)partial, g.slab, ksplit, N,
-                           Hout * Hout, d_count, scale, shift, relu, out);
-    }
-    OZ_HIP(hipGetLastError());
-    return OZ_OK;
+    const OzLayerShape L = {Hin, Hout, pad, Cin, taps, N};
+    const long long Mmax = (long long)max_count * L.pixels();
+    const bool big = pad == 0 && b3_big_tile_pays(Mmax, N);
+    // (one 144 KB block per CU)
+    const int ksplit = !big && partial ? trainer_ksplit(((Mmax + B3_BM - 1) / B3_BM) * (N / B3_BN), L.K() / B3_BK, Mmax * N, partial_floats) : 1;
+    auto go = [&](auto t) {
+        return launch_b3<decltype(t)::value>(L, (const uint4*)in_b3, (const uint4*)Wb, scale, shift, out, 0, nullptr, d_count, max_count, big, ksplit, partial,
+                                             Mmax * N, (const uint4*)zero_line, s, relu);
+    };
+    return tag ? go(std::integral_constant<int, 8>()) : go(std::integral_constant<int, 7>());
 }
 // k_f32_to_b3 for callers outside the network object: fp32 rows [*d_count * P][C] -> the b3 layout (grid sized for max_count boards)
 int oz_f32_to_b3_launch(const float* x, const int* d_count, int max_count, int P, int C, void* out, hipStream_t s) {
@@ -856,6 +880,7 @@ struct OnnNet : oz_net {
     int profile = 0;
     OzTimer timer{OZ_NET_KERNELS};
     int tables_mode = -1;            // oz_net_set_tables: -1 = default (2), 0 / 1 / 2 see forward_h2
+    OzLayers layers() const { return oz_onn_layers(n, C); }     // conv2, conv3, conv4, fc1, fc2 (index = `layer` of the launch wrappers - 1)
     int sizing() const { return max_batch; }     // the batch size the k-splits of the medium path are chosen for: the capacity, a per-network constant
     size_t partial_cap = 0;          // floats d_partial holds
     bool latency_splits = false;     // oz_net_set_option(OZ_NET_OPT_LATENCY_SPLITS): see conv_ksplit
@@ -883,8 +908,6 @@ struct OnnNet : oz_net {
     int w_target_log2 = H2_W_TOP;    // OZ_NET_OPT_W_TARGET_LOG2: every weight column's largest |w| lands in [2^(target-1), 2^target)
     int low_guard_log2 = H2_LOW_GUARD;  // OZ_NET_OPT_LOW_GUARD_LOG2 (<= -100: guard off); committed value below
     float low_thr = 0.f;
-    H2Low next_low;                  // guard of the NEXT launch_gemm_h2 (consumed by it)
-    int next_relu = 1;               // 0: the NEXT launch_gemm_h2 writes the BN output without the ReLU (calibration passes; consumed by it)
     int self_check = 1;              // OZ_NET_OPT_SELF_CHECK: compare with the exact-fp32 kernels on the calibration positions at commit
     double sc_dpi = -1.0, sc_dv = -1.0;                          // what the last commit's self-check measured (oz_net_self_check)
     int sc_positions = 0;
@@ -900,7 +923,7 @@ struct OnnNet : oz_net {
     // positions of capacity run the exact-fp32 forward as it is (their layers are weight streams / split-K launches: latency, not matrix rate) --
     // a per-network constant, so a position's result does not depend on the size of the call it sits in.
     uint4* d_wb[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // conv2 (the all-GEMM form only), conv3, conv4, fc1, fc2
-    uint4* b3a1 = nullptr;           // conv1's output in the b3 layout (the all-GEMM form only: allocated at its first use)
+    uint4* b3a1 = nullptr;           // conv1's output in the b3 layout (the all-GEMM form only: ensure_b3a1)
     uint4 *b3a2 = nullptr, *b3a3 = nullptr, *b3a4 = nullptr, *b3f1 = nullptr;   // conv2 / conv3 / conv4 / fc1 outputs in the b3 layout
     float* d_part_b3 = nullptr;                              // fc1's k-slices (fixed-order fp32 reduce)
     bool use_b3() const { return precision == 2 && max_batch >= B3_MIN_BATCH; }
@@ -918,8 +941,32 @@ struct OnnNet : oz_net {
         while (k < 8 && blocks * k < 192) k *= 2;
         return k;
     }
+    // b3a1 exists exactly where a forward may need it: a committed network of precision bf16x3 on the b3 kernels with the tables off.  oz_net_commit
+    // and (on a committed network) oz_net_set_tables call this, in either order; default networks never allocate it, and the forward path allocates nothing
+    int ensure_b3a1() {
+        if (b3a1 || !use_b3() || (tables_mode != 0 && tables_mode != 1)) return OZ_OK;
+        return alloc(&b3a1, (size_t)max_batch * n * n * (C / 32 * 12));
+    }
     int fc2_b3_ksplit() const {                              // fc2 (512 columns = 2 column tiles, 32 k-tiles): 4 slices of 8 k-tiles; the heads kernel adds them
         return 4;
+    }
+
+    // HIP events around the launches of one profile slot (slot order: OZ_NET_KERNELS in the header), from construction to the end of the scope:
+    // profile mode 2 times every slot, mode 1 only the dominant launch's (slot profiled_layer - 1); otherwise nothing is recorded
+    struct TimedSlot {
+        OzTimer* t = nullptr;
+        hipStream_t s;
+        long long h = -1;
+        TimedSlot(OnnNet* o, int slot, hipStream_t s_) : s(s_) {
+            if (o->profile == 2 || (o->profile == 1 && slot == o->profiled_layer - 1)) { t = &o->timer; h = t->begin(slot, s); }
+        }
+        ~TimedSlot() { if (t) t->end(h, s); }
+        TimedSlot(const TimedSlot&) = delete;
+    };
+    // start of a forward: names the dominant launch; no host stall inside an enqueue loop -- only pairs that have completed are folded
+    void begin_timing(int dominant_layer) {
+        profiled_layer = dominant_layer;
+        if (profile && timer.backlog() > 4096) timer.drain();
     }
 
     template <typename T> int alloc(T** p, size_t count) {
@@ -929,10 +976,8 @@ struct OnnNet : oz_net {
     }
     std::vector<int64_t> sizes() const {
         std::vector<int64_t> s;
-        const int cins[4] = {cin, C, C, C};
-        for (int l = 0; l < 4; ++l) { s.push_back(9ll * cins[l] * C); for (int k = 0; k < 5; ++k) s.push_back(C); }
-        s.push_back((int64_t)F * 1024); for (int k = 0; k < 5; ++k) s.push_back(1024);
-        s.push_back(1024ll * 512); for (int k = 0; k < 5; ++k) s.push_back(512);
+        s.push_back(9ll * cin * C); for (int k = 0; k < 5; ++k) s.push_back(C);            // conv1: kernel, then bias + the four BN arrays
+        for (const OzLayerShape& L : layers()) { s.push_back((int64_t)L.K() * L.N); for (int k = 0; k < 5; ++k) s.push_back(L.N); }
         s.push_back(512ll * A); s.push_back(A); s.push_back(512); s.push_back(1);
         return s;
     }
@@ -942,10 +987,11 @@ struct OnnNet : oz_net {
         for (void* p : allocs) hipFree(p);
     }
 
-    int launch_gemm(const float* in, const float* Wt, int layer, float* out, const int* d_count, int max_count, int Hin,
-                    int Hout, int pad, int Cin, int taps, int N, hipStream_t s, OzDeferredReduce* defer = nullptr) {
+    // layer: 1..3 = conv2..4, 4 = fc1, 5 = fc2
+    int launch_gemm(const float* in, int layer, float* out, const int* d_count, int max_count, hipStream_t s, OzDeferredReduce* defer = nullptr) {
+        const OzLayerShape L = layers()[layer - 1];
         // small and medium networks (max_batch <= 512) split K over the idle CUs: latency, not throughput
-        return oz_gemm_f32_launch(in, Wt, d_scale[layer], d_shift[layer], out, d_count, max_count, Hin, Hout, pad, Cin, taps, N, 1, s,
+        return oz_gemm_f32_launch(in, d_wt[layer - 1], d_scale[layer], d_shift[layer], out, d_count, max_count, L.Hin, L.Hout, L.pad, L.Cin, L.taps, L.N, 1, s,
                                   d_part32, d_part32 ? (long long)part32_floats() : 0, sizing(), 0, -1,
                                   layer == 2 ? &last_conv3_rows : nullptr, f32_std_tile ? 1 : 0, defer);  // layer 2 = conv3: what oz_net_get_info reports
     }
@@ -983,65 +1029,32 @@ struct OnnNet : oz_net {
     // loop) with half the k-slices the 256-row tile would need to fill the chip: the arena's 512-game networks 2 slices of 72 k-tiles instead of
     // 4 of 36 (83 + 14 us -> see DESIGN.md); a per-network constant like every k-split
     bool conv4_low() const {
-        const long long rows = (long long)sizing() * (n - 4) * (n - 4);
+        const long long rows = (long long)sizing() * layers()[2].pixels();
         return sizing() > 32 && sizing() <= 1024 && ((rows + 127) / 128) * (C / 256) <= 256;
     }
     size_t partial_floats() const {
         if (max_batch <= 32) return (size_t)16 * max_batch * 64 * 1024;
         size_t need = (size_t)(sizing() >= 1024 ? 4 : 16) * max_batch * 1024;        // fc1 (forward_h2: kfc1)
-        const int px[3] = {n * n, (n - 2) * (n - 2), (n - 4) * (n - 4)}, bm[3] = {256, 192, conv4_low() ? 128 : 256};
+        const OzLayers L = layers();
+        const int bm[3] = {256, 192, conv4_low() ? 128 : 256};
         for (int i = 0; i < 3; ++i) {
-            int k = conv_ksplit(px[i], bm[i]);
-            if (i == 1 && conv_ksplit(px[i], 256) > k) k = conv_ksplit(px[i], 256);          // conv3 may run on either tile
-            if (k > 1 && (size_t)k * max_batch * px[i] * C > need) need = (size_t)k * max_batch * px[i] * C;
+            const int px = L[i].pixels();
+            int k = conv_ksplit(px, bm[i]);
+            if (i == 1 && conv_ksplit(px, 256) > k) k = conv_ksplit(px, 256);          // conv3 may run on either tile
+            if (k > 1 && (size_t)k * max_batch * px * C > need) need = (size_t)k * max_batch * px * C;
         }
         return need;
     }
 
-    // layer: 1..3 = conv2..4 (3x3, Cin = N = C), 4 = fc1, 5 = fc2 (taps 1)
+    // layer: 1..3 = conv2..4 (3x3, Cin = N = C), 4 = fc1, 5 = fc2 (taps 1), on tile CF with the k loop in `ksplit` slices (slabs in d_partial, spaced
+    // for max_batch).  out_h2 = 1: the layer's output in the h2 layout, guarded by `low`; out_h2 = 0: fp32 rows -- fc2's (the heads kernel adds the
+    // slices of a split launch: fc2_defer), or, for conv2 .. fc1, a calibration pass: the layer's BN output BEFORE the ReLU
     template <typename CF, int TAG = 0>
-    int launch_gemm_h2(const void* in, int layer, void* out, int out_h2, const int* d_count, int max_count, int Hin,
-                       int Hout, int pad, int Cin, int taps, int N, hipStream_t s, int ksplit = 1,
-                       const unsigned* lut_ids = nullptr, const uint4* w_alt = nullptr, const float* scale_alt = nullptr,
-                       const float* shift_alt = nullptr, int relu = 1) {
-        H2Geom g;
-        g.Hin = Hin; g.Hout = Hout; g.pad = pad; g.Cin = Cin; g.taps = taps; g.N = N; g.K = taps * Cin; g.out_h2 = out_h2; g.relu = relu;
-        g.ksplit = ksplit; g.slab = (long long)max_batch * Hout * Hout * N;
-        const H2Low low = next_low;               // the guard of this launch's h2 output, if the caller armed one
-        next_low = H2Low();
-        if (!next_relu) { relu = 0; g.relu = 0; next_relu = 1; }          // calibration pass: the layer's BN output before the ReLU
-        if (out_h2 && ksplit == 1) g.low = low;
-        const long long Mmax = (long long)max_count * Hout * Hout;
-        const int num_mt = (int)((Mmax + CF::BM - 1) / CF::BM);
-        const int per_mt = (N / CF::BN) * ksplit;
-        const int grid = num_mt < 8 ? ((per_mt + 7) / 8) * 8 * num_mt : ((num_mt + 7) / 8) * 8 * per_mt;   // (the kernel's two block mappings)
-        void* out_final = out;
-        if (ksplit > 1) out = d_partial;          // raw k-slice sums; k_splitk_reduce_h2 below writes out_final (h2 layout)
-        {   // the dynamic-LDS limit of THIS instantiation, once per device
-            static bool attr_done[64] = {};
-            if (!attr_done[device & 63]) {
-                OZ_HIP(hipFuncSetAttribute((const void*)k_gemm_h2<CF, TAG>, hipFuncAttributeMaxDynamicSharedMemorySize, CF::LDS + (CF::LUT ? 9 * CF::BM * 2 : 0)));
-                attr_done[device & 63] = true;
-            }
-        }
-        hipLaunchKernelGGL((k_gemm_h2<CF, TAG>), dim3(grid), dim3(CF::NT), CF::LDS + (CF::LUT ? 9 * CF::BM * 2 : 0), s, (const uint4*)in,
-                           w_alt ? w_alt : (const uint4*)d_wh[layer - 1], scale_alt ? scale_alt : d_scale_h2[layer - 1],
-                           shift_alt ? shift_alt : d_shift_h2[layer - 1], out, d_count, g, num_mt, d_zero, d_flag, lut_ids);
-        if (ksplit > 1 && out_h2) {
-            const long long threads = (long long)max_count * Hout * Hout * (N / 8);
-            hipLaunchKernelGGL(k_splitk_reduce_h2, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, (const float*)d_partial,
-                               g.slab, ksplit, N, Hout * Hout, d_count, d_scale_h2[layer - 1], d_shift_h2[layer - 1], 1, (uint4*)out_final, d_flag, low);
-        } else if (ksplit > 1 && layer == 5 && relu && !scale_alt) {      // fc2: the heads kernel adds the slices (launch_heads)
-            fc2_defer.partial = d_partial; fc2_defer.slab = g.slab; fc2_defer.ksplit = ksplit;
-            fc2_defer.scale = d_scale_h2[layer - 1]; fc2_defer.shift = d_shift_h2[layer - 1];
-        } else if (ksplit > 1) {                  // fp32 rows out (calibration passes): the fp32 path's fixed-order reduce
-            const long long quads = ((long long)max_count * Hout * Hout * N + 3) / 4;
-            hipLaunchKernelGGL(k_splitk_reduce_f32, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, s, (const float*)d_partial, g.slab, ksplit, N,
-                               Hout * Hout, d_count, scale_alt ? scale_alt : d_scale_h2[layer - 1], shift_alt ? shift_alt : d_shift_h2[layer - 1], relu,
-                               (float*)out_final);
-        }
-        OZ_HIP(hipGetLastError());
-        return OZ_OK;
+    int launch_gemm_h2(const void* in, int layer, void* out, int out_h2, H2Low low, const int* d_count, int max_count, hipStream_t s, int ksplit = 1,
+                       const unsigned* lut_ids = nullptr) {
+        const OzLayerShape L = layers()[layer - 1];
+        return launch_h2<CF, TAG>(L, in, d_wh[layer - 1], d_scale_h2[layer - 1], d_shift_h2[layer - 1], out, out_h2, layer == 5 ? &fc2_defer : nullptr, d_count,
+                                  max_count, ksplit, d_partial, (long long)max_batch * L.pixels() * L.N, d_zero, d_flag, s, out_h2 || layer == 5, low, lut_ids);
     }
 
     // small tiles (dense layers, latency path): three LDS stages for medium and large networks (-4 .. -6 % per forward at 128 .. 512
@@ -1084,9 +1097,8 @@ struct OnnNet : oz_net {
         return lo;
     }
 
-    // T2[t] = table . W_t^T (raw k-sums, column c scaled 2^wexp[0][c] like the convolution's): nine GEMMs M = OZ_LUT_PATTERNS, K = N = C
-    int build_t2() {
-        // d_wtap (conv2's kernel as nine [C][C] matrices in the h2 layout, same power-of-two scale as d_wh[0]) was written by oz_net_commit
+    // what both forms of the T2 tables need: unit scale / zero shift / the row count of the table GEMMs, the tables and one tap's staging rows
+    int alloc_t2() {
         if (!d_one) {
             if (int rc = alloc(&d_one, (size_t)C)) return rc;
             if (int rc = alloc(&d_nul, (size_t)C)) return rc;
@@ -1098,11 +1110,19 @@ struct OnnNet : oz_net {
             OZ_HIP(hipMemcpy(d_rows, &rows, sizeof(int), hipMemcpyHostToDevice));
         }
         if (!d_t2) { if (int rc = alloc(&d_t2, (size_t)9 * OZ_LUT_ROWS * C)) return rc; }
+        if (!d_t2rows) { if (int rc = alloc(&d_t2rows, (size_t)OZ_LUT_PATTERNS * C)) return rc; }
+        return OZ_OK;
+    }
+
+    // T2[t] = table . W_t^T (raw k-sums, column c scaled 2^wexp[0][c] like the convolution's): nine GEMMs M = OZ_LUT_PATTERNS, K = N = C
+    int build_t2() {
+        // d_wtap (conv2's kernel as nine [C][C] matrices in the h2 layout, same power-of-two scale as d_wh[0]) was written by oz_net_commit
+        if (int rc0 = alloc_t2()) return rc0;
         int rc = OZ_OK;
-        if (!d_t2rows) { if (int rc2 = alloc(&d_t2rows, (size_t)OZ_LUT_PATTERNS * C)) return rc2; }
+        const OzLayerShape tap = {1, 1, 0, C, 1, C};        // a dense [OZ_LUT_PATTERNS][C] x [C][C] product, raw sums (scale 1, shift 0, no ReLU) as fp32 rows
         for (int t = 0; t < 9 && rc == OZ_OK; ++t) {        // one tap at a time: GEMM rows -> staging -> slice-major records (same stream: ordered)
-            rc = launch_gemm_h2<H2BigPP>(d_lut, 1, d_t2rows, 0, d_rows, OZ_LUT_PATTERNS, 1, 1, 0, C, 1, C, 0, 1, nullptr,
-                                         d_wtap + (size_t)t * C * (C / 4), d_one, d_nul, 0);
+            rc = launch_h2<H2BigPP>(tap, d_lut, d_wtap + (size_t)t * C * (C / 4), d_one, d_nul, d_t2rows, 0, nullptr, d_rows, OZ_LUT_PATTERNS, 1, nullptr,
+                                    (long long)max_batch * C, d_zero, d_flag, 0, 0);
             const long long quads = (long long)OZ_LUT_ROWS * C / 4;
             hipLaunchKernelGGL(k_t2_to_slices, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, 0, d_t2rows, C, t, d_t2);
         }
@@ -1116,18 +1136,7 @@ struct OnnNet : oz_net {
         if (!d_lut32) { if (int rc = alloc(&d_lut32, (size_t)OZ_LUT_PATTERNS * C)) return rc; }
         if (!d_lut_ids) { if (int rc = alloc(&d_lut_ids, (size_t)max_batch * (n + 2) * (n + 2))) return rc; }
         if (!d_wtap32) { if (int rc = alloc(&d_wtap32, (size_t)9 * C * C)) return rc; }
-        if (!d_one) {
-            if (int rc = alloc(&d_one, (size_t)C)) return rc;
-            if (int rc = alloc(&d_nul, (size_t)C)) return rc;
-            if (int rc = alloc(&d_rows, (size_t)1)) return rc;
-            std::vector<float> one((size_t)C, 1.0f);
-            const int rows = OZ_LUT_PATTERNS;
-            OZ_HIP(hipMemcpy(d_one, one.data(), sizeof(float) * C, hipMemcpyHostToDevice));
-            OZ_HIP(hipMemset(d_nul, 0, sizeof(float) * C));
-            OZ_HIP(hipMemcpy(d_rows, &rows, sizeof(int), hipMemcpyHostToDevice));
-        }
-        if (!d_t2) { if (int rc = alloc(&d_t2, (size_t)9 * OZ_LUT_ROWS * C)) return rc; }
-        if (!d_t2rows) { if (int rc2 = alloc(&d_t2rows, (size_t)OZ_LUT_PATTERNS * C)) return rc2; }
+        if (int rc = alloc_t2()) return rc;
         const long long threads = (long long)OZ_LUT_PATTERNS * C;
         hipLaunchKernelGGL(k_lut_build_f32, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, 0, C, d_w1, d_scale[0], d_shift[0], d_lut32);
         OZ_HIP(hipGetLastError());
@@ -1165,10 +1174,11 @@ struct OnnNet : oz_net {
     //   the calibration positions as fp32 rows -> per-channel maxima -> aexp[i + 1], folded into the layer's scale and shift.
     int commit_h2() {
         const int gl[5] = {6, 12, 18, 24, 30};
-        const int Ks[5] = {9 * C, 9 * C, 9 * C, F, 1024}, Ns[5] = {C, C, C, 1024, 512};
+        const OzLayers L = layers();
         const int Wt[5] = {C, C, C, C, 1024};                                          // channels of tensor t
-        const size_t rows_t[5] = {(size_t)max_batch * n * n, (size_t)max_batch * n * n, (size_t)max_batch * (n - 2) * (n - 2),
-                                  (size_t)max_batch * (n - 4) * (n - 4), (size_t)max_batch};
+        // pixel rows of tensor t: act1 (conv2's input), then the outputs of conv2 .. fc1
+        const size_t rows_t[5] = {(size_t)max_batch * n * n, (size_t)max_batch * L[0].pixels(), (size_t)max_batch * L[1].pixels(),
+                                  (size_t)max_batch * L[2].pixels(), (size_t)max_batch * L[3].pixels()};
         const int wide = std::max(C, 1024);
         if (!d_flag) { if (int rc = alloc(&d_flag, 1)) return rc; }
         OZ_HIP(hipMemset(d_flag, 0, sizeof(int)));
@@ -1203,7 +1213,6 @@ struct OnnNet : oz_net {
             ~ProfileOff() { p = keep; }
         } profile_off(profile);
         float* const act_of[4] = {act2, act3, act4, f1};
-        const int P_of[4] = {n * n, (n - 2) * (n - 2), (n - 4) * (n - 4), 1};
         // Pass 0 calibrates (maxima -> [2^(H2_ACT_TOP - 1), 2^H2_ACT_TOP)) and builds every image as it goes.  Another OZ_NET_OPT_ACT_TARGET_LOG2
         // (a test hook / the window experiments of tools/target_probe.py) is applied AFTERWARDS as an exact bump of every exponent, and pass 1
         // rebuilds the images from the bumped exponents without calibrating: the calibration passes themselves never run outside the fp16
@@ -1254,7 +1263,7 @@ struct OnnNet : oz_net {
             }
             for (int i = 0; i < 5; ++i) {
                 const auto& src = w[gl[i]];
-                const int K = Ks[i], N = Ns[i], Cmod = Wt[i], taps = i < 3 ? 9 : 1;
+                const int K = L[i].K(), N = L[i].N, Cmod = Wt[i], taps = L[i].taps;
                 OZ_REQUIRE(src.size() == (size_t)K * N, "weight %d has %zu values, expected %zu", gl[i], src.size(), (size_t)K * N);
                 OZ_HIP(hipMemcpy(d_raw, src.data(), sizeof(float) * src.size(), hipMemcpyHostToDevice));
                 if (calibrating) {
@@ -1293,8 +1302,8 @@ struct OnnNet : oz_net {
                     const int cnt = std::min(max_batch, cal_total - c0);
                     OZ_HIP(hipMemcpy(d_cal_count, &cnt, sizeof(int), hipMemcpyHostToDevice));
                     if (int rc = forward_h2(d_cal_own + c0, d_cal_opp + c0, d_cal_count, cnt, nullptr, nullptr, 0, i + 1)) return rc;
-                    const long long rows = (long long)cnt * P_of[i];
-                    hipLaunchKernelGGL(k_rows_colmax, dim3((N + 255) / 256, (unsigned)((rows + 63) / 64)), dim3(256), 0, 0, act_of[i], d_cal_count, P_of[i], N, d_colmax);
+                    const long long rows = (long long)cnt * L[i].pixels();
+                    hipLaunchKernelGGL(k_rows_colmax, dim3((N + 255) / 256, (unsigned)((rows + 63) / 64)), dim3(256), 0, 0, act_of[i], d_cal_count, L[i].pixels(), N, d_colmax);
                     OZ_HIP(hipGetLastError());
                     OZ_HIP(hipDeviceSynchronize());                   // d_cal_count is rewritten for the next chunk
                 }
@@ -1330,12 +1339,13 @@ struct OnnNet : oz_net {
     // OZ_NET_OPT_SELF_CHECK: 0 off, 2 measure only (the commit succeeds; oz_net_self_check / OZ_NET_INFO_SELF_CHECK_GUARD say what was seen).
     int run_self_check() {
         const int gl[5] = {6, 12, 18, 24, 30};
-        const int Ks[5] = {9 * C, 9 * C, 9 * C, F, 1024}, Ns[5] = {C, C, C, 1024, 512};
+        const OzLayers L = layers();
         for (int i = 0; i < 5; ++i) {
             const auto& src = w[gl[i]];
+            const int K = L[i].K(), N = L[i].N;
             OZ_HIP(hipMemcpy(d_raw, src.data(), sizeof(float) * src.size(), hipMemcpyHostToDevice));
-            if (!d_wt[i]) { if (int rc = alloc(&d_wt[i], (size_t)Ks[i] * Ns[i])) return rc; }
-            hipLaunchKernelGGL(k_w_transpose, dim3((Ks[i] + 31) / 32, (Ns[i] + 31) / 32), dim3(256), 0, 0, d_raw, Ks[i], Ns[i], d_wt[i]);
+            if (!d_wt[i]) { if (int rc = alloc(&d_wt[i], (size_t)K * N)) return rc; }
+            hipLaunchKernelGGL(k_w_transpose, dim3((K + 31) / 32, (N + 31) / 32), dim3(256), 0, 0, d_raw, K, N, d_wt[i]);
             OZ_HIP(hipGetLastError());
             OZ_HIP(hipDeviceSynchronize());
         }
@@ -1416,18 +1426,10 @@ struct OnnNet : oz_net {
         const bool use_t2 = want_t2 && t2_ok;
         const bool use_lut = !use_t2 && pp && want_lut && lut_ok && max_batch > 32;
         // HIP events around the dominant launch (the conv2 GEMM, or conv3 when conv2 is the gather-sum), or around every kernel
-        profiled_layer = use_t2 ? 3 : 2;
-        if (profile && timer.backlog() > 4096) timer.drain();          // no host stall inside an enqueue loop: only pairs that have completed
-        long long tidx = -1;
-        auto mark = [&](int slot, bool begin) {
-            if (!(profile == 2 || (profile == 1 && slot == profiled_layer - 1))) return;
-            if (begin) tidx = timer.begin(slot, s);
-            else { timer.end(tidx, s); tidx = -1; }
-        };
+        begin_timing(use_t2 ? 3 : 2);
         const bool guard = calib == 0;
         if (guard) { fwd_seq = (fwd_seq + 1) & 0x3FFFFFFu; if (!fwd_seq) fwd_seq = 1; }
-        mark(0, true);
-        if (use_t2 || use_lut) {
+        if (TimedSlot t0(this, 0, s); use_t2 || use_lut) {
             const long long threads = (long long)max_count * (n + 2) * (n + 2);
             hipLaunchKernelGGL(k_lut_ids, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, d_own, d_opp, d_count, n, d_lut_ids,
                                (guard && low_thr > 0.f) ? d_lut_low : (const unsigned char*)nullptr, d_flag);
@@ -1436,7 +1438,6 @@ struct OnnNet : oz_net {
             hipLaunchKernelGGL(k_conv1_h2, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, d_own, d_opp, d_count, n, C,
                                d_w1, d_scale1_h2, d_shift1_h2, (uint4*)act1, d_flag, low_of(0, guard));
         }
-        mark(0, false);
         const bool small = max_batch <= 32;
         // small networks (the drop-in OthelloMCTS / agents path, one position per call): latency, not throughput --
         // 128 x 128 tiles with the k loop split 16 ways over otherwise idle CUs, fixed-order reduce (keyed on max_batch,
@@ -1453,193 +1454,133 @@ struct OnnNet : oz_net {
         //  of 2.0.  conv4 547 / 529 -> 508 us, not the 483 the round count promises (a round of 192-row tiles costs 0.84 of a 256-row round on conv4,
         //  235 against 280 us, not 0.75), and the layers that do not shrink with the cap eat most of it: 1.696 / 1.680 M -> 1.696 / 1.691 M
         //  expansions/s, within the run-to-run spread.)
-        auto tile_cost = [&](int BM) {
-            const long long blocks = (((long long)max_count * (n - 2) * (n - 2) + BM - 1) / BM) * (C / 256);
-            return ((blocks + 255) / 256) * BM;
-        };
+        const OzLayers L = layers();
+        auto conv3_cost = [&](int BM) { return tile_cost((long long)max_count * L[1].pixels(), C, BM); };
         // ... and the 128-row tile when a call's rows fit ONE round on it but leave a third of the chip idle on the taller tiles (the arena's
         // <= 512-leaf batches: 430 leaves = 162 blocks of 192 rows, 242 of 128).  Its round costs CONV3_LOW_COST of the row-proportional figure
         // (24 instead of 36 MFMAs per phase of the 2-phase loop against the same LDS reads and barriers: 151 / 158 us against 172 / 177 us
         // for one round of 192-row tiles).
-        int c3rows = n == 6 ? 256 : tile_cost(256) < tile_cost(192) ? 256 : 192;
-        if (n != 6 && pp && (double)tile_cost(128) * CONV3_LOW_COST < (double)tile_cost(c3rows)) c3rows = 128;
+        int c3rows = n == 6 ? 256 : conv3_cost(256) < conv3_cost(192) ? 256 : 192;
+        if (n != 6 && pp && (double)conv3_cost(128) * CONV3_LOW_COST < (double)conv3_cost(c3rows)) c3rows = 128;
         if (conv3_tile && pp && !small) c3rows = conv3_tile;
         const bool conv3_big = c3rows == 256, conv3_low = c3rows == 128;
         last_conv3_rows = small ? 128 : pp ? c3rows : 192;
         // (the k-split stays a constant of the network -- max_batch and the board decide it, not the tile this call picked -- so a position's
         //  result does not depend on the size of the call it sits in)
-        const int k2 = conv_ksplit(n * n, 256), k3 = conv_ksplit((n - 2) * (n - 2), n == 6 ? 256 : 192),
-                  k4 = conv_ksplit((n - 4) * (n - 4), conv4_low() ? 128 : 256);
+        const int k2 = conv_ksplit(L[0].pixels(), 256), k3 = conv_ksplit(L[1].pixels(), n == 6 ? 256 : 192),
+                  k4 = conv_ksplit(L[2].pixels(), conv4_low() ? 128 : 256);
         // h2 output (and the low-side guard of the tensor) unless this is the layer a calibration pass wants as fp32 rows
         const int h2o1 = calib == 1 ? 0 : 1, h2o2 = calib == 2 ? 0 : 1, h2o3 = calib == 3 ? 0 : 1, h2o4 = calib == 4 ? 0 : 1;
-        mark(1, true);
-        if (use_t2) {
+        if (TimedSlot t1(this, 1, s); use_t2) {
             if (h2o1) launch_conv2_lut<true>(max_count, d_count, d_scale_h2[0], d_shift_h2[0], act2, s, low_of(1, guard));
             else launch_conv2_lut<false>(max_count, d_count, d_scale_h2[0], d_shift_h2[0], act2, s, H2Low(), -__builtin_inff());
         } else {
-            next_low = low_of(1, guard);
-            next_relu = h2o1;
-            if (int rc = small     ? launch_small<H2Small, H2Small2>(act1, 1, act2, h2o1, d_count, max_count, n, n, 1, C, 9, C, s, 16)
-                         : use_lut ? launch_gemm_h2<H2BigPPLut, 2>(d_lut, 1, act2, h2o1, d_count, max_count, n, n, 1, C, 9, C, s, k2, d_lut_ids)
-                         : pp      ? launch_gemm_h2<H2BigPP, 2>(act1, 1, act2, h2o1, d_count, max_count, n, n, 1, C, 9, C, s, k2)
-                                   : launch_gemm_h2<H2Big>(act1, 1, act2, h2o1, d_count, max_count, n, n, 1, C, 9, C, s, k2)) return rc;
+            const H2Low lo = low_of(1, guard);
+            if (int rc = small     ? launch_small<H2Small, H2Small2>(act1, 1, act2, h2o1, lo, d_count, max_count, s, 16)
+                         : use_lut ? launch_gemm_h2<H2BigPPLut, 2>(d_lut, 1, act2, h2o1, lo, d_count, max_count, s, k2, d_lut_ids)
+                         : pp      ? launch_gemm_h2<H2BigPP, 2>(act1, 1, act2, h2o1, lo, d_count, max_count, s, k2)
+                                   : launch_gemm_h2<H2Big>(act1, 1, act2, h2o1, lo, d_count, max_count, s, k2)) return rc;
         }
-        mark(1, false);
         if (calib == 1) { OZ_HIP(hipGetLastError()); return OZ_OK; }
-        mark(2, true);
         // (a 3-phase loop on the 192-row tile -- 24-MFMA clusters -- measured 0 .. +2 % in round 2: the layer is clock / power bound,
         //  not load-section bound; deleted in round 3)
-        next_low = low_of(2, guard);
-        next_relu = h2o2;
-        if (int rc = small ? launch_small<H2Small, H2Small2>(act2, 2, act3, h2o2, d_count, max_count, n, n - 2, 0, C, 9, C, s, 16)
-                     : pp && conv3_big ? launch_gemm_h2<H2BigPP, 3>(act2, 2, act3, h2o2, d_count, max_count, n, n - 2, 0, C, 9, C, s, k3)
-                     : pp && conv3_low && low_loop_phases == 2 ? launch_gemm_h2<H2LowPP, 3>(act2, 2, act3, h2o2, d_count, max_count, n, n - 2, 0, C, 9, C, s, k3)
-                     : pp && conv3_low ? launch_gemm_h2<H2LowPP1, 3>(act2, 2, act3, h2o2, d_count, max_count, n, n - 2, 0, C, 9, C, s, k3)
-                     : pp  ? launch_gemm_h2<H2MidPP, 3>(act2, 2, act3, h2o2, d_count, max_count, n, n - 2, 0, C, 9, C, s, k3)
-                           : launch_gemm_h2<H2Mid>(act2, 2, act3, h2o2, d_count, max_count, n, n - 2, 0, C, 9, C, s, k3)) return rc;
-        mark(2, false);
+        {
+            TimedSlot t2(this, 2, s);
+            const H2Low lo = low_of(2, guard);
+            if (int rc = small ? launch_small<H2Small, H2Small2>(act2, 2, act3, h2o2, lo, d_count, max_count, s, 16)
+                         : pp && conv3_big ? launch_gemm_h2<H2BigPP, 3>(act2, 2, act3, h2o2, lo, d_count, max_count, s, k3)
+                         : pp && conv3_low && low_loop_phases == 2 ? launch_gemm_h2<H2LowPP, 3>(act2, 2, act3, h2o2, lo, d_count, max_count, s, k3)
+                         : pp && conv3_low ? launch_gemm_h2<H2LowPP1, 3>(act2, 2, act3, h2o2, lo, d_count, max_count, s, k3)
+                         : pp  ? launch_gemm_h2<H2MidPP, 3>(act2, 2, act3, h2o2, lo, d_count, max_count, s, k3)
+                               : launch_gemm_h2<H2Mid>(act2, 2, act3, h2o2, lo, d_count, max_count, s, k3)) return rc;
+        }
         if (calib == 2) { OZ_HIP(hipGetLastError()); return OZ_OK; }
-        mark(3, true);
-        next_low = low_of(3, guard);
-        next_relu = h2o3;
-        if (int rc = small ? launch_small<H2Small, H2Small2>(act3, 3, act4, h2o3, d_count, max_count, n - 2, n - 4, 0, C, 9, C, s, 16)
-                     : pp && conv4_low() && low_loop_phases == 2 ? launch_gemm_h2<H2LowPP, 4>(act3, 3, act4, h2o3, d_count, max_count, n - 2, n - 4, 0, C, 9, C, s, k4)
-                     : pp && conv4_low() ? launch_gemm_h2<H2LowPP1, 4>(act3, 3, act4, h2o3, d_count, max_count, n - 2, n - 4, 0, C, 9, C, s, k4)
-                     : pp  ? launch_gemm_h2<H2BigPP, 4>(act3, 3, act4, h2o3, d_count, max_count, n - 2, n - 4, 0, C, 9, C, s, k4)
-                           : launch_gemm_h2<H2Big>(act3, 3, act4, h2o3, d_count, max_count, n - 2, n - 4, 0, C, 9, C, s, k4)) return rc;
-        mark(3, false);
+        {
+            TimedSlot t3(this, 3, s);
+            const H2Low lo = low_of(3, guard);
+            if (int rc = small ? launch_small<H2Small, H2Small2>(act3, 3, act4, h2o3, lo, d_count, max_count, s, 16)
+                         : pp && conv4_low() && low_loop_phases == 2 ? launch_gemm_h2<H2LowPP, 4>(act3, 3, act4, h2o3, lo, d_count, max_count, s, k4)
+                         : pp && conv4_low() ? launch_gemm_h2<H2LowPP1, 4>(act3, 3, act4, h2o3, lo, d_count, max_count, s, k4)
+                         : pp  ? launch_gemm_h2<H2BigPP, 4>(act3, 3, act4, h2o3, lo, d_count, max_count, s, k4)
+                               : launch_gemm_h2<H2Big>(act3, 3, act4, h2o3, lo, d_count, max_count, s, k4)) return rc;
+        }
         if (calib == 3) { OZ_HIP(hipGetLastError()); return OZ_OK; }
-        mark(4, true);
         // fc1: K = 8192 but only batch x 1024 outputs -> split-K (fixed-order reduce) to fill the chip
         // (large batches: on the 256 x 256 ping-pong tile, 16 x 4 tiles x 4 k-slices = one block per CU; bit-identical to
         //  the 128 x 128 tile because the k-slices and the order inside them are the same -- tools/pp_race_check.py)
-        next_low = low_of(4, guard);
-        next_relu = h2o4;
         // (medium networks, max_batch < 1024: 16 k-slices on the 128 x 256 tile of the 2-phase ping-pong loop -- fc1 at 512 rows is 16 output tiles,
         //  x 16 slices = one block of 16 k-tiles per CU: 34 us in the arena's 512-leaf batches; 8 slices on 128 x 128 tiles 41 us, 4 slices 58 us
         //  (round 5); the split is keyed on max_batch, a per-network constant)
-        const int kfc1 = sizing() >= 1024 ? 4 : 16;
-        if (int rc = small ? launch_small<H2Small, H2Small2>(act4, 4, f1, h2o4, d_count, max_count, 1, 1, 0, F, 1, 1024, s, 16)
-                     : (pp && sizing() >= 1024 && max_count >= 1024) ? launch_gemm_h2<H2BigPP, 5>(act4, 4, f1, h2o4, d_count, max_count, 1, 1, 0, F, 1, 1024, s, 4)
-                     : pp && low_loop_phases == 2 ? launch_gemm_h2<H2LowPP, 5>(act4, 4, f1, h2o4, d_count, max_count, 1, 1, 0, F, 1, 1024, s, kfc1)
-                     : pp ? launch_gemm_h2<H2LowPP1, 5>(act4, 4, f1, h2o4, d_count, max_count, 1, 1, 0, F, 1, 1024, s, kfc1)
-                          : launch_small<H2Small, H2Small2>(act4, 4, f1, h2o4, d_count, max_count, 1, 1, 0, F, 1, 1024, s, kfc1)) return rc;
-        mark(4, false);
+        {
+            TimedSlot t4(this, 4, s);
+            const H2Low lo = low_of(4, guard);
+            const int kfc1 = sizing() >= 1024 ? 4 : 16;
+            if (int rc = small ? launch_small<H2Small, H2Small2>(act4, 4, f1, h2o4, lo, d_count, max_count, s, 16)
+                         : (pp && sizing() >= 1024 && max_count >= 1024) ? launch_gemm_h2<H2BigPP, 5>(act4, 4, f1, h2o4, lo, d_count, max_count, s, 4)
+                         : pp && low_loop_phases == 2 ? launch_gemm_h2<H2LowPP, 5>(act4, 4, f1, h2o4, lo, d_count, max_count, s, kfc1)
+                         : pp ? launch_gemm_h2<H2LowPP1, 5>(act4, 4, f1, h2o4, lo, d_count, max_count, s, kfc1)
+                              : launch_small<H2Small, H2Small2>(act4, 4, f1, h2o4, lo, d_count, max_count, s, kfc1)) return rc;
+        }
         if (calib == 4) { OZ_HIP(hipGetLastError()); return OZ_OK; }
-        mark(5, true);
         // fc2: one position has 4 blocks of 32 k-tiles -> small and medium networks split k 8 ways (from max_batch); the heads kernel adds the slices
         // (large networks: one k-slice on the four-wave form of the thin tile, bit-identical to the two-wave one)
-        if (int rc = sizing() > 512 ? launch_gemm_h2<H2Thin4w, 6>(f1, 5, f2, 0, d_count, max_count, 1, 1, 0, 1024, 1, 512, s, 1)
-                                   : launch_small<H2Thin, H2Thin2>(f1, 5, f2, 0, d_count, max_count, 1, 1, 0, 1024, 1, 512, s, 8)) return rc;
-        mark(5, false);
-        mark(6, true);
-        launch_heads(max_count, d_count, d_pi, d_v, s);
-        mark(6, false);
+        {
+            TimedSlot t5(this, 5, s);
+            if (int rc = sizing() > 512 ? launch_gemm_h2<H2Thin4w, 6>(f1, 5, f2, 0, H2Low(), d_count, max_count, s, 1)
+                                       : launch_small<H2Thin, H2Thin2>(f1, 5, f2, 0, H2Low(), d_count, max_count, s, 8)) return rc;
+        }
+        {
+            TimedSlot t6(this, 6, s);
+            launch_heads(max_count, d_count, d_pi, d_v, s);
+        }
         OZ_HIP(hipGetLastError());
         return OZ_OK;
     }
 
     // layer: 1 = conv2 (the all-GEMM form), 2 = conv3, 3 = conv4 (3x3, Cin = N = C), 4 = fc1, 5 = fc2 (taps 1); the d_scale / d_shift of precision f32 (no power-of-two bookkeeping)
+    // out_b3 = 1: the b3 layout for the next GEMM; 0: fp32 rows (fc2: the heads kernel adds the slices, fc2_defer).  k-slices go to d_part_b3, spaced for max_batch.
     template <int TAG>
-    int launch_gemm_b3(const uint4* in, int layer, void* out, int out_b3, const int* d_count, int max_count, int Hin, int Hout, int pad,
-                       int Cin, int taps, int N, hipStream_t s, int ksplit = 1) {
-        B3Geom g;
-        g.Hin = Hin; g.Hout = Hout; g.pad = pad; g.Cin = Cin; g.taps = taps; g.N = N; g.K = taps * Cin; g.out_b3 = out_b3; g.relu = 1;
-        g.ksplit = ksplit; g.slab = (long long)max_batch * Hout * Hout * N;
-        OZ_REQUIRE(N % B3_BN == 0 && Cin % B3_BK == 0, "gemm_b3: N %% 256 and Cin %% 32 must be 0 (N=%d Cin=%d)", N, Cin);
-        const long long Mmax = (long long)max_count * Hout * Hout;
+    int launch_gemm_b3(const uint4* in, int layer, void* out, int out_b3, const int* d_count, int max_count, hipStream_t s, int ksplit = 1) {
+        const OzLayerShape L = layers()[layer - 1];
         // the 256 x 256 tile (two thirds of the operand bytes per MFMA: the small tile is bound by its LDS-DMA stream out of the L2s) for unsplit 'valid'
         // layers whose grid fills the chip on it -- keyed on the CAPACITY of the network (max_batch), like every tile / split choice, so that a position's
         // bits do not depend on the call (they would not anyway: both tiles add the same products in the same order; OZ_NET_OPT_B3_TILE screens that)
-        // Which tile: the one whose grid pays fewer tile-rows at the network's capacity (rounds of the 256 CUs x tile height), the 256-row tile priced at
-        // 0.96 of its rows (measured at equal fill: 3.59 us per k-tile against 2 x 1.87).  4096 positions of 8x8: conv3 = 9 rounds of 128 rows against 5 (4.5
-        // paid as 5) of 256 -> the small tile; conv4 = 4 rounds of 128 against 2.0 of 256 -> the big one (974 against 1048 us at 3916 leaves).  The tile does not
-        // dissolve the kernel's real bound, which turned out to be the clock under load, not the L2 stream (docs/HISTORY.md, round 6).
-        const long long rows_cap = (long long)max_batch * Hout * Hout;
-        auto paid = [&](int bm) { return (double)(((((rows_cap + bm - 1) / bm) * (N / B3_BN)) + 255) / 256) * bm; };
-        const long long big_blocks = ((rows_cap + B3B_BM - 1) / B3B_BM) * (N / B3B_BN);
-        const bool big = b3_tile != 128 && pad == 0 && ksplit == 1 && (b3_tile == 256 || (big_blocks >= 192 && 0.96 * paid(B3B_BM) <= paid(B3_BM)));
+        // Which tile: the one whose grid pays fewer tile-rows at the network's capacity (b3_big_tile_pays).  4096 positions of 8x8: conv3 = 9 rounds of 128
+        // rows against 5 (4.5 paid as 5) of 256 -> the small tile; conv4 = 4 rounds of 128 against 2.0 of 256 -> the big one (974 against 1048 us at 3916
+        // leaves).  The tile does not dissolve the kernel's real bound, which turned out to be the clock under load, not the L2 stream (docs/HISTORY.md, round 6).
+        const long long rows_cap = (long long)max_batch * L.pixels();
+        const bool big = b3_tile != 128 && L.pad == 0 && ksplit == 1 && (b3_tile == 256 || b3_big_tile_pays(rows_cap, L.N));
         if (layer == 2) last_conv3_rows = big ? B3B_BM : B3_BM;
-        const int BMt = big ? B3B_BM : B3_BM;
-        const int num_mt = (int)((Mmax + BMt - 1) / BMt);
-        const int per_mt = (N / B3_BN) * ksplit;
-        const int grid = num_mt < 8 ? ((per_mt + 7) / 8) * 8 * num_mt : ((num_mt + 7) / 8) * 8 * per_mt;   // (the kernels' two block mappings)
-        {
-            static bool attr_done[64] = {};
-            if (!attr_done[device & 63]) {
-                OZ_HIP(hipFuncSetAttribute((const void*)k_gemm_b3<TAG>, hipFuncAttributeMaxDynamicSharedMemorySize, B3_LDS));
-                OZ_HIP(hipFuncSetAttribute((const void*)k_gemm_b3_big<TAG>, hipFuncAttributeMaxDynamicSharedMemorySize, B3B_LDS));
-                attr_done[device & 63] = true;
-            }
-        }
-        void* dst = ksplit > 1 ? (void*)d_part_b3 : out;
-        if (big)
-            hipLaunchKernelGGL((k_gemm_b3_big<TAG>), dim3(grid), dim3(B3_NT), B3B_LDS, s, in, (const uint4*)d_wb[layer - 1], d_scale[layer], d_shift[layer], dst,
-                               d_count, g, num_mt, d_zero);
-        else
-            hipLaunchKernelGGL((k_gemm_b3<TAG>), dim3(grid), dim3(B3_NT), B3_LDS, s, in, (const uint4*)d_wb[layer - 1], d_scale[layer], d_shift[layer], dst,
-                               d_count, g, num_mt, d_zero);
-        if (ksplit > 1 && layer == 5) {           // fc2: the heads kernel adds the slices in fixed order (launch_heads), BN + ReLU there
-            fc2_defer.partial = d_part_b3; fc2_defer.slab = g.slab; fc2_defer.ksplit = ksplit; fc2_defer.scale = d_scale[layer]; fc2_defer.shift = d_shift[layer];
-        } else if (ksplit > 1 && out_b3) {        // the consumer reads the b3 layout: fixed-order reduce + BN + ReLU + split
-            const long long threads = (long long)max_count * Hout * Hout * (N / 8);
-            hipLaunchKernelGGL(k_splitk_reduce_b3, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, (const float*)d_part_b3, g.slab, ksplit, N,
-                               Hout * Hout, d_count, d_scale[layer], d_shift[layer], (uint4*)out);
-        } else if (ksplit > 1) {                  // fp32 rows out: the fp32 path's fixed-order reduce (BN + ReLU there)
-            const long long quads = ((long long)max_count * Hout * Hout * N + 3) / 4;
-            hipLaunchKernelGGL(k_splitk_reduce_f32, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, s, (const float*)d_part_b3, g.slab, ksplit, N,
-                               Hout * Hout, d_count, d_scale[layer], d_shift[layer], 1, (float*)out);
-        }
-        OZ_HIP(hipGetLastError());
-        return OZ_OK;
+        return launch_b3<TAG>(L, in, d_wb[layer - 1], d_scale[layer], d_shift[layer], out, out_b3, layer == 5 ? &fc2_defer : nullptr, d_count, max_count, big,
+                              ksplit, d_part_b3, rows_cap * L.N, d_zero, s);
     }
 
     // precision bf16x3, networks of >= B3_MIN_BATCH positions: gather (exact fp32 tables) -> b3 rows -> conv3 / conv4 / fc1 on k_gemm_b3 -> fc2 and heads in fp32
     int forward_b3(const uint64_t* d_own, const uint64_t* d_opp, const int* d_count, int max_count, float* d_pi, float* d_v, hipStream_t s) {
         const bool use_t2f = (tables_mode < 0 || tables_mode >= 2) && t2f_ok;      // else (oz_net_set_tables 0 / 1): conv1 kernel + conv2 as a b3 GEMM
         last_conv3_rows = B3_BM;                     // (set by conv3's launch below)
-        profiled_layer = use_t2f ? 3 : 2;            // the dominant launch: conv3 on k_gemm_b3, or conv2 on it when the tables are off
-        if (profile && timer.backlog() > 4096) timer.drain();
-        long long tidx = -1;
-        auto mark = [&](int slot, bool begin) {
-            if (!(profile == 2 || (profile == 1 && slot == profiled_layer - 1))) return;
-            if (begin) tidx = timer.begin(slot, s);
-            else { timer.end(tidx, s); tidx = -1; }
-        };
+        begin_timing(use_t2f ? 3 : 2);               // the dominant launch: conv3 on k_gemm_b3, or conv2 on it when the tables are off
+        const OzLayers L = layers();
         const long long cells = (long long)max_count * (n + 2) * (n + 2);
-        mark(0, true);
-        if (use_t2f)
+        if (TimedSlot t0(this, 0, s); use_t2f)
             hipLaunchKernelGGL(k_lut_ids, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, d_own, d_opp, d_count, n, d_lut_ids,
                                (const unsigned char*)nullptr, (int*)nullptr);
         else {
             const long long threads = (long long)max_count * n * n * (C / 4);
             hipLaunchKernelGGL(k_conv1, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, d_own, d_opp, d_count, n, C, d_w1, d_scale[0], d_shift[0], act1);
         }
-        mark(0, false);
-        mark(1, true);
-        if (use_t2f) launch_conv2_lut<2>(max_count, d_count, d_scale[1], d_shift[1], b3a2, s);      // the gather writes the b3 layout itself
-        else {      // every layer as a kernel / GEMM: conv1's rows split into the three planes, conv2 on k_gemm_b3 like the rest ('same' padding: the 128-row tile)
-            if (!b3a1) { if (int rc = alloc(&b3a1, (size_t)max_batch * n * n * (C / 32 * 12))) return rc; }
+        if (TimedSlot t1(this, 1, s); use_t2f) launch_conv2_lut<2>(max_count, d_count, d_scale[1], d_shift[1], b3a2, s);      // the gather writes the b3 layout itself
+        else {      // every layer as a kernel / GEMM: conv1's rows split into the three planes (b3a1: oz_net_commit / oz_net_set_tables), conv2 on k_gemm_b3 like the rest ('same' padding: the 128-row tile)
+            OZ_REQUIRE(b3a1, "forward_b3: the all-GEMM form has no conv1 operand buffer");
             const long long threads = (long long)max_count * n * n * (C / 8);
             hipLaunchKernelGGL(k_f32_to_b3, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, act1, d_count, n * n, C, b3a1);
-            if (int rc = launch_gemm_b3<2>(b3a1, 1, b3a2, 1, d_count, max_count, n, n, 1, C, 9, C, s, conv_b3_ksplit(n * n))) return rc;
+            if (int rc = launch_gemm_b3<2>(b3a1, 1, b3a2, 1, d_count, max_count, s, conv_b3_ksplit(L[0].pixels()))) return rc;
         }
-        mark(1, false);
-        mark(2, true);
-        if (int rc = launch_gemm_b3<3>(b3a2, 2, b3a3, 1, d_count, max_count, n, n - 2, 0, C, 9, C, s, conv_b3_ksplit((n - 2) * (n - 2)))) return rc;
-        mark(2, false);
-        mark(3, true);
-        if (int rc = launch_gemm_b3<4>(b3a3, 3, b3a4, 1, d_count, max_count, n - 2, n - 4, 0, C, 9, C, s, conv_b3_ksplit((n - 4) * (n - 4)))) return rc;
-        mark(3, false);
-        mark(4, true);
-        if (int rc = launch_gemm_b3<5>(b3a4, 4, b3f1, 1, d_count, max_count, 1, 1, 0, F, 1, 1024, s, fc1_b3_ksplit())) return rc;
-        mark(4, false);
-        mark(5, true);
-        if (int rc = launch_gemm_b3<6>(b3f1, 5, f2, 0, d_count, max_count, 1, 1, 0, 1024, 1, 512, s, fc2_b3_ksplit())) return rc;
-        mark(5, false);
-        mark(6, true);
-        launch_heads(max_count, d_count, d_pi, d_v, s);
-        mark(6, false);
+        { TimedSlot t2(this, 2, s); if (int rc = launch_gemm_b3<3>(b3a2, 2, b3a3, 1, d_count, max_count, s, conv_b3_ksplit(L[1].pixels()))) return rc; }
+        { TimedSlot t3(this, 3, s); if (int rc = launch_gemm_b3<4>(b3a3, 3, b3a4, 1, d_count, max_count, s, conv_b3_ksplit(L[2].pixels()))) return rc; }
+        { TimedSlot t4(this, 4, s); if (int rc = launch_gemm_b3<5>(b3a4, 4, b3f1, 1, d_count, max_count, s, fc1_b3_ksplit())) return rc; }
+        { TimedSlot t5(this, 5, s); if (int rc = launch_gemm_b3<6>(b3f1, 5, f2, 0, d_count, max_count, s, fc2_b3_ksplit())) return rc; }
+        { TimedSlot t6(this, 6, s); launch_heads(max_count, d_count, d_pi, d_v, s); }
         OZ_HIP(hipGetLastError());
         return OZ_OK;
     }
@@ -1660,55 +1601,37 @@ struct OnnNet : oz_net {
         // precision f32: conv1 + conv2 from the fp32 pattern tables (default), or conv1 kernel + conv2 GEMM (oz_net_set_tables 0 / 1)
         const bool use_t2f = (tables_mode < 0 || tables_mode >= 2) && t2f_ok;
         last_conv3_rows = 0;             // set by conv3's launch below (launch_gemm, layer 2): 64 weight stream / 128 GmStd / 256 GmBig
-        profiled_layer = use_t2f ? 3 : 2;
-        if (profile && timer.backlog() > 4096) timer.drain();          // no host stall inside an enqueue loop: only pairs that have completed
-        long long tidx = -1;
-        auto mark = [&](int slot, bool begin) {
-            if (!(profile == 2 || (profile == 1 && slot == profiled_layer - 1))) return;
-            if (begin) tidx = timer.begin(slot, s);
-            else { timer.end(tidx, s); tidx = -1; }
-        };
+        begin_timing(use_t2f ? 3 : 2);
         if (use_t2f && max_batch <= 32 && C == 512) {
             // few positions: pattern ids computed inside the gather (INLINE_IDS) -- one launch less
-            mark(1, true);
+            TimedSlot t1(this, 1, s);
             const unsigned blocks = 8u * (unsigned)(((long long)max_count * P + 32 * OZ_C2L_PPT - 1) / (32 * OZ_C2L_PPT));
             if (n == 8) hipLaunchKernelGGL((k_conv2_lut_xcd<8, false, true>), dim3(blocks), dim3(256), 0, s, (const unsigned*)nullptr, d_count, d_t2, d_scale[1], d_shift[1], (void*)act2, (int*)nullptr, H2Low(), 0.f, d_own, d_opp);
             else hipLaunchKernelGGL((k_conv2_lut_xcd<6, false, true>), dim3(blocks), dim3(256), 0, s, (const unsigned*)nullptr, d_count, d_t2, d_scale[1], d_shift[1], (void*)act2, (int*)nullptr, H2Low(), 0.f, d_own, d_opp);
-            mark(1, false);
         } else if (use_t2f) {
             const long long cells = (long long)max_count * (n + 2) * (n + 2);
-            mark(0, true);
-            hipLaunchKernelGGL(k_lut_ids, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, d_own, d_opp, d_count, n, d_lut_ids,
-                               (const unsigned char*)nullptr, (int*)nullptr);
-            mark(0, false);
-            mark(1, true);
+            {
+                TimedSlot t0(this, 0, s);
+                hipLaunchKernelGGL(k_lut_ids, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, d_own, d_opp, d_count, n, d_lut_ids,
+                                   (const unsigned char*)nullptr, (int*)nullptr);
+            }
+            TimedSlot t1(this, 1, s);
             launch_conv2_lut<false>(max_count, d_count, d_scale[1], d_shift[1], act2, s);
-            mark(1, false);
         } else {
             const long long threads = (long long)max_count * P * (C / 4);
-            mark(0, true);
-            hipLaunchKernelGGL(k_conv1, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, d_own, d_opp, d_count, n, C,
-                               d_w1, d_scale[0], d_shift[0], act1);
-            mark(0, false);
-            mark(1, true);
-            if (int rc = launch_gemm(act1, d_wt[0], 1, act2, d_count, max_count, n, n, 1, C, 9, C, s)) return rc;
-            mark(1, false);
+            {
+                TimedSlot t0(this, 0, s);
+                hipLaunchKernelGGL(k_conv1, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, d_own, d_opp, d_count, n, C,
+                                   d_w1, d_scale[0], d_shift[0], act1);
+            }
+            TimedSlot t1(this, 1, s);
+            if (int rc = launch_gemm(act1, 1, act2, d_count, max_count, s)) return rc;
         }
-        mark(2, true);
-        if (int rc = launch_gemm(act2, d_wt[1], 2, act3, d_count, max_count, n, n - 2, 0, C, 9, C, s)) return rc;
-        mark(2, false);
-        mark(3, true);
-        if (int rc = launch_gemm(act3, d_wt[2], 3, act4, d_count, max_count, n - 2, n - 4, 0, C, 9, C, s)) return rc;
-        mark(3, false);
-        mark(4, true);
-        if (int rc = launch_gemm(act4, d_wt[3], 4, f1, d_count, max_count, 1, 1, 0, F, 1, 1024, s)) return rc;
-        mark(4, false);
-        mark(5, true);
-        if (int rc = launch_gemm(f1, d_wt[4], 5, f2, d_count, max_count, 1, 1, 0, 1024, 1, 512, s, &fc2_defer)) return rc;
-        mark(5, false);
-        mark(6, true);
-        launch_heads(max_count, d_count, d_pi, d_v, s);
-        mark(6, false);
+        { TimedSlot t2(this, 2, s); if (int rc = launch_gemm(act2, 2, act3, d_count, max_count, s)) return rc; }
+        { TimedSlot t3(this, 3, s); if (int rc = launch_gemm(act3, 3, act4, d_count, max_count, s)) return rc; }
+        { TimedSlot t4(this, 4, s); if (int rc = launch_gemm(act4, 4, f1, d_count, max_count, s)) return rc; }
+        { TimedSlot t5(this, 5, s); if (int rc = launch_gemm(f1, 5, f2, d_count, max_count, s, &fc2_defer)) return rc; }
+        { TimedSlot t6(this, 6, s); launch_heads(max_count, d_count, d_pi, d_v, s); }
         OZ_HIP(hipGetLastError());
         return OZ_OK;
     }
@@ -1909,10 +1832,10 @@ OZ_API int oz_net_commit(oz_net* net) {
     // re-laid out on the device: [N][K] fp32 for precision f32; the h2 layout [N][K/8][h1 x8 | h2 x8] in the GEMM's k order,
     // pre-scaled by an exact power of two, for precision f16x2 (k_w_transpose / k_w_to_h2; the host loops took 0.4 s per commit)
     const int gl[5] = {6, 12, 18, 24, 30};
-    const int Ks[5] = {9 * C, 9 * C, 9 * C, o->F, 1024}, Ns[5] = {C, C, C, 1024, 512};
+    const OzLayers L = o->layers();
     {
         size_t raw_max = 0;
-        for (int i = 0; i < 5; ++i) raw_max = std::max(raw_max, (size_t)Ks[i] * Ns[i]);
+        for (const OzLayerShape& l : L) raw_max = std::max(raw_max, (size_t)l.K() * l.N);
         if (!o->d_raw) { if (int rc = o->alloc(&o->d_raw, raw_max)) return rc; }
     }
     if (o->precision != 1 && !o->d_part32 && o->part32_mult() > 0) {
@@ -1921,11 +1844,9 @@ OZ_API int oz_net_commit(oz_net* net) {
     if (!o->act1) {
         const size_t B = (size_t)o->max_batch;
         if (int rc = o->alloc(&o->act1, B * n * n * C)) return rc;
-        if (int rc = o->alloc(&o->act2, B * n * n * C)) return rc;
-        if (int rc = o->alloc(&o->act3, B * (n - 2) * (n - 2) * C)) return rc;
-        if (int rc = o->alloc(&o->act4, B * (size_t)o->F)) return rc;
-        if (int rc = o->alloc(&o->f1, B * 1024)) return rc;
-        if (int rc = o->alloc(&o->f2, B * 512)) return rc;
+        float** const outs[5] = {&o->act2, &o->act3, &o->act4, &o->f1, &o->f2};          // the outputs of conv2 .. fc2
+        for (int i = 0; i < 5; ++i)
+            if (int rc = o->alloc(outs[i], B * L[i].pixels() * L[i].N)) return rc;
     }
     // the heads first: precision f16x2's commit ends with whole forwards (its self-check)
     if (int rc = upload(o, &o->d_wpi, o->w[36])) return rc;
@@ -1937,7 +1858,7 @@ OZ_API int oz_net_commit(oz_net* net) {
     if (o->precision != 1) {
         for (int i = 0; i < 5; ++i) {
             const auto& src = o->w[gl[i]];
-            const int K = Ks[i], N = Ns[i];
+            const int K = L[i].K(), N = L[i].N;
             OZ_REQUIRE(src.size() == (size_t)K * N, "weight %d has %zu values, expected %zu", gl[i], src.size(), (size_t)K * N);
             OZ_HIP(hipMemcpy(o->d_raw, src.data(), sizeof(float) * src.size(), hipMemcpyHostToDevice));
             if (!o->d_wt[i]) { if (int rc = o->alloc(&o->d_wt[i], (size_t)K * N)) return rc; }
@@ -1950,25 +1871,24 @@ OZ_API int oz_net_commit(oz_net* net) {
             }
             if (o->use_b3()) {                         // conv2 .. fc2 once more in the b3 layout (three bf16 planes, the GEMM's tap-inner k order)
                 if (!o->d_wb[i]) { if (int rc = o->alloc(&o->d_wb[i], (size_t)N * (K / 32) * 12)) return rc; }
-                if (int rc = oz_w_to_b3_launch(o->d_raw, K, N, i < 3 ? 9 : 1, o->d_wb[i], 0)) return rc;
+                if (int rc = oz_w_to_b3_launch(o->d_raw, K, N, L[i].taps, o->d_wb[i], 0)) return rc;
             }
             OZ_HIP(hipGetLastError());
             OZ_HIP(hipDeviceSynchronize());                       // d_raw is reused by the next layer
         }
         if (o->use_b3() && !o->b3a2) {
-            const size_t B = (size_t)o->max_batch, rq = (size_t)C / 32 * 12;        // uint4 per pixel row
-            if (int rc = o->alloc(&o->b3a2, B * n * n * rq)) return rc;
-            if (int rc = o->alloc(&o->b3a3, B * (n - 2) * (n - 2) * rq)) return rc;
-            if (int rc = o->alloc(&o->b3a4, B * (n - 4) * (n - 4) * rq)) return rc;
-            if (int rc = o->alloc(&o->b3f1, B * (1024 / 32 * 12))) return rc;
-            size_t part = (size_t)std::max(o->fc1_b3_ksplit() * 1024, o->fc2_b3_ksplit() * 512) * B;       // the largest set of k-slices any layer writes
-            const int px[3] = {n * n, (n - 2) * (n - 2), (n - 4) * (n - 4)};
+            const size_t B = (size_t)o->max_batch;                                  // (a pixel row of N channels = N / 32 * 12 uint4)
+            uint4** const outs[4] = {&o->b3a2, &o->b3a3, &o->b3a4, &o->b3f1};                // the outputs of conv2 .. fc1
+            for (int q = 0; q < 4; ++q)
+                if (int rc = o->alloc(outs[q], B * L[q].pixels() * (L[q].N / 32 * 12))) return rc;
+            size_t part = (size_t)std::max(o->fc1_b3_ksplit() * L[3].N, o->fc2_b3_ksplit() * L[4].N) * B;       // the largest set of k-slices any layer writes
             for (int q = 0; q < 3; ++q)
-                if (o->conv_b3_ksplit(px[q]) > 1) part = std::max(part, (size_t)o->conv_b3_ksplit(px[q]) * B * px[q] * C);
+                if (const int k = o->conv_b3_ksplit(L[q].pixels()); k > 1) part = std::max(part, (size_t)k * B * L[q].pixels() * C);
             if (int rc = o->alloc(&o->d_part_b3, part)) return rc;
             if (!o->d_zero) { if (int rc = o->alloc(&o->d_zero, 16)) return rc; }
             OZ_HIP(hipMemset(o->d_zero, 0, 256));
         }
+        if (int rc = o->ensure_b3a1()) return rc;
         if (int rc = o->build_t2_f32()) return rc;
     } else {
         if (int rc = o->commit_h2()) return rc;
@@ -2188,6 +2108,7 @@ OZ_API int oz_net_set_tables(oz_net* net, int mode) {
         if (int rc = eval_cache_clear(o)) return rc;
     }
     o->tables_mode = mode;
+    if (o->committed) { hipSetDevice(o->device); return o->ensure_b3a1(); }
     return OZ_OK;
 }
 

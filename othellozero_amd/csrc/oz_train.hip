@@ -1133,11 +1133,11 @@ OZ_API int oz_trainer_create(oz_trainer** out, int n, int channels, int in_chann
         T_ALLOC(t->P, t->total); T_ALLOC(t->M1, t->total); T_ALLOC(t->V2, t->total);
         if (external_grads) { t->G = external_grads; t->own_grads = false; } else T_ALLOC(t->G, t->total);
         for (int i = 0; i < 36; ++i) if (t->toff[i] < 0) { T_ALLOC(t->stats[i], t->size[i]); T_ALLOC(t->stats_new[i], t->size[i]); }
-        const int Hs[6] = {n, n, n - 2, n - 4, 1, 1};
+        const OzLayers L = oz_onn_layers(n, C);              // layer l >= 1 is GEMM layer l - 1; layer 0 = conv1 ('same', C filters)
         for (int l = 0; l < 6; ++l) {
-            t->Hout[l] = Hs[l]; t->P_[l] = Hs[l] * Hs[l]; t->Co[l] = l < 4 ? C : (l == 4 ? 1024 : 512);
+            t->Hout[l] = l ? L[l - 1].Hout : n; t->P_[l] = t->Hout[l] * t->Hout[l]; t->Co[l] = l ? L[l - 1].N : C;
             // conv3 / conv4 ('valid'): dz lives in a zero-bordered (Hout + 4)^2 buffer so that the data gradient is a plain valid conv
-            t->zoff[l] = (l == 2 || l == 3) ? 2 : 0; t->Hz[l] = Hs[l] + 2 * t->zoff[l];
+            t->zoff[l] = (l == 2 || l == 3) ? 2 : 0; t->Hz[l] = t->Hout[l] + 2 * t->zoff[l];
             const size_t rows = (size_t)max_batch * t->P_[l];
             T_ALLOC(t->z[l], rows * t->Co[l]); T_ALLOC(t->a[l], rows * t->Co[l]);
             T_ALLOC(t->dz[l], (size_t)max_batch * t->Hz[l] * t->Hz[l] * t->Co[l]);

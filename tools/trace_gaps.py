@@ -7,12 +7,18 @@ import csv, glob, os, sys
 from collections import defaultdict
 
 
+def read_kernel_trace(d):
+    """the rows (dicts keyed by rocprofv3's column names) of the kernel trace under directory d, by start time"""
+    f = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)[0]
+    with open(f) as fh:
+        return sorted(csv.DictReader(fh), key=lambda r: int(r["Start_Timestamp"]))
+
+
 def main():
     d = sys.argv[1]
     first = sys.argv[2] if len(sys.argv) > 2 else "k_lut_ids"
     skip = int(sys.argv[3]) if len(sys.argv) > 3 else 200
-    f = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)[0]
-    rows = sorted(csv.DictReader(open(f)), key=lambda r: int(r["Start_Timestamp"]))
+    rows = read_kernel_trace(d)
     fwd, cur = [], None
     for r in rows:
         if first in r["Kernel_Name"]:
