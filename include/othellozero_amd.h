@@ -42,7 +42,7 @@ extern "C" {
 #define OZ_LEAF_WAIT 3       /* free-running driver with a batch cap: the leaf is chosen and waits for a slot of a later batch */
 
 const char* oz_last_error(void);
-int oz_version(void);                 /* 200 */
+int oz_version(void);                 /* 210 */
 int oz_device_count(void);
 int oz_set_device(int device);       /* device used by objects created afterwards on this thread */
 
@@ -225,6 +225,31 @@ int oz_mcts_dump_node(oz_mcts* m, int game, int index, uint64_t* own, uint64_t* 
 /* counters since creation: [0] simulations [1] node visits [2] expansions [3] terminal hits [4] uniform-prior fallbacks */
 int oz_mcts_stats(oz_mcts* m, int64_t* out5);
 
+/* ---- leaf-parallel search: K = leaves_per_step descents per game and step under virtual loss (opt-in; the default 1 is the search above, bit for bit)
+ * For one game and one step, `left` = simulations of the simulate call still to run: min(K, left) descents, one after the other, each exactly
+ * the descent above except that an edge (s, a) which k > 0 earlier descents of this step took is seen as N' = N + k,
+ * Q' = ((double)N * Q - (double)k) / (double)(N + k) (float64; every in-flight descent counts as one visit that returned -1; k == 0 reads
+ * the stored bits) and the node as Ns + k(s) visits: U = Q' + (c * P) * (sqrt(Ns + k(s)) / (1 + N')).  A descent that ends on a finished
+ * board takes its place with the integer value; one that ends on an unknown state is a leaf, unless an earlier leaf of the step is the same
+ * board: then it is discarded (no simulation; counted as a collision) and the step closes for that game.  All leaves of all games form ONE
+ * network batch in (game, j) order; then per game, j ascending, leaf j is expanded and its value backed up along path j.  A simulate call
+ * runs steps until every active game has done exactly nsims simulations; a game's result depends on its own state only.
+ * K > 1 evaluates every leaf: no cross-game de-duplication and no evaluation cache (results would be identical), so
+ * leaves_evaluated == expansions.  OZ_QMODE_NEP50 at K > 1: the view is float64 in both regimes and every stored value goes through the
+ * same update as at K = 1, which the reference's traces hold through these kernels (oz_mcts_use_wide_kernels); it has no replay of its own.
+ * OZ_ERR_ARG: k outside 1 .. OZ_MCTS_MAX_LEAVES_PER_STEP, a network whose max_batch < num_games * k (here for the drivers, in
+ * oz_mcts_simulate for a bare search).  OZ_ERR_STATE: a change while a step is pending / after the first driver call, and for k > 1 the
+ * host-evaluator split (oz_mcts_select / leaves / backup) and the free-running driver oz_selfplay_run_steps (its batches are full already). */
+#define OZ_MCTS_MAX_LEAVES_PER_STEP 16
+/* the first k > 1 (or oz_mcts_use_wide_kernels) allocates the per-(game, j) arrays, sized for OZ_MCTS_MAX_LEAVES_PER_STEP whatever k is:
+ * 8.9 KB per game (the paths are 8 KB of it: 36 MB at 4 096 games) plus the batch and (pi, v) rows for num_games x 16 leaves */
+int oz_mcts_set_leaves_per_step(oz_mcts* m, int k);
+int oz_mcts_get_leaves_per_step(oz_mcts* m, int* k);
+/* diagnostic: run k = 1 through the leaf-parallel kernels */
+int oz_mcts_use_wide_kernels(oz_mcts* m, int enable);
+/* out[0] game-steps run by the leaf-parallel kernels, out[1] descents discarded on a collision, out[2] leaves handed to the network */
+int oz_mcts_wide_stats(oz_mcts* m, int64_t* out3);
+
 /* ------------------------------------------------------------------ self-play
  * execute_episode (training.py:26-72) for num_games concurrent games in lock step. */
 typedef struct oz_selfplay oz_selfplay;
@@ -295,6 +320,11 @@ int oz_selfplay_run_steps(oz_selfplay* sp, int steps);
 int oz_selfplay_set_batch_cap(oz_selfplay* sp, int cap);
 /* cross-game leaf de-duplication on / off from the next batch on (oz_selfplay_config.dedup sets the initial state) */
 int oz_selfplay_set_dedup(oz_selfplay* sp, int enable);
+/* leaves_per_step of the engine's search for the lock-step drivers oz_selfplay_run / oz_selfplay_stagger (see oz_mcts_set_leaves_per_step);
+ * before the first driver call.  With k > 1 the drivers read 4 bytes back per move round (the largest remaining budget), i.e. they synchronise
+ * the stream once per round and are no longer asynchronous; every leaf goes to the network: oz_selfplay_config.dedup and .eval_cache have no
+ * effect (records would be identical either way), leaves_evaluated == expansions. */
+int oz_selfplay_set_leaves_per_step(oz_selfplay* sp, int k);
 int oz_selfplay_sync(oz_selfplay* sp);
 /* continuous self-play (cfg.refill): bring a fresh engine to the steady state of a long-running one before measuring it --
  * slot g is advanced (g * P) / num_games plies into its first game, P = n*n - 4, by searched self-play moves at `sims_pre`
@@ -371,6 +401,9 @@ int oz_arena_leaves_evaluated(oz_arena* a, int64_t* black, int64_t* white);
 /* the two agents' leaves go through their networks' persistent evaluation caches (oz_net_set_eval_cache; default 0 = every leaf is evaluated):
  * identical moves, boards and results -- the reference's per-search _predict_cache (othelo_mcts.py:13,82-88) across games, plies and steps */
 int oz_arena_set_eval_cache(oz_arena* a, int enable);
+/* leaves_per_step of the BLACK (net_a) and WHITE (net_b) agent's search; before the first run.  The networks want max_batch >= num_games * k.
+ * With k > 1 an agent's leaves bypass the evaluation cache. */
+int oz_arena_set_leaves_per_step(oz_arena* a, int k_black, int k_white);
 /* HIP-event timing of the two agents' tree kernels on the launch stream, slots of oz_selfplay_profile (0 select 1 leaf compaction 2 evaluator = all
  * network launches 3 expand + backup 4 move), summed over both searches; the networks' own kernels: oz_net_profile on net_a / net_b */
 int oz_arena_profile(oz_arena* a, int enable);

@@ -22,6 +22,7 @@ NET_OPT_B3_TILE = 10
 NET_INFO_CONV3_TILE_ROWS, NET_INFO_SELF_CHECK_GUARD, NET_INFO_ARITHMETIC = 1, 2, 3                                                          # oz_net_get_info
 LEAF_IDLE, LEAF_TERMINAL, LEAF_EVAL = 0, 1, 2
 VT_INT, VT_F32, VT_F64 = 0, 1, 2
+MAX_LEAVES_PER_STEP = 16                                                             # OZ_MCTS_MAX_LEAVES_PER_STEP
 POLICY_LOSS_ROWS, POLICY_LOSS_FLAT = 0, 1                                            # oz_trainer_set_policy_loss
 NET_KERNELS = ("input", "conv2", "conv3", "conv4", "fc1", "fc2", "heads")           # OZ_NET_KERNELS slots
 TREE_KERNELS = ("select", "compact", "network", "expand_backup", "roots_move")       # OZ_TREE_KERNELS slots
@@ -106,6 +107,9 @@ SIGNATURES = {
     "oz_mcts_num_nodes": [_vp, _i32p],
     "oz_mcts_dump_node": [_vp, C.c_int, C.c_int, _u64p, _u64p, _i32p, _u64p, _i32p, _f64p, _u8p, _f64p],
     "oz_mcts_stats": [_vp, _i64p],
+    "oz_mcts_set_leaves_per_step": [_vp, C.c_int], "oz_mcts_get_leaves_per_step": [_vp, C.POINTER(C.c_int)],
+    "oz_mcts_use_wide_kernels": [_vp, C.c_int], "oz_mcts_wide_stats": [_vp, _i64p],
+    "oz_selfplay_set_leaves_per_step": [_vp, C.c_int], "oz_arena_set_leaves_per_step": [_vp, C.c_int, C.c_int],
     "oz_selfplay_create": [C.POINTER(_vp), C.POINTER(SelfplayConfig), _vp],
     "oz_selfplay_destroy": [_vp], "oz_selfplay_run": [_vp, C.c_int], "oz_selfplay_run_steps": [_vp, C.c_int], "oz_selfplay_sync": [_vp],
     "oz_selfplay_stagger": [_vp, C.c_int], "oz_selfplay_profile": [_vp, C.c_int], "oz_selfplay_set_batch_cap": [_vp, C.c_int], "oz_selfplay_set_dedup": [_vp, C.c_int],

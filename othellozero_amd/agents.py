@@ -39,13 +39,13 @@ class NeuralNetworkOthelloAgent(OthelloAgent):
     the first valid action with the largest policy entry."""
 
     def __init__(self, game, neural_network, num_simulations, degree_exploration, temperature=0,
-                 q_mode=_lib.QMODE_F64):
+                 q_mode=_lib.QMODE_F64, leaves_per_step=1):
         super().__init__(game)
         self.neural_network, self.num_simulations, self.temperature = neural_network, num_simulations, 0
         side = game.board_size
         # an agent searches on its own turns only: about half the plies
         self.mcts = OthelloMCTS(side, neural_network, degree_exploration, q_mode=q_mode,
-                                node_cap=num_simulations * (side * side // 2) + 64)
+                                node_cap=num_simulations * (side * side // 2) + 64, leaves_per_step=leaves_per_step)
 
     def play(self):
         game = self.game
@@ -74,14 +74,18 @@ def duel_between_agents(game, agent_1, agent_2):
 
 
 def arena_batch(net_a, net_b, board_size=8, num_games=512, num_simulations=800, degree_exploration=1.0, seed=0,
-                first_game_id=0, q_mode=_lib.QMODE_F64, node_cap=0, max_rounds=0, dedup=True, profile=False, eval_cache=False):
+                first_game_id=0, q_mode=_lib.QMODE_F64, node_cap=0, max_rounds=0, dedup=True, profile=False, eval_cache=False,
+                leaves_per_step=1):
     """num_games games of net_a (BLACK) vs net_b (WHITE), temperature 0, max-visit ties broken by the RNG_TIE
     stream keyed (seed, game id, ply).  One of the two may be None: RandomOthelloAgent plays that colour.
     max_rounds > 0 stops after that many plies per game (unfinished boards: winner / points then describe the position reached).
     Returns dict(winner (+1 = BLACK's agent), points, n_moves, actions, players, final boards, stats_black / stats_white =
     the two agents' search counters [simulations, node visits, expansions, terminal hits, fallbacks], leaves_evaluated = positions the
     networks evaluated: fewer than the expansions with dedup=True (the default), where a board several games reach in one step is evaluated once;
-    tree_kernels = {slot: (ms, launches)} of both searches' tree kernels with profile=True, else None)."""
+    tree_kernels = {slot: (ms, launches)} of both searches' tree kernels with profile=True, else None).
+    leaves_per_step = k or (k_black, k_white): descents per game and network batch of the two agents' searches under virtual loss
+    (oz_arena_set_leaves_per_step); an agent's network needs max_batch >= num_games * its k."""
+    kb, kw = (leaves_per_step, leaves_per_step) if np.isscalar(leaves_per_step) else leaves_per_step
     lib = _lib.require_gpu()
     h = C.c_void_p()
     _lib.check(lib.oz_arena_create(C.byref(h), board_size, num_games, num_simulations, float(degree_exploration), q_mode,
@@ -92,6 +96,8 @@ def arena_batch(net_a, net_b, board_size=8, num_games=512, num_simulations=800, 
             _lib.check(lib.oz_arena_set_dedup(h, 0))
         if eval_cache:                                       # leaves looked up in / inserted into the two networks' evaluation caches (net.set_eval_cache first)
             _lib.check(lib.oz_arena_set_eval_cache(h, 1))
+        if not (np.isscalar(leaves_per_step) and leaves_per_step == 1):
+            _lib.check(lib.oz_arena_set_leaves_per_step(h, int(kb), int(kw)))
         if profile:                                          # HIP events around the tree kernels of both searches (bench.py's config5 kernels[])
             _lib.check(lib.oz_arena_profile(h, 1))
         _lib.check(lib.oz_arena_run_rounds(h, int(max_rounds)))

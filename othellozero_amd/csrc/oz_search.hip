@@ -14,7 +14,8 @@
 //   * lock step: every active game advances exactly one simulation per step (simulations of one
 //     game are sequential in the reference; no virtual loss), leaves that need the network are
 //     compacted by ballot + prefix sum into one dense batch (deterministic slot order), evaluated
-//     by one NN launch sequence, then expanded / backed up;
+//     by one NN launch sequence, then expanded / backed up; opt-in (oz_mcts_set_leaves_per_step): K descents per game and step under a
+//     virtual loss, the k_wide_* kernels below -- the default and every golden fixture stay on one descent per step;
 //   * float semantics that decide discrete outcomes are restated exactly (SURVEY.md R-FP):
 //     U in float64 evaluated left to right with no FMA contraction, P normalised with NumPy's
 //     pairwise order, Q accumulated in the dynamic type NumPy would use (q_mode).
@@ -542,6 +543,336 @@ __global__ __launch_bounds__(64) void k_backup_select(MctsDev t) {
     select_body(t, L, blockIdx.x, threadIdx.x);
 }
 
+
+// ---------------------------------------------------------------- leaf-parallel search: K leaves per game and step under virtual loss
+// (opt-in: oz_mcts_set_leaves_per_step; the kernels above stay the default and are what K = 1 runs.)  For ONE game and ONE step, with
+// `left` = simulations of the current simulate call still to run:
+//   1. for j = 0 .. min(K, left) - 1, one after the other, the game's wave descends from the root exactly as select_body does, except that
+//      at a node s at depth d the statistics are seen through the descents of this step already in flight: k(s, a) = the number of them
+//      whose level d is (s, a), k(s) = the number whose level d is at s (a state sits at one depth only, so level d is all there is to
+//      compare: <= K - 1 compares per level).  k(s, a) == 0: N' = N, Q' = Q, the stored bits.  Otherwise N' = N + k and
+//      Q' = ((double)N * Q - (double)k) / (double)(N + k) in float64 (every in-flight descent counts as one visit that returned -1 to the
+//      chooser; a view, nothing is stored and the Q type tag is not touched).  U = Q' + (c * P) * (sqrt((double)(Ns + k(s))) / (double)(1 + N')).
+//   2. a descent that ends on a finished board joins the in-flight set with its integer value; one that ends on a state not in the table
+//      joins it as a leaf -- unless an earlier leaf of this step is the same board (its child edge is still -1, the table does not know it:
+//      the boards are compared), then it is DISCARDED (no simulation, counted in the collision counter only) and the step closes for the game.
+//   3. all leaves of all games form one batch in (game, j) order (k_wide_compact); EVERY leaf is evaluated: no cross-game de-duplication
+//      and no evaluation cache here (results would be identical), so leaves_evaluated == expansions for K > 1.
+//   4. per game, j ascending: expand leaf j (the table is probed again for the free slot: two pending leaves of one step may have been
+//      shown the same one), back its value up along path j with q_update; a terminal descent in its place in that order.
+//   5. left -= the descents of the step.  A simulate call runs steps until every game has done exactly nsims simulations.
+// At K = 1 this is the search above (oz_mcts_use_wide_kernels runs it through these kernels: the reference's traces hold them bit for bit in
+// both Q regimes).  At K > 1 the float64 regime is held against a restatement (tests/wide_search_ref.py); OZ_QMODE_NEP50 has no replay of its
+// own at K > 1: the view above is float64 in both regimes and everything stored goes through the one q_update, so it holds by construction.
+struct WideDev {
+    int K;                                       // descents per game and step
+    int *status, *depth, *term_value, *slot;     // [G][OZ_MCTS_MAX_LEAVES_PER_STEP]
+    uint64_t *own, *opp, *legal;                 // [G][OZ_MCTS_MAX_LEAVES_PER_STEP]
+    int2* path;                                  // [G][OZ_MCTS_MAX_LEAVES_PER_STEP][OZ_MAX_DEPTH]
+    int* count;                                  // [G] descents in flight (between a wide descent and its expand + backup)
+    int* left;                                   // [G] simulations of the current simulate call still to run
+    int* max_left;                               // [1] the largest `left` (k_wide_left)
+    unsigned long long* stat;                    // [G][3] steps, descents discarded on a collision, leaves handed to the network
+};
+#define OZ_WK OZ_MCTS_MAX_LEAVES_PER_STEP
+struct WideLds {
+    TreeLds t;
+    int2 path[OZ_WK][OZ_MAX_DEPTH];              // the frontiers of the step's descents
+    uint64_t own[OZ_WK], opp[OZ_WK];             // where they ended
+    int depth[OZ_WK], status[OZ_WK];
+};
+
+// the expand + backup of ONE descent of a step, on the per-(game, j) arrays.  A restatement of backup_body / expand_backup_body above (kept as they
+// are, so that the K = 1 kernels compile to the code they always were); the arithmetic is the same line for line.
+__device__ __forceinline__ void wide_backup_one(const MctsDev& t, int g, int lane, int depth, const int2* __restrict__ path, double value, int vt) {
+    if (lane < depth) {
+        const int2 pe = path[lane];
+        const double val = ((depth - 1 - lane) & 1) ? -value : value;
+        if ((unsigned)pe.x < (unsigned)t.node_cap && (unsigned)pe.y < (unsigned)t.row_cap) {
+            q_update(t, rec_edge(t, g, pe.x, pe.y), val, vt);
+            *rec_Ns(t, g, pe.x) += 1;
+        } else atomicOr(t.error_flag, EF_CORRUPT);
+    }
+    if (lane == 0) {
+        t.last_value[g] = (depth & 1) ? -value : value;
+        t.last_vtype[g] = vt;
+    }
+}
+// one descent's end as the wide expand + backup sees it
+struct LeafRef {
+    int status;
+    uint64_t own, opp, legal;
+    int slot;                  // row of pi / v
+    int fs;                    // free table slot for the new node
+    int depth, tval;
+    const int2* path;          // [depth]
+};
+__device__ __forceinline__ void wide_expand_backup_one(const MctsDev& t, TreeLds& L, int g, int lane, const LeafRef& lf) {
+    const int status = lf.status;
+    if (status == OZ_LEAF_IDLE || status == OZ_LEAF_WAIT) return;           // (WAIT: the leaf was not in the batch, nothing to expand yet)
+    double value;
+    int vt;
+    if (status == OZ_LEAF_EVAL) {
+        // first visit (MCTS/__init__.py:44-57): P = pi * mask, normalised; uniform over legal if the sum is 0
+        const uint64_t own = lf.own, opp = lf.opp, legal = lf.legal;
+        const int slot = lf.slot;
+        const int r = lane >> 3, c = lane & 7, n = t.n;
+        const bool inb = r < n && c < n, is_legal = (legal >> lane) & 1;
+        const int a = r * n + c;
+        double p = is_legal ? (double)t.pi[(size_t)slot * t.n2 + a] : 0.0;     // float32 * float64 mask
+        if (inb) L.arr[a] = p;
+        __syncthreads();
+        const double sum = pairwise_sum(L.arr, t.n2);
+        const int cnt = oz_popc(legal);
+        if (sum > 0) p = p / sum;
+        else p = is_legal ? 1.0 / (double)cnt : 0.0;                           // mask / np.sum(mask)
+        const int node = unii(t.node_count[g]), fs = lf.fs, depth = lf.depth;
+        const bool ok = node < t.node_cap && cnt <= t.row_cap && fs >= 0;
+        if (ok) {
+            // build the record in LDS (header + one edge per legal square, N = 0, Q = 0, child unknown), store it with one
+            // wave-wide 16-byte store, link it into the table and into the edge we came through
+            uint64_t* w = reinterpret_cast<uint64_t*>(L.rec);
+            if (lane == 0) { w[0] = own; w[1] = opp; w[2] = (uint64_t)(uint32_t)cnt << 32; w[3] = 0; }
+            if (is_legal) {
+                const int rank = oz_popc(legal & ((1ULL << lane) - 1ULL));
+                w[4 + 3 * rank] = 0xFFFFFFFF00000000ULL;                       // N|tag = 0, child = -1
+                w[5 + 3 * rank] = 0;                                           // Q = 0.0
+                w[6 + 3 * rank] = (uint64_t)__double_as_longlong(p);
+            }
+            if (lane == 63 && (cnt * 3) % 2) w[4 + 3 * cnt] = 0;               // the last 16-byte chunk is half used: no stale bytes
+            __syncthreads();
+            const int chunks = (OZ_REC_HDR + cnt * OZ_EDGE_BYTES + 15) >> 4;
+            if (lane < chunks) reinterpret_cast<uint4*>(rec_ptr(t, g, node))[lane] = L.rec[lane];
+            if (lane == 0) {
+                t.node_count[g] = node + 1;
+                t.ht[(size_t)g * t.ht_cap + fs] = ht_entry(own, opp, node);
+                if (depth > 0) {
+                    const int2 pe = lf.path[depth - 1];
+                    rec_edge(t, g, pe.x, pe.y)->child = node;
+                } else t.root_node[g] = node;
+            }
+        }
+        if (lane == 0) {
+            unsigned long long* st = t.stat + (size_t)g * OZ_NSTAT;
+            st[ST_EXPAND] += 1;
+            if (!(sum > 0)) st[ST_FALLBACK] += 1;
+            if (!ok) atomicOr(t.error_flag, node >= t.node_cap || fs < 0 ? EF_NODES : EF_EDGES);
+        }
+        value = -(double)t.v[slot];                                            // return -v (:57)
+        vt = t.qmode == OZ_QMODE_F64 ? VT_F64 : VT_F32;
+    } else {
+        value = (double)lf.tval;
+        vt = VT_INT;
+    }
+    wide_backup_one(t, g, lane, lf.depth, lf.path, value, vt);
+}
+
+__device__ __forceinline__ void wide_select_body(const MctsDev& t, const WideDev& w, WideLds& L, int g, int lane) {
+    const int left = t.active[g] ? unii(w.left[g]) : 0;
+    const int nd = left < w.K ? left : w.K;
+    if (nd <= 0) {
+        if (lane == 0) w.count[g] = 0;
+        return;
+    }
+    const uint64_t rown = uni64(t.root_own[g]), ropp = uni64(t.root_opp[g]);
+    const uint64_t rlegal = oz_legal(rown, ropp, t.valid);
+    int rootn = unii(t.root_node[g]);
+    int count = 0, coll = 0, leaves = 0, nterm = 0, visits = 0, err = 0;
+    const size_t gb = (size_t)g * OZ_WK;
+    for (int j = 0; j < nd; ++j) {
+        uint64_t own = rown, opp = ropp, legal = rlegal;
+        int depth = 0, status, tval = 0, fs = -1;
+        int node = rootn, pnode = -1, prank = 0;
+        for (;;) {
+            if (legal == 0 && oz_legal(opp, own, t.valid) == 0) {
+                tval = oz_popc(own) >= oz_popc(opp) ? -1 : 1;
+                status = OZ_LEAF_TERMINAL;
+                break;
+            }
+            if (node < 0) {
+                node = ht_find(t, g, own, opp, lane, &fs);
+                if (node < 0) { status = OZ_LEAF_EVAL; break; }
+                if (pnode < 0) rootn = node;
+                if (lane == 0) {
+                    if (pnode >= 0) rec_edge(t, g, pnode, prank)->child = node;
+                    else t.root_node[g] = node;
+                }
+            }
+            if (legal == 0) { err = EF_NOMOVE; status = OZ_LEAF_IDLE; break; }
+            if (depth >= OZ_MAX_DEPTH) { err = EF_DEPTH; status = OZ_LEAF_IDLE; break; }
+            if (node >= t.node_cap) { err = EF_CORRUPT; status = OZ_LEAF_IDLE; break; }
+            const int cnt = oz_popc(legal);
+            const int chunks = (OZ_REC_HDR + cnt * OZ_EDGE_BYTES + 15) >> 4;
+            __syncthreads();
+            if (lane < chunks) L.t.rec[lane] = reinterpret_cast<const uint4*>(rec_ptr(t, g, node))[lane];
+            __syncthreads();
+            const uint64_t* rw = reinterpret_cast<const uint64_t*>(L.t.rec);
+            const int Ns = unii((int)(uint32_t)rw[2]);
+            const bool is_legal = (legal >> lane) & 1;
+            const int rank = oz_popc(legal & ((1ULL << lane) - 1ULL));
+            // the in-flight descents of this step that stand on this node at this level, and those that took this lane's edge from it
+            int ks = 0, ke = 0;
+            for (int i = 0; i < j; ++i)
+                if (L.depth[i] > depth) {
+                    const int2 pe = L.path[i][depth];
+                    if (pe.x == node) { ++ks; ke += pe.y == rank ? 1 : 0; }
+                }
+            double U = -INFINITY;
+            int child = -1;
+            if (is_legal) {
+                const uint64_t w0 = rw[4 + 3 * rank];
+                int N = (int)((uint32_t)w0 & ~OZ_TAG_F32);
+                child = (int)(w0 >> 32);
+                double Q = __longlong_as_double((long long)rw[5 + 3 * rank]);
+                const double P = __longlong_as_double((long long)rw[6 + 3 * rank]);
+                if (ke) {                                                       // ke == 0 reads the stored bits: (N * Q) / N is not Q
+                    Q = ((double)N * Q - (double)ke) / (double)(N + ke);
+                    N += ke;
+                }
+                const double bound = sqrt((double)(Ns + ks)) / (double)(1 + N);
+                U = Q + (t.c * P) * bound;
+            }
+            const double m = wave_max_f64(U);
+            const int best = oz_ctz(__ballot(is_legal && U == m));
+            const int brank = oz_popc(legal & ((1ULL << best) - 1ULL));
+            if (lane == 0) L.path[j][depth] = make_int2(node, brank);
+            ++depth;
+            pnode = node; prank = brank;
+            node = lane_get(child, best);
+            oz_apply(own, opp, best);
+            const uint64_t theirs = oz_legal(opp, own, t.valid);
+            if (theirs != 0) { uint64_t sw = own; own = opp; opp = sw; legal = theirs; }
+            else legal = oz_legal(own, opp, t.valid);
+        }
+        if (err) break;
+        if (status == OZ_LEAF_EVAL) {
+            bool same = false;
+            for (int i = 0; i < j; ++i) same = same || (L.status[i] == OZ_LEAF_EVAL && L.own[i] == own && L.opp[i] == opp);
+            if (same) { coll = 1; break; }                                      // discarded: the step's collection closes for this game
+            ++leaves;
+        } else ++nterm;
+        if (lane == 0) {
+            L.own[j] = own; L.opp[j] = opp; L.depth[j] = depth; L.status[j] = status;
+            w.status[gb + j] = status; w.own[gb + j] = own; w.opp[gb + j] = opp; w.legal[gb + j] = legal;
+            w.depth[gb + j] = depth; w.term_value[gb + j] = tval;
+        }
+        ++count;
+        visits += depth + 1;
+        wave_sync();                                                            // lane 0's frontier / child-index stores before the next descent's loads
+    }
+    wave_sync();
+    for (int i = 0; i < count; ++i)
+        if (lane < L.depth[i]) w.path[(gb + i) * OZ_MAX_DEPTH + lane] = L.path[i][lane];
+    if (lane == 0) {
+        w.count[g] = count;
+        unsigned long long* st = t.stat + (size_t)g * OZ_NSTAT;
+        st[ST_SIMS] += (unsigned long long)count; st[ST_VISITS] += (unsigned long long)visits; st[ST_TERMINAL] += (unsigned long long)nterm;
+        unsigned long long* ws = w.stat + (size_t)g * 3;
+        ws[0] += 1; ws[1] += (unsigned long long)coll; ws[2] += (unsigned long long)leaves;
+        if (err) {
+            atomicOr(t.error_flag, err);
+            w.left[g] = count;                                                  // nothing more for this game: the host's loop ends, the caller gets the error
+        }
+    }
+}
+
+// per game, j ascending: expand leaf j / take the terminal value, back it up along path j
+__device__ __forceinline__ void wide_expand_backup_body(const MctsDev& t, const WideDev& w, WideLds& L, int g, int lane) {
+    const int count = unii(w.count[g]);
+    if (count <= 0) return;
+    const size_t gb = (size_t)g * OZ_WK;
+    int depth = 0;
+    for (int j = 0; j < count; ++j) {
+        LeafRef lf;
+        lf.status = unii(w.status[gb + j]);
+        lf.own = uni64(w.own[gb + j]); lf.opp = uni64(w.opp[gb + j]); lf.legal = uni64(w.legal[gb + j]);
+        lf.slot = unii(w.slot[gb + j]);
+        lf.depth = depth = unii(w.depth[gb + j]); lf.tval = unii(w.term_value[gb + j]);
+        lf.path = w.path + (gb + j) * OZ_MAX_DEPTH;
+        lf.fs = -1;
+        if (lf.status == OZ_LEAF_EVAL) {                                        // the free slot NOW: the earlier leaves of the step are in
+            int fs = -1;
+            if (ht_find(t, g, lf.own, lf.opp, lane, &fs) >= 0) fs = -1;          // (cannot be in the table: the step holds a board once)
+            lf.fs = fs;
+        }
+        wide_expand_backup_one(t, L.t, g, lane, lf);
+        wave_sync();                                                            // records, table entry, Q / N of this descent before the next one's loads
+        __syncthreads();
+    }
+    if (lane == 0) {
+        w.left[g] -= count;
+        w.count[g] = 0;
+        t.depth[g] = depth;                                                     // oz_mcts_last_value: of the last simulation backed up
+    }
+}
+__global__ __launch_bounds__(64) void k_wide_select(MctsDev t, WideDev w) {
+    __shared__ WideLds L;
+    wide_select_body(t, w, L, blockIdx.x, threadIdx.x);
+}
+__global__ __launch_bounds__(64) void k_wide_expand_backup(MctsDev t, WideDev w) {
+    __shared__ WideLds L;
+    wide_expand_backup_body(t, w, L, blockIdx.x, threadIdx.x);
+}
+// expand + backup of step s-1 and the descents of step s in ONE launch (the wide counterpart of k_backup_select)
+__global__ __launch_bounds__(64) void k_wide_backup_select(MctsDev t, WideDev w) {
+    __shared__ WideLds L;
+    wide_expand_backup_body(t, w, L, blockIdx.x, threadIdx.x);
+    wave_sync();
+    __syncthreads();
+    wide_select_body(t, w, L, blockIdx.x, threadIdx.x);
+}
+// dense batch in (game, j) order: prefix sum over the per-game leaf counts
+__global__ __launch_bounds__(1024) void k_wide_compact(MctsDev t, WideDev w) {
+    __shared__ int wtot[16];
+    __shared__ int base_s;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    if (tid == 0) base_s = 0;
+    __syncthreads();
+    for (int start = 0; start < t.G; start += 1024) {
+        const int g = start + tid;
+        const size_t gb = (size_t)g * OZ_WK;
+        int cnt = 0, n = 0;
+        if (g < t.G) {
+            cnt = w.count[g];
+            for (int j = 0; j < cnt; ++j) n += w.status[gb + j] == OZ_LEAF_EVAL ? 1 : 0;
+        }
+        int x = n;                                                              // inclusive scan over the wave
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int y = __shfl_up(x, off, 64);
+            if (lane >= off) x += y;
+        }
+        if (lane == 63) wtot[wv] = x;
+        __syncthreads();
+        int woff = 0, total = 0;
+        for (int i = 0; i < 16; ++i) { const int y = wtot[i]; if (i < wv) woff += y; total += y; }
+        int pos = base_s + woff + x - n;
+        for (int j = 0; j < cnt; ++j)
+            if (w.status[gb + j] == OZ_LEAF_EVAL) {
+                w.slot[gb + j] = pos;
+                t.batch_own[pos] = w.own[gb + j];
+                t.batch_opp[pos] = w.opp[gb + j];
+                ++pos;
+            }
+        __syncthreads();
+        if (tid == 0) base_s += total;
+        __syncthreads();
+    }
+    if (tid == 0) { *t.batch_count = base_s; *t.eval_leaves += (unsigned long long)base_s; }
+}
+__global__ void k_wide_begin(MctsDev t, WideDev w, int nsims) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= t.G) return;
+    w.left[g] = t.active[g] ? nsims : 0;
+    w.count[g] = 0;
+}
+__global__ void k_wide_left(MctsDev t, WideDev w) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    const int left = g < t.G ? w.left[g] : 0;
+    const int m = wave_max_i32(left);
+    if ((threadIdx.x & 63) == 0 && m > 0) atomicMax(w.max_left, m);
+}
+
 // ---------------------------------------------------------------- host object
 struct oz_mcts {
     MctsDev d;
@@ -557,6 +888,11 @@ struct oz_mcts {
     unsigned batch_no = 0;           // batches evaluated (stamp of the evaluation-cache inserts)
     // staging of oz_mcts_root_counts (called once per move by the drop-in agents): lives with the object
     int32_t* rc_counts = nullptr; uint64_t* rc_legal = nullptr; int32_t* rc_rc = nullptr;
+    // leaf-parallel search (oz_mcts_set_leaves_per_step): w.status == nullptr until it is asked for
+    WideDev w{};
+    int leaves_per_step = 1;
+    bool use_wide = false;           // oz_mcts_use_wide_kernels: K = 1 through the wide kernels
+    bool wide() const { return leaves_per_step > 1 || use_wide; }
 
     template <typename T> int alloc(T** p, size_t count) {
         OZ_HIP(hipMalloc((void**)p, sizeof(T) * (count ? count : 1)));
@@ -710,6 +1046,92 @@ static int mcts_step_async(oz_mcts* m, oz_net* net, bool time_eval) {
     return OZ_OK;
 }
 
+// ---- leaf-parallel search: host side
+// the per-(game, j) arrays, and batch / (pi, v) arrays for G * OZ_WK leaves in place of the G-leaf ones (which stay allocated until destroy)
+static int wide_alloc(oz_mcts* m) {
+    if (m->w.status) return OZ_OK;
+    MctsDev& d = m->d;
+    WideDev& w = m->w;
+    const size_t GK = (size_t)d.G * OZ_WK;
+    const size_t held = m->allocs.size();
+    int rc = OZ_OK;
+#define A(ptr, cnt) if (!rc) rc = m->alloc(&ptr, cnt)
+    A(w.depth, GK); A(w.term_value, GK); A(w.slot, GK);
+    A(w.own, GK); A(w.opp, GK); A(w.legal, GK); A(w.path, GK * OZ_MAX_DEPTH);
+    A(w.count, d.G); A(w.left, d.G); A(w.max_left, 1); A(w.stat, (size_t)d.G * 3);
+    uint64_t *bo = nullptr, *bp = nullptr; float *pi = nullptr, *v = nullptr;
+    A(bo, GK); A(bp, GK); A(pi, GK * d.n2); A(v, GK);
+    A(w.status, GK);
+#undef A
+    if (rc) {                                                   // all or nothing: give back what this call allocated
+        for (size_t i = held; i < m->allocs.size(); ++i) hipFree(m->allocs[i]);
+        m->allocs.resize(held);
+        w = WideDev{};
+        return rc;
+    }
+    d.batch_own = bo; d.batch_opp = bp; d.pi = pi; d.v = v;
+    OZ_HIP(hipMemsetAsync(w.count, 0, sizeof(int) * d.G, m->stream));
+    OZ_HIP(hipMemsetAsync(w.left, 0, sizeof(int) * d.G, m->stream));
+    OZ_HIP(hipMemsetAsync(w.stat, 0, sizeof(unsigned long long) * 3 * d.G, m->stream));
+    OZ_HIP(hipStreamSynchronize(m->stream));
+    return OZ_OK;
+}
+static int wide_check_k(int k) {
+    OZ_REQUIRE(k >= 1 && k <= OZ_MCTS_MAX_LEAVES_PER_STEP, "leaves_per_step %d outside 1 .. %d", k, OZ_MCTS_MAX_LEAVES_PER_STEP);
+    return OZ_OK;
+}
+static int wide_set_k(oz_mcts* m, int k) {
+    if (k > 1) if (int rc = wide_alloc(m)) return rc;
+    m->leaves_per_step = k;
+    return OZ_OK;
+}
+
+// `nsims` simulations for every active game, K = leaves_per_step descents per game and step: ceil(nsims / K) steps are enqueued without a
+// host round trip (descents | compaction | evaluator, the previous step's expand + backup fused with the next step's descents, one closing
+// expand + backup), then the largest remaining budget is read back (4 bytes) and further steps follow until it is zero (steps cut short by
+// a collision leave a remainder).  max_games = an upper bound of the active games: the evaluator is launched for max_games * K leaves.
+static int mcts_wide_steps(oz_mcts* m, oz_net* net, int nsims, int max_games, bool time_eval) {
+    MctsDev& d = m->d;
+    if (int rc = wide_alloc(m)) return rc;
+    WideDev w = m->w;
+    w.K = m->leaves_per_step;
+    hipStream_t s = m->stream;
+    const bool all = m->profile;
+    const int cap = max_games * w.K;
+    const dim3 gg((unsigned)((d.G + 255) / 256));
+    hipLaunchKernelGGL(k_wide_begin, gg, dim3(256), 0, s, d, w, nsims);
+    int steps = (nsims + w.K - 1) / w.K;
+    long long enqueued = 0;                                     // every step runs >= 1 simulation of every game with budget left: <= nsims steps in all
+    while (steps > 0) {
+        enqueued += steps;
+        if (enqueued > (long long)nsims) { oz_set_error("leaf-parallel search: the simulation budget did not run out after %d steps (internal error)", nsims); return OZ_ERR_STATE; }
+        for (int k = 0; k < steps; ++k) {
+            long long i = all ? m->timer.begin(TS_SELECT, s) : -1;
+            if (k == 0) hipLaunchKernelGGL(k_wide_select, dim3(d.G), dim3(64), 0, s, d, w);
+            else hipLaunchKernelGGL(k_wide_backup_select, dim3(d.G), dim3(64), 0, s, d, w);
+            m->timer.end(i, s);
+            i = all ? m->timer.begin(TS_COMPACT, s) : -1;
+            hipLaunchKernelGGL(k_wide_compact, dim3(1), dim3(1024), 0, s, d, w);
+            m->timer.end(i, s);
+            i = (time_eval || all) ? m->timer.begin(TS_NN, s) : -1;
+            if (int rc = oz_net_forward_device(net, d.batch_own, d.batch_opp, d.batch_count, cap, d.pi, d.v, s)) { m->timer.cancel(i); return rc; }
+            m->timer.end(i, s);
+        }
+        const long long i = all ? m->timer.begin(TS_BACKUP, s) : -1;
+        hipLaunchKernelGGL(k_wide_expand_backup, dim3(d.G), dim3(64), 0, s, d, w);
+        m->timer.end(i, s);
+        OZ_HIP(hipGetLastError());
+        int max_left = 0;
+        OZ_HIP(hipMemsetAsync(w.max_left, 0, sizeof(int), s));
+        hipLaunchKernelGGL(k_wide_left, gg, dim3(256), 0, s, d, w);
+        OZ_HIP(hipMemcpyAsync(&max_left, w.max_left, sizeof(int), hipMemcpyDeviceToHost, s));
+        OZ_HIP(hipStreamSynchronize(s));
+        steps = (max_left + w.K - 1) / w.K;
+        if (m->timer.backlog() > 4096) m->timer.drain();
+    }
+    return OZ_OK;
+}
+
 static int mcts_collect_eval_time(oz_mcts* m) {
     if (m->timer.collect() != OZ_OK) { oz_set_error("HIP event timing failed"); return OZ_ERR_HIP; }
     return OZ_OK;
@@ -743,6 +1165,7 @@ static int mcts_steps_close(oz_mcts* m) {
     return OZ_OK;
 }
 static int mcts_steps_async(oz_mcts* m, oz_net* net, int nsims, bool time_eval) {
+    if (m->wide()) return mcts_wide_steps(m, net, nsims, m->d.G, time_eval);
     if (nsims < 2) {
         for (int i = 0; i < nsims; ++i)
             if (int rc = mcts_step_async(m, net, time_eval)) return rc;
@@ -796,8 +1219,10 @@ OZ_API int oz_mcts_set_roots(oz_mcts* m, const uint64_t* own, const uint64_t* op
 OZ_API int oz_mcts_simulate(oz_mcts* m, oz_net* net, int nsims) {
     OZ_REQUIRE(m && net, "null argument");
     OZ_REQUIRE(net->n == m->d.n, "network board size %d != search board size %d", net->n, m->d.n);
-    OZ_REQUIRE(net->max_batch >= m->d.G, "network max_batch %d < num_games %d", net->max_batch, m->d.G);
     std::lock_guard<std::mutex> lk(m->mu);
+    OZ_REQUIRE(net->max_batch >= m->d.G * m->leaves_per_step, "network max_batch %d < num_games %d x leaves_per_step %d", net->max_batch, m->d.G,
+               m->leaves_per_step);
+    if (m->wide() && m->selected) { oz_set_error("oz_mcts_simulate: a host-evaluated step is pending (oz_mcts_select without oz_mcts_backup)"); return OZ_ERR_STATE; }
     std::lock_guard<std::mutex> lkn(net->mu);
     hipSetDevice(m->device);
     if (int rc = mcts_steps_async(m, net, nsims, false)) return rc;
@@ -805,9 +1230,54 @@ OZ_API int oz_mcts_simulate(oz_mcts* m, oz_net* net, int nsims) {
     return check_error_flag(m);
 }
 
+#define OZ_REFUSE_WIDE(m, fn) \
+    do { if ((m)->leaves_per_step > 1) { oz_set_error(fn ": the host-evaluator split runs one leaf per game and step (leaves_per_step is %d: set it to 1)", (m)->leaves_per_step); return OZ_ERR_STATE; } } while (0)
+
+OZ_API int oz_mcts_set_leaves_per_step(oz_mcts* m, int k) {
+    OZ_REQUIRE(m, "null mcts");
+    if (int rc = wide_check_k(k)) return rc;
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (m->selected) { oz_set_error("oz_mcts_set_leaves_per_step: a step is pending (oz_mcts_select without oz_mcts_backup)"); return OZ_ERR_STATE; }
+    hipSetDevice(m->device);
+    return wide_set_k(m, k);
+}
+OZ_API int oz_mcts_get_leaves_per_step(oz_mcts* m, int* k) {
+    OZ_REQUIRE(m && k, "null argument");
+    std::lock_guard<std::mutex> lk(m->mu);
+    *k = m->leaves_per_step;
+    return OZ_OK;
+}
+// diagnostic: leaves_per_step = 1 through the wide kernels (the reference's fixtures then hold the wide kernels)
+OZ_API int oz_mcts_use_wide_kernels(oz_mcts* m, int enable) {
+    OZ_REQUIRE(m, "null mcts");
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (m->selected) { oz_set_error("oz_mcts_use_wide_kernels: a step is pending (oz_mcts_select without oz_mcts_backup)"); return OZ_ERR_STATE; }
+    hipSetDevice(m->device);
+    if (enable) if (int rc = wide_alloc(m)) return rc;
+    m->use_wide = enable != 0;
+    return OZ_OK;
+}
+static int wide_stats_locked(oz_mcts* m, int64_t* out3) {
+    out3[0] = out3[1] = out3[2] = 0;
+    if (!m->w.status) return OZ_OK;
+    const size_t cnt = (size_t)m->d.G * 3;
+    std::vector<unsigned long long> h(cnt);
+    OZ_HIP(hipMemcpyAsync(h.data(), m->w.stat, 8 * cnt, hipMemcpyDeviceToHost, m->stream));
+    OZ_HIP(hipStreamSynchronize(m->stream));
+    for (size_t i = 0; i < cnt; ++i) out3[i % 3] += (int64_t)h[i];
+    return OZ_OK;
+}
+OZ_API int oz_mcts_wide_stats(oz_mcts* m, int64_t* out3) {
+    OZ_REQUIRE(m && out3, "null argument");
+    std::lock_guard<std::mutex> lk(m->mu);
+    hipSetDevice(m->device);
+    return wide_stats_locked(m, out3);
+}
+
 OZ_API int oz_mcts_select(oz_mcts* m) {
     OZ_REQUIRE(m, "null mcts");
     std::lock_guard<std::mutex> lk(m->mu);
+    OZ_REFUSE_WIDE(m, "oz_mcts_select");
     hipSetDevice(m->device);
     hipLaunchKernelGGL(k_select, dim3(m->d.G), dim3(64), 0, m->stream, m->d);
     OZ_HIP(hipGetLastError());
@@ -818,6 +1288,7 @@ OZ_API int oz_mcts_select(oz_mcts* m) {
 OZ_API int oz_mcts_leaves(oz_mcts* m, int32_t* status, uint64_t* own, uint64_t* opp) {
     OZ_REQUIRE(m && status && own && opp, "null argument");
     std::lock_guard<std::mutex> lk(m->mu);
+    OZ_REFUSE_WIDE(m, "oz_mcts_leaves");
     OZ_REQUIRE(m->selected, "oz_mcts_leaves: call oz_mcts_select first");
     hipSetDevice(m->device);
     const int G = m->d.G;
@@ -831,6 +1302,7 @@ OZ_API int oz_mcts_leaves(oz_mcts* m, int32_t* status, uint64_t* own, uint64_t* 
 OZ_API int oz_mcts_backup(oz_mcts* m, const float* pi, const float* v) {
     OZ_REQUIRE(m && pi && v, "null argument");
     std::lock_guard<std::mutex> lk(m->mu);
+    OZ_REFUSE_WIDE(m, "oz_mcts_backup");
     if (!m->selected) { oz_set_error("oz_mcts_backup: call oz_mcts_select first"); return OZ_ERR_STATE; }
     hipSetDevice(m->device);
     const int G = m->d.G;
@@ -1332,7 +1804,8 @@ static void selfplay_attach_cache(oz_selfplay* sp) {
 }
 
 // one move round on m->stream: roots, `sims` lock-step simulations, move.  stagger_round >= 0: only slots whose start
-// offset (oz_selfplay_stagger) is still ahead of that round take part
+// offset (oz_selfplay_stagger) is still ahead of that round take part.  With leaves_per_step > 1 the round synchronises the stream once (the
+// 4-byte budget read-back of mcts_wide_steps): the lock-step drivers are then no longer asynchronous.
 static int selfplay_round_async(oz_selfplay* sp, int sims, int stagger_round) {
     oz_mcts* m = sp->m;
     const int G = sp->gm.G;
@@ -1368,7 +1841,8 @@ OZ_API int oz_selfplay_run(oz_selfplay* sp, int rounds) {
 // the same move round.  Slot g gets the start offset (g * period) / num_games, period = the longest game (n*n - 4 plies):
 // in round r (r = 0 .. period-2) the slots whose offset is > r play one move with `sims_pre` simulations -- real searched
 // self-play moves by the same kernels and RNG streams, recorded like any other -- the others wait.  Afterwards slot g is
-// offset(g) plies into its first game, and the refills keep the spread.  Asynchronous, like oz_selfplay_run.
+// offset(g) plies into its first game, and the refills keep the spread.  Asynchronous, like oz_selfplay_run (both synchronise
+// once per round when leaves_per_step > 1).
 OZ_API int oz_selfplay_stagger(oz_selfplay* sp, int sims_pre) {
     OZ_REQUIRE(sp, "null selfplay");
     OZ_REQUIRE(sims_pre >= 2, "sims_pre must be >= 2 (the reference raises KeyError with one simulation)");
@@ -1405,9 +1879,24 @@ OZ_API int oz_selfplay_profile_read(oz_selfplay* sp, double* ms_total, int64_t* 
     return OZ_OK;
 }
 
+// leaf-parallel search for the lock-step drivers (oz_selfplay_run, oz_selfplay_stagger); before the first driver call
+OZ_API int oz_selfplay_set_leaves_per_step(oz_selfplay* sp, int k) {
+    OZ_REQUIRE(sp, "null selfplay");
+    if (int rc = wide_check_k(k)) return rc;
+    std::lock_guard<std::mutex> lk(sp->mu);
+    if (sp->mode != 0) { oz_set_error("oz_selfplay_set_leaves_per_step: the engine has been driven already (set it before the first driver call)"); return OZ_ERR_STATE; }
+    OZ_REQUIRE(sp->net->max_batch >= sp->gm.G * k, "network max_batch %d < num_games %d x leaves_per_step %d", sp->net->max_batch, sp->gm.G, k);
+    hipSetDevice(sp->m->device);
+    return wide_set_k(sp->m, k);
+}
+
 OZ_API int oz_selfplay_run_steps(oz_selfplay* sp, int steps) {
     OZ_REQUIRE(sp, "null selfplay");
     std::lock_guard<std::mutex> lk(sp->mu);
+    if (sp->m->leaves_per_step > 1) {
+        oz_set_error("oz_selfplay_run_steps: the free-running driver runs one leaf per game and batch (leaves_per_step is %d); use oz_selfplay_run", sp->m->leaves_per_step);
+        return OZ_ERR_STATE;
+    }
     std::lock_guard<std::mutex> lkn(sp->net->mu);
     oz_mcts* m = sp->m;
     hipSetDevice(m->device);
@@ -1588,6 +2077,7 @@ struct oz_arena {
     uint8_t* d_actions = nullptr; int8_t* d_players = nullptr;
     int* d_nmoves = nullptr;
     int* d_movers = nullptr;     // [2] live games with BLACK / WHITE to move (k_arena_movers)
+    bool started = false;        // oz_arena_run / oz_arena_run_rounds has been called
     int eval_cache = 0;          // oz_arena_set_eval_cache: the two searches look their leaves up in (and insert them into) their networks' evaluation caches
 };
 
@@ -1731,10 +2221,26 @@ OZ_API int oz_arena_set_eval_cache(oz_arena* a, int enable) {
     return OZ_OK;
 }
 
+// leaf-parallel search per agent (k_black for net_a's search, k_white for net_b's); before the first run
+OZ_API int oz_arena_set_leaves_per_step(oz_arena* a, int k_black, int k_white) {
+    OZ_REQUIRE(a, "null arena");
+    if (int rc = wide_check_k(k_black)) return rc;
+    if (int rc = wide_check_k(k_white)) return rc;
+    std::lock_guard<std::mutex> lk(a->mu);
+    if (a->started) { oz_set_error("oz_arena_set_leaves_per_step: the arena has run already (set it before the first run)"); return OZ_ERR_STATE; }
+    const int G = a->games.gm.G;
+    OZ_REQUIRE(!a->na || a->na->max_batch >= G * k_black, "BLACK network max_batch %d < num_games %d x leaves_per_step %d", a->na->max_batch, G, k_black);
+    OZ_REQUIRE(!a->nb || a->nb->max_batch >= G * k_white, "WHITE network max_batch %d < num_games %d x leaves_per_step %d", a->nb->max_batch, G, k_white);
+    hipSetDevice(a->games.m->device);
+    if (int rc = wide_set_k(a->games.m, k_black)) return rc;
+    return wide_set_k(a->mb, k_white);
+}
+
 OZ_API int oz_arena_run_rounds(oz_arena* a, int max_rounds_arg) {
     OZ_REQUIRE(a, "null arena");
     OZ_REQUIRE(max_rounds_arg >= 0, "oz_arena_run_rounds: max_rounds %d", max_rounds_arg);
     std::lock_guard<std::mutex> lk(a->mu);
+    a->started = true;
     oz_selfplay* sp = &a->games;
     oz_mcts *ma = sp->m, *mb = a->mb;
     hipSetDevice(ma->device);
@@ -1773,13 +2279,19 @@ OZ_API int oz_arena_run_rounds(oz_arena* a, int max_rounds_arg) {
         // the evaluator's launches are made for the movers of the round (an upper bound of the leaves a batch can hold), not for all G slots
         if (run_a) {
             std::lock_guard<std::mutex> la(a->na->mu);
-            for (int k = 0; k < a->sims && !rc; ++k) rc = mcts_step_k(ma, a->na, k, movers[0], false);
-            if (!rc) rc = mcts_steps_close(ma);
+            if (ma->wide()) rc = mcts_wide_steps(ma, a->na, a->sims, movers[0], false);
+            else {
+                for (int k = 0; k < a->sims && !rc; ++k) rc = mcts_step_k(ma, a->na, k, movers[0], false);
+                if (!rc) rc = mcts_steps_close(ma);
+            }
         }
         if (!rc && run_b) {
             std::lock_guard<std::mutex> lb(a->nb->mu);
-            for (int k = 0; k < a->sims && !rc; ++k) rc = mcts_step_k(mb, a->nb, k, movers[1], false);
-            if (!rc) rc = mcts_steps_close(mb);
+            if (mb->wide()) rc = mcts_wide_steps(mb, a->nb, a->sims, movers[1], false);
+            else {
+                for (int k = 0; k < a->sims && !rc; ++k) rc = mcts_step_k(mb, a->nb, k, movers[1], false);
+                if (!rc) rc = mcts_steps_close(mb);
+            }
         }
         if (rc) break;
         {

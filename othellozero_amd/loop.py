@@ -131,17 +131,19 @@ def evaluate_against_random(board_size, neural_network, games, num_simulations, 
     return r
 
 
-def evaluate_against_random_batch(board_size, neural_network, games, num_simulations, degree_exploration, seed=0):
+def evaluate_against_random_batch(board_size, neural_network, games, num_simulations, degree_exploration, seed=0, leaves_per_step=1):
     """The same evaluation as `evaluate_against_random` played in lock step on the GPU (agents.arena_batch with a random
     mover): the network takes BLACK in the first games // 2 + games % 2 games and WHITE in the rest (the reference draws the
     colours with random.shuffle; the split here is fixed).  -> dict(wins, black_wins, black_games, white_wins, white_games)"""
     as_black, as_white = games // 2 + games % 2, games // 2
     r = dict(wins=0, black_wins=0, black_games=0, white_wins=0, white_games=0)
     if as_black:
-        res = arena_batch(neural_network, None, board_size, as_black, num_simulations, degree_exploration, seed=seed)
+        res = arena_batch(neural_network, None, board_size, as_black, num_simulations, degree_exploration, seed=seed,
+                          leaves_per_step=leaves_per_step)
         r["black_wins"] = int((res["winner"] == 1).sum())
     if as_white:
-        res = arena_batch(None, neural_network, board_size, as_white, num_simulations, degree_exploration, seed=seed, first_game_id=as_black)
+        res = arena_batch(None, neural_network, board_size, as_white, num_simulations, degree_exploration, seed=seed, first_game_id=as_black,
+                          leaves_per_step=leaves_per_step)
         r["white_wins"] = int((res["winner"] == -1).sum())
         r["black_games"] = as_white - r["white_wins"]              # games BLACK (the random agent) won
     r["white_games"] = r["white_wins"] + (as_black - r["black_wins"])
@@ -150,17 +152,19 @@ def evaluate_against_random_batch(board_size, neural_network, games, num_simulat
     return r
 
 
-def self_play_match(board_size, neural_network, old_neural_network, total_games, num_simulations, degree_exploration, seed=0):
+def self_play_match(board_size, neural_network, old_neural_network, total_games, num_simulations, degree_exploration, seed=0,
+                    leaves_per_step=1):
     """main.py:110-134: total_games // 2 games with the new network as BLACK, the rest with it as WHITE.
     -> number of games the new network won (a drawn game goes to BLACK, like get_winning_player)."""
     as_black, as_white = total_games // 2, total_games // 2 + total_games % 2
     wins = 0
     if as_black:
-        res = arena_batch(neural_network, old_neural_network, board_size, as_black, num_simulations, degree_exploration, seed=seed)
+        res = arena_batch(neural_network, old_neural_network, board_size, as_black, num_simulations, degree_exploration, seed=seed,
+                          leaves_per_step=leaves_per_step)
         wins += int((res["winner"] == 1).sum())
     if as_white:
         res = arena_batch(old_neural_network, neural_network, board_size, as_white, num_simulations, degree_exploration,
-                          seed=seed, first_game_id=as_black)
+                          seed=seed, first_game_id=as_black, leaves_per_step=leaves_per_step)
         wins += int((res["winner"] == -1).sum())
     return wins
 
@@ -169,7 +173,7 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
              e_greedy, evaluation_interval, evaluation_iterations, temperature_threshold, self_play_training,
              self_play_interval, self_play_total_games, self_play_threshold, checkpoint_filepath, training_buffer_size,
              seed=1234, reference_aliasing=True, alias_final_boards=True, dump_examples=False, q_mode=_lib.QMODE_F64,
-             distributed=False, batched_evaluation=False, policy_target="onehot", target_temperature=1.0):
+             distributed=False, batched_evaluation=False, policy_target="onehot", target_temperature=1.0, leaves_per_step=1):
     """main.py:56-259 on the GPU engines; returns `historic` = [(episodes done, win rate vs random), ...]
 
     batched_evaluation=True plays the evaluation games against RandomOthelloAgent in lock step on the GPU
@@ -184,7 +188,10 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
     policy_target="visits" trains the policy on the search's visit distribution (the AlphaZero pi, from the root visit counts the
     engines record, at target_temperature) instead of the one-hot of the move played.  It needs alias_final_boards=False (pi belongs
     to the position of the move, not the game's final one) and a network whose policy_loss is "flat" (the reference's row-wise loss
-    cannot learn how pi's mass splits between board rows)."""
+    cannot learn how pi's mass splits between board rows).
+
+    leaves_per_step > 1: the batched engines (self-play, matches, batched evaluation) run that many descents per game and network
+    batch under virtual loss; the networks need max_batch >= games * leaves_per_step.  The drop-in evaluation agents keep 1."""
     if policy_target not in ("onehot", "visits"):
         raise ValueError(f"policy_target must be 'onehot' or 'visits' (got {policy_target!r})")
     visits = policy_target == "visits"
@@ -231,14 +238,16 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
         if distributed:
             first, count = shard_games(num_episodes, rank, world)
             eng = SelfPlayEngine(neural_network, board_size, count, num_simulations, degree_exploration, temperature, e_greedy,
-                                 seed=seed, first_game_id=total_episodes_done + first, q_mode=q_mode, record_visits=visits)
+                                 seed=seed, first_game_id=total_episodes_done + first, q_mode=q_mode, record_visits=visits,
+                                 leaves_per_step=leaves_per_step)
             eng.play_to_end()
             records = pooled_selfplay_records(eng, device, with_visits=visits)      # the only exchange of the self-play phase
             del eng
         else:
             records = selfplay_batch(neural_network, board_size, num_games=num_episodes, num_simulations=num_simulations,
                                      degree_exploration=degree_exploration, policy_temperature=temperature, e_greedy=e_greedy,
-                                     seed=seed, first_game_id=total_episodes_done, q_mode=q_mode, record_visits=visits)
+                                     seed=seed, first_game_id=total_episodes_done, q_mode=q_mode, record_visits=visits,
+                                     leaves_per_step=leaves_per_step)
         counts = None
         if visits:
             records, counts = records
@@ -260,7 +269,7 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
         if self_play_training and i % self_play_interval == 0:
             logging.info('[%d/%d] arena: trained network against the previous one', i, num_iterations)
             new_net_victories = self_play_match(board_size, neural_network, old_neural_network, self_play_total_games,
-                                                num_simulations, degree_exploration, seed=seed + i)
+                                                num_simulations, degree_exploration, seed=seed + i, leaves_per_step=leaves_per_step)
             logging.info('[%d/%d] arena: %d of %d games to the trained network', i, num_iterations, new_net_victories, self_play_total_games)
             if new_net_victories >= self_play_threshold:
                 logging.info('[%d/%d] trained network promoted', i, num_iterations)
@@ -277,9 +286,9 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
             logging.info('[%d/%d] evaluation against the random agent: current network', i, num_iterations)
             if batched_evaluation:
                 new = evaluate_against_random_batch(board_size, neural_network, evaluation_iterations, num_simulations,
-                                                    degree_exploration, seed=seed + 7919 * i)
+                                                    degree_exploration, seed=seed + 7919 * i, leaves_per_step=leaves_per_step)
                 old = evaluate_against_random_batch(board_size, old_neural_network, evaluation_iterations, num_simulations,
-                                                    degree_exploration, seed=seed + 7919 * i + 1)
+                                                    degree_exploration, seed=seed + 7919 * i + 1, leaves_per_step=leaves_per_step)
             else:
                 new = evaluate_against_random(board_size, neural_network, evaluation_iterations, num_simulations, degree_exploration,
                                               label=f'after {total_episodes_done} episodes, current network')

@@ -18,9 +18,11 @@ from .Othello import OthelloGame, OthelloPlayer
 
 class OthelloMCTS:
     def __init__(self, board_size, neural_network, degree_exploration, q_mode=_lib.QMODE_F64,
-                 node_cap=8192):
+                 node_cap=8192, leaves_per_step=1):
         """q_mode: OZ_QMODE_F64 = the NumPy 1.18.5 promotion the reference pins (requirements.txt:19),
-        OZ_QMODE_NEP50 = what NumPy >= 2 computes (SURVEY.md R-FP)."""
+        OZ_QMODE_NEP50 = what NumPy >= 2 computes (SURVEY.md R-FP).
+        leaves_per_step > 1 (native networks only, created with max_batch >= leaves_per_step): that many descents of the tree per
+        network batch, kept apart by a virtual loss (oz_mcts_set_leaves_per_step); not the reference's search order."""
         self._board_size = board_size
         self._neural_network = neural_network
         # othelo_mcts.py:15-18: ONN nets see the two-channel board, BNN nets the one-channel (+1 / -1) view
@@ -29,10 +31,17 @@ class OthelloMCTS:
         self._q_mode = q_mode
         self._node_cap = node_cap
         self._h = C.c_void_p()
+        self._native = getattr(neural_network, "_h", None) is not None
+        self.leaves_per_step = int(leaves_per_step)
+        if not 1 <= self.leaves_per_step <= _lib.MAX_LEAVES_PER_STEP:
+            raise ValueError(f"leaves_per_step must be 1 .. {_lib.MAX_LEAVES_PER_STEP} (got {leaves_per_step})")
+        if self.leaves_per_step != 1 and not self._native:
+            raise ValueError("leaves_per_step > 1 needs a native NNetWrapper / StubNetWrapper (the leaves are evaluated on the device)")
         lib = _lib.require_gpu()
         _lib.check(lib.oz_mcts_create(C.byref(self._h), board_size, 1, node_cap, float(degree_exploration), q_mode))
-        self._native = getattr(neural_network, "_h", None) is not None
         self._root = None
+        if self.leaves_per_step != 1:
+            _lib.check(lib.oz_mcts_set_leaves_per_step(self._h, self.leaves_per_step))
 
     def __del__(self):
         try:
@@ -209,6 +218,11 @@ class OthelloMCTS:
                                              _lib.p_i32(N), _lib.p_f64(Q), _lib.p_u8(qt), _lib.p_f64(P)))
             out.append(dict(k0=own.value, k1=opp.value, Ns=Ns.value, legal=legal.value, N=N, Q=Q, qtag=qt, P=P))
         return out
+
+    def wide_stats(self):
+        s = np.zeros(3, np.int64)
+        _lib.check(_lib.load().oz_mcts_wide_stats(self._h, _lib.p_i64(s)))
+        return dict(steps=int(s[0]), collisions=int(s[1]), leaves=int(s[2]))
 
     def stats(self):
         s = np.zeros(5, np.int64)

@@ -31,7 +31,8 @@ def training_example_symmetries(board, policy):
 
 
 def execute_episode(board_size, neural_network, degree_exploration, num_simulations, policy_temperature, e_greedy,
-                    q_mode=_lib.QMODE_F64, snapshot_boards=False, policy_target="onehot", target_temperature=1.0):
+                    q_mode=_lib.QMODE_F64, snapshot_boards=False, policy_target="onehot", target_temperature=1.0,
+                    leaves_per_step=1):
     """training.py:26-72.  Returns [(board (n,n,2) bool, one-hot policy (n,n) float64, z int), ...], 8 per move.
 
     snapshot_boards=False reproduces the reference exactly, including its aliasing quirk: the
@@ -40,14 +41,16 @@ def execute_episode(board_size, neural_network, degree_exploration, num_simulati
 
     policy_target="visits" stores the search's visit distribution instead of the one-hot of the move played (the AlphaZero
     pi): mcts.get_policy_action_probabilities(state, target_temperature) at every move.  With target_temperature > 0 that
-    call draws no random number, so moves and random streams are those of the default "onehot"."""
+    call draws no random number, so moves and random streams are those of the default "onehot".
+
+    leaves_per_step > 1: that many descents per network batch under virtual loss (OthelloMCTS); a native network only."""
     assert policy_target in ("onehot", "visits"), policy_target
     if policy_target == "visits" and not target_temperature > 0:
         raise ValueError(f"target_temperature must be > 0 for visit-count targets (got {target_temperature})")
     examples = []
     game = OthelloGame(board_size)
     mcts = OthelloMCTS(board_size, neural_network, degree_exploration, q_mode=q_mode,
-                       node_cap=num_simulations * (board_size * board_size - 3) + 64)
+                       node_cap=num_simulations * (board_size * board_size - 3) + 64, leaves_per_step=leaves_per_step)
     # training.py:34-37 (BNN examples are one-channel boards, a fresh array per round: no aliasing for them)
     board_view_type = BoardView.ONE_CHANNEL if getattr(neural_network.network_type, "name", "") == "BNN" else BoardView.TWO_CHANNELS
 
@@ -124,13 +127,16 @@ class SelfPlayEngine:
     def __init__(self, neural_network, board_size=8, num_games=4096, num_simulations=100, degree_exploration=1.0,
                  policy_temperature=1.0, e_greedy=0.9, seed=1234, first_game_id=0, game_id_stride=0,
                  q_mode=_lib.QMODE_F64, refill=False, node_cap=0, record_cap=0, dedup=True, batch_cap=0, eval_cache=False,
-                 record_visits=False):
+                 record_visits=False, leaves_per_step=1):
         """dedup: cross-game leaf de-duplication (a board several games reach in one batch is evaluated once; no record changes);
         batch_cap: leaves per network batch of the free-running driver (0 = none; see preferred_batch_cap);
         eval_cache: take (pi, v) of boards the network has evaluated before from its persistent cache (NNetWrapper.set_eval_cache) --
         the reference's per-search _predict_cache (othelo_mcts.py:82-88) across batches, games and refilled slots; no record changes;
         record_visits: keep every recorded move's root visit counts (records(with_visits=True)) -- the policy targets of
-        expand_examples(visits=...); 16 KB per slot + 256 B per record of device memory, no record changes"""
+        expand_examples(visits=...); 16 KB per slot + 256 B per record of device memory, no record changes;
+        leaves_per_step > 1: that many descents per game and network batch under virtual loss (oz_mcts_set_leaves_per_step) for run() /
+        stagger(); the network needs max_batch >= num_games * leaves_per_step; run_steps() then raises; dedup and eval_cache then have no
+        effect (every leaf is evaluated) and run(sync=False) still waits once per move round.  Not the reference's search order."""
         lib = _lib.require_gpu()
         assert getattr(neural_network, "_h", None) is not None, "SelfPlayEngine needs a native NNetWrapper / StubNetWrapper"
         self.net = neural_network
@@ -143,6 +149,9 @@ class SelfPlayEngine:
         self._h = C.c_void_p()
         _lib.check(lib.oz_selfplay_create(C.byref(self._h), C.byref(self.cfg), neural_network._h))
         self.n, self.num_games = board_size, num_games
+        self.leaves_per_step = int(leaves_per_step)
+        if self.leaves_per_step != 1:
+            _lib.check(lib.oz_selfplay_set_leaves_per_step(self._h, self.leaves_per_step))
 
     def __del__(self):
         try:
@@ -305,11 +314,11 @@ def expand_examples(records, board_size, alias_final=False, visits=None, target_
 
 def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations=100, degree_exploration=1.0,
                    policy_temperature=1.0, e_greedy=0.9, seed=1234, first_game_id=0, q_mode=_lib.QMODE_F64,
-                   expand=False, alias_final=False, record_visits=False, target_temperature=1.0):
+                   expand=False, alias_final=False, record_visits=False, target_temperature=1.0, leaves_per_step=1):
     """Play num_games complete games; returns the move records (or the expanded examples).
     record_visits=True: (records, visit counts) -- or, with expand, the examples with visit-distribution targets at target_temperature."""
     eng = SelfPlayEngine(neural_network, board_size, num_games, num_simulations, degree_exploration, policy_temperature,
-                         e_greedy, seed, first_game_id, q_mode=q_mode, record_visits=record_visits)
+                         e_greedy, seed, first_game_id, q_mode=q_mode, record_visits=record_visits, leaves_per_step=leaves_per_step)
     if record_visits:
         rec, counts = eng.play_to_end(with_visits=True)
         return expand_examples(rec, board_size, alias_final, visits=counts, target_temperature=target_temperature) if expand else (rec, counts)

@@ -3,7 +3,7 @@
 With the device stub network the leaf evaluation costs nothing, so this times the TREE side alone -- select / compaction /
 expand / backup at 800 simulations per move, two search trees per game (one per agent, agents.py:44-68).
 
-    python tools/arena_bench.py [--games 512] [--sims 800] [--board 8] [--check 2]
+    python tools/arena_bench.py [--games 512] [--sims 800] [--board 8] [--check 2] [--leaves-per-step 1]
 
 Prints one JSON line: simulations/s, games/s, and (--check k) the first k games re-played by the CPU oracle bit for bit."""
 import argparse
@@ -23,6 +23,7 @@ def main():
     ap.add_argument("--board", type=int, default=8)
     ap.add_argument("--check", type=int, default=2)
     ap.add_argument("--reps", type=int, default=2)
+    ap.add_argument("--leaves-per-step", type=int, default=1, help="descents per game and network batch under virtual loss (not the oracle's search order: no --check)")
     args = ap.parse_args()
     import numpy as np
     from othellozero_amd import _lib
@@ -30,11 +31,11 @@ def main():
     from othellozero_amd.agents import arena_batch
     _lib.require_gpu()
     n, G = args.board, args.games
-    a, b = StubNetWrapper((n, n), 301, 0, max_batch=G), StubNetWrapper((n, n), 302, 0, max_batch=G)
+    a, b = StubNetWrapper((n, n), 301, 0, max_batch=G * args.leaves_per_step), StubNetWrapper((n, n), 302, 0, max_batch=G * args.leaves_per_step)
     best, r = None, None
     for rep in range(args.reps):                               # the first repetition also pays allocation / code load
         t0 = time.perf_counter()
-        r = arena_batch(a, b, n, G, args.sims, 1.0, seed=11, first_game_id=0, q_mode=1)
+        r = arena_batch(a, b, n, G, args.sims, 1.0, seed=11, first_game_id=0, q_mode=1, leaves_per_step=args.leaves_per_step)
         dt = time.perf_counter() - t0
         best = dt if best is None else min(best, dt)
     moves = int(r["n_moves"].sum())
@@ -42,7 +43,7 @@ def main():
            "seconds": best, "moves": moves, "simulations": moves * args.sims, "sims_per_s": moves * args.sims / best,
            "games_per_s": G / best, "moves_per_s": moves / best,
            "tree_side_hbm_GBps_at_1300B_per_sim": moves * args.sims * 1300 / best / 1e9}
-    if args.check:
+    if args.check and args.leaves_per_step == 1:
         import oracle
         ok = 0
         for gi in range(args.check):
