@@ -42,7 +42,7 @@ extern "C" {
 #define OZ_LEAF_WAIT 3       /* free-running driver with a batch cap: the leaf is chosen and waits for a slot of a later batch */
 
 const char* oz_last_error(void);
-int oz_version(void);                 /* 210 */
+int oz_version(void);                 /* 220 */
 int oz_device_count(void);
 int oz_set_device(int device);       /* device used by objects created afterwards on this thread */
 
@@ -250,6 +250,37 @@ int oz_mcts_use_wide_kernels(oz_mcts* m, int enable);
 /* out[0] game-steps run by the leaf-parallel kernels, out[1] descents discarded on a collision, out[2] leaves handed to the network */
 int oz_mcts_wide_stats(oz_mcts* m, int64_t* out3);
 
+/* ---- root noise: Dirichlet noise on the root prior, AlphaZero's exploration inside the search (opt-in; off, every result stays bit for bit)
+ * P'(root, a) = (1 - eps) P(root, a) + eps eta_a, eta ~ Dir(alpha) over the root's legal moves, fresh for every searched move.
+ * STORED PRIORS ARE NEVER MODIFIED: the node tables are transposition tables that persist across the moves of a game, so the noise is applied
+ * at selection time only, at depth 0 of a descent, to the root it was drawn for (an Othello position cannot recur below itself, so "depth 0"
+ * and "is the root" coincide).  In float64, no contraction, on an armed root and a legal square sq:
+ *     Pn = (1.0 - eps) * P + eps * eta[sq]          two products, one sum, as written
+ *     U  = Q + (c * Pn) * (sqrt(Ns) / (1 + N))      the shape of the search above; at leaves_per_step > 1 with the virtual-loss view of Ns, N, Q
+ * Deeper levels, unarmed roots and eps == 0 use the stored P; the first maximum still wins ties and the reference's Ns == 0 quirk (all U equal:
+ * the first legal square) is unchanged.  The host-evaluator split (oz_mcts_select / leaves / backup) honours the noise too.
+ * Lifetime: noise belongs to ONE root board of ONE slot.  Giving the slot a different board drops it (oz_mcts_set_roots with another board, the
+ * engines' root kernels, the move of the free-running driver); arming again replaces it.  The arena and the evaluation games never use noise.
+ * The sampler (device side, one lane per square, counter based, no state): with u(sq, i) = the unit draw of the library's stream
+ * (seed, game id, ply, 3 + 256 sq + 65536 i) and w(sq, i) = 1.0 - u(sq, i) in (0, 1], Gamma(alpha) of a legal square is Marsaglia-Tsang with the
+ * alpha < 1 boost, all float64:
+ *     a = alpha < 1 ? alpha + 1 : alpha;  d = a - 1.0/3.0;  cc = 1.0 / sqrt(9.0 * d);  g = d
+ *     for t in 0 .. 15:  x = sqrt(-2.0 * log(w(sq, 3t))) * cos(2.0 * pi * u(sq, 3t + 1));  v = 1.0 + cc * x;  if v <= 0: continue;  v = v * v * v
+ *                        if log(w(sq, 3t + 2)) < 0.5 * x * x + d - d * v + d * log(v): g = d * v; break
+ *     if alpha < 1: g *= pow(w(sq, 48), 1.0 / alpha)
+ * eta[sq] = g / S, S = the sum of g over the (n, n) array in NumPy's pairwise order (zeros off the legal set); S == 0 or not finite: 1 / count
+ * on the legal squares.  Squares off the legal set are exactly 0; a root with one legal move gets exactly 1.0.
+ * OZ_ERR_ARG: alpha not in [0.01, 100], eps not in [0, 1] (NaN included), an eta outside [0, 1].  OZ_ERR_STATE: a change while a step is pending
+ * (oz_mcts_select without oz_mcts_backup) / after an engine's first driver call.  eps == 0 disarms and allocates nothing; the first arming
+ * allocates 513 B per game (2 MB at 4 096 games) and moves the object's descents to the noise-aware instantiation of the kernels. */
+/* host-supplied noise for a bare search: eta[num_games][64] by square (row*8+col), 0 off the legal set; armed[g] != 0 arms slot g for its
+ * CURRENT root (null: every active slot); eta == NULL or eps == 0 disarms all */
+int oz_mcts_set_root_noise(oz_mcts* m, double eps, const double* eta, const uint8_t* armed);
+/* device-drawn noise for the current roots of the active slots, keyed (seed, game_ids[g], plies[g]) */
+int oz_mcts_sample_root_noise(oz_mcts* m, double alpha, double eps, uint64_t seed, const uint64_t* game_ids, const int32_t* plies);
+/* what is set: eta[num_games][64], armed[num_games], *eps (each may be NULL); an object that never armed noise reads zeros */
+int oz_mcts_get_root_noise(oz_mcts* m, double* eta /* [num_games][64] */, uint8_t* armed /* [num_games] */, double* eps);
+
 /* ------------------------------------------------------------------ self-play
  * execute_episode (training.py:26-72) for num_games concurrent games in lock step. */
 typedef struct oz_selfplay oz_selfplay;
@@ -325,6 +356,12 @@ int oz_selfplay_set_dedup(oz_selfplay* sp, int enable);
  * the stream once per round and are no longer asynchronous; every leaf goes to the network: oz_selfplay_config.dedup and .eval_cache have no
  * effect (records would be identical either way), leaves_evaluated == expansions. */
 int oz_selfplay_set_leaves_per_step(oz_selfplay* sp, int k);
+/* self-play with root noise: every searched move of every game (oz_selfplay_stagger's included) draws Dir(alpha) at its root, keyed
+ * (cfg.seed, game id, ply) -- in a kernel of its own behind the roots kernel of a lock-step round, inside the advance kernel of the
+ * free-running driver (whose records stay exactly those of oz_selfplay_run).  Before the first driver call. */
+int oz_selfplay_set_root_noise(oz_selfplay* sp, double alpha, double eps);
+/* the noise of the searches of the last move round of oz_selfplay_run (tests; eta[num_games][64], armed[num_games]) */
+int oz_selfplay_root_noise(oz_selfplay* sp, double* eta, uint8_t* armed);
 int oz_selfplay_sync(oz_selfplay* sp);
 /* continuous self-play (cfg.refill): bring a fresh engine to the steady state of a long-running one before measuring it --
  * slot g is advanced (g * P) / num_games plies into its first game, P = n*n - 4, by searched self-play moves at `sims_pre`

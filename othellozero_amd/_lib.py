@@ -110,6 +110,10 @@ SIGNATURES = {
     "oz_mcts_set_leaves_per_step": [_vp, C.c_int], "oz_mcts_get_leaves_per_step": [_vp, C.POINTER(C.c_int)],
     "oz_mcts_use_wide_kernels": [_vp, C.c_int], "oz_mcts_wide_stats": [_vp, _i64p],
     "oz_selfplay_set_leaves_per_step": [_vp, C.c_int], "oz_arena_set_leaves_per_step": [_vp, C.c_int, C.c_int],
+    "oz_mcts_set_root_noise": [_vp, C.c_double, _f64p, _u8p],
+    "oz_mcts_sample_root_noise": [_vp, C.c_double, C.c_double, C.c_uint64, _u64p, _i32p],
+    "oz_mcts_get_root_noise": [_vp, _f64p, _u8p, _f64p],
+    "oz_selfplay_set_root_noise": [_vp, C.c_double, C.c_double], "oz_selfplay_root_noise": [_vp, _f64p, _u8p],
     "oz_selfplay_create": [C.POINTER(_vp), C.POINTER(SelfplayConfig), _vp],
     "oz_selfplay_destroy": [_vp], "oz_selfplay_run": [_vp, C.c_int], "oz_selfplay_run_steps": [_vp, C.c_int], "oz_selfplay_sync": [_vp],
     "oz_selfplay_stagger": [_vp, C.c_int], "oz_selfplay_profile": [_vp, C.c_int], "oz_selfplay_set_batch_cap": [_vp, C.c_int], "oz_selfplay_set_dedup": [_vp, C.c_int],
@@ -266,6 +270,22 @@ def load(path=None):
     if path is None:
         _LIB = lib
     return lib
+
+
+def check_root_noise(root_noise):
+    """root_noise = None or (alpha, epsilon): Dirichlet noise on the root prior of every searched self-play move.  Returns None or the pair
+    as floats; ValueError for anything the library would refuse (alpha in [0.01, 100], epsilon in [0, 1])."""
+    if root_noise is None:
+        return None
+    try:
+        alpha, eps = (float(x) for x in root_noise)
+    except (TypeError, ValueError):
+        raise ValueError(f"root_noise must be None or (alpha, epsilon), got {root_noise!r}") from None
+    if not 0.01 <= alpha <= 100.0:
+        raise ValueError(f"root_noise: alpha must be in [0.01, 100] (got {alpha})")
+    if not 0.0 <= eps <= 1.0:
+        raise ValueError(f"root_noise: epsilon must be in [0, 1] (got {eps})")
+    return alpha, eps
 
 
 def check(rc):

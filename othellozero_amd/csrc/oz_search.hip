@@ -80,6 +80,10 @@ struct MctsDev {
     int* hit_count;            // leaves of this batch served from the cache: they take the pi / v rows G-1, G-2, ... (never the network's rows 0 ..)
     int* hit_entry;            // [G] cache entry of hit h
     unsigned batch_stamp;      // k_cache_insert: number of this batch (two inserts into one entry within a batch: the first wins)
+    // Dirichlet root noise ("root noise" below): null / 0 until an object arms it for the first time
+    double* noise_eta;         // [G][64] eta by square, 0 off the legal set of the root it was drawn for
+    uint8_t* noise_armed;      // [G] the slot's CURRENT root carries noise
+    double noise_eps;          // the mixing weight (0: off)
 };
 
 __device__ __forceinline__ unsigned char* rec_ptr(const MctsDev& t, int g, int node) {
@@ -174,15 +178,96 @@ __device__ __forceinline__ uint32_t ht_entry(uint64_t own, uint64_t opp, int nod
     return ((uint32_t)(key_hash64(own, opp) >> 52) << OZ_HT_IDX_BITS) | (uint32_t)(node + 1);
 }
 
+// ---------------------------------------------------------------- root noise: Dirichlet noise on the root prior (opt-in, AlphaZero's exploration)
+// (the semantics are stated in include/othellozero_amd.h, "root noise"; the restatement the tests hold this against is tests/root_noise_ref.py.)
+//   * STORED PRIORS ARE NEVER MODIFIED: the node tables are transposition tables that outlive a move, so the noise is a view taken at selection
+//     time, at depth 0 of a descent only, of the root it was drawn for (a position cannot recur below itself: every move adds a disc, so
+//     "depth 0" and "is the root" coincide).  On an armed slot, for a legal square: Pn = (1.0 - eps) * P + eps * eta[sq] in float64, two products
+//     and one sum as written, and U = Q + (c * Pn) * (sqrt(Ns) / (1 + N)) -- under leaf-parallel search with the virtual-loss view of Ns, N, Q.
+//     Deeper levels, unarmed slots and eps == 0 read the stored P.  First-maximum tie break and the Ns == 0 quirk are untouched.
+//   * the noise belongs to ONE root board of ONE slot: noise_armed[g] says that eta[g] is that of the slot's current root; whatever gives a slot
+//     another board clears it (oz_mcts_set_roots, k_sp_roots / k_sp_roots_stagger, the move inside the free-running advance) or draws anew.
+//   * a compile-time variant: the bodies below take template <bool NOISE>; an object that never armed noise launches the NOISE = false kernels,
+//     which are the code they were before this section existed.  The host picks per launch (oz_mcts::noise_ever).
+// The sampler: one lane per square, counter based, no state.  u(sq, i) = oz_rng_unit(oz_rng(seed, game id, ply, OZ_RNG_NOISE + 256 sq + 65536 i)),
+// w = 1 - u in (0, 1].  Gamma(alpha) by Marsaglia-Tsang (with the alpha < 1 boost g *= w^(1 / alpha)), at most 16 attempts of three draws each
+// (draws 3t, 3t + 1, 3t + 2; the boost takes draw 48) -- all float64; eta = g / S, S = NumPy's pairwise sum of g over the (n, n) array with zeros
+// off the legal set; S == 0 or not finite: uniform over the legal squares.  A root with one legal move gets g / g = 1.0 exactly.
+__device__ __forceinline__ double noise_unit(uint64_t seed, uint64_t gid, uint64_t ply, int sq, int i) {
+    return oz_rng_unit(oz_rng(seed, gid, ply, (uint64_t)OZ_RNG_NOISE + 256ull * (uint64_t)sq + 65536ull * (uint64_t)i));
+}
+__device__ __forceinline__ double noise_gamma(double alpha, uint64_t seed, uint64_t gid, uint64_t ply, int sq) {
+    const double a = alpha < 1.0 ? alpha + 1.0 : alpha;
+    const double d = a - 1.0 / 3.0, cc = 1.0 / sqrt(9.0 * d);
+    double g = d;                                                               // (16 rejections in a row: never seen; the mean of the law)
+    for (int t = 0; t < 16; ++t) {
+        const double w0 = 1.0 - noise_unit(seed, gid, ply, sq, 3 * t), u1 = noise_unit(seed, gid, ply, sq, 3 * t + 1);
+        const double x = sqrt(-2.0 * log(w0)) * cos(2.0 * 3.14159265358979323846 * u1);          // Box-Muller
+        double v = 1.0 + cc * x;
+        if (v <= 0.0) continue;
+        v = v * v * v;
+        const double w2 = 1.0 - noise_unit(seed, gid, ply, sq, 3 * t + 2);
+        if (log(w2) < 0.5 * x * x + d - d * v + d * log(v)) { g = d * v; break; }
+    }
+    if (alpha < 1.0) g *= pow(1.0 - noise_unit(seed, gid, ply, sq, 48), 1.0 / alpha);
+    return g;
+}
+// one wave = one game: draws eta for the root (own, opp) of slot g and arms the slot.  arr = 64 doubles of LDS (free on entry, free on return).
+__device__ __forceinline__ void root_noise_body(const MctsDev& t, double* arr, int g, int lane, uint64_t own, uint64_t opp, double alpha,
+                                                uint64_t seed, uint64_t gid, int ply) {
+    const uint64_t legal = oz_legal(own, opp, t.valid);
+    const int r = lane >> 3, c = lane & 7, n = t.n;
+    const bool inb = r < n && c < n, is_legal = (legal >> lane) & 1;
+    const double gm = is_legal ? noise_gamma(alpha, seed, gid, (uint64_t)ply, lane) : 0.0;
+    __syncthreads();
+    if (inb) arr[r * n + c] = gm;
+    __syncthreads();
+    const double S = pairwise_sum(arr, t.n2);
+    double eta = 0.0;
+    if (is_legal) eta = (S > 0.0 && S < INFINITY) ? gm / S : 1.0 / (double)oz_popc(legal);
+    t.noise_eta[(size_t)g * 64 + lane] = eta;
+    if (lane == 0) t.noise_armed[g] = legal != 0 ? 1 : 0;
+    __syncthreads();
+}
+// the noise of the CURRENT roots of the active slots, keyed (seed, game_ids[g], plies[g]); an idle slot is disarmed
+__global__ __launch_bounds__(64) void k_root_noise(MctsDev t, double alpha, uint64_t seed, const uint64_t* __restrict__ game_ids,
+                                                   const int* __restrict__ plies) {
+    __shared__ double arr[64];
+    const int g = blockIdx.x, lane = threadIdx.x;
+    if (!t.active[g]) {
+        if (lane == 0) t.noise_armed[g] = 0;
+        return;
+    }
+    root_noise_body(t, arr, g, lane, uni64(t.root_own[g]), uni64(t.root_opp[g]), alpha, seed, uni64(game_ids[g]), unii(plies[g]));
+}
+// armed = active (oz_mcts_set_root_noise with a null `armed`)
+__global__ void k_noise_arm_active(MctsDev t) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g < t.G) t.noise_armed[g] = t.active[g] ? 1 : 0;
+}
+// what a descent of slot g mixes into its root's priors: true and *eta = this lane's share if the slot is armed
+template <bool NOISE> __device__ __forceinline__ bool noise_of_slot(const MctsDev& t, int g, int lane, double* eta) {
+    if constexpr (NOISE) {
+        if (t.noise_eps > 0.0 && unii((int)t.noise_armed[g]) != 0) {
+            *eta = t.noise_eta[(size_t)g * 64 + lane];                          // one coalesced 512-byte load per descent
+            return true;
+        }
+    }
+    return false;
+}
+
 // ---------------------------------------------------------------- K4: select / descend
 // MCTS.simulate down to the first terminal or unexpanded state (MCTS/__init__.py:39-44,58-67),
 // get_next_state (othelo_mcts.py:43-49).  One wave per game; per level ONE wave-wide load stages the node's record in LDS.
 // (body shared by k_select and the free-running k_advance; returns the status it stored in leaf_status[g])
+template <bool NOISE = false>
 __device__ __forceinline__ int select_body(const MctsDev& t, TreeLds& L, int g, int lane) {
     if (!t.active[g]) {
         if (lane == 0) t.leaf_status[g] = OZ_LEAF_IDLE;
         return OZ_LEAF_IDLE;
     }
+    double eta = 0.0;
+    const bool noisy = noise_of_slot<NOISE>(t, g, lane, &eta);
     uint64_t own = uni64(t.root_own[g]), opp = uni64(t.root_opp[g]);
     int depth = 0, status, tval = 0, err = 0, fs = -1;
     int node = unii(t.root_node[g]);                            // record index of the state we stand on, -1 = unknown
@@ -226,6 +311,9 @@ __device__ __forceinline__ int select_body(const MctsDev& t, TreeLds& L, int g, 
             const double Q = __longlong_as_double((long long)w[5 + 3 * rank]), P = __longlong_as_double((long long)w[6 + 3 * rank]);
             const double bound = sqrt((double)Ns) / (double)(1 + N);       // MCTS/__init__.py:169
             U = Q + (t.c * P) * bound;                                     // :170, left to right
+            if constexpr (NOISE) {
+                if (noisy && depth == 0) U = Q + (t.c * ((1.0 - t.noise_eps) * P + t.noise_eps * eta)) * bound;     // the root's noisy view of P
+            }
         }
         const double m = wave_max_f64(U);
         const int best = oz_ctz(__ballot(is_legal && U == m));             // first maximum
@@ -256,6 +344,11 @@ __device__ __forceinline__ int select_body(const MctsDev& t, TreeLds& L, int g, 
 __global__ __launch_bounds__(64) void k_select(MctsDev t) {
     __shared__ TreeLds L;
     select_body(t, L, blockIdx.x, threadIdx.x);
+}
+// (the *_n kernels: the same kernels over the NOISE = true bodies, launched by objects that have armed root noise)
+__global__ __launch_bounds__(64) void k_select_n(MctsDev t) {
+    __shared__ TreeLds L;
+    select_body<true>(t, L, blockIdx.x, threadIdx.x);
 }
 
 // ---------------------------------------------------------------- K13: leaf compaction
@@ -542,6 +635,13 @@ __global__ __launch_bounds__(64) void k_backup_select(MctsDev t) {
     __syncthreads();
     select_body(t, L, blockIdx.x, threadIdx.x);
 }
+__global__ __launch_bounds__(64) void k_backup_select_n(MctsDev t) {
+    __shared__ TreeLds L;
+    expand_backup_body(t, L, blockIdx.x, threadIdx.x, 0);
+    wave_sync();
+    __syncthreads();
+    select_body<true>(t, L, blockIdx.x, threadIdx.x);
+}
 
 
 // ---------------------------------------------------------------- leaf-parallel search: K leaves per game and step under virtual loss
@@ -667,6 +767,7 @@ __device__ __forceinline__ void wide_expand_backup_one(const MctsDev& t, TreeLds
     wide_backup_one(t, g, lane, lf.depth, lf.path, value, vt);
 }
 
+template <bool NOISE = false>
 __device__ __forceinline__ void wide_select_body(const MctsDev& t, const WideDev& w, WideLds& L, int g, int lane) {
     const int left = t.active[g] ? unii(w.left[g]) : 0;
     const int nd = left < w.K ? left : w.K;
@@ -674,6 +775,8 @@ __device__ __forceinline__ void wide_select_body(const MctsDev& t, const WideDev
         if (lane == 0) w.count[g] = 0;
         return;
     }
+    double eta = 0.0;
+    const bool noisy = noise_of_slot<NOISE>(t, g, lane, &eta);
     const uint64_t rown = uni64(t.root_own[g]), ropp = uni64(t.root_opp[g]);
     const uint64_t rlegal = oz_legal(rown, ropp, t.valid);
     int rootn = unii(t.root_node[g]);
@@ -731,6 +834,9 @@ __device__ __forceinline__ void wide_select_body(const MctsDev& t, const WideDev
                 }
                 const double bound = sqrt((double)(Ns + ks)) / (double)(1 + N);
                 U = Q + (t.c * P) * bound;
+                if constexpr (NOISE) {
+                    if (noisy && depth == 0) U = Q + (t.c * ((1.0 - t.noise_eps) * P + t.noise_eps * eta)) * bound;
+                }
             }
             const double m = wave_max_f64(U);
             const int best = oz_ctz(__ballot(is_legal && U == m));
@@ -809,6 +915,10 @@ __global__ __launch_bounds__(64) void k_wide_select(MctsDev t, WideDev w) {
     __shared__ WideLds L;
     wide_select_body(t, w, L, blockIdx.x, threadIdx.x);
 }
+__global__ __launch_bounds__(64) void k_wide_select_n(MctsDev t, WideDev w) {
+    __shared__ WideLds L;
+    wide_select_body<true>(t, w, L, blockIdx.x, threadIdx.x);
+}
 __global__ __launch_bounds__(64) void k_wide_expand_backup(MctsDev t, WideDev w) {
     __shared__ WideLds L;
     wide_expand_backup_body(t, w, L, blockIdx.x, threadIdx.x);
@@ -820,6 +930,13 @@ __global__ __launch_bounds__(64) void k_wide_backup_select(MctsDev t, WideDev w)
     wave_sync();
     __syncthreads();
     wide_select_body(t, w, L, blockIdx.x, threadIdx.x);
+}
+__global__ __launch_bounds__(64) void k_wide_backup_select_n(MctsDev t, WideDev w) {
+    __shared__ WideLds L;
+    wide_expand_backup_body(t, w, L, blockIdx.x, threadIdx.x);
+    wave_sync();
+    __syncthreads();
+    wide_select_body<true>(t, w, L, blockIdx.x, threadIdx.x);
 }
 // dense batch in (game, j) order: prefix sum over the per-game leaf counts
 __global__ __launch_bounds__(1024) void k_wide_compact(MctsDev t, WideDev w) {
@@ -893,6 +1010,9 @@ struct oz_mcts {
     int leaves_per_step = 1;
     bool use_wide = false;           // oz_mcts_use_wide_kernels: K = 1 through the wide kernels
     bool wide() const { return leaves_per_step > 1 || use_wide; }
+    // root noise: true from the first arming on (d.noise_eta / d.noise_armed are then allocated): the descents run on the *_n kernels
+    bool noise_ever = false;
+    uint64_t* noise_ids = nullptr; int32_t* noise_plies = nullptr;      // staging of oz_mcts_sample_root_noise's keys, [G] each
 
     template <typename T> int alloc(T** p, size_t count) {
         OZ_HIP(hipMalloc((void**)p, sizeof(T) * (count ? count : 1)));
@@ -1033,7 +1153,7 @@ static int mcts_step_async(oz_mcts* m, oz_net* net, bool time_eval) {
     hipStream_t s = m->stream;
     const bool all = m->profile;
     long long i = all ? m->timer.begin(TS_SELECT, s) : -1;
-    hipLaunchKernelGGL(k_select, dim3(d.G), dim3(64), 0, s, d);
+    hipLaunchKernelGGL(m->noise_ever ? k_select_n : k_select, dim3(d.G), dim3(64), 0, s, d);
     m->timer.end(i, s);
     i = all ? m->timer.begin(TS_COMPACT, s) : -1;
     hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, s, d);
@@ -1107,8 +1227,8 @@ static int mcts_wide_steps(oz_mcts* m, oz_net* net, int nsims, int max_games, bo
         if (enqueued > (long long)nsims) { oz_set_error("leaf-parallel search: the simulation budget did not run out after %d steps (internal error)", nsims); return OZ_ERR_STATE; }
         for (int k = 0; k < steps; ++k) {
             long long i = all ? m->timer.begin(TS_SELECT, s) : -1;
-            if (k == 0) hipLaunchKernelGGL(k_wide_select, dim3(d.G), dim3(64), 0, s, d, w);
-            else hipLaunchKernelGGL(k_wide_backup_select, dim3(d.G), dim3(64), 0, s, d, w);
+            if (k == 0) hipLaunchKernelGGL(m->noise_ever ? k_wide_select_n : k_wide_select, dim3(d.G), dim3(64), 0, s, d, w);
+            else hipLaunchKernelGGL(m->noise_ever ? k_wide_backup_select_n : k_wide_backup_select, dim3(d.G), dim3(64), 0, s, d, w);
             m->timer.end(i, s);
             i = all ? m->timer.begin(TS_COMPACT, s) : -1;
             hipLaunchKernelGGL(k_wide_compact, dim3(1), dim3(1024), 0, s, d, w);
@@ -1148,8 +1268,8 @@ static int mcts_step_k(oz_mcts* m, oz_net* net, int k, int max_leaves, bool time
     hipStream_t s = m->stream;
     const bool all = m->profile;
     long long i = all ? m->timer.begin(TS_SELECT, s) : -1;
-    if (k == 0) hipLaunchKernelGGL(k_select, dim3(d.G), dim3(64), 0, s, d);
-    else hipLaunchKernelGGL(k_backup_select, dim3(d.G), dim3(64), 0, s, d);
+    if (k == 0) hipLaunchKernelGGL(m->noise_ever ? k_select_n : k_select, dim3(d.G), dim3(64), 0, s, d);
+    else hipLaunchKernelGGL(m->noise_ever ? k_backup_select_n : k_backup_select, dim3(d.G), dim3(64), 0, s, d);
     m->timer.end(i, s);
     i = all ? m->timer.begin(TS_COMPACT, s) : -1;
     hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, s, d);
@@ -1206,6 +1326,18 @@ OZ_API int oz_mcts_set_roots(oz_mcts* m, const uint64_t* own, const uint64_t* op
     const int G = m->d.G;
     for (int i = 0; i < G; ++i)
         OZ_REQUIRE((own[i] & opp[i]) == 0 && ((own[i] | opp[i]) & ~m->d.valid) == 0, "root %d is not a valid %dx%d board", i, m->d.n, m->d.n);
+    if (m->noise_ever) {                                   // root noise belongs to one board: a slot that gets another one loses it
+        std::vector<uint64_t> o(G), p(G);
+        std::vector<uint8_t> armed(G);
+        OZ_HIP(hipMemcpyAsync(o.data(), m->d.root_own, 8ull * G, hipMemcpyDeviceToHost, m->stream));
+        OZ_HIP(hipMemcpyAsync(p.data(), m->d.root_opp, 8ull * G, hipMemcpyDeviceToHost, m->stream));
+        OZ_HIP(hipMemcpyAsync(armed.data(), m->d.noise_armed, G, hipMemcpyDeviceToHost, m->stream));
+        OZ_HIP(hipStreamSynchronize(m->stream));
+        for (int i = 0; i < G; ++i)
+            if (o[i] != own[i] || p[i] != opp[i]) armed[i] = 0;
+        OZ_HIP(hipMemcpyAsync(m->d.noise_armed, armed.data(), G, hipMemcpyHostToDevice, m->stream));
+        OZ_HIP(hipStreamSynchronize(m->stream));           // (`armed` is a local: the copy must be done before it goes)
+    }
     OZ_HIP(hipMemcpyAsync(m->d.root_own, own, 8ull * G, hipMemcpyHostToDevice, m->stream));
     OZ_HIP(hipMemcpyAsync(m->d.root_opp, opp, 8ull * G, hipMemcpyHostToDevice, m->stream));
     if (active) OZ_HIP(hipMemcpyAsync(m->d.active, active, G, hipMemcpyHostToDevice, m->stream));
@@ -1274,12 +1406,116 @@ OZ_API int oz_mcts_wide_stats(oz_mcts* m, int64_t* out3) {
     return wide_stats_locked(m, out3);
 }
 
+// ---- root noise: host side
+static int noise_check(const char* fn, double alpha, double eps, bool with_alpha) {
+    OZ_REQUIRE(!with_alpha || (alpha >= 0.01 && alpha <= 100.0), "%s: alpha %g outside [0.01, 100]", fn, alpha);       // (NaN fails both compares)
+    OZ_REQUIRE(eps >= 0.0 && eps <= 1.0, "%s: eps %g outside [0, 1]", fn, eps);
+    return OZ_OK;
+}
+// eta and the armed flags, at the first arming: 513 B per game
+static int noise_alloc(oz_mcts* m) {
+    if (m->noise_ever) return OZ_OK;
+    MctsDev& d = m->d;
+    const size_t held = m->allocs.size();
+    double* eta = nullptr; uint8_t* armed = nullptr;
+    int rc = m->alloc(&eta, (size_t)d.G * 64);
+    if (!rc) rc = m->alloc(&armed, (size_t)d.G);
+    if (!rc && (hipMemsetAsync(eta, 0, sizeof(double) * 64 * (size_t)d.G, m->stream) != hipSuccess ||
+                hipMemsetAsync(armed, 0, (size_t)d.G, m->stream) != hipSuccess || hipStreamSynchronize(m->stream) != hipSuccess)) {
+        oz_set_error("root noise: clearing the buffers failed");
+        rc = OZ_ERR_HIP;
+    }
+    if (rc) {
+        for (size_t i = held; i < m->allocs.size(); ++i) hipFree(m->allocs[i]);
+        m->allocs.resize(held);
+        return rc;
+    }
+    d.noise_eta = eta; d.noise_armed = armed;
+    m->noise_ever = true;
+    return OZ_OK;
+}
+// every slot disarmed, nothing allocated
+static int noise_disarm(oz_mcts* m) {
+    m->d.noise_eps = 0.0;
+    if (m->noise_ever) {
+        OZ_HIP(hipMemsetAsync(m->d.noise_armed, 0, (size_t)m->d.G, m->stream));
+        OZ_HIP(hipStreamSynchronize(m->stream));
+    }
+    return OZ_OK;
+}
+#define OZ_REFUSE_PENDING(m, fn) \
+    do { if ((m)->selected) { oz_set_error(fn ": a step is pending (oz_mcts_select without oz_mcts_backup)"); return OZ_ERR_STATE; } } while (0)
+
+OZ_API int oz_mcts_set_root_noise(oz_mcts* m, double eps, const double* eta, const uint8_t* armed) {
+    OZ_REQUIRE(m, "null mcts");
+    if (int rc = noise_check("oz_mcts_set_root_noise", 1.0, eps, false)) return rc;
+    std::lock_guard<std::mutex> lk(m->mu);
+    OZ_REFUSE_PENDING(m, "oz_mcts_set_root_noise");
+    hipSetDevice(m->device);
+    if (!eta || eps == 0.0) return noise_disarm(m);
+    const int G = m->d.G;
+    for (size_t i = 0; i < (size_t)G * 64; ++i) OZ_REQUIRE(eta[i] >= 0.0 && eta[i] <= 1.0, "oz_mcts_set_root_noise: eta[%zu][%zu] = %g outside [0, 1]", i / 64, i % 64, eta[i]);
+    if (int rc = noise_alloc(m)) return rc;
+    OZ_HIP(hipMemcpyAsync(m->d.noise_eta, eta, sizeof(double) * 64 * (size_t)G, hipMemcpyHostToDevice, m->stream));
+    std::vector<uint8_t> a;
+    if (armed) {
+        a.resize(G);
+        for (int i = 0; i < G; ++i) a[i] = armed[i] ? 1 : 0;
+        OZ_HIP(hipMemcpyAsync(m->d.noise_armed, a.data(), G, hipMemcpyHostToDevice, m->stream));
+    } else hipLaunchKernelGGL(k_noise_arm_active, dim3((G + 255) / 256), dim3(256), 0, m->stream, m->d);
+    OZ_HIP(hipGetLastError());
+    OZ_HIP(hipStreamSynchronize(m->stream));
+    m->d.noise_eps = eps;
+    return OZ_OK;
+}
+OZ_API int oz_mcts_sample_root_noise(oz_mcts* m, double alpha, double eps, uint64_t seed, const uint64_t* game_ids, const int32_t* plies) {
+    OZ_REQUIRE(m && game_ids && plies, "null argument");
+    if (int rc = noise_check("oz_mcts_sample_root_noise", alpha, eps, true)) return rc;
+    std::lock_guard<std::mutex> lk(m->mu);
+    OZ_REFUSE_PENDING(m, "oz_mcts_sample_root_noise");
+    hipSetDevice(m->device);
+    if (eps == 0.0) return noise_disarm(m);
+    const int G = m->d.G;
+    for (int i = 0; i < G; ++i) OZ_REQUIRE(plies[i] >= 0, "oz_mcts_sample_root_noise: plies[%d] = %d", i, plies[i]);
+    if (int rc = noise_alloc(m)) return rc;
+    if (!m->noise_ids) {
+        if (int rc = m->alloc(&m->noise_ids, (size_t)G)) return rc;
+        if (int rc = m->alloc(&m->noise_plies, (size_t)G)) return rc;
+    }
+    OZ_HIP(hipMemcpyAsync(m->noise_ids, game_ids, 8ull * G, hipMemcpyHostToDevice, m->stream));
+    OZ_HIP(hipMemcpyAsync(m->noise_plies, plies, 4ull * G, hipMemcpyHostToDevice, m->stream));
+    hipLaunchKernelGGL(k_root_noise, dim3(G), dim3(64), 0, m->stream, m->d, alpha, seed, (const uint64_t*)m->noise_ids, (const int*)m->noise_plies);
+    OZ_HIP(hipGetLastError());
+    OZ_HIP(hipStreamSynchronize(m->stream));
+    m->d.noise_eps = eps;
+    return OZ_OK;
+}
+static int noise_read_locked(oz_mcts* m, double* eta, uint8_t* armed) {
+    const int G = m->d.G;
+    if (!m->noise_ever) {
+        if (eta) memset(eta, 0, sizeof(double) * 64 * (size_t)G);
+        if (armed) memset(armed, 0, (size_t)G);
+        return OZ_OK;
+    }
+    if (eta) OZ_HIP(hipMemcpyAsync(eta, m->d.noise_eta, sizeof(double) * 64 * (size_t)G, hipMemcpyDeviceToHost, m->stream));
+    if (armed) OZ_HIP(hipMemcpyAsync(armed, m->d.noise_armed, (size_t)G, hipMemcpyDeviceToHost, m->stream));
+    OZ_HIP(hipStreamSynchronize(m->stream));
+    return OZ_OK;
+}
+OZ_API int oz_mcts_get_root_noise(oz_mcts* m, double* eta, uint8_t* armed, double* eps) {
+    OZ_REQUIRE(m, "null mcts");
+    std::lock_guard<std::mutex> lk(m->mu);
+    hipSetDevice(m->device);
+    if (eps) *eps = m->d.noise_eps;
+    return noise_read_locked(m, eta, armed);
+}
+
 OZ_API int oz_mcts_select(oz_mcts* m) {
     OZ_REQUIRE(m, "null mcts");
     std::lock_guard<std::mutex> lk(m->mu);
     OZ_REFUSE_WIDE(m, "oz_mcts_select");
     hipSetDevice(m->device);
-    hipLaunchKernelGGL(k_select, dim3(m->d.G), dim3(64), 0, m->stream, m->d);
+    hipLaunchKernelGGL(m->noise_ever ? k_select_n : k_select, dim3(m->d.G), dim3(64), 0, m->stream, m->d);
     OZ_HIP(hipGetLastError());
     m->selected = true;
     return check_error_flag(m);
@@ -1484,6 +1720,7 @@ __global__ void k_sp_roots(GamesDev gm, MctsDev t, int mover_filter /* 0 all, +1
     const int p = gm.player[g];
     const bool act = !gm.finished[g] && (mover_filter == 0 || mover_filter == p);
     t.active[g] = act ? 1 : 0;
+    if (t.noise_armed) t.noise_armed[g] = 0;              // root noise belongs to the old root (k_root_noise follows where the engine draws it)
     if (act) {
         t.root_node[g] = -1;
         t.root_own[g] = p == 1 ? gm.black[g] : gm.white[g];
@@ -1499,6 +1736,7 @@ __global__ void k_sp_roots_stagger(GamesDev gm, MctsDev t, int round, int period
     const int p = gm.player[g];
     const bool act = !gm.finished[g] && offset > round;
     t.active[g] = act ? 1 : 0;
+    if (t.noise_armed) t.noise_armed[g] = 0;              // root noise belongs to the old root (k_root_noise follows where the engine draws it)
     if (act) {
         t.root_node[g] = -1;
         t.root_own[g] = p == 1 ? gm.black[g] : gm.white[g];
@@ -1509,8 +1747,13 @@ __global__ void k_sp_roots_stagger(GamesDev gm, MctsDev t, int round, int period
 // K7: root policy extraction + action choice + OthelloGame.play + example recording
 // (othelo_mcts.py:51-67, training.py:45-67 / agents.py:52-68).  One wave per game.
 //   arena != 0: agents.py semantics (temperature 0, argmax over valid actions of the one-hot).
+// NOISE (the free-running advance of an engine with root noise): the move takes the slot to another root -- its noise is dropped, the advance
+// draws the next root's.  The lock-step k_sp_move leaves root and noise as they are until the next round's roots kernel (oz_selfplay_root_noise
+// reads them in between).
+template <bool NOISE = false>
 __device__ __forceinline__ void sp_move_body(const GamesDev& gm, const MctsDev& t, int g, int lane, int arena) {
     if (!t.active[g]) return;
+    if constexpr (NOISE) { if (lane == 0) t.noise_armed[g] = 0; }
     const uint64_t own = uni64(t.root_own[g]), opp = uni64(t.root_opp[g]);
     const uint64_t legal = oz_legal(own, opp, t.valid);
     const int node = root_lookup(t, g, own, opp, lane);
@@ -1618,7 +1861,12 @@ __global__ __launch_bounds__(64) void k_sp_move(GamesDev gm, MctsDev t, int aren
 // (bench.py --driver free): cap 24 -> 4081 leaves per batch but 367 us per launch, 1.40 M expansions/s; cap 8 -> 1.56 M;
 // cap 4 -> 1.585 M; cap 2 -> 3908 leaves per batch, 1.59 M (1.60 M with k_backup_advance; the lock-step driver: 1.56-1.58 M).
 #define OZ_ADVANCE_CAP 2
-__device__ __forceinline__ void advance_body(const GamesDev& gm, const MctsDev& t, TreeLds& L, int g, int lane, int sims, int* __restrict__ sims_done, int cap) {
+// NOISE: the root noise of a game's root is drawn here, before the first descent from it (noise_armed[g] == 0: a fresh engine, or the move above
+// has just changed the root), keyed (seed, game id, ply) like k_root_noise in the lock-step round: the records stay those of oz_selfplay_run.
+struct NoiseDraw { double alpha; uint64_t seed; };
+template <bool NOISE = false>
+__device__ __forceinline__ void advance_body(const GamesDev& gm, const MctsDev& t, TreeLds& L, int g, int lane, int sims, int* __restrict__ sims_done, int cap,
+                                             NoiseDraw nz = NoiseDraw{}) {
     if (unii(t.leaf_status[g]) == OZ_LEAF_WAIT) {          // batch cap: the leaf of the simulation in progress found no slot -- offer it again, unchanged
         if (lane == 0) t.leaf_status[g] = OZ_LEAF_EVAL;
         return;
@@ -1637,13 +1885,19 @@ __device__ __forceinline__ void advance_body(const GamesDev& gm, const MctsDev& 
         }
         wave_sync();                                       // lane 0's stores are visible to the wave's next loads
         if (done >= sims) {                                // training.py:42-67: the move after num_simulations simulations
-            sp_move_body(gm, t, g, lane, 0);
+            sp_move_body<NOISE>(gm, t, g, lane, 0);
             done = 0;
             if (lane == 0) t.leaf_status[g] = OZ_LEAF_IDLE;    // the evaluated leaf is consumed: nothing pending if the cap ends the loop here
             wave_sync();
             continue;                                      // (a finished game is refilled by the move, or goes idle above)
         }
-        status = select_body(t, L, g, lane);
+        if constexpr (NOISE) {
+            if (t.noise_eps > 0.0 && unii((int)t.noise_armed[g]) == 0) {
+                root_noise_body(t, L.arr, g, lane, uni64(t.root_own[g]), uni64(t.root_opp[g]), nz.alpha, nz.seed, uni64(gm.game_id[g]), unii(gm.ply[g]));
+                wave_sync();
+            }
+        }
+        status = select_body<NOISE>(t, L, g, lane);
         if (status != OZ_LEAF_TERMINAL) break;             // EVAL: wait for the network; IDLE: error path
         wave_sync();
         backup_body(t, g, lane, (double)t.term_value[g], VT_INT);
@@ -1666,6 +1920,18 @@ __global__ __launch_bounds__(64) void k_backup_advance(GamesDev gm, MctsDev t, i
     wave_sync();
     __syncthreads();
     advance_body(gm, t, L, blockIdx.x, threadIdx.x, sims, sims_done, cap);
+}
+
+__global__ __launch_bounds__(64) void k_advance_n(GamesDev gm, MctsDev t, int sims, int* __restrict__ sims_done, int cap, NoiseDraw nz) {
+    __shared__ TreeLds L;
+    advance_body<true>(gm, t, L, blockIdx.x, threadIdx.x, sims, sims_done, cap, nz);
+}
+__global__ __launch_bounds__(64) void k_backup_advance_n(GamesDev gm, MctsDev t, int sims, int* __restrict__ sims_done, int cap, NoiseDraw nz) {
+    __shared__ TreeLds L;
+    expand_backup_body(t, L, blockIdx.x, threadIdx.x, 0);
+    wave_sync();
+    __syncthreads();
+    advance_body<true>(gm, t, L, blockIdx.x, threadIdx.x, sims, sims_done, cap, nz);
 }
 
 // RandomOthelloAgent.play (agents.py:20-24) for every live game whose mover is `side`: random.choice over the valid
@@ -1705,6 +1971,8 @@ struct oz_selfplay {
     int batch_cap = 0;               // free-running driver: leaves per network batch (0: up to G)
     long long batch_no = 0;          // batches launched by the free-running driver (rotation of the slot order under a cap)
     int stagger_period = 0;
+    bool noise_on = false;           // oz_selfplay_set_root_noise: every searched move draws Dir(noise_alpha) at its root
+    double noise_alpha = 0.0;
     std::vector<void*> allocs;
     std::mutex mu;
     long long records_read = 0;
@@ -1813,6 +2081,7 @@ static int selfplay_round_async(oz_selfplay* sp, int sims, int stagger_round) {
     long long ti = m->profile ? m->timer.begin(TS_MOVE, s) : -1;
     if (stagger_round >= 0) hipLaunchKernelGGL(k_sp_roots_stagger, dim3((G + 255) / 256), dim3(256), 0, s, sp->gm, m->d, stagger_round, sp->stagger_period);
     else hipLaunchKernelGGL(k_sp_roots, dim3((G + 255) / 256), dim3(256), 0, s, sp->gm, m->d, 0);
+    if (sp->noise_on) hipLaunchKernelGGL(k_root_noise, dim3(G), dim3(64), 0, s, m->d, sp->noise_alpha, sp->gm.seed, (const uint64_t*)sp->gm.game_id, (const int*)sp->gm.ply);
     m->timer.end(ti, s);
     if (int rc = mcts_steps_async(m, sp->net, sims, true)) return rc;
     ti = m->profile ? m->timer.begin(TS_MOVE, s) : -1;
@@ -1890,6 +2159,30 @@ OZ_API int oz_selfplay_set_leaves_per_step(oz_selfplay* sp, int k) {
     return wide_set_k(sp->m, k);
 }
 
+// root noise for every searched move of the engine (the lock-step rounds, oz_selfplay_stagger's included, and the free-running driver); before
+// the first driver call
+OZ_API int oz_selfplay_set_root_noise(oz_selfplay* sp, double alpha, double eps) {
+    OZ_REQUIRE(sp, "null selfplay");
+    if (int rc = noise_check("oz_selfplay_set_root_noise", alpha, eps, true)) return rc;
+    std::lock_guard<std::mutex> lk(sp->mu);
+    if (sp->mode != 0) { oz_set_error("oz_selfplay_set_root_noise: the engine has been driven already (set it before the first driver call)"); return OZ_ERR_STATE; }
+    std::lock_guard<std::mutex> lkm(sp->m->mu);
+    hipSetDevice(sp->m->device);
+    if (eps == 0.0) { sp->noise_on = false; return noise_disarm(sp->m); }
+    if (int rc = noise_alloc(sp->m)) return rc;
+    sp->m->d.noise_eps = eps;
+    sp->noise_alpha = alpha; sp->noise_on = true;
+    return OZ_OK;
+}
+OZ_API int oz_selfplay_root_noise(oz_selfplay* sp, double* eta, uint8_t* armed) {
+    OZ_REQUIRE(sp, "null selfplay");
+    std::lock_guard<std::mutex> lk(sp->mu);
+    std::lock_guard<std::mutex> lkm(sp->m->mu);
+    hipSetDevice(sp->m->device);
+    OZ_HIP(hipStreamSynchronize(sp->m->stream));
+    return noise_read_locked(sp->m, eta, armed);
+}
+
 OZ_API int oz_selfplay_run_steps(oz_selfplay* sp, int steps) {
     OZ_REQUIRE(sp, "null selfplay");
     std::lock_guard<std::mutex> lk(sp->mu);
@@ -1902,6 +2195,7 @@ OZ_API int oz_selfplay_run_steps(oz_selfplay* sp, int steps) {
     hipSetDevice(m->device);
     MctsDev& d = m->d;
     if (sp->mode == 1) OZ_HIP(hipMemsetAsync(d.leaf_status, 0, sizeof(int) * d.G, m->stream));    // no simulation is pending after whole rounds
+    if (sp->mode == 1 && m->noise_ever) OZ_HIP(hipMemsetAsync(d.noise_armed, 0, (size_t)d.G, m->stream));     // ... and the last round's noise is that of the roots before its moves
     sp->mode = 2;
     selfplay_attach_cache(sp);
     const bool fuse = true;
@@ -1913,7 +2207,11 @@ OZ_API int oz_selfplay_run_steps(oz_selfplay* sp, int steps) {
         // enough to keep the batches full and the launch is as short as the lock-step one (measured: +1.2 % expansions/s, +3 % games/s over 2)
         const int adv_cap = (sp->batch_cap > 0 && sp->batch_cap < d.G ? 1 : OZ_ADVANCE_CAP);
         // (from the second batch of a call on, the previous batch's expand + backup rides in the same launch; one closing k_expand_backup per call)
-        if (fuse && i > 0) hipLaunchKernelGGL(k_backup_advance, dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap);
+        if (m->noise_ever) {
+            const NoiseDraw nz{sp->noise_alpha, sp->gm.seed};
+            if (fuse && i > 0) hipLaunchKernelGGL(k_backup_advance_n, dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap, nz);
+            else hipLaunchKernelGGL(k_advance_n, dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap, nz);
+        } else if (fuse && i > 0) hipLaunchKernelGGL(k_backup_advance, dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap);
         else hipLaunchKernelGGL(k_advance, dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap);
         m->timer.end(ti, s);
         ti = all ? m->timer.begin(TS_COMPACT, s) : -1;

@@ -173,7 +173,8 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
              e_greedy, evaluation_interval, evaluation_iterations, temperature_threshold, self_play_training,
              self_play_interval, self_play_total_games, self_play_threshold, checkpoint_filepath, training_buffer_size,
              seed=1234, reference_aliasing=True, alias_final_boards=True, dump_examples=False, q_mode=_lib.QMODE_F64,
-             distributed=False, batched_evaluation=False, policy_target="onehot", target_temperature=1.0, leaves_per_step=1):
+             distributed=False, batched_evaluation=False, policy_target="onehot", target_temperature=1.0, leaves_per_step=1,
+             root_noise=None):
     """main.py:56-259 on the GPU engines; returns `historic` = [(episodes done, win rate vs random), ...]
 
     batched_evaluation=True plays the evaluation games against RandomOthelloAgent in lock step on the GPU
@@ -191,7 +192,11 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
     cannot learn how pi's mass splits between board rows).
 
     leaves_per_step > 1: the batched engines (self-play, matches, batched evaluation) run that many descents per game and network
-    batch under virtual loss; the networks need max_batch >= games * leaves_per_step.  The drop-in evaluation agents keep 1."""
+    batch under virtual loss; the networks need max_batch >= games * leaves_per_step.  The drop-in evaluation agents keep 1.
+
+    root_noise=(alpha, epsilon): Dirichlet noise on the root prior of every searched SELF-PLAY move (SelfPlayEngine), in the single-process and
+    the distributed path alike; matches and evaluations stay noise-free."""
+    root_noise = _lib.check_root_noise(root_noise)
     if policy_target not in ("onehot", "visits"):
         raise ValueError(f"policy_target must be 'onehot' or 'visits' (got {policy_target!r})")
     visits = policy_target == "visits"
@@ -239,7 +244,7 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
             first, count = shard_games(num_episodes, rank, world)
             eng = SelfPlayEngine(neural_network, board_size, count, num_simulations, degree_exploration, temperature, e_greedy,
                                  seed=seed, first_game_id=total_episodes_done + first, q_mode=q_mode, record_visits=visits,
-                                 leaves_per_step=leaves_per_step)
+                                 leaves_per_step=leaves_per_step, root_noise=root_noise)
             eng.play_to_end()
             records = pooled_selfplay_records(eng, device, with_visits=visits)      # the only exchange of the self-play phase
             del eng
@@ -247,7 +252,7 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
             records = selfplay_batch(neural_network, board_size, num_games=num_episodes, num_simulations=num_simulations,
                                      degree_exploration=degree_exploration, policy_temperature=temperature, e_greedy=e_greedy,
                                      seed=seed, first_game_id=total_episodes_done, q_mode=q_mode, record_visits=visits,
-                                     leaves_per_step=leaves_per_step)
+                                     leaves_per_step=leaves_per_step, root_noise=root_noise)
         counts = None
         if visits:
             records, counts = records

@@ -71,6 +71,45 @@ class OthelloMCTS:
         c0, c1 = _lib.pack_board(state)
         return (c1, c0) if player is OthelloPlayer.WHITE or getattr(player, "value", 1) == -1 else (c0, c1)
 
+    # ---- root noise (include/othellozero_amd.h, "root noise"): applied at selection time to the root it is set for; stored priors never change
+    def set_root_noise(self, eta, epsilon, state=None, player=None):
+        """host-supplied noise for the current root (or for `state` seen by `player`, which becomes the root): eta = (n, n) or (64,) by square
+        row*8+col, 0 off the legal set.  eta None or epsilon 0 disarms."""
+        epsilon = float(epsilon)
+        if not 0.0 <= epsilon <= 1.0:
+            raise ValueError(f"epsilon must be in [0, 1] (got {epsilon})")
+        if state is not None:
+            self._set_root(*self._canonical(state, player))
+        row = None
+        if eta is not None:
+            e = np.asarray(eta, dtype=np.float64)
+            n = self._board_size
+            row = np.zeros((1, 64), np.float64)
+            if e.shape == (n, n):
+                row.reshape(8, 8)[:n, :n] = e
+            elif e.size == 64:
+                row[0] = e.ravel()
+            else:
+                raise ValueError(f"eta must be ({n}, {n}) or 64 values (got shape {e.shape})")
+            if not (np.isfinite(row).all() and (row >= 0).all() and (row <= 1).all()):
+                raise ValueError("eta must lie in [0, 1]")
+        _lib.check(_lib.load().oz_mcts_set_root_noise(self._h, epsilon, None if row is None else _lib.p_f64(row), None))
+
+    def sample_root_noise(self, alpha, epsilon, seed, game_id, ply, state=None, player=None):
+        """device-drawn Dirichlet(alpha) noise over the legal moves of the current root (or of `state` seen by `player`, which becomes the
+        root), keyed (seed, game_id, ply)"""
+        alpha, epsilon = _lib.check_root_noise((alpha, epsilon))
+        if state is not None:
+            self._set_root(*self._canonical(state, player))
+        gid, pl = np.array([int(game_id)], np.uint64), np.array([int(ply)], np.int32)
+        _lib.check(_lib.load().oz_mcts_sample_root_noise(self._h, alpha, epsilon, int(seed), _lib.p_u64(gid), _lib.p_i32(pl)))
+
+    def root_noise(self):
+        """(eta (64,) float64 by square, armed bool, epsilon) of the current root"""
+        eta, armed, eps = np.zeros((1, 64), np.float64), np.zeros(1, np.uint8), C.c_double()
+        _lib.check(_lib.load().oz_mcts_get_root_noise(self._h, _lib.p_f64(eta), _lib.p_u8(armed), C.byref(eps)))
+        return eta[0], bool(armed[0]), eps.value
+
     # ---- reference surface
     def simulate(self, state, player):
         """othelo_mcts.py:22-26 + MCTS/__init__.py:30-71; `state` is not mutated."""

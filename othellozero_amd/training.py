@@ -32,7 +32,7 @@ def training_example_symmetries(board, policy):
 
 def execute_episode(board_size, neural_network, degree_exploration, num_simulations, policy_temperature, e_greedy,
                     q_mode=_lib.QMODE_F64, snapshot_boards=False, policy_target="onehot", target_temperature=1.0,
-                    leaves_per_step=1):
+                    leaves_per_step=1, root_noise=None, noise_seed=0):
     """training.py:26-72.  Returns [(board (n,n,2) bool, one-hot policy (n,n) float64, z int), ...], 8 per move.
 
     snapshot_boards=False reproduces the reference exactly, including its aliasing quirk: the
@@ -43,7 +43,11 @@ def execute_episode(board_size, neural_network, degree_exploration, num_simulati
     pi): mcts.get_policy_action_probabilities(state, target_temperature) at every move.  With target_temperature > 0 that
     call draws no random number, so moves and random streams are those of the default "onehot".
 
-    leaves_per_step > 1: that many descents per network batch under virtual loss (OthelloMCTS); a native network only."""
+    leaves_per_step > 1: that many descents per network batch under virtual loss (OthelloMCTS); a native network only.
+
+    root_noise=(alpha, epsilon): Dirichlet noise on the root prior, drawn on the device once per move before that move's simulations, keyed
+    (noise_seed, 0, ply) with ply = the moves played so far; None is the function without it."""
+    root_noise = _lib.check_root_noise(root_noise)
     assert policy_target in ("onehot", "visits"), policy_target
     if policy_target == "visits" and not target_temperature > 0:
         raise ValueError(f"target_temperature must be > 0 for visit-count targets (got {target_temperature})")
@@ -56,6 +60,8 @@ def execute_episode(board_size, neural_network, degree_exploration, num_simulati
 
     while not game.has_finished():
         state = game.board(BoardView.TWO_CHANNELS)
+        if root_noise is not None:
+            mcts.sample_root_noise(root_noise[0], root_noise[1], noise_seed, 0, len(examples) // 8, state=state, player=game.current_player)
         mcts.simulate_n(state, game.current_player, num_simulations)
         if game.current_player == OthelloPlayer.WHITE:
             state = OthelloGame.invert_board(state)
@@ -127,7 +133,7 @@ class SelfPlayEngine:
     def __init__(self, neural_network, board_size=8, num_games=4096, num_simulations=100, degree_exploration=1.0,
                  policy_temperature=1.0, e_greedy=0.9, seed=1234, first_game_id=0, game_id_stride=0,
                  q_mode=_lib.QMODE_F64, refill=False, node_cap=0, record_cap=0, dedup=True, batch_cap=0, eval_cache=False,
-                 record_visits=False, leaves_per_step=1):
+                 record_visits=False, leaves_per_step=1, root_noise=None):
         """dedup: cross-game leaf de-duplication (a board several games reach in one batch is evaluated once; no record changes);
         batch_cap: leaves per network batch of the free-running driver (0 = none; see preferred_batch_cap);
         eval_cache: take (pi, v) of boards the network has evaluated before from its persistent cache (NNetWrapper.set_eval_cache) --
@@ -136,7 +142,11 @@ class SelfPlayEngine:
         expand_examples(visits=...); 16 KB per slot + 256 B per record of device memory, no record changes;
         leaves_per_step > 1: that many descents per game and network batch under virtual loss (oz_mcts_set_leaves_per_step) for run() /
         stagger(); the network needs max_batch >= num_games * leaves_per_step; run_steps() then raises; dedup and eval_cache then have no
-        effect (every leaf is evaluated) and run(sync=False) still waits once per move round.  Not the reference's search order."""
+        effect (every leaf is evaluated) and run(sync=False) still waits once per move round.  Not the reference's search order.
+        root_noise=(alpha, epsilon): every searched move draws Dirichlet(alpha) noise over its root's legal moves on the device, keyed
+        (seed, game id, ply), and its descents see (1 - epsilon) P + epsilon eta at the root (oz_selfplay_set_root_noise); stored priors and
+        the records' layout do not change."""
+        root_noise = _lib.check_root_noise(root_noise)
         lib = _lib.require_gpu()
         assert getattr(neural_network, "_h", None) is not None, "SelfPlayEngine needs a native NNetWrapper / StubNetWrapper"
         self.net = neural_network
@@ -152,6 +162,9 @@ class SelfPlayEngine:
         self.leaves_per_step = int(leaves_per_step)
         if self.leaves_per_step != 1:
             _lib.check(lib.oz_selfplay_set_leaves_per_step(self._h, self.leaves_per_step))
+        self.root_noise = root_noise
+        if root_noise is not None:
+            _lib.check(lib.oz_selfplay_set_root_noise(self._h, root_noise[0], root_noise[1]))
 
     def __del__(self):
         try:
@@ -219,6 +232,12 @@ class SelfPlayEngine:
         _lib.check(_lib.load().oz_selfplay_state(self._h, _lib.p_u64(b), _lib.p_u64(w), _lib.p_i8(p), _lib.p_u8(f),
                                                  _lib.p_i32(ply), _lib.p_u64(gid)))
         return dict(black=b, white=w, player=p, finished=f, ply=ply, game_id=gid)
+
+    def last_root_noise(self):
+        """(eta float64 (num_games, 64) by square, armed uint8 (num_games,)) of the searches of the last move round of run()"""
+        eta, armed = np.zeros((self.num_games, 64), np.float64), np.zeros(self.num_games, np.uint8)
+        _lib.check(_lib.load().oz_selfplay_root_noise(self._h, _lib.p_f64(eta), _lib.p_u8(armed)))
+        return eta, armed
 
     def last_counts(self):
         c = np.zeros((self.num_games, 64), np.int32)
@@ -314,11 +333,13 @@ def expand_examples(records, board_size, alias_final=False, visits=None, target_
 
 def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations=100, degree_exploration=1.0,
                    policy_temperature=1.0, e_greedy=0.9, seed=1234, first_game_id=0, q_mode=_lib.QMODE_F64,
-                   expand=False, alias_final=False, record_visits=False, target_temperature=1.0, leaves_per_step=1):
+                   expand=False, alias_final=False, record_visits=False, target_temperature=1.0, leaves_per_step=1, root_noise=None):
     """Play num_games complete games; returns the move records (or the expanded examples).
-    record_visits=True: (records, visit counts) -- or, with expand, the examples with visit-distribution targets at target_temperature."""
+    record_visits=True: (records, visit counts) -- or, with expand, the examples with visit-distribution targets at target_temperature.
+    root_noise=(alpha, epsilon): Dirichlet root noise in every search (SelfPlayEngine)."""
     eng = SelfPlayEngine(neural_network, board_size, num_games, num_simulations, degree_exploration, policy_temperature,
-                         e_greedy, seed, first_game_id, q_mode=q_mode, record_visits=record_visits, leaves_per_step=leaves_per_step)
+                         e_greedy, seed, first_game_id, q_mode=q_mode, record_visits=record_visits, leaves_per_step=leaves_per_step,
+                         root_noise=root_noise)
     if record_visits:
         rec, counts = eng.play_to_end(with_visits=True)
         return expand_examples(rec, board_size, alias_final, visits=counts, target_temperature=target_temperature) if expand else (rec, counts)
