@@ -259,20 +259,24 @@ template <bool NOISE> __device__ __forceinline__ bool noise_of_slot(const MctsDe
 // ---------------------------------------------------------------- K4: select / descend
 // MCTS.simulate down to the first terminal or unexpanded state (MCTS/__init__.py:39-44,58-67),
 // get_next_state (othelo_mcts.py:43-49).  One wave per game; per level ONE wave-wide load stages the node's record in LDS.
-// (body shared by k_select and the free-running k_advance; returns the status it stored in leaf_status[g])
-template <bool NOISE = false>
-__device__ __forceinline__ int select_body(const MctsDev& t, TreeLds& L, int g, int lane) {
-    if (!t.active[g]) {
-        if (lane == 0) t.leaf_status[g] = OZ_LEAF_IDLE;
-        return OZ_LEAF_IDLE;
-    }
-    double eta = 0.0;
-    const bool noisy = noise_of_slot<NOISE>(t, g, lane, &eta);
-    uint64_t own = uni64(t.root_own[g]), opp = uni64(t.root_opp[g]);
+// One descent from a root down to the first terminal or unknown state; shared by the one-descent-per-step search (select_body) and the
+// leaf-parallel one (wide_select_body).  `rec` / `path` = the LDS record stage and this descent's frontier (OZ_MAX_DEPTH entries);
+// `rootn` = the caller's cached record index of the root, kept up to date; noisy / eta = the slot's root-noise view (noise_of_slot).
+// The statistics are seen through the step's descents already in flight ("leaf-parallel search" below): descents 0 .. fl.n-1 with their
+// frontiers and depths.  With none in flight (select_body passes a literal 0: the loop compiles away) the view is the identity.
+struct InFlight { const int2 (*path)[OZ_MAX_DEPTH]; const int* depth; int n; };
+struct Descent {
+    uint64_t own, opp, legal;  // where it ended, and the mover's legal set there
+    int depth, status, tval;
+    int fs;                    // free table slot of the probe that left the known tree (-1: none)
+    int err;                   // EF_* bit of an error exit (status is then OZ_LEAF_IDLE), 0: none
+};
+template <bool NOISE>
+__device__ __forceinline__ Descent descend_one(const MctsDev& t, uint4* rec, int2* path, int g, int lane, uint64_t own, uint64_t opp, uint64_t legal,
+                                               int& rootn, bool noisy, double eta, const InFlight fl) {
     int depth = 0, status, tval = 0, err = 0, fs = -1;
-    int node = unii(t.root_node[g]);                            // record index of the state we stand on, -1 = unknown
+    int node = rootn;                                           // record index of the state we stand on, -1 = unknown
     int pnode = -1, prank = 0;                                  // the edge we arrived through (to cache the child index)
-    uint64_t legal = oz_legal(own, opp, t.valid);
     for (;;) {
         // `legal` = the mover's legal set of the state we stand on (of the root above; below, the move that led here computed it)
         if (legal == 0 && oz_legal(opp, own, t.valid) == 0) {       // is_terminal_state, othelo_mcts.py:28-29
@@ -284,6 +288,7 @@ __device__ __forceinline__ int select_body(const MctsDev& t, TreeLds& L, int g, 
         if (node < 0) {                                             // leaving the known tree: is the state in the table (transposition)?
             node = ht_find(t, g, own, opp, lane, &fs);
             if (node < 0) { status = OZ_LEAF_EVAL; break; }
+            if (pnode < 0) rootn = node;
             if (lane == 0) {
                 if (pnode >= 0) rec_edge(t, g, pnode, prank)->child = node;
                 else t.root_node[g] = node;
@@ -296,20 +301,32 @@ __device__ __forceinline__ int select_body(const MctsDev& t, TreeLds& L, int g, 
         const int cnt = oz_popc(legal);
         const int chunks = (OZ_REC_HDR + cnt * OZ_EDGE_BYTES + 15) >> 4;
         __syncthreads();                                            // the previous level's LDS reads are done
-        if (lane < chunks) L.rec[lane] = reinterpret_cast<const uint4*>(rec_ptr(t, g, node))[lane];
+        if (lane < chunks) rec[lane] = reinterpret_cast<const uint4*>(rec_ptr(t, g, node))[lane];
         __syncthreads();
-        const uint64_t* w = reinterpret_cast<const uint64_t*>(L.rec);
+        const uint64_t* w = reinterpret_cast<const uint64_t*>(rec);
         const int Ns = unii((int)(uint32_t)w[2]);
         const bool is_legal = (legal >> lane) & 1;
         const int rank = oz_popc(legal & ((1ULL << lane) - 1ULL));
+        // the in-flight descents of this step that stand on this node at this level, and those that took this lane's edge from it
+        int ks = 0, ke = 0;
+        for (int i = 0; i < fl.n; ++i)
+            if (fl.depth[i] > depth) {
+                const int2 pe = fl.path[i][depth];
+                if (pe.x == node) { ++ks; ke += pe.y == rank ? 1 : 0; }
+            }
         double U = -INFINITY;
         int child = -1;
         if (is_legal) {
             const uint64_t w0 = w[4 + 3 * rank];
-            const int N = (int)((uint32_t)w0 & ~OZ_TAG_F32);
+            int N = (int)((uint32_t)w0 & ~OZ_TAG_F32);
             child = (int)(w0 >> 32);
-            const double Q = __longlong_as_double((long long)w[5 + 3 * rank]), P = __longlong_as_double((long long)w[6 + 3 * rank]);
-            const double bound = sqrt((double)Ns) / (double)(1 + N);       // MCTS/__init__.py:169
+            double Q = __longlong_as_double((long long)w[5 + 3 * rank]);
+            const double P = __longlong_as_double((long long)w[6 + 3 * rank]);
+            if (ke) {                                                       // ke == 0 reads the stored bits: (N * Q) / N is not Q
+                Q = ((double)N * Q - (double)ke) / (double)(N + ke);
+                N += ke;
+            }
+            const double bound = sqrt((double)(Ns + ks)) / (double)(1 + N);    // MCTS/__init__.py:169
             U = Q + (t.c * P) * bound;                                     // :170, left to right
             if constexpr (NOISE) {
                 if (noisy && depth == 0) U = Q + (t.c * ((1.0 - t.noise_eps) * P + t.noise_eps * eta)) * bound;     // the root's noisy view of P
@@ -318,7 +335,7 @@ __device__ __forceinline__ int select_body(const MctsDev& t, TreeLds& L, int g, 
         const double m = wave_max_f64(U);
         const int best = oz_ctz(__ballot(is_legal && U == m));             // first maximum
         const int brank = oz_popc(legal & ((1ULL << best) - 1ULL));
-        if (lane == 0) L.path[depth] = make_int2(node, brank);
+        if (lane == 0) path[depth] = make_int2(node, brank);
         ++depth;
         pnode = node; prank = brank;
         node = lane_get(child, best);
@@ -328,18 +345,33 @@ __device__ __forceinline__ int select_body(const MctsDev& t, TreeLds& L, int g, 
         if (theirs != 0) { uint64_t s = own; own = opp; opp = s; legal = theirs; }
         else legal = oz_legal(own, opp, t.valid);                   // pass (or the game is over): the same side is to move again
     }
-    __syncthreads();
-    if (lane < depth) t.path[(size_t)g * OZ_MAX_DEPTH + lane] = L.path[lane];            // the frontier, one coalesced store
-    if (lane == 0) {
-        t.leaf_status[g] = status;
-        t.leaf_own[g] = own; t.leaf_opp[g] = opp; t.leaf_legal[g] = legal; t.leaf_fs[g] = fs;
-        t.depth[g] = depth; t.term_value[g] = tval;
-        unsigned long long* st = t.stat + (size_t)g * OZ_NSTAT;
-        st[ST_SIMS] += 1; st[ST_VISITS] += (unsigned long long)(depth + 1);
-        if (status == OZ_LEAF_TERMINAL) st[ST_TERMINAL] += 1;
-        if (err) atomicOr(t.error_flag, err);
+    return Descent{own, opp, legal, depth, status, tval, fs, err};
+}
+// (body shared by k_select and the free-running k_advance; returns the status it stored in leaf_status[g].  A descent that ends in an error
+// is stored like any other, with status OZ_LEAF_IDLE.)
+template <bool NOISE = false>
+__device__ __forceinline__ int select_body(const MctsDev& t, TreeLds& L, int g, int lane) {
+    if (!t.active[g]) {
+        if (lane == 0) t.leaf_status[g] = OZ_LEAF_IDLE;
+        return OZ_LEAF_IDLE;
     }
-    return status;
+    double eta = 0.0;
+    const bool noisy = noise_of_slot<NOISE>(t, g, lane, &eta);
+    const uint64_t own = uni64(t.root_own[g]), opp = uni64(t.root_opp[g]);
+    int rootn = unii(t.root_node[g]);
+    const Descent e = descend_one<NOISE>(t, L.rec, L.path, g, lane, own, opp, oz_legal(own, opp, t.valid), rootn, noisy, eta, InFlight{nullptr, nullptr, 0});
+    __syncthreads();
+    if (lane < e.depth) t.path[(size_t)g * OZ_MAX_DEPTH + lane] = L.path[lane];          // the frontier, one coalesced store
+    if (lane == 0) {
+        t.leaf_status[g] = e.status;
+        t.leaf_own[g] = e.own; t.leaf_opp[g] = e.opp; t.leaf_legal[g] = e.legal; t.leaf_fs[g] = e.fs;
+        t.depth[g] = e.depth; t.term_value[g] = e.tval;
+        unsigned long long* st = t.stat + (size_t)g * OZ_NSTAT;
+        st[ST_SIMS] += 1; st[ST_VISITS] += (unsigned long long)(e.depth + 1);
+        if (e.status == OZ_LEAF_TERMINAL) st[ST_TERMINAL] += 1;
+        if (e.err) atomicOr(t.error_flag, e.err);
+    }
+    return e.status;
 }
 __global__ __launch_bounds__(64) void k_select(MctsDev t) {
     __shared__ TreeLds L;
@@ -544,147 +576,19 @@ __device__ __forceinline__ void q_update(const MctsDev& t, OzEdge* e, double val
     e->n_tag = (uint32_t)(N + 1) | tag;
 }
 
+// one descent's end as the expand + backup sees it: the one-descent-per-step kernels fill it from the per-game arrays (leaf_*[g], depth[g], path[g]),
+// the leaf-parallel ones from the per-(game, j) arrays
+struct LeafRef {
+    int status;
+    uint64_t own, opp, legal;
+    int slot;                  // row of pi / v
+    int fs;                    // free table slot for the new node
+    int depth, tval;
+    const int2* path;          // [depth]
+};
 // backup (MCTS/__init__.py:68-71): the level-d caller sees the leaf value negated (depth-1-d) times; all levels in
 // parallel, one lane per level (a path never visits a node twice: every move adds a disc)
-__device__ __forceinline__ void backup_body(const MctsDev& t, int g, int lane, double value, int vt) {
-    const int depth = t.depth[g];
-    if (lane < depth) {
-        const int2 pe = t.path[(size_t)g * OZ_MAX_DEPTH + lane];
-        const double val = ((depth - 1 - lane) & 1) ? -value : value;
-        if ((unsigned)pe.x < (unsigned)t.node_cap && (unsigned)pe.y < (unsigned)t.row_cap) {
-            q_update(t, rec_edge(t, g, pe.x, pe.y), val, vt);
-            *rec_Ns(t, g, pe.x) += 1;
-        } else atomicOr(t.error_flag, EF_CORRUPT);
-    }
-    if (lane == 0) {
-        t.last_value[g] = (depth & 1) ? -value : value;
-        t.last_vtype[g] = vt;
-    }
-}
-
-// slot_is_game != 0: pi / v are indexed by game (host evaluator path); else by compacted slot.
-__device__ __forceinline__ void expand_backup_body(const MctsDev& t, TreeLds& L, int g, int lane, int slot_is_game) {
-    const int status = unii(t.leaf_status[g]);
-    if (status == OZ_LEAF_IDLE || status == OZ_LEAF_WAIT) return;           // (WAIT: the leaf was not in the batch, nothing to expand yet)
-    double value;
-    int vt;
-    if (status == OZ_LEAF_EVAL) {
-        // first visit (MCTS/__init__.py:44-57): P = pi * mask, normalised; uniform over legal if the sum is 0
-        const uint64_t own = uni64(t.leaf_own[g]), opp = uni64(t.leaf_opp[g]), legal = uni64(t.leaf_legal[g]);
-        const int slot = slot_is_game ? g : unii(t.leaf_slot[g]);
-        const int r = lane >> 3, c = lane & 7, n = t.n;
-        const bool inb = r < n && c < n, is_legal = (legal >> lane) & 1;
-        const int a = r * n + c;
-        double p = is_legal ? (double)t.pi[(size_t)slot * t.n2 + a] : 0.0;     // float32 * float64 mask
-        if (inb) L.arr[a] = p;
-        __syncthreads();
-        const double sum = pairwise_sum(L.arr, t.n2);
-        const int cnt = oz_popc(legal);
-        if (sum > 0) p = p / sum;
-        else p = is_legal ? 1.0 / (double)cnt : 0.0;                           // mask / np.sum(mask)
-        const int node = unii(t.node_count[g]), fs = unii(t.leaf_fs[g]), depth = unii(t.depth[g]);
-        const bool ok = node < t.node_cap && cnt <= t.row_cap && fs >= 0;
-        if (ok) {
-            // build the record in LDS (header + one edge per legal square, N = 0, Q = 0, child unknown), store it with one
-            // wave-wide 16-byte store, link it into the table and into the edge we came through
-            uint64_t* w = reinterpret_cast<uint64_t*>(L.rec);
-            if (lane == 0) { w[0] = own; w[1] = opp; w[2] = (uint64_t)(uint32_t)cnt << 32; w[3] = 0; }
-            if (is_legal) {
-                const int rank = oz_popc(legal & ((1ULL << lane) - 1ULL));
-                w[4 + 3 * rank] = 0xFFFFFFFF00000000ULL;                       // N|tag = 0, child = -1
-                w[5 + 3 * rank] = 0;                                           // Q = 0.0
-                w[6 + 3 * rank] = (uint64_t)__double_as_longlong(p);
-            }
-            if (lane == 63 && (cnt * 3) % 2) w[4 + 3 * cnt] = 0;               // the last 16-byte chunk is half used: no stale bytes
-            __syncthreads();
-            const int chunks = (OZ_REC_HDR + cnt * OZ_EDGE_BYTES + 15) >> 4;
-            if (lane < chunks) reinterpret_cast<uint4*>(rec_ptr(t, g, node))[lane] = L.rec[lane];
-            if (lane == 0) {
-                t.node_count[g] = node + 1;
-                t.ht[(size_t)g * t.ht_cap + fs] = ht_entry(own, opp, node);
-                if (depth > 0) {
-                    const int2 pe = t.path[(size_t)g * OZ_MAX_DEPTH + depth - 1];
-                    rec_edge(t, g, pe.x, pe.y)->child = node;
-                } else t.root_node[g] = node;
-            }
-        }
-        if (lane == 0) {
-            unsigned long long* st = t.stat + (size_t)g * OZ_NSTAT;
-            st[ST_EXPAND] += 1;
-            if (!(sum > 0)) st[ST_FALLBACK] += 1;
-            if (!ok) atomicOr(t.error_flag, node >= t.node_cap || fs < 0 ? EF_NODES : EF_EDGES);
-        }
-        value = -(double)t.v[slot];                                            // return -v (:57)
-        vt = t.qmode == OZ_QMODE_F64 ? VT_F64 : VT_F32;
-    } else {
-        value = (double)t.term_value[g];
-        vt = VT_INT;
-    }
-    backup_body(t, g, lane, value, vt);
-}
-__global__ __launch_bounds__(64) void k_expand_backup(MctsDev t, int slot_is_game) {
-    __shared__ TreeLds L;
-    expand_backup_body(t, L, blockIdx.x, threadIdx.x, slot_is_game);
-}
-// expand + backup of simulation s-1 and the descent of simulation s in ONE launch (same wave, same game): one kernel boundary
-// less per simulation step, and the records the backup has just written are re-read by the descent while still in the CU's cache
-__global__ __launch_bounds__(64) void k_backup_select(MctsDev t) {
-    __shared__ TreeLds L;
-    expand_backup_body(t, L, blockIdx.x, threadIdx.x, 0);
-    wave_sync();                                           // the wave's own stores (records, child indices, table entry, root index) before its loads
-    __syncthreads();
-    select_body(t, L, blockIdx.x, threadIdx.x);
-}
-__global__ __launch_bounds__(64) void k_backup_select_n(MctsDev t) {
-    __shared__ TreeLds L;
-    expand_backup_body(t, L, blockIdx.x, threadIdx.x, 0);
-    wave_sync();
-    __syncthreads();
-    select_body<true>(t, L, blockIdx.x, threadIdx.x);
-}
-
-
-// ---------------------------------------------------------------- leaf-parallel search: K leaves per game and step under virtual loss
-// (opt-in: oz_mcts_set_leaves_per_step; the kernels above stay the default and are what K = 1 runs.)  For ONE game and ONE step, with
-// `left` = simulations of the current simulate call still to run:
-//   1. for j = 0 .. min(K, left) - 1, one after the other, the game's wave descends from the root exactly as select_body does, except that
-//      at a node s at depth d the statistics are seen through the descents of this step already in flight: k(s, a) = the number of them
-//      whose level d is (s, a), k(s) = the number whose level d is at s (a state sits at one depth only, so level d is all there is to
-//      compare: <= K - 1 compares per level).  k(s, a) == 0: N' = N, Q' = Q, the stored bits.  Otherwise N' = N + k and
-//      Q' = ((double)N * Q - (double)k) / (double)(N + k) in float64 (every in-flight descent counts as one visit that returned -1 to the
-//      chooser; a view, nothing is stored and the Q type tag is not touched).  U = Q' + (c * P) * (sqrt((double)(Ns + k(s))) / (double)(1 + N')).
-//   2. a descent that ends on a finished board joins the in-flight set with its integer value; one that ends on a state not in the table
-//      joins it as a leaf -- unless an earlier leaf of this step is the same board (its child edge is still -1, the table does not know it:
-//      the boards are compared), then it is DISCARDED (no simulation, counted in the collision counter only) and the step closes for the game.
-//   3. all leaves of all games form one batch in (game, j) order (k_wide_compact); EVERY leaf is evaluated: no cross-game de-duplication
-//      and no evaluation cache here (results would be identical), so leaves_evaluated == expansions for K > 1.
-//   4. per game, j ascending: expand leaf j (the table is probed again for the free slot: two pending leaves of one step may have been
-//      shown the same one), back its value up along path j with q_update; a terminal descent in its place in that order.
-//   5. left -= the descents of the step.  A simulate call runs steps until every game has done exactly nsims simulations.
-// At K = 1 this is the search above (oz_mcts_use_wide_kernels runs it through these kernels: the reference's traces hold them bit for bit in
-// both Q regimes).  At K > 1 the float64 regime is held against a restatement (tests/wide_search_ref.py); OZ_QMODE_NEP50 has no replay of its
-// own at K > 1: the view above is float64 in both regimes and everything stored goes through the one q_update, so it holds by construction.
-struct WideDev {
-    int K;                                       // descents per game and step
-    int *status, *depth, *term_value, *slot;     // [G][OZ_MCTS_MAX_LEAVES_PER_STEP]
-    uint64_t *own, *opp, *legal;                 // [G][OZ_MCTS_MAX_LEAVES_PER_STEP]
-    int2* path;                                  // [G][OZ_MCTS_MAX_LEAVES_PER_STEP][OZ_MAX_DEPTH]
-    int* count;                                  // [G] descents in flight (between a wide descent and its expand + backup)
-    int* left;                                   // [G] simulations of the current simulate call still to run
-    int* max_left;                               // [1] the largest `left` (k_wide_left)
-    unsigned long long* stat;                    // [G][3] steps, descents discarded on a collision, leaves handed to the network
-};
-#define OZ_WK OZ_MCTS_MAX_LEAVES_PER_STEP
-struct WideLds {
-    TreeLds t;
-    int2 path[OZ_WK][OZ_MAX_DEPTH];              // the frontiers of the step's descents
-    uint64_t own[OZ_WK], opp[OZ_WK];             // where they ended
-    int depth[OZ_WK], status[OZ_WK];
-};
-
-// the expand + backup of ONE descent of a step, on the per-(game, j) arrays.  A restatement of backup_body / expand_backup_body above (kept as they
-// are, so that the K = 1 kernels compile to the code they always were); the arithmetic is the same line for line.
-__device__ __forceinline__ void wide_backup_one(const MctsDev& t, int g, int lane, int depth, const int2* __restrict__ path, double value, int vt) {
+__device__ __forceinline__ void backup_one(const MctsDev& t, int g, int lane, int depth, const int2* __restrict__ path, double value, int vt) {
     if (lane < depth) {
         const int2 pe = path[lane];
         const double val = ((depth - 1 - lane) & 1) ? -value : value;
@@ -698,16 +602,8 @@ __device__ __forceinline__ void wide_backup_one(const MctsDev& t, int g, int lan
         t.last_vtype[g] = vt;
     }
 }
-// one descent's end as the wide expand + backup sees it
-struct LeafRef {
-    int status;
-    uint64_t own, opp, legal;
-    int slot;                  // row of pi / v
-    int fs;                    // free table slot for the new node
-    int depth, tval;
-    const int2* path;          // [depth]
-};
-__device__ __forceinline__ void wide_expand_backup_one(const MctsDev& t, TreeLds& L, int g, int lane, const LeafRef& lf) {
+// expand the leaf if it needs it, then back its value up along its path
+__device__ __forceinline__ void expand_backup_one(const MctsDev& t, TreeLds& L, int g, int lane, const LeafRef& lf) {
     const int status = lf.status;
     if (status == OZ_LEAF_IDLE || status == OZ_LEAF_WAIT) return;           // (WAIT: the leaf was not in the batch, nothing to expand yet)
     double value;
@@ -764,8 +660,83 @@ __device__ __forceinline__ void wide_expand_backup_one(const MctsDev& t, TreeLds
         value = (double)lf.tval;
         vt = VT_INT;
     }
-    wide_backup_one(t, g, lane, lf.depth, lf.path, value, vt);
+    backup_one(t, g, lane, lf.depth, lf.path, value, vt);
 }
+// ... of the descent select_body stored in the per-game arrays.  slot_is_game != 0: pi / v are indexed by game (host evaluator path); else
+// by compacted slot.
+__device__ __forceinline__ void backup_body(const MctsDev& t, int g, int lane, double value, int vt) {
+    backup_one(t, g, lane, t.depth[g], t.path + (size_t)g * OZ_MAX_DEPTH, value, vt);
+}
+__device__ __forceinline__ void expand_backup_body(const MctsDev& t, TreeLds& L, int g, int lane, int slot_is_game) {
+    LeafRef lf;
+    lf.status = unii(t.leaf_status[g]);
+    lf.own = uni64(t.leaf_own[g]); lf.opp = uni64(t.leaf_opp[g]); lf.legal = uni64(t.leaf_legal[g]);
+    lf.slot = slot_is_game ? g : unii(t.leaf_slot[g]);
+    lf.fs = unii(t.leaf_fs[g]);
+    lf.depth = unii(t.depth[g]); lf.tval = unii(t.term_value[g]);
+    lf.path = t.path + (size_t)g * OZ_MAX_DEPTH;
+    expand_backup_one(t, L, g, lane, lf);
+}
+__global__ __launch_bounds__(64) void k_expand_backup(MctsDev t, int slot_is_game) {
+    __shared__ TreeLds L;
+    expand_backup_body(t, L, blockIdx.x, threadIdx.x, slot_is_game);
+}
+// expand + backup of simulation s-1 and the descent of simulation s in ONE launch (same wave, same game): one kernel boundary
+// less per simulation step, and the records the backup has just written are re-read by the descent while still in the CU's cache
+__global__ __launch_bounds__(64) void k_backup_select(MctsDev t) {
+    __shared__ TreeLds L;
+    expand_backup_body(t, L, blockIdx.x, threadIdx.x, 0);
+    wave_sync();                                           // the wave's own stores (records, child indices, table entry, root index) before its loads
+    __syncthreads();
+    select_body(t, L, blockIdx.x, threadIdx.x);
+}
+__global__ __launch_bounds__(64) void k_backup_select_n(MctsDev t) {
+    __shared__ TreeLds L;
+    expand_backup_body(t, L, blockIdx.x, threadIdx.x, 0);
+    wave_sync();
+    __syncthreads();
+    select_body<true>(t, L, blockIdx.x, threadIdx.x);
+}
+
+
+// ---------------------------------------------------------------- leaf-parallel search: K leaves per game and step under virtual loss
+// (opt-in: oz_mcts_set_leaves_per_step; the kernels above stay the default and are what K = 1 runs.  Both sets of kernels walk the tree with
+// the one descend_one and expand and back up with the one expand_backup_one: the k_wide_* bodies below add the loop over the step's descents
+// and the per-(game, j) arrays.)  For ONE game and ONE step, with `left` = simulations of the current simulate call still to run:
+//   1. for j = 0 .. min(K, left) - 1, one after the other, the game's wave descends from the root (descend_one), where
+//      at a node s at depth d the statistics are seen through the descents of this step already in flight: k(s, a) = the number of them
+//      whose level d is (s, a), k(s) = the number whose level d is at s (a state sits at one depth only, so level d is all there is to
+//      compare: <= K - 1 compares per level).  k(s, a) == 0: N' = N, Q' = Q, the stored bits.  Otherwise N' = N + k and
+//      Q' = ((double)N * Q - (double)k) / (double)(N + k) in float64 (every in-flight descent counts as one visit that returned -1 to the
+//      chooser; a view, nothing is stored and the Q type tag is not touched).  U = Q' + (c * P) * (sqrt((double)(Ns + k(s))) / (double)(1 + N')).
+//   2. a descent that ends on a finished board joins the in-flight set with its integer value; one that ends on a state not in the table
+//      joins it as a leaf -- unless an earlier leaf of this step is the same board (its child edge is still -1, the table does not know it:
+//      the boards are compared), then it is DISCARDED (no simulation, counted in the collision counter only) and the step closes for the game.
+//   3. all leaves of all games form one batch in (game, j) order (k_wide_compact); EVERY leaf is evaluated: no cross-game de-duplication
+//      and no evaluation cache here (results would be identical), so leaves_evaluated == expansions for K > 1.
+//   4. per game, j ascending: expand leaf j (the table is probed again for the free slot: two pending leaves of one step may have been
+//      shown the same one), back its value up along path j with q_update; a terminal descent in its place in that order.
+//   5. left -= the descents of the step.  A simulate call runs steps until every game has done exactly nsims simulations.
+// At K = 1 this is the search above (oz_mcts_use_wide_kernels runs it through these kernels: the reference's traces hold them bit for bit in
+// both Q regimes).  At K > 1 the float64 regime is held against a restatement (tests/wide_search_ref.py); OZ_QMODE_NEP50 has no replay of its
+// own at K > 1: the view above is float64 in both regimes and everything stored goes through the one q_update, so it holds by construction.
+struct WideDev {
+    int K;                                       // descents per game and step
+    int *status, *depth, *term_value, *slot;     // [G][OZ_MCTS_MAX_LEAVES_PER_STEP]
+    uint64_t *own, *opp, *legal;                 // [G][OZ_MCTS_MAX_LEAVES_PER_STEP]
+    int2* path;                                  // [G][OZ_MCTS_MAX_LEAVES_PER_STEP][OZ_MAX_DEPTH]
+    int* count;                                  // [G] descents in flight (between a wide descent and its expand + backup)
+    int* left;                                   // [G] simulations of the current simulate call still to run
+    int* max_left;                               // [1] the largest `left` (k_wide_left)
+    unsigned long long* stat;                    // [G][3] steps, descents discarded on a collision, leaves handed to the network
+};
+#define OZ_WK OZ_MCTS_MAX_LEAVES_PER_STEP
+struct WideLds {
+    TreeLds t;
+    int2 path[OZ_WK][OZ_MAX_DEPTH];              // the frontiers of the step's descents
+    uint64_t own[OZ_WK], opp[OZ_WK];             // where they ended
+    int depth[OZ_WK], status[OZ_WK];
+};
 
 template <bool NOISE = false>
 __device__ __forceinline__ void wide_select_body(const MctsDev& t, const WideDev& w, WideLds& L, int g, int lane) {
@@ -783,87 +754,21 @@ __device__ __forceinline__ void wide_select_body(const MctsDev& t, const WideDev
     int count = 0, coll = 0, leaves = 0, nterm = 0, visits = 0, err = 0;
     const size_t gb = (size_t)g * OZ_WK;
     for (int j = 0; j < nd; ++j) {
-        uint64_t own = rown, opp = ropp, legal = rlegal;
-        int depth = 0, status, tval = 0, fs = -1;
-        int node = rootn, pnode = -1, prank = 0;
-        for (;;) {
-            if (legal == 0 && oz_legal(opp, own, t.valid) == 0) {
-                tval = oz_popc(own) >= oz_popc(opp) ? -1 : 1;
-                status = OZ_LEAF_TERMINAL;
-                break;
-            }
-            if (node < 0) {
-                node = ht_find(t, g, own, opp, lane, &fs);
-                if (node < 0) { status = OZ_LEAF_EVAL; break; }
-                if (pnode < 0) rootn = node;
-                if (lane == 0) {
-                    if (pnode >= 0) rec_edge(t, g, pnode, prank)->child = node;
-                    else t.root_node[g] = node;
-                }
-            }
-            if (legal == 0) { err = EF_NOMOVE; status = OZ_LEAF_IDLE; break; }
-            if (depth >= OZ_MAX_DEPTH) { err = EF_DEPTH; status = OZ_LEAF_IDLE; break; }
-            if (node >= t.node_cap) { err = EF_CORRUPT; status = OZ_LEAF_IDLE; break; }
-            const int cnt = oz_popc(legal);
-            const int chunks = (OZ_REC_HDR + cnt * OZ_EDGE_BYTES + 15) >> 4;
-            __syncthreads();
-            if (lane < chunks) L.t.rec[lane] = reinterpret_cast<const uint4*>(rec_ptr(t, g, node))[lane];
-            __syncthreads();
-            const uint64_t* rw = reinterpret_cast<const uint64_t*>(L.t.rec);
-            const int Ns = unii((int)(uint32_t)rw[2]);
-            const bool is_legal = (legal >> lane) & 1;
-            const int rank = oz_popc(legal & ((1ULL << lane) - 1ULL));
-            // the in-flight descents of this step that stand on this node at this level, and those that took this lane's edge from it
-            int ks = 0, ke = 0;
-            for (int i = 0; i < j; ++i)
-                if (L.depth[i] > depth) {
-                    const int2 pe = L.path[i][depth];
-                    if (pe.x == node) { ++ks; ke += pe.y == rank ? 1 : 0; }
-                }
-            double U = -INFINITY;
-            int child = -1;
-            if (is_legal) {
-                const uint64_t w0 = rw[4 + 3 * rank];
-                int N = (int)((uint32_t)w0 & ~OZ_TAG_F32);
-                child = (int)(w0 >> 32);
-                double Q = __longlong_as_double((long long)rw[5 + 3 * rank]);
-                const double P = __longlong_as_double((long long)rw[6 + 3 * rank]);
-                if (ke) {                                                       // ke == 0 reads the stored bits: (N * Q) / N is not Q
-                    Q = ((double)N * Q - (double)ke) / (double)(N + ke);
-                    N += ke;
-                }
-                const double bound = sqrt((double)(Ns + ks)) / (double)(1 + N);
-                U = Q + (t.c * P) * bound;
-                if constexpr (NOISE) {
-                    if (noisy && depth == 0) U = Q + (t.c * ((1.0 - t.noise_eps) * P + t.noise_eps * eta)) * bound;
-                }
-            }
-            const double m = wave_max_f64(U);
-            const int best = oz_ctz(__ballot(is_legal && U == m));
-            const int brank = oz_popc(legal & ((1ULL << best) - 1ULL));
-            if (lane == 0) L.path[j][depth] = make_int2(node, brank);
-            ++depth;
-            pnode = node; prank = brank;
-            node = lane_get(child, best);
-            oz_apply(own, opp, best);
-            const uint64_t theirs = oz_legal(opp, own, t.valid);
-            if (theirs != 0) { uint64_t sw = own; own = opp; opp = sw; legal = theirs; }
-            else legal = oz_legal(own, opp, t.valid);
-        }
-        if (err) break;
-        if (status == OZ_LEAF_EVAL) {
+        const Descent e = descend_one<NOISE>(t, L.t.rec, L.path[j], g, lane, rown, ropp, rlegal, rootn, noisy, eta, InFlight{L.path, L.depth, j});
+        if (e.err) { err = e.err; break; }                                      // the step stops here for this game (nothing of this descent is stored)
+        if (e.status == OZ_LEAF_EVAL) {
             bool same = false;
-            for (int i = 0; i < j; ++i) same = same || (L.status[i] == OZ_LEAF_EVAL && L.own[i] == own && L.opp[i] == opp);
+            for (int i = 0; i < j; ++i) same = same || (L.status[i] == OZ_LEAF_EVAL && L.own[i] == e.own && L.opp[i] == e.opp);
             if (same) { coll = 1; break; }                                      // discarded: the step's collection closes for this game
             ++leaves;
         } else ++nterm;
         if (lane == 0) {
-            L.own[j] = own; L.opp[j] = opp; L.depth[j] = depth; L.status[j] = status;
-            w.status[gb + j] = status; w.own[gb + j] = own; w.opp[gb + j] = opp; w.legal[gb + j] = legal;
-            w.depth[gb + j] = depth; w.term_value[gb + j] = tval;
+            L.own[j] = e.own; L.opp[j] = e.opp; L.depth[j] = e.depth; L.status[j] = e.status;
+            w.status[gb + j] = e.status; w.own[gb + j] = e.own; w.opp[gb + j] = e.opp; w.legal[gb + j] = e.legal;
+            w.depth[gb + j] = e.depth; w.term_value[gb + j] = e.tval;
         }
         ++count;
-        visits += depth + 1;
+        visits += e.depth + 1;
         wave_sync();                                                            // lane 0's frontier / child-index stores before the next descent's loads
     }
     wave_sync();
@@ -901,7 +806,7 @@ __device__ __forceinline__ void wide_expand_backup_body(const MctsDev& t, const 
             if (ht_find(t, g, lf.own, lf.opp, lane, &fs) >= 0) fs = -1;          // (cannot be in the table: the step holds a board once)
             lf.fs = fs;
         }
-        wide_expand_backup_one(t, L.t, g, lane, lf);
+        expand_backup_one(t, L.t, g, lane, lf);
         wave_sync();                                                            // records, table entry, Q / N of this descent before the next one's loads
         __syncthreads();
     }
@@ -1147,23 +1052,11 @@ static int eval_batch_async(oz_mcts* m, oz_net* net, int max_count, bool timed) 
     return OZ_OK;
 }
 
-// one lock-step simulation for every active game, leaves evaluated by `net` (all on m->stream)
-static int mcts_step_async(oz_mcts* m, oz_net* net, bool time_eval) {
-    MctsDev& d = m->d;
-    hipStream_t s = m->stream;
-    const bool all = m->profile;
-    long long i = all ? m->timer.begin(TS_SELECT, s) : -1;
-    hipLaunchKernelGGL(m->noise_ever ? k_select_n : k_select, dim3(d.G), dim3(64), 0, s, d);
-    m->timer.end(i, s);
-    i = all ? m->timer.begin(TS_COMPACT, s) : -1;
-    hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, s, d);
-    m->timer.end(i, s);
-    if (int rc = eval_batch_async(m, net, d.G, time_eval || all)) return rc;
-    i = all ? m->timer.begin(TS_BACKUP, s) : -1;
-    hipLaunchKernelGGL(k_expand_backup, dim3(d.G), dim3(64), 0, s, d, 0);
-    m->timer.end(i, s);
-    OZ_HIP(hipGetLastError());
-    return OZ_OK;
+// `launch` on m->stream, between a pair of timing events of slot `slot` if `on`
+template <typename F> static void timed(oz_mcts* m, int slot, bool on, F&& launch) {
+    const long long i = on ? m->timer.begin(slot, m->stream) : -1;
+    launch();
+    m->timer.end(i, m->stream);
 }
 
 // ---- leaf-parallel search: host side
@@ -1226,20 +1119,16 @@ static int mcts_wide_steps(oz_mcts* m, oz_net* net, int nsims, int max_games, bo
         enqueued += steps;
         if (enqueued > (long long)nsims) { oz_set_error("leaf-parallel search: the simulation budget did not run out after %d steps (internal error)", nsims); return OZ_ERR_STATE; }
         for (int k = 0; k < steps; ++k) {
-            long long i = all ? m->timer.begin(TS_SELECT, s) : -1;
-            if (k == 0) hipLaunchKernelGGL(m->noise_ever ? k_wide_select_n : k_wide_select, dim3(d.G), dim3(64), 0, s, d, w);
-            else hipLaunchKernelGGL(m->noise_ever ? k_wide_backup_select_n : k_wide_backup_select, dim3(d.G), dim3(64), 0, s, d, w);
-            m->timer.end(i, s);
-            i = all ? m->timer.begin(TS_COMPACT, s) : -1;
-            hipLaunchKernelGGL(k_wide_compact, dim3(1), dim3(1024), 0, s, d, w);
-            m->timer.end(i, s);
-            i = (time_eval || all) ? m->timer.begin(TS_NN, s) : -1;
+            timed(m, TS_SELECT, all, [&] {
+                if (k == 0) hipLaunchKernelGGL(m->noise_ever ? k_wide_select_n : k_wide_select, dim3(d.G), dim3(64), 0, s, d, w);
+                else hipLaunchKernelGGL(m->noise_ever ? k_wide_backup_select_n : k_wide_backup_select, dim3(d.G), dim3(64), 0, s, d, w);
+            });
+            timed(m, TS_COMPACT, all, [&] { hipLaunchKernelGGL(k_wide_compact, dim3(1), dim3(1024), 0, s, d, w); });
+            const long long i = (time_eval || all) ? m->timer.begin(TS_NN, s) : -1;
             if (int rc = oz_net_forward_device(net, d.batch_own, d.batch_opp, d.batch_count, cap, d.pi, d.v, s)) { m->timer.cancel(i); return rc; }
             m->timer.end(i, s);
         }
-        const long long i = all ? m->timer.begin(TS_BACKUP, s) : -1;
-        hipLaunchKernelGGL(k_wide_expand_backup, dim3(d.G), dim3(64), 0, s, d, w);
-        m->timer.end(i, s);
+        timed(m, TS_BACKUP, all, [&] { hipLaunchKernelGGL(k_wide_expand_backup, dim3(d.G), dim3(64), 0, s, d, w); });
         OZ_HIP(hipGetLastError());
         int max_left = 0;
         OZ_HIP(hipMemsetAsync(w.max_left, 0, sizeof(int), s));
@@ -1257,43 +1146,28 @@ static int mcts_collect_eval_time(oz_mcts* m) {
     return OZ_OK;
 }
 
-// `nsims` lock-step simulations: descent | compaction | evaluator, then per further simulation the previous one's expand + backup
-// fused with the next descent (k_backup_select), and one closing expand + backup: nsims + 1 tree launches instead of 2 nsims
-// (results are identical to the unfused sequence, which a single step still uses).
-// mcts_step_k enqueues simulation k of such a sequence, mcts_steps_close the closing expand + backup: the arena interleaves the steps of
-// its two searches on two streams.  max_leaves = an upper bound of the leaves a batch can hold (<= G: the active games), the size the
-// evaluator's launches are made for.
-static int mcts_step_k(oz_mcts* m, oz_net* net, int k, int max_leaves, bool time_eval) {
+// `nsims` simulations for every active game (all on m->stream), leaves evaluated by `net`.  max_games = an upper bound of the active games (<= G):
+// the evaluator's launches are made for max_games x leaves_per_step leaves.  One descent per game and step: descent | compaction | evaluator,
+// then per further simulation the previous one's expand + backup fused with the next descent (k_backup_select), and one closing expand +
+// backup: nsims + 1 tree launches instead of 2 nsims (results are identical to the unfused sequence, which oz_mcts_select / oz_mcts_backup
+// still run).  nsims <= 0 launches nothing: the closing expand + backup would run over the leaf_status of an earlier call.
+static int mcts_steps_async(oz_mcts* m, oz_net* net, int nsims, int max_games, bool time_eval) {
+    if (m->wide()) return mcts_wide_steps(m, net, nsims, max_games, time_eval);
+    if (nsims <= 0) return OZ_OK;
     MctsDev& d = m->d;
     hipStream_t s = m->stream;
     const bool all = m->profile;
-    long long i = all ? m->timer.begin(TS_SELECT, s) : -1;
-    if (k == 0) hipLaunchKernelGGL(m->noise_ever ? k_select_n : k_select, dim3(d.G), dim3(64), 0, s, d);
-    else hipLaunchKernelGGL(m->noise_ever ? k_backup_select_n : k_backup_select, dim3(d.G), dim3(64), 0, s, d);
-    m->timer.end(i, s);
-    i = all ? m->timer.begin(TS_COMPACT, s) : -1;
-    hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, s, d);
-    m->timer.end(i, s);
-    return eval_batch_async(m, net, max_leaves, time_eval || all);
-}
-static int mcts_steps_close(oz_mcts* m) {
-    const bool all = m->profile;
-    const long long i = all ? m->timer.begin(TS_BACKUP, m->stream) : -1;
-    hipLaunchKernelGGL(k_expand_backup, dim3(m->d.G), dim3(64), 0, m->stream, m->d, 0);
-    m->timer.end(i, m->stream);
+    for (int k = 0; k < nsims; ++k) {
+        timed(m, TS_SELECT, all, [&] {
+            if (k == 0) hipLaunchKernelGGL(m->noise_ever ? k_select_n : k_select, dim3(d.G), dim3(64), 0, s, d);
+            else hipLaunchKernelGGL(m->noise_ever ? k_backup_select_n : k_backup_select, dim3(d.G), dim3(64), 0, s, d);
+        });
+        timed(m, TS_COMPACT, all, [&] { hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, s, d); });
+        if (int rc = eval_batch_async(m, net, max_games, time_eval || all)) return rc;
+    }
+    timed(m, TS_BACKUP, all, [&] { hipLaunchKernelGGL(k_expand_backup, dim3(d.G), dim3(64), 0, s, d, 0); });
     OZ_HIP(hipGetLastError());
     return OZ_OK;
-}
-static int mcts_steps_async(oz_mcts* m, oz_net* net, int nsims, bool time_eval) {
-    if (m->wide()) return mcts_wide_steps(m, net, nsims, m->d.G, time_eval);
-    if (nsims < 2) {
-        for (int i = 0; i < nsims; ++i)
-            if (int rc = mcts_step_async(m, net, time_eval)) return rc;
-        return OZ_OK;
-    }
-    for (int k = 0; k < nsims; ++k)
-        if (int rc = mcts_step_k(m, net, k, m->d.G, time_eval)) return rc;
-    return mcts_steps_close(m);
 }
 
 OZ_API int oz_mcts_create(oz_mcts** out, int n, int num_games, int node_cap, double c, int q_mode) {
@@ -1357,7 +1231,7 @@ OZ_API int oz_mcts_simulate(oz_mcts* m, oz_net* net, int nsims) {
     if (m->wide() && m->selected) { oz_set_error("oz_mcts_simulate: a host-evaluated step is pending (oz_mcts_select without oz_mcts_backup)"); return OZ_ERR_STATE; }
     std::lock_guard<std::mutex> lkn(net->mu);
     hipSetDevice(m->device);
-    if (int rc = mcts_steps_async(m, net, nsims, false)) return rc;
+    if (int rc = mcts_steps_async(m, net, nsims, m->d.G, false)) return rc;
     m->selected = false;
     return check_error_flag(m);
 }
@@ -2078,15 +1952,13 @@ static int selfplay_round_async(oz_selfplay* sp, int sims, int stagger_round) {
     oz_mcts* m = sp->m;
     const int G = sp->gm.G;
     hipStream_t s = m->stream;
-    long long ti = m->profile ? m->timer.begin(TS_MOVE, s) : -1;
-    if (stagger_round >= 0) hipLaunchKernelGGL(k_sp_roots_stagger, dim3((G + 255) / 256), dim3(256), 0, s, sp->gm, m->d, stagger_round, sp->stagger_period);
-    else hipLaunchKernelGGL(k_sp_roots, dim3((G + 255) / 256), dim3(256), 0, s, sp->gm, m->d, 0);
-    if (sp->noise_on) hipLaunchKernelGGL(k_root_noise, dim3(G), dim3(64), 0, s, m->d, sp->noise_alpha, sp->gm.seed, (const uint64_t*)sp->gm.game_id, (const int*)sp->gm.ply);
-    m->timer.end(ti, s);
-    if (int rc = mcts_steps_async(m, sp->net, sims, true)) return rc;
-    ti = m->profile ? m->timer.begin(TS_MOVE, s) : -1;
-    hipLaunchKernelGGL(k_sp_move, dim3(G), dim3(64), 0, s, sp->gm, m->d, 0);
-    m->timer.end(ti, s);
+    timed(m, TS_MOVE, m->profile, [&] {
+        if (stagger_round >= 0) hipLaunchKernelGGL(k_sp_roots_stagger, dim3((G + 255) / 256), dim3(256), 0, s, sp->gm, m->d, stagger_round, sp->stagger_period);
+        else hipLaunchKernelGGL(k_sp_roots, dim3((G + 255) / 256), dim3(256), 0, s, sp->gm, m->d, 0);
+        if (sp->noise_on) hipLaunchKernelGGL(k_root_noise, dim3(G), dim3(64), 0, s, m->d, sp->noise_alpha, sp->gm.seed, (const uint64_t*)sp->gm.game_id, (const int*)sp->gm.ply);
+    });
+    if (int rc = mcts_steps_async(m, sp->net, sims, G, true)) return rc;
+    timed(m, TS_MOVE, m->profile, [&] { hipLaunchKernelGGL(k_sp_move, dim3(G), dim3(64), 0, s, sp->gm, m->d, 0); });
     OZ_HIP(hipGetLastError());
     if (m->timer.backlog() > 4096) m->timer.drain();      // completed pairs only: never a host stall inside the enqueue loop
     return OZ_OK;
@@ -2202,33 +2074,27 @@ OZ_API int oz_selfplay_run_steps(oz_selfplay* sp, int steps) {
     for (int i = 0; i < steps; ++i) {
         const bool all = m->profile;
         hipStream_t s = m->stream;
-        long long ti = all ? m->timer.begin(TS_SELECT, s) : -1;
         // under a batch cap the leaves on offer exceed the slots anyway (waiting games re-offer theirs), so one descent per game and call is
         // enough to keep the batches full and the launch is as short as the lock-step one (measured: +1.2 % expansions/s, +3 % games/s over 2)
         const int adv_cap = (sp->batch_cap > 0 && sp->batch_cap < d.G ? 1 : OZ_ADVANCE_CAP);
         // (from the second batch of a call on, the previous batch's expand + backup rides in the same launch; one closing k_expand_backup per call)
-        if (m->noise_ever) {
-            const NoiseDraw nz{sp->noise_alpha, sp->gm.seed};
-            if (fuse && i > 0) hipLaunchKernelGGL(k_backup_advance_n, dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap, nz);
-            else hipLaunchKernelGGL(k_advance_n, dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap, nz);
-        } else if (fuse && i > 0) hipLaunchKernelGGL(k_backup_advance, dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap);
-        else hipLaunchKernelGGL(k_advance, dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap);
-        m->timer.end(ti, s);
-        ti = all ? m->timer.begin(TS_COMPACT, s) : -1;
+        timed(m, TS_SELECT, all, [&] {
+            if (m->noise_ever) {
+                const NoiseDraw nz{sp->noise_alpha, sp->gm.seed};
+                if (fuse && i > 0) hipLaunchKernelGGL(k_backup_advance_n, dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap, nz);
+                else hipLaunchKernelGGL(k_advance_n, dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap, nz);
+            } else if (fuse && i > 0) hipLaunchKernelGGL(k_backup_advance, dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap);
+            else hipLaunchKernelGGL(k_advance, dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap);
+        });
         MctsDev dc = d;                                    // this batch's cap and slot order (the kernels take the struct by value)
         const int cap = sp->batch_cap > 0 && sp->batch_cap < d.G ? sp->batch_cap : 0;
         dc.batch_cap = cap;
         dc.batch_rot = cap ? (int)((sp->batch_no * (long long)cap) % d.G) : 0;
         sp->batch_no += 1;
-        hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, s, dc);
-        m->timer.end(ti, s);
+        timed(m, TS_COMPACT, all, [&] { hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, s, dc); });
         // (the network's launches are sized for the cap: it picks its tile shapes from the batch it is asked to hold)
         if (int rc = eval_batch_async(m, sp->net, cap ? cap : d.G, true)) return rc;
-        if (!fuse || i == steps - 1) {
-            ti = all ? m->timer.begin(TS_BACKUP, s) : -1;
-            hipLaunchKernelGGL(k_expand_backup, dim3(d.G), dim3(64), 0, s, d, 0);
-            m->timer.end(ti, s);
-        }
+        if (!fuse || i == steps - 1) timed(m, TS_BACKUP, all, [&] { hipLaunchKernelGGL(k_expand_backup, dim3(d.G), dim3(64), 0, s, d, 0); });
         OZ_HIP(hipGetLastError());
         if (m->timer.backlog() > 4096) m->timer.drain();      // completed pairs only: never a host stall inside the enqueue loop
     }
@@ -2577,29 +2443,15 @@ OZ_API int oz_arena_run_rounds(oz_arena* a, int max_rounds_arg) {
         // the evaluator's launches are made for the movers of the round (an upper bound of the leaves a batch can hold), not for all G slots
         if (run_a) {
             std::lock_guard<std::mutex> la(a->na->mu);
-            if (ma->wide()) rc = mcts_wide_steps(ma, a->na, a->sims, movers[0], false);
-            else {
-                for (int k = 0; k < a->sims && !rc; ++k) rc = mcts_step_k(ma, a->na, k, movers[0], false);
-                if (!rc) rc = mcts_steps_close(ma);
-            }
+            rc = mcts_steps_async(ma, a->na, a->sims, movers[0], false);
         }
         if (!rc && run_b) {
             std::lock_guard<std::mutex> lb(a->nb->mu);
-            if (mb->wide()) rc = mcts_wide_steps(mb, a->nb, a->sims, movers[1], false);
-            else {
-                for (int k = 0; k < a->sims && !rc; ++k) rc = mcts_step_k(mb, a->nb, k, movers[1], false);
-                if (!rc) rc = mcts_steps_close(mb);
-            }
+            rc = mcts_steps_async(mb, a->nb, a->sims, movers[1], false);
         }
         if (rc) break;
-        {
-            const long long ta = (run_a && ma->profile) ? ma->timer.begin(TS_MOVE, s) : -1;
-            if (run_a) hipLaunchKernelGGL(k_sp_move, dim3(G), dim3(64), 0, s, sp->gm, ma->d, 1);
-            ma->timer.end(ta, s);
-            const long long tb = (run_b && mb->profile) ? mb->timer.begin(TS_MOVE, s) : -1;
-            if (run_b) hipLaunchKernelGGL(k_sp_move, dim3(G), dim3(64), 0, s, sp->gm, mb->d, 1);
-            mb->timer.end(tb, s);
-        }
+        if (run_a) timed(ma, TS_MOVE, ma->profile, [&] { hipLaunchKernelGGL(k_sp_move, dim3(G), dim3(64), 0, s, sp->gm, ma->d, 1); });
+        if (run_b) timed(mb, TS_MOVE, mb->profile, [&] { hipLaunchKernelGGL(k_sp_move, dim3(G), dim3(64), 0, s, sp->gm, mb->d, 1); });
         if (hipGetLastError() != hipSuccess) { oz_set_error("arena kernel launch failed"); rc = OZ_ERR_HIP; break; }
         if ((round & 3) == 3 || round + 1 == max_rounds) {
             if ((rc = check_error_flag(ma))) break;

@@ -52,9 +52,13 @@ class Search:
     def simulate(self, net, nsims):
         return self.lib.oz_mcts_simulate(self.h, net._h, int(nsims))
 
-    def dump(self, g):
+    def num_nodes(self):
         nn = np.zeros(self.G, np.int32)
         self.oz.check(self.lib.oz_mcts_num_nodes(self.h, self.oz.p_i32(nn)))
+        return nn
+
+    def dump(self, g):
+        nn = self.num_nodes()
         out = []
         for i in range(int(nn[g])):
             own, opp, legal, Ns = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_int32()
@@ -151,6 +155,35 @@ def test_wide_kernels_at_k1_vs_golden_traces(oz, golden_mcts):
         steps, coll, leaves = (m.wide_stats()[k] for k in ("steps", "collisions", "leaves"))
         assert (steps, coll) == (done, 0) and leaves == m.stats()["expansions"], name
     assert regimes == {0, 1}
+
+
+@pytest.mark.parametrize("wide", [False, True], ids=["narrow", "wide_at_1"])
+@pytest.mark.parametrize("qmode", [0, 1], ids=["nep50", "f64"])
+def test_simulate_call_sizes_compose_at_k1(oz, qmode, wide):
+    """simulate(0), (1), (1), (3) == simulate(5), bit for bit: one descent per step, so a call boundary changes nothing (the single-step, the
+    fused and the empty launch sequence).  Not so at K > 1, where a call boundary changes which descents are in flight together."""
+    from othellozero_amd.NNet import StubNetWrapper
+    n, G = 6, 4
+    roots = _golden_roots(n, G)
+    net = StubNetWrapper((n, n), 13, 0, max_batch=G)
+    a, b = Search(oz, n, G, qmode=qmode), Search(oz, n, G, qmode=qmode)
+    for s in (a, b):
+        oz.check(oz.load().oz_mcts_use_wide_kernels(s.h, 1 if wide else 0))
+        s.set_roots([r[0] for r in roots], [r[1] for r in roots])
+    nodes0, stats0 = a.num_nodes(), a.stats()
+    oz.check(a.simulate(net, 0))
+    assert np.array_equal(a.num_nodes(), nodes0) and a.stats() == stats0
+    for nsims in (1, 1, 3):
+        oz.check(a.simulate(net, nsims))
+    oz.check(b.simulate(net, 5))
+    assert np.array_equal(a.num_nodes(), b.num_nodes()) and int(b.num_nodes().min()) > 0
+    for gi in range(G):
+        for x, y in zip(a.dump(gi), b.dump(gi)):
+            assert (x["k0"], x["k1"], x["Ns"], x["legal"]) == (y["k0"], y["k1"], y["Ns"], y["legal"]), gi
+            for key in ("N", "Q", "qtag", "P"):
+                assert np.array_equal(x[key], y[key]), (gi, key)
+    assert a.stats() == b.stats() and a.stats()[0] == 5 * G
+    assert np.array_equal(a.counts(), b.counts())
 
 
 # ------------------------------------------------------------------ 2. K > 1 against the restatement
@@ -426,6 +459,21 @@ def test_refusals_leave_the_objects_usable(oz):
             raise AssertionError("not reached")
     with pytest.raises(ValueError):
         OthelloMCTS(n, HostNet(), 1.0, leaves_per_step=4)
+
+
+def test_capacity_overflow_through_the_wide_kernels(oz):
+    """the wide counterpart of test_gpu_parity.py's capacity error: a full node table ends the simulate call with the clean error code"""
+    from othellozero_amd.NNet import StubNetWrapper
+    lib = oz.load()
+    n, G, K = 6, 8, 4
+    roots = _golden_roots(n, G)
+    net = StubNetWrapper((n, n), 13, 0, max_batch=G * K)
+    s = Search(oz, n, G, node_cap=16)
+    oz.check(s.set_k(K))
+    s.set_roots([r[0] for r in roots], [r[1] for r in roots])
+    assert s.simulate(net, 40) == oz.OZ_ERR_CAPACITY and "node table" in lib.oz_last_error().decode()
+    h, s.h = s.h, C.c_void_p()
+    assert lib.oz_mcts_destroy(h) == oz.OZ_OK
 
 
 # ------------------------------------------------------------------ 8. the drop-in episode
