@@ -11,6 +11,18 @@
 
 int oz_current_device();
 
+// The dynamic-LDS limit of ONE kernel instantiation, set once per device (function attributes belong to the device the caller is on)
+template <auto Kernel> static int set_max_lds_once(int bytes) {
+    static bool attr_done[64] = {};
+    int dev_now = 0;
+    OZ_HIP(hipGetDevice(&dev_now));
+    if (!attr_done[dev_now & 63]) {
+        OZ_HIP(hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+        attr_done[dev_now & 63] = true;
+    }
+    return OZ_OK;
+}
+
 // HIP-event stopwatch with named slots, for timing launches on the stream they are launched on without a host sync:
 // begin / end record a pooled event pair around a launch sequence; collect() waits for every finished pair and folds it into
 // the per-slot totals, drain() folds only the pairs whose end event has ALREADY completed (hipEventQuery: no host stall --

@@ -383,18 +383,6 @@ __global__ __launch_bounds__(256) void k_splitk_reduce_f32(const float* __restri
 // padded to a multiple of the 8 XCDs (few row tiles: the blocks of one row tile go round the XCDs; otherwise the row tiles do).
 static inline int gemm_grid(int num_mt, int per_mt) { return num_mt < 8 ? ((per_mt + 7) / 8) * 8 * num_mt : ((num_mt + 7) / 8) * 8 * per_mt; }
 
-// The dynamic-LDS limit of ONE kernel instantiation, set once per device (function attributes belong to the device the caller is on)
-template <auto Kernel> static int set_max_lds_once(int bytes) {
-    static bool attr_done[64] = {};
-    int dev_now = 0;
-    OZ_HIP(hipGetDevice(&dev_now));
-    if (!attr_done[dev_now & 63]) {
-        OZ_HIP(hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-        attr_done[dev_now & 63] = true;
-    }
-    return OZ_OK;
-}
-
 // Finishes a split-K launch whose consumer reads fp32 rows: out[rows][N] = act(sum of the k-slices (fixed order) * scale + shift), rows = boards x P
 // (round 5, measured and removed: one output per thread with all 72 slices in flight -- 6.1 against 6.6 us: a kernel of this kind is
 //  launch + count + one round trip to the slabs + store ~ 5 us whatever the loop looks like; fewer launches is what is left)

@@ -137,11 +137,10 @@ __global__ void k_t_sum_partials(const float* __restrict__ partial, int S, long 
 // ---------------------------------------------------------------- column reductions over the rows of [M][C] matrices
 // MODE 0: sum x            MODE 1: sum (x - mean)^2
 // MODE 2: BN backward sums: dy = (a > 0 ? dA * post_scale : 0); s0 = sum dy, s1 = sum dy * xhat, xhat = (z - mean) * rstd
-// MODE 3: sum x with x stored in a zero-bordered buffer (rows (b, oy, ox) of an Hout^2 block at offset zoff in Hz^2)
 struct RedArgs {
     const float *x, *a, *z, *mean, *rstd;
     float post_scale;
-    int P, C, Hout, Hz, zoff;
+    int P, C;
 };
 // Streaming form: a thread owns 4 consecutive channels (16-byte loads), the lanes of a row cover up to 256 channels
 // (1 KB per wave instruction), the 256 threads of a block cover 4 rows (8 at 128 channels) per pass, rows strided RED_S
@@ -175,10 +174,6 @@ __global__ __launch_bounds__(256) void k_t_colreduce(RedArgs r, const int* __res
                 s0[k] += dy;
                 s1[k] = fmaf(dy, (zv[k] - mu[k]) * rs[k], s1[k]);
             }
-        }
-        if (MODE == 3) {
-            const int HH = r.Hout * r.Hout, b = (int)(m / HH), pix = (int)(m % HH);
-            s0 += *reinterpret_cast<const f32x4*>(r.x + (((size_t)b * r.Hz + pix / r.Hout + r.zoff) * r.Hz + pix % r.Hout + r.zoff) * r.C + c);
         }
     }
     __shared__ f32x4 sh[2][256];
@@ -215,11 +210,6 @@ __global__ void k_t_fin_var(const float* __restrict__ partial, const int* __rest
     mm_new[c] = mm[c] * mom + mean[c] * (1.0f - mom);
     mv_new[c] = mv[c] * mom + uv * (1.0f - mom);
 }
-// out[c] = sum over the rows (fixed order over the RED_S partials)
-__global__ void k_t_fin_colsum(const float* __restrict__ partial, int C, float* __restrict__ out) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c < C) out[c] = t_sum_s(partial, 0, C, c);
-}
 // a = relu((z - mean) * rstd * gamma + beta) [* keep / (1 - rate)]; 4 consecutive channels per thread
 __global__ __launch_bounds__(256) void k_t_bn_fwd(const float* __restrict__ z, const float* __restrict__ mean, const float* __restrict__ rstd,
                                                   const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ a,
@@ -241,40 +231,6 @@ __global__ __launch_bounds__(256) void k_t_bn_fwd(const float* __restrict__ z, c
     }
     *reinterpret_cast<f32x4*>(a + i) = out;
 }
-// dgamma = s1, dbeta = s0
-__global__ void k_t_fin_bnbwd(const float* __restrict__ partial, int C, float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ sums /*[2][C]*/) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= C) return;
-    const float s0 = t_sum_s(partial, 0, C, c), s1 = t_sum_s(partial, 1, C, c);
-    dbeta[c] = s0; dgamma[c] = s1; sums[c] = s0; sums[C + c] = s1;
-}
-// dz = gamma * rstd * (dy - s0/M - xhat * s1/M), written at (b, oy+zoff, ox+zoff) of an Hz x Hz buffer; 4 channels per thread
-__global__ __launch_bounds__(256) void k_t_bn_bwd(const float* __restrict__ dA, const float* __restrict__ a, const float* __restrict__ z,
-                                                  const float* __restrict__ mean, const float* __restrict__ rstd, const float* __restrict__ gamma,
-                                                  const float* __restrict__ sums, float post_scale, const int* __restrict__ d_count,
-                                                  int Hout, int C, int Hz, int zoff, float* __restrict__ dz) {
-    const int P = Hout * Hout;
-    const long long M = (long long)(*d_count) * P, total = M * C;
-    const long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-    if (i >= total) return;
-    const int c = (int)(i % C);
-    const long long m = i / C;
-    const f32x4 av = *reinterpret_cast<const f32x4*>(a + i), dv = *reinterpret_cast<const f32x4*>(dA + i), zv = *reinterpret_cast<const f32x4*>(z + i),
-                mu = *reinterpret_cast<const f32x4*>(mean + c), rs = *reinterpret_cast<const f32x4*>(rstd + c),
-                ga = *reinterpret_cast<const f32x4*>(gamma + c), s0 = *reinterpret_cast<const f32x4*>(sums + c),
-                s1 = *reinterpret_cast<const f32x4*>(sums + C + c);
-    const float inv = 1.0f / (float)M;
-    f32x4 g;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const float dy = av[k] > 0.f ? dv[k] * post_scale : 0.f;
-        const float xh = (zv[k] - mu[k]) * rs[k];
-        g[k] = ga[k] * rs[k] * (dy - s0[k] * inv - xh * s1[k] * inv);
-    }
-    const int b = (int)(m / P), pix = (int)(m % P);
-    *reinterpret_cast<f32x4*>(dz + (((size_t)b * Hz + pix / Hout + zoff) * Hz + pix % Hout + zoff) * C + c) = g;
-}
-
 // ---------------------------------------------------------------- heads: forward, losses, gradient wrt f2
 // one 64-thread block per sample (A = n*n <= 64 policy outputs, lane = action)
 // flat = 0 (OZ_POLICY_LOSS_ROWS): the reference's loss on the (n, n) view, every row renormalised and the rows averaged;
@@ -625,35 +581,65 @@ __device__ __forceinline__ int t_exp_for(unsigned max_bits, float target) {
     const int e = (int)floorf(log2f(target / mx));
     return e < -120 ? -120 : e > 120 ? 120 : e;
 }
-// Keras kernel W[9][Cin][Cout] fp32 -> a k_gemm_h2 weight operand in the h2 layout, k order k' = (slice * 9 + tap) * 32 + c32,
-// scaled by 2^kexp (kexp from the tensor's maximum), straight from the master weights (no fp32 intermediate):
+// The k order of a 3x3 weight operand of k_gemm_h2 / k_gemm_b3 is k' = (slice * 9 + tap) * 32 + c32: the group of 8 k' starting at kp lies in one tap,
+// at 8 consecutive channels from ch = slice * 32 + c32
+__device__ __forceinline__ void t_kp_tap_channel(int kp, int& tap, int& ch) {
+    const int tile = kp >> 5, slice = tile / 9;
+    tap = tile - slice * 9; ch = slice * 32 + (kp & 31);
+}
+// Data-gradient weight operand (both split formats): row n = ci, channel of k' = co, value W[8 - tap][ci][co] (the reversed, channel-swapped taps).
+// One thread per (row, group of 8 k'), the groups of a row adjacent: thread idx -> its row, its kp and its 8 values = 8 consecutive co (one 32-byte
+// read); false beyond the operand
+__device__ __forceinline__ bool t_wd_load8(const float* __restrict__ W, int Cin, int Cout, long long idx, int& nrow, int& kp, float* v) {
+    const int ng = 9 * Cout / 8;
+    if (idx >= (long long)Cin * ng) return false;
+    nrow = (int)(idx / ng); kp = (int)(idx % ng) * 8;
+    int tap, ch;
+    t_kp_tap_channel(kp, tap, ch);
+    const float* q = W + ((size_t)(8 - tap) * Cin + nrow) * Cout + ch;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = q[j];
+    return true;
+}
+// dz (zero-bordered [B][Hz][Hz][C] fp32, interior Hout^2 at offset zoff) -> the same geometry in a split format, one thread per (interior pixel, 8
+// channels): thread idx -> the pixel's row in the zero-bordered buffer and the group's first channel; false beyond the *d_count boards.  Only the
+// interior is written: the packed buffers are zeroed once at allocation, so their border stays zero.
+__device__ __forceinline__ bool t_dz_row8(long long idx, const int* __restrict__ d_count, int Hout, int Hz, int zoff, int C, size_t& row, int& c8) {
+    const int cg = C >> 3, P = Hout * Hout;
+    const long long m = idx / cg;
+    if (m >= (long long)(*d_count) * P) return false;
+    const int b = (int)(m / P), pix = (int)(m % P);
+    row = ((size_t)b * Hz + pix / Hout + zoff) * Hz + pix % Hout + zoff;
+    c8 = (int)(idx % cg) * 8;
+    return true;
+}
+// Keras kernel W[9][Cin][Cout] fp32 -> a k_gemm_h2 weight operand in the h2 layout, scaled by 2^kexp (kexp from the tensor's maximum), straight
+// from the master weights (no fp32 intermediate):
 //   DGRAD = 0  forward operand:       row n = co, channel of k' = ci:  W[tap][ci][co]        (threads adjacent in co: coalesced reads)
-//   DGRAD = 1  data-gradient operand: row n = ci, channel of k' = co:  W[8 - tap][ci][co]    (the reversed, channel-swapped taps;
-//              a thread's 8 values are 8 consecutive co = one 32-byte read)
+//   DGRAD = 1  data-gradient operand: t_wd_load8
 // scale_out[n] = 2^-kexp (forward only).  One thread per (row, group of 8 k').
 template <int DGRAD>
 __global__ __launch_bounds__(256) void k_t_w_to_h2(const float* __restrict__ W, int Cin, int Cout, const unsigned* __restrict__ wmax,
                                                    uint4* __restrict__ out, float* __restrict__ scale_out, int* __restrict__ flag) {
-    const int N = DGRAD ? Cin : Cout, Cch = DGRAD ? Cout : Cin, ng = 9 * Cch / 8;
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    int nrow, grp;
-    if (DGRAD) { grp = (int)(idx % ng); nrow = (int)(idx / ng); }
-    else { nrow = (int)(idx % N); grp = (int)(idx / N); }
-    if (idx >= (long long)N * ng) return;
     const int kexp = t_exp_for(*wmax, T_W_TARGET);
     if (idx == 0 && t_bad_max(*wmax)) atomicOr(flag, 2);
-    const int kp = grp * 8, tile = kp >> 5, c32 = kp & 31, slice = tile / 9, tap = tile - slice * 9, ch = slice * 32 + c32;
+    int nrow, kp;
     float v[8];
     if (DGRAD) {
-        const float* q = W + ((size_t)(8 - tap) * Cin + nrow) * Cout + ch;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = ldexpf(q[j], kexp);
+        if (!t_wd_load8(W, Cin, Cout, idx, nrow, kp, v)) return;
     } else {
+        if (idx >= (long long)Cout * (9 * Cin / 8)) return;
+        nrow = (int)(idx % Cout); kp = (int)(idx / Cout) * 8;
+        int tap, ch;
+        t_kp_tap_channel(kp, tap, ch);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = ldexpf(W[((size_t)tap * Cin + ch + j) * Cout + nrow], kexp);
+        for (int j = 0; j < 8; ++j) v[j] = W[((size_t)tap * Cin + ch + j) * Cout + nrow];
     }
-    h2_store8(out, nrow, ng * 8, kp, v);
-    if (!DGRAD && grp == 0) scale_out[nrow] = ldexpf(1.0f, -kexp);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = ldexpf(v[j], kexp);
+    h2_store8(out, nrow, 9 * (DGRAD ? Cout : Cin), kp, v);
+    if (!DGRAD && kp == 0) scale_out[nrow] = ldexpf(1.0f, -kexp);
 }
 // activation rows [M][C] fp32 -> h2 layout (the next layer's A operand)
 __global__ __launch_bounds__(256) void k_t_act_to_h2(const float* __restrict__ a, const int* __restrict__ d_count, int P, int C,
@@ -670,51 +656,70 @@ __global__ __launch_bounds__(256) void k_t_act_to_h2(const float* __restrict__ a
     h2_store8(out, m, C, g8 * 8, v);
     if (over) atomicOr(flag, 1);
 }
-// dz (zero-bordered [B][Hz][Hz][C] fp32, interior Hout^2 at offset zoff) -> the same geometry in the h2 layout, scaled by 2^ez with ez
-// from the tensor's maximum (dzmax, left by the BN backward); dscale[c] = 2^-(ez + kexp of the data-gradient weights)
+// dz -> the h2 layout (t_dz_row8), scaled by 2^ez with ez from the tensor's maximum (dzmax, left by the BN backward);
+// dscale[c] = 2^-(ez + kexp of the data-gradient weights)
 __global__ __launch_bounds__(256) void k_t_dz_to_h2(const float* __restrict__ dz, const int* __restrict__ d_count, int Hout, int Hz, int zoff, int C,
                                                     const unsigned* __restrict__ dzmax, const unsigned* __restrict__ wmax,
                                                     uint4* __restrict__ out, float* __restrict__ dscale, int ncols, int* __restrict__ flag) {
-    const int cg = C >> 3, P = Hout * Hout;
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x, m = idx / cg;
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const int ez = t_exp_for(*dzmax, T_DZ_TARGET);
     if (idx == 0 && (t_bad_max(*dzmax) || t_bad_max(*wmax))) atomicOr(flag, 2);
     if (idx < ncols) dscale[idx] = ldexpf(1.0f, -(ez + t_exp_for(*wmax, T_W_TARGET)));
-    if (m >= (long long)(*d_count) * P) return;
-    const int g8 = (int)(idx % cg), b = (int)(m / P), pix = (int)(m % P);
-    const size_t row = ((size_t)b * Hz + pix / Hout + zoff) * Hz + pix % Hout + zoff;
-    const float* q = dz + row * C + g8 * 8;
+    size_t row;
+    int c8;
+    if (!t_dz_row8(idx, d_count, Hout, Hz, zoff, C, row, c8)) return;
+    const float* q = dz + row * C + c8;
     float v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = ldexpf(q[j], ez);
-    h2_store8(out, row, C, g8 * 8, v);
+    h2_store8(out, row, C, c8, v);
 }
 
-// ---------------------------------------------------------------- f16x2 weight gradient of the 3x3 layers (round 3)
+// ---------------------------------------------------------------- bf16x3 mode of the 3x3 layers (oz_trainer_set_precision 2)
+// Every fp32 operand travels EXACTLY as three bf16 planes (oz_net_b3.h: b3_split, the b3 layout, six products per fp32 product in the order
+// a3 b1 + a1 b3 + a2 b2 + a2 b1 + a1 b2 + a1 b1, fp32 accumulation).  bf16 has fp32's exponent range: no scaling, no maxima, no range flag.
+// Forward and data gradient of conv2..conv4 run on k_gemm_b3 (oz_gemm_b3_launch), their weight gradients on k_wgrad_b3 below; conv1, the
+// dense layers, the heads, BN and Adam stay exact fp32.  The operands are converted per step from the fp32 masters / tensors.
+// Fallback rule: none.  Every trainer capacity (Bmax) takes these kernels: the GEMMs split their k loop until the grid fills the chip (keyed on
+// Bmax), the weight gradient splits its board range; at the reference's batch of 32 both already beat the exact-fp32 kernels they replace.
+//
+// The forward weight operand is k_w_to_b3's (oz_w_to_b3_launch, taps = 9); the data-gradient operand is t_wd_load8's, unscaled.
+__global__ __launch_bounds__(256) void k_t_w_to_b3(const float* __restrict__ W, int Cin, int Cout, uint4* __restrict__ out) {
+    int nrow, kp;
+    float v[8];
+    if (!t_wd_load8(W, Cin, Cout, (long long)blockIdx.x * blockDim.x + threadIdx.x, nrow, kp, v)) return;
+    b3_store8(out, nrow, 9 * Cout, kp, v);
+}
+// dz -> the b3 layout (t_dz_row8), unscaled
+__global__ __launch_bounds__(256) void k_t_dz_to_b3(const float* __restrict__ dz, const int* __restrict__ d_count, int Hout, int Hz, int zoff, int C,
+                                                    uint4* __restrict__ out) {
+    size_t row;
+    int c8;
+    if (!t_dz_row8((long long)blockIdx.x * blockDim.x + threadIdx.x, d_count, Hout, Hz, zoff, C, row, c8)) return;
+    const f32x4 lo = *reinterpret_cast<const f32x4*>(dz + row * C + c8), hi = *reinterpret_cast<const f32x4*>(dz + row * C + c8 + 4);
+    const float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    b3_store8(out, row, C, c8, v);
+}
+
+// ---------------------------------------------------------------- weight gradient of the 3x3 layers on the fp16 / bf16 matrix cores (f16x2: round 3, bf16x3: round 7)
 // dW[tap][ci][co] = sum over boards b and output pixels p of X[b][p + tap][ci] * dZ[b][p][co]: the contraction runs over (board, pixel),
-// the WRONG major for the fp16 operand map (v_mfma_f32_16x16x32_f16 wants, per lane, 8 consecutive k of one row / column; the tensors are
+// the WRONG major for the 16-bit operand map (v_mfma_f32_16x16x32_{f16,bf16} wants, per lane, 8 consecutive k of one row / column; the tensors are
 // stored pixel-major with the channels contiguous).  The k-groups of 8 are therefore 8 BOARDS at one pixel: a tap shift changes the pixel,
 // never the alignment of a k-group, and the four k-groups of one MFMA are four neighbouring output pixels.  Both tensors are first written
-// as "octet images" -- [octet of 8 boards][row][pixel slot][plane h1 | h2][channel][8 boards] fp16, 16 bytes per (pixel, plane, channel) --
-// by two bandwidth-bound kernels (X with its zero border for 'same' layers and zero columns up to WH_XW; dZ scaled into the fp16 range by the
-// power of two the data gradient uses, zero columns up to WH_ZW: a row of either is two whole k-quads for every layer), so the GEMM kernel
+// as "octet images" -- [octet of 8 boards][row][pixel slot][plane][channel][8 boards] 16-bit, 16 bytes per (pixel, plane, channel) --
+// by two bandwidth-bound kernels (X with its zero border for 'same' layers and zero columns up to WH_XW; dZ with zero columns up to WH_ZW, in f16x2
+// scaled into the fp16 range by the power of two the data gradient uses: a row of either is two whole k-quads for every layer), so the GEMM kernel
 // stages with LDS-DMA only: no transposes, no staging registers.
-// k_wgrad_h2: a block owns a 64 (ci) x 128 (co) tile for ALL NINE taps (9 x 4 accumulator tiles of 16 x 16 per wave, 8 waves = 4 x 16 ci by
-// 2 x 64 co).  Per octet it walks the output rows: three X rows (a ring of four 20 KB row slots: the row of the next step streams in during
-// the MFMAs of this one) and one dZ row (two 32 KB buffers) are resident; every tap reads the SAME staged rows at a shifted pixel slot, and
-// the dZ fragments of a pixel quad are read once for all nine taps: 26 ds_read_b128 per 108 MFMAs per wave.  fp32 accumulation, three
-// fp16 products per fp32 product (x2*z1 + x1*z2 + x1*z1), 2^-ez folded into the epilogue.  Octet ranges split over blockIdx.y until every CU
-// has a block (raw slabs + k_t_sum_partials, fixed order).  Rows of fewer than 8 real pixels (conv3: 6, conv4: 4) pay for the zero columns
-// (+24 % MFMA work over the three layers) -- the price of one uniform step shape.
-#define WH_MIN_BATCH 32     // batches from here on take this kernel (round 6: was 128; at the reference's batch of 32 the fp32 weight gradients on the second stream -- 52 + 82 +
+// wgrad_oct_body: a block of 8 waves owns a CI x CO tile for ALL NINE taps (9 x NJ accumulator tiles of 16 x 16 per wave).  Per octet it walks the
+// output rows: three X rows (a ring of four row slots: the row of the next step streams in during the MFMAs of this one) and one dZ row (two
+// buffers) are resident; every tap reads the SAME staged rows at a shifted pixel slot, and the dZ fragments of a pixel quad are read once for all
+// nine taps.  fp32 accumulation.  Octet ranges split over blockIdx.y until every CU has a block (raw slabs + k_t_sum_partials, fixed order).  Rows
+// of fewer than 8 real pixels (conv3: 6, conv4: 4) pay for the zero columns (+24 % MFMA work over the three layers) -- the price of one uniform
+// step shape.  What differs between the two precisions is in WgradH2 / WgradB3 below.
+#define WH_MIN_BATCH 32     // f16x2: batches from here on take k_wgrad_h2 (round 6: was 128; at the reference's batch of 32 the fp32 weight gradients on the second stream -- 52 + 82 +
                             // 151 us -- WERE the critical path of the backward pass)
-#define WH_CI 64
-#define WH_CO 128
 #define WH_XW 10           // pixel slots of an X row (columns >= Hin + 2 pad hold zeros)
 #define WH_ZW 8            // pixel slots of a dZ row (columns >= Hout hold zeros)
-#define WH_XROW (2 * WH_XW * WH_CI * 16)        // bytes of one staged X row: [plane][slot][ci] x 16 B = 20 KB
-#define WH_ZROW (2 * WH_ZW * WH_CO * 16)        // bytes of one staged dZ row: [plane][slot][co] x 16 B = 32 KB
-#define WH_LDS (4 * WH_XROW + 2 * WH_ZROW)      // 144 KB
 // Octet images, PLANES = 2 (f16x2: h1 | h2 in fp16, dZ scaled) or 3 (bf16x3: the three bf16 planes, unscaled); a 16-byte entry holds one
 // (pixel, plane, channel) of 8 boards, split by oz_split8_store.
 // X octet image of a[l - 1] ([B][Hin][Hin][C] fp32): out[octet][row < Hin + 2 pad][slot < WH_XW][plane][C] x 16 B (zero border, zero columns,
@@ -778,226 +783,144 @@ __global__ __launch_bounds__(256) void k_t_z_octets(const float* __restrict__ dz
     t_store_octet4<PLANES>(out + (size_t)cell * PLANES * C + ch, C, v);
 }
 struct WhGeom { int XR, Hout, Cin, Cout; };
+// What a precision brings to wgrad_oct_body: PLANES per value, the block's CI x CO tile as 8 waves = (CI / 16) x WN with NJ 16-wide co tiles per
+// wave, the fragment type, and mac() = the MFMA products of one fp32 product IN ACCUMULATION ORDER (small terms first; the order is the bits).
+// k_wgrad_h2: 64 ci x 128 co, 8 waves = 4 x 16 ci by 2 x 64 co; X row 20 KB, dZ row 32 KB, 144 KB of LDS; 26 ds_read_b128 per 108 MFMAs per wave;
+// three fp16 products per fp32 product (x2 z1 + x1 z2 + x1 z1), 2^-ez of the scaled dZ folded into the epilogue.
+struct WgradH2 {
+    typedef f16x8 Frag;
+    static constexpr int PLANES = 2, CI = 64, CO = 128, NJ = 4, WN = 2;
+    static constexpr bool SCALED = true;
+    static __device__ __forceinline__ f32x4 mac(const Frag* x, const Frag (*z)[NJ], int j, f32x4 acc) {
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(x[1], z[0][j], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(x[0], z[1][j], acc, 0, 0, 0);
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(x[0], z[0][j], acc, 0, 0, 0);
+    }
+};
+// k_wgrad_b3: six bf16 products per fp32 product (x3 z1, x1 z3, x2 z2, x2 z1, x1 z2, x1 z1), unscaled.
+// LDS plan: with three planes k_wgrad_h2's 64 ci x 128 co tile would need 4 X rows of 30 KB + 2 dZ rows of 48 KB = 216 KB, more than a CU's
+// 160 KB.  This kernel uses 32 ci x 128 co: 4 x 15 KB + 2 x 48 KB = 156 KB (one block per CU), which keeps the ring's one-row prefetch; a
+// 64 x 64 tile would fit only with a 3-row X ring (138 KB), which cannot stream the next row in beside the MFMAs of the current one, and was not built.
+// 8 waves = 2 (16 ci) x 4 (32 co); per pixel quad a wave reads 6 dZ + 27 X fragments (ds_read_b128) for 108 MFMAs.
+// Measured in the training step (8x8, 512 filters, rocprofv3): 56 us per layer at batch 32, 406 us at batch 256 -- bound by the operand stream
+// (every dZ row is staged by C / 32 blocks), not the matrix pipe (profiles/r7_train_b{32,256}_bf16x3_kernel_stats.csv, docs/HISTORY.md round 7).
+struct WgradB3 {
+    typedef bf16x8 Frag;
+    static constexpr int PLANES = 3, CI = 32, CO = 128, NJ = 2, WN = 4;
+    static constexpr bool SCALED = false;
+    static __device__ __forceinline__ f32x4 mac(const Frag* x, const Frag (*z)[NJ], int j, f32x4 acc) {
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x[2], z[0][j], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x[0], z[2][j], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x[1], z[1][j], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x[1], z[0][j], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x[0], z[1][j], acc, 0, 0, 0);
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(x[0], z[0][j], acc, 0, 0, 0);
+    }
+};
+template <typename T> struct WgradLds {
+    static constexpr int XROW = T::PLANES * WH_XW * T::CI * 16;      // bytes of one staged X row: [plane][slot][ci] x 16 B
+    static constexpr int ZROW = T::PLANES * WH_ZW * T::CO * 16;      // bytes of one staged dZ row: [plane][slot][co] x 16 B
+    static constexpr int BYTES = 4 * XROW + 2 * ZROW;
+    static_assert(T::CI * T::WN == 128 && T::CO == T::WN * T::NJ * 16 && T::CO == 128 && 64 % T::CI == 0, "8 waves of 16 ci x NJ x 16 co; a dZ row in halves of 64 co");
+    static_assert(BYTES <= 160 * 1024, "a CU's LDS");
+};
+template <typename T>
+__device__ __forceinline__ void wgrad_oct_body(unsigned char* const lds, const uint4* __restrict__ Xt, const uint4* __restrict__ Zt, const int* __restrict__ d_count,
+                                               WhGeom g, const unsigned* __restrict__ dzmax, float* __restrict__ dW, int msplit, float* __restrict__ partial,
+                                               long long slab) {
+    typedef typename T::Frag Frag;
+    constexpr int PLANES = T::PLANES, CI = T::CI, CO = T::CO, NJ = T::NJ, XROW = WgradLds<T>::XROW, ZROW = WgradLds<T>::ZROW;
+    unsigned char* const Xring = lds;
+    unsigned char* const Zbuf = lds + 4 * XROW;
+    const int nco = g.Cout / CO;
+    const int ci0 = (blockIdx.x / nco) * CI, co0 = (blockIdx.x % nco) * CO;
+    const int noct = (*d_count + 7) >> 3;
+    const int per = (noct + msplit - 1) / msplit, o0 = blockIdx.y * per, o1 = o0 + per < noct ? o0 + per : noct;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int wm = wave / T::WN, wn = wave % T::WN, r16 = lane & 15, g4 = lane >> 4;
+
+    // LDS-DMA: one instruction = 64 consecutive 16-byte entries, and a staged row is its instructions in order (instruction q lands at q x 1 KB).
+    // X row: the (plane, slot) pairs in plane-major order, 64 / CI of them per instruction (WH_XW is a multiple of that: both in one plane), lanes =
+    // pairs x the CI channels of the tile -- 20 instructions at 64 ci, 15 at 32 ci.  dZ row: (plane, slot, half) with lanes = 64 of the tile's 128
+    // co -- 32 / 48 instructions.  Wave w issues q = w, w + 8, ...
+    auto dma_x = [&](int oct, int row, int slot) {
+        constexpr int PER = 64 / CI;
+        const uint4* src = Xt + (((size_t)oct * g.XR + row) * WH_XW) * PLANES * g.Cin + ci0 + (lane & (CI - 1));
+        for (int q = wave; q < PLANES * WH_XW / PER; q += 8) {
+            const int pc = PER * q + lane / CI, p = pc / WH_XW, c = pc - p * WH_XW;
+            __builtin_amdgcn_global_load_lds((oz_gptr)(src + ((size_t)c * PLANES + p) * g.Cin), (oz_lptr)(Xring + slot * XROW + q * 1024), 16, 0, 0);
+        }
+    };
+    auto dma_z = [&](int oct, int row, int buf) {
+        const uint4* src = Zt + (((size_t)oct * g.Hout + row) * WH_ZW) * PLANES * g.Cout + co0 + lane;
+        for (int q = wave; q < PLANES * WH_ZW * 2; q += 8) {
+            const int h = q & 1, pc = q >> 1, p = pc / WH_ZW, c = pc - p * WH_ZW;
+            __builtin_amdgcn_global_load_lds((oz_gptr)(src + ((size_t)c * PLANES + p) * g.Cout + h * 64), (oz_lptr)(Zbuf + buf * ZROW + q * 1024), 16, 0, 0);
+        }
+    };
+
+    f32x4 acc[9][NJ];
+#pragma unroll
+    for (int t = 0; t < 9; ++t)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) acc[t][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    for (int oct = o0; oct < o1; ++oct) {
+        // the three X rows and the dZ row of output row 0 (the previous octet's last step ended with a barrier: every slot is free)
+        dma_x(oct, 0, 0); dma_x(oct, 1, 1); dma_x(oct, 2, 2); dma_z(oct, 0, 0);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        for (int oy = 0; oy < g.Hout; ++oy) {
+            if (oy + 1 < g.Hout) { dma_x(oct, oy + 3, (oy + 3) & 3); dma_z(oct, oy + 1, (oy + 1) & 1); }     // slots last read in step oy - 1
+            const unsigned char* Zr = Zbuf + (oy & 1) * ZROW + (wn * NJ * 16 + r16) * 16;
+#pragma unroll
+            for (int quad = 0; quad < 2; ++quad) {
+                const int px = quad * 4 + g4;
+                Frag z[PLANES][NJ];
+#pragma unroll
+                for (int p = 0; p < PLANES; ++p)
+#pragma unroll
+                    for (int j = 0; j < NJ; ++j) z[p][j] = *reinterpret_cast<const Frag*>(Zr + ((p * WH_ZW + px) * CO + j * 16) * 16);
+#pragma unroll
+                for (int t = 0; t < 9; ++t) {
+                    const int dy = t / 3, dx = t - 3 * dy;
+                    const unsigned char* Xr = Xring + ((oy + dy) & 3) * XROW + (wm * 16 + r16) * 16;
+                    Frag x[PLANES];
+#pragma unroll
+                    for (int p = 0; p < PLANES; ++p) x[p] = *reinterpret_cast<const Frag*>(Xr + ((p * WH_XW + px + dx) * CI) * 16);
+#pragma unroll
+                    for (int j = 0; j < NJ; ++j) acc[t][j] = T::mac(x, z, j, acc[t][j]);
+                }
+            }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the next step's rows have landed (this wave's pieces) ...
+            __syncthreads();                                       // ... everybody's, and everybody is done reading this step's
+        }
+    }
+    // C/D layout of the 16 x 16 MFMA: col = lane & 15 (co), row = (lane >> 4) * 4 + reg (ci).  The scale is read HERE: read at the top it lives
+    // through the main loop in registers the accumulators need
+    float sc = 1.0f;
+    if constexpr (T::SCALED) sc = ldexpf(1.0f, -t_exp_for(*dzmax, T_DZ_TARGET));
+    float* __restrict__ outp = msplit > 1 ? partial + (size_t)blockIdx.y * slab : dW;
+#pragma unroll
+    for (int t = 0; t < 9; ++t)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int ci = ci0 + wm * 16 + g4 * 4 + r, co = co0 + (wn * NJ + j) * 16 + r16;
+                outp[((size_t)t * g.Cin + ci) * g.Cout + co] = T::SCALED ? acc[t][j][r] * sc : acc[t][j][r];
+            }
+}
 __global__ __launch_bounds__(512, 2) void k_wgrad_h2(const uint4* __restrict__ Xt, const uint4* __restrict__ Zt, const int* __restrict__ d_count, WhGeom g,
                                                      const unsigned* __restrict__ dzmax, float* __restrict__ dW, int msplit, float* __restrict__ partial,
                                                      long long slab) {
     extern __shared__ __attribute__((aligned(16))) unsigned char wh_lds[];
-    unsigned char* const Xring = wh_lds;
-    unsigned char* const Zbuf = wh_lds + 4 * WH_XROW;
-    const int nco = g.Cout / WH_CO;
-    const int ci0 = (blockIdx.x / nco) * WH_CI, co0 = (blockIdx.x % nco) * WH_CO;
-    const int noct = (*d_count + 7) >> 3;
-    const int per = (noct + msplit - 1) / msplit, o0 = blockIdx.y * per, o1 = o0 + per < noct ? o0 + per : noct;
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int wm = wave >> 1, wn = wave & 1, r16 = lane & 15, g4 = lane >> 4;
-
-    // LDS-DMA: one instruction = 64 consecutive 16-byte entries.  X row = 20 instructions q = (plane, slot): lanes = the 64 ci of the tile;
-    // dZ row = 32 instructions q = (plane, slot, half): lanes = 64 of the tile's 128 co.  Wave w issues q = w, w + 8, ...
-    auto dma_x = [&](int oct, int row, int slot) {
-        const uint4* src = Xt + (((size_t)oct * g.XR + row) * WH_XW) * 2 * g.Cin + ci0 + lane;
-        for (int q = wave; q < 2 * WH_XW; q += 8) {
-            const int p = q / WH_XW, c = q - p * WH_XW;
-            __builtin_amdgcn_global_load_lds((oz_gptr)(src + ((size_t)c * 2 + p) * g.Cin), (oz_lptr)(Xring + slot * WH_XROW + q * 1024), 16, 0, 0);
-        }
-    };
-    auto dma_z = [&](int oct, int row, int buf) {
-        const uint4* src = Zt + (((size_t)oct * g.Hout + row) * WH_ZW) * 2 * g.Cout + co0 + lane;
-        for (int q = wave; q < 4 * WH_ZW; q += 8) {
-            const int h = q & 1, c = (q >> 1) % WH_ZW, p = q / (2 * WH_ZW);
-            __builtin_amdgcn_global_load_lds((oz_gptr)(src + ((size_t)c * 2 + p) * g.Cout + h * 64), (oz_lptr)(Zbuf + buf * WH_ZROW + ((p * WH_ZW + c) * 2 + h) * 1024), 16, 0, 0);
-        }
-    };
-
-    f32x4 acc[9][4];
-#pragma unroll
-    for (int t = 0; t < 9; ++t)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[t][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    for (int oct = o0; oct < o1; ++oct) {
-        // the three X rows and the dZ row of output row 0 (the previous octet's last step ended with a barrier: every slot is free)
-        dma_x(oct, 0, 0); dma_x(oct, 1, 1); dma_x(oct, 2, 2); dma_z(oct, 0, 0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        for (int oy = 0; oy < g.Hout; ++oy) {
-            if (oy + 1 < g.Hout) { dma_x(oct, oy + 3, (oy + 3) & 3); dma_z(oct, oy + 1, (oy + 1) & 1); }     // slots last read in step oy - 1
-            const unsigned char* Zr = Zbuf + (oy & 1) * WH_ZROW + (wn * 64 + r16) * 16;
-#pragma unroll
-            for (int quad = 0; quad < 2; ++quad) {
-                const int px = quad * 4 + g4;
-                f16x8 z1[4], z2[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    z1[j] = *reinterpret_cast<const f16x8*>(Zr + ((0 * WH_ZW + px) * WH_CO + j * 16) * 16);
-                    z2[j] = *reinterpret_cast<const f16x8*>(Zr + ((1 * WH_ZW + px) * WH_CO + j * 16) * 16);
-                }
-#pragma unroll
-                for (int t = 0; t < 9; ++t) {
-                    const int dy = t / 3, dx = t - 3 * dy;
-                    const unsigned char* Xr = Xring + ((oy + dy) & 3) * WH_XROW + (wm * 16 + r16) * 16;
-                    const f16x8 x1 = *reinterpret_cast<const f16x8*>(Xr + ((0 * WH_XW + px + dx) * WH_CI) * 16);
-                    const f16x8 x2 = *reinterpret_cast<const f16x8*>(Xr + ((1 * WH_XW + px + dx) * WH_CI) * 16);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(x2, z1[j], acc[t][j], 0, 0, 0);
-                        acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(x1, z2[j], acc[t][j], 0, 0, 0);
-                        acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(x1, z1[j], acc[t][j], 0, 0, 0);
-                    }
-                }
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the next step's rows have landed (this wave's pieces) ...
-            __syncthreads();                                       // ... everybody's, and everybody is done reading this step's
-        }
-    }
-    // C/D layout of the 16 x 16 MFMA: col = lane & 15 (co), row = (lane >> 4) * 4 + reg (ci)
-    const float sc = ldexpf(1.0f, -t_exp_for(*dzmax, T_DZ_TARGET));
-    float* __restrict__ outp = msplit > 1 ? partial + (size_t)blockIdx.y * slab : dW;
-#pragma unroll
-    for (int t = 0; t < 9; ++t)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int ci = ci0 + wm * 16 + g4 * 4 + r, co = co0 + wn * 64 + j * 16 + r16;
-                outp[((size_t)t * g.Cin + ci) * g.Cout + co] = acc[t][j][r] * sc;
-            }
+    wgrad_oct_body<WgradH2>(wh_lds, Xt, Zt, d_count, g, dzmax, dW, msplit, partial, slab);
 }
-
-// ---------------------------------------------------------------- bf16x3 mode of the 3x3 layers (oz_trainer_set_precision 2)
-// Every fp32 operand travels EXACTLY as three bf16 planes (oz_net_b3.h: b3_split, the b3 layout, six products per fp32 product in the order
-// a3 b1 + a1 b3 + a2 b2 + a2 b1 + a1 b2 + a1 b1, fp32 accumulation).  bf16 has fp32's exponent range: no scaling, no maxima, no range flag.
-// Forward and data gradient of conv2..conv4 run on k_gemm_b3 (oz_gemm_b3_launch), their weight gradients on k_wgrad_b3 below; conv1, the
-// dense layers, the heads, BN and Adam stay exact fp32.  The operands are converted per step from the fp32 masters / tensors.
-// Fallback rule: none.  Every trainer capacity (Bmax) takes these kernels: the GEMMs split their k loop until the grid fills the chip (keyed on
-// Bmax), the weight gradient splits its board range; at the reference's batch of 32 both already beat the exact-fp32 kernels they replace.
-//
-// The forward weight operand is k_w_to_b3's (oz_w_to_b3_launch, taps = 9).  The data-gradient operand: Keras kernel W[9][Cin][Cout] fp32 -> row
-// n = ci, channel of k' = co: W[8 - tap][ci][co] (the reversed, channel-swapped taps) in k order k' = (slice * 9 + tap) * 32 + c32, as k_t_w_to_h2<1>
-// unscaled.  One thread per (row, group of 8 k'): a thread's 8 values are 8 consecutive co = one 32-byte read.
-__global__ __launch_bounds__(256) void k_t_w_to_b3(const float* __restrict__ W, int Cin, int Cout, uint4* __restrict__ out) {
-    const int ng = 9 * Cout / 8;
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int grp = (int)(idx % ng), nrow = (int)(idx / ng);
-    if (idx >= (long long)Cin * ng) return;
-    const int kp = grp * 8, tile = kp >> 5, c32 = kp & 31, slice = tile / 9, tap = tile - slice * 9, ch = slice * 32 + c32;
-    const float* q = W + ((size_t)(8 - tap) * Cin + nrow) * Cout + ch;
-    float v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = q[j];
-    b3_store8(out, nrow, 9 * Cout, kp, v);
-}
-// dz (zero-bordered [B][Hz][Hz][C] fp32, interior Hout^2 at offset zoff) -> the same geometry in the b3 layout; only the interior is written
-// (the b3 buffer is zeroed once at allocation, so its border stays zero).  One thread per (row, 8 channels).
-__global__ __launch_bounds__(256) void k_t_dz_to_b3(const float* __restrict__ dz, const int* __restrict__ d_count, int Hout, int Hz, int zoff, int C,
-                                                    uint4* __restrict__ out) {
-    const int cg = C >> 3, P = Hout * Hout;
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x, m = idx / cg;
-    if (m >= (long long)(*d_count) * P) return;
-    const int g8 = (int)(idx % cg), b = (int)(m / P), pix = (int)(m % P);
-    const size_t row = ((size_t)b * Hz + pix / Hout + zoff) * Hz + pix % Hout + zoff;
-    const f32x4 lo = *reinterpret_cast<const f32x4*>(dz + row * C + g8 * 8), hi = *reinterpret_cast<const f32x4*>(dz + row * C + g8 * 8 + 4);
-    const float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    b3_store8(out, row, C, g8 * 8, v);
-}
-// k_wgrad_b3: the weight gradient of conv2..conv4 on v_mfma_f32_16x16x32_bf16, k_wgrad_h2's scheme (octet images, a block owns a ci x co tile
-// for all nine taps, walks the output rows of each octet with a 4-slot X row ring and two dZ row buffers, every tap reads the same staged rows
-// at a shifted pixel slot) with three planes per value and six products per fp32 product (the order above).
-// LDS plan: with three planes k_wgrad_h2's 64 ci x 128 co tile would need 4 X rows of 30 KB + 2 dZ rows of 48 KB = 216 KB, more than a CU's
-// 160 KB.  This kernel uses 32 ci x 128 co: 4 x 15 KB + 2 x 48 KB = 156 KB (one block per CU), which keeps the ring's one-row prefetch; a
-// 64 x 64 tile would fit only with a 3-row X ring (138 KB), which cannot stream the next row in beside the MFMAs of the current one, and was not built.
-// 8 waves = 2 (16 ci) x 4 (32 co): 9 taps x 2 accumulator tiles of 16 x 16 per wave; per pixel quad a wave reads 6 dZ + 27 X fragments
-// (ds_read_b128) for 108 MFMAs.  Octet ranges split over blockIdx.y (raw slabs + k_t_sum_partials, fixed order).
-// Measured in the training step (8x8, 512 filters, rocprofv3): 56 us per layer at batch 32, 406 us at batch 256 -- bound by the operand stream
-// (every dZ row is staged by C / 32 blocks), not the matrix pipe (profiles/r7_train_b{32,256}_bf16x3_kernel_stats.csv, docs/HISTORY.md round 7).
-#define WB_CI 32
-#define WB_CO 128
-#define WB_XROW (3 * WH_XW * WB_CI * 16)        // bytes of one staged X row: [plane][slot][ci] x 16 B = 15 KB
-#define WB_ZROW (3 * WH_ZW * WB_CO * 16)        // bytes of one staged dZ row: [plane][slot][co] x 16 B = 48 KB
-#define WB_LDS (4 * WB_XROW + 2 * WB_ZROW)      // 156 KB
 __global__ __launch_bounds__(512) void k_wgrad_b3(const uint4* __restrict__ Xt, const uint4* __restrict__ Zt, const int* __restrict__ d_count, WhGeom g,
                                                   float* __restrict__ dW, int msplit, float* __restrict__ partial, long long slab) {
     extern __shared__ __attribute__((aligned(16))) unsigned char wb_lds[];
-    unsigned char* const Xring = wb_lds;
-    unsigned char* const Zbuf = wb_lds + 4 * WB_XROW;
-    const int nco = g.Cout / WB_CO;
-    const int ci0 = (blockIdx.x / nco) * WB_CI, co0 = (blockIdx.x % nco) * WB_CO;
-    const int noct = (*d_count + 7) >> 3;
-    const int per = (noct + msplit - 1) / msplit, o0 = blockIdx.y * per, o1 = o0 + per < noct ? o0 + per : noct;
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int wm = wave >> 2, wn = wave & 3, r16 = lane & 15, g4 = lane >> 4;
-
-    // LDS-DMA: one instruction = 64 consecutive 16-byte entries.  X row = 15 instructions, instruction q = the (plane, slot) pairs 2q and 2q + 1
-    // (WH_XW is even: both in one plane), lanes = 2 slots x the 32 ci of the tile; dZ row = 48 instructions q = (plane, slot, half), lanes = 64
-    // of the tile's 128 co.  Wave w issues q = w, w + 8, ...
-    auto dma_x = [&](int oct, int row, int slot) {
-        const uint4* src = Xt + (((size_t)oct * g.XR + row) * WH_XW) * 3 * g.Cin + ci0 + (lane & 31);
-        for (int q = wave; q < 3 * WH_XW / 2; q += 8) {
-            const int pc = 2 * q + (lane >> 5), p = pc / WH_XW, c = pc - p * WH_XW;
-            __builtin_amdgcn_global_load_lds((oz_gptr)(src + ((size_t)c * 3 + p) * g.Cin), (oz_lptr)(Xring + slot * WB_XROW + q * 1024), 16, 0, 0);
-        }
-    };
-    auto dma_z = [&](int oct, int row, int buf) {
-        const uint4* src = Zt + (((size_t)oct * g.Hout + row) * WH_ZW) * 3 * g.Cout + co0 + lane;
-        for (int q = wave; q < 6 * WH_ZW; q += 8) {
-            const int h = q & 1, pc = q >> 1, p = pc / WH_ZW, c = pc - p * WH_ZW;
-            __builtin_amdgcn_global_load_lds((oz_gptr)(src + ((size_t)c * 3 + p) * g.Cout + h * 64), (oz_lptr)(Zbuf + buf * WB_ZROW + q * 1024), 16, 0, 0);
-        }
-    };
-
-    f32x4 acc[9][2];
-#pragma unroll
-    for (int t = 0; t < 9; ++t)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[t][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    for (int oct = o0; oct < o1; ++oct) {
-        // the three X rows and the dZ row of output row 0 (the previous octet's last step ended with a barrier: every slot is free)
-        dma_x(oct, 0, 0); dma_x(oct, 1, 1); dma_x(oct, 2, 2); dma_z(oct, 0, 0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        for (int oy = 0; oy < g.Hout; ++oy) {
-            if (oy + 1 < g.Hout) { dma_x(oct, oy + 3, (oy + 3) & 3); dma_z(oct, oy + 1, (oy + 1) & 1); }     // slots last read in step oy - 1
-            const unsigned char* Zr = Zbuf + (oy & 1) * WB_ZROW + (wn * 32 + r16) * 16;
-#pragma unroll
-            for (int quad = 0; quad < 2; ++quad) {
-                const int px = quad * 4 + g4;
-                bf16x8 z[3][2];
-#pragma unroll
-                for (int p = 0; p < 3; ++p)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) z[p][j] = *reinterpret_cast<const bf16x8*>(Zr + ((p * WH_ZW + px) * WB_CO + j * 16) * 16);
-#pragma unroll
-                for (int t = 0; t < 9; ++t) {
-                    const int dy = t / 3, dx = t - 3 * dy;
-                    const unsigned char* Xr = Xring + ((oy + dy) & 3) * WB_XROW + (wm * 16 + r16) * 16;
-                    bf16x8 x[3];
-#pragma unroll
-                    for (int p = 0; p < 3; ++p) x[p] = *reinterpret_cast<const bf16x8*>(Xr + ((p * WH_XW + px + dx) * WB_CI) * 16);
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-#pragma unroll
-                        for (int q = 0; q < 6; ++q) {      // small terms first: x3 z1, x1 z3, x2 z2, x2 z1, x1 z2, x1 z1
-                            constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
-                            acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x[PA[q]], z[PB[q]][j], acc[t][j], 0, 0, 0);
-                        }
-                    }
-                }
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the next step's rows have landed (this wave's pieces) ...
-            __syncthreads();                                       // ... everybody's, and everybody is done reading this step's
-        }
-    }
-    // C/D layout of the 16 x 16 MFMA: col = lane & 15 (co), row = (lane >> 4) * 4 + reg (ci)
-    float* __restrict__ outp = msplit > 1 ? partial + (size_t)blockIdx.y * slab : dW;
-#pragma unroll
-    for (int t = 0; t < 9; ++t)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int ci = ci0 + wm * 16 + g4 * 4 + r, co = co0 + wn * 32 + j * 16 + r16;
-                outp[((size_t)t * g.Cin + ci) * g.Cout + co] = acc[t][j][r];
-            }
+    wgrad_oct_body<WgradB3>(wb_lds, Xt, Zt, d_count, g, nullptr, dW, msplit, partial, slab);
 }
 
 // ---------------------------------------------------------------- Adam (tf.keras formulation) with clipvalue
@@ -1014,8 +937,17 @@ __global__ __launch_bounds__(256) void k_t_adam(float* __restrict__ P, const flo
 }
 
 // ---------------------------------------------------------------- host object
+// Layer l = 0 .. 5 (conv1 .. conv4, fc1, fc2) as the step sees it: the GEMM shape (conv1 is no GEMM: its Cin is the input planes), P = Hout^2
+// output pixels, and the dz buffer's geometry -- conv3 / conv4 ('valid') keep dz in a zero-bordered Hz x Hz buffer (zoff = 2) so that their data
+// gradient is a plain valid convolution.  Built once in oz_trainer_create from oz_onn_layers; every buffer size and launch reads it.
+struct TLayer { int Hin, Hout, pad, Cin, taps, Co, P, Hz, zoff; };
+// The operands of conv2 .. conv4 (l = 1 .. 3) in a split format, PLANES 16-bit planes per fp32 value: f16x2 (2, the h2 layout) or bf16x3 (3, the b3
+// layout).  W / Wd: forward / data-gradient weight operand; act[l - 1]: the layer's input rows; dz: its zero-bordered data gradient;
+// xoct / zoct: the octet images of the weight gradient (k_t_x_octets / k_t_z_octets).
+struct TPacked { uint4 *W[4] = {}, *Wd[4] = {}, *act[3] = {}, *dz[4] = {}, *xoct[4] = {}, *zoct[4] = {}; };
 struct oz_trainer {
     int n = 8, C = 512, cin = 2, Bmax = 32, device = 0;
+    TLayer L[6];
     float lr = 1e-3f, clip = 0.5f, rate = 0.3f, mom = 0.99f;
     uint64_t seed = 0;
     int64_t step = 0;
@@ -1033,39 +965,30 @@ struct oz_trainer {
     unsigned char *d_in = nullptr, *h_in = nullptr;      // the device block the five pointers above point into, and its pinned host mirror
     size_t in_bytes = 0;
     float *z[6] = {}, *a[6] = {}, *mean[6] = {}, *rstd[6] = {}, *dz[6] = {};
-    float *dA[2] = {}, *sums = nullptr, *partial = nullptr, *ones = nullptr, *zeros = nullptr;
+    float *dA[2] = {}, *partial = nullptr, *ones = nullptr, *zeros = nullptr;
     float *p = nullptr, *v = nullptr, *dlogit = nullptr, *dvpre = nullptr, *loss = nullptr, *losses = nullptr;
     float* gpartial = nullptr;           // split-K scratch of the small-batch GEMMs
     float* wpartial = nullptr;           // row-split scratch of the weight-gradient launches (they run on s2, beside the data-gradient chain)
     hipStream_t s2 = nullptr;
     hipEvent_t ev_dz[6] = {}, ev_w = nullptr;
     hipEvent_t ev_pre = nullptr, ev_wt = nullptr, ev_wd = nullptr;      // derived weight operands are rebuilt on s2 beside the first forward kernels
-    hipEvent_t ev_wl[4] = {nullptr, nullptr, nullptr, nullptr};         // f16x2: the h2 forward operand of layer l = 1 .. 3 is ready (the main stream waits layer by layer)
+    hipEvent_t ev_wl[4] = {nullptr, nullptr, nullptr, nullptr};         // f16x2 / bf16x3: the packed forward operand of layer l = 1 .. 3 is ready (the main stream waits layer by layer)
     bool wait_wt = false, wait_wd = false, wait_wl[4] = {false, false, false, false};
-    // f16x2 mode (oz_trainer_set_precision 1): conv2..4 forward and data gradient on k_gemm_h2
-    int h2 = 0;
-    uint4 *Wh[4] = {}, *Whd[4] = {}, *a_h2[3] = {}, *dz_h2[4] = {};
+    // oz_trainer_set_precision: 0 f32; 1 f16x2 (conv2..4 forward and data gradient on k_gemm_h2, weight gradient on k_wgrad_h2); 2 bf16x3 (k_gemm_b3,
+    // k_wgrad_b3).  pk[mode - 1] is allocated at the first use of a split mode and kept; the scales, maxima and the range flag are f16x2's alone
+    int mode = 0;
+    TPacked pk[2];
     float *wscale[4] = {}, *dscale[4] = {};
     unsigned *wmax = nullptr, *dzmax = nullptr;          // [3] max |w| of conv2..4, [6] max |dz| per layer (bit patterns)
     int* h2flag = nullptr;
     float* bnb2[6] = {};                 // per-layer row-block partials of the bias gradient (mid-size BN backward)
-    bool overlap = true;                 // weight gradients on the second stream beside the data-gradient chain (false: all on the main stream)
     long long gpartial_floats = 40LL << 20;      // 160 MB each: 16 row-split slabs of a 3x3 x 512 x 512 weight gradient
-    bool wconv_attr = false, wh_attr = false;
-    uint4 *xt_oct[4] = {}, *zt_oct[4] = {};     // f16x2 weight gradient: octet images of a[l - 1] / dz[l] (k_t_x_octets<2> / k_t_z_octets<2>)
-    // bf16x3 mode (oz_trainer_set_precision 2): conv2..4 forward, data gradient and weight gradient on the bf16 matrix cores
-    int b3 = 0;
-    bool wb3_attr = false;
-    uint4 *Wb3[4] = {}, *Wb3d[4] = {}, *a_b3[3] = {}, *dz_b3[4] = {};
-    uint4 *xt_b3[4] = {}, *zt_b3[4] = {};     // octet images in three planes (k_t_x_octets<3> / k_t_z_octets<3>)
     // HBM-resident data set of a fit (oz_trainer_set_dataset / oz_trainer_fit_epoch)
     uint64_t *ds_own = nullptr, *ds_opp = nullptr;
     float *ds_pi = nullptr, *ds_z = nullptr;
     int* ds_order = nullptr;
     double* ds_acc = nullptr;
     int64_t ds_n = 0, ds_cap = 0;
-    int split_mask = 7;                  // 1 forward, 2 dense dgrad, 4 conv dgrad GEMMs may split K
-    int P_[6], Co[6], Hout[6], Hz[6], zoff[6];
     std::vector<void*> allocs;
     bool dirty = true;                   // derived operands need a refresh
     std::mutex mu;                       // one caller at a time (ThreadWorker-style Python threads)
@@ -1089,12 +1012,13 @@ struct oz_trainer {
 // element counts of the 40 get_weights() arrays and their offsets in the trainable arena (-1: moving statistic);
 // every array starts 16-byte aligned.  Returns the arena size in floats.
 static int64_t t_layout(int n, int C, int cin, int64_t* size, int64_t* toff) {
-    const int64_t A = n * n, F = (int64_t)(n - 4) * (n - 4) * C;
-    const int cins[4] = {cin, C, C, C};
-    int idx = 0;
-    for (int l = 0; l < 4; ++l) { size[idx++] = 9LL * cins[l] * C; for (int j = 0; j < 5; ++j) size[idx++] = C; }
-    size[idx++] = F * 1024; for (int j = 0; j < 5; ++j) size[idx++] = 1024;
-    size[idx++] = 1024LL * 512; for (int j = 0; j < 5; ++j) size[idx++] = 512;
+    const int64_t A = n * n;
+    const OzLayers net = oz_onn_layers(n, C);
+    for (int l = 0; l < 6; ++l) {          // kernel [K][N], then bias, gamma, beta and the two moving statistics [N]
+        const int64_t K = l ? net[l - 1].K() : 9 * cin, N = l ? net[l - 1].N : C;
+        size[6 * l] = K * N;
+        for (int j = 1; j < 6; ++j) size[6 * l + j] = N;
+    }
     size[36] = 512 * A; size[37] = A; size[38] = 512; size[39] = 1;
     int64_t total = 0;
     for (int i = 0; i < 40; ++i) {
@@ -1133,19 +1057,18 @@ OZ_API int oz_trainer_create(oz_trainer** out, int n, int channels, int in_chann
         T_ALLOC(t->P, t->total); T_ALLOC(t->M1, t->total); T_ALLOC(t->V2, t->total);
         if (external_grads) { t->G = external_grads; t->own_grads = false; } else T_ALLOC(t->G, t->total);
         for (int i = 0; i < 36; ++i) if (t->toff[i] < 0) { T_ALLOC(t->stats[i], t->size[i]); T_ALLOC(t->stats_new[i], t->size[i]); }
-        const OzLayers L = oz_onn_layers(n, C);              // layer l >= 1 is GEMM layer l - 1; layer 0 = conv1 ('same', C filters)
+        const OzLayers net = oz_onn_layers(n, C);            // layer l >= 1 is GEMM layer l - 1; layer 0 = conv1 ('same', C filters)
         for (int l = 0; l < 6; ++l) {
-            t->Hout[l] = l ? L[l - 1].Hout : n; t->P_[l] = t->Hout[l] * t->Hout[l]; t->Co[l] = l ? L[l - 1].N : C;
-            // conv3 / conv4 ('valid'): dz lives in a zero-bordered (Hout + 4)^2 buffer so that the data gradient is a plain valid conv
-            t->zoff[l] = (l == 2 || l == 3) ? 2 : 0; t->Hz[l] = t->Hout[l] + 2 * t->zoff[l];
-            const size_t rows = (size_t)max_batch * t->P_[l];
-            T_ALLOC(t->z[l], rows * t->Co[l]); T_ALLOC(t->a[l], rows * t->Co[l]);
-            T_ALLOC(t->dz[l], (size_t)max_batch * t->Hz[l] * t->Hz[l] * t->Co[l]);
-            T_ALLOC(t->mean[l], t->Co[l]); T_ALLOC(t->rstd[l], t->Co[l]);
+            const OzLayerShape sh = l ? net[l - 1] : OzLayerShape{n, n, 1, in_channels, 9, C};
+            const int zoff = sh.taps == 9 && sh.pad == 0 ? 2 : 0;
+            const TLayer& L = t->L[l] = {sh.Hin, sh.Hout, sh.pad, sh.Cin, sh.taps, sh.N, sh.pixels(), sh.Hout + 2 * zoff, zoff};
+            const size_t rows = (size_t)max_batch * L.P;
+            T_ALLOC(t->z[l], rows * L.Co); T_ALLOC(t->a[l], rows * L.Co);
+            T_ALLOC(t->dz[l], (size_t)max_batch * L.Hz * L.Hz * L.Co);
+            T_ALLOC(t->mean[l], L.Co); T_ALLOC(t->rstd[l], L.Co);
         }
         const size_t amax = (size_t)max_batch * (size_t)A * C > (size_t)max_batch * 1024 ? (size_t)max_batch * A * C : (size_t)max_batch * 1024;
         T_ALLOC(t->dA[0], amax); T_ALLOC(t->dA[1], amax);
-        T_ALLOC(t->sums, 2 * 8192);
         size_t pmax = (size_t)RED_S * 2 * 1024;
         if ((size_t)RED_S * 2 * C > pmax) pmax = (size_t)RED_S * 2 * C;
         if ((size_t)RED_S * 9 * in_channels * C > pmax) pmax = (size_t)RED_S * 9 * in_channels * C;
@@ -1175,7 +1098,7 @@ OZ_API int oz_trainer_create(oz_trainer** out, int n, int channels, int in_chann
         for (int l = 0; l < 6; ++l) OZ_HIP(hipEventCreateWithFlags(&t->ev_dz[l], hipEventDisableTiming));
         OZ_HIP(hipEventCreateWithFlags(&t->ev_w, hipEventDisableTiming));
         for (hipEvent_t* e : {&t->ev_pre, &t->ev_wt, &t->ev_wd, &t->ev_wl[1], &t->ev_wl[2], &t->ev_wl[3]}) OZ_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
-        for (int l = 0; l < 6; ++l) T_ALLOC(t->bnb2[l], (size_t)OZ_BNB_MAX_RB * t->Co[l]);
+        for (int l = 0; l < 6; ++l) T_ALLOC(t->bnb2[l], (size_t)OZ_BNB_MAX_RB * t->L[l].Co);
         OZ_HIP(hipStreamSynchronize(t->s));
         return OZ_OK;
     }();
@@ -1188,7 +1111,7 @@ OZ_API int oz_trainer_destroy(oz_trainer* t) { delete t; return OZ_OK; }
 
 // sticky range flag of the f16x2 mode (an activation above the fp16 range): reported at the synchronising calls
 static int t_check_range(oz_trainer* t) {
-    if (!t->h2 || !t->h2flag) return OZ_OK;
+    if (t->mode != 1 || !t->h2flag) return OZ_OK;
     int f = 0;
     OZ_HIP(hipMemcpyAsync(&f, t->h2flag, sizeof(int), hipMemcpyDeviceToHost, t->s));
     OZ_HIP(hipStreamSynchronize(t->s));
@@ -1210,42 +1133,35 @@ OZ_API int oz_trainer_set_policy_loss(oz_trainer* t, int mode) {
     return OZ_OK;
 }
 
+// the packed operands of one split mode (planes 16-bit planes per value: values x planes / 8 uint4 units); zeroed, and the dz border stays zero
+static int t_alloc_packed(oz_trainer* t, TPacked& k, int planes) {
+    const size_t C = t->C, Bmax = t->Bmax, noct = (Bmax + 7) / 8, wq = C * 9 * C * planes / 8;
+    for (int l = 1; l < 4; ++l) {
+        const TLayer& L = t->L[l];
+        T_ALLOC(k.W[l], wq); T_ALLOC(k.Wd[l], wq);
+        T_ALLOC(k.act[l - 1], Bmax * t->L[l - 1].P * C * planes / 8);
+        T_ALLOC(k.dz[l], Bmax * L.Hz * L.Hz * C * planes / 8);
+        T_ALLOC(k.xoct[l], noct * (L.Hout + 2) * WH_XW * planes * C);
+        T_ALLOC(k.zoct[l], noct * L.Hout * WH_ZW * planes * C);
+    }
+    return OZ_OK;
+}
+
 OZ_API int oz_trainer_set_precision(oz_trainer* t, int mode) {
     OZ_REQUIRE(t && (mode == 0 || mode == 1 || mode == 2), "oz_trainer_set_precision: mode 0 (f32), 1 (f16x2) or 2 (bf16x3)");
     T_LOCK(t);
     OZ_REQUIRE(t->C % 256 == 0 || mode == 0, "oz_trainer_set_precision: %s needs channels %% 256 == 0 (got %d)", mode == 1 ? "f16x2" : "bf16x3", t->C);
     OZ_HIP(hipSetDevice(t->device));
     OZ_HIP(hipStreamSynchronize(t->s));
-    if (mode == 1 && !t->wmax) {
-        const int C = t->C;
-        const size_t wq = (size_t)C * 9 * C / 4;             // uint4 units of a 3x3 kernel in the h2 layout (4 B per value)
-        for (int l = 1; l < 4; ++l) {
-            T_ALLOC(t->Wh[l], wq); T_ALLOC(t->Whd[l], wq);
-            T_ALLOC(t->wscale[l], C); T_ALLOC(t->dscale[l], C);
-            T_ALLOC(t->a_h2[l - 1], (size_t)t->Bmax * t->P_[l - 1] * C / 4);
-            T_ALLOC(t->dz_h2[l], (size_t)t->Bmax * t->Hz[l] * t->Hz[l] * C / 4);      // zeroed: the border stays zero
-            const size_t noct = (size_t)(t->Bmax + 7) / 8;
-            T_ALLOC(t->xt_oct[l], noct * (t->Hout[l] + 2) * WH_XW * 2 * C);
-            T_ALLOC(t->zt_oct[l], noct * t->Hout[l] * WH_ZW * 2 * C);
-        }
-        T_ALLOC(t->wmax, 4); T_ALLOC(t->dzmax, 8); T_ALLOC(t->h2flag, 1);
-        OZ_HIP(hipStreamSynchronize(t->s));
-    }
-    if (mode == 2 && !t->Wb3[1]) {
-        const int C = t->C;
-        const size_t wq = (size_t)C * 9 * C * 3 / 8;         // uint4 units of a 3x3 kernel in the b3 layout (6 B per value)
-        const size_t noct = (size_t)(t->Bmax + 7) / 8;
-        for (int l = 1; l < 4; ++l) {
-            T_ALLOC(t->Wb3[l], wq); T_ALLOC(t->Wb3d[l], wq);
-            T_ALLOC(t->a_b3[l - 1], (size_t)t->Bmax * t->P_[l - 1] * C * 3 / 8);
-            T_ALLOC(t->dz_b3[l], (size_t)t->Bmax * t->Hz[l] * t->Hz[l] * C * 3 / 8);      // zeroed: the border stays zero
-            T_ALLOC(t->xt_b3[l], noct * (t->Hout[l] + 2) * WH_XW * 3 * C);
-            T_ALLOC(t->zt_b3[l], noct * t->Hout[l] * WH_ZW * 3 * C);
+    if (mode && !t->pk[mode - 1].W[1]) {
+        if (int rc = t_alloc_packed(t, t->pk[mode - 1], mode + 1)) return rc;
+        if (mode == 1) {
+            for (int l = 1; l < 4; ++l) { T_ALLOC(t->wscale[l], t->C); T_ALLOC(t->dscale[l], t->C); }
+            T_ALLOC(t->wmax, 4); T_ALLOC(t->dzmax, 8); T_ALLOC(t->h2flag, 1);
         }
         OZ_HIP(hipStreamSynchronize(t->s));
     }
-    t->h2 = mode == 1;
-    t->b3 = mode == 2;
+    t->mode = mode;
     t->dirty = true;
     return OZ_OK;
 }
@@ -1303,57 +1219,50 @@ OZ_API int oz_trainer_step_count(oz_trainer* t, int64_t* step) {
     return OZ_OK;
 }
 
-// The weights changed (optimiser step, set_weight): rebuild the GEMM operands derived from them.  With the second stream
-// available the eight launches run THERE, after everything already queued on the main stream (the optimiser step that wrote
-// the weights, the previous step's readers of Wt / Wd), and the main stream only waits where it first needs them -- the
-// forward operands before conv2's GEMM, the data-gradient operands before conv4's dgrad -- so the uploads, conv1 and its BN
-// run beside them instead of behind them (~70 us of a 1.4 ms step at batch 32).
+// The weights changed (optimiser step, set_weight): rebuild the GEMM operands derived from them.  The launches run on the SECOND stream,
+// after everything already queued on the main stream (the optimiser step that wrote the weights, the previous step's readers of Wt / Wd),
+// and the main stream only waits where it first needs them -- the forward operands before conv2's GEMM, the data-gradient operands before
+// conv4's dgrad -- so the uploads, conv1 and its BN run beside them instead of behind them (~70 us of a 1.4 ms step at batch 32).
 static int t_refresh(oz_trainer* t) {
-    const int C = t->C, F = (t->n - 4) * (t->n - 4) * C;
-    const int Ks[6] = {0, 9 * C, 9 * C, 9 * C, F, 1024}, Ns[6] = {0, C, C, C, 1024, 512};
-    hipStream_t r = t->s;
-    if (t->overlap) {
-        OZ_HIP(hipEventRecord(t->ev_pre, t->s));
-        OZ_HIP(hipStreamWaitEvent(t->s2, t->ev_pre, 0));
-        r = t->s2;
-    }
-    const unsigned h2_blocks = (unsigned)(((long long)C * (9 * C / 8) + 255) / 256);
-    if (t->h2) {         // f16x2: per-tensor maxima -> power-of-two scales -> the h2 forward operands, straight from the masters
+    const int C = t->C;
+    hipStream_t r = t->s2;
+    OZ_HIP(hipEventRecord(t->ev_pre, t->s));
+    OZ_HIP(hipStreamWaitEvent(r, t->ev_pre, 0));
+    const TPacked* k = t->mode ? &t->pk[t->mode - 1] : nullptr;
+    const unsigned wd_blocks = (unsigned)(((long long)C * (9 * C / 8) + 255) / 256);      // one thread per (row, group of 8 k') of a packed 3x3 operand
+    if (t->mode == 1) {  // f16x2: per-tensor maxima -> power-of-two scales (the forward operands below, the data-gradient operands further down)
         OZ_HIP(hipMemsetAsync(t->wmax, 0, 3 * sizeof(unsigned), r));
         AbsMaxArgs am;
         for (int l = 1; l < 4; ++l) { am.p[l - 1] = t->param(6 * l); am.n[l - 1] = 9LL * C * C; }
         hipLaunchKernelGGL(k_t_absmax, dim3(192, 3), dim3(256), 0, r, am, t->wmax);      // (12 x 16-byte loads per thread cover 9 x 512 x 512 floats in one trip)
-        for (int l = 1; l < 4; ++l) {
-            hipLaunchKernelGGL(k_t_w_to_h2<0>, dim3(h2_blocks), dim3(256), 0, r, t->param(6 * l), C, C, t->wmax + (l - 1), t->Wh[l], t->wscale[l], t->h2flag);
-            if (t->overlap) { OZ_HIP(hipEventRecord(t->ev_wl[l], r)); t->wait_wl[l] = true; }      // conv2's GEMM waits for ITS operand only (round 5: it waited
-        }                                                                                          // for all five forward operands, 64 us of an idle main stream per step)
+    }
+    // forward operands: the packed ones of conv2..4 straight from the masters, each with its own event -- conv2's GEMM waits for ITS operand only
+    // (round 5: it waited for all five forward operands, 64 us of an idle main stream per step) -- then the fp32 ones (the dense layers; the 3x3
+    // layers too in f32 mode)
+    for (int l = 1; k && l < 4; ++l) {
+        if (t->mode == 1)
+            hipLaunchKernelGGL(k_t_w_to_h2<0>, dim3(wd_blocks), dim3(256), 0, r, t->param(6 * l), C, C, t->wmax + (l - 1), k->W[l], t->wscale[l], t->h2flag);
+        else if (int rc = oz_w_to_b3_launch(t->param(6 * l), 9 * C, C, 9, k->W[l], r)) return rc;
+        OZ_HIP(hipEventRecord(t->ev_wl[l], r));
+        t->wait_wl[l] = true;
+    }
+    OZ_HIP(hipGetLastError());
+    for (int l = k ? 4 : 1; l < 6; ++l) {
+        const int K = t->L[l].taps * t->L[l].Cin, N = t->L[l].Co;
+        hipLaunchKernelGGL(k_t_transpose, dim3((N + 31) / 32, (K + 31) / 32), dim3(256), 0, r, t->param(6 * l), K, N, t->Wt[l]);
         OZ_HIP(hipGetLastError());
     }
-    if (t->b3) {         // bf16x3: the b3 forward operands, straight from the masters (no scaling)
-        for (int l = 1; l < 4; ++l) {
-            if (int rc = oz_w_to_b3_launch(t->param(6 * l), 9 * C, C, 9, t->Wb3[l], r)) return rc;
-            if (t->overlap) { OZ_HIP(hipEventRecord(t->ev_wl[l], r)); t->wait_wl[l] = true; }
+    OZ_HIP(hipEventRecord(t->ev_wt, r));
+    for (int l = 1; l < 4; ++l) {      // data-gradient operands of the 3x3 layers
+        switch (t->mode) {
+        case 1: hipLaunchKernelGGL(k_t_w_to_h2<1>, dim3(wd_blocks), dim3(256), 0, r, t->param(6 * l), C, C, t->wmax + (l - 1), k->Wd[l], (float*)nullptr, t->h2flag); break;
+        case 2: hipLaunchKernelGGL(k_t_w_to_b3, dim3(wd_blocks), dim3(256), 0, r, t->param(6 * l), C, C, k->Wd[l]); break;
+        default: hipLaunchKernelGGL(k_t_dgrad_operand, dim3((unsigned)((9LL * C * C + 255) / 256)), dim3(256), 0, r, t->param(6 * l), C, C, t->Wd[l]);
         }
         OZ_HIP(hipGetLastError());
     }
-    for (int l = (t->h2 || t->b3) ? 4 : 1; l < 6; ++l) {      // fp32 forward operands (the dense layers; the 3x3 layers too in f32 mode)
-        hipLaunchKernelGGL(k_t_transpose, dim3((Ns[l] + 31) / 32, (Ks[l] + 31) / 32), dim3(256), 0, r, t->param(6 * l), Ks[l], Ns[l], t->Wt[l]);
-        OZ_HIP(hipGetLastError());
-    }
-    if (t->overlap) OZ_HIP(hipEventRecord(t->ev_wt, r));
-    for (int l = 1; l < 4; ++l) {
-        if (t->h2)
-            hipLaunchKernelGGL(k_t_w_to_h2<1>, dim3(h2_blocks), dim3(256), 0, r, t->param(6 * l), C, C, t->wmax + (l - 1), t->Whd[l], (float*)nullptr, t->h2flag);
-        else if (t->b3)
-            hipLaunchKernelGGL(k_t_w_to_b3, dim3(h2_blocks), dim3(256), 0, r, t->param(6 * l), C, C, t->Wb3d[l]);
-        else {
-            const long long cnt = 9LL * C * C;
-            hipLaunchKernelGGL(k_t_dgrad_operand, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, r, t->param(6 * l), C, C, t->Wd[l]);
-        }
-        OZ_HIP(hipGetLastError());
-    }
-    if (t->overlap) OZ_HIP(hipEventRecord(t->ev_wd, r));
-    t->wait_wt = t->wait_wd = t->overlap;
+    OZ_HIP(hipEventRecord(t->ev_wd, r));
+    t->wait_wt = t->wait_wd = true;
     t->dirty = false;
     return OZ_OK;
 }
@@ -1367,7 +1276,7 @@ static int t_reduce(oz_trainer* t, RedArgs r) {
 
 // BN (training mode) + ReLU (+ dropout) of layer l: z[l] -> a[l]
 static int t_bn_forward(oz_trainer* t, int l, int B) {
-    const int Cc = t->Co[l], P = t->P_[l];
+    const int Cc = t->L[l].Co, P = t->L[l].P;
     if ((long long)B * P <= OZ_BN_FUSED_MAX_ROWS) {      // small batch: the whole layer in one launch (oz_train_fused.h)
         if ((long long)B * P <= 32 * OZ_BN_RL)
             hipLaunchKernelGGL(k_t_bn_fwd_fused<32>, dim3(Cc / OZ_BN_COLS), dim3(1024), 0, t->s, t->z[l], t->a[l], t->d_count, P, Cc, t->param(6 * l + 2),
@@ -1394,212 +1303,244 @@ static int t_bn_forward(oz_trainer* t, int l, int B) {
     return OZ_OK;
 }
 
-// forward + backward of the batch staged in d_own / d_opp / d_pit / d_zt / d_count (B boards): everything is enqueued on the
-// trainer's streams, nothing is waited for; gradients land in the arena, the batch-mean losses in t->losses
-static int t_forward_backward_async(oz_trainer* t, int B) {
-    hipStream_t s = t->s;
-    const int n = t->n, C = t->C, A = n * n, F = (n - 4) * (n - 4) * C;
-    if (t->dirty) if (int rc = t_refresh(t)) return rc;
+// the main stream waits for an operand of t_refresh where it first reads it, once per refresh
+static int t_wait_once(hipStream_t s, hipEvent_t e, bool& pending) {
+    if (pending) { OZ_HIP(hipStreamWaitEvent(s, e, 0)); pending = false; }
+    return OZ_OK;
+}
 
-    // ---- forward
-    { const long long tot = (long long)B * A * (C / 4);
-      hipLaunchKernelGGL(k_t_conv1_fwd, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, t->d_own, t->d_opp, t->d_count, n, C, t->cin,
-                         t->param(0), t->param(1), t->z[0]);
-      OZ_HIP(hipGetLastError()); }
+// The pieces of a step.  Everything is enqueued on the trainer's two streams, nothing is waited for on the host.  The data-gradient chain (BN
+// backward -> dgrad -> BN backward of the layer below -> ...) stays on the main stream; what only needs a[l - 1] and dz[l] -- the weight gradient
+// and the bias gradient's last sum -- runs on the second stream behind ev_dz[l], beside the chain, whose small-batch launches leave most CUs idle.
+
+// forward: boards -> conv1 .. fc2 (each with its BN) -> heads and losses
+static int t_forward(oz_trainer* t, int B) {
+    hipStream_t s = t->s;
+    const int n = t->n, C = t->C, A = n * n;
+    const long long tot = (long long)B * A * (C / 4);
+    hipLaunchKernelGGL(k_t_conv1_fwd, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, t->d_own, t->d_opp, t->d_count, n, C, t->cin,
+                       t->param(0), t->param(1), t->z[0]);
+    OZ_HIP(hipGetLastError());
     if (int rc = t_bn_forward(t, 0, B)) return rc;
-    const int Hin[6] = {n, n, n, n - 2, 1, 1}, pad[6] = {1, 1, 0, 0, 0, 0}, Cin[6] = {t->cin, C, C, C, F, 1024}, taps[6] = {9, 9, 9, 9, 1, 1};
-    if (t->wait_wt && !t->h2 && !t->b3) { OZ_HIP(hipStreamWaitEvent(s, t->ev_wt, 0)); t->wait_wt = false; }
     for (int l = 1; l < 6; ++l) {
-        if (t->wait_wt && l == 4) { OZ_HIP(hipStreamWaitEvent(s, t->ev_wt, 0)); t->wait_wt = false; }      // f16x2 / bf16x3: the fp32 operands of the dense layers
-        if (t->b3 && l < 4) {      // bf16x3: the previous layer's activation in the b3 layout, then the GEMM on the bf16 matrix cores (z is pre-BN: no ReLU)
-            if (int rc = oz_f32_to_b3_launch(t->a[l - 1], t->d_count, t->Bmax, t->P_[l - 1], C, t->a_b3[l - 1], s)) return rc;
-            if (t->wait_wl[l]) { OZ_HIP(hipStreamWaitEvent(s, t->ev_wl[l], 0)); t->wait_wl[l] = false; }
-            if (int rc = oz_gemm_b3_launch(t->a_b3[l - 1], t->Wb3[l], t->ones, t->param(6 * l + 1), t->z[l], t->d_count, t->Bmax, Hin[l], t->Hout[l], pad[l],
-                                           Cin[l], 9, t->Co[l], 0, s, t->gpartial, t->gpartial_floats, t->zeros, 0)) return rc;
-        } else
-        if (t->h2 && l < 4) {      // f16x2: the previous layer's activation in the h2 layout, then the GEMM on the fp16 matrix cores
-            const long long thr = (long long)B * t->P_[l - 1] * (C / 8);
-            hipLaunchKernelGGL(k_t_act_to_h2, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, s, t->a[l - 1], t->d_count, t->P_[l - 1], C, t->a_h2[l - 1], t->h2flag);
-            if (t->wait_wl[l]) { OZ_HIP(hipStreamWaitEvent(s, t->ev_wl[l], 0)); t->wait_wl[l] = false; }
-            if (int rc = oz_gemm_h2_launch(t->a_h2[l - 1], t->Wh[l], t->wscale[l], t->param(6 * l + 1), t->z[l], t->d_count, B, Hin[l], t->Hout[l], pad[l],
-                                           Cin[l], 9, t->Co[l], s, t->gpartial, t->gpartial_floats, t->zeros, t->h2flag)) return rc;
-        } else
-        if (int rc = oz_gemm_f32_launch(t->a[l - 1], t->Wt[l], t->ones, t->param(6 * l + 1), t->z[l], t->d_count, B, Hin[l], t->Hout[l], pad[l],
-                                        Cin[l], taps[l], t->Co[l], 0, s, t->gpartial, (t->split_mask & 1) ? t->gpartial_floats : 0)) return rc;
+        const TLayer& L = t->L[l];
+        const int Pin = t->L[l - 1].P;
+        switch (l < 4 ? t->mode : 0) {      // the 3x3 layers of a split mode: the previous layer's activation in the packed layout, then the GEMM on the 16-bit matrix cores
+        case 0:
+            if (int rc = t_wait_once(s, t->ev_wt, t->wait_wt)) return rc;          // the first fp32 operand of the step: conv2's, or fc1's in a split mode
+            if (int rc = oz_gemm_f32_launch(t->a[l - 1], t->Wt[l], t->ones, t->param(6 * l + 1), t->z[l], t->d_count, B, L.Hin, L.Hout, L.pad,
+                                            L.Cin, L.taps, L.Co, 0, s, t->gpartial, t->gpartial_floats)) return rc;
+            break;
+        case 1: {
+            const TPacked& k = t->pk[0];
+            const long long thr = (long long)B * Pin * (C / 8);
+            hipLaunchKernelGGL(k_t_act_to_h2, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, s, t->a[l - 1], t->d_count, Pin, C, k.act[l - 1], t->h2flag);
+            if (int rc = t_wait_once(s, t->ev_wl[l], t->wait_wl[l])) return rc;
+            if (int rc = oz_gemm_h2_launch(k.act[l - 1], k.W[l], t->wscale[l], t->param(6 * l + 1), t->z[l], t->d_count, B, L.Hin, L.Hout, L.pad,
+                                           L.Cin, 9, L.Co, s, t->gpartial, t->gpartial_floats, t->zeros, t->h2flag)) return rc;
+            break;
+        }
+        case 2: {        // (z is pre-BN: no ReLU)
+            const TPacked& k = t->pk[1];
+            if (int rc = oz_f32_to_b3_launch(t->a[l - 1], t->d_count, t->Bmax, Pin, C, k.act[l - 1], s)) return rc;
+            if (int rc = t_wait_once(s, t->ev_wl[l], t->wait_wl[l])) return rc;
+            if (int rc = oz_gemm_b3_launch(k.act[l - 1], k.W[l], t->ones, t->param(6 * l + 1), t->z[l], t->d_count, t->Bmax, L.Hin, L.Hout, L.pad,
+                                           L.Cin, 9, L.Co, 0, s, t->gpartial, t->gpartial_floats, t->zeros, 0)) return rc;
+        }
+        }
         if (int rc = t_bn_forward(t, l, B)) return rc;
     }
     hipLaunchKernelGGL(k_t_heads, dim3(B), dim3(64), 0, s, t->a[5], t->d_count, n, t->policy_loss, t->param(36), t->param(37), t->param(38), t->param(39),
                        t->d_pit, t->d_zt, t->p, t->v, t->dlogit, t->dvpre, t->loss);
     OZ_HIP(hipGetLastError());
+    return OZ_OK;
+}
 
-    // ---- backward
+// heads backward: their weight and bias gradients, the batch-mean losses, dA = the gradient wrt a[5]
+static int t_heads_backward(oz_trainer* t, int B, float* dA) {
+    hipStream_t s = t->s;
+    const int A = t->n * t->n;
     hipLaunchKernelGGL(k_t_heads_wgrad, dim3(512), dim3(128), 0, s, t->a[5], t->dlogit, t->dvpre, t->d_count, A, t->grad(36), t->grad(38));
     hipLaunchKernelGGL(k_t_heads_bias, dim3(1), dim3(128), 0, s, t->dlogit, t->dvpre, t->loss, t->d_count, A, t->grad(37), t->grad(39), t->losses,
-                       t->h2 ? t->dzmax : (unsigned*)nullptr);
+                       t->mode == 1 ? t->dzmax : (unsigned*)nullptr);
     hipLaunchKernelGGL(k_t_heads_dgrad, dim3((unsigned)(((long long)B * 512 + 255) / 256)), dim3(256), 0, s, t->dlogit, t->dvpre, t->param(36),
-                       t->param(38), t->d_count, A, t->dA[1]);
+                       t->param(38), t->d_count, A, dA);
     OZ_HIP(hipGetLastError());
+    return OZ_OK;
+}
+
+// BN backward of layer l: dA (the gradient wrt a[l]) -> dz[l], the gradients of gamma, beta and the bias; f16x2 also leaves max |dz[l]| in dzmax[l]
+static int t_bn_backward(oz_trainer* t, int l, int B, const float* dA) {
+    hipStream_t s = t->s;
+    const TLayer& L = t->L[l];
+    const int Cc = L.Co;
+    const long long M = (long long)B * L.P;
+    const float post = l >= 4 && t->rate > 0.f ? 1.0f / (1.0f - t->rate) : 1.0f;
+    unsigned* dzmax = t->mode == 1 ? t->dzmax + l : nullptr;
+    if (M <= OZ_BNB_MIN_ROWS) {         // small batch: BN backward, dgamma / dbeta / bias gradient in one launch
+        hipLaunchKernelGGL(k_t_bn_bwd_fused, dim3(Cc / OZ_BN_COLS), dim3(1024), 0, s, dA, t->a[l], t->z[l], t->mean[l], t->rstd[l],
+                           t->param(6 * l + 2), post, t->d_count, L.Hout, Cc, L.Hz, L.zoff, t->dz[l], t->grad(6 * l + 2),
+                           t->grad(6 * l + 3), t->grad(6 * l + 1), dzmax);
+        OZ_HIP(hipGetLastError());
+        return OZ_OK;
+    }
+    // partial sums over row splits, then one launch that finishes the sums and writes dz (oz_train_fused.h)
+    const int Q = Cc / 4, lpr = Q < 64 ? Q : 64, rpp = 256 / lpr;
+    int RS = 16; while (RS < OZ_BNB_MAX_RB && M > (long long)RS * rpp * 8) RS *= 2;          // ~8 rows per thread
+    RedArgs r = {}; r.x = dA; r.a = t->a[l]; r.z = t->z[l]; r.mean = t->mean[l]; r.rstd = t->rstd[l]; r.post_scale = post; r.P = L.P; r.C = Cc;
+    hipLaunchKernelGGL(k_t_colreduce<2>, dim3((Q + 63) / 64, RS), dim3(256), 0, s, r, t->d_count, t->partial);
+    hipLaunchKernelGGL(k_t_bnb_apply, dim3((Q + 63) / 64, RS), dim3(256), 0, s, dA, t->a[l], t->z[l], t->mean[l], t->rstd[l], t->param(6 * l + 2),
+                       post, t->d_count, L.Hout, Cc, L.Hz, L.zoff, t->partial, RS, t->dz[l], t->grad(6 * l + 2), t->grad(6 * l + 3), t->bnb2[l], dzmax);
+    // the bias gradient (column sums of dz) is off the dgrad chain: finished beside it (conv1 has no chain below it: on the main stream)
+    hipStream_t sb = s;
+    if (l > 0) {
+        OZ_HIP(hipEventRecord(t->ev_dz[l], s));
+        OZ_HIP(hipStreamWaitEvent(t->s2, t->ev_dz[l], 0));
+        sb = t->s2;
+    }
+    hipLaunchKernelGGL(k_t_sum_partials, dim3((unsigned)((Cc + 255) / 256)), dim3(256), 0, sb, t->bnb2[l], RS, (long long)Cc, t->grad(6 * l + 1));
+    OZ_HIP(hipGetLastError());
+    return OZ_OK;
+}
+
+// weight gradient of conv1 (its input is the bitboards): on the main stream, nothing runs beside it
+static int t_wgrad_conv1(oz_trainer* t, int B) {
+    hipStream_t s = t->s;
+    const int n = t->n, C = t->C;
+    int S1 = 8;                                    // row splits: ~16 rows per thread (each a dependent ~1 us load at small batch), at most RED_S (the partial buffer's capacity)
+    while (S1 < RED_S && (long long)B * n * n > 16LL * S1) S1 *= 2;
+    if (n == 8) hipLaunchKernelGGL(k_t_conv1_wgrad<8>, dim3((C + 255) / 256, S1), dim3(256), 0, s, t->d_own, t->d_opp, t->d_count, C, t->cin, t->dz[0], t->partial, S1);
+    else hipLaunchKernelGGL(k_t_conv1_wgrad<6>, dim3((C + 255) / 256, S1), dim3(256), 0, s, t->d_own, t->d_opp, t->d_count, C, t->cin, t->dz[0], t->partial, S1);
+    const long long cnt = 9LL * t->cin * C;
+    hipLaunchKernelGGL(k_t_sum_partials, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, t->partial, S1, cnt, t->grad(0));
+    OZ_HIP(hipGetLastError());
+    return OZ_OK;
+}
+
+// the octet-image weight gradient of 3x3 layer l on stream sw: octet images of a[l - 1] and dz[l], then k_wgrad_h2 (two planes of the scaled dz
+// on the fp16 matrix cores) or k_wgrad_b3 (three planes on the bf16 matrix cores); returns the number of slabs left in wp
+template <typename T>
+static int t_wgrad_oct(oz_trainer* t, int l, int B, hipStream_t sw, float* wp, int& msplit) {
+    const TLayer& L = t->L[l];
+    const TPacked& k = t->pk[T::PLANES - 2];
+    const unsigned* dzmax = T::SCALED ? t->dzmax + l : nullptr;
+    int* flag = T::SCALED ? t->h2flag : nullptr;
+    const int noct = (B + 7) / 8, XR = L.Hout + 2, tiles = (L.Cin / T::CI) * (L.Co / T::CO), lds = WgradLds<T>::BYTES;
+    const long long wcount = 9LL * L.Cin * L.Co;
+    msplit = 1;
+    while (msplit < 32 && tiles * msplit < 256 && msplit * 2 <= noct && wcount * msplit * 2 <= t->gpartial_floats) msplit *= 2;
+    const long long xthr = (long long)noct * XR * WH_XW * (L.Cin / 4), zthr = (long long)noct * L.Hout * WH_ZW * (L.Co / 4);
+    hipLaunchKernelGGL(k_t_x_octets<T::PLANES>, dim3((unsigned)((xthr + 255) / 256)), dim3(256), 0, sw, t->a[l - 1], t->d_count, L.Hin, L.pad, L.Cin, k.xoct[l]);
+    hipLaunchKernelGGL(k_t_z_octets<T::PLANES>, dim3((unsigned)((zthr + 255) / 256)), dim3(256), 0, sw, t->dz[l], t->d_count, L.Hout, L.Hz, L.zoff, L.Co,
+                       dzmax, k.zoct[l], flag);
+    const WhGeom wg = {XR, L.Hout, L.Cin, L.Co};
+    if constexpr (T::SCALED) {
+        if (int rc = set_max_lds_once<k_wgrad_h2>(lds)) return rc;
+        hipLaunchKernelGGL(k_wgrad_h2, dim3(tiles, msplit), dim3(512), lds, sw, k.xoct[l], k.zoct[l], t->d_count, wg, dzmax, t->grad(6 * l), msplit, wp, wcount);
+    } else {
+        if (int rc = set_max_lds_once<k_wgrad_b3>(lds)) return rc;
+        hipLaunchKernelGGL(k_wgrad_b3, dim3(tiles, msplit), dim3(512), lds, sw, k.xoct[l], k.zoct[l], t->d_count, wg, t->grad(6 * l), msplit, wp, wcount);
+    }
+    return OZ_OK;
+}
+
+// weight gradient of layer l = 1 .. 5 from a[l - 1] and dz[l], on the second stream
+static int t_wgrad(oz_trainer* t, int l, int B) {
+    const TLayer& L = t->L[l];
+    hipStream_t sw = t->s2;
+    float* wp = t->wpartial;
+    OZ_HIP(hipEventRecord(t->ev_dz[l], t->s));
+    OZ_HIP(hipStreamWaitEvent(sw, t->ev_dz[l], 0));
+    const long long wcount = (long long)L.taps * L.Cin * L.Co;
+    // The kernel of the launch.  Dense layers: the tap-per-block fp32 kernel.  3x3 layers: bf16x3 always takes k_wgrad_b3 (no fallback rule); f16x2
+    // takes k_wgrad_h2 from WH_MIN_BATCH boards on; otherwise the board-resident fp32 kernel from 192 boards on, the tap-per-block one below
+    // (measured on one MI355X, 8x8 / 512 filters: the board-resident kernel wins from batch 256 on -- 6.01 vs 6.36 ms per step, 17.0 vs
+    //  19.9 at 1024 -- and loses 3-4 % at 32 .. 128, where the tap-per-block kernel's 144 x 4 short blocks finish sooner)
+    enum { TAPS_F32, BOARDS_F32, OCT_H2, OCT_B3 } kernel = TAPS_F32;
+    if (L.taps == 9) {
+        if (t->mode == 2) kernel = OCT_B3;
+        else if (t->mode == 1 && B >= WH_MIN_BATCH && L.Cin % WgradH2::CI == 0 && L.Co % WgradH2::CO == 0) kernel = OCT_H2;
+        else if (B >= 192 && L.Cin % WC_CI == 0 && L.Co % WC_CO == 0) kernel = BOARDS_F32;
+    }
+    int msplit = 1;
+    switch (kernel) {
+    case OCT_B3: if (int rc = t_wgrad_oct<WgradB3>(t, l, B, sw, wp, msplit)) return rc; break;
+    case OCT_H2: if (int rc = t_wgrad_oct<WgradH2>(t, l, B, sw, wp, msplit)) return rc; break;
+    case BOARDS_F32: {
+        // board-resident kernel: (Cin / 64) x (Cout / 128) tiles, boards split over blockIdx.y until every CU has a block
+        const WconvGeom cg = {L.Hin, L.Hout, L.pad, L.Cin, L.Co, L.Hz, L.zoff};
+        const int tiles = (L.Cin / WC_CI) * (L.Co / WC_CO);
+        while (msplit < 16 && tiles * msplit < 256 && msplit * 2 <= B && wcount * msplit * 2 <= t->gpartial_floats) msplit *= 2;
+        const int XW = L.Hin + 2 * L.pad;
+        const size_t lds_bytes = 2 * sizeof(float) * ((size_t)XW * XW * WC_CI + (size_t)L.P * WC_CO);
+        if (int rc = set_max_lds_once<k_wgrad_conv>(160 * 1024 - 1024)) return rc;
+        hipLaunchKernelGGL(k_wgrad_conv, dim3(tiles, msplit), dim3(512), lds_bytes, sw, t->a[l - 1], t->dz[l], t->d_count, cg, t->grad(6 * l), msplit, wp, wcount);
+        break;
+    }
+    case TAPS_F32: {
+        const WgradGeom g = {L.Hin, L.Hout, L.pad, L.Cin, L.Co, L.taps, L.Hz, L.zoff};
+        const int wblocks = L.taps * (L.Cin / 128) * (L.Co / 128);
+        const long long wtiles = ((long long)B * L.P + 31) / 32;
+        while (msplit < 16 && wblocks * msplit < 512 && wtiles / (msplit * 2) >= 8 && wcount * msplit * 2 <= t->gpartial_floats) msplit *= 2;
+        // (round 5, measured and removed: 3 splits instead of 4 so that 144 tiles x splits stays below 512 blocks -- the launch got SLOWER, 147 -> 227 us on
+        //  conv2: more than two of these 40 KB-LDS blocks share a CU, 576 blocks are one round)
+        hipLaunchKernelGGL(k_wgrad_f32, dim3(wblocks, msplit), dim3(256), 0, sw, t->a[l - 1], t->dz[l], t->d_count, g, t->grad(6 * l), msplit, wp, wcount);
+    }
+    }
+    if (msplit > 1)
+        hipLaunchKernelGGL(k_t_sum_partials, dim3((unsigned)((wcount + 255) / 256)), dim3(256), 0, sw, wp, msplit, wcount, t->grad(6 * l));
+    OZ_HIP(hipGetLastError());
+    return OZ_OK;
+}
+
+// data gradient of layer l = 1 .. 5: dz[l] -> dA = the gradient wrt a[l - 1]
+static int t_dgrad(oz_trainer* t, int l, int B, float* dA) {
+    hipStream_t s = t->s;
+    const TLayer& L = t->L[l];
+    if (l >= 4)            // dense: dX = dZ . W^T; the Keras kernel [in][out] already is the [N = in][K = out] operand
+        return oz_gemm_f32_launch(t->dz[l], t->param(6 * l), t->ones, t->zeros, dA, t->d_count, B, 1, 1, 0, L.Co, 1, L.Cin, 0, s, t->gpartial, t->gpartial_floats);
+    // 3x3 conv: conv of dz (zero-bordered for 'valid' layers) with the reversed, channel-swapped taps
+    const int same = L.pad ? 1 : 0;
+    if (int rc = t_wait_once(s, t->ev_wd, t->wait_wd)) return rc;
+    switch (t->mode) {
+    case 2: {              // bf16x3: dz in the b3 layout, same zero-bordered geometry, unscaled
+        const TPacked& k = t->pk[1];
+        const long long thr = (long long)B * L.P * (L.Co / 8);
+        hipLaunchKernelGGL(k_t_dz_to_b3, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, s, t->dz[l], t->d_count, L.Hout, L.Hz, L.zoff, L.Co, k.dz[l]);
+        return oz_gemm_b3_launch(k.dz[l], k.Wd[l], t->ones, t->zeros, dA, t->d_count, t->Bmax, L.Hz, L.Hin, same, L.Co, 9, L.Cin, 0, s, t->gpartial,
+                                 t->gpartial_floats, t->zeros, 1);
+    }
+    case 1: {              // f16x2: dz scaled into the fp16 range by its own maximum, h2 layout, same zero-bordered geometry
+        const TPacked& k = t->pk[0];
+        long long thr = (long long)B * L.P * (L.Co / 8);
+        if (thr < L.Cin) thr = L.Cin;                      // (the kernel's first Cin threads also write dscale)
+        hipLaunchKernelGGL(k_t_dz_to_h2, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, s, t->dz[l], t->d_count, L.Hout, L.Hz, L.zoff, L.Co,
+                           t->dzmax + l, t->wmax + (l - 1), k.dz[l], t->dscale[l], L.Cin, t->h2flag);
+        return oz_gemm_h2_launch(k.dz[l], k.Wd[l], t->dscale[l], t->zeros, dA, t->d_count, B, L.Hz, L.Hin, same, L.Co, 9, L.Cin, s, t->gpartial,
+                                 t->gpartial_floats, t->zeros, t->h2flag);
+    }
+    default:               // (the non-zero core of the zero-bordered dz buffer: taps that only read the border are skipped at large batch)
+        return oz_gemm_f32_launch(t->dz[l], t->Wd[l], t->ones, t->zeros, dA, t->d_count, B, L.Hz, L.Hin, same, L.Co, 9, L.Cin, 0, s, t->gpartial,
+                                  t->gpartial_floats, 0, L.zoff, L.zoff + L.Hout);
+    }
+}
+
+// forward + backward of the batch staged in d_own / d_opp / d_pit / d_zt / d_count (B boards): gradients land in the arena, the batch-mean
+// losses in t->losses
+static int t_forward_backward_async(oz_trainer* t, int B) {
+    if (t->dirty) if (int rc = t_refresh(t)) return rc;
+    if (int rc = t_forward(t, B)) return rc;
     int cur = 1;                                   // dA[cur] = gradient wrt a[l]
+    if (int rc = t_heads_backward(t, B, t->dA[cur])) return rc;
     for (int l = 5; l >= 0; --l) {
-        bool have_dzmax = false;
-        const int Cc = t->Co[l], P = t->P_[l];
-        const float post = l >= 4 && t->rate > 0.f ? 1.0f / (1.0f - t->rate) : 1.0f;
-        if ((long long)B * P > OZ_BNB_MIN_ROWS && (long long)B * P <= OZ_BNB_MAX_ROWS) {
-            // partial sums over row splits, then one launch that finishes the sums and writes dz (oz_train_fused.h)
-            const long long M = (long long)B * P;
-            const int Q = Cc / 4, lpr = Q < 64 ? Q : 64, rpp = 256 / lpr;
-            int RS = 16; while (RS < OZ_BNB_MAX_RB && M > (long long)RS * rpp * 8) RS *= 2;          // ~8 rows per thread
-            RedArgs r = {}; r.x = t->dA[cur]; r.a = t->a[l]; r.z = t->z[l]; r.mean = t->mean[l]; r.rstd = t->rstd[l]; r.post_scale = post; r.P = P; r.C = Cc;
-            hipLaunchKernelGGL(k_t_colreduce<2>, dim3((Q + 63) / 64, RS), dim3(256), 0, s, r, t->d_count, t->partial);
-            hipLaunchKernelGGL(k_t_bnb_apply, dim3((Q + 63) / 64, RS), dim3(256), 0, s, t->dA[cur], t->a[l], t->z[l], t->mean[l], t->rstd[l], t->param(6 * l + 2),
-                               post, t->d_count, t->Hout[l], Cc, t->Hz[l], t->zoff[l], t->partial, RS, t->dz[l], t->grad(6 * l + 2), t->grad(6 * l + 3), t->bnb2[l],
-                               t->h2 ? t->dzmax + l : (unsigned*)nullptr);
-            have_dzmax = t->h2 != 0;
-            // the bias gradient (column sums of dz) is off the dgrad chain: finished beside it
-            hipStream_t sb = s;
-            if (t->overlap && l > 0) {
-                OZ_HIP(hipEventRecord(t->ev_dz[l], s));
-                OZ_HIP(hipStreamWaitEvent(t->s2, t->ev_dz[l], 0));
-                sb = t->s2;
-            }
-            hipLaunchKernelGGL(k_t_sum_partials, dim3((unsigned)((Cc + 255) / 256)), dim3(256), 0, sb, t->bnb2[l], RS, (long long)Cc, t->grad(6 * l + 1));
-            OZ_HIP(hipGetLastError());
-        } else if ((long long)B * P <= OZ_BN_FUSED_MAX_ROWS) {  // small batch: BN backward, dgamma / dbeta / bias gradient in one launch
-            hipLaunchKernelGGL(k_t_bn_bwd_fused, dim3(Cc / OZ_BN_COLS), dim3(1024), 0, s, t->dA[cur], t->a[l], t->z[l], t->mean[l], t->rstd[l],
-                               t->param(6 * l + 2), post, t->d_count, t->Hout[l], Cc, t->Hz[l], t->zoff[l], t->dz[l], t->grad(6 * l + 2),
-                               t->grad(6 * l + 3), t->grad(6 * l + 1), t->h2 ? t->dzmax + l : (unsigned*)nullptr);
-            have_dzmax = t->h2 != 0;
-            OZ_HIP(hipGetLastError());
-        } else {
-        RedArgs r = {}; r.x = t->dA[cur]; r.a = t->a[l]; r.z = t->z[l]; r.mean = t->mean[l]; r.rstd = t->rstd[l]; r.post_scale = post; r.P = P; r.C = Cc;
-        if (int rc = t_reduce<2>(t, r)) return rc;
-        hipLaunchKernelGGL(k_t_fin_bnbwd, dim3((Cc + 255) / 256), dim3(256), 0, s, t->partial, Cc, t->grad(6 * l + 2), t->grad(6 * l + 3), t->sums);
-        const long long total = (long long)B * P * Cc;
-        hipLaunchKernelGGL(k_t_bn_bwd, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, s, t->dA[cur], t->a[l], t->z[l], t->mean[l], t->rstd[l],
-                           t->param(6 * l + 2), t->sums, post, t->d_count, t->Hout[l], Cc, t->Hz[l], t->zoff[l], t->dz[l]);
-        OZ_HIP(hipGetLastError());
-        // bias gradient = column sums of dz (mathematically 0 behind a training-mode BN; computed like autograd would)
-        RedArgs rb = {}; rb.x = t->dz[l]; rb.P = P; rb.C = Cc; rb.Hout = t->Hout[l]; rb.Hz = t->Hz[l]; rb.zoff = t->zoff[l];
-        if (int rc = t_reduce<3>(t, rb)) return rc;
-        hipLaunchKernelGGL(k_t_fin_colsum, dim3((Cc + 255) / 256), dim3(256), 0, s, t->partial, Cc, t->grad(6 * l + 1));
-        OZ_HIP(hipGetLastError());
-        }
-        // weight gradient
-        if (l == 0) {
-            int S1 = 8;                                    // row splits: ~16 rows per thread (each a dependent ~1 us load at small batch), at most RED_S (the partial buffer's capacity)
-            while (S1 < RED_S && (long long)B * A > 16LL * S1) S1 *= 2;
-            if (n == 8) hipLaunchKernelGGL(k_t_conv1_wgrad<8>, dim3((C + 255) / 256, S1), dim3(256), 0, s, t->d_own, t->d_opp, t->d_count, C, t->cin, t->dz[0], t->partial, S1);
-            else hipLaunchKernelGGL(k_t_conv1_wgrad<6>, dim3((C + 255) / 256, S1), dim3(256), 0, s, t->d_own, t->d_opp, t->d_count, C, t->cin, t->dz[0], t->partial, S1);
-            const long long cnt = 9LL * t->cin * C;
-            hipLaunchKernelGGL(k_t_sum_partials, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, t->partial, S1, cnt, t->grad(0));
-            OZ_HIP(hipGetLastError());
-        } else {
-            WgradGeom g; g.Hin = Hin[l]; g.Hout = t->Hout[l]; g.pad = pad[l]; g.Cin = Cin[l]; g.Cout = Cc; g.taps = taps[l]; g.Hz = t->Hz[l]; g.zoff = t->zoff[l];
-            const int wblocks = taps[l] * (Cin[l] / 128) * (Cc / 128);
-            const long long wcount = (long long)taps[l] * Cin[l] * Cc, wtiles = ((long long)B * P + 31) / 32;
-            int msplit = 1;
-            while (msplit < 16 && wblocks * msplit < 512 && wtiles / (msplit * 2) >= 8 && wcount * msplit * 2 <= t->gpartial_floats) msplit *= 2;
-            // (round 5, measured and removed: 3 splits instead of 4 so that 144 tiles x splits stays below 512 blocks -- the launch got SLOWER, 147 -> 227 us on
-            //  conv2: more than two of these 40 KB-LDS blocks share a CU, 576 blocks are one round)
-            // the weight gradient only needs a[l - 1] and dz[l]: it runs on the second stream beside the data-gradient chain
-            // (dgrad -> BN backward of the layer below -> ...), whose small-batch launches leave most CUs idle
-            hipStream_t sw = s;
-            float* wp = t->gpartial;
-            if (t->overlap) {
-                OZ_HIP(hipEventRecord(t->ev_dz[l], s));
-                OZ_HIP(hipStreamWaitEvent(t->s2, t->ev_dz[l], 0));
-                sw = t->s2; wp = t->wpartial;
-            }
-            // (measured on one MI355X, 8x8 / 512 filters: the board-resident kernel wins from batch 256 on -- 6.01 vs 6.36 ms per step, 17.0 vs
-            //  19.9 at 1024 -- and loses 3-4 % at 32 .. 128, where the tap-per-block kernel's 144 x 4 short blocks finish sooner)
-            const bool wgrad_b3 = taps[l] == 9 && t->b3;
-            const bool wgrad_h2 = taps[l] == 9 && t->h2 && have_dzmax && l >= 1 && B >= WH_MIN_BATCH && Cin[l] % WH_CI == 0 && Cc % WH_CO == 0;
-            if (wgrad_b3 || wgrad_h2) {
-                // octet images of a[l - 1] and dz[l], then the MFMA kernel: bf16x3 three planes on the bf16 matrix cores (six products per fp32
-                // product), f16x2 two planes of the scaled dz on the fp16 matrix cores (three products per fp32 product)
-                const int noct = (B + 7) / 8, XR = t->Hout[l] + 2;
-                const int tiles = (Cin[l] / (wgrad_b3 ? WB_CI : WH_CI)) * (Cc / (wgrad_b3 ? WB_CO : WH_CO));
-                msplit = 1;
-                while (msplit < 32 && tiles * msplit < 256 && msplit * 2 <= noct && wcount * msplit * 2 <= t->gpartial_floats) msplit *= 2;
-                const long long xthr = (long long)noct * XR * WH_XW * (Cin[l] / 4), zthr = (long long)noct * t->Hout[l] * WH_ZW * (Cc / 4);
-                const dim3 xgrid((unsigned)((xthr + 255) / 256)), zgrid((unsigned)((zthr + 255) / 256));
-                WhGeom wg; wg.XR = XR; wg.Hout = t->Hout[l]; wg.Cin = Cin[l]; wg.Cout = Cc;
-                if (wgrad_b3) {
-                    hipLaunchKernelGGL(k_t_x_octets<3>, xgrid, dim3(256), 0, sw, t->a[l - 1], t->d_count, Hin[l], pad[l], Cin[l], t->xt_b3[l]);
-                    hipLaunchKernelGGL(k_t_z_octets<3>, zgrid, dim3(256), 0, sw, t->dz[l], t->d_count, t->Hout[l], t->Hz[l], t->zoff[l], Cc,
-                                       (const unsigned*)nullptr, t->zt_b3[l], (int*)nullptr);
-                    if (!t->wb3_attr) {
-                        OZ_HIP(hipFuncSetAttribute((const void*)k_wgrad_b3, hipFuncAttributeMaxDynamicSharedMemorySize, WB_LDS));
-                        t->wb3_attr = true;
-                    }
-                    hipLaunchKernelGGL(k_wgrad_b3, dim3(tiles, msplit), dim3(512), WB_LDS, sw, t->xt_b3[l], t->zt_b3[l], t->d_count, wg, t->grad(6 * l), msplit, wp, wcount);
-                } else {
-                    hipLaunchKernelGGL(k_t_x_octets<2>, xgrid, dim3(256), 0, sw, t->a[l - 1], t->d_count, Hin[l], pad[l], Cin[l], t->xt_oct[l]);
-                    hipLaunchKernelGGL(k_t_z_octets<2>, zgrid, dim3(256), 0, sw, t->dz[l], t->d_count, t->Hout[l], t->Hz[l], t->zoff[l], Cc,
-                                       t->dzmax + l, t->zt_oct[l], t->h2flag);
-                    if (!t->wh_attr) {
-                        OZ_HIP(hipFuncSetAttribute((const void*)k_wgrad_h2, hipFuncAttributeMaxDynamicSharedMemorySize, WH_LDS));
-                        t->wh_attr = true;
-                    }
-                    hipLaunchKernelGGL(k_wgrad_h2, dim3(tiles, msplit), dim3(512), WH_LDS, sw, t->xt_oct[l], t->zt_oct[l], t->d_count, wg, t->dzmax + l, t->grad(6 * l),
-                                       msplit, wp, wcount);
-                }
-            } else if (taps[l] == 9 && B >= 192 && Cin[l] % WC_CI == 0 && Cc % WC_CO == 0) {
-                // board-resident kernel: (Cin / 64) x (Cout / 128) tiles, boards split over blockIdx.y until every CU has a block
-                WconvGeom cg; cg.Hin = Hin[l]; cg.Hout = t->Hout[l]; cg.pad = pad[l]; cg.Cin = Cin[l]; cg.Cout = Cc; cg.Hz = t->Hz[l]; cg.zoff = t->zoff[l];
-                const int tiles = (Cin[l] / WC_CI) * (Cc / WC_CO);
-                msplit = 1;
-                while (msplit < 16 && tiles * msplit < 256 && msplit * 2 <= B && wcount * msplit * 2 <= t->gpartial_floats) msplit *= 2;
-                const int XW = cg.Hin + 2 * cg.pad;
-                const size_t lds_bytes = 2 * sizeof(float) * ((size_t)XW * XW * WC_CI + (size_t)P * WC_CO);
-                if (!t->wconv_attr) {
-                    OZ_HIP(hipFuncSetAttribute((const void*)k_wgrad_conv, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
-                    t->wconv_attr = true;
-                }
-                hipLaunchKernelGGL(k_wgrad_conv, dim3(tiles, msplit), dim3(512), lds_bytes, sw, t->a[l - 1], t->dz[l], t->d_count, cg, t->grad(6 * l), msplit,
-                                   wp, wcount);
-            } else {
-                hipLaunchKernelGGL(k_wgrad_f32, dim3(wblocks, msplit), dim3(256), 0, sw, t->a[l - 1], t->dz[l], t->d_count, g, t->grad(6 * l), msplit,
-                                   wp, wcount);
-            }
-            if (msplit > 1)
-                hipLaunchKernelGGL(k_t_sum_partials, dim3((unsigned)((wcount + 255) / 256)), dim3(256), 0, sw, wp, msplit, wcount, t->grad(6 * l));
-            OZ_HIP(hipGetLastError());
-            // data gradient -> dA[cur ^ 1] = gradient wrt a[l - 1]
-            if (l >= 4) {          // dense: dX = dZ . W^T; the Keras kernel [in][out] already is the [N = in][K = out] operand
-                if (int rc = oz_gemm_f32_launch(t->dz[l], t->param(6 * l), t->ones, t->zeros, t->dA[cur ^ 1], t->d_count, B, 1, 1, 0, Cc, 1, Cin[l], 0, s, t->gpartial, (t->split_mask & 2) ? t->gpartial_floats : 0)) return rc;
-            } else {               // 3x3 conv: conv of dz (zero-bordered for 'valid' layers) with the reversed, channel-swapped taps
-                const int same = pad[l];
-                if (t->wait_wd) { OZ_HIP(hipStreamWaitEvent(s, t->ev_wd, 0)); t->wait_wd = false; }
-                if (t->b3) {       // bf16x3: dz in the b3 layout, same zero-bordered geometry, unscaled
-                    const long long thr = (long long)B * P * (Cc / 8);
-                    hipLaunchKernelGGL(k_t_dz_to_b3, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, s, t->dz[l], t->d_count, t->Hout[l], t->Hz[l], t->zoff[l], Cc,
-                                       t->dz_b3[l]);
-                    if (int rc = oz_gemm_b3_launch(t->dz_b3[l], t->Wb3d[l], t->ones, t->zeros, t->dA[cur ^ 1], t->d_count, t->Bmax, t->Hz[l], Hin[l], same ? 1 : 0, Cc, 9,
-                                                   Cin[l], 0, s, t->gpartial, t->gpartial_floats, t->zeros, 1)) return rc;
-                } else if (have_dzmax) {  // f16x2: dz scaled into the fp16 range by its own maximum, h2 layout, same zero-bordered geometry
-                    long long thr = (long long)B * P * (Cc / 8);
-                    if (thr < Cin[l]) thr = Cin[l];
-                    hipLaunchKernelGGL(k_t_dz_to_h2, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, s, t->dz[l], t->d_count, t->Hout[l], t->Hz[l], t->zoff[l], Cc,
-                                       t->dzmax + l, t->wmax + (l - 1), t->dz_h2[l], t->dscale[l], Cin[l], t->h2flag);
-                    if (int rc = oz_gemm_h2_launch(t->dz_h2[l], t->Whd[l], t->dscale[l], t->zeros, t->dA[cur ^ 1], t->d_count, B, t->Hz[l], Hin[l], same ? 1 : 0, Cc, 9,
-                                                   Cin[l], s, t->gpartial, t->gpartial_floats, t->zeros, t->h2flag)) return rc;
-                } else if (t->h2) {
-                    oz_set_error("trainer f16x2: no |dz| maximum for layer %d", l);        // (every BN backward path of this mode leaves one)
-                    return OZ_ERR_STATE;
-                } else
-                // (the non-zero core of the zero-bordered dz buffer: taps that only read the border are skipped at large batch)
-                if (int rc = oz_gemm_f32_launch(t->dz[l], t->Wd[l], t->ones, t->zeros, t->dA[cur ^ 1], t->d_count, B, t->Hz[l], Hin[l], same ? 1 : 0, Cc, 9,
-                                                Cin[l], 0, s, t->gpartial, (t->split_mask & 4) ? t->gpartial_floats : 0, 0, t->zoff[l],
-                                                t->zoff[l] + t->Hout[l])) return rc;
-            }
-            cur ^= 1;
-        }
+        if (int rc = t_bn_backward(t, l, B, t->dA[cur])) return rc;
+        if (l == 0) { if (int rc = t_wgrad_conv1(t, B)) return rc; break; }
+        if (int rc = t_wgrad(t, l, B)) return rc;
+        if (int rc = t_dgrad(t, l, B, t->dA[cur ^ 1])) return rc;
+        cur ^= 1;
     }
-    if (t->overlap) {                              // every gradient is complete before the caller (Adam, all-reduce, get_grad) sees the arena
-        OZ_HIP(hipEventRecord(t->ev_w, t->s2));
-        OZ_HIP(hipStreamWaitEvent(s, t->ev_w, 0));
-    }
+    OZ_HIP(hipEventRecord(t->ev_w, t->s2));        // every gradient is complete before the caller (Adam, all-reduce, get_grad) sees the arena
+    OZ_HIP(hipStreamWaitEvent(t->s, t->ev_w, 0));
     return OZ_OK;
 }
 
@@ -1715,8 +1656,7 @@ static int t_apply_locked(oz_trainer* t) {
     t->dirty = true;
     // the operands derived from the new weights are rebuilt now, on the second stream, behind the optimiser step -- not at the next forward's
     // first launch: what the host does between two steps (the next batch's upload) no longer delays them
-    if (t->overlap) return t_refresh(t);
-    return OZ_OK;
+    return t_refresh(t);
 }
 OZ_API int oz_trainer_apply(oz_trainer* t) {
     OZ_REQUIRE(t, "oz_trainer_apply: NULL");
@@ -1728,7 +1668,7 @@ OZ_API int oz_trainer_apply(oz_trainer* t) {
 OZ_API int oz_trainer_get_activation(oz_trainer* t, int layer, int B, float* data, int64_t nelem) {
     OZ_REQUIRE(t && data && layer >= 0 && layer < 6 && B >= 1 && B <= t->Bmax, "oz_trainer_get_activation: bad argument");
     T_LOCK(t);
-    OZ_REQUIRE(nelem == (int64_t)B * t->P_[layer] * t->Co[layer], "oz_trainer_get_activation: expected %lld elements", (long long)B * t->P_[layer] * t->Co[layer]);
+    OZ_REQUIRE(nelem == (int64_t)B * t->L[layer].P * t->L[layer].Co, "oz_trainer_get_activation: expected %lld elements", (long long)B * t->L[layer].P * t->L[layer].Co);
     OZ_HIP(hipSetDevice(t->device));
     OZ_HIP(hipMemcpyAsync(data, t->a[layer], nelem * sizeof(float), hipMemcpyDeviceToHost, t->s));
     OZ_HIP(hipStreamSynchronize(t->s));

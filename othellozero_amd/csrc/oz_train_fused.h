@@ -5,7 +5,8 @@
 // backward path cost ~5 us each for a few microseconds of work.  Here one 1024-thread block owns 16 channels for ALL rows
 // and does the whole layer in one launch: 64 row lanes x 16 columns (C / 16 blocks), every thread walks its rows in order (loads unrolled for
 // memory-level parallelism), the 64 partial sums are combined in a fixed order through LDS (bit-reproducible), the activation stays L2-resident between passes.
-// Used when rows <= OZ_BN_FUSED_MAX_ROWS; larger batches keep the multi-block reductions (bandwidth-bound there).
+// Two regimes each way.  Forward: this kernel up to OZ_BN_FUSED_MAX_ROWS rows, the streaming multi-block reductions of oz_train.hip above
+// (bandwidth-bound there).  Backward: the one-launch kernel up to OZ_BNB_MIN_ROWS rows, k_t_colreduce<2> + k_t_bnb_apply above, whatever the batch.
 #pragma once
 
 #define OZ_BN_FUSED_MAX_ROWS 4096        // (64 boards of 8x8; above that the streaming multi-block reductions win: 32 blocks cannot feed HBM)
@@ -128,8 +129,8 @@ __global__ __launch_bounds__(1024) void k_t_bn_bwd_fused(const float* __restrict
 // kernel: every block finishes the two sums from the RS partials (fixed order; 2 x RS independent 16-byte loads per thread),
 // writes dz for its rows and leaves the column sums of its dz rows in part2[split]; the bias gradient (sum of part2 over the
 // splits, k_t_sum_partials) is not on the data-gradient chain and is finished on the second stream.
-#define OZ_BNB_MIN_ROWS 256                // at most this many rows: the one-launch kernel above (a handful of rows per thread there)
-#define OZ_BNB_MAX_ROWS (1LL << 40)      // (no upper bound: at large batch the same two launches replace five and one pass over dz)
+#define OZ_BNB_MIN_ROWS 256                // at most this many rows: the one-launch kernel above (a handful of rows per thread there); no upper bound on
+                                           // this path (at large batch the same two launches replaced five and one pass over dz)
 #define OZ_BNB_MAX_RB 256
 __global__ __launch_bounds__(256) void k_t_bnb_apply(const float* __restrict__ dA, const float* __restrict__ a, const float* __restrict__ z,
                                                      const float* __restrict__ mean, const float* __restrict__ rstd, const float* __restrict__ gamma,

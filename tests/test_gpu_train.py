@@ -150,6 +150,35 @@ def test_no_dropout_no_clip_and_determinism():
     assert l1 == l2 and all(np.array_equal(g1[i], g2[i]) for i in g1)          # fixed-order reductions: bit-reproducible
 
 
+def test_precision_switch_on_one_trainer_equals_fresh_trainers():
+    """oz_trainer_set_precision 0, 1, 2, 1, 0 on ONE trainer, a forward_backward of the same batch after each call: losses and every gradient are
+    bit-equal to a fresh trainer created in that precision (same seed, same weights).  Pins the packed-operand sets of the two split modes, their
+    lazy allocation and the refresh of the derived operands across modes.  6x6 / 256 filters / batch 33: the smallest shape that reaches
+    k_wgrad_h2 (>= 32 boards), leaves a partly filled octet and has both 'valid' layers; dropout on, no apply(), so the step counter and with it
+    the dropout mask stay fixed."""
+    from othellozero_amd import _lib
+    from othellozero_amd.trainer import PRECISION_MODES, Trainer
+    from othellozero_amd.weights import init_weights
+    n, C, B = 6, 256, 33
+    w = init_weights(n, seed=9, channels=C, randomize_all=True)
+    batch = _batch(n, B, 21)
+    make = lambda precision: Trainer(n, C, 2, max_batch=B, lr=1e-3, clipvalue=0.5, dropout=0.3, seed=13, precision=precision)
+    want = {}
+    for precision, mode in PRECISION_MODES.items():
+        fresh = make(precision)
+        fresh.set_weights(w)
+        want[mode] = (fresh.forward_backward(*batch), fresh.get_grads())
+        del fresh
+    one = make("f32")
+    one.set_weights(w)
+    for mode in (0, 1, 2, 1, 0):
+        _lib.check(_lib.load().oz_trainer_set_precision(one._h, mode))
+        losses, grads = one.forward_backward(*batch), one.get_grads()
+        assert losses == want[mode][0], (mode, losses, want[mode][0])
+        for i, g in grads.items():
+            assert np.array_equal(g, want[mode][1][i]), f"mode {mode}: gradient {i} differs from a fresh trainer's"
+
+
 @pytest.mark.parametrize("precision,C", [("f32", 128), ("f16x2", 256)])
 def test_adam_steps_and_moving_statistics_match(precision, C):
     """Step-locked comparison: at every step the gradients are checked against autograd at the (matched) weights, then

@@ -5,9 +5,10 @@
     python tools/launch_plan_probe.py --plan TRACE > profiles/launch_plan.txt
 
 The first form creates, row by row, a network with seeded random weights (board 6 / 8 x max_batch 1 .. 4096 x the three precisions x the pattern
-tables on / off) and runs one forward at full capacity and one at a ragged count, then one training step at batch 32 and 1024 in the three
-precisions; --out keeps every row's (pi, v) as one .npy.  In front of a row's set-up and of each of its calls it launches the stub evaluator on
-a number of positions that encodes (row, phase), so that the trace says where each begins.  The second form turns the trace into the launches of
+tables on / off) and runs one forward at full capacity and one at a ragged count, then one training step per (board, batch) of TRAIN_SHAPES in
+the three precisions; --out keeps every row's (pi, v) as one .npy and, of a training row, every gradient and every weight after the step as one
+.npz.  In front of a row's set-up and of each of its calls it launches the stub evaluator on a number of positions that encodes (row, phase), so
+that the trace says where each begins.  The second form turns the trace into the launches of
 the calls, in launch order: kernel, grid (threads; `a | b` = the full and the ragged call), workgroup, LDS bytes.  --plan TRACE --full lists
 every launch of the run instead, set-up (commit, calibration) included: what two builds are compared on.
 A change that is meant to leave every launch decision alone leaves both lists alone: diff the first against profiles/launch_plan.txt."""
@@ -23,6 +24,10 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 CHANNELS = 512
 PHASES = 3                                                           # markers per row: set-up, first call, second call
 RAGGED = {32: 27, 128: 108, 512: 430, 1024: 860, 4096: 3640}        # (430 / 3640: the arena's and the bench's batch caps)
+# training steps, in row order (rows are only ever appended: a row keeps its number).  8x8 at 32 / 1024: the reference's batch and a large one;
+# 8: below the f16x2 weight-gradient kernel's smallest batch, one-launch BN both ways; 37: a partly filled octet; 256: the board-resident fp32
+# weight gradient; 6x6 at 64: the second board size
+TRAIN_SHAPES = ((8, 32), (8, 1024), (8, 8), (8, 37), (8, 256), (6, 64))
 
 
 def rows():
@@ -33,9 +38,9 @@ def rows():
             for prec in ("f32", "f16x2", "bf16x3"):
                 for tables in (2, 0):
                     out.append((f"net {n}x{n} max_batch {mb} {prec} tables {tables}", "net", n, mb, prec, tables, [mb] + ([RAGGED[mb]] if mb in RAGGED else [])))
-    for B in (32, 1024):
+    for n, B in TRAIN_SHAPES:
         for prec in ("f32", "f16x2", "bf16x3"):
-            out.append((f"train 8x8 batch {B} {prec}", "train", 8, B, prec, 2, [B]))
+            out.append((f"train {n}x{n} batch {B} {prec}", "train", n, B, prec, 2, [B]))
     return out
 
 
@@ -82,9 +87,13 @@ def run(out_dir):
             marker(i, 1)
             tr.forward_backward(own, opp, pit, rs.choice([-1.0, 1.0], mb).astype(np.float32))
             p, v = tr.outputs(mb)                           # the forward's heads, before the step is applied
+            grads = tr.get_grads()
             tr.apply()
             tr.sync()
             res = np.hstack([p, v[:, None]])
+            if out_dir:
+                np.savez(os.path.join(out_dir, f"row{i:03d}_step.npz"), **{f"grad{k:02d}": g for k, g in grads.items()},
+                         **{f"weight{k:02d}": w for k, w in enumerate(tr.get_weights())})
             del tr
         assert np.isfinite(res).all(), label
         if out_dir:
@@ -127,7 +136,7 @@ def plan(trace_dir, full=False):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default="", help="directory for one .npy of (pi | v) per row")
+    ap.add_argument("--out", default="", help="directory for one .npy of (pi | v) per row (+ one .npz of gradients and stepped weights per training row)")
     ap.add_argument("--plan", default="", help="a rocprofv3 output directory of the probe: print its launch plan and exit")
     ap.add_argument("--full", action="store_true", help="with --plan: every launch of the run, set-up included")
     args = ap.parse_args()
