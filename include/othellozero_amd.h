@@ -42,7 +42,7 @@ extern "C" {
 #define OZ_LEAF_WAIT 3       /* free-running driver with a batch cap: the leaf is chosen and waits for a slot of a later batch */
 
 const char* oz_last_error(void);
-int oz_version(void);                 /* 220 */
+int oz_version(void);                 /* 230 */
 int oz_device_count(void);
 int oz_set_device(int device);       /* device used by objects created afterwards on this thread */
 
@@ -281,6 +281,25 @@ int oz_mcts_sample_root_noise(oz_mcts* m, double alpha, double eps, uint64_t see
 /* what is set: eta[num_games][64], armed[num_games], *eps (each may be NULL); an object that never armed noise reads zeros */
 int oz_mcts_get_root_noise(oz_mcts* m, double* eta /* [num_games][64] */, uint8_t* armed /* [num_games] */, double* eps);
 
+/* ---- move sampling: a ~ N(root, a)^(1/T) for the opening plies, AlphaZero's move rule (opt-in; off, every record stays bit for bit)
+ * The reference plays the arg-max of the root's visit counts, or (coin > e_greedy) a uniformly random legal move.  With move sampling the
+ * greedy branch of the coin draws the move of a game whose ply < plies in proportion to N^(1/T) instead; later plies and the explore branch
+ * are unchanged (pure AlphaZero: e_greedy = 1).  One definition for the engines and for the bare search, on the device, one wave per game,
+ * one lane per square.  With N[sq] the root's visit counts, mx = max N (>= 1), T the temperature and ONE unit draw
+ * u = the library's stream (seed, game id, ply, 4) -- stream 4 is none of the root-noise streams 3 + 256 sq + 65536 i -- in float64, no
+ * contraction, squares in ascending sq = row*8 + col:
+ *     inv     = 1.0 / T
+ *     w[sq]   = N[sq] == 0 ? 0.0 : pow((double)N[sq] / (double)mx, inv)      legal squares only; a max-count square gets exactly 1.0
+ *     cum[sq] = the running sum of w, added one square after the other in ascending order (c = c + w[sq]); the order is part of the definition
+ *     r       = u * c_total                                                  c_total = cum of the last legal square
+ *     action  = the first legal square with cum[sq] > r; if there is none (u * c rounded up to c), the last legal square with w > 0
+ * Dividing by mx keeps pow in (0, 1] for every T.  A square with N == 0 is never chosen; a root with one visited move always plays it.
+ * OZ_ERR_ARG: temperature not in [0.01, 100] (NaN included), plies not in [0, 64]. */
+/* the sampled move of the current roots of the active slots, keyed (seed, game_ids[g], plies[g]): action[g] = the square, or -1 where rc[g] != 0
+ * (rc as oz_mcts_root_counts: 1 unknown root, 2 expanded but never selected from) and on an idle slot */
+int oz_mcts_sample_moves(oz_mcts* m, double temperature, uint64_t seed, const uint64_t* game_ids, const int32_t* plies,
+                         int32_t* action /* [num_games], sq or -1 */, int32_t* rc /* [num_games] */);
+
 /* ------------------------------------------------------------------ self-play
  * execute_episode (training.py:26-72) for num_games concurrent games in lock step. */
 typedef struct oz_selfplay oz_selfplay;
@@ -321,7 +340,8 @@ typedef struct {
     uint8_t action;         /* sq = row*8+col */
     int8_t player;          /* mover: +1 BLACK, -1 WHITE */
     int8_t z;               /* +1 if winner == mover else -1 (draw -> BLACK wins) */
-    uint8_t greedy;         /* 1 = greedy branch of the coin */
+    uint8_t greedy;         /* 1 = greedy branch of the coin (arg-max), 0 = explore branch (uniform legal move), 2 = greedy branch, move
+                             * drawn by move sampling (oz_selfplay_set_move_sampling; ply < plies) */
     uint8_t pad[3];
 } oz_record;
 
@@ -362,6 +382,11 @@ int oz_selfplay_set_leaves_per_step(oz_selfplay* sp, int k);
 int oz_selfplay_set_root_noise(oz_selfplay* sp, double alpha, double eps);
 /* the noise of the searches of the last move round of oz_selfplay_run (tests; eta[num_games][64], armed[num_games]) */
 int oz_selfplay_root_noise(oz_selfplay* sp, double* eta, uint8_t* armed);
+/* self-play with move sampling ("move sampling" above): the coin is drawn as ever; where it falls on the greedy branch, the move of a game
+ * whose ply < plies is sampled, keyed (cfg.seed, game id, ply), and its record has greedy = 2.  Holds for oz_selfplay_run, the free-running
+ * oz_selfplay_run_steps (whose records stay exactly those of oz_selfplay_run), oz_selfplay_stagger and leaves_per_step > 1; the arena and the
+ * evaluation games never sample.  Before the first driver call (OZ_ERR_STATE afterwards).  plies == 0 disarms; nothing is allocated. */
+int oz_selfplay_set_move_sampling(oz_selfplay* sp, double temperature, int plies);
 int oz_selfplay_sync(oz_selfplay* sp);
 /* continuous self-play (cfg.refill): bring a fresh engine to the steady state of a long-running one before measuring it --
  * slot g is advanced (g * P) / num_games plies into its first game, P = n*n - 4, by searched self-play moves at `sims_pre`

@@ -114,6 +114,8 @@ SIGNATURES = {
     "oz_mcts_sample_root_noise": [_vp, C.c_double, C.c_double, C.c_uint64, _u64p, _i32p],
     "oz_mcts_get_root_noise": [_vp, _f64p, _u8p, _f64p],
     "oz_selfplay_set_root_noise": [_vp, C.c_double, C.c_double], "oz_selfplay_root_noise": [_vp, _f64p, _u8p],
+    "oz_mcts_sample_moves": [_vp, C.c_double, C.c_uint64, _u64p, _i32p, _i32p, _i32p],
+    "oz_selfplay_set_move_sampling": [_vp, C.c_double, C.c_int],
     "oz_selfplay_create": [C.POINTER(_vp), C.POINTER(SelfplayConfig), _vp],
     "oz_selfplay_destroy": [_vp], "oz_selfplay_run": [_vp, C.c_int], "oz_selfplay_run_steps": [_vp, C.c_int], "oz_selfplay_sync": [_vp],
     "oz_selfplay_stagger": [_vp, C.c_int], "oz_selfplay_profile": [_vp, C.c_int], "oz_selfplay_set_batch_cap": [_vp, C.c_int], "oz_selfplay_set_dedup": [_vp, C.c_int],
@@ -286,6 +288,27 @@ def check_root_noise(root_noise):
     if not 0.0 <= eps <= 1.0:
         raise ValueError(f"root_noise: epsilon must be in [0, 1] (got {eps})")
     return alpha, eps
+
+
+def check_sample_moves(sample_moves):
+    """sample_moves = None or (temperature, plies): the greedy branch of the self-play coin draws the move of the first `plies` plies in
+    proportion to N ** (1 / temperature) instead of taking the arg-max.  Returns None or (float, int); ValueError for anything the library
+    would refuse (temperature in [0.01, 100], plies a whole number in [0, 64])."""
+    if sample_moves is None:
+        return None
+    try:
+        temperature, plies = sample_moves
+        temperature = float(temperature)
+        if isinstance(plies, bool) or int(plies) != plies:
+            raise ValueError
+        plies = int(plies)
+    except (TypeError, ValueError):
+        raise ValueError(f"sample_moves must be None or (temperature, plies), got {sample_moves!r}") from None
+    if not 0.01 <= temperature <= 100.0:
+        raise ValueError(f"sample_moves: temperature must be in [0.01, 100] (got {temperature})")
+    if not 0 <= plies <= 64:
+        raise ValueError(f"sample_moves: plies must be in [0, 64] (got {plies})")
+    return temperature, plies
 
 
 def check(rc):

@@ -256,6 +256,38 @@ template <bool NOISE> __device__ __forceinline__ bool noise_of_slot(const MctsDe
     return false;
 }
 
+// ---------------------------------------------------------------- move sampling: a ~ N(root, a)^(1/T) for the opening plies (opt-in, AlphaZero's move rule)
+// (the definition is stated in include/othellozero_amd.h, "move sampling"; the restatement the tests hold this against is tests/move_sampling_ref.py.)
+// One wave = one game, lane = square.  cnt = the root's visit count of this lane's square, mx = their maximum (>= 1), legal uniform, u = the unit
+// draw of stream (seed, game id, ply, OZ_RNG_SAMPLE).  All float64, no contraction:
+//     w[sq] = N[sq] == 0 ? 0.0 : pow((double)N[sq] / (double)mx, 1.0 / T)     legal squares only; in (0, 1] for every T, exactly 1.0 at the maximum
+//     cum[sq] = the running sum of w over the legal squares in ascending sq, ONE ADDITION AFTER THE OTHER (c = c + w[sq]): the order is part of the
+//     definition, so this is a 64-step lane loop and not a tree scan (nothing next to the `sims` simulations of a move)
+//     r = u * c_total;  action = the first legal square with cum[sq] > r, else (u * c rounded up to c) the last legal square with w > 0
+// A square with N == 0 adds 0.0 and its cum equals its predecessor's: never chosen.  -1: no visited legal square (the callers exclude it).
+struct MoveSampling { double temperature; int plies; };    // plies == 0: off
+__device__ __forceinline__ double lane_get_f64(double x, int lane) {      // lane must be uniform
+    const long long b = __double_as_longlong(x);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)b, lane), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(b >> 32), lane);
+    return __longlong_as_double((long long)(((uint64_t)hi << 32) | (uint64_t)lo));
+}
+__device__ __forceinline__ int sample_move(int cnt, uint64_t legal, int mx, double temperature, double u, int lane) {
+    const bool is_legal = (legal >> lane) & 1;
+    const double inv = 1.0 / temperature;
+    const double w = (is_legal && cnt != 0) ? pow((double)cnt / (double)mx, inv) : 0.0;
+    double c = 0.0, cum = 0.0;
+    for (int sq = 0; sq < 64; ++sq) {
+        if (!((legal >> sq) & 1)) continue;
+        c = c + lane_get_f64(w, sq);
+        if (lane == sq) cum = c;
+    }
+    const double r = u * c;
+    const uint64_t over = __ballot(is_legal && cum > r);
+    if (over) return oz_ctz(over);
+    const uint64_t visited = __ballot(is_legal && w > 0.0);
+    return visited ? 63 - __builtin_clzll(visited) : -1;
+}
+
 // ---------------------------------------------------------------- K4: select / descend
 // MCTS.simulate down to the first terminal or unexpanded state (MCTS/__init__.py:39-44,58-67),
 // get_next_state (othelo_mcts.py:43-49).  One wave per game; per level ONE wave-wide load stages the node's record in LDS.
@@ -917,7 +949,7 @@ struct oz_mcts {
     bool wide() const { return leaves_per_step > 1 || use_wide; }
     // root noise: true from the first arming on (d.noise_eta / d.noise_armed are then allocated): the descents run on the *_n kernels
     bool noise_ever = false;
-    uint64_t* noise_ids = nullptr; int32_t* noise_plies = nullptr;      // staging of oz_mcts_sample_root_noise's keys, [G] each
+    uint64_t* noise_ids = nullptr; int32_t* noise_plies = nullptr;      // staging of the keys of oz_mcts_sample_root_noise / oz_mcts_sample_moves, [G] each
 
     template <typename T> int alloc(T** p, size_t count) {
         OZ_HIP(hipMalloc((void**)p, sizeof(T) * (count ? count : 1)));
@@ -1342,6 +1374,17 @@ OZ_API int oz_mcts_set_root_noise(oz_mcts* m, double eps, const double* eta, con
     m->d.noise_eps = eps;
     return OZ_OK;
 }
+// the (game id, ply) keys of oz_mcts_sample_root_noise / oz_mcts_sample_moves, on the device (allocated at the first use)
+static int stage_keys(oz_mcts* m, const uint64_t* game_ids, const int32_t* plies) {
+    const int G = m->d.G;
+    if (!m->noise_ids) {
+        if (int rc = m->alloc(&m->noise_ids, (size_t)G)) return rc;
+        if (int rc = m->alloc(&m->noise_plies, (size_t)G)) return rc;
+    }
+    OZ_HIP(hipMemcpyAsync(m->noise_ids, game_ids, 8ull * G, hipMemcpyHostToDevice, m->stream));
+    OZ_HIP(hipMemcpyAsync(m->noise_plies, plies, 4ull * G, hipMemcpyHostToDevice, m->stream));
+    return OZ_OK;
+}
 OZ_API int oz_mcts_sample_root_noise(oz_mcts* m, double alpha, double eps, uint64_t seed, const uint64_t* game_ids, const int32_t* plies) {
     OZ_REQUIRE(m && game_ids && plies, "null argument");
     if (int rc = noise_check("oz_mcts_sample_root_noise", alpha, eps, true)) return rc;
@@ -1352,12 +1395,7 @@ OZ_API int oz_mcts_sample_root_noise(oz_mcts* m, double alpha, double eps, uint6
     const int G = m->d.G;
     for (int i = 0; i < G; ++i) OZ_REQUIRE(plies[i] >= 0, "oz_mcts_sample_root_noise: plies[%d] = %d", i, plies[i]);
     if (int rc = noise_alloc(m)) return rc;
-    if (!m->noise_ids) {
-        if (int rc = m->alloc(&m->noise_ids, (size_t)G)) return rc;
-        if (int rc = m->alloc(&m->noise_plies, (size_t)G)) return rc;
-    }
-    OZ_HIP(hipMemcpyAsync(m->noise_ids, game_ids, 8ull * G, hipMemcpyHostToDevice, m->stream));
-    OZ_HIP(hipMemcpyAsync(m->noise_plies, plies, 4ull * G, hipMemcpyHostToDevice, m->stream));
+    if (int rc = stage_keys(m, game_ids, plies)) return rc;
     hipLaunchKernelGGL(k_root_noise, dim3(G), dim3(64), 0, m->stream, m->d, alpha, seed, (const uint64_t*)m->noise_ids, (const int*)m->noise_plies);
     OZ_HIP(hipGetLastError());
     OZ_HIP(hipStreamSynchronize(m->stream));
@@ -1466,6 +1504,46 @@ OZ_API int oz_mcts_root_counts(oz_mcts* m, int32_t* counts, uint64_t* legal, int
     hipLaunchKernelGGL(k_root_counts, dim3(G), dim3(64), 0, m->stream, m->d, dc, dl, dr);
     OZ_HIP(hipMemcpyAsync(counts, dc, 4ull * G * 64, hipMemcpyDeviceToHost, m->stream));
     OZ_HIP(hipMemcpyAsync(legal, dl, 8ull * G, hipMemcpyDeviceToHost, m->stream));
+    OZ_HIP(hipMemcpyAsync(rc, dr, 4ull * G, hipMemcpyDeviceToHost, m->stream));
+    OZ_HIP(hipStreamSynchronize(m->stream));
+    return OZ_OK;
+}
+
+// move sampling on the current roots of the active slots (the drop-in path's move rule: the engine's sample_move, the same keys).
+// action[g] = the sampled square; -1 where rc[g] != 0 (rc as k_root_counts) and on an idle slot.
+__global__ __launch_bounds__(64) void k_sample_moves(MctsDev t, double temperature, uint64_t seed, const uint64_t* __restrict__ game_ids,
+                                                     const int* __restrict__ plies, int32_t* action_out, int32_t* rc_out) {
+    const int g = blockIdx.x, lane = threadIdx.x;
+    const uint64_t own = uni64(t.root_own[g]), opp = uni64(t.root_opp[g]);
+    const uint64_t legal = oz_legal(own, opp, t.valid);
+    const int node = root_lookup(t, g, own, opp, lane);
+    int cnt = 0, rc = 0, action = -1;
+    if (node < 0) rc = 1;
+    else if (*rec_Ns(t, g, node) == 0) rc = 2;
+    else if ((legal >> lane) & 1)
+        cnt = (int)(rec_edge(t, g, node, oz_popc(legal & ((1ULL << lane) - 1ULL)))->n_tag & ~OZ_TAG_F32);
+    rc = unii(rc);
+    const int mx = unii(wave_max_i32(cnt));
+    if (rc == 0 && mx >= 1 && t.active[g])
+        action = sample_move(cnt, legal, mx, temperature, oz_rng_unit(oz_rng(seed, uni64(game_ids[g]), (uint64_t)unii(plies[g]), OZ_RNG_SAMPLE)), lane);
+    if (lane == 0) { action_out[g] = action; rc_out[g] = rc; }
+}
+static int sample_check(const char* fn, double temperature) {
+    OZ_REQUIRE(temperature >= 0.01 && temperature <= 100.0, "%s: temperature %g outside [0.01, 100]", fn, temperature);     // (NaN fails both compares)
+    return OZ_OK;
+}
+OZ_API int oz_mcts_sample_moves(oz_mcts* m, double temperature, uint64_t seed, const uint64_t* game_ids, const int32_t* plies, int32_t* action, int32_t* rc) {
+    OZ_REQUIRE(m && game_ids && plies && action && rc, "null argument");
+    if (int r = sample_check("oz_mcts_sample_moves", temperature)) return r;
+    std::lock_guard<std::mutex> lk(m->mu);
+    hipSetDevice(m->device);
+    const int G = m->d.G;
+    for (int i = 0; i < G; ++i) OZ_REQUIRE(plies[i] >= 0, "oz_mcts_sample_moves: plies[%d] = %d", i, plies[i]);
+    if (int r = stage_keys(m, game_ids, plies)) return r;
+    int32_t* da = m->rc_counts; int32_t* dr = m->rc_rc;           // (the staging of oz_mcts_root_counts: [G][64] and [G])
+    hipLaunchKernelGGL(k_sample_moves, dim3(G), dim3(64), 0, m->stream, m->d, temperature, seed, (const uint64_t*)m->noise_ids, (const int*)m->noise_plies, da, dr);
+    OZ_HIP(hipGetLastError());
+    OZ_HIP(hipMemcpyAsync(action, da, 4ull * G, hipMemcpyDeviceToHost, m->stream));
     OZ_HIP(hipMemcpyAsync(rc, dr, 4ull * G, hipMemcpyDeviceToHost, m->stream));
     OZ_HIP(hipStreamSynchronize(m->stream));
     return OZ_OK;
@@ -1623,11 +1701,13 @@ __global__ void k_sp_roots_stagger(GamesDev gm, MctsDev t, int round, int period
 //   arena != 0: agents.py semantics (temperature 0, argmax over valid actions of the one-hot).
 // NOISE (the free-running advance of an engine with root noise): the move takes the slot to another root -- its noise is dropped, the advance
 // draws the next root's.  The lock-step k_sp_move leaves root and noise as they are until the next round's roots kernel (oz_selfplay_root_noise
-// reads them in between).
-template <bool NOISE = false>
-__device__ __forceinline__ void sp_move_body(const GamesDev& gm, const MctsDev& t, int g, int lane, int arena) {
+// reads them in between).  (noise_armed is null on an engine whose only extra is move sampling.)
+// SAMPLE (an engine with move sampling, oz_selfplay_set_move_sampling): where the coin falls on the greedy branch and ply < ms.plies, the move is
+// drawn by sample_move, keyed (seed, game id, ply), instead of taken as the arg-max; greedy = 2 in its record.  Never in the arena.
+template <bool NOISE = false, bool SAMPLE = false>
+__device__ __forceinline__ void sp_move_body(const GamesDev& gm, const MctsDev& t, int g, int lane, int arena, MoveSampling ms = MoveSampling{}) {
     if (!t.active[g]) return;
-    if constexpr (NOISE) { if (lane == 0) t.noise_armed[g] = 0; }
+    if constexpr (NOISE) { if (lane == 0 && t.noise_armed) t.noise_armed[g] = 0; }
     const uint64_t own = uni64(t.root_own[g]), opp = uni64(t.root_opp[g]);
     const uint64_t legal = oz_legal(own, opp, t.valid);
     const int node = root_lookup(t, g, own, opp, lane);
@@ -1658,6 +1738,11 @@ __device__ __forceinline__ void sp_move_body(const GamesDev& gm, const MctsDev& 
         if (!(coin <= gm.e_greedy)) {                      // training.py:53-56
             greedy = 0;
             action = oz_kth_bit(legal, (int)(oz_rng(gm.seed, gid, (uint64_t)ply, OZ_RNG_EXPLORE) % (uint64_t)oz_popc(legal)));
+        } else if constexpr (SAMPLE) {
+            if (ply < ms.plies) {
+                greedy = 2;
+                action = sample_move(cnt, legal, mx, ms.temperature, oz_rng_unit(oz_rng(gm.seed, gid, (uint64_t)ply, OZ_RNG_SAMPLE)), lane);
+            }
         }
     }
     uint64_t black = uni64(gm.black[g]), white = uni64(gm.white[g]);
@@ -1719,6 +1804,8 @@ __device__ __forceinline__ void sp_move_body(const GamesDev& gm, const MctsDev& 
     }
 }
 __global__ __launch_bounds__(64) void k_sp_move(GamesDev gm, MctsDev t, int arena) { sp_move_body(gm, t, blockIdx.x, threadIdx.x, arena); }
+// the self-play move of an engine with move sampling (lock-step rounds; the arena keeps k_sp_move)
+__global__ __launch_bounds__(64) void k_sp_move_s(GamesDev gm, MctsDev t, MoveSampling ms) { sp_move_body<false, true>(gm, t, blockIdx.x, threadIdx.x, 0, ms); }
 
 // ---------------------------------------------------------------- free-running self-play step
 // The lock-step driver gives every game one simulation per step; simulations that end on a finished board need no
@@ -1735,12 +1822,15 @@ __global__ __launch_bounds__(64) void k_sp_move(GamesDev gm, MctsDev t, int aren
 // (bench.py --driver free): cap 24 -> 4081 leaves per batch but 367 us per launch, 1.40 M expansions/s; cap 8 -> 1.56 M;
 // cap 4 -> 1.585 M; cap 2 -> 3908 leaves per batch, 1.59 M (1.60 M with k_backup_advance; the lock-step driver: 1.56-1.58 M).
 #define OZ_ADVANCE_CAP 2
-// NOISE: the root noise of a game's root is drawn here, before the first descent from it (noise_armed[g] == 0: a fresh engine, or the move above
-// has just changed the root), keyed (seed, game id, ply) like k_root_noise in the lock-step round: the records stay those of oz_selfplay_run.
-struct NoiseDraw { double alpha; uint64_t seed; };
-template <bool NOISE = false>
+// EXTRAS: the one instantiation for engines with root noise, move sampling or both; which of them is on is looked at when it runs
+// (t.noise_eps > 0, xt.sample.plies > 0).  An engine with neither launches the EXTRAS = false kernels, which are the code they were before.
+//   root noise: the noise of a game's root is drawn here, before the first descent from it (noise_armed[g] == 0: a fresh engine, or the move above
+//   has just changed the root), keyed (seed, game id, ply) like k_root_noise in the lock-step round: the records stay those of oz_selfplay_run.
+//   move sampling: sp_move_body<.., SAMPLE> is a function of the root's counts and (seed, game id, ply): the same records again.
+struct SelfplayExtras { double alpha; uint64_t seed; MoveSampling sample; };
+template <bool EXTRAS = false>
 __device__ __forceinline__ void advance_body(const GamesDev& gm, const MctsDev& t, TreeLds& L, int g, int lane, int sims, int* __restrict__ sims_done, int cap,
-                                             NoiseDraw nz = NoiseDraw{}) {
+                                             SelfplayExtras xt = SelfplayExtras{}) {
     if (unii(t.leaf_status[g]) == OZ_LEAF_WAIT) {          // batch cap: the leaf of the simulation in progress found no slot -- offer it again, unchanged
         if (lane == 0) t.leaf_status[g] = OZ_LEAF_EVAL;
         return;
@@ -1759,19 +1849,19 @@ __device__ __forceinline__ void advance_body(const GamesDev& gm, const MctsDev& 
         }
         wave_sync();                                       // lane 0's stores are visible to the wave's next loads
         if (done >= sims) {                                // training.py:42-67: the move after num_simulations simulations
-            sp_move_body<NOISE>(gm, t, g, lane, 0);
+            sp_move_body<EXTRAS, EXTRAS>(gm, t, g, lane, 0, xt.sample);
             done = 0;
             if (lane == 0) t.leaf_status[g] = OZ_LEAF_IDLE;    // the evaluated leaf is consumed: nothing pending if the cap ends the loop here
             wave_sync();
             continue;                                      // (a finished game is refilled by the move, or goes idle above)
         }
-        if constexpr (NOISE) {
+        if constexpr (EXTRAS) {
             if (t.noise_eps > 0.0 && unii((int)t.noise_armed[g]) == 0) {
-                root_noise_body(t, L.arr, g, lane, uni64(t.root_own[g]), uni64(t.root_opp[g]), nz.alpha, nz.seed, uni64(gm.game_id[g]), unii(gm.ply[g]));
+                root_noise_body(t, L.arr, g, lane, uni64(t.root_own[g]), uni64(t.root_opp[g]), xt.alpha, xt.seed, uni64(gm.game_id[g]), unii(gm.ply[g]));
                 wave_sync();
             }
         }
-        status = select_body<NOISE>(t, L, g, lane);
+        status = select_body<EXTRAS>(t, L, g, lane);
         if (status != OZ_LEAF_TERMINAL) break;             // EVAL: wait for the network; IDLE: error path
         wave_sync();
         backup_body(t, g, lane, (double)t.term_value[g], VT_INT);
@@ -1796,16 +1886,17 @@ __global__ __launch_bounds__(64) void k_backup_advance(GamesDev gm, MctsDev t, i
     advance_body(gm, t, L, blockIdx.x, threadIdx.x, sims, sims_done, cap);
 }
 
-__global__ __launch_bounds__(64) void k_advance_n(GamesDev gm, MctsDev t, int sims, int* __restrict__ sims_done, int cap, NoiseDraw nz) {
+// (the *_x kernels: the same kernels over the EXTRAS = true bodies, launched by engines with root noise or move sampling)
+__global__ __launch_bounds__(64) void k_advance_x(GamesDev gm, MctsDev t, int sims, int* __restrict__ sims_done, int cap, SelfplayExtras xt) {
     __shared__ TreeLds L;
-    advance_body<true>(gm, t, L, blockIdx.x, threadIdx.x, sims, sims_done, cap, nz);
+    advance_body<true>(gm, t, L, blockIdx.x, threadIdx.x, sims, sims_done, cap, xt);
 }
-__global__ __launch_bounds__(64) void k_backup_advance_n(GamesDev gm, MctsDev t, int sims, int* __restrict__ sims_done, int cap, NoiseDraw nz) {
+__global__ __launch_bounds__(64) void k_backup_advance_x(GamesDev gm, MctsDev t, int sims, int* __restrict__ sims_done, int cap, SelfplayExtras xt) {
     __shared__ TreeLds L;
     expand_backup_body(t, L, blockIdx.x, threadIdx.x, 0);
     wave_sync();
     __syncthreads();
-    advance_body<true>(gm, t, L, blockIdx.x, threadIdx.x, sims, sims_done, cap, nz);
+    advance_body<true>(gm, t, L, blockIdx.x, threadIdx.x, sims, sims_done, cap, xt);
 }
 
 // RandomOthelloAgent.play (agents.py:20-24) for every live game whose mover is `side`: random.choice over the valid
@@ -1847,6 +1938,7 @@ struct oz_selfplay {
     int stagger_period = 0;
     bool noise_on = false;           // oz_selfplay_set_root_noise: every searched move draws Dir(noise_alpha) at its root
     double noise_alpha = 0.0;
+    MoveSampling sample{0.0, 0};     // oz_selfplay_set_move_sampling: plies > 0 = on
     std::vector<void*> allocs;
     std::mutex mu;
     long long records_read = 0;
@@ -1958,7 +2050,10 @@ static int selfplay_round_async(oz_selfplay* sp, int sims, int stagger_round) {
         if (sp->noise_on) hipLaunchKernelGGL(k_root_noise, dim3(G), dim3(64), 0, s, m->d, sp->noise_alpha, sp->gm.seed, (const uint64_t*)sp->gm.game_id, (const int*)sp->gm.ply);
     });
     if (int rc = mcts_steps_async(m, sp->net, sims, G, true)) return rc;
-    timed(m, TS_MOVE, m->profile, [&] { hipLaunchKernelGGL(k_sp_move, dim3(G), dim3(64), 0, s, sp->gm, m->d, 0); });
+    timed(m, TS_MOVE, m->profile, [&] {
+        if (sp->sample.plies > 0) hipLaunchKernelGGL(k_sp_move_s, dim3(G), dim3(64), 0, s, sp->gm, m->d, sp->sample);
+        else hipLaunchKernelGGL(k_sp_move, dim3(G), dim3(64), 0, s, sp->gm, m->d, 0);
+    });
     OZ_HIP(hipGetLastError());
     if (m->timer.backlog() > 4096) m->timer.drain();      // completed pairs only: never a host stall inside the enqueue loop
     return OZ_OK;
@@ -2046,6 +2141,17 @@ OZ_API int oz_selfplay_set_root_noise(oz_selfplay* sp, double alpha, double eps)
     sp->noise_alpha = alpha; sp->noise_on = true;
     return OZ_OK;
 }
+// move sampling for the self-play moves of the engine (lock-step rounds, oz_selfplay_stagger's included, at any leaves_per_step, and the
+// free-running driver); before the first driver call.  plies == 0 disarms; nothing is allocated either way.
+OZ_API int oz_selfplay_set_move_sampling(oz_selfplay* sp, double temperature, int plies) {
+    OZ_REQUIRE(sp, "null selfplay");
+    if (int rc = sample_check("oz_selfplay_set_move_sampling", temperature)) return rc;
+    OZ_REQUIRE(plies >= 0 && plies <= 64, "oz_selfplay_set_move_sampling: plies %d outside [0, 64]", plies);
+    std::lock_guard<std::mutex> lk(sp->mu);
+    if (sp->mode != 0) { oz_set_error("oz_selfplay_set_move_sampling: the engine has been driven already (set it before the first driver call)"); return OZ_ERR_STATE; }
+    sp->sample = MoveSampling{plies > 0 ? temperature : 0.0, plies};
+    return OZ_OK;
+}
 OZ_API int oz_selfplay_root_noise(oz_selfplay* sp, double* eta, uint8_t* armed) {
     OZ_REQUIRE(sp, "null selfplay");
     std::lock_guard<std::mutex> lk(sp->mu);
@@ -2079,10 +2185,10 @@ OZ_API int oz_selfplay_run_steps(oz_selfplay* sp, int steps) {
         const int adv_cap = (sp->batch_cap > 0 && sp->batch_cap < d.G ? 1 : OZ_ADVANCE_CAP);
         // (from the second batch of a call on, the previous batch's expand + backup rides in the same launch; one closing k_expand_backup per call)
         timed(m, TS_SELECT, all, [&] {
-            if (m->noise_ever) {
-                const NoiseDraw nz{sp->noise_alpha, sp->gm.seed};
-                if (fuse && i > 0) hipLaunchKernelGGL(k_backup_advance_n, dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap, nz);
-                else hipLaunchKernelGGL(k_advance_n, dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap, nz);
+            if (m->noise_ever || sp->sample.plies > 0) {
+                const SelfplayExtras xt{sp->noise_alpha, sp->gm.seed, sp->sample};
+                if (fuse && i > 0) hipLaunchKernelGGL(k_backup_advance_x, dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap, xt);
+                else hipLaunchKernelGGL(k_advance_x, dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap, xt);
             } else if (fuse && i > 0) hipLaunchKernelGGL(k_backup_advance, dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap);
             else hipLaunchKernelGGL(k_advance, dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap);
         });

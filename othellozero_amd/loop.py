@@ -174,7 +174,7 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
              self_play_interval, self_play_total_games, self_play_threshold, checkpoint_filepath, training_buffer_size,
              seed=1234, reference_aliasing=True, alias_final_boards=True, dump_examples=False, q_mode=_lib.QMODE_F64,
              distributed=False, batched_evaluation=False, policy_target="onehot", target_temperature=1.0, leaves_per_step=1,
-             root_noise=None):
+             root_noise=None, sample_moves=None):
     """main.py:56-259 on the GPU engines; returns `historic` = [(episodes done, win rate vs random), ...]
 
     batched_evaluation=True plays the evaluation games against RandomOthelloAgent in lock step on the GPU
@@ -195,8 +195,13 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
     batch under virtual loss; the networks need max_batch >= games * leaves_per_step.  The drop-in evaluation agents keep 1.
 
     root_noise=(alpha, epsilon): Dirichlet noise on the root prior of every searched SELF-PLAY move (SelfPlayEngine), in the single-process and
-    the distributed path alike; matches and evaluations stay noise-free."""
+    the distributed path alike; matches and evaluations stay noise-free.
+
+    sample_moves=(temperature, plies): where the e_greedy coin falls on the greedy branch, the SELF-PLAY move of a game's first `plies`
+    plies is drawn in proportion to N ** (1 / temperature) instead of taken as the arg-max (SelfPlayEngine), in both paths; matches and
+    evaluations never sample.  Pure AlphaZero is e_greedy = 1.  temperature_threshold keeps its meaning."""
     root_noise = _lib.check_root_noise(root_noise)
+    sample_moves = _lib.check_sample_moves(sample_moves)
     if policy_target not in ("onehot", "visits"):
         raise ValueError(f"policy_target must be 'onehot' or 'visits' (got {policy_target!r})")
     visits = policy_target == "visits"
@@ -244,7 +249,7 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
             first, count = shard_games(num_episodes, rank, world)
             eng = SelfPlayEngine(neural_network, board_size, count, num_simulations, degree_exploration, temperature, e_greedy,
                                  seed=seed, first_game_id=total_episodes_done + first, q_mode=q_mode, record_visits=visits,
-                                 leaves_per_step=leaves_per_step, root_noise=root_noise)
+                                 leaves_per_step=leaves_per_step, root_noise=root_noise, sample_moves=sample_moves)
             eng.play_to_end()
             records = pooled_selfplay_records(eng, device, with_visits=visits)      # the only exchange of the self-play phase
             del eng
@@ -252,7 +257,7 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
             records = selfplay_batch(neural_network, board_size, num_games=num_episodes, num_simulations=num_simulations,
                                      degree_exploration=degree_exploration, policy_temperature=temperature, e_greedy=e_greedy,
                                      seed=seed, first_game_id=total_episodes_done, q_mode=q_mode, record_visits=visits,
-                                     leaves_per_step=leaves_per_step, root_noise=root_noise)
+                                     leaves_per_step=leaves_per_step, root_noise=root_noise, sample_moves=sample_moves)
         counts = None
         if visits:
             records, counts = records

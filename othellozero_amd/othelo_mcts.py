@@ -110,6 +110,22 @@ class OthelloMCTS:
         _lib.check(_lib.load().oz_mcts_get_root_noise(self._h, _lib.p_f64(eta), _lib.p_u8(armed), C.byref(eps)))
         return eta[0], bool(armed[0]), eps.value
 
+    # ---- move sampling (include/othellozero_amd.h, "move sampling"): the engines' move rule for the opening plies, on the bare search
+    def sample_action(self, state, temperature, seed, game_id, ply):
+        """the move drawn in proportion to N ** (1 / temperature) over the visit counts of the mover-canonical `state` (as
+        get_policy_action_probabilities takes it), keyed (seed, game_id, ply): (row, col).  KeyError if the state is unknown or was never
+        selected from."""
+        temperature, _ = _lib.check_sample_moves((temperature, 0))
+        own, opp = _lib.pack_board(state)
+        self._set_root(own, opp)
+        gid, pl = np.array([int(game_id)], np.uint64), np.array([int(ply)], np.int32)
+        action, rc = np.zeros(1, np.int32), np.zeros(1, np.int32)
+        _lib.check(_lib.load().oz_mcts_sample_moves(self._h, temperature, int(seed), _lib.p_u64(gid), _lib.p_i32(pl), _lib.p_i32(action),
+                                                    _lib.p_i32(rc)))
+        if rc[0] != 0 or action[0] < 0:
+            raise KeyError("state is unknown to the search or was never selected from")
+        return int(action[0]) >> 3, int(action[0]) & 7
+
     # ---- reference surface
     def simulate(self, state, player):
         """othelo_mcts.py:22-26 + MCTS/__init__.py:30-71; `state` is not mutated."""

@@ -32,7 +32,7 @@ def training_example_symmetries(board, policy):
 
 def execute_episode(board_size, neural_network, degree_exploration, num_simulations, policy_temperature, e_greedy,
                     q_mode=_lib.QMODE_F64, snapshot_boards=False, policy_target="onehot", target_temperature=1.0,
-                    leaves_per_step=1, root_noise=None, noise_seed=0):
+                    leaves_per_step=1, root_noise=None, noise_seed=0, sample_moves=None, sample_seed=0):
     """training.py:26-72.  Returns [(board (n,n,2) bool, one-hot policy (n,n) float64, z int), ...], 8 per move.
 
     snapshot_boards=False reproduces the reference exactly, including its aliasing quirk: the
@@ -46,8 +46,13 @@ def execute_episode(board_size, neural_network, degree_exploration, num_simulati
     leaves_per_step > 1: that many descents per network batch under virtual loss (OthelloMCTS); a native network only.
 
     root_noise=(alpha, epsilon): Dirichlet noise on the root prior, drawn on the device once per move before that move's simulations, keyed
-    (noise_seed, 0, ply) with ply = the moves played so far; None is the function without it."""
+    (noise_seed, 0, ply) with ply = the moves played so far; None is the function without it.
+
+    sample_moves=(temperature, plies): where the coin falls on the greedy branch, the move of a ply < plies is drawn on the device in proportion
+    to N ** (1 / temperature) (OthelloMCTS.sample_action), keyed (sample_seed, 0, ply), instead of taken as the arg-max; None is the function
+    without it."""
     root_noise = _lib.check_root_noise(root_noise)
+    sample_moves = _lib.check_sample_moves(sample_moves)
     assert policy_target in ("onehot", "visits"), policy_target
     if policy_target == "visits" and not target_temperature > 0:
         raise ValueError(f"target_temperature must be > 0 for visit-count targets (got {target_temperature})")
@@ -70,6 +75,8 @@ def execute_episode(board_size, neural_network, degree_exploration, num_simulati
         coin = random.random()                      # e-greedy, training.py:51-56
         if coin <= e_greedy:
             action = np.argwhere(policy == policy.max())[0]
+            if sample_moves is not None and len(examples) // 8 < sample_moves[1]:
+                action = mcts.sample_action(state, sample_moves[0], sample_seed, 0, len(examples) // 8)
         else:
             actions = mcts.get_state_actions(state)
             action = actions[np.random.choice(len(actions))]
@@ -133,7 +140,7 @@ class SelfPlayEngine:
     def __init__(self, neural_network, board_size=8, num_games=4096, num_simulations=100, degree_exploration=1.0,
                  policy_temperature=1.0, e_greedy=0.9, seed=1234, first_game_id=0, game_id_stride=0,
                  q_mode=_lib.QMODE_F64, refill=False, node_cap=0, record_cap=0, dedup=True, batch_cap=0, eval_cache=False,
-                 record_visits=False, leaves_per_step=1, root_noise=None):
+                 record_visits=False, leaves_per_step=1, root_noise=None, sample_moves=None):
         """dedup: cross-game leaf de-duplication (a board several games reach in one batch is evaluated once; no record changes);
         batch_cap: leaves per network batch of the free-running driver (0 = none; see preferred_batch_cap);
         eval_cache: take (pi, v) of boards the network has evaluated before from its persistent cache (NNetWrapper.set_eval_cache) --
@@ -145,8 +152,12 @@ class SelfPlayEngine:
         effect (every leaf is evaluated) and run(sync=False) still waits once per move round.  Not the reference's search order.
         root_noise=(alpha, epsilon): every searched move draws Dirichlet(alpha) noise over its root's legal moves on the device, keyed
         (seed, game id, ply), and its descents see (1 - epsilon) P + epsilon eta at the root (oz_selfplay_set_root_noise); stored priors and
-        the records' layout do not change."""
+        the records' layout do not change.
+        sample_moves=(temperature, plies): where the coin falls on the greedy branch, the move of a game whose ply < plies is drawn in
+        proportion to N ** (1 / temperature), keyed (seed, game id, ply), instead of taken as the arg-max (oz_selfplay_set_move_sampling);
+        such a record has greedy == 2.  run(), run_steps() and stagger() alike; later plies and the explore branch are unchanged."""
         root_noise = _lib.check_root_noise(root_noise)
+        sample_moves = _lib.check_sample_moves(sample_moves)
         lib = _lib.require_gpu()
         assert getattr(neural_network, "_h", None) is not None, "SelfPlayEngine needs a native NNetWrapper / StubNetWrapper"
         self.net = neural_network
@@ -165,6 +176,9 @@ class SelfPlayEngine:
         self.root_noise = root_noise
         if root_noise is not None:
             _lib.check(lib.oz_selfplay_set_root_noise(self._h, root_noise[0], root_noise[1]))
+        self.sample_moves = sample_moves
+        if sample_moves is not None:
+            _lib.check(lib.oz_selfplay_set_move_sampling(self._h, sample_moves[0], sample_moves[1]))
 
     def __del__(self):
         try:
@@ -333,13 +347,15 @@ def expand_examples(records, board_size, alias_final=False, visits=None, target_
 
 def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations=100, degree_exploration=1.0,
                    policy_temperature=1.0, e_greedy=0.9, seed=1234, first_game_id=0, q_mode=_lib.QMODE_F64,
-                   expand=False, alias_final=False, record_visits=False, target_temperature=1.0, leaves_per_step=1, root_noise=None):
+                   expand=False, alias_final=False, record_visits=False, target_temperature=1.0, leaves_per_step=1, root_noise=None,
+                   sample_moves=None):
     """Play num_games complete games; returns the move records (or the expanded examples).
     record_visits=True: (records, visit counts) -- or, with expand, the examples with visit-distribution targets at target_temperature.
-    root_noise=(alpha, epsilon): Dirichlet root noise in every search (SelfPlayEngine)."""
+    root_noise=(alpha, epsilon): Dirichlet root noise in every search (SelfPlayEngine).
+    sample_moves=(temperature, plies): the opening plies' moves are sampled from the visit counts (SelfPlayEngine)."""
     eng = SelfPlayEngine(neural_network, board_size, num_games, num_simulations, degree_exploration, policy_temperature,
                          e_greedy, seed, first_game_id, q_mode=q_mode, record_visits=record_visits, leaves_per_step=leaves_per_step,
-                         root_noise=root_noise)
+                         root_noise=root_noise, sample_moves=sample_moves)
     if record_visits:
         rec, counts = eng.play_to_end(with_visits=True)
         return expand_examples(rec, board_size, alias_final, visits=counts, target_temperature=target_temperature) if expand else (rec, counts)
