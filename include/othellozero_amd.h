@@ -544,6 +544,57 @@ int oz_trainer_get_activation(oz_trainer* t, int layer, int B, float* data, int6
 int oz_trainer_sync(oz_trainer* t);
 int oz_trainer_step_count(oz_trainer* t, int64_t* step);
 
+/* ------------------------------------------------------------------ replay buffer (opt-in; without it every result, record and file is unchanged)
+ * Finished training examples RESIDENT on the device, between the self-play engines that produce them and the trainer that consumes them:
+ * the replacement, for callers that ask for it, of the host's list of example tuples (main.py:21-53 CircularArray, training.py:58-72).
+ * Storage: slot s holds exactly what the trainer's resident data set holds for an example -- own[s], opp[s] uint64 (own = channel 0 of the
+ * example board = the record's BLACK board, opp = channel 1 = its WHITE board: absolute colours; bit row*8+col), pi[s][n*n] float32 indexed
+ * row*n+col, z[s] float32.  276 B per 8x8 example.
+ * The 8 examples of a record: example 8i+t is symmetry t of training_example_symmetries' order (oz_symmetry_table; the identity is example 7):
+ * output bit (r, c) of the board is the source bit perm[t][r][c] of the board at the move -- of the game's final board (final_black /
+ * final_white) when alias_final != 0; z = (float)record.z.  OZ_REPLAY_TARGET_ONEHOT: pi is 1.0f at the output cell whose source cell is the
+ * action, 0 elsewhere.  OZ_REPLAY_TARGET_VISITS: the float64 row of oz_examples_expand_visits at `temperature` (the same device code: N ** (1 / T)
+ * on the legal squares over their np.sum in NumPy's pairwise order, or over 1 if that is 0), each element rounded once to float32 (round to
+ * nearest), then the 8 symmetries.  A slot so equals, bit for bit, what trainer.pack_examples(loop.examples_from_records(...)) yields.
+ * Order: the records of ONE append are appended in ascending (game_id, ply), whatever order the engine's buffer or the caller's array holds
+ * them in (games that finish in the same kernel reserve their blocks of the engine's buffer in a race): contents never depend on it.
+ * Ring: the example with running index k (counted from creation or the last clear) lives in slot k % capacity -- the oldest example is
+ * overwritten.  (NOT the reference's CircularArray + in-place random.shuffle, which overwrites random survivors; the host path keeps that.)
+ * capacity need not be a multiple of 8: a record's examples may straddle the wrap.  An append of more than `capacity` examples keeps its last
+ * `capacity`.
+ * Errors, all OZ_ERR_ARG: a board size of the engine / trainer that differs from the buffer's; an object on another device; VISITS with
+ * temperature <= 0, from an engine created without record_visits, or with counts == NULL; first_record < 0; an order index outside [0, held);
+ * batch outside [1, max_batch]; alias_final not 0 / 1; an unknown target; capacity outside [1, 2^31 - 1]; a read beyond `held`.
+ * Synchronisation: every call is synchronous; the appends wait for the engine's stream first (like oz_selfplay_records).  One mutex per
+ * object; oz_trainer_fit_epoch_replay locks the trainer, then the buffer, and runs on the trainer's stream like oz_trainer_fit_epoch. */
+typedef struct oz_replay oz_replay;
+#define OZ_REPLAY_TARGET_ONEHOT 0   /* pi = one-hot of the move played (oz_examples_expand) */
+#define OZ_REPLAY_TARGET_VISITS 1   /* pi = the visit distribution at `temperature` (oz_examples_expand_visits) */
+int oz_replay_create(oz_replay** out, int n, int64_t capacity /* examples, 1 .. 2^31-1 */);
+int oz_replay_destroy(oz_replay* r);
+int oz_replay_clear(oz_replay* r);
+/* held = min(total, capacity); total = examples appended since creation / clear (each may be NULL) */
+int oz_replay_info(oz_replay* r, int64_t* held, int64_t* capacity, int64_t* total);
+/* records [first_record, completed so far) of the engine -> 8 examples each, device to device (the 48-byte records alone visit the host, to be
+ * ordered; the examples never leave the device); *appended_records (optional) says how many */
+int oz_replay_append_selfplay(oz_replay* r, oz_selfplay* sp, int64_t first_record, int alias_final, int target, double temperature,
+                              int64_t* appended_records);
+/* the same from host records (+ counts[count][64], the rows of oz_selfplay_visits, for OZ_REPLAY_TARGET_VISITS, else NULL): the pooled records
+ * of a multi-GPU run, saved games.  count < 2^28. */
+int oz_replay_append_records(oz_replay* r, const oz_record* records, const int32_t* counts, int64_t count, int alias_final,
+                             int target, double temperature);
+/* finished examples from the host, in the given order (restoring a saved buffer, hand-made data) */
+int oz_replay_append_examples(oz_replay* r, const uint64_t* own, const uint64_t* opp, const float* pi /* [count][n*n] */,
+                              const float* z, int64_t count);
+/* a saved buffer back: clears, then places the `count` = min(total, capacity) newest examples, oldest first, at the running indices
+ * [total - count, total) -- the slots they had when they were appended -- and leaves the running index at `total` */
+int oz_replay_restore(oz_replay* r, const uint64_t* own, const uint64_t* opp, const float* pi, const float* z, int64_t count, int64_t total);
+/* slots [first_slot, first_slot + count) to the host (tests, saving; each array may be NULL) */
+int oz_replay_read(oz_replay* r, int64_t first_slot, int64_t count, uint64_t* own, uint64_t* opp, float* pi, float* z);
+/* oz_trainer_fit_epoch with the replay buffer as the resident data set: order[i] = a slot index in [0, held); the same launches, steps and
+ * losses as oz_trainer_fit_epoch on a data set with the slots' contents */
+int oz_trainer_fit_epoch_replay(oz_trainer* t, oz_replay* r, const int32_t* order, int64_t count, int batch, float* losses3);
+
 /* ------------------------------------------------------------------ diagnostics
  * device arithmetic behind the PUCT / backup formulas (MCTS/__init__.py:68,168-170), for bit-exact
  * comparison with the host: sqrt(a), a/b in float64; a/b and (a*b+a)/b in float32 (no FMA contraction). */

@@ -161,9 +161,20 @@ class NNetWrapper(_NetHandle):
         lr=self.lr with clipvalue 0.5 for ONN / none for BNN, Dropout self.dropout, BN momentum 0.99).  Returns a History-like object (`.history['loss']`, ...).  The TensorBoard
         callback of the reference is not reproduced.  Optimiser state persists across calls like the compiled Keras model's."""
         from . import trainer as T
-        if not examples:
+        from .replay import ReplayBuffer
+        replay = examples if isinstance(examples, ReplayBuffer) else None
+        if replay is not None:
+            # a device-resident replay buffer in place of the tuple list: the fit reads its slots in place (trainer.fit_replay)
+            if allreduce is not None:
+                raise ValueError("training from a ReplayBuffer is single-process: a data-parallel fit keeps the step-wise path (pass example tuples)")
+            if replay.n != self.board_size_x:
+                raise ValueError(f"the ReplayBuffer holds {replay.n} x {replay.n} examples, this network plays {self.board_size_x} x {self.board_size_x}")
+            if len(replay) == 0:
+                return T.History()
+        elif not examples:
             return T.History()
-        own, opp, pi, z = T.pack_examples(examples, self.board_size_x, self.in_channels)
+        else:
+            own, opp, pi, z = T.pack_examples(examples, self.board_size_x, self.in_channels)
         if getattr(self, "_trainer", None) is None:
             assert self.num_channels % 128 == 0, "the training kernels need num_channels % 128 == 0"
             # a GradientAllReduce owns the gradient arena (a torch tensor RCCL can reduce in place): the library writes into it
@@ -176,9 +187,12 @@ class NNetWrapper(_NetHandle):
             self._fit_calls = 0
         assert getattr(allreduce, "ptr", None) == self._trainer_arena, "train() must keep using the GradientAllReduce it started with"
         self._trainer.set_weights(self.get_weights())
-        hist = T.fit(self._trainer, own, opp, pi, z, batch_size=self.batch_size, epochs=self.epochs,
-                     shuffle_seed=1000003 * self._fit_calls + (self._model_index if seed is None else seed), allreduce=allreduce,
-                     verbose=verbose)
+        shuffle_seed = 1000003 * self._fit_calls + (self._model_index if seed is None else seed)
+        if replay is not None:
+            hist = T.fit_replay(self._trainer, replay, batch_size=self.batch_size, epochs=self.epochs, shuffle_seed=shuffle_seed, verbose=verbose)
+        else:
+            hist = T.fit(self._trainer, own, opp, pi, z, batch_size=self.batch_size, epochs=self.epochs, shuffle_seed=shuffle_seed,
+                         allreduce=allreduce, verbose=verbose)
         self._fit_calls += 1
         weights = self._trainer.get_weights()
         if allreduce is not None:                       # BN moving statistics are per replica: average them

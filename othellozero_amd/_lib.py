@@ -24,6 +24,7 @@ LEAF_IDLE, LEAF_TERMINAL, LEAF_EVAL = 0, 1, 2
 VT_INT, VT_F32, VT_F64 = 0, 1, 2
 MAX_LEAVES_PER_STEP = 16                                                             # OZ_MCTS_MAX_LEAVES_PER_STEP
 POLICY_LOSS_ROWS, POLICY_LOSS_FLAT = 0, 1                                            # oz_trainer_set_policy_loss
+REPLAY_TARGET_ONEHOT, REPLAY_TARGET_VISITS = 0, 1                                    # oz_replay_append_*
 NET_KERNELS = ("input", "conv2", "conv3", "conv4", "fc1", "fc2", "heads")           # OZ_NET_KERNELS slots
 TREE_KERNELS = ("select", "compact", "network", "expand_backup", "roots_move")       # OZ_TREE_KERNELS slots
 
@@ -159,6 +160,14 @@ SIGNATURES = {
     "oz_trainer_set_precision": [_vp, C.c_int],
     "oz_trainer_set_policy_loss": [_vp, C.c_int],
     "oz_trainer_step_count": [_vp, C.POINTER(C.c_int64)],
+    "oz_replay_create": [C.POINTER(_vp), C.c_int, C.c_int64], "oz_replay_destroy": [_vp], "oz_replay_clear": [_vp],
+    "oz_replay_info": [_vp, _i64p, _i64p, _i64p],
+    "oz_replay_append_selfplay": [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_double, _i64p],
+    "oz_replay_append_records": [_vp, _vp, _i32p, C.c_int64, C.c_int, C.c_int, C.c_double],
+    "oz_replay_append_examples": [_vp, _u64p, _u64p, _f32p, _f32p, C.c_int64],
+    "oz_replay_restore": [_vp, _u64p, _u64p, _f32p, _f32p, C.c_int64, C.c_int64],
+    "oz_replay_read": [_vp, C.c_int64, C.c_int64, _u64p, _u64p, _f32p, _f32p],
+    "oz_trainer_fit_epoch_replay": [_vp, _vp, _i32p, C.c_int64, C.c_int, _f32p],
 }
 
 _LIB = None

@@ -9,6 +9,7 @@
 // NN action index = row*n + col (Net/NNet.py:86 reshape order).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 
 #define OZ_HD __host__ __device__ __forceinline__
@@ -153,6 +154,31 @@ __host__ __device__ inline double pairwise_sum(const double* a, int len) {
     for (; i < len; ++i) res += a[i];
     return res;
 }
+
+// ---------------------------------------------------------------- training examples
+// training_example_symmetries, training.py:13-23: outputs in the order rot90 k=1..4 (CCW), each
+// first with fliplr then without.  src(t, r, c) = source cell of output cell (r, c).
+OZ_HD int oz_sym_src(int t, int n, int r, int c) {
+    const int k = (t >> 1) + 1, flip = !(t & 1);
+    int rr = r, cc = flip ? (n - 1 - c) : c;
+    for (int q = 0; q < (k & 3); ++q) { int ti = cc, tj = n - 1 - rr; rr = ti; cc = tj; }
+    return rr * n + cc;
+}
+
+// N ** (1 / T) of get_policy_action_probabilities (othelo_mcts.py:59-60) for a visit count.  k = 1 / T where that is an integer (else 0):
+// the product of k factors is exact while it stays <= 2^53 (every partial product is then an integer below it), so it equals the
+// correctly rounded power the host computes; beyond that, and for any other exponent, the device's pow.
+__device__ __forceinline__ double oz_count_pow(int cnt, double inv, int k) {
+    const double x = (double)cnt;
+    if (k > 0) {
+        double r = x;
+        for (int i = 1; i < k; ++i) r *= x;
+        if (r <= 9007199254740992.0) return r;
+    }
+    return pow(x, inv);
+}
+// the k of oz_count_pow for inv = 1 / T
+inline int oz_count_pow_k(double inv) { return (inv == floor(inv) && inv <= 64.0) ? (int)inv : 0; }
 
 // ---------------------------------------------------------------- error plumbing (host)
 #include <stdio.h>

@@ -204,3 +204,23 @@ int oz_gemm_b3_launch(const void* in_b3, const void* Wb, const float* scale, con
 int oz_f32_to_b3_launch(const float* x, const int* d_count, int max_count, int P, int C, void* out, hipStream_t s);
 // Keras weights [K][N] with k = tap * Cin + ci -> b3 rows [N][K] in the GEMM's tap-inner k order (k_w_to_b3)
 int oz_w_to_b3_launch(const float* W, int K, int N, int taps, void* out, hipStream_t s);
+
+// Device-resident replay buffer (oz_replay.hip): `capacity` finished examples in the trainer's data-set layout -- own / opp bitboards, one float32
+// pi row of n*n, one float32 z per slot -- filled device to device by k_replay_append and read in place by oz_trainer_fit_epoch_replay
+// (oz_train.hip).  The example with running index k (counted from creation / clear) lives in slot k % capacity.
+struct oz_replay {
+    int n = 8, device = 0;
+    int64_t capacity = 0, total = 0;
+    uint64_t *own = nullptr, *opp = nullptr;
+    float *pi = nullptr, *z = nullptr;
+    hipStream_t s = nullptr;
+    // staging of an append, grown on demand and kept: the records (and visit-count rows) as the engine / the host holds them, and the
+    // permutation that puts them in (game_id, ply) order
+    oz_record* st_rec = nullptr;
+    int32_t *st_cnt = nullptr, *st_perm = nullptr;
+    int64_t st_rec_cap = 0, st_cnt_cap = 0;
+    std::mutex mu;
+    int64_t held() const { return total < capacity ? total : capacity; }
+};
+// what an append needs to know about an engine (oz_search.hip): waits for the engine's stream; completed = records of completed games it holds
+int oz_selfplay_replay_facts(oz_selfplay* sp, int* n, int* device, int* record_visits, int64_t* completed);

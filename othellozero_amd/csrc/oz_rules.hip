@@ -199,14 +199,7 @@ OZ_API int oz_rules_play(const uint64_t* black, const uint64_t* white, const int
 }
 
 // ---------------------------------------------------------------- symmetries (K8)
-// training_example_symmetries, training.py:13-23: outputs in the order rot90 k=1..4 (CCW), each
-// first with fliplr then without.  src(t, r, c) = source cell of output cell (r, c).
-OZ_HD int oz_sym_src(int t, int n, int r, int c) {
-    const int k = (t >> 1) + 1, flip = !(t & 1);
-    int rr = r, cc = flip ? (n - 1 - c) : c;
-    for (int q = 0; q < (k & 3); ++q) { int ti = cc, tj = n - 1 - rr; rr = ti; cc = tj; }
-    return rr * n + cc;
-}
+// (oz_sym_src, the source cell of an output cell under symmetry t, lives in oz_common.h: the replay buffer's append kernel shares it)
 
 OZ_API int oz_symmetry_table(int n, int32_t* perm) {
     if (int rc = check_n(n)) return rc;
@@ -256,19 +249,7 @@ OZ_API int oz_examples_expand(const oz_record* records, int64_t count, int n, in
     return OZ_OK;
 }
 
-// N ** (1 / T) of get_policy_action_probabilities (othelo_mcts.py:59-60) for a visit count.  k = 1 / T where that is an integer (else 0):
-// the product of k factors is exact while it stays <= 2^53 (every partial product is then an integer below it), so it equals the
-// correctly rounded power the host computes; beyond that, and for any other exponent, the device's pow.
-__device__ __forceinline__ double oz_count_pow(int cnt, double inv, int k) {
-    const double x = (double)cnt;
-    if (k > 0) {
-        double r = x;
-        for (int i = 1; i < k; ++i) r *= x;
-        if (r <= 9007199254740992.0) return r;
-    }
-    return pow(x, inv);
-}
-
+// (oz_count_pow, N ** (1 / T) of a visit count, lives in oz_common.h)
 // one 64-lane block per record, lane = cell r*n+c of the record's own (n, n) view: pi of the root (pairwise np.sum by lane 0, as on the
 // host), then for each of the 8 symmetries the output cell `lane` takes its source cell's value -- boards, pi and z of the 8 examples
 __global__ __launch_bounds__(64) void k_expand_visits(const oz_record* __restrict__ recs, const int32_t* __restrict__ counts, int n, int alias_final,
@@ -318,7 +299,7 @@ OZ_API int oz_examples_expand_visits(const oz_record* records, const int32_t* co
     OZ_HIP(hipMemcpy(r.p, records, sizeof(oz_record) * count, hipMemcpyHostToDevice));
     OZ_HIP(hipMemcpy(cn.p, counts, sizeof(int32_t) * 64 * count, hipMemcpyHostToDevice));
     const double inv = 1.0 / temperature;
-    const int k = (inv == floor(inv) && inv <= 64.0) ? (int)inv : 0;
+    const int k = oz_count_pow_k(inv);
     hipLaunchKernelGGL(k_expand_visits, dim3((unsigned)count), dim3(64), 0, 0, r.p, cn.p, n, alias_final, inv, k, b.p, p.p, zz.p);
     OZ_HIP(hipGetLastError());
     OZ_HIP(hipMemcpy(boards, b.p, cells * 2, hipMemcpyDeviceToHost));

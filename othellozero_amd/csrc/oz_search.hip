@@ -2300,6 +2300,17 @@ OZ_API int oz_selfplay_records_device(oz_selfplay* sp, void* dst_device, int64_t
     OZ_REQUIRE(sp, "null selfplay");
     return selfplay_rows(sp, sp->gm.records, sizeof(oz_record), dst_device, max_records, written, hipMemcpyDeviceToDevice);
 }
+int oz_selfplay_replay_facts(oz_selfplay* sp, int* n, int* device, int* record_visits, int64_t* completed) {
+    OZ_REQUIRE(sp, "null selfplay");
+    std::lock_guard<std::mutex> lk(sp->mu);
+    hipSetDevice(sp->m->device);
+    OZ_HIP(hipStreamSynchronize(sp->m->stream));
+    unsigned long long total = 0;
+    OZ_HIP(hipMemcpy(&total, sp->gm.counters, 8, hipMemcpyDeviceToHost));
+    *n = sp->gm.n; *device = sp->m->device; *record_visits = sp->gm.record_visits;
+    *completed = (long long)total > sp->gm.record_cap ? sp->gm.record_cap : (int64_t)total;
+    return OZ_OK;
+}
 #define OZ_REQUIRE_VISITS(sp) OZ_REQUIRE((sp)->gm.record_visits, "this engine does not record visit counts: create it with oz_selfplay_config.record_visits = 1")
 OZ_API int oz_selfplay_visits(oz_selfplay* sp, int32_t* out, int64_t max_records, int64_t* written) {
     OZ_REQUIRE(sp, "null selfplay");

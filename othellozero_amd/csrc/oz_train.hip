@@ -988,7 +988,7 @@ struct oz_trainer {
     float *ds_pi = nullptr, *ds_z = nullptr;
     int* ds_order = nullptr;
     double* ds_acc = nullptr;
-    int64_t ds_n = 0, ds_cap = 0;
+    int64_t ds_n = 0, ds_cap = 0, ds_order_cap = 0;
     std::vector<void*> allocs;
     bool dirty = true;                   // derived operands need a refresh
     std::mutex mu;                       // one caller at a time (ThreadWorker-style Python threads)
@@ -1599,12 +1599,13 @@ OZ_API int oz_trainer_set_dataset(oz_trainer* t, const uint64_t* own, const uint
     const int A = t->n * t->n;
     if (N > t->ds_cap) {
         OZ_HIP(hipStreamSynchronize(t->s));
-        if (t->ds_own) { hipFree(t->ds_own); hipFree(t->ds_opp); hipFree(t->ds_pi); hipFree(t->ds_z); hipFree(t->ds_order); }
-        t->ds_own = t->ds_opp = nullptr; t->ds_pi = t->ds_z = nullptr; t->ds_order = nullptr; t->ds_cap = 0;
+        if (t->ds_own) { hipFree(t->ds_own); hipFree(t->ds_opp); hipFree(t->ds_pi); hipFree(t->ds_z); }
+        if (t->ds_order) hipFree(t->ds_order);          // (an epoch from a replay buffer may have sized it before any data set)
+        t->ds_own = t->ds_opp = nullptr; t->ds_pi = t->ds_z = nullptr; t->ds_order = nullptr; t->ds_cap = 0; t->ds_order_cap = 0;
         OZ_HIP(hipMalloc((void**)&t->ds_own, N * sizeof(uint64_t))); OZ_HIP(hipMalloc((void**)&t->ds_opp, N * sizeof(uint64_t)));
         OZ_HIP(hipMalloc((void**)&t->ds_pi, (size_t)N * A * sizeof(float))); OZ_HIP(hipMalloc((void**)&t->ds_z, N * sizeof(float)));
         OZ_HIP(hipMalloc((void**)&t->ds_order, N * sizeof(int)));
-        t->ds_cap = N;
+        t->ds_cap = N; t->ds_order_cap = N;
     }
     if (!t->ds_acc) OZ_HIP(hipMalloc((void**)&t->ds_acc, 4 * sizeof(double)));
     OZ_HIP(hipMemcpyAsync(t->ds_own, own, N * sizeof(uint64_t), hipMemcpyHostToDevice, t->s));
@@ -1618,21 +1619,29 @@ OZ_API int oz_trainer_set_dataset(oz_trainer* t, const uint64_t* own, const uint
 
 static int t_apply_locked(oz_trainer* t);
 
-OZ_API int oz_trainer_fit_epoch(oz_trainer* t, const int32_t* order, int64_t count, int batch, float* losses3) {
-    OZ_REQUIRE(t && order && count >= 1, "oz_trainer_fit_epoch: bad argument");
-    T_LOCK(t);
-    OZ_REQUIRE(t->ds_n > 0 && count <= t->ds_n, "oz_trainer_fit_epoch: %lld indices but the resident data set holds %lld examples (oz_trainer_set_dataset first)",
-               (long long)count, (long long)t->ds_n);
-    OZ_REQUIRE(batch >= 1 && batch <= t->Bmax, "oz_trainer_fit_epoch: batch %d outside [1, %d]", batch, t->Bmax);
-    for (int64_t i = 0; i < count; ++i) OZ_REQUIRE(order[i] >= 0 && order[i] < t->ds_n, "oz_trainer_fit_epoch: index %d outside the data set", order[i]);
+// What an epoch reads its examples from: the trainer's own resident data set (oz_trainer_set_dataset) or a replay buffer's slots
+// (oz_replay.hip) -- `n` examples in the same four arrays.
+struct TDataView { const uint64_t *own, *opp; const float *pi, *z; int64_t n; };
+
+// the optimiser steps of one epoch over `d` in the order `order` (validated by the caller's entry point): per step one device-side gather of
+// the batch, forward + backward, the loss accumulation and Adam, back to back on the stream; one read-back at the end
+static int t_fit_epoch_view(oz_trainer* t, const TDataView& d, const int32_t* order, int64_t count, int batch, float* losses3) {
     OZ_HIP(hipSetDevice(t->device));
     hipStream_t s = t->s;
     const int A = t->n * t->n;
+    if (count > t->ds_order_cap) {             // (never on the resident path: oz_trainer_set_dataset sized it for the data set)
+        OZ_HIP(hipStreamSynchronize(s));
+        if (t->ds_order) hipFree(t->ds_order);
+        t->ds_order = nullptr; t->ds_order_cap = 0;
+        OZ_HIP(hipMalloc((void**)&t->ds_order, count * sizeof(int)));
+        t->ds_order_cap = count;
+    }
+    if (!t->ds_acc) OZ_HIP(hipMalloc((void**)&t->ds_acc, 4 * sizeof(double)));
     OZ_HIP(hipMemcpyAsync(t->ds_order, order, count * sizeof(int), hipMemcpyHostToDevice, s));
     OZ_HIP(hipMemsetAsync(t->ds_acc, 0, 4 * sizeof(double), s));
     for (int64_t first = 0; first < count; first += batch) {
         const int B = (int)(count - first < batch ? count - first : batch);            // the last batch may be short, as in keras
-        hipLaunchKernelGGL(k_t_gather_batch, dim3((B * A + 255) / 256), dim3(256), 0, s, t->ds_own, t->ds_opp, t->ds_pi, t->ds_z, t->ds_order,
+        hipLaunchKernelGGL(k_t_gather_batch, dim3((B * A + 255) / 256), dim3(256), 0, s, d.own, d.opp, d.pi, d.z, t->ds_order,
                            (int)first, B, A, t->d_own, t->d_opp, t->d_pit, t->d_zt, t->d_count);
         if (int rc = t_forward_backward_async(t, B)) return rc;
         hipLaunchKernelGGL(k_t_acc_losses, dim3(1), dim3(64), 0, s, t->losses, B, t->ds_acc);
@@ -1643,6 +1652,31 @@ OZ_API int oz_trainer_fit_epoch(oz_trainer* t, const int32_t* order, int64_t cou
     OZ_HIP(hipStreamSynchronize(s));
     if (losses3) for (int k = 0; k < 3; ++k) losses3[k] = (float)(h[k] / (h[3] > 0 ? h[3] : 1.0));
     return t_check_range(t);
+}
+
+OZ_API int oz_trainer_fit_epoch(oz_trainer* t, const int32_t* order, int64_t count, int batch, float* losses3) {
+    OZ_REQUIRE(t && order && count >= 1, "oz_trainer_fit_epoch: bad argument");
+    T_LOCK(t);
+    OZ_REQUIRE(t->ds_n > 0 && count <= t->ds_n, "oz_trainer_fit_epoch: %lld indices but the resident data set holds %lld examples (oz_trainer_set_dataset first)",
+               (long long)count, (long long)t->ds_n);
+    OZ_REQUIRE(batch >= 1 && batch <= t->Bmax, "oz_trainer_fit_epoch: batch %d outside [1, %d]", batch, t->Bmax);
+    for (int64_t i = 0; i < count; ++i) OZ_REQUIRE(order[i] >= 0 && order[i] < t->ds_n, "oz_trainer_fit_epoch: index %d outside the data set", order[i]);
+    return t_fit_epoch_view(t, {t->ds_own, t->ds_opp, t->ds_pi, t->ds_z, t->ds_n}, order, count, batch, losses3);
+}
+
+// the same epoch with a replay buffer's slots as the resident data set (trainer locked before the replay buffer; the appends are synchronous,
+// so every held slot is complete)
+OZ_API int oz_trainer_fit_epoch_replay(oz_trainer* t, oz_replay* r, const int32_t* order, int64_t count, int batch, float* losses3) {
+    OZ_REQUIRE(t && r && order && count >= 1 && count < (1ll << 31), "oz_trainer_fit_epoch_replay: bad argument");
+    T_LOCK(t);
+    std::lock_guard<std::mutex> rlock(r->mu);
+    OZ_REQUIRE(r->n == t->n, "oz_trainer_fit_epoch_replay: the trainer's boards are %d x %d, the replay buffer's %d x %d", t->n, t->n, r->n, r->n);
+    OZ_REQUIRE(r->device == t->device, "oz_trainer_fit_epoch_replay: the trainer lives on device %d, the replay buffer on device %d", t->device, r->device);
+    OZ_REQUIRE(batch >= 1 && batch <= t->Bmax, "oz_trainer_fit_epoch_replay: batch %d outside [1, %d]", batch, t->Bmax);
+    const int64_t held = r->held();
+    for (int64_t i = 0; i < count; ++i)
+        OZ_REQUIRE(order[i] >= 0 && order[i] < held, "oz_trainer_fit_epoch_replay: index %d outside the %lld examples the replay buffer holds", order[i], (long long)held);
+    return t_fit_epoch_view(t, {r->own, r->opp, r->pi, r->z, held}, order, count, batch, losses3);
 }
 
 static int t_apply_locked(oz_trainer* t) {

@@ -169,12 +169,29 @@ def self_play_match(board_size, neural_network, old_neural_network, total_games,
     return wins
 
 
+def _selfplay_into_replay(replay, neural_network, board_size, num_episodes, num_simulations, degree_exploration, temperature, e_greedy, seed,
+                          first_game_id, q_mode, visits, leaves_per_step, root_noise, sample_moves, alias_final_boards, policy_target,
+                          target_temperature):
+    """one iteration's games on the engine selfplay_batch would create, played to the end without reading a record, and their examples
+    appended to the device buffer; -> records appended.  One-channel (BaseNN) examples are never aliased (examples_from_records)."""
+    from .training import SelfPlayEngine
+    eng = SelfPlayEngine(neural_network, board_size, num_episodes, num_simulations, degree_exploration, temperature, e_greedy, seed,
+                         first_game_id, q_mode=q_mode, record_visits=visits, leaves_per_step=leaves_per_step, root_noise=root_noise,
+                         sample_moves=sample_moves)
+    for _ in range(board_size * board_size):
+        eng.run(4)
+        if eng.stats()["live_games"] == 0:
+            break
+    return replay.append_engine(eng, alias_final=alias_final_boards and getattr(neural_network, "in_channels", 2) == 2,
+                                policy_target=policy_target, target_temperature=target_temperature)
+
+
 def training(board_size, num_iterations, num_episodes, num_simulations, degree_exploration, temperature, neural_network,
              e_greedy, evaluation_interval, evaluation_iterations, temperature_threshold, self_play_training,
              self_play_interval, self_play_total_games, self_play_threshold, checkpoint_filepath, training_buffer_size,
              seed=1234, reference_aliasing=True, alias_final_boards=True, dump_examples=False, q_mode=_lib.QMODE_F64,
              distributed=False, batched_evaluation=False, policy_target="onehot", target_temperature=1.0, leaves_per_step=1,
-             root_noise=None, sample_moves=None):
+             root_noise=None, sample_moves=None, replay="host"):
     """main.py:56-259 on the GPU engines; returns `historic` = [(episodes done, win rate vs random), ...]
 
     batched_evaluation=True plays the evaluation games against RandomOthelloAgent in lock step on the GPU
@@ -199,7 +216,21 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
 
     sample_moves=(temperature, plies): where the e_greedy coin falls on the greedy branch, the SELF-PLAY move of a game's first `plies`
     plies is drawn in proportion to N ** (1 / temperature) instead of taken as the arg-max (SelfPlayEngine), in both paths; matches and
-    evaluations never sample.  Pure AlphaZero is e_greedy = 1.  temperature_threshold keeps its meaning."""
+    evaluations never sample.  Pure AlphaZero is e_greedy = 1.  temperature_threshold keeps its meaning.
+
+    replay="device": the replay buffer is ONE replay.ReplayBuffer(board_size, training_buffer_size) in HBM for the run.  An iteration's
+    engine plays to the end without its records being read, the buffer appends their examples device to device
+    (ReplayBuffer.append_engine) and the network trains from the buffer in place (NNetWrapper.train(replay)): no example tuples, no
+    random.shuffle of examples (the fit draws its own order per epoch).  The ring overwrites the OLDEST example, where the default "host"
+    path keeps the reference's CircularArray + random.shuffle (which overwrites random survivors).  Matches, evaluation and promotion
+    are unchanged.  Single-process, and there is no tuple list to dump: not with distributed=True or dump_examples=True."""
+    if replay not in ("host", "device"):
+        raise ValueError(f"replay must be 'host' or 'device' (got {replay!r})")
+    if replay == "device" and distributed:
+        raise ValueError("replay='device' is single-process: the data-parallel fit has no entry point that reads the device buffer yet "
+                         "(use replay='host' with distributed=True)")
+    if replay == "device" and dump_examples:
+        raise ValueError("replay='device' keeps no example tuples to dump: use replay='host' with dump_examples=True, or ReplayBuffer.save")
     root_noise = _lib.check_root_noise(root_noise)
     sample_moves = _lib.check_sample_moves(sample_moves)
     if policy_target not in ("onehot", "visits"):
@@ -237,6 +268,10 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
     historic = []
     total_episodes_done = 0
     training_examples = CircularArray(training_buffer_size)
+    device_replay = None
+    if replay == "device":
+        from .replay import ReplayBuffer
+        device_replay = ReplayBuffer(board_size, training_buffer_size)
     old_neural_network = neural_network.copy()
     for i in range(1, num_iterations + 1):
         logging.info('[%d/%d] begin', i, num_iterations)
@@ -245,36 +280,45 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
             temperature = 0
 
         logging.info('[%d/%d] self-play: %d games x %d simulations on the GPU', i, num_iterations, num_episodes, num_simulations)
-        if distributed:
-            first, count = shard_games(num_episodes, rank, world)
-            eng = SelfPlayEngine(neural_network, board_size, count, num_simulations, degree_exploration, temperature, e_greedy,
-                                 seed=seed, first_game_id=total_episodes_done + first, q_mode=q_mode, record_visits=visits,
-                                 leaves_per_step=leaves_per_step, root_noise=root_noise, sample_moves=sample_moves)
-            eng.play_to_end()
-            records = pooled_selfplay_records(eng, device, with_visits=visits)      # the only exchange of the self-play phase
-            del eng
+        if device_replay is not None:
+            appended = _selfplay_into_replay(device_replay, neural_network, board_size, num_episodes, num_simulations, degree_exploration,
+                                             temperature, e_greedy, seed, total_episodes_done, q_mode, visits, leaves_per_step, root_noise,
+                                             sample_moves, alias_final_boards, policy_target, target_temperature)
+            total_episodes_done += num_episodes
+            logging.info('[%d/%d] self-play done: %d records, device buffer holds %d examples', i, num_iterations, appended, len(device_replay))
+            logging.info('[%d/%d] fit on the device buffer', i, num_iterations)
+            neural_network.train(device_replay, verbose=2 if logging.root.level <= logging.DEBUG else None)
         else:
-            records = selfplay_batch(neural_network, board_size, num_games=num_episodes, num_simulations=num_simulations,
-                                     degree_exploration=degree_exploration, policy_temperature=temperature, e_greedy=e_greedy,
-                                     seed=seed, first_game_id=total_episodes_done, q_mode=q_mode, record_visits=visits,
+            if distributed:
+                first, count = shard_games(num_episodes, rank, world)
+                eng = SelfPlayEngine(neural_network, board_size, count, num_simulations, degree_exploration, temperature, e_greedy,
+                                     seed=seed, first_game_id=total_episodes_done + first, q_mode=q_mode, record_visits=visits,
                                      leaves_per_step=leaves_per_step, root_noise=root_noise, sample_moves=sample_moves)
-        counts = None
-        if visits:
-            records, counts = records
-        training_examples.extend(examples_from_records(records, board_size, alias_final=alias_final_boards,
-                                                       in_channels=getattr(neural_network, "in_channels", 2), visits=counts,
-                                                       target_temperature=target_temperature))
-        total_episodes_done += num_episodes
-        logging.info('[%d/%d] self-play done: %d records, buffer holds %d examples', i, num_iterations, len(records), len(training_examples))
+                eng.play_to_end()
+                records = pooled_selfplay_records(eng, device, with_visits=visits)      # the only exchange of the self-play phase
+                del eng
+            else:
+                records = selfplay_batch(neural_network, board_size, num_games=num_episodes, num_simulations=num_simulations,
+                                         degree_exploration=degree_exploration, policy_temperature=temperature, e_greedy=e_greedy,
+                                         seed=seed, first_game_id=total_episodes_done, q_mode=q_mode, record_visits=visits,
+                                         leaves_per_step=leaves_per_step, root_noise=root_noise, sample_moves=sample_moves)
+            counts = None
+            if visits:
+                records, counts = records
+            training_examples.extend(examples_from_records(records, board_size, alias_final=alias_final_boards,
+                                                           in_channels=getattr(neural_network, "in_channels", 2), visits=counts,
+                                                           target_temperature=target_temperature))
+            total_episodes_done += num_episodes
+            logging.info('[%d/%d] self-play done: %d records, buffer holds %d examples', i, num_iterations, len(records), len(training_examples))
 
-        logging.info('[%d/%d] fit on the buffer', i, num_iterations)
-        random.shuffle(training_examples)
-        verbose = 2 if logging.root.level <= logging.DEBUG else None
-        if distributed:
-            usable = len(training_examples) - len(training_examples) % world     # equal step counts on every rank
-            neural_network.train([training_examples[j] for j in range(rank, usable, world)], verbose=verbose, allreduce=allreduce)
-        else:
-            neural_network.train(training_examples, verbose=verbose)
+            logging.info('[%d/%d] fit on the buffer', i, num_iterations)
+            random.shuffle(training_examples)
+            verbose = 2 if logging.root.level <= logging.DEBUG else None
+            if distributed:
+                usable = len(training_examples) - len(training_examples) % world     # equal step counts on every rank
+                neural_network.train([training_examples[j] for j in range(rank, usable, world)], verbose=verbose, allreduce=allreduce)
+            else:
+                neural_network.train(training_examples, verbose=verbose)
 
         if self_play_training and i % self_play_interval == 0:
             logging.info('[%d/%d] arena: trained network against the previous one', i, num_iterations)

@@ -1,0 +1,131 @@
+"""Device-resident replay buffer -- C ABI: oz_replay_*.
+
+`ReplayBuffer(board_size, capacity)` holds finished training examples in HBM, in the layout of the trainer's resident data set
+(own / opp bitboards, one float32 pi row, one float32 z per slot).  It is filled device to device from a `SelfPlayEngine`
+(`append_engine`), from move records the host holds (`append_records`: pooled records of a multi-GPU run, saved games) or from finished
+examples (`append_examples`), and `trainer.fit_replay` / `NNetWrapper.train(replay)` train from it in place: no example tuples, no
+host arrays of examples.  The opt-in counterpart of `loop.CircularArray` for large engines; `loop.training(..., replay="device")` uses it.
+
+Ring rule: the example with running index k (counted from creation or `clear()`) lives in slot k % capacity, the oldest example is
+overwritten -- deliberately not the reference's CircularArray + in-place random.shuffle, which overwrites random survivors.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+
+POLICY_TARGETS = {"onehot": _lib.REPLAY_TARGET_ONEHOT, "visits": _lib.REPLAY_TARGET_VISITS}
+
+
+def _target(policy_target, target_temperature):
+    if policy_target not in POLICY_TARGETS:
+        raise ValueError(f"policy_target must be 'onehot' or 'visits' (got {policy_target!r})")
+    return POLICY_TARGETS[policy_target], float(target_temperature)
+
+
+class ReplayBuffer:
+    def __init__(self, board_size, capacity):
+        """room for `capacity` examples (1 .. 2^31 - 1) of board_size x board_size boards on the current device: 24 + 4 n^2 bytes each"""
+        lib = _lib.require_gpu()
+        self.n = int(board_size)
+        self._h = C.c_void_p()
+        _lib.check(lib.oz_replay_create(C.byref(self._h), self.n, int(capacity)))
+
+    def __del__(self):
+        try:
+            if self._h:
+                _lib.load().oz_replay_destroy(self._h)
+                self._h = C.c_void_p()
+        except Exception:
+            pass
+
+    def info(self):
+        """(held, capacity, total): held = min(total, capacity), total = examples appended since creation / clear()"""
+        held, cap, total = C.c_int64(), C.c_int64(), C.c_int64()
+        _lib.check(_lib.load().oz_replay_info(self._h, C.byref(held), C.byref(cap), C.byref(total)))
+        return held.value, cap.value, total.value
+
+    def __len__(self):
+        return self.info()[0]
+
+    @property
+    def capacity(self):
+        return self.info()[1]
+
+    @property
+    def total(self):
+        return self.info()[2]
+
+    def clear(self):
+        _lib.check(_lib.load().oz_replay_clear(self._h))
+
+    def append_engine(self, eng, first_record=0, alias_final=False, policy_target="onehot", target_temperature=1.0):
+        """the records [first_record, completed so far) of a SelfPlayEngine -> 8 examples each, in ascending (game_id, ply), device to
+        device; returns the number of records appended.  policy_target="visits" needs an engine created with record_visits=True."""
+        target, T = _target(policy_target, target_temperature)
+        done = C.c_int64()
+        _lib.check(_lib.load().oz_replay_append_selfplay(self._h, eng._h, int(first_record), 1 if alias_final else 0, target, T, C.byref(done)))
+        return done.value
+
+    def append_records(self, records, visits=None, alias_final=False, policy_target="onehot", target_temperature=1.0):
+        """the same from records on the host (_lib.RECORD_DTYPE; visits = their int32 (R, 64) root visit counts for policy_target="visits"),
+        in any order: they are appended in ascending (game_id, ply); returns the number of records appended"""
+        target, T = _target(policy_target, target_temperature)
+        rec = np.ascontiguousarray(records, dtype=_lib.RECORD_DTYPE)
+        cnt = None
+        if visits is not None:
+            cnt = np.ascontiguousarray(visits, dtype=np.int32).reshape(-1, 64)
+            assert cnt.shape[0] == rec.size, f"{cnt.shape[0]} visit-count rows for {rec.size} records"
+        _lib.check(_lib.load().oz_replay_append_records(self._h, rec.ctypes.data_as(C.c_void_p), None if cnt is None else _lib.p_i32(cnt),
+                                                        rec.size, 1 if alias_final else 0, target, T))
+        return rec.size
+
+    def append_examples(self, own, opp, pi, z):
+        """finished examples in the given order: own / opp uint64 (N,), pi float32 (N, n*n), z float32 (N,) -- what read() returns"""
+        own = np.ascontiguousarray(own, dtype=np.uint64).ravel()
+        opp = np.ascontiguousarray(opp, dtype=np.uint64).ravel()
+        N = own.size
+        pi = np.ascontiguousarray(pi, dtype=np.float32).reshape(N, self.n * self.n)
+        z = np.ascontiguousarray(z, dtype=np.float32).reshape(N)
+        assert opp.size == N, (opp.size, N)
+        _lib.check(_lib.load().oz_replay_append_examples(self._h, _lib.p_u64(own), _lib.p_u64(opp), _lib.p_f32(pi), _lib.p_f32(z), N))
+
+    def read(self, first=0, count=None):
+        """slots [first, first + count) (default: every held slot from `first` on) -> (own, opp, pi (count, n*n), z)"""
+        first = int(first)
+        count = len(self) - first if count is None else int(count)
+        k = max(count, 0)
+        own, opp = np.zeros(k, np.uint64), np.zeros(k, np.uint64)
+        pi, z = np.zeros((k, self.n * self.n), np.float32), np.zeros(k, np.float32)
+        _lib.check(_lib.load().oz_replay_read(self._h, first, count, _lib.p_u64(own), _lib.p_u64(opp), _lib.p_f32(pi), _lib.p_f32(z)))
+        return own, opp, pi, z
+
+    def save(self, path):
+        """one .npz: the held examples in AGE order (oldest first) plus board size, capacity and total"""
+        held, cap, total = self.info()
+        own, opp, pi, z = self.read(0, held)
+        age = (np.arange(total - held, total) % cap).astype(np.int64)          # slot of the i-th oldest held example
+        with open(path, "wb") as f:
+            np.savez(f, own=own[age], opp=opp[age], pi=pi[age], z=z[age], board_size=np.int64(self.n), capacity=np.int64(cap),
+                     total=np.int64(total))
+
+    @classmethod
+    def load(cls, path, capacity=None):
+        """a buffer with the slot layout, contents and `total` of the saved one.  capacity: the saved one's unless given -- a smaller one
+        keeps the newest examples; a larger one than a buffer that had already wrapped restarts the running index at the number kept
+        (the overwritten examples are gone)"""
+        with np.load(path, allow_pickle=False) as f:
+            own, opp, pi, z = (np.ascontiguousarray(f[k]) for k in ("own", "opp", "pi", "z"))
+            n, cap, total = int(f["board_size"]), int(f["capacity"]), int(f["total"])
+        buf = cls(n, cap if capacity is None else capacity)
+        keep = min(own.size, buf.capacity)
+        if keep < min(total, buf.capacity):
+            total = keep
+        first = own.size - keep
+        own = np.ascontiguousarray(own[first:], dtype=np.uint64)
+        opp = np.ascontiguousarray(opp[first:], dtype=np.uint64)
+        pi = np.ascontiguousarray(pi.reshape(-1, n * n)[first:], dtype=np.float32)
+        z = np.ascontiguousarray(z[first:], dtype=np.float32)
+        _lib.check(_lib.load().oz_replay_restore(buf._h, _lib.p_u64(own), _lib.p_u64(opp), _lib.p_f32(pi), _lib.p_f32(z), keep, total))
+        return buf

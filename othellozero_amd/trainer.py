@@ -121,6 +121,13 @@ class Trainer:
         _lib.check(_lib.load().oz_trainer_fit_epoch(self._h, _lib.p_i32(order), order.size, int(batch_size), _lib.p_f32(out)))
         return out
 
+    def fit_epoch_replay(self, replay, order, batch_size):
+        """fit_epoch with a ReplayBuffer's slots as the resident examples: order = slot indices in [0, len(replay))"""
+        order = np.ascontiguousarray(order, dtype=np.int32)
+        out = np.zeros(3, np.float32)
+        _lib.check(_lib.load().oz_trainer_fit_epoch_replay(self._h, replay._h, _lib.p_i32(order), order.size, int(batch_size), _lib.p_f32(out)))
+        return out
+
     def apply(self):
         _lib.check(_lib.load().oz_trainer_apply(self._h))
 
@@ -163,6 +170,29 @@ def pack_examples(examples, board_size, in_channels=2):
     return own, opp, pi, z
 
 
+def _record_epoch(hist, ep, epochs, means, verbose):
+    for k, val in zip(("loss", "pi-reshaped_loss", "v_loss"), means):
+        hist.history[k].append(float(val))
+    hist.epoch.append(ep)
+    if verbose:
+        print(f"Epoch {ep + 1}/{epochs} - loss: {hist.history['loss'][-1]:.4f} - pi-reshaped_loss: "
+              f"{hist.history['pi-reshaped_loss'][-1]:.4f} - v_loss: {hist.history['v_loss'][-1]:.4f}")
+
+
+def fit_replay(trainer, replay, batch_size=32, epochs=10, shuffle_seed=0, verbose=None):
+    """`fit(..., resident=True)` on the examples a ReplayBuffer holds, read in place on the device (oz_trainer_fit_epoch_replay): the same
+    per-epoch order RandomState(shuffle_seed + ep).permutation(len(replay)) over the slots, the same batches, steps, weights and losses
+    as fit() on replay.read().  Single-process training."""
+    N = len(replay)
+    hist = History()
+    for ep in range(epochs if N else 0):
+        order = np.random.RandomState(shuffle_seed + ep).permutation(N)
+        means = np.asarray(trainer.fit_epoch_replay(replay, order, batch_size), dtype=np.float64)
+        _record_epoch(hist, ep, epochs, means, verbose)
+    trainer.sync()
+    return hist
+
+
 def fit(trainer, own, opp, pi, z, batch_size=32, epochs=10, shuffle_seed=0, allreduce=None, verbose=None, resident=None):
     """keras Model.fit(x, y, batch_size, epochs) with shuffle=True (the default the reference relies on).
     `allreduce(trainer)` -- if given -- averages the gradient arena across ranks between backward and apply.
@@ -202,11 +232,6 @@ def fit(trainer, own, opp, pi, z, batch_size=32, epochs=10, shuffle_seed=0, allr
                 tot += np.asarray(losses) * len(idx)            # keras reports the sample-weighted running mean
                 seen += len(idx)
             means = tot / max(seen, 1)
-        for k, val in zip(("loss", "pi-reshaped_loss", "v_loss"), means):
-            hist.history[k].append(float(val))
-        hist.epoch.append(ep)
-        if verbose:
-            print(f"Epoch {ep + 1}/{epochs} - loss: {hist.history['loss'][-1]:.4f} - pi-reshaped_loss: "
-                  f"{hist.history['pi-reshaped_loss'][-1]:.4f} - v_loss: {hist.history['v_loss'][-1]:.4f}")
+        _record_epoch(hist, ep, epochs, means, verbose)
     trainer.sync()
     return hist
