@@ -60,6 +60,25 @@ int oz_rules_status(const uint64_t* ch0, const uint64_t* ch1, int n, int count, 
 int oz_rules_play(const uint64_t* black, const uint64_t* white, const int8_t* player, const uint8_t* sq, int n,
                   int count, uint64_t* black_out, uint64_t* white_out, int8_t* player_out, uint8_t* finished_out);
 
+/* fixed-depth minimax (agents.py:27-41: GreedyOthelloAgent, dead code in the reference -- "play the move that gains the most discs" is depth 1 on
+ * the disc count).  V(P, d), from the viewpoint of P's mover: T(P) if P is finished, else E(P) if d == 0, else max over legal a of
+ * s * V(child(P, a), d - 1), the child as OthelloGame.play leaves it (s = +1 where the turn passed back, -1 otherwise; a finished child's T is taken
+ * from its stored player, with the same s).  Depth counts moves made, passes are free.  int32 throughout, antisymmetric in the mover:
+ *   OZ_MINIMAX_EVAL_DISCS     E = T = own discs - opponent discs
+ *   OZ_MINIMAX_EVAL_WEIGHTED  E = sum of w(sq) over own - sum over opponent, T = 1000 * (own - opponent); w by (a, b) = (min(min(dr, dc), 2),
+ *                             min(max(dr, dc), 2)), dr = min(r, n-1-r), dc = min(c, n-1-c): (0,0) 100, (0,1) -20, (1,1) -50, (0,2) 10, (1,2) -2,
+ *                             (2,2) 1; |E| <= 576 < 1000 on 8x8, so a decided game outranks every static value
+ * One wavefront per position, exact root values (every root move searched with a full window). */
+#define OZ_MINIMAX_EVAL_DISCS 0
+#define OZ_MINIMAX_EVAL_WEIGHTED 1
+#define OZ_MINIMAX_MAX_DEPTH 6       /* a condition, not a knob: one launch must stay short */
+#define OZ_MINIMAX_NONE INT32_MIN
+/* batch entry (agents.py:27-41): the exact root value of every legal move of `count` positions; values[count][64] by square row*8+col
+ * (OZ_MINIMAX_NONE off the legal set), bests[count] = mask of the maximal moves (0 when the mover has no move or the board is finished); any
+ * output may be NULL */
+int oz_rules_minimax(const uint64_t* black, const uint64_t* white, const int8_t* player, int n, int count, int depth, int eval,
+                     int32_t* values, uint64_t* bests);
+
 /* ------------------------------------------------------------------ network
  * NNetWrapper (Net/NNet.py:22-101) inference side; OthelloNN graph (Net/OthelloNN.py:42-56). */
 typedef struct oz_net oz_net;
@@ -445,7 +464,8 @@ int oz_selfplay_gather_visits(oz_selfplay* sp, oz_comm* comm, int64_t first_reco
  * duel_between_agents with two NeuralNetworkOthelloAgent (agents.py:44-84): net_a = BLACK, net_b = WHITE,
  * one OthelloMCTS per agent per game, temperature 0, ties broken by the RNG_TIE stream.
  * One of net_a / net_b may be NULL: that colour is played by RandomOthelloAgent (agents.py:20-24; the evaluation games of
- * main.py:163-233), its random.choice drawn from the RNG_TIE stream at that ply. */
+ * main.py:163-233), its random.choice drawn from the RNG_TIE stream at that ply.  Both may be NULL (no search at all): the opponents of
+ * oz_arena_set_opponent against each other. */
 typedef struct oz_arena oz_arena;
 int oz_arena_create(oz_arena** out, int n, int num_games, int sims, double c, int q_mode, uint64_t seed,
                     uint64_t first_game_id, oz_net* net_a, oz_net* net_b, int node_cap);
@@ -470,6 +490,16 @@ int oz_arena_set_leaves_per_step(oz_arena* a, int k_black, int k_white);
  * network launches 3 expand + backup 4 move), summed over both searches; the networks' own kernels: oz_net_profile on net_a / net_b */
 int oz_arena_profile(oz_arena* a, int enable);
 int oz_arena_profile_read(oz_arena* a, double* ms_total /* [OZ_TREE_KERNELS] */, int64_t* launches /* [OZ_TREE_KERNELS] */, int reset);
+#define OZ_AGENT_RANDOM 0
+#define OZ_AGENT_MINIMAX 1
+/* who moves for a colour whose network is NULL (agents.py:27-41; default OZ_AGENT_RANDOM, unchanged): OZ_AGENT_MINIMAX plays
+ * oz_kth_bit(bests, RNG_TIE draw of (seed, game id, ply) % popcount(bests)) with bests as oz_rules_minimax defines it -- the stream and the
+ * random.choice shape of the random mover.  Before the first run, OZ_ERR_STATE afterwards; OZ_ERR_ARG for a colour that has a network, a depth
+ * outside 1..OZ_MINIMAX_MAX_DEPTH or an unknown eval (depth and eval are not read for OZ_AGENT_RANDOM) */
+int oz_arena_set_opponent(oz_arena* a, int side /* +1 BLACK, -1 WHITE */, int kind, int depth, int eval);
+/* with oz_arena_profile on: HIP-event time and launches of the network-free colour's move kernel under OZ_AGENT_MINIMAX (agents.py:27-41;
+ * zeros for OZ_AGENT_RANDOM, whose launches are not timed) */
+int oz_arena_opponent_time(oz_arena* a, double* ms_total, int64_t* launches);
 int oz_arena_results(oz_arena* a, int8_t* winner /* +1 net_a */, int32_t* points, int32_t* n_moves,
                      uint8_t* actions /* [num_games][128] */, int8_t* players /* [num_games][128] */,
                      uint64_t* final_black, uint64_t* final_white);

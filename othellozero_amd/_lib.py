@@ -24,6 +24,9 @@ LEAF_IDLE, LEAF_TERMINAL, LEAF_EVAL = 0, 1, 2
 VT_INT, VT_F32, VT_F64 = 0, 1, 2
 MAX_LEAVES_PER_STEP = 16                                                             # OZ_MCTS_MAX_LEAVES_PER_STEP
 POLICY_LOSS_ROWS, POLICY_LOSS_FLAT = 0, 1                                            # oz_trainer_set_policy_loss
+MINIMAX_EVAL_DISCS, MINIMAX_EVAL_WEIGHTED, MINIMAX_MAX_DEPTH, MINIMAX_NONE = 0, 1, 6, -2 ** 31    # OZ_MINIMAX_*
+MINIMAX_EVALS = {"discs": MINIMAX_EVAL_DISCS, "weighted": MINIMAX_EVAL_WEIGHTED}
+AGENT_RANDOM, AGENT_MINIMAX = 0, 1                                                   # oz_arena_set_opponent
 REPLAY_TARGET_ONEHOT, REPLAY_TARGET_VISITS = 0, 1                                    # oz_replay_append_*
 NET_KERNELS = ("input", "conv2", "conv3", "conv4", "fc1", "fc2", "heads")           # OZ_NET_KERNELS slots
 TREE_KERNELS = ("select", "compact", "network", "expand_backup", "roots_move")       # OZ_TREE_KERNELS slots
@@ -76,6 +79,7 @@ SIGNATURES = {
     "oz_rules_apply_moves": [_u64p, _u64p, _u8p, C.c_int, C.c_int, _u64p, _u64p],
     "oz_rules_status": [_u64p, _u64p, C.c_int, C.c_int, _u8p, _i32p, _i32p, _i8p],
     "oz_rules_play": [_u64p, _u64p, _i8p, _u8p, C.c_int, C.c_int, _u64p, _u64p, _i8p, _u8p],
+    "oz_rules_minimax": [_u64p, _u64p, _i8p, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _u64p],      # agents.py:27-41
     "oz_net_create": [C.POINTER(_vp), C.c_int, C.c_int, C.c_int],
     "oz_net_create_bnn": [C.POINTER(_vp), C.c_int, C.c_int, C.c_int],
     "oz_net_create_stub": [C.POINTER(_vp), C.c_int, C.c_uint64, C.c_uint64, C.c_int],
@@ -135,6 +139,7 @@ SIGNATURES = {
     "oz_arena_create": [C.POINTER(_vp), C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_uint64, C.c_uint64, _vp, _vp, C.c_int],
     "oz_arena_destroy": [_vp], "oz_arena_run": [_vp], "oz_arena_run_rounds": [_vp, C.c_int], "oz_arena_stats": [_vp, _i64p, _i64p],
     "oz_arena_set_dedup": [_vp, C.c_int], "oz_arena_set_eval_cache": [_vp, C.c_int], "oz_arena_profile": [_vp, C.c_int], "oz_arena_profile_read": [_vp, _f64p, _i64p, C.c_int], "oz_arena_leaves_evaluated": [_vp, _i64p, _i64p],
+    "oz_arena_set_opponent": [_vp, C.c_int, C.c_int, C.c_int, C.c_int], "oz_arena_opponent_time": [_vp, _f64p, _i64p],      # agents.py:27-41
     "oz_arena_results": [_vp, _i8p, _i32p, _i32p, _u8p, _i8p, _u64p, _u64p],
     "oz_examples_expand": [_vp, C.c_int64, C.c_int, C.c_int, _u8p, _i32p, _i8p],
     "oz_examples_expand_visits": [_vp, _i32p, C.c_int64, C.c_int, C.c_int, C.c_double, _u8p, _f64p, _i8p],
@@ -318,6 +323,48 @@ def check_sample_moves(sample_moves):
     if not 0 <= plies <= 64:
         raise ValueError(f"sample_moves: plies must be in [0, 64] (got {plies})")
     return temperature, plies
+
+
+def check_minimax(depth, evaluation):
+    """depth and evaluation of a minimax opponent -> (int depth, OZ_MINIMAX_EVAL_* code); ValueError for anything the library would refuse
+    (depth a whole number in 1..OZ_MINIMAX_MAX_DEPTH, evaluation "discs" or "weighted")."""
+    if isinstance(depth, bool) or not isinstance(depth, (int, np.integer)) or not 1 <= depth <= MINIMAX_MAX_DEPTH:
+        raise ValueError(f"minimax: depth must be a whole number in 1..{MINIMAX_MAX_DEPTH} (got {depth!r})")
+    if not isinstance(evaluation, str) or evaluation not in MINIMAX_EVALS:
+        raise ValueError(f"minimax: evaluation must be 'discs' or 'weighted' (got {evaluation!r})")
+    return int(depth), MINIMAX_EVALS[evaluation]
+
+
+def check_opponent(opponent):
+    """opponent = None / "random" (RandomOthelloAgent), or ("minimax", depth) / ("minimax", depth, "discs" | "weighted"): who plays the colour that
+    has no network in an arena or an evaluation.  Returns None for the random mover, else (depth, OZ_MINIMAX_EVAL_* code) -- the evaluation defaults
+    to "weighted"; ValueError for anything else."""
+    if opponent is None or (isinstance(opponent, str) and opponent == "random"):
+        return None
+    if isinstance(opponent, (tuple, list)) and len(opponent) in (2, 3) and isinstance(opponent[0], str) and opponent[0] == "minimax":
+        return check_minimax(opponent[1], opponent[2] if len(opponent) == 3 else "weighted")
+    raise ValueError(f"opponent must be None, 'random', ('minimax', depth) or ('minimax', depth, 'discs' | 'weighted'), got {opponent!r}")
+
+
+def check_opponents(opponent, black_free, white_free):
+    """the `opponent` argument of an arena whose BLACK / WHITE colour has no network (black_free / white_free) -> (BLACK's, WHITE's) checked
+    opponent, each None (random mover, or a colour a network plays) or (depth, evaluation code).  One colour free: `opponent` is check_opponent's
+    argument.  Both free: None (random against random) or a dict with the keys "black" / "white", each a check_opponent argument."""
+    if isinstance(opponent, dict):
+        if set(opponent) - {"black", "white"}:
+            raise ValueError(f"opponent: a dict takes the keys 'black' and 'white' (got {sorted(map(str, opponent))})")
+        black, white = check_opponent(opponent.get("black")), check_opponent(opponent.get("white"))
+        if (black is not None and not black_free) or (white is not None and not white_free):
+            raise ValueError("opponent: a colour that has a network cannot be given a minimax opponent")
+        return black, white
+    spec = check_opponent(opponent)
+    if spec is None:
+        return None, None
+    if black_free and white_free:
+        raise ValueError("opponent: neither colour has a network; say who plays which as {'black': ..., 'white': ...}")
+    if not black_free and not white_free:
+        raise ValueError("opponent: both colours have a network, there is no colour for the minimax opponent to play")
+    return (spec, None) if black_free else (None, spec)
 
 
 def check(rc):

@@ -3,7 +3,8 @@
 `NeuralNetworkOthelloAgent` / `RandomOthelloAgent` / `duel_between_agents` keep the reference's
 behaviour (one OthelloMCTS per agent, temperature forced to 0, BLACK = agent_1, a draw goes to BLACK).
 `arena_batch` plays many deterministic best-vs-candidate games in lock step on the GPU.
-The reference's GreedyOthelloAgent is dead code (undefined names, agents.py:27-41) and is not reproduced.
+The reference's GreedyOthelloAgent is dead code (undefined names, agents.py:27-41); its intent -- play the move that gains the most discs --
+is `MinimaxOthelloAgent(game, depth=1, evaluation="discs")`, and the same fixed-depth minimax plays a colour of `arena_batch` on the device.
 """
 import ctypes as C
 import logging
@@ -31,6 +32,39 @@ class RandomOthelloAgent(OthelloAgent):
         """agents.py:20-24: one `random.choice` over the valid actions in row-major order"""
         moves = tuple(self.game.get_valid_actions())
         self.game.play(*random.choice(moves))
+
+
+def rules_minimax(black, white, player, n, depth, evaluation="weighted"):
+    """oz_rules_minimax over a batch of positions (black, white bitboards, player +1 / -1): -> (values int32 (count, 64) by square row*8+col,
+    OZ_MINIMAX_NONE off the legal set; bests uint64 (count,) = the moves of maximal root value, 0 where the mover has none)"""
+    depth, code = _lib.check_minimax(depth, evaluation)
+    black = np.ascontiguousarray(black, dtype=np.uint64).ravel()
+    white = np.ascontiguousarray(white, dtype=np.uint64).ravel()
+    player = np.ascontiguousarray(player, dtype=np.int8).ravel()
+    k = black.size
+    values, bests = np.zeros((k, 64), np.int32), np.zeros(k, np.uint64)
+    _lib.check(_lib.require_gpu().oz_rules_minimax(_lib.p_u64(black), _lib.p_u64(white), _lib.p_i8(player), n, k, depth, code,
+                                                   _lib.p_i32(values), _lib.p_u64(bests)))
+    return values, bests
+
+
+class MinimaxOthelloAgent(OthelloAgent):
+    """Fixed-depth minimax on the device (oz_rules_minimax): what the reference's GreedyOthelloAgent (agents.py:27-41, dead code) was meant to
+    be at depth=1, evaluation="discs", and harder by one integer.  One call for the game's position, then `random.choice` over the moves of
+    maximal root value in ascending row-major order (Python's own `random`, like RandomOthelloAgent)."""
+
+    def __init__(self, game, depth=3, evaluation="weighted"):
+        _lib.check_minimax(depth, evaluation)
+        super().__init__(game)
+        self.depth, self.evaluation = int(depth), evaluation
+
+    def play(self):
+        game = self.game
+        black, white = _lib.pack_board(game.board(BoardView.TWO_CHANNELS))
+        _, bests = rules_minimax([black], [white], [game.current_player.value], game.board_size, self.depth, self.evaluation)
+        mask = int(bests[0])
+        moves = tuple((s >> 3, s & 7) for s in range(64) if (mask >> s) & 1)
+        game.play(*random.choice(moves))
 
 
 class NeuralNetworkOthelloAgent(OthelloAgent):
@@ -75,9 +109,13 @@ def duel_between_agents(game, agent_1, agent_2):
 
 def arena_batch(net_a, net_b, board_size=8, num_games=512, num_simulations=800, degree_exploration=1.0, seed=0,
                 first_game_id=0, q_mode=_lib.QMODE_F64, node_cap=0, max_rounds=0, dedup=True, profile=False, eval_cache=False,
-                leaves_per_step=1):
+                leaves_per_step=1, opponent=None):
     """num_games games of net_a (BLACK) vs net_b (WHITE), temperature 0, max-visit ties broken by the RNG_TIE
-    stream keyed (seed, game id, ply).  One of the two may be None: RandomOthelloAgent plays that colour.
+    stream keyed (seed, game id, ply).  One of the two may be None: RandomOthelloAgent plays that colour, or with
+    opponent=("minimax", depth) / ("minimax", depth, "discs" | "weighted") the fixed-depth minimax (oz_arena_set_opponent; ties between its
+    best moves drawn from the same RNG_TIE stream); opponent=None / "random" is the random mover.  Both may be None (no network at all: a
+    yardstick for the opponents themselves): then opponent={"black": ..., "white": ...} says who plays which, a missing key the random mover.
+    With profile=True the result then carries opponent_kernel = (ms, launches) of the minimax move kernel.
     max_rounds > 0 stops after that many plies per game (unfinished boards: winner / points then describe the position reached).
     Returns dict(winner (+1 = BLACK's agent), points, n_moves, actions, players, final boards, stats_black / stats_white =
     the two agents' search counters [simulations, node visits, expansions, terminal hits, fallbacks], leaves_evaluated = positions the
@@ -86,6 +124,7 @@ def arena_batch(net_a, net_b, board_size=8, num_games=512, num_simulations=800, 
     leaves_per_step = k or (k_black, k_white): descents per game and network batch of the two agents' searches under virtual loss
     (oz_arena_set_leaves_per_step); an agent's network needs max_batch >= num_games * its k."""
     kb, kw = (leaves_per_step, leaves_per_step) if np.isscalar(leaves_per_step) else leaves_per_step
+    minimax = _lib.check_opponents(opponent, net_a is None, net_b is None)
     lib = _lib.require_gpu()
     h = C.c_void_p()
     _lib.check(lib.oz_arena_create(C.byref(h), board_size, num_games, num_simulations, float(degree_exploration), q_mode,
@@ -98,10 +137,17 @@ def arena_batch(net_a, net_b, board_size=8, num_games=512, num_simulations=800, 
             _lib.check(lib.oz_arena_set_eval_cache(h, 1))
         if not (np.isscalar(leaves_per_step) and leaves_per_step == 1):
             _lib.check(lib.oz_arena_set_leaves_per_step(h, int(kb), int(kw)))
+        for side, spec in zip((1, -1), minimax):             # a colour without a network
+            if spec is not None:
+                _lib.check(lib.oz_arena_set_opponent(h, side, _lib.AGENT_MINIMAX, spec[0], spec[1]))
         if profile:                                          # HIP events around the tree kernels of both searches (bench.py's config5 kernels[])
             _lib.check(lib.oz_arena_profile(h, 1))
         _lib.check(lib.oz_arena_run_rounds(h, int(max_rounds)))
-        tree = None
+        tree = opp_kernel = None
+        if profile and any(minimax):
+            ms1, cnt1 = C.c_double(), C.c_int64()
+            _lib.check(lib.oz_arena_opponent_time(h, C.byref(ms1), C.byref(cnt1)))
+            opp_kernel = (ms1.value, cnt1.value)
         if profile:
             ms, cnt = np.zeros(len(_lib.TREE_KERNELS), np.float64), np.zeros(len(_lib.TREE_KERNELS), np.int64)
             _lib.check(lib.oz_arena_profile_read(h, _lib.p_f64(ms), _lib.p_i64(cnt), 0))
@@ -119,4 +165,5 @@ def arena_batch(net_a, net_b, board_size=8, num_games=512, num_simulations=800, 
     finally:
         lib.oz_arena_destroy(h)
     return dict(winner=winner, points=points, n_moves=nm, actions=acts, players=pls, final_black=fb, final_white=fw,
-                stats_black=sa, stats_white=sb, leaves_evaluated=ea.value + eb.value, tree_kernels=tree)
+                stats_black=sa, stats_white=sb, leaves_evaluated=ea.value + eb.value, tree_kernels=tree,
+                **({"opponent_kernel": opp_kernel} if any(minimax) else {}))

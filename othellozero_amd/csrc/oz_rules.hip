@@ -1,10 +1,12 @@
 // oz_rules.hip -- library core (errors, device selection), batched rule kernels (K1-K3) and the
 // dihedral symmetry expansion of training examples (K8).  HBM-bound integer/byte work: one thread
-// per position / per output example, SoA inputs, coalesced loads and stores.
+// per position / per output example, SoA inputs, coalesced loads and stores.  Plus the batch entry of
+// the fixed-depth minimax (one wavefront per position, oz_minimax.h).
 #include <stdarg.h>
 #include <string.h>
 
 #include "oz_internal.h"
+#include "oz_minimax.h"
 
 // ---------------------------------------------------------------- errors / device
 static thread_local char g_err[512] = "";
@@ -195,6 +197,41 @@ OZ_API int oz_rules_play(const uint64_t* black, const uint64_t* white, const int
         },
         [&](const unsigned char* h) {
             memcpy(black_out, h, c8); memcpy(white_out, h + c8, c8); memcpy(player_out, h + 2 * c8, count); memcpy(finished_out, h + 2 * c8 + c1, count);
+        });
+}
+
+// ---------------------------------------------------------------- minimax (agents.py:27-41, the greedy agent's intent, made deeper by one integer)
+// one 64-lane block per position (oz_minimax.h): values[i][sq] = exact root value of the move on sq, bests[i] = the maximal moves
+__global__ __launch_bounds__(64) void k_minimax(const uint64_t* __restrict__ black, const uint64_t* __restrict__ white, const int8_t* __restrict__ player,
+                                                uint64_t valid, int depth, MinimaxEval ev, int32_t* __restrict__ values, uint64_t* __restrict__ bests) {
+    __shared__ MinimaxLds L;
+    const int i = blockIdx.x, lane = threadIdx.x;
+    uint64_t b = 0;
+    const int v = mm_root(L, ev, valid, lane, black[i], white[i], player[i], depth, &b);
+    values[(size_t)i * 64 + lane] = v;
+    if (lane == 0) bests[i] = b;
+}
+
+OZ_API int oz_rules_minimax(const uint64_t* black, const uint64_t* white, const int8_t* player, int n, int count, int depth, int eval,
+                            int32_t* values, uint64_t* bests) {
+    if (int rc = check_n(n)) return rc;
+    OZ_REQUIRE(depth >= 1 && depth <= OZ_MINIMAX_MAX_DEPTH, "oz_rules_minimax: depth %d outside 1..%d", depth, OZ_MINIMAX_MAX_DEPTH);
+    OZ_REQUIRE(eval == OZ_MINIMAX_EVAL_DISCS || eval == OZ_MINIMAX_EVAL_WEIGHTED, "oz_rules_minimax: unknown evaluation %d", eval);
+    if (count <= 0) return OZ_OK;
+    OZ_REQUIRE(black && white && player, "null argument");
+    for (int i = 0; i < count; ++i) OZ_REQUIRE(player[i] == 1 || player[i] == -1, "player must be +1 or -1");
+    const size_t c8 = 8ull * count, c1 = pad8(count), cv = 256ull * count;
+    const MinimaxEval ev = oz_minimax_eval_make(n, eval);
+    // output image: values | bests
+    return rules_call(2 * c8 + c1, cv + c8,
+        [&](unsigned char* h) { memcpy(h, black, c8); memcpy(h + c8, white, c8); memcpy(h + 2 * c8, player, count); },
+        [&](unsigned char* di, unsigned char* dout, hipStream_t s) {
+            hipLaunchKernelGGL(k_minimax, dim3(count), dim3(64), 0, s, (const uint64_t*)di, (const uint64_t*)(di + c8), (const int8_t*)(di + 2 * c8),
+                               oz_valid_mask(n), depth, ev, (int32_t*)dout, (uint64_t*)(dout + cv));
+        },
+        [&](const unsigned char* h) {
+            if (values) memcpy(values, h, cv);
+            if (bests) memcpy(bests, h + cv, c8);
         });
 }
 

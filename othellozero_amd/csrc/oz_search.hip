@@ -24,6 +24,7 @@
 #include <string.h>
 
 #include "oz_internal.h"
+#include "oz_minimax.h"
 
 enum { VT_INT = 0, VT_F32 = 1, VT_F64 = 2 };
 #define OZ_MAX_DEPTH 64
@@ -1920,6 +1921,29 @@ __global__ void k_arena_random_move(GamesDev gm, int side) {
     atomicAdd(&gm.counters[2], 1ULL);
 }
 
+// The minimax opponent (agents.py:27-41, oz_minimax.h) in k_arena_random_move's place: one wave per game, the move = the RNG_TIE choice among the
+// moves of maximal root value; the same move log, oz_game_play, ply and move counter.
+__global__ __launch_bounds__(64) void k_arena_minimax_move(GamesDev gm, int side, int depth, MinimaxEval ev) {
+    __shared__ MinimaxLds L;
+    const int g = blockIdx.x, lane = threadIdx.x;
+    if (gm.finished[g] || gm.player[g] != side) return;                 // block-uniform
+    uint64_t black = gm.black[g], white = gm.white[g], bests = 0;
+    mm_root(L, ev, gm.valid, lane, black, white, side, depth, &bests);
+    if (lane != 0 || bests == 0) return;                                // (a live game's mover always has a move)
+    int player = side, fin = 0;
+    const int ply = gm.ply[g];
+    const int action = oz_kth_bit(bests, (int)(oz_rng(gm.seed, gm.game_id[g], (uint64_t)ply, OZ_RNG_TIE) % (uint64_t)oz_popc(bests)));
+    const size_t lb = (size_t)g * 64;
+    if (ply < 64) {
+        gm.log_black[lb + ply] = black; gm.log_white[lb + ply] = white;
+        gm.log_action[lb + ply] = (uint8_t)action; gm.log_player[lb + ply] = (int8_t)player; gm.log_greedy[lb + ply] = 0;
+    }
+    oz_game_play(black, white, player, fin, action, gm.valid);
+    gm.black[g] = black; gm.white[g] = white; gm.player[g] = (int8_t)player;
+    gm.finished[g] = (uint8_t)fin; gm.ply[g] = ply + 1;
+    atomicAdd(&gm.counters[2], 1ULL);
+}
+
 static void initial_board(int n, uint64_t* black, uint64_t* white) {     // Othello/__init__.py:177-184
     const int h = n / 2;
     *white = (1ULL << ((h - 1) * 8 + h - 1)) | (1ULL << (h * 8 + h));
@@ -2360,6 +2384,9 @@ struct oz_arena {
     int* d_movers = nullptr;     // [2] live games with BLACK / WHITE to move (k_arena_movers)
     bool started = false;        // oz_arena_run / oz_arena_run_rounds has been called
     int eval_cache = 0;          // oz_arena_set_eval_cache: the two searches look their leaves up in (and insert them into) their networks' evaluation caches
+    // oz_arena_set_opponent: who moves for the colour without a network ([0] BLACK, [1] WHITE)
+    int opp_kind[2] = {OZ_AGENT_RANDOM, OZ_AGENT_RANDOM}, opp_depth[2] = {1, 1}, opp_eval[2] = {OZ_MINIMAX_EVAL_DISCS, OZ_MINIMAX_EVAL_DISCS};
+    OzTimer opp_timer{1};        // k_arena_minimax_move, with oz_arena_profile on
 };
 
 // live games per mover: counts[0] = BLACK to move, counts[1] = WHITE to move (an agent with nothing to move this round is not launched)
@@ -2387,7 +2414,7 @@ __global__ void k_arena_collect(GamesDev gm, uint8_t* actions, int8_t* players, 
 
 OZ_API int oz_arena_create(oz_arena** out, int n, int num_games, int sims, double c, int q_mode, uint64_t seed,
                            uint64_t first_game_id, oz_net* net_a, oz_net* net_b, int node_cap) {
-    OZ_REQUIRE(out && (net_a || net_b), "null argument (at most one of the two networks may be NULL = RandomOthelloAgent)");
+    OZ_REQUIRE(out, "null argument");            // a NULL network = that colour is played by RandomOthelloAgent or by oz_arena_set_opponent's choice
     OZ_REQUIRE(sims >= 2, "num_simulations must be >= 2");
     OZ_REQUIRE((!net_a || net_a->n == n) && (!net_b || net_b->n == n), "network board size mismatch");
     OZ_REQUIRE((!net_a || net_a->max_batch >= num_games) && (!net_b || net_b->max_batch >= num_games), "network max_batch < num_games");
@@ -2434,6 +2461,7 @@ OZ_API int oz_arena_destroy(oz_arena* a) {
     for (void* p : a->games.allocs) hipFree(p);
     mcts_destroy(a->games.m); mcts_destroy(a->mb);
     hipFree(a->d_actions); hipFree(a->d_players); hipFree(a->d_nmoves); hipFree(a->d_movers);
+    a->opp_timer.destroy();
     delete a;
     return OZ_OK;
 }
@@ -2517,6 +2545,46 @@ OZ_API int oz_arena_set_leaves_per_step(oz_arena* a, int k_black, int k_white) {
     return wide_set_k(a->mb, k_white);
 }
 
+// the mover of a colour without a network (default OZ_AGENT_RANDOM = RandomOthelloAgent); before the first run
+OZ_API int oz_arena_set_opponent(oz_arena* a, int side, int kind, int depth, int eval) {
+    OZ_REQUIRE(a, "null arena");
+    OZ_REQUIRE(side == 1 || side == -1, "oz_arena_set_opponent: side must be +1 (BLACK) or -1 (WHITE), got %d", side);
+    OZ_REQUIRE(kind == OZ_AGENT_RANDOM || kind == OZ_AGENT_MINIMAX, "oz_arena_set_opponent: unknown agent kind %d", kind);
+    OZ_REQUIRE(!(side == 1 ? a->na : a->nb), "oz_arena_set_opponent: %s is played by a network", side == 1 ? "BLACK" : "WHITE");
+    if (kind == OZ_AGENT_MINIMAX) {
+        OZ_REQUIRE(depth >= 1 && depth <= OZ_MINIMAX_MAX_DEPTH, "oz_arena_set_opponent: depth %d outside 1..%d", depth, OZ_MINIMAX_MAX_DEPTH);
+        OZ_REQUIRE(eval == OZ_MINIMAX_EVAL_DISCS || eval == OZ_MINIMAX_EVAL_WEIGHTED, "oz_arena_set_opponent: unknown evaluation %d", eval);
+    }
+    std::lock_guard<std::mutex> lk(a->mu);
+    if (a->started) { oz_set_error("oz_arena_set_opponent: the arena has run already (set it before the first run)"); return OZ_ERR_STATE; }
+    const int i = side == 1 ? 0 : 1;
+    a->opp_kind[i] = kind;
+    if (kind == OZ_AGENT_MINIMAX) { a->opp_depth[i] = depth; a->opp_eval[i] = eval; }
+    return OZ_OK;
+}
+OZ_API int oz_arena_opponent_time(oz_arena* a, double* ms_total, int64_t* launches) {
+    OZ_REQUIRE(a, "null arena");
+    std::lock_guard<std::mutex> lk(a->mu);
+    hipSetDevice(a->games.m->device);
+    if (a->opp_timer.collect()) { oz_set_error("oz_arena_opponent_time: event timing failed"); return OZ_ERR_HIP; }
+    if (ms_total) *ms_total = a->opp_timer.ms[0];
+    if (launches) *launches = a->opp_timer.count[0];
+    return OZ_OK;
+}
+
+// the move of the colour `side` that has no network: RandomOthelloAgent, or the minimax opponent oz_arena_set_opponent chose
+static void arena_opponent_move(oz_arena* a, int side, hipStream_t s) {
+    const GamesDev& gm = a->games.gm;
+    const int i = side == 1 ? 0 : 1;
+    if (a->opp_kind[i] == OZ_AGENT_RANDOM) {
+        hipLaunchKernelGGL(k_arena_random_move, dim3((gm.G + 255) / 256), dim3(256), 0, s, gm, side);
+        return;
+    }
+    const long long h = a->games.m->profile ? a->opp_timer.begin(0, s) : -1;
+    hipLaunchKernelGGL(k_arena_minimax_move, dim3(gm.G), dim3(64), 0, s, gm, side, a->opp_depth[i], oz_minimax_eval_make(gm.n, a->opp_eval[i]));
+    a->opp_timer.end(h, s);
+}
+
 OZ_API int oz_arena_run_rounds(oz_arena* a, int max_rounds_arg) {
     OZ_REQUIRE(a, "null arena");
     OZ_REQUIRE(max_rounds_arg >= 0, "oz_arena_run_rounds: max_rounds %d", max_rounds_arg);
@@ -2541,8 +2609,8 @@ OZ_API int oz_arena_run_rounds(oz_arena* a, int max_rounds_arg) {
         // BLACK movers search in agent A's tables with net A, WHITE movers in agent B's with net B
         // a NULL network = RandomOthelloAgent on that colour: it moves first in the round (a game may then play two plies
         // in one round, which changes nothing: games are independent and every ply is keyed by (game id, ply))
-        if (!a->na) hipLaunchKernelGGL(k_arena_random_move, dim3((G + 255) / 256), dim3(256), 0, s, sp->gm, 1);
-        if (!a->nb) hipLaunchKernelGGL(k_arena_random_move, dim3((G + 255) / 256), dim3(256), 0, s, sp->gm, -1);
+        if (!a->na) arena_opponent_move(a, 1, s);
+        if (!a->nb) arena_opponent_move(a, -1, s);
         // who has to move?  Without passes every game of a round has the same mover, so one of the two agents has nothing to search: its
         // a->sims steps (11 launches each over zero leaves) are skipped -- one 8-byte read-back per round buys ~10 % at 800 sims per move.
         // (Round 5, measured and removed: BOTH agents in every round -- the odd slots held back one ply, agent A's and agent B's chains on two

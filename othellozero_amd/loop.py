@@ -28,7 +28,7 @@ import random
 import numpy as np
 
 from . import _lib
-from .agents import NeuralNetworkOthelloAgent, RandomOthelloAgent, arena_batch, duel_between_agents
+from .agents import MinimaxOthelloAgent, NeuralNetworkOthelloAgent, RandomOthelloAgent, arena_batch, duel_between_agents
 from .Othello import OthelloGame, OthelloPlayer
 from .training import expand_examples, selfplay_batch
 
@@ -103,9 +103,11 @@ def examples_from_records(records, board_size, alias_final=True, in_channels=2, 
     return out
 
 
-def evaluate_against_random(board_size, neural_network, games, num_simulations, degree_exploration, label="Network"):
+def evaluate_against_random(board_size, neural_network, games, num_simulations, degree_exploration, label="Network", opponent=None):
     """main.py:163-192 / :197-233: `games` duels against RandomOthelloAgent, colours drawn by random.shuffle.
+    opponent=("minimax", depth[, "discs" | "weighted"]): against MinimaxOthelloAgent instead (None / "random": the random agent).
     -> dict(wins, black_wins, black_games, white_wins, white_games)"""
+    minimax = _lib.check_opponent(opponent)
     r = dict(wins=0, black_wins=0, black_games=0, white_wins=0, white_games=0)
     if getattr(neural_network, "max_batch", 1) > 32 and hasattr(neural_network, "get_weights"):
         # one position per call: a twin with max_batch 1 takes the library's latency path (k loops split over idle CUs)
@@ -116,7 +118,8 @@ def evaluate_against_random(board_size, neural_network, games, num_simulations, 
     for k in range(games):
         game = OthelloGame(board_size, current_player=OthelloPlayer.BLACK)
         nn_agent = NeuralNetworkOthelloAgent(game, neural_network, num_simulations, degree_exploration)
-        random_agent = RandomOthelloAgent(game)
+        random_agent = (RandomOthelloAgent(game) if minimax is None else
+                        MinimaxOthelloAgent(game, minimax[0], "discs" if minimax[1] == _lib.MINIMAX_EVAL_DISCS else "weighted"))
         agents = [nn_agent, random_agent]
         random.shuffle(agents)
         agent_winner, points = duel_between_agents(game, *agents)
@@ -131,25 +134,39 @@ def evaluate_against_random(board_size, neural_network, games, num_simulations, 
     return r
 
 
-def evaluate_against_random_batch(board_size, neural_network, games, num_simulations, degree_exploration, seed=0, leaves_per_step=1):
+def evaluate_against_random_batch(board_size, neural_network, games, num_simulations, degree_exploration, seed=0, leaves_per_step=1,
+                                  opponent=None):
     """The same evaluation as `evaluate_against_random` played in lock step on the GPU (agents.arena_batch with a random
     mover): the network takes BLACK in the first games // 2 + games % 2 games and WHITE in the rest (the reference draws the
-    colours with random.shuffle; the split here is fixed).  -> dict(wins, black_wins, black_games, white_wins, white_games)"""
+    colours with random.shuffle; the split here is fixed).  opponent: arena_batch's (None / "random", or ("minimax", depth[, evaluation])).
+    -> dict(wins, black_wins, black_games, white_wins, white_games)"""
+    _lib.check_opponent(opponent)
     as_black, as_white = games // 2 + games % 2, games // 2
     r = dict(wins=0, black_wins=0, black_games=0, white_wins=0, white_games=0)
     if as_black:
         res = arena_batch(neural_network, None, board_size, as_black, num_simulations, degree_exploration, seed=seed,
-                          leaves_per_step=leaves_per_step)
+                          leaves_per_step=leaves_per_step, opponent=opponent)
         r["black_wins"] = int((res["winner"] == 1).sum())
     if as_white:
         res = arena_batch(None, neural_network, board_size, as_white, num_simulations, degree_exploration, seed=seed, first_game_id=as_black,
-                          leaves_per_step=leaves_per_step)
+                          leaves_per_step=leaves_per_step, opponent=opponent)
         r["white_wins"] = int((res["winner"] == -1).sum())
         r["black_games"] = as_white - r["white_wins"]              # games BLACK (the random agent) won
     r["white_games"] = r["white_wins"] + (as_black - r["black_wins"])
     r["black_games"] += r["black_wins"]
     r["wins"] = r["black_wins"] + r["white_wins"]
     return r
+
+
+def evaluate_against_opponent(board_size, neural_network, games, num_simulations, degree_exploration, opponent, label="Network"):
+    """`evaluate_against_random` under the name that says what it does when the opponent is not the random agent"""
+    return evaluate_against_random(board_size, neural_network, games, num_simulations, degree_exploration, label=label, opponent=opponent)
+
+
+def evaluate_against_opponent_batch(board_size, neural_network, games, num_simulations, degree_exploration, opponent, seed=0, leaves_per_step=1):
+    """`evaluate_against_random_batch` under the name that says what it does when the opponent is not the random agent"""
+    return evaluate_against_random_batch(board_size, neural_network, games, num_simulations, degree_exploration, seed=seed,
+                                         leaves_per_step=leaves_per_step, opponent=opponent)
 
 
 def self_play_match(board_size, neural_network, old_neural_network, total_games, num_simulations, degree_exploration, seed=0,
@@ -191,7 +208,7 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
              self_play_interval, self_play_total_games, self_play_threshold, checkpoint_filepath, training_buffer_size,
              seed=1234, reference_aliasing=True, alias_final_boards=True, dump_examples=False, q_mode=_lib.QMODE_F64,
              distributed=False, batched_evaluation=False, policy_target="onehot", target_temperature=1.0, leaves_per_step=1,
-             root_noise=None, sample_moves=None, replay="host"):
+             root_noise=None, sample_moves=None, replay="host", evaluation_opponent="random"):
     """main.py:56-259 on the GPU engines; returns `historic` = [(episodes done, win rate vs random), ...]
 
     batched_evaluation=True plays the evaluation games against RandomOthelloAgent in lock step on the GPU
@@ -223,7 +240,13 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
     (ReplayBuffer.append_engine) and the network trains from the buffer in place (NNetWrapper.train(replay)): no example tuples, no
     random.shuffle of examples (the fit draws its own order per epoch).  The ring overwrites the OLDEST example, where the default "host"
     path keeps the reference's CircularArray + random.shuffle (which overwrites random survivors).  Matches, evaluation and promotion
-    are unchanged.  Single-process, and there is no tuple list to dump: not with distributed=True or dump_examples=True."""
+    are unchanged.  Single-process, and there is no tuple list to dump: not with distributed=True or dump_examples=True.
+
+    evaluation_opponent="random" (RandomOthelloAgent, the reference's yardstick) or ("minimax", depth) / ("minimax", depth, "discs" | "weighted"):
+    who the evaluation games at `evaluation_interval` are played against, in the drop-in and the batched evaluation alike.  A network that
+    wins 91 % of its games against the random agent can never be kept by the `new > old * 1.1` rule again; a fixed-depth minimax (depth 1 on
+    "discs" is the reference's GreedyOthelloAgent, agents.py:27-41) is the harder opponent.  Matches between networks and self-play are untouched."""
+    _lib.check_opponent(evaluation_opponent)
     if replay not in ("host", "device"):
         raise ValueError(f"replay must be 'host' or 'device' (got {replay!r})")
     if replay == "device" and distributed:
@@ -337,18 +360,21 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
             save(neural_network)
 
         if i % evaluation_interval == 0:
-            logging.info('[%d/%d] evaluation against the random agent: current network', i, num_iterations)
+            logging.info('[%d/%d] evaluation against %s: current network', i, num_iterations,
+                         'the random agent' if _lib.check_opponent(evaluation_opponent) is None else f'{evaluation_opponent!r}')
             if batched_evaluation:
                 new = evaluate_against_random_batch(board_size, neural_network, evaluation_iterations, num_simulations,
-                                                    degree_exploration, seed=seed + 7919 * i, leaves_per_step=leaves_per_step)
+                                                    degree_exploration, seed=seed + 7919 * i, leaves_per_step=leaves_per_step,
+                                                    opponent=evaluation_opponent)
                 old = evaluate_against_random_batch(board_size, old_neural_network, evaluation_iterations, num_simulations,
-                                                    degree_exploration, seed=seed + 7919 * i + 1, leaves_per_step=leaves_per_step)
+                                                    degree_exploration, seed=seed + 7919 * i + 1, leaves_per_step=leaves_per_step,
+                                                    opponent=evaluation_opponent)
             else:
                 new = evaluate_against_random(board_size, neural_network, evaluation_iterations, num_simulations, degree_exploration,
-                                              label=f'after {total_episodes_done} episodes, current network')
+                                              label=f'after {total_episodes_done} episodes, current network', opponent=evaluation_opponent)
                 logging.info('[%d/%d] evaluation against the random agent: previous network', i, num_iterations)
                 old = evaluate_against_random(board_size, old_neural_network, evaluation_iterations, num_simulations, degree_exploration,
-                                              label=f'after {total_episodes_done} episodes, previous network')
+                                              label=f'after {total_episodes_done} episodes, previous network', opponent=evaluation_opponent)
             if new["wins"] > (old["wins"] * 1.1):
                 logging.info('[%d/%d] evaluation: current network kept (%d wins vs %d)', i, num_iterations, new['wins'], old['wins'])
                 historic.append((total_episodes_done, (new["wins"] / evaluation_iterations)))
