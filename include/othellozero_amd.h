@@ -79,6 +79,23 @@ int oz_rules_play(const uint64_t* black, const uint64_t* white, const int8_t* pl
 int oz_rules_minimax(const uint64_t* black, const uint64_t* white, const int8_t* player, int n, int count, int depth, int eval,
                      int32_t* values, uint64_t* bests);
 
+/* exact endgame solver (the reference has none: it trains on played outcomes only).  S(P), from the viewpoint of P's mover: own discs - opponent
+ * discs if P is finished, else max over legal a of s * S(child(P, a)), the child as OthelloGame.play leaves it (s = +1 where the turn passed back,
+ * -1 otherwise): oz_rules_minimax on OZ_MINIMAX_EVAL_DISCS without a horizon, on the library's own rules (flip-through and pass logic included);
+ * empties are not awarded to the winner.  One wavefront per position; every root move's value is exact, not a bound. */
+#define OZ_SOLVE_MAX_EMPTIES 12      /* a condition, not a knob: a whole 4x4 game, a 12-ply 8x8 endgame; the frame stack in LDS is sized by it */
+/* batch entry: values[count][64] = S after the move on each legal square (OZ_MINIMAX_NONE elsewhere), bests[count] = mask of the maximal moves,
+ * value[count] = S of the position, solved[count] = 1.  A position with more than max_empties empties (n*n - popcount(black | white)) is
+ * skipped, not refused: solved 0, values all OZ_MINIMAX_NONE, bests 0, value 0.  A finished board or a mover without a move is solved with
+ * bests 0 and no move value; its value is that of the finished board, or of the position after the pass.  Any output may be NULL.
+ * OZ_ERR_ARG: max_empties outside 0..OZ_SOLVE_MAX_EMPTIES, a player that is not +1 / -1, discs off the n x n board or on one square twice. */
+int oz_rules_solve(const uint64_t* black, const uint64_t* white, const int8_t* player, int n, int count, int max_empties,
+                   int32_t* values /* [count][64] */, uint64_t* bests /* [count] */, int32_t* value /* [count] */, uint8_t* solved /* [count] */);
+/* HIP-event timing of the kernel of every oz_rules_* batch call on the current device (default off: nothing is recorded); the read returns
+ * the total since creation / the last reset and the number of launches (each may be NULL) */
+int oz_rules_profile(int enable);
+int oz_rules_profile_read(double* ms_total, int64_t* launches, int reset);
+
 /* ------------------------------------------------------------------ network
  * NNetWrapper (Net/NNet.py:22-101) inference side; OthelloNN graph (Net/OthelloNN.py:42-56). */
 typedef struct oz_net oz_net;
@@ -432,6 +449,22 @@ int oz_selfplay_records_device(oz_selfplay* sp, void* dst_device, int64_t max_re
 int oz_selfplay_visits(oz_selfplay* sp, int32_t* out /* [max_records][64] */, int64_t max_records, int64_t* written);
 /* same, device to device */
 int oz_selfplay_visits_device(oz_selfplay* sp, void* dst_device, int64_t max_records, int64_t* written);
+/* exact value targets for the endgame records (opt-in; never called, every record stays bit for bit): the completed records
+ * [first_record, completed so far) of the engine, in place on the device, one wavefront per record.  The position solved is the board BEFORE
+ * the move (black, white, player), never the aliased final board.  A record with at most max_empties empties gets z = +1 if S > 0, -1 if
+ * S < 0, and for S == 0 z = +1 if the mover is BLACK, else -1 (the draw -> BLACK convention of oz_record.z); its disc loss is
+ * S - values[action] >= 0.  No other byte of a record, no visit-count row and no record above the cap changes; a second call finds
+ * z_changed == 0.  Waits for the engine's stream like oz_selfplay_records.  OZ_ERR_ARG: max_empties outside 1..OZ_SOLVE_MAX_EMPTIES,
+ * first_record < 0; OZ_ERR_STATE: a step is pending. */
+typedef struct {
+    int64_t records;        /* records looked at */
+    int64_t solved;         /* of them, at or below max_empties */
+    int64_t z_changed;      /* solved records whose z was rewritten */
+    int64_t optimal_moves;  /* solved records whose move has the maximal value (disc loss 0) */
+    int64_t disc_loss_sum;  /* sum of S - values[action] over the solved records */
+    int32_t disc_loss_max, pad;
+} oz_endgame_stats;
+int oz_selfplay_solve_records(oz_selfplay* sp, int64_t first_record, int max_empties, oz_endgame_stats* stats /* optional */);
 /* root visit counts of the last move round, counts[num_games][64] (parity tests) */
 int oz_selfplay_last_counts(oz_selfplay* sp, int32_t* counts);
 /* HIP-event time of the evaluator (NN) launches since creation, and their count */

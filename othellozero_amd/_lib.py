@@ -26,6 +26,7 @@ MAX_LEAVES_PER_STEP = 16                                                        
 POLICY_LOSS_ROWS, POLICY_LOSS_FLAT = 0, 1                                            # oz_trainer_set_policy_loss
 MINIMAX_EVAL_DISCS, MINIMAX_EVAL_WEIGHTED, MINIMAX_MAX_DEPTH, MINIMAX_NONE = 0, 1, 6, -2 ** 31    # OZ_MINIMAX_*
 MINIMAX_EVALS = {"discs": MINIMAX_EVAL_DISCS, "weighted": MINIMAX_EVAL_WEIGHTED}
+SOLVE_MAX_EMPTIES = 12                                                               # OZ_SOLVE_MAX_EMPTIES
 AGENT_RANDOM, AGENT_MINIMAX = 0, 1                                                   # oz_arena_set_opponent
 REPLAY_TARGET_ONEHOT, REPLAY_TARGET_VISITS = 0, 1                                    # oz_replay_append_*
 NET_KERNELS = ("input", "conv2", "conv3", "conv4", "fc1", "fc2", "heads")           # OZ_NET_KERNELS slots
@@ -62,6 +63,13 @@ class SelfplayStats(C.Structure):
     ]
 
 
+class EndgameStats(C.Structure):                                                     # oz_endgame_stats
+    _fields_ = [
+        ("records", C.c_int64), ("solved", C.c_int64), ("z_changed", C.c_int64), ("optimal_moves", C.c_int64), ("disc_loss_sum", C.c_int64),
+        ("disc_loss_max", C.c_int32), ("pad", C.c_int32),
+    ]
+
+
 # numpy view of oz_record (48 bytes)
 RECORD_DTYPE = np.dtype([
     ("black", "<u8"), ("white", "<u8"), ("final_black", "<u8"), ("final_white", "<u8"), ("game_id", "<u8"),
@@ -80,6 +88,9 @@ SIGNATURES = {
     "oz_rules_status": [_u64p, _u64p, C.c_int, C.c_int, _u8p, _i32p, _i32p, _i8p],
     "oz_rules_play": [_u64p, _u64p, _i8p, _u8p, C.c_int, C.c_int, _u64p, _u64p, _i8p, _u8p],
     "oz_rules_minimax": [_u64p, _u64p, _i8p, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _u64p],      # agents.py:27-41
+    "oz_rules_solve": [_u64p, _u64p, _i8p, C.c_int, C.c_int, C.c_int, _i32p, _u64p, _i32p, _u8p],
+    "oz_rules_profile": [C.c_int], "oz_rules_profile_read": [_f64p, _i64p, C.c_int],
+    "oz_selfplay_solve_records": [_vp, C.c_int64, C.c_int, C.POINTER(EndgameStats)],
     "oz_net_create": [C.POINTER(_vp), C.c_int, C.c_int, C.c_int],
     "oz_net_create_bnn": [C.POINTER(_vp), C.c_int, C.c_int, C.c_int],
     "oz_net_create_stub": [C.POINTER(_vp), C.c_int, C.c_uint64, C.c_uint64, C.c_int],
@@ -333,6 +344,23 @@ def check_minimax(depth, evaluation):
     if not isinstance(evaluation, str) or evaluation not in MINIMAX_EVALS:
         raise ValueError(f"minimax: evaluation must be 'discs' or 'weighted' (got {evaluation!r})")
     return int(depth), MINIMAX_EVALS[evaluation]
+
+
+def check_solve_empties(empties, least=0, what="max_empties"):
+    """the empties bound of the exact endgame solver -> int; ValueError for anything the library would refuse (a whole number in
+    least..OZ_SOLVE_MAX_EMPTIES; least is 0 where 0 means "off" or "finished boards only", 1 for oz_selfplay_solve_records)."""
+    if isinstance(empties, bool) or not isinstance(empties, (int, np.integer)) or not least <= empties <= SOLVE_MAX_EMPTIES:
+        raise ValueError(f"endgame solver: {what} must be a whole number in {least}..{SOLVE_MAX_EMPTIES} (got {empties!r})")
+    return int(empties)
+
+
+def check_endgame_targets(endgame_targets, alias_final_boards):
+    """training(endgame_targets=E) -> int E; 0 is off.  E > 0 needs alias_final_boards=False: an exact value belongs to the position of the move."""
+    e = check_solve_empties(endgame_targets, 0, "endgame_targets")
+    if e > 0 and alias_final_boards:
+        raise ValueError("endgame_targets needs alias_final_boards=False: an exact value belongs to the position of its move, not to the "
+                         "game's final position")
+    return e
 
 
 def check_opponent(opponent):

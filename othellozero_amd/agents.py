@@ -48,20 +48,42 @@ def rules_minimax(black, white, player, n, depth, evaluation="weighted"):
     return values, bests
 
 
+def rules_solve(black, white, player, n, max_empties=_lib.SOLVE_MAX_EMPTIES):
+    """oz_rules_solve, the exact endgame solver, over a batch of positions: -> (values int32 (count, 64) = the final disc difference for the mover
+    after each legal move under perfect play, OZ_MINIMAX_NONE elsewhere; bests uint64 (count,) = the moves of maximal value; value int32 (count,) =
+    the position's own; solved uint8 (count,) = 0 where the position has more than max_empties empties and was left alone: no values, bests 0,
+    value 0)"""
+    max_empties = _lib.check_solve_empties(max_empties)
+    black = np.ascontiguousarray(black, dtype=np.uint64).ravel()
+    white = np.ascontiguousarray(white, dtype=np.uint64).ravel()
+    player = np.ascontiguousarray(player, dtype=np.int8).ravel()
+    k = black.size
+    values, bests, value, solved = np.zeros((k, 64), np.int32), np.zeros(k, np.uint64), np.zeros(k, np.int32), np.zeros(k, np.uint8)
+    _lib.check(_lib.require_gpu().oz_rules_solve(_lib.p_u64(black), _lib.p_u64(white), _lib.p_i8(player), n, k, max_empties,
+                                                 _lib.p_i32(values), _lib.p_u64(bests), _lib.p_i32(value), _lib.p_u8(solved)))
+    return values, bests, value, solved
+
+
 class MinimaxOthelloAgent(OthelloAgent):
     """Fixed-depth minimax on the device (oz_rules_minimax): what the reference's GreedyOthelloAgent (agents.py:27-41, dead code) was meant to
     be at depth=1, evaluation="discs", and harder by one integer.  One call for the game's position, then `random.choice` over the moves of
-    maximal root value in ascending row-major order (Python's own `random`, like RandomOthelloAgent)."""
+    maximal root value in ascending row-major order (Python's own `random`, like RandomOthelloAgent).
+    solve_empties=E > 0: a position with E empties or fewer is played perfectly -- the same `random.choice`, over the exact solver's best
+    moves (oz_rules_solve).  The default 0 never asks the solver."""
 
-    def __init__(self, game, depth=3, evaluation="weighted"):
+    def __init__(self, game, depth=3, evaluation="weighted", solve_empties=0):
         _lib.check_minimax(depth, evaluation)
+        solve_empties = _lib.check_solve_empties(solve_empties, 0, "solve_empties")
         super().__init__(game)
-        self.depth, self.evaluation = int(depth), evaluation
+        self.depth, self.evaluation, self.solve_empties = int(depth), evaluation, solve_empties
 
     def play(self):
         game = self.game
         black, white = _lib.pack_board(game.board(BoardView.TWO_CHANNELS))
-        _, bests = rules_minimax([black], [white], [game.current_player.value], game.board_size, self.depth, self.evaluation)
+        if self.solve_empties > 0 and game.board_size ** 2 - bin(black | white).count("1") <= self.solve_empties:
+            _, bests, _, _ = rules_solve([black], [white], [game.current_player.value], game.board_size, self.solve_empties)
+        else:
+            _, bests = rules_minimax([black], [white], [game.current_player.value], game.board_size, self.depth, self.evaluation)
         mask = int(bests[0])
         moves = tuple((s >> 3, s & 7) for s in range(64) if (mask >> s) & 1)
         game.play(*random.choice(moves))

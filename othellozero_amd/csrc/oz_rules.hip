@@ -1,12 +1,13 @@
 // oz_rules.hip -- library core (errors, device selection), batched rule kernels (K1-K3) and the
 // dihedral symmetry expansion of training examples (K8).  HBM-bound integer/byte work: one thread
 // per position / per output example, SoA inputs, coalesced loads and stores.  Plus the batch entry of
-// the fixed-depth minimax (one wavefront per position, oz_minimax.h).
+// the fixed-depth minimax (one wavefront per position, oz_minimax.h) and of the exact endgame solver (oz_solve.h).
 #include <stdarg.h>
 #include <string.h>
 
 #include "oz_internal.h"
 #include "oz_minimax.h"
+#include "oz_solve.h"
 
 // ---------------------------------------------------------------- errors / device
 static thread_local char g_err[512] = "";
@@ -56,6 +57,10 @@ struct RulesStage {
     hipStream_t stream = nullptr;
     unsigned char *dev = nullptr, *host = nullptr;       // host = pinned (hipHostMalloc)
     size_t cap = 0;
+    bool profile = false;                                // oz_rules_profile: HIP events around the kernel of every call
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    double ms_total = 0.0;
+    long long launches = 0;
     int reserve(size_t bytes) {
         if (!stream) OZ_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         if (bytes <= cap) return OZ_OK;
@@ -124,11 +129,39 @@ static int rules_call(size_t in_bytes, size_t out_bytes, Pack pack, Launch launc
     if (int rc = st.reserve(in_p + pad8(out_bytes))) return rc;
     pack(st.host);
     OZ_HIP(hipMemcpyAsync(st.dev, st.host, in_bytes, hipMemcpyHostToDevice, st.stream));
+    if (st.profile) OZ_HIP(hipEventRecord(st.ev0, st.stream));
     launch(st.dev, st.dev + in_p, st.stream);
     OZ_HIP(hipGetLastError());
+    if (st.profile) OZ_HIP(hipEventRecord(st.ev1, st.stream));
     OZ_HIP(hipMemcpyAsync(st.host + in_p, st.dev + in_p, out_bytes, hipMemcpyDeviceToHost, st.stream));
     OZ_HIP(hipStreamSynchronize(st.stream));
+    if (st.profile) {
+        float ms = 0.f;
+        OZ_HIP(hipEventElapsedTime(&ms, st.ev0, st.ev1));
+        st.ms_total += ms; st.launches += 1;
+    }
     unpack(st.host + in_p);
+    return OZ_OK;
+}
+
+// HIP-event timing of the kernels behind the oz_rules_* batch entries on the current device (tools/solve_bench.py); off, a call records nothing
+OZ_API int oz_rules_profile(int enable) {
+    const int dev = oz_current_device();
+    OZ_REQUIRE(dev >= 0 && dev < 16, "device index %d out of range", dev);
+    RulesStage& st = g_stage[dev];
+    std::lock_guard<std::mutex> lk(st.mu);
+    if (enable && !st.ev0) { OZ_HIP(hipEventCreate(&st.ev0)); OZ_HIP(hipEventCreate(&st.ev1)); }
+    st.profile = enable != 0;
+    return OZ_OK;
+}
+OZ_API int oz_rules_profile_read(double* ms_total, int64_t* launches, int reset) {
+    const int dev = oz_current_device();
+    OZ_REQUIRE(dev >= 0 && dev < 16, "device index %d out of range", dev);
+    RulesStage& st = g_stage[dev];
+    std::lock_guard<std::mutex> lk(st.mu);
+    if (ms_total) *ms_total = st.ms_total;
+    if (launches) *launches = st.launches;
+    if (reset) { st.ms_total = 0.0; st.launches = 0; }
     return OZ_OK;
 }
 
@@ -232,6 +265,51 @@ OZ_API int oz_rules_minimax(const uint64_t* black, const uint64_t* white, const 
         [&](const unsigned char* h) {
             if (values) memcpy(values, h, cv);
             if (bests) memcpy(bests, h + cv, c8);
+        });
+}
+
+// ---------------------------------------------------------------- exact endgame solver (oz_solve.h; the reference has none)
+// one 64-lane block per position: values[i][sq] = S after the move on sq, bests[i] = the maximal moves, value[i] = S of the position;
+// a position with more than max_empties empties is left alone (solved[i] = 0)
+__global__ __launch_bounds__(64) void k_solve(const uint64_t* __restrict__ black, const uint64_t* __restrict__ white, const int8_t* __restrict__ player,
+                                              uint64_t valid, uint64_t corners, int n2, int max_empties, int32_t* __restrict__ values,
+                                              uint64_t* __restrict__ bests, int32_t* __restrict__ value, uint8_t* __restrict__ solved) {
+    __shared__ SolveLds L;
+    const int i = blockIdx.x, lane = threadIdx.x;
+    const uint64_t b = black[i], w = white[i];
+    const int empties = n2 - oz_popc(b | w);
+    uint64_t best = 0;
+    int v = OZ_MINIMAX_NONE, root = 0;
+    if (empties <= max_empties) v = sv_position(L, valid, corners, lane, b, w, player[i], empties, &best, &root);
+    values[(size_t)i * 64 + lane] = v;
+    if (lane == 0) { bests[i] = best; value[i] = root; solved[i] = empties <= max_empties ? 1 : 0; }
+}
+
+OZ_API int oz_rules_solve(const uint64_t* black, const uint64_t* white, const int8_t* player, int n, int count, int max_empties,
+                          int32_t* values, uint64_t* bests, int32_t* value, uint8_t* solved) {
+    if (int rc = check_n(n)) return rc;
+    OZ_REQUIRE(max_empties >= 0 && max_empties <= OZ_SOLVE_MAX_EMPTIES, "oz_rules_solve: max_empties %d outside 0..%d", max_empties, OZ_SOLVE_MAX_EMPTIES);
+    if (count <= 0) return OZ_OK;
+    OZ_REQUIRE(black && white && player, "null argument");
+    const uint64_t valid = oz_valid_mask(n);
+    for (int i = 0; i < count; ++i) {
+        OZ_REQUIRE(player[i] == 1 || player[i] == -1, "player must be +1 or -1");
+        OZ_REQUIRE(((black[i] | white[i]) & ~valid) == 0 && (black[i] & white[i]) == 0, "oz_rules_solve: position %d is no %dx%d board", i, n, n);
+    }
+    const size_t c8 = 8ull * count, c4 = pad8(4ull * count), c1 = pad8(count), cv = 256ull * count;
+    // output image: values | bests | value | solved
+    return rules_call(2 * c8 + c1, cv + c8 + c4 + c1,
+        [&](unsigned char* h) { memcpy(h, black, c8); memcpy(h + c8, white, c8); memcpy(h + 2 * c8, player, count); },
+        [&](unsigned char* di, unsigned char* dout, hipStream_t s) {
+            hipLaunchKernelGGL(k_solve, dim3(count), dim3(64), 0, s, (const uint64_t*)di, (const uint64_t*)(di + c8), (const int8_t*)(di + 2 * c8),
+                               valid, oz_solve_corners(n), n * n, max_empties, (int32_t*)dout, (uint64_t*)(dout + cv), (int32_t*)(dout + cv + c8),
+                               (uint8_t*)(dout + cv + c8 + c4));
+        },
+        [&](const unsigned char* h) {
+            if (values) memcpy(values, h, cv);
+            if (bests) memcpy(bests, h + cv, c8);
+            if (value) memcpy(value, h + cv + c8, 4ull * count);
+            if (solved) memcpy(solved, h + cv + c8 + c4, count);
         });
 }
 

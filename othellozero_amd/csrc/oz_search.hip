@@ -25,6 +25,7 @@
 
 #include "oz_internal.h"
 #include "oz_minimax.h"
+#include "oz_solve.h"
 
 enum { VT_INT = 0, VT_F32 = 1, VT_F64 = 2 };
 #define OZ_MAX_DEPTH 64
@@ -1966,6 +1967,7 @@ struct oz_selfplay {
     std::vector<void*> allocs;
     std::mutex mu;
     long long records_read = 0;
+    long long* d_endgame = nullptr;  // oz_selfplay_solve_records: its six counters (allocated by the first call)
     template <typename T> int alloc(T** p, size_t count) {
         OZ_HIP(hipMalloc((void**)p, sizeof(T) * (count ? count : 1)));
         allocs.push_back(*p);
@@ -2345,6 +2347,68 @@ OZ_API int oz_selfplay_visits_device(oz_selfplay* sp, void* dst_device, int64_t 
     OZ_REQUIRE(sp, "null selfplay");
     OZ_REQUIRE_VISITS(sp);
     return selfplay_rows(sp, sp->gm.visits, 64 * sizeof(int32_t), dst_device, max_records, written, hipMemcpyDeviceToDevice);
+}
+
+// ---------------------------------------------------------------- exact value targets for the endgame records (oz_solve.h)
+// one 64-lane block per record: S of the board BEFORE the move; z = the sign of S for the mover (0 -> BLACK wins, as oz_record.z has it);
+// acc: [0] records seen [1] solved [2] z changed [3] moves of maximal value [4] sum of S - values[action] [5] its maximum
+__global__ __launch_bounds__(64) void k_solve_records(oz_record* __restrict__ recs, uint64_t valid, uint64_t corners, int n2, int max_empties,
+                                                      long long* __restrict__ acc) {
+    __shared__ SolveLds L;
+    oz_record* rec = recs + blockIdx.x;
+    const int lane = threadIdx.x;
+    const uint64_t b = rec->black, w = rec->white;
+    const int player = rec->player, action = rec->action, z_old = rec->z;
+    const int empties = n2 - oz_popc(b | w);
+    if (empties > max_empties) {
+        if (lane == 0) atomicAdd((unsigned long long*)&acc[0], 1ULL);
+        return;
+    }
+    uint64_t bests = 0;
+    int S = 0;
+    const int v = sv_position(L, valid, corners, lane, b, w, player, empties, &bests, &S);
+    const int played = __shfl(v, action & 63, 64);
+    if (lane != 0) return;
+    const int z = S > 0 ? 1 : S < 0 ? -1 : player == 1 ? 1 : -1;
+    if (z != z_old) rec->z = (int8_t)z;
+    const int loss = played == OZ_MINIMAX_NONE ? 0 : S - played;
+    atomicAdd((unsigned long long*)&acc[0], 1ULL);
+    atomicAdd((unsigned long long*)&acc[1], 1ULL);
+    if (z != z_old) atomicAdd((unsigned long long*)&acc[2], 1ULL);
+    if (loss == 0) atomicAdd((unsigned long long*)&acc[3], 1ULL);
+    else { atomicAdd((unsigned long long*)&acc[4], (unsigned long long)loss); atomicMax(&acc[5], (long long)loss); }
+}
+
+OZ_API int oz_selfplay_solve_records(oz_selfplay* sp, int64_t first_record, int max_empties, oz_endgame_stats* stats) {
+    OZ_REQUIRE(sp, "null selfplay");
+    OZ_REQUIRE(max_empties >= 1 && max_empties <= OZ_SOLVE_MAX_EMPTIES, "oz_selfplay_solve_records: max_empties %d outside 1..%d", max_empties, OZ_SOLVE_MAX_EMPTIES);
+    OZ_REQUIRE(first_record >= 0, "oz_selfplay_solve_records: first_record %lld", (long long)first_record);
+    std::lock_guard<std::mutex> lk(sp->mu);
+    if (sp->m->selected) { oz_set_error("oz_selfplay_solve_records: a step is pending (oz_mcts_select without oz_mcts_backup)"); return OZ_ERR_STATE; }
+    hipSetDevice(sp->m->device);
+    hipStream_t s = sp->m->stream;
+    OZ_HIP(hipStreamSynchronize(s));
+    unsigned long long total = 0;
+    OZ_HIP(hipMemcpy(&total, sp->gm.counters, 8, hipMemcpyDeviceToHost));
+    long long have = (long long)total > sp->gm.record_cap ? sp->gm.record_cap : (long long)total;
+    const long long count = have > first_record ? have - first_record : 0;
+    OZ_REQUIRE(count < (1ll << 31), "too many records in one call");
+    long long acc[6] = {0, 0, 0, 0, 0, 0};
+    if (count > 0) {
+        if (!sp->d_endgame) { if (int rc = sp->alloc(&sp->d_endgame, 6)) return rc; }
+        OZ_HIP(hipMemsetAsync(sp->d_endgame, 0, sizeof acc, s));
+        const int n = sp->gm.n;
+        hipLaunchKernelGGL(k_solve_records, dim3((unsigned)count), dim3(64), 0, s, sp->gm.records + first_record, sp->gm.valid, oz_solve_corners(n),
+                           n * n, max_empties, sp->d_endgame);
+        OZ_HIP(hipGetLastError());
+        OZ_HIP(hipMemcpyAsync(acc, sp->d_endgame, sizeof acc, hipMemcpyDeviceToHost, s));
+        OZ_HIP(hipStreamSynchronize(s));
+    }
+    if (stats) {
+        stats->records = acc[0]; stats->solved = acc[1]; stats->z_changed = acc[2]; stats->optimal_moves = acc[3];
+        stats->disc_loss_sum = acc[4]; stats->disc_loss_max = (int32_t)acc[5]; stats->pad = 0;
+    }
+    return OZ_OK;
 }
 
 OZ_API int oz_selfplay_last_counts(oz_selfplay* sp, int32_t* counts) {

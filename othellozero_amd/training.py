@@ -276,6 +276,18 @@ class SelfPlayEngine:
         assert got.value == out.size, (got.value, out.size)
         return out[order], counts[:out.size][order]
 
+    def solve_records(self, max_empties, first_record=0):
+        """oz_selfplay_solve_records: the completed records from `first_record` on whose position has at most max_empties empties get the
+        exact solver's value target in place on the device (z = the sign of the final disc difference under perfect play, for the mover; a
+        draw goes to BLACK) -- nothing else of a record changes.  -> dict(records, solved, z_changed, optimal_moves, disc_loss_sum,
+        disc_loss_max, mean_disc_loss): the discs the moves played gave away against perfect play, over the solved records."""
+        max_empties = _lib.check_solve_empties(max_empties, 1)
+        s = _lib.EndgameStats()
+        _lib.check(_lib.load().oz_selfplay_solve_records(self._h, int(first_record), max_empties, C.byref(s)))
+        out = {k: int(getattr(s, k)) for k, _ in s._fields_ if k != "pad"}
+        out["mean_disc_loss"] = out["disc_loss_sum"] / out["solved"] if out["solved"] else 0.0
+        return out
+
     def records_to_device(self, device_ptr, max_records):
         written = C.c_int64()
         _lib.check(_lib.load().oz_selfplay_records_device(self._h, C.c_void_p(device_ptr), max_records, C.byref(written)))
@@ -292,12 +304,15 @@ class SelfPlayEngine:
         _lib.check(_lib.load().oz_selfplay_eval_time(self._h, C.byref(ms), C.byref(launches), C.byref(leaves)))
         return dict(ms=ms.value, launches=launches.value, leaves=leaves.value)
 
-    def play_to_end(self, max_rounds=None, with_visits=False):
+    def play_to_end(self, max_rounds=None, with_visits=False, endgame_targets=0):
+        """endgame_targets=E > 0: solve_records(E) once the games are over, before the records are read (its stats: self.endgame_stats)"""
         max_rounds = max_rounds or self.n * self.n
         for _ in range(max_rounds):
             self.run(4)
             if self.stats()["live_games"] == 0:
                 break
+        if endgame_targets:
+            self.endgame_stats = self.solve_records(endgame_targets)
         return self.records(with_visits=with_visits)
 
 
@@ -348,16 +363,22 @@ def expand_examples(records, board_size, alias_final=False, visits=None, target_
 def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations=100, degree_exploration=1.0,
                    policy_temperature=1.0, e_greedy=0.9, seed=1234, first_game_id=0, q_mode=_lib.QMODE_F64,
                    expand=False, alias_final=False, record_visits=False, target_temperature=1.0, leaves_per_step=1, root_noise=None,
-                   sample_moves=None):
+                   sample_moves=None, endgame_targets=0):
     """Play num_games complete games; returns the move records (or the expanded examples).
     record_visits=True: (records, visit counts) -- or, with expand, the examples with visit-distribution targets at target_temperature.
     root_noise=(alpha, epsilon): Dirichlet root noise in every search (SelfPlayEngine).
-    sample_moves=(temperature, plies): the opening plies' moves are sampled from the visit counts (SelfPlayEngine)."""
+    sample_moves=(temperature, plies): the opening plies' moves are sampled from the visit counts (SelfPlayEngine).
+    endgame_targets=E > 0: records with E empties or fewer carry the exact solver's value target (SelfPlayEngine.solve_records); with expand it
+    needs alias_final=False.  selfplay_batch.endgame_stats holds the last call's statistics (None when off)."""
+    endgame_targets = _lib.check_endgame_targets(endgame_targets, expand and alias_final)
     eng = SelfPlayEngine(neural_network, board_size, num_games, num_simulations, degree_exploration, policy_temperature,
                          e_greedy, seed, first_game_id, q_mode=q_mode, record_visits=record_visits, leaves_per_step=leaves_per_step,
                          root_noise=root_noise, sample_moves=sample_moves)
+    selfplay_batch.endgame_stats = None
     if record_visits:
-        rec, counts = eng.play_to_end(with_visits=True)
+        rec, counts = eng.play_to_end(with_visits=True, endgame_targets=endgame_targets)
+        selfplay_batch.endgame_stats = getattr(eng, "endgame_stats", None)
         return expand_examples(rec, board_size, alias_final, visits=counts, target_temperature=target_temperature) if expand else (rec, counts)
-    rec = eng.play_to_end()
+    rec = eng.play_to_end(endgame_targets=endgame_targets)
+    selfplay_batch.endgame_stats = getattr(eng, "endgame_stats", None)
     return expand_examples(rec, board_size, alias_final) if expand else rec
