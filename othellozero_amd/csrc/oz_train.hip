@@ -1378,7 +1378,7 @@ static int t_bn_backward(oz_trainer* t, int l, int B, const float* dA) {
     const float post = l >= 4 && t->rate > 0.f ? 1.0f / (1.0f - t->rate) : 1.0f;
     unsigned* dzmax = t->mode == 1 ? t->dzmax + l : nullptr;
     if (M <= OZ_BNB_MIN_ROWS) {         // small batch: BN backward, dgamma / dbeta / bias gradient in one launch
-        hipLaunchKernelGGL(k_t_bn_bwd_fused, dim3(Cc / OZ_BN_COLS), dim3(1024), 0, s, dA, t->a[l], t->z[l], t->mean[l], t->rstd[l],
+        hipLaunchKernelGGL(k_t_bn_bwd_fused, dim3(Cc / OZ_BN_COLS), dim3(1024), 0, s, dA, t->a[l], t->z[l], t->rstd[l],
                            t->param(6 * l + 2), post, t->d_count, L.Hout, Cc, L.Hz, L.zoff, t->dz[l], t->grad(6 * l + 2),
                            t->grad(6 * l + 3), t->grad(6 * l + 1), dzmax);
         OZ_HIP(hipGetLastError());

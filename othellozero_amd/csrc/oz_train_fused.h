@@ -75,37 +75,57 @@ __global__ __launch_bounds__(1024) void k_t_bn_fwd_fused(const float* __restrict
 
 // dy = (a > 0 ? dA * post_scale : 0); dgamma = sum dy * xhat, dbeta = sum dy;
 // dz = gamma * rstd * (dy - dbeta / M - xhat * dgamma / M), written at (b, oy + zoff, ox + zoff) of an Hz x Hz buffer;
-// dbias = sum dz (rounding noise behind a training-mode BN, computed like autograd would)
+// dbias = sum dz (0 in exact arithmetic behind a training-mode BN).
+// The column sums and dz are formed in float64, and xhat is centred on the float64 mean of z, not on the forward pass's rounded one.  With few
+// rows the gradients below a BN are large (dense BN with M = 2: xhat = +-1, they survive only through eps) and dz is a difference of
+// terms ~gamma * rstd^2 larger than itself: in fp32 the errors that every row shares -- the rounding of sum dy, and sum xhat =
+// M * rstd * (the rounding of the mean) times dgamma / M -- do not average out over the rows and left ~2e-5 in conv1's bias gradient at 2
+// boards (rstd ~ 30 there).  At most OZ_BNB_MIN_ROWS rows: four rows per thread, the float64 costs nothing that shows.
+__device__ __forceinline__ double t_block_sum4d(double v, double (*sh)[OZ_BN_COLS], int lane4, int c64) {
+    __syncthreads();                       // sh may still be read from the previous reduction
+    sh[lane4][c64] = v;
+    __syncthreads();
+    double s = 0.0;
+#pragma unroll
+    for (int i = 0; i < OZ_BN_RL; ++i) s += sh[i][c64];          // fixed order
+    return s;
+}
+
 __global__ __launch_bounds__(1024) void k_t_bn_bwd_fused(const float* __restrict__ dA, const float* __restrict__ a, const float* __restrict__ z,
-                                                        const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                        const float* __restrict__ rstd,
                                                         const float* __restrict__ gamma, float post_scale, const int* __restrict__ d_count,
                                                         int Hout, int C, int Hz, int zoff, float* __restrict__ dz,
                                                         float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ dbias,
                                                         unsigned* __restrict__ dzmax /* nullable: atomic max of |dz| (bit pattern), f16x2 data gradient */) {
-    __shared__ float sh[OZ_BN_RL][OZ_BN_COLS];
+    __shared__ double sh[OZ_BN_RL][OZ_BN_COLS];
     const int c64 = threadIdx.x & (OZ_BN_COLS - 1), lane4 = threadIdx.x / OZ_BN_COLS, c = blockIdx.x * OZ_BN_COLS + c64;
     const int P = Hout * Hout;
     const long long M = (long long)(*d_count) * P;
-    const float mu = mean[c], rs = rstd[c];
-    float s0 = 0.f, s1 = 0.f;
+    const double rs = (double)rstd[c];
+    double sy = 0.0, sz = 0.0, syz = 0.0;                    // sum dy, sum z, sum dy * z (the products are exact in float64)
     _Pragma("unroll 4") for (long long m = lane4; m < M; m += OZ_BN_RL) {
         const size_t i = (size_t)m * C + c;
-        const float dy = a[i] > 0.f ? dA[i] * post_scale : 0.f;
-        s0 += dy;
-        s1 = fmaf(dy, (z[i] - mu) * rs, s1);
+        const double dy = a[i] > 0.f ? dA[i] * post_scale : 0.f, zv = (double)z[i];
+        sy += dy;
+        sz += zv;
+        syz = fma(dy, zv, syz);
     }
-    const float S0 = t_block_sum4(s0, sh, lane4, c64);
-    const float S1 = t_block_sum4(s1, sh, lane4, c64);
-    const float inv = 1.0f / (float)M, gr = gamma[c] * rs;
-    float sb = 0.f, amax = 0.f;
+    const double inv = 1.0 / (double)M;
+    const double S0 = t_block_sum4d(sy, sh, lane4, c64);
+    const double mu = t_block_sum4d(sz, sh, lane4, c64) * inv;
+    const double S1 = (t_block_sum4d(syz, sh, lane4, c64) - mu * S0) * rs;         // sum dy * (z - mu) * rstd
+    const double gr = (double)gamma[c] * rs;
+    double sb = 0.0;
+    float amax = 0.f;
     _Pragma("unroll 4") for (long long m = lane4; m < M; m += OZ_BN_RL) {
         const size_t i = (size_t)m * C + c;
-        const float dy = a[i] > 0.f ? dA[i] * post_scale : 0.f;
-        const float xh = (z[i] - mu) * rs;
-        const float g = gr * (dy - S0 * inv - xh * S1 * inv);
+        const double dy = a[i] > 0.f ? dA[i] * post_scale : 0.f;
+        const double xh = ((double)z[i] - mu) * rs;
+        const double gd = gr * (dy - S0 * inv - xh * S1 * inv);
+        const float g = (float)gd;
         const int b = (int)(m / P), pix = (int)(m % P);
         dz[(((size_t)b * Hz + pix / Hout + zoff) * Hz + pix % Hout + zoff) * C + c] = g;
-        sb += g;
+        sb += gd;                                            // (before dz is rounded to fp32: the roundings of the rows are not part of the sum)
         amax = fmaxf(amax, fabsf(g));
     }
     if (dzmax) {                                             // one atomic per block (see k_t_bnb_apply)
@@ -119,8 +139,8 @@ __global__ __launch_bounds__(1024) void k_t_bn_bwd_fused(const float* __restrict
             atomicMax(dzmax, __float_as_uint(mx));
         }
     }
-    const float SB = t_block_sum4(sb, sh, lane4, c64);
-    if (lane4 == 0) { dgamma[c] = S1; dbeta[c] = S0; dbias[c] = SB; }
+    const double SB = t_block_sum4d(sb, sh, lane4, c64);
+    if (lane4 == 0) { dgamma[c] = (float)S1; dbeta[c] = (float)S0; dbias[c] = (float)SB; }
 }
 
 // ---- more than OZ_BNB_MIN_ROWS rows (from the reference's 32 boards on the 8x8 conv layers, 1152-2048 rows, upwards): one block per 16 channels leaves

@@ -273,14 +273,16 @@ def test_nnetwrapper_train_drop_in():
     assert net._trainer.step == 6 * 3 + 6 * 2 and np.isfinite(hist2.history["loss"]).all()
 
 
-@pytest.mark.parametrize("precision,C", [("f32", 128), ("f16x2", 256)])
-def test_resident_dataset_fit_equals_stepwise_fit(precision, C):
+@pytest.mark.parametrize("precision,C,N", [pytest.param("f32", 128, 75, id="f32-128"), pytest.param("f16x2", 256, 75, id="f16x2-256"),
+                                           # 65 = 4 * 16 + 1: the last batch of every epoch is ONE board (dense BNs over M = 1)
+                                           pytest.param("f32", 128, 65, id="f32-128-N65"), pytest.param("f16x2", 256, 65, id="f16x2-256-N65")])
+def test_resident_dataset_fit_equals_stepwise_fit(precision, C, N):
     """trainer.fit with the examples resident in HBM (one upload, one library call per epoch, batches gathered by index on
     the device, no per-step synchronisation) takes exactly the optimiser steps of the step-wise loop: identical weights
     bit for bit after two epochs with a short last batch, the same epoch-mean losses"""
     from othellozero_amd.trainer import Trainer, fit
     from othellozero_amd.weights import init_weights
-    n, N, bs = 6, 75, 16
+    n, bs = 6, 16
     own, opp, pi, z = _batch(n, N, seed=77)
     runs = []
     for resident in (False, True):
@@ -292,6 +294,7 @@ def test_resident_dataset_fit_equals_stepwise_fit(precision, C):
     assert s0 == s1 == 2 * 5
     assert all(np.array_equal(a, b) for a, b in zip(w0, w1))
     for k in h0:
+        assert np.isfinite(h0[k]).all() and np.isfinite(h1[k]).all(), (k, h0[k], h1[k])
         assert np.allclose(h0[k], h1[k], rtol=1e-6, atol=1e-7), (k, h0[k], h1[k])
 
 

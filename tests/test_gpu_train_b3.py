@@ -112,10 +112,11 @@ def test_bf16x3_determinism():
     assert l1 == l2 and all(np.array_equal(g1[i], g2[i]) for i in g1)
 
 
-def test_bf16x3_resident_dataset_fit_equals_stepwise_fit():
+@pytest.mark.parametrize("N", [75, 65])      # 65 = 4 * 16 + 1: the last batch of every epoch is ONE board
+def test_bf16x3_resident_dataset_fit_equals_stepwise_fit(N):
     from othellozero_amd.trainer import Trainer, fit
     from othellozero_amd.weights import init_weights
-    n, N, bs, C = 6, 75, 16, 256
+    n, bs, C = 6, 16, 256
     own, opp, pi, z = _batch(n, N, seed=77)
     runs = []
     for resident in (False, True):
@@ -127,6 +128,7 @@ def test_bf16x3_resident_dataset_fit_equals_stepwise_fit():
     assert s0 == s1 == 2 * 5
     assert all(np.array_equal(a, b) for a, b in zip(w0, w1))
     for k in h0:
+        assert np.isfinite(h0[k]).all() and np.isfinite(h1[k]).all(), (k, h0[k], h1[k])
         assert np.allclose(h0[k], h1[k], rtol=1e-6, atol=1e-7), (k, h0[k], h1[k])
 
 

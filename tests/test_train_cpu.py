@@ -65,6 +65,34 @@ def test_oracle_forward_matches_torch_modules_in_training_mode():
     assert all(ref.grads[6 * l + 1].abs().max() < 1e-12 for l in range(6))
 
 
+def test_oracle_gradients_of_one_and_two_board_batches():
+    """The oracle's side of the short-batch edge (tests/test_gpu_train_ragged.py).  One board: the dense BatchNormalizations normalise over
+    M = 1, so xhat = 0 and dz of fc2 = gamma * rstd * (dy - mean(dy) - xhat * mean(dy * xhat)) is exactly 0 -- every trainable tensor below
+    fc2's beta (indices 0 .. 32) has max |g| = 0, and 33 (fc2's beta), 36 .. 39 (the heads) do not.  Two boards: nothing vanishes but the
+    biases behind a BN."""
+    n, C = 6, 128
+    w = init_weights(n, seed=3, channels=C, randomize_all=True)
+    bn_biases = [6 * l + 1 for l in range(6)]
+    ref = TrainRef(w, n, seed=77)
+    loss = ref.forward_backward(*_batch(n, 1, 11))
+    assert np.isfinite(loss).all()
+    for i in TRAINABLE:
+        g = ref.grads[i].abs().max().item()
+        if i <= 32:
+            assert g == 0.0, (i, g)
+        else:
+            assert i in (33, 36, 37, 38, 39) and g > 0.0 and np.isfinite(g), (i, g)
+    ref = TrainRef(w, n, seed=77)
+    loss = ref.forward_backward(*_batch(n, 2, 11))
+    assert np.isfinite(loss).all()
+    for i in TRAINABLE:
+        g = ref.grads[i].abs().max().item()
+        if i in bn_biases:
+            assert g < 1e-12, (i, g)
+        else:
+            assert g > 0.0 and np.isfinite(g), (i, g)
+
+
 def test_oracle_adam_is_tf_keras_adam():
     n, C = 6, 8
     w = init_weights(n, seed=2, channels=C, randomize_all=True)
