@@ -222,7 +222,38 @@ int oz_net_get_scaling(oz_net* net, int which, int32_t* out, int64_t nelem);
 /* the arithmetic the network's GEMM layers really run in: the precision mode, except that a precision-2 (bf16x3) network of max_batch < 128 reports 0 --
  * its layers are the exact-fp32 latency kernels (see oz_net_set_precision) */
 #define OZ_NET_INFO_ARITHMETIC 3
+/* the launch plan of the last forward, per layer l = 1 .. 5 (conv2, conv3, conv4, fc1, fc2): the row-tile height of the kernel that ran the layer
+ * (64 / 128 / 192 / 256; 0 = no row tiles: the table gather), the number of k-slices its k loop was cut into (1 = unsplit; slices of layers
+ * 1 .. 4 are added by the precision's fixed-order reduce kernel, those of fc2 by the heads kernel), and which kernel / main loop it was
+ * (OZ_NET_KERNEL_*).  What a test matrix needs to show that it ran the configuration it names. */
+#define OZ_NET_INFO_LAYER_TILE_ROWS(l) (16 + (l))
+#define OZ_NET_INFO_LAYER_KSLICES(l) (32 + (l))
+#define OZ_NET_INFO_LAYER_KERNEL(l) (48 + (l))
+enum {
+    OZ_NET_KERNEL_NONE = 0,
+    OZ_NET_KERNEL_F32_SKINNY = 1,        /* k_gemm_f32_skinny: the weight stream of layers with at most 64 rows */
+    OZ_NET_KERNEL_F32_STD = 2,           /* k_gemm_f32<GmStd>, board-major row tiles */
+    OZ_NET_KERNEL_F32_STD_PIXMAJOR = 3,  /* k_gemm_f32<GmStd>, pixel-major row tiles (conv2 as a GEMM) */
+    OZ_NET_KERNEL_F32_BIG = 4,           /* k_gemm_f32<GmBig> */
+    OZ_NET_KERNEL_LUT = 5,               /* conv1 + conv2 as the table gather, one thread per (pixel, 8 channels) */
+    OZ_NET_KERNEL_LUT_XCD = 6,           /* ... one table slice per XCD (512 filters) */
+    OZ_NET_KERNEL_LUT_XCD_INLINE = 7,    /* ... with the pattern ids computed inside the gather (precision f32, max_batch <= 32) */
+    OZ_NET_KERNEL_H2_SMALL2 = 10, OZ_NET_KERNEL_H2_SMALL = 11, OZ_NET_KERNEL_H2_BIGPP = 12, OZ_NET_KERNEL_H2_BIGPP_LUT = 13,
+    OZ_NET_KERNEL_H2_MIDPP = 14, OZ_NET_KERNEL_H2_LOWPP1 = 15, OZ_NET_KERNEL_H2_LOWPP = 16, OZ_NET_KERNEL_H2_BIG = 17, OZ_NET_KERNEL_H2_MID = 18,
+    OZ_NET_KERNEL_H2_THIN2 = 19, OZ_NET_KERNEL_H2_THIN = 20, OZ_NET_KERNEL_H2_THIN4W = 21,     /* k_gemm_h2 on the tile configuration of that name */
+    OZ_NET_KERNEL_B3 = 30,               /* k_gemm_b3 (128 x 256) */
+    OZ_NET_KERNEL_B3_BIG = 31            /* k_gemm_b3_big (256 x 256) */
+};
 int oz_net_get_info(oz_net* net, int what, int* value);
+/* Diagnostics: a read-only view of the last forward (the inference side's counterpart of oz_trainer_get_activation).  layer 0 .. 3 = the outputs
+ * of conv1 .. conv4, 4 / 5 = fc1 / fc2 (the trainer's numbering); a row is a (board, pixel) index of the last forward -- oz_net_predict's boards in
+ * call order -- and out[rows][channels] receives rows first_row .. first_row + rows - 1 as float64: EXACTLY the numbers the consuming kernel
+ * multiplies.  fp32 rows as they are; rows in the h2 layout as (h1 + h2) x 2^-aexp[channel] (the exact inverse of the channel's power of two);
+ * rows in the b3 layout as b1 + b2 + b3.  fc2 of a forward that left its k-slices to the heads kernel: what that kernel forms -- the slices added
+ * in slice order in fp32, then scale, shift and ReLU.  OZ_ERR_STATE (with a message) for a layer the forward never materialises -- conv1 when it is
+ * folded into a table -- and before the first forward after a commit; OZ_ERR_ARG for rows outside the last forward and for a stub network.
+ * Takes the network's mutex; changes no state. */
+int oz_net_get_activation(oz_net* net, int layer, int64_t first_row, int64_t rows, double* out /* [rows][channels] */);
 
 /* ------------------------------------------------------------------ search
  * OthelloMCTS / MCTS (othelo_mcts.py:9-88, MCTS/__init__.py:19-187): num_games independent

@@ -135,6 +135,7 @@ class NNetWrapper(_NetHandle):
         lib = _lib.load()
         for s in range(0, B, self.max_batch):
             e = min(B, s + self.max_batch)
+            self._last_call_boards = e - s
             _lib.check(lib.oz_net_predict(self._h, _lib.p_u64(own[s:e]), _lib.p_u64(opp[s:e]), e - s,
                                           _lib.p_f32(pi[s:e]), _lib.p_f32(v[s:e])))
         return pi, v
@@ -332,6 +333,33 @@ class NNetWrapper(_NetHandle):
         v = C.c_int()
         _lib.check(_lib.load().oz_net_get_info(self._h, _lib.NET_INFO_ARITHMETIC, C.byref(v)))
         return {0: "f32", 1: "f16x2", 2: "bf16x3"}[v.value]
+
+    def layer_plan(self):
+        """the launch plan of the LAST forward: {layer 1 .. 5 (conv2, conv3, conv4, fc1, fc2): dict(tile_rows=row-tile height (0: the table gather),
+        kslices=k-slices of the layer's k loop, kernel=_lib.NET_KERNEL_NAMES name of the kernel / main loop)} -- what a test reads to show that it ran
+        the configuration it names (oz_net_get_info, OZ_NET_INFO_LAYER_*)"""
+        lib, v, plan = _lib.load(), C.c_int(), {}
+        for layer in range(1, 6):
+            row = []
+            for base in (_lib.NET_INFO_LAYER_TILE_ROWS, _lib.NET_INFO_LAYER_KSLICES, _lib.NET_INFO_LAYER_KERNEL):
+                _lib.check(lib.oz_net_get_info(self._h, base + layer, C.byref(v)))
+                row.append(v.value)
+            plan[layer] = dict(tile_rows=row[0], kslices=row[1], kernel=_lib.NET_KERNEL_NAMES[row[2]])
+        return plan
+
+    def activation(self, layer, first_row=0, rows=None):
+        """diagnostics: rows [first_row, first_row + rows) of the output of `layer` (0 .. 3 = conv1 .. conv4, 4 / 5 = fc1 / fc2) in the LAST
+        oz_net_predict call (predict_batch cuts its boards into calls of max_batch), as float64 (rows, channels) -- exactly what the consuming
+        kernel multiplies (oz_net_get_activation).  A row is a (board, pixel) index, boards in call order; rows=None reads to the end of the call.
+        OzError(OZ_ERR_STATE) for a layer the forward does not materialise (conv1 in the table modes)."""
+        n, C_ = self.board_size_x, self.num_channels
+        pixels = [n * n, n * n, (n - 2) ** 2, (n - 4) ** 2, 1, 1][layer]
+        channels = [C_, C_, C_, C_, 1024, 512][layer]
+        if rows is None:
+            rows = getattr(self, "_last_call_boards", 0) * pixels - first_row
+        out = np.zeros((int(rows), channels), np.float64)
+        _lib.check(_lib.load().oz_net_get_activation(self._h, int(layer), int(first_row), int(rows), _lib.p_f64(out)))
+        return out
 
     def profiled_layer(self):
         """which launch profile_read() timed: 2 = the conv2 GEMM, 3 = the conv3 GEMM (f16x2: conv1 + conv2 are a table gather-sum)"""

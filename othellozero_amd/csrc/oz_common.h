@@ -258,14 +258,37 @@ __device__ __forceinline__ void oz_split8_store(uint4* dst, size_t pstride, cons
 }
 // The h2 layout: a row of K values (a pixel's channels or a weight row's k) is K / 8 groups of 32 bytes, group g = [h1 x 8][h2 x 8] at chunks
 // 2 g, 2 g + 1 of the row; rows follow each other.  Stores the group of k .. k + 7 (k % 8 == 0) of row `row`.
+OZ_HD size_t h2_group_chunk(size_t row, int K, int k) { return (row * (size_t)(K >> 3) + (k >> 3)) * 2; }      // the h1 chunk; h2 follows it
 template <bool NT = false>
 __device__ __forceinline__ void h2_store8(uint4* out, size_t row, int K, int k, const float (&v)[8]) {
-    oz_split8_store<2, NT>(out + (row * (size_t)(K >> 3) + (k >> 3)) * 2, 1, v);
+    oz_split8_store<2, NT>(out + h2_group_chunk(row, K, k), 1, v);
 }
 // The b3 layout: a row of K values is K / 32 k-tiles of 192 bytes = 12 chunks [plane 0: 32 bf16][plane 1: 32 bf16][plane 2: 32 bf16]; the chunk
 // of plane p and 8-group kg = (k / 8) % 4 of k-tile k / 32 sits at 12 (k / 32) + 4 p + kg of the row; rows follow each other.  Stores the group of
 // k .. k + 7 (k % 8 == 0) of row `row`.
+OZ_HD size_t b3_group_chunk(size_t row, int K, int k) { return row * (size_t)(K / 32 * 12) + (k >> 5) * 12 + ((k >> 3) & 3); }   // plane 0; plane p 4 p chunks on
 template <bool NT = false>
 __device__ __forceinline__ void b3_store8(uint4* out, size_t row, int K, int k, const float (&v)[8]) {
-    oz_split8_store<3, NT>(out + row * (size_t)(K / 32 * 12) + (k >> 5) * 12 + ((k >> 3) & 3), 4, v);
+    oz_split8_store<3, NT>(out + b3_group_chunk(row, K, k), 4, v);
+}
+// The way back (diagnostics: oz_net_get_activation): the eight values of the group at `src` (h2_group_chunk / b3_group_chunk) as the exact sum of
+// their PLANES planes, plane p one 16-byte chunk at src[p * pstride] -- what a kernel that consumes the layout multiplies, in float64.
+template <int PLANES>
+__device__ __forceinline__ void oz_split8_load(const uint4* src, size_t pstride, double (&v)[8]) {
+    static_assert(PLANES == 2 || PLANES == 3, "f16x2 or bf16x3");
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = 0.0;
+#pragma unroll
+    for (int p = 0; p < PLANES; ++p) {
+        const u32x4 raw = *reinterpret_cast<const u32x4*>(src + p * pstride);
+        if constexpr (PLANES == 2) {
+            const f16x8 h = __builtin_bit_cast(f16x8, raw);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] += (double)(float)h[j];
+        } else {
+            const bf16x8 b = __builtin_bit_cast(bf16x8, raw);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] += (double)(float)b[j];
+        }
+    }
 }

@@ -398,13 +398,15 @@ static void launch_splitk_reduce_f32(const float* partial, long long slab, int k
 int oz_gemm_f32_launch(const float* in, const float* Wt, const float* scale, const float* shift, float* out,
                        const int* d_count, int max_count, int Hin, int Hout, int pad, int Cin, int taps, int N, int relu,
                        hipStream_t s, float* partial, long long partial_floats, int sizing_count, int core_lo, int core_hi,
-                       int* tile_rows_out, int force_std_tile, OzDeferredReduce* defer) {
+                       int* tile_rows_out, int force_std_tile, OzDeferredReduce* defer, int* plan_out) {
     // defer (optional): a split launch leaves its reduce to the consumer (defer->ksplit > 1 says so; relu must be 1, the consumer applies it)
     if (defer) *defer = OzDeferredReduce();
     // tile_rows_out (optional): the row-tile height this launch ran on -- 64 = the weight-stream kernel, 128 = GmStd, 256 = GmBig;
     // force_std_tile: never the 256 x 256 tile (OZ_NET_OPT_F32_STD_TILE: the bit-identity screen of the two tiles)
-    int tile_rows_dummy = 0;
+    // plan_out (optional): [0] = the k-slices of this launch, [1] = the kernel (OZ_NET_KERNEL_F32_*) -- oz_net_get_info's launch plan
+    int tile_rows_dummy = 0, plan_dummy[2] = {1, 0};
     int& tile_rows = tile_rows_out ? *tile_rows_out : tile_rows_dummy;
+    int* const plan = plan_out ? plan_out : plan_dummy;
     OZ_REQUIRE(N % GM_BN == 0 && Cin % GM_BK == 0, "gemm_f32: N %% 128 and Cin %% 32 must be 0 (N=%d Cin=%d)", N, Cin);
     GemmGeom g;
     oz_geom_set_shape(g, OzLayerShape{Hin, Hout, pad, Cin, taps, N});
@@ -429,7 +431,7 @@ int oz_gemm_f32_launch(const float* in, const float* Wt, const float* scale, con
         if ((long long)ks * max_count * Pout * N <= partial_floats) {
             const long long slab = (long long)max_count * Pout * N;
             g.ksplit = ks; g.slab = slab; g.pixmajor = 0;
-            tile_rows = 64;
+            tile_rows = 64; plan[0] = ks; plan[1] = OZ_NET_KERNEL_F32_SKINNY;
             hipLaunchKernelGGL(k_gemm_f32_skinny, dim3(N / SK_COLS, ks), dim3(256), 0, s, in, Wt, d_count, g.K, N, kb, partial, slab, g);
             if (defer && relu) { defer->partial = partial; defer->slab = slab; defer->ksplit = ks; defer->scale = scale; defer->shift = shift; OZ_HIP(hipGetLastError()); return OZ_OK; }
             launch_splitk_reduce_f32(partial, slab, ks, N, Pout, max_count, d_count, scale, shift, relu, out, s);
@@ -453,7 +455,7 @@ int oz_gemm_f32_launch(const float* in, const float* Wt, const float* scale, con
     // products are added in the same order as on the standard tile (bit-identical), keyed on the call's capacity like the other choices
     const long long big_blocks = ((Mmax + GmBig::BM - 1) / GmBig::BM) * (N / GmBig::BN);
     if (taps == 9 && !g.pixmajor && ksplit == 1 && N % GmBig::BN == 0 && big_blocks >= 192 && !force_std_tile) {
-        tile_rows = GmBig::BM;
+        tile_rows = GmBig::BM; plan[0] = 1; plan[1] = OZ_NET_KERNEL_F32_BIG;
         const int num_mt_big = (int)((Mmax + GmBig::BM - 1) / GmBig::BM);
         const int grid_big = ((num_mt_big + 7) / 8) * 8 * (N / GmBig::BN);
         if (int rc = set_max_lds_once<k_gemm_f32<GmBig>>(GmBig::LDS_BYTES)) return rc;
@@ -461,7 +463,7 @@ int oz_gemm_f32_launch(const float* in, const float* Wt, const float* scale, con
         OZ_HIP(hipGetLastError());
         return OZ_OK;
     }
-    tile_rows = GmStd::BM;
+    tile_rows = GmStd::BM; plan[0] = ksplit; plan[1] = g.pixmajor ? OZ_NET_KERNEL_F32_STD_PIXMAJOR : OZ_NET_KERNEL_F32_STD;
     if (int rc = set_max_lds_once<k_gemm_f32<GmStd>>(GmStd::LDS_BYTES)) return rc;
     hipLaunchKernelGGL(k_gemm_f32<GmStd>, dim3(grid, ksplit), dim3(GmStd::NT), GmStd::LDS_BYTES, s, in, Wt, scale, shift, out, d_count, g, num_mt, partial);
     OZ_HIP(hipGetLastError());
@@ -641,6 +643,8 @@ int oz_w_to_b3_launch(const float* W, int K, int N, int taps, void* out, hipStre
 // The policy weights of a wave's 128 reduction indices are fetched 32 rows at a time: the loop is a chain of L2 round trips (~0.6 us each),
 // so the depth of a batch IS the launch time -- with 4-8 rows in flight the launch took 20 us for ONE position, as long as conv3's 9.4 MB
 // weight stream, and 21 us at 512 positions (round 5: rocprofv3 of the arena and of predict(); 32 in flight: see DESIGN.md).
+// how a consumer finishes an element of a deferred split-K layer (OzDeferredReduce) from the fp32 sum `a` of its k-slices
+__device__ __forceinline__ float oz_deferred_finish(float a, float sc, float sh) { const float y = fmaf(a, sc, sh); return y < 0.f ? 0.f : y; }
 template <int LP>
 __global__ __launch_bounds__(256) void k_heads_t(const float* __restrict__ f2 /*[B][512]*/, const int* __restrict__ d_count,
                                                  int A, const float* __restrict__ Wpi /*[512][A]*/, const float* __restrict__ bpi,
@@ -688,7 +692,7 @@ __global__ __launch_bounds__(256) void k_heads_t(const float* __restrict__ f2 /*
             const f32x4 sc = *reinterpret_cast<const f32x4*>(dr.scale + c4), sh = *reinterpret_cast<const f32x4*>(dr.shift + c4);
             f32x4 r;
 #pragma unroll
-            for (int t = 0; t < 4; ++t) { const float y = fmaf(a[t], sc[t], sh[t]); r[t] = y < 0.f ? 0.f : y; }
+            for (int t = 0; t < 4; ++t) r[t] = oz_deferred_finish(a[t], sc[t], sh[t]);
             *reinterpret_cast<f32x4*>(&xs[p][c4]) = r;
         }
     } else
@@ -754,6 +758,41 @@ __global__ __launch_bounds__(256) void k_heads_t(const float* __restrict__ f2 /*
 }
 #define HEADS_P 8
 #define HEADS_LP 16
+
+// ---------------------------------------------------------------- diagnostics: rows of the last forward as float64 (oz_net_get_activation)
+// FMT 0: fp32 rows; 1: the h2 layout, times the exact inverse of the channel's power of two; 2: the b3 layout (layouts and plane sums: oz_common.h).
+// One thread per (row, 8 channels).
+template <int FMT>
+__global__ __launch_bounds__(256) void k_act_rows_f64(const void* __restrict__ src, const int* __restrict__ aexp, long long first_row, long long rows, int N,
+                                                      double* __restrict__ out) {
+    const int ng = N >> 3;
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long r = idx / ng;
+    if (r >= rows) return;
+    const int c8 = (int)(idx % ng) * 8;
+    const size_t row = (size_t)(first_row + r);
+    double v[8];
+    if constexpr (FMT == 0) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = (double)static_cast<const float*>(src)[row * N + c8 + j];
+    } else if constexpr (FMT == 1) {
+        oz_split8_load<2>(static_cast<const uint4*>(src) + h2_group_chunk(row, N, c8), 1, v);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = ldexp(v[j], -aexp[c8 + j]);
+    } else oz_split8_load<3>(static_cast<const uint4*>(src) + b3_group_chunk(row, N, c8), 4, v);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) out[(size_t)r * N + c8 + j] = v[j];
+}
+// rows of a layer whose k-slices were left to its consumer (fc2 -> k_heads_t): the slices added in slice order in fp32, then the consumer's own finish
+__global__ __launch_bounds__(256) void k_deferred_rows_f64(OzDeferredReduce dr, long long first_row, long long rows, int N, double* __restrict__ out) {
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= rows * N) return;
+    const int c = (int)(idx % N);
+    const float* src = dr.partial + (size_t)(first_row + idx / N) * N + c;
+    float a = src[0];
+    for (int s = 1; s < dr.ksplit; ++s) a += src[(size_t)s * dr.slab];
+    out[idx] = (double)oz_deferred_finish(a, dr.scale[c], dr.shift[c]);
+}
 
 // ---------------------------------------------------------------- stub evaluator (test nets)
 __global__ __launch_bounds__(64) void k_stub(const uint64_t* __restrict__ own, const uint64_t* __restrict__ opp,
@@ -879,6 +918,20 @@ struct OnnNet : oz_net {
     int low_loop_phases = 1;         // oz_net_set_option(OZ_NET_OPT_LOW_LOOP_PHASES): main loop of the 128 x 256 tile -- 1 (default) = one phase per k-tile, three LDS stages; 2 = round 5's 2-phase loop
     float* d_t2rows = nullptr;       // commit staging: one tap's T2 rows [OZ_LUT_PATTERNS][C] before the slice-major re-layout
     int last_conv3_rows = 0;         // row-tile height the last forward ran conv3 on (oz_net_get_info)
+    // the launch plan of the last forward (oz_net_get_info, OZ_NET_INFO_LAYER_*): index = layer 1 .. 5 (conv2 .. fc2), written by the launch wrappers
+    struct LayerPlan { int tile_rows = 0, ksplit = 0, kernel = OZ_NET_KERNEL_NONE; };
+    LayerPlan plan[6];
+    // where the last forward left the output of conv1 .. fc2 (oz_net_get_activation; index = its `layer`), written at the end of the three forwards.
+    // fmt: -1 not materialised, 0 fp32 rows, 1 the h2 layout (aexp: the tensor's exponents on the device), 2 the b3 layout, 3 k-slices left to the heads kernel (last_defer)
+    struct ActView { const void* p = nullptr; int fmt = -1; const int* aexp = nullptr; };
+    ActView view[6];
+    OzDeferredReduce last_defer;     // the fc2_defer the last launch_heads consumed
+    int last_count = 0;              // boards (capacity) of the last forward_device; 0 = none since the last commit
+    void set_views(const void* a1, int fmt1, const void* a2, const void* a3, const void* a4, const void* a5, int fmt) {
+        const void* const p[5] = {a1, a2, a3, a4, a5};
+        for (int t = 0; t < 5; ++t) view[t] = ActView{p[t], t == 0 ? fmt1 : fmt, (t == 0 ? fmt1 : fmt) == 1 ? d_aexp[t] : nullptr};
+        view[5] = last_defer.ksplit > 1 ? ActView{nullptr, 3, nullptr} : ActView{f2, 0, nullptr};
+    }
     int profiled_layer = 2;          // 2 = conv2 GEMM, 3 = conv3 GEMM (when conv2 runs as the table gather-sum)
     // precision f16x2, scaling and guards (oz_net_h2.h, header): tensor t = 0..4 is act1, act2, act3, act4, f1; layer i = 0..4 is conv2..fc2
     std::vector<int> aexp[5];        // per-channel activation exponents of tensor t (exact powers of two, from the calibration maxima)
@@ -979,9 +1032,12 @@ struct OnnNet : oz_net {
     int launch_gemm(const float* in, int layer, float* out, const int* d_count, int max_count, hipStream_t s, OzDeferredReduce* defer = nullptr) {
         const OzLayerShape L = layers()[layer - 1];
         // small and medium networks (max_batch <= 512) split K over the idle CUs: latency, not throughput
-        return oz_gemm_f32_launch(in, d_wt[layer - 1], d_scale[layer], d_shift[layer], out, d_count, max_count, L.Hin, L.Hout, L.pad, L.Cin, L.taps, L.N, 1, s,
-                                  d_part32, d_part32 ? (long long)part32_floats() : 0, sizing(), 0, -1,
-                                  layer == 2 ? &last_conv3_rows : nullptr, f32_std_tile ? 1 : 0, defer);  // layer 2 = conv3: what oz_net_get_info reports
+        int rows = 0, pl[2] = {1, OZ_NET_KERNEL_NONE};
+        const int rc = oz_gemm_f32_launch(in, d_wt[layer - 1], d_scale[layer], d_shift[layer], out, d_count, max_count, L.Hin, L.Hout, L.pad, L.Cin, L.taps, L.N, 1, s,
+                                          d_part32, d_part32 ? (long long)part32_floats() : 0, sizing(), 0, -1, &rows, f32_std_tile ? 1 : 0, defer, pl);
+        plan[layer] = LayerPlan{rows, pl[0], pl[1]};
+        if (layer == 2) last_conv3_rows = rows;              // conv3: what OZ_NET_INFO_CONV3_TILE_ROWS reports
+        return rc;
     }
 
     // precision f32: split-K slabs per position-row budget (small networks 16 slices, medium ones fewer; none for large batches)
@@ -1034,6 +1090,14 @@ struct OnnNet : oz_net {
         return need;
     }
 
+    template <typename CF> static constexpr int h2_kernel_id() {
+        return std::is_same<CF, H2Small2>::value ? OZ_NET_KERNEL_H2_SMALL2 : std::is_same<CF, H2Small>::value ? OZ_NET_KERNEL_H2_SMALL
+             : std::is_same<CF, H2BigPP>::value ? OZ_NET_KERNEL_H2_BIGPP : std::is_same<CF, H2BigPPLut>::value ? OZ_NET_KERNEL_H2_BIGPP_LUT
+             : std::is_same<CF, H2MidPP>::value ? OZ_NET_KERNEL_H2_MIDPP : std::is_same<CF, H2LowPP1>::value ? OZ_NET_KERNEL_H2_LOWPP1
+             : std::is_same<CF, H2LowPP>::value ? OZ_NET_KERNEL_H2_LOWPP : std::is_same<CF, H2Big>::value ? OZ_NET_KERNEL_H2_BIG
+             : std::is_same<CF, H2Mid>::value ? OZ_NET_KERNEL_H2_MID : std::is_same<CF, H2Thin2>::value ? OZ_NET_KERNEL_H2_THIN2
+             : std::is_same<CF, H2Thin>::value ? OZ_NET_KERNEL_H2_THIN : std::is_same<CF, H2Thin4w>::value ? OZ_NET_KERNEL_H2_THIN4W : OZ_NET_KERNEL_NONE;
+    }
     // layer: 1..3 = conv2..4 (3x3, Cin = N = C), 4 = fc1, 5 = fc2 (taps 1), on tile CF with the k loop in `ksplit` slices (slabs in d_partial, spaced
     // for max_batch).  out_h2 = 1: the layer's output in the h2 layout, guarded by `low`; out_h2 = 0: fp32 rows -- fc2's (the heads kernel adds the
     // slices of a split launch: fc2_defer), or, for conv2 .. fc1, a calibration pass: the layer's BN output BEFORE the ReLU
@@ -1041,6 +1105,7 @@ struct OnnNet : oz_net {
     int launch_gemm_h2(const void* in, int layer, void* out, int out_h2, H2Low low, const int* d_count, int max_count, hipStream_t s, int ksplit = 1,
                        const unsigned* lut_ids = nullptr) {
         const OzLayerShape L = layers()[layer - 1];
+        plan[layer] = LayerPlan{CF::BM, ksplit, h2_kernel_id<CF>()};
         return launch_h2<CF, TAG>(L, in, d_wh[layer - 1], d_scale_h2[layer - 1], d_shift_h2[layer - 1], out, out_h2, layer == 5 ? &fc2_defer : nullptr, d_count,
                                   max_count, ksplit, d_partial, (long long)max_batch * L.pixels() * L.N, d_zero, d_flag, s, out_h2 || layer == 5, low, lut_ids);
     }
@@ -1059,6 +1124,7 @@ struct OnnNet : oz_net {
     void launch_heads(int max_count, const int* d_count, float* d_pi, float* d_v, hipStream_t s) {
         const OzDeferredReduce dr = fc2_defer;
         fc2_defer = OzDeferredReduce();
+        last_defer = dr;
         if (max_count >= 3072) hipLaunchKernelGGL(k_heads_t<HEADS_LP>, dim3((max_count + HEADS_LP - 1) / HEADS_LP), dim3(256), 0, s, f2, d_count, A, d_wpi, d_bpi, d_wv, d_bv, d_pi, d_v, dr);
         else if (max_count > HEADS_P) hipLaunchKernelGGL(k_heads_t<4>, dim3((max_count + 3) / 4), dim3(256), 0, s, f2, d_count, A, d_wpi, d_bpi, d_wv, d_bv, d_pi, d_v, dr);
         else hipLaunchKernelGGL(k_heads_t<HEADS_P>, dim3((max_count + HEADS_P - 1) / HEADS_P), dim3(256), 0, s, f2, d_count, A, d_wpi, d_bpi, d_wv, d_bv, d_pi, d_v, dr);
@@ -1068,6 +1134,7 @@ struct OnnNet : oz_net {
     template <int OUT_H2> void launch_conv2_lut(int max_count, const int* d_count, const float* scale, const float* shift, void* out, hipStream_t s,
                                                  H2Low low = H2Low(), float floor = 0.f) {
         const long long pixels = (long long)max_count * n * n;
+        plan[1] = LayerPlan{0, 1, C == 512 ? OZ_NET_KERNEL_LUT_XCD : OZ_NET_KERNEL_LUT};
         if (C == 512) {
             const unsigned blocks = 8u * (unsigned)((pixels + 32 * OZ_C2L_PPT - 1) / (32 * OZ_C2L_PPT));
             if (n == 8) hipLaunchKernelGGL((k_conv2_lut_xcd<8, OUT_H2>), dim3(blocks), dim3(256), 0, s, d_lut_ids, d_count, d_t2, scale, shift, out, d_flag, low, floor);
@@ -1521,6 +1588,7 @@ struct OnnNet : oz_net {
             TimedSlot t6(this, 6, s);
             launch_heads(max_count, d_count, d_pi, d_v, s);
         }
+        set_views(act1, use_t2 || use_lut ? -1 : 1, act2, act3, act4, f1, 1);
         OZ_HIP(hipGetLastError());
         return OZ_OK;
     }
@@ -1539,6 +1607,7 @@ struct OnnNet : oz_net {
         const long long rows_cap = (long long)max_batch * L.pixels();
         const bool big = b3_tile != 128 && L.pad == 0 && ksplit == 1 && (b3_tile == 256 || b3_big_tile_pays(rows_cap, L.N));
         if (layer == 2) last_conv3_rows = big ? B3B_BM : B3_BM;
+        plan[layer] = LayerPlan{big ? B3B_BM : B3_BM, ksplit, big ? OZ_NET_KERNEL_B3_BIG : OZ_NET_KERNEL_B3};
         return launch_b3<TAG>(L, in, d_wb[layer - 1], d_scale[layer], d_shift[layer], out, out_b3, layer == 5 ? &fc2_defer : nullptr, d_count, max_count, big,
                               ksplit, d_part_b3, rows_cap * L.N, d_zero, s);
     }
@@ -1569,6 +1638,7 @@ struct OnnNet : oz_net {
         { TimedSlot t4(this, 4, s); if (int rc = launch_gemm_b3<5>(b3a4, 4, b3f1, 1, d_count, max_count, s, fc1_b3_ksplit())) return rc; }
         { TimedSlot t5(this, 5, s); if (int rc = launch_gemm_b3<6>(b3f1, 5, f2, 0, d_count, max_count, s, fc2_b3_ksplit())) return rc; }
         { TimedSlot t6(this, 6, s); launch_heads(max_count, d_count, d_pi, d_v, s); }
+        set_views(b3a1, use_t2f ? -1 : 2, b3a2, b3a3, b3a4, b3f1, 2);
         OZ_HIP(hipGetLastError());
         return OZ_OK;
     }
@@ -1577,6 +1647,7 @@ struct OnnNet : oz_net {
                        float* d_v, hipStream_t s) override {
         if (!committed) { oz_set_error("network weights not committed (call oz_net_commit)"); return OZ_ERR_STATE; }
         if (max_count > max_batch) { oz_set_error("batch %d exceeds max_batch %d", max_count, max_batch); return OZ_ERR_ARG; }
+        last_count = max_count;
         if (precision == 1) return forward_h2(d_own, d_opp, d_count, max_count, d_pi, d_v, s);
         if (use_b3()) return forward_b3(d_own, d_opp, d_count, max_count, d_pi, d_v, s);
         return forward_f32(d_own, d_opp, d_count, max_count, d_pi, d_v, s);
@@ -1593,6 +1664,7 @@ struct OnnNet : oz_net {
         if (use_t2f && max_batch <= 32 && C == 512) {
             // few positions: pattern ids computed inside the gather (INLINE_IDS) -- one launch less
             TimedSlot t1(this, 1, s);
+            plan[1] = LayerPlan{0, 1, OZ_NET_KERNEL_LUT_XCD_INLINE};
             const unsigned blocks = 8u * (unsigned)(((long long)max_count * P + 32 * OZ_C2L_PPT - 1) / (32 * OZ_C2L_PPT));
             if (n == 8) hipLaunchKernelGGL((k_conv2_lut_xcd<8, false, true>), dim3(blocks), dim3(256), 0, s, (const unsigned*)nullptr, d_count, d_t2, d_scale[1], d_shift[1], (void*)act2, (int*)nullptr, H2Low(), 0.f, d_own, d_opp);
             else hipLaunchKernelGGL((k_conv2_lut_xcd<6, false, true>), dim3(blocks), dim3(256), 0, s, (const unsigned*)nullptr, d_count, d_t2, d_scale[1], d_shift[1], (void*)act2, (int*)nullptr, H2Low(), 0.f, d_own, d_opp);
@@ -1620,6 +1692,7 @@ struct OnnNet : oz_net {
         { TimedSlot t4(this, 4, s); if (int rc = launch_gemm(act4, 4, f1, d_count, max_count, s)) return rc; }
         { TimedSlot t5(this, 5, s); if (int rc = launch_gemm(f1, 5, f2, d_count, max_count, s, &fc2_defer)) return rc; }
         { TimedSlot t6(this, 6, s); launch_heads(max_count, d_count, d_pi, d_v, s); }
+        set_views(act1, use_t2f ? -1 : 0, act2, act3, act4, f1, 0);
         OZ_HIP(hipGetLastError());
         return OZ_OK;
     }
@@ -1883,6 +1956,7 @@ OZ_API int oz_net_commit(oz_net* net) {
     }
     OZ_HIP(hipDeviceSynchronize());
     if (int rc = eval_cache_clear(o)) return rc;             // new weights: every cached (pi, v) is stale
+    o->last_count = 0;                                       // ... and so is the view of the last forward (the commit ran forwards of its own)
     o->committed = true;
     return OZ_OK;
 }
@@ -2166,9 +2240,48 @@ OZ_API int oz_net_get_scaling(oz_net* net, int which, int32_t* out, int64_t nele
 OZ_API int oz_net_get_info(oz_net* net, int what, int* value) {
     OnnNet* o = as_onn(net);
     OZ_REQUIRE(o && value, "not an OthelloNN network / null argument");
-    OZ_REQUIRE(what == OZ_NET_INFO_CONV3_TILE_ROWS || what == OZ_NET_INFO_SELF_CHECK_GUARD || what == OZ_NET_INFO_ARITHMETIC, "unknown network info %d", what);
     std::lock_guard<std::mutex> lk(o->mu);
+    for (int l = 1; l <= 5; ++l) {                           // the launch plan of the last forward
+        const OnnNet::LayerPlan& p = o->plan[l];
+        if (what == OZ_NET_INFO_LAYER_TILE_ROWS(l)) { *value = p.tile_rows; return OZ_OK; }
+        if (what == OZ_NET_INFO_LAYER_KSLICES(l)) { *value = p.ksplit; return OZ_OK; }
+        if (what == OZ_NET_INFO_LAYER_KERNEL(l)) { *value = p.kernel; return OZ_OK; }
+    }
+    OZ_REQUIRE(what == OZ_NET_INFO_CONV3_TILE_ROWS || what == OZ_NET_INFO_SELF_CHECK_GUARD || what == OZ_NET_INFO_ARITHMETIC, "unknown network info %d", what);
     *value = what == OZ_NET_INFO_CONV3_TILE_ROWS ? o->last_conv3_rows : what == OZ_NET_INFO_ARITHMETIC ? (o->precision == 2 && !o->use_b3() ? 0 : o->precision) : o->sc_guard;
+    return OZ_OK;
+}
+
+// rows first_row .. first_row + rows - 1 of the output of `layer` (0 .. 3 = conv1 .. conv4, 4 / 5 = fc1 / fc2) in the last forward, as float64: what the
+// consuming kernel multiplies (header).  Reads only: a temporary device buffer, the null stream, no member written.
+OZ_API int oz_net_get_activation(oz_net* net, int layer, int64_t first_row, int64_t rows, double* out) {
+    OnnNet* o = as_onn(net);
+    OZ_REQUIRE(o && out, "oz_net_get_activation: not an OthelloNN network / null argument");
+    OZ_REQUIRE(layer >= 0 && layer <= 5, "oz_net_get_activation: layer must be 0 .. 5 (got %d)", layer);
+    std::lock_guard<std::mutex> lk(o->mu);
+    hipSetDevice(o->device);
+    if (!o->committed || o->last_count == 0) { oz_set_error("oz_net_get_activation: no forward since the last oz_net_commit"); return OZ_ERR_STATE; }
+    const int P = layer == 0 ? o->n * o->n : o->layers()[layer - 1].pixels(), N = layer == 0 ? o->C : o->layers()[layer - 1].N;
+    const long long total = (long long)o->last_count * P;
+    OZ_REQUIRE(first_row >= 0 && rows > 0 && first_row <= total && rows <= total - first_row,
+               "oz_net_get_activation: rows [%lld, %lld) outside the %lld rows of the last forward", (long long)first_row, (long long)(first_row + rows), total);
+    const OnnNet::ActView v = o->view[layer];
+    if (v.fmt < 0 || (v.fmt != 3 && !v.p)) {
+        oz_set_error("oz_net_get_activation: the last forward did not materialise the output of layer %d (conv1 folded into a pattern table: "
+                     "oz_net_set_tables(0) runs it as a kernel)", layer);
+        return OZ_ERR_STATE;
+    }
+    double* d_out = nullptr;
+    OZ_HIP(hipMalloc((void**)&d_out, sizeof(double) * (size_t)rows * N));
+    const dim3 grid8((unsigned)((rows * (N / 8) + 255) / 256)), grid1((unsigned)((rows * N + 255) / 256));
+    if (v.fmt == 0) hipLaunchKernelGGL(k_act_rows_f64<0>, grid8, dim3(256), 0, 0, v.p, (const int*)nullptr, (long long)first_row, (long long)rows, N, d_out);
+    else if (v.fmt == 1) hipLaunchKernelGGL(k_act_rows_f64<1>, grid8, dim3(256), 0, 0, v.p, v.aexp, (long long)first_row, (long long)rows, N, d_out);
+    else if (v.fmt == 2) hipLaunchKernelGGL(k_act_rows_f64<2>, grid8, dim3(256), 0, 0, v.p, (const int*)nullptr, (long long)first_row, (long long)rows, N, d_out);
+    else hipLaunchKernelGGL(k_deferred_rows_f64, grid1, dim3(256), 0, 0, o->last_defer, (long long)first_row, (long long)rows, N, d_out);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpy(out, d_out, sizeof(double) * (size_t)rows * N, hipMemcpyDeviceToHost);
+    hipFree(d_out);
+    OZ_HIP(e);
     return OZ_OK;
 }
 
