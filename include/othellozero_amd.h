@@ -635,6 +635,40 @@ int oz_trainer_fit_epoch(oz_trainer* t, const int32_t* order, int64_t count, int
 int oz_trainer_outputs(oz_trainer* t, int B, float* p /* [B][n*n] */, float* v /* [B] */);   /* of the last forward pass */
 /* post-activation output of block `layer` (0-3 conv, 4-5 dense; [B][pixels][channels]) of the last forward pass -- inspection */
 int oz_trainer_get_activation(oz_trainer* t, int layer, int B, float* data, int64_t nelem);
+/* Diagnostics: read-only views of the last step, for judging every GEMM of the trainer on its own (no kernel is changed by them).
+ * get_preact: z[layer], the GEMM output plus bias BEFORE the BN, [B][Hout][Hout][Co], layer 0 .. 5.
+ * get_dz:     the WHOLE buffer of the gradient wrt z[layer], [B][Hz][Hz][Co]: conv3 / conv4 ('valid') keep it zero-bordered (Hz = Hout + 4, interior at
+ *             offset 2), every other layer has Hz = Hout (dense layers 1).
+ * set_capture (off by default): while on, every data-gradient launch (and the heads' backward) is followed by a device-to-device copy on the main
+ *             stream of the live rows of its output into a per-layer buffer (allocated at the first `on`) -- the data gradients live in two
+ *             ping-pong buffers that are overwritten two layers later.  With capture off the launch sequence of a step is unchanged.
+ * get_dgrad:  the captured gradient wrt a[layer] (layer 0 .. 5; [B][Hout][Hout][Co]): the raw GEMM output, before the ReLU mask of the BN backward.
+ *             OZ_ERR_STATE when capture is off or no step ran since it was switched on.
+ * get_head_grads: the gradients wrt the policy logits and the value head's pre-activation, the two operands of the heads' data gradient.
+ * get_preact, get_dz and get_head_grads return OZ_ERR_STATE before the first step of the trainer.
+ * get_plan:   the launch plan of the last step, as the launchers themselves reported it (oz_net_get_info's counterpart): for layer l = 1 .. 5
+ *             (conv2 .. fc2) the OZ_TRAINER_PLAN_FIELDS ints at plan[(l - 1) * OZ_TRAINER_PLAN_FIELDS]; n = 5 * OZ_TRAINER_PLAN_FIELDS. */
+#define OZ_TRAINER_PLAN_FIELDS 8             /* ints per layer; [7] is reserved (0) */
+#define OZ_TRAINER_PLAN_FWD_KSLICES 0        /* forward GEMM: k-slices, then the kernel (OZ_NET_KERNEL_*: names the tile) */
+#define OZ_TRAINER_PLAN_FWD_KERNEL 1
+#define OZ_TRAINER_PLAN_DGRAD_KSLICES 2      /* data-gradient GEMM likewise */
+#define OZ_TRAINER_PLAN_DGRAD_KERNEL 3
+#define OZ_TRAINER_PLAN_DGRAD_TAP_SKIP 4     /* 1: the data gradient ran on pixel-major row tiles (OZ_NET_KERNEL_F32_STD_PIXMAJOR), the form of k_gemm_f32
+                                              * that skips the k-tiles of taps reading only zeros; derived from the kernel the launcher reports */
+#define OZ_TRAINER_PLAN_WGRAD_KERNEL 5       /* OZ_TRAINER_WGRAD_* */
+#define OZ_TRAINER_PLAN_WGRAD_MSPLIT 6       /* row splits of the weight gradient (> 1: raw slabs + the fixed-order sum) */
+enum {
+    OZ_TRAINER_WGRAD_TAPS_F32 = 1,           /* k_wgrad_f32, one tap per block */
+    OZ_TRAINER_WGRAD_BOARDS_F32 = 2,         /* k_wgrad_conv, board-resident */
+    OZ_TRAINER_WGRAD_OCT_H2 = 3,             /* k_wgrad_h2 on the octet images */
+    OZ_TRAINER_WGRAD_OCT_B3 = 4              /* k_wgrad_b3 on the octet images */
+};
+int oz_trainer_get_preact(oz_trainer* t, int layer, int B, float* data, int64_t nelem);
+int oz_trainer_get_dz(oz_trainer* t, int layer, int B, float* data, int64_t nelem);
+int oz_trainer_set_capture(oz_trainer* t, int on);
+int oz_trainer_get_dgrad(oz_trainer* t, int layer, int B, float* data, int64_t nelem);
+int oz_trainer_get_head_grads(oz_trainer* t, int B, float* dlogit /* [B][n*n] */, float* dvpre /* [B] */);
+int oz_trainer_get_plan(oz_trainer* t, int* plan, int n);
 int oz_trainer_sync(oz_trainer* t);
 int oz_trainer_step_count(oz_trainer* t, int64_t* step);
 

@@ -194,12 +194,12 @@ int oz_gemm_f32_launch(const float* in, const float* Wt, const float* scale, con
 // the f16x2 GEMM (k_gemm_h2, oz_net_h2.h) on h2-layout operands, fp32 rows out; zero_line = >= 256 B of zeros, flag = sticky range flag
 int oz_gemm_h2_launch(const void* in_h2, const void* Wh, const float* scale, const float* shift, float* out, const int* d_count, int max_count,
                       int Hin, int Hout, int pad, int Cin, int taps, int N, hipStream_t s, float* partial, long long partial_floats,
-                      const void* zero_line, int* flag);
+                      const void* zero_line, int* flag, int* plan_out = nullptr);
 // the bf16x3 GEMM (k_gemm_b3, oz_net_b3.h) on b3-layout operands, fp32 rows out (act = relu or identity); zero_line = >= 128 B of zeros;
-// tag 0 / 1: forward / data-gradient symbol in a profile
+// tag 0 / 1: forward / data-gradient symbol in a profile.  plan_out (optional, both launchers): [0] = k-slices, [1] = OZ_NET_KERNEL_* of the launch
 int oz_gemm_b3_launch(const void* in_b3, const void* Wb, const float* scale, const float* shift, float* out, const int* d_count, int max_count,
                       int Hin, int Hout, int pad, int Cin, int taps, int N, int relu, hipStream_t s, float* partial, long long partial_floats,
-                      const void* zero_line, int tag);
+                      const void* zero_line, int tag, int* plan_out = nullptr);
 // fp32 rows [*d_count * P][C] -> the b3 layout (k_f32_to_b3)
 int oz_f32_to_b3_launch(const float* x, const int* d_count, int max_count, int P, int C, void* out, hipStream_t s);
 // Keras weights [K][N] with k = tap * Cin + ci -> b3 rows [N][K] in the GEMM's tap-inner k order (k_w_to_b3)

@@ -576,7 +576,7 @@ static bool b3_big_tile_pays(long long rows, int N) {
 // 128 x 256 tiles with the k loop split until every CU has a block (raw slabs + the fixed-order fp32 reduce).
 int oz_gemm_h2_launch(const void* in_h2, const void* Wh, const float* scale, const float* shift, float* out, const int* d_count, int max_count,
                       int Hin, int Hout, int pad, int Cin, int taps, int N, hipStream_t s, float* partial, long long partial_floats,
-                      const void* zero_line, int* flag) {
+                      const void* zero_line, int* flag, int* plan_out) {
     OZ_REQUIRE(N % 256 == 0 && Cin % 32 == 0, "gemm_h2: N %% 256 and Cin %% 32 must be 0 (N=%d Cin=%d)", N, Cin);
     const OzLayerShape L = {Hin, Hout, pad, Cin, taps, N};
     const long long Mmax = (long long)max_count * L.pixels();
@@ -595,6 +595,8 @@ int oz_gemm_h2_launch(const void* in_h2, const void* Wh, const float* scale, con
     };
     // (round 6: the 1-phase / 3-stage loop of the 128 x 256 tile, H2LowPP1, measured SLOWER here -- 1.00 against 0.93-0.96 ms per step at the reference's batch: the
     //  trainer's k-slices are 8 .. 36 tiles and the deeper prologue, two tiles staged before the first MFMA, costs more than the halved barriers return)
+    // plan_out (optional): [0] = the k-slices of this launch, [1] = the kernel (OZ_NET_KERNEL_H2_*), as oz_gemm_f32_launch reports them
+    if (plan_out) { plan_out[0] = ksplit; plan_out[1] = mid ? OZ_NET_KERNEL_H2_MIDPP : big ? OZ_NET_KERNEL_H2_BIGPP : low ? OZ_NET_KERNEL_H2_LOWPP : OZ_NET_KERNEL_H2_SMALL; }
     return mid ? go(H2MidPP()) : big ? go(H2BigPP()) : low ? go(H2LowPP()) : go(H2Small());
 }
 
@@ -606,7 +608,7 @@ int oz_gemm_h2_launch(const void* in_h2, const void* Wh, const float* scale, con
 // forward launches through the same launch_b3 with its own tiles and splits (OnnNet::launch_gemm_b3).
 int oz_gemm_b3_launch(const void* in_b3, const void* Wb, const float* scale, const float* shift, float* out, const int* d_count, int max_count,
                       int Hin, int Hout, int pad, int Cin, int taps, int N, int relu, hipStream_t s, float* partial, long long partial_floats,
-                      const void* zero_line, int tag) {
+                      const void* zero_line, int tag, int* plan_out) {
     const OzLayerShape L = {Hin, Hout, pad, Cin, taps, N};
     const long long Mmax = (long long)max_count * L.pixels();
     const bool big = pad == 0 && b3_big_tile_pays(Mmax, N);
@@ -616,6 +618,8 @@ int oz_gemm_b3_launch(const void* in_b3, const void* Wb, const float* scale, con
         return launch_b3<decltype(t)::value>(L, (const uint4*)in_b3, (const uint4*)Wb, scale, shift, out, 0, nullptr, d_count, max_count, big, ksplit, partial,
                                              Mmax * N, (const uint4*)zero_line, s, relu);
     };
+    // plan_out (optional): [0] = the k-slices of this launch, [1] = the kernel (OZ_NET_KERNEL_B3 / OZ_NET_KERNEL_B3_BIG)
+    if (plan_out) { plan_out[0] = ksplit; plan_out[1] = big ? OZ_NET_KERNEL_B3_BIG : OZ_NET_KERNEL_B3; }
     return tag ? go(std::integral_constant<int, 8>()) : go(std::integral_constant<int, 7>());
 }
 // k_f32_to_b3 for callers outside the network object: fp32 rows [*d_count * P][C] -> the b3 layout (grid sized for max_count boards)

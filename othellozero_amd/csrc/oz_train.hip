@@ -989,6 +989,10 @@ struct oz_trainer {
     int* ds_order = nullptr;
     double* ds_acc = nullptr;
     int64_t ds_n = 0, ds_cap = 0, ds_order_cap = 0;
+    // diagnostics (oz_trainer_set_capture / get_dgrad / get_plan): the raw data gradients of a step, copied out of the ping-pong buffers, and its launch plan
+    bool capture = false, cap_valid = false, ran = false;      // ran: a step has been enqueued (the views below have something to show)
+    float* cap[6] = {};                  // cap[l] = the gradient wrt a[l] as the heads / the data-gradient launch of layer l + 1 left it (allocated at the first capture)
+    int plan[5][OZ_TRAINER_PLAN_FIELDS] = {};
     std::vector<void*> allocs;
     bool dirty = true;                   // derived operands need a refresh
     std::mutex mu;                       // one caller at a time (ThreadWorker-style Python threads)
@@ -1329,7 +1333,8 @@ static int t_forward(oz_trainer* t, int B) {
         case 0:
             if (int rc = t_wait_once(s, t->ev_wt, t->wait_wt)) return rc;          // the first fp32 operand of the step: conv2's, or fc1's in a split mode
             if (int rc = oz_gemm_f32_launch(t->a[l - 1], t->Wt[l], t->ones, t->param(6 * l + 1), t->z[l], t->d_count, B, L.Hin, L.Hout, L.pad,
-                                            L.Cin, L.taps, L.Co, 0, s, t->gpartial, t->gpartial_floats)) return rc;
+                                            L.Cin, L.taps, L.Co, 0, s, t->gpartial, t->gpartial_floats, 0, 0, -1, nullptr, 0, nullptr,
+                                            &t->plan[l - 1][OZ_TRAINER_PLAN_FWD_KSLICES])) return rc;
             break;
         case 1: {
             const TPacked& k = t->pk[0];
@@ -1337,7 +1342,7 @@ static int t_forward(oz_trainer* t, int B) {
             hipLaunchKernelGGL(k_t_act_to_h2, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, s, t->a[l - 1], t->d_count, Pin, C, k.act[l - 1], t->h2flag);
             if (int rc = t_wait_once(s, t->ev_wl[l], t->wait_wl[l])) return rc;
             if (int rc = oz_gemm_h2_launch(k.act[l - 1], k.W[l], t->wscale[l], t->param(6 * l + 1), t->z[l], t->d_count, B, L.Hin, L.Hout, L.pad,
-                                           L.Cin, 9, L.Co, s, t->gpartial, t->gpartial_floats, t->zeros, t->h2flag)) return rc;
+                                           L.Cin, 9, L.Co, s, t->gpartial, t->gpartial_floats, t->zeros, t->h2flag, &t->plan[l - 1][OZ_TRAINER_PLAN_FWD_KSLICES])) return rc;
             break;
         }
         case 2: {        // (z is pre-BN: no ReLU)
@@ -1345,7 +1350,7 @@ static int t_forward(oz_trainer* t, int B) {
             if (int rc = oz_f32_to_b3_launch(t->a[l - 1], t->d_count, t->Bmax, Pin, C, k.act[l - 1], s)) return rc;
             if (int rc = t_wait_once(s, t->ev_wl[l], t->wait_wl[l])) return rc;
             if (int rc = oz_gemm_b3_launch(k.act[l - 1], k.W[l], t->ones, t->param(6 * l + 1), t->z[l], t->d_count, t->Bmax, L.Hin, L.Hout, L.pad,
-                                           L.Cin, 9, L.Co, 0, s, t->gpartial, t->gpartial_floats, t->zeros, 0)) return rc;
+                                           L.Cin, 9, L.Co, 0, s, t->gpartial, t->gpartial_floats, t->zeros, 0, &t->plan[l - 1][OZ_TRAINER_PLAN_FWD_KSLICES])) return rc;
         }
         }
         if (int rc = t_bn_forward(t, l, B)) return rc;
@@ -1353,6 +1358,13 @@ static int t_forward(oz_trainer* t, int B) {
     hipLaunchKernelGGL(k_t_heads, dim3(B), dim3(64), 0, s, t->a[5], t->d_count, n, t->policy_loss, t->param(36), t->param(37), t->param(38), t->param(39),
                        t->d_pit, t->d_zt, t->p, t->v, t->dlogit, t->dvpre, t->loss);
     OZ_HIP(hipGetLastError());
+    return OZ_OK;
+}
+
+// capture on: the live rows of dA (the gradient wrt a[l], B boards) are copied to cap[l] behind the launch that wrote them, on the main stream
+static int t_capture(oz_trainer* t, int l, int B, const float* dA) {
+    if (!t->capture) return OZ_OK;
+    OZ_HIP(hipMemcpyAsync(t->cap[l], dA, (size_t)B * t->L[l].P * t->L[l].Co * sizeof(float), hipMemcpyDeviceToDevice, t->s));
     return OZ_OK;
 }
 
@@ -1366,7 +1378,7 @@ static int t_heads_backward(oz_trainer* t, int B, float* dA) {
     hipLaunchKernelGGL(k_t_heads_dgrad, dim3((unsigned)(((long long)B * 512 + 255) / 256)), dim3(256), 0, s, t->dlogit, t->dvpre, t->param(36),
                        t->param(38), t->d_count, A, dA);
     OZ_HIP(hipGetLastError());
-    return OZ_OK;
+    return t_capture(t, 5, B, dA);
 }
 
 // BN backward of layer l: dA (the gradient wrt a[l]) -> dz[l], the gradients of gamma, beta and the bias; f16x2 also leaves max |dz[l]| in dzmax[l]
@@ -1487,6 +1499,9 @@ static int t_wgrad(oz_trainer* t, int l, int B) {
         hipLaunchKernelGGL(k_wgrad_f32, dim3(wblocks, msplit), dim3(256), 0, sw, t->a[l - 1], t->dz[l], t->d_count, g, t->grad(6 * l), msplit, wp, wcount);
     }
     }
+    t->plan[l - 1][OZ_TRAINER_PLAN_WGRAD_KERNEL] = kernel == TAPS_F32 ? OZ_TRAINER_WGRAD_TAPS_F32 : kernel == BOARDS_F32 ? OZ_TRAINER_WGRAD_BOARDS_F32
+                                                 : kernel == OCT_H2 ? OZ_TRAINER_WGRAD_OCT_H2 : OZ_TRAINER_WGRAD_OCT_B3;
+    t->plan[l - 1][OZ_TRAINER_PLAN_WGRAD_MSPLIT] = msplit;
     if (msplit > 1)
         hipLaunchKernelGGL(k_t_sum_partials, dim3((unsigned)((wcount + 255) / 256)), dim3(256), 0, sw, wp, msplit, wcount, t->grad(6 * l));
     OZ_HIP(hipGetLastError());
@@ -1494,11 +1509,13 @@ static int t_wgrad(oz_trainer* t, int l, int B) {
 }
 
 // data gradient of layer l = 1 .. 5: dz[l] -> dA = the gradient wrt a[l - 1]
-static int t_dgrad(oz_trainer* t, int l, int B, float* dA) {
+static int t_dgrad_launch(oz_trainer* t, int l, int B, float* dA) {
     hipStream_t s = t->s;
     const TLayer& L = t->L[l];
+    int* const plan = &t->plan[l - 1][OZ_TRAINER_PLAN_DGRAD_KSLICES];      // [0] k-slices, [1] kernel: what the launchers report
     if (l >= 4)            // dense: dX = dZ . W^T; the Keras kernel [in][out] already is the [N = in][K = out] operand
-        return oz_gemm_f32_launch(t->dz[l], t->param(6 * l), t->ones, t->zeros, dA, t->d_count, B, 1, 1, 0, L.Co, 1, L.Cin, 0, s, t->gpartial, t->gpartial_floats);
+        return oz_gemm_f32_launch(t->dz[l], t->param(6 * l), t->ones, t->zeros, dA, t->d_count, B, 1, 1, 0, L.Co, 1, L.Cin, 0, s, t->gpartial, t->gpartial_floats,
+                                  0, 0, -1, nullptr, 0, nullptr, plan);
     // 3x3 conv: conv of dz (zero-bordered for 'valid' layers) with the reversed, channel-swapped taps
     const int same = L.pad ? 1 : 0;
     if (int rc = t_wait_once(s, t->ev_wd, t->wait_wd)) return rc;
@@ -1508,7 +1525,7 @@ static int t_dgrad(oz_trainer* t, int l, int B, float* dA) {
         const long long thr = (long long)B * L.P * (L.Co / 8);
         hipLaunchKernelGGL(k_t_dz_to_b3, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, s, t->dz[l], t->d_count, L.Hout, L.Hz, L.zoff, L.Co, k.dz[l]);
         return oz_gemm_b3_launch(k.dz[l], k.Wd[l], t->ones, t->zeros, dA, t->d_count, t->Bmax, L.Hz, L.Hin, same, L.Co, 9, L.Cin, 0, s, t->gpartial,
-                                 t->gpartial_floats, t->zeros, 1);
+                                 t->gpartial_floats, t->zeros, 1, plan);
     }
     case 1: {              // f16x2: dz scaled into the fp16 range by its own maximum, h2 layout, same zero-bordered geometry
         const TPacked& k = t->pk[0];
@@ -1517,12 +1534,17 @@ static int t_dgrad(oz_trainer* t, int l, int B, float* dA) {
         hipLaunchKernelGGL(k_t_dz_to_h2, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, s, t->dz[l], t->d_count, L.Hout, L.Hz, L.zoff, L.Co,
                            t->dzmax + l, t->wmax + (l - 1), k.dz[l], t->dscale[l], L.Cin, t->h2flag);
         return oz_gemm_h2_launch(k.dz[l], k.Wd[l], t->dscale[l], t->zeros, dA, t->d_count, B, L.Hz, L.Hin, same, L.Co, 9, L.Cin, s, t->gpartial,
-                                 t->gpartial_floats, t->zeros, t->h2flag);
+                                 t->gpartial_floats, t->zeros, t->h2flag, plan);
     }
     default:               // (the non-zero core of the zero-bordered dz buffer: taps that only read the border are skipped at large batch)
         return oz_gemm_f32_launch(t->dz[l], t->Wd[l], t->ones, t->zeros, dA, t->d_count, B, L.Hz, L.Hin, same, L.Co, 9, L.Cin, 0, s, t->gpartial,
-                                  t->gpartial_floats, 0, L.zoff, L.zoff + L.Hout);
+                                  t->gpartial_floats, 0, L.zoff, L.zoff + L.Hout, nullptr, 0, nullptr, plan);
     }
+}
+static int t_dgrad(oz_trainer* t, int l, int B, float* dA) {
+    if (int rc = t_dgrad_launch(t, l, B, dA)) return rc;
+    t->plan[l - 1][OZ_TRAINER_PLAN_DGRAD_TAP_SKIP] = t->plan[l - 1][OZ_TRAINER_PLAN_DGRAD_KERNEL] == OZ_NET_KERNEL_F32_STD_PIXMAJOR;
+    return t_capture(t, l - 1, B, dA);
 }
 
 // forward + backward of the batch staged in d_own / d_opp / d_pit / d_zt / d_count (B boards): gradients land in the arena, the batch-mean
@@ -1541,6 +1563,8 @@ static int t_forward_backward_async(oz_trainer* t, int B) {
     }
     OZ_HIP(hipEventRecord(t->ev_w, t->s2));        // every gradient is complete before the caller (Adam, all-reduce, get_grad) sees the arena
     OZ_HIP(hipStreamWaitEvent(t->s, t->ev_w, 0));
+    t->cap_valid = t->capture;
+    t->ran = true;
     return OZ_OK;
 }
 
@@ -1716,5 +1740,71 @@ OZ_API int oz_trainer_outputs(oz_trainer* t, int B, float* p, float* v) {
     if (p) OZ_HIP(hipMemcpyAsync(p, t->p, (size_t)B * t->n * t->n * sizeof(float), hipMemcpyDeviceToHost, t->s));
     if (v) OZ_HIP(hipMemcpyAsync(v, t->v, B * sizeof(float), hipMemcpyDeviceToHost, t->s));
     OZ_HIP(hipStreamSynchronize(t->s));
+    return OZ_OK;
+}
+
+// ---------------------------------------------------------------- diagnostics: read-only views of the last step (the per-kernel parity tests)
+// a device buffer of the last step -> host, on the main stream (every entry point that ran the step has synchronised it)
+static int t_read(oz_trainer* t, const float* src, float* data, int64_t nelem) {
+    OZ_HIP(hipSetDevice(t->device));
+    OZ_HIP(hipMemcpyAsync(data, src, nelem * sizeof(float), hipMemcpyDeviceToHost, t->s));
+    OZ_HIP(hipStreamSynchronize(t->s));
+    return OZ_OK;
+}
+static int t_need_step(oz_trainer* t, const char* who) {
+    if (t->ran) return OZ_OK;
+    oz_set_error("%s: no step has run on this trainer yet", who);
+    return OZ_ERR_STATE;
+}
+OZ_API int oz_trainer_get_preact(oz_trainer* t, int layer, int B, float* data, int64_t nelem) {
+    OZ_REQUIRE(t && data && layer >= 0 && layer < 6 && B >= 1 && B <= t->Bmax, "oz_trainer_get_preact: bad argument");
+    T_LOCK(t);
+    const TLayer& L = t->L[layer];
+    OZ_REQUIRE(nelem == (int64_t)B * L.P * L.Co, "oz_trainer_get_preact: expected %lld elements", (long long)B * L.P * L.Co);
+    if (int rc = t_need_step(t, "oz_trainer_get_preact")) return rc;
+    return t_read(t, t->z[layer], data, nelem);
+}
+OZ_API int oz_trainer_get_dz(oz_trainer* t, int layer, int B, float* data, int64_t nelem) {
+    OZ_REQUIRE(t && data && layer >= 0 && layer < 6 && B >= 1 && B <= t->Bmax, "oz_trainer_get_dz: bad argument");
+    T_LOCK(t);
+    const TLayer& L = t->L[layer];
+    OZ_REQUIRE(nelem == (int64_t)B * L.Hz * L.Hz * L.Co, "oz_trainer_get_dz: expected %lld elements", (long long)B * L.Hz * L.Hz * L.Co);
+    if (int rc = t_need_step(t, "oz_trainer_get_dz")) return rc;
+    return t_read(t, t->dz[layer], data, nelem);
+}
+OZ_API int oz_trainer_set_capture(oz_trainer* t, int on) {
+    OZ_REQUIRE(t, "oz_trainer_set_capture: NULL");
+    T_LOCK(t);
+    OZ_HIP(hipSetDevice(t->device));
+    if (on && !t->cap[5]) {              // (the last of the six: an allocation that failed part-way is repeated, never half used)
+        for (int l = 0; l < 6; ++l) T_ALLOC(t->cap[l], (size_t)t->Bmax * t->L[l].P * t->L[l].Co);
+        OZ_HIP(hipStreamSynchronize(t->s));
+    }
+    t->capture = on != 0;
+    t->cap_valid = false;                 // what an earlier step captured is not the next reader's step
+    return OZ_OK;
+}
+OZ_API int oz_trainer_get_dgrad(oz_trainer* t, int layer, int B, float* data, int64_t nelem) {
+    OZ_REQUIRE(t && data && layer >= 0 && layer < 6 && B >= 1 && B <= t->Bmax, "oz_trainer_get_dgrad: bad argument");
+    T_LOCK(t);
+    if (!t->capture || !t->cap_valid) {
+        oz_set_error("oz_trainer_get_dgrad: no captured step (oz_trainer_set_capture(t, 1), then a step)");
+        return OZ_ERR_STATE;
+    }
+    const TLayer& L = t->L[layer];
+    OZ_REQUIRE(nelem == (int64_t)B * L.P * L.Co, "oz_trainer_get_dgrad: expected %lld elements", (long long)B * L.P * L.Co);
+    return t_read(t, t->cap[layer], data, nelem);
+}
+OZ_API int oz_trainer_get_head_grads(oz_trainer* t, int B, float* dlogit, float* dvpre) {
+    OZ_REQUIRE(t && dlogit && dvpre && B >= 1 && B <= t->Bmax, "oz_trainer_get_head_grads: bad argument");
+    T_LOCK(t);
+    if (int rc = t_need_step(t, "oz_trainer_get_head_grads")) return rc;
+    if (int rc = t_read(t, t->dlogit, dlogit, (int64_t)B * t->n * t->n)) return rc;
+    return t_read(t, t->dvpre, dvpre, B);
+}
+OZ_API int oz_trainer_get_plan(oz_trainer* t, int* plan, int n) {
+    OZ_REQUIRE(t && plan && n == 5 * OZ_TRAINER_PLAN_FIELDS, "oz_trainer_get_plan: plan holds 5 x OZ_TRAINER_PLAN_FIELDS ints");
+    T_LOCK(t);
+    memcpy(plan, t->plan, sizeof t->plan);
     return OZ_OK;
 }

@@ -89,6 +89,12 @@ class Trainer:
             out[i] = a
         return out
 
+    def get_grad(self, index):
+        """the gradient of trainable array `index` after forward_backward"""
+        a = np.zeros(self.shapes[index], dtype=np.float32)
+        _lib.check(_lib.load().oz_trainer_get_grad(self._h, index, _lib.p_f32(a), a.size))
+        return a
+
     def grad_arena(self):
         ptr, n = C.c_void_p(), C.c_int64()
         _lib.check(_lib.load().oz_trainer_grad_arena(self._h, C.byref(ptr), C.byref(n)))
@@ -146,6 +152,52 @@ class Trainer:
         a = np.zeros(shape, np.float32)
         _lib.check(_lib.load().oz_trainer_get_activation(self._h, layer, B, _lib.p_f32(a), a.size))
         return a
+
+    # ---- read-only views of the last step (diagnostics: the per-kernel parity tests)
+    def _layer_shape(self, layer, border=False):
+        n, C_ = self.n, self.channels
+        side = [n, n, n - 2, n - 4][layer] + (4 if border and layer in (2, 3) else 0) if layer < 4 else 1
+        return (side, side, C_) if layer < 4 else (1, 1, (1024, 512)[layer - 4])
+
+    def _view(self, fn, layer, B, border=False):
+        a = np.zeros((B,) + self._layer_shape(layer, border), np.float32)
+        _lib.check(fn(self._h, layer, B, _lib.p_f32(a), a.size))
+        return a
+
+    def preact(self, layer, B):
+        """z[layer] of the last forward pass: the GEMM output plus bias BEFORE the BN, (B, Hout, Hout, Co); layer 0 .. 5 (dense: Hout = 1)"""
+        return self._view(_lib.load().oz_trainer_get_preact, layer, B)
+
+    def dz(self, layer, B):
+        """the whole buffer of the gradient wrt z[layer] of the last step, (B, Hz, Hz, Co): conv3 / conv4 keep it zero-bordered (Hz = Hout + 4)"""
+        return self._view(_lib.load().oz_trainer_get_dz, layer, B, border=True)
+
+    def set_capture(self, on):
+        """while on, a step keeps a copy of every raw data gradient (dgrad); off by default, and then the launch sequence is unchanged"""
+        _lib.check(_lib.load().oz_trainer_set_capture(self._h, 1 if on else 0))
+
+    def dgrad(self, layer, B):
+        """the captured gradient wrt a[layer] (the raw output of the data-gradient GEMM of layer + 1, of the heads for layer 5), (B, Hout, Hout, Co)"""
+        return self._view(_lib.load().oz_trainer_get_dgrad, layer, B)
+
+    def head_grads(self, B):
+        """(dlogit (B, n*n), dvpre (B,)) of the last step: the gradients wrt the policy logits and the value head's pre-activation"""
+        dl, dv = np.zeros((B, self.n * self.n), np.float32), np.zeros(B, np.float32)
+        _lib.check(_lib.load().oz_trainer_get_head_grads(self._h, B, _lib.p_f32(dl), _lib.p_f32(dv)))
+        return dl, dv
+
+    def plan(self):
+        """{layer 1 .. 5: dict(fwd_kernel, fwd_kslices, dgrad_kernel, dgrad_kslices, dgrad_tap_skip, wgrad_kernel, wgrad_msplit)} of the last step,
+        as the launchers reported it (oz_trainer_get_plan)"""
+        F = _lib.TRAINER_PLAN_FIELDS
+        v = np.zeros(5 * F, np.int32)
+        _lib.check(_lib.load().oz_trainer_get_plan(self._h, _lib.p_i32(v), v.size))
+        out = {}
+        for l in range(1, 6):
+            f = [int(x) for x in v[(l - 1) * F:l * F]]
+            out[l] = dict(fwd_kslices=f[0], fwd_kernel=_lib.NET_KERNEL_NAMES[f[1]], dgrad_kslices=f[2], dgrad_kernel=_lib.NET_KERNEL_NAMES[f[3]],
+                          dgrad_tap_skip=bool(f[4]), wgrad_kernel=_lib.TRAINER_WGRAD_NAMES[f[5]], wgrad_msplit=f[6])
+        return out
 
     @property
     def step(self):

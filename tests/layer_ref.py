@@ -57,13 +57,59 @@ def sparse_columns(kernel, rs, nnz=SPARSE_NNZ):
     return out.reshape(w.shape)
 
 
+def _biregular(rows, cols, per_row, per_col, rs):
+    """a random 0/1 pattern (rows, cols) with exactly per_row ones in every row and per_col in every column: the row stubs against a random
+    permutation of the column stubs, a stub pair that repeats an earlier (row, col) re-dealt by swapping its column with a random other stub's"""
+    assert rows * per_row == cols * per_col and per_row <= cols and per_col <= rows
+    r = np.repeat(np.arange(rows), per_row)
+    c = rs.permutation(np.repeat(np.arange(cols), per_col))
+    for _ in range(1000):
+        key = r * cols + c
+        _, first = np.unique(key, return_index=True)
+        dup = np.setdiff1d(np.arange(key.size), first)
+        if dup.size == 0:
+            break
+        for i in dup:
+            j = rs.randint(key.size)
+            c[i], c[j] = c[j], c[i]
+    keep = np.zeros((rows, cols), bool)
+    keep[r, c] = True
+    assert np.all(keep.sum(axis=1) == per_row) and np.all(keep.sum(axis=0) == per_col)
+    return keep
+
+
+def bisparse_kernel(kernel, rs, nnz=SPARSE_NNZ):
+    """`kernel` thinned in BOTH directions, so that the forward sum (over k, for an output column) and the data-gradient sum (over (tap, co), for
+    an input channel) are both short.  3x3 kernels (3, 3, Cin, Co): exactly nnz entries per output channel and exactly nnz per input channel, each
+    at a random tap (the (ci, co) pairs are a biregular pattern, so no position repeats).  Dense kernels (K, N): exactly `per_row` = max(2, N nnz / K)
+    entries per input row and per_row K / N per output column (= nnz wherever N nnz / K >= 2).  Kept entries are scaled by sqrt(K / entries per
+    column), as sparse_columns does"""
+    w = np.asarray(kernel)
+    if w.ndim == 4:
+        _, _, ci, co = w.shape
+        pair = _biregular(ci, co, nnz * co // ci, nnz, rs)
+        i, o = np.nonzero(pair)
+        keep = np.zeros(w.shape, bool)
+        keep[rs.randint(3, size=i.size), rs.randint(3, size=i.size), i, o] = True
+        K, per_col = 9 * ci, nnz
+    else:
+        K, N = w.shape
+        per_row = max(2, N * nnz // K)
+        per_col = per_row * K // N
+        keep = _biregular(K, N, per_row, per_col, rs)
+    out = (np.where(keep, w, np.float32(0)) * np.float32(np.sqrt(K / per_col))).astype(np.float32)
+    assert np.count_nonzero(out) == np.count_nonzero(keep)
+    return out
+
+
 _weights_cache = {}
 
 
 def network_weights(n, channels, kind):
     """the two test networks, built once per (board, filters, kind) and never modified: 'dense' = init_weights(randomize_all=True) as the existing
     tests use it; 'sparse' = the same draw with the kernels of conv2, conv3, conv4, fc1 and fc2 thinned to SPARSE_NNZ entries per output column
-    and scaled by sqrt(K / SPARSE_NNZ) (sparse_columns); biases and all four BN arrays stay random"""
+    and scaled by sqrt(K / SPARSE_NNZ) (sparse_columns); 'bisparse' = the same draw thinned per output column AND per input channel / row
+    (bisparse_kernel: the trainer's data gradient contracts over the output channels); biases and all four BN arrays stay random"""
     key = (n, channels, kind)
     if key not in _weights_cache:
         w = init_weights(n, seed=1000 + n + channels, channels=channels, randomize_all=True)
@@ -71,6 +117,10 @@ def network_weights(n, channels, kind):
             rs = np.random.RandomState(77 + n + channels)
             for i in KERNELS:
                 w[i] = sparse_columns(w[i], rs)
+        elif kind == "bisparse":
+            rs = np.random.RandomState(4177 + n + channels)
+            for i in KERNELS:
+                w[i] = bisparse_kernel(w[i], rs)
         else:
             assert kind == "dense", kind
         for a in w:
