@@ -91,6 +91,12 @@ int oz_rules_minimax(const uint64_t* black, const uint64_t* white, const int8_t*
  * OZ_ERR_ARG: max_empties outside 0..OZ_SOLVE_MAX_EMPTIES, a player that is not +1 / -1, discs off the n x n board or on one square twice. */
 int oz_rules_solve(const uint64_t* black, const uint64_t* white, const int8_t* player, int n, int count, int max_empties,
                    int32_t* values /* [count][64] */, uint64_t* bests /* [count] */, int32_t* value /* [count] */, uint8_t* solved /* [count] */);
+/* sign of S for the mover (after the pass where the mover has none): -1 / 0 / +1; positions above max_empties: solved 0, sign 0.
+ * The same solver under the root window (-1, +1): the root's own best tightens every subtree's window and nothing more starts once a win is
+ * found, so it costs a fraction of oz_rules_solve -- and says nothing about the moves.  What a search leaf needs (oz_mcts_set_solve_leaves).
+ * Same argument checks and errors as oz_rules_solve. */
+int oz_rules_solve_sign(const uint64_t* black, const uint64_t* white, const int8_t* player, int n, int count, int max_empties,
+                        int8_t* sign /* [count] */, uint8_t* solved /* [count] */);
 /* HIP-event timing of the kernel of every oz_rules_* batch call on the current device (default off: nothing is recorded); the read returns
  * the total since creation / the last reset and the number of launches (each may be NULL) */
 int oz_rules_profile(int enable);
@@ -317,6 +323,23 @@ int oz_mcts_use_wide_kernels(oz_mcts* m, int enable);
 /* out[0] game-steps run by the leaf-parallel kernels, out[1] descents discarded on a collision, out[2] leaves handed to the network */
 int oz_mcts_wide_stats(oz_mcts* m, int64_t* out3);
 
+/* ---- solved leaves: exact values for leaves with few empties (opt-in; 0 = off is the search above, launch for launch; the reference has none)
+ * In every step, after the evaluator has written the step's (pi, v) rows and the evaluation cache has taken them (the cache keeps the NETWORK's
+ * v: engines that share it may run without this option), a row whose board has at most max_empties empties gets v = (float)sign(S), S the
+ * exact value of the position for the side to move (oz_rules_solve_sign); pi stays the network's.  A DRAW IS 0.0f -- the search's own terminal
+ * rule, which gives a drawn final board to whichever side is channel 0 there, is not reproduced.  The value is backed up like any network value
+ * (its type follows q_mode).  Every distinct row is solved once per step: de-duplicated games share it as they share the network's.  Works at
+ * any leaves_per_step, with root noise, move sampling, the evaluation cache and every driver.
+ * OZ_SOLVE_LEAVES_MAX_EMPTIES is below OZ_SOLVE_MAX_EMPTIES on purpose: a step waits for its slowest row, and it may hold hundreds.
+ * OZ_ERR_ARG: max_empties outside 0 .. OZ_SOLVE_LEAVES_MAX_EMPTIES (the object stays as it was).  OZ_ERR_STATE: oz_mcts_select / oz_mcts_backup
+ * while the option is on (the host-evaluator split takes the caller's (pi, v) as they are). */
+#define OZ_SOLVE_LEAVES_MAX_EMPTIES 10
+int oz_mcts_set_solve_leaves(oz_mcts* m, int max_empties);        /* 0 = off (default) .. OZ_SOLVE_LEAVES_MAX_EMPTIES; takes effect at the next step */
+int oz_mcts_get_solve_leaves(oz_mcts* m, int* max_empties, int64_t* rows_solved /* since create */);      /* either may be NULL */
+/* HIP-event timing of the solving kernel (default off); the read returns the total and the launches since creation / the last reset */
+int oz_mcts_solve_leaves_profile(oz_mcts* m, int enable);
+int oz_mcts_solve_leaves_profile_read(oz_mcts* m, double* ms_total, int64_t* launches, int reset);
+
 /* ---- root noise: Dirichlet noise on the root prior, AlphaZero's exploration inside the search (opt-in; off, every result stays bit for bit)
  * P'(root, a) = (1 - eps) P(root, a) + eps eta_a, eta ~ Dir(alpha) over the root's legal moves, fresh for every searched move.
  * STORED PRIORS ARE NEVER MODIFIED: the node tables are transposition tables that persist across the moves of a game, so the noise is applied
@@ -443,6 +466,12 @@ int oz_selfplay_set_dedup(oz_selfplay* sp, int enable);
  * the stream once per round and are no longer asynchronous; every leaf goes to the network: oz_selfplay_config.dedup and .eval_cache have no
  * effect (records would be identical either way), leaves_evaluated == expansions. */
 int oz_selfplay_set_leaves_per_step(oz_selfplay* sp, int k);
+/* solved leaves of the engine's search (see oz_mcts_set_solve_leaves), for every driver; takes effect at the next step */
+int oz_selfplay_set_solve_leaves(oz_selfplay* sp, int max_empties);
+int oz_selfplay_get_solve_leaves(oz_selfplay* sp, int* max_empties, int64_t* rows_solved);
+/* HIP-event timing of the engine's solving kernel (oz_mcts_solve_leaves_profile / _read on the engine's search) */
+int oz_selfplay_solve_leaves_profile(oz_selfplay* sp, int enable);
+int oz_selfplay_solve_leaves_profile_read(oz_selfplay* sp, double* ms_total, int64_t* launches, int reset);
 /* self-play with root noise: every searched move of every game (oz_selfplay_stagger's included) draws Dir(alpha) at its root, keyed
  * (cfg.seed, game id, ply) -- in a kernel of its own behind the roots kernel of a lock-step round, inside the advance kernel of the
  * free-running driver (whose records stay exactly those of oz_selfplay_run).  Before the first driver call. */
@@ -550,6 +579,10 @@ int oz_arena_set_eval_cache(oz_arena* a, int enable);
 /* leaves_per_step of the BLACK (net_a) and WHITE (net_b) agent's search; before the first run.  The networks want max_batch >= num_games * k.
  * With k > 1 an agent's leaves bypass the evaluation cache. */
 int oz_arena_set_leaves_per_step(oz_arena* a, int k_black, int k_white);
+/* solved leaves of the BLACK (net_a) and WHITE (net_b) agent's search (see oz_mcts_set_solve_leaves); before the first run, like
+ * oz_arena_set_leaves_per_step.  The read returns the rows each search has solved so far. */
+int oz_arena_set_solve_leaves(oz_arena* a, int black, int white); /* per agent, before the first run, like oz_arena_set_leaves_per_step */
+int oz_arena_get_solve_leaves(oz_arena* a, int64_t* rows_black, int64_t* rows_white);
 /* HIP-event timing of the two agents' tree kernels on the launch stream, slots of oz_selfplay_profile (0 select 1 leaf compaction 2 evaluator = all
  * network launches 3 expand + backup 4 move), summed over both searches; the networks' own kernels: oz_net_profile on net_a / net_b */
 int oz_arena_profile(oz_arena* a, int enable);

@@ -33,6 +33,7 @@ TRAINER_WGRAD_NAMES = {0: "none", 1: "taps_f32", 2: "boards_f32", 3: "oct_h2", 4
 MINIMAX_EVAL_DISCS, MINIMAX_EVAL_WEIGHTED, MINIMAX_MAX_DEPTH, MINIMAX_NONE = 0, 1, 6, -2 ** 31    # OZ_MINIMAX_*
 MINIMAX_EVALS = {"discs": MINIMAX_EVAL_DISCS, "weighted": MINIMAX_EVAL_WEIGHTED}
 SOLVE_MAX_EMPTIES = 12                                                               # OZ_SOLVE_MAX_EMPTIES
+SOLVE_LEAVES_MAX_EMPTIES = 10                                                        # OZ_SOLVE_LEAVES_MAX_EMPTIES
 AGENT_RANDOM, AGENT_MINIMAX = 0, 1                                                   # oz_arena_set_opponent
 REPLAY_TARGET_ONEHOT, REPLAY_TARGET_VISITS = 0, 1                                    # oz_replay_append_*
 NET_KERNELS = ("input", "conv2", "conv3", "conv4", "fc1", "fc2", "heads")           # OZ_NET_KERNELS slots
@@ -95,6 +96,7 @@ SIGNATURES = {
     "oz_rules_play": [_u64p, _u64p, _i8p, _u8p, C.c_int, C.c_int, _u64p, _u64p, _i8p, _u8p],
     "oz_rules_minimax": [_u64p, _u64p, _i8p, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _u64p],      # agents.py:27-41
     "oz_rules_solve": [_u64p, _u64p, _i8p, C.c_int, C.c_int, C.c_int, _i32p, _u64p, _i32p, _u8p],
+    "oz_rules_solve_sign": [_u64p, _u64p, _i8p, C.c_int, C.c_int, C.c_int, _i8p, _u8p],
     "oz_rules_profile": [C.c_int], "oz_rules_profile_read": [_f64p, _i64p, C.c_int],
     "oz_selfplay_solve_records": [_vp, C.c_int64, C.c_int, C.POINTER(EndgameStats)],
     "oz_net_create": [C.POINTER(_vp), C.c_int, C.c_int, C.c_int],
@@ -133,6 +135,11 @@ SIGNATURES = {
     "oz_mcts_set_leaves_per_step": [_vp, C.c_int], "oz_mcts_get_leaves_per_step": [_vp, C.POINTER(C.c_int)],
     "oz_mcts_use_wide_kernels": [_vp, C.c_int], "oz_mcts_wide_stats": [_vp, _i64p],
     "oz_selfplay_set_leaves_per_step": [_vp, C.c_int], "oz_arena_set_leaves_per_step": [_vp, C.c_int, C.c_int],
+    "oz_mcts_set_solve_leaves": [_vp, C.c_int], "oz_mcts_get_solve_leaves": [_vp, C.POINTER(C.c_int), _i64p],
+    "oz_mcts_solve_leaves_profile": [_vp, C.c_int], "oz_mcts_solve_leaves_profile_read": [_vp, _f64p, _i64p, C.c_int],
+    "oz_selfplay_set_solve_leaves": [_vp, C.c_int], "oz_selfplay_get_solve_leaves": [_vp, C.POINTER(C.c_int), _i64p],
+    "oz_selfplay_solve_leaves_profile": [_vp, C.c_int], "oz_selfplay_solve_leaves_profile_read": [_vp, _f64p, _i64p, C.c_int],
+    "oz_arena_set_solve_leaves": [_vp, C.c_int, C.c_int], "oz_arena_get_solve_leaves": [_vp, _i64p, _i64p],
     "oz_mcts_set_root_noise": [_vp, C.c_double, _f64p, _u8p],
     "oz_mcts_sample_root_noise": [_vp, C.c_double, C.c_double, C.c_uint64, _u64p, _i32p],
     "oz_mcts_get_root_noise": [_vp, _f64p, _u8p, _f64p],
@@ -363,6 +370,25 @@ def check_solve_empties(empties, least=0, what="max_empties"):
     if isinstance(empties, bool) or not isinstance(empties, (int, np.integer)) or not least <= empties <= SOLVE_MAX_EMPTIES:
         raise ValueError(f"endgame solver: {what} must be a whole number in {least}..{SOLVE_MAX_EMPTIES} (got {empties!r})")
     return int(empties)
+
+
+def check_solve_leaves(solve_leaves, what="solve_leaves"):
+    """solve_leaves=E of the searches (oz_mcts_set_solve_leaves) -> int E; 0 is off.  ValueError for anything the library would refuse: a
+    whole number in 0..OZ_SOLVE_LEAVES_MAX_EMPTIES, which is below the solver's own bound (a search step waits for its slowest row)."""
+    if (isinstance(solve_leaves, bool) or not isinstance(solve_leaves, (int, np.integer))
+            or not 0 <= solve_leaves <= SOLVE_LEAVES_MAX_EMPTIES):
+        raise ValueError(f"{what} must be a whole number in 0..{SOLVE_LEAVES_MAX_EMPTIES} (got {solve_leaves!r})")
+    return int(solve_leaves)
+
+
+def check_solve_leaves_pair(solve_leaves):
+    """arena_batch(solve_leaves=E or (E_black, E_white)) -> (int, int)"""
+    if isinstance(solve_leaves, (tuple, list)):
+        if len(solve_leaves) != 2:
+            raise ValueError(f"solve_leaves must be E or (E_black, E_white) (got {solve_leaves!r})")
+        return check_solve_leaves(solve_leaves[0], "solve_leaves[black]"), check_solve_leaves(solve_leaves[1], "solve_leaves[white]")
+    e = check_solve_leaves(solve_leaves)
+    return e, e
 
 
 def check_endgame_targets(endgame_targets, alias_final_boards):

@@ -64,6 +64,21 @@ def rules_solve(black, white, player, n, max_empties=_lib.SOLVE_MAX_EMPTIES):
     return values, bests, value, solved
 
 
+def rules_solve_sign(black, white, player, n, max_empties=_lib.SOLVE_MAX_EMPTIES):
+    """oz_rules_solve_sign over a batch of positions: -> (sign int8 (count,) = -1 / 0 / +1, who wins under perfect play as the mover sees it;
+    solved uint8 (count,) = 0 where the position has more than max_empties empties and was left alone: sign 0).  The solver under the window
+    (-1, +1): much cheaper than rules_solve, and it says nothing about the moves.  What solve_leaves=E puts into a search's leaves."""
+    max_empties = _lib.check_solve_empties(max_empties)
+    black = np.ascontiguousarray(black, dtype=np.uint64).ravel()
+    white = np.ascontiguousarray(white, dtype=np.uint64).ravel()
+    player = np.ascontiguousarray(player, dtype=np.int8).ravel()
+    k = black.size
+    sign, solved = np.zeros(k, np.int8), np.zeros(k, np.uint8)
+    _lib.check(_lib.require_gpu().oz_rules_solve_sign(_lib.p_u64(black), _lib.p_u64(white), _lib.p_i8(player), n, k, max_empties,
+                                                      _lib.p_i8(sign), _lib.p_u8(solved)))
+    return sign, solved
+
+
 class MinimaxOthelloAgent(OthelloAgent):
     """Fixed-depth minimax on the device (oz_rules_minimax): what the reference's GreedyOthelloAgent (agents.py:27-41, dead code) was meant to
     be at depth=1, evaluation="discs", and harder by one integer.  One call for the game's position, then `random.choice` over the moves of
@@ -95,13 +110,15 @@ class NeuralNetworkOthelloAgent(OthelloAgent):
     the first valid action with the largest policy entry."""
 
     def __init__(self, game, neural_network, num_simulations, degree_exploration, temperature=0,
-                 q_mode=_lib.QMODE_F64, leaves_per_step=1):
+                 q_mode=_lib.QMODE_F64, leaves_per_step=1, solve_leaves=0):
+        solve_leaves = _lib.check_solve_leaves(solve_leaves)
         super().__init__(game)
         self.neural_network, self.num_simulations, self.temperature = neural_network, num_simulations, 0
         side = game.board_size
         # an agent searches on its own turns only: about half the plies
         self.mcts = OthelloMCTS(side, neural_network, degree_exploration, q_mode=q_mode,
-                                node_cap=num_simulations * (side * side // 2) + 64, leaves_per_step=leaves_per_step)
+                                node_cap=num_simulations * (side * side // 2) + 64, leaves_per_step=leaves_per_step,
+                                solve_leaves=solve_leaves)
 
     def play(self):
         game = self.game
@@ -131,7 +148,7 @@ def duel_between_agents(game, agent_1, agent_2):
 
 def arena_batch(net_a, net_b, board_size=8, num_games=512, num_simulations=800, degree_exploration=1.0, seed=0,
                 first_game_id=0, q_mode=_lib.QMODE_F64, node_cap=0, max_rounds=0, dedup=True, profile=False, eval_cache=False,
-                leaves_per_step=1, opponent=None):
+                leaves_per_step=1, opponent=None, solve_leaves=0):
     """num_games games of net_a (BLACK) vs net_b (WHITE), temperature 0, max-visit ties broken by the RNG_TIE
     stream keyed (seed, game id, ply).  One of the two may be None: RandomOthelloAgent plays that colour, or with
     opponent=("minimax", depth) / ("minimax", depth, "discs" | "weighted") the fixed-depth minimax (oz_arena_set_opponent; ties between its
@@ -144,7 +161,10 @@ def arena_batch(net_a, net_b, board_size=8, num_games=512, num_simulations=800, 
     networks evaluated: fewer than the expansions with dedup=True (the default), where a board several games reach in one step is evaluated once;
     tree_kernels = {slot: (ms, launches)} of both searches' tree kernels with profile=True, else None).
     leaves_per_step = k or (k_black, k_white): descents per game and network batch of the two agents' searches under virtual loss
-    (oz_arena_set_leaves_per_step); an agent's network needs max_batch >= num_games * its k."""
+    (oz_arena_set_leaves_per_step); an agent's network needs max_batch >= num_games * its k.
+    solve_leaves = E or (E_black, E_white): the agent's search takes the exact win / draw / loss of a leaf with at most E empties in place of
+    its network's value (oz_arena_set_solve_leaves; 0 = off); the result then carries rows_solved = (black, white)."""
+    eb_, ew_ = _lib.check_solve_leaves_pair(solve_leaves)
     kb, kw = (leaves_per_step, leaves_per_step) if np.isscalar(leaves_per_step) else leaves_per_step
     minimax = _lib.check_opponents(opponent, net_a is None, net_b is None)
     lib = _lib.require_gpu()
@@ -159,12 +179,19 @@ def arena_batch(net_a, net_b, board_size=8, num_games=512, num_simulations=800, 
             _lib.check(lib.oz_arena_set_eval_cache(h, 1))
         if not (np.isscalar(leaves_per_step) and leaves_per_step == 1):
             _lib.check(lib.oz_arena_set_leaves_per_step(h, int(kb), int(kw)))
+        if not (np.isscalar(solve_leaves) and solve_leaves == 0):
+            _lib.check(lib.oz_arena_set_solve_leaves(h, eb_, ew_))
         for side, spec in zip((1, -1), minimax):             # a colour without a network
             if spec is not None:
                 _lib.check(lib.oz_arena_set_opponent(h, side, _lib.AGENT_MINIMAX, spec[0], spec[1]))
         if profile:                                          # HIP events around the tree kernels of both searches (bench.py's config5 kernels[])
             _lib.check(lib.oz_arena_profile(h, 1))
         _lib.check(lib.oz_arena_run_rounds(h, int(max_rounds)))
+        rows = None
+        if not (np.isscalar(solve_leaves) and solve_leaves == 0):
+            rb, rw = C.c_int64(), C.c_int64()
+            _lib.check(lib.oz_arena_get_solve_leaves(h, C.byref(rb), C.byref(rw)))
+            rows = (rb.value, rw.value)
         tree = opp_kernel = None
         if profile and any(minimax):
             ms1, cnt1 = C.c_double(), C.c_int64()
@@ -188,4 +215,4 @@ def arena_batch(net_a, net_b, board_size=8, num_games=512, num_simulations=800, 
         lib.oz_arena_destroy(h)
     return dict(winner=winner, points=points, n_moves=nm, actions=acts, players=pls, final_black=fb, final_white=fw,
                 stats_black=sa, stats_white=sb, leaves_evaluated=ea.value + eb.value, tree_kernels=tree,
-                **({"opponent_kernel": opp_kernel} if any(minimax) else {}))
+                **({"opponent_kernel": opp_kernel} if any(minimax) else {}), **({"rows_solved": rows} if rows is not None else {}))

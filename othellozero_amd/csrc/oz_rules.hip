@@ -313,6 +313,44 @@ OZ_API int oz_rules_solve(const uint64_t* black, const uint64_t* white, const in
         });
 }
 
+// the sign of S only: sv_root under the root window (-1, +1) (oz_solve.h), what a search leaf needs (k_solve_leaves, oz_search.hip)
+__global__ __launch_bounds__(64) void k_solve_sign(const uint64_t* __restrict__ black, const uint64_t* __restrict__ white, const int8_t* __restrict__ player,
+                                                   uint64_t valid, uint64_t corners, int n2, int max_empties, int8_t* __restrict__ sign,
+                                                   uint8_t* __restrict__ solved) {
+    __shared__ SolveLdsW L;
+    const int i = blockIdx.x, lane = threadIdx.x;
+    const uint64_t b = black[i], w = white[i];
+    const int empties = n2 - oz_popc(b | w);
+    int sg = 0;
+    if (empties <= max_empties) sg = player[i] == 1 ? sv_sign(L, valid, corners, lane, b, w, empties) : sv_sign(L, valid, corners, lane, w, b, empties);
+    if (lane == 0) { sign[i] = (int8_t)sg; solved[i] = empties <= max_empties ? 1 : 0; }
+}
+
+OZ_API int oz_rules_solve_sign(const uint64_t* black, const uint64_t* white, const int8_t* player, int n, int count, int max_empties,
+                               int8_t* sign, uint8_t* solved) {
+    if (int rc = check_n(n)) return rc;
+    OZ_REQUIRE(max_empties >= 0 && max_empties <= OZ_SOLVE_MAX_EMPTIES, "oz_rules_solve_sign: max_empties %d outside 0..%d", max_empties, OZ_SOLVE_MAX_EMPTIES);
+    if (count <= 0) return OZ_OK;
+    OZ_REQUIRE(black && white && player, "null argument");
+    const uint64_t valid = oz_valid_mask(n);
+    for (int i = 0; i < count; ++i) {
+        OZ_REQUIRE(player[i] == 1 || player[i] == -1, "player must be +1 or -1");
+        OZ_REQUIRE(((black[i] | white[i]) & ~valid) == 0 && (black[i] & white[i]) == 0, "oz_rules_solve_sign: position %d is no %dx%d board", i, n, n);
+    }
+    const size_t c8 = 8ull * count, c1 = pad8(count);
+    // output image: sign | solved
+    return rules_call(2 * c8 + c1, 2 * c1,
+        [&](unsigned char* h) { memcpy(h, black, c8); memcpy(h + c8, white, c8); memcpy(h + 2 * c8, player, count); },
+        [&](unsigned char* di, unsigned char* dout, hipStream_t s) {
+            hipLaunchKernelGGL(k_solve_sign, dim3(count), dim3(64), 0, s, (const uint64_t*)di, (const uint64_t*)(di + c8), (const int8_t*)(di + 2 * c8),
+                               valid, oz_solve_corners(n), n * n, max_empties, (int8_t*)dout, (uint8_t*)(dout + c1));
+        },
+        [&](const unsigned char* h) {
+            if (sign) memcpy(sign, h, count);
+            if (solved) memcpy(solved, h + c1, count);
+        });
+}
+
 // ---------------------------------------------------------------- symmetries (K8)
 // (oz_sym_src, the source cell of an output cell under symmetry t, lives in oz_common.h: the replay buffer's append kernel shares it)
 

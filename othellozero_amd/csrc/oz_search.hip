@@ -590,6 +590,48 @@ __global__ __launch_bounds__(1024) void k_compact(MctsDev t) {
     }
 }
 
+// ---------------------------------------------------------------- solved leaves (opt-in: oz_mcts_set_solve_leaves; the reference's search has none)
+// After the evaluator (and after k_cache_insert: the network's cache keeps the NETWORK's v, other engines share it), before expand + backup: a
+// row of this step whose board has at most E empties gets v = (float)sign(S), S its exact value for the side to move (oz_solve.h under the root
+// window (-1, +1)); pi stays the network's.  A draw is 0.0f.  One wave per row that some game reads this step: blocks [0, cap) are the network's
+// rows (the board is the batch's), blocks cap + g (launched where the search looks leaves up in the evaluation cache) the games, for the
+// rows G-1-h of the cache hits.  A hit row's board is the leaf of a game that reads it -- not the key of cache entry hit_entry[h], which
+// k_cache_insert may have given to another position of this very batch by now -- and the first game to put the launch's stamp on the row
+// solves it, so a row shared by de-duplicated games is solved once.  A search leaf always has a legal move (descend_one ends on a finished
+// board as TERMINAL), sv_sign covers the other cases all the same.
+struct SolveLeavesDev {
+    int E, cap, hits;                                     // rows with <= E empties; the network's rows are [0, min(cap, *batch_count)); hits: the game blocks are there
+    uint64_t corners;
+    unsigned stamp;                                       // of this launch, never 0
+    unsigned* claim;                                      // [G] the stamp of the launch that solved the row last
+    unsigned long long* rows;                             // rows solved so far
+};
+__global__ __launch_bounds__(64) void k_solve_leaves(MctsDev t, SolveLeavesDev sl) {
+    __shared__ SolveLdsW L;
+    const int lane = threadIdx.x;
+    int row = blockIdx.x;
+    uint64_t own, opp;
+    if (row < sl.cap) {
+        if (row >= *t.batch_count) return;
+        own = t.batch_own[row]; opp = t.batch_opp[row];
+    } else {
+        const int g = row - sl.cap;
+        if (g >= t.G || t.leaf_status[g] != OZ_LEAF_EVAL) return;
+        row = t.leaf_slot[g];
+        if (row < t.G - *t.hit_count || row >= t.G) return;              // the network's row: solved above
+        own = t.leaf_own[g]; opp = t.leaf_opp[g];
+    }
+    const int empties = t.n2 - oz_popc(own | opp);
+    if (empties > sl.E) return;
+    if (blockIdx.x >= (unsigned)sl.cap) {
+        int mine = 0;
+        if (lane == 0) mine = atomicExch(&sl.claim[row], sl.stamp) != sl.stamp;
+        if (!__shfl(mine, 0, 64)) return;
+    }
+    const int sg = sv_sign(L, t.valid, sl.corners, lane, own, opp, empties);
+    if (lane == 0) { t.v[row] = (float)sg; atomicAdd(sl.rows, 1ULL); }
+}
+
 // ---------------------------------------------------------------- K5 + K6: expand and backup
 __device__ __forceinline__ void q_update(const MctsDev& t, OzEdge* e, double val, int vt) {
     const uint32_t nt = e->n_tag;
@@ -952,6 +994,12 @@ struct oz_mcts {
     // root noise: true from the first arming on (d.noise_eta / d.noise_armed are then allocated): the descents run on the *_n kernels
     bool noise_ever = false;
     uint64_t* noise_ids = nullptr; int32_t* noise_plies = nullptr;      // staging of the keys of oz_mcts_sample_root_noise / oz_mcts_sample_moves, [G] each
+    // solved leaves (oz_mcts_set_solve_leaves): 0 = off, nothing allocated and nothing launched
+    int solve_leaves = 0;
+    unsigned solve_stamp = 0;
+    unsigned* solve_claim = nullptr; unsigned long long* solve_rows = nullptr;
+    bool solve_profile = false;      // oz_mcts_solve_leaves_profile: HIP events around k_solve_leaves
+    OzTimer solve_timer{1};
 
     template <typename T> int alloc(T** p, size_t count) {
         OZ_HIP(hipMalloc((void**)p, sizeof(T) * (count ? count : 1)));
@@ -1045,6 +1093,7 @@ static void mcts_destroy(oz_mcts* m) {
     hipSetDevice(m->device);
     hipStreamSynchronize(m->stream);
     m->timer.destroy();
+    m->solve_timer.destroy();
     for (void* p : m->allocs) hipFree(p);
     hipStreamDestroy(m->stream);
     delete m;
@@ -1068,6 +1117,19 @@ static int check_error_flag(oz_mcts* m) {
 }
 
 enum { TS_SELECT = 0, TS_COMPACT = 1, TS_NN = 2, TS_BACKUP = 3, TS_MOVE = 4 };
+// the step's solved rows (k_solve_leaves): after the evaluator of EITHER kind of step has written the rows [0, cap) (and the cache has taken
+// them), before their expand + backup.  hits: the step may have rows served from the evaluation cache.  Off (the default), nothing is launched.
+static void solve_leaves_async(oz_mcts* m, int cap, bool hits) {
+    if (m->solve_leaves <= 0) return;
+    const MctsDev& d = m->d;
+    m->solve_stamp += 1;
+    if (m->solve_stamp == 0) m->solve_stamp = 1;             // 0 = "never solved"
+    const SolveLeavesDev sl{m->solve_leaves, cap, hits ? 1 : 0, oz_solve_corners(d.n), m->solve_stamp, m->solve_claim, m->solve_rows};
+    const long long ti = m->solve_profile ? m->solve_timer.begin(0, m->stream) : -1;
+    hipLaunchKernelGGL(k_solve_leaves, dim3((unsigned)(cap + (hits ? d.G : 0))), dim3(64), 0, m->stream, d, sl);
+    m->solve_timer.end(ti, m->stream);
+    if (m->solve_profile && m->solve_timer.backlog() > 4096) m->solve_timer.drain();
+}
 // the evaluator's part of a batch: the rows of the leaves k_compact found in the network's evaluation cache (if the search uses one),
 // the network on the compacted batch (launched for up to max_count leaves), the evaluated positions into the cache
 static int eval_batch_async(oz_mcts* m, oz_net* net, int max_count, bool timed) {
@@ -1083,6 +1145,7 @@ static int eval_batch_async(oz_mcts* m, oz_net* net, int max_count, bool timed) 
         d.batch_stamp = m->batch_no;
         hipLaunchKernelGGL(k_cache_insert, dim3((unsigned)((max_count + 3) / 4)), dim3(256), 0, s, d);
     }
+    solve_leaves_async(m, max_count, d.ec.buckets != 0);
     return OZ_OK;
 }
 
@@ -1161,6 +1224,7 @@ static int mcts_wide_steps(oz_mcts* m, oz_net* net, int nsims, int max_games, bo
             const long long i = (time_eval || all) ? m->timer.begin(TS_NN, s) : -1;
             if (int rc = oz_net_forward_device(net, d.batch_own, d.batch_opp, d.batch_count, cap, d.pi, d.v, s)) { m->timer.cancel(i); return rc; }
             m->timer.end(i, s);
+            solve_leaves_async(m, cap, false);              // (no evaluation cache here: every leaf has a row of its own)
         }
         timed(m, TS_BACKUP, all, [&] { hipLaunchKernelGGL(k_wide_expand_backup, dim3(d.G), dim3(64), 0, s, d, w); });
         OZ_HIP(hipGetLastError());
@@ -1272,6 +1336,73 @@ OZ_API int oz_mcts_simulate(oz_mcts* m, oz_net* net, int nsims) {
 
 #define OZ_REFUSE_WIDE(m, fn) \
     do { if ((m)->leaves_per_step > 1) { oz_set_error(fn ": the host-evaluator split runs one leaf per game and step (leaves_per_step is %d: set it to 1)", (m)->leaves_per_step); return OZ_ERR_STATE; } } while (0)
+
+// ---- solved leaves: the option
+static int solve_leaves_check(const char* fn, int e) {
+    OZ_REQUIRE(e >= 0 && e <= OZ_SOLVE_LEAVES_MAX_EMPTIES, "%s: max_empties %d outside 0 .. %d", fn, e, OZ_SOLVE_LEAVES_MAX_EMPTIES);
+    return OZ_OK;
+}
+static int solve_leaves_set_locked(oz_mcts* m, int e) {
+    if (e > 0 && !m->solve_rows) {
+        hipSetDevice(m->device);
+        const size_t held = m->allocs.size();
+        int rc = m->alloc(&m->solve_claim, (size_t)m->d.G);
+        if (!rc) rc = m->alloc(&m->solve_rows, 1);
+        if (rc) {
+            for (size_t i = held; i < m->allocs.size(); ++i) hipFree(m->allocs[i]);
+            m->allocs.resize(held);
+            m->solve_claim = nullptr; m->solve_rows = nullptr;
+            return rc;
+        }
+        OZ_HIP(hipMemsetAsync(m->solve_claim, 0, sizeof(unsigned) * (size_t)m->d.G, m->stream));
+        OZ_HIP(hipMemsetAsync(m->solve_rows, 0, sizeof(unsigned long long), m->stream));
+    }
+    m->solve_leaves = e;
+    return OZ_OK;
+}
+static int solve_leaves_rows_locked(oz_mcts* m, int64_t* rows) {
+    unsigned long long r = 0;
+    if (m->solve_rows) {
+        hipSetDevice(m->device);
+        OZ_HIP(hipMemcpyAsync(&r, m->solve_rows, sizeof r, hipMemcpyDeviceToHost, m->stream));
+        OZ_HIP(hipStreamSynchronize(m->stream));
+    }
+    *rows = (int64_t)r;
+    return OZ_OK;
+}
+OZ_API int oz_mcts_set_solve_leaves(oz_mcts* m, int max_empties) {
+    OZ_REQUIRE(m, "null mcts");
+    if (int rc = solve_leaves_check("oz_mcts_set_solve_leaves", max_empties)) return rc;
+    std::lock_guard<std::mutex> lk(m->mu);
+    return solve_leaves_set_locked(m, max_empties);
+}
+OZ_API int oz_mcts_get_solve_leaves(oz_mcts* m, int* max_empties, int64_t* rows_solved) {
+    OZ_REQUIRE(m, "null mcts");
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (max_empties) *max_empties = m->solve_leaves;
+    if (rows_solved) return solve_leaves_rows_locked(m, rows_solved);
+    return OZ_OK;
+}
+// HIP-event timing of k_solve_leaves (tools/solve_leaves_bench.py); off, nothing is recorded
+OZ_API int oz_mcts_solve_leaves_profile(oz_mcts* m, int enable) {
+    OZ_REQUIRE(m, "null mcts");
+    std::lock_guard<std::mutex> lk(m->mu);
+    m->solve_profile = enable != 0;
+    return OZ_OK;
+}
+OZ_API int oz_mcts_solve_leaves_profile_read(oz_mcts* m, double* ms_total, int64_t* launches, int reset) {
+    OZ_REQUIRE(m, "null mcts");
+    std::lock_guard<std::mutex> lk(m->mu);
+    hipSetDevice(m->device);
+    if (m->solve_timer.collect() != OZ_OK) { oz_set_error("HIP event timing failed"); return OZ_ERR_HIP; }
+    if (ms_total) *ms_total = m->solve_timer.ms[0];
+    if (launches) *launches = m->solve_timer.count[0];
+    if (reset) m->solve_timer.reset();
+    return OZ_OK;
+}
+
+#define OZ_REFUSE_SOLVED(m, fn) \
+    do { if ((m)->solve_leaves > 0) { oz_set_error(fn ": the host-evaluator split takes the caller's (pi, v) as they are (solve_leaves is %d: set it to 0)", (m)->solve_leaves); return OZ_ERR_STATE; } } while (0)
 
 OZ_API int oz_mcts_set_leaves_per_step(oz_mcts* m, int k) {
     OZ_REQUIRE(m, "null mcts");
@@ -1428,6 +1559,7 @@ OZ_API int oz_mcts_select(oz_mcts* m) {
     OZ_REQUIRE(m, "null mcts");
     std::lock_guard<std::mutex> lk(m->mu);
     OZ_REFUSE_WIDE(m, "oz_mcts_select");
+    OZ_REFUSE_SOLVED(m, "oz_mcts_select");
     hipSetDevice(m->device);
     hipLaunchKernelGGL(m->noise_ever ? k_select_n : k_select, dim3(m->d.G), dim3(64), 0, m->stream, m->d);
     OZ_HIP(hipGetLastError());
@@ -1453,6 +1585,7 @@ OZ_API int oz_mcts_backup(oz_mcts* m, const float* pi, const float* v) {
     OZ_REQUIRE(m && pi && v, "null argument");
     std::lock_guard<std::mutex> lk(m->mu);
     OZ_REFUSE_WIDE(m, "oz_mcts_backup");
+    OZ_REFUSE_SOLVED(m, "oz_mcts_backup");
     if (!m->selected) { oz_set_error("oz_mcts_backup: call oz_mcts_select first"); return OZ_ERR_STATE; }
     hipSetDevice(m->device);
     const int G = m->d.G;
@@ -2152,6 +2285,32 @@ OZ_API int oz_selfplay_set_leaves_per_step(oz_selfplay* sp, int k) {
     return wide_set_k(sp->m, k);
 }
 
+// solved leaves for every search of the engine (lock-step rounds at any leaves_per_step, oz_selfplay_stagger, the free-running driver); takes
+// effect at the next step
+OZ_API int oz_selfplay_set_solve_leaves(oz_selfplay* sp, int max_empties) {
+    OZ_REQUIRE(sp, "null selfplay");
+    if (int rc = solve_leaves_check("oz_selfplay_set_solve_leaves", max_empties)) return rc;
+    std::lock_guard<std::mutex> lk(sp->mu);
+    std::lock_guard<std::mutex> lkm(sp->m->mu);
+    return solve_leaves_set_locked(sp->m, max_empties);
+}
+OZ_API int oz_selfplay_get_solve_leaves(oz_selfplay* sp, int* max_empties, int64_t* rows_solved) {
+    OZ_REQUIRE(sp, "null selfplay");
+    std::lock_guard<std::mutex> lk(sp->mu);
+    return oz_mcts_get_solve_leaves(sp->m, max_empties, rows_solved);
+}
+// HIP-event timing of the engine's k_solve_leaves launches (oz_mcts_solve_leaves_profile on the engine's search)
+OZ_API int oz_selfplay_solve_leaves_profile(oz_selfplay* sp, int enable) {
+    OZ_REQUIRE(sp, "null selfplay");
+    std::lock_guard<std::mutex> lk(sp->mu);
+    return oz_mcts_solve_leaves_profile(sp->m, enable);
+}
+OZ_API int oz_selfplay_solve_leaves_profile_read(oz_selfplay* sp, double* ms_total, int64_t* launches, int reset) {
+    OZ_REQUIRE(sp, "null selfplay");
+    std::lock_guard<std::mutex> lk(sp->mu);
+    return oz_mcts_solve_leaves_profile_read(sp->m, ms_total, launches, reset);
+}
+
 // root noise for every searched move of the engine (the lock-step rounds, oz_selfplay_stagger's included, and the free-running driver); before
 // the first driver call
 OZ_API int oz_selfplay_set_root_noise(oz_selfplay* sp, double alpha, double eps) {
@@ -2607,6 +2766,23 @@ OZ_API int oz_arena_set_leaves_per_step(oz_arena* a, int k_black, int k_white) {
     hipSetDevice(a->games.m->device);
     if (int rc = wide_set_k(a->games.m, k_black)) return rc;
     return wide_set_k(a->mb, k_white);
+}
+
+// solved leaves per agent (black for net_a's search, white for net_b's; a colour without a network searches nothing); before the first run
+OZ_API int oz_arena_set_solve_leaves(oz_arena* a, int black, int white) {
+    OZ_REQUIRE(a, "null arena");
+    if (int rc = solve_leaves_check("oz_arena_set_solve_leaves", black)) return rc;
+    if (int rc = solve_leaves_check("oz_arena_set_solve_leaves", white)) return rc;
+    std::lock_guard<std::mutex> lk(a->mu);
+    if (a->started) { oz_set_error("oz_arena_set_solve_leaves: the arena has run already (set it before the first run)"); return OZ_ERR_STATE; }
+    if (int rc = solve_leaves_set_locked(a->games.m, black)) return rc;
+    return solve_leaves_set_locked(a->mb, white);
+}
+OZ_API int oz_arena_get_solve_leaves(oz_arena* a, int64_t* rows_black, int64_t* rows_white) {
+    OZ_REQUIRE(a && rows_black && rows_white, "null argument");
+    std::lock_guard<std::mutex> lk(a->mu);
+    if (int rc = solve_leaves_rows_locked(a->games.m, rows_black)) return rc;
+    return solve_leaves_rows_locked(a->mb, rows_white);
 }
 
 // the mover of a colour without a network (default OZ_AGENT_RANDOM = RandomOthelloAgent); before the first run

@@ -17,6 +17,16 @@
 // on which lane finished when.  A node whose window is already empty is skipped (its value cannot matter to its parent any more).
 // No lane waits for another: every loop is bounded by the tree, the only synchronisation is the block barrier between expansion levels.
 //
+// Root window (compile time: sv_root<RA, RB>, the default is the full window above and compiles to what it was).  Where only the fail-hard value of
+// the ROOT in (RA, RB) is wanted -- (-1, +1) gives sign(S), what a search leaf needs -- the root is one more ancestor: its `best` (L.root, in
+// SolveLdsW) starts at RA, a completed root child raises it by the same LDS max, and the ancestor walk of an item ends there: an item of the root's
+// orientation gets alpha >= root best and beta <= RB, one of the other orientation beta <= -root best and alpha >= -RB.  Once root best >= RB
+// every window that is read is empty and nothing more starts.  The argument above carries over unchanged: the root's best only grows, so the
+// bound an item read is never tighter than the final one and its fail-hard result stays valid under it; a result at or beyond the bound it was
+// cut at reaches the root as a value <= root best (no effect on the max) or >= RB (clamped to RB at the end); and the root's value is a max,
+// order-free.  The output min(root best, RB) therefore does not depend on which lane finished when -- only the amount of work does.  The per-move
+// values and *bests of a windowed root are NOT exact and are not returned.
+//
 // Inside an item: iterative fail-hard alpha-beta, the lane's frame stack in LDS (20 bytes a frame -- the moves left, the discs the move changed, so
 // that the parent's board is the child's with the move undone -- in lane-contiguous arrays: consecutive lanes hit consecutive banks, no scratch),
 // corners first, the last empty counted by its flips without a frame or a legal-move flood.
@@ -43,6 +53,7 @@ struct SolveLds {
     int link[OZ_SV_NODES];
     int next;                                             // the item counter
 };
+struct SolveLdsW : SolveLds { int root; };                // a windowed root's best (sv_root<RA, RB>); the full-window kernels keep SolveLds
 
 // one empty square x, `own` to move: exact disc difference for own at the end (a square is playable iff it flips something)
 __device__ __forceinline__ int sv_last1(uint64_t own, uint64_t opp, int x) {
@@ -97,12 +108,16 @@ __device__ __forceinline__ int sv_search(SolveLds& L, uint64_t valid, uint64_t c
     }
 }
 
-// node i is complete: its best goes to its parent; whoever completes the parent's last child carries on from there
-__device__ __forceinline__ void sv_complete(SolveLds& L, int i) {
+// node i is complete: its best goes to its parent; whoever completes the parent's last child carries on from there.  WIN: a root child's goes
+// to the root's best
+template <bool WIN, class LDS> __device__ __forceinline__ void sv_complete(LDS& L, int i) {
     for (;;) {
         const int lk = L.link[i], p = (lk >> 2) - 1;
-        if (p < 0) return;
         const int v = L.best[i];
+        if (p < 0) {
+            if constexpr (WIN) if (v != -OZ_SV_INF) atomicMax(&L.root, (lk & 1) ? v : -v);
+            return;
+        }
         if (v != -OZ_SV_INF) atomicMax(&L.best[p], (lk & 1) ? v : -v);      // (-inf: every child was skipped, the node has nothing to say)
         __threadfence_block();
         if (atomicSub(&L.pend[p], 1) != 1) return;
@@ -114,12 +129,20 @@ __device__ __forceinline__ void sv_complete(SolveLds& L, int i) {
 // One wave (a block of 64 lanes) on one position whose mover (own) has the legal moves `legal` (not empty) and `empties` <= OZ_SOLVE_MAX_EMPTIES
 // empty squares: -> the exact value of the move on square `lane` (OZ_MINIMAX_NONE off the legal set); *bests = the moves of maximal value,
 // *value = that maximum = S of the position, the same in every lane.  Every lane of the block must call it (block-wide barriers inside).
-__device__ __forceinline__ int sv_root(SolveLds& L, uint64_t valid, uint64_t corners, int lane, uint64_t own, uint64_t opp, uint64_t legal,
+// With a root window (RA, RB) inside (-inf, +inf) (LDS = SolveLdsW): *value = the fail-hard value of the position in that window, RA <= *value <=
+// RB, the same in every lane; *bests = 0 and the return value is OZ_MINIMAX_NONE (see the header: the moves' values are not exact then).
+template <int RA = -OZ_SV_INF, int RB = OZ_SV_INF, class LDS = SolveLds>
+__device__ __forceinline__ int sv_root(LDS& L, uint64_t valid, uint64_t corners, int lane, uint64_t own, uint64_t opp, uint64_t legal,
                                        int empties, uint64_t* bests, int* value) {
+    constexpr bool WIN = RA > -OZ_SV_INF || RB < OZ_SV_INF;
+    static_assert(RA < RB, "an empty root window");
     const bool is_root = (legal >> lane) & 1;
     const int idx = oz_popc(legal & ((1ULL << lane) - 1ULL));
     __syncthreads();                                        // (a caller may run several positions through one SolveLds)
-    if (lane == 0) L.next = 0;
+    if (lane == 0) {
+        L.next = 0;
+        if constexpr (WIN) L.root = RA;
+    }
     if (is_root) {
         uint64_t co = own, cp = opp, m;
         oz_apply(co, cp, lane);
@@ -131,6 +154,10 @@ __device__ __forceinline__ int sv_root(SolveLds& L, uint64_t valid, uint64_t cor
         L.link[idx] = s > 0 ? 1 : s == 0 ? 3 : 0;
     }
     __syncthreads();
+    if constexpr (WIN) {                                    // a root child that ends the game is complete already
+        if (is_root && (L.link[idx] & 2)) atomicMax(&L.root, L.best[idx]);
+        __syncthreads();
+    }
     int lo = 0, hi = oz_popc(legal), e = empties - 1;       // the current level [lo, hi), its positions' empties
     while (e > OZ_SV_MIN_EMPTIES && hi - lo < OZ_SV_ITEMS) {
         int total = 0;
@@ -171,7 +198,7 @@ __device__ __forceinline__ int sv_root(SolveLds& L, uint64_t valid, uint64_t cor
         }
         __syncthreads();
         for (int c0 = lo; c0 < hi; c0 += 64)                // a node all of whose children are finished boards is complete already
-            if (c0 + lane < hi && !(L.link[c0 + lane] & 2) && L.pend[c0 + lane] == 0) sv_complete(L, c0 + lane);
+            if (c0 + lane < hi && !(L.link[c0 + lane] & 2) && L.pend[c0 + lane] == 0) sv_complete<WIN>(L, c0 + lane);
         __syncthreads();
         lo = hi; hi = base; --e;
     }
@@ -188,14 +215,25 @@ __device__ __forceinline__ int sv_root(SolveLds& L, uint64_t valid, uint64_t cor
             lk = L.link[p];
             same = same == (bool)(lk & 1);
         }
+        if constexpr (WIN) {                                // ... and ends at the root (`same`: the root's viewpoint equals the item's)
+            const int b = L.root;
+            if (same) { alpha = b > alpha ? b : alpha; beta = RB < beta ? RB : beta; }
+            else { beta = -b < beta ? -b : beta; alpha = -RB > alpha ? -RB : alpha; }
+        }
         if (alpha < beta) {
             const uint64_t io = L.n_own[i], ip = L.n_opp[i];
             L.best[i] = sv_search(L, valid, corners, lane, io, ip, oz_legal(io, ip, valid), e, alpha, beta);
         }
         __threadfence_block();
-        sv_complete(L, i);
+        sv_complete<WIN>(L, i);
     }
     __syncthreads();
+    if constexpr (WIN) {
+        const int b = L.root;
+        *bests = 0;
+        *value = b < RB ? b : RB;
+        return OZ_MINIMAX_NONE;
+    }
     int v = OZ_MINIMAX_NONE;
     if (is_root) {
         const int b = L.best[idx];
@@ -231,3 +269,16 @@ __device__ __forceinline__ int sv_position(SolveLds& L, uint64_t valid, uint64_t
 
 // the four corners of the n x n board
 inline uint64_t oz_solve_corners(int n) { return 1ULL | 1ULL << (n - 1) | 1ULL << (8 * (n - 1)) | 1ULL << (8 * (n - 1) + n - 1); }
+
+// sign of S for `own` to move (after the pass where own has no move): -1 / 0 / +1, the same in every lane.  The root window (-1, +1) is symmetric,
+// so the passed position's sign is minus the opponent's.  Every lane of the block must call it.
+__device__ __forceinline__ int sv_sign(SolveLdsW& L, uint64_t valid, uint64_t corners, int lane, uint64_t own, uint64_t opp, int empties) {
+    uint64_t b;
+    int v;
+    const uint64_t legal = oz_legal(own, opp, valid);
+    if (legal) { sv_root<-1, 1>(L, valid, corners, lane, own, opp, legal, empties, &b, &v); return v; }
+    const uint64_t theirs = oz_legal(opp, own, valid);
+    if (theirs == 0) { const int d = oz_popc(own) - oz_popc(opp); return (d > 0) - (d < 0); }
+    sv_root<-1, 1>(L, valid, corners, lane, opp, own, theirs, empties, &b, &v);
+    return -v;
+}

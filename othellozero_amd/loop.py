@@ -135,21 +135,23 @@ def evaluate_against_random(board_size, neural_network, games, num_simulations, 
 
 
 def evaluate_against_random_batch(board_size, neural_network, games, num_simulations, degree_exploration, seed=0, leaves_per_step=1,
-                                  opponent=None):
+                                  opponent=None, solve_leaves=0):
     """The same evaluation as `evaluate_against_random` played in lock step on the GPU (agents.arena_batch with a random
     mover): the network takes BLACK in the first games // 2 + games % 2 games and WHITE in the rest (the reference draws the
     colours with random.shuffle; the split here is fixed).  opponent: arena_batch's (None / "random", or ("minimax", depth[, evaluation])).
+    solve_leaves=E > 0: the network's search takes exact values for leaves with at most E empties (arena_batch).
     -> dict(wins, black_wins, black_games, white_wins, white_games)"""
     _lib.check_opponent(opponent)
+    solve_leaves = _lib.check_solve_leaves(solve_leaves)
     as_black, as_white = games // 2 + games % 2, games // 2
     r = dict(wins=0, black_wins=0, black_games=0, white_wins=0, white_games=0)
     if as_black:
         res = arena_batch(neural_network, None, board_size, as_black, num_simulations, degree_exploration, seed=seed,
-                          leaves_per_step=leaves_per_step, opponent=opponent)
+                          leaves_per_step=leaves_per_step, opponent=opponent, **({"solve_leaves": solve_leaves} if solve_leaves else {}))
         r["black_wins"] = int((res["winner"] == 1).sum())
     if as_white:
         res = arena_batch(None, neural_network, board_size, as_white, num_simulations, degree_exploration, seed=seed, first_game_id=as_black,
-                          leaves_per_step=leaves_per_step, opponent=opponent)
+                          leaves_per_step=leaves_per_step, opponent=opponent, **({"solve_leaves": solve_leaves} if solve_leaves else {}))
         r["white_wins"] = int((res["winner"] == -1).sum())
         r["black_games"] = as_white - r["white_wins"]              # games BLACK (the random agent) won
     r["white_games"] = r["white_wins"] + (as_black - r["black_wins"])
@@ -163,44 +165,50 @@ def evaluate_against_opponent(board_size, neural_network, games, num_simulations
     return evaluate_against_random(board_size, neural_network, games, num_simulations, degree_exploration, label=label, opponent=opponent)
 
 
-def evaluate_against_opponent_batch(board_size, neural_network, games, num_simulations, degree_exploration, opponent, seed=0, leaves_per_step=1):
+def evaluate_against_opponent_batch(board_size, neural_network, games, num_simulations, degree_exploration, opponent, seed=0, leaves_per_step=1,
+                                    solve_leaves=0):
     """`evaluate_against_random_batch` under the name that says what it does when the opponent is not the random agent"""
+    solve_leaves = _lib.check_solve_leaves(solve_leaves)
     return evaluate_against_random_batch(board_size, neural_network, games, num_simulations, degree_exploration, seed=seed,
-                                         leaves_per_step=leaves_per_step, opponent=opponent)
+                                         leaves_per_step=leaves_per_step, opponent=opponent, **({"solve_leaves": solve_leaves} if solve_leaves else {}))
 
 
 def self_play_match(board_size, neural_network, old_neural_network, total_games, num_simulations, degree_exploration, seed=0,
-                    leaves_per_step=1):
+                    leaves_per_step=1, solve_leaves=0):
     """main.py:110-134: total_games // 2 games with the new network as BLACK, the rest with it as WHITE.
-    -> number of games the new network won (a drawn game goes to BLACK, like get_winning_player)."""
+    -> number of games the new network won (a drawn game goes to BLACK, like get_winning_player).
+    solve_leaves=E > 0: both networks' searches take exact values for leaves with at most E empties (arena_batch)."""
+    solve_leaves = _lib.check_solve_leaves(solve_leaves)
     as_black, as_white = total_games // 2, total_games // 2 + total_games % 2
     wins = 0
     if as_black:
         res = arena_batch(neural_network, old_neural_network, board_size, as_black, num_simulations, degree_exploration, seed=seed,
-                          leaves_per_step=leaves_per_step)
+                          leaves_per_step=leaves_per_step, **({"solve_leaves": solve_leaves} if solve_leaves else {}))
         wins += int((res["winner"] == 1).sum())
     if as_white:
         res = arena_batch(old_neural_network, neural_network, board_size, as_white, num_simulations, degree_exploration,
-                          seed=seed, first_game_id=as_black, leaves_per_step=leaves_per_step)
+                          seed=seed, first_game_id=as_black, leaves_per_step=leaves_per_step, **({"solve_leaves": solve_leaves} if solve_leaves else {}))
         wins += int((res["winner"] == -1).sum())
     return wins
 
 
 def _selfplay_into_replay(replay, neural_network, board_size, num_episodes, num_simulations, degree_exploration, temperature, e_greedy, seed,
                           first_game_id, q_mode, visits, leaves_per_step, root_noise, sample_moves, alias_final_boards, policy_target,
-                          target_temperature, endgame_targets=0):
+                          target_temperature, endgame_targets=0, solve_leaves=0):
     """one iteration's games on the engine selfplay_batch would create, played to the end without reading a record, and their examples
     appended to the device buffer; -> (records appended, the endgame solver's statistics or None).  One-channel (BaseNN) examples are never
     aliased (examples_from_records).  endgame_targets > 0: SelfPlayEngine.solve_records before the append."""
     from .training import SelfPlayEngine
     eng = SelfPlayEngine(neural_network, board_size, num_episodes, num_simulations, degree_exploration, temperature, e_greedy, seed,
                          first_game_id, q_mode=q_mode, record_visits=visits, leaves_per_step=leaves_per_step, root_noise=root_noise,
-                         sample_moves=sample_moves)
+                         sample_moves=sample_moves, solve_leaves=solve_leaves)
     for _ in range(board_size * board_size):
         eng.run(4)
         if eng.stats()["live_games"] == 0:
             break
     endgame = eng.solve_records(endgame_targets) if endgame_targets else None
+    if solve_leaves:
+        training.rows_solved += eng.rows_solved()
     return replay.append_engine(eng, alias_final=alias_final_boards and getattr(neural_network, "in_channels", 2) == 2,
                                 policy_target=policy_target, target_temperature=target_temperature), endgame
 
@@ -215,7 +223,8 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
              self_play_interval, self_play_total_games, self_play_threshold, checkpoint_filepath, training_buffer_size,
              seed=1234, reference_aliasing=True, alias_final_boards=True, dump_examples=False, q_mode=_lib.QMODE_F64,
              distributed=False, batched_evaluation=False, policy_target="onehot", target_temperature=1.0, leaves_per_step=1,
-             root_noise=None, sample_moves=None, replay="host", evaluation_opponent="random", endgame_targets=0):
+             root_noise=None, sample_moves=None, replay="host", evaluation_opponent="random", endgame_targets=0,
+             solve_leaves=0):
     """main.py:56-259 on the GPU engines; returns `historic` = [(episodes done, win rate vs random), ...]
 
     batched_evaluation=True plays the evaluation games against RandomOthelloAgent in lock step on the GPU
@@ -260,8 +269,19 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
     and with replay="device" (before the append).  The reference trains on played outcomes only.  Logs solved / z_changed / mean_disc_loss per
     iteration (the discs the moves played gave away against perfect play); training.endgame_history keeps the dicts.  It needs
     alias_final_boards=False.  Use 10, not the cap: on an MI355X the slowest of 64 random 8x8 positions takes 42 ms at 10 empties and 0.98 s at
-    12, and relabelling 4 096 games at 10 costs 1 % of their self-play ("Endgame solver")."""
+    12, and relabelling 4 096 games at 10 costs 1 % of their self-play ("Endgame solver").
+
+    solve_leaves=E (0 = off, the default; at most 10): inside every search of the batched engines -- self-play, matches and batched evaluation
+    -- a leaf with E empties or fewer takes its exact win / draw / loss (+1 / 0 / -1 for the side to move, a draw is 0) in place of the
+    network's value, solved on the device right after the network's batch; the priors stay the network's.  The visit counts that
+    policy_target="visits" trains on and the moves that mean_disc_loss measures then come from exact values over the last plies.  The
+    reference has nothing like it.  training.rows_solved counts the self-play leaves solved.  The drop-in evaluation agents stay without it.
+    Use 6: on an MI355X at 4 096 games of 8x8 the solving kernel then takes 0.11 ms of a 3.8 ms network batch (174 leaves solved per batch), inside
+    the run-to-run spread of the search without it; 8 costs 0.53 ms (a fifth more per batch), 10 costs 5.2 ms and more than doubles the batch
+    (DESIGN.md, "Solved leaves"; tools/solve_leaves_bench.py, profiles/solve_leaves_bench.json)."""
     _lib.check_opponent(evaluation_opponent)
+    solve_leaves = _lib.check_solve_leaves(solve_leaves)
+    training.rows_solved = 0
     endgame_targets = _lib.check_endgame_targets(endgame_targets, alias_final_boards)
     training.endgame_history = []
     if replay not in ("host", "device"):
@@ -324,7 +344,7 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
             appended, endgame = _selfplay_into_replay(device_replay, neural_network, board_size, num_episodes, num_simulations,
                                                       degree_exploration, temperature, e_greedy, seed, total_episodes_done, q_mode, visits,
                                                       leaves_per_step, root_noise, sample_moves, alias_final_boards, policy_target,
-                                                      target_temperature, endgame_targets)
+                                                      target_temperature, endgame_targets, solve_leaves)
             if endgame is not None:
                 training.endgame_history.append(endgame)
                 _log_endgame(i, num_iterations, endgame)
@@ -337,8 +357,10 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
                 first, count = shard_games(num_episodes, rank, world)
                 eng = SelfPlayEngine(neural_network, board_size, count, num_simulations, degree_exploration, temperature, e_greedy,
                                      seed=seed, first_game_id=total_episodes_done + first, q_mode=q_mode, record_visits=visits,
-                                     leaves_per_step=leaves_per_step, root_noise=root_noise, sample_moves=sample_moves)
+                                     leaves_per_step=leaves_per_step, root_noise=root_noise, sample_moves=sample_moves,
+                                     solve_leaves=solve_leaves)
                 eng.play_to_end(endgame_targets=endgame_targets)                        # each rank relabels its own records
+                training.rows_solved += eng.rows_solved() if solve_leaves else 0
                 records = pooled_selfplay_records(eng, device, with_visits=visits)      # the only exchange of the self-play phase
                 endgame = getattr(eng, "endgame_stats", None)
                 del eng
@@ -347,7 +369,8 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
                                          degree_exploration=degree_exploration, policy_temperature=temperature, e_greedy=e_greedy,
                                          seed=seed, first_game_id=total_episodes_done, q_mode=q_mode, record_visits=visits,
                                          leaves_per_step=leaves_per_step, root_noise=root_noise, sample_moves=sample_moves,
-                                         **({"endgame_targets": endgame_targets} if endgame_targets else {}))
+                                         **({"endgame_targets": endgame_targets} if endgame_targets else {}), **({"solve_leaves": solve_leaves} if solve_leaves else {}))
+                training.rows_solved += selfplay_batch.rows_solved if solve_leaves else 0
                 endgame = getattr(selfplay_batch, "endgame_stats", None) if endgame_targets else None
             if endgame is not None:
                 training.endgame_history.append(endgame)
@@ -373,7 +396,8 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
         if self_play_training and i % self_play_interval == 0:
             logging.info('[%d/%d] arena: trained network against the previous one', i, num_iterations)
             new_net_victories = self_play_match(board_size, neural_network, old_neural_network, self_play_total_games,
-                                                num_simulations, degree_exploration, seed=seed + i, leaves_per_step=leaves_per_step)
+                                                num_simulations, degree_exploration, seed=seed + i, leaves_per_step=leaves_per_step,
+                                                **({"solve_leaves": solve_leaves} if solve_leaves else {}))
             logging.info('[%d/%d] arena: %d of %d games to the trained network', i, num_iterations, new_net_victories, self_play_total_games)
             if new_net_victories >= self_play_threshold:
                 logging.info('[%d/%d] trained network promoted', i, num_iterations)
@@ -392,10 +416,10 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
             if batched_evaluation:
                 new = evaluate_against_random_batch(board_size, neural_network, evaluation_iterations, num_simulations,
                                                     degree_exploration, seed=seed + 7919 * i, leaves_per_step=leaves_per_step,
-                                                    opponent=evaluation_opponent)
+                                                    opponent=evaluation_opponent, **({"solve_leaves": solve_leaves} if solve_leaves else {}))
                 old = evaluate_against_random_batch(board_size, old_neural_network, evaluation_iterations, num_simulations,
                                                     degree_exploration, seed=seed + 7919 * i + 1, leaves_per_step=leaves_per_step,
-                                                    opponent=evaluation_opponent)
+                                                    opponent=evaluation_opponent, **({"solve_leaves": solve_leaves} if solve_leaves else {}))
             else:
                 new = evaluate_against_random(board_size, neural_network, evaluation_iterations, num_simulations, degree_exploration,
                                               label=f'after {total_episodes_done} episodes, current network', opponent=evaluation_opponent)

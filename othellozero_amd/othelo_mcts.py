@@ -18,11 +18,14 @@ from .Othello import OthelloGame, OthelloPlayer
 
 class OthelloMCTS:
     def __init__(self, board_size, neural_network, degree_exploration, q_mode=_lib.QMODE_F64,
-                 node_cap=8192, leaves_per_step=1):
+                 node_cap=8192, leaves_per_step=1, solve_leaves=0):
         """q_mode: OZ_QMODE_F64 = the NumPy 1.18.5 promotion the reference pins (requirements.txt:19),
         OZ_QMODE_NEP50 = what NumPy >= 2 computes (SURVEY.md R-FP).
         leaves_per_step > 1 (native networks only, created with max_batch >= leaves_per_step): that many descents of the tree per
-        network batch, kept apart by a virtual loss (oz_mcts_set_leaves_per_step); not the reference's search order."""
+        network batch, kept apart by a virtual loss (oz_mcts_set_leaves_per_step); not the reference's search order.
+        solve_leaves=E > 0 (native networks only): a leaf with at most E empties takes its exact win / draw / loss (+1 / 0 / -1 for the side
+        to move, oz_mcts_set_solve_leaves) in place of the network's value; the priors stay the network's.  Not the reference's search."""
+        self.solve_leaves = _lib.check_solve_leaves(solve_leaves)
         self._board_size = board_size
         self._neural_network = neural_network
         # othelo_mcts.py:15-18: ONN nets see the two-channel board, BNN nets the one-channel (+1 / -1) view
@@ -37,11 +40,21 @@ class OthelloMCTS:
             raise ValueError(f"leaves_per_step must be 1 .. {_lib.MAX_LEAVES_PER_STEP} (got {leaves_per_step})")
         if self.leaves_per_step != 1 and not self._native:
             raise ValueError("leaves_per_step > 1 needs a native NNetWrapper / StubNetWrapper (the leaves are evaluated on the device)")
+        if self.solve_leaves and not self._native:
+            raise ValueError("solve_leaves > 0 needs a native NNetWrapper / StubNetWrapper (the leaves are evaluated and solved on the device)")
         lib = _lib.require_gpu()
         _lib.check(lib.oz_mcts_create(C.byref(self._h), board_size, 1, node_cap, float(degree_exploration), q_mode))
         self._root = None
         if self.leaves_per_step != 1:
             _lib.check(lib.oz_mcts_set_leaves_per_step(self._h, self.leaves_per_step))
+        if self.solve_leaves:
+            _lib.check(lib.oz_mcts_set_solve_leaves(self._h, self.solve_leaves))
+
+    def rows_solved(self):
+        """leaves this search has given their exact value so far (0 without solve_leaves)"""
+        e, rows = C.c_int(), C.c_int64()
+        _lib.check(_lib.load().oz_mcts_get_solve_leaves(self._h, C.byref(e), C.byref(rows)))
+        return rows.value
 
     def __del__(self):
         try:

@@ -32,7 +32,7 @@ def training_example_symmetries(board, policy):
 
 def execute_episode(board_size, neural_network, degree_exploration, num_simulations, policy_temperature, e_greedy,
                     q_mode=_lib.QMODE_F64, snapshot_boards=False, policy_target="onehot", target_temperature=1.0,
-                    leaves_per_step=1, root_noise=None, noise_seed=0, sample_moves=None, sample_seed=0):
+                    leaves_per_step=1, root_noise=None, noise_seed=0, sample_moves=None, sample_seed=0, solve_leaves=0):
     """training.py:26-72.  Returns [(board (n,n,2) bool, one-hot policy (n,n) float64, z int), ...], 8 per move.
 
     snapshot_boards=False reproduces the reference exactly, including its aliasing quirk: the
@@ -50,7 +50,11 @@ def execute_episode(board_size, neural_network, degree_exploration, num_simulati
 
     sample_moves=(temperature, plies): where the coin falls on the greedy branch, the move of a ply < plies is drawn on the device in proportion
     to N ** (1 / temperature) (OthelloMCTS.sample_action), keyed (sample_seed, 0, ply), instead of taken as the arg-max; None is the function
-    without it."""
+    without it.
+
+    solve_leaves=E > 0: the search takes the exact win / draw / loss of a leaf with at most E empties in place of the network's value
+    (OthelloMCTS); a native network only."""
+    solve_leaves = _lib.check_solve_leaves(solve_leaves)
     root_noise = _lib.check_root_noise(root_noise)
     sample_moves = _lib.check_sample_moves(sample_moves)
     assert policy_target in ("onehot", "visits"), policy_target
@@ -59,7 +63,8 @@ def execute_episode(board_size, neural_network, degree_exploration, num_simulati
     examples = []
     game = OthelloGame(board_size)
     mcts = OthelloMCTS(board_size, neural_network, degree_exploration, q_mode=q_mode,
-                       node_cap=num_simulations * (board_size * board_size - 3) + 64, leaves_per_step=leaves_per_step)
+                       node_cap=num_simulations * (board_size * board_size - 3) + 64, leaves_per_step=leaves_per_step,
+                       solve_leaves=solve_leaves)
     # training.py:34-37 (BNN examples are one-channel boards, a fresh array per round: no aliasing for them)
     board_view_type = BoardView.ONE_CHANNEL if getattr(neural_network.network_type, "name", "") == "BNN" else BoardView.TWO_CHANNELS
 
@@ -140,7 +145,7 @@ class SelfPlayEngine:
     def __init__(self, neural_network, board_size=8, num_games=4096, num_simulations=100, degree_exploration=1.0,
                  policy_temperature=1.0, e_greedy=0.9, seed=1234, first_game_id=0, game_id_stride=0,
                  q_mode=_lib.QMODE_F64, refill=False, node_cap=0, record_cap=0, dedup=True, batch_cap=0, eval_cache=False,
-                 record_visits=False, leaves_per_step=1, root_noise=None, sample_moves=None):
+                 record_visits=False, leaves_per_step=1, root_noise=None, sample_moves=None, solve_leaves=0):
         """dedup: cross-game leaf de-duplication (a board several games reach in one batch is evaluated once; no record changes);
         batch_cap: leaves per network batch of the free-running driver (0 = none; see preferred_batch_cap);
         eval_cache: take (pi, v) of boards the network has evaluated before from its persistent cache (NNetWrapper.set_eval_cache) --
@@ -155,7 +160,12 @@ class SelfPlayEngine:
         the records' layout do not change.
         sample_moves=(temperature, plies): where the coin falls on the greedy branch, the move of a game whose ply < plies is drawn in
         proportion to N ** (1 / temperature), keyed (seed, game id, ply), instead of taken as the arg-max (oz_selfplay_set_move_sampling);
-        such a record has greedy == 2.  run(), run_steps() and stagger() alike; later plies and the explore branch are unchanged."""
+        such a record has greedy == 2.  run(), run_steps() and stagger() alike; later plies and the explore branch are unchanged.
+        solve_leaves=E > 0: in every search a leaf with at most E empties takes its exact win / draw / loss (+1 / 0 / -1 for the side to
+        move) in place of the network's value, solved on the device right after the network's batch (oz_selfplay_set_solve_leaves); the
+        priors stay the network's and its evaluation cache keeps the network's value.  Every driver, any leaves_per_step.  rows_solved()
+        counts them.  Not the reference's search."""
+        solve_leaves = _lib.check_solve_leaves(solve_leaves)
         root_noise = _lib.check_root_noise(root_noise)
         sample_moves = _lib.check_sample_moves(sample_moves)
         lib = _lib.require_gpu()
@@ -179,6 +189,31 @@ class SelfPlayEngine:
         self.sample_moves = sample_moves
         if sample_moves is not None:
             _lib.check(lib.oz_selfplay_set_move_sampling(self._h, sample_moves[0], sample_moves[1]))
+        self.solve_leaves = solve_leaves
+        if solve_leaves:
+            _lib.check(lib.oz_selfplay_set_solve_leaves(self._h, solve_leaves))
+
+    def set_solve_leaves(self, max_empties):
+        """solved leaves on (E > 0) / off (0) from the next search step on"""
+        max_empties = _lib.check_solve_leaves(max_empties)
+        _lib.check(_lib.load().oz_selfplay_set_solve_leaves(self._h, max_empties))
+        self.solve_leaves = max_empties
+
+    def solve_leaves_profile(self, enable=True):
+        """HIP-event timing of the solving kernel on the launch stream (tools/solve_leaves_bench.py)"""
+        _lib.check(_lib.load().oz_selfplay_solve_leaves_profile(self._h, 1 if enable else 0))
+
+    def solve_leaves_profile_read(self, reset=False):
+        """(ms_total, launches) of the solving kernel since the last reset"""
+        ms, cnt = C.c_double(), C.c_int64()
+        _lib.check(_lib.load().oz_selfplay_solve_leaves_profile_read(self._h, C.byref(ms), C.byref(cnt), 1 if reset else 0))
+        return ms.value, cnt.value
+
+    def rows_solved(self):
+        """leaves the engine's searches have given their exact value so far"""
+        e, rows = C.c_int(), C.c_int64()
+        _lib.check(_lib.load().oz_selfplay_get_solve_leaves(self._h, C.byref(e), C.byref(rows)))
+        return rows.value
 
     def __del__(self):
         try:
@@ -363,22 +398,27 @@ def expand_examples(records, board_size, alias_final=False, visits=None, target_
 def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations=100, degree_exploration=1.0,
                    policy_temperature=1.0, e_greedy=0.9, seed=1234, first_game_id=0, q_mode=_lib.QMODE_F64,
                    expand=False, alias_final=False, record_visits=False, target_temperature=1.0, leaves_per_step=1, root_noise=None,
-                   sample_moves=None, endgame_targets=0):
+                   sample_moves=None, endgame_targets=0, solve_leaves=0):
     """Play num_games complete games; returns the move records (or the expanded examples).
     record_visits=True: (records, visit counts) -- or, with expand, the examples with visit-distribution targets at target_temperature.
     root_noise=(alpha, epsilon): Dirichlet root noise in every search (SelfPlayEngine).
     sample_moves=(temperature, plies): the opening plies' moves are sampled from the visit counts (SelfPlayEngine).
     endgame_targets=E > 0: records with E empties or fewer carry the exact solver's value target (SelfPlayEngine.solve_records); with expand it
-    needs alias_final=False.  selfplay_batch.endgame_stats holds the last call's statistics (None when off)."""
+    needs alias_final=False.  selfplay_batch.endgame_stats holds the last call's statistics (None when off).
+    solve_leaves=E > 0: exact values for the searches' leaves with at most E empties (SelfPlayEngine); selfplay_batch.rows_solved holds the
+    last call's count (None when off)."""
+    solve_leaves = _lib.check_solve_leaves(solve_leaves)
     endgame_targets = _lib.check_endgame_targets(endgame_targets, expand and alias_final)
     eng = SelfPlayEngine(neural_network, board_size, num_games, num_simulations, degree_exploration, policy_temperature,
                          e_greedy, seed, first_game_id, q_mode=q_mode, record_visits=record_visits, leaves_per_step=leaves_per_step,
-                         root_noise=root_noise, sample_moves=sample_moves)
-    selfplay_batch.endgame_stats = None
+                         root_noise=root_noise, sample_moves=sample_moves, solve_leaves=solve_leaves)
+    selfplay_batch.endgame_stats = selfplay_batch.rows_solved = None
     if record_visits:
         rec, counts = eng.play_to_end(with_visits=True, endgame_targets=endgame_targets)
+        selfplay_batch.rows_solved = eng.rows_solved() if solve_leaves else None
         selfplay_batch.endgame_stats = getattr(eng, "endgame_stats", None)
         return expand_examples(rec, board_size, alias_final, visits=counts, target_temperature=target_temperature) if expand else (rec, counts)
     rec = eng.play_to_end(endgame_targets=endgame_targets)
+    selfplay_batch.rows_solved = eng.rows_solved() if solve_leaves else None
     selfplay_batch.endgame_stats = getattr(eng, "endgame_stats", None)
     return expand_examples(rec, board_size, alias_final) if expand else rec
