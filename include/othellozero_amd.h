@@ -97,6 +97,18 @@ int oz_rules_solve(const uint64_t* black, const uint64_t* white, const int8_t* p
  * Same argument checks and errors as oz_rules_solve. */
 int oz_rules_solve_sign(const uint64_t* black, const uint64_t* white, const int8_t* player, int n, int count, int max_empties,
                         int8_t* sign /* [count] */, uint8_t* solved /* [count] */);
+/* random openings (the reference has none: every game of a match starts from the one standard position, agents.py:71-84).  Opening `id` of
+ * (plies, opening_seed): from the standard position with BLACK to move, while ply < plies and the game is not over, the mover OthelloGame.play left
+ * plays oz_kth_bit(legal, oz_rng(opening_seed, id, ply, OZ_RNG_OPENING = 5) % popcount(legal)) -- RandomOthelloAgent's random.choice on a stream
+ * of its own; a pass lets one side move twice in a row, a game that ends inside its opening stays ended with n_plies < plies.
+ * Batch entry: the openings first_opening_id .. first_opening_id + count - 1 (count <= 2^22): the position each one reaches, who is to move, whether
+ * the game is over, the squares played (row*8+col, 0 beyond n_plies) and their number.  Any output may be NULL.  What oz_arena_set_openings
+ * plays, obtainable without an arena -- and handed back to one as lists through oz_arena_set_opening_moves.
+ * OZ_ERR_ARG: plies outside 0..OZ_OPENING_MAX_PLIES, count outside 0..2^22. */
+#define OZ_OPENING_MAX_PLIES 16
+int oz_rules_random_openings(int n, int64_t count, int plies, uint64_t opening_seed, uint64_t first_opening_id,
+                             uint64_t* black, uint64_t* white, int8_t* player, uint8_t* finished,
+                             uint8_t* actions /* [count][OZ_OPENING_MAX_PLIES], 0 beyond n_plies */, int32_t* n_plies);
 /* HIP-event timing of the kernel of every oz_rules_* batch call on the current device (default off: nothing is recorded); the read returns
  * the total since creation / the last reset and the number of launches (each may be NULL) */
 int oz_rules_profile(int enable);
@@ -597,6 +609,23 @@ int oz_arena_set_opponent(oz_arena* a, int side /* +1 BLACK, -1 WHITE */, int ki
 /* with oz_arena_profile on: HIP-event time and launches of the network-free colour's move kernel under OZ_AGENT_MINIMAX (agents.py:27-41;
  * zeros for OZ_AGENT_RANDOM, whose launches are not timed) */
 int oz_arena_opponent_time(oz_arena* a, double* ms_total, int64_t* launches);
+/* Openings: every game plays its first plies without any search, once, at the head of the first oz_arena_run / oz_arena_run_rounds (whose
+ * max_rounds counts the searched rounds after them), then the agents take over from the position reached.  Default off: every game starts
+ * from the standard position, as in the reference.  The opening plies are ordinary logged moves (actions / players / n_moves of
+ * oz_arena_results include them, so `actions` still replays a game from the standard position).  The opening id of game slot g is
+ * first_opening_id + g and does NOT depend on seed or first_game_id: two arenas given the same (opening_seed, first_opening_id) play the same
+ * openings -- new against old and old against new, or two candidates against one suite; every later ply stays keyed (seed, game id, true ply).
+ * A game that ends inside its opening stays ended and its result stands.  Independent of leaves_per_step, solve_leaves, the evaluation
+ * cache, de-duplication and oz_arena_set_opponent.
+ * oz_arena_set_openings: random openings of `plies` plies as oz_rules_random_openings defines them; plies == 0 switches openings off.
+ * oz_arena_set_opening_moves: game g plays moves[g][0 .. n_plies[g] - 1] (squares row*8+col).  Every list is replayed on the host first:
+ * OZ_ERR_ARG, naming the game and the ply, for a move that is not legal, a move after the game has ended or an n_plies outside
+ * 0..OZ_OPENING_MAX_PLIES (and nothing is changed).
+ * Both only before the first run (OZ_ERR_STATE afterwards); the later call counts.  oz_arena_set_openings: OZ_ERR_ARG for plies outside
+ * 0..OZ_OPENING_MAX_PLIES.  oz_arena_opening_plies: the plies each game's opening played (zeros with openings off and before the first run). */
+int oz_arena_set_openings(oz_arena* a, int plies, uint64_t opening_seed, uint64_t first_opening_id);
+int oz_arena_set_opening_moves(oz_arena* a, const uint8_t* moves /* [num_games][OZ_OPENING_MAX_PLIES] */, const int32_t* n_plies /* [num_games] */);
+int oz_arena_opening_plies(oz_arena* a, int32_t* out /* [num_games] */);
 int oz_arena_results(oz_arena* a, int8_t* winner /* +1 net_a */, int32_t* points, int32_t* n_moves,
                      uint8_t* actions /* [num_games][128] */, int8_t* players /* [num_games][128] */,
                      uint64_t* final_black, uint64_t* final_white);

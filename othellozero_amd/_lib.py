@@ -35,6 +35,7 @@ MINIMAX_EVALS = {"discs": MINIMAX_EVAL_DISCS, "weighted": MINIMAX_EVAL_WEIGHTED}
 SOLVE_MAX_EMPTIES = 12                                                               # OZ_SOLVE_MAX_EMPTIES
 SOLVE_LEAVES_MAX_EMPTIES = 10                                                        # OZ_SOLVE_LEAVES_MAX_EMPTIES
 AGENT_RANDOM, AGENT_MINIMAX = 0, 1                                                   # oz_arena_set_opponent
+OPENING_MAX_PLIES = 16                                                               # OZ_OPENING_MAX_PLIES
 REPLAY_TARGET_ONEHOT, REPLAY_TARGET_VISITS = 0, 1                                    # oz_replay_append_*
 NET_KERNELS = ("input", "conv2", "conv3", "conv4", "fc1", "fc2", "heads")           # OZ_NET_KERNELS slots
 TREE_KERNELS = ("select", "compact", "network", "expand_backup", "roots_move")       # OZ_TREE_KERNELS slots
@@ -97,6 +98,7 @@ SIGNATURES = {
     "oz_rules_minimax": [_u64p, _u64p, _i8p, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _u64p],      # agents.py:27-41
     "oz_rules_solve": [_u64p, _u64p, _i8p, C.c_int, C.c_int, C.c_int, _i32p, _u64p, _i32p, _u8p],
     "oz_rules_solve_sign": [_u64p, _u64p, _i8p, C.c_int, C.c_int, C.c_int, _i8p, _u8p],
+    "oz_rules_random_openings": [C.c_int, C.c_int64, C.c_int, C.c_uint64, C.c_uint64, _u64p, _u64p, _i8p, _u8p, _u8p, _i32p],
     "oz_rules_profile": [C.c_int], "oz_rules_profile_read": [_f64p, _i64p, C.c_int],
     "oz_selfplay_solve_records": [_vp, C.c_int64, C.c_int, C.POINTER(EndgameStats)],
     "oz_net_create": [C.POINTER(_vp), C.c_int, C.c_int, C.c_int],
@@ -165,6 +167,8 @@ SIGNATURES = {
     "oz_arena_destroy": [_vp], "oz_arena_run": [_vp], "oz_arena_run_rounds": [_vp, C.c_int], "oz_arena_stats": [_vp, _i64p, _i64p],
     "oz_arena_set_dedup": [_vp, C.c_int], "oz_arena_set_eval_cache": [_vp, C.c_int], "oz_arena_profile": [_vp, C.c_int], "oz_arena_profile_read": [_vp, _f64p, _i64p, C.c_int], "oz_arena_leaves_evaluated": [_vp, _i64p, _i64p],
     "oz_arena_set_opponent": [_vp, C.c_int, C.c_int, C.c_int, C.c_int], "oz_arena_opponent_time": [_vp, _f64p, _i64p],      # agents.py:27-41
+    "oz_arena_set_openings": [_vp, C.c_int, C.c_uint64, C.c_uint64], "oz_arena_set_opening_moves": [_vp, _u8p, _i32p],
+    "oz_arena_opening_plies": [_vp, _i32p],
     "oz_arena_results": [_vp, _i8p, _i32p, _i32p, _u8p, _i8p, _u64p, _u64p],
     "oz_examples_expand": [_vp, C.c_int64, C.c_int, C.c_int, _u8p, _i32p, _i8p],
     "oz_examples_expand_visits": [_vp, _i32p, C.c_int64, C.c_int, C.c_int, C.c_double, _u8p, _f64p, _i8p],
@@ -430,6 +434,52 @@ def check_opponents(opponent, black_free, white_free):
     if not black_free and not white_free:
         raise ValueError("opponent: both colours have a network, there is no colour for the minimax opponent to play")
     return (spec, None) if black_free else (None, spec)
+
+
+def _whole(x, lo, hi):
+    return not isinstance(x, bool) and isinstance(x, (int, np.integer)) and lo <= x <= hi
+
+
+def check_opening_plies(plies, what="openings"):
+    """the plies of a random opening -> int; ValueError for anything but a whole number in 0..OZ_OPENING_MAX_PLIES"""
+    if not _whole(plies, 0, OPENING_MAX_PLIES):
+        raise ValueError(f"{what}: plies must be a whole number in 0..{OPENING_MAX_PLIES} (got {plies!r})")
+    return int(plies)
+
+
+def check_openings(openings=None, first_opening_id=0, opening_moves=None, num_games=None):
+    """The opening options of an arena.  openings = None or (plies, opening_seed): random openings (oz_arena_set_openings), game slot g playing
+    opening first_opening_id + g.  opening_moves = None or (moves, n_plies): game g plays moves[g][:n_plies[g]] (oz_arena_set_opening_moves);
+    moves an unsigned 8-bit integer array of shape (num_games, OZ_OPENING_MAX_PLIES), n_plies a 32-bit integer array of shape (num_games,).
+    Returns None (off), ("random", plies, seed, first_opening_id) or ("moves", moves, n_plies) with contiguous arrays; ValueError for anything
+    the library would refuse or could not read: both options at once, a wrong tuple shape, a plies that is no whole number (or a bool) or lies
+    outside 0..OZ_OPENING_MAX_PLIES, a seed or id that is no whole number in 0..2^64 - 1, arrays of another shape or dtype, an n_plies entry
+    out of range.  (Whether a listed move is legal is the library's check: it replays the lists.)"""
+    if not _whole(first_opening_id, 0, 2 ** 64 - 1):
+        raise ValueError(f"first_opening_id must be a whole number in 0..2^64 - 1 (got {first_opening_id!r})")
+    if openings is not None and opening_moves is not None:
+        raise ValueError("openings and opening_moves are two ways to say how the games start: give one of them")
+    if openings is not None:
+        if not isinstance(openings, (tuple, list)) or len(openings) != 2:
+            raise ValueError(f"openings must be None or (plies, opening_seed), got {openings!r}")
+        plies = check_opening_plies(openings[0])
+        if not _whole(openings[1], 0, 2 ** 64 - 1):
+            raise ValueError(f"openings: opening_seed must be a whole number in 0..2^64 - 1 (got {openings[1]!r})")
+        return "random", plies, int(openings[1]), int(first_opening_id)
+    if opening_moves is not None:
+        if not isinstance(opening_moves, (tuple, list)) or len(opening_moves) != 2:
+            raise ValueError(f"opening_moves must be None or (moves, n_plies), got {opening_moves!r}")
+        moves, n_plies = opening_moves
+        if not isinstance(moves, np.ndarray) or moves.dtype != np.uint8 or moves.ndim != 2 or moves.shape[1] != OPENING_MAX_PLIES:
+            raise ValueError(f"opening_moves: moves must be a uint8 array of shape (num_games, {OPENING_MAX_PLIES})")
+        if not isinstance(n_plies, np.ndarray) or n_plies.dtype != np.int32 or n_plies.shape != (moves.shape[0],):
+            raise ValueError("opening_moves: n_plies must be an int32 array of shape (num_games,)")
+        if num_games is not None and moves.shape[0] != num_games:
+            raise ValueError(f"opening_moves: {moves.shape[0]} move lists for {num_games} games")
+        if n_plies.size and (n_plies.min() < 0 or n_plies.max() > OPENING_MAX_PLIES):
+            raise ValueError(f"opening_moves: every n_plies must be in 0..{OPENING_MAX_PLIES}")
+        return "moves", np.ascontiguousarray(moves), np.ascontiguousarray(n_plies)
+    return None
 
 
 def check(rc):

@@ -79,6 +79,25 @@ def rules_solve_sign(black, white, player, n, max_empties=_lib.SOLVE_MAX_EMPTIES
     return sign, solved
 
 
+def rules_random_openings(n, count, plies, seed, first_opening_id=0):
+    """oz_rules_random_openings: the random openings first_opening_id .. first_opening_id + count - 1 of (plies, seed) on the n x n board, what
+    arena_batch(openings=(plies, seed), first_opening_id=...) lets its games start with.  -> dict(black, white uint64 (count,) = the position
+    reached, player int8 (+1 BLACK / -1 WHITE to move), finished uint8 (the game ended inside the opening), actions uint8 (count, 16) = the
+    squares played, row*8+col, 0 beyond n_plies, n_plies int32 (count,)).  (actions, n_plies) is what opening_moves= takes."""
+    plies = _lib.check_opening_plies(plies, "rules_random_openings")
+    if not _lib._whole(count, 0, 1 << 22):
+        raise ValueError(f"rules_random_openings: count must be a whole number in 0..2^22 (got {count!r})")
+    for what, x in (("seed", seed), ("first_opening_id", first_opening_id)):
+        if not _lib._whole(x, 0, 2 ** 64 - 1):
+            raise ValueError(f"rules_random_openings: {what} must be a whole number in 0..2^64 - 1 (got {x!r})")
+    k = int(count)
+    black, white, player, finished = np.zeros(k, np.uint64), np.zeros(k, np.uint64), np.zeros(k, np.int8), np.zeros(k, np.uint8)
+    actions, n_plies = np.zeros((k, _lib.OPENING_MAX_PLIES), np.uint8), np.zeros(k, np.int32)
+    _lib.check(_lib.require_gpu().oz_rules_random_openings(n, k, plies, int(seed), int(first_opening_id), _lib.p_u64(black), _lib.p_u64(white),
+                                                           _lib.p_i8(player), _lib.p_u8(finished), _lib.p_u8(actions), _lib.p_i32(n_plies)))
+    return dict(black=black, white=white, player=player, finished=finished, actions=actions, n_plies=n_plies)
+
+
 class MinimaxOthelloAgent(OthelloAgent):
     """Fixed-depth minimax on the device (oz_rules_minimax): what the reference's GreedyOthelloAgent (agents.py:27-41, dead code) was meant to
     be at depth=1, evaluation="discs", and harder by one integer.  One call for the game's position, then `random.choice` over the moves of
@@ -148,7 +167,7 @@ def duel_between_agents(game, agent_1, agent_2):
 
 def arena_batch(net_a, net_b, board_size=8, num_games=512, num_simulations=800, degree_exploration=1.0, seed=0,
                 first_game_id=0, q_mode=_lib.QMODE_F64, node_cap=0, max_rounds=0, dedup=True, profile=False, eval_cache=False,
-                leaves_per_step=1, opponent=None, solve_leaves=0):
+                leaves_per_step=1, opponent=None, solve_leaves=0, openings=None, first_opening_id=0, opening_moves=None):
     """num_games games of net_a (BLACK) vs net_b (WHITE), temperature 0, max-visit ties broken by the RNG_TIE
     stream keyed (seed, game id, ply).  One of the two may be None: RandomOthelloAgent plays that colour, or with
     opponent=("minimax", depth) / ("minimax", depth, "discs" | "weighted") the fixed-depth minimax (oz_arena_set_opponent; ties between its
@@ -163,7 +182,14 @@ def arena_batch(net_a, net_b, board_size=8, num_games=512, num_simulations=800, 
     leaves_per_step = k or (k_black, k_white): descents per game and network batch of the two agents' searches under virtual loss
     (oz_arena_set_leaves_per_step); an agent's network needs max_batch >= num_games * its k.
     solve_leaves = E or (E_black, E_white): the agent's search takes the exact win / draw / loss of a leaf with at most E empties in place of
-    its network's value (oz_arena_set_solve_leaves; 0 = off); the result then carries rows_solved = (black, white)."""
+    its network's value (oz_arena_set_solve_leaves; 0 = off); the result then carries rows_solved = (black, white).
+    openings = (plies, opening_seed): every game first plays a random opening of `plies` plies (at most 16) without any search
+    (oz_arena_set_openings, rules_random_openings); game slot g plays opening first_opening_id + g whatever seed and first_game_id are, so two
+    arenas given the same (openings, first_opening_id) start from the same positions.  opening_moves = (moves uint8 (num_games, 16), n_plies int32
+    (num_games,)): game g plays that list instead (oz_arena_set_opening_moves; an illegal move is an OzError naming game and ply).  The opening
+    plies are part of actions / players / n_moves; the result then carries opening_plies int32 (num_games,) = how many each game played (fewer
+    than asked for where the game ended first)."""
+    opening = _lib.check_openings(openings, first_opening_id, opening_moves, num_games)
     eb_, ew_ = _lib.check_solve_leaves_pair(solve_leaves)
     kb, kw = (leaves_per_step, leaves_per_step) if np.isscalar(leaves_per_step) else leaves_per_step
     minimax = _lib.check_opponents(opponent, net_a is None, net_b is None)
@@ -181,6 +207,10 @@ def arena_batch(net_a, net_b, board_size=8, num_games=512, num_simulations=800, 
             _lib.check(lib.oz_arena_set_leaves_per_step(h, int(kb), int(kw)))
         if not (np.isscalar(solve_leaves) and solve_leaves == 0):
             _lib.check(lib.oz_arena_set_solve_leaves(h, eb_, ew_))
+        if opening is not None and opening[0] == "random":
+            _lib.check(lib.oz_arena_set_openings(h, opening[1], opening[2], opening[3]))
+        elif opening is not None:
+            _lib.check(lib.oz_arena_set_opening_moves(h, _lib.p_u8(opening[1]), _lib.p_i32(opening[2])))
         for side, spec in zip((1, -1), minimax):             # a colour without a network
             if spec is not None:
                 _lib.check(lib.oz_arena_set_opponent(h, side, _lib.AGENT_MINIMAX, spec[0], spec[1]))
@@ -206,6 +236,10 @@ def arena_batch(net_a, net_b, board_size=8, num_games=512, num_simulations=800, 
         _lib.check(lib.oz_arena_stats(h, _lib.p_i64(sa), _lib.p_i64(sb)))
         ea, eb = C.c_int64(), C.c_int64()
         _lib.check(lib.oz_arena_leaves_evaluated(h, C.byref(ea), C.byref(eb)))
+        opening_plies = None
+        if opening is not None:
+            opening_plies = np.zeros(G, np.int32)
+            _lib.check(lib.oz_arena_opening_plies(h, _lib.p_i32(opening_plies)))
         winner, points, nm = np.zeros(G, np.int8), np.zeros(G, np.int32), np.zeros(G, np.int32)
         acts, pls = np.zeros((G, 128), np.uint8), np.zeros((G, 128), np.int8)
         fb, fw = np.zeros(G, np.uint64), np.zeros(G, np.uint64)
@@ -215,4 +249,5 @@ def arena_batch(net_a, net_b, board_size=8, num_games=512, num_simulations=800, 
         lib.oz_arena_destroy(h)
     return dict(winner=winner, points=points, n_moves=nm, actions=acts, players=pls, final_black=fb, final_white=fw,
                 stats_black=sa, stats_white=sb, leaves_evaluated=ea.value + eb.value, tree_kernels=tree,
-                **({"opponent_kernel": opp_kernel} if any(minimax) else {}), **({"rows_solved": rows} if rows is not None else {}))
+                **({"opponent_kernel": opp_kernel} if any(minimax) else {}), **({"rows_solved": rows} if rows is not None else {}),
+                **({"opening_plies": opening_plies} if opening is not None else {}))

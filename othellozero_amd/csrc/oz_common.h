@@ -24,9 +24,10 @@ OZ_HD uint64_t oz_sm64(uint64_t z) {
 }
 OZ_HD uint64_t oz_rotl64(uint64_t x, int r) { return (x << r) | (x >> (64 - r)); }
 
-enum { OZ_RNG_COIN = 0, OZ_RNG_EXPLORE = 1, OZ_RNG_TIE = 2, OZ_RNG_NOISE = 3, OZ_RNG_SAMPLE = 4 };
+enum { OZ_RNG_COIN = 0, OZ_RNG_EXPLORE = 1, OZ_RNG_TIE = 2, OZ_RNG_NOISE = 3, OZ_RNG_SAMPLE = 4, OZ_RNG_OPENING = 5 };
 // NOISE: stream 3 + 256 * square + 65536 * draw (root noise, oz_search.hip); SAMPLE: the one unit draw of a sampled move (move sampling,
-// oz_search.hip) -- 4 is none of 3 + 256 sq + 65536 i
+// oz_search.hip) -- 4 is none of 3 + 256 sq + 65536 i; OPENING: the move of an opening ply, keyed (opening seed, opening id, ply)
+// (oz_openings.h) -- nor is 5
 // counter-based stream replacing random.random / np.random.choice / random.choice
 // (training.py:51,56; othelo_mcts.py:59): keyed (seed, global game id, ply, purpose)
 OZ_HD uint64_t oz_rng(uint64_t seed, uint64_t game, uint64_t move, uint64_t stream) {

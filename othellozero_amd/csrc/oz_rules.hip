@@ -7,6 +7,7 @@
 
 #include "oz_internal.h"
 #include "oz_minimax.h"
+#include "oz_openings.h"
 #include "oz_solve.h"
 
 // ---------------------------------------------------------------- errors / device
@@ -348,6 +349,49 @@ OZ_API int oz_rules_solve_sign(const uint64_t* black, const uint64_t* white, con
         [&](const unsigned char* h) {
             if (sign) memcpy(sign, h, count);
             if (solved) memcpy(solved, h + c1, count);
+        });
+}
+
+// ---------------------------------------------------------------- random openings (oz_openings.h; the reference has none)
+// one thread per opening: the position it reaches and the squares it played (0 beyond n_plies)
+__global__ void k_random_openings(int n, uint64_t valid, int count, int plies, uint64_t seed, uint64_t first_id, uint64_t* __restrict__ black,
+                                  uint64_t* __restrict__ white, int32_t* __restrict__ n_plies, int8_t* __restrict__ player,
+                                  uint8_t* __restrict__ finished, uint8_t* __restrict__ actions) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    uint64_t b, w;
+    int p, f;
+    uint8_t* row = actions + (size_t)i * OZ_OPENING_MAX_PLIES;
+    const int played = oz_opening_play(n, valid, plies, nullptr, seed, first_id + (uint64_t)i, b, w, p, f,
+                                       [&](int ply, uint64_t, uint64_t, int, int action) { row[ply] = (uint8_t)action; });
+    for (int k = played; k < OZ_OPENING_MAX_PLIES; ++k) row[k] = 0;
+    black[i] = b; white[i] = w; n_plies[i] = played; player[i] = (int8_t)p; finished[i] = (uint8_t)f;
+}
+
+OZ_API int oz_rules_random_openings(int n, int64_t count64, int plies, uint64_t opening_seed, uint64_t first_opening_id, uint64_t* black,
+                                    uint64_t* white, int8_t* player, uint8_t* finished, uint8_t* actions, int32_t* n_plies) {
+    if (int rc = check_n(n)) return rc;
+    OZ_REQUIRE(plies >= 0 && plies <= OZ_OPENING_MAX_PLIES, "oz_rules_random_openings: plies %d outside 0..%d", plies, OZ_OPENING_MAX_PLIES);
+    OZ_REQUIRE(count64 >= 0 && count64 <= (1LL << 22), "oz_rules_random_openings: count %lld outside 0..2^22", (long long)count64);
+    if (count64 == 0) return OZ_OK;
+    const int count = (int)count64;
+    const size_t c8 = 8ull * count, c4 = pad8(4ull * count), c1 = pad8(count), ca = (size_t)count * OZ_OPENING_MAX_PLIES;
+    // no input but the scalars (eight bytes go up so that the one upload of rules_call has something to carry); output image:
+    // black | white | n_plies | player | finished | actions
+    return rules_call(8, 2 * c8 + c4 + 2 * c1 + ca,
+        [&](unsigned char* h) { memset(h, 0, 8); },
+        [&](unsigned char*, unsigned char* dout, hipStream_t s) {
+            hipLaunchKernelGGL(k_random_openings, dim3(grid_for(count)), dim3(256), 0, s, n, oz_valid_mask(n), count, plies, opening_seed,
+                               first_opening_id, (uint64_t*)dout, (uint64_t*)(dout + c8), (int32_t*)(dout + 2 * c8), (int8_t*)(dout + 2 * c8 + c4),
+                               (uint8_t*)(dout + 2 * c8 + c4 + c1), (uint8_t*)(dout + 2 * c8 + c4 + 2 * c1));
+        },
+        [&](const unsigned char* h) {
+            if (black) memcpy(black, h, c8);
+            if (white) memcpy(white, h + c8, c8);
+            if (n_plies) memcpy(n_plies, h + 2 * c8, 4ull * count);
+            if (player) memcpy(player, h + 2 * c8 + c4, count);
+            if (finished) memcpy(finished, h + 2 * c8 + c4 + c1, count);
+            if (actions) memcpy(actions, h + 2 * c8 + c4 + 2 * c1, ca);
         });
 }
 

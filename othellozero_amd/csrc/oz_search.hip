@@ -25,6 +25,7 @@
 
 #include "oz_internal.h"
 #include "oz_minimax.h"
+#include "oz_openings.h"
 #include "oz_solve.h"
 
 enum { VT_INT = 0, VT_F32 = 1, VT_F64 = 2 };
@@ -2078,11 +2079,28 @@ __global__ __launch_bounds__(64) void k_arena_minimax_move(GamesDev gm, int side
     atomicAdd(&gm.counters[2], 1ULL);
 }
 
-static void initial_board(int n, uint64_t* black, uint64_t* white) {     // Othello/__init__.py:177-184
-    const int h = n / 2;
-    *white = (1ULL << ((h - 1) * 8 + h - 1)) | (1ULL << (h * 8 + h));
-    *black = (1ULL << ((h - 1) * 8 + h)) | (1ULL << (h * 8 + h - 1));
+// The opening of every arena game (oz_openings.h; oz_arena_set_openings / oz_arena_set_opening_moves), once, before the first round: one thread
+// per game plays the opening with id first_id + g -- NOT the game's id -- from the standard position the slot holds, logs its plies like any other
+// move (greedy 0) and leaves board, mover, finished flag and ply where the first searched round takes over.  At most 16 plies: the log has room.
+__global__ void k_arena_openings(GamesDev gm, OpeningsDev op) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= gm.G) return;
+    uint64_t black, white;
+    int player, fin;
+    const size_t lb = (size_t)g * 64;
+    const int played = oz_opening_play(gm.n, gm.valid, op.moves ? op.n_plies[g] : op.plies, op.moves ? op.moves + (size_t)g * OZ_OPENING_MAX_PLIES : nullptr,
+                                       op.seed, op.first_id + (uint64_t)g, black, white, player, fin,
+                                       [&](int ply, uint64_t b, uint64_t w, int p, int action) {
+                                           gm.log_black[lb + ply] = b; gm.log_white[lb + ply] = w;
+                                           gm.log_action[lb + ply] = (uint8_t)action; gm.log_player[lb + ply] = (int8_t)p; gm.log_greedy[lb + ply] = 0;
+                                       });
+    gm.black[g] = black; gm.white[g] = white; gm.player[g] = (int8_t)player;
+    gm.finished[g] = (uint8_t)fin; gm.ply[g] = played;
+    op.opening_plies[g] = played;
+    if (played) atomicAdd(&gm.counters[2], (unsigned long long)played);
 }
+
+static void initial_board(int n, uint64_t* black, uint64_t* white) { oz_initial_board(n, *black, *white); }
 
 struct oz_selfplay {
     oz_selfplay_config cfg;
@@ -2610,6 +2628,12 @@ struct oz_arena {
     // oz_arena_set_opponent: who moves for the colour without a network ([0] BLACK, [1] WHITE)
     int opp_kind[2] = {OZ_AGENT_RANDOM, OZ_AGENT_RANDOM}, opp_depth[2] = {1, 1}, opp_eval[2] = {OZ_MINIMAX_EVAL_DISCS, OZ_MINIMAX_EVAL_DISCS};
     OzTimer opp_timer{1};        // k_arena_minimax_move, with oz_arena_profile on
+    // oz_arena_set_openings / oz_arena_set_opening_moves (the later call counts): 0 off, 1 random, 2 lists; the buffers are allocated by the setters
+    int open_mode = 0, open_plies = 0;
+    uint64_t open_seed = 0, open_first_id = 0;
+    uint8_t* d_open_moves = nullptr;      // [G][OZ_OPENING_MAX_PLIES], list mode
+    int32_t* d_open_n = nullptr;          // [G], list mode
+    int32_t* d_open_plies = nullptr;      // [G] plies the opening kernel played
 };
 
 // live games per mover: counts[0] = BLACK to move, counts[1] = WHITE to move (an agent with nothing to move this round is not launched)
@@ -2684,6 +2708,9 @@ OZ_API int oz_arena_destroy(oz_arena* a) {
     for (void* p : a->games.allocs) hipFree(p);
     mcts_destroy(a->games.m); mcts_destroy(a->mb);
     hipFree(a->d_actions); hipFree(a->d_players); hipFree(a->d_nmoves); hipFree(a->d_movers);
+    if (a->d_open_moves) hipFree(a->d_open_moves);
+    if (a->d_open_n) hipFree(a->d_open_n);
+    if (a->d_open_plies) hipFree(a->d_open_plies);
     a->opp_timer.destroy();
     delete a;
     return OZ_OK;
@@ -2812,6 +2839,71 @@ OZ_API int oz_arena_opponent_time(oz_arena* a, double* ms_total, int64_t* launch
     return OZ_OK;
 }
 
+// Openings (oz_openings.h): before the first run; plies == 0 / every n_plies == 0 plays nothing.  Random mode keeps three numbers; list mode
+// replays every list on the host through the same rules the kernel runs (they are OZ_HD) and refuses what is not a game, so the kernel has no
+// error path.
+static int arena_openings_buffers(oz_arena* a, bool lists) {
+    const int G = a->games.gm.G;
+    hipSetDevice(a->games.m->device);
+    if (!a->d_open_plies) {
+        OZ_HIP(hipMalloc((void**)&a->d_open_plies, 4ull * G));
+        OZ_HIP(hipMemset(a->d_open_plies, 0, 4ull * G));
+    }
+    if (lists && !a->d_open_moves) {
+        OZ_HIP(hipMalloc((void**)&a->d_open_moves, (size_t)G * OZ_OPENING_MAX_PLIES));
+        OZ_HIP(hipMalloc((void**)&a->d_open_n, 4ull * G));
+    }
+    return OZ_OK;
+}
+OZ_API int oz_arena_set_openings(oz_arena* a, int plies, uint64_t opening_seed, uint64_t first_opening_id) {
+    OZ_REQUIRE(a, "null arena");
+    OZ_REQUIRE(plies >= 0 && plies <= OZ_OPENING_MAX_PLIES, "oz_arena_set_openings: plies %d outside 0..%d", plies, OZ_OPENING_MAX_PLIES);
+    std::lock_guard<std::mutex> lk(a->mu);
+    if (a->started) { oz_set_error("oz_arena_set_openings: the arena has run already (set it before the first run)"); return OZ_ERR_STATE; }
+    if (plies > 0) if (int rc = arena_openings_buffers(a, false)) return rc;
+    a->open_mode = plies > 0 ? 1 : 0;
+    a->open_plies = plies; a->open_seed = opening_seed; a->open_first_id = first_opening_id;
+    return OZ_OK;
+}
+OZ_API int oz_arena_set_opening_moves(oz_arena* a, const uint8_t* moves, const int32_t* n_plies) {
+    OZ_REQUIRE(a && moves && n_plies, "null argument");
+    std::lock_guard<std::mutex> lk(a->mu);
+    if (a->started) { oz_set_error("oz_arena_set_opening_moves: the arena has run already (set it before the first run)"); return OZ_ERR_STATE; }
+    const GamesDev& gm = a->games.gm;
+    const int G = gm.G;
+    for (int g = 0; g < G; ++g) {
+        OZ_REQUIRE(n_plies[g] >= 0 && n_plies[g] <= OZ_OPENING_MAX_PLIES, "oz_arena_set_opening_moves: game %d: n_plies %d outside 0..%d", g, n_plies[g],
+                   OZ_OPENING_MAX_PLIES);
+        uint64_t black, white;
+        int player = 1, fin = 0;
+        oz_initial_board(gm.n, black, white);
+        for (int ply = 0; ply < n_plies[g]; ++ply) {
+            const int sq = moves[(size_t)g * OZ_OPENING_MAX_PLIES + ply];
+            OZ_REQUIRE(!fin, "oz_arena_set_opening_moves: game %d, ply %d: the game has ended before this move", g, ply);
+            const uint64_t legal = oz_legal(player == 1 ? black : white, player == 1 ? white : black, gm.valid);
+            OZ_REQUIRE(sq < 64 && ((legal >> sq) & 1), "oz_arena_set_opening_moves: game %d, ply %d: square %d is no legal move of %s", g, ply, sq,
+                       player == 1 ? "BLACK" : "WHITE");
+            oz_game_play(black, white, player, fin, sq, gm.valid);
+        }
+    }
+    if (int rc = arena_openings_buffers(a, true)) return rc;
+    OZ_HIP(hipMemcpy(a->d_open_moves, moves, (size_t)G * OZ_OPENING_MAX_PLIES, hipMemcpyHostToDevice));
+    OZ_HIP(hipMemcpy(a->d_open_n, n_plies, 4ull * G, hipMemcpyHostToDevice));
+    a->open_mode = 2;
+    return OZ_OK;
+}
+// plies the opening of every game played (zeros with openings off, and before the first run)
+OZ_API int oz_arena_opening_plies(oz_arena* a, int32_t* out) {
+    OZ_REQUIRE(a && out, "null argument");
+    std::lock_guard<std::mutex> lk(a->mu);
+    const int G = a->games.gm.G;
+    if (!a->d_open_plies) { memset(out, 0, 4ull * G); return OZ_OK; }
+    hipSetDevice(a->games.m->device);
+    OZ_HIP(hipStreamSynchronize(a->games.m->stream));
+    OZ_HIP(hipMemcpy(out, a->d_open_plies, 4ull * G, hipMemcpyDeviceToHost));
+    return OZ_OK;
+}
+
 // the move of the colour `side` that has no network: RandomOthelloAgent, or the minimax opponent oz_arena_set_opponent chose
 static void arena_opponent_move(oz_arena* a, int side, hipStream_t s) {
     const GamesDev& gm = a->games.gm;
@@ -2829,10 +2921,16 @@ OZ_API int oz_arena_run_rounds(oz_arena* a, int max_rounds_arg) {
     OZ_REQUIRE(a, "null arena");
     OZ_REQUIRE(max_rounds_arg >= 0, "oz_arena_run_rounds: max_rounds %d", max_rounds_arg);
     std::lock_guard<std::mutex> lk(a->mu);
+    const bool first_run = !a->started;
     a->started = true;
     oz_selfplay* sp = &a->games;
     oz_mcts *ma = sp->m, *mb = a->mb;
     hipSetDevice(ma->device);
+    if (first_run && a->open_mode) {     // the openings, once, ahead of the first round on the stream the rounds run on
+        const OpeningsDev op = {a->open_mode == 1 ? a->open_plies : 0, a->open_seed, a->open_first_id, a->open_mode == 2 ? a->d_open_moves : nullptr,
+                                a->d_open_n, a->d_open_plies};
+        hipLaunchKernelGGL(k_arena_openings, dim3((sp->gm.G + 255) / 256), dim3(256), 0, ma->stream, sp->gm, op);
+    }
     // (the caches as they are NOW: oz_net_set_eval_cache may have been called since the arena was created.  The two searches run one after
     //  the other on one stream, so even ONE network playing itself never has two users of its cache at a time.)
     ma->d.ec = (a->eval_cache && a->na && a->na->ec.buckets && a->na->ec.n2 == ma->d.n2) ? a->na->ec : EvalCacheDev();

@@ -122,11 +122,19 @@ def arena_sharded(net_a, net_b, board_size=8, total_games=512, num_simulations=8
     sorted by game id.  Replaces the reference's fan-out of duels over workers and the concatenation of their result lists
     (workers.py:168-184, main.py:196-214).  A game's moves depend on its global id only (RNG streams are keyed by it), never on the
     rank that played it: the pooled result equals one arena_batch of all the games.  `device`: where the gathered tensor lives
-    ("cuda" for the nccl = RCCL backend, "cpu" for gloo); extra keyword arguments go to arena_batch."""
+    ("cuda" for the nccl = RCCL backend, "cpu" for gloo); extra keyword arguments go to arena_batch.  With openings=(plies, opening_seed) a shard
+    adds its first game index to first_opening_id, and of opening_moves=(moves, n_plies) over all the games it takes its own rows: game k of the
+    match plays opening first_opening_id + k on whichever rank, and the pooled games equal the one-process arena's."""
+    from . import _lib
     from .agents import arena_batch
+    opening = _lib.check_openings(arena_kwargs.get("openings"), arena_kwargs.get("first_opening_id", 0), arena_kwargs.get("opening_moves"), total_games)
     rank = dist.get_rank(group) if dist.is_available() and dist.is_initialized() else 0
     world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
     first, count = shard_games(total_games, rank, world)
+    if opening is not None and opening[0] == "random":
+        arena_kwargs = dict(arena_kwargs, first_opening_id=(opening[3] + first) % 2 ** 64)
+    elif opening is not None:
+        arena_kwargs = dict(arena_kwargs, opening_moves=(opening[1][first:first + count], opening[2][first:first + count]))
     rows = np.zeros(count, dtype=ARENA_RESULT_DTYPE)
     failed = None
     if count:

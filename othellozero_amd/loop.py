@@ -135,23 +135,27 @@ def evaluate_against_random(board_size, neural_network, games, num_simulations, 
 
 
 def evaluate_against_random_batch(board_size, neural_network, games, num_simulations, degree_exploration, seed=0, leaves_per_step=1,
-                                  opponent=None, solve_leaves=0):
+                                  opponent=None, solve_leaves=0, openings=None):
     """The same evaluation as `evaluate_against_random` played in lock step on the GPU (agents.arena_batch with a random
     mover): the network takes BLACK in the first games // 2 + games % 2 games and WHITE in the rest (the reference draws the
     colours with random.shuffle; the split here is fixed).  opponent: arena_batch's (None / "random", or ("minimax", depth[, evaluation])).
     solve_leaves=E > 0: the network's search takes exact values for leaves with at most E empties (arena_batch).
+    openings=(plies, opening_seed): every game starts with a random opening (arena_batch); game k of the BLACK half and game k of the WHITE half
+    play opening k, so the network meets every opening from both sides (with an odd `games` the BLACK half has one opening more).
     -> dict(wins, black_wins, black_games, white_wins, white_games)"""
     _lib.check_opponent(opponent)
     solve_leaves = _lib.check_solve_leaves(solve_leaves)
+    _lib.check_openings(openings)
+    opening_kw = {"openings": openings, "first_opening_id": 0} if openings is not None else {}
     as_black, as_white = games // 2 + games % 2, games // 2
     r = dict(wins=0, black_wins=0, black_games=0, white_wins=0, white_games=0)
     if as_black:
         res = arena_batch(neural_network, None, board_size, as_black, num_simulations, degree_exploration, seed=seed,
-                          leaves_per_step=leaves_per_step, opponent=opponent, **({"solve_leaves": solve_leaves} if solve_leaves else {}))
+                          leaves_per_step=leaves_per_step, opponent=opponent, **({"solve_leaves": solve_leaves} if solve_leaves else {}), **opening_kw)
         r["black_wins"] = int((res["winner"] == 1).sum())
     if as_white:
         res = arena_batch(None, neural_network, board_size, as_white, num_simulations, degree_exploration, seed=seed, first_game_id=as_black,
-                          leaves_per_step=leaves_per_step, opponent=opponent, **({"solve_leaves": solve_leaves} if solve_leaves else {}))
+                          leaves_per_step=leaves_per_step, opponent=opponent, **({"solve_leaves": solve_leaves} if solve_leaves else {}), **opening_kw)
         r["white_wins"] = int((res["winner"] == -1).sum())
         r["black_games"] = as_white - r["white_wins"]              # games BLACK (the random agent) won
     r["white_games"] = r["white_wins"] + (as_black - r["black_wins"])
@@ -166,19 +170,81 @@ def evaluate_against_opponent(board_size, neural_network, games, num_simulations
 
 
 def evaluate_against_opponent_batch(board_size, neural_network, games, num_simulations, degree_exploration, opponent, seed=0, leaves_per_step=1,
-                                    solve_leaves=0):
+                                    solve_leaves=0, openings=None):
     """`evaluate_against_random_batch` under the name that says what it does when the opponent is not the random agent"""
     solve_leaves = _lib.check_solve_leaves(solve_leaves)
     return evaluate_against_random_batch(board_size, neural_network, games, num_simulations, degree_exploration, seed=seed,
-                                         leaves_per_step=leaves_per_step, opponent=opponent, **({"solve_leaves": solve_leaves} if solve_leaves else {}))
+                                         leaves_per_step=leaves_per_step, opponent=opponent, **({"solve_leaves": solve_leaves} if solve_leaves else {}),
+                                         **({"openings": openings} if openings is not None else {}))
+
+
+def _discs(boards):
+    return np.array([int(x).bit_count() for x in np.asarray(boards, dtype=np.uint64).ravel()], dtype=np.int64)
+
+
+def pair_statistics(new_black_final_black, new_black_final_white, old_black_final_black, old_black_final_white, opening_plies=None):
+    """The arithmetic of paired_match, on final boards alone (uint64 bitboards, one entry per pair): pair i is game i of the arena where the new
+    network was BLACK (first two arguments: its final black / white discs) and game i of the arena where the old one was BLACK (last two), both
+    begun with the same opening.  -> dict(
+      pairs,
+      wins        games to the new network by the reference's rule, where a drawn board goes to BLACK (get_winning_player): what self_play_match
+                  counts, so a draw is a win for whoever happened to hold BLACK;
+      wins_true, draws, losses   the 2 * pairs games by disc count, a drawn board counted as a draw;
+      margin      int64 (pairs, 2): the new network's discs minus the old one's, [:, 0] as BLACK, [:, 1] as WHITE;
+      pair_margin int64 (pairs,) = their sum: the opening's own advantage for BLACK cancels in it;
+      mean_margin, se   mean of pair_margin and its standard error over pairs, std(ddof=1) / sqrt(pairs) (nan with fewer than two pairs);
+      split_pairs pairs in which each network won one game: there the opening decided the games, not the networks;
+      opening_plies     as given (None if not).)"""
+    ab, aw, bb, bw = _discs(new_black_final_black), _discs(new_black_final_white), _discs(old_black_final_black), _discs(old_black_final_white)
+    if not ab.size == aw.size == bb.size == bw.size:
+        raise ValueError("pair_statistics: the four arrays hold one entry per pair each")
+    pairs = int(ab.size)
+    margin = np.stack([ab - aw, bw - bb], axis=1).reshape(pairs, 2)
+    pair_margin = margin.sum(axis=1)
+    return dict(pairs=pairs, wins=int((ab >= aw).sum() + (bw > bb).sum()), wins_true=int((margin > 0).sum()), draws=int((margin == 0).sum()),
+                losses=int((margin < 0).sum()), margin=margin, pair_margin=pair_margin,
+                mean_margin=float(pair_margin.mean()) if pairs else float("nan"),
+                se=float(pair_margin.std(ddof=1) / np.sqrt(pairs)) if pairs > 1 else float("nan"),
+                split_pairs=int((margin[:, 0] * margin[:, 1] < 0).sum()), opening_plies=opening_plies)
+
+
+def paired_match(board_size, neural_network, old_neural_network, pairs, num_simulations, degree_exploration, openings, seed=0, leaves_per_step=1,
+                 solve_leaves=0):
+    """A match over an opening suite, every opening played twice with the colours swapped -- NOT the reference's match (main.py:110-134 starts
+    every game from the standard position).  Two arenas of `pairs` games: the new network as BLACK against the old one, then the old one as
+    BLACK against the new; both get openings=(plies, opening_seed) and first_opening_id=0, so game i of either starts with opening i.  Game ids
+    are 0 .. pairs - 1 and pairs .. 2 pairs - 1, as in self_play_match.  -> pair_statistics' dict, plus games = the two arena_batch results."""
+    solve_leaves = _lib.check_solve_leaves(solve_leaves)
+    if openings is None:
+        raise ValueError("paired_match needs openings=(plies, opening_seed): without them every pair is the same two games")
+    _lib.check_openings(openings)
+    if isinstance(pairs, bool) or not isinstance(pairs, (int, np.integer)) or pairs < 1:
+        raise ValueError(f"paired_match: pairs must be a whole number >= 1 (got {pairs!r})")
+    kw = dict(leaves_per_step=leaves_per_step, openings=openings, first_opening_id=0, **({"solve_leaves": solve_leaves} if solve_leaves else {}))
+    a = arena_batch(neural_network, old_neural_network, board_size, int(pairs), num_simulations, degree_exploration, seed=seed, **kw)
+    b = arena_batch(old_neural_network, neural_network, board_size, int(pairs), num_simulations, degree_exploration, seed=seed,
+                    first_game_id=int(pairs), **kw)
+    assert np.array_equal(a["opening_plies"], b["opening_plies"])
+    return dict(pair_statistics(a["final_black"], a["final_white"], b["final_black"], b["final_white"], a["opening_plies"]), games=(a, b))
 
 
 def self_play_match(board_size, neural_network, old_neural_network, total_games, num_simulations, degree_exploration, seed=0,
-                    leaves_per_step=1, solve_leaves=0):
+                    leaves_per_step=1, solve_leaves=0, openings=None):
     """main.py:110-134: total_games // 2 games with the new network as BLACK, the rest with it as WHITE.
     -> number of games the new network won (a drawn game goes to BLACK, like get_winning_player).
-    solve_leaves=E > 0: both networks' searches take exact values for leaves with at most E empties (arena_batch)."""
+    solve_leaves=E > 0: both networks' searches take exact values for leaves with at most E empties (arena_batch).
+    openings=(plies, opening_seed): paired_match over total_games // 2 openings instead (total_games must be even: a pair is two games); the
+    return value is its `wins`, counted by the same rule, and self_play_match.stats holds its dict (None after a match without openings)."""
     solve_leaves = _lib.check_solve_leaves(solve_leaves)
+    self_play_match.stats = None
+    if openings is not None:
+        _lib.check_openings(openings)
+        if total_games % 2 or total_games < 2:
+            raise ValueError(f"self_play_match with openings plays pairs of games: total_games must be even and >= 2 (got {total_games})")
+        stats = paired_match(board_size, neural_network, old_neural_network, total_games // 2, num_simulations, degree_exploration, openings,
+                             seed=seed, leaves_per_step=leaves_per_step, solve_leaves=solve_leaves)
+        self_play_match.stats = {k: v for k, v in stats.items() if k != "games"}
+        return stats["wins"]
     as_black, as_white = total_games // 2, total_games // 2 + total_games % 2
     wins = 0
     if as_black:
@@ -224,7 +290,7 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
              seed=1234, reference_aliasing=True, alias_final_boards=True, dump_examples=False, q_mode=_lib.QMODE_F64,
              distributed=False, batched_evaluation=False, policy_target="onehot", target_temperature=1.0, leaves_per_step=1,
              root_noise=None, sample_moves=None, replay="host", evaluation_opponent="random", endgame_targets=0,
-             solve_leaves=0):
+             solve_leaves=0, match_openings=None, evaluation_openings=None):
     """main.py:56-259 on the GPU engines; returns `historic` = [(episodes done, win rate vs random), ...]
 
     batched_evaluation=True plays the evaluation games against RandomOthelloAgent in lock step on the GPU
@@ -278,8 +344,24 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
     reference has nothing like it.  training.rows_solved counts the self-play leaves solved.  The drop-in evaluation agents stay without it.
     Use 6: on an MI355X at 4 096 games of 8x8 the solving kernel then takes 0.11 ms of a 3.8 ms network batch (174 leaves solved per batch), inside
     the run-to-run spread of the search without it; 8 costs 0.53 ms (a fifth more per batch), 10 costs 5.2 ms and more than doubles the batch
-    (DESIGN.md, "Solved leaves"; tools/solve_leaves_bench.py, profiles/solve_leaves_bench.json)."""
+    (DESIGN.md, "Solved leaves"; tools/solve_leaves_bench.py, profiles/solve_leaves_bench.json).
+
+    match_openings=(plies, opening_seed) / evaluation_openings=(plies, opening_seed) (None = off, the default): the games of the new-vs-old
+    match / of the batched evaluation start with random openings of `plies` plies instead of the one standard position, every opening played
+    from both sides (self_play_match / evaluate_against_random_batch with openings=; DESIGN.md, "Openings").  At temperature 0 the reference's
+    match is a handful of distinct games; this is not the reference's match.  The promotion rules are the same: the match still returns games
+    won, counted the same way.  A match with openings also logs mean_margin +- se (discs per pair of games) and split_pairs, and
+    training.match_history keeps its dicts (paired_match).  self_play_total_games must then be even; evaluation_openings needs
+    batched_evaluation=True (the drop-in agents play one game at a time on the host, from the standard position).  With distributed=True every
+    rank plays the whole match, as without openings."""
     _lib.check_opponent(evaluation_opponent)
+    _lib.check_openings(match_openings)
+    _lib.check_openings(evaluation_openings)
+    if evaluation_openings is not None and not batched_evaluation:
+        raise ValueError("evaluation_openings needs batched_evaluation=True: the drop-in evaluation agents play from the standard position")
+    if match_openings is not None and self_play_training and (self_play_total_games % 2 or self_play_total_games < 2):
+        raise ValueError(f"match_openings plays pairs of games: self_play_total_games must be even and >= 2 (got {self_play_total_games})")
+    training.match_history = []
     solve_leaves = _lib.check_solve_leaves(solve_leaves)
     training.rows_solved = 0
     endgame_targets = _lib.check_endgame_targets(endgame_targets, alias_final_boards)
@@ -397,7 +479,13 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
             logging.info('[%d/%d] arena: trained network against the previous one', i, num_iterations)
             new_net_victories = self_play_match(board_size, neural_network, old_neural_network, self_play_total_games,
                                                 num_simulations, degree_exploration, seed=seed + i, leaves_per_step=leaves_per_step,
-                                                **({"solve_leaves": solve_leaves} if solve_leaves else {}))
+                                                **({"solve_leaves": solve_leaves} if solve_leaves else {}),
+                                                **({"openings": match_openings} if match_openings is not None else {}))
+            if match_openings is not None:
+                stats = self_play_match.stats
+                training.match_history.append(stats)
+                logging.info('[%d/%d] arena: mean_margin %+.2f +- %.2f discs per pair over %d openings, split_pairs %d', i, num_iterations,
+                             stats["mean_margin"], stats["se"], stats["pairs"], stats["split_pairs"])
             logging.info('[%d/%d] arena: %d of %d games to the trained network', i, num_iterations, new_net_victories, self_play_total_games)
             if new_net_victories >= self_play_threshold:
                 logging.info('[%d/%d] trained network promoted', i, num_iterations)
@@ -416,10 +504,12 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
             if batched_evaluation:
                 new = evaluate_against_random_batch(board_size, neural_network, evaluation_iterations, num_simulations,
                                                     degree_exploration, seed=seed + 7919 * i, leaves_per_step=leaves_per_step,
-                                                    opponent=evaluation_opponent, **({"solve_leaves": solve_leaves} if solve_leaves else {}))
+                                                    opponent=evaluation_opponent, **({"solve_leaves": solve_leaves} if solve_leaves else {}),
+                                                    **({"openings": evaluation_openings} if evaluation_openings is not None else {}))
                 old = evaluate_against_random_batch(board_size, old_neural_network, evaluation_iterations, num_simulations,
                                                     degree_exploration, seed=seed + 7919 * i + 1, leaves_per_step=leaves_per_step,
-                                                    opponent=evaluation_opponent, **({"solve_leaves": solve_leaves} if solve_leaves else {}))
+                                                    opponent=evaluation_opponent, **({"solve_leaves": solve_leaves} if solve_leaves else {}),
+                                                    **({"openings": evaluation_openings} if evaluation_openings is not None else {}))
             else:
                 new = evaluate_against_random(board_size, neural_network, evaluation_iterations, num_simulations, degree_exploration,
                                               label=f'after {total_episodes_done} episodes, current network', opponent=evaluation_opponent)

@@ -3,9 +3,12 @@
 With the device stub network the leaf evaluation costs nothing, so this times the TREE side alone -- select / compaction /
 expand / backup at 800 simulations per move, two search trees per game (one per agent, agents.py:44-68).
 
-    python tools/arena_bench.py [--games 512] [--sims 800] [--board 8] [--check 2] [--leaves-per-step 1]
+    python tools/arena_bench.py [--games 512] [--sims 800] [--board 8] [--check 2] [--leaves-per-step 1] [--openings PLIES]
 
-Prints one JSON line: simulations/s, games/s, and (--check k) the first k games re-played by the CPU oracle bit for bit."""
+Prints one JSON line: simulations/s, games/s, the share of expansions the networks really evaluated (cross-game de-duplication is on), the
+number of distinct move lists among the games, and (--check k) the first k games re-played by the CPU oracle bit for bit.
+--openings PLIES: every game starts with a random opening of PLIES plies (arena_batch(openings=(PLIES, --opening-seed))): the games stop
+sharing their boards, which is what de-duplication lives on (the oracle plays from the standard position only: no --check)."""
 import argparse
 import json
 import os
@@ -24,6 +27,8 @@ def main():
     ap.add_argument("--check", type=int, default=2)
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--leaves-per-step", type=int, default=1, help="descents per game and network batch under virtual loss (not the oracle's search order: no --check)")
+    ap.add_argument("--openings", type=int, default=0, help="plies of the random opening every game starts with (0 = the standard position)")
+    ap.add_argument("--opening-seed", type=int, default=1)
     args = ap.parse_args()
     import numpy as np
     from othellozero_amd import _lib
@@ -35,7 +40,8 @@ def main():
     best, r = None, None
     for rep in range(args.reps):                               # the first repetition also pays allocation / code load
         t0 = time.perf_counter()
-        r = arena_batch(a, b, n, G, args.sims, 1.0, seed=11, first_game_id=0, q_mode=1, leaves_per_step=args.leaves_per_step)
+        r = arena_batch(a, b, n, G, args.sims, 1.0, seed=11, first_game_id=0, q_mode=1, leaves_per_step=args.leaves_per_step,
+                        **({"openings": (args.openings, args.opening_seed)} if args.openings else {}))
         dt = time.perf_counter() - t0
         best = dt if best is None else min(best, dt)
     moves = int(r["n_moves"].sum())
@@ -43,7 +49,11 @@ def main():
            "seconds": best, "moves": moves, "simulations": moves * args.sims, "sims_per_s": moves * args.sims / best,
            "games_per_s": G / best, "moves_per_s": moves / best,
            "tree_side_hbm_GBps_at_1300B_per_sim": moves * args.sims * 1300 / best / 1e9}
-    if args.check and args.leaves_per_step == 1:
+    expansions = int(r["stats_black"][2] + r["stats_white"][2])
+    out.update(openings=args.openings, expansions=expansions, leaves_evaluated=int(r["leaves_evaluated"]),
+               leaves_evaluated_per_expansion=r["leaves_evaluated"] / max(expansions, 1),
+               distinct_move_lists=len({bytes(row[:k]) for row, k in zip(r["actions"], r["n_moves"])}))
+    if args.check and args.leaves_per_step == 1 and not args.openings:
         import oracle
         ok = 0
         for gi in range(args.check):
