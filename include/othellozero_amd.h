@@ -402,6 +402,27 @@ int oz_mcts_get_root_noise(oz_mcts* m, double* eta /* [num_games][64] */, uint8_
 int oz_mcts_sample_moves(oz_mcts* m, double temperature, uint64_t seed, const uint64_t* game_ids, const int32_t* plies,
                          int32_t* action /* [num_games], sq or -1 */, int32_t* rc /* [num_games] */);
 
+/* ---- playout cap: most self-play moves on a small simulation budget, a random share on the full one (opt-in, KataGo's playout cap
+ * randomization; off, every record stays bit for bit).  Most moves of a self-play game exist only to carry the game forward; only a fully
+ * searched move is worth a training example.  With the cap (fast_sims, full_prob), 2 <= fast_sims <= num_simulations, 0 < full_prob <= 1:
+ *     u      = the unit draw of the library's stream (seed, game id, ply, OZ_RNG_PLAYOUT = 6) -- stream 6 is none of 0 .. 5 and none of
+ *              the root-noise streams 3 + 256 sq + 65536 i
+ *     the searched self-play move of (game id, ply) is FULL iff u < full_prob; its budget is num_simulations when full, fast_sims otherwise
+ * The budget counts NEW simulations of that move, as num_simulations always did; the node tables persist across the moves of a game,
+ * unchanged.  ONE function, oz_playout_budget (csrc/oz_common.h), is what the kernels and oz_playout_budgets evaluate.
+ *   * the record of a fast move has pad[0] == 1, of a full move 0 (the first spare byte of oz_record; the layout does not change).  A fast
+ *     record is not a training example: oz_replay_append_selfplay / oz_replay_append_records leave it out, and so do the Python consumers.
+ *   * a fast move draws no root noise: its descents read the stored priors and oz_selfplay_root_noise reports its slot unarmed (noise
+ *     widens a policy target, and a fast move has none).  The e-greedy coin, the explore branch and move sampling are untouched, keyed by
+ *     ply as ever.
+ *   * full_prob == 1: every move is full and every flag 0 -- the bytes of the engine without the option.
+ *   * never touched: the arena, matches and evaluations, the bare oz_mcts, and the rounds of oz_selfplay_stagger (every slot plays at
+ *     sims_pre, flag 0, and is counted neither full nor fast). */
+/* the budgets of `count` (game id, ply) pairs, on the host (no device needed): out[i] = sims or fast_sims.  fast_sims == 0: off, every
+ * out[i] = sims.  OZ_ERR_ARG: sims < 2, fast_sims not 0 and outside [2, sims], full_prob outside (0, 1] (NaN included), a negative ply. */
+int oz_playout_budgets(uint64_t seed, const uint64_t* game_ids, const int32_t* plies, int64_t count, int sims, int fast_sims,
+                       double full_prob, int32_t* out /* [count] */);
+
 /* ------------------------------------------------------------------ self-play
  * execute_episode (training.py:26-72) for num_games concurrent games in lock step. */
 typedef struct oz_selfplay oz_selfplay;
@@ -444,7 +465,8 @@ typedef struct {
     int8_t z;               /* +1 if winner == mover else -1 (draw -> BLACK wins) */
     uint8_t greedy;         /* 1 = greedy branch of the coin (arg-max), 0 = explore branch (uniform legal move), 2 = greedy branch, move
                              * drawn by move sampling (oz_selfplay_set_move_sampling; ply < plies) */
-    uint8_t pad[3];
+    uint8_t pad[3];         /* pad[0]: 0 = the move was searched on the full budget, 1 = on the fast one ("playout cap" above: not a training
+                             * example); always 0 without the option.  pad[1], pad[2]: 0 */
 } oz_record;
 
 typedef struct {
@@ -495,6 +517,15 @@ int oz_selfplay_root_noise(oz_selfplay* sp, double* eta, uint8_t* armed);
  * oz_selfplay_run_steps (whose records stay exactly those of oz_selfplay_run), oz_selfplay_stagger and leaves_per_step > 1; the arena and the
  * evaluation games never sample.  Before the first driver call (OZ_ERR_STATE afterwards).  plies == 0 disarms; nothing is allocated. */
 int oz_selfplay_set_move_sampling(oz_selfplay* sp, double temperature, int plies);
+/* self-play under a playout cap ("playout cap" above), keyed (cfg.seed, game id, ply).  Holds for oz_selfplay_run at any leaves_per_step and
+ * for the free-running oz_selfplay_run_steps, whose records stay exactly those of oz_selfplay_run; oz_selfplay_stagger's rounds are not
+ * capped.  Before the first driver call (OZ_ERR_STATE afterwards).  fast_sims == 0 disarms (full_prob is then not looked at).  OZ_ERR_ARG:
+ * fast_sims not 0 and outside [2, cfg.sims], full_prob outside (0, 1] (NaN included).  The engine stays usable after a refusal.
+ * 64 B per slot of device memory at the first arming. */
+int oz_selfplay_set_playout_cap(oz_selfplay* sp, int fast_sims, double full_prob);
+/* what is set (fast_sims 0 = off) and the moves played under the cap so far: full_moves + fast_moves = the moves of oz_selfplay_run /
+ * oz_selfplay_run_steps since the cap was armed.  Every pointer may be NULL; reading a counter waits for the engine's stream. */
+int oz_selfplay_get_playout_cap(oz_selfplay* sp, int* fast_sims, double* full_prob, int64_t* full_moves, int64_t* fast_moves);
 int oz_selfplay_sync(oz_selfplay* sp);
 /* continuous self-play (cfg.refill): bring a fresh engine to the steady state of a long-running one before measuring it --
  * slot g is advanced (g * P) / num_games plies into its first game, P = n*n - 4, by searched self-play moves at `sims_pre`
@@ -752,6 +783,8 @@ int oz_trainer_step_count(oz_trainer* t, int64_t* step);
  * overwritten.  (NOT the reference's CircularArray + in-place random.shuffle, which overwrites random survivors; the host path keeps that.)
  * capacity need not be a multiple of 8: a record's examples may straddle the wrap.  An append of more than `capacity` examples keeps its last
  * `capacity`.
+ * Fast records: a record with pad[0] != 0 (a move searched on the fast budget of a playout cap) is not a training example and is left out of
+ * an append -- out of the order the host builds anyway; *appended_records, `total` and the kept-last-`capacity` rule count the kept records.
  * Errors, all OZ_ERR_ARG: a board size of the engine / trainer that differs from the buffer's; an object on another device; VISITS with
  * temperature <= 0, from an engine created without record_visits, or with counts == NULL; first_record < 0; an order index outside [0, held);
  * batch outside [1, max_batch]; alias_final not 0 / 1; an unknown target; capacity outside [1, 2^31 - 1]; a read beyond `held`.

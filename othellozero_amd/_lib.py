@@ -84,6 +84,27 @@ RECORD_DTYPE = np.dtype([
     ("ply", "u1"), ("action", "u1"), ("player", "i1"), ("z", "i1"), ("greedy", "u1"), ("pad", "u1", (3,)),
 ])
 assert RECORD_DTYPE.itemsize == 48
+RNG_PLAYOUT = 6                                                                      # OZ_RNG_PLAYOUT
+
+
+def record_fast(records):
+    """the playout-cap flag of move records (RECORD_DTYPE): uint8, 1 = the move was searched on the fast budget (no training example),
+    0 = on the full one; the first spare byte of oz_record, always 0 without the option"""
+    return np.asarray(records)["pad"][..., 0]
+
+
+def full_records(records, visits=None):
+    """the filter of the record consumers: (records, visits) without the fast records of a playout cap and their visit-count rows, order
+    kept; with no flag set the arguments come back as they are"""
+    rec = np.asarray(records)
+    keep = record_fast(rec) == 0
+    if keep.all():
+        return records, visits
+    if visits is not None:
+        cnt = np.asarray(visits).reshape(-1, 64)
+        assert cnt.shape[0] == rec.size, f"{cnt.shape[0]} visit-count rows for {rec.size} records"
+        visits = cnt[keep]
+    return rec[keep], visits
 
 _u64p, _i32p, _f32p, _f64p = (C.POINTER(t) for t in (C.c_uint64, C.c_int32, C.c_float, C.c_double))
 _u8p, _i8p, _i64p, _vp = C.POINTER(C.c_uint8), C.POINTER(C.c_int8), C.POINTER(C.c_int64), C.c_void_p
@@ -148,6 +169,9 @@ SIGNATURES = {
     "oz_selfplay_set_root_noise": [_vp, C.c_double, C.c_double], "oz_selfplay_root_noise": [_vp, _f64p, _u8p],
     "oz_mcts_sample_moves": [_vp, C.c_double, C.c_uint64, _u64p, _i32p, _i32p, _i32p],
     "oz_selfplay_set_move_sampling": [_vp, C.c_double, C.c_int],
+    "oz_selfplay_set_playout_cap": [_vp, C.c_int, C.c_double],
+    "oz_selfplay_get_playout_cap": [_vp, C.POINTER(C.c_int), _f64p, _i64p, _i64p],
+    "oz_playout_budgets": [C.c_uint64, _u64p, _i32p, C.c_int64, C.c_int, C.c_int, C.c_double, _i32p],
     "oz_selfplay_create": [C.POINTER(_vp), C.POINTER(SelfplayConfig), _vp],
     "oz_selfplay_destroy": [_vp], "oz_selfplay_run": [_vp, C.c_int], "oz_selfplay_run_steps": [_vp, C.c_int], "oz_selfplay_sync": [_vp],
     "oz_selfplay_stagger": [_vp, C.c_int], "oz_selfplay_profile": [_vp, C.c_int], "oz_selfplay_set_batch_cap": [_vp, C.c_int], "oz_selfplay_set_dedup": [_vp, C.c_int],
@@ -356,6 +380,40 @@ def check_sample_moves(sample_moves):
     if not 0 <= plies <= 64:
         raise ValueError(f"sample_moves: plies must be in [0, 64] (got {plies})")
     return temperature, plies
+
+
+def check_playout_cap(playout_cap, num_simulations=None):
+    """playout_cap = None or (fast_sims, full_prob): a searched self-play move runs num_simulations simulations with probability full_prob and
+    fast_sims otherwise, and only the fully searched moves become training examples (oz_selfplay_set_playout_cap).  Returns None or
+    (int, float); ValueError for anything the library would refuse: fast_sims a whole number in [2, num_simulations] (the upper bound is
+    checked where num_simulations is given), full_prob in (0, 1]."""
+    if playout_cap is None:
+        return None
+    try:
+        fast_sims, full_prob = playout_cap
+        if isinstance(fast_sims, bool) or int(fast_sims) != fast_sims:
+            raise ValueError
+        fast_sims, full_prob = int(fast_sims), float(full_prob)
+    except (TypeError, ValueError):
+        raise ValueError(f"playout_cap must be None or (fast_sims, full_prob), got {playout_cap!r}") from None
+    if fast_sims < 2 or (num_simulations is not None and fast_sims > num_simulations):
+        raise ValueError(f"playout_cap: fast_sims must be in [2, num_simulations{'' if num_simulations is None else ' = %d' % num_simulations}] "
+                         f"(got {fast_sims})")
+    if not 0.0 < full_prob <= 1.0:
+        raise ValueError(f"playout_cap: full_prob must be in (0, 1] (got {full_prob})")
+    return fast_sims, full_prob
+
+
+def playout_budgets(seed, game_ids, plies, num_simulations, playout_cap):
+    """oz_playout_budgets: the simulation budgets (int32) of the searched self-play moves (game_ids[i], plies[i]) under playout_cap --
+    num_simulations for a full move, fast_sims for a fast one; the function the kernels evaluate, run on the host (no GPU needed)"""
+    cap = check_playout_cap(playout_cap, num_simulations) or (0, 1.0)
+    ids = np.ascontiguousarray(game_ids, dtype=np.uint64).ravel()
+    ply = np.ascontiguousarray(plies, dtype=np.int32).ravel()
+    assert ids.size == ply.size, (ids.size, ply.size)
+    out = np.zeros(ids.size, np.int32)
+    check(load().oz_playout_budgets(int(seed), p_u64(ids), p_i32(ply), ids.size, int(num_simulations), cap[0], cap[1], p_i32(out)))
+    return out
 
 
 def check_minimax(depth, evaluation):

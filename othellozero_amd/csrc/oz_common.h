@@ -24,10 +24,10 @@ OZ_HD uint64_t oz_sm64(uint64_t z) {
 }
 OZ_HD uint64_t oz_rotl64(uint64_t x, int r) { return (x << r) | (x >> (64 - r)); }
 
-enum { OZ_RNG_COIN = 0, OZ_RNG_EXPLORE = 1, OZ_RNG_TIE = 2, OZ_RNG_NOISE = 3, OZ_RNG_SAMPLE = 4, OZ_RNG_OPENING = 5 };
+enum { OZ_RNG_COIN = 0, OZ_RNG_EXPLORE = 1, OZ_RNG_TIE = 2, OZ_RNG_NOISE = 3, OZ_RNG_SAMPLE = 4, OZ_RNG_OPENING = 5, OZ_RNG_PLAYOUT = 6 };
 // NOISE: stream 3 + 256 * square + 65536 * draw (root noise, oz_search.hip); SAMPLE: the one unit draw of a sampled move (move sampling,
 // oz_search.hip) -- 4 is none of 3 + 256 sq + 65536 i; OPENING: the move of an opening ply, keyed (opening seed, opening id, ply)
-// (oz_openings.h) -- nor is 5
+// (oz_openings.h) -- nor is 5; PLAYOUT: the full / fast draw of a self-play move (playout cap, oz_playout_budget below) -- nor is 6
 // counter-based stream replacing random.random / np.random.choice / random.choice
 // (training.py:51,56; othelo_mcts.py:59): keyed (seed, global game id, ply, purpose)
 OZ_HD uint64_t oz_rng(uint64_t seed, uint64_t game, uint64_t move, uint64_t stream) {
@@ -35,6 +35,16 @@ OZ_HD uint64_t oz_rng(uint64_t seed, uint64_t game, uint64_t move, uint64_t stre
     return oz_sm64(a ^ (move * 0x9E3779B97F4A7C15ULL) ^ (stream * 0xD1B54A32D192ED03ULL));
 }
 OZ_HD double oz_rng_unit(uint64_t u) { return (double)(u >> 11) * (1.0 / 9007199254740992.0); }
+
+// playout cap (include/othellozero_amd.h, "playout cap"): the simulation budget of the searched self-play move of game `game` at ply `ply`.
+// The move is FULL iff u < full_prob, u = the unit draw of stream (seed, game, ply, OZ_RNG_PLAYOUT): `sims` simulations, *fast = 0; otherwise
+// `fast_sims` simulations, *fast = 1.  fast_sims == 0 is the option switched off: every move is full.  The one definition the kernels
+// (oz_search.hip) and the host's oz_playout_budgets share.
+OZ_HD int oz_playout_budget(uint64_t seed, uint64_t game, uint64_t ply, int sims, int fast_sims, double full_prob, int* fast) {
+    const int f = fast_sims > 0 && !(oz_rng_unit(oz_rng(seed, game, ply, OZ_RNG_PLAYOUT)) < full_prob) ? 1 : 0;
+    *fast = f;
+    return f ? fast_sims : sims;
+}
 
 OZ_HD uint64_t oz_stub_h(uint64_t own, uint64_t opp, uint64_t salt, uint64_t i) {
     return oz_sm64(oz_sm64(own ^ salt) ^ oz_rotl64(opp, 29) ^ ((i + 1) * 0xD6E8FEB86659FD93ULL));

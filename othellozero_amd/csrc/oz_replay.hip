@@ -154,10 +154,18 @@ template <int N> static void replay_launch(oz_replay* r, int64_t count, int alia
                            (long long)r->total, skip, (long long)r->capacity, r->own, r->opp, r->pi, r->z);
 }
 
-// the staged records [first, first + count) of r->st_rec (host copy: h[0 .. count)) -> 8 examples each, in ascending (game_id, ply)
-static int replay_append_staged(oz_replay* r, const oz_record* h, int64_t first, int64_t count, int alias_final, int target, double temperature) {
-    std::vector<int32_t> perm((size_t)count);
-    std::iota(perm.begin(), perm.end(), 0);
+// the staged records [first, first + count) of r->st_rec (host copy: h[0 .. count)) -> 8 examples each, in ascending (game_id, ply).  The fast
+// records of a playout cap (pad[0] != 0) are no training examples: they stay out of the permutation, so the kernel never sees them;
+// *kept = the records appended.
+static int replay_append_staged(oz_replay* r, const oz_record* h, int64_t first, int64_t staged, int alias_final, int target, double temperature,
+                                int64_t* kept) {
+    std::vector<int32_t> perm;
+    perm.reserve((size_t)staged);
+    for (int64_t i = 0; i < staged; ++i)
+        if (h[i].pad[0] == 0) perm.push_back((int32_t)i);
+    const int64_t count = (int64_t)perm.size();
+    *kept = count;
+    if (count == 0) return OZ_OK;
     std::stable_sort(perm.begin(), perm.end(), [h](int32_t a, int32_t b) {
         return h[a].game_id != h[b].game_id ? h[a].game_id < h[b].game_id : h[a].ply < h[b].ply;
     });
@@ -210,8 +218,9 @@ OZ_API int oz_replay_append_selfplay(oz_replay* r, oz_selfplay* sp, int64_t firs
     std::vector<oz_record> h((size_t)count);     // 48 B per record: 2 % of the example bytes; the examples never leave the device
     OZ_HIP(hipMemcpyAsync(h.data(), r->st_rec + first_record, sizeof(oz_record) * count, hipMemcpyDeviceToHost, r->s));
     OZ_HIP(hipStreamSynchronize(r->s));
-    if (int rc = replay_append_staged(r, h.data(), first_record, count, alias_final, target, temperature)) return rc;
-    if (appended_records) *appended_records = count;
+    int64_t kept = 0;
+    if (int rc = replay_append_staged(r, h.data(), first_record, count, alias_final, target, temperature, &kept)) return rc;
+    if (appended_records) *appended_records = kept;
     return OZ_OK;
 }
 
@@ -229,7 +238,12 @@ OZ_API int oz_replay_append_records(oz_replay* r, const oz_record* records, cons
     if (int rc = replay_reserve(r, count, visits ? count : 0)) return rc;
     OZ_HIP(hipMemcpyAsync(r->st_rec, records, sizeof(oz_record) * count, hipMemcpyHostToDevice, r->s));
     if (visits) OZ_HIP(hipMemcpyAsync(r->st_cnt, counts, sizeof(int32_t) * 64 * count, hipMemcpyHostToDevice, r->s));
-    return replay_append_staged(r, records, 0, count, alias_final, target, temperature);
+    int64_t kept = 0;
+    const int rc = replay_append_staged(r, records, 0, count, alias_final, target, temperature, &kept);
+    const hipError_t es = hipStreamSynchronize(r->s);          // (nothing kept: no launch waited for the uploads, and the caller's arrays may go away)
+    if (rc) return rc;
+    OZ_HIP(es);
+    return OZ_OK;
 }
 
 // `count` rows of `width` bytes from the host into the ring at running index `k0` (count <= capacity): at most two pieces

@@ -269,6 +269,17 @@ template <bool NOISE> __device__ __forceinline__ bool noise_of_slot(const MctsDe
 //     r = u * c_total;  action = the first legal square with cum[sq] > r, else (u * c rounded up to c) the last legal square with w > 0
 // A square with N == 0 adds 0.0 and its cum equals its predecessor's: never chosen.  -1: no visited legal square (the callers exclude it).
 struct MoveSampling { double temperature; int plies; };    // plies == 0: off
+// ---------------------------------------------------------------- playout cap: most self-play moves on a small budget, a random share on the full one (opt-in, KataGo's)
+// (the definition is stated in include/othellozero_amd.h, "playout cap"; the restatement the tests hold this against is tests/playout_cap_ref.py.)
+// The budget of the searched move of (game id, ply) is oz_playout_budget (oz_common.h): a function of the key alone, so every kernel that needs
+// it -- the budget, the noise decision, the flag of the move -- evaluates it again (two integer mixes and one compare per wave) instead of
+// carrying a per-slot state.  A fast move draws no root noise, and its record carries flag 1 in the first spare byte.
+struct PlayoutCap {
+    int fast_sims;                  // 0: off
+    double full_prob;
+    uint8_t* log_fast;              // [G][64] the flag of every ply of the game in progress, next to GamesDev.log_greedy
+    unsigned long long* moves;      // [0] full moves [1] fast moves played under the cap
+};
 __device__ __forceinline__ double lane_get_f64(double x, int lane) {      // lane must be uniform
     const long long b = __double_as_longlong(x);
     const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)b, lane), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(b >> 32), lane);
@@ -965,6 +976,45 @@ __global__ void k_wide_begin(MctsDev t, WideDev w, int nsims) {
     w.left[g] = t.active[g] ? nsims : 0;
     w.count[g] = 0;
 }
+// the keys a lock-step round under a playout cap evaluates oz_playout_budget with: the slots' (game id, ply) and the engine's seed
+struct CapKeys { PlayoutCap pc; uint64_t seed; const uint64_t* game_id; const int* ply; };
+__device__ __forceinline__ int cap_budget(const CapKeys& ck, int g, int nsims, int* fast) {
+    return oz_playout_budget(ck.seed, ck.game_id[g], (uint64_t)ck.ply[g], nsims, ck.pc.fast_sims, ck.pc.full_prob, fast);
+}
+// k_wide_begin under a playout cap: every game's own budget (mcts_wide_steps runs until the largest remaining one is zero)
+__global__ void k_wide_begin_c(MctsDev t, WideDev w, int nsims, CapKeys ck) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= t.G) return;
+    int fast;
+    w.left[g] = t.active[g] ? cap_budget(ck, g, nsims, &fast) : 0;
+    w.count[g] = 0;
+}
+// one-descent-per-step rounds under a playout cap: after the first fast_sims simulations the slots whose move is fast sit out the rest (an
+// inactive slot descends nowhere and backs nothing up, as in a staggered round); k_cap_resume brings them back for the move (a round under
+// the cap is never a staggered one: every live game takes part, so "live" is "active")
+__global__ void k_cap_park(MctsDev t, CapKeys ck) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= t.G || !t.active[g]) return;
+    int fast;
+    cap_budget(ck, g, 0, &fast);
+    if (fast) t.active[g] = 0;
+}
+__global__ void k_cap_resume(MctsDev t, const uint8_t* __restrict__ finished) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g < t.G) t.active[g] = finished[g] ? 0 : 1;
+}
+// k_root_noise under a playout cap: the full moves draw, a fast move's slot stays disarmed (its descents read the stored priors)
+__global__ __launch_bounds__(64) void k_root_noise_c(MctsDev t, double alpha, CapKeys ck) {
+    __shared__ double arr[64];
+    const int g = blockIdx.x, lane = threadIdx.x;
+    int fast = 0;
+    if (t.active[g]) cap_budget(ck, g, 0, &fast);
+    if (!t.active[g] || unii(fast)) {
+        if (lane == 0) t.noise_armed[g] = 0;
+        return;
+    }
+    root_noise_body(t, arr, g, lane, uni64(t.root_own[g]), uni64(t.root_opp[g]), alpha, ck.seed, uni64(ck.game_id[g]), unii(ck.ply[g]));
+}
 __global__ void k_wide_left(MctsDev t, WideDev w) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     const int left = g < t.G ? w.left[g] : 0;
@@ -1201,7 +1251,7 @@ static int wide_set_k(oz_mcts* m, int k) {
 // host round trip (descents | compaction | evaluator, the previous step's expand + backup fused with the next step's descents, one closing
 // expand + backup), then the largest remaining budget is read back (4 bytes) and further steps follow until it is zero (steps cut short by
 // a collision leave a remainder).  max_games = an upper bound of the active games: the evaluator is launched for max_games * K leaves.
-static int mcts_wide_steps(oz_mcts* m, oz_net* net, int nsims, int max_games, bool time_eval) {
+static int mcts_wide_steps(oz_mcts* m, oz_net* net, int nsims, int max_games, bool time_eval, const CapKeys* ck = nullptr) {
     MctsDev& d = m->d;
     if (int rc = wide_alloc(m)) return rc;
     WideDev w = m->w;
@@ -1210,7 +1260,8 @@ static int mcts_wide_steps(oz_mcts* m, oz_net* net, int nsims, int max_games, bo
     const bool all = m->profile;
     const int cap = max_games * w.K;
     const dim3 gg((unsigned)((d.G + 255) / 256));
-    hipLaunchKernelGGL(k_wide_begin, gg, dim3(256), 0, s, d, w, nsims);
+    if (ck) hipLaunchKernelGGL(k_wide_begin_c, gg, dim3(256), 0, s, d, w, nsims, *ck);       // a playout cap: every game's own budget (<= nsims)
+    else hipLaunchKernelGGL(k_wide_begin, gg, dim3(256), 0, s, d, w, nsims);
     int steps = (nsims + w.K - 1) / w.K;
     long long enqueued = 0;                                     // every step runs >= 1 simulation of every game with budget left: <= nsims steps in all
     while (steps > 0) {
@@ -1250,8 +1301,8 @@ static int mcts_collect_eval_time(oz_mcts* m) {
 // then per further simulation the previous one's expand + backup fused with the next descent (k_backup_select), and one closing expand +
 // backup: nsims + 1 tree launches instead of 2 nsims (results are identical to the unfused sequence, which oz_mcts_select / oz_mcts_backup
 // still run).  nsims <= 0 launches nothing: the closing expand + backup would run over the leaf_status of an earlier call.
-static int mcts_steps_async(oz_mcts* m, oz_net* net, int nsims, int max_games, bool time_eval) {
-    if (m->wide()) return mcts_wide_steps(m, net, nsims, max_games, time_eval);
+static int mcts_steps_async(oz_mcts* m, oz_net* net, int nsims, int max_games, bool time_eval, const CapKeys* ck = nullptr) {
+    if (m->wide()) return mcts_wide_steps(m, net, nsims, max_games, time_eval, ck);
     if (nsims <= 0) return OZ_OK;
     MctsDev& d = m->d;
     hipStream_t s = m->stream;
@@ -1840,8 +1891,12 @@ __global__ void k_sp_roots_stagger(GamesDev gm, MctsDev t, int round, int period
 // reads them in between).  (noise_armed is null on an engine whose only extra is move sampling.)
 // SAMPLE (an engine with move sampling, oz_selfplay_set_move_sampling): where the coin falls on the greedy branch and ply < ms.plies, the move is
 // drawn by sample_move, keyed (seed, game id, ply), instead of taken as the arg-max; greedy = 2 in its record.  Never in the arena.
-template <bool NOISE = false, bool SAMPLE = false>
-__device__ __forceinline__ void sp_move_body(const GamesDev& gm, const MctsDev& t, int g, int lane, int arena, MoveSampling ms = MoveSampling{}) {
+// CAP (an engine with a playout cap, oz_selfplay_set_playout_cap; pc.fast_sims > 0 where it is on): the move's full / fast bit, oz_playout_budget
+// of (seed, game id, ply), goes into the move log next to `greedy` and from there into byte pad[0] of the game's records; one of two counters
+// counts the move.  The move rule itself does not look at the bit.  Never in the arena, never in a staggered round.
+template <bool NOISE = false, bool SAMPLE = false, bool CAP = false>
+__device__ __forceinline__ void sp_move_body(const GamesDev& gm, const MctsDev& t, int g, int lane, int arena, MoveSampling ms = MoveSampling{},
+                                             PlayoutCap pc = PlayoutCap{}) {
     if (!t.active[g]) return;
     if constexpr (NOISE) { if (lane == 0 && t.noise_armed) t.noise_armed[g] = 0; }
     const uint64_t own = uni64(t.root_own[g]), opp = uni64(t.root_opp[g]);
@@ -1888,6 +1943,17 @@ __device__ __forceinline__ void sp_move_body(const GamesDev& gm, const MctsDev& 
         gm.log_action[lb + ply] = (uint8_t)action; gm.log_player[lb + ply] = (int8_t)player;
         gm.log_greedy[lb + ply] = (uint8_t)greedy;
     }
+    int fast = 0;
+    (void)fast;
+    if constexpr (CAP) {
+        if (pc.fast_sims > 0) {
+            oz_playout_budget(gm.seed, gid, (uint64_t)ply, 0, pc.fast_sims, pc.full_prob, &fast);
+            if (lane == 0) {
+                if (ply < 64) pc.log_fast[lb + ply] = (uint8_t)fast;
+                atomicAdd(&pc.moves[fast], 1ULL);
+            }
+        }
+    }
     oz_game_play(black, white, player, fin, action, gm.valid);
     const int nply = ply + 1;
     if (fin) {
@@ -1911,6 +1977,7 @@ __device__ __forceinline__ void sp_move_body(const GamesDev& gm, const MctsDev& 
                 r.z = (int8_t)(winner == r.player ? 1 : -1);
                 r.greedy = cur ? (uint8_t)greedy : gm.log_greedy[lb + lane];
                 r.pad[0] = r.pad[1] = r.pad[2] = 0;
+                if constexpr (CAP) { if (pc.fast_sims > 0) r.pad[0] = cur ? (uint8_t)fast : pc.log_fast[lb + lane]; }
                 gm.records[base + lane] = r;
             } else atomicOr(t.error_flag, EF_RECORDS);
         }
@@ -1942,6 +2009,10 @@ __device__ __forceinline__ void sp_move_body(const GamesDev& gm, const MctsDev& 
 __global__ __launch_bounds__(64) void k_sp_move(GamesDev gm, MctsDev t, int arena) { sp_move_body(gm, t, blockIdx.x, threadIdx.x, arena); }
 // the self-play move of an engine with move sampling (lock-step rounds; the arena keeps k_sp_move)
 __global__ __launch_bounds__(64) void k_sp_move_s(GamesDev gm, MctsDev t, MoveSampling ms) { sp_move_body<false, true>(gm, t, blockIdx.x, threadIdx.x, 0, ms); }
+// the self-play move of a lock-step round under a playout cap (with or without move sampling: ms.plies says)
+__global__ __launch_bounds__(64) void k_sp_move_c(GamesDev gm, MctsDev t, MoveSampling ms, PlayoutCap pc) {
+    sp_move_body<false, true, true>(gm, t, blockIdx.x, threadIdx.x, 0, ms, pc);
+}
 
 // ---------------------------------------------------------------- free-running self-play step
 // The lock-step driver gives every game one simulation per step; simulations that end on a finished board need no
@@ -1958,12 +2029,16 @@ __global__ __launch_bounds__(64) void k_sp_move_s(GamesDev gm, MctsDev t, MoveSa
 // (bench.py --driver free): cap 24 -> 4081 leaves per batch but 367 us per launch, 1.40 M expansions/s; cap 8 -> 1.56 M;
 // cap 4 -> 1.585 M; cap 2 -> 3908 leaves per batch, 1.59 M (1.60 M with k_backup_advance; the lock-step driver: 1.56-1.58 M).
 #define OZ_ADVANCE_CAP 2
-// EXTRAS: the one instantiation for engines with root noise, move sampling or both; which of them is on is looked at when it runs
-// (t.noise_eps > 0, xt.sample.plies > 0).  An engine with neither launches the EXTRAS = false kernels, which are the code they were before.
+// EXTRAS: the one instantiation for engines with root noise, move sampling, a playout cap or any of them together; which of them is on is looked
+// at when it runs (t.noise_eps > 0, xt.sample.plies > 0, xt.cap.fast_sims > 0).  An engine with none launches the EXTRAS = false kernels, which
+// are the code they were before.
+//   playout cap: the move is played once `done` reaches the budget of the slot's current (game id, ply) instead of `sims`; a fast root draws no
+//   noise.  Both are oz_playout_budget of the key, evaluated again at every pass of the loop: noise_armed[g] == 0 keeps meaning "no noise on this
+//   root" and needs no third state for "decided: none", and a fast root stays unarmed for oz_selfplay_root_noise to report.
 //   root noise: the noise of a game's root is drawn here, before the first descent from it (noise_armed[g] == 0: a fresh engine, or the move above
 //   has just changed the root), keyed (seed, game id, ply) like k_root_noise in the lock-step round: the records stay those of oz_selfplay_run.
 //   move sampling: sp_move_body<.., SAMPLE> is a function of the root's counts and (seed, game id, ply): the same records again.
-struct SelfplayExtras { double alpha; uint64_t seed; MoveSampling sample; };
+struct SelfplayExtras { double alpha; uint64_t seed; MoveSampling sample; PlayoutCap cap; };
 template <bool EXTRAS = false>
 __device__ __forceinline__ void advance_body(const GamesDev& gm, const MctsDev& t, TreeLds& L, int g, int lane, int sims, int* __restrict__ sims_done, int cap,
                                              SelfplayExtras xt = SelfplayExtras{}) {
@@ -1984,15 +2059,20 @@ __device__ __forceinline__ void advance_body(const GamesDev& gm, const MctsDev& 
             t.root_opp[g] = p == 1 ? gm.white[g] : gm.black[g];
         }
         wave_sync();                                       // lane 0's stores are visible to the wave's next loads
-        if (done >= sims) {                                // training.py:42-67: the move after num_simulations simulations
-            sp_move_body<EXTRAS, EXTRAS>(gm, t, g, lane, 0, xt.sample);
+        int budget = sims, fast = 0;
+        if constexpr (EXTRAS) {
+            if (xt.cap.fast_sims > 0)
+                budget = oz_playout_budget(gm.seed, uni64(gm.game_id[g]), (uint64_t)unii(gm.ply[g]), sims, xt.cap.fast_sims, xt.cap.full_prob, &fast);
+        }
+        if (done >= budget) {                              // training.py:42-67: the move after num_simulations simulations
+            sp_move_body<EXTRAS, EXTRAS, EXTRAS>(gm, t, g, lane, 0, xt.sample, xt.cap);
             done = 0;
             if (lane == 0) t.leaf_status[g] = OZ_LEAF_IDLE;    // the evaluated leaf is consumed: nothing pending if the cap ends the loop here
             wave_sync();
             continue;                                      // (a finished game is refilled by the move, or goes idle above)
         }
         if constexpr (EXTRAS) {
-            if (t.noise_eps > 0.0 && unii((int)t.noise_armed[g]) == 0) {
+            if (t.noise_eps > 0.0 && !fast && unii((int)t.noise_armed[g]) == 0) {
                 root_noise_body(t, L.arr, g, lane, uni64(t.root_own[g]), uni64(t.root_opp[g]), xt.alpha, xt.seed, uni64(gm.game_id[g]), unii(gm.ply[g]));
                 wave_sync();
             }
@@ -2115,6 +2195,7 @@ struct oz_selfplay {
     bool noise_on = false;           // oz_selfplay_set_root_noise: every searched move draws Dir(noise_alpha) at its root
     double noise_alpha = 0.0;
     MoveSampling sample{0.0, 0};     // oz_selfplay_set_move_sampling: plies > 0 = on
+    PlayoutCap cap{0, 0.0, nullptr, nullptr};      // oz_selfplay_set_playout_cap: fast_sims > 0 = on (the buffers stay once allocated)
     std::vector<void*> allocs;
     std::mutex mu;
     long long records_read = 0;
@@ -2221,14 +2302,30 @@ static int selfplay_round_async(oz_selfplay* sp, int sims, int stagger_round) {
     oz_mcts* m = sp->m;
     const int G = sp->gm.G;
     hipStream_t s = m->stream;
+    // a playout cap holds for the rounds of oz_selfplay_run; a staggered round plays every slot at `sims`, flag 0, through the kernels it always ran
+    const bool capped = sp->cap.fast_sims > 0 && stagger_round < 0;
+    const CapKeys ck{sp->cap, sp->gm.seed, (const uint64_t*)sp->gm.game_id, (const int*)sp->gm.ply};
+    const dim3 gg((unsigned)((G + 255) / 256));
     timed(m, TS_MOVE, m->profile, [&] {
-        if (stagger_round >= 0) hipLaunchKernelGGL(k_sp_roots_stagger, dim3((G + 255) / 256), dim3(256), 0, s, sp->gm, m->d, stagger_round, sp->stagger_period);
-        else hipLaunchKernelGGL(k_sp_roots, dim3((G + 255) / 256), dim3(256), 0, s, sp->gm, m->d, 0);
-        if (sp->noise_on) hipLaunchKernelGGL(k_root_noise, dim3(G), dim3(64), 0, s, m->d, sp->noise_alpha, sp->gm.seed, (const uint64_t*)sp->gm.game_id, (const int*)sp->gm.ply);
+        if (stagger_round >= 0) hipLaunchKernelGGL(k_sp_roots_stagger, gg, dim3(256), 0, s, sp->gm, m->d, stagger_round, sp->stagger_period);
+        else hipLaunchKernelGGL(k_sp_roots, gg, dim3(256), 0, s, sp->gm, m->d, 0);
+        if (sp->noise_on && capped) hipLaunchKernelGGL(k_root_noise_c, dim3(G), dim3(64), 0, s, m->d, sp->noise_alpha, ck);
+        else if (sp->noise_on) hipLaunchKernelGGL(k_root_noise, dim3(G), dim3(64), 0, s, m->d, sp->noise_alpha, sp->gm.seed, (const uint64_t*)sp->gm.game_id, (const int*)sp->gm.ply);
     });
-    if (int rc = mcts_steps_async(m, sp->net, sims, G, true)) return rc;
+    if (capped && !m->wide()) {
+        // one descent per step: the first fast_sims simulations for every game, the rest for the games whose move is full.  A game's own
+        // sequence of simulations does not depend on where the call is split, nor on who else is active.
+        const int fs = sp->cap.fast_sims;
+        if (int rc = mcts_steps_async(m, sp->net, fs, G, true)) return rc;
+        if (sims > fs) {
+            hipLaunchKernelGGL(k_cap_park, gg, dim3(256), 0, s, m->d, ck);
+            if (int rc = mcts_steps_async(m, sp->net, sims - fs, G, true)) return rc;
+            hipLaunchKernelGGL(k_cap_resume, gg, dim3(256), 0, s, m->d, (const uint8_t*)sp->gm.finished);
+        }
+    } else if (int rc = mcts_steps_async(m, sp->net, sims, G, true, capped ? &ck : nullptr)) return rc;
     timed(m, TS_MOVE, m->profile, [&] {
-        if (sp->sample.plies > 0) hipLaunchKernelGGL(k_sp_move_s, dim3(G), dim3(64), 0, s, sp->gm, m->d, sp->sample);
+        if (capped) hipLaunchKernelGGL(k_sp_move_c, dim3(G), dim3(64), 0, s, sp->gm, m->d, sp->sample, sp->cap);
+        else if (sp->sample.plies > 0) hipLaunchKernelGGL(k_sp_move_s, dim3(G), dim3(64), 0, s, sp->gm, m->d, sp->sample);
         else hipLaunchKernelGGL(k_sp_move, dim3(G), dim3(64), 0, s, sp->gm, m->d, 0);
     });
     OZ_HIP(hipGetLastError());
@@ -2355,6 +2452,71 @@ OZ_API int oz_selfplay_set_move_sampling(oz_selfplay* sp, double temperature, in
     sp->sample = MoveSampling{plies > 0 ? temperature : 0.0, plies};
     return OZ_OK;
 }
+// playout cap for the self-play moves of the engine (oz_selfplay_run at any leaves_per_step and the free-running driver; oz_selfplay_stagger's
+// rounds stay at sims_pre, flag 0); before the first driver call.  fast_sims == 0 disarms.  64 B per slot at the first arming.
+OZ_API int oz_selfplay_set_playout_cap(oz_selfplay* sp, int fast_sims, double full_prob) {
+    OZ_REQUIRE(sp, "null selfplay");
+    if (fast_sims != 0) {
+        OZ_REQUIRE(fast_sims >= 2 && fast_sims <= sp->cfg.sims, "oz_selfplay_set_playout_cap: fast_sims %d outside [2, num_simulations = %d] (0 = off)", fast_sims,
+                   sp->cfg.sims);
+        OZ_REQUIRE(full_prob > 0.0 && full_prob <= 1.0, "oz_selfplay_set_playout_cap: full_prob %g outside (0, 1]", full_prob);       // (NaN fails both compares)
+    }
+    std::lock_guard<std::mutex> lk(sp->mu);
+    if (sp->mode != 0) { oz_set_error("oz_selfplay_set_playout_cap: the engine has been driven already (set it before the first driver call)"); return OZ_ERR_STATE; }
+    if (fast_sims == 0) { sp->cap.fast_sims = 0; sp->cap.full_prob = 0.0; return OZ_OK; }
+    if (!sp->cap.log_fast) {
+        hipSetDevice(sp->m->device);
+        const size_t held = sp->allocs.size(), G = (size_t)sp->gm.G;
+        uint8_t* log_fast = nullptr; unsigned long long* moves = nullptr;
+        int rc = sp->alloc(&log_fast, G * 64);
+        if (!rc) rc = sp->alloc(&moves, 2);
+        if (!rc && (hipMemset(log_fast, 0, G * 64) != hipSuccess || hipMemset(moves, 0, 2 * sizeof(unsigned long long)) != hipSuccess)) {
+            oz_set_error("oz_selfplay_set_playout_cap: clearing the buffers failed");
+            rc = OZ_ERR_HIP;
+        }
+        if (rc) {
+            for (size_t i = held; i < sp->allocs.size(); ++i) hipFree(sp->allocs[i]);
+            sp->allocs.resize(held);
+            return rc;
+        }
+        sp->cap.log_fast = log_fast; sp->cap.moves = moves;
+    }
+    sp->cap.fast_sims = fast_sims; sp->cap.full_prob = full_prob;
+    return OZ_OK;
+}
+OZ_API int oz_selfplay_get_playout_cap(oz_selfplay* sp, int* fast_sims, double* full_prob, int64_t* full_moves, int64_t* fast_moves) {
+    OZ_REQUIRE(sp, "null selfplay");
+    std::lock_guard<std::mutex> lk(sp->mu);
+    if (fast_sims) *fast_sims = sp->cap.fast_sims;
+    if (full_prob) *full_prob = sp->cap.full_prob;
+    unsigned long long c[2] = {0, 0};
+    if ((full_moves || fast_moves) && sp->cap.moves) {
+        hipSetDevice(sp->m->device);
+        OZ_HIP(hipStreamSynchronize(sp->m->stream));
+        OZ_HIP(hipMemcpy(c, sp->cap.moves, sizeof c, hipMemcpyDeviceToHost));
+    }
+    if (full_moves) *full_moves = (int64_t)c[0];
+    if (fast_moves) *fast_moves = (int64_t)c[1];
+    return OZ_OK;
+}
+// oz_playout_budget over a batch, on the host: needs no device
+OZ_API int oz_playout_budgets(uint64_t seed, const uint64_t* game_ids, const int32_t* plies, int64_t count, int sims, int fast_sims, double full_prob,
+                              int32_t* out) {
+    OZ_REQUIRE(count >= 0, "oz_playout_budgets: count %lld", (long long)count);
+    OZ_REQUIRE(sims >= 2, "oz_playout_budgets: num_simulations %d (>= 2)", sims);
+    if (fast_sims != 0) {
+        OZ_REQUIRE(fast_sims >= 2 && fast_sims <= sims, "oz_playout_budgets: fast_sims %d outside [2, num_simulations = %d] (0 = off)", fast_sims, sims);
+        OZ_REQUIRE(full_prob > 0.0 && full_prob <= 1.0, "oz_playout_budgets: full_prob %g outside (0, 1]", full_prob);
+    }
+    if (count == 0) return OZ_OK;
+    OZ_REQUIRE(game_ids && plies && out, "oz_playout_budgets: null argument");
+    for (int64_t i = 0; i < count; ++i) {
+        OZ_REQUIRE(plies[i] >= 0, "oz_playout_budgets: plies[%lld] = %d", (long long)i, plies[i]);
+        int fast;
+        out[i] = oz_playout_budget(seed, game_ids[i], (uint64_t)plies[i], sims, fast_sims, full_prob, &fast);
+    }
+    return OZ_OK;
+}
 OZ_API int oz_selfplay_root_noise(oz_selfplay* sp, double* eta, uint8_t* armed) {
     OZ_REQUIRE(sp, "null selfplay");
     std::lock_guard<std::mutex> lk(sp->mu);
@@ -2388,8 +2550,8 @@ OZ_API int oz_selfplay_run_steps(oz_selfplay* sp, int steps) {
         const int adv_cap = (sp->batch_cap > 0 && sp->batch_cap < d.G ? 1 : OZ_ADVANCE_CAP);
         // (from the second batch of a call on, the previous batch's expand + backup rides in the same launch; one closing k_expand_backup per call)
         timed(m, TS_SELECT, all, [&] {
-            if (m->noise_ever || sp->sample.plies > 0) {
-                const SelfplayExtras xt{sp->noise_alpha, sp->gm.seed, sp->sample};
+            if (m->noise_ever || sp->sample.plies > 0 || sp->cap.fast_sims > 0) {
+                const SelfplayExtras xt{sp->noise_alpha, sp->gm.seed, sp->sample, sp->cap};
                 if (fuse && i > 0) hipLaunchKernelGGL(k_backup_advance_x, dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap, xt);
                 else hipLaunchKernelGGL(k_advance_x, dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap, xt);
             } else if (fuse && i > 0) hipLaunchKernelGGL(k_backup_advance, dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap);

@@ -84,7 +84,9 @@ def examples_from_records(records, board_size, alias_final=True, in_channels=2, 
     reference builds a fresh one-channel array per round for BNN (training.py:34-37, Othello/__init__.py:79-84,266-270), so
     those examples are never aliased.
     visits (int32 (R, 64), the records' root visit counts): the policy of every example is the search's visit distribution at
-    target_temperature (expand_examples) instead of the one-hot of the move played."""
+    target_temperature (expand_examples) instead of the one-hot of the move played.
+    The fast records of a playout cap (_lib.record_fast) are no training examples: they and their visit-count rows are dropped first."""
+    records, visits = _lib.full_records(records, visits)
     one_channel = in_channels == 1
     boards, pol, z = expand_examples(records, board_size, alias_final=alias_final and not one_channel, visits=visits,
                                      target_temperature=target_temperature)
@@ -260,14 +262,15 @@ def self_play_match(board_size, neural_network, old_neural_network, total_games,
 
 def _selfplay_into_replay(replay, neural_network, board_size, num_episodes, num_simulations, degree_exploration, temperature, e_greedy, seed,
                           first_game_id, q_mode, visits, leaves_per_step, root_noise, sample_moves, alias_final_boards, policy_target,
-                          target_temperature, endgame_targets=0, solve_leaves=0):
+                          target_temperature, endgame_targets=0, solve_leaves=0, playout_cap=None):
     """one iteration's games on the engine selfplay_batch would create, played to the end without reading a record, and their examples
     appended to the device buffer; -> (records appended, the endgame solver's statistics or None).  One-channel (BaseNN) examples are never
-    aliased (examples_from_records).  endgame_targets > 0: SelfPlayEngine.solve_records before the append."""
+    aliased (examples_from_records).  endgame_targets > 0: SelfPlayEngine.solve_records before the append.  playout_cap: the engine's; the
+    append leaves the fast records out and counts the fully searched ones."""
     from .training import SelfPlayEngine
     eng = SelfPlayEngine(neural_network, board_size, num_episodes, num_simulations, degree_exploration, temperature, e_greedy, seed,
                          first_game_id, q_mode=q_mode, record_visits=visits, leaves_per_step=leaves_per_step, root_noise=root_noise,
-                         sample_moves=sample_moves, solve_leaves=solve_leaves)
+                         sample_moves=sample_moves, solve_leaves=solve_leaves, **({"playout_cap": playout_cap} if playout_cap is not None else {}))
     for _ in range(board_size * board_size):
         eng.run(4)
         if eng.stats()["live_games"] == 0:
@@ -290,7 +293,7 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
              seed=1234, reference_aliasing=True, alias_final_boards=True, dump_examples=False, q_mode=_lib.QMODE_F64,
              distributed=False, batched_evaluation=False, policy_target="onehot", target_temperature=1.0, leaves_per_step=1,
              root_noise=None, sample_moves=None, replay="host", evaluation_opponent="random", endgame_targets=0,
-             solve_leaves=0, match_openings=None, evaluation_openings=None):
+             solve_leaves=0, match_openings=None, evaluation_openings=None, playout_cap=None):
     """main.py:56-259 on the GPU engines; returns `historic` = [(episodes done, win rate vs random), ...]
 
     batched_evaluation=True plays the evaluation games against RandomOthelloAgent in lock step on the GPU
@@ -353,7 +356,21 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
     won, counted the same way.  A match with openings also logs mean_margin +- se (discs per pair of games) and split_pairs, and
     training.match_history keeps its dicts (paired_match).  self_play_total_games must then be even; evaluation_openings needs
     batched_evaluation=True (the drop-in agents play one game at a time on the host, from the standard position).  With distributed=True every
-    rank plays the whole match, as without openings."""
+    rank plays the whole match, as without openings.
+
+    playout_cap=(fast_sims, full_prob) (None = off, the default): KataGo's playout cap randomization for the SELF-PLAY games (SelfPlayEngine).
+    A searched move runs num_simulations simulations with probability full_prob and fast_sims otherwise; only the fully searched moves become
+    training examples -- in the host path (examples_from_records drops the flagged records), in the distributed path (the flag travels inside
+    the 48-byte records through the all-gather) and with replay="device" (the append leaves them out) -- while every game still ends in an
+    outcome for them: more finished games per GPU-second for the value head, full-search visit distributions only for the policy head.  A
+    fast move draws no root noise.  endgame_targets still relabels all records, so its mean_disc_loss measures the moves actually played, fast
+    ones included.  Matches and evaluations are never capped.  The reference has nothing like it.  Use (20, 0.25) at 100 simulations, the
+    one setting that has been measured: on an MI355X at 4 096 games of 8x8 it finishes 1.89 times as many games per second as the engine without
+    it (2.03 times the moves at 40 simulations per move on average), while the fully searched records per second fall to 0.51 times -- a quarter
+    of twice as many moves; expansions per second fall to 0.84 times because the capped games share fewer leaves for the cross-game
+    de-duplication to take out ("Playout cap"; tools/playout_cap_bench.py, profiles/playout_cap_bench.json)."""
+    playout_cap = _lib.check_playout_cap(playout_cap, num_simulations)
+    cap_kw = {"playout_cap": playout_cap} if playout_cap is not None else {}
     _lib.check_opponent(evaluation_opponent)
     _lib.check_openings(match_openings)
     _lib.check_openings(evaluation_openings)
@@ -426,7 +443,7 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
             appended, endgame = _selfplay_into_replay(device_replay, neural_network, board_size, num_episodes, num_simulations,
                                                       degree_exploration, temperature, e_greedy, seed, total_episodes_done, q_mode, visits,
                                                       leaves_per_step, root_noise, sample_moves, alias_final_boards, policy_target,
-                                                      target_temperature, endgame_targets, solve_leaves)
+                                                      target_temperature, endgame_targets, solve_leaves, playout_cap)
             if endgame is not None:
                 training.endgame_history.append(endgame)
                 _log_endgame(i, num_iterations, endgame)
@@ -440,7 +457,7 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
                 eng = SelfPlayEngine(neural_network, board_size, count, num_simulations, degree_exploration, temperature, e_greedy,
                                      seed=seed, first_game_id=total_episodes_done + first, q_mode=q_mode, record_visits=visits,
                                      leaves_per_step=leaves_per_step, root_noise=root_noise, sample_moves=sample_moves,
-                                     solve_leaves=solve_leaves)
+                                     solve_leaves=solve_leaves, **cap_kw)
                 eng.play_to_end(endgame_targets=endgame_targets)                        # each rank relabels its own records
                 training.rows_solved += eng.rows_solved() if solve_leaves else 0
                 records = pooled_selfplay_records(eng, device, with_visits=visits)      # the only exchange of the self-play phase
@@ -451,7 +468,8 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
                                          degree_exploration=degree_exploration, policy_temperature=temperature, e_greedy=e_greedy,
                                          seed=seed, first_game_id=total_episodes_done, q_mode=q_mode, record_visits=visits,
                                          leaves_per_step=leaves_per_step, root_noise=root_noise, sample_moves=sample_moves,
-                                         **({"endgame_targets": endgame_targets} if endgame_targets else {}), **({"solve_leaves": solve_leaves} if solve_leaves else {}))
+                                         **({"endgame_targets": endgame_targets} if endgame_targets else {}), **({"solve_leaves": solve_leaves} if solve_leaves else {}),
+                                         **cap_kw)
                 training.rows_solved += selfplay_batch.rows_solved if solve_leaves else 0
                 endgame = getattr(selfplay_batch, "endgame_stats", None) if endgame_targets else None
             if endgame is not None:

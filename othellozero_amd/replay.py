@@ -62,7 +62,8 @@ class ReplayBuffer:
 
     def append_engine(self, eng, first_record=0, alias_final=False, policy_target="onehot", target_temperature=1.0):
         """the records [first_record, completed so far) of a SelfPlayEngine -> 8 examples each, in ascending (game_id, ply), device to
-        device; returns the number of records appended.  policy_target="visits" needs an engine created with record_visits=True."""
+        device; returns the number of records appended.  policy_target="visits" needs an engine created with record_visits=True.
+        The fast records of a playout cap (_lib.record_fast) are left out and not counted."""
         target, T = _target(policy_target, target_temperature)
         done = C.c_int64()
         _lib.check(_lib.load().oz_replay_append_selfplay(self._h, eng._h, int(first_record), 1 if alias_final else 0, target, T, C.byref(done)))
@@ -70,7 +71,8 @@ class ReplayBuffer:
 
     def append_records(self, records, visits=None, alias_final=False, policy_target="onehot", target_temperature=1.0):
         """the same from records on the host (_lib.RECORD_DTYPE; visits = their int32 (R, 64) root visit counts for policy_target="visits"),
-        in any order: they are appended in ascending (game_id, ply); returns the number of records appended"""
+        in any order: they are appended in ascending (game_id, ply); returns the number of records appended -- the fast records of a
+        playout cap (_lib.record_fast) are left out and not counted"""
         target, T = _target(policy_target, target_temperature)
         rec = np.ascontiguousarray(records, dtype=_lib.RECORD_DTYPE)
         cnt = None
@@ -79,7 +81,7 @@ class ReplayBuffer:
             assert cnt.shape[0] == rec.size, f"{cnt.shape[0]} visit-count rows for {rec.size} records"
         _lib.check(_lib.load().oz_replay_append_records(self._h, rec.ctypes.data_as(C.c_void_p), None if cnt is None else _lib.p_i32(cnt),
                                                         rec.size, 1 if alias_final else 0, target, T))
-        return rec.size
+        return int((_lib.record_fast(rec) == 0).sum())
 
     def append_examples(self, own, opp, pi, z):
         """finished examples in the given order: own / opp uint64 (N,), pi float32 (N, n*n), z float32 (N,) -- what read() returns"""

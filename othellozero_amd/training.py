@@ -145,7 +145,7 @@ class SelfPlayEngine:
     def __init__(self, neural_network, board_size=8, num_games=4096, num_simulations=100, degree_exploration=1.0,
                  policy_temperature=1.0, e_greedy=0.9, seed=1234, first_game_id=0, game_id_stride=0,
                  q_mode=_lib.QMODE_F64, refill=False, node_cap=0, record_cap=0, dedup=True, batch_cap=0, eval_cache=False,
-                 record_visits=False, leaves_per_step=1, root_noise=None, sample_moves=None, solve_leaves=0):
+                 record_visits=False, leaves_per_step=1, root_noise=None, sample_moves=None, solve_leaves=0, playout_cap=None):
         """dedup: cross-game leaf de-duplication (a board several games reach in one batch is evaluated once; no record changes);
         batch_cap: leaves per network batch of the free-running driver (0 = none; see preferred_batch_cap);
         eval_cache: take (pi, v) of boards the network has evaluated before from its persistent cache (NNetWrapper.set_eval_cache) --
@@ -164,7 +164,15 @@ class SelfPlayEngine:
         solve_leaves=E > 0: in every search a leaf with at most E empties takes its exact win / draw / loss (+1 / 0 / -1 for the side to
         move) in place of the network's value, solved on the device right after the network's batch (oz_selfplay_set_solve_leaves); the
         priors stay the network's and its evaluation cache keeps the network's value.  Every driver, any leaves_per_step.  rows_solved()
-        counts them.  Not the reference's search."""
+        counts them.  Not the reference's search.
+        playout_cap=(fast_sims, full_prob): KataGo's playout cap randomization (oz_selfplay_set_playout_cap).  A searched move runs
+        num_simulations simulations with probability full_prob and fast_sims (2 .. num_simulations) otherwise, drawn per (seed, game id, ply);
+        a fast move draws no root noise, and its record carries the flag _lib.record_fast reads: the record consumers (expand_examples,
+        loop.examples_from_records, ReplayBuffer.append_*) train on the fully searched moves only, while every game still ends in an outcome
+        for them.  run() at any leaves_per_step and run_steps() alike; stagger()'s rounds are not capped; playout_stats() counts the moves.
+        full_prob = 1 plays the games of the engine without the option.  Measured at (20, 0.25), 4 096 games of 8x8 at 100 simulations:
+        1.89 times the finished games per second, 0.51 times the fully searched records per second ("Playout cap")."""
+        playout_cap = _lib.check_playout_cap(playout_cap, num_simulations)
         solve_leaves = _lib.check_solve_leaves(solve_leaves)
         root_noise = _lib.check_root_noise(root_noise)
         sample_moves = _lib.check_sample_moves(sample_moves)
@@ -192,6 +200,16 @@ class SelfPlayEngine:
         self.solve_leaves = solve_leaves
         if solve_leaves:
             _lib.check(lib.oz_selfplay_set_solve_leaves(self._h, solve_leaves))
+        self.playout_cap = playout_cap
+        if playout_cap is not None:
+            _lib.check(lib.oz_selfplay_set_playout_cap(self._h, playout_cap[0], playout_cap[1]))
+
+    def playout_stats(self):
+        """dict(fast_sims, full_prob, full_moves, fast_moves): the playout cap that is set (fast_sims 0 = none) and the moves run() /
+        run_steps() have played under it so far"""
+        fs, p, full, fast = C.c_int(), C.c_double(), C.c_int64(), C.c_int64()
+        _lib.check(_lib.load().oz_selfplay_get_playout_cap(self._h, C.byref(fs), C.byref(p), C.byref(full), C.byref(fast)))
+        return dict(fast_sims=fs.value, full_prob=p.value, full_moves=full.value, fast_moves=fast.value)
 
     def set_solve_leaves(self, max_empties):
         """solved leaves on (E > 0) / off (0) from the next search step on"""
@@ -315,7 +333,9 @@ class SelfPlayEngine:
         """oz_selfplay_solve_records: the completed records from `first_record` on whose position has at most max_empties empties get the
         exact solver's value target in place on the device (z = the sign of the final disc difference under perfect play, for the mover; a
         draw goes to BLACK) -- nothing else of a record changes.  -> dict(records, solved, z_changed, optimal_moves, disc_loss_sum,
-        disc_loss_max, mean_disc_loss): the discs the moves played gave away against perfect play, over the solved records."""
+        disc_loss_max, mean_disc_loss): the discs the moves played gave away against perfect play, over the solved records.
+        Under a playout cap it works on ALL records, the fast ones included: mean_disc_loss then measures the moves actually played, most of
+        them searched on the fast budget, not the training examples alone."""
         max_empties = _lib.check_solve_empties(max_empties, 1)
         s = _lib.EndgameStats()
         _lib.check(_lib.load().oz_selfplay_solve_records(self._h, int(first_record), max_empties, C.byref(s)))
@@ -373,7 +393,11 @@ def expand_examples(records, board_size, alias_final=False, visits=None, target_
 
     visits = the records' root visit counts (int32 (R, 64), SelfPlayEngine.records(with_visits=True)): the policy is the search's
     visit distribution get_policy_action_probabilities(root, target_temperature) (othelo_mcts.py:51-67) in place of the one-hot,
-    and the second array returned is pi (R*8, n, n) float64 (target_temperature > 0)."""
+    and the second array returned is pi (R*8, n, n) float64 (target_temperature > 0).
+
+    The fast records of a playout cap (_lib.record_fast) are no training examples: they and their visit-count rows are dropped first, so R
+    counts the fully searched moves."""
+    records, visits = _lib.full_records(np.ascontiguousarray(records, dtype=_lib.RECORD_DTYPE), visits)
     rec = np.ascontiguousarray(records, dtype=_lib.RECORD_DTYPE)
     R, n = rec.size, board_size
     if visits is not None:
@@ -398,7 +422,7 @@ def expand_examples(records, board_size, alias_final=False, visits=None, target_
 def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations=100, degree_exploration=1.0,
                    policy_temperature=1.0, e_greedy=0.9, seed=1234, first_game_id=0, q_mode=_lib.QMODE_F64,
                    expand=False, alias_final=False, record_visits=False, target_temperature=1.0, leaves_per_step=1, root_noise=None,
-                   sample_moves=None, endgame_targets=0, solve_leaves=0):
+                   sample_moves=None, endgame_targets=0, solve_leaves=0, playout_cap=None):
     """Play num_games complete games; returns the move records (or the expanded examples).
     record_visits=True: (records, visit counts) -- or, with expand, the examples with visit-distribution targets at target_temperature.
     root_noise=(alpha, epsilon): Dirichlet root noise in every search (SelfPlayEngine).
@@ -406,19 +430,25 @@ def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations
     endgame_targets=E > 0: records with E empties or fewer carry the exact solver's value target (SelfPlayEngine.solve_records); with expand it
     needs alias_final=False.  selfplay_batch.endgame_stats holds the last call's statistics (None when off).
     solve_leaves=E > 0: exact values for the searches' leaves with at most E empties (SelfPlayEngine); selfplay_batch.rows_solved holds the
-    last call's count (None when off)."""
+    last call's count (None when off).
+    playout_cap=(fast_sims, full_prob): a playout cap on the searched moves (SelfPlayEngine).  The records returned are ALL records, the fast
+    ones flagged (_lib.record_fast); with expand, the examples of the fully searched moves only.  selfplay_batch.playout_stats holds the last
+    call's SelfPlayEngine.playout_stats() (None when off)."""
+    playout_cap = _lib.check_playout_cap(playout_cap, num_simulations)
     solve_leaves = _lib.check_solve_leaves(solve_leaves)
     endgame_targets = _lib.check_endgame_targets(endgame_targets, expand and alias_final)
     eng = SelfPlayEngine(neural_network, board_size, num_games, num_simulations, degree_exploration, policy_temperature,
                          e_greedy, seed, first_game_id, q_mode=q_mode, record_visits=record_visits, leaves_per_step=leaves_per_step,
-                         root_noise=root_noise, sample_moves=sample_moves, solve_leaves=solve_leaves)
-    selfplay_batch.endgame_stats = selfplay_batch.rows_solved = None
+                         root_noise=root_noise, sample_moves=sample_moves, solve_leaves=solve_leaves, playout_cap=playout_cap)
+    selfplay_batch.endgame_stats = selfplay_batch.rows_solved = selfplay_batch.playout_stats = None
     if record_visits:
         rec, counts = eng.play_to_end(with_visits=True, endgame_targets=endgame_targets)
+        selfplay_batch.playout_stats = eng.playout_stats() if playout_cap is not None else None
         selfplay_batch.rows_solved = eng.rows_solved() if solve_leaves else None
         selfplay_batch.endgame_stats = getattr(eng, "endgame_stats", None)
         return expand_examples(rec, board_size, alias_final, visits=counts, target_temperature=target_temperature) if expand else (rec, counts)
     rec = eng.play_to_end(endgame_targets=endgame_targets)
+    selfplay_batch.playout_stats = eng.playout_stats() if playout_cap is not None else None
     selfplay_batch.rows_solved = eng.rows_solved() if solve_leaves else None
     selfplay_batch.endgame_stats = getattr(eng, "endgame_stats", None)
     return expand_examples(rec, board_size, alias_final) if expand else rec
