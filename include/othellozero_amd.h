@@ -423,6 +423,50 @@ int oz_mcts_sample_moves(oz_mcts* m, double temperature, uint64_t seed, const ui
 int oz_playout_budgets(uint64_t seed, const uint64_t* game_ids, const int32_t* plies, int64_t count, int sims, int fast_sims,
                        double full_prob, int32_t* out /* [count] */);
 
+/* ---- forced playouts: forced playouts and policy target pruning for the noisy root (opt-in, KataGo's; off, every launch, record and row stays
+ * bit for bit).  At ~100 simulations a move the noise favours but the prior dismisses gets a visit or two and is dropped: if it is good the
+ * search never finds out, if it is bad its visits stay in the row policy_target="visits" trains on.  With the forcing constant k (KataGo: 2.0;
+ * accepted: [0, 16], 0 = off), all in float64, no contraction, as written; Pn(sq) = (1.0 - eps) * P + eps * eta[sq] is the root noise's view:
+ * FORCING -- only at depth 0 of a descent from a root whose noise is armed (where the descent already reads Pn).  With the descent's view
+ * Ns + ks, N', Q' (virtual loss included) and U computed for a legal square as ever:
+ *     nf = sqrt((k * Pn) * (double)(Ns + ks))
+ *     if (N' > 0 && (double)N' < nf) U = +INFINITY
+ * The first maximum in ascending square order still wins, among several infinities too.  A child with N' == 0 is never forced; the Ns == 0 quirk
+ * gives nf == 0 and stays.  Deeper levels, unarmed roots, the fast moves of a playout cap (they draw no noise), arenas, matches and evaluations
+ * are never forced.  At leaves_per_step > 1 the in-flight descents count in N', so forcing spreads over them.  The host-evaluator split
+ * (oz_mcts_select / leaves / backup) honours forcing as it honours noise.
+ * PRUNING -- of a root's count row, when the move is chosen, on a root whose noise is armed, k > 0.  From the stored N[sq], Q[sq], P[sq], Ns of the
+ * root record (no virtual loss exists then), eta, eps and c:
+ *     root  = sqrt((double)Ns)
+ *     star  = the first legal square, ascending, with N == max N
+ *     Ustar = Q[star] + (c * Pn[star]) * (root / (double)(1 + N[star]))
+ *     for every other legal sq with N[sq] > 0:
+ *         F    = (int)ceil(sqrt((k * Pn[sq]) * (double)Ns))                     the most forcing can have added
+ *         gap  = Ustar - Q[sq]
+ *         if !(gap > 0.0):  Np = N[sq]                                          its Q alone reaches Ustar: keep
+ *         else:
+ *             need = ((c * Pn[sq]) * root) / gap - 1.0
+ *             m    = need < (double)N[sq] ? max(0, (int)ceil(need)) : N[sq]     NaN / inf: keep
+ *             Np   = min(N[sq], max(N[sq] - F, m))
+ *         if (Np < N[sq] && Np <= 1) Np = 0                                     a child cut down to one visit is dropped
+ *     pruned[star] = N[star];  pruned[sq] = N[sq] where N[sq] == 0;  pruned[sq] = 0 off the legal set
+ * star keeps its count, so a pruned row is never all zero.  ONE function, oz_forced_prune (csrc/oz_common.h), is what the kernels and
+ * oz_forced_playouts_prune evaluate.
+ * MOVE CHOICE IS EXPLORATION, THE TARGET IS WHAT IS LEARNED: only the row that becomes the policy target (the engine's visit rows with
+ * record_visits = 1, oz_mcts_pruned_counts) is pruned.  oz_selfplay_last_counts, oz_mcts_root_counts, the arg-max, the tie rule, move sampling
+ * and the e-greedy branch read the raw counts: the games change through forcing alone.
+ * OZ_ERR_ARG: k outside [0, 16] (NaN included).  OZ_ERR_STATE: k > 0 on an object without root noise, a change while a step is pending / after
+ * an engine's first driver call.  A refused call leaves the object as it was. */
+/* oz_forced_prune over `count` rows, on the host (no device needed): N, Q, P, eta, pruned are [count][64] by square, legal and Ns [count].
+ * OZ_ERR_ARG also for eps outside [0, 1], a NaN c, a negative N or Ns. */
+int oz_forced_playouts_prune(const int32_t* N, const double* Q, const double* P, const double* eta, const uint64_t* legal, const int32_t* Ns,
+                             int64_t count, double c, double eps, double k, int32_t* pruned /* [count][64] */);
+/* the forcing constant of a bare search: needs root noise armed before (oz_mcts_set_root_noise / oz_mcts_sample_root_noise with eps > 0) */
+int oz_mcts_set_forced_playouts(oz_mcts* m, double k);
+int oz_mcts_get_forced_playouts(oz_mcts* m, double* k);
+/* oz_mcts_root_counts with the policy target's rows: pruned on the slots whose noise is armed (k > 0), raw on the others */
+int oz_mcts_pruned_counts(oz_mcts* m, int32_t* counts, uint64_t* legal, int32_t* rc);
+
 /* ------------------------------------------------------------------ self-play
  * execute_episode (training.py:26-72) for num_games concurrent games in lock step. */
 typedef struct oz_selfplay oz_selfplay;
@@ -526,6 +570,14 @@ int oz_selfplay_set_playout_cap(oz_selfplay* sp, int fast_sims, double full_prob
 /* what is set (fast_sims 0 = off) and the moves played under the cap so far: full_moves + fast_moves = the moves of oz_selfplay_run /
  * oz_selfplay_run_steps since the cap was armed.  Every pointer may be NULL; reading a counter waits for the engine's stream. */
 int oz_selfplay_get_playout_cap(oz_selfplay* sp, int* fast_sims, double* full_prob, int64_t* full_moves, int64_t* fast_moves);
+/* self-play with forced playouts ("forced playouts" above): every searched move whose root draws noise is forced, and its visit row
+ * (record_visits = 1) is the pruned one.  Holds for oz_selfplay_run at any leaves_per_step, for oz_selfplay_stagger (its rounds draw noise) and
+ * for the free-running oz_selfplay_run_steps, whose records and rows stay exactly those of oz_selfplay_run; the fast moves of a playout cap are
+ * neither forced nor pruned.  After oz_selfplay_set_root_noise, before the first driver call (OZ_ERR_STATE otherwise); k == 0 switches off. */
+int oz_selfplay_set_forced_playouts(oz_selfplay* sp, double k);
+/* what is set and, since it was armed: the moves whose recorded row differs from the raw counts, and the visits before / after pruning summed
+ * over every move pruning ran on (the moves with an armed root).  Every pointer may be NULL; reading a counter waits for the engine's stream. */
+int oz_selfplay_get_forced_playouts(oz_selfplay* sp, double* k, int64_t* moves_pruned, int64_t* visits_raw, int64_t* visits_kept);
 int oz_selfplay_sync(oz_selfplay* sp);
 /* continuous self-play (cfg.refill): bring a fresh engine to the steady state of a long-running one before measuring it --
  * slot g is advanced (g * P) / num_games plies into its first game, P = n*n - 4, by searched self-play moves at `sims_pre`

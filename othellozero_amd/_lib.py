@@ -171,6 +171,11 @@ SIGNATURES = {
     "oz_selfplay_set_move_sampling": [_vp, C.c_double, C.c_int],
     "oz_selfplay_set_playout_cap": [_vp, C.c_int, C.c_double],
     "oz_selfplay_get_playout_cap": [_vp, C.POINTER(C.c_int), _f64p, _i64p, _i64p],
+    "oz_forced_playouts_prune": [_i32p, _f64p, _f64p, _f64p, _u64p, _i32p, C.c_int64, C.c_double, C.c_double, C.c_double, _i32p],
+    "oz_mcts_set_forced_playouts": [_vp, C.c_double], "oz_mcts_get_forced_playouts": [_vp, _f64p],
+    "oz_mcts_pruned_counts": [_vp, _i32p, _u64p, _i32p],
+    "oz_selfplay_set_forced_playouts": [_vp, C.c_double],
+    "oz_selfplay_get_forced_playouts": [_vp, _f64p, _i64p, _i64p, _i64p],
     "oz_playout_budgets": [C.c_uint64, _u64p, _i32p, C.c_int64, C.c_int, C.c_int, C.c_double, _i32p],
     "oz_selfplay_create": [C.POINTER(_vp), C.POINTER(SelfplayConfig), _vp],
     "oz_selfplay_destroy": [_vp], "oz_selfplay_run": [_vp, C.c_int], "oz_selfplay_run_steps": [_vp, C.c_int], "oz_selfplay_sync": [_vp],
@@ -359,6 +364,26 @@ def check_root_noise(root_noise):
     if not 0.0 <= eps <= 1.0:
         raise ValueError(f"root_noise: epsilon must be in [0, 1] (got {eps})")
     return alpha, eps
+
+
+def check_forced_playouts(forced_playouts, root_noise=None, need_noise=True):
+    """forced_playouts = None or k: KataGo's forced playouts and policy target pruning on every searched self-play move whose root draws
+    noise (include/othellozero_amd.h, "forced playouts").  Returns 0.0 (off: None or 0) or k as a float; ValueError for anything the library
+    would refuse: k a number in [0, 16], and -- forcing is a rule of the noisy root -- k > 0 without root_noise (an epsilon of 0 is none)
+    where need_noise is set."""
+    if forced_playouts is None:
+        return 0.0
+    if isinstance(forced_playouts, (bool, str, bytes)):
+        raise ValueError(f"forced_playouts must be None or a number k in [0, 16], got {forced_playouts!r}")
+    try:
+        k = float(forced_playouts)
+    except (TypeError, ValueError):
+        raise ValueError(f"forced_playouts must be None or a number k in [0, 16], got {forced_playouts!r}") from None
+    if not 0.0 <= k <= 16.0:
+        raise ValueError(f"forced_playouts: k must be in [0, 16] (got {k})")
+    if k > 0.0 and need_noise and (root_noise is None or not root_noise[1] > 0.0):
+        raise ValueError("forced_playouts needs root_noise=(alpha, epsilon > 0): forcing and pruning are rules of the noisy root")
+    return k
 
 
 def check_sample_moves(sample_moves):

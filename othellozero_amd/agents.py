@@ -79,6 +79,26 @@ def rules_solve_sign(black, white, player, n, max_empties=_lib.SOLVE_MAX_EMPTIES
     return sign, solved
 
 
+def rules_prune_counts(N, Q, P, eta, legal, Ns, c, epsilon, k):
+    """oz_forced_playouts_prune, policy target pruning over a batch of root rows, on the host (no GPU needed): N int32, Q, P, eta float64
+    (count, 64) by square row*8+col, legal uint64 (count,), Ns int32 (count,) = the roots' stored statistics, their noise and visits; c, epsilon =
+    the search's exploration constant and the noise's mixing weight, k = the forcing constant (0: the rows come back as they are, 0 off the
+    legal set).  -> pruned int32 (count, 64): the rows a search with forced_playouts=k records as policy targets."""
+    k = _lib.check_forced_playouts(k, need_noise=False)
+    N = np.ascontiguousarray(N, dtype=np.int32).reshape(-1, 64)
+    Q, P, eta = (np.ascontiguousarray(x, dtype=np.float64).reshape(-1, 64) for x in (Q, P, eta))
+    legal = np.ascontiguousarray(legal, dtype=np.uint64).ravel()
+    Ns = np.ascontiguousarray(Ns, dtype=np.int32).ravel()
+    count = N.shape[0]
+    if not (Q.shape[0] == P.shape[0] == eta.shape[0] == legal.size == Ns.size == count):
+        raise ValueError(f"rules_prune_counts: {count} count rows, {Q.shape[0]} / {P.shape[0]} / {eta.shape[0]} Q / P / eta rows, {legal.size} legal "
+                         f"masks, {Ns.size} Ns")
+    pruned = np.zeros((count, 64), np.int32)
+    _lib.check(_lib.load().oz_forced_playouts_prune(_lib.p_i32(N), _lib.p_f64(Q), _lib.p_f64(P), _lib.p_f64(eta), _lib.p_u64(legal), _lib.p_i32(Ns),
+                                                    count, float(c), float(epsilon), k, _lib.p_i32(pruned)))
+    return pruned
+
+
 def rules_random_openings(n, count, plies, seed, first_opening_id=0):
     """oz_rules_random_openings: the random openings first_opening_id .. first_opening_id + count - 1 of (plies, seed) on the n x n board, what
     arena_batch(openings=(plies, seed), first_opening_id=...) lets its games start with.  -> dict(black, white uint64 (count,) = the position

@@ -46,6 +46,32 @@ OZ_HD int oz_playout_budget(uint64_t seed, uint64_t game, uint64_t ply, int sims
     return f ? fast_sims : sims;
 }
 
+// forced playouts (include/othellozero_amd.h, "forced playouts"): the count of one legal square of an armed root's row as the policy target
+// keeps it.  N, Q, P, eta = the square's stored statistics and its share of the noise; the *s operands = those of `star`, the first legal
+// square with the largest N (is_star != 0: this square is star and keeps its count); Ns, c, eps, k = the root's visits, the exploration
+// constant, the noise's mixing weight and the forcing constant.  float64, no contraction, every
+// expression as the header writes it.  The one definition the kernels (oz_search.hip) and the host's oz_forced_playouts_prune share.
+OZ_HD int oz_forced_prune(int N, double Q, double P, double eta, int Nstar, double Qstar, double Pstar, double etastar, int is_star, int Ns, double c,
+                          double eps, double k) {
+#pragma clang fp contract(off)
+    if (is_star || N <= 0 || !(k > 0.0)) return N;
+    const double root = sqrt((double)Ns);
+    const double Pn = (1.0 - eps) * P + eps * eta, Pns = (1.0 - eps) * Pstar + eps * etastar;
+    const double Ustar = Qstar + (c * Pns) * (root / (double)(1 + Nstar));
+    const double f = ceil(sqrt((k * Pn) * (double)Ns));
+    const int F = f < 2147483647.0 ? (int)f : 2147483647;          // the most forcing can have added (NaN: everything, the PUCT bound below decides alone)
+    const double gap = Ustar - Q;
+    int Np = N;
+    if (gap > 0.0) {                                                // else its Q alone reaches Ustar: keep
+        const double need = ((c * Pn) * root) / gap - 1.0;
+        const int m = need < (double)N ? (need > 0.0 ? (int)ceil(need) : 0) : N;          // NaN / inf: keep
+        const int lo = N - F > m ? N - F : m;
+        Np = N < lo ? N : lo;
+    }
+    if (Np < N && Np <= 1) Np = 0;                                  // a child cut down to one visit is dropped
+    return Np;
+}
+
 OZ_HD uint64_t oz_stub_h(uint64_t own, uint64_t opp, uint64_t salt, uint64_t i) {
     return oz_sm64(oz_sm64(own ^ salt) ^ oz_rotl64(opp, 29) ^ ((i + 1) * 0xD6E8FEB86659FD93ULL));
 }

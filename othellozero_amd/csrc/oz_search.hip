@@ -87,6 +87,7 @@ struct MctsDev {
     double* noise_eta;         // [G][64] eta by square, 0 off the legal set of the root it was drawn for
     uint8_t* noise_armed;      // [G] the slot's CURRENT root carries noise
     double noise_eps;          // the mixing weight (0: off)
+    double forced_k;           // forced playouts ("forced playouts" below): the forcing constant k (0: off); needs noise, so the *_n kernels alone read it
 };
 
 __device__ __forceinline__ unsigned char* rec_ptr(const MctsDev& t, int g, int node) {
@@ -302,6 +303,42 @@ __device__ __forceinline__ int sample_move(int cnt, uint64_t legal, int mx, doub
     return visited ? 63 - __builtin_clzll(visited) : -1;
 }
 
+// ---------------------------------------------------------------- forced playouts and policy target pruning (opt-in, KataGo's; needs root noise)
+// (the definition is stated in include/othellozero_amd.h, "forced playouts"; the restatement the tests hold this against is tests/forced_playouts_ref.py.)
+//   * forcing lives in descend_one<true>, at depth 0 of a descent from an armed root: a child tried at least once whose count (in-flight descents
+//     included) is below sqrt((k * Pn) * Ns) gets U = +inf.  MctsDev.forced_k is uniform, and so are `noisy` and `depth`: the wave takes one
+//     branch, only the compare is per lane.  k == 0 leaves the expression the noise kernels evaluated before.
+//   * pruning lives in the move (sp_move_body<.., FORCE>) and in k_pruned_counts: one lane per square computes oz_forced_prune (oz_common.h) of
+//     its own (N, Q, P, eta) and of star's, fetched with lane_get.  Only the row that becomes the policy target is pruned; last_counts, the
+//     arg-max, the tie rule, sample_move and the e-greedy branch read the raw counts.
+struct ForcedPlayouts {
+    double k;                       // 0: off
+    unsigned long long* stat;       // [0] moves whose recorded row differs from the raw one [1] visits of the rows pruning ran on [2] visits kept of them
+};
+__device__ __forceinline__ int wave_sum_i32(int x) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
+    return x;
+}
+// the pruned count of this lane's square at the root record `node` of slot g (its noise armed, eta[g] that of this root); cnt = the lane's raw
+// count (0 off the legal set), mx = the largest
+__device__ __forceinline__ int forced_prune_lane(const MctsDev& t, int g, int node, int lane, uint64_t legal, int cnt, int mx, double k) {
+    const bool is_legal = (legal >> lane) & 1;
+    double Q = 0.0, P = 0.0;
+    if (is_legal) {
+        const OzEdge* e = rec_edge(t, g, node, oz_popc(legal & ((1ULL << lane) - 1ULL)));
+        Q = e->q; P = e->p;
+    }
+    const double eta = t.noise_eta[(size_t)g * 64 + lane];
+    const int Ns = unii(*rec_Ns(t, g, node));
+    const uint64_t top = __ballot(is_legal && cnt == mx);
+    if (top == 0) return cnt;                                               // no legal move: nothing to prune
+    const int star = oz_ctz(top);
+    const int Nstar = lane_get(cnt, star);
+    const double Qstar = lane_get_f64(Q, star), Pstar = lane_get_f64(P, star), etastar = lane_get_f64(eta, star);
+    return is_legal ? oz_forced_prune(cnt, Q, P, eta, Nstar, Qstar, Pstar, etastar, lane == star ? 1 : 0, Ns, t.c, t.noise_eps, k) : 0;
+}
+
 // ---------------------------------------------------------------- K4: select / descend
 // MCTS.simulate down to the first terminal or unexpanded state (MCTS/__init__.py:39-44,58-67),
 // get_next_state (othelo_mcts.py:43-49).  One wave per game; per level ONE wave-wide load stages the node's record in LDS.
@@ -375,7 +412,12 @@ __device__ __forceinline__ Descent descend_one(const MctsDev& t, uint4* rec, int
             const double bound = sqrt((double)(Ns + ks)) / (double)(1 + N);    // MCTS/__init__.py:169
             U = Q + (t.c * P) * bound;                                     // :170, left to right
             if constexpr (NOISE) {
-                if (noisy && depth == 0) U = Q + (t.c * ((1.0 - t.noise_eps) * P + t.noise_eps * eta)) * bound;     // the root's noisy view of P
+                if (noisy && depth == 0) {                                  // (uniform: one branch per wave, only the forcing compare is per lane)
+                    const double Pn = (1.0 - t.noise_eps) * P + t.noise_eps * eta;          // the root's noisy view of P
+                    U = Q + (t.c * Pn) * bound;
+                    // forced playouts: a tried child of the noisy root below its quota is selected before any PUCT value (the first such square)
+                    if (t.forced_k > 0.0 && N > 0 && (double)N < sqrt((t.forced_k * Pn) * (double)(Ns + ks))) U = INFINITY;
+                }
             }
         }
         const double m = wave_max_f64(U);
@@ -1696,6 +1738,91 @@ OZ_API int oz_mcts_root_counts(oz_mcts* m, int32_t* counts, uint64_t* legal, int
     return OZ_OK;
 }
 
+// ---- forced playouts: host side
+static int forced_check(const char* fn, double k) {
+    OZ_REQUIRE(k >= 0.0 && k <= 16.0, "%s: k %g outside [0, 16] (0 = off)", fn, k);          // (NaN fails both compares)
+    return OZ_OK;
+}
+// k > 0 needs root noise armed on the object (forcing is a rule of the noisy root); k == 0 switches off
+static int forced_set_locked(oz_mcts* m, const char* fn, double k) {
+    if (k > 0.0 && !(m->noise_ever && m->d.noise_eps > 0.0)) {
+        oz_set_error("%s: forced playouts need root noise (arm it first)", fn);
+        return OZ_ERR_STATE;
+    }
+    m->d.forced_k = k;                                     // takes effect at the next launch (kernels get the struct by value)
+    return OZ_OK;
+}
+OZ_API int oz_mcts_set_forced_playouts(oz_mcts* m, double k) {
+    OZ_REQUIRE(m, "null mcts");
+    if (int rc = forced_check("oz_mcts_set_forced_playouts", k)) return rc;
+    std::lock_guard<std::mutex> lk(m->mu);
+    OZ_REFUSE_PENDING(m, "oz_mcts_set_forced_playouts");
+    return forced_set_locked(m, "oz_mcts_set_forced_playouts", k);
+}
+OZ_API int oz_mcts_get_forced_playouts(oz_mcts* m, double* k) {
+    OZ_REQUIRE(m && k, "null argument");
+    std::lock_guard<std::mutex> lk(m->mu);
+    *k = m->d.forced_k;
+    return OZ_OK;
+}
+// k_root_counts with the policy target's row: pruned where the slot's noise is armed (and k > 0), raw elsewhere
+__global__ __launch_bounds__(64) void k_pruned_counts(MctsDev t, int32_t* counts, uint64_t* legal_out, int32_t* rc_out) {
+    const int g = blockIdx.x, lane = threadIdx.x;
+    const uint64_t own = uni64(t.root_own[g]), opp = uni64(t.root_opp[g]);
+    const uint64_t legal = oz_legal(own, opp, t.valid);
+    const int node = root_lookup(t, g, own, opp, lane);
+    int cnt = 0, rc = 0;
+    if (node < 0) rc = 1;
+    else if (*rec_Ns(t, g, node) == 0) rc = 2;
+    else if ((legal >> lane) & 1)
+        cnt = (int)(rec_edge(t, g, node, oz_popc(legal & ((1ULL << lane) - 1ULL)))->n_tag & ~OZ_TAG_F32);
+    rc = unii(rc);
+    if (rc == 0 && t.forced_k > 0.0 && t.noise_eps > 0.0 && t.noise_armed && unii((int)t.noise_armed[g]) != 0)
+        cnt = forced_prune_lane(t, g, node, lane, legal, cnt, unii(wave_max_i32(cnt)), t.forced_k);
+    counts[(size_t)g * 64 + lane] = cnt;
+    if (lane == 0) { legal_out[g] = legal; rc_out[g] = rc; }
+}
+OZ_API int oz_mcts_pruned_counts(oz_mcts* m, int32_t* counts, uint64_t* legal, int32_t* rc) {
+    OZ_REQUIRE(m && counts && legal && rc, "null argument");
+    std::lock_guard<std::mutex> lk(m->mu);
+    hipSetDevice(m->device);
+    const int G = m->d.G;
+    int32_t* dc = m->rc_counts; uint64_t* dl = m->rc_legal; int32_t* dr = m->rc_rc;
+    hipLaunchKernelGGL(k_pruned_counts, dim3(G), dim3(64), 0, m->stream, m->d, dc, dl, dr);
+    OZ_HIP(hipGetLastError());
+    OZ_HIP(hipMemcpyAsync(counts, dc, 4ull * G * 64, hipMemcpyDeviceToHost, m->stream));
+    OZ_HIP(hipMemcpyAsync(legal, dl, 8ull * G, hipMemcpyDeviceToHost, m->stream));
+    OZ_HIP(hipMemcpyAsync(rc, dr, 4ull * G, hipMemcpyDeviceToHost, m->stream));
+    OZ_HIP(hipStreamSynchronize(m->stream));
+    return OZ_OK;
+}
+// oz_forced_prune over `count` rows, on the host: needs no device
+OZ_API int oz_forced_playouts_prune(const int32_t* N, const double* Q, const double* P, const double* eta, const uint64_t* legal, const int32_t* Ns,
+                                    int64_t count, double c, double eps, double k, int32_t* pruned) {
+    OZ_REQUIRE(count >= 0, "oz_forced_playouts_prune: count %lld", (long long)count);
+    if (int rc = forced_check("oz_forced_playouts_prune", k)) return rc;
+    OZ_REQUIRE(eps >= 0.0 && eps <= 1.0, "oz_forced_playouts_prune: eps %g outside [0, 1]", eps);
+    OZ_REQUIRE(c == c, "oz_forced_playouts_prune: c is NaN");
+    if (count == 0) return OZ_OK;
+    OZ_REQUIRE(N && Q && P && eta && legal && Ns && pruned, "oz_forced_playouts_prune: null argument");
+    for (int64_t i = 0; i < count; ++i) {
+        OZ_REQUIRE(Ns[i] >= 0, "oz_forced_playouts_prune: Ns[%lld] = %d", (long long)i, Ns[i]);
+        for (int sq = 0; sq < 64; ++sq)
+            OZ_REQUIRE(N[i * 64 + sq] >= 0, "oz_forced_playouts_prune: N[%lld][%d] = %d", (long long)i, sq, N[i * 64 + sq]);
+    }
+    for (int64_t i = 0; i < count; ++i) {
+        const int32_t* n = N + i * 64;
+        const double *q = Q + i * 64, *p = P + i * 64, *e = eta + i * 64;
+        int32_t* out = pruned + i * 64;
+        int star = -1;
+        for (int sq = 0; sq < 64; ++sq)
+            if (((legal[i] >> sq) & 1) && (star < 0 || n[sq] > n[star])) star = sq;          // the first legal square with the largest N
+        for (int sq = 0; sq < 64; ++sq)
+            out[sq] = ((legal[i] >> sq) & 1) ? oz_forced_prune(n[sq], q[sq], p[sq], e[sq], n[star], q[star], p[star], e[star], sq == star, Ns[i], c, eps, k) : 0;
+    }
+    return OZ_OK;
+}
+
 // move sampling on the current roots of the active slots (the drop-in path's move rule: the engine's sample_move, the same keys).
 // action[g] = the sampled square; -1 where rc[g] != 0 (rc as k_root_counts) and on an idle slot.
 __global__ __launch_bounds__(64) void k_sample_moves(MctsDev t, double temperature, uint64_t seed, const uint64_t* __restrict__ game_ids,
@@ -1894,10 +2021,16 @@ __global__ void k_sp_roots_stagger(GamesDev gm, MctsDev t, int round, int period
 // CAP (an engine with a playout cap, oz_selfplay_set_playout_cap; pc.fast_sims > 0 where it is on): the move's full / fast bit, oz_playout_budget
 // of (seed, game id, ply), goes into the move log next to `greedy` and from there into byte pad[0] of the game's records; one of two counters
 // counts the move.  The move rule itself does not look at the bit.  Never in the arena, never in a staggered round.
-template <bool NOISE = false, bool SAMPLE = false, bool CAP = false>
+// FORCE (an engine with forced playouts, oz_selfplay_set_forced_playouts; fp.k > 0 where it is on): on a root whose noise is armed -- read before
+// NOISE clears the flag -- the row that goes to log_counts / visits is the pruned one (forced_prune_lane) and three counters count it.  Everything
+// that chooses the move keeps reading the raw counts.  A fast move of a playout cap is unarmed: never pruned.  Never in the arena.
+template <bool NOISE = false, bool SAMPLE = false, bool CAP = false, bool FORCE = false>
 __device__ __forceinline__ void sp_move_body(const GamesDev& gm, const MctsDev& t, int g, int lane, int arena, MoveSampling ms = MoveSampling{},
-                                             PlayoutCap pc = PlayoutCap{}) {
+                                             PlayoutCap pc = PlayoutCap{}, ForcedPlayouts fp = ForcedPlayouts{}) {
     if (!t.active[g]) return;
+    bool prune = false;
+    (void)prune;
+    if constexpr (FORCE) prune = fp.k > 0.0 && t.noise_eps > 0.0 && t.noise_armed && unii((int)t.noise_armed[g]) != 0;
     if constexpr (NOISE) { if (lane == 0 && t.noise_armed) t.noise_armed[g] = 0; }
     const uint64_t own = uni64(t.root_own[g]), opp = uni64(t.root_opp[g]);
     const uint64_t legal = oz_legal(own, opp, t.valid);
@@ -1914,6 +2047,18 @@ __device__ __forceinline__ void sp_move_body(const GamesDev& gm, const MctsDev& 
     const size_t lb = (size_t)g * 64;
     const uint64_t gid = uni64(gm.game_id[g]);
     const int mx = unii(wave_max_i32(cnt));                      // >= 1 once the root has been selected from
+    int row = cnt;                                               // what the policy target keeps of cnt
+    if constexpr (FORCE) {
+        if (prune) {
+            row = forced_prune_lane(t, g, node, lane, legal, cnt, mx, fp.k);
+            const int raw = wave_sum_i32(cnt), kept = wave_sum_i32(row);
+            if (lane == 0) {
+                if (kept != raw) atomicAdd(&fp.stat[0], 1ULL);
+                atomicAdd(&fp.stat[1], (unsigned long long)raw);
+                atomicAdd(&fp.stat[2], (unsigned long long)kept);
+            }
+        }
+    }
     int action, greedy = 1;
     if (arena || gm.temperature == 0.0) {
         // bests = argwhere(p == p.max()) over the whole board; random.choice(bests) -> RNG_TIE stream
@@ -1986,10 +2131,10 @@ __device__ __forceinline__ void sp_move_body(const GamesDev& gm, const MctsDev& 
             // (the loop above has flagged EF_RECORDS for the rest).  This ply's row is still in registers.
             const long long room = gm.record_cap - (long long)base;
             for (int i = 0; i < nply && i < room; ++i)
-                gm.visits[(size_t)(base + i) * 64 + lane] = i == ply ? cnt : gm.log_counts[(lb + i) * 64 + lane];
+                gm.visits[(size_t)(base + i) * 64 + lane] = i == ply ? row : gm.log_counts[(lb + i) * 64 + lane];
         }
     } else if (gm.record_visits && ply < 64) {
-        gm.log_counts[(lb + ply) * 64 + lane] = cnt;
+        gm.log_counts[(lb + ply) * 64 + lane] = row;
     }
     if (lane == 0) atomicAdd(&gm.counters[2], 1ULL);
     if (fin && gm.refill) {
@@ -2012,6 +2157,11 @@ __global__ __launch_bounds__(64) void k_sp_move_s(GamesDev gm, MctsDev t, MoveSa
 // the self-play move of a lock-step round under a playout cap (with or without move sampling: ms.plies says)
 __global__ __launch_bounds__(64) void k_sp_move_c(GamesDev gm, MctsDev t, MoveSampling ms, PlayoutCap pc) {
     sp_move_body<false, true, true>(gm, t, blockIdx.x, threadIdx.x, 0, ms, pc);
+}
+// the self-play move of a lock-step round of an engine with forced playouts (with or without move sampling and a playout cap: ms.plies and
+// pc.fast_sims say; a staggered round passes a cap that is off)
+__global__ __launch_bounds__(64) void k_sp_move_f(GamesDev gm, MctsDev t, MoveSampling ms, PlayoutCap pc, ForcedPlayouts fp) {
+    sp_move_body<false, true, true, true>(gm, t, blockIdx.x, threadIdx.x, 0, ms, pc, fp);
 }
 
 // ---------------------------------------------------------------- free-running self-play step
@@ -2038,7 +2188,9 @@ __global__ __launch_bounds__(64) void k_sp_move_c(GamesDev gm, MctsDev t, MoveSa
 //   root noise: the noise of a game's root is drawn here, before the first descent from it (noise_armed[g] == 0: a fresh engine, or the move above
 //   has just changed the root), keyed (seed, game id, ply) like k_root_noise in the lock-step round: the records stay those of oz_selfplay_run.
 //   move sampling: sp_move_body<.., SAMPLE> is a function of the root's counts and (seed, game id, ply): the same records again.
-struct SelfplayExtras { double alpha; uint64_t seed; MoveSampling sample; PlayoutCap cap; };
+//   forced playouts: the descents force through t.forced_k, the move prunes its row while the root's noise is still armed (sp_move_body<.., FORCE>
+//   reads the flag before it clears it): a function of the root record and eta, the same rows again.
+struct SelfplayExtras { double alpha; uint64_t seed; MoveSampling sample; PlayoutCap cap; ForcedPlayouts forced; };
 template <bool EXTRAS = false>
 __device__ __forceinline__ void advance_body(const GamesDev& gm, const MctsDev& t, TreeLds& L, int g, int lane, int sims, int* __restrict__ sims_done, int cap,
                                              SelfplayExtras xt = SelfplayExtras{}) {
@@ -2065,7 +2217,7 @@ __device__ __forceinline__ void advance_body(const GamesDev& gm, const MctsDev& 
                 budget = oz_playout_budget(gm.seed, uni64(gm.game_id[g]), (uint64_t)unii(gm.ply[g]), sims, xt.cap.fast_sims, xt.cap.full_prob, &fast);
         }
         if (done >= budget) {                              // training.py:42-67: the move after num_simulations simulations
-            sp_move_body<EXTRAS, EXTRAS, EXTRAS>(gm, t, g, lane, 0, xt.sample, xt.cap);
+            sp_move_body<EXTRAS, EXTRAS, EXTRAS, EXTRAS>(gm, t, g, lane, 0, xt.sample, xt.cap, xt.forced);
             done = 0;
             if (lane == 0) t.leaf_status[g] = OZ_LEAF_IDLE;    // the evaluated leaf is consumed: nothing pending if the cap ends the loop here
             wave_sync();
@@ -2196,6 +2348,7 @@ struct oz_selfplay {
     double noise_alpha = 0.0;
     MoveSampling sample{0.0, 0};     // oz_selfplay_set_move_sampling: plies > 0 = on
     PlayoutCap cap{0, 0.0, nullptr, nullptr};      // oz_selfplay_set_playout_cap: fast_sims > 0 = on (the buffers stay once allocated)
+    ForcedPlayouts forced{0.0, nullptr};           // oz_selfplay_set_forced_playouts: k > 0 = on (the counters stay once allocated); m->d.forced_k holds the same k
     std::vector<void*> allocs;
     std::mutex mu;
     long long records_read = 0;
@@ -2324,7 +2477,8 @@ static int selfplay_round_async(oz_selfplay* sp, int sims, int stagger_round) {
         }
     } else if (int rc = mcts_steps_async(m, sp->net, sims, G, true, capped ? &ck : nullptr)) return rc;
     timed(m, TS_MOVE, m->profile, [&] {
-        if (capped) hipLaunchKernelGGL(k_sp_move_c, dim3(G), dim3(64), 0, s, sp->gm, m->d, sp->sample, sp->cap);
+        if (sp->forced.k > 0.0) hipLaunchKernelGGL(k_sp_move_f, dim3(G), dim3(64), 0, s, sp->gm, m->d, sp->sample, capped ? sp->cap : PlayoutCap{0, 0.0, nullptr, nullptr}, sp->forced);
+        else if (capped) hipLaunchKernelGGL(k_sp_move_c, dim3(G), dim3(64), 0, s, sp->gm, m->d, sp->sample, sp->cap);
         else if (sp->sample.plies > 0) hipLaunchKernelGGL(k_sp_move_s, dim3(G), dim3(64), 0, s, sp->gm, m->d, sp->sample);
         else hipLaunchKernelGGL(k_sp_move, dim3(G), dim3(64), 0, s, sp->gm, m->d, 0);
     });
@@ -2435,7 +2589,7 @@ OZ_API int oz_selfplay_set_root_noise(oz_selfplay* sp, double alpha, double eps)
     if (sp->mode != 0) { oz_set_error("oz_selfplay_set_root_noise: the engine has been driven already (set it before the first driver call)"); return OZ_ERR_STATE; }
     std::lock_guard<std::mutex> lkm(sp->m->mu);
     hipSetDevice(sp->m->device);
-    if (eps == 0.0) { sp->noise_on = false; return noise_disarm(sp->m); }
+    if (eps == 0.0) { sp->noise_on = false; sp->forced.k = 0.0; sp->m->d.forced_k = 0.0; return noise_disarm(sp->m); }       // (forced playouts go with the noise)
     if (int rc = noise_alloc(sp->m)) return rc;
     sp->m->d.noise_eps = eps;
     sp->noise_alpha = alpha; sp->noise_on = true;
@@ -2499,6 +2653,50 @@ OZ_API int oz_selfplay_get_playout_cap(oz_selfplay* sp, int* fast_sims, double* 
     if (fast_moves) *fast_moves = (int64_t)c[1];
     return OZ_OK;
 }
+// forced playouts for every searched move whose root draws noise (lock-step rounds at any leaves_per_step, oz_selfplay_stagger's included, and the
+// free-running driver); after oz_selfplay_set_root_noise, before the first driver call.  k == 0 switches off.  24 B at the first arming.
+OZ_API int oz_selfplay_set_forced_playouts(oz_selfplay* sp, double k) {
+    OZ_REQUIRE(sp, "null selfplay");
+    if (int rc = forced_check("oz_selfplay_set_forced_playouts", k)) return rc;
+    std::lock_guard<std::mutex> lk(sp->mu);
+    if (sp->mode != 0) { oz_set_error("oz_selfplay_set_forced_playouts: the engine has been driven already (set it before the first driver call)"); return OZ_ERR_STATE; }
+    if (k > 0.0 && !sp->noise_on) { oz_set_error("oz_selfplay_set_forced_playouts: forced playouts need root noise (oz_selfplay_set_root_noise first)"); return OZ_ERR_STATE; }
+    std::lock_guard<std::mutex> lkm(sp->m->mu);
+    if (k > 0.0 && !sp->forced.stat) {
+        hipSetDevice(sp->m->device);
+        const size_t held = sp->allocs.size();
+        unsigned long long* stat = nullptr;
+        int rc = sp->alloc(&stat, 3);
+        if (!rc && hipMemset(stat, 0, 3 * sizeof(unsigned long long)) != hipSuccess) {
+            oz_set_error("oz_selfplay_set_forced_playouts: clearing the counters failed");
+            rc = OZ_ERR_HIP;
+        }
+        if (rc) {
+            for (size_t i = held; i < sp->allocs.size(); ++i) hipFree(sp->allocs[i]);
+            sp->allocs.resize(held);
+            return rc;
+        }
+        sp->forced.stat = stat;
+    }
+    if (int rc = forced_set_locked(sp->m, "oz_selfplay_set_forced_playouts", k)) return rc;
+    sp->forced.k = k;
+    return OZ_OK;
+}
+OZ_API int oz_selfplay_get_forced_playouts(oz_selfplay* sp, double* k, int64_t* moves_pruned, int64_t* visits_raw, int64_t* visits_kept) {
+    OZ_REQUIRE(sp, "null selfplay");
+    std::lock_guard<std::mutex> lk(sp->mu);
+    if (k) *k = sp->forced.k;
+    unsigned long long c[3] = {0, 0, 0};
+    if ((moves_pruned || visits_raw || visits_kept) && sp->forced.stat) {
+        hipSetDevice(sp->m->device);
+        OZ_HIP(hipStreamSynchronize(sp->m->stream));
+        OZ_HIP(hipMemcpy(c, sp->forced.stat, sizeof c, hipMemcpyDeviceToHost));
+    }
+    if (moves_pruned) *moves_pruned = (int64_t)c[0];
+    if (visits_raw) *visits_raw = (int64_t)c[1];
+    if (visits_kept) *visits_kept = (int64_t)c[2];
+    return OZ_OK;
+}
 // oz_playout_budget over a batch, on the host: needs no device
 OZ_API int oz_playout_budgets(uint64_t seed, const uint64_t* game_ids, const int32_t* plies, int64_t count, int sims, int fast_sims, double full_prob,
                               int32_t* out) {
@@ -2551,7 +2749,7 @@ OZ_API int oz_selfplay_run_steps(oz_selfplay* sp, int steps) {
         // (from the second batch of a call on, the previous batch's expand + backup rides in the same launch; one closing k_expand_backup per call)
         timed(m, TS_SELECT, all, [&] {
             if (m->noise_ever || sp->sample.plies > 0 || sp->cap.fast_sims > 0) {
-                const SelfplayExtras xt{sp->noise_alpha, sp->gm.seed, sp->sample, sp->cap};
+                const SelfplayExtras xt{sp->noise_alpha, sp->gm.seed, sp->sample, sp->cap, sp->forced};
                 if (fuse && i > 0) hipLaunchKernelGGL(k_backup_advance_x, dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap, xt);
                 else hipLaunchKernelGGL(k_advance_x, dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap, xt);
             } else if (fuse && i > 0) hipLaunchKernelGGL(k_backup_advance, dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap);

@@ -262,15 +262,17 @@ def self_play_match(board_size, neural_network, old_neural_network, total_games,
 
 def _selfplay_into_replay(replay, neural_network, board_size, num_episodes, num_simulations, degree_exploration, temperature, e_greedy, seed,
                           first_game_id, q_mode, visits, leaves_per_step, root_noise, sample_moves, alias_final_boards, policy_target,
-                          target_temperature, endgame_targets=0, solve_leaves=0, playout_cap=None):
+                          target_temperature, endgame_targets=0, solve_leaves=0, playout_cap=None, forced_playouts=0.0):
     """one iteration's games on the engine selfplay_batch would create, played to the end without reading a record, and their examples
     appended to the device buffer; -> (records appended, the endgame solver's statistics or None).  One-channel (BaseNN) examples are never
     aliased (examples_from_records).  endgame_targets > 0: SelfPlayEngine.solve_records before the append.  playout_cap: the engine's; the
-    append leaves the fast records out and counts the fully searched ones."""
+    append leaves the fast records out and counts the fully searched ones.  forced_playouts: the engine's; its visit rows, which the append
+    reads, are then the pruned ones."""
     from .training import SelfPlayEngine
     eng = SelfPlayEngine(neural_network, board_size, num_episodes, num_simulations, degree_exploration, temperature, e_greedy, seed,
                          first_game_id, q_mode=q_mode, record_visits=visits, leaves_per_step=leaves_per_step, root_noise=root_noise,
-                         sample_moves=sample_moves, solve_leaves=solve_leaves, **({"playout_cap": playout_cap} if playout_cap is not None else {}))
+                         sample_moves=sample_moves, solve_leaves=solve_leaves, **({"playout_cap": playout_cap} if playout_cap is not None else {}),
+                         **({"forced_playouts": forced_playouts} if forced_playouts else {}))
     for _ in range(board_size * board_size):
         eng.run(4)
         if eng.stats()["live_games"] == 0:
@@ -293,7 +295,7 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
              seed=1234, reference_aliasing=True, alias_final_boards=True, dump_examples=False, q_mode=_lib.QMODE_F64,
              distributed=False, batched_evaluation=False, policy_target="onehot", target_temperature=1.0, leaves_per_step=1,
              root_noise=None, sample_moves=None, replay="host", evaluation_opponent="random", endgame_targets=0,
-             solve_leaves=0, match_openings=None, evaluation_openings=None, playout_cap=None):
+             solve_leaves=0, match_openings=None, evaluation_openings=None, playout_cap=None, forced_playouts=None):
     """main.py:56-259 on the GPU engines; returns `historic` = [(episodes done, win rate vs random), ...]
 
     batched_evaluation=True plays the evaluation games against RandomOthelloAgent in lock step on the GPU
@@ -368,9 +370,21 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
     one setting that has been measured: on an MI355X at 4 096 games of 8x8 it finishes 1.89 times as many games per second as the engine without
     it (2.03 times the moves at 40 simulations per move on average), while the fully searched records per second fall to 0.51 times -- a quarter
     of twice as many moves; expansions per second fall to 0.84 times because the capped games share fewer leaves for the cross-game
-    de-duplication to take out ("Playout cap"; tools/playout_cap_bench.py, profiles/playout_cap_bench.json)."""
+    de-duplication to take out ("Playout cap"; tools/playout_cap_bench.py, profiles/playout_cap_bench.json).
+
+    forced_playouts=k (None or 0 = off, the default; KataGo uses 2; needs root_noise): forced playouts and policy target pruning for the
+    SELF-PLAY searches (SelfPlayEngine), in the host path, the distributed path and with replay="device" alike.  At the noisy root every child
+    tried once is searched until it has sqrt(k * Pn * Ns) visits, so a move the noise favours is examined instead of abandoned; when the move
+    is played, the visits PUCT would not have granted are subtracted from the recorded row, so with policy_target="visits" the network trains
+    on what the search concluded, not on how it explored.  The visit rows ARE the pruned counts then: examples_from_records, expand_examples
+    and the device replay buffer read them unchanged.  The moves are still chosen from the raw counts; the fast moves of a playout cap,
+    matches and evaluations are neither forced nor pruned.  The reference has nothing like it (DESIGN.md, "Forced playouts";
+    tools/forced_playouts_bench.py, profiles/forced_playouts_bench.json)."""
     playout_cap = _lib.check_playout_cap(playout_cap, num_simulations)
     cap_kw = {"playout_cap": playout_cap} if playout_cap is not None else {}
+    forced_playouts = _lib.check_forced_playouts(forced_playouts, _lib.check_root_noise(root_noise))
+    if forced_playouts:
+        cap_kw["forced_playouts"] = forced_playouts
     _lib.check_opponent(evaluation_opponent)
     _lib.check_openings(match_openings)
     _lib.check_openings(evaluation_openings)
@@ -443,7 +457,7 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
             appended, endgame = _selfplay_into_replay(device_replay, neural_network, board_size, num_episodes, num_simulations,
                                                       degree_exploration, temperature, e_greedy, seed, total_episodes_done, q_mode, visits,
                                                       leaves_per_step, root_noise, sample_moves, alias_final_boards, policy_target,
-                                                      target_temperature, endgame_targets, solve_leaves, playout_cap)
+                                                      target_temperature, endgame_targets, solve_leaves, playout_cap, forced_playouts)
             if endgame is not None:
                 training.endgame_history.append(endgame)
                 _log_endgame(i, num_iterations, endgame)

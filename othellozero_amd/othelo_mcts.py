@@ -18,13 +18,18 @@ from .Othello import OthelloGame, OthelloPlayer
 
 class OthelloMCTS:
     def __init__(self, board_size, neural_network, degree_exploration, q_mode=_lib.QMODE_F64,
-                 node_cap=8192, leaves_per_step=1, solve_leaves=0):
+                 node_cap=8192, leaves_per_step=1, solve_leaves=0, forced_playouts=None):
         """q_mode: OZ_QMODE_F64 = the NumPy 1.18.5 promotion the reference pins (requirements.txt:19),
         OZ_QMODE_NEP50 = what NumPy >= 2 computes (SURVEY.md R-FP).
         leaves_per_step > 1 (native networks only, created with max_batch >= leaves_per_step): that many descents of the tree per
         network batch, kept apart by a virtual loss (oz_mcts_set_leaves_per_step); not the reference's search order.
         solve_leaves=E > 0 (native networks only): a leaf with at most E empties takes its exact win / draw / loss (+1 / 0 / -1 for the side
-        to move, oz_mcts_set_solve_leaves) in place of the network's value; the priors stay the network's.  Not the reference's search."""
+        to move, oz_mcts_set_solve_leaves) in place of the network's value; the priors stay the network's.  Not the reference's search.
+        forced_playouts=k > 0: KataGo's forced playouts on every root that carries noise (set_root_noise / sample_root_noise; without noise
+        the search is unchanged), and pruned_counts / get_policy_action_probabilities(..., pruned=True) give the pruned policy target
+        (oz_mcts_set_forced_playouts).  Not the reference's search."""
+        self.forced_playouts = _lib.check_forced_playouts(forced_playouts, need_noise=False)
+        self._forced_set = False
         self.solve_leaves = _lib.check_solve_leaves(solve_leaves)
         self._board_size = board_size
         self._neural_network = neural_network
@@ -107,6 +112,7 @@ class OthelloMCTS:
             if not (np.isfinite(row).all() and (row >= 0).all() and (row <= 1).all()):
                 raise ValueError("eta must lie in [0, 1]")
         _lib.check(_lib.load().oz_mcts_set_root_noise(self._h, epsilon, None if row is None else _lib.p_f64(row), None))
+        self._arm_forced(row is not None and epsilon > 0.0)
 
     def sample_root_noise(self, alpha, epsilon, seed, game_id, ply, state=None, player=None):
         """device-drawn Dirichlet(alpha) noise over the legal moves of the current root (or of `state` seen by `player`, which becomes the
@@ -116,6 +122,13 @@ class OthelloMCTS:
             self._set_root(*self._canonical(state, player))
         gid, pl = np.array([int(game_id)], np.uint64), np.array([int(ply)], np.int32)
         _lib.check(_lib.load().oz_mcts_sample_root_noise(self._h, alpha, epsilon, int(seed), _lib.p_u64(gid), _lib.p_i32(pl)))
+        self._arm_forced(epsilon > 0.0)
+
+    def _arm_forced(self, noisy):
+        """the library takes the forcing constant once noise is armed: hand it over at the first arming"""
+        if self.forced_playouts > 0.0 and noisy and not self._forced_set:
+            _lib.check(_lib.load().oz_mcts_set_forced_playouts(self._h, self.forced_playouts))
+            self._forced_set = True
 
     def root_noise(self):
         """(eta (64,) float64 by square, armed bool, epsilon) of the current root"""
@@ -168,13 +181,23 @@ class OthelloMCTS:
             _lib.check(lib.oz_mcts_backup(self._h, _lib.p_f32(pi), _lib.p_f32(v)))
         return self._last_value()
 
-    def _counts(self, state):
-        """visit counts of a mover-canonical state: (rc, counts[64], legal mask)"""
+    def _counts(self, state, pruned=False):
+        """visit counts of a mover-canonical state: (rc, counts[64], legal mask); pruned: the policy target's row (oz_mcts_pruned_counts)"""
         own, opp = _lib.pack_board(state)
         self._set_root(own, opp)
         cnt, legal, rc = np.zeros(64, np.int32), np.zeros(1, np.uint64), np.zeros(1, np.int32)
-        _lib.check(_lib.load().oz_mcts_root_counts(self._h, _lib.p_i32(cnt), _lib.p_u64(legal), _lib.p_i32(rc)))
+        fn = _lib.load().oz_mcts_pruned_counts if pruned else _lib.load().oz_mcts_root_counts
+        _lib.check(fn(self._h, _lib.p_i32(cnt), _lib.p_u64(legal), _lib.p_i32(rc)))
         return int(rc[0]), cnt, int(legal[0])
+
+    def pruned_counts(self, state):
+        """int32 (64,) by square: the visit counts of the mover-canonical `state` as the policy target keeps them -- pruned
+        (include/othellozero_amd.h, "forced playouts") while the state is the root and carries noise and forced_playouts is on, the raw counts
+        otherwise.  KeyError if the state is unknown or was never selected from."""
+        rc, cnt, _ = self._counts(state, pruned=True)
+        if rc != 0:
+            raise KeyError("state is unknown to the search or was never selected from")
+        return cnt
 
     def N(self, state, action=None):
         """MCTS/__init__.py:73-84,172-175: 0 for an unknown state, Ns without an action, Nsa[action] otherwise
@@ -193,10 +216,11 @@ class OthelloMCTS:
         """othelo_mcts.py:40-41: legal actions of BLACK (= channel 0) as tuples, ascending row-major."""
         return [tuple(int(x) for x in a) for a in OthelloGame.get_player_valid_actions(state, OthelloPlayer.BLACK)]
 
-    def get_policy_action_probabilities(self, state, temperature):
-        """othelo_mcts.py:51-67, evaluated with the same NumPy / random calls as the reference."""
+    def get_policy_action_probabilities(self, state, temperature, pruned=False):
+        """othelo_mcts.py:51-67, evaluated with the same NumPy / random calls as the reference.  pruned=True: over pruned_counts(state), the
+        policy target of a search with forced playouts."""
         n = self._board_size
-        rc, cnt, legal = self._counts(state)
+        rc, cnt, legal = self._counts(state, pruned)
         if rc == 2:
             raise KeyError("state was expanded but never selected from (num_simulations < 2)")
         probabilities = np.zeros((n, n))

@@ -32,7 +32,8 @@ def training_example_symmetries(board, policy):
 
 def execute_episode(board_size, neural_network, degree_exploration, num_simulations, policy_temperature, e_greedy,
                     q_mode=_lib.QMODE_F64, snapshot_boards=False, policy_target="onehot", target_temperature=1.0,
-                    leaves_per_step=1, root_noise=None, noise_seed=0, sample_moves=None, sample_seed=0, solve_leaves=0):
+                    leaves_per_step=1, root_noise=None, noise_seed=0, sample_moves=None, sample_seed=0, solve_leaves=0,
+                    forced_playouts=None):
     """training.py:26-72.  Returns [(board (n,n,2) bool, one-hot policy (n,n) float64, z int), ...], 8 per move.
 
     snapshot_boards=False reproduces the reference exactly, including its aliasing quirk: the
@@ -53,9 +54,13 @@ def execute_episode(board_size, neural_network, degree_exploration, num_simulati
     without it.
 
     solve_leaves=E > 0: the search takes the exact win / draw / loss of a leaf with at most E empties in place of the network's value
-    (OthelloMCTS); a native network only."""
+    (OthelloMCTS); a native network only.
+
+    forced_playouts=k > 0 (needs root_noise): KataGo's forced playouts in every move's search, and with policy_target="visits" the stored
+    distribution is that of the pruned counts (OthelloMCTS.pruned_counts); the move is still chosen from the raw counts."""
     solve_leaves = _lib.check_solve_leaves(solve_leaves)
     root_noise = _lib.check_root_noise(root_noise)
+    forced_playouts = _lib.check_forced_playouts(forced_playouts, root_noise)
     sample_moves = _lib.check_sample_moves(sample_moves)
     assert policy_target in ("onehot", "visits"), policy_target
     if policy_target == "visits" and not target_temperature > 0:
@@ -64,7 +69,7 @@ def execute_episode(board_size, neural_network, degree_exploration, num_simulati
     game = OthelloGame(board_size)
     mcts = OthelloMCTS(board_size, neural_network, degree_exploration, q_mode=q_mode,
                        node_cap=num_simulations * (board_size * board_size - 3) + 64, leaves_per_step=leaves_per_step,
-                       solve_leaves=solve_leaves)
+                       solve_leaves=solve_leaves, forced_playouts=forced_playouts)
     # training.py:34-37 (BNN examples are one-channel boards, a fresh array per round: no aliasing for them)
     board_view_type = BoardView.ONE_CHANNEL if getattr(neural_network.network_type, "name", "") == "BNN" else BoardView.TWO_CHANNELS
 
@@ -89,7 +94,7 @@ def execute_episode(board_size, neural_network, degree_exploration, num_simulati
         action_choosed = np.zeros((board_size, board_size))
         action_choosed[action[0]][action[1]] = 1
         if policy_target == "visits":
-            action_choosed = mcts.get_policy_action_probabilities(state, target_temperature)
+            action_choosed = mcts.get_policy_action_probabilities(state, target_temperature, pruned=forced_playouts > 0.0)
         board_now = game.board(board_view_type)
         if snapshot_boards:
             board_now = np.copy(board_now)
@@ -145,7 +150,8 @@ class SelfPlayEngine:
     def __init__(self, neural_network, board_size=8, num_games=4096, num_simulations=100, degree_exploration=1.0,
                  policy_temperature=1.0, e_greedy=0.9, seed=1234, first_game_id=0, game_id_stride=0,
                  q_mode=_lib.QMODE_F64, refill=False, node_cap=0, record_cap=0, dedup=True, batch_cap=0, eval_cache=False,
-                 record_visits=False, leaves_per_step=1, root_noise=None, sample_moves=None, solve_leaves=0, playout_cap=None):
+                 record_visits=False, leaves_per_step=1, root_noise=None, sample_moves=None, solve_leaves=0, playout_cap=None,
+                 forced_playouts=None):
         """dedup: cross-game leaf de-duplication (a board several games reach in one batch is evaluated once; no record changes);
         batch_cap: leaves per network batch of the free-running driver (0 = none; see preferred_batch_cap);
         eval_cache: take (pi, v) of boards the network has evaluated before from its persistent cache (NNetWrapper.set_eval_cache) --
@@ -171,10 +177,17 @@ class SelfPlayEngine:
         loop.examples_from_records, ReplayBuffer.append_*) train on the fully searched moves only, while every game still ends in an outcome
         for them.  run() at any leaves_per_step and run_steps() alike; stagger()'s rounds are not capped; playout_stats() counts the moves.
         full_prob = 1 plays the games of the engine without the option.  Measured at (20, 0.25), 4 096 games of 8x8 at 100 simulations:
-        1.89 times the finished games per second, 0.51 times the fully searched records per second ("Playout cap")."""
+        1.89 times the finished games per second, 0.51 times the fully searched records per second ("Playout cap").
+        forced_playouts=k > 0 (None or 0 = off; needs root_noise): KataGo's forced playouts and policy target pruning
+        (oz_selfplay_set_forced_playouts).  At the noisy root a child tried once is searched until it has sqrt(k * Pn * Ns) visits, and with
+        record_visits the rows of records(with_visits=True) hold the PRUNED counts -- the visits PUCT would not have granted are taken out, a
+        child cut down to one visit is dropped -- so everything downstream (expand_examples, the replay buffers) trains on what the search
+        concluded.  last_counts() and the moves stay on the raw counts.  run(), run_steps() and stagger() alike; the fast moves of a playout
+        cap are neither forced nor pruned.  forced_playout_stats() counts ("Forced playouts")."""
         playout_cap = _lib.check_playout_cap(playout_cap, num_simulations)
         solve_leaves = _lib.check_solve_leaves(solve_leaves)
         root_noise = _lib.check_root_noise(root_noise)
+        forced_playouts = _lib.check_forced_playouts(forced_playouts, root_noise)
         sample_moves = _lib.check_sample_moves(sample_moves)
         lib = _lib.require_gpu()
         assert getattr(neural_network, "_h", None) is not None, "SelfPlayEngine needs a native NNetWrapper / StubNetWrapper"
@@ -203,6 +216,16 @@ class SelfPlayEngine:
         self.playout_cap = playout_cap
         if playout_cap is not None:
             _lib.check(lib.oz_selfplay_set_playout_cap(self._h, playout_cap[0], playout_cap[1]))
+        self.forced_playouts = forced_playouts
+        if forced_playouts > 0.0:
+            _lib.check(lib.oz_selfplay_set_forced_playouts(self._h, forced_playouts))
+
+    def forced_playout_stats(self):
+        """dict(k, moves_pruned, visits_raw, visits_kept): the forcing constant that is set (0 = off), the moves whose recorded row differs
+        from their raw counts, and the visits before / after pruning summed over every move pruning ran on (the moves with a noisy root)"""
+        k, moves, raw, kept = C.c_double(), C.c_int64(), C.c_int64(), C.c_int64()
+        _lib.check(_lib.load().oz_selfplay_get_forced_playouts(self._h, C.byref(k), C.byref(moves), C.byref(raw), C.byref(kept)))
+        return dict(k=k.value, moves_pruned=moves.value, visits_raw=raw.value, visits_kept=kept.value)
 
     def playout_stats(self):
         """dict(fast_sims, full_prob, full_moves, fast_moves): the playout cap that is set (fast_sims 0 = none) and the moves run() /
@@ -422,7 +445,7 @@ def expand_examples(records, board_size, alias_final=False, visits=None, target_
 def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations=100, degree_exploration=1.0,
                    policy_temperature=1.0, e_greedy=0.9, seed=1234, first_game_id=0, q_mode=_lib.QMODE_F64,
                    expand=False, alias_final=False, record_visits=False, target_temperature=1.0, leaves_per_step=1, root_noise=None,
-                   sample_moves=None, endgame_targets=0, solve_leaves=0, playout_cap=None):
+                   sample_moves=None, endgame_targets=0, solve_leaves=0, playout_cap=None, forced_playouts=None):
     """Play num_games complete games; returns the move records (or the expanded examples).
     record_visits=True: (records, visit counts) -- or, with expand, the examples with visit-distribution targets at target_temperature.
     root_noise=(alpha, epsilon): Dirichlet root noise in every search (SelfPlayEngine).
@@ -433,21 +456,28 @@ def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations
     last call's count (None when off).
     playout_cap=(fast_sims, full_prob): a playout cap on the searched moves (SelfPlayEngine).  The records returned are ALL records, the fast
     ones flagged (_lib.record_fast); with expand, the examples of the fully searched moves only.  selfplay_batch.playout_stats holds the last
-    call's SelfPlayEngine.playout_stats() (None when off)."""
+    call's SelfPlayEngine.playout_stats() (None when off).
+    forced_playouts=k > 0 (needs root_noise): forced playouts and policy target pruning (SelfPlayEngine): with record_visits the counts
+    returned, and the targets expanded from them, are the pruned ones.  selfplay_batch.forced_playout_stats holds the last call's
+    SelfPlayEngine.forced_playout_stats() (None when off)."""
+    forced_playouts = _lib.check_forced_playouts(forced_playouts, _lib.check_root_noise(root_noise))
     playout_cap = _lib.check_playout_cap(playout_cap, num_simulations)
     solve_leaves = _lib.check_solve_leaves(solve_leaves)
     endgame_targets = _lib.check_endgame_targets(endgame_targets, expand and alias_final)
     eng = SelfPlayEngine(neural_network, board_size, num_games, num_simulations, degree_exploration, policy_temperature,
                          e_greedy, seed, first_game_id, q_mode=q_mode, record_visits=record_visits, leaves_per_step=leaves_per_step,
-                         root_noise=root_noise, sample_moves=sample_moves, solve_leaves=solve_leaves, playout_cap=playout_cap)
-    selfplay_batch.endgame_stats = selfplay_batch.rows_solved = selfplay_batch.playout_stats = None
+                         root_noise=root_noise, sample_moves=sample_moves, solve_leaves=solve_leaves, playout_cap=playout_cap,
+                         **({"forced_playouts": forced_playouts} if forced_playouts > 0.0 else {}))
+    selfplay_batch.endgame_stats = selfplay_batch.rows_solved = selfplay_batch.playout_stats = selfplay_batch.forced_playout_stats = None
     if record_visits:
         rec, counts = eng.play_to_end(with_visits=True, endgame_targets=endgame_targets)
+        selfplay_batch.forced_playout_stats = eng.forced_playout_stats() if forced_playouts > 0.0 else None
         selfplay_batch.playout_stats = eng.playout_stats() if playout_cap is not None else None
         selfplay_batch.rows_solved = eng.rows_solved() if solve_leaves else None
         selfplay_batch.endgame_stats = getattr(eng, "endgame_stats", None)
         return expand_examples(rec, board_size, alias_final, visits=counts, target_temperature=target_temperature) if expand else (rec, counts)
     rec = eng.play_to_end(endgame_targets=endgame_targets)
+    selfplay_batch.forced_playout_stats = eng.forced_playout_stats() if forced_playouts > 0.0 else None
     selfplay_batch.playout_stats = eng.playout_stats() if playout_cap is not None else None
     selfplay_batch.rows_solved = eng.rows_solved() if solve_leaves else None
     selfplay_batch.endgame_stats = getattr(eng, "endgame_stats", None)
