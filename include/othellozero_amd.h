@@ -185,6 +185,35 @@ int oz_net_set_tables(oz_net* net, int mode);
  * serialised by the network's mutex, their streams are not, and an entry one engine replaces could be read half-written by the other. */
 int oz_net_set_eval_cache(oz_net* net, int64_t entries);
 int oz_net_eval_cache_stats(oz_net* net, int64_t* entries, int64_t* lookups, int64_t* hits, int64_t* inserts);
+/* ---- evaluation symmetry: evaluate a position in a dihedral symmetry of the board (opt-in; off, every forward issues exactly the launches it
+ * issued before; the reference has none).  AlphaZero and KataGo evaluate every leaf in a randomly chosen orientation, so that a network that is
+ * only approximately equivariant does not show the search the same orientation bias in every game.  Here the orientation is no draw per call:
+ *     f_sym(own, opp) = S_t^-1( f( S_t(own), S_t(opp) ) ),   t = oz_eval_symmetry(seed, own, opp) = sm64(sm64(seed ^ own) + opp) >> 61
+ * (csrc/oz_common.h), a pure function of the position and a seed that lives in the NETWORK.  The network stays a deterministic function of the
+ * board, so batch-position bit-identity, the searches' de-duplication, the evaluation cache and the transposition tables hold unchanged; a
+ * search evaluates a position once, so "random per position" differs from "random per evaluation" only across searches -- give every iteration
+ * a new seed.  Orientations are numbered as the training symmetries (oz_symmetry_table; 7 = the identity): cell (r, c) of the board in
+ * orientation t is cell src_t(r, c) of the original, and pi[src_t(r, c)] = pi_t[r * n + c].
+ * OZ_EVAL_SYM_RANDOM: one orientation per position, two small launches around the forward.  OZ_EVAL_SYM_MEAN: all eight, pi and v their float32 mean
+ * 0.125f * (((x_0 + x_1) + x_2) + ... + x_7) with x_t mapped back to the original cells -- the smoother evaluator for matches and measurements at 8x
+ * the network work; a call of `count` positions then needs 8 * count <= max_batch (OZ_ERR_ARG otherwise), so a search needs a network with
+ * max_batch >= 8 * games * leaves_per_step.
+ * oz_net_set_eval_symmetry takes the network's mutex, synchronises the device, allocates the scratch boards (and outputs) on first use and empties
+ * the evaluation cache; modes other than the three are refused.  The setting is part of the network: it survives oz_net_set_weight and
+ * oz_net_commit, and every caller of the network sees it -- the searches, the self-play drivers, the arenas, oz_net_predict / _predict_boards and
+ * oz_net_time_forward (which then times the transform kernels too).  oz_net_get_activation and oz_net_get_info then describe the TRANSFORMED batch
+ * (RANDOM: the boards in their orientations, in call order; MEAN: rows 8 i + t = position i in orientation t).  Commit-time calibration, the f16x2
+ * self-check and the table builds never see the option.  Engines that share a network must not run concurrently (as with the evaluation cache). */
+enum { OZ_EVAL_SYM_OFF = 0, OZ_EVAL_SYM_RANDOM = 1, OZ_EVAL_SYM_MEAN = 2 };
+int oz_net_set_eval_symmetry(oz_net* net, int mode, uint64_t seed);
+int oz_net_get_eval_symmetry(oz_net* net, int* mode, uint64_t* seed);
+/* HIP-event timing of the two kernels of the option on the stream they are launched on: enable != 0 switches it on for the forwards that follow;
+ * ms_total[2] / launches[2] (either may be null) receive the totals so far, slot 0 = k_sym_boards, 1 = k_sym_policy; reset != 0 zeroes them. */
+int oz_net_eval_symmetry_profile(oz_net* net, int enable, double* ms_total /* [2] */, int64_t* launches /* [2] */, int reset);
+/* host only, no GPU needed: the two functions above as the kernels evaluate them.  t_out[i] = oz_eval_symmetry(seed, own[i], opp[i]);
+ * out[i] = boards[i] in orientation t[i] on an n x n board (bits outside the n x n corner are 0; t outside 0 .. 7 is refused). */
+int oz_eval_symmetries(uint64_t seed, const uint64_t* own, const uint64_t* opp, int64_t count, int32_t* t_out);
+int oz_sym_boards(const int32_t* t, int n, const uint64_t* boards, int64_t count, uint64_t* out);
 /* diagnostics switch, per network (default 0): the 3x3 convolutions of precision f16x2 on the one-barrier-per-k-tile main loop instead of
  * the ping-pong loops (4-phase on the 256-row tile, 2-phase on the 192- and 128-row tiles).  Same accumulation order, bit-identical results: the reference form the LDS-DMA race screen
  * (tools/pp_race_check.py, test_pingpong_conv_loop_bit_identical_to_simple_loop) compares the ping-pong schedule against. */

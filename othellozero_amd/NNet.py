@@ -247,9 +247,13 @@ class NNetWrapper(_NetHandle):
         self.set_weights(flat)
 
     def copy(self):
-        return NNetWrapper((self.board_size_x, self.board_size_y), network=self.network_type,
-                           num_channels_1=self.num_channels, max_batch=self.max_batch, weights=self.get_weights(),
-                           precision=self.precision, train_precision=self.train_precision, policy_loss=self.policy_loss)
+        net = NNetWrapper((self.board_size_x, self.board_size_y), network=self.network_type,
+                          num_channels_1=self.num_channels, max_batch=self.max_batch, weights=self.get_weights(),
+                          precision=self.precision, train_precision=self.train_precision, policy_loss=self.policy_loss)
+        mode, seed = self.eval_symmetry()
+        if mode != "off" or seed:
+            net.set_eval_symmetry(mode, seed)          # the evaluation symmetry is part of the network
+        return net
 
     # ---- profiling hooks used by bench.py
     def time_forward(self, count, iters=3):
@@ -281,6 +285,28 @@ class NNetWrapper(_NetHandle):
         """persistent exact-key evaluation cache of this network for up to ~`entries` positions (0 frees it); used by engines created with
         eval_cache=True, emptied whenever the weights change"""
         _lib.check(_lib.load().oz_net_set_eval_cache(self._h, int(entries)))
+
+    def set_eval_symmetry(self, mode, seed=0):
+        """the orientation this network evaluates a position in (oz_net_set_eval_symmetry): None / "off" = as given; "random" = the dihedral
+        symmetry oz_eval_symmetry(seed, own, opp) of the board, a pure function of the position and the seed -- what AlphaZero and KataGo draw
+        per evaluation, here without giving up a deterministic network; "mean" = all eight and the float32 mean of (pi, v), for matches and
+        measurements (8x the network work; a call of k positions needs 8 k <= max_batch).  Part of the network: every search, engine, arena
+        and predict call that uses it sees the setting; it survives set_weights / train and travels with copy().  Empties the evaluation cache."""
+        code, seed = _lib.check_eval_symmetry(mode, seed)
+        _lib.check(_lib.load().oz_net_set_eval_symmetry(self._h, code, seed))
+
+    def eval_symmetry(self):
+        """(mode, seed) as set_eval_symmetry takes them; ("off", 0) for a network whose option was never touched"""
+        m, s = C.c_int(), C.c_uint64()
+        _lib.check(_lib.load().oz_net_get_eval_symmetry(self._h, C.byref(m), C.byref(s)))
+        return _lib.EVAL_SYM_NAMES[m.value], int(s.value)
+
+    def eval_symmetry_profile(self, enable=True, reset=False):
+        """HIP-event timing of the option's two kernels: switches it on / off for the forwards that follow and returns what was timed so far,
+        {"k_sym_boards": (ms_total, launches), "k_sym_policy": (ms_total, launches)}"""
+        ms, cnt = np.zeros(2, np.float64), np.zeros(2, np.int64)
+        _lib.check(_lib.load().oz_net_eval_symmetry_profile(self._h, 1 if enable else 0, _lib.p_f64(ms), _lib.p_i64(cnt), 1 if reset else 0))
+        return {"k_sym_boards": (float(ms[0]), int(cnt[0])), "k_sym_policy": (float(ms[1]), int(cnt[1]))}
 
     def eval_cache_stats(self):
         e, l, h, i = (C.c_int64() for _ in range(4))
@@ -386,3 +412,6 @@ class StubNetWrapper(_NetHandle):
     predict = NNetWrapper.predict
     set_eval_cache = NNetWrapper.set_eval_cache
     eval_cache_stats = NNetWrapper.eval_cache_stats
+    set_eval_symmetry = NNetWrapper.set_eval_symmetry
+    eval_symmetry = NNetWrapper.eval_symmetry
+    eval_symmetry_profile = NNetWrapper.eval_symmetry_profile

@@ -139,6 +139,9 @@ SIGNATURES = {
     "oz_net_profiled_layer": [_vp, C.POINTER(C.c_int)], "oz_net_set_tables": [_vp, C.c_int],
     "oz_net_profile_kernels": [_vp, _f64p, _i64p, C.c_int],
     "oz_net_set_eval_cache": [_vp, C.c_int64], "oz_net_eval_cache_stats": [_vp, _i64p, _i64p, _i64p, _i64p],
+    "oz_net_set_eval_symmetry": [_vp, C.c_int, C.c_uint64], "oz_net_get_eval_symmetry": [_vp, C.POINTER(C.c_int), _u64p],
+    "oz_net_eval_symmetry_profile": [_vp, C.c_int, _f64p, _i64p, C.c_int],
+    "oz_eval_symmetries": [C.c_uint64, _u64p, _u64p, C.c_int64, _i32p], "oz_sym_boards": [_i32p, C.c_int, _u64p, C.c_int64, _u64p],
     "oz_net_set_option": [_vp, C.c_int, C.c_int], "oz_net_get_info": [_vp, C.c_int, C.POINTER(C.c_int)],
     "oz_net_get_scaling": [_vp, C.c_int, _i32p, C.c_int64],
     "oz_net_get_activation": [_vp, C.c_int, C.c_int64, C.c_int64, _f64p],
@@ -384,6 +387,23 @@ def check_forced_playouts(forced_playouts, root_noise=None, need_noise=True):
     if k > 0.0 and need_noise and (root_noise is None or not root_noise[1] > 0.0):
         raise ValueError("forced_playouts needs root_noise=(alpha, epsilon > 0): forcing and pruning are rules of the noisy root")
     return k
+
+
+EVAL_SYM_OFF, EVAL_SYM_RANDOM, EVAL_SYM_MEAN = 0, 1, 2       # oz_net_set_eval_symmetry
+EVAL_SYM_MODES = {"off": EVAL_SYM_OFF, "random": EVAL_SYM_RANDOM, "mean": EVAL_SYM_MEAN}
+EVAL_SYM_NAMES = {v: k for k, v in EVAL_SYM_MODES.items()}
+
+
+def check_eval_symmetry(mode, seed=0):
+    """mode = None, "off", "random" or "mean", seed a whole number in [0, 2^64): the orientation a network evaluates a position in
+    (include/othellozero_amd.h, "evaluation symmetry").  Returns (OZ_EVAL_SYM_* code, seed); ValueError for anything else."""
+    if mode is None:
+        mode = "off"
+    if not isinstance(mode, str) or mode not in EVAL_SYM_MODES:
+        raise ValueError(f'eval_symmetry: mode must be None, "off", "random" or "mean" (got {mode!r})')
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
+        raise ValueError(f"eval_symmetry: seed must be a whole number in [0, 2^64) (got {seed!r})")
+    return EVAL_SYM_MODES[mode], int(seed)
 
 
 def check_sample_moves(sample_moves):

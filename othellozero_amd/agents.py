@@ -99,6 +99,29 @@ def rules_prune_counts(N, Q, P, eta, legal, Ns, c, epsilon, k):
     return pruned
 
 
+def rules_eval_symmetries(own, opp, seed):
+    """oz_eval_symmetries on the host (no GPU needed): the orientation t in 0..7 (int32) a network set to ("random", seed) evaluates each
+    mover-canonical position (own[i], opp[i]) in -- the function the kernels evaluate"""
+    _, seed = _lib.check_eval_symmetry("random", seed)
+    own = np.ascontiguousarray(own, dtype=np.uint64).ravel()
+    opp = np.ascontiguousarray(opp, dtype=np.uint64).ravel()
+    if own.size != opp.size:
+        raise ValueError(f"rules_eval_symmetries: {own.size} own boards, {opp.size} opp boards")
+    t = np.zeros(own.size, np.int32)
+    _lib.check(_lib.load().oz_eval_symmetries(seed, _lib.p_u64(own), _lib.p_u64(opp), own.size, _lib.p_i32(t)))
+    return t
+
+
+def rules_sym_boards(boards, n, t):
+    """oz_sym_boards on the host (no GPU needed): the bitboards `boards` of an n x n board in orientation t (one number, or one per board;
+    the numbering of the training symmetries, 7 = the identity) -> uint64, same shape"""
+    b = np.ascontiguousarray(boards, dtype=np.uint64)
+    tt = np.ascontiguousarray(np.broadcast_to(np.asarray(t, dtype=np.int32), b.shape)).ravel()
+    out = np.zeros(b.size, np.uint64)
+    _lib.check(_lib.load().oz_sym_boards(_lib.p_i32(tt), int(n), _lib.p_u64(b.ravel()), b.size, _lib.p_u64(out)))
+    return out.reshape(b.shape)
+
+
 def rules_random_openings(n, count, plies, seed, first_opening_id=0):
     """oz_rules_random_openings: the random openings first_opening_id .. first_opening_id + count - 1 of (plies, seed) on the n x n board, what
     arena_batch(openings=(plies, seed), first_opening_id=...) lets its games start with.  -> dict(black, white uint64 (count,) = the position

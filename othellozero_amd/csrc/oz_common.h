@@ -202,6 +202,23 @@ OZ_HD int oz_sym_src(int t, int n, int r, int c) {
     return rr * n + cc;
 }
 
+// ---------------------------------------------------------------- evaluation symmetry
+// (include/othellozero_amd.h, "evaluation symmetry").  The orientation a position is evaluated in: a pure function of the position and a
+// seed, so that a network with the option on is still a deterministic function of the board.  The one definition the kernels (oz_net.hip)
+// and the host's oz_eval_symmetries share.
+OZ_HD int oz_eval_symmetry(uint64_t seed, uint64_t own, uint64_t opp) { return (int)(oz_sm64(oz_sm64(seed ^ own) + opp) >> 61); }
+// the bitboard b in orientation t (the numbering of oz_sym_src; t = 7 is the identity): bit r*8+c of the result, r, c < n, is the bit of b at
+// the cell oz_sym_src(t, n, r, c); bits outside the n x n corner are 0.  Shared with the host's oz_sym_boards.
+OZ_HD uint64_t oz_sym_board(int t, int n, uint64_t b) {
+    uint64_t out = 0;
+    for (int r = 0; r < n; ++r)
+        for (int c = 0; c < n; ++c) {
+            const int src = oz_sym_src(t, n, r, c);
+            out |= ((b >> ((src / n) * 8 + src % n)) & 1ULL) << (r * 8 + c);
+        }
+    return out;
+}
+
 // N ** (1 / T) of get_policy_action_probabilities (othelo_mcts.py:59-60) for a visit count.  k = 1 / T where that is an integer (else 0):
 // the product of k factors is exact while it stays <= 2^53 (every partial product is then an integer below it), so it equals the
 // correctly rounded power the host computes; beyond that, and for any other exponent, the device's pow.

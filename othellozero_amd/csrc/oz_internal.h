@@ -132,15 +132,32 @@ struct oz_net {
         hipFree(ec.keys); hipFree(ec.pi); hipFree(ec.v); hipFree(ec.stamp); hipFree(ec.counters);
         ec = EvalCacheDev();
     }
+    // evaluation symmetry (oz_net_set_eval_symmetry): the orientation a position is evaluated in is oz_eval_symmetry(es_seed, own, opp), or all
+    // eight and their mean.  Scratch lives with the network, allocated when the option is first set: es_boards = own[max_batch] | opp[max_batch]
+    // in the evaluated orientations, es_out = pi[max_batch][n*n] | v[max_batch] of the eight orientations (MEAN only), es_count = 8 * *d_count (MEAN)
+    int es_mode = OZ_EVAL_SYM_OFF;
+    uint64_t es_seed = 0;
+    uint64_t* es_boards = nullptr;
+    float* es_out = nullptr;
+    int* es_count = nullptr;
+    int es_profile = 0;                     // oz_net_eval_symmetry_profile: HIP events around the two kernels, slot 0 = k_sym_boards, 1 = k_sym_policy
+    OzTimer es_timer{2};
     virtual ~oz_net() {
+        if (es_boards || es_out || es_count) { hipSetDevice(device); hipFree(es_boards); hipFree(es_out); hipFree(es_count); }
+        es_timer.destroy();
         if (p_in) { hipSetDevice(device); hipFree(p_in); hipFree(p_out); }
         if (hp_in) { hipSetDevice(device); hipHostFree(hp_in); hipHostFree(hp_out); hipFree(d_counts); }
         free_eval_cache();
     }
     virtual int check() { return 0; }      // sticky device-side validity flags (f16x2 range)
     virtual const int* flag_device() { return nullptr; }     // the device word check() reads (nullptr: nothing to check)
-    virtual int forward_device(const uint64_t* d_own, const uint64_t* d_opp, const int* d_count, int max_count,
-                               float* d_pi, float* d_v, hipStream_t s) = 0;
+    // the network itself on the caller's boards: what commit-time calibration, the f16x2 self-check and the table builds run, whatever the option says
+    virtual int forward_raw(const uint64_t* d_own, const uint64_t* d_opp, const int* d_count, int max_count,
+                            float* d_pi, float* d_v, hipStream_t s) = 0;
+    // the evaluator every search, arena and predict call uses: forward_raw under the evaluation symmetry (oz_net.hip); with the option off it
+    // IS forward_raw on the caller's pointers and launches nothing else
+    int forward_device(const uint64_t* d_own, const uint64_t* d_opp, const int* d_count, int max_count,
+                       float* d_pi, float* d_v, hipStream_t s);
 };
 
 int oz_net_forward_device(oz_net* net, const uint64_t* d_own, const uint64_t* d_opp, const int* d_count,

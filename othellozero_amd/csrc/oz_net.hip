@@ -824,11 +824,65 @@ __global__ __launch_bounds__(64) void k_stub(const uint64_t* __restrict__ own, c
     }
 }
 
+// ---------------------------------------------------------------- evaluation symmetry (include/othellozero_amd.h, "evaluation symmetry")
+// Rows [0, *d_count) of (own, opp) in the orientation they are evaluated in, into the network's scratch boards.  RANDOM: row i in orientation
+// oz_eval_symmetry(seed, own[i], opp[i]); MEAN: rows 8 i + t = row i in orientation t, and 8 * *d_count into out_count.  One wavefront per
+// output row, lane = bit r*8+c of the result: the bit of the input at cell oz_sym_src(t, n, r, c), gathered by a ballot -- oz_sym_board
+// (oz_common.h) with its loop spread over the lanes.  cap = the rows the scratch holds for this call.  own / opp may be pinned host memory
+// (oz_net::hp_in): they are only read.
+__global__ __launch_bounds__(256) void k_sym_boards(const uint64_t* own, const uint64_t* opp, const int* __restrict__ d_count, int cap, int n, int mode,
+                                                    uint64_t seed, uint64_t* __restrict__ out_own, uint64_t* __restrict__ out_opp,
+                                                    int* __restrict__ out_count) {
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int count = *d_count;
+    const bool mean = mode == OZ_EVAL_SYM_MEAN;
+    if (mean && blockIdx.x == 0 && threadIdx.x == 0) *out_count = 8 * count;
+    if (i >= cap || i >= (mean ? 8 * count : count)) return;                // (wave-uniform)
+    const int b = mean ? i >> 3 : i;
+    const uint64_t o = own[b], p = opp[b];
+    const int t = mean ? (i & 7) : oz_eval_symmetry(seed, o, p);
+    const int r = lane >> 3, c = lane & 7;
+    int sbit = 0;
+    const bool inb = r < n && c < n;
+    if (inb) { const int src = oz_sym_src(t, n, r, c); sbit = (src / n) * 8 + src % n; }
+    const uint64_t to = __ballot(inb && ((o >> sbit) & 1ULL)), tp = __ballot(inb && ((p >> sbit) & 1ULL));
+    if (lane == 0) { out_own[i] = to; out_opp[i] = tp; }
+}
+// (pi, v) of the evaluated orientations back onto the caller's boards, one wavefront per input row, lane = cell of the evaluated board: cell
+// (r, c) of orientation t is cell oz_sym_src(t, n, r, c) of the original.  RANDOM: pi of row b un-permuted (src_pi may be pi itself: every lane
+// loads before the barrier, every store comes after it), v copied.  MEAN: src rows 8 b + t; pi[b][a] = 0.125f * (((p_0 + p_1) + p_2) + ... + p_7)
+// with p_t = orientation t's value mapped back to cell a, v[b] alike -- float32, that order, no contraction.  Rows from *d_count on are not touched.
+__global__ __launch_bounds__(64) void k_sym_policy(const uint64_t* own, const uint64_t* opp, const int* __restrict__ d_count, int n, int mode, uint64_t seed,
+                                                   const float* src_pi, const float* src_v, float* pi, float* v) {
+#pragma clang fp contract(off)
+    __shared__ float sh[8][64];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (b >= *d_count) return;
+    const int n2 = n * n, r = lane / n, c = lane % n;
+    if (mode == OZ_EVAL_SYM_MEAN) {
+        if (lane < n2)
+            for (int t = 0; t < 8; ++t) sh[t][oz_sym_src(t, n, r, c)] = src_pi[((size_t)b * 8 + t) * n2 + lane];
+        __syncthreads();
+        if (lane < n2) pi[(size_t)b * n2 + lane] = 0.125f * (((((((sh[0][lane] + sh[1][lane]) + sh[2][lane]) + sh[3][lane]) + sh[4][lane]) + sh[5][lane]) + sh[6][lane]) + sh[7][lane]);
+        if (lane == 0) {
+            const float* q = src_v + (size_t)b * 8;
+            v[b] = 0.125f * (((((((q[0] + q[1]) + q[2]) + q[3]) + q[4]) + q[5]) + q[6]) + q[7]);
+        }
+    } else {
+        const int t = oz_eval_symmetry(seed, own[b], opp[b]);
+        if (lane < n2) sh[0][oz_sym_src(t, n, r, c)] = src_pi[(size_t)b * n2 + lane];
+        const float val = lane == 0 ? src_v[b] : 0.f;
+        __syncthreads();
+        if (lane < n2) pi[(size_t)b * n2 + lane] = sh[0][lane];
+        if (lane == 0) v[b] = val;
+    }
+}
+
 // ================================================================ host objects
 struct StubNet : oz_net {
     uint64_t salt = 0, keep = 0;
-    int forward_device(const uint64_t* d_own, const uint64_t* d_opp, const int* d_count, int max_count, float* d_pi,
-                       float* d_v, hipStream_t s) override {
+    int forward_raw(const uint64_t* d_own, const uint64_t* d_opp, const int* d_count, int max_count, float* d_pi,
+                    float* d_v, hipStream_t s) override {
         hipLaunchKernelGGL(k_stub, dim3(max_count), dim3(64), 0, s, d_own, d_opp, d_count, n, salt, keep, d_pi, d_v);
         OZ_HIP(hipGetLastError());
         return OZ_OK;
@@ -930,7 +984,7 @@ struct OnnNet : oz_net {
     struct ActView { const void* p = nullptr; int fmt = -1; const int* aexp = nullptr; };
     ActView view[6];
     OzDeferredReduce last_defer;     // the fc2_defer the last launch_heads consumed
-    int last_count = 0;              // boards (capacity) of the last forward_device; 0 = none since the last commit
+    int last_count = 0;              // boards (capacity) of the last forward_raw; 0 = none since the last commit
     void set_views(const void* a1, int fmt1, const void* a2, const void* a3, const void* a4, const void* a5, int fmt) {
         const void* const p[5] = {a1, a2, a3, a4, a5};
         for (int t = 0; t < 5; ++t) view[t] = ActView{p[t], t == 0 ? fmt1 : fmt, (t == 0 ? fmt1 : fmt) == 1 ? d_aexp[t] : nullptr};
@@ -1647,8 +1701,8 @@ struct OnnNet : oz_net {
         return OZ_OK;
     }
 
-    int forward_device(const uint64_t* d_own, const uint64_t* d_opp, const int* d_count, int max_count, float* d_pi,
-                       float* d_v, hipStream_t s) override {
+    int forward_raw(const uint64_t* d_own, const uint64_t* d_opp, const int* d_count, int max_count, float* d_pi,
+                    float* d_v, hipStream_t s) override {
         if (!committed) { oz_set_error("network weights not committed (call oz_net_commit)"); return OZ_ERR_STATE; }
         if (max_count > max_batch) { oz_set_error("batch %d exceeds max_batch %d", max_count, max_batch); return OZ_ERR_ARG; }
         last_count = max_count;
@@ -1705,6 +1759,38 @@ struct OnnNet : oz_net {
         return OZ_OK;
     }
 };
+
+// The evaluator under the evaluation symmetry.  OFF: forward_raw on the caller's pointers, nothing else.  RANDOM: k_sym_boards, forward_raw on the
+// scratch boards into the caller's (pi, v), k_sym_policy in place.  MEAN: k_sym_boards (8 rows per position and their count), forward_raw into the
+// scratch outputs, k_sym_policy into the caller's (pi, v).
+int oz_net::forward_device(const uint64_t* d_own, const uint64_t* d_opp, const int* d_count, int max_count, float* d_pi, float* d_v, hipStream_t s) {
+    if (es_mode == OZ_EVAL_SYM_OFF) return forward_raw(d_own, d_opp, d_count, max_count, d_pi, d_v, s);
+    const bool mean = es_mode == OZ_EVAL_SYM_MEAN;
+    if (max_count <= 0) { oz_set_error("evaluation symmetry: batch %d", max_count); return OZ_ERR_ARG; }
+    if (mean && 8ll * max_count > max_batch) {
+        oz_set_error("evaluation symmetry \"mean\" evaluates 8 boards per position: 8 x batch %d exceeds max_batch %d", max_count, max_batch);
+        return OZ_ERR_ARG;
+    }
+    if (max_count > max_batch) { oz_set_error("batch %d exceeds max_batch %d", max_count, max_batch); return OZ_ERR_ARG; }
+    if (!es_boards || (mean && (!es_out || !es_count))) { oz_set_error("evaluation symmetry: scratch not allocated"); return OZ_ERR_STATE; }
+    if (es_profile && es_timer.backlog() > 4096) es_timer.drain();
+    const int cap = mean ? 8 * max_count : max_count, n2 = n * n;
+    uint64_t *t_own = es_boards, *t_opp = es_boards + max_batch;
+    {
+        const long long h = es_profile ? es_timer.begin(0, s) : -1;
+        hipLaunchKernelGGL(k_sym_boards, dim3((unsigned)((cap + 3) / 4)), dim3(256), 0, s, d_own, d_opp, d_count, cap, n, es_mode, es_seed, t_own, t_opp, es_count);
+        if (h >= 0) es_timer.end(h, s);
+    }
+    float *r_pi = mean ? es_out : d_pi, *r_v = mean ? es_out + (size_t)max_batch * n2 : d_v;
+    if (int rc = forward_raw(t_own, t_opp, mean ? es_count : d_count, cap, r_pi, r_v, s)) return rc;
+    {
+        const long long h = es_profile ? es_timer.begin(1, s) : -1;
+        hipLaunchKernelGGL(k_sym_policy, dim3((unsigned)max_count), dim3(64), 0, s, d_own, d_opp, d_count, n, es_mode, es_seed, r_pi, r_v, d_pi, d_v);
+        if (h >= 0) es_timer.end(h, s);
+    }
+    OZ_HIP(hipGetLastError());
+    return OZ_OK;
+}
 
 int oz_net_forward_device(oz_net* net, const uint64_t* d_own, const uint64_t* d_opp, const int* d_count, int max_count,
                           float* d_pi, float* d_v, hipStream_t s) {
@@ -1795,6 +1881,59 @@ OZ_API int oz_net_eval_cache_stats(oz_net* net, int64_t* entries, int64_t* looku
     if (lookups) *lookups = (int64_t)c[0];
     if (hits) *hits = (int64_t)c[1];
     if (inserts) *inserts = (int64_t)c[2];
+    return OZ_OK;
+}
+
+// ---------------------------------------------------------------- evaluation symmetry (oz_net::es_*, oz_internal.h)
+OZ_API int oz_net_set_eval_symmetry(oz_net* net, int mode, uint64_t seed) {
+    OZ_REQUIRE(net, "null net");
+    OZ_REQUIRE(mode == OZ_EVAL_SYM_OFF || mode == OZ_EVAL_SYM_RANDOM || mode == OZ_EVAL_SYM_MEAN,
+               "oz_net_set_eval_symmetry: mode %d is none of OZ_EVAL_SYM_OFF (0), _RANDOM (1), _MEAN (2)", mode);
+    std::lock_guard<std::mutex> lk(net->mu);
+    hipSetDevice(net->device);
+    OZ_HIP(hipDeviceSynchronize());                          // no forward may be using the scratch or the old setting
+    OZ_REQUIRE(mode == OZ_EVAL_SYM_OFF || net->max_batch >= 1, "oz_net_set_eval_symmetry: network max_batch %d", net->max_batch);
+    OZ_REQUIRE(mode != OZ_EVAL_SYM_MEAN || net->max_batch >= 8,
+               "oz_net_set_eval_symmetry: \"mean\" evaluates 8 boards per position, network max_batch %d < 8", net->max_batch);
+    const size_t B = (size_t)net->max_batch, n2 = (size_t)net->n * net->n;
+    if (mode != OZ_EVAL_SYM_OFF && !net->es_boards) OZ_HIP(hipMalloc((void**)&net->es_boards, 8 * 2 * B));
+    if (mode == OZ_EVAL_SYM_MEAN && !net->es_out) OZ_HIP(hipMalloc((void**)&net->es_out, 4 * B * (n2 + 1)));
+    if (mode == OZ_EVAL_SYM_MEAN && !net->es_count) OZ_HIP(hipMalloc((void**)&net->es_count, sizeof(int)));
+    net->es_mode = mode;
+    net->es_seed = seed;
+    return eval_cache_clear(net);                            // another function of the board: every cached (pi, v) is stale
+}
+OZ_API int oz_net_get_eval_symmetry(oz_net* net, int* mode, uint64_t* seed) {
+    OZ_REQUIRE(net, "null net");
+    std::lock_guard<std::mutex> lk(net->mu);
+    if (mode) *mode = net->es_mode;
+    if (seed) *seed = net->es_seed;
+    return OZ_OK;
+}
+OZ_API int oz_net_eval_symmetry_profile(oz_net* net, int enable, double* ms_total, int64_t* launches, int reset) {
+    OZ_REQUIRE(net, "null net");
+    std::lock_guard<std::mutex> lk(net->mu);
+    hipSetDevice(net->device);
+    if (net->es_timer.collect() != OZ_OK) { oz_set_error("HIP event timing failed"); return OZ_ERR_HIP; }
+    for (int i = 0; i < 2; ++i) {
+        if (ms_total) ms_total[i] = net->es_timer.ms[i];
+        if (launches) launches[i] = net->es_timer.count[i];
+    }
+    if (reset) net->es_timer.reset();
+    net->es_profile = enable ? 1 : 0;
+    return OZ_OK;
+}
+// host-only: the OZ_HD functions of oz_common.h as the kernels evaluate them
+OZ_API int oz_eval_symmetries(uint64_t seed, const uint64_t* own, const uint64_t* opp, int64_t count, int32_t* t_out) {
+    OZ_REQUIRE(count >= 0 && (count == 0 || (own && opp && t_out)), "oz_eval_symmetries: null argument or negative count");
+    for (int64_t i = 0; i < count; ++i) t_out[i] = oz_eval_symmetry(seed, own[i], opp[i]);
+    return OZ_OK;
+}
+OZ_API int oz_sym_boards(const int32_t* t, int n, const uint64_t* boards, int64_t count, uint64_t* out) {
+    OZ_REQUIRE(n == 4 || n == 6 || n == 8, "oz_sym_boards: board size must be 4, 6 or 8 (got %d)", n);
+    OZ_REQUIRE(count >= 0 && (count == 0 || (t && boards && out)), "oz_sym_boards: null argument or negative count");
+    for (int64_t i = 0; i < count; ++i) OZ_REQUIRE(t[i] >= 0 && t[i] < 8, "oz_sym_boards: t[%lld] = %d outside 0 .. 7", (long long)i, t[i]);
+    for (int64_t i = 0; i < count; ++i) out[i] = oz_sym_board(t[i], n, boards[i]);
     return OZ_OK;
 }
 

@@ -295,7 +295,7 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
              seed=1234, reference_aliasing=True, alias_final_boards=True, dump_examples=False, q_mode=_lib.QMODE_F64,
              distributed=False, batched_evaluation=False, policy_target="onehot", target_temperature=1.0, leaves_per_step=1,
              root_noise=None, sample_moves=None, replay="host", evaluation_opponent="random", endgame_targets=0,
-             solve_leaves=0, match_openings=None, evaluation_openings=None, playout_cap=None, forced_playouts=None):
+             solve_leaves=0, match_openings=None, evaluation_openings=None, playout_cap=None, forced_playouts=None, eval_symmetry=None):
     """main.py:56-259 on the GPU engines; returns `historic` = [(episodes done, win rate vs random), ...]
 
     batched_evaluation=True plays the evaluation games against RandomOthelloAgent in lock step on the GPU
@@ -379,7 +379,28 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
     on what the search concluded, not on how it explored.  The visit rows ARE the pruned counts then: examples_from_records, expand_examples
     and the device replay buffer read them unchanged.  The moves are still chosen from the raw counts; the fast moves of a playout cap,
     matches and evaluations are neither forced nor pruned.  The reference has nothing like it (DESIGN.md, "Forced playouts";
-    tools/forced_playouts_bench.py, profiles/forced_playouts_bench.json)."""
+    tools/forced_playouts_bench.py, profiles/forced_playouts_bench.json).
+
+    eval_symmetry=("random", s) (None = off, the default): the SELF-PLAY network of iteration i (1, 2, ...) evaluates every position in the
+    dihedral symmetry oz_eval_symmetry(s + i, own, opp) of the board (NNetWrapper.set_eval_symmetry("random", s + i)), in the host path, the
+    distributed path and with replay="device" alike: AlphaZero's and KataGo's random leaf symmetry as a pure function of the position, with a
+    new seed per iteration, so that the orientation bias of a network that is only approximately equivariant does not repeat in every game
+    and in the visit rows policy_target="visits" trains on.  The network's previous setting is back before the fit, matches and evaluation,
+    which stay untouched like under every other self-play option.  "mean" (all eight orientations, 8x the network work) is for matches and
+    measurements and is refused here: set it on the networks themselves with set_eval_symmetry("mean") ("Evaluation symmetry")."""
+    if eval_symmetry is not None:
+        try:
+            es_mode, es_seed = (eval_symmetry, 0) if isinstance(eval_symmetry, str) and eval_symmetry == "mean" else eval_symmetry
+        except (TypeError, ValueError):
+            raise ValueError(f'eval_symmetry must be None or ("random", seed), got {eval_symmetry!r}') from None
+        if isinstance(es_mode, str) and es_mode == "mean":
+            raise ValueError('eval_symmetry="mean" is not a self-play option (8x the network work per leaf): for matches and measurements set it on '
+                             'the networks with NNetWrapper.set_eval_symmetry("mean")')
+        if not isinstance(es_mode, str) or es_mode != "random":
+            raise ValueError(f'eval_symmetry must be None or ("random", seed), got {eval_symmetry!r}')
+        _lib.check_eval_symmetry(es_mode, es_seed)
+        _lib.check_eval_symmetry(es_mode, es_seed + num_iterations)
+        eval_symmetry = (es_mode, int(es_seed))
     playout_cap = _lib.check_playout_cap(playout_cap, num_simulations)
     cap_kw = {"playout_cap": playout_cap} if playout_cap is not None else {}
     forced_playouts = _lib.check_forced_playouts(forced_playouts, _lib.check_root_noise(root_noise))
@@ -453,6 +474,14 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
             temperature = 0
 
         logging.info('[%d/%d] self-play: %d games x %d simulations on the GPU', i, num_iterations, num_episodes, num_simulations)
+        es_previous = None
+        if eval_symmetry is not None:                      # this iteration's self-play only: restore_eval_symmetry() precedes every fit
+            es_previous = neural_network.eval_symmetry()
+            neural_network.set_eval_symmetry(eval_symmetry[0], eval_symmetry[1] + i)
+
+        def restore_eval_symmetry(net=neural_network, previous=es_previous):
+            if previous is not None:
+                net.set_eval_symmetry(*previous)
         if device_replay is not None:
             appended, endgame = _selfplay_into_replay(device_replay, neural_network, board_size, num_episodes, num_simulations,
                                                       degree_exploration, temperature, e_greedy, seed, total_episodes_done, q_mode, visits,
@@ -463,6 +492,7 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
                 _log_endgame(i, num_iterations, endgame)
             total_episodes_done += num_episodes
             logging.info('[%d/%d] self-play done: %d records, device buffer holds %d examples', i, num_iterations, appended, len(device_replay))
+            restore_eval_symmetry()
             logging.info('[%d/%d] fit on the device buffer', i, num_iterations)
             neural_network.train(device_replay, verbose=2 if logging.root.level <= logging.DEBUG else None)
         else:
@@ -486,6 +516,7 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
                                          **cap_kw)
                 training.rows_solved += selfplay_batch.rows_solved if solve_leaves else 0
                 endgame = getattr(selfplay_batch, "endgame_stats", None) if endgame_targets else None
+            restore_eval_symmetry()
             if endgame is not None:
                 training.endgame_history.append(endgame)
                 _log_endgame(i, num_iterations, endgame)
