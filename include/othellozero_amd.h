@@ -649,6 +649,59 @@ typedef struct {
     int32_t disc_loss_max, pad;
 } oz_endgame_stats;
 int oz_selfplay_solve_records(oz_selfplay* sp, int64_t first_record, int max_empties, oz_endgame_stats* stats /* optional */);
+/* ------------------------------------------------------------------ value targets (opt-in; with nothing of it called every record, launch and
+ * result is bit for bit what it was).  A record's z is the outcome of one noisy game.  The search knows more about the position it moved from:
+ * its ROOT VALUE, the visit-weighted mean of the root's Q,
+ *     a[sq]  = N[sq] > 0 ? (double)N[sq] * Q[sq] : 0.0          sq = 0 .. 63; N is 0 off the legal set
+ *     value  = pairwise_sum(a, 64) / (double)sum(N)              NumPy's pairwise sum (np.sum of 64 float64); sum(N) == 0: value 0, rc 2
+ * in float64 without contraction, N the RAW root counts (never the pruned row of forced playouts) and Q the stored edge value read as a
+ * double whatever its q_mode tag: the root's value for the player to move (MCTS/__init__.py:68 keeps Q(s, a) for the mover at s).  ONE
+ * definition, oz_root_term / oz_root_mean (csrc/oz_common.h), is what the kernels and oz_root_values evaluate.
+ * A VALUE TARGET combines z with the root values.  Take one game's records i = 0 .. T-1 in ply order, mover p_i = +-1, z_i as stored at the
+ * time of the call (after oz_selfplay_solve_records if that ran), root value q_i, exact_i = (E > 0 and empties_i <= E), E = exact_empties:
+ *     OZ_VALUE_TARGET_OUTCOME   t_i = z_i
+ *     OZ_VALUE_TARGET_BLEND     t_i = exact_i ? z_i : (1 - w) * z_i + w * q_i                                   param = w in [0, 1]
+ *     OZ_VALUE_TARGET_TD        from BLACK's side: B_T = p_{T-1} * z_{T-1};  for i = T-1 .. 0:                   param = lam in [0, 1]
+ *                               B_i = exact_i ? p_i * z_i : (1 - lam) * (p_i * q_i) + lam * B_{i+1};  t_i = p_i * B_i
+ * float64, every product and every sum rounded on its own, 1 - w / 1 - lam computed once, the result rounded once to float32.  A solved
+ * record restarts the chain: earlier plies bootstrap from the exact value.  After a pass the movers do not alternate: the sign always comes
+ * from `player`.  The fast records of a playout cap take part in the chain (they are dropped as examples, as ever).  ONE definition,
+ * oz_value_target_* (csrc/oz_common.h), is what k_value_targets and oz_value_targets evaluate.  lam = 1 and w = 0 are the outcome,
+ * lam = 0 and (off the exact records) w = 1 the root value itself. */
+#define OZ_VALUE_TARGET_OUTCOME 0
+#define OZ_VALUE_TARGET_BLEND 1
+#define OZ_VALUE_TARGET_TD 2
+typedef struct {
+    int64_t records;        /* records given a target */
+    int64_t exact;          /* of them, exact_i */
+    int64_t sign_changed;   /* of them, sign(t_i) != z_i (t_i == 0 counts) */
+} oz_value_target_stats;
+/* the root value of `count` rows N[count][64], Q[count][64] by square, on the host (no device needed).  OZ_ERR_ARG: a negative N. */
+int oz_root_values(const int32_t* N, const double* Q, int64_t count, double* out /* [count] */);
+/* the root value of every slot's current root: value[num_games], rc[num_games] as oz_mcts_root_counts (0 ok, 1 unknown state, 2 never
+ * selected from; value 0 where rc != 0) */
+int oz_mcts_root_values(oz_mcts* m, double* value, int32_t* rc);
+/* the engine keeps the root value of every searched move next to its record: lock-step rounds at any leaves_per_step, oz_selfplay_stagger
+ * and the free-running driver alike, whose values stay exactly those of oz_selfplay_run; no record and no statistic changes.  Before the
+ * first driver call (OZ_ERR_STATE afterwards).  512 B per slot + 8 B per record of device memory at the first enabling. */
+int oz_selfplay_set_record_values(oz_selfplay* sp, int enable);
+/* value i belongs to record i of oz_selfplay_records, the same ring order (OZ_ERR_ARG on an engine that does not record values) */
+int oz_selfplay_values(oz_selfplay* sp, double* out /* [max_records] */, int64_t max_records, int64_t* written);
+int oz_selfplay_values_device(oz_selfplay* sp, void* dst_device, int64_t max_records, int64_t* written);
+/* the value targets of the completed records [first_record, completed so far) into the engine's float32 targets[record_cap] on the device,
+ * one wavefront per record; a first_record inside a game still reads that game to its end.  Needs oz_selfplay_set_record_values.  Records
+ * are not touched.  OZ_ERR_ARG: an unknown mode, param outside [0, 1] (NaN included; not looked at for OUTCOME), exact_empties outside
+ * 0..OZ_SOLVE_MAX_EMPTIES, first_record < 0; OZ_ERR_STATE: a step is pending. */
+int oz_selfplay_value_targets(oz_selfplay* sp, int64_t first_record, int mode, double param, int exact_empties,
+                              oz_value_target_stats* stats /* optional */);
+/* target i belongs to record i (OZ_ERR_ARG before the first oz_selfplay_value_targets; targets below its first_record are 0 or stale) */
+int oz_selfplay_targets(oz_selfplay* sp, float* out /* [max_records] */, int64_t max_records, int64_t* written);
+int oz_selfplay_targets_device(oz_selfplay* sp, void* dst_device, int64_t max_records, int64_t* written);
+/* the same targets on the host (no device needed): R records in any order with their root values; records of one game_id are one game,
+ * taken in ply order.  out[i] belongs to records[i]. */
+int oz_value_targets(const oz_record* records, const double* values, int64_t R, int n, int mode, double param, int exact_empties,
+                     float* out /* [R] */);
+
 /* root visit counts of the last move round, counts[num_games][64] (parity tests) */
 int oz_selfplay_last_counts(oz_selfplay* sp, int32_t* counts);
 /* HIP-event time of the evaluator (NN) launches since creation, and their count */
@@ -887,6 +940,13 @@ int oz_replay_append_selfplay(oz_replay* r, oz_selfplay* sp, int64_t first_recor
  * of a multi-GPU run, saved games.  count < 2^28. */
 int oz_replay_append_records(oz_replay* r, const oz_record* records, const int32_t* counts, int64_t count, int alias_final,
                              int target, double temperature);
+/* the two appends with VALUE TARGETS ("value targets" above) in place of the records' z: example z = the float32 target of its record, 8 per
+ * record.  _targets: the engine's targets as the last oz_selfplay_value_targets left them (OZ_ERR_ARG before the first; the caller computes them
+ * for first_record or earlier), staged device to device beside the records and the counts.  _values: values[count] float32, one per record. */
+int oz_replay_append_selfplay_targets(oz_replay* r, oz_selfplay* sp, int64_t first_record, int alias_final, int target, double temperature,
+                                      int64_t* appended_records);
+int oz_replay_append_records_values(oz_replay* r, const oz_record* records, const int32_t* counts, const float* values, int64_t count,
+                                    int alias_final, int target, double temperature);
 /* finished examples from the host, in the given order (restoring a saved buffer, hand-made data) */
 int oz_replay_append_examples(oz_replay* r, const uint64_t* own, const uint64_t* opp, const float* pi /* [count][n*n] */,
                               const float* z, int64_t count);

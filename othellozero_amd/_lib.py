@@ -37,6 +37,8 @@ SOLVE_LEAVES_MAX_EMPTIES = 10                                                   
 AGENT_RANDOM, AGENT_MINIMAX = 0, 1                                                   # oz_arena_set_opponent
 OPENING_MAX_PLIES = 16                                                               # OZ_OPENING_MAX_PLIES
 REPLAY_TARGET_ONEHOT, REPLAY_TARGET_VISITS = 0, 1                                    # oz_replay_append_*
+VALUE_TARGET_OUTCOME, VALUE_TARGET_BLEND, VALUE_TARGET_TD = 0, 1, 2                  # OZ_VALUE_TARGET_*
+VALUE_TARGET_MODES = {"outcome": VALUE_TARGET_OUTCOME, "blend": VALUE_TARGET_BLEND, "td": VALUE_TARGET_TD}
 NET_KERNELS = ("input", "conv2", "conv3", "conv4", "fc1", "fc2", "heads")           # OZ_NET_KERNELS slots
 TREE_KERNELS = ("select", "compact", "network", "expand_backup", "roots_move")       # OZ_TREE_KERNELS slots
 
@@ -76,6 +78,10 @@ class EndgameStats(C.Structure):                                                
         ("records", C.c_int64), ("solved", C.c_int64), ("z_changed", C.c_int64), ("optimal_moves", C.c_int64), ("disc_loss_sum", C.c_int64),
         ("disc_loss_max", C.c_int32), ("pad", C.c_int32),
     ]
+
+
+class ValueTargetStats(C.Structure):                                                 # oz_value_target_stats
+    _fields_ = [("records", C.c_int64), ("exact", C.c_int64), ("sign_changed", C.c_int64)]
 
 
 # numpy view of oz_record (48 bytes)
@@ -191,6 +197,12 @@ SIGNATURES = {
     "oz_selfplay_visits": [_vp, _i32p, C.c_int64, _i64p],
     "oz_selfplay_visits_device": [_vp, _vp, C.c_int64, _i64p],
     "oz_selfplay_last_counts": [_vp, _i32p],
+    "oz_root_values": [_i32p, _f64p, C.c_int64, _f64p], "oz_mcts_root_values": [_vp, _f64p, _i32p],
+    "oz_selfplay_set_record_values": [_vp, C.c_int],
+    "oz_selfplay_values": [_vp, _f64p, C.c_int64, _i64p], "oz_selfplay_values_device": [_vp, _vp, C.c_int64, _i64p],
+    "oz_selfplay_value_targets": [_vp, C.c_int64, C.c_int, C.c_double, C.c_int, C.POINTER(ValueTargetStats)],
+    "oz_selfplay_targets": [_vp, _f32p, C.c_int64, _i64p], "oz_selfplay_targets_device": [_vp, _vp, C.c_int64, _i64p],
+    "oz_value_targets": [_vp, _f64p, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int, _f32p],
     "oz_selfplay_eval_time": [_vp, _f64p, _i64p, _i64p],
     "oz_comm_unique_id": [_u8p], "oz_comm_create": [C.POINTER(_vp), _u8p, C.c_int, C.c_int], "oz_comm_destroy": [_vp],
     "oz_selfplay_gather_records": [_vp, _vp, C.c_int64, _vp, C.c_int64, _i64p, _i64p],
@@ -234,6 +246,8 @@ SIGNATURES = {
     "oz_replay_info": [_vp, _i64p, _i64p, _i64p],
     "oz_replay_append_selfplay": [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_double, _i64p],
     "oz_replay_append_records": [_vp, _vp, _i32p, C.c_int64, C.c_int, C.c_int, C.c_double],
+    "oz_replay_append_selfplay_targets": [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_double, _i64p],
+    "oz_replay_append_records_values": [_vp, _vp, _i32p, _f32p, C.c_int64, C.c_int, C.c_int, C.c_double],
     "oz_replay_append_examples": [_vp, _u64p, _u64p, _f32p, _f32p, C.c_int64],
     "oz_replay_restore": [_vp, _u64p, _u64p, _f32p, _f32p, C.c_int64, C.c_int64],
     "oz_replay_read": [_vp, C.c_int64, C.c_int64, _u64p, _u64p, _f32p, _f32p],
@@ -505,6 +519,31 @@ def check_endgame_targets(endgame_targets, alias_final_boards):
         raise ValueError("endgame_targets needs alias_final_boards=False: an exact value belongs to the position of its move, not to the "
                          "game's final position")
     return e
+
+
+def check_value_target(value_target, alias_final_boards=False):
+    """value_target = None / "outcome" (the records' z), ("blend", w) or ("td", lam), both parameters in [0, 1]: the value target of the
+    training examples (include/othellozero_amd.h, "value targets").  Returns (OZ_VALUE_TARGET_* code, parameter) -- (VALUE_TARGET_OUTCOME,
+    0.0) is the option off; ValueError for anything else, and for a search-value target with alias_final_boards: a search value belongs to
+    the position of its move, not to the game's final position."""
+    if value_target is None or (isinstance(value_target, str) and value_target == "outcome"):
+        return VALUE_TARGET_OUTCOME, 0.0
+    bad = f'value_target must be None, "outcome", ("blend", w) or ("td", lam), got {value_target!r}'
+    if not isinstance(value_target, (tuple, list)) or len(value_target) != 2 or not isinstance(value_target[0], str) \
+            or value_target[0] not in ("blend", "td"):
+        raise ValueError(bad)
+    if isinstance(value_target[1], (bool, str, bytes)):
+        raise ValueError(bad)
+    try:
+        param = float(value_target[1])
+    except (TypeError, ValueError):
+        raise ValueError(bad) from None
+    if not 0.0 <= param <= 1.0:
+        raise ValueError(f"value_target: the parameter of {value_target[0]!r} must be in [0, 1] (got {param})")
+    if alias_final_boards:
+        raise ValueError("value_target needs alias_final_boards=False: a search value belongs to the position of its move, not to the game's "
+                         "final position")
+    return VALUE_TARGET_MODES[value_target[0]], param
 
 
 def check_opponent(opponent):

@@ -99,6 +99,36 @@ def rules_prune_counts(N, Q, P, eta, legal, Ns, c, epsilon, k):
     return pruned
 
 
+def rules_root_values(N, Q):
+    """oz_root_values: the root value of searches from their root rows, on the host (no GPU needed).  N int32 (..., 64) raw visit counts by
+    square, Q float64 (..., 64) the stored edge values -> float64 (...): pairwise_sum(N * Q) / sum(N), the visit-weighted mean of Q for the
+    player to move; 0.0 where nothing was visited.  The function the kernels evaluate (include/othellozero_amd.h, "value targets")."""
+    n_ = np.ascontiguousarray(N, dtype=np.int32)
+    q_ = np.ascontiguousarray(Q, dtype=np.float64)
+    if n_.shape != q_.shape or n_.ndim < 1 or n_.shape[-1] != 64:
+        raise ValueError(f"N and Q must both have shape (..., 64) (got {n_.shape} and {q_.shape})")
+    out = np.zeros(n_.shape[:-1], np.float64)
+    _lib.check(_lib.load().oz_root_values(_lib.p_i32(n_), _lib.p_f64(q_), out.size, _lib.p_f64(out)))
+    return out
+
+
+def rules_value_targets(records, values, n, value_target, exact_empties=0):
+    """oz_value_targets: the value targets of move records (_lib.RECORD_DTYPE, any order; records of one game_id are one game) with their
+    root values (float64 (R,)), on the host (no GPU needed) -> float32 (R,), target i for record i.  value_target = "outcome", ("blend", w)
+    or ("td", lam); exact_empties=E > 0: a record with at most E empties keeps its z (an exact value of SelfPlayEngine.solve_records(E)) and
+    restarts the TD chain.  The function k_value_targets evaluates (include/othellozero_amd.h, "value targets")."""
+    mode, param = _lib.check_value_target(value_target)
+    exact_empties = _lib.check_solve_empties(exact_empties, 0, "exact_empties")
+    rec = np.ascontiguousarray(records, dtype=_lib.RECORD_DTYPE).ravel()
+    val = np.ascontiguousarray(values, dtype=np.float64).ravel()
+    if val.size != rec.size:
+        raise ValueError(f"{val.size} root values for {rec.size} records")
+    out = np.zeros(rec.size, np.float32)
+    _lib.check(_lib.load().oz_value_targets(rec.ctypes.data_as(C.c_void_p), _lib.p_f64(val), rec.size, int(n), mode, param, exact_empties,
+                                            _lib.p_f32(out)))
+    return out
+
+
 def rules_eval_symmetries(own, opp, seed):
     """oz_eval_symmetries on the host (no GPU needed): the orientation t in 0..7 (int32) a network set to ("random", seed) evaluates each
     mover-canonical position (own[i], opp[i]) in -- the function the kernels evaluate"""

@@ -192,6 +192,47 @@ __host__ __device__ inline double pairwise_sum(const double* a, int len) {
     return res;
 }
 
+// ---------------------------------------------------------------- root value and value targets
+// (include/othellozero_amd.h, "value targets").  The root value of a search: the visit-weighted mean of the root's Q, for the player to
+// move.  a[sq] = oz_root_term: (double)N * Q where N > 0, else 0 (counts are 0 off the legal set); oz_root_mean = pairwise_sum(a, 64) /
+// (double)sum N, or 0 with *rc = 2 where nothing was visited.  float64, no contraction.  The kernels (oz_search.hip: one lane per square
+// computes its term into a[], the wave sums N) and the host's oz_root_values (oz_root_value below) evaluate these two functions.
+OZ_HD double oz_root_term(int32_t N, double Q) {
+#pragma clang fp contract(off)
+    return N > 0 ? (double)N * Q : 0.0;
+}
+__host__ __device__ inline double oz_root_mean(const double* a /* [64] */, long long total, int* rc) {
+    if (total <= 0) { *rc = 2; return 0.0; }
+    *rc = 0;
+    return pairwise_sum(a, 64) / (double)total;
+}
+__host__ __device__ inline double oz_root_value(const int32_t* N /* [64] */, const double* Q /* [64] */, int* rc) {
+    double a[64];
+    long long total = 0;
+    for (int sq = 0; sq < 64; ++sq) {
+        a[sq] = oz_root_term(N[sq], Q[sq]);
+        if (N[sq] > 0) total += N[sq];
+    }
+    return oz_root_mean(a, total, rc);
+}
+// The value target of a record from the game outcome z, the root value q and the targets of the plies after it.  exact: the record's z
+// is an exact endgame value (oz_selfplay_solve_records with max_empties = E) and stays; blend: (1 - w) z + w q; td_step: one step of
+// the TD(lambda) recurrence from BLACK's side, B_i = (1 - lam) (p_i q_i) + lam B_{i+1}.  om = 1 - w / 1 - lam, computed once by the
+// caller.  float64, every product and the sum rounded on their own.  The one definition k_value_targets and the host's oz_value_targets share.
+OZ_HD bool oz_value_target_exact(uint64_t black, uint64_t white, int n2, int exact_empties) {
+    return exact_empties > 0 && n2 - oz_popc(black | white) <= exact_empties;
+}
+OZ_HD double oz_value_target_blend(double z, double q, double om, double w) {
+#pragma clang fp contract(off)
+    const double a = om * z, b = w * q;
+    return a + b;
+}
+OZ_HD double oz_value_target_td_step(double pq, double b_next, double om, double lam) {
+#pragma clang fp contract(off)
+    const double a = om * pq, b = lam * b_next;
+    return a + b;
+}
+
 // ---------------------------------------------------------------- training examples
 // training_example_symmetries, training.py:13-23: outputs in the order rot90 k=1..4 (CCW), each
 // first with fliplr then without.  src(t, r, c) = source cell of output cell (r, c).

@@ -235,7 +235,8 @@ struct oz_replay {
     // permutation that puts them in (game_id, ply) order
     oz_record* st_rec = nullptr;
     int32_t *st_cnt = nullptr, *st_perm = nullptr;
-    int64_t st_rec_cap = 0, st_cnt_cap = 0;
+    float* st_tgt = nullptr;               // the records' value targets (the *_targets / *_values appends), beside st_rec
+    int64_t st_rec_cap = 0, st_cnt_cap = 0, st_tgt_cap = 0;
     std::mutex mu;
     int64_t held() const { return total < capacity ? total : capacity; }
 };

@@ -16,13 +16,15 @@
 // pi:     lane = cell row*n+col.  VISITS: the float64 row of k_expand_visits (oz_count_pow, lane 0's pairwise_sum, one division), rounded
 //         once to float32, then every symmetry's output cell takes its source cell's value by a cross-lane read; ONEHOT: 1.0f where the
 //         source cell is the action.  Stores of a row are contiguous over the lanes.
-// own / opp / z of example t are written by lane t: one 8-lane store each per record.
+// own / opp / z of example t are written by lane t: one 8-lane store each per record.  z = the record's z, or with zt (the records' value
+// targets, indexed like recs) the record's float32 target.
 // No atomics, no scratch, fixed order.
 template <int N, bool VISITS>
 __global__ __launch_bounds__(64) void k_replay_append(const oz_record* __restrict__ recs, const int32_t* __restrict__ counts,
                                                       const int32_t* __restrict__ perm, int alias_final, double inv, int k, long long base,
                                                       long long skip, long long capacity, uint64_t* __restrict__ own,
-                                                      uint64_t* __restrict__ opp, float* __restrict__ pi, float* __restrict__ z) {
+                                                      uint64_t* __restrict__ opp, float* __restrict__ pi, float* __restrict__ z,
+                                                      const float* __restrict__ zt) {
     constexpr int N2 = N * N;
     __shared__ double arr[64];
     __shared__ double divisor;
@@ -64,7 +66,7 @@ __global__ __launch_bounds__(64) void k_replay_append(const oz_record* __restric
     const long long e = i * 8 + lane;
     if (lane < 8 && e >= skip) {
         const long long slot = (base + e) % capacity;
-        own[slot] = my_own; opp[slot] = my_opp; z[slot] = (float)rec.z;
+        own[slot] = my_own; opp[slot] = my_opp; z[slot] = zt ? zt[rix] : (float)rec.z;
     }
 }
 
@@ -97,7 +99,7 @@ OZ_API int oz_replay_destroy(oz_replay* r) {
     if (!r) return OZ_OK;
     hipSetDevice(r->device);
     if (r->s) hipStreamSynchronize(r->s);
-    for (void* q : {(void*)r->own, (void*)r->opp, (void*)r->pi, (void*)r->z, (void*)r->st_rec, (void*)r->st_cnt, (void*)r->st_perm}) if (q) hipFree(q);
+    for (void* q : {(void*)r->own, (void*)r->opp, (void*)r->pi, (void*)r->z, (void*)r->st_rec, (void*)r->st_cnt, (void*)r->st_perm, (void*)r->st_tgt}) if (q) hipFree(q);
     if (r->s) hipStreamDestroy(r->s);
     delete r;
     return OZ_OK;
@@ -120,7 +122,13 @@ OZ_API int oz_replay_info(oz_replay* r, int64_t* held, int64_t* capacity, int64_
 }
 
 // room for `records` staged records (+ their permutation) and `count_rows` visit-count rows
-static int replay_reserve(oz_replay* r, int64_t records, int64_t count_rows) {
+static int replay_reserve(oz_replay* r, int64_t records, int64_t count_rows, int64_t target_rows = 0) {
+    if (target_rows > r->st_tgt_cap) {
+        if (r->st_tgt) hipFree(r->st_tgt);
+        r->st_tgt = nullptr; r->st_tgt_cap = 0;
+        OZ_HIP(hipMalloc((void**)&r->st_tgt, sizeof(float) * target_rows));
+        r->st_tgt_cap = target_rows;
+    }
     if (records > r->st_rec_cap) {
         if (r->st_rec) { hipFree(r->st_rec); hipFree(r->st_perm); }
         r->st_rec = nullptr; r->st_perm = nullptr; r->st_rec_cap = 0;
@@ -144,21 +152,21 @@ static int replay_check_target(const char* who, int alias_final, int target, dou
     return OZ_OK;
 }
 
-template <int N> static void replay_launch(oz_replay* r, int64_t count, int alias_final, int target, double inv, int k, long long skip) {
+template <int N> static void replay_launch(oz_replay* r, int64_t count, int alias_final, int target, double inv, int k, long long skip, const float* zt) {
     const dim3 grid((unsigned)count), block(64);
     if (target == OZ_REPLAY_TARGET_VISITS)
         hipLaunchKernelGGL((k_replay_append<N, true>), grid, block, 0, r->s, r->st_rec, r->st_cnt, r->st_perm, alias_final, inv, k, (long long)r->total, skip,
-                           (long long)r->capacity, r->own, r->opp, r->pi, r->z);
+                           (long long)r->capacity, r->own, r->opp, r->pi, r->z, zt);
     else
         hipLaunchKernelGGL((k_replay_append<N, false>), grid, block, 0, r->s, r->st_rec, (const int32_t*)nullptr, r->st_perm, alias_final, inv, k,
-                           (long long)r->total, skip, (long long)r->capacity, r->own, r->opp, r->pi, r->z);
+                           (long long)r->total, skip, (long long)r->capacity, r->own, r->opp, r->pi, r->z, zt);
 }
 
 // the staged records [first, first + count) of r->st_rec (host copy: h[0 .. count)) -> 8 examples each, in ascending (game_id, ply).  The fast
 // records of a playout cap (pad[0] != 0) are no training examples: they stay out of the permutation, so the kernel never sees them;
 // *kept = the records appended.
 static int replay_append_staged(oz_replay* r, const oz_record* h, int64_t first, int64_t staged, int alias_final, int target, double temperature,
-                                int64_t* kept) {
+                                int64_t* kept, const float* zt = nullptr) {
     std::vector<int32_t> perm;
     perm.reserve((size_t)staged);
     for (int64_t i = 0; i < staged; ++i)
@@ -176,9 +184,9 @@ static int replay_append_staged(oz_replay* r, const oz_record* h, int64_t first,
     hipError_t e = hipMemcpyAsync(r->st_perm, perm.data(), sizeof(int32_t) * count, hipMemcpyHostToDevice, r->s);
     if (e == hipSuccess) {
         switch (r->n) {
-        case 4: replay_launch<4>(r, count, alias_final, target, inv, k, skip); break;
-        case 6: replay_launch<6>(r, count, alias_final, target, inv, k, skip); break;
-        default: replay_launch<8>(r, count, alias_final, target, inv, k, skip);
+        case 4: replay_launch<4>(r, count, alias_final, target, inv, k, skip, zt); break;
+        case 6: replay_launch<6>(r, count, alias_final, target, inv, k, skip, zt); break;
+        default: replay_launch<8>(r, count, alias_final, target, inv, k, skip, zt);
         }
         e = hipGetLastError();
     }
@@ -189,8 +197,8 @@ static int replay_append_staged(oz_replay* r, const oz_record* h, int64_t first,
     return OZ_OK;
 }
 
-OZ_API int oz_replay_append_selfplay(oz_replay* r, oz_selfplay* sp, int64_t first_record, int alias_final, int target, double temperature,
-                                     int64_t* appended_records) {
+static int replay_append_selfplay(oz_replay* r, oz_selfplay* sp, int64_t first_record, int alias_final, int target, double temperature,
+                                  int64_t* appended_records, bool targets) {
     OZ_REQUIRE(r && sp, "oz_replay_append_selfplay: null argument");
     if (int rc = replay_check_target("oz_replay_append_selfplay", alias_final, target, temperature)) return rc;
     OZ_REQUIRE(first_record >= 0, "oz_replay_append_selfplay: first_record %lld", (long long)first_record);
@@ -205,11 +213,15 @@ OZ_API int oz_replay_append_selfplay(oz_replay* r, oz_selfplay* sp, int64_t firs
     if (appended_records) *appended_records = 0;
     if (completed <= first_record) return OZ_OK;
     OZ_HIP(hipSetDevice(r->device));
-    if (int rc = replay_reserve(r, completed, visits ? completed : 0)) return rc;
+    if (int rc = replay_reserve(r, completed, visits ? completed : 0, targets ? completed : 0)) return rc;
     int64_t got = 0, got_rows = 0;
     if (int rc = oz_selfplay_records_device(sp, r->st_rec, completed, &got)) return rc;
     if (visits) {
         if (int rc = oz_selfplay_visits_device(sp, r->st_cnt, got, &got_rows)) return rc;
+        if (got_rows < got) got = got_rows;
+    }
+    if (targets) {
+        if (int rc = oz_selfplay_targets_device(sp, r->st_tgt, got, &got_rows)) return rc;
         if (got_rows < got) got = got_rows;
     }
     OZ_HIP(hipStreamSynchronize(nullptr));       // the engine's device-to-device copies ran on the null stream
@@ -219,13 +231,21 @@ OZ_API int oz_replay_append_selfplay(oz_replay* r, oz_selfplay* sp, int64_t firs
     OZ_HIP(hipMemcpyAsync(h.data(), r->st_rec + first_record, sizeof(oz_record) * count, hipMemcpyDeviceToHost, r->s));
     OZ_HIP(hipStreamSynchronize(r->s));
     int64_t kept = 0;
-    if (int rc = replay_append_staged(r, h.data(), first_record, count, alias_final, target, temperature, &kept)) return rc;
+    if (int rc = replay_append_staged(r, h.data(), first_record, count, alias_final, target, temperature, &kept, targets ? r->st_tgt : nullptr)) return rc;
     if (appended_records) *appended_records = kept;
     return OZ_OK;
 }
+OZ_API int oz_replay_append_selfplay(oz_replay* r, oz_selfplay* sp, int64_t first_record, int alias_final, int target, double temperature,
+                                     int64_t* appended_records) {
+    return replay_append_selfplay(r, sp, first_record, alias_final, target, temperature, appended_records, false);
+}
+OZ_API int oz_replay_append_selfplay_targets(oz_replay* r, oz_selfplay* sp, int64_t first_record, int alias_final, int target, double temperature,
+                                             int64_t* appended_records) {
+    return replay_append_selfplay(r, sp, first_record, alias_final, target, temperature, appended_records, true);
+}
 
-OZ_API int oz_replay_append_records(oz_replay* r, const oz_record* records, const int32_t* counts, int64_t count, int alias_final, int target,
-                                    double temperature) {
+static int replay_append_records(oz_replay* r, const oz_record* records, const int32_t* counts, const float* values, int64_t count, int alias_final,
+                                 int target, double temperature) {
     OZ_REQUIRE(r, "oz_replay_append_records: null replay buffer");
     if (int rc = replay_check_target("oz_replay_append_records", alias_final, target, temperature)) return rc;
     const bool visits = target == OZ_REPLAY_TARGET_VISITS;
@@ -235,15 +255,25 @@ OZ_API int oz_replay_append_records(oz_replay* r, const oz_record* records, cons
     OZ_REQUIRE(records, "oz_replay_append_records: null records");
     R_LOCK(r);
     OZ_HIP(hipSetDevice(r->device));
-    if (int rc = replay_reserve(r, count, visits ? count : 0)) return rc;
+    if (int rc = replay_reserve(r, count, visits ? count : 0, values ? count : 0)) return rc;
     OZ_HIP(hipMemcpyAsync(r->st_rec, records, sizeof(oz_record) * count, hipMemcpyHostToDevice, r->s));
+    if (values) OZ_HIP(hipMemcpyAsync(r->st_tgt, values, sizeof(float) * count, hipMemcpyHostToDevice, r->s));
     if (visits) OZ_HIP(hipMemcpyAsync(r->st_cnt, counts, sizeof(int32_t) * 64 * count, hipMemcpyHostToDevice, r->s));
     int64_t kept = 0;
-    const int rc = replay_append_staged(r, records, 0, count, alias_final, target, temperature, &kept);
+    const int rc = replay_append_staged(r, records, 0, count, alias_final, target, temperature, &kept, values ? r->st_tgt : nullptr);
     const hipError_t es = hipStreamSynchronize(r->s);          // (nothing kept: no launch waited for the uploads, and the caller's arrays may go away)
     if (rc) return rc;
     OZ_HIP(es);
     return OZ_OK;
+}
+OZ_API int oz_replay_append_records(oz_replay* r, const oz_record* records, const int32_t* counts, int64_t count, int alias_final, int target,
+                                    double temperature) {
+    return replay_append_records(r, records, counts, nullptr, count, alias_final, target, temperature);
+}
+OZ_API int oz_replay_append_records_values(oz_replay* r, const oz_record* records, const int32_t* counts, const float* values, int64_t count,
+                                           int alias_final, int target, double temperature) {
+    OZ_REQUIRE(values || count == 0, "oz_replay_append_records_values: null values");
+    return replay_append_records(r, records, counts, values, count, alias_final, target, temperature);
 }
 
 // `count` rows of `width` bytes from the host into the ring at running index `k0` (count <= capacity): at most two pieces

@@ -1738,6 +1738,58 @@ OZ_API int oz_mcts_root_counts(oz_mcts* m, int32_t* counts, uint64_t* legal, int
     return OZ_OK;
 }
 
+// the root value of every slot's search ("value targets" in the header): the visit-weighted mean of the root's stored Q over the raw counts.
+// One wave per game, lane = square: a[lane] = oz_root_term of the lane's edge, the wave sums N, oz_root_mean divides.  rc as k_root_counts
+__global__ __launch_bounds__(64) void k_root_values(MctsDev t, double* value_out, int32_t* rc_out) {
+    __shared__ double terms[64];
+    const int g = blockIdx.x, lane = threadIdx.x;
+    const uint64_t own = uni64(t.root_own[g]), opp = uni64(t.root_opp[g]);
+    const uint64_t legal = oz_legal(own, opp, t.valid);
+    const int node = root_lookup(t, g, own, opp, lane);
+    int cnt = 0, rc = 0;
+    double q = 0.0;
+    if (node < 0) rc = 1;
+    else if (*rec_Ns(t, g, node) == 0) rc = 2;
+    else if ((legal >> lane) & 1) {
+        const OzEdge* e = rec_edge(t, g, node, oz_popc(legal & ((1ULL << lane) - 1ULL)));
+        cnt = (int)(e->n_tag & ~OZ_TAG_F32);
+        q = e->q;
+    }
+    rc = unii(rc);
+    terms[lane] = oz_root_term(cnt, q);
+    const int total = wave_sum_i32(cnt);
+    wave_sync();
+    int vrc = 0;
+    const double v = oz_root_mean(terms, (long long)total, &vrc);
+    if (lane == 0) { value_out[g] = rc == 0 ? v : 0.0; rc_out[g] = rc == 0 ? vrc : rc; }
+}
+OZ_API int oz_mcts_root_values(oz_mcts* m, double* value, int32_t* rc) {
+    OZ_REQUIRE(m && value && rc, "null argument");
+    std::lock_guard<std::mutex> lk(m->mu);
+    hipSetDevice(m->device);
+    const int G = m->d.G;
+    double* dv = reinterpret_cast<double*>(m->rc_legal);          // (the staging of oz_mcts_root_counts: [G] 8-byte words and [G] codes)
+    int32_t* dr = m->rc_rc;
+    hipLaunchKernelGGL(k_root_values, dim3(G), dim3(64), 0, m->stream, m->d, dv, dr);
+    OZ_HIP(hipGetLastError());
+    OZ_HIP(hipMemcpyAsync(value, dv, 8ull * G, hipMemcpyDeviceToHost, m->stream));
+    OZ_HIP(hipMemcpyAsync(rc, dr, 4ull * G, hipMemcpyDeviceToHost, m->stream));
+    OZ_HIP(hipStreamSynchronize(m->stream));
+    return OZ_OK;
+}
+// oz_root_value over `count` rows, on the host: needs no device
+OZ_API int oz_root_values(const int32_t* N, const double* Q, int64_t count, double* out) {
+    OZ_REQUIRE(count >= 0, "oz_root_values: count %lld", (long long)count);
+    if (count == 0) return OZ_OK;
+    OZ_REQUIRE(N && Q && out, "oz_root_values: null argument");
+    for (int64_t i = 0; i < count * 64; ++i) OZ_REQUIRE(N[i] >= 0, "oz_root_values: N[%lld][%d] = %d", (long long)(i / 64), (int)(i % 64), N[i]);
+    for (int64_t i = 0; i < count; ++i) {
+        int rc;
+        out[i] = oz_root_value(N + i * 64, Q + i * 64, &rc);
+    }
+    return OZ_OK;
+}
+
 // ---- forced playouts: host side
 static int forced_check(const char* fn, double k) {
     OZ_REQUIRE(k >= 0.0 && k <= 16.0, "%s: k %g outside [0, 16] (0 = off)", fn, k);          // (NaN fails both compares)
@@ -1971,6 +2023,9 @@ struct GamesDev {
     // oz_selfplay_config.record_visits: root visit counts of every move of the game in progress, and of every record (same ring index)
     int32_t* log_counts;                  // [G][64 plies][64 squares], or null
     int32_t* visits;                      // [record_cap][64], or null
+    // oz_selfplay_set_record_values: the root value of every move of the game in progress, and of every record (same ring index)
+    double* log_values;                   // [G][64 plies], or null
+    double* values;                       // [record_cap], or null
     unsigned long long* counters;         // [0] records [1] games completed [2] moves
     long long record_cap;
     int record_visits;
@@ -2024,7 +2079,11 @@ __global__ void k_sp_roots_stagger(GamesDev gm, MctsDev t, int round, int period
 // FORCE (an engine with forced playouts, oz_selfplay_set_forced_playouts; fp.k > 0 where it is on): on a root whose noise is armed -- read before
 // NOISE clears the flag -- the row that goes to log_counts / visits is the pruned one (forced_prune_lane) and three counters count it.  Everything
 // that chooses the move keeps reading the raw counts.  A fast move of a playout cap is unarmed: never pruned.  Never in the arena.
-template <bool NOISE = false, bool SAMPLE = false, bool CAP = false, bool FORCE = false>
+// VALUES (an engine that records root values, oz_selfplay_set_record_values; gm.log_values != null where it is on): the visit-weighted mean of
+// the root's Q over the raw counts goes into the move log next to the counts and from there beside the game's records.  Such an engine launches
+// instantiations of its own (k_sp_move_f in a lock-step round; the EXTRAS advance or, with no other option, k_advance_v), so the kernels of an
+// engine without it stay the code they were, register for register.  Never in the arena.
+template <bool NOISE = false, bool SAMPLE = false, bool CAP = false, bool FORCE = false, bool VALUES = false>
 __device__ __forceinline__ void sp_move_body(const GamesDev& gm, const MctsDev& t, int g, int lane, int arena, MoveSampling ms = MoveSampling{},
                                              PlayoutCap pc = PlayoutCap{}, ForcedPlayouts fp = ForcedPlayouts{}) {
     if (!t.active[g]) return;
@@ -2043,6 +2102,20 @@ __device__ __forceinline__ void sp_move_body(const GamesDev& gm, const MctsDev& 
     int cnt = 0;
     if (is_legal) cnt = (int)(rec_edge(t, g, node, oz_popc(legal & ((1ULL << lane) - 1ULL)))->n_tag & ~OZ_TAG_F32);
     gm.last_counts[(size_t)g * 64 + lane] = cnt;
+    // record_values: the root value of this search from the RAW counts and the stored Q (oz_root_term / oz_root_mean, oz_common.h)
+    double rootv = 0.0;
+    (void)rootv;
+    if constexpr (VALUES) {
+        if (gm.log_values) {
+            __shared__ double terms[64];
+            terms[lane] = oz_root_term(cnt, is_legal ? rec_edge(t, g, node, oz_popc(legal & ((1ULL << lane) - 1ULL)))->q : 0.0);
+            const int total = wave_sum_i32(cnt);
+            wave_sync();
+            int vrc;
+            rootv = oz_root_mean(terms, (long long)total, &vrc);
+            wave_sync();                                         // the next move of this wave (free-running loop) writes terms[] again
+        }
+    }
     const int ply = unii(gm.ply[g]);
     const size_t lb = (size_t)g * 64;
     const uint64_t gid = uni64(gm.game_id[g]);
@@ -2133,8 +2206,14 @@ __device__ __forceinline__ void sp_move_body(const GamesDev& gm, const MctsDev& 
             for (int i = 0; i < nply && i < room; ++i)
                 gm.visits[(size_t)(base + i) * 64 + lane] = i == ply ? row : gm.log_counts[(lb + i) * 64 + lane];
         }
-    } else if (gm.record_visits && ply < 64) {
-        gm.log_counts[(lb + ply) * 64 + lane] = row;
+        // the game's root values next to its records, lane i the value of ply i; this ply's is still in registers
+        if constexpr (VALUES) {
+            if (gm.log_values && lane < nply && (long long)(base + lane) < gm.record_cap)
+                gm.values[base + lane] = lane == ply ? rootv : gm.log_values[lb + lane];
+        }
+    } else {
+        if (gm.record_visits && ply < 64) gm.log_counts[(lb + ply) * 64 + lane] = row;
+        if constexpr (VALUES) { if (gm.log_values && lane == 0 && ply < 64) gm.log_values[lb + ply] = rootv; }
     }
     if (lane == 0) atomicAdd(&gm.counters[2], 1ULL);
     if (fin && gm.refill) {
@@ -2158,10 +2237,10 @@ __global__ __launch_bounds__(64) void k_sp_move_s(GamesDev gm, MctsDev t, MoveSa
 __global__ __launch_bounds__(64) void k_sp_move_c(GamesDev gm, MctsDev t, MoveSampling ms, PlayoutCap pc) {
     sp_move_body<false, true, true>(gm, t, blockIdx.x, threadIdx.x, 0, ms, pc);
 }
-// the self-play move of a lock-step round of an engine with forced playouts (with or without move sampling and a playout cap: ms.plies and
-// pc.fast_sims say; a staggered round passes a cap that is off)
+// the self-play move of a lock-step round of an engine with forced playouts or recorded root values (with or without move sampling and a
+// playout cap: ms.plies and pc.fast_sims say; a staggered round passes a cap that is off; fp.k == 0: no forcing)
 __global__ __launch_bounds__(64) void k_sp_move_f(GamesDev gm, MctsDev t, MoveSampling ms, PlayoutCap pc, ForcedPlayouts fp) {
-    sp_move_body<false, true, true, true>(gm, t, blockIdx.x, threadIdx.x, 0, ms, pc, fp);
+    sp_move_body<false, true, true, true, true>(gm, t, blockIdx.x, threadIdx.x, 0, ms, pc, fp);
 }
 
 // ---------------------------------------------------------------- free-running self-play step
@@ -2181,7 +2260,9 @@ __global__ __launch_bounds__(64) void k_sp_move_f(GamesDev gm, MctsDev t, MoveSa
 #define OZ_ADVANCE_CAP 2
 // EXTRAS: the one instantiation for engines with root noise, move sampling, a playout cap or any of them together; which of them is on is looked
 // at when it runs (t.noise_eps > 0, xt.sample.plies > 0, xt.cap.fast_sims > 0).  An engine with none launches the EXTRAS = false kernels, which
-// are the code they were before.
+// are the code they were before.  VALUES: the move records root values where gm.log_values is set (sp_move_body<.., VALUES>); part of EXTRAS,
+// and on its own the instantiation of an engine whose only option it is (k_advance_v: the plain kernels plus the move's value, not the
+// registers of every extra).
 //   playout cap: the move is played once `done` reaches the budget of the slot's current (game id, ply) instead of `sims`; a fast root draws no
 //   noise.  Both are oz_playout_budget of the key, evaluated again at every pass of the loop: noise_armed[g] == 0 keeps meaning "no noise on this
 //   root" and needs no third state for "decided: none", and a fast root stays unarmed for oz_selfplay_root_noise to report.
@@ -2191,7 +2272,7 @@ __global__ __launch_bounds__(64) void k_sp_move_f(GamesDev gm, MctsDev t, MoveSa
 //   forced playouts: the descents force through t.forced_k, the move prunes its row while the root's noise is still armed (sp_move_body<.., FORCE>
 //   reads the flag before it clears it): a function of the root record and eta, the same rows again.
 struct SelfplayExtras { double alpha; uint64_t seed; MoveSampling sample; PlayoutCap cap; ForcedPlayouts forced; };
-template <bool EXTRAS = false>
+template <bool EXTRAS = false, bool VALUES = EXTRAS>
 __device__ __forceinline__ void advance_body(const GamesDev& gm, const MctsDev& t, TreeLds& L, int g, int lane, int sims, int* __restrict__ sims_done, int cap,
                                              SelfplayExtras xt = SelfplayExtras{}) {
     if (unii(t.leaf_status[g]) == OZ_LEAF_WAIT) {          // batch cap: the leaf of the simulation in progress found no slot -- offer it again, unchanged
@@ -2217,7 +2298,7 @@ __device__ __forceinline__ void advance_body(const GamesDev& gm, const MctsDev& 
                 budget = oz_playout_budget(gm.seed, uni64(gm.game_id[g]), (uint64_t)unii(gm.ply[g]), sims, xt.cap.fast_sims, xt.cap.full_prob, &fast);
         }
         if (done >= budget) {                              // training.py:42-67: the move after num_simulations simulations
-            sp_move_body<EXTRAS, EXTRAS, EXTRAS, EXTRAS>(gm, t, g, lane, 0, xt.sample, xt.cap, xt.forced);
+            sp_move_body<EXTRAS, EXTRAS, EXTRAS, EXTRAS, VALUES>(gm, t, g, lane, 0, xt.sample, xt.cap, xt.forced);
             done = 0;
             if (lane == 0) t.leaf_status[g] = OZ_LEAF_IDLE;    // the evaluated leaf is consumed: nothing pending if the cap ends the loop here
             wave_sync();
@@ -2265,6 +2346,19 @@ __global__ __launch_bounds__(64) void k_backup_advance_x(GamesDev gm, MctsDev t,
     wave_sync();
     __syncthreads();
     advance_body<true>(gm, t, L, blockIdx.x, threadIdx.x, sims, sims_done, cap, xt);
+}
+
+// (the *_v kernels: the plain kernels whose move records root values, launched by engines with record_values and no other extra)
+__global__ __launch_bounds__(64) void k_advance_v(GamesDev gm, MctsDev t, int sims, int* __restrict__ sims_done, int cap) {
+    __shared__ TreeLds L;
+    advance_body<false, true>(gm, t, L, blockIdx.x, threadIdx.x, sims, sims_done, cap);
+}
+__global__ __launch_bounds__(64) void k_backup_advance_v(GamesDev gm, MctsDev t, int sims, int* __restrict__ sims_done, int cap) {
+    __shared__ TreeLds L;
+    expand_backup_body(t, L, blockIdx.x, threadIdx.x, 0);
+    wave_sync();
+    __syncthreads();
+    advance_body<false, true>(gm, t, L, blockIdx.x, threadIdx.x, sims, sims_done, cap);
 }
 
 // RandomOthelloAgent.play (agents.py:20-24) for every live game whose mover is `side`: random.choice over the valid
@@ -2353,6 +2447,10 @@ struct oz_selfplay {
     std::mutex mu;
     long long records_read = 0;
     long long* d_endgame = nullptr;  // oz_selfplay_solve_records: its six counters (allocated by the first call)
+    // oz_selfplay_set_record_values: the buffers stay once allocated; gm.log_values / gm.values point at them while the option is on
+    double *val_log = nullptr, *val_rec = nullptr;
+    float* targets = nullptr;        // oz_selfplay_value_targets: [record_cap], allocated by the first call
+    long long* d_vt = nullptr;       // ... and its three counters
     template <typename T> int alloc(T** p, size_t count) {
         OZ_HIP(hipMalloc((void**)p, sizeof(T) * (count ? count : 1)));
         allocs.push_back(*p);
@@ -2477,7 +2575,7 @@ static int selfplay_round_async(oz_selfplay* sp, int sims, int stagger_round) {
         }
     } else if (int rc = mcts_steps_async(m, sp->net, sims, G, true, capped ? &ck : nullptr)) return rc;
     timed(m, TS_MOVE, m->profile, [&] {
-        if (sp->forced.k > 0.0) hipLaunchKernelGGL(k_sp_move_f, dim3(G), dim3(64), 0, s, sp->gm, m->d, sp->sample, capped ? sp->cap : PlayoutCap{0, 0.0, nullptr, nullptr}, sp->forced);
+        if (sp->forced.k > 0.0 || sp->gm.log_values) hipLaunchKernelGGL(k_sp_move_f, dim3(G), dim3(64), 0, s, sp->gm, m->d, sp->sample, capped ? sp->cap : PlayoutCap{0, 0.0, nullptr, nullptr}, sp->forced);
         else if (capped) hipLaunchKernelGGL(k_sp_move_c, dim3(G), dim3(64), 0, s, sp->gm, m->d, sp->sample, sp->cap);
         else if (sp->sample.plies > 0) hipLaunchKernelGGL(k_sp_move_s, dim3(G), dim3(64), 0, s, sp->gm, m->d, sp->sample);
         else hipLaunchKernelGGL(k_sp_move, dim3(G), dim3(64), 0, s, sp->gm, m->d, 0);
@@ -2752,6 +2850,9 @@ OZ_API int oz_selfplay_run_steps(oz_selfplay* sp, int steps) {
                 const SelfplayExtras xt{sp->noise_alpha, sp->gm.seed, sp->sample, sp->cap, sp->forced};
                 if (fuse && i > 0) hipLaunchKernelGGL(k_backup_advance_x, dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap, xt);
                 else hipLaunchKernelGGL(k_advance_x, dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap, xt);
+            } else if (sp->gm.log_values) {
+                if (fuse && i > 0) hipLaunchKernelGGL(k_backup_advance_v, dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap);
+                else hipLaunchKernelGGL(k_advance_v, dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap);
             } else if (fuse && i > 0) hipLaunchKernelGGL(k_backup_advance, dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap);
             else hipLaunchKernelGGL(k_advance, dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap);
         });
@@ -2944,6 +3045,178 @@ OZ_API int oz_selfplay_solve_records(oz_selfplay* sp, int64_t first_record, int 
     if (stats) {
         stats->records = acc[0]; stats->solved = acc[1]; stats->z_changed = acc[2]; stats->optimal_moves = acc[3];
         stats->disc_loss_sum = acc[4]; stats->disc_loss_max = (int32_t)acc[5]; stats->pad = 0;
+    }
+    return OZ_OK;
+}
+
+// ---------------------------------------------------------------- value targets from the search ("value targets" in the header)
+// root values of the engine's searched moves: [G][64 plies] of the games in progress and one double per record.  Before the first driver call.
+OZ_API int oz_selfplay_set_record_values(oz_selfplay* sp, int enable) {
+    OZ_REQUIRE(sp, "null selfplay");
+    OZ_REQUIRE(enable == 0 || enable == 1, "oz_selfplay_set_record_values: enable = %d (0 or 1)", enable);
+    std::lock_guard<std::mutex> lk(sp->mu);
+    if (sp->mode != 0) { oz_set_error("oz_selfplay_set_record_values: the engine has been driven already (set it before the first driver call)"); return OZ_ERR_STATE; }
+    if (enable && !sp->val_log) {
+        hipSetDevice(sp->m->device);
+        const size_t held = sp->allocs.size(), G = (size_t)sp->gm.G, cap = (size_t)sp->gm.record_cap;
+        double *val_log = nullptr, *val_rec = nullptr;
+        int rc = sp->alloc(&val_log, G * 64);
+        if (!rc) rc = sp->alloc(&val_rec, cap);
+        if (!rc && (hipMemset(val_log, 0, 8 * G * 64) != hipSuccess || hipMemset(val_rec, 0, 8 * (cap ? cap : 1)) != hipSuccess)) {
+            oz_set_error("oz_selfplay_set_record_values: clearing the buffers failed");
+            rc = OZ_ERR_HIP;
+        }
+        if (rc) {
+            for (size_t i = held; i < sp->allocs.size(); ++i) hipFree(sp->allocs[i]);
+            sp->allocs.resize(held);
+            return rc;
+        }
+        sp->val_log = val_log; sp->val_rec = val_rec;
+    }
+    sp->gm.log_values = enable ? sp->val_log : nullptr;
+    sp->gm.values = enable ? sp->val_rec : nullptr;
+    return OZ_OK;
+}
+#define OZ_REQUIRE_VALUES(sp) OZ_REQUIRE((sp)->gm.values, "this engine does not record root values: call oz_selfplay_set_record_values(sp, 1) before the first driver call")
+OZ_API int oz_selfplay_values(oz_selfplay* sp, double* out, int64_t max_records, int64_t* written) {
+    OZ_REQUIRE(sp, "null selfplay");
+    OZ_REQUIRE_VALUES(sp);
+    return selfplay_rows(sp, sp->gm.values, sizeof(double), out, max_records, written, hipMemcpyDeviceToHost);
+}
+OZ_API int oz_selfplay_values_device(oz_selfplay* sp, void* dst_device, int64_t max_records, int64_t* written) {
+    OZ_REQUIRE(sp, "null selfplay");
+    OZ_REQUIRE_VALUES(sp);
+    return selfplay_rows(sp, sp->gm.values, sizeof(double), dst_device, max_records, written, hipMemcpyDeviceToDevice);
+}
+
+// One wavefront per record i of [first, have).  Lane l loads record i + l: a game's records are contiguous and ascending in ply, so the
+// game ends before the first lane l >= 1 whose record has ply 0 or another game id, or lies past the range (a game has at most 60 plies:
+// the end is always inside the wave).  TD: the recurrence runs backwards from there over the lanes' (p z, p q, exact), every lane the
+// same steps (oz_value_target_td_step); lane 0 stores.  acc: [0] records [1] exact [2] sign(t) != z
+__global__ __launch_bounds__(64) void k_value_targets(const oz_record* __restrict__ recs, const double* __restrict__ values, long long first, long long have,
+                                                      int n2, int mode, double om, double param, int exact_empties, float* __restrict__ targets,
+                                                      long long* __restrict__ acc) {
+    const int lane = threadIdx.x;
+    const long long i = first + blockIdx.x, j = i + lane;
+    const bool in = j < have;
+    uint64_t gid = 0, black = 0, white = 0;
+    int ply = 0, p = 1, z = 1;
+    double q = 0.0;
+    if (in) {
+        const oz_record* r = recs + j;
+        gid = r->game_id; black = r->black; white = r->white; ply = r->ply; p = r->player; z = r->z;
+        q = values[j];
+    }
+    const uint64_t gid0 = uni64(gid);
+    const uint64_t stop = __ballot(lane >= 1 && (!in || ply == 0 || gid != gid0));
+    const int T = stop ? oz_ctz(stop) : 64;                       // records from i to the end of its game
+    const bool exact = oz_value_target_exact(black, white, n2, exact_empties);
+    const double pz = (double)(p * z), pq = (double)p * q;
+    double t;
+    if (mode == OZ_VALUE_TARGET_TD) {
+        double B = __shfl(pz, T - 1, 64);
+        for (int k = T - 1; k >= 0; --k) {
+            const double kpz = __shfl(pz, k, 64), kpq = __shfl(pq, k, 64);
+            const int kex = __shfl((int)exact, k, 64);
+            B = kex ? kpz : oz_value_target_td_step(kpq, B, om, param);
+        }
+        t = (double)p * B;
+    } else if (mode == OZ_VALUE_TARGET_BLEND) {
+        t = exact ? (double)z : oz_value_target_blend((double)z, q, om, param);
+    } else t = (double)z;
+    if (lane != 0) return;
+    const float t32 = (float)t;
+    targets[i] = t32;
+    const int sgn = t32 > 0.f ? 1 : t32 < 0.f ? -1 : 0;
+    atomicAdd((unsigned long long*)&acc[0], 1ULL);
+    if (exact) atomicAdd((unsigned long long*)&acc[1], 1ULL);
+    if (sgn != z) atomicAdd((unsigned long long*)&acc[2], 1ULL);
+}
+
+static int value_target_check(const char* fn, int mode, double param, int exact_empties) {
+    OZ_REQUIRE(mode == OZ_VALUE_TARGET_OUTCOME || mode == OZ_VALUE_TARGET_BLEND || mode == OZ_VALUE_TARGET_TD, "%s: mode = %d (OZ_VALUE_TARGET_*)", fn, mode);
+    OZ_REQUIRE(mode == OZ_VALUE_TARGET_OUTCOME || (param >= 0.0 && param <= 1.0), "%s: parameter %g outside [0, 1]", fn, param);      // (NaN fails both compares)
+    OZ_REQUIRE(exact_empties >= 0 && exact_empties <= OZ_SOLVE_MAX_EMPTIES, "%s: exact_empties %d outside 0..%d", fn, exact_empties, OZ_SOLVE_MAX_EMPTIES);
+    return OZ_OK;
+}
+
+OZ_API int oz_selfplay_value_targets(oz_selfplay* sp, int64_t first_record, int mode, double param, int exact_empties, oz_value_target_stats* stats) {
+    OZ_REQUIRE(sp, "null selfplay");
+    if (int rc = value_target_check("oz_selfplay_value_targets", mode, param, exact_empties)) return rc;
+    OZ_REQUIRE(first_record >= 0, "oz_selfplay_value_targets: first_record %lld", (long long)first_record);
+    std::lock_guard<std::mutex> lk(sp->mu);
+    OZ_REQUIRE_VALUES(sp);
+    if (sp->m->selected) { oz_set_error("oz_selfplay_value_targets: a step is pending (oz_mcts_select without oz_mcts_backup)"); return OZ_ERR_STATE; }
+    hipSetDevice(sp->m->device);
+    hipStream_t s = sp->m->stream;
+    OZ_HIP(hipStreamSynchronize(s));
+    unsigned long long total = 0;
+    OZ_HIP(hipMemcpy(&total, sp->gm.counters, 8, hipMemcpyDeviceToHost));
+    const long long have = (long long)total > sp->gm.record_cap ? sp->gm.record_cap : (long long)total;
+    const long long count = have > first_record ? have - first_record : 0;
+    OZ_REQUIRE(count < (1ll << 31), "too many records in one call");
+    if (!sp->targets) {
+        if (int rc = sp->alloc(&sp->targets, (size_t)sp->gm.record_cap)) return rc;
+        OZ_HIP(hipMemsetAsync(sp->targets, 0, sizeof(float) * (size_t)(sp->gm.record_cap ? sp->gm.record_cap : 1), s));
+    }
+    long long acc[3] = {0, 0, 0};
+    if (count > 0) {
+        if (!sp->d_vt) { if (int rc = sp->alloc(&sp->d_vt, 3)) return rc; }
+        OZ_HIP(hipMemsetAsync(sp->d_vt, 0, sizeof acc, s));
+        const int n = sp->gm.n;
+        const double om = 1.0 - param;
+        hipLaunchKernelGGL(k_value_targets, dim3((unsigned)count), dim3(64), 0, s, sp->gm.records, sp->gm.values, (long long)first_record, have, n * n, mode, om,
+                           param, exact_empties, sp->targets, sp->d_vt);
+        OZ_HIP(hipGetLastError());
+        OZ_HIP(hipMemcpyAsync(acc, sp->d_vt, sizeof acc, hipMemcpyDeviceToHost, s));
+    }
+    OZ_HIP(hipStreamSynchronize(s));
+    if (stats) { stats->records = acc[0]; stats->exact = acc[1]; stats->sign_changed = acc[2]; }
+    return OZ_OK;
+}
+#define OZ_REQUIRE_TARGETS(sp) OZ_REQUIRE((sp)->targets, "this engine holds no value targets: call oz_selfplay_value_targets first")
+OZ_API int oz_selfplay_targets(oz_selfplay* sp, float* out, int64_t max_records, int64_t* written) {
+    OZ_REQUIRE(sp, "null selfplay");
+    OZ_REQUIRE_TARGETS(sp);
+    return selfplay_rows(sp, sp->targets, sizeof(float), out, max_records, written, hipMemcpyDeviceToHost);
+}
+OZ_API int oz_selfplay_targets_device(oz_selfplay* sp, void* dst_device, int64_t max_records, int64_t* written) {
+    OZ_REQUIRE(sp, "null selfplay");
+    OZ_REQUIRE_TARGETS(sp);
+    return selfplay_rows(sp, sp->targets, sizeof(float), dst_device, max_records, written, hipMemcpyDeviceToDevice);
+}
+// the same targets on the host (no device needed): records in any order, grouped by game id and sorted by ply
+OZ_API int oz_value_targets(const oz_record* records, const double* values, int64_t R, int n, int mode, double param, int exact_empties, float* out) {
+    if (int rc = value_target_check("oz_value_targets", mode, param, exact_empties)) return rc;
+    OZ_REQUIRE(n == 4 || n == 6 || n == 8, "oz_value_targets: board size must be 4, 6 or 8 (got %d)", n);
+    OZ_REQUIRE(R >= 0, "oz_value_targets: R %lld", (long long)R);
+    if (R == 0) return OZ_OK;
+    OZ_REQUIRE(records && values && out, "oz_value_targets: null argument");
+    std::vector<int64_t> order((size_t)R);
+    for (int64_t i = 0; i < R; ++i) order[(size_t)i] = i;
+    std::stable_sort(order.begin(), order.end(), [records](int64_t a, int64_t b) {
+        return records[a].game_id != records[b].game_id ? records[a].game_id < records[b].game_id : records[a].ply < records[b].ply;
+    });
+    const double om = 1.0 - param;
+    const int n2 = n * n;
+    for (int64_t lo = 0; lo < R;) {
+        int64_t hi = lo + 1;
+        while (hi < R && records[order[(size_t)hi]].game_id == records[order[(size_t)lo]].game_id) ++hi;
+        const oz_record& last = records[order[(size_t)hi - 1]];
+        double B = (double)(last.player * last.z);
+        for (int64_t k = hi - 1; k >= lo; --k) {
+            const int64_t ix = order[(size_t)k];
+            const oz_record& r = records[ix];
+            const bool exact = oz_value_target_exact(r.black, r.white, n2, exact_empties);
+            const double z = (double)r.z, p = (double)r.player, q = values[ix];
+            double t = z;
+            if (mode == OZ_VALUE_TARGET_TD) {
+                B = exact ? (double)(r.player * r.z) : oz_value_target_td_step(p * q, B, om, param);
+                t = p * B;
+            } else if (mode == OZ_VALUE_TARGET_BLEND && !exact) t = oz_value_target_blend(z, q, om, param);
+            out[ix] = (float)t;
+        }
+        lo = hi;
     }
     return OZ_OK;
 }

@@ -15,6 +15,7 @@ from ._lib import RECORD_DTYPE
 
 RECORD_BYTES = RECORD_DTYPE.itemsize
 VISITS_BYTES = 64 * 4                  # one record's root visit counts, int32 by square row*8+col
+TARGET_BYTES = 4                       # one record's value target, float32
 
 
 def shard_games(total_games, rank, world_size):
@@ -90,11 +91,26 @@ def engine_visits_tensor(engine, device, count):
     return t[:count]
 
 
-def pooled_selfplay_records(engine, device, group=None, with_visits=False):
+def engine_targets_tensor(engine, device, count):
+    """the first `count` value targets of the engine (after SelfPlayEngine.value_targets) as a uint8 [count, 4] tensor on `device` -- the
+    float32 target of each record, in the ring order of engine_records_tensor; device to device"""
+    t = torch.empty((max(count, 1), TARGET_BYTES), dtype=torch.uint8, device=device)
+    written = engine.targets_to_device(t.data_ptr(), count) if count else 0
+    assert written == count, (written, count)
+    return t[:count]
+
+
+def pooled_selfplay_records(engine, device, group=None, with_visits=False, with_values=False):
     """records of every rank's completed games, identical on all ranks, sorted by (game_id, ply).
     with_visits=True (engines created with record_visits=True): (records, counts int32 [R, 64]) -- each rank's rows travel as
-    record || counts (48 + 256 bytes) in the same all-gather and are split after the sort"""
+    record || counts (48 + 256 bytes) in the same all-gather and are split after the sort.
+    with_values=True (every rank has called SelfPlayEngine.value_targets on its own records): the float32 value targets travel as 4 more
+    bytes per row in the same all-gather and come back last: (records, [counts,] targets)."""
     local = engine_records_tensor(engine, device)
+    if with_values:
+        parts = [local] + ([engine_visits_tensor(engine, device, local.shape[0])] if with_visits else [])
+        rows = gather_records(torch.cat(parts + [engine_targets_tensor(engine, device, local.shape[0])], dim=1), group)
+        return split_record_rows(rows, with_targets=True, with_visits=with_visits)
     if not with_visits:
         allrec = tensor_to_records(gather_records(local, group))
         return allrec[np.lexsort((allrec["ply"], allrec["game_id"]))]
@@ -102,13 +118,20 @@ def pooled_selfplay_records(engine, device, group=None, with_visits=False):
     return split_record_rows(rows)
 
 
-def split_record_rows(rows):
-    """uint8 [R, 48 + 256] rows (record || int32 [64] visit counts) -> (records, counts) sorted by (game_id, ply)"""
-    a = rows.detach().cpu().contiguous().numpy().reshape(-1, RECORD_BYTES + VISITS_BYTES)
+def split_record_rows(rows, with_targets=False, with_visits=True):
+    """uint8 [R, 48 + 256] rows (record || int32 [64] visit counts) -> (records, counts) sorted by (game_id, ply).
+    with_targets=True: the rows end in a float32 value target (4 more bytes) -> (records, [counts,] targets float32 (R,));
+    with_visits=False: the rows hold no visit counts."""
+    width = RECORD_BYTES + (VISITS_BYTES if with_visits else 0) + (TARGET_BYTES if with_targets else 0)
+    a = rows.detach().cpu().contiguous().numpy().reshape(-1, width)
     rec = np.ascontiguousarray(a[:, :RECORD_BYTES]).view(RECORD_DTYPE).reshape(-1)
-    counts = np.ascontiguousarray(a[:, RECORD_BYTES:]).view("<i4").reshape(-1, 64)
     order = np.lexsort((rec["ply"], rec["game_id"]))
-    return rec[order], counts[order]
+    out = [rec[order]]
+    if with_visits:
+        out.append(np.ascontiguousarray(a[:, RECORD_BYTES:RECORD_BYTES + VISITS_BYTES]).view("<i4").reshape(-1, 64)[order])
+    if with_targets:
+        out.append(np.ascontiguousarray(a[:, width - TARGET_BYTES:]).view("<f4").reshape(-1)[order])
+    return tuple(out)
 
 
 # ---------------------------------------------------------------- arena games sharded over the ranks (SURVEY.md 8(e): all-gather of (winner, points))

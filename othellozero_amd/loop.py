@@ -73,7 +73,7 @@ class CircularArray:
         return f'{type(self).__name__}({len(self._list)!r})'
 
 
-def examples_from_records(records, board_size, alias_final=True, in_channels=2, visits=None, target_temperature=1.0):
+def examples_from_records(records, board_size, alias_final=True, in_channels=2, visits=None, target_temperature=1.0, values=None):
     """move records of finished games -> the reference's example tuples [(board, one-hot policy (n,n), z)], 8 per move in
     training.py:13-23's order.
 
@@ -85,7 +85,12 @@ def examples_from_records(records, board_size, alias_final=True, in_channels=2, 
     those examples are never aliased.
     visits (int32 (R, 64), the records' root visit counts): the policy of every example is the search's visit distribution at
     target_temperature (expand_examples) instead of the one-hot of the move played.
-    The fast records of a playout cap (_lib.record_fast) are no training examples: they and their visit-count rows are dropped first."""
+    The fast records of a playout cap (_lib.record_fast) are no training examples: they and their visit-count rows are dropped first.
+    values (float32 (R,), the records' value targets): the z of every example is its record's target, a float, instead of the int outcome."""
+    if values is not None:
+        val = np.ascontiguousarray(values, dtype=np.float32).ravel()
+        assert val.size == np.asarray(records).size, f"{val.size} value targets for {np.asarray(records).size} records"
+        values = val[_lib.record_fast(records).ravel() == 0]
     records, visits = _lib.full_records(records, visits)
     one_channel = in_channels == 1
     boards, pol, z = expand_examples(records, board_size, alias_final=alias_final and not one_channel, visits=visits,
@@ -95,13 +100,17 @@ def examples_from_records(records, board_size, alias_final=True, in_channels=2, 
         boards = boards[..., 0].astype(np.int64) - boards[..., 1].astype(np.int64)      # convert_to_one_channel_board
     else:
         boards = boards.astype(bool)
+    if values is not None:
+        z = [float(t) for t in np.repeat(values, 8)]
+    else:
+        z = [int(zz) for zz in z]
     if visits is not None:
-        return [(b, p, int(zz)) for b, p, zz in zip(boards, pol, z)]
+        return list(zip(boards, pol, z))
     out = []
     for b, p, zz in zip(boards, pol, z):
         policy = np.zeros((n, n))
         policy[p // n, p % n] = 1
-        out.append((b, policy, int(zz)))
+        out.append((b, policy, zz))
     return out
 
 
@@ -262,17 +271,19 @@ def self_play_match(board_size, neural_network, old_neural_network, total_games,
 
 def _selfplay_into_replay(replay, neural_network, board_size, num_episodes, num_simulations, degree_exploration, temperature, e_greedy, seed,
                           first_game_id, q_mode, visits, leaves_per_step, root_noise, sample_moves, alias_final_boards, policy_target,
-                          target_temperature, endgame_targets=0, solve_leaves=0, playout_cap=None, forced_playouts=0.0):
+                          target_temperature, endgame_targets=0, solve_leaves=0, playout_cap=None, forced_playouts=0.0, value_target="outcome"):
     """one iteration's games on the engine selfplay_batch would create, played to the end without reading a record, and their examples
     appended to the device buffer; -> (records appended, the endgame solver's statistics or None).  One-channel (BaseNN) examples are never
     aliased (examples_from_records).  endgame_targets > 0: SelfPlayEngine.solve_records before the append.  playout_cap: the engine's; the
     append leaves the fast records out and counts the fully searched ones.  forced_playouts: the engine's; its visit rows, which the append
-    reads, are then the pruned ones."""
+    reads, are then the pruned ones.  value_target: the engine records root values and the append computes the value targets (after the
+    endgame solver, exact_empties = endgame_targets)."""
     from .training import SelfPlayEngine
+    vt_on = _lib.check_value_target(value_target)[0] != _lib.VALUE_TARGET_OUTCOME
     eng = SelfPlayEngine(neural_network, board_size, num_episodes, num_simulations, degree_exploration, temperature, e_greedy, seed,
                          first_game_id, q_mode=q_mode, record_visits=visits, leaves_per_step=leaves_per_step, root_noise=root_noise,
                          sample_moves=sample_moves, solve_leaves=solve_leaves, **({"playout_cap": playout_cap} if playout_cap is not None else {}),
-                         **({"forced_playouts": forced_playouts} if forced_playouts else {}))
+                         **({"forced_playouts": forced_playouts} if forced_playouts else {}), **({"record_values": True} if vt_on else {}))
     for _ in range(board_size * board_size):
         eng.run(4)
         if eng.stats()["live_games"] == 0:
@@ -281,7 +292,8 @@ def _selfplay_into_replay(replay, neural_network, board_size, num_episodes, num_
     if solve_leaves:
         training.rows_solved += eng.rows_solved()
     return replay.append_engine(eng, alias_final=alias_final_boards and getattr(neural_network, "in_channels", 2) == 2,
-                                policy_target=policy_target, target_temperature=target_temperature), endgame
+                                policy_target=policy_target, target_temperature=target_temperature,
+                                **({"value_target": value_target, "exact_empties": endgame_targets} if vt_on else {})), endgame
 
 
 def _log_endgame(i, num_iterations, stats):
@@ -295,7 +307,8 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
              seed=1234, reference_aliasing=True, alias_final_boards=True, dump_examples=False, q_mode=_lib.QMODE_F64,
              distributed=False, batched_evaluation=False, policy_target="onehot", target_temperature=1.0, leaves_per_step=1,
              root_noise=None, sample_moves=None, replay="host", evaluation_opponent="random", endgame_targets=0,
-             solve_leaves=0, match_openings=None, evaluation_openings=None, playout_cap=None, forced_playouts=None, eval_symmetry=None):
+             solve_leaves=0, match_openings=None, evaluation_openings=None, playout_cap=None, forced_playouts=None, eval_symmetry=None,
+             value_target="outcome"):
     """main.py:56-259 on the GPU engines; returns `historic` = [(episodes done, win rate vs random), ...]
 
     batched_evaluation=True plays the evaluation games against RandomOthelloAgent in lock step on the GPU
@@ -387,7 +400,18 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
     new seed per iteration, so that the orientation bias of a network that is only approximately equivariant does not repeat in every game
     and in the visit rows policy_target="visits" trains on.  The network's previous setting is back before the fit, matches and evaluation,
     which stay untouched like under every other self-play option.  "mean" (all eight orientations, 8x the network work) is for matches and
-    measurements and is refused here: set it on the networks themselves with set_eval_symmetry("mean") ("Evaluation symmetry")."""
+    measurements and is refused here: set it on the networks themselves with set_eval_symmetry("mean") ("Evaluation symmetry").
+
+    value_target="outcome" (the default: z = the game's outcome, as ever), ("blend", w) or ("td", lam), w / lam in [0, 1]: the value head trains
+    on targets built from the SELF-PLAY searches' root values -- the visit-weighted mean of the root's Q, which the engines then record per
+    move (SelfPlayEngine(record_values=True)).  "blend": (1 - w) z + w q of the move's own search.  "td": KataGo-style short-term targets,
+    TD(lam) backwards over the root values of the following plies, ending in the outcome (lam = 1 is the outcome, lam = 0 the root value).
+    With endgame_targets=E the order is solve, then targets, then append: a solved record keeps its exact z and the plies before it bootstrap
+    from it (exact_empties = E).  Host path, distributed path (each rank computes its own targets, 4 more bytes per row in the all-gather) and
+    replay="device" (the append reads the engine's targets on the device) alike; the examples' z is then a float.  It needs
+    alias_final_boards=False.  Playing strength is neither gated nor claimed ("Value targets")."""
+    vt_on = _lib.check_value_target(value_target, alias_final_boards)[0] != _lib.VALUE_TARGET_OUTCOME
+    vt_kw = {"value_target": value_target} if vt_on else {}
     if eval_symmetry is not None:
         try:
             es_mode, es_seed = (eval_symmetry, 0) if isinstance(eval_symmetry, str) and eval_symmetry == "mean" else eval_symmetry
@@ -486,7 +510,7 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
             appended, endgame = _selfplay_into_replay(device_replay, neural_network, board_size, num_episodes, num_simulations,
                                                       degree_exploration, temperature, e_greedy, seed, total_episodes_done, q_mode, visits,
                                                       leaves_per_step, root_noise, sample_moves, alias_final_boards, policy_target,
-                                                      target_temperature, endgame_targets, solve_leaves, playout_cap, forced_playouts)
+                                                      target_temperature, endgame_targets, solve_leaves, playout_cap, forced_playouts, **vt_kw)
             if endgame is not None:
                 training.endgame_history.append(endgame)
                 _log_endgame(i, num_iterations, endgame)
@@ -501,10 +525,11 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
                 eng = SelfPlayEngine(neural_network, board_size, count, num_simulations, degree_exploration, temperature, e_greedy,
                                      seed=seed, first_game_id=total_episodes_done + first, q_mode=q_mode, record_visits=visits,
                                      leaves_per_step=leaves_per_step, root_noise=root_noise, sample_moves=sample_moves,
-                                     solve_leaves=solve_leaves, **cap_kw)
-                eng.play_to_end(endgame_targets=endgame_targets)                        # each rank relabels its own records
+                                     solve_leaves=solve_leaves, **cap_kw, **({"record_values": True} if vt_on else {}))
+                eng.play_to_end(endgame_targets=endgame_targets, **vt_kw)               # each rank relabels its own records (and computes its targets)
                 training.rows_solved += eng.rows_solved() if solve_leaves else 0
-                records = pooled_selfplay_records(eng, device, with_visits=visits)      # the only exchange of the self-play phase
+                records = pooled_selfplay_records(eng, device, with_visits=visits,      # the only exchange of the self-play phase
+                                                  **({"with_values": True} if vt_on else {}))
                 endgame = getattr(eng, "endgame_stats", None)
                 del eng
             else:
@@ -513,19 +538,21 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
                                          seed=seed, first_game_id=total_episodes_done, q_mode=q_mode, record_visits=visits,
                                          leaves_per_step=leaves_per_step, root_noise=root_noise, sample_moves=sample_moves,
                                          **({"endgame_targets": endgame_targets} if endgame_targets else {}), **({"solve_leaves": solve_leaves} if solve_leaves else {}),
-                                         **cap_kw)
+                                         **cap_kw, **vt_kw)
                 training.rows_solved += selfplay_batch.rows_solved if solve_leaves else 0
                 endgame = getattr(selfplay_batch, "endgame_stats", None) if endgame_targets else None
             restore_eval_symmetry()
             if endgame is not None:
                 training.endgame_history.append(endgame)
                 _log_endgame(i, num_iterations, endgame)
-            counts = None
+            counts = targets = None
+            if vt_on:
+                records, targets = (records[0], records[-1]) if not visits else ((records[0], records[1]), records[2])
             if visits:
                 records, counts = records
             training_examples.extend(examples_from_records(records, board_size, alias_final=alias_final_boards,
                                                            in_channels=getattr(neural_network, "in_channels", 2), visits=counts,
-                                                           target_temperature=target_temperature))
+                                                           target_temperature=target_temperature, **({"values": targets} if vt_on else {})))
             total_episodes_done += num_episodes
             logging.info('[%d/%d] self-play done: %d records, buffer holds %d examples', i, num_iterations, len(records), len(training_examples))
 

@@ -199,6 +199,18 @@ class OthelloMCTS:
             raise KeyError("state is unknown to the search or was never selected from")
         return cnt
 
+    def root_value(self, state):
+        """the search's value of the mover-canonical `state` for the player to move: the visit-weighted mean of its edges' Q over the raw
+        visit counts (include/othellozero_amd.h, "value targets"; agents.rules_root_values of the node's dump).  KeyError if the state is
+        unknown or was never selected from."""
+        own, opp = _lib.pack_board(state)
+        self._set_root(own, opp)
+        val, rc = np.zeros(1, np.float64), np.zeros(1, np.int32)
+        _lib.check(_lib.load().oz_mcts_root_values(self._h, _lib.p_f64(val), _lib.p_i32(rc)))
+        if rc[0] != 0:
+            raise KeyError("state is unknown to the search or was never selected from")
+        return float(val[0])
+
     def N(self, state, action=None):
         """MCTS/__init__.py:73-84,172-175: 0 for an unknown state, Ns without an action, Nsa[action] otherwise
         (KeyError if the state was never selected from)."""

@@ -60,21 +60,42 @@ class ReplayBuffer:
     def clear(self):
         _lib.check(_lib.load().oz_replay_clear(self._h))
 
-    def append_engine(self, eng, first_record=0, alias_final=False, policy_target="onehot", target_temperature=1.0):
+    def append_engine(self, eng, first_record=0, alias_final=False, policy_target="onehot", target_temperature=1.0, value_target="outcome",
+                      exact_empties=0):
         """the records [first_record, completed so far) of a SelfPlayEngine -> 8 examples each, in ascending (game_id, ply), device to
         device; returns the number of records appended.  policy_target="visits" needs an engine created with record_visits=True.
-        The fast records of a playout cap (_lib.record_fast) are left out and not counted."""
+        The fast records of a playout cap (_lib.record_fast) are left out and not counted.
+        value_target=("blend", w) / ("td", lam) (an engine created with record_values=True; alias_final=False): the engine computes the
+        value targets of those records (SelfPlayEngine.value_targets(value_target, exact_empties, first_record)) and every example's z is
+        its record's float32 target instead of the game outcome; "outcome" is the call without it."""
         target, T = _target(policy_target, target_temperature)
+        mode, _ = _lib.check_value_target(value_target, alias_final)
         done = C.c_int64()
+        if mode != _lib.VALUE_TARGET_OUTCOME:
+            eng.value_targets(value_target, exact_empties=exact_empties, first_record=first_record)
+            _lib.check(_lib.load().oz_replay_append_selfplay_targets(self._h, eng._h, int(first_record), 0, target, T, C.byref(done)))
+            return done.value
         _lib.check(_lib.load().oz_replay_append_selfplay(self._h, eng._h, int(first_record), 1 if alias_final else 0, target, T, C.byref(done)))
         return done.value
 
-    def append_records(self, records, visits=None, alias_final=False, policy_target="onehot", target_temperature=1.0):
+    def append_records(self, records, visits=None, alias_final=False, policy_target="onehot", target_temperature=1.0, values=None):
         """the same from records on the host (_lib.RECORD_DTYPE; visits = their int32 (R, 64) root visit counts for policy_target="visits"),
         in any order: they are appended in ascending (game_id, ply); returns the number of records appended -- the fast records of a
-        playout cap (_lib.record_fast) are left out and not counted"""
+        playout cap (_lib.record_fast) are left out and not counted.
+        values = the records' value targets, float32 (R,) (agents.rules_value_targets, SelfPlayEngine.records(with_targets=True)): every
+        example's z is its record's target instead of the records' z"""
         target, T = _target(policy_target, target_temperature)
         rec = np.ascontiguousarray(records, dtype=_lib.RECORD_DTYPE)
+        if values is not None:
+            val = np.ascontiguousarray(values, dtype=np.float32).ravel()
+            assert val.size == rec.size, f"{val.size} value targets for {rec.size} records"
+            cnt = None
+            if visits is not None:
+                cnt = np.ascontiguousarray(visits, dtype=np.int32).reshape(-1, 64)
+                assert cnt.shape[0] == rec.size, f"{cnt.shape[0]} visit-count rows for {rec.size} records"
+            _lib.check(_lib.load().oz_replay_append_records_values(self._h, rec.ctypes.data_as(C.c_void_p), None if cnt is None else _lib.p_i32(cnt),
+                                                                   _lib.p_f32(val), rec.size, 1 if alias_final else 0, target, T))
+            return int((_lib.record_fast(rec) == 0).sum())
         cnt = None
         if visits is not None:
             cnt = np.ascontiguousarray(visits, dtype=np.int32).reshape(-1, 64)

@@ -33,7 +33,7 @@ def training_example_symmetries(board, policy):
 def execute_episode(board_size, neural_network, degree_exploration, num_simulations, policy_temperature, e_greedy,
                     q_mode=_lib.QMODE_F64, snapshot_boards=False, policy_target="onehot", target_temperature=1.0,
                     leaves_per_step=1, root_noise=None, noise_seed=0, sample_moves=None, sample_seed=0, solve_leaves=0,
-                    forced_playouts=None):
+                    forced_playouts=None, value_target="outcome"):
     """training.py:26-72.  Returns [(board (n,n,2) bool, one-hot policy (n,n) float64, z int), ...], 8 per move.
 
     snapshot_boards=False reproduces the reference exactly, including its aliasing quirk: the
@@ -57,7 +57,13 @@ def execute_episode(board_size, neural_network, degree_exploration, num_simulati
     (OthelloMCTS); a native network only.
 
     forced_playouts=k > 0 (needs root_noise): KataGo's forced playouts in every move's search, and with policy_target="visits" the stored
-    distribution is that of the pruned counts (OthelloMCTS.pruned_counts); the move is still chosen from the raw counts."""
+    distribution is that of the pruned counts (OthelloMCTS.pruned_counts); the move is still chosen from the raw counts.
+
+    value_target=("blend", w) / ("td", lam): every move's root value (OthelloMCTS.root_value) is recorded and z is the float value target of the
+    move (agents.rules_value_targets) instead of the int outcome; needs snapshot_boards=True (a search value belongs to the position of its
+    move).  "outcome" is the function without it."""
+    vt_mode, _ = _lib.check_value_target(value_target, not snapshot_boards)
+    root_values, movers, positions = [], [], []
     solve_leaves = _lib.check_solve_leaves(solve_leaves)
     root_noise = _lib.check_root_noise(root_noise)
     forced_playouts = _lib.check_forced_playouts(forced_playouts, root_noise)
@@ -81,6 +87,10 @@ def execute_episode(board_size, neural_network, degree_exploration, num_simulati
         if game.current_player == OthelloPlayer.WHITE:
             state = OthelloGame.invert_board(state)
         policy = mcts.get_policy_action_probabilities(state, policy_temperature)
+        if vt_mode != _lib.VALUE_TARGET_OUTCOME:
+            root_values.append(mcts.root_value(state))
+            movers.append(game.current_player.value)
+            positions.append(_lib.pack_board(game.board(BoardView.TWO_CHANNELS)))
 
         coin = random.random()                      # e-greedy, training.py:51-56
         if coin <= e_greedy:
@@ -104,6 +114,15 @@ def execute_episode(board_size, neural_network, degree_exploration, num_simulati
 
     winner, winner_points = game.get_winning_player()
     logging.info(f'Episode finished: The winner obtained {winner_points} points.')
+    if vt_mode != _lib.VALUE_TARGET_OUTCOME:
+        from .agents import rules_value_targets
+        rec = np.zeros(len(movers), _lib.RECORD_DTYPE)
+        rec["ply"] = np.arange(len(movers))
+        rec["player"] = movers
+        rec["z"] = [1 if winner.value == p else -1 for p in movers]
+        rec["black"], rec["white"] = [b for b, _ in positions], [w for _, w in positions]
+        targets = rules_value_targets(rec, root_values, board_size, value_target)
+        return [(state, policy, float(targets[i // 8])) for i, (state, policy, _player) in enumerate(examples)]
     return [(state, policy, 1 if winner == player else -1) for state, policy, player in examples]
 
 
@@ -151,7 +170,7 @@ class SelfPlayEngine:
                  policy_temperature=1.0, e_greedy=0.9, seed=1234, first_game_id=0, game_id_stride=0,
                  q_mode=_lib.QMODE_F64, refill=False, node_cap=0, record_cap=0, dedup=True, batch_cap=0, eval_cache=False,
                  record_visits=False, leaves_per_step=1, root_noise=None, sample_moves=None, solve_leaves=0, playout_cap=None,
-                 forced_playouts=None):
+                 forced_playouts=None, record_values=False):
         """dedup: cross-game leaf de-duplication (a board several games reach in one batch is evaluated once; no record changes);
         batch_cap: leaves per network batch of the free-running driver (0 = none; see preferred_batch_cap);
         eval_cache: take (pi, v) of boards the network has evaluated before from its persistent cache (NNetWrapper.set_eval_cache) --
@@ -183,7 +202,10 @@ class SelfPlayEngine:
         record_visits the rows of records(with_visits=True) hold the PRUNED counts -- the visits PUCT would not have granted are taken out, a
         child cut down to one visit is dropped -- so everything downstream (expand_examples, the replay buffers) trains on what the search
         concluded.  last_counts() and the moves stay on the raw counts.  run(), run_steps() and stagger() alike; the fast moves of a playout
-        cap are neither forced nor pruned.  forced_playout_stats() counts ("Forced playouts")."""
+        cap are neither forced nor pruned.  forced_playout_stats() counts ("Forced playouts").
+        record_values=True: keep every recorded move's root value -- the visit-weighted mean of the root's Q over the raw counts, for the player
+        to move (oz_selfplay_set_record_values) -- for records(with_values=True) and value_targets(); 512 B per slot + 8 B per record of device
+        memory, no record changes.  Every driver ("Value targets")."""
         playout_cap = _lib.check_playout_cap(playout_cap, num_simulations)
         solve_leaves = _lib.check_solve_leaves(solve_leaves)
         root_noise = _lib.check_root_noise(root_noise)
@@ -219,6 +241,21 @@ class SelfPlayEngine:
         self.forced_playouts = forced_playouts
         if forced_playouts > 0.0:
             _lib.check(lib.oz_selfplay_set_forced_playouts(self._h, forced_playouts))
+        self.record_values = bool(record_values)
+        if record_values:
+            _lib.check(lib.oz_selfplay_set_record_values(self._h, 1))
+
+    def value_targets(self, value_target, exact_empties=0, first_record=0):
+        """oz_selfplay_value_targets: the value targets of the completed records from `first_record` on, computed on the device into the
+        engine's float32 targets (records(with_targets=True), ReplayBuffer.append_engine(value_target=...)); the records are not touched.
+        value_target = "outcome", ("blend", w): (1 - w) z + w q, or ("td", lam): TD(lam) over the root values of the following plies, ending
+        in the outcome.  exact_empties=E > 0 (after solve_records(E)): a record with at most E empties keeps its exact z and restarts the
+        chain.  Needs record_values=True.  -> dict(records, exact, sign_changed)."""
+        mode, param = _lib.check_value_target(value_target)
+        exact_empties = _lib.check_solve_empties(exact_empties, 0, "exact_empties")
+        s = _lib.ValueTargetStats()
+        _lib.check(_lib.load().oz_selfplay_value_targets(self._h, int(first_record), mode, param, exact_empties, C.byref(s)))
+        return {k: int(getattr(s, k)) for k, _ in s._fields_}
 
     def forced_playout_stats(self):
         """dict(k, moves_pruned, visits_raw, visits_kept): the forcing constant that is set (0 = off), the moves whose recorded row differs
@@ -334,23 +371,38 @@ class SelfPlayEngine:
         _lib.check(_lib.load().oz_selfplay_last_counts(self._h, _lib.p_i32(c)))
         return c
 
-    def records(self, with_visits=False):
+    def records(self, with_visits=False, with_values=False, with_targets=False):
         """move records of the games completed so far (numpy structured array, _lib.RECORD_DTYPE),
         sorted by (game_id, ply).  with_visits=True (engine created with record_visits=True): (records, counts), counts =
-        int32 (R, 64) root visit counts of each record's move by square row*8+col, in the same order."""
+        int32 (R, 64) root visit counts of each record's move by square row*8+col, in the same order.
+        with_values=True (record_values=True): (records, [counts,] values), values = float64 (R,) root value of each record's search.
+        with_targets=True (after value_targets()): the float32 (R,) value targets come last, (records, [counts,] [values,] targets)."""
         total = self.stats()["records"]
         out = np.zeros(max(total, 1), dtype=_lib.RECORD_DTYPE)
         written = C.c_int64()
         _lib.check(_lib.load().oz_selfplay_records(self._h, out.ctypes.data_as(C.c_void_p), total, C.byref(written)))
         out = out[:written.value]
         order = np.lexsort((out["ply"], out["game_id"]))
-        if not with_visits:
+        if not (with_visits or with_values or with_targets):
             return out[order]
-        counts = np.zeros((max(out.size, 1), 64), np.int32)
+        ret = [out[order]]
         got = C.c_int64()
-        _lib.check(_lib.load().oz_selfplay_visits(self._h, _lib.p_i32(counts), out.size, C.byref(got)))
-        assert got.value == out.size, (got.value, out.size)
-        return out[order], counts[:out.size][order]
+        if with_visits:
+            counts = np.zeros((max(out.size, 1), 64), np.int32)
+            _lib.check(_lib.load().oz_selfplay_visits(self._h, _lib.p_i32(counts), out.size, C.byref(got)))
+            assert got.value == out.size, (got.value, out.size)
+            ret.append(counts[:out.size][order])
+        if with_values:
+            values = np.zeros(max(out.size, 1), np.float64)
+            _lib.check(_lib.load().oz_selfplay_values(self._h, _lib.p_f64(values), out.size, C.byref(got)))
+            assert got.value == out.size, (got.value, out.size)
+            ret.append(values[:out.size][order])
+        if with_targets:
+            targets = np.zeros(max(out.size, 1), np.float32)
+            _lib.check(_lib.load().oz_selfplay_targets(self._h, _lib.p_f32(targets), out.size, C.byref(got)))
+            assert got.value == out.size, (got.value, out.size)
+            ret.append(targets[:out.size][order])
+        return tuple(ret)
 
     def solve_records(self, max_empties, first_record=0):
         """oz_selfplay_solve_records: the completed records from `first_record` on whose position has at most max_empties empties get the
@@ -377,13 +429,21 @@ class SelfPlayEngine:
         _lib.check(_lib.load().oz_selfplay_visits_device(self._h, C.c_void_p(device_ptr), max_records, C.byref(written)))
         return written.value
 
+    def targets_to_device(self, device_ptr, max_records):
+        """the value targets (float32 [max_records], after value_targets()) in the ring order of records_to_device, device to device"""
+        written = C.c_int64()
+        _lib.check(_lib.load().oz_selfplay_targets_device(self._h, C.c_void_p(device_ptr), max_records, C.byref(written)))
+        return written.value
+
     def eval_time(self):
         ms, launches, leaves = C.c_double(), C.c_int64(), C.c_int64()
         _lib.check(_lib.load().oz_selfplay_eval_time(self._h, C.byref(ms), C.byref(launches), C.byref(leaves)))
         return dict(ms=ms.value, launches=launches.value, leaves=leaves.value)
 
-    def play_to_end(self, max_rounds=None, with_visits=False, endgame_targets=0):
-        """endgame_targets=E > 0: solve_records(E) once the games are over, before the records are read (its stats: self.endgame_stats)"""
+    def play_to_end(self, max_rounds=None, with_visits=False, endgame_targets=0, value_target="outcome"):
+        """endgame_targets=E > 0: solve_records(E) once the games are over, before the records are read (its stats: self.endgame_stats).
+        value_target other than "outcome": value_targets(value_target, exact_empties=endgame_targets) after that (its stats:
+        self.value_target_stats), and the targets come back last: (records, [counts,] targets)"""
         max_rounds = max_rounds or self.n * self.n
         for _ in range(max_rounds):
             self.run(4)
@@ -391,6 +451,9 @@ class SelfPlayEngine:
                 break
         if endgame_targets:
             self.endgame_stats = self.solve_records(endgame_targets)
+        if _lib.check_value_target(value_target)[0] != _lib.VALUE_TARGET_OUTCOME:
+            self.value_target_stats = self.value_targets(value_target, exact_empties=endgame_targets)
+            return self.records(with_visits=with_visits, with_targets=True)
         return self.records(with_visits=with_visits)
 
 
@@ -410,7 +473,7 @@ def preferred_batch_cap(board_size, num_games, channels=512, precision="f16x2"):
     return 0 if cap >= num_games else int(cap)
 
 
-def expand_examples(records, board_size, alias_final=False, visits=None, target_temperature=1.0):
+def expand_examples(records, board_size, alias_final=False, visits=None, target_temperature=1.0, values=None):
     """8-fold symmetry expansion of move records on the GPU (training.py:13-23,58-65).
     Returns boards (R*8, n, n, 2) uint8, policy_index (R*8,) int32 (position of the one-hot), z (R*8,) int8.
 
@@ -419,7 +482,16 @@ def expand_examples(records, board_size, alias_final=False, visits=None, target_
     and the second array returned is pi (R*8, n, n) float64 (target_temperature > 0).
 
     The fast records of a playout cap (_lib.record_fast) are no training examples: they and their visit-count rows are dropped first, so R
-    counts the fully searched moves."""
+    counts the fully searched moves.
+
+    values = the records' value targets (float32 (R,), agents.rules_value_targets / SelfPlayEngine.records(with_targets=True)): each
+    example takes its record's target, 8 per record, and z comes back as float32 (in that case only)."""
+    if values is not None:
+        rec_all = np.ascontiguousarray(records, dtype=_lib.RECORD_DTYPE)
+        val = np.ascontiguousarray(values, dtype=np.float32).ravel()
+        assert val.size == rec_all.size, f"{val.size} value targets for {rec_all.size} records"
+        boards, pol, _z = expand_examples(rec_all, board_size, alias_final, visits=visits, target_temperature=target_temperature)
+        return boards, pol, np.repeat(val[_lib.record_fast(rec_all).ravel() == 0], 8)
     records, visits = _lib.full_records(np.ascontiguousarray(records, dtype=_lib.RECORD_DTYPE), visits)
     rec = np.ascontiguousarray(records, dtype=_lib.RECORD_DTYPE)
     R, n = rec.size, board_size
@@ -445,7 +517,7 @@ def expand_examples(records, board_size, alias_final=False, visits=None, target_
 def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations=100, degree_exploration=1.0,
                    policy_temperature=1.0, e_greedy=0.9, seed=1234, first_game_id=0, q_mode=_lib.QMODE_F64,
                    expand=False, alias_final=False, record_visits=False, target_temperature=1.0, leaves_per_step=1, root_noise=None,
-                   sample_moves=None, endgame_targets=0, solve_leaves=0, playout_cap=None, forced_playouts=None):
+                   sample_moves=None, endgame_targets=0, solve_leaves=0, playout_cap=None, forced_playouts=None, value_target="outcome"):
     """Play num_games complete games; returns the move records (or the expanded examples).
     record_visits=True: (records, visit counts) -- or, with expand, the examples with visit-distribution targets at target_temperature.
     root_noise=(alpha, epsilon): Dirichlet root noise in every search (SelfPlayEngine).
@@ -459,7 +531,12 @@ def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations
     call's SelfPlayEngine.playout_stats() (None when off).
     forced_playouts=k > 0 (needs root_noise): forced playouts and policy target pruning (SelfPlayEngine): with record_visits the counts
     returned, and the targets expanded from them, are the pruned ones.  selfplay_batch.forced_playout_stats holds the last call's
-    SelfPlayEngine.forced_playout_stats() (None when off)."""
+    SelfPlayEngine.forced_playout_stats() (None when off).
+    value_target=("blend", w) / ("td", lam): value targets from the searches' root values (SelfPlayEngine.value_targets, after the endgame
+    targets, exact_empties = endgame_targets).  The float32 targets come back last -- (records, [counts,] targets) -- or, with expand, as
+    the examples' float32 z; with expand it needs alias_final=False.  selfplay_batch.value_target_stats holds the last call's statistics
+    (None when off)."""
+    vt_on = _lib.check_value_target(value_target, expand and alias_final)[0] != _lib.VALUE_TARGET_OUTCOME
     forced_playouts = _lib.check_forced_playouts(forced_playouts, _lib.check_root_noise(root_noise))
     playout_cap = _lib.check_playout_cap(playout_cap, num_simulations)
     solve_leaves = _lib.check_solve_leaves(solve_leaves)
@@ -467,7 +544,19 @@ def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations
     eng = SelfPlayEngine(neural_network, board_size, num_games, num_simulations, degree_exploration, policy_temperature,
                          e_greedy, seed, first_game_id, q_mode=q_mode, record_visits=record_visits, leaves_per_step=leaves_per_step,
                          root_noise=root_noise, sample_moves=sample_moves, solve_leaves=solve_leaves, playout_cap=playout_cap,
-                         **({"forced_playouts": forced_playouts} if forced_playouts > 0.0 else {}))
+                         **({"forced_playouts": forced_playouts} if forced_playouts > 0.0 else {}), **({"record_values": True} if vt_on else {}))
+    selfplay_batch.value_target_stats = None
+    if vt_on:
+        got = eng.play_to_end(with_visits=record_visits, endgame_targets=endgame_targets, value_target=value_target)
+        rec, counts, targets = got if record_visits else (got[0], None, got[1])
+        selfplay_batch.endgame_stats = getattr(eng, "endgame_stats", None)
+        selfplay_batch.value_target_stats = eng.value_target_stats
+        selfplay_batch.forced_playout_stats = eng.forced_playout_stats() if forced_playouts > 0.0 else None
+        selfplay_batch.playout_stats = eng.playout_stats() if playout_cap is not None else None
+        selfplay_batch.rows_solved = eng.rows_solved() if solve_leaves else None
+        if expand:
+            return expand_examples(rec, board_size, alias_final, visits=counts, target_temperature=target_temperature, values=targets)
+        return (rec, counts, targets) if record_visits else (rec, targets)
     selfplay_batch.endgame_stats = selfplay_batch.rows_solved = selfplay_batch.playout_stats = selfplay_batch.forced_playout_stats = None
     if record_visits:
         rec, counts = eng.play_to_end(with_visits=True, endgame_targets=endgame_targets)
