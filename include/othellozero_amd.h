@@ -496,6 +496,76 @@ int oz_mcts_get_forced_playouts(oz_mcts* m, double* k);
 /* oz_mcts_root_counts with the policy target's rows: pruned on the slots whose noise is armed (k > 0), raw on the others */
 int oz_mcts_pruned_counts(oz_mcts* m, int32_t* counts, uint64_t* legal, int32_t* rc);
 
+/* ---- Gumbel search: the root rule of Gumbel AlphaZero (Danihelka et al., ICLR 2022) for a bare search (opt-in; off, every launch and every result
+ * stays bit for bit).  At 16 .. 100 simulations over up to 33 legal moves a visit-count row is mostly "where PUCT happened to look".  The Gumbel
+ * root samples max_considered moves without replacement (Gumbel-top-k of g + logit), spends the budget on them by sequential halving, and yields
+ * pi' = softmax(logit + sigma(completed Q)), a policy target that improves on the prior at any budget.  It replaces root noise, forced playouts
+ * and move sampling.  All arithmetic is float64, no contraction, squares in ascending sq = row*8 + col, the first maximum wins; ONE set of
+ * functions (csrc/oz_common.h: oz_gumbel_value, oz_gumbel_schedule, oz_gumbel_acc / _vmix / _sigma / _x / _score) is what the kernels and the
+ * host-only twins below evaluate.
+ * DRAW       g[sq] = -log(-log(w)) on the legal squares, 0 elsewhere; w = u, the unit draw of the library's stream (seed, game id, ply,
+ *            OZ_RNG_GUMBEL + 256 sq), OZ_RNG_GUMBEL = 7 -- none of the streams 0 .. 6 and none of the root-noise streams 3 + 256 sq + 65536 i.
+ *            u is a multiple of 2^-53 in [0, 1): its one endpoint u == 0 maps to w = 2^-54, so w lies in [2^-54, 1 - 2^-53] and g in
+ *            [-3.63, 36.8], always finite.
+ * SCHEDULE   considered_visits(m, n), a list of length n: for m <= 1 it is 0, 1, .., n-1; else L = ceil(log2 m), visits = [0] * m, k = m, and
+ *            while the list is short: extra = max(1, n / (L k)) times append visits[0 .. k-1] and increment those k entries, then k = max(2, k / 2);
+ *            truncated to n.  m = 4, n = 16: 0 0 0 0 1 1 1 1 2 2 3 3 4 4 5 5.  The host builds the tables of m = 1 .. max_considered at the budget
+ *            and uploads them once.
+ * ROOT       at an armed root with stored priors P, edge statistics N (type tag masked) and Q, N0 = the snapshot of N taken at arming (0 for a
+ *            root not yet in the table) and vhat = the root's own value (header word 3 of its record, below):
+ *                n(a)     = N(a) - N0(a)        this search's visits: a position cannot recur below itself, so only root picks change root edges
+ *                sumN     = sum N;  maxN = max N;  Pvis = sum over N > 0 of P;  PQ = sum over N > 0 of P * Q        one legal square after the other
+ *                vmix     = sumN == 0 ? vhat : (vhat + (sumN / Pvis) * PQ) / (1 + sumN)        Pvis == 0 (only zero-prior squares visited): that term is 0
+ *                qhat(a)  = N(a) > 0 ? Q(a) : vmix
+ *                sigma(a) = ((c_visit + maxN) * c_scale) * ((qhat(a) + 1.0) * 0.5)
+ *                score(a) = (g[a] + log(P(a))) + sigma(a)                log(0) = -inf: such a square wins only where nothing else is legal
+ * PICK       at depth 0 of a descent from an armed root: t = sum n(a), m_eff = min(max_considered, number of legal moves),
+ *            cv = t < budget ? considered_visits(m_eff, budget)[t] : max n(a); the first maximum of score over the legal a with n(a) == cv, or over
+ *            all legal squares if none matches.  Deeper levels and unarmed roots are PUCT exactly as without the option.
+ * MOVE       the first maximum of score over the legal a with n(a) == max n.
+ * POLICY     pi'[a] = exp(x[a] - max x) / sum exp(..), x = log(P) + sigma over the legal squares, the sum in ascending order, each element rounded
+ *            once to float32, 0 off the legal set (every x == -inf: 1 / count).
+ * STORAGE    a search with the option on keeps, in header word 3 of every node it expands (8 bytes that are 0 otherwise), the value the expansion
+ *            backs up before negation: the network's v of the node, or the exact one where solve_leaves replaced it.  Hence the option is switched
+ *            on over an EMPTY tree only: at creation, or after oz_mcts_reset(-1); OZ_ERR_STATE otherwise.  Once on, the object stays on the
+ *            Gumbel-aware kernels (772 B per game plus the tables, at the first call); an object that never switched it on allocates nothing and
+ *            launches the kernels it always launched.
+ * Lifetime: as root noise -- the draw and the snapshot belong to ONE root board of ONE slot; oz_mcts_set_roots with another board disarms the
+ * slot, arming again replaces them.  The host-evaluator split (oz_mcts_select / leaves / backup) honours the option.
+ * OZ_ERR_ARG: max_considered outside [1, 64], c_visit < 0, c_scale <= 0 (NaN included; both at most 1e9), budget outside
+ * [1, OZ_GUMBEL_MAX_BUDGET], a g that is not finite.  OZ_ERR_STATE: a non-empty tree at the first call, a step pending, an object that has armed
+ * root noise or runs leaves_per_step > 1 / the wide kernels -- and, once the option is on, oz_mcts_set_root_noise / oz_mcts_sample_root_noise
+ * with eps > 0, oz_mcts_sample_moves, oz_mcts_set_leaves_per_step(k > 1) and oz_mcts_use_wide_kernels(1).  A refused call leaves the object as
+ * it was. */
+#define OZ_GUMBEL_MAX_BUDGET 65536
+/* host-supplied draws: g[num_games][64] by square; armed[g] != 0 arms slot g for its CURRENT root and snapshots N0 (null: every active slot);
+ * g == NULL sets the parameters and disarms every slot */
+int oz_mcts_set_gumbel(oz_mcts* m, int max_considered, double c_visit, double c_scale, int budget, const double* g /* [num_games][64] or NULL */,
+                       const uint8_t* armed);
+/* device-drawn g for the current roots of the active slots, keyed (seed, game_ids[g], plies[g]) */
+int oz_mcts_sample_gumbel(oz_mcts* m, int max_considered, double c_visit, double c_scale, int budget, uint64_t seed, const uint64_t* game_ids,
+                          const int32_t* plies);
+/* what is set (each pointer may be NULL); an object without the option reads zeros */
+int oz_mcts_get_gumbel(oz_mcts* m, double* g /* [num_games][64] */, uint8_t* armed /* [num_games] */, int32_t* N0 /* [num_games][64] */,
+                       int32_t* max_considered, double* c_visit, double* c_scale, int32_t* budget);
+/* the improved policy rows and the moves of the current roots: rc[g] 0 = ok; 1 = the root is not in the table; 3 = the slot is idle or not armed
+ * (then a zero row and action -1) */
+int oz_mcts_gumbel_policy(oz_mcts* m, float* pi /* [num_games][64] */, int32_t* action /* [num_games] */, int32_t* rc /* [num_games] */);
+/* the scores the last oz_mcts_gumbel_policy evaluated, -inf off the legal set (inspection) */
+int oz_mcts_gumbel_scores(oz_mcts* m, double* score /* [num_games][64] */);
+/* header word 3 of a node (indices as oz_mcts_dump_node): its own value where it was expanded under the option, 0.0 elsewhere */
+int oz_mcts_node_value(oz_mcts* m, int game, int index, double* value);
+/* the host-only twins (no device needed).  oz_gumbel_considered_visits: out[n], m in [1, 64].  oz_gumbel_draws: g[count][64] of `count` roots from
+ * their keys and legal sets.  oz_gumbel_from_units: g of given unit draws u in [0, 1) (the endpoint mapping above).  oz_gumbel_root: pick, move and
+ * pi'[count][64] of `count` roots from their rows by square; score[count][64] and gaps[count][2] may be NULL -- gaps = the distance between the
+ * best and the second-best score among the candidates of the pick and of the move (inf with one candidate). */
+int oz_gumbel_considered_visits(int m, int n, int32_t* out /* [n] */);
+int oz_gumbel_draws(uint64_t seed, const uint64_t* game_ids, const int32_t* plies, const uint64_t* legal, int64_t count, double* g /* [count][64] */);
+int oz_gumbel_from_units(const double* u, int64_t count, double* g);
+int oz_gumbel_root(const int32_t* N, const int32_t* N0, const double* Q, const double* P, const double* g, const uint64_t* legal, const double* vhat,
+                   int64_t count, int max_considered, double c_visit, double c_scale, int budget, int32_t* pick, int32_t* move, float* pi,
+                   double* score, double* gaps);
+
 /* ------------------------------------------------------------------ self-play
  * execute_episode (training.py:26-72) for num_games concurrent games in lock step. */
 typedef struct oz_selfplay oz_selfplay;
@@ -626,6 +696,24 @@ int oz_selfplay_state(oz_selfplay* sp, uint64_t* black, uint64_t* white, int8_t*
 int oz_selfplay_records(oz_selfplay* sp, oz_record* out, int64_t max_records, int64_t* written);
 /* same, device to device, for the RCCL all-gather (dst = device pointer, e.g. a torch tensor) */
 int oz_selfplay_records_device(oz_selfplay* sp, void* dst_device, int64_t max_records, int64_t* written);
+/* self-play with the Gumbel search ("Gumbel search" above): every searched move of the lock-step rounds of oz_selfplay_run arms its root in the
+ * round's roots step -- g drawn on the device, keyed (seed, game id, ply) with the engine's seed, N0 snapshot from the game's persistent tree, the
+ * budget = num_simulations -- and its descents pick by the Gumbel rule at depth 0.  Where the e-greedy coin falls on its greedy branch the move is
+ * the Gumbel root's MOVE and the record's `greedy` byte is 3; the explore branch is unchanged (pure Gumbel: e_greedy = 1).  The engine keeps the
+ * float32 improved-policy row of every searched move beside its record (256 B each; storage, flush and refill as the visit-count rows).
+ * Before the first driver call (OZ_ERR_STATE afterwards).  OZ_ERR_STATE also: together with root noise, forced playouts, move sampling, a playout
+ * cap or leaves_per_step > 1 (whichever comes second is refused), and, once it is on, oz_selfplay_run_steps and oz_selfplay_stagger.  Arenas,
+ * matches and evaluations never use it; solved leaves, recorded values and value targets, de-duplication and the evaluation cache combine with
+ * it unchanged. */
+int oz_selfplay_set_gumbel(oz_selfplay* sp, int max_considered, double c_visit, double c_scale);
+/* what is set (max_considered 0 = off) and the moves picked by the Gumbel rule so far (each may be NULL) */
+int oz_selfplay_get_gumbel(oz_selfplay* sp, int32_t* max_considered, double* c_visit, double* c_scale, int64_t* moves);
+/* g, armed and N0 of the searches of the last move round, as oz_mcts_get_gumbel */
+int oz_selfplay_gumbel(oz_selfplay* sp, double* g /* [num_games][64] */, uint8_t* armed /* [num_games] */, int32_t* N0 /* [num_games][64] */);
+/* the improved-policy rows: row i (float32 [64] by square) belongs to record i of oz_selfplay_records, the same ring order (OZ_ERR_ARG on an
+ * engine without the option) */
+int oz_selfplay_policies(oz_selfplay* sp, float* out /* [max_records][64] */, int64_t max_records, int64_t* written);
+int oz_selfplay_policies_device(oz_selfplay* sp, void* dst_device, int64_t max_records, int64_t* written);
 /* root visit counts of every recorded move (oz_selfplay_config.record_visits = 1; OZ_ERR_ARG otherwise): row i belongs to record i of
  * oz_selfplay_records -- the same ring order, so one permutation sorts both.  A row holds the N(state, action) the move's search left at
  * its root, visits earlier moves' searches left in the same tree included, at square row*8+col, 0 off the legal set: exactly what
@@ -811,6 +899,10 @@ int oz_symmetry_table(int n, int32_t* perm /* [8][n*n] source index of every out
  * device's pow per element.  temperature <= 0: OZ_ERR_ARG.  boards and z as in oz_examples_expand. */
 int oz_examples_expand_visits(const oz_record* records, const int32_t* counts, int64_t count, int n, int alias_final, double temperature,
                               uint8_t* boards, double* pi, int8_t* z);
+/* the same with a float32 policy row by square per record (rows[count][64], e.g. the improved policy of a Gumbel search), on the host (no
+ * device needed): pi[8 * count][n][n] float32, every value copied from its source cell, bit for bit */
+int oz_examples_expand_policy(const oz_record* records, const float* rows, int64_t count, int n, int alias_final, uint8_t* boards, float* pi,
+                              int8_t* z);
 
 /* ------------------------------------------------------------------ training step
  * NNetWrapper.train (Net/NNet.py:53-68) = keras Model.fit on Net/OthelloNN.py:42-56 / Net/BaseNN.py:41-57:
@@ -927,6 +1019,8 @@ int oz_trainer_step_count(oz_trainer* t, int64_t* step);
 typedef struct oz_replay oz_replay;
 #define OZ_REPLAY_TARGET_ONEHOT 0   /* pi = one-hot of the move played (oz_examples_expand) */
 #define OZ_REPLAY_TARGET_VISITS 1   /* pi = the visit distribution at `temperature` (oz_examples_expand_visits) */
+#define OZ_REPLAY_TARGET_POLICY 2   /* pi = the record's improved-policy row of a Gumbel search (oz_examples_expand_policy), bit for bit; an engine
+                                     * with oz_selfplay_set_gumbel, oz_replay_append_selfplay / _targets only (OZ_ERR_ARG elsewhere) */
 int oz_replay_create(oz_replay** out, int n, int64_t capacity /* examples, 1 .. 2^31-1 */);
 int oz_replay_destroy(oz_replay* r);
 int oz_replay_clear(oz_replay* r);

@@ -36,7 +36,7 @@ SOLVE_MAX_EMPTIES = 12                                                          
 SOLVE_LEAVES_MAX_EMPTIES = 10                                                        # OZ_SOLVE_LEAVES_MAX_EMPTIES
 AGENT_RANDOM, AGENT_MINIMAX = 0, 1                                                   # oz_arena_set_opponent
 OPENING_MAX_PLIES = 16                                                               # OZ_OPENING_MAX_PLIES
-REPLAY_TARGET_ONEHOT, REPLAY_TARGET_VISITS = 0, 1                                    # oz_replay_append_*
+REPLAY_TARGET_ONEHOT, REPLAY_TARGET_VISITS, REPLAY_TARGET_POLICY = 0, 1, 2                                    # oz_replay_append_*
 VALUE_TARGET_OUTCOME, VALUE_TARGET_BLEND, VALUE_TARGET_TD = 0, 1, 2                  # OZ_VALUE_TARGET_*
 VALUE_TARGET_MODES = {"outcome": VALUE_TARGET_OUTCOME, "blend": VALUE_TARGET_BLEND, "td": VALUE_TARGET_TD}
 NET_KERNELS = ("input", "conv2", "conv3", "conv4", "fc1", "fc2", "heads")           # OZ_NET_KERNELS slots
@@ -186,6 +186,18 @@ SIGNATURES = {
     "oz_selfplay_set_forced_playouts": [_vp, C.c_double],
     "oz_selfplay_get_forced_playouts": [_vp, _f64p, _i64p, _i64p, _i64p],
     "oz_playout_budgets": [C.c_uint64, _u64p, _i32p, C.c_int64, C.c_int, C.c_int, C.c_double, _i32p],
+    "oz_mcts_set_gumbel": [_vp, C.c_int, C.c_double, C.c_double, C.c_int, _f64p, _u8p],
+    "oz_mcts_sample_gumbel": [_vp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_uint64, _u64p, _i32p],
+    "oz_mcts_get_gumbel": [_vp, _f64p, _u8p, _i32p, _i32p, _f64p, _f64p, _i32p],
+    "oz_mcts_gumbel_policy": [_vp, _f32p, _i32p, _i32p], "oz_mcts_gumbel_scores": [_vp, _f64p],
+    "oz_mcts_node_value": [_vp, C.c_int, C.c_int, _f64p],
+    "oz_selfplay_set_gumbel": [_vp, C.c_int, C.c_double, C.c_double], "oz_selfplay_get_gumbel": [_vp, _i32p, _f64p, _f64p, _i64p],
+    "oz_selfplay_gumbel": [_vp, _f64p, _u8p, _i32p],
+    "oz_selfplay_policies": [_vp, _f32p, C.c_int64, _i64p], "oz_selfplay_policies_device": [_vp, _vp, C.c_int64, _i64p],
+    "oz_gumbel_considered_visits": [C.c_int, C.c_int, _i32p],
+    "oz_gumbel_draws": [C.c_uint64, _u64p, _i32p, _u64p, C.c_int64, _f64p], "oz_gumbel_from_units": [_f64p, C.c_int64, _f64p],
+    "oz_gumbel_root": [_i32p, _i32p, _f64p, _f64p, _f64p, _u64p, _f64p, C.c_int64, C.c_int, C.c_double, C.c_double, C.c_int, _i32p, _i32p, _f32p,
+                       _f64p, _f64p],
     "oz_selfplay_create": [C.POINTER(_vp), C.POINTER(SelfplayConfig), _vp],
     "oz_selfplay_destroy": [_vp], "oz_selfplay_run": [_vp, C.c_int], "oz_selfplay_run_steps": [_vp, C.c_int], "oz_selfplay_sync": [_vp],
     "oz_selfplay_stagger": [_vp, C.c_int], "oz_selfplay_profile": [_vp, C.c_int], "oz_selfplay_set_batch_cap": [_vp, C.c_int], "oz_selfplay_set_dedup": [_vp, C.c_int],
@@ -216,6 +228,7 @@ SIGNATURES = {
     "oz_arena_results": [_vp, _i8p, _i32p, _i32p, _u8p, _i8p, _u64p, _u64p],
     "oz_examples_expand": [_vp, C.c_int64, C.c_int, C.c_int, _u8p, _i32p, _i8p],
     "oz_examples_expand_visits": [_vp, _i32p, C.c_int64, C.c_int, C.c_int, C.c_double, _u8p, _f64p, _i8p],
+    "oz_examples_expand_policy": [_vp, _f32p, C.c_int64, C.c_int, C.c_int, _u8p, _f32p, _i8p],
     "oz_symmetry_table": [C.c_int, _i32p],
     "oz_selftest_arith": [_f64p, _f64p, C.c_int, _f64p, _f64p, _f32p, _f32p],
     "oz_selftest_mfma_rate": [C.c_int, C.c_double, _f64p, _f64p, _f64p],
@@ -406,6 +419,54 @@ def check_forced_playouts(forced_playouts, root_noise=None, need_noise=True):
 EVAL_SYM_OFF, EVAL_SYM_RANDOM, EVAL_SYM_MEAN = 0, 1, 2       # oz_net_set_eval_symmetry
 EVAL_SYM_MODES = {"off": EVAL_SYM_OFF, "random": EVAL_SYM_RANDOM, "mean": EVAL_SYM_MEAN}
 EVAL_SYM_NAMES = {v: k for k, v in EVAL_SYM_MODES.items()}
+
+
+GUMBEL_DEFAULT = (16, 50.0, 1.0)
+
+
+def check_gumbel(gumbel):
+    """gumbel = None, True (= GUMBEL_DEFAULT) or (max_considered, c_visit, c_scale): the Gumbel root search of include/othellozero_amd.h,
+    "Gumbel search".  Returns None or the triple (int, float, float); ValueError for what the library would refuse: max_considered an integer in
+    [1, 64], c_visit in [0, 1e9], c_scale in (0, 1e9]."""
+    if gumbel is None or gumbel is False:
+        return None
+    if gumbel is True:
+        return GUMBEL_DEFAULT
+    try:
+        m, c_visit, c_scale = gumbel
+        if isinstance(m, bool) or int(m) != m:
+            raise TypeError
+        m, c_visit, c_scale = int(m), float(c_visit), float(c_scale)
+    except (TypeError, ValueError):
+        raise ValueError(f"gumbel must be None, True or (max_considered, c_visit, c_scale), got {gumbel!r}") from None
+    if not 1 <= m <= 64:
+        raise ValueError(f"gumbel: max_considered must be in [1, 64] (got {m})")
+    if not 0.0 <= c_visit <= 1e9:
+        raise ValueError(f"gumbel: c_visit must be in [0, 1e9] (got {c_visit})")
+    if not 0.0 < c_scale <= 1e9:
+        raise ValueError(f"gumbel: c_scale must be in (0, 1e9] (got {c_scale})")
+    return m, c_visit, c_scale
+
+
+def check_gumbel_options(gumbel, root_noise=None, forced_playouts=None, sample_moves=None, playout_cap=None, leaves_per_step=1,
+                         free_running=False, distributed=False):
+    """check_gumbel plus what the Gumbel search does not combine with -- a ValueError before any library call: root_noise, forced_playouts
+    and sample_moves (it replaces them), playout_cap (two budgets and two schedules), leaves_per_step > 1, the free-running driver and
+    distributed self-play."""
+    gumbel = check_gumbel(gumbel)
+    if gumbel is None:
+        return None
+    if root_noise is not None or (forced_playouts is not None and forced_playouts != 0) or sample_moves is not None:
+        raise ValueError("gumbel replaces root_noise, forced_playouts and sample_moves: leave them off")
+    if playout_cap is not None:
+        raise ValueError("gumbel does not combine with playout_cap (a cap needs two budgets and two schedules)")
+    if int(leaves_per_step) != 1:
+        raise ValueError(f"gumbel runs one leaf per game and step (leaves_per_step is {leaves_per_step})")
+    if free_running:
+        raise ValueError("gumbel runs in the lock-step rounds only (not the free-running driver, not stagger)")
+    if distributed:
+        raise ValueError("gumbel is not offered with distributed=True")
+    return gumbel
 
 
 def check_eval_symmetry(mode, seed=0):

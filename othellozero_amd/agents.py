@@ -129,6 +129,50 @@ def rules_value_targets(records, values, n, value_target, exact_empties=0):
     return out
 
 
+def rules_gumbel_considered_visits(m, n):
+    """oz_gumbel_considered_visits on the host (no GPU needed): the sequential-halving schedule of a Gumbel root that considers m moves over n
+    simulations -> int32 (n,): the visit count the pick of simulation t must match (include/othellozero_amd.h, "Gumbel search")"""
+    out = np.zeros(max(int(n), 0), np.int32)
+    _lib.check(_lib.load().oz_gumbel_considered_visits(int(m), int(n), _lib.p_i32(out)))
+    return out
+
+
+def rules_gumbel_draws(seed, game_ids, plies, legal):
+    """oz_gumbel_draws on the host (no GPU needed): the Gumbel draws of roots from their keys (seed, game id, ply) and legal sets (uint64 masks)
+    -> float64 (count, 64) by square row*8+col, 0 off the legal set -- the function k_gumbel_arm evaluates"""
+    ids = np.ascontiguousarray(game_ids, dtype=np.uint64).ravel()
+    pl = np.ascontiguousarray(plies, dtype=np.int32).ravel()
+    lg = np.ascontiguousarray(legal, dtype=np.uint64).ravel()
+    if not (ids.size == pl.size == lg.size):
+        raise ValueError(f"rules_gumbel_draws: {ids.size} game ids, {pl.size} plies, {lg.size} legal masks")
+    g = np.zeros((ids.size, 64), np.float64)
+    _lib.check(_lib.load().oz_gumbel_draws(int(seed), _lib.p_u64(ids), _lib.p_i32(pl), _lib.p_u64(lg), ids.size, _lib.p_f64(g)))
+    return g
+
+
+def rules_gumbel_root(N, N0, Q, P, g, legal, vhat, gumbel, budget, with_scores=False):
+    """oz_gumbel_root on the host (no GPU needed): the Gumbel root rule over a batch of root rows.  N, N0 int32, Q, P, g float64 (count, 64) by
+    square row*8+col, legal uint64 (count,), vhat float64 (count,) = the roots' stored statistics, their snapshots at arming, their draws and own
+    values; gumbel = (max_considered, c_visit, c_scale), budget = the simulations of the search.  -> (pick int32 (count,) = the root edge the
+    next descent takes, move int32 (count,), pi float32 (count, 64) = the improved policy rows); with_scores=True adds (score float64 (count, 64),
+    gaps float64 (count, 2) = best minus second-best score among the candidates of the pick and of the move)."""
+    m, c_visit, c_scale = _lib.check_gumbel(gumbel)
+    N, N0 = (np.ascontiguousarray(x, dtype=np.int32).reshape(-1, 64) for x in (N, N0))
+    Q, P, g = (np.ascontiguousarray(x, dtype=np.float64).reshape(-1, 64) for x in (Q, P, g))
+    legal = np.ascontiguousarray(legal, dtype=np.uint64).ravel()
+    vhat = np.ascontiguousarray(vhat, dtype=np.float64).ravel()
+    count = N.shape[0]
+    if not (N0.shape[0] == Q.shape[0] == P.shape[0] == g.shape[0] == legal.size == vhat.size == count):
+        raise ValueError(f"rules_gumbel_root: {count} N rows, {N0.shape[0]} / {Q.shape[0]} / {P.shape[0]} / {g.shape[0]} N0 / Q / P / g rows, "
+                         f"{legal.size} legal masks, {vhat.size} values")
+    pick, move, pi = np.zeros(count, np.int32), np.zeros(count, np.int32), np.zeros((count, 64), np.float32)
+    score, gaps = np.zeros((count, 64), np.float64), np.zeros((count, 2), np.float64)
+    _lib.check(_lib.load().oz_gumbel_root(_lib.p_i32(N), _lib.p_i32(N0), _lib.p_f64(Q), _lib.p_f64(P), _lib.p_f64(g), _lib.p_u64(legal),
+                                          _lib.p_f64(vhat), count, m, c_visit, c_scale, int(budget), _lib.p_i32(pick), _lib.p_i32(move),
+                                          _lib.p_f32(pi), _lib.p_f64(score), _lib.p_f64(gaps)))
+    return (pick, move, pi, score, gaps) if with_scores else (pick, move, pi)
+
+
 def rules_eval_symmetries(own, opp, seed):
     """oz_eval_symmetries on the host (no GPU needed): the orientation t in 0..7 (int32) a network set to ("random", seed) evaluates each
     mover-canonical position (own[i], opp[i]) in -- the function the kernels evaluate"""

@@ -24,7 +24,9 @@ OZ_HD uint64_t oz_sm64(uint64_t z) {
 }
 OZ_HD uint64_t oz_rotl64(uint64_t x, int r) { return (x << r) | (x >> (64 - r)); }
 
-enum { OZ_RNG_COIN = 0, OZ_RNG_EXPLORE = 1, OZ_RNG_TIE = 2, OZ_RNG_NOISE = 3, OZ_RNG_SAMPLE = 4, OZ_RNG_OPENING = 5, OZ_RNG_PLAYOUT = 6 };
+enum { OZ_RNG_COIN = 0, OZ_RNG_EXPLORE = 1, OZ_RNG_TIE = 2, OZ_RNG_NOISE = 3, OZ_RNG_SAMPLE = 4, OZ_RNG_OPENING = 5, OZ_RNG_PLAYOUT = 6, OZ_RNG_GUMBEL = 7 };
+// GUMBEL: stream 7 + 256 * square, the Gumbel draw of a root's square (Gumbel search below).  7 + 256 sq is none of 0 .. 6 for sq >= 1 and is 7 for
+// sq == 0; it is none of 3 + 256 sq' + 65536 i either: that would need 4 == 256 (sq' - sq) + 65536 i, and the right side is a multiple of 256.
 // NOISE: stream 3 + 256 * square + 65536 * draw (root noise, oz_search.hip); SAMPLE: the one unit draw of a sampled move (move sampling,
 // oz_search.hip) -- 4 is none of 3 + 256 sq + 65536 i; OPENING: the move of an opening ply, keyed (opening seed, opening id, ply)
 // (oz_openings.h) -- nor is 5; PLAYOUT: the full / fast draw of a self-play move (playout cap, oz_playout_budget below) -- nor is 6
@@ -70,6 +72,201 @@ OZ_HD int oz_forced_prune(int N, double Q, double P, double eta, int Nstar, doub
     }
     if (Np < N && Np <= 1) Np = 0;                                  // a child cut down to one visit is dropped
     return Np;
+}
+
+// Gumbel search (include/othellozero_amd.h, "Gumbel search"): the root rule of Gumbel AlphaZero.  float64, no contraction, squares in ascending
+// sq = row*8 + col, the first maximum wins.  The kernels (oz_search.hip) and the host's oz_gumbel_* evaluate the functions below.
+// The Gumbel draw of a legal square from its unit draw u in [0, 1) (a multiple of 2^-53): g = -log(-log(w)), w = u except that the one endpoint
+// the stream can give, u == 0, maps to w = 2^-54 (half the smallest draw above it).  w lies in [2^-54, 1 - 2^-53], so -log(w) lies in
+// [1.1e-16, 37.5] and g in [-3.63, 36.8]: always finite.
+// g is ill-conditioned where -log(w) is near 1 (g near 0): one ulp of the inner logarithm is then many ulps of g, so the inner logarithm has to be
+// the correctly rounded one.  The host's libm log is (in all but 1 of 1 400 arguments); the device's is a 1-ulp function, so the device evaluates
+// both logarithms with oz_log_cr below: double-double arithmetic (error below 2^-85, correctly rounded in practice), IEEE operations only.
+struct OzDD { double hi, lo; };
+OZ_HD OzDD oz_dd_two_sum(double a, double b) {
+#pragma clang fp contract(off)
+    const double s = a + b, bb = s - a;
+    return OzDD{s, (a - (s - bb)) + (b - bb)};
+}
+OZ_HD OzDD oz_dd_norm(double a, double b) {                         // |a| >= |b|
+#pragma clang fp contract(off)
+    const double s = a + b;
+    return OzDD{s, b - (s - a)};
+}
+OZ_HD OzDD oz_dd_add(OzDD a, OzDD b) {
+#pragma clang fp contract(off)
+    OzDD s = oz_dd_two_sum(a.hi, b.hi);
+    const double l = (a.lo + b.lo) + s.lo;
+    return oz_dd_norm(s.hi, l);
+}
+OZ_HD OzDD oz_dd_mul(OzDD a, OzDD b) {
+#pragma clang fp contract(off)
+    const double p = a.hi * b.hi;
+    const double e = __builtin_fma(a.hi, b.hi, -p);                 // the exact error of the product
+    const double c = a.hi * b.lo + a.lo * b.hi;
+    return oz_dd_norm(p, e + c);
+}
+OZ_HD OzDD oz_dd_div(OzDD a, OzDD b) {
+#pragma clang fp contract(off)
+    const double q1 = a.hi / b.hi;
+    const OzDD p = oz_dd_mul(b, OzDD{q1, 0.0});
+    const OzDD r = oz_dd_add(a, OzDD{-p.hi, -p.lo});
+    const double q2 = r.hi / b.hi;
+    return oz_dd_norm(q1, q2);
+}
+// log(x) of a positive normal x: x = 2^e m, m in [0.75, 1.5); s = (m - 1) / (m + 1), |s| <= 0.2; log(m) = 2 s (1 + z/3 + z^2/5 + ..), z = s^2, the
+// terms up to z^4 / 9 in double-double, z^5 / 11 .. z^17 / 35 in double (below 2^-79 of the sum); the next term is below 2^-88
+OZ_HD double oz_log_cr(double x) {
+#pragma clang fp contract(off)
+    union { double d; uint64_t u; } b;
+    b.d = x;
+    int e = (int)((b.u >> 52) & 0x7FF) - 1023;
+    b.u = (b.u & 0x000FFFFFFFFFFFFFULL) | 0x3FF0000000000000ULL;
+    double m = b.d;
+    if (m >= 1.5) { m *= 0.5; e += 1; }
+    const OzDD s = oz_dd_div(OzDD{m - 1.0, 0.0}, oz_dd_two_sum(m, 1.0));
+    const OzDD z = oz_dd_mul(s, s);
+    double t = 1.0 / 35.0;
+    for (int c = 33; c >= 11; c -= 2) t = t * z.hi + 1.0 / (double)c;
+    OzDD h{t, 0.0};
+    for (int c = 9; c >= 1; c -= 2) h = oz_dd_add(oz_dd_mul(h, z), oz_dd_div(OzDD{1.0, 0.0}, OzDD{(double)c, 0.0}));
+    OzDD r = oz_dd_mul(s, h);
+    r.hi *= 2.0; r.lo *= 2.0;
+    const OzDD ln2{0x1.62e42fefa39efp-1, 0x1.abc9e3b39803fp-56};
+    const OzDD k = oz_dd_mul(ln2, OzDD{(double)e, 0.0});
+    r = oz_dd_add(k, r);
+    return r.hi + r.lo;
+}
+OZ_HD double oz_gumbel_value(double u) {
+#pragma clang fp contract(off)
+    const double w = u > 0.0 ? u : 5.5511151231257827e-17;
+#if defined(__HIP_DEVICE_COMPILE__)
+    return -oz_log_cr(-oz_log_cr(w));
+#else
+    return -log(-log(w));
+#endif
+}
+OZ_HD double oz_gumbel_draw(uint64_t seed, uint64_t game, uint64_t ply, int sq) {
+    return oz_gumbel_value(oz_rng_unit(oz_rng(seed, game, ply, (uint64_t)OZ_RNG_GUMBEL + 256ull * (uint64_t)sq)));
+}
+// considered_visits(m, n): the visit count a root's pick must match at each of the n simulations of a search that considers m moves
+// (sequential halving).  out[n].  m <= 1: 0, 1, .., n-1.
+inline void oz_gumbel_schedule(int m, int n, int* out) {
+    if (m <= 1) { for (int i = 0; i < n; ++i) out[i] = i; return; }
+    int L = 0;
+    while ((1 << L) < m) ++L;                                      // ceil(log2 m)
+    int visits[64];
+    for (int i = 0; i < 64; ++i) visits[i] = 0;
+    int k = m, len = 0;
+    while (len < n) {
+        int extra = n / (L * k);
+        if (extra < 1) extra = 1;
+        for (int e = 0; e < extra && len < n; ++e)
+            for (int i = 0; i < k; ++i) {
+                if (len < n) out[len++] = visits[i];
+                visits[i] += 1;
+            }
+        k = k / 2 > 2 ? k / 2 : 2;
+    }
+}
+// The root's sums, one legal square after the other in ascending order: sumN, maxN over the stored N; Pvis, PQ over the squares with N > 0.
+struct OzGumbelSums { long long sumN; int maxN; double Pvis, PQ; };
+OZ_HD void oz_gumbel_acc(OzGumbelSums& s, int N, double Q, double P) {
+#pragma clang fp contract(off)
+    s.sumN += N;
+    if (N > s.maxN) s.maxN = N;
+    if (N > 0) {
+        const double pq = P * Q;
+        s.Pvis = s.Pvis + P;
+        s.PQ = s.PQ + pq;
+    }
+}
+// the value every unvisited move is completed with
+OZ_HD double oz_gumbel_vmix(const OzGumbelSums& s, double vhat) {
+#pragma clang fp contract(off)
+    if (s.sumN == 0) return vhat;
+    const double r = (double)s.sumN / s.Pvis;
+    const double a = s.Pvis > 0.0 ? r * s.PQ : 0.0;              // (only zero-prior squares visited: no prior-weighted mean, the term is 0)
+    return (vhat + a) / (1.0 + (double)s.sumN);
+}
+// x = logit + sigma of a legal square (the improved policy is its softmax, the score adds g in front)
+OZ_HD double oz_gumbel_sigma(int N, double Q, double vmix, int maxN, double c_visit, double c_scale) {
+#pragma clang fp contract(off)
+    const double qhat = N > 0 ? Q : vmix;
+    const double h = (qhat + 1.0) * 0.5;
+    const double s = (c_visit + (double)maxN) * c_scale;
+    return s * h;
+}
+OZ_HD double oz_gumbel_x(double P, double sigma) {
+#pragma clang fp contract(off)
+    return log(P) + sigma;                                         // log(0) = -inf: such a square wins only where nothing else is legal
+}
+OZ_HD double oz_gumbel_score(double g, double P, double sigma) {
+#pragma clang fp contract(off)
+    const double a = g + log(P);
+    return a + sigma;
+}
+// One root on the host, from its rows by square: the pick of the next descent, the move, the improved policy row (float32 [64]) and the
+// scores (float64 [64], -inf off the legal set; may be null).  tables[max_considered][budget] = oz_gumbel_schedule(m, budget) for m = 1 .. max_considered.  *gap_pick / *gap_move (may be null) = the
+// distance between the best and the second-best score among the candidates of the decision (inf with one candidate).
+inline void oz_gumbel_root_row(const int32_t* N, const int32_t* N0, const double* Q, const double* P, const double* g, uint64_t legal, double vhat,
+                               int max_considered, double c_visit, double c_scale, int budget, const int* tables, int* pick, int* move, float* pi, double* score,
+                               double* gap_pick, double* gap_move) {
+#pragma clang fp contract(off)
+    OzGumbelSums s{0, 0, 0.0, 0.0};
+    long long t = 0;
+    int maxn = 0;
+    for (int sq = 0; sq < 64; ++sq)
+        if ((legal >> sq) & 1) {
+            oz_gumbel_acc(s, N[sq], Q[sq], P[sq]);
+            const int n = N[sq] - N0[sq];
+            t += n;
+            if (n > maxn) maxn = n;
+        }
+    const double vmix = oz_gumbel_vmix(s, vhat);
+    double x[64], sc[64], mx = -INFINITY;
+    for (int sq = 0; sq < 64; ++sq) {
+        x[sq] = sc[sq] = -INFINITY;
+        pi[sq] = 0.0f;
+        if ((legal >> sq) & 1) {
+            const double sg = oz_gumbel_sigma(N[sq], Q[sq], vmix, s.maxN, c_visit, c_scale);
+            x[sq] = oz_gumbel_x(P[sq], sg);
+            sc[sq] = oz_gumbel_score(g[sq], P[sq], sg);
+            if (x[sq] > mx) mx = x[sq];
+        }
+        if (score) score[sq] = sc[sq];
+    }
+    const int cnt = __builtin_popcountll(legal);
+    *pick = -1; *move = -1;
+    if (gap_pick) *gap_pick = INFINITY;
+    if (gap_move) *gap_move = INFINITY;
+    if (cnt == 0) return;
+    const int m_eff = max_considered < cnt ? max_considered : cnt;
+    const int cv = t >= 0 && t < budget ? tables[(size_t)(m_eff - 1) * budget + t] : maxn;
+    for (int which = 0; which < 2; ++which) {
+        const int want = which ? maxn : cv;
+        bool any = false;
+        for (int sq = 0; sq < 64; ++sq) any = any || (((legal >> sq) & 1) && N[sq] - N0[sq] == want);
+        int best = -1;
+        double bs = 0.0, second = -INFINITY;
+        for (int sq = 0; sq < 64; ++sq) {
+            if (!((legal >> sq) & 1) || (any && N[sq] - N0[sq] != want)) continue;
+            if (best < 0) { best = sq; bs = sc[sq]; }
+            else if (sc[sq] > bs) { second = bs; best = sq; bs = sc[sq]; }
+            else if (sc[sq] > second) second = sc[sq];
+        }
+        const double gap = second == -INFINITY ? INFINITY : bs - second;
+        if (which) { *move = best; if (gap_move) *gap_move = gap; }
+        else { *pick = best; if (gap_pick) *gap_pick = gap; }
+    }
+    // the improved policy: softmax of x over the legal squares, the sum in ascending order, one rounding to float32 per element
+    if (mx == -INFINITY) { for (int sq = 0; sq < 64; ++sq) if ((legal >> sq) & 1) pi[sq] = (float)(1.0 / (double)cnt); return; }
+    double e[64], sum = 0.0;
+    for (int sq = 0; sq < 64; ++sq) {
+        e[sq] = ((legal >> sq) & 1) ? exp(x[sq] - mx) : 0.0;
+        sum = sum + e[sq];
+    }
+    for (int sq = 0; sq < 64; ++sq) pi[sq] = (float)(e[sq] / sum);
 }
 
 OZ_HD uint64_t oz_stub_h(uint64_t own, uint64_t opp, uint64_t salt, uint64_t i) {

@@ -242,3 +242,5 @@ struct oz_replay {
 };
 // what an append needs to know about an engine (oz_search.hip): waits for the engine's stream; completed = records of completed games it holds
 int oz_selfplay_replay_facts(oz_selfplay* sp, int* n, int* device, int* record_visits, int64_t* completed);
+// ... and whether it runs the Gumbel search (keeps improved-policy rows beside its records)
+int oz_selfplay_has_gumbel(oz_selfplay* sp);

@@ -16,10 +16,12 @@
 // pi:     lane = cell row*n+col.  VISITS: the float64 row of k_expand_visits (oz_count_pow, lane 0's pairwise_sum, one division), rounded
 //         once to float32, then every symmetry's output cell takes its source cell's value by a cross-lane read; ONEHOT: 1.0f where the
 //         source cell is the action.  Stores of a row are contiguous over the lanes.
+//         POLICY (the improved policy of a Gumbel search): `counts` holds the records' float32 rows by square, bit for bit in the int32 words;
+//         every symmetry's output cell takes its source cell's value: a copy, no arithmetic.
 // own / opp / z of example t are written by lane t: one 8-lane store each per record.  z = the record's z, or with zt (the records' value
 // targets, indexed like recs) the record's float32 target.
 // No atomics, no scratch, fixed order.
-template <int N, bool VISITS>
+template <int N, bool VISITS, bool POLICY = false>
 __global__ __launch_bounds__(64) void k_replay_append(const oz_record* __restrict__ recs, const int32_t* __restrict__ counts,
                                                       const int32_t* __restrict__ perm, int alias_final, double inv, int k, long long base,
                                                       long long skip, long long capacity, uint64_t* __restrict__ own,
@@ -48,6 +50,7 @@ __global__ __launch_bounds__(64) void k_replay_append(const oz_record* __restric
         __syncthreads();
         q32 = (float)(arr[lane] / divisor);
     }
+    if constexpr (POLICY) q32 = is_cell ? __int_as_float(counts[(long long)rix * 64 + rn * 8 + cn]) : 0.f;
     const int action = (rec.action >> 3) * N + (rec.action & 7);
     uint64_t my_own = 0, my_opp = 0;
 #pragma unroll
@@ -58,7 +61,7 @@ __global__ __launch_bounds__(64) void k_replay_append(const oz_record* __restric
         if (lane == t) { my_own = bo; my_opp = bw; }
         const int src = is_cell ? oz_sym_src(t, N, rn, cn) : 0;
         float p;
-        if constexpr (VISITS) p = __shfl(q32, src);
+        if constexpr (VISITS || POLICY) p = __shfl(q32, src);
         else p = src == action ? 1.0f : 0.0f;
         const long long e = i * 8 + t;
         if (is_cell && e >= skip) pi[((base + e) % capacity) * N2 + lane] = p;
@@ -145,16 +148,21 @@ static int replay_reserve(oz_replay* r, int64_t records, int64_t count_rows, int
     return OZ_OK;
 }
 
-static int replay_check_target(const char* who, int alias_final, int target, double temperature) {
+static int replay_check_target(const char* who, int alias_final, int target, double temperature, bool engine = false) {
     OZ_REQUIRE(alias_final == 0 || alias_final == 1, "%s: alias_final = %d (0 or 1)", who, alias_final);
-    OZ_REQUIRE(target == OZ_REPLAY_TARGET_ONEHOT || target == OZ_REPLAY_TARGET_VISITS, "%s: target = %d (OZ_REPLAY_TARGET_ONEHOT or OZ_REPLAY_TARGET_VISITS)", who, target);
+    OZ_REQUIRE(target != OZ_REPLAY_TARGET_POLICY || engine, "%s: OZ_REPLAY_TARGET_POLICY is offered for an engine's records only (oz_replay_append_selfplay)", who);
+    OZ_REQUIRE(target == OZ_REPLAY_TARGET_ONEHOT || target == OZ_REPLAY_TARGET_VISITS || target == OZ_REPLAY_TARGET_POLICY,
+               "%s: target = %d (OZ_REPLAY_TARGET_ONEHOT, OZ_REPLAY_TARGET_VISITS or OZ_REPLAY_TARGET_POLICY)", who, target);
     OZ_REQUIRE(target != OZ_REPLAY_TARGET_VISITS || temperature > 0, "%s: temperature %g (the visit distribution needs T > 0)", who, temperature);
     return OZ_OK;
 }
 
 template <int N> static void replay_launch(oz_replay* r, int64_t count, int alias_final, int target, double inv, int k, long long skip, const float* zt) {
     const dim3 grid((unsigned)count), block(64);
-    if (target == OZ_REPLAY_TARGET_VISITS)
+    if (target == OZ_REPLAY_TARGET_POLICY)
+        hipLaunchKernelGGL((k_replay_append<N, false, true>), grid, block, 0, r->s, r->st_rec, r->st_cnt, r->st_perm, alias_final, inv, k, (long long)r->total, skip,
+                           (long long)r->capacity, r->own, r->opp, r->pi, r->z, zt);
+    else if (target == OZ_REPLAY_TARGET_VISITS)
         hipLaunchKernelGGL((k_replay_append<N, true>), grid, block, 0, r->s, r->st_rec, r->st_cnt, r->st_perm, alias_final, inv, k, (long long)r->total, skip,
                            (long long)r->capacity, r->own, r->opp, r->pi, r->z, zt);
     else
@@ -200,7 +208,7 @@ static int replay_append_staged(oz_replay* r, const oz_record* h, int64_t first,
 static int replay_append_selfplay(oz_replay* r, oz_selfplay* sp, int64_t first_record, int alias_final, int target, double temperature,
                                   int64_t* appended_records, bool targets) {
     OZ_REQUIRE(r && sp, "oz_replay_append_selfplay: null argument");
-    if (int rc = replay_check_target("oz_replay_append_selfplay", alias_final, target, temperature)) return rc;
+    if (int rc = replay_check_target("oz_replay_append_selfplay", alias_final, target, temperature, true)) return rc;
     OZ_REQUIRE(first_record >= 0, "oz_replay_append_selfplay: first_record %lld", (long long)first_record);
     R_LOCK(r);
     int n = 0, device = 0, record_visits = 0;
@@ -208,16 +216,21 @@ static int replay_append_selfplay(oz_replay* r, oz_selfplay* sp, int64_t first_r
     if (int rc = oz_selfplay_replay_facts(sp, &n, &device, &record_visits, &completed)) return rc;       // waits for the engine's stream
     OZ_REQUIRE(n == r->n, "oz_replay_append_selfplay: the engine plays %d x %d, the replay buffer holds %d x %d examples", n, n, r->n, r->n);
     OZ_REQUIRE(device == r->device, "oz_replay_append_selfplay: the engine lives on device %d, the replay buffer on device %d", device, r->device);
-    const bool visits = target == OZ_REPLAY_TARGET_VISITS;
+    const bool visits = target == OZ_REPLAY_TARGET_VISITS, policy = target == OZ_REPLAY_TARGET_POLICY;
     OZ_REQUIRE(!visits || record_visits, "oz_replay_append_selfplay: this engine does not record visit counts: create it with oz_selfplay_config.record_visits = 1");
+    OZ_REQUIRE(!policy || oz_selfplay_has_gumbel(sp), "oz_replay_append_selfplay: target OZ_REPLAY_TARGET_POLICY needs an engine with the Gumbel search (oz_selfplay_set_gumbel)");
     if (appended_records) *appended_records = 0;
     if (completed <= first_record) return OZ_OK;
     OZ_HIP(hipSetDevice(r->device));
-    if (int rc = replay_reserve(r, completed, visits ? completed : 0, targets ? completed : 0)) return rc;
+    if (int rc = replay_reserve(r, completed, visits || policy ? completed : 0, targets ? completed : 0)) return rc;
     int64_t got = 0, got_rows = 0;
     if (int rc = oz_selfplay_records_device(sp, r->st_rec, completed, &got)) return rc;
     if (visits) {
         if (int rc = oz_selfplay_visits_device(sp, r->st_cnt, got, &got_rows)) return rc;
+        if (got_rows < got) got = got_rows;
+    }
+    if (policy) {                                // the float32 rows into the staging of the int32 count rows: 256 B each, either way
+        if (int rc = oz_selfplay_policies_device(sp, r->st_cnt, got, &got_rows)) return rc;
         if (got_rows < got) got = got_rows;
     }
     if (targets) {

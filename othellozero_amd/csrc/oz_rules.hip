@@ -504,3 +504,29 @@ OZ_API int oz_examples_expand_visits(const oz_record* records, const int32_t* co
     OZ_HIP(hipMemcpy(z, zz.p, nex, hipMemcpyDeviceToHost));
     return OZ_OK;
 }
+
+// the 8 symmetric examples of every record with a float32 policy row by square (rows[count][64], the improved policy of a Gumbel search): on the
+// host, no device needed.  Example 8 i + t: boards and z as oz_examples_expand, pi[(8 i + t)][r][c] = the row's value at the source cell of (r, c)
+// under symmetry t -- values are copied, never recomputed, so the rows are the record's bit for bit.
+OZ_API int oz_examples_expand_policy(const oz_record* records, const float* rows, int64_t count, int n, int alias_final, uint8_t* boards, float* pi,
+                                     int8_t* z) {
+    if (int rc = check_n(n)) return rc;
+    if (count <= 0) return OZ_OK;
+    OZ_REQUIRE(records && rows && boards && pi && z, "null argument");
+    const int n2 = n * n;
+    for (int64_t i = 0; i < count; ++i) {
+        const oz_record& rec = records[i];
+        const uint64_t b = alias_final ? rec.final_black : rec.black, w = alias_final ? rec.final_white : rec.white;
+        for (int t = 0; t < 8; ++t) {
+            const int64_t ex = i * 8 + t;
+            for (int cell = 0; cell < n2; ++cell) {
+                const int src = oz_sym_src(t, n, cell / n, cell % n), sq = (src / n) * 8 + src % n;
+                pi[ex * n2 + cell] = rows[i * 64 + sq];
+                boards[(ex * n2 + cell) * 2] = (uint8_t)((b >> sq) & 1);
+                boards[(ex * n2 + cell) * 2 + 1] = (uint8_t)((w >> sq) & 1);
+            }
+            z[ex] = rec.z;
+        }
+    }
+    return OZ_OK;
+}

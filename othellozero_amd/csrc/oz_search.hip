@@ -90,6 +90,16 @@ struct MctsDev {
     double forced_k;           // forced playouts ("forced playouts" below): the forcing constant k (0: off); needs noise, so the *_n kernels alone read it
 };
 
+// Gumbel search ("Gumbel search" below): what the *_g kernels get beside MctsDev.  An object without the option never fills or passes it.
+struct GumbelDev {
+    double* g;                 // [G][64] the Gumbel draw by square, 0 off the legal set of the root it was drawn for
+    int* n0;                   // [G][64] the root's stored N when the slot was armed (0: the root was not in the table)
+    uint8_t* armed;            // [G] the slot's CURRENT root is a Gumbel root
+    const int* table;          // [max_considered][budget] considered_visits(m, budget), m = 1 .. max_considered
+    int max_considered, budget;
+    double c_visit, c_scale;
+};
+
 __device__ __forceinline__ unsigned char* rec_ptr(const MctsDev& t, int g, int node) {
     return t.recs + ((size_t)g * t.node_cap + (size_t)node) * (size_t)t.rec_bytes;
 }
@@ -354,9 +364,11 @@ struct Descent {
     int fs;                    // free table slot of the probe that left the known tree (-1: none)
     int err;                   // EF_* bit of an error exit (status is then OZ_LEAF_IDLE), 0: none
 };
-template <bool NOISE>
+// GUMBEL (the *_g kernels): gr = the slot's Gumbel view (gumbel_of_slot); on an armed root, depth 0 picks by the Gumbel rule instead of PUCT.
+struct GumbelRoot { bool armed; double g; int n0; const GumbelDev* gd; };
+template <bool NOISE, bool GUMBEL = false>
 __device__ __forceinline__ Descent descend_one(const MctsDev& t, uint4* rec, int2* path, int g, int lane, uint64_t own, uint64_t opp, uint64_t legal,
-                                               int& rootn, bool noisy, double eta, const InFlight fl) {
+                                               int& rootn, bool noisy, double eta, const InFlight fl, const GumbelRoot gr = GumbelRoot{false, 0.0, 0, nullptr}) {
     int depth = 0, status, tval = 0, err = 0, fs = -1;
     int node = rootn;                                           // record index of the state we stand on, -1 = unknown
     int pnode = -1, prank = 0;                                  // the edge we arrived through (to cache the child index)
@@ -420,8 +432,33 @@ __device__ __forceinline__ Descent descend_one(const MctsDev& t, uint4* rec, int
                 }
             }
         }
+        bool cand = is_legal;
+        if constexpr (GUMBEL) {
+            if (gr.armed && depth == 0) {                                   // (uniform: one branch per wave)
+                const GumbelDev& gd = *gr.gd;
+                int N = 0;
+                double Q = 0.0, P = 0.0;
+                if (is_legal) {
+                    N = (int)((uint32_t)w[4 + 3 * rank] & ~OZ_TAG_F32);
+                    Q = __longlong_as_double((long long)w[5 + 3 * rank]);
+                    P = __longlong_as_double((long long)w[6 + 3 * rank]);
+                }
+                const int nv = is_legal ? N - gr.n0 : 0;                    // this search's visits of the lane's move
+                const int tv = wave_sum_i32(nv), maxn = wave_max_i32(nv);
+                OzGumbelSums sm{0, 0, 0.0, 0.0};                            // the float sums are sequential in square order: every lane walks the staged edges
+                for (int r = 0; r < cnt; ++r)
+                    oz_gumbel_acc(sm, (int)((uint32_t)w[4 + 3 * r] & ~OZ_TAG_F32), __longlong_as_double((long long)w[5 + 3 * r]),
+                                  __longlong_as_double((long long)w[6 + 3 * r]));
+                const double vmix = oz_gumbel_vmix(sm, __longlong_as_double((long long)w[3]));
+                const int m_eff = gd.max_considered < cnt ? gd.max_considered : cnt;
+                const int cv = tv >= 0 && tv < gd.budget ? gd.table[(size_t)(m_eff - 1) * gd.budget + tv] : maxn;
+                const bool match = is_legal && nv == cv;
+                cand = __ballot(match) ? match : is_legal;
+                U = cand ? oz_gumbel_score(gr.g, P, oz_gumbel_sigma(N, Q, vmix, sm.maxN, gd.c_visit, gd.c_scale)) : -INFINITY;
+            }
+        }
         const double m = wave_max_f64(U);
-        const int best = oz_ctz(__ballot(is_legal && U == m));             // first maximum
+        const int best = oz_ctz(__ballot(cand && U == m));                 // first maximum
         const int brank = oz_popc(legal & ((1ULL << best) - 1ULL));
         if (lane == 0) path[depth] = make_int2(node, brank);
         ++depth;
@@ -437,8 +474,18 @@ __device__ __forceinline__ Descent descend_one(const MctsDev& t, uint4* rec, int
 }
 // (body shared by k_select and the free-running k_advance; returns the status it stored in leaf_status[g].  A descent that ends in an error
 // is stored like any other, with status OZ_LEAF_IDLE.)
-template <bool NOISE = false>
-__device__ __forceinline__ int select_body(const MctsDev& t, TreeLds& L, int g, int lane) {
+// the slot's Gumbel view: armed, and then this lane's draw and snapshot (one coalesced 512-byte and one 256-byte load per descent)
+__device__ __forceinline__ GumbelRoot gumbel_of_slot(const GumbelDev& gd, int g, int lane) {
+    GumbelRoot gr{false, 0.0, 0, &gd};
+    if (unii((int)gd.armed[g]) != 0) {
+        gr.armed = true;
+        gr.g = gd.g[(size_t)g * 64 + lane];
+        gr.n0 = gd.n0[(size_t)g * 64 + lane];
+    }
+    return gr;
+}
+template <bool NOISE = false, bool GUMBEL = false>
+__device__ __forceinline__ int select_body(const MctsDev& t, TreeLds& L, int g, int lane, const GumbelDev* gd = nullptr) {
     if (!t.active[g]) {
         if (lane == 0) t.leaf_status[g] = OZ_LEAF_IDLE;
         return OZ_LEAF_IDLE;
@@ -447,7 +494,9 @@ __device__ __forceinline__ int select_body(const MctsDev& t, TreeLds& L, int g, 
     const bool noisy = noise_of_slot<NOISE>(t, g, lane, &eta);
     const uint64_t own = uni64(t.root_own[g]), opp = uni64(t.root_opp[g]);
     int rootn = unii(t.root_node[g]);
-    const Descent e = descend_one<NOISE>(t, L.rec, L.path, g, lane, own, opp, oz_legal(own, opp, t.valid), rootn, noisy, eta, InFlight{nullptr, nullptr, 0});
+    GumbelRoot gr{false, 0.0, 0, nullptr};
+    if constexpr (GUMBEL) gr = gumbel_of_slot(*gd, g, lane);
+    const Descent e = descend_one<NOISE, GUMBEL>(t, L.rec, L.path, g, lane, own, opp, oz_legal(own, opp, t.valid), rootn, noisy, eta, InFlight{nullptr, nullptr, 0}, gr);
     __syncthreads();
     if (lane < e.depth) t.path[(size_t)g * OZ_MAX_DEPTH + lane] = L.path[lane];          // the frontier, one coalesced store
     if (lane == 0) {
@@ -469,6 +518,11 @@ __global__ __launch_bounds__(64) void k_select(MctsDev t) {
 __global__ __launch_bounds__(64) void k_select_n(MctsDev t) {
     __shared__ TreeLds L;
     select_body<true>(t, L, blockIdx.x, threadIdx.x);
+}
+// (the *_g kernels: the same kernels over the GUMBEL = true bodies, launched by objects with the Gumbel search switched on)
+__global__ __launch_bounds__(64) void k_select_g(MctsDev t, GumbelDev gd) {
+    __shared__ TreeLds L;
+    select_body<false, true>(t, L, blockIdx.x, threadIdx.x, &gd);
 }
 
 // ---------------------------------------------------------------- K13: leaf compaction
@@ -732,7 +786,9 @@ __device__ __forceinline__ void backup_one(const MctsDev& t, int g, int lane, in
         t.last_vtype[g] = vt;
     }
 }
-// expand the leaf if it needs it, then back its value up along its path
+// expand the leaf if it needs it, then back its value up along its path.  GUMBEL: the new node's header keeps the value the expansion backs
+// up, before negation (the network's v, or the exact one where solve_leaves replaced it) -- vhat of the completed-Q formula, in header word 3
+template <bool GUMBEL = false>
 __device__ __forceinline__ void expand_backup_one(const MctsDev& t, TreeLds& L, int g, int lane, const LeafRef& lf) {
     const int status = lf.status;
     if (status == OZ_LEAF_IDLE || status == OZ_LEAF_WAIT) return;           // (WAIT: the leaf was not in the batch, nothing to expand yet)
@@ -758,7 +814,10 @@ __device__ __forceinline__ void expand_backup_one(const MctsDev& t, TreeLds& L, 
             // build the record in LDS (header + one edge per legal square, N = 0, Q = 0, child unknown), store it with one
             // wave-wide 16-byte store, link it into the table and into the edge we came through
             uint64_t* w = reinterpret_cast<uint64_t*>(L.rec);
-            if (lane == 0) { w[0] = own; w[1] = opp; w[2] = (uint64_t)(uint32_t)cnt << 32; w[3] = 0; }
+            if (lane == 0) {
+                w[0] = own; w[1] = opp; w[2] = (uint64_t)(uint32_t)cnt << 32; w[3] = 0;
+                if constexpr (GUMBEL) w[3] = (uint64_t)__double_as_longlong((double)t.v[slot]);
+            }
             if (is_legal) {
                 const int rank = oz_popc(legal & ((1ULL << lane) - 1ULL));
                 w[4 + 3 * rank] = 0xFFFFFFFF00000000ULL;                       // N|tag = 0, child = -1
@@ -797,6 +856,7 @@ __device__ __forceinline__ void expand_backup_one(const MctsDev& t, TreeLds& L, 
 __device__ __forceinline__ void backup_body(const MctsDev& t, int g, int lane, double value, int vt) {
     backup_one(t, g, lane, t.depth[g], t.path + (size_t)g * OZ_MAX_DEPTH, value, vt);
 }
+template <bool GUMBEL = false>
 __device__ __forceinline__ void expand_backup_body(const MctsDev& t, TreeLds& L, int g, int lane, int slot_is_game) {
     LeafRef lf;
     lf.status = unii(t.leaf_status[g]);
@@ -805,7 +865,7 @@ __device__ __forceinline__ void expand_backup_body(const MctsDev& t, TreeLds& L,
     lf.fs = unii(t.leaf_fs[g]);
     lf.depth = unii(t.depth[g]); lf.tval = unii(t.term_value[g]);
     lf.path = t.path + (size_t)g * OZ_MAX_DEPTH;
-    expand_backup_one(t, L, g, lane, lf);
+    expand_backup_one<GUMBEL>(t, L, g, lane, lf);
 }
 __global__ __launch_bounds__(64) void k_expand_backup(MctsDev t, int slot_is_game) {
     __shared__ TreeLds L;
@@ -826,6 +886,17 @@ __global__ __launch_bounds__(64) void k_backup_select_n(MctsDev t) {
     wave_sync();
     __syncthreads();
     select_body<true>(t, L, blockIdx.x, threadIdx.x);
+}
+__global__ __launch_bounds__(64) void k_expand_backup_g(MctsDev t, int slot_is_game) {
+    __shared__ TreeLds L;
+    expand_backup_body<true>(t, L, blockIdx.x, threadIdx.x, slot_is_game);
+}
+__global__ __launch_bounds__(64) void k_backup_select_g(MctsDev t, GumbelDev gd) {
+    __shared__ TreeLds L;
+    expand_backup_body<true>(t, L, blockIdx.x, threadIdx.x, 0);
+    wave_sync();
+    __syncthreads();
+    select_body<false, true>(t, L, blockIdx.x, threadIdx.x, &gd);
 }
 
 
@@ -1087,6 +1158,12 @@ struct oz_mcts {
     // root noise: true from the first arming on (d.noise_eta / d.noise_armed are then allocated): the descents run on the *_n kernels
     bool noise_ever = false;
     uint64_t* noise_ids = nullptr; int32_t* noise_plies = nullptr;      // staging of the keys of oz_mcts_sample_root_noise / oz_mcts_sample_moves, [G] each
+    // Gumbel search: true from the first oz_mcts_set_gumbel / oz_mcts_sample_gumbel on (gd's arrays are then allocated): the object runs on the *_g kernels
+    bool gumbel_ever = false;
+    GumbelDev gd{};
+    int* gumbel_table = nullptr; size_t gumbel_table_len = 0;           // the device copy of the schedule gd.table points to
+    uint8_t* gumbel_want = nullptr;                                     // [G] staging of the host's `armed`
+    float* gumbel_pi = nullptr; double* gumbel_score = nullptr;         // [G][64] each: what k_gumbel_policy wrote last
     // solved leaves (oz_mcts_set_solve_leaves): 0 = off, nothing allocated and nothing launched
     int solve_leaves = 0;
     unsigned solve_stamp = 0;
@@ -1284,6 +1361,7 @@ static int wide_check_k(int k) {
     return OZ_OK;
 }
 static int wide_set_k(oz_mcts* m, int k) {
+    if (k > 1 && m->gumbel_ever) { oz_set_error("leaves_per_step %d: the Gumbel search runs one leaf per game and step", k); return OZ_ERR_STATE; }
     if (k > 1) if (int rc = wide_alloc(m)) return rc;
     m->leaves_per_step = k;
     return OZ_OK;
@@ -1351,13 +1429,16 @@ static int mcts_steps_async(oz_mcts* m, oz_net* net, int nsims, int max_games, b
     const bool all = m->profile;
     for (int k = 0; k < nsims; ++k) {
         timed(m, TS_SELECT, all, [&] {
-            if (k == 0) hipLaunchKernelGGL(m->noise_ever ? k_select_n : k_select, dim3(d.G), dim3(64), 0, s, d);
+            if (m->gumbel_ever) {
+                if (k == 0) hipLaunchKernelGGL(k_select_g, dim3(d.G), dim3(64), 0, s, d, m->gd);
+                else hipLaunchKernelGGL(k_backup_select_g, dim3(d.G), dim3(64), 0, s, d, m->gd);
+            } else if (k == 0) hipLaunchKernelGGL(m->noise_ever ? k_select_n : k_select, dim3(d.G), dim3(64), 0, s, d);
             else hipLaunchKernelGGL(m->noise_ever ? k_backup_select_n : k_backup_select, dim3(d.G), dim3(64), 0, s, d);
         });
         timed(m, TS_COMPACT, all, [&] { hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, s, d); });
         if (int rc = eval_batch_async(m, net, max_games, time_eval || all)) return rc;
     }
-    timed(m, TS_BACKUP, all, [&] { hipLaunchKernelGGL(k_expand_backup, dim3(d.G), dim3(64), 0, s, d, 0); });
+    timed(m, TS_BACKUP, all, [&] { hipLaunchKernelGGL(m->gumbel_ever ? k_expand_backup_g : k_expand_backup, dim3(d.G), dim3(64), 0, s, d, 0); });
     OZ_HIP(hipGetLastError());
     return OZ_OK;
 }
@@ -1403,6 +1484,18 @@ OZ_API int oz_mcts_set_roots(oz_mcts* m, const uint64_t* own, const uint64_t* op
             if (o[i] != own[i] || p[i] != opp[i]) armed[i] = 0;
         OZ_HIP(hipMemcpyAsync(m->d.noise_armed, armed.data(), G, hipMemcpyHostToDevice, m->stream));
         OZ_HIP(hipStreamSynchronize(m->stream));           // (`armed` is a local: the copy must be done before it goes)
+    }
+    if (m->gumbel_ever) {                                  // so do the Gumbel draw and the snapshot of the root's counts
+        std::vector<uint64_t> o(G), p(G);
+        std::vector<uint8_t> armed(G);
+        OZ_HIP(hipMemcpyAsync(o.data(), m->d.root_own, 8ull * G, hipMemcpyDeviceToHost, m->stream));
+        OZ_HIP(hipMemcpyAsync(p.data(), m->d.root_opp, 8ull * G, hipMemcpyDeviceToHost, m->stream));
+        OZ_HIP(hipMemcpyAsync(armed.data(), m->gd.armed, G, hipMemcpyDeviceToHost, m->stream));
+        OZ_HIP(hipStreamSynchronize(m->stream));
+        for (int i = 0; i < G; ++i)
+            if (o[i] != own[i] || p[i] != opp[i]) armed[i] = 0;
+        OZ_HIP(hipMemcpyAsync(m->gd.armed, armed.data(), G, hipMemcpyHostToDevice, m->stream));
+        OZ_HIP(hipStreamSynchronize(m->stream));
     }
     OZ_HIP(hipMemcpyAsync(m->d.root_own, own, 8ull * G, hipMemcpyHostToDevice, m->stream));
     OZ_HIP(hipMemcpyAsync(m->d.root_opp, opp, 8ull * G, hipMemcpyHostToDevice, m->stream));
@@ -1518,6 +1611,7 @@ OZ_API int oz_mcts_use_wide_kernels(oz_mcts* m, int enable) {
     std::lock_guard<std::mutex> lk(m->mu);
     if (m->selected) { oz_set_error("oz_mcts_use_wide_kernels: a step is pending (oz_mcts_select without oz_mcts_backup)"); return OZ_ERR_STATE; }
     hipSetDevice(m->device);
+    if (enable && m->gumbel_ever) { oz_set_error("oz_mcts_use_wide_kernels: the Gumbel search runs on the one-descent kernels"); return OZ_ERR_STATE; }
     if (enable) if (int rc = wide_alloc(m)) return rc;
     m->use_wide = enable != 0;
     return OZ_OK;
@@ -1576,6 +1670,8 @@ static int noise_disarm(oz_mcts* m) {
     }
     return OZ_OK;
 }
+#define OZ_REFUSE_GUMBEL(m, fn, what) \
+    do { if ((m)->gumbel_ever) { oz_set_error(fn ": the Gumbel search replaces " what " (the object has it switched on)"); return OZ_ERR_STATE; } } while (0)
 #define OZ_REFUSE_PENDING(m, fn) \
     do { if ((m)->selected) { oz_set_error(fn ": a step is pending (oz_mcts_select without oz_mcts_backup)"); return OZ_ERR_STATE; } } while (0)
 
@@ -1584,6 +1680,7 @@ OZ_API int oz_mcts_set_root_noise(oz_mcts* m, double eps, const double* eta, con
     if (int rc = noise_check("oz_mcts_set_root_noise", 1.0, eps, false)) return rc;
     std::lock_guard<std::mutex> lk(m->mu);
     OZ_REFUSE_PENDING(m, "oz_mcts_set_root_noise");
+    if (eta && eps != 0.0) OZ_REFUSE_GUMBEL(m, "oz_mcts_set_root_noise", "root noise");
     hipSetDevice(m->device);
     if (!eta || eps == 0.0) return noise_disarm(m);
     const int G = m->d.G;
@@ -1617,6 +1714,7 @@ OZ_API int oz_mcts_sample_root_noise(oz_mcts* m, double alpha, double eps, uint6
     if (int rc = noise_check("oz_mcts_sample_root_noise", alpha, eps, true)) return rc;
     std::lock_guard<std::mutex> lk(m->mu);
     OZ_REFUSE_PENDING(m, "oz_mcts_sample_root_noise");
+    if (eps != 0.0) OZ_REFUSE_GUMBEL(m, "oz_mcts_sample_root_noise", "root noise");
     hipSetDevice(m->device);
     if (eps == 0.0) return noise_disarm(m);
     const int G = m->d.G;
@@ -1655,7 +1753,8 @@ OZ_API int oz_mcts_select(oz_mcts* m) {
     OZ_REFUSE_WIDE(m, "oz_mcts_select");
     OZ_REFUSE_SOLVED(m, "oz_mcts_select");
     hipSetDevice(m->device);
-    hipLaunchKernelGGL(m->noise_ever ? k_select_n : k_select, dim3(m->d.G), dim3(64), 0, m->stream, m->d);
+    if (m->gumbel_ever) hipLaunchKernelGGL(k_select_g, dim3(m->d.G), dim3(64), 0, m->stream, m->d, m->gd);
+    else hipLaunchKernelGGL(m->noise_ever ? k_select_n : k_select, dim3(m->d.G), dim3(64), 0, m->stream, m->d);
     OZ_HIP(hipGetLastError());
     m->selected = true;
     return check_error_flag(m);
@@ -1685,7 +1784,7 @@ OZ_API int oz_mcts_backup(oz_mcts* m, const float* pi, const float* v) {
     const int G = m->d.G;
     OZ_HIP(hipMemcpyAsync(m->d.pi, pi, 4ull * G * m->d.n2, hipMemcpyHostToDevice, m->stream));
     OZ_HIP(hipMemcpyAsync(m->d.v, v, 4ull * G, hipMemcpyHostToDevice, m->stream));
-    hipLaunchKernelGGL(k_expand_backup, dim3(G), dim3(64), 0, m->stream, m->d, 1);
+    hipLaunchKernelGGL(m->gumbel_ever ? k_expand_backup_g : k_expand_backup, dim3(G), dim3(64), 0, m->stream, m->d, 1);
     OZ_HIP(hipGetLastError());
     m->selected = false;
     return check_error_flag(m);
@@ -1786,6 +1885,313 @@ OZ_API int oz_root_values(const int32_t* N, const double* Q, int64_t count, doub
     for (int64_t i = 0; i < count; ++i) {
         int rc;
         out[i] = oz_root_value(N + i * 64, Q + i * 64, &rc);
+    }
+    return OZ_OK;
+}
+
+// ---------------------------------------------------------------- Gumbel search: the root rule of Gumbel AlphaZero (opt-in)
+// (the semantics are stated in include/othellozero_amd.h, "Gumbel search"; the restatement the tests hold this against is tests/gumbel_ref.py.)
+//   * a view at depth 0, like root noise: the stored statistics are what PUCT stores, the Gumbel rule only decides which root edge a descent takes
+//     (descend_one<.., GUMBEL>), on the root the slot was armed for; deeper levels and unarmed roots are PUCT;
+//   * the one thing stored differently: the *_g expansion keeps the node's own value in header word 3 (expand_backup_one<GUMBEL>), which the
+//     completed-Q formula needs at the root -- so the option is switched on over an empty tree only;
+//   * a compile-time variant: an object that never switched it on launches the kernels it launched before this section existed.
+// arm the CURRENT roots: one wave per slot, one lane per square.  draw != 0: g from the streams (seed, ids[g], plies[g]); else g is the host's, already
+// in place.  want: null = every active slot, else the slots with want[g] != 0.  N0 = the root record's counts now (0: the root is not in the table).
+__global__ __launch_bounds__(64) void k_gumbel_arm(MctsDev t, GumbelDev gd, int draw, uint64_t seed, const uint64_t* __restrict__ ids,
+                                                   const int* __restrict__ plies, const uint8_t* __restrict__ want) {
+    const int g = blockIdx.x, lane = threadIdx.x;
+    const uint64_t own = uni64(t.root_own[g]), opp = uni64(t.root_opp[g]);
+    const uint64_t legal = oz_legal(own, opp, t.valid);
+    const bool on = unii((int)t.active[g]) != 0 && legal != 0 && (want == nullptr || unii((int)want[g]) != 0);
+    if (!on) {
+        if (lane == 0) gd.armed[g] = 0;
+        return;
+    }
+    const bool is_legal = (legal >> lane) & 1;
+    if (draw) gd.g[(size_t)g * 64 + lane] = is_legal ? oz_gumbel_draw(seed, uni64(ids[g]), (uint64_t)unii(plies[g]), lane) : 0.0;
+    const int node = root_lookup(t, g, own, opp, lane);
+    int n0 = 0;
+    if (node >= 0 && node < t.node_cap && is_legal) n0 = (int)(rec_edge(t, g, node, oz_popc(legal & ((1ULL << lane) - 1ULL)))->n_tag & ~OZ_TAG_F32);
+    gd.n0[(size_t)g * 64 + lane] = n0;
+    if (lane == 0) gd.armed[g] = 1;
+}
+// the improved policy, the move and this lane's score at the root record `node` of an armed slot: one wave, one lane per square.  arr = 64 doubles
+// of LDS.  Shared by k_gumbel_policy and the engine's move (sp_move_body<.., GUMBEL>).
+struct GumbelPick { float p; double score; int move; };
+__device__ __forceinline__ GumbelPick gumbel_policy_lane(const MctsDev& t, const GumbelDev& gd, double* arr, int g, int node, int lane, uint64_t legal) {
+    const bool is_legal = (legal >> lane) & 1;
+    const int cnt = oz_popc(legal);
+    int N = 0;
+    double Q = 0.0, P = 0.0;
+    if (is_legal) {
+        const OzEdge* e = rec_edge(t, g, node, oz_popc(legal & ((1ULL << lane) - 1ULL)));
+        N = (int)(e->n_tag & ~OZ_TAG_F32); Q = e->q; P = e->p;
+    }
+    const int nv = is_legal ? N - gd.n0[(size_t)g * 64 + lane] : 0;
+    const int maxn = wave_max_i32(is_legal ? nv : -2147483647 - 1);
+    OzGumbelSums sm{0, 0, 0.0, 0.0};
+    for (int r = 0; r < cnt && r < t.row_cap; ++r) {                    // sequential, in square order (every lane reads the same edge: one broadcast load)
+        const OzEdge* e = rec_edge(t, g, node, r);
+        oz_gumbel_acc(sm, (int)(e->n_tag & ~OZ_TAG_F32), e->q, e->p);
+    }
+    const double vhat = *reinterpret_cast<const double*>(rec_ptr(t, g, node) + 24);
+    const double vmix = oz_gumbel_vmix(sm, vhat);
+    double x = -INFINITY, sc = -INFINITY;
+    if (is_legal) {
+        const double sg = oz_gumbel_sigma(N, Q, vmix, sm.maxN, gd.c_visit, gd.c_scale);
+        x = oz_gumbel_x(P, sg);
+        sc = oz_gumbel_score(gd.g[(size_t)g * 64 + lane], P, sg);
+    }
+    const bool cand = is_legal && nv == maxn;
+    const double ms = wave_max_f64(cand ? sc : -INFINITY);
+    const int best = oz_ctz(__ballot(cand && sc == ms));
+    const double mx = wave_max_f64(x);
+    float p;
+    if (mx == -INFINITY) p = is_legal ? (float)(1.0 / (double)cnt) : 0.0f;
+    else {
+        const double e = is_legal ? exp(x - mx) : 0.0;
+        __syncthreads();                                                // (arr may still be read by the caller's previous use)
+        arr[lane] = e;
+        __syncthreads();
+        double sum = 0.0;
+        for (int sq = 0; sq < 64; ++sq) sum = sum + arr[sq];
+        p = (float)(e / sum);
+    }
+    return GumbelPick{p, sc, best};
+}
+// the improved policy row, the move and the scores of every armed slot's root: one wave per slot, one lane per square.
+// rc: 0 = ok, 1 = the root is not in the table, 3 = the slot is idle or not armed (rows of zeros, scores -inf, action -1)
+__global__ __launch_bounds__(64) void k_gumbel_policy(MctsDev t, GumbelDev gd, float* __restrict__ pi_out, int* __restrict__ action_out,
+                                                      int* __restrict__ rc_out, double* __restrict__ score_out) {
+    __shared__ double arr[64];
+    const int g = blockIdx.x, lane = threadIdx.x;
+    const uint64_t own = uni64(t.root_own[g]), opp = uni64(t.root_opp[g]);
+    const uint64_t legal = oz_legal(own, opp, t.valid);
+    const bool armed = unii((int)t.active[g]) != 0 && unii((int)gd.armed[g]) != 0 && legal != 0;
+    int node = -1;
+    if (armed) node = root_lookup(t, g, own, opp, lane);
+    if (node < 0 || node >= t.node_cap) {
+        pi_out[(size_t)g * 64 + lane] = 0.0f;
+        score_out[(size_t)g * 64 + lane] = -INFINITY;
+        if (lane == 0) { action_out[g] = -1; rc_out[g] = armed ? 1 : 3; }
+        return;
+    }
+    const GumbelPick pk = gumbel_policy_lane(t, gd, arr, g, node, lane, legal);
+    pi_out[(size_t)g * 64 + lane] = pk.p;
+    score_out[(size_t)g * 64 + lane] = pk.score;
+    if (lane == 0) { action_out[g] = pk.move; rc_out[g] = 0; }
+}
+
+static int gumbel_check(const char* fn, int max_considered, double c_visit, double c_scale, int budget) {
+    OZ_REQUIRE(max_considered >= 1 && max_considered <= 64, "%s: max_considered %d outside [1, 64]", fn, max_considered);
+    OZ_REQUIRE(c_visit >= 0.0 && c_visit <= 1e9, "%s: c_visit %g outside [0, 1e9]", fn, c_visit);                  // (NaN fails both compares)
+    OZ_REQUIRE(c_scale > 0.0 && c_scale <= 1e9, "%s: c_scale %g outside (0, 1e9]", fn, c_scale);
+    OZ_REQUIRE(budget >= 1 && budget <= OZ_GUMBEL_MAX_BUDGET, "%s: budget %d outside [1, %d]", fn, budget, OZ_GUMBEL_MAX_BUDGET);
+    return OZ_OK;
+}
+// the schedule of every m = 1 .. max_considered at the budget, [max_considered][budget]
+static std::vector<int> gumbel_tables(int max_considered, int budget) {
+    std::vector<int> tab((size_t)max_considered * budget);
+    for (int mm = 1; mm <= max_considered; ++mm) oz_gumbel_schedule(mm, budget, tab.data() + (size_t)(mm - 1) * budget);
+    return tab;
+}
+// switch the option on (the first call: the arrays, 772 B per game + the table) and set its parameters
+static int gumbel_enable(oz_mcts* m, const char* fn, int max_considered, double c_visit, double c_scale, int budget) {
+    MctsDev& d = m->d;
+    const int G = d.G;
+    if (!m->gumbel_ever) {
+        if (m->noise_ever) { oz_set_error("%s: the Gumbel search replaces root noise and forced playouts (the object has armed root noise)", fn); return OZ_ERR_STATE; }
+        if (m->wide()) { oz_set_error("%s: the Gumbel search runs one leaf per game and step (leaves_per_step is %d)", fn, m->leaves_per_step); return OZ_ERR_STATE; }
+        std::vector<int> nn(G);
+        OZ_HIP(hipMemcpyAsync(nn.data(), d.node_count, 4ull * G, hipMemcpyDeviceToHost, m->stream));
+        OZ_HIP(hipStreamSynchronize(m->stream));
+        for (int i = 0; i < G; ++i)
+            if (nn[i] != 0) {
+                oz_set_error("%s: the tree of game %d holds %d nodes expanded without the option (switch it on at creation or after oz_mcts_reset(-1))", fn, i, nn[i]);
+                return OZ_ERR_STATE;
+            }
+        const size_t held = m->allocs.size();
+        GumbelDev gd{};
+        int rc = m->alloc(&gd.g, (size_t)G * 64);
+        if (!rc) rc = m->alloc(&gd.n0, (size_t)G * 64);
+        if (!rc) rc = m->alloc(&gd.armed, (size_t)G);
+        if (!rc) rc = m->alloc(&m->gumbel_want, (size_t)G);
+        if (!rc) rc = m->alloc(&m->gumbel_pi, (size_t)G * 64);
+        if (!rc) rc = m->alloc(&m->gumbel_score, (size_t)G * 64);
+        if (!rc && (hipMemsetAsync(gd.g, 0, sizeof(double) * 64 * (size_t)G, m->stream) != hipSuccess ||
+                    hipMemsetAsync(gd.n0, 0, sizeof(int) * 64 * (size_t)G, m->stream) != hipSuccess ||
+                    hipMemsetAsync(gd.armed, 0, (size_t)G, m->stream) != hipSuccess ||
+                    hipMemsetAsync(m->gumbel_score, 0, sizeof(double) * 64 * (size_t)G, m->stream) != hipSuccess || hipStreamSynchronize(m->stream) != hipSuccess)) {
+            oz_set_error("Gumbel search: clearing the buffers failed");
+            rc = OZ_ERR_HIP;
+        }
+        if (rc) {
+            for (size_t i = held; i < m->allocs.size(); ++i) hipFree(m->allocs[i]);
+            m->allocs.resize(held);
+            m->gumbel_want = nullptr; m->gumbel_pi = nullptr; m->gumbel_score = nullptr;
+            return rc;
+        }
+        m->gd = gd;
+        m->gumbel_ever = true;
+    }
+    GumbelDev& gd = m->gd;
+    if (!gd.table || gd.max_considered != max_considered || gd.budget != budget) {
+        const std::vector<int> tab = gumbel_tables(max_considered, budget);
+        if (tab.size() > m->gumbel_table_len) {
+            if (int rc = m->alloc(&m->gumbel_table, tab.size())) return rc;       // (the smaller one stays in allocs until destroy)
+            m->gumbel_table_len = tab.size();
+        }
+        OZ_HIP(hipStreamSynchronize(m->stream));                                  // no launch still reads the table
+        OZ_HIP(hipMemcpy(m->gumbel_table, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice));
+        gd.table = m->gumbel_table;
+    }
+    gd.max_considered = max_considered; gd.budget = budget; gd.c_visit = c_visit; gd.c_scale = c_scale;
+    return OZ_OK;
+}
+OZ_API int oz_mcts_set_gumbel(oz_mcts* m, int max_considered, double c_visit, double c_scale, int budget, const double* g, const uint8_t* armed) {
+    OZ_REQUIRE(m, "null mcts");
+    if (int rc = gumbel_check("oz_mcts_set_gumbel", max_considered, c_visit, c_scale, budget)) return rc;
+    std::lock_guard<std::mutex> lk(m->mu);
+    OZ_REFUSE_PENDING(m, "oz_mcts_set_gumbel");
+    hipSetDevice(m->device);
+    const int G = m->d.G;
+    if (g) for (size_t i = 0; i < (size_t)G * 64; ++i) OZ_REQUIRE(g[i] == g[i] && g[i] > -INFINITY && g[i] < INFINITY, "oz_mcts_set_gumbel: g[%zu][%zu] is not finite", i / 64, i % 64);
+    if (int rc = gumbel_enable(m, "oz_mcts_set_gumbel", max_considered, c_visit, c_scale, budget)) return rc;
+    if (!g) {                                              // the parameters only: every slot disarmed
+        OZ_HIP(hipMemsetAsync(m->gd.armed, 0, (size_t)G, m->stream));
+        OZ_HIP(hipStreamSynchronize(m->stream));
+        return OZ_OK;
+    }
+    OZ_HIP(hipMemcpyAsync(m->gd.g, g, sizeof(double) * 64 * (size_t)G, hipMemcpyHostToDevice, m->stream));
+    std::vector<uint8_t> a;
+    if (armed) {
+        a.assign(armed, armed + G);
+        OZ_HIP(hipMemcpyAsync(m->gumbel_want, a.data(), G, hipMemcpyHostToDevice, m->stream));
+    }
+    hipLaunchKernelGGL(k_gumbel_arm, dim3(G), dim3(64), 0, m->stream, m->d, m->gd, 0, 0ull, (const uint64_t*)nullptr, (const int*)nullptr,
+                       armed ? (const uint8_t*)m->gumbel_want : (const uint8_t*)nullptr);
+    OZ_HIP(hipGetLastError());
+    OZ_HIP(hipStreamSynchronize(m->stream));
+    return OZ_OK;
+}
+OZ_API int oz_mcts_sample_gumbel(oz_mcts* m, int max_considered, double c_visit, double c_scale, int budget, uint64_t seed, const uint64_t* game_ids,
+                                 const int32_t* plies) {
+    OZ_REQUIRE(m && game_ids && plies, "null argument");
+    if (int rc = gumbel_check("oz_mcts_sample_gumbel", max_considered, c_visit, c_scale, budget)) return rc;
+    std::lock_guard<std::mutex> lk(m->mu);
+    OZ_REFUSE_PENDING(m, "oz_mcts_sample_gumbel");
+    hipSetDevice(m->device);
+    const int G = m->d.G;
+    for (int i = 0; i < G; ++i) OZ_REQUIRE(plies[i] >= 0, "oz_mcts_sample_gumbel: plies[%d] = %d", i, plies[i]);
+    if (int rc = gumbel_enable(m, "oz_mcts_sample_gumbel", max_considered, c_visit, c_scale, budget)) return rc;
+    if (int rc = stage_keys(m, game_ids, plies)) return rc;
+    hipLaunchKernelGGL(k_gumbel_arm, dim3(G), dim3(64), 0, m->stream, m->d, m->gd, 1, seed, (const uint64_t*)m->noise_ids, (const int*)m->noise_plies,
+                       (const uint8_t*)nullptr);
+    OZ_HIP(hipGetLastError());
+    OZ_HIP(hipStreamSynchronize(m->stream));
+    return OZ_OK;
+}
+OZ_API int oz_mcts_get_gumbel(oz_mcts* m, double* g, uint8_t* armed, int32_t* N0, int32_t* max_considered, double* c_visit, double* c_scale, int32_t* budget) {
+    OZ_REQUIRE(m, "null mcts");
+    std::lock_guard<std::mutex> lk(m->mu);
+    hipSetDevice(m->device);
+    const int G = m->d.G;
+    if (max_considered) *max_considered = m->gd.max_considered;         // (0 on an object without the option)
+    if (c_visit) *c_visit = m->gd.c_visit;
+    if (c_scale) *c_scale = m->gd.c_scale;
+    if (budget) *budget = m->gd.budget;
+    if (!m->gumbel_ever) {
+        if (g) memset(g, 0, sizeof(double) * 64 * (size_t)G);
+        if (armed) memset(armed, 0, (size_t)G);
+        if (N0) memset(N0, 0, sizeof(int32_t) * 64 * (size_t)G);
+        return OZ_OK;
+    }
+    if (g) OZ_HIP(hipMemcpyAsync(g, m->gd.g, sizeof(double) * 64 * (size_t)G, hipMemcpyDeviceToHost, m->stream));
+    if (armed) OZ_HIP(hipMemcpyAsync(armed, m->gd.armed, (size_t)G, hipMemcpyDeviceToHost, m->stream));
+    if (N0) OZ_HIP(hipMemcpyAsync(N0, m->gd.n0, sizeof(int32_t) * 64 * (size_t)G, hipMemcpyDeviceToHost, m->stream));
+    OZ_HIP(hipStreamSynchronize(m->stream));
+    return OZ_OK;
+}
+OZ_API int oz_mcts_gumbel_policy(oz_mcts* m, float* pi, int32_t* action, int32_t* rc) {
+    OZ_REQUIRE(m && pi && action && rc, "null argument");
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (!m->gumbel_ever) { oz_set_error("oz_mcts_gumbel_policy: the object has no Gumbel search (oz_mcts_set_gumbel / oz_mcts_sample_gumbel first)"); return OZ_ERR_STATE; }
+    hipSetDevice(m->device);
+    const int G = m->d.G;
+    int32_t* da = m->rc_counts; int32_t* dr = m->rc_rc;           // (the staging of oz_mcts_root_counts: [G][64] and [G])
+    hipLaunchKernelGGL(k_gumbel_policy, dim3(G), dim3(64), 0, m->stream, m->d, m->gd, m->gumbel_pi, da, dr, m->gumbel_score);
+    OZ_HIP(hipGetLastError());
+    OZ_HIP(hipMemcpyAsync(pi, m->gumbel_pi, 4ull * G * 64, hipMemcpyDeviceToHost, m->stream));
+    OZ_HIP(hipMemcpyAsync(action, da, 4ull * G, hipMemcpyDeviceToHost, m->stream));
+    OZ_HIP(hipMemcpyAsync(rc, dr, 4ull * G, hipMemcpyDeviceToHost, m->stream));
+    OZ_HIP(hipStreamSynchronize(m->stream));
+    return OZ_OK;
+}
+// the scores g + logit + sigma the last oz_mcts_gumbel_policy evaluated, [num_games][64] by square, -inf off the legal set (for inspection)
+OZ_API int oz_mcts_gumbel_scores(oz_mcts* m, double* score) {
+    OZ_REQUIRE(m && score, "null argument");
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (!m->gumbel_ever) { oz_set_error("oz_mcts_gumbel_scores: the object has no Gumbel search"); return OZ_ERR_STATE; }
+    hipSetDevice(m->device);
+    OZ_HIP(hipMemcpyAsync(score, m->gumbel_score, 8ull * m->d.G * 64, hipMemcpyDeviceToHost, m->stream));
+    OZ_HIP(hipStreamSynchronize(m->stream));
+    return OZ_OK;
+}
+// header word 3 of node `index` of game `game`: the node's own value where it was expanded under the Gumbel search, 0.0 elsewhere
+OZ_API int oz_mcts_node_value(oz_mcts* m, int game, int index, double* value) {
+    OZ_REQUIRE(m && value, "null argument");
+    std::lock_guard<std::mutex> lk(m->mu);
+    hipSetDevice(m->device);
+    MctsDev& d = m->d;
+    OZ_REQUIRE(game >= 0 && game < d.G, "game index out of range");
+    OZ_HIP(hipStreamSynchronize(m->stream));
+    int nn = 0;
+    OZ_HIP(hipMemcpy(&nn, d.node_count + game, 4, hipMemcpyDeviceToHost));
+    OZ_REQUIRE(index >= 0 && index < nn, "node index %d out of range (%d nodes)", index, nn);
+    OZ_HIP(hipMemcpy(value, d.recs + ((size_t)game * d.node_cap + index) * (size_t)d.rec_bytes + 24, sizeof(double), hipMemcpyDeviceToHost));
+    return OZ_OK;
+}
+// ---- the host-only twins (no device needed)
+OZ_API int oz_gumbel_considered_visits(int m, int n, int32_t* out) {
+    OZ_REQUIRE(m >= 1 && m <= 64, "oz_gumbel_considered_visits: m %d outside [1, 64]", m);
+    OZ_REQUIRE(n >= 1 && n <= OZ_GUMBEL_MAX_BUDGET, "oz_gumbel_considered_visits: n %d outside [1, %d]", n, OZ_GUMBEL_MAX_BUDGET);
+    OZ_REQUIRE(out, "oz_gumbel_considered_visits: null argument");
+    oz_gumbel_schedule(m, n, out);
+    return OZ_OK;
+}
+OZ_API int oz_gumbel_draws(uint64_t seed, const uint64_t* game_ids, const int32_t* plies, const uint64_t* legal, int64_t count, double* g) {
+    OZ_REQUIRE(count >= 0, "oz_gumbel_draws: count %lld", (long long)count);
+    if (count == 0) return OZ_OK;
+    OZ_REQUIRE(game_ids && plies && legal && g, "oz_gumbel_draws: null argument");
+    for (int64_t i = 0; i < count; ++i) OZ_REQUIRE(plies[i] >= 0, "oz_gumbel_draws: plies[%lld] = %d", (long long)i, plies[i]);
+    for (int64_t i = 0; i < count; ++i)
+        for (int sq = 0; sq < 64; ++sq) g[i * 64 + sq] = ((legal[i] >> sq) & 1) ? oz_gumbel_draw(seed, game_ids[i], (uint64_t)plies[i], sq) : 0.0;
+    return OZ_OK;
+}
+OZ_API int oz_gumbel_from_units(const double* u, int64_t count, double* g) {
+    OZ_REQUIRE(count >= 0, "oz_gumbel_from_units: count %lld", (long long)count);
+    if (count == 0) return OZ_OK;
+    OZ_REQUIRE(u && g, "oz_gumbel_from_units: null argument");
+    for (int64_t i = 0; i < count; ++i) OZ_REQUIRE(u[i] >= 0.0 && u[i] < 1.0, "oz_gumbel_from_units: u[%lld] = %g outside [0, 1)", (long long)i, u[i]);
+    for (int64_t i = 0; i < count; ++i) g[i] = oz_gumbel_value(u[i]);
+    return OZ_OK;
+}
+OZ_API int oz_gumbel_root(const int32_t* N, const int32_t* N0, const double* Q, const double* P, const double* g, const uint64_t* legal, const double* vhat,
+                          int64_t count, int max_considered, double c_visit, double c_scale, int budget, int32_t* pick, int32_t* move, float* pi,
+                          double* score, double* gaps) {
+    if (int rc = gumbel_check("oz_gumbel_root", max_considered, c_visit, c_scale, budget)) return rc;
+    OZ_REQUIRE(count >= 0, "oz_gumbel_root: count %lld", (long long)count);
+    if (count == 0) return OZ_OK;
+    OZ_REQUIRE(N && N0 && Q && P && g && legal && vhat && pick && move && pi, "oz_gumbel_root: null argument");
+    for (int64_t i = 0; i < count * 64; ++i)
+        OZ_REQUIRE(N[i] >= 0 && N0[i] >= 0 && N0[i] <= N[i], "oz_gumbel_root: N[%lld][%d] = %d, N0 = %d", (long long)(i / 64), (int)(i % 64), N[i], N0[i]);
+    const std::vector<int> tab = gumbel_tables(max_considered, budget);
+    for (int64_t i = 0; i < count; ++i) {
+        int pk, mv;
+        oz_gumbel_root_row(N + i * 64, N0 + i * 64, Q + i * 64, P + i * 64, g + i * 64, legal[i], vhat[i], max_considered, c_visit, c_scale, budget, tab.data(),
+                           &pk, &mv, pi + i * 64, score ? score + i * 64 : nullptr, gaps ? gaps + 2 * i : nullptr, gaps ? gaps + 2 * i + 1 : nullptr);
+        pick[i] = pk; move[i] = mv;
     }
     return OZ_OK;
 }
@@ -1902,6 +2308,7 @@ OZ_API int oz_mcts_sample_moves(oz_mcts* m, double temperature, uint64_t seed, c
     OZ_REQUIRE(m && game_ids && plies && action && rc, "null argument");
     if (int r = sample_check("oz_mcts_sample_moves", temperature)) return r;
     std::lock_guard<std::mutex> lk(m->mu);
+    OZ_REFUSE_GUMBEL(m, "oz_mcts_sample_moves", "move sampling");
     hipSetDevice(m->device);
     const int G = m->d.G;
     for (int i = 0; i < G; ++i) OZ_REQUIRE(plies[i] >= 0, "oz_mcts_sample_moves: plies[%d] = %d", i, plies[i]);
@@ -2083,9 +2490,19 @@ __global__ void k_sp_roots_stagger(GamesDev gm, MctsDev t, int round, int period
 // the root's Q over the raw counts goes into the move log next to the counts and from there beside the game's records.  Such an engine launches
 // instantiations of its own (k_sp_move_f in a lock-step round; the EXTRAS advance or, with no other option, k_advance_v), so the kernels of an
 // engine without it stay the code they were, register for register.  Never in the arena.
-template <bool NOISE = false, bool SAMPLE = false, bool CAP = false, bool FORCE = false, bool VALUES = false>
+// GUMBEL (an engine with the Gumbel search, oz_selfplay_set_gumbel; lock-step rounds only): the round's roots kernel is followed by k_gumbel_arm,
+// so the root of every active slot with a legal move is armed.  Where the coin falls on its greedy branch the move is the Gumbel root's
+// (gumbel_policy_lane), greedy = 3 in its record; the explore branch is unchanged.  The float32 improved-policy row of the search goes into the
+// move log and from there beside the game's records, as the visit-count rows do.  Never in the arena.
+struct GumbelPlay {
+    GumbelDev gd;
+    float* log_pi;                         // [G][64 plies][64 squares]
+    float* policies;                       // [record_cap][64]
+    unsigned long long* moves;             // [1] moves picked by the Gumbel rule
+};
+template <bool NOISE = false, bool SAMPLE = false, bool CAP = false, bool FORCE = false, bool VALUES = false, bool GUMBEL = false>
 __device__ __forceinline__ void sp_move_body(const GamesDev& gm, const MctsDev& t, int g, int lane, int arena, MoveSampling ms = MoveSampling{},
-                                             PlayoutCap pc = PlayoutCap{}, ForcedPlayouts fp = ForcedPlayouts{}) {
+                                             PlayoutCap pc = PlayoutCap{}, ForcedPlayouts fp = ForcedPlayouts{}, GumbelPlay gp = GumbelPlay{}) {
     if (!t.active[g]) return;
     bool prune = false;
     (void)prune;
@@ -2132,6 +2549,16 @@ __device__ __forceinline__ void sp_move_body(const GamesDev& gm, const MctsDev& 
             }
         }
     }
+    float gpi = 0.0f;                                            // this lane's entry of the improved policy row
+    int gmove = -1;
+    (void)gpi; (void)gmove;
+    if constexpr (GUMBEL) {
+        if (unii((int)gp.gd.armed[g]) != 0) {
+            __shared__ double garr[64];
+            const GumbelPick pk = gumbel_policy_lane(t, gp.gd, garr, g, node, lane, legal);
+            gpi = pk.p; gmove = pk.move;
+        }
+    }
     int action, greedy = 1;
     if (arena || gm.temperature == 0.0) {
         // bests = argwhere(p == p.max()) over the whole board; random.choice(bests) -> RNG_TIE stream
@@ -2141,6 +2568,9 @@ __device__ __forceinline__ void sp_move_body(const GamesDev& gm, const MctsDev& 
     } else {
         // N**(1/T) / sum is monotone in N: argwhere(policy == policy.max())[0] = first max-visit square
         action = oz_ctz(__ballot(is_legal && cnt == mx));
+    }
+    if constexpr (GUMBEL) {
+        if (gmove >= 0) { action = gmove; greedy = 3; }
     }
     if (!arena) {
         const double coin = oz_rng_unit(oz_rng(gm.seed, gid, (uint64_t)ply, OZ_RNG_COIN));
@@ -2206,6 +2636,11 @@ __device__ __forceinline__ void sp_move_body(const GamesDev& gm, const MctsDev& 
             for (int i = 0; i < nply && i < room; ++i)
                 gm.visits[(size_t)(base + i) * 64 + lane] = i == ply ? row : gm.log_counts[(lb + i) * 64 + lane];
         }
+        if constexpr (GUMBEL) {                               // the improved-policy rows next to the records, as the visit-count rows above
+            const long long room = gm.record_cap - (long long)base;
+            for (int i = 0; i < nply && i < room; ++i)
+                gp.policies[(size_t)(base + i) * 64 + lane] = i == ply ? gpi : gp.log_pi[(lb + i) * 64 + lane];
+        }
         // the game's root values next to its records, lane i the value of ply i; this ply's is still in registers
         if constexpr (VALUES) {
             if (gm.log_values && lane < nply && (long long)(base + lane) < gm.record_cap)
@@ -2214,7 +2649,9 @@ __device__ __forceinline__ void sp_move_body(const GamesDev& gm, const MctsDev& 
     } else {
         if (gm.record_visits && ply < 64) gm.log_counts[(lb + ply) * 64 + lane] = row;
         if constexpr (VALUES) { if (gm.log_values && lane == 0 && ply < 64) gm.log_values[lb + ply] = rootv; }
+        if constexpr (GUMBEL) { if (ply < 64) gp.log_pi[(lb + ply) * 64 + lane] = gpi; }
     }
+    if constexpr (GUMBEL) { if (lane == 0 && greedy == 3) atomicAdd(gp.moves, 1ULL); }
     if (lane == 0) atomicAdd(&gm.counters[2], 1ULL);
     if (fin && gm.refill) {
         // a fresh OthelloGame + a fresh OthelloMCTS in the same slot (training.py:30-32)
@@ -2241,6 +2678,10 @@ __global__ __launch_bounds__(64) void k_sp_move_c(GamesDev gm, MctsDev t, MoveSa
 // playout cap: ms.plies and pc.fast_sims say; a staggered round passes a cap that is off; fp.k == 0: no forcing)
 __global__ __launch_bounds__(64) void k_sp_move_f(GamesDev gm, MctsDev t, MoveSampling ms, PlayoutCap pc, ForcedPlayouts fp) {
     sp_move_body<false, true, true, true, true>(gm, t, blockIdx.x, threadIdx.x, 0, ms, pc, fp);
+}
+// the self-play move of a lock-step round of an engine with the Gumbel search (with or without recorded root values: gm.log_values says)
+__global__ __launch_bounds__(64) void k_sp_move_g(GamesDev gm, MctsDev t, GumbelPlay gp) {
+    sp_move_body<false, false, false, false, true, true>(gm, t, blockIdx.x, threadIdx.x, 0, MoveSampling{}, PlayoutCap{}, ForcedPlayouts{}, gp);
 }
 
 // ---------------------------------------------------------------- free-running self-play step
@@ -2443,6 +2884,9 @@ struct oz_selfplay {
     MoveSampling sample{0.0, 0};     // oz_selfplay_set_move_sampling: plies > 0 = on
     PlayoutCap cap{0, 0.0, nullptr, nullptr};      // oz_selfplay_set_playout_cap: fast_sims > 0 = on (the buffers stay once allocated)
     ForcedPlayouts forced{0.0, nullptr};           // oz_selfplay_set_forced_playouts: k > 0 = on (the counters stay once allocated); m->d.forced_k holds the same k
+    bool gumbel_on = false;          // oz_selfplay_set_gumbel: every searched move of a lock-step round is a Gumbel root search
+    float *gumbel_log = nullptr, *gumbel_rows = nullptr;       // its improved-policy rows: the move log and the rows beside the records
+    unsigned long long* gumbel_moves = nullptr;
     std::vector<void*> allocs;
     std::mutex mu;
     long long records_read = 0;
@@ -2560,6 +3004,7 @@ static int selfplay_round_async(oz_selfplay* sp, int sims, int stagger_round) {
     timed(m, TS_MOVE, m->profile, [&] {
         if (stagger_round >= 0) hipLaunchKernelGGL(k_sp_roots_stagger, gg, dim3(256), 0, s, sp->gm, m->d, stagger_round, sp->stagger_period);
         else hipLaunchKernelGGL(k_sp_roots, gg, dim3(256), 0, s, sp->gm, m->d, 0);
+        if (sp->gumbel_on) hipLaunchKernelGGL(k_gumbel_arm, dim3(G), dim3(64), 0, s, m->d, m->gd, 1, sp->gm.seed, (const uint64_t*)sp->gm.game_id, (const int*)sp->gm.ply, (const uint8_t*)nullptr);
         if (sp->noise_on && capped) hipLaunchKernelGGL(k_root_noise_c, dim3(G), dim3(64), 0, s, m->d, sp->noise_alpha, ck);
         else if (sp->noise_on) hipLaunchKernelGGL(k_root_noise, dim3(G), dim3(64), 0, s, m->d, sp->noise_alpha, sp->gm.seed, (const uint64_t*)sp->gm.game_id, (const int*)sp->gm.ply);
     });
@@ -2575,7 +3020,8 @@ static int selfplay_round_async(oz_selfplay* sp, int sims, int stagger_round) {
         }
     } else if (int rc = mcts_steps_async(m, sp->net, sims, G, true, capped ? &ck : nullptr)) return rc;
     timed(m, TS_MOVE, m->profile, [&] {
-        if (sp->forced.k > 0.0 || sp->gm.log_values) hipLaunchKernelGGL(k_sp_move_f, dim3(G), dim3(64), 0, s, sp->gm, m->d, sp->sample, capped ? sp->cap : PlayoutCap{0, 0.0, nullptr, nullptr}, sp->forced);
+        if (sp->gumbel_on) hipLaunchKernelGGL(k_sp_move_g, dim3(G), dim3(64), 0, s, sp->gm, m->d, GumbelPlay{m->gd, sp->gumbel_log, sp->gumbel_rows, sp->gumbel_moves});
+        else if (sp->forced.k > 0.0 || sp->gm.log_values) hipLaunchKernelGGL(k_sp_move_f, dim3(G), dim3(64), 0, s, sp->gm, m->d, sp->sample, capped ? sp->cap : PlayoutCap{0, 0.0, nullptr, nullptr}, sp->forced);
         else if (capped) hipLaunchKernelGGL(k_sp_move_c, dim3(G), dim3(64), 0, s, sp->gm, m->d, sp->sample, sp->cap);
         else if (sp->sample.plies > 0) hipLaunchKernelGGL(k_sp_move_s, dim3(G), dim3(64), 0, s, sp->gm, m->d, sp->sample);
         else hipLaunchKernelGGL(k_sp_move, dim3(G), dim3(64), 0, s, sp->gm, m->d, 0);
@@ -2612,6 +3058,7 @@ OZ_API int oz_selfplay_stagger(oz_selfplay* sp, int sims_pre) {
     std::lock_guard<std::mutex> lkn(sp->net->mu);
     hipSetDevice(sp->m->device);
     OZ_REQUIRE(sp->mode == 0, "oz_selfplay_stagger must be the first driver call on an engine");
+    if (sp->gumbel_on) { oz_set_error("oz_selfplay_stagger: not with the Gumbel search (its budget is num_simulations; use oz_selfplay_run)"); return OZ_ERR_STATE; }
     OZ_REQUIRE(sp->cfg.refill, "oz_selfplay_stagger is for continuous self-play (cfg.refill = 1)");
     sp->mode = 1;
     selfplay_attach_cache(sp);
@@ -2647,6 +3094,7 @@ OZ_API int oz_selfplay_set_leaves_per_step(oz_selfplay* sp, int k) {
     if (int rc = wide_check_k(k)) return rc;
     std::lock_guard<std::mutex> lk(sp->mu);
     if (sp->mode != 0) { oz_set_error("oz_selfplay_set_leaves_per_step: the engine has been driven already (set it before the first driver call)"); return OZ_ERR_STATE; }
+    if (sp->gumbel_on && k > 1) { oz_set_error("oz_selfplay_set_leaves_per_step: the Gumbel search runs one leaf per game and step"); return OZ_ERR_STATE; }
     OZ_REQUIRE(sp->net->max_batch >= sp->gm.G * k, "network max_batch %d < num_games %d x leaves_per_step %d", sp->net->max_batch, sp->gm.G, k);
     hipSetDevice(sp->m->device);
     return wide_set_k(sp->m, k);
@@ -2685,6 +3133,7 @@ OZ_API int oz_selfplay_set_root_noise(oz_selfplay* sp, double alpha, double eps)
     if (int rc = noise_check("oz_selfplay_set_root_noise", alpha, eps, true)) return rc;
     std::lock_guard<std::mutex> lk(sp->mu);
     if (sp->mode != 0) { oz_set_error("oz_selfplay_set_root_noise: the engine has been driven already (set it before the first driver call)"); return OZ_ERR_STATE; }
+    if (sp->gumbel_on) { oz_set_error("oz_selfplay_set_root_noise: the Gumbel search replaces root noise (the engine has it switched on)"); return OZ_ERR_STATE; }
     std::lock_guard<std::mutex> lkm(sp->m->mu);
     hipSetDevice(sp->m->device);
     if (eps == 0.0) { sp->noise_on = false; sp->forced.k = 0.0; sp->m->d.forced_k = 0.0; return noise_disarm(sp->m); }       // (forced playouts go with the noise)
@@ -2701,6 +3150,7 @@ OZ_API int oz_selfplay_set_move_sampling(oz_selfplay* sp, double temperature, in
     OZ_REQUIRE(plies >= 0 && plies <= 64, "oz_selfplay_set_move_sampling: plies %d outside [0, 64]", plies);
     std::lock_guard<std::mutex> lk(sp->mu);
     if (sp->mode != 0) { oz_set_error("oz_selfplay_set_move_sampling: the engine has been driven already (set it before the first driver call)"); return OZ_ERR_STATE; }
+    if (sp->gumbel_on) { oz_set_error("oz_selfplay_set_move_sampling: the Gumbel search replaces move sampling (the engine has it switched on)"); return OZ_ERR_STATE; }
     sp->sample = MoveSampling{plies > 0 ? temperature : 0.0, plies};
     return OZ_OK;
 }
@@ -2715,6 +3165,7 @@ OZ_API int oz_selfplay_set_playout_cap(oz_selfplay* sp, int fast_sims, double fu
     }
     std::lock_guard<std::mutex> lk(sp->mu);
     if (sp->mode != 0) { oz_set_error("oz_selfplay_set_playout_cap: the engine has been driven already (set it before the first driver call)"); return OZ_ERR_STATE; }
+    if (sp->gumbel_on && fast_sims != 0) { oz_set_error("oz_selfplay_set_playout_cap: not with the Gumbel search (a cap needs two budgets and two schedules)"); return OZ_ERR_STATE; }
     if (fast_sims == 0) { sp->cap.fast_sims = 0; sp->cap.full_prob = 0.0; return OZ_OK; }
     if (!sp->cap.log_fast) {
         hipSetDevice(sp->m->device);
@@ -2758,6 +3209,7 @@ OZ_API int oz_selfplay_set_forced_playouts(oz_selfplay* sp, double k) {
     if (int rc = forced_check("oz_selfplay_set_forced_playouts", k)) return rc;
     std::lock_guard<std::mutex> lk(sp->mu);
     if (sp->mode != 0) { oz_set_error("oz_selfplay_set_forced_playouts: the engine has been driven already (set it before the first driver call)"); return OZ_ERR_STATE; }
+    if (sp->gumbel_on) { oz_set_error("oz_selfplay_set_forced_playouts: the Gumbel search replaces forced playouts (the engine has it switched on)"); return OZ_ERR_STATE; }
     if (k > 0.0 && !sp->noise_on) { oz_set_error("oz_selfplay_set_forced_playouts: forced playouts need root noise (oz_selfplay_set_root_noise first)"); return OZ_ERR_STATE; }
     std::lock_guard<std::mutex> lkm(sp->m->mu);
     if (k > 0.0 && !sp->forced.stat) {
@@ -2813,6 +3265,60 @@ OZ_API int oz_playout_budgets(uint64_t seed, const uint64_t* game_ids, const int
     }
     return OZ_OK;
 }
+// the Gumbel search for every searched move of the lock-step rounds of oz_selfplay_run; before the first driver call.  The budget is the
+// engine's num_simulations, the seed the engine's.  16 KB per slot + 256 B per record for the improved-policy rows at the first call.
+OZ_API int oz_selfplay_set_gumbel(oz_selfplay* sp, int max_considered, double c_visit, double c_scale) {
+    OZ_REQUIRE(sp, "null selfplay");
+    if (int rc = gumbel_check("oz_selfplay_set_gumbel", max_considered, c_visit, c_scale, sp->cfg.sims)) return rc;
+    std::lock_guard<std::mutex> lk(sp->mu);
+    if (sp->mode != 0) { oz_set_error("oz_selfplay_set_gumbel: the engine has been driven already (set it before the first driver call)"); return OZ_ERR_STATE; }
+    if (sp->noise_on || sp->forced.k > 0.0) { oz_set_error("oz_selfplay_set_gumbel: the Gumbel search replaces root noise and forced playouts (the engine has them switched on)"); return OZ_ERR_STATE; }
+    if (sp->sample.plies > 0) { oz_set_error("oz_selfplay_set_gumbel: the Gumbel search replaces move sampling (the engine has it switched on)"); return OZ_ERR_STATE; }
+    if (sp->cap.fast_sims > 0) { oz_set_error("oz_selfplay_set_gumbel: not with a playout cap (it needs two budgets and two schedules)"); return OZ_ERR_STATE; }
+    std::lock_guard<std::mutex> lkm(sp->m->mu);
+    hipSetDevice(sp->m->device);
+    if (!sp->gumbel_log) {
+        const size_t held = sp->allocs.size(), G = (size_t)sp->gm.G;
+        float *lg = nullptr, *rows = nullptr; unsigned long long* moves = nullptr;
+        int rc = sp->alloc(&lg, G * 64 * 64);
+        if (!rc) rc = sp->alloc(&rows, (size_t)sp->gm.record_cap * 64);
+        if (!rc) rc = sp->alloc(&moves, 1);
+        if (!rc && (hipMemset(lg, 0, sizeof(float) * G * 64 * 64) != hipSuccess || hipMemset(moves, 0, sizeof(unsigned long long)) != hipSuccess)) {
+            oz_set_error("oz_selfplay_set_gumbel: clearing the buffers failed");
+            rc = OZ_ERR_HIP;
+        }
+        if (rc) {
+            for (size_t i = held; i < sp->allocs.size(); ++i) hipFree(sp->allocs[i]);
+            sp->allocs.resize(held);
+            return rc;
+        }
+        sp->gumbel_log = lg; sp->gumbel_rows = rows; sp->gumbel_moves = moves;
+    }
+    if (int rc = gumbel_enable(sp->m, "oz_selfplay_set_gumbel", max_considered, c_visit, c_scale, sp->cfg.sims)) return rc;
+    sp->gumbel_on = true;
+    return OZ_OK;
+}
+OZ_API int oz_selfplay_get_gumbel(oz_selfplay* sp, int32_t* max_considered, double* c_visit, double* c_scale, int64_t* moves) {
+    OZ_REQUIRE(sp, "null selfplay");
+    std::lock_guard<std::mutex> lk(sp->mu);
+    if (max_considered) *max_considered = sp->gumbel_on ? sp->m->gd.max_considered : 0;
+    if (c_visit) *c_visit = sp->gumbel_on ? sp->m->gd.c_visit : 0.0;
+    if (c_scale) *c_scale = sp->gumbel_on ? sp->m->gd.c_scale : 0.0;
+    unsigned long long c = 0;
+    if (moves && sp->gumbel_moves) {
+        hipSetDevice(sp->m->device);
+        OZ_HIP(hipStreamSynchronize(sp->m->stream));
+        OZ_HIP(hipMemcpy(&c, sp->gumbel_moves, sizeof c, hipMemcpyDeviceToHost));
+    }
+    if (moves) *moves = (int64_t)c;
+    return OZ_OK;
+}
+// what the last round's searches ran on: g, armed, N0 as oz_mcts_get_gumbel (zeros on an engine without the option)
+OZ_API int oz_selfplay_gumbel(oz_selfplay* sp, double* g, uint8_t* armed, int32_t* N0) {
+    OZ_REQUIRE(sp, "null selfplay");
+    { std::lock_guard<std::mutex> lk(sp->mu); hipSetDevice(sp->m->device); OZ_HIP(hipStreamSynchronize(sp->m->stream)); }
+    return oz_mcts_get_gumbel(sp->m, g, armed, N0, nullptr, nullptr, nullptr, nullptr);
+}
 OZ_API int oz_selfplay_root_noise(oz_selfplay* sp, double* eta, uint8_t* armed) {
     OZ_REQUIRE(sp, "null selfplay");
     std::lock_guard<std::mutex> lk(sp->mu);
@@ -2829,6 +3335,7 @@ OZ_API int oz_selfplay_run_steps(oz_selfplay* sp, int steps) {
         oz_set_error("oz_selfplay_run_steps: the free-running driver runs one leaf per game and batch (leaves_per_step is %d); use oz_selfplay_run", sp->m->leaves_per_step);
         return OZ_ERR_STATE;
     }
+    if (sp->gumbel_on) { oz_set_error("oz_selfplay_run_steps: the free-running driver does not run the Gumbel search; use oz_selfplay_run"); return OZ_ERR_STATE; }
     std::lock_guard<std::mutex> lkn(sp->net->mu);
     oz_mcts* m = sp->m;
     hipSetDevice(m->device);
@@ -2974,6 +3481,19 @@ int oz_selfplay_replay_facts(oz_selfplay* sp, int* n, int* device, int* record_v
     *n = sp->gm.n; *device = sp->m->device; *record_visits = sp->gm.record_visits;
     *completed = (long long)total > sp->gm.record_cap ? sp->gm.record_cap : (int64_t)total;
     return OZ_OK;
+}
+int oz_selfplay_has_gumbel(oz_selfplay* sp) { std::lock_guard<std::mutex> lk(sp->mu); return sp->gumbel_on ? 1 : 0; }
+#define OZ_REQUIRE_GUMBEL(sp) OZ_REQUIRE((sp)->gumbel_on, "this engine does not run the Gumbel search: oz_selfplay_set_gumbel before the first driver call")
+// the float32 improved-policy row of every recorded move, by square: row i belongs to record i of oz_selfplay_records, the same ring order
+OZ_API int oz_selfplay_policies(oz_selfplay* sp, float* out, int64_t max_records, int64_t* written) {
+    OZ_REQUIRE(sp, "null selfplay");
+    OZ_REQUIRE_GUMBEL(sp);
+    return selfplay_rows(sp, sp->gumbel_rows, 64 * sizeof(float), out, max_records, written, hipMemcpyDeviceToHost);
+}
+OZ_API int oz_selfplay_policies_device(oz_selfplay* sp, void* dst_device, int64_t max_records, int64_t* written) {
+    OZ_REQUIRE(sp, "null selfplay");
+    OZ_REQUIRE_GUMBEL(sp);
+    return selfplay_rows(sp, sp->gumbel_rows, 64 * sizeof(float), dst_device, max_records, written, hipMemcpyDeviceToDevice);
 }
 #define OZ_REQUIRE_VISITS(sp) OZ_REQUIRE((sp)->gm.record_visits, "this engine does not record visit counts: create it with oz_selfplay_config.record_visits = 1")
 OZ_API int oz_selfplay_visits(oz_selfplay* sp, int32_t* out, int64_t max_records, int64_t* written) {

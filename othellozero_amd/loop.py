@@ -22,6 +22,7 @@ Deliberate differences (documented, switchable where it matters):
   `arena_batch` plays.
 * `examples-<n>.txt` (a str() dump of the whole buffer every iteration, main.py:252-253) is only written when asked.
 """
+import ctypes as C
 import logging
 import random
 
@@ -73,7 +74,7 @@ class CircularArray:
         return f'{type(self).__name__}({len(self._list)!r})'
 
 
-def examples_from_records(records, board_size, alias_final=True, in_channels=2, visits=None, target_temperature=1.0, values=None):
+def examples_from_records(records, board_size, alias_final=True, in_channels=2, visits=None, target_temperature=1.0, values=None, policies=None):
     """move records of finished games -> the reference's example tuples [(board, one-hot policy (n,n), z)], 8 per move in
     training.py:13-23's order.
 
@@ -86,7 +87,31 @@ def examples_from_records(records, board_size, alias_final=True, in_channels=2, 
     visits (int32 (R, 64), the records' root visit counts): the policy of every example is the search's visit distribution at
     target_temperature (expand_examples) instead of the one-hot of the move played.
     The fast records of a playout cap (_lib.record_fast) are no training examples: they and their visit-count rows are dropped first.
-    values (float32 (R,), the records' value targets): the z of every example is its record's target, a float, instead of the int outcome."""
+    values (float32 (R,), the records' value targets): the z of every example is its record's target, a float, instead of the int outcome.
+    policies (float32 (R, 64) by square, the records' improved-policy rows of a Gumbel search, SelfPlayEngine.records(with_policies=True)): the
+    policy of every example is its record's row under the example's symmetry, float32 (n, n), bit for bit (oz_examples_expand_policy, on the
+    host); not together with visits."""
+    if policies is not None:
+        if visits is not None:
+            raise ValueError("examples_from_records: policies and visits are two policy targets; pass one")
+        rec = np.ascontiguousarray(records, dtype=_lib.RECORD_DTYPE).ravel()
+        rows = np.ascontiguousarray(policies, dtype=np.float32).reshape(-1, 64)
+        if rows.shape[0] != rec.size:
+            raise ValueError(f"{rows.shape[0]} policy rows for {rec.size} records")
+        keep = _lib.record_fast(rec).ravel() == 0
+        if values is not None:
+            val = np.ascontiguousarray(values, dtype=np.float32).ravel()
+            assert val.size == rec.size, f"{val.size} value targets for {rec.size} records"
+            values = val[keep]
+        rec, rows = np.ascontiguousarray(rec[keep]), np.ascontiguousarray(rows[keep])
+        R, n, one_channel = rec.size, board_size, in_channels == 1
+        boards, pi, z = np.zeros((R * 8, n, n, 2), np.uint8), np.zeros((R * 8, n, n), np.float32), np.zeros(R * 8, np.int8)
+        if R:
+            _lib.check(_lib.load().oz_examples_expand_policy(rec.ctypes.data_as(C.c_void_p), _lib.p_f32(rows), R, n,
+                                                             1 if alias_final and not one_channel else 0, _lib.p_u8(boards), _lib.p_f32(pi), _lib.p_i8(z)))
+        boards = boards[..., 0].astype(np.int64) - boards[..., 1].astype(np.int64) if one_channel else boards.astype(bool)
+        zz = [float(t) for t in np.repeat(values, 8)] if values is not None else [int(t) for t in z]
+        return list(zip(boards, pi, zz))
     if values is not None:
         val = np.ascontiguousarray(values, dtype=np.float32).ravel()
         assert val.size == np.asarray(records).size, f"{val.size} value targets for {np.asarray(records).size} records"
@@ -271,19 +296,21 @@ def self_play_match(board_size, neural_network, old_neural_network, total_games,
 
 def _selfplay_into_replay(replay, neural_network, board_size, num_episodes, num_simulations, degree_exploration, temperature, e_greedy, seed,
                           first_game_id, q_mode, visits, leaves_per_step, root_noise, sample_moves, alias_final_boards, policy_target,
-                          target_temperature, endgame_targets=0, solve_leaves=0, playout_cap=None, forced_playouts=0.0, value_target="outcome"):
+                          target_temperature, endgame_targets=0, solve_leaves=0, playout_cap=None, forced_playouts=0.0, value_target="outcome",
+                          gumbel=None):
     """one iteration's games on the engine selfplay_batch would create, played to the end without reading a record, and their examples
     appended to the device buffer; -> (records appended, the endgame solver's statistics or None).  One-channel (BaseNN) examples are never
     aliased (examples_from_records).  endgame_targets > 0: SelfPlayEngine.solve_records before the append.  playout_cap: the engine's; the
     append leaves the fast records out and counts the fully searched ones.  forced_playouts: the engine's; its visit rows, which the append
     reads, are then the pruned ones.  value_target: the engine records root values and the append computes the value targets (after the
-    endgame solver, exact_empties = endgame_targets)."""
+    endgame solver, exact_empties = endgame_targets).  gumbel: the engine's; policy_target="improved" appends its improved-policy rows."""
     from .training import SelfPlayEngine
     vt_on = _lib.check_value_target(value_target)[0] != _lib.VALUE_TARGET_OUTCOME
     eng = SelfPlayEngine(neural_network, board_size, num_episodes, num_simulations, degree_exploration, temperature, e_greedy, seed,
                          first_game_id, q_mode=q_mode, record_visits=visits, leaves_per_step=leaves_per_step, root_noise=root_noise,
                          sample_moves=sample_moves, solve_leaves=solve_leaves, **({"playout_cap": playout_cap} if playout_cap is not None else {}),
-                         **({"forced_playouts": forced_playouts} if forced_playouts else {}), **({"record_values": True} if vt_on else {}))
+                         **({"forced_playouts": forced_playouts} if forced_playouts else {}), **({"record_values": True} if vt_on else {}),
+                         **({"gumbel": gumbel} if gumbel is not None else {}))
     for _ in range(board_size * board_size):
         eng.run(4)
         if eng.stats()["live_games"] == 0:
@@ -308,8 +335,14 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
              distributed=False, batched_evaluation=False, policy_target="onehot", target_temperature=1.0, leaves_per_step=1,
              root_noise=None, sample_moves=None, replay="host", evaluation_opponent="random", endgame_targets=0,
              solve_leaves=0, match_openings=None, evaluation_openings=None, playout_cap=None, forced_playouts=None, eval_symmetry=None,
-             value_target="outcome"):
+             value_target="outcome", gumbel=None):
     """main.py:56-259 on the GPU engines; returns `historic` = [(episodes done, win rate vs random), ...]
+
+    gumbel=(max_considered, c_visit, c_scale) or True (None = off, the default): the root search of Gumbel AlphaZero for every searched
+    SELF-PLAY move (SelfPlayEngine), with replay="host" and replay="device" alike; matches and evaluations stay on PUCT.  It replaces
+    root_noise, forced_playouts and sample_moves and does not combine with playout_cap, leaves_per_step > 1 or distributed=True
+    (ValueError).  policy_target="improved" (needs gumbel, alias_final_boards=False and the flat policy loss) trains the policy on the
+    searches' improved-policy rows softmax(logit + sigma(completed Q)); policy_target="visits" with gumbel keeps training on the raw counts.
 
     batched_evaluation=True plays the evaluation games against RandomOthelloAgent in lock step on the GPU
     (evaluate_against_random_batch) instead of one by one through the drop-in agents.
@@ -451,8 +484,20 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
         raise ValueError("replay='device' keeps no example tuples to dump: use replay='host' with dump_examples=True, or ReplayBuffer.save")
     root_noise = _lib.check_root_noise(root_noise)
     sample_moves = _lib.check_sample_moves(sample_moves)
-    if policy_target not in ("onehot", "visits"):
-        raise ValueError(f"policy_target must be 'onehot' or 'visits' (got {policy_target!r})")
+    gumbel = _lib.check_gumbel_options(gumbel, root_noise=root_noise, forced_playouts=forced_playouts, sample_moves=sample_moves,
+                                       playout_cap=playout_cap, leaves_per_step=leaves_per_step, distributed=distributed)
+    gumbel_kw = {"gumbel": gumbel} if gumbel is not None else {}
+    if policy_target not in ("onehot", "visits", "improved"):
+        raise ValueError(f"policy_target must be 'onehot', 'visits' or 'improved' (got {policy_target!r})")
+    improved = policy_target == "improved"
+    if improved and gumbel is None:
+        raise ValueError("policy_target='improved' needs gumbel=(max_considered, c_visit, c_scale): the improved policy is the Gumbel search's")
+    if improved and alias_final_boards:
+        raise ValueError("policy_target='improved' needs alias_final_boards=False: an improved policy belongs to the position of its "
+                         "move, not to the game's final position")
+    if improved and getattr(neural_network, "policy_loss", "rows") != "flat":
+        raise ValueError("policy_target='improved' needs a network trained with the flat policy loss: create it with "
+                         "NNetWrapper(..., policy_loss='flat')")
     visits = policy_target == "visits"
     if visits and alias_final_boards:
         raise ValueError("policy_target='visits' needs alias_final_boards=False: a visit distribution belongs to the position of its "
@@ -510,7 +555,8 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
             appended, endgame = _selfplay_into_replay(device_replay, neural_network, board_size, num_episodes, num_simulations,
                                                       degree_exploration, temperature, e_greedy, seed, total_episodes_done, q_mode, visits,
                                                       leaves_per_step, root_noise, sample_moves, alias_final_boards, policy_target,
-                                                      target_temperature, endgame_targets, solve_leaves, playout_cap, forced_playouts, **vt_kw)
+                                                      target_temperature, endgame_targets, solve_leaves, playout_cap, forced_playouts, **vt_kw,
+                                                      **gumbel_kw)
             if endgame is not None:
                 training.endgame_history.append(endgame)
                 _log_endgame(i, num_iterations, endgame)
@@ -538,21 +584,24 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
                                          seed=seed, first_game_id=total_episodes_done, q_mode=q_mode, record_visits=visits,
                                          leaves_per_step=leaves_per_step, root_noise=root_noise, sample_moves=sample_moves,
                                          **({"endgame_targets": endgame_targets} if endgame_targets else {}), **({"solve_leaves": solve_leaves} if solve_leaves else {}),
-                                         **cap_kw, **vt_kw)
+                                         **cap_kw, **vt_kw, **gumbel_kw)
                 training.rows_solved += selfplay_batch.rows_solved if solve_leaves else 0
                 endgame = getattr(selfplay_batch, "endgame_stats", None) if endgame_targets else None
             restore_eval_symmetry()
             if endgame is not None:
                 training.endgame_history.append(endgame)
                 _log_endgame(i, num_iterations, endgame)
-            counts = targets = None
+            counts = targets = policies = None
+            if gumbel is not None:                             # the improved-policy rows come last
+                policies, records = records[-1], (records[0] if len(records) == 2 else records[:-1])
             if vt_on:
                 records, targets = (records[0], records[-1]) if not visits else ((records[0], records[1]), records[2])
             if visits:
                 records, counts = records
             training_examples.extend(examples_from_records(records, board_size, alias_final=alias_final_boards,
                                                            in_channels=getattr(neural_network, "in_channels", 2), visits=counts,
-                                                           target_temperature=target_temperature, **({"values": targets} if vt_on else {})))
+                                                           target_temperature=target_temperature, **({"values": targets} if vt_on else {}),
+                                                           **({"policies": policies} if improved else {})))
             total_episodes_done += num_episodes
             logging.info('[%d/%d] self-play done: %d records, buffer holds %d examples', i, num_iterations, len(records), len(training_examples))
 

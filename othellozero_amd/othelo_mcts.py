@@ -18,7 +18,7 @@ from .Othello import OthelloGame, OthelloPlayer
 
 class OthelloMCTS:
     def __init__(self, board_size, neural_network, degree_exploration, q_mode=_lib.QMODE_F64,
-                 node_cap=8192, leaves_per_step=1, solve_leaves=0, forced_playouts=None):
+                 node_cap=8192, leaves_per_step=1, solve_leaves=0, forced_playouts=None, gumbel=None):
         """q_mode: OZ_QMODE_F64 = the NumPy 1.18.5 promotion the reference pins (requirements.txt:19),
         OZ_QMODE_NEP50 = what NumPy >= 2 computes (SURVEY.md R-FP).
         leaves_per_step > 1 (native networks only, created with max_batch >= leaves_per_step): that many descents of the tree per
@@ -27,7 +27,12 @@ class OthelloMCTS:
         to move, oz_mcts_set_solve_leaves) in place of the network's value; the priors stay the network's.  Not the reference's search.
         forced_playouts=k > 0: KataGo's forced playouts on every root that carries noise (set_root_noise / sample_root_noise; without noise
         the search is unchanged), and pruned_counts / get_policy_action_probabilities(..., pruned=True) give the pruned policy target
-        (oz_mcts_set_forced_playouts).  Not the reference's search."""
+        (oz_mcts_set_forced_playouts).  Not the reference's search.
+        gumbel=(max_considered, c_visit, c_scale) or True: the search keeps every node's own value and is ready for the Gumbel root rule
+        (include/othellozero_amd.h, "Gumbel search"): sample_gumbel / set_gumbel arm a root before its simulations, gumbel_policy gives the
+        move and the improved policy afterwards.  It replaces root noise, forced playouts and move sampling; not with leaves_per_step > 1.
+        Not the reference's search."""
+        self.gumbel = _lib.check_gumbel_options(gumbel, forced_playouts=forced_playouts, leaves_per_step=leaves_per_step)
         self.forced_playouts = _lib.check_forced_playouts(forced_playouts, need_noise=False)
         self._forced_set = False
         self.solve_leaves = _lib.check_solve_leaves(solve_leaves)
@@ -54,6 +59,62 @@ class OthelloMCTS:
             _lib.check(lib.oz_mcts_set_leaves_per_step(self._h, self.leaves_per_step))
         if self.solve_leaves:
             _lib.check(lib.oz_mcts_set_solve_leaves(self._h, self.solve_leaves))
+        if self.gumbel is not None:                        # over the empty tree: the parameters, no root armed yet (the budget comes with the arming)
+            _lib.check(lib.oz_mcts_set_gumbel(self._h, self.gumbel[0], self.gumbel[1], self.gumbel[2], 1, None, None))
+
+    # ---- Gumbel search (include/othellozero_amd.h, "Gumbel search")
+    def _need_gumbel(self):
+        if self.gumbel is None:
+            raise ValueError("this search was created without gumbel=(max_considered, c_visit, c_scale)")
+
+    def sample_gumbel(self, budget, seed, game_id, ply, state=None, player=None):
+        """arm the current root (or `state` seen by `player`, which becomes the root) for a search of `budget` simulations: g drawn on the
+        device, keyed (seed, game_id, ply), N0 = the root's counts now"""
+        self._need_gumbel()
+        if state is not None:
+            self._set_root(*self._canonical(state, player))
+        gid, pl = np.array([int(game_id)], np.uint64), np.array([int(ply)], np.int32)
+        _lib.check(_lib.load().oz_mcts_sample_gumbel(self._h, self.gumbel[0], self.gumbel[1], self.gumbel[2], int(budget), int(seed),
+                                                     _lib.p_u64(gid), _lib.p_i32(pl)))
+
+    def set_gumbel(self, g, budget, state=None, player=None):
+        """the same with host-supplied draws: g = (n, n) or (64,) by square row*8+col; None disarms"""
+        self._need_gumbel()
+        if state is not None:
+            self._set_root(*self._canonical(state, player))
+        row = None
+        if g is not None:
+            e = np.asarray(g, dtype=np.float64)
+            n = self._board_size
+            row = np.zeros((1, 64), np.float64)
+            if e.shape == (n, n):
+                row.reshape(8, 8)[:n, :n] = e
+            elif e.size == 64:
+                row[0] = e.ravel()
+            else:
+                raise ValueError(f"g must be ({n}, {n}) or 64 values (got shape {e.shape})")
+        _lib.check(_lib.load().oz_mcts_set_gumbel(self._h, self.gumbel[0], self.gumbel[1], self.gumbel[2], int(budget),
+                                                  None if row is None else _lib.p_f64(row), None))
+
+    def gumbel_root(self):
+        """(g (64,) float64 by square, armed bool, N0 (64,) int32) of the current root"""
+        g, armed, n0 = np.zeros((1, 64), np.float64), np.zeros(1, np.uint8), np.zeros((1, 64), np.int32)
+        _lib.check(_lib.load().oz_mcts_get_gumbel(self._h, _lib.p_f64(g), _lib.p_u8(armed), _lib.p_i32(n0), None, None, None, None))
+        return g[0], bool(armed[0]), n0[0]
+
+    def gumbel_policy(self, state):
+        """after the simulations of an armed root, for the mover-canonical `state` (as get_policy_action_probabilities takes it):
+        ((row, col) = the Gumbel root's move, pi float32 (n, n) = the improved policy softmax(logit + sigma(completed Q))).  KeyError if the
+        state is unknown or its root is not armed."""
+        self._need_gumbel()
+        own, opp = _lib.pack_board(state)
+        self._set_root(own, opp)
+        pi, action, rc = np.zeros((1, 64), np.float32), np.zeros(1, np.int32), np.zeros(1, np.int32)
+        _lib.check(_lib.load().oz_mcts_gumbel_policy(self._h, _lib.p_f32(pi), _lib.p_i32(action), _lib.p_i32(rc)))
+        if rc[0] != 0 or action[0] < 0:
+            raise KeyError("state is unknown to the search or its root is not armed (sample_gumbel / set_gumbel before the simulations)")
+        n = self._board_size
+        return (int(action[0]) >> 3, int(action[0]) & 7), pi.reshape(8, 8)[:n, :n].copy()
 
     def rows_solved(self):
         """leaves this search has given their exact value so far (0 without solve_leaves)"""

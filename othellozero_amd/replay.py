@@ -18,7 +18,11 @@ from . import _lib
 POLICY_TARGETS = {"onehot": _lib.REPLAY_TARGET_ONEHOT, "visits": _lib.REPLAY_TARGET_VISITS}
 
 
-def _target(policy_target, target_temperature):
+def _target(policy_target, target_temperature, engine=False):
+    if engine and policy_target == "improved":
+        return _lib.REPLAY_TARGET_POLICY, float(target_temperature)
+    if policy_target == "improved":
+        raise ValueError("policy_target 'improved' is offered for an engine's records only (append_engine)")
     if policy_target not in POLICY_TARGETS:
         raise ValueError(f"policy_target must be 'onehot' or 'visits' (got {policy_target!r})")
     return POLICY_TARGETS[policy_target], float(target_temperature)
@@ -61,14 +65,16 @@ class ReplayBuffer:
         _lib.check(_lib.load().oz_replay_clear(self._h))
 
     def append_engine(self, eng, first_record=0, alias_final=False, policy_target="onehot", target_temperature=1.0, value_target="outcome",
-                      exact_empties=0):
+                      exact_empties=0, target=None):
         """the records [first_record, completed so far) of a SelfPlayEngine -> 8 examples each, in ascending (game_id, ply), device to
         device; returns the number of records appended.  policy_target="visits" needs an engine created with record_visits=True.
+        policy_target="improved" (or target="improved") needs an engine created with gumbel=...: every example's pi is its record's float32
+        improved-policy row under the example's symmetry, staged device to device, bit for bit.
         The fast records of a playout cap (_lib.record_fast) are left out and not counted.
         value_target=("blend", w) / ("td", lam) (an engine created with record_values=True; alias_final=False): the engine computes the
         value targets of those records (SelfPlayEngine.value_targets(value_target, exact_empties, first_record)) and every example's z is
         its record's float32 target instead of the game outcome; "outcome" is the call without it."""
-        target, T = _target(policy_target, target_temperature)
+        target, T = _target(policy_target if target is None else target, target_temperature, engine=True)
         mode, _ = _lib.check_value_target(value_target, alias_final)
         done = C.c_int64()
         if mode != _lib.VALUE_TARGET_OUTCOME:

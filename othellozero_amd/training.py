@@ -33,8 +33,14 @@ def training_example_symmetries(board, policy):
 def execute_episode(board_size, neural_network, degree_exploration, num_simulations, policy_temperature, e_greedy,
                     q_mode=_lib.QMODE_F64, snapshot_boards=False, policy_target="onehot", target_temperature=1.0,
                     leaves_per_step=1, root_noise=None, noise_seed=0, sample_moves=None, sample_seed=0, solve_leaves=0,
-                    forced_playouts=None, value_target="outcome"):
+                    forced_playouts=None, value_target="outcome", gumbel=None, gumbel_seed=0):
     """training.py:26-72.  Returns [(board (n,n,2) bool, one-hot policy (n,n) float64, z int), ...], 8 per move.
+
+    gumbel=(max_considered, c_visit, c_scale) or True: every move's search is a Gumbel root search of num_simulations simulations
+    (OthelloMCTS.sample_gumbel before them, keyed (gumbel_seed, 0, ply) with ply = the moves played so far), and the greedy branch of the coin
+    plays the Gumbel root's move; the explore branch is unchanged.  policy_target="improved" (needs gumbel and snapshot_boards=True) stores the
+    search's float32 improved policy (OthelloMCTS.gumbel_policy).  It replaces root_noise, forced_playouts and sample_moves; not with
+    leaves_per_step > 1.  None is the function without it.
 
     snapshot_boards=False reproduces the reference exactly, including its aliasing quirk: the
     returned boards are views of the live game array, so every example shows the FINAL position.  Pass
@@ -68,14 +74,20 @@ def execute_episode(board_size, neural_network, degree_exploration, num_simulati
     root_noise = _lib.check_root_noise(root_noise)
     forced_playouts = _lib.check_forced_playouts(forced_playouts, root_noise)
     sample_moves = _lib.check_sample_moves(sample_moves)
-    assert policy_target in ("onehot", "visits"), policy_target
+    gumbel = _lib.check_gumbel_options(gumbel, root_noise=root_noise, forced_playouts=forced_playouts, sample_moves=sample_moves,
+                                       leaves_per_step=leaves_per_step)
+    assert policy_target in ("onehot", "visits", "improved"), policy_target
+    if policy_target == "improved" and gumbel is None:
+        raise ValueError("policy_target='improved' needs gumbel=(max_considered, c_visit, c_scale)")
+    if policy_target == "improved" and not snapshot_boards:
+        raise ValueError("policy_target='improved' needs snapshot_boards=True: an improved policy belongs to the position of its move")
     if policy_target == "visits" and not target_temperature > 0:
         raise ValueError(f"target_temperature must be > 0 for visit-count targets (got {target_temperature})")
     examples = []
     game = OthelloGame(board_size)
     mcts = OthelloMCTS(board_size, neural_network, degree_exploration, q_mode=q_mode,
                        node_cap=num_simulations * (board_size * board_size - 3) + 64, leaves_per_step=leaves_per_step,
-                       solve_leaves=solve_leaves, forced_playouts=forced_playouts)
+                       solve_leaves=solve_leaves, forced_playouts=forced_playouts, **({"gumbel": gumbel} if gumbel is not None else {}))
     # training.py:34-37 (BNN examples are one-channel boards, a fresh array per round: no aliasing for them)
     board_view_type = BoardView.ONE_CHANNEL if getattr(neural_network.network_type, "name", "") == "BNN" else BoardView.TWO_CHANNELS
 
@@ -83,6 +95,8 @@ def execute_episode(board_size, neural_network, degree_exploration, num_simulati
         state = game.board(BoardView.TWO_CHANNELS)
         if root_noise is not None:
             mcts.sample_root_noise(root_noise[0], root_noise[1], noise_seed, 0, len(examples) // 8, state=state, player=game.current_player)
+        if gumbel is not None:
+            mcts.sample_gumbel(num_simulations, gumbel_seed, 0, len(examples) // 8, state=state, player=game.current_player)
         mcts.simulate_n(state, game.current_player, num_simulations)
         if game.current_player == OthelloPlayer.WHITE:
             state = OthelloGame.invert_board(state)
@@ -95,6 +109,8 @@ def execute_episode(board_size, neural_network, degree_exploration, num_simulati
         coin = random.random()                      # e-greedy, training.py:51-56
         if coin <= e_greedy:
             action = np.argwhere(policy == policy.max())[0]
+            if gumbel is not None:
+                action = mcts.gumbel_policy(state)[0]
             if sample_moves is not None and len(examples) // 8 < sample_moves[1]:
                 action = mcts.sample_action(state, sample_moves[0], sample_seed, 0, len(examples) // 8)
         else:
@@ -103,6 +119,8 @@ def execute_episode(board_size, neural_network, degree_exploration, num_simulati
 
         action_choosed = np.zeros((board_size, board_size))
         action_choosed[action[0]][action[1]] = 1
+        if policy_target == "improved":
+            action_choosed = mcts.gumbel_policy(state)[1]
         if policy_target == "visits":
             action_choosed = mcts.get_policy_action_probabilities(state, target_temperature, pruned=forced_playouts > 0.0)
         board_now = game.board(board_view_type)
@@ -170,7 +188,7 @@ class SelfPlayEngine:
                  policy_temperature=1.0, e_greedy=0.9, seed=1234, first_game_id=0, game_id_stride=0,
                  q_mode=_lib.QMODE_F64, refill=False, node_cap=0, record_cap=0, dedup=True, batch_cap=0, eval_cache=False,
                  record_visits=False, leaves_per_step=1, root_noise=None, sample_moves=None, solve_leaves=0, playout_cap=None,
-                 forced_playouts=None, record_values=False):
+                 forced_playouts=None, record_values=False, gumbel=None):
         """dedup: cross-game leaf de-duplication (a board several games reach in one batch is evaluated once; no record changes);
         batch_cap: leaves per network batch of the free-running driver (0 = none; see preferred_batch_cap);
         eval_cache: take (pi, v) of boards the network has evaluated before from its persistent cache (NNetWrapper.set_eval_cache) --
@@ -205,7 +223,16 @@ class SelfPlayEngine:
         cap are neither forced nor pruned.  forced_playout_stats() counts ("Forced playouts").
         record_values=True: keep every recorded move's root value -- the visit-weighted mean of the root's Q over the raw counts, for the player
         to move (oz_selfplay_set_record_values) -- for records(with_values=True) and value_targets(); 512 B per slot + 8 B per record of device
-        memory, no record changes.  Every driver ("Value targets")."""
+        memory, no record changes.  Every driver ("Value targets").
+        gumbel=(max_considered, c_visit, c_scale) or True (= (16, 50.0, 1.0)): the root search of Gumbel AlphaZero for every searched move of
+        run() (oz_selfplay_set_gumbel): the root samples max_considered moves without replacement with Gumbel noise drawn on the device, keyed
+        (seed, game id, ply), spends num_simulations on them by sequential halving, and the greedy branch of the coin plays the root's move
+        (greedy == 3 in its record; pure Gumbel: e_greedy = 1).  The engine keeps the float32 improved-policy row softmax(logit + sigma(completed
+        Q)) of every searched move: records(with_policies=True), the targets of loop.examples_from_records(policies=...).  16 KB per slot +
+        256 B per record.  It replaces root_noise, forced_playouts and sample_moves, and does not combine with playout_cap or
+        leaves_per_step > 1 (ValueError); run_steps() and stagger() then raise.  gumbel_stats() counts (DESIGN.md, "Gumbel search")."""
+        gumbel = _lib.check_gumbel_options(gumbel, root_noise=root_noise, forced_playouts=forced_playouts, sample_moves=sample_moves,
+                                           playout_cap=playout_cap, leaves_per_step=leaves_per_step)
         playout_cap = _lib.check_playout_cap(playout_cap, num_simulations)
         solve_leaves = _lib.check_solve_leaves(solve_leaves)
         root_noise = _lib.check_root_noise(root_noise)
@@ -244,6 +271,23 @@ class SelfPlayEngine:
         self.record_values = bool(record_values)
         if record_values:
             _lib.check(lib.oz_selfplay_set_record_values(self._h, 1))
+        self.gumbel = gumbel
+        if gumbel is not None:
+            _lib.check(lib.oz_selfplay_set_gumbel(self._h, gumbel[0], gumbel[1], gumbel[2]))
+
+    def gumbel_stats(self):
+        """dict(max_considered, c_visit, c_scale, moves): the Gumbel search that is set (max_considered 0 = off) and the moves the Gumbel rule
+        has picked so far (the records with greedy == 3, those of games still in progress included)"""
+        m, cv, cs, moves = C.c_int32(), C.c_double(), C.c_double(), C.c_int64()
+        _lib.check(_lib.load().oz_selfplay_get_gumbel(self._h, C.byref(m), C.byref(cv), C.byref(cs), C.byref(moves)))
+        return dict(max_considered=m.value, c_visit=cv.value, c_scale=cs.value, moves=moves.value)
+
+    def last_gumbel(self):
+        """(g float64 (num_games, 64) by square, armed uint8 (num_games,), N0 int32 (num_games, 64)) of the searches of the last move round"""
+        G = self.num_games
+        g, armed, n0 = np.zeros((G, 64), np.float64), np.zeros(G, np.uint8), np.zeros((G, 64), np.int32)
+        _lib.check(_lib.load().oz_selfplay_gumbel(self._h, _lib.p_f64(g), _lib.p_u8(armed), _lib.p_i32(n0)))
+        return g, armed, n0
 
     def value_targets(self, value_target, exact_empties=0, first_record=0):
         """oz_selfplay_value_targets: the value targets of the completed records from `first_record` on, computed on the device into the
@@ -371,19 +415,20 @@ class SelfPlayEngine:
         _lib.check(_lib.load().oz_selfplay_last_counts(self._h, _lib.p_i32(c)))
         return c
 
-    def records(self, with_visits=False, with_values=False, with_targets=False):
+    def records(self, with_visits=False, with_values=False, with_targets=False, with_policies=False):
         """move records of the games completed so far (numpy structured array, _lib.RECORD_DTYPE),
         sorted by (game_id, ply).  with_visits=True (engine created with record_visits=True): (records, counts), counts =
         int32 (R, 64) root visit counts of each record's move by square row*8+col, in the same order.
         with_values=True (record_values=True): (records, [counts,] values), values = float64 (R,) root value of each record's search.
-        with_targets=True (after value_targets()): the float32 (R,) value targets come last, (records, [counts,] [values,] targets)."""
+        with_targets=True (after value_targets()): the float32 (R,) value targets follow, (records, [counts,] [values,] targets).
+        with_policies=True (gumbel=...): the float32 (R, 64) improved-policy rows by square come last."""
         total = self.stats()["records"]
         out = np.zeros(max(total, 1), dtype=_lib.RECORD_DTYPE)
         written = C.c_int64()
         _lib.check(_lib.load().oz_selfplay_records(self._h, out.ctypes.data_as(C.c_void_p), total, C.byref(written)))
         out = out[:written.value]
         order = np.lexsort((out["ply"], out["game_id"]))
-        if not (with_visits or with_values or with_targets):
+        if not (with_visits or with_values or with_targets or with_policies):
             return out[order]
         ret = [out[order]]
         got = C.c_int64()
@@ -402,6 +447,11 @@ class SelfPlayEngine:
             _lib.check(_lib.load().oz_selfplay_targets(self._h, _lib.p_f32(targets), out.size, C.byref(got)))
             assert got.value == out.size, (got.value, out.size)
             ret.append(targets[:out.size][order])
+        if with_policies:
+            rows = np.zeros((max(out.size, 1), 64), np.float32)
+            _lib.check(_lib.load().oz_selfplay_policies(self._h, _lib.p_f32(rows), out.size, C.byref(got)))
+            assert got.value == out.size, (got.value, out.size)
+            ret.append(rows[:out.size][order])
         return tuple(ret)
 
     def solve_records(self, max_empties, first_record=0):
@@ -429,6 +479,12 @@ class SelfPlayEngine:
         _lib.check(_lib.load().oz_selfplay_visits_device(self._h, C.c_void_p(device_ptr), max_records, C.byref(written)))
         return written.value
 
+    def policies_to_device(self, device_ptr, max_records):
+        """the improved-policy rows (float32 [max_records][64], gumbel=...) in the ring order of records_to_device, device to device"""
+        written = C.c_int64()
+        _lib.check(_lib.load().oz_selfplay_policies_device(self._h, C.c_void_p(device_ptr), max_records, C.byref(written)))
+        return written.value
+
     def targets_to_device(self, device_ptr, max_records):
         """the value targets (float32 [max_records], after value_targets()) in the ring order of records_to_device, device to device"""
         written = C.c_int64()
@@ -440,10 +496,11 @@ class SelfPlayEngine:
         _lib.check(_lib.load().oz_selfplay_eval_time(self._h, C.byref(ms), C.byref(launches), C.byref(leaves)))
         return dict(ms=ms.value, launches=launches.value, leaves=leaves.value)
 
-    def play_to_end(self, max_rounds=None, with_visits=False, endgame_targets=0, value_target="outcome"):
+    def play_to_end(self, max_rounds=None, with_visits=False, endgame_targets=0, value_target="outcome", with_policies=False):
         """endgame_targets=E > 0: solve_records(E) once the games are over, before the records are read (its stats: self.endgame_stats).
         value_target other than "outcome": value_targets(value_target, exact_empties=endgame_targets) after that (its stats:
-        self.value_target_stats), and the targets come back last: (records, [counts,] targets)"""
+        self.value_target_stats), and the targets come back too: (records, [counts,] targets).  with_policies=True (gumbel=...): the
+        improved-policy rows come last"""
         max_rounds = max_rounds or self.n * self.n
         for _ in range(max_rounds):
             self.run(4)
@@ -453,8 +510,8 @@ class SelfPlayEngine:
             self.endgame_stats = self.solve_records(endgame_targets)
         if _lib.check_value_target(value_target)[0] != _lib.VALUE_TARGET_OUTCOME:
             self.value_target_stats = self.value_targets(value_target, exact_empties=endgame_targets)
-            return self.records(with_visits=with_visits, with_targets=True)
-        return self.records(with_visits=with_visits)
+            return self.records(with_visits=with_visits, with_targets=True, with_policies=with_policies)
+        return self.records(with_visits=with_visits, with_policies=with_policies)
 
 
 def preferred_batch_cap(board_size, num_games, channels=512, precision="f16x2"):
@@ -517,8 +574,11 @@ def expand_examples(records, board_size, alias_final=False, visits=None, target_
 def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations=100, degree_exploration=1.0,
                    policy_temperature=1.0, e_greedy=0.9, seed=1234, first_game_id=0, q_mode=_lib.QMODE_F64,
                    expand=False, alias_final=False, record_visits=False, target_temperature=1.0, leaves_per_step=1, root_noise=None,
-                   sample_moves=None, endgame_targets=0, solve_leaves=0, playout_cap=None, forced_playouts=None, value_target="outcome"):
+                   sample_moves=None, endgame_targets=0, solve_leaves=0, playout_cap=None, forced_playouts=None, value_target="outcome", gumbel=None):
     """Play num_games complete games; returns the move records (or the expanded examples).
+    gumbel=(max_considered, c_visit, c_scale) or True: the Gumbel root search in every searched move (SelfPlayEngine).  The float32 (R, 64)
+    improved-policy rows come back last -- (records, [counts,] [targets,] policies) -- for loop.examples_from_records(policies=...); not with
+    expand (ValueError).  selfplay_batch.gumbel_stats holds the last call's SelfPlayEngine.gumbel_stats() (None when off).
     record_visits=True: (records, visit counts) -- or, with expand, the examples with visit-distribution targets at target_temperature.
     root_noise=(alpha, epsilon): Dirichlet root noise in every search (SelfPlayEngine).
     sample_moves=(temperature, plies): the opening plies' moves are sampled from the visit counts (SelfPlayEngine).
@@ -537,6 +597,10 @@ def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations
     the examples' float32 z; with expand it needs alias_final=False.  selfplay_batch.value_target_stats holds the last call's statistics
     (None when off)."""
     vt_on = _lib.check_value_target(value_target, expand and alias_final)[0] != _lib.VALUE_TARGET_OUTCOME
+    gumbel = _lib.check_gumbel_options(gumbel, root_noise=root_noise, forced_playouts=forced_playouts, sample_moves=sample_moves,
+                                       playout_cap=playout_cap, leaves_per_step=leaves_per_step)
+    if gumbel is not None and expand:
+        raise ValueError("selfplay_batch: gumbel with expand=True is not offered; expand the rows with loop.examples_from_records(policies=...)")
     forced_playouts = _lib.check_forced_playouts(forced_playouts, _lib.check_root_noise(root_noise))
     playout_cap = _lib.check_playout_cap(playout_cap, num_simulations)
     solve_leaves = _lib.check_solve_leaves(solve_leaves)
@@ -544,8 +608,18 @@ def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations
     eng = SelfPlayEngine(neural_network, board_size, num_games, num_simulations, degree_exploration, policy_temperature,
                          e_greedy, seed, first_game_id, q_mode=q_mode, record_visits=record_visits, leaves_per_step=leaves_per_step,
                          root_noise=root_noise, sample_moves=sample_moves, solve_leaves=solve_leaves, playout_cap=playout_cap,
-                         **({"forced_playouts": forced_playouts} if forced_playouts > 0.0 else {}), **({"record_values": True} if vt_on else {}))
+                         **({"forced_playouts": forced_playouts} if forced_playouts > 0.0 else {}), **({"record_values": True} if vt_on else {}),
+                         **({"gumbel": gumbel} if gumbel is not None else {}))
     selfplay_batch.value_target_stats = None
+    selfplay_batch.gumbel_stats = None
+    if gumbel is not None:                                 # (the options' statistics as below; the rows come last)
+        got = eng.play_to_end(with_visits=record_visits, endgame_targets=endgame_targets, value_target=value_target, with_policies=True)
+        selfplay_batch.gumbel_stats = eng.gumbel_stats()
+        selfplay_batch.endgame_stats = getattr(eng, "endgame_stats", None)
+        selfplay_batch.value_target_stats = getattr(eng, "value_target_stats", None)
+        selfplay_batch.forced_playout_stats = selfplay_batch.playout_stats = None
+        selfplay_batch.rows_solved = eng.rows_solved() if solve_leaves else None
+        return got
     if vt_on:
         got = eng.play_to_end(with_visits=record_visits, endgame_targets=endgame_targets, value_target=value_target)
         rec, counts, targets = got if record_visits else (got[0], None, got[1])
