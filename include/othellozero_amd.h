@@ -965,9 +965,13 @@ int oz_trainer_get_activation(oz_trainer* t, int layer, int B, float* data, int6
  *             OZ_ERR_STATE when capture is off or no step ran since it was switched on.
  * get_head_grads: the gradients wrt the policy logits and the value head's pre-activation, the two operands of the heads' data gradient.
  * get_preact, get_dz and get_head_grads return OZ_ERR_STATE before the first step of the trainer.
+ * get_bn_stats: the batch mean and rstd = 1 / sqrt(biased variance + 1e-3) that the BN forward of `layer` (0 .. 5) left, Co floats each.
+ * get_adam_state: the two Adam moments of trainable array `index` (get_weights() order; a moving statistic is refused), as many floats each as the array holds.
  * get_plan:   the launch plan of the last step, as the launchers themselves reported it (oz_net_get_info's counterpart): for layer l = 1 .. 5
- *             (conv2 .. fc2) the OZ_TRAINER_PLAN_FIELDS ints at plan[(l - 1) * OZ_TRAINER_PLAN_FIELDS]; n = 5 * OZ_TRAINER_PLAN_FIELDS. */
-#define OZ_TRAINER_PLAN_FIELDS 8             /* ints per layer; [7] is reserved (0) */
+ *             (conv2 .. fc2) the OZ_TRAINER_PLAN_FIELDS ints at plan[(l - 1) * OZ_TRAINER_PLAN_FIELDS], then a sixth row for conv1 (layer 0), which
+ *             has no GEMM: only its OZ_TRAINER_PLAN_BN_* and OZ_TRAINER_PLAN_CONV1_* fields are set; n = 6 * OZ_TRAINER_PLAN_FIELDS. */
+#define OZ_TRAINER_PLAN_ROWS 6               /* rows 0 .. 4: layers 1 .. 5; row 5: layer 0 (conv1) */
+#define OZ_TRAINER_PLAN_FIELDS 12            /* ints per layer; [7] is reserved (0) */
 #define OZ_TRAINER_PLAN_FWD_KSLICES 0        /* forward GEMM: k-slices, then the kernel (OZ_NET_KERNEL_*: names the tile) */
 #define OZ_TRAINER_PLAN_FWD_KERNEL 1
 #define OZ_TRAINER_PLAN_DGRAD_KSLICES 2      /* data-gradient GEMM likewise */
@@ -976,6 +980,17 @@ int oz_trainer_get_activation(oz_trainer* t, int layer, int B, float* data, int6
                                               * that skips the k-tiles of taps reading only zeros; derived from the kernel the launcher reports */
 #define OZ_TRAINER_PLAN_WGRAD_KERNEL 5       /* OZ_TRAINER_WGRAD_* */
 #define OZ_TRAINER_PLAN_WGRAD_MSPLIT 6       /* row splits of the weight gradient (> 1: raw slabs + the fixed-order sum) */
+#define OZ_TRAINER_PLAN_BN_FWD 8             /* OZ_TRAINER_BN_FWD_*: the regime t_bn_forward took for the layer's BN */
+#define OZ_TRAINER_PLAN_BN_BWD 9             /* OZ_TRAINER_BN_BWD_* (t_bn_backward) */
+#define OZ_TRAINER_PLAN_BN_BWD_RS 10         /* row splits of the split BN backward (1 on the fused path) */
+#define OZ_TRAINER_PLAN_CONV1_S1 11          /* conv1's row only: row splits of k_t_conv1_wgrad */
+enum {
+    OZ_TRAINER_BN_FWD_FUSED32 = 1,           /* k_t_bn_fwd_fused<32>: up to 2048 rows */
+    OZ_TRAINER_BN_FWD_FUSED64 = 2,           /* k_t_bn_fwd_fused<64>: up to OZ_BN_FUSED_MAX_ROWS rows */
+    OZ_TRAINER_BN_FWD_STREAM = 3,            /* k_t_colreduce<0 / 1> + k_t_fin_mean / k_t_fin_var + k_t_bn_fwd */
+    OZ_TRAINER_BN_BWD_FUSED = 1,             /* k_t_bn_bwd_fused (float64 sums) */
+    OZ_TRAINER_BN_BWD_SPLIT = 2              /* k_t_colreduce<2> + k_t_bnb_apply + k_t_sum_partials */
+};
 enum {
     OZ_TRAINER_WGRAD_TAPS_F32 = 1,           /* k_wgrad_f32, one tap per block */
     OZ_TRAINER_WGRAD_BOARDS_F32 = 2,         /* k_wgrad_conv, board-resident */
@@ -988,6 +1003,8 @@ int oz_trainer_set_capture(oz_trainer* t, int on);
 int oz_trainer_get_dgrad(oz_trainer* t, int layer, int B, float* data, int64_t nelem);
 int oz_trainer_get_head_grads(oz_trainer* t, int B, float* dlogit /* [B][n*n] */, float* dvpre /* [B] */);
 int oz_trainer_get_plan(oz_trainer* t, int* plan, int n);
+int oz_trainer_get_bn_stats(oz_trainer* t, int layer, float* mean /* [Co] */, float* rstd /* [Co] */);
+int oz_trainer_get_adam_state(oz_trainer* t, int index, float* m, float* v);
 int oz_trainer_sync(oz_trainer* t);
 int oz_trainer_step_count(oz_trainer* t, int64_t* step);
 

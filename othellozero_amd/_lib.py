@@ -28,7 +28,9 @@ LEAF_IDLE, LEAF_TERMINAL, LEAF_EVAL = 0, 1, 2
 VT_INT, VT_F32, VT_F64 = 0, 1, 2
 MAX_LEAVES_PER_STEP = 16                                                             # OZ_MCTS_MAX_LEAVES_PER_STEP
 POLICY_LOSS_ROWS, POLICY_LOSS_FLAT = 0, 1                                            # oz_trainer_set_policy_loss
-TRAINER_PLAN_FIELDS = 8                                                              # OZ_TRAINER_PLAN_*: per layer 1 .. 5 of oz_trainer_get_plan
+TRAINER_PLAN_FIELDS, TRAINER_PLAN_ROWS = 12, 6                                       # OZ_TRAINER_PLAN_*: rows for layers 1 .. 5, then conv1's, of oz_trainer_get_plan
+TRAINER_BN_FWD_NAMES = {0: "none", 1: "fused32", 2: "fused64", 3: "stream"}          # OZ_TRAINER_BN_FWD_*
+TRAINER_BN_BWD_NAMES = {0: "none", 1: "fused", 2: "split"}                           # OZ_TRAINER_BN_BWD_*
 TRAINER_WGRAD_NAMES = {0: "none", 1: "taps_f32", 2: "boards_f32", 3: "oct_h2", 4: "oct_b3"}      # OZ_TRAINER_WGRAD_*
 MINIMAX_EVAL_DISCS, MINIMAX_EVAL_WEIGHTED, MINIMAX_MAX_DEPTH, MINIMAX_NONE = 0, 1, 6, -2 ** 31    # OZ_MINIMAX_*
 MINIMAX_EVALS = {"discs": MINIMAX_EVAL_DISCS, "weighted": MINIMAX_EVAL_WEIGHTED}
@@ -250,6 +252,7 @@ SIGNATURES = {
     "oz_trainer_get_preact": [_vp, C.c_int, C.c_int, _f32p, C.c_int64], "oz_trainer_get_dz": [_vp, C.c_int, C.c_int, _f32p, C.c_int64],
     "oz_trainer_set_capture": [_vp, C.c_int], "oz_trainer_get_dgrad": [_vp, C.c_int, C.c_int, _f32p, C.c_int64],
     "oz_trainer_get_plan": [_vp, _i32p, C.c_int],
+    "oz_trainer_get_bn_stats": [_vp, C.c_int, _f32p, _f32p], "oz_trainer_get_adam_state": [_vp, C.c_int, _f32p, _f32p],
     "oz_trainer_get_head_grads": [_vp, C.c_int, _f32p, _f32p],
     "oz_trainer_sync": [_vp],
     "oz_trainer_set_precision": [_vp, C.c_int],

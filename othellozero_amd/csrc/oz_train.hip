@@ -992,7 +992,7 @@ struct oz_trainer {
     // diagnostics (oz_trainer_set_capture / get_dgrad / get_plan): the raw data gradients of a step, copied out of the ping-pong buffers, and its launch plan
     bool capture = false, cap_valid = false, ran = false;      // ran: a step has been enqueued (the views below have something to show)
     float* cap[6] = {};                  // cap[l] = the gradient wrt a[l] as the heads / the data-gradient launch of layer l + 1 left it (allocated at the first capture)
-    int plan[5][OZ_TRAINER_PLAN_FIELDS] = {};
+    int plan[OZ_TRAINER_PLAN_ROWS][OZ_TRAINER_PLAN_FIELDS] = {};      // rows 0 .. 4: layers 1 .. 5, row 5: conv1 (t_plan_row)
     std::vector<void*> allocs;
     bool dirty = true;                   // derived operands need a refresh
     std::mutex mu;                       // one caller at a time (ThreadWorker-style Python threads)
@@ -1271,6 +1271,9 @@ static int t_refresh(oz_trainer* t) {
     return OZ_OK;
 }
 
+// the plan row of layer l = 0 .. 5 (conv1 has the last row: the rows of the GEMM layers keep their places)
+static int* t_plan_row(oz_trainer* t, int l) { return t->plan[l ? l - 1 : OZ_TRAINER_PLAN_ROWS - 1]; }
+
 template <int MODE>
 static int t_reduce(oz_trainer* t, RedArgs r) {
     hipLaunchKernelGGL(k_t_colreduce<MODE>, dim3((r.C / 4 + 63) / 64, RED_S), dim3(256), 0, t->s, r, t->d_count, t->partial);
@@ -1281,7 +1284,9 @@ static int t_reduce(oz_trainer* t, RedArgs r) {
 // BN (training mode) + ReLU (+ dropout) of layer l: z[l] -> a[l]
 static int t_bn_forward(oz_trainer* t, int l, int B) {
     const int Cc = t->L[l].Co, P = t->L[l].P;
+    int& regime = t_plan_row(t, l)[OZ_TRAINER_PLAN_BN_FWD];
     if ((long long)B * P <= OZ_BN_FUSED_MAX_ROWS) {      // small batch: the whole layer in one launch (oz_train_fused.h)
+        regime = (long long)B * P <= 32 * OZ_BN_RL ? OZ_TRAINER_BN_FWD_FUSED32 : OZ_TRAINER_BN_FWD_FUSED64;
         if ((long long)B * P <= 32 * OZ_BN_RL)
             hipLaunchKernelGGL(k_t_bn_fwd_fused<32>, dim3(Cc / OZ_BN_COLS), dim3(1024), 0, t->s, t->z[l], t->a[l], t->d_count, P, Cc, t->param(6 * l + 2),
                                t->param(6 * l + 3), t->mean[l], t->rstd[l], t->stats[6 * l + 4], t->stats[6 * l + 5], t->stats_new[6 * l + 4],
@@ -1293,6 +1298,7 @@ static int t_bn_forward(oz_trainer* t, int l, int B) {
         OZ_HIP(hipGetLastError());
         return OZ_OK;
     }
+    regime = OZ_TRAINER_BN_FWD_STREAM;
     RedArgs r = {}; r.x = t->z[l]; r.P = P; r.C = Cc;
     if (int rc = t_reduce<0>(t, r)) return rc;
     hipLaunchKernelGGL(k_t_fin_mean, dim3((Cc + 255) / 256), dim3(256), 0, t->s, t->partial, t->d_count, P, Cc, t->mean[l]);
@@ -1389,7 +1395,9 @@ static int t_bn_backward(oz_trainer* t, int l, int B, const float* dA) {
     const long long M = (long long)B * L.P;
     const float post = l >= 4 && t->rate > 0.f ? 1.0f / (1.0f - t->rate) : 1.0f;
     unsigned* dzmax = t->mode == 1 ? t->dzmax + l : nullptr;
+    int* const plan = t_plan_row(t, l);
     if (M <= OZ_BNB_MIN_ROWS) {         // small batch: BN backward, dgamma / dbeta / bias gradient in one launch
+        plan[OZ_TRAINER_PLAN_BN_BWD] = OZ_TRAINER_BN_BWD_FUSED; plan[OZ_TRAINER_PLAN_BN_BWD_RS] = 1;
         hipLaunchKernelGGL(k_t_bn_bwd_fused, dim3(Cc / OZ_BN_COLS), dim3(1024), 0, s, dA, t->a[l], t->z[l], t->rstd[l],
                            t->param(6 * l + 2), post, t->d_count, L.Hout, Cc, L.Hz, L.zoff, t->dz[l], t->grad(6 * l + 2),
                            t->grad(6 * l + 3), t->grad(6 * l + 1), dzmax);
@@ -1399,6 +1407,7 @@ static int t_bn_backward(oz_trainer* t, int l, int B, const float* dA) {
     // partial sums over row splits, then one launch that finishes the sums and writes dz (oz_train_fused.h)
     const int Q = Cc / 4, lpr = Q < 64 ? Q : 64, rpp = 256 / lpr;
     int RS = 16; while (RS < OZ_BNB_MAX_RB && M > (long long)RS * rpp * 8) RS *= 2;          // ~8 rows per thread
+    plan[OZ_TRAINER_PLAN_BN_BWD] = OZ_TRAINER_BN_BWD_SPLIT; plan[OZ_TRAINER_PLAN_BN_BWD_RS] = RS;
     RedArgs r = {}; r.x = dA; r.a = t->a[l]; r.z = t->z[l]; r.mean = t->mean[l]; r.rstd = t->rstd[l]; r.post_scale = post; r.P = L.P; r.C = Cc;
     hipLaunchKernelGGL(k_t_colreduce<2>, dim3((Q + 63) / 64, RS), dim3(256), 0, s, r, t->d_count, t->partial);
     hipLaunchKernelGGL(k_t_bnb_apply, dim3((Q + 63) / 64, RS), dim3(256), 0, s, dA, t->a[l], t->z[l], t->mean[l], t->rstd[l], t->param(6 * l + 2),
@@ -1421,6 +1430,7 @@ static int t_wgrad_conv1(oz_trainer* t, int B) {
     const int n = t->n, C = t->C;
     int S1 = 8;                                    // row splits: ~16 rows per thread (each a dependent ~1 us load at small batch), at most RED_S (the partial buffer's capacity)
     while (S1 < RED_S && (long long)B * n * n > 16LL * S1) S1 *= 2;
+    t_plan_row(t, 0)[OZ_TRAINER_PLAN_CONV1_S1] = S1;
     if (n == 8) hipLaunchKernelGGL(k_t_conv1_wgrad<8>, dim3((C + 255) / 256, S1), dim3(256), 0, s, t->d_own, t->d_opp, t->d_count, C, t->cin, t->dz[0], t->partial, S1);
     else hipLaunchKernelGGL(k_t_conv1_wgrad<6>, dim3((C + 255) / 256, S1), dim3(256), 0, s, t->d_own, t->d_opp, t->d_count, C, t->cin, t->dz[0], t->partial, S1);
     const long long cnt = 9LL * t->cin * C;
@@ -1803,8 +1813,22 @@ OZ_API int oz_trainer_get_head_grads(oz_trainer* t, int B, float* dlogit, float*
     return t_read(t, t->dvpre, dvpre, B);
 }
 OZ_API int oz_trainer_get_plan(oz_trainer* t, int* plan, int n) {
-    OZ_REQUIRE(t && plan && n == 5 * OZ_TRAINER_PLAN_FIELDS, "oz_trainer_get_plan: plan holds 5 x OZ_TRAINER_PLAN_FIELDS ints");
+    OZ_REQUIRE(t && plan && n == OZ_TRAINER_PLAN_ROWS * OZ_TRAINER_PLAN_FIELDS, "oz_trainer_get_plan: plan holds OZ_TRAINER_PLAN_ROWS x OZ_TRAINER_PLAN_FIELDS ints");
     T_LOCK(t);
     memcpy(plan, t->plan, sizeof t->plan);
     return OZ_OK;
+}
+OZ_API int oz_trainer_get_bn_stats(oz_trainer* t, int layer, float* mean, float* rstd) {
+    OZ_REQUIRE(t && mean && rstd && layer >= 0 && layer < 6, "oz_trainer_get_bn_stats: bad argument");
+    T_LOCK(t);
+    if (int rc = t_need_step(t, "oz_trainer_get_bn_stats")) return rc;
+    if (int rc = t_read(t, t->mean[layer], mean, t->L[layer].Co)) return rc;
+    return t_read(t, t->rstd[layer], rstd, t->L[layer].Co);
+}
+OZ_API int oz_trainer_get_adam_state(oz_trainer* t, int index, float* m, float* v) {
+    OZ_REQUIRE(t && m && v && index >= 0 && index < 40, "oz_trainer_get_adam_state: bad argument");
+    T_LOCK(t);
+    OZ_REQUIRE(t->toff[index] >= 0, "oz_trainer_get_adam_state: array %d is a moving statistic, it has no moments", index);
+    if (int rc = t_read(t, t->M1 + t->toff[index], m, t->size[index])) return rc;
+    return t_read(t, t->V2 + t->toff[index], v, t->size[index]);
 }

@@ -186,17 +186,36 @@ class Trainer:
         _lib.check(_lib.load().oz_trainer_get_head_grads(self._h, B, _lib.p_f32(dl), _lib.p_f32(dv)))
         return dl, dv
 
+    def bn_stats(self, layer):
+        """(mean, rstd) of the batch as the BN forward of `layer` (0 .. 5) left them: rstd = 1 / sqrt(biased variance + 1e-3)"""
+        co = self._layer_shape(layer)[2]
+        mean, rstd = np.zeros(co, np.float32), np.zeros(co, np.float32)
+        _lib.check(_lib.load().oz_trainer_get_bn_stats(self._h, layer, _lib.p_f32(mean), _lib.p_f32(rstd)))
+        return mean, rstd
+
+    def adam_state(self, index):
+        """(m, v): the two Adam moments of trainable array `index` (get_weights() order)"""
+        m, v = np.zeros(self.shapes[index], np.float32), np.zeros(self.shapes[index], np.float32)
+        _lib.check(_lib.load().oz_trainer_get_adam_state(self._h, index, _lib.p_f32(m), _lib.p_f32(v)))
+        return m, v
+
     def plan(self):
-        """{layer 1 .. 5: dict(fwd_kernel, fwd_kslices, dgrad_kernel, dgrad_kslices, dgrad_tap_skip, wgrad_kernel, wgrad_msplit)} of the last step,
-        as the launchers reported it (oz_trainer_get_plan)"""
+        """{layer 1 .. 5: dict(fwd_kernel, fwd_kslices, dgrad_kernel, dgrad_kslices, dgrad_tap_skip, wgrad_kernel, wgrad_msplit, bn_fwd, bn_bwd,
+        bn_bwd_rs), 0 (conv1, no GEMM): dict(bn_fwd, bn_bwd, bn_bwd_rs, conv1_s1)} of the last step, as the launchers reported it
+        (oz_trainer_get_plan); bn_fwd: fused32 / fused64 / stream, bn_bwd: fused / split"""
         F = _lib.TRAINER_PLAN_FIELDS
-        v = np.zeros(5 * F, np.int32)
+        v = np.zeros(_lib.TRAINER_PLAN_ROWS * F, np.int32)
         _lib.check(_lib.load().oz_trainer_get_plan(self._h, _lib.p_i32(v), v.size))
         out = {}
-        for l in range(1, 6):
-            f = [int(x) for x in v[(l - 1) * F:l * F]]
-            out[l] = dict(fwd_kslices=f[0], fwd_kernel=_lib.NET_KERNEL_NAMES[f[1]], dgrad_kslices=f[2], dgrad_kernel=_lib.NET_KERNEL_NAMES[f[3]],
-                          dgrad_tap_skip=bool(f[4]), wgrad_kernel=_lib.TRAINER_WGRAD_NAMES[f[5]], wgrad_msplit=f[6])
+        for l in range(6):
+            row = l - 1 if l else _lib.TRAINER_PLAN_ROWS - 1
+            f = [int(x) for x in v[row * F:(row + 1) * F]]
+            bn = dict(bn_fwd=_lib.TRAINER_BN_FWD_NAMES[f[8]], bn_bwd=_lib.TRAINER_BN_BWD_NAMES[f[9]], bn_bwd_rs=f[10])
+            if l == 0:
+                out[l] = dict(bn, conv1_s1=f[11])
+            else:
+                out[l] = dict(fwd_kslices=f[0], fwd_kernel=_lib.NET_KERNEL_NAMES[f[1]], dgrad_kslices=f[2], dgrad_kernel=_lib.NET_KERNEL_NAMES[f[3]],
+                              dgrad_tap_skip=bool(f[4]), wgrad_kernel=_lib.TRAINER_WGRAD_NAMES[f[5]], wgrad_msplit=f[6], **bn)
         return out
 
     @property
