@@ -1008,6 +1008,70 @@ int oz_trainer_get_adam_state(oz_trainer* t, int index, float* m, float* v);
 int oz_trainer_sync(oz_trainer* t);
 int oz_trainer_step_count(oz_trainer* t, int64_t* step);
 
+/* ---- optimiser options (opt-in; with none set oz_trainer_apply launches k_t_adam as before and every weight, moment, loss and file is unchanged)
+ * What AlphaZero's objective (z - v)^2 - pi^T log p + c |theta|^2 and KataGo's training add to plain Adam with clipvalue: an L2 term or a
+ * decoupled weight decay, a learning-rate schedule, a clip of the gradient's global norm and an exponential moving average of the weights.  They
+ * live here, behind oz_trainer_apply, because oz_trainer_fit_epoch / _replay run every optimiser step of an epoch back to back on the device:
+ * there is no host hook between two steps.
+ *
+ * ONE STEP, PER ELEMENT, IN THIS ORDER (the definition; G = the gradient arena as backward -- or a data-parallel job's all-reduce -- left it):
+ *   1. g = G * s                            s = min(1, global_clipnorm / |G|_2), as float32; 1 with the clip off
+ *   2. g += 2 c w                           decayed arrays only (l2 = c; the factor enters as the float32 rounding of 2 c)
+ *   3. g = clip(g, -clipvalue, clipvalue)   oz_trainer_create's clipvalue
+ *   4. m = 0.9 m + 0.1 g, v = 0.999 v + 0.001 g g            as before
+ *   5. w_new = (w - lr_t m / (sqrt(v) + 1e-7)) - (lr_s lambda) w      the last term on decayed arrays only (weight_decay = lambda; the product
+ *                                           lr_s lambda is formed in double and enters as its float32 rounding)
+ *   6. E = d E + (1 - d) w_new              average_decay = d; d and 1 - d (formed in double) enter as their float32 roundings
+ * |G|_2 is taken over every trainable element of the arena, the padding between arrays excluded.  THE L2 TERM IS NOT PART OF THE CLIPPED NORM:
+ * the norm pass reads G alone (one streaming read), and the clip bounds the data gradient, not the regulariser.  The norm is GLOBAL, one
+ * number per step (Keras' clipnorm is per variable; its global_clipnorm is this one).  It is a two-stage sum in float64 whose partial sums are
+ * combined in a fixed order, without floating-point atomics: a step is bit-reproducible from run to run.
+ * The rate of step s (1-based count of the step being applied) is lr_s = lr * f(s), in double on the host (oz_lr_schedule_at is the one
+ * definition; oz_trainer_apply calls it):  s <= warmup_steps: f = s / warmup_steps;  otherwise q = min(1, (s - warmup_steps) /
+ * max(1, total_steps - warmup_steps)) and  OZ_LR_CONSTANT: f = 1;  OZ_LR_LINEAR: f = 1 - (1 - r) q;  OZ_LR_COSINE: f = r + (1 - r) (1 + cos(pi q)) / 2,
+ * r = final_ratio.  lr_t = lr_s sqrt(1 - 0.999^s) / (1 - 0.9^s) is then formed and rounded to float32 as before.
+ * decay_mask: bit i selects get_weights() index i; 0 = the default, the eight kernels (indices 0, 6, .., 30, 36, 38: no bias, gamma or beta).
+ * The average E (+ one arena, 64 MB at 512 filters) is allocated only when average_decay is on, seeded with the weights when it is switched on,
+ * and re-seeded by oz_trainer_set_weight for the trainable array that call writes.  The BN moving statistics are not averaged.
+ * Refused with OZ_ERR_ARG: a negative or NaN l2 / weight_decay / global_clipnorm, l2 and weight_decay both positive, average_decay outside [0, 1)
+ * (0 = off), an unknown schedule, final_ratio outside [0, 1], negative warmup_steps / total_steps, warmup_steps > total_steps for a LINEAR or
+ * COSINE schedule (CONSTANT does not look at total_steps), a mask bit >= 40 or on a moving statistic (6 l + 4, 6 l + 5). */
+#define OZ_LR_CONSTANT 0
+#define OZ_LR_LINEAR 1
+#define OZ_LR_COSINE 2
+typedef struct {
+    double l2;                 /* c >= 0; 0 = off */
+    double weight_decay;       /* lambda >= 0, decoupled (AdamW); 0 = off */
+    uint64_t decay_mask;       /* 0 = the default mask */
+    double global_clipnorm;    /* > 0 switches the global-norm clip on */
+    double average_decay;      /* d in (0, 1) switches the weight average on */
+    int32_t schedule;          /* OZ_LR_* */
+    int32_t reserved;          /* 0 */
+    int64_t warmup_steps, total_steps;
+    double final_ratio;        /* r in [0, 1] */
+} oz_optimizer;
+/* opt == NULL: everything off (what a trainer starts with).  Takes effect at the next apply; the step count is not touched. */
+int oz_trainer_set_optimizer(oz_trainer* t, const oz_optimizer* opt);
+int oz_trainer_get_optimizer(oz_trainer* t, oz_optimizer* opt);
+int oz_trainer_set_lr(oz_trainer* t, float lr);              /* the base rate `lr`, from the next apply on */
+/* *out = lr_s of step `step` (>= 1) under `opt` (NULL: lr).  Pure host function, no GPU needed; validates the whole struct (list above). */
+int oz_lr_schedule_at(const oz_optimizer* opt, float lr, int64_t step, double* out);
+/* the last applied step: its lr_s, and -- valid with global_clipnorm on, else 0 and 1 -- |G|_2 and s (the double the float32 factor was rounded
+ * from).  Waits for the stream.  OZ_ERR_STATE before the first apply. */
+int oz_trainer_get_step_info(oz_trainer* t, double* lr_s, double* grad_norm, double* clip_scale);
+/* E of a trainable array; the current value of a moving statistic.  OZ_ERR_STATE with the average off. */
+int oz_trainer_get_weight_average(oz_trainer* t, int index, float* data, int64_t nelem);
+/* on demand, the same reduction kernels: the sum of squares of the gradient arena's array elements (OZ_SQSUM_GRADIENTS) or of the decayed
+ * arrays' weights (OZ_SQSUM_DECAYED_WEIGHTS, under the current or default mask: c * this is the L2 term of the objective).  Waits for the stream.
+ * The three loss numbers of a step or an epoch stay the data losses. */
+#define OZ_SQSUM_GRADIENTS 0
+#define OZ_SQSUM_DECAYED_WEIGHTS 1
+int oz_trainer_sqsum(oz_trainer* t, int what, double* out);
+/* Benchmark hook: mean HIP-event milliseconds of `iters` back-to-back launches of the step's optimiser kernel (ms3[0]: k_t_adam with the options
+ * off, k_t_adam_x otherwise) and of the norm's two kernels (ms3[1]; 0 with global_clipnorm off); ms3[2] is reserved (0).  The launches are real:
+ * weights, moments and average move as under `iters` steps on the arena as it stands (the step count does not) -- for a scratch trainer. */
+int oz_trainer_time_optimizer(oz_trainer* t, int iters, double* ms3);
+
 /* ------------------------------------------------------------------ replay buffer (opt-in; without it every result, record and file is unchanged)
  * Finished training examples RESIDENT on the device, between the self-play engines that produce them and the trainer that consumes them:
  * the replacement, for callers that ask for it, of the host's list of example tuples (main.py:21-53 CircularArray, training.py:58-72).

@@ -41,7 +41,7 @@ class NNetWrapper(_NetHandle):
 
     def __init__(self, board_size=(8, 8), batch_size=32, epochs=10, num_channels_1=512, num_channels_2=256,
                  lr=0.001, dropout=0.3, network=NeuralNets.ONN, max_batch=1, seed=0, weights=None, precision="f32", train_precision=None,
-                 policy_loss="rows"):
+                 policy_loss="rows", optimizer=None):
         super().__init__()
         self._model_index = NNetWrapper._models_built
         NNetWrapper._models_built += 1
@@ -72,6 +72,18 @@ class NNetWrapper(_NetHandle):
         # whole n*n softmax, what dense visit-distribution targets need (loop.training(policy_target="visits"))
         assert policy_loss in ("rows", "flat"), policy_loss
         self.policy_loss = policy_loss
+        # optimizer: None or a dict of Trainer.set_optimizer's options (l2, weight_decay, decay_mask, global_clipnorm, average_decay, schedule) plus
+        # use_average -- train() then commits the trainer's weight AVERAGE to this network (self-play, matches and checkpoints run on it) while the
+        # trainer keeps its raw iterate.  Part of the network object: copy() carries the settings (not the optimiser's state), and
+        # loop.training needs no parameter for them
+        self.optimizer = dict(optimizer) if optimizer else None
+        if self.optimizer:
+            from .trainer import OPTIMIZER_KEYS
+            unknown = set(self.optimizer) - set(OPTIMIZER_KEYS) - {"use_average"}
+            assert not unknown, f"optimizer: unknown option(s) {sorted(unknown)}"
+            assert not self.optimizer.get("use_average") or self.optimizer.get("average_decay", 0) > 0, "use_average needs average_decay in (0, 1)"
+        self._weights_version = 0                     # counts set_weights / init_random: train() re-seeds its trainer when somebody else set the weights
+        self._exported_version = None                 # the version train() itself left behind
         self.requested_precision = precision          # what the caller asked for: a refused f16x2 commit falls back for THAT set of weights only
         self.f16x2_refusals = 0                       # commits precision f16x2 refused so far (train() reports it in its history)
         _lib.check(lib.oz_net_set_precision(self._h, PRECISION_MODES[precision]))
@@ -86,6 +98,7 @@ class NNetWrapper(_NetHandle):
         precision f32 (exact fp32 kernels on the GPU, always valid) and commits again -- what train() uses, so that a long f16x2 run is not
         ended by the weights of one iteration."""
         lib = _lib.load()
+        self._weights_version += 1
         if self.precision != self.requested_precision:        # an earlier set of weights was refused: THIS one gets the requested arithmetic again
             _lib.check(lib.oz_net_set_precision(self._h, PRECISION_MODES[self.requested_precision]))
             self.precision = self.requested_precision
@@ -112,6 +125,7 @@ class NNetWrapper(_NetHandle):
         """a fresh network as Keras initialises it (glorot_uniform kernels, zero biases, identity BatchNormalization) from the LIBRARY's own
         deterministic stream (oz_net_init_random: what a C host gets; not NumPy's numbers for that seed), committed"""
         lib = _lib.load()
+        self._weights_version += 1
         _lib.check(lib.oz_net_init_random(self._h, int(seed)))
         _lib.check(lib.oz_net_commit(self._h))
 
@@ -159,7 +173,8 @@ class NNetWrapper(_NetHandle):
         (oz_trainer_*: MFMA forward / backward in the wrapper's precision -- "f16x2" runs the 3x3 layers' forward and data
         gradient on the fp16 matrix cores like the inference kernels (needs num_channels % 256 == 0, else fp32); train_precision="bf16x3"
         runs their forward and both gradients as three bf16 planes per fp32 value (fp32-class, no scaling, no guard) -- Adam
-        lr=self.lr with clipvalue 0.5 for ONN / none for BNN, Dropout self.dropout, BN momentum 0.99).  Returns a History-like object (`.history['loss']`, ...).  The TensorBoard
+        lr=self.lr with clipvalue 0.5 for ONN / none for BNN, Dropout self.dropout, BN momentum 0.99; the wrapper's `optimizer` options act inside
+        every step; with use_average the network receives the weight average after the fit).  Returns a History-like object (`.history['loss']`, ...).  The TensorBoard
         callback of the reference is not reproduced.  Optimiser state persists across calls like the compiled Keras model's."""
         from . import trainer as T
         from .replay import ReplayBuffer
@@ -183,11 +198,21 @@ class NNetWrapper(_NetHandle):
                                       clipvalue=0.5 if self.network_type is NeuralNets.ONN else 0.0, dropout=self.dropout,
                                       seed=self._model_index if seed is None else seed,
                                       external_grads_ptr=getattr(allreduce, "ptr", None),
-                                      precision=self._train_arithmetic(), policy_loss=self.policy_loss)
+                                      precision=self._train_arithmetic(), policy_loss=self.policy_loss,
+                                      optimizer={k: v for k, v in (self.optimizer or {}).items() if k != "use_average"})
             self._trainer_arena = getattr(allreduce, "ptr", None)
             self._fit_calls = 0
+            self._exported_version = None
         assert getattr(allreduce, "ptr", None) == self._trainer_arena, "train() must keep using the GradientAllReduce it started with"
-        self._trainer.set_weights(self.get_weights())
+        if not self.optimizer or self._exported_version != self._weights_version:
+            # (without options: as ever.)  Somebody else set the network's weights: the trainer (and its average) starts from them
+            self._trainer.set_weights(self.get_weights())
+        elif allreduce is not None:
+            # nobody has: the trainer keeps its raw iterate, moments and average; only the moving statistics the ranks averaged go back in
+            mine = self.get_weights()
+            for i in range(36):
+                if i % 6 in (4, 5):
+                    _lib.check(_lib.load().oz_trainer_set_weight(self._trainer._h, i, _lib.p_f32(mine[i]), mine[i].size))
         shuffle_seed = 1000003 * self._fit_calls + (self._model_index if seed is None else seed)
         if replay is not None:
             hist = T.fit_replay(self._trainer, replay, batch_size=self.batch_size, epochs=self.epochs, shuffle_seed=shuffle_seed, verbose=verbose)
@@ -195,7 +220,8 @@ class NNetWrapper(_NetHandle):
             hist = T.fit(self._trainer, own, opp, pi, z, batch_size=self.batch_size, epochs=self.epochs, shuffle_seed=shuffle_seed,
                          allreduce=allreduce, verbose=verbose)
         self._fit_calls += 1
-        weights = self._trainer.get_weights()
+        use_average = bool(self.optimizer and self.optimizer.get("use_average"))
+        weights = self._trainer.get_weights(average=use_average)
         if allreduce is not None:                       # BN moving statistics are per replica: average them
             from .distributed import average_moving_statistics
             weights = average_moving_statistics(weights, getattr(allreduce, "group", None))
@@ -210,6 +236,7 @@ class NNetWrapper(_NetHandle):
                 _lib.check(lib.oz_net_set_precision(self._h, PRECISION_MODES["f32"]))
                 self.precision = "f32"
                 _lib.check(lib.oz_net_commit(self._h))
+        self._exported_version = self._weights_version
         hist.precision = self.precision                     # the arithmetic these weights are evaluated in until the next set_weights
         hist.train_precision = self._trainer.precision      # the arithmetic the trainer's 3x3 layers ran in
         hist.f16x2_refusals = self.f16x2_refusals           # (attributes, not history entries: Keras' history holds per-epoch number lists only)
@@ -249,7 +276,8 @@ class NNetWrapper(_NetHandle):
     def copy(self):
         net = NNetWrapper((self.board_size_x, self.board_size_y), network=self.network_type,
                           num_channels_1=self.num_channels, max_batch=self.max_batch, weights=self.get_weights(),
-                          precision=self.precision, train_precision=self.train_precision, policy_loss=self.policy_loss)
+                          precision=self.precision, train_precision=self.train_precision, policy_loss=self.policy_loss,
+                          optimizer=self.optimizer)
         mode, seed = self.eval_symmetry()
         if mode != "off" or seed:
             net.set_eval_symmetry(mode, seed)          # the evaluation symmetry is part of the network

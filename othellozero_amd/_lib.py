@@ -86,6 +86,18 @@ class ValueTargetStats(C.Structure):                                            
     _fields_ = [("records", C.c_int64), ("exact", C.c_int64), ("sign_changed", C.c_int64)]
 
 
+class Optimizer(C.Structure):                                                        # oz_optimizer
+    _fields_ = [
+        ("l2", C.c_double), ("weight_decay", C.c_double), ("decay_mask", C.c_uint64), ("global_clipnorm", C.c_double),
+        ("average_decay", C.c_double), ("schedule", C.c_int32), ("reserved", C.c_int32), ("warmup_steps", C.c_int64),
+        ("total_steps", C.c_int64), ("final_ratio", C.c_double),
+    ]
+
+
+LR_SCHEDULES = {"constant": 0, "linear": 1, "cosine": 2}                             # OZ_LR_*
+SQSUM_KINDS = {"gradients": 0, "weights": 1}                                         # OZ_SQSUM_GRADIENTS / OZ_SQSUM_DECAYED_WEIGHTS
+
+
 # numpy view of oz_record (48 bytes)
 RECORD_DTYPE = np.dtype([
     ("black", "<u8"), ("white", "<u8"), ("final_black", "<u8"), ("final_white", "<u8"), ("game_id", "<u8"),
@@ -258,6 +270,13 @@ SIGNATURES = {
     "oz_trainer_set_precision": [_vp, C.c_int],
     "oz_trainer_set_policy_loss": [_vp, C.c_int],
     "oz_trainer_step_count": [_vp, C.POINTER(C.c_int64)],
+    "oz_trainer_set_optimizer": [_vp, C.POINTER(Optimizer)], "oz_trainer_get_optimizer": [_vp, C.POINTER(Optimizer)],
+    "oz_trainer_set_lr": [_vp, C.c_float],
+    "oz_lr_schedule_at": [C.POINTER(Optimizer), C.c_float, C.c_int64, C.POINTER(C.c_double)],
+    "oz_trainer_get_step_info": [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)],
+    "oz_trainer_get_weight_average": [_vp, C.c_int, _f32p, C.c_int64],
+    "oz_trainer_sqsum": [_vp, C.c_int, C.POINTER(C.c_double)],
+    "oz_trainer_time_optimizer": [_vp, C.c_int, _f64p],
     "oz_replay_create": [C.POINTER(_vp), C.c_int, C.c_int64], "oz_replay_destroy": [_vp], "oz_replay_clear": [_vp],
     "oz_replay_info": [_vp, _i64p, _i64p, _i64p],
     "oz_replay_append_selfplay": [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_double, _i64p],

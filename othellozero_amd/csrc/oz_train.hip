@@ -936,6 +936,87 @@ __global__ __launch_bounds__(256) void k_t_adam(float* __restrict__ P, const flo
     P[i] -= lr_t * m / (sqrtf(v) + 1e-7f);
 }
 
+// ---------------------------------------------------------------- optimiser options (oz_trainer_set_optimizer): the fused step and the norm
+// The arena as 16-byte units: every array starts on one and is padded to whole ones (t_layout), so a unit never straddles two arrays.  The
+// decayed arrays reach the kernel as at most T_OPT_SEGS merged unit ranges, BY VALUE in the kernel arguments: the range loop's index is uniform,
+// so the bounds are scalar loads and the test costs two compares per range and unit (eight ranges under the default mask) beside nine 16-byte
+// streams -- no table in memory, no per-lane indexing of the arguments (which would go to scratch).
+#define T_OPT_SEGS 28                        // trainable arrays of the network
+struct TUnitRanges { int n; int lo[T_OPT_SEGS], hi[T_OPT_SEGS]; };             // units [lo, hi)
+struct TSegs { int n; long long off[T_OPT_SEGS], len[T_OPT_SEGS]; };           // arrays: offset in the arena (floats, a multiple of 4) and ELEMENT count
+struct TAdamX { float lr_t, clip, c2 /* 2 c */, lam /* lr_s lambda */, d, omd /* 1 - d */; };
+struct TNormOut { double sumsq, norm, scale; float scale32, pad; };
+#define T_OPT_ADAM_BLOCKS 2048               // grid caps: the rest is grid-stride
+#define T_OPT_SQ_BLOCKS 1024
+
+// one element of the six-step order in the header; what it shares with k_t_adam is spelled as there (bit-identical where no option acts)
+__device__ __forceinline__ void t_adam_x_elem(float& p, float g, float& m1, float& v2, float& e, bool scaled, float s, bool dec, bool avg, const TAdamX& a) {
+    if (scaled) g = g * s;
+    if (dec && a.c2 > 0.f) g = g + a.c2 * p;
+    if (a.clip > 0.f) g = fminf(fmaxf(g, -a.clip), a.clip);
+    const float m = 0.9f * m1 + 0.1f * g;
+    const float v = 0.999f * v2 + 0.001f * g * g;
+    m1 = m; v2 = v;
+    float w = p - a.lr_t * m / (sqrtf(v) + 1e-7f);
+    if (dec && a.lam > 0.f) w = w - a.lam * p;
+    p = w;
+    if (avg) e = a.d * e + a.omd * w;
+}
+__global__ __launch_bounds__(256) void k_t_adam_x(float4* __restrict__ P, const float4* __restrict__ G, float4* __restrict__ M1, float4* __restrict__ V2,
+                                                  float4* __restrict__ E /* nullptr: no average */, int units, TAdamX a,
+                                                  const float* __restrict__ scale /* nullptr: no global-norm clip */, TUnitRanges decay) {
+    const bool scaled = scale != nullptr, avg = E != nullptr;
+    const float s = scaled ? *scale : 1.0f;
+    for (int q = blockIdx.x * 256 + threadIdx.x; q < units; q += gridDim.x * 256) {
+        bool dec = false;
+        for (int r = 0; r < decay.n; ++r) dec |= q >= decay.lo[r] && q < decay.hi[r];
+        float4 p = P[q], m = M1[q], v = V2[q], e = avg ? E[q] : make_float4(0.f, 0.f, 0.f, 0.f);
+        const float4 g = G[q];
+        t_adam_x_elem(p.x, g.x, m.x, v.x, e.x, scaled, s, dec, avg, a);
+        t_adam_x_elem(p.y, g.y, m.y, v.y, e.y, scaled, s, dec, avg, a);
+        t_adam_x_elem(p.z, g.z, m.z, v.z, e.z, scaled, s, dec, avg, a);
+        t_adam_x_elem(p.w, g.w, m.w, v.w, e.w, scaled, s, dec, avg, a);
+        P[q] = p; M1[q] = m; V2[q] = v;
+        if (avg) E[q] = e;
+    }
+}
+
+// Sum of squares of the ELEMENTS of the listed arrays (the padding behind an array is never read into the sum), float64, two stages, every
+// partial sum combined in a fixed order (no atomics): thread -> wave (shuffle tree) -> block (the four wave sums in order) -> partial[block];
+// then one block adds the partials, thread i taking i, i + 256, .., and finishes.
+__device__ __forceinline__ double t_block_sum(double acc, double* sh) {
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    return sh[0] + sh[1] + sh[2] + sh[3];
+}
+__global__ __launch_bounds__(256) void k_t_sqsum(const float* __restrict__ X, TSegs sg, double* __restrict__ partial) {
+    __shared__ double sh[4];
+    const int tid = blockIdx.x * 256 + threadIdx.x, nth = gridDim.x * 256;
+    double acc = 0.0;
+    for (int r = 0; r < sg.n; ++r) {
+        const float* x = X + sg.off[r];
+        const long long len = sg.len[r], n4 = len >> 2;
+        for (long long q = tid; q < n4; q += nth) {
+            const float4 f = reinterpret_cast<const float4*>(x)[q];
+            acc += (double)f.x * (double)f.x; acc += (double)f.y * (double)f.y; acc += (double)f.z * (double)f.z; acc += (double)f.w * (double)f.w;
+        }
+        if (tid == 0) for (long long i = n4 * 4; i < len; ++i) acc += (double)x[i] * (double)x[i];      // the array's last, partial unit
+    }
+    const double sum = t_block_sum(acc, sh);
+    if (threadIdx.x == 0) partial[blockIdx.x] = sum;
+}
+__global__ __launch_bounds__(256) void k_t_sqsum_fin(const double* __restrict__ partial, int count, double clipnorm, TNormOut* __restrict__ out) {
+    __shared__ double sh[4];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < count; i += 256) acc += partial[i];
+    const double sum = t_block_sum(acc, sh);
+    if (threadIdx.x == 0) {
+        const double norm = sqrt(sum), sc = clipnorm > 0.0 && norm > clipnorm ? clipnorm / norm : 1.0;
+        out->sumsq = sum; out->norm = norm; out->scale = sc; out->scale32 = (float)sc; out->pad = 0.f;
+    }
+}
+
 // ---------------------------------------------------------------- host object
 // Layer l = 0 .. 5 (conv1 .. conv4, fc1, fc2) as the step sees it: the GEMM shape (conv1 is no GEMM: its Cin is the input planes), P = Hout^2
 // output pixels, and the dz buffer's geometry -- conv3 / conv4 ('valid') keep dz in a zero-bordered Hz x Hz buffer (zoff = 2) so that their data
@@ -993,6 +1074,16 @@ struct oz_trainer {
     bool capture = false, cap_valid = false, ran = false;      // ran: a step has been enqueued (the views below have something to show)
     float* cap[6] = {};                  // cap[l] = the gradient wrt a[l] as the heads / the data-gradient launch of layer l + 1 left it (allocated at the first capture)
     int plan[OZ_TRAINER_PLAN_ROWS][OZ_TRAINER_PLAN_FIELDS] = {};      // rows 0 .. 4: layers 1 .. 5, row 5: conv1 (t_plan_row)
+    // optimiser options (oz_trainer_set_optimizer).  fused: one of l2 / weight_decay / global_clipnorm / average_decay is on and the step runs
+    // k_t_adam_x; otherwise t_apply_locked launches k_t_adam as it always did (a schedule alone only changes lr_t)
+    oz_optimizer opt = {};
+    bool fused = false, applied = false, last_clipped = false;
+    float* E = nullptr;                  // the weight average: one more arena, allocated when average_decay is first switched on
+    double* sq_partial = nullptr;        // T_OPT_SQ_BLOCKS partial sums of k_t_sqsum
+    TNormOut* norm_out = nullptr;        // [0]: the last step's norm and scale (k_t_adam_x reads scale32), [1]: oz_trainer_sqsum's
+    double last_lr_s = 0.0;
+    TSegs seg_all = {}, seg_dec = {};    // the trainable arrays; the decayed ones (current or default mask)
+    TUnitRanges dec_units = {};
     std::vector<void*> allocs;
     bool dirty = true;                   // derived operands need a refresh
     std::mutex mu;                       // one caller at a time (ThreadWorker-style Python threads)
@@ -1042,6 +1133,69 @@ static int t_alloc(oz_trainer* t, void** out, size_t bytes, bool zero = true) {
 #define T_LOCK(t) std::lock_guard<std::mutex> lock__((t)->mu)
 #define T_ALLOC(ptr, count) do { if (int rc__ = t_alloc(t, (void**)&(ptr), (size_t)(count) * sizeof(*(ptr)))) return rc__; } while (0)
 
+// ---------------------------------------------------------------- optimiser options: validation, the schedule (host only), the segment tables
+static bool t_is_stat(int i) { return i < 36 && (i % 6 == 4 || i % 6 == 5); }
+static uint64_t t_decay_mask(const oz_optimizer& o) {            // 0 = the default: the eight kernels
+    if (o.decay_mask) return o.decay_mask;
+    uint64_t m = (1ull << 36) | (1ull << 38);
+    for (int l = 0; l < 6; ++l) m |= 1ull << (6 * l);
+    return m;
+}
+static int t_opt_check(const oz_optimizer* o, const char* who) {
+    if (!o) return OZ_OK;
+    OZ_REQUIRE(o->l2 >= 0.0 && std::isfinite(o->l2), "%s: l2 %g (>= 0)", who, o->l2);
+    OZ_REQUIRE(o->weight_decay >= 0.0 && std::isfinite(o->weight_decay), "%s: weight_decay %g (>= 0)", who, o->weight_decay);
+    OZ_REQUIRE(!(o->l2 > 0.0 && o->weight_decay > 0.0), "%s: l2 and weight_decay are both positive (one decay at a time)", who);
+    OZ_REQUIRE(o->global_clipnorm >= 0.0 && std::isfinite(o->global_clipnorm), "%s: global_clipnorm %g (>= 0)", who, o->global_clipnorm);
+    OZ_REQUIRE(o->average_decay >= 0.0 && o->average_decay < 1.0, "%s: average_decay %g outside [0, 1)", who, o->average_decay);
+    OZ_REQUIRE(o->schedule == OZ_LR_CONSTANT || o->schedule == OZ_LR_LINEAR || o->schedule == OZ_LR_COSINE, "%s: schedule %d", who, (int)o->schedule);
+    OZ_REQUIRE(o->final_ratio >= 0.0 && o->final_ratio <= 1.0, "%s: final_ratio %g outside [0, 1]", who, o->final_ratio);
+    OZ_REQUIRE(o->warmup_steps >= 0 && o->total_steps >= 0, "%s: negative warmup_steps / total_steps", who);
+    OZ_REQUIRE(o->schedule == OZ_LR_CONSTANT || o->warmup_steps <= o->total_steps, "%s: warmup_steps %lld > total_steps %lld", who,
+               (long long)o->warmup_steps, (long long)o->total_steps);
+    OZ_REQUIRE(!(o->decay_mask >> 40), "%s: decay_mask has a bit past get_weights() index 39", who);
+    for (int i = 0; i < 40; ++i)
+        OZ_REQUIRE(!((o->decay_mask >> i) & 1) || !t_is_stat(i), "%s: decay_mask bit %d is a BN moving statistic (not trained, not decayed)", who, i);
+    return OZ_OK;
+}
+// lr_s = lr f(s): the one definition (othellozero_amd.h); `o` is valid or NULL
+static double t_lr_at(const oz_optimizer* o, float lr, int64_t step) {
+    const double base = (double)lr;
+    if (!o) return base;
+    if (step <= o->warmup_steps) return base * ((double)step / (double)o->warmup_steps);
+    if (o->schedule == OZ_LR_CONSTANT) return base;
+    const int64_t span = o->total_steps - o->warmup_steps;
+    double q = (double)(step - o->warmup_steps) / (double)(span > 1 ? span : 1);
+    if (q > 1.0) q = 1.0;
+    const double r = o->final_ratio;
+    const double f = o->schedule == OZ_LR_LINEAR ? 1.0 - (1.0 - r) * q : r + (1.0 - r) * (0.5 * (1.0 + cos(M_PI * q)));
+    return base * f;
+}
+OZ_API int oz_lr_schedule_at(const oz_optimizer* opt, float lr, int64_t step, double* out) {
+    OZ_REQUIRE(out && step >= 1, "oz_lr_schedule_at: out is NULL or step < 1");
+    if (int rc = t_opt_check(opt, "oz_lr_schedule_at")) return rc;
+    *out = t_lr_at(opt, lr, step);
+    return OZ_OK;
+}
+// the segment tables of the current options: every trainable array (the norm), the decayed ones (oz_trainer_sqsum), and the decayed ones as
+// merged 16-byte-unit ranges (k_t_adam_x)
+static void t_opt_tables(oz_trainer* t) {
+    const uint64_t mask = t_decay_mask(t->opt);
+    t->seg_all.n = t->seg_dec.n = t->dec_units.n = 0;
+    for (int i = 0; i < 40; ++i) {
+        if (t->toff[i] < 0) continue;
+        TSegs& a = t->seg_all;
+        a.off[a.n] = t->toff[i]; a.len[a.n] = t->size[i]; a.n += 1;
+        if (!((mask >> i) & 1)) continue;
+        TSegs& d = t->seg_dec;
+        d.off[d.n] = t->toff[i]; d.len[d.n] = t->size[i]; d.n += 1;
+        TUnitRanges& u = t->dec_units;
+        const int lo = (int)(t->toff[i] / 4), hi = (int)((t->toff[i] + (t->size[i] + 3) / 4 * 4) / 4);
+        if (u.n && u.hi[u.n - 1] == lo) u.hi[u.n - 1] = hi;
+        else { u.lo[u.n] = lo; u.hi[u.n] = hi; u.n += 1; }
+    }
+}
+
 OZ_API int oz_trainer_create(oz_trainer** out, int n, int channels, int in_channels, int max_batch, float lr, float clipvalue,
                              float dropout, float bn_momentum, uint64_t seed, float* external_grads) {
     OZ_REQUIRE(out, "oz_trainer_create: out is NULL");
@@ -1057,6 +1211,7 @@ OZ_API int oz_trainer_create(oz_trainer** out, int n, int channels, int in_chann
     if (hipSetDevice(t->device) != hipSuccess || hipStreamCreate(&t->s) != hipSuccess) { oz_set_error("oz_trainer_create: no GPU stream"); return fail(OZ_ERR_HIP); }
     const int C = channels, A = n * n, F = (n - 4) * (n - 4) * C;
     t->total = t_layout(n, C, in_channels, t->size, t->toff);
+    t_opt_tables(t);
     int rc = [&]() -> int {
         T_ALLOC(t->P, t->total); T_ALLOC(t->M1, t->total); T_ALLOC(t->V2, t->total);
         if (external_grads) { t->G = external_grads; t->own_grads = false; } else T_ALLOC(t->G, t->total);
@@ -1176,6 +1331,8 @@ OZ_API int oz_trainer_set_weight(oz_trainer* t, int index, const float* data, in
     OZ_REQUIRE(nelem == t->size[index], "oz_trainer_set_weight: weight %d has %lld elements, got %lld", index, (long long)t->size[index], (long long)nelem);
     OZ_HIP(hipSetDevice(t->device));
     OZ_HIP(hipMemcpyAsync(t->param(index), data, nelem * sizeof(float), hipMemcpyHostToDevice, t->s));
+    if (t->opt.average_decay > 0.0 && t->toff[index] >= 0)      // the weight average of this array starts again from what was set
+        OZ_HIP(hipMemcpyAsync(t->E + t->toff[index], data, nelem * sizeof(float), hipMemcpyHostToDevice, t->s));
     OZ_HIP(hipStreamSynchronize(t->s));
     t->dirty = true;
     return OZ_OK;
@@ -1713,12 +1870,50 @@ OZ_API int oz_trainer_fit_epoch_replay(oz_trainer* t, oz_replay* r, const int32_
     return t_fit_epoch_view(t, {r->own, r->opp, r->pi, r->z, held}, order, count, batch, losses3);
 }
 
+// the two stages of the sum of squares of `X`'s arrays `sg` on the main stream -> norm_out[slot] (clipnorm > 0: the clip scale too)
+static int t_sqsum_launch(oz_trainer* t, const float* X, const TSegs& sg, double clipnorm, int slot) {
+    if (!t->norm_out) {
+        T_ALLOC(t->sq_partial, T_OPT_SQ_BLOCKS);
+        T_ALLOC(t->norm_out, 2);
+    }
+    int64_t units = 0;
+    for (int r = 0; r < sg.n; ++r) if (sg.len[r] / 4 > units) units = sg.len[r] / 4;      // every thread walks every array: the grid covers the largest
+    int blocks = (int)((units + 255) / 256);
+    blocks = blocks < 1 ? 1 : blocks > T_OPT_SQ_BLOCKS ? T_OPT_SQ_BLOCKS : blocks;
+    hipLaunchKernelGGL(k_t_sqsum, dim3(blocks), dim3(256), 0, t->s, X, sg, t->sq_partial);
+    hipLaunchKernelGGL(k_t_sqsum_fin, dim3(1), dim3(256), 0, t->s, t->sq_partial, blocks, clipnorm, t->norm_out + slot);
+    OZ_HIP(hipGetLastError());
+    return OZ_OK;
+}
+
+// the optimiser kernel of one step at the rates (lr_s, lr_t): k_t_adam, or with an option on the norm (global-norm clip) and k_t_adam_x
+static int t_launch_optimizer(oz_trainer* t, double lr_s, float lr_t, bool with_norm = true) {
+    if (!t->fused)
+        hipLaunchKernelGGL(k_t_adam, dim3((unsigned)((t->total + 255) / 256)), dim3(256), 0, t->s, t->P, t->G, t->M1, t->V2, (long long)t->total, lr_t, t->clip);
+    else {
+        const oz_optimizer& o = t->opt;
+        const bool clipped = o.global_clipnorm > 0.0, avg = o.average_decay > 0.0;
+        if (clipped && with_norm) {       // between the last gradient (the main stream has waited for the weight gradients) and the optimiser
+            if (int rc = t_sqsum_launch(t, t->G, t->seg_all, o.global_clipnorm, 0)) return rc;
+            t->last_clipped = true;
+        }
+        const TAdamX a = {lr_t, t->clip, (float)(2.0 * o.l2), (float)(lr_s * o.weight_decay), (float)o.average_decay, (float)(1.0 - o.average_decay)};
+        const int units = (int)(t->total / 4);
+        const int blocks = (units + 255) / 256 < T_OPT_ADAM_BLOCKS ? (units + 255) / 256 : T_OPT_ADAM_BLOCKS;
+        hipLaunchKernelGGL(k_t_adam_x, dim3(blocks), dim3(256), 0, t->s, (float4*)t->P, (const float4*)t->G, (float4*)t->M1, (float4*)t->V2,
+                           avg ? (float4*)t->E : (float4*)nullptr, units, a, clipped ? &t->norm_out[0].scale32 : (const float*)nullptr, t->dec_units);
+    }
+    OZ_HIP(hipGetLastError());
+    return OZ_OK;
+}
+
 static int t_apply_locked(oz_trainer* t) {
     t->step += 1;
     const double b1t = pow(0.9, (double)t->step), b2t = pow(0.999, (double)t->step);
-    const float lr_t = (float)((double)t->lr * sqrt(1.0 - b2t) / (1.0 - b1t));
-    hipLaunchKernelGGL(k_t_adam, dim3((unsigned)((t->total + 255) / 256)), dim3(256), 0, t->s, t->P, t->G, t->M1, t->V2, (long long)t->total, lr_t, t->clip);
-    OZ_HIP(hipGetLastError());
+    const double lr_s = t_lr_at(&t->opt, t->lr, t->step);               // (no schedule: (double)lr, the value this line always used)
+    const float lr_t = (float)(lr_s * sqrt(1.0 - b2t) / (1.0 - b1t));
+    t->last_lr_s = lr_s; t->applied = true; t->last_clipped = false;
+    if (int rc = t_launch_optimizer(t, lr_s, lr_t)) return rc;
     for (int i = 0; i < 36; ++i)            // the staged moving statistics become the current ones (pointer swap, stream-ordered use)
         if (t->toff[i] < 0) { float* tmp = t->stats[i]; t->stats[i] = t->stats_new[i]; t->stats_new[i] = tmp; }
     t->dirty = true;
@@ -1731,6 +1926,114 @@ OZ_API int oz_trainer_apply(oz_trainer* t) {
     T_LOCK(t);
     OZ_HIP(hipSetDevice(t->device));
     return t_apply_locked(t);
+}
+
+// ---------------------------------------------------------------- optimiser options: the entry points
+OZ_API int oz_trainer_set_optimizer(oz_trainer* t, const oz_optimizer* opt) {
+    OZ_REQUIRE(t, "oz_trainer_set_optimizer: NULL");
+    if (int rc = t_opt_check(opt, "oz_trainer_set_optimizer")) return rc;
+    T_LOCK(t);
+    const oz_optimizer o = opt ? *opt : oz_optimizer{};
+    const bool fused = o.l2 > 0.0 || o.weight_decay > 0.0 || o.global_clipnorm > 0.0 || o.average_decay > 0.0;
+    OZ_REQUIRE(!fused || ((uintptr_t)t->G & 15) == 0, "oz_trainer_set_optimizer: the external gradient arena is not 16-byte aligned");
+    OZ_HIP(hipSetDevice(t->device));
+    if (o.average_decay > 0.0 && !(t->opt.average_decay > 0.0)) {        // switched on: E = the weights as they are now (stream order)
+        if (!t->E) T_ALLOC(t->E, t->total);
+        OZ_HIP(hipMemcpyAsync(t->E, t->P, t->total * sizeof(float), hipMemcpyDeviceToDevice, t->s));
+        OZ_HIP(hipStreamSynchronize(t->s));
+    }
+    t->opt = o;
+    t->fused = fused;
+    t_opt_tables(t);
+    return OZ_OK;
+}
+OZ_API int oz_trainer_get_optimizer(oz_trainer* t, oz_optimizer* opt) {
+    OZ_REQUIRE(t && opt, "oz_trainer_get_optimizer: bad argument");
+    T_LOCK(t);
+    *opt = t->opt;
+    return OZ_OK;
+}
+OZ_API int oz_trainer_set_lr(oz_trainer* t, float lr) {
+    OZ_REQUIRE(t && lr >= 0.f && std::isfinite(lr), "oz_trainer_set_lr: bad argument");
+    T_LOCK(t);
+    t->lr = lr;                          // read on the host at the next apply
+    return OZ_OK;
+}
+OZ_API int oz_trainer_get_step_info(oz_trainer* t, double* lr_s, double* grad_norm, double* clip_scale) {
+    OZ_REQUIRE(t && lr_s && grad_norm && clip_scale, "oz_trainer_get_step_info: bad argument");
+    T_LOCK(t);
+    if (!t->applied) { oz_set_error("oz_trainer_get_step_info: no optimiser step has been applied yet"); return OZ_ERR_STATE; }
+    *lr_s = t->last_lr_s; *grad_norm = 0.0; *clip_scale = 1.0;
+    OZ_HIP(hipSetDevice(t->device));
+    if (t->last_clipped) {
+        TNormOut h;
+        OZ_HIP(hipMemcpyAsync(&h, t->norm_out, sizeof h, hipMemcpyDeviceToHost, t->s));
+        OZ_HIP(hipStreamSynchronize(t->s));
+        *grad_norm = h.norm; *clip_scale = h.scale;
+    } else OZ_HIP(hipStreamSynchronize(t->s));
+    return OZ_OK;
+}
+OZ_API int oz_trainer_get_weight_average(oz_trainer* t, int index, float* data, int64_t nelem) {
+    OZ_REQUIRE(t && data && index >= 0 && index < 40, "oz_trainer_get_weight_average: bad argument");
+    T_LOCK(t);
+    OZ_REQUIRE(nelem == t->size[index], "oz_trainer_get_weight_average: weight %d has %lld elements, got %lld", index, (long long)t->size[index], (long long)nelem);
+    if (!(t->opt.average_decay > 0.0)) { oz_set_error("oz_trainer_get_weight_average: the weight average is off (oz_optimizer.average_decay)"); return OZ_ERR_STATE; }
+    OZ_HIP(hipSetDevice(t->device));
+    const float* src = t->toff[index] >= 0 ? t->E + t->toff[index] : t->stats[index];
+    OZ_HIP(hipMemcpyAsync(data, src, nelem * sizeof(float), hipMemcpyDeviceToHost, t->s));
+    OZ_HIP(hipStreamSynchronize(t->s));
+    return OZ_OK;
+}
+OZ_API int oz_trainer_sqsum(oz_trainer* t, int what, double* out) {
+    OZ_REQUIRE(t && out && (what == OZ_SQSUM_GRADIENTS || what == OZ_SQSUM_DECAYED_WEIGHTS), "oz_trainer_sqsum: bad argument");
+    T_LOCK(t);
+    OZ_REQUIRE(((uintptr_t)t->G & 15) == 0, "oz_trainer_sqsum: the external gradient arena is not 16-byte aligned");
+    OZ_HIP(hipSetDevice(t->device));
+    const bool grads = what == OZ_SQSUM_GRADIENTS;
+    if (int rc = t_sqsum_launch(t, grads ? t->G : t->P, grads ? t->seg_all : t->seg_dec, 0.0, 1)) return rc;
+    TNormOut h;
+    OZ_HIP(hipMemcpyAsync(&h, t->norm_out + 1, sizeof h, hipMemcpyDeviceToHost, t->s));
+    OZ_HIP(hipStreamSynchronize(t->s));
+    *out = h.sumsq;
+    return OZ_OK;
+}
+
+// Benchmark hook (tools/optimizer_bench.py): HIP-event time of the step's optimiser kernel and of the norm's two kernels, `iters` launches each on an
+// otherwise idle device.  It RUNS the kernels on the trainer's arrays with the arena as it is: the weights, moments and average move as under
+// `iters` steps (the step count does not) -- for a scratch trainer.
+OZ_API int oz_trainer_time_optimizer(oz_trainer* t, int iters, double* ms3) {
+    OZ_REQUIRE(t && ms3 && iters >= 1 && iters <= 10000, "oz_trainer_time_optimizer: bad argument");
+    T_LOCK(t);
+    OZ_HIP(hipSetDevice(t->device));
+    OZ_HIP(hipStreamSynchronize(t->s));
+    OZ_HIP(hipStreamSynchronize(t->s2));
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    OZ_HIP(hipEventCreate(&e0));
+    if (hipEventCreate(&e1) != hipSuccess) { hipEventDestroy(e0); oz_set_error("oz_trainer_time_optimizer: no event"); return OZ_ERR_HIP; }
+    const int rc = [&]() -> int {
+        float ms = 0.f;
+        ms3[0] = ms3[1] = ms3[2] = 0.0;
+        const double lr_s = t_lr_at(&t->opt, t->lr, t->step + 1);
+        const float lr_t = (float)(lr_s * sqrt(1.0 - pow(0.999, (double)t->step + 1)) / (1.0 - pow(0.9, (double)t->step + 1)));
+        if (t->fused && t->opt.global_clipnorm > 0.0) {
+            OZ_HIP(hipEventRecord(e0, t->s));
+            for (int i = 0; i < iters; ++i) if (int r = t_sqsum_launch(t, t->G, t->seg_all, t->opt.global_clipnorm, 0)) return r;
+            OZ_HIP(hipEventRecord(e1, t->s));
+            OZ_HIP(hipEventSynchronize(e1));
+            OZ_HIP(hipEventElapsedTime(&ms, e0, e1));
+            ms3[1] = (double)ms / iters;
+        }
+        OZ_HIP(hipEventRecord(e0, t->s));
+        for (int i = 0; i < iters; ++i) if (int r = t_launch_optimizer(t, lr_s, lr_t, false)) return r;
+        OZ_HIP(hipEventRecord(e1, t->s));
+        OZ_HIP(hipEventSynchronize(e1));
+        OZ_HIP(hipEventElapsedTime(&ms, e0, e1));
+        ms3[0] = (double)ms / iters;
+        t->dirty = true;
+        return OZ_OK;
+    }();
+    hipEventDestroy(e0); hipEventDestroy(e1);
+    return rc;
 }
 
 OZ_API int oz_trainer_get_activation(oz_trainer* t, int layer, int B, float* data, int64_t nelem) {

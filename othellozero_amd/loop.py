@@ -344,6 +344,10 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
     (ValueError).  policy_target="improved" (needs gumbel, alias_final_boards=False and the flat policy loss) trains the policy on the
     searches' improved-policy rows softmax(logit + sigma(completed Q)); policy_target="visits" with gumbel keeps training on the raw counts.
 
+    The optimiser's options (L2 term / decoupled weight decay, global-norm clip, learning-rate schedule, weight average) need no parameter
+    here: the network object carries them -- NNetWrapper(..., optimizer=dict(...)); with use_average=True every train() commits the weight
+    average, so self-play, matches, evaluations and checkpoints of the loop run on it, and copy() hands the settings to the promoted network.
+
     batched_evaluation=True plays the evaluation games against RandomOthelloAgent in lock step on the GPU
     (evaluate_against_random_batch) instead of one by one through the drop-in agents.
 

@@ -18,17 +18,50 @@ POLICY_LOSSES = {"rows": _lib.POLICY_LOSS_ROWS, "flat": _lib.POLICY_LOSS_FLAT}  
 
 
 class History:
-    """what keras Model.fit returns, as far as the reference uses it (main.py:108: kept, never read)"""
+    """what keras Model.fit returns, as far as the reference uses it (main.py:108: kept, never read).  `lr` / `grad_norm`: the scheduled rate and the
+    gradient's global norm (None with global_clipnorm off) of each epoch's LAST step -- attributes, Keras' history holds the three losses only"""
 
     def __init__(self):
         self.history = {"loss": [], "pi-reshaped_loss": [], "v_loss": []}
         self.epoch = []
+        self.lr, self.grad_norm = [], []
+
+
+OPTIMIZER_KEYS = ("l2", "weight_decay", "decay_mask", "global_clipnorm", "average_decay", "schedule")
+
+
+def make_optimizer(l2=0.0, weight_decay=0.0, decay_mask=None, global_clipnorm=0.0, average_decay=0.0, schedule=None):
+    """the options as an oz_optimizer (_lib.Optimizer).  decay_mask: None = the default (the eight kernels), an int bit mask or an iterable of
+    get_weights() indices; schedule: None or (kind, warmup_steps, total_steps, final_ratio), kind "constant" / "linear" / "cosine".  Values are
+    passed on as given: the library validates them (OzError OZ_ERR_ARG)."""
+    o = _lib.Optimizer()
+    o.l2, o.weight_decay, o.global_clipnorm, o.average_decay = float(l2), float(weight_decay), float(global_clipnorm), float(average_decay)
+    if decay_mask is None:
+        o.decay_mask = 0
+    elif isinstance(decay_mask, (int, np.integer)):
+        o.decay_mask = int(decay_mask)
+    else:
+        idx = [int(i) for i in decay_mask]
+        assert idx and all(0 <= i < 64 for i in idx), "decay_mask: a non-empty list of get_weights() indices (None: the default)"
+        o.decay_mask = sum(1 << i for i in set(idx))
+    kind, warmup, total, ratio = schedule if schedule is not None else ("constant", 0, 0, 1.0)
+    assert kind in _lib.LR_SCHEDULES, kind
+    o.schedule, o.warmup_steps, o.total_steps, o.final_ratio = _lib.LR_SCHEDULES[kind], int(warmup), int(total), float(ratio)
+    return o
+
+
+def lr_schedule_at(lr, step, schedule=None, **options):
+    """lr_s of optimiser step `step` (1-based) under `schedule` (oz_lr_schedule_at: the library's one definition; no GPU needed)"""
+    out = C.c_double()
+    _lib.check(_lib.load().oz_lr_schedule_at(C.byref(make_optimizer(schedule=schedule, **options)), float(lr), int(step), C.byref(out)))
+    return out.value
 
 
 class Trainer:
     def __init__(self, board_size=8, channels=512, in_channels=2, max_batch=32, lr=1e-3, clipvalue=0.5, dropout=0.3,
-                 bn_momentum=0.99, seed=0, external_grads_ptr=None, precision="f32", policy_loss="rows"):
-        """precision: arithmetic of the 3x3 layers -- "f32" (fp32 matrix cores), "f16x2" (forward / data-gradient GEMMs: fp32 values
+                 bn_momentum=0.99, seed=0, external_grads_ptr=None, precision="f32", policy_loss="rows", optimizer=None):
+        """optimizer: None or a dict of set_optimizer's keyword arguments
+        precision: arithmetic of the 3x3 layers -- "f32" (fp32 matrix cores), "f16x2" (forward / data-gradient GEMMs: fp32 values
         as two fp16 planes on the fp16 matrix cores, per-step power-of-two scaling and a range guard; channels % 256 == 0) or "bf16x3"
         (forward, data gradient and weight gradient: every fp32 value exactly as three bf16 planes on the bf16 matrix cores, no scaling,
         no guard; channels % 256 == 0)
@@ -49,6 +82,8 @@ class Trainer:
         self.policy_loss = policy_loss
         if policy_loss != "rows":
             _lib.check(lib.oz_trainer_set_policy_loss(self._h, POLICY_LOSSES[policy_loss]))
+        if optimizer:
+            self.set_optimizer(**optimizer)
 
     def __del__(self):
         try:
@@ -72,13 +107,56 @@ class Trainer:
             assert a.shape == tuple(shp), f"weight {i}: shape {a.shape} != {shp}"
             _lib.check(lib.oz_trainer_set_weight(self._h, i, _lib.p_f32(a), a.size))
 
-    def get_weights(self):
+    def get_weights(self, average=False):
+        """the 40 arrays; average=True: the weight average E in place of every trainable array (the BN moving statistics as they are);
+        OzError(OZ_ERR_STATE) with average_decay off"""
         lib, out = _lib.load(), []
+        get = lib.oz_trainer_get_weight_average if average else lib.oz_trainer_get_weight
         for i, shp in enumerate(self.shapes):
             a = np.zeros(shp, dtype=np.float32)
-            _lib.check(lib.oz_trainer_get_weight(self._h, i, _lib.p_f32(a), a.size))
+            _lib.check(get(self._h, i, _lib.p_f32(a), a.size))
             out.append(a)
         return out
+
+    # ---- optimiser options (oz_trainer_set_optimizer: they act inside apply, so the resident and the step-wise paths see the same steps)
+    def set_optimizer(self, l2=0.0, weight_decay=0.0, decay_mask=None, global_clipnorm=0.0, average_decay=0.0, schedule=None):
+        """l2: c of Keras' kernel_regularizer=l2(c), 2 c w joins the gradient before clipvalue; weight_decay: decoupled (AdamW), w -= lr_s lambda w;
+        decay_mask: the arrays both act on (None: the eight kernels); global_clipnorm: the gradient is scaled by min(1, clipnorm / its global norm);
+        average_decay: d of the weight average E = d E + (1 - d) w, read with get_weights(average=True); schedule: (kind, warmup_steps,
+        total_steps, final_ratio).  No argument: everything off.  The per-element order of a step is defined in othellozero_amd.h."""
+        o = make_optimizer(l2, weight_decay, decay_mask, global_clipnorm, average_decay, schedule)
+        _lib.check(_lib.load().oz_trainer_set_optimizer(self._h, C.byref(o)))
+
+    def optimizer(self):
+        """the options in force, as set_optimizer's keyword arguments"""
+        o = _lib.Optimizer()
+        _lib.check(_lib.load().oz_trainer_get_optimizer(self._h, C.byref(o)))
+        kind = {v: k for k, v in _lib.LR_SCHEDULES.items()}[o.schedule]
+        return dict(l2=o.l2, weight_decay=o.weight_decay, decay_mask=int(o.decay_mask) or None, global_clipnorm=o.global_clipnorm,
+                    average_decay=o.average_decay, schedule=(kind, int(o.warmup_steps), int(o.total_steps), o.final_ratio))
+
+    def set_lr(self, lr):
+        """the base learning rate from the next apply on"""
+        _lib.check(_lib.load().oz_trainer_set_lr(self._h, float(lr)))
+
+    def step_info(self):
+        """dict(lr_s, grad_norm, clip_scale) of the last applied step (the two norm fields are 0 and 1 with global_clipnorm off)"""
+        a, b, c = C.c_double(), C.c_double(), C.c_double()
+        _lib.check(_lib.load().oz_trainer_get_step_info(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return dict(lr_s=a.value, grad_norm=b.value, clip_scale=c.value)
+
+    def time_optimizer(self, iters=20):
+        """benchmark hook: dict(kernel_ms, reduction_ms), mean HIP-event time of `iters` launches of the step's optimiser kernel and of the norm's
+        two kernels (0 with global_clipnorm off).  The launches are real: for a scratch trainer"""
+        ms = np.zeros(3, np.float64)
+        _lib.check(_lib.load().oz_trainer_time_optimizer(self._h, int(iters), _lib.p_f64(ms)))
+        return dict(kernel_ms=float(ms[0]), reduction_ms=float(ms[1]))
+
+    def sqsum(self, what):
+        """the sum of squares of the gradient arena ("gradients") or of the decayed arrays' weights ("weights": c times this is the L2 term), float64"""
+        out = C.c_double()
+        _lib.check(_lib.load().oz_trainer_sqsum(self._h, _lib.SQSUM_KINDS[what], C.byref(out)))
+        return out.value
 
     def get_grads(self):
         """{index: gradient} of the trainable arrays after forward_backward"""
@@ -241,10 +319,14 @@ def pack_examples(examples, board_size, in_channels=2):
     return own, opp, pi, z
 
 
-def _record_epoch(hist, ep, epochs, means, verbose):
+def _record_epoch(hist, ep, epochs, means, verbose, trainer=None):
     for k, val in zip(("loss", "pi-reshaped_loss", "v_loss"), means):
         hist.history[k].append(float(val))
     hist.epoch.append(ep)
+    if hasattr(trainer, "step_info") and trainer.step > 0:
+        info = trainer.step_info()
+        hist.lr.append(info["lr_s"])
+        hist.grad_norm.append(info["grad_norm"] if trainer.optimizer()["global_clipnorm"] > 0 else None)
     if verbose:
         print(f"Epoch {ep + 1}/{epochs} - loss: {hist.history['loss'][-1]:.4f} - pi-reshaped_loss: "
               f"{hist.history['pi-reshaped_loss'][-1]:.4f} - v_loss: {hist.history['v_loss'][-1]:.4f}")
@@ -259,7 +341,7 @@ def fit_replay(trainer, replay, batch_size=32, epochs=10, shuffle_seed=0, verbos
     for ep in range(epochs if N else 0):
         order = np.random.RandomState(shuffle_seed + ep).permutation(N)
         means = np.asarray(trainer.fit_epoch_replay(replay, order, batch_size), dtype=np.float64)
-        _record_epoch(hist, ep, epochs, means, verbose)
+        _record_epoch(hist, ep, epochs, means, verbose, trainer)
     trainer.sync()
     return hist
 
@@ -303,6 +385,6 @@ def fit(trainer, own, opp, pi, z, batch_size=32, epochs=10, shuffle_seed=0, allr
                 tot += np.asarray(losses) * len(idx)            # keras reports the sample-weighted running mean
                 seen += len(idx)
             means = tot / max(seen, 1)
-        _record_epoch(hist, ep, epochs, means, verbose)
+        _record_epoch(hist, ep, epochs, means, verbose, trainer)
     trainer.sync()
     return hist
