@@ -790,6 +790,59 @@ int oz_selfplay_targets_device(oz_selfplay* sp, void* dst_device, int64_t max_re
 int oz_value_targets(const oz_record* records, const double* values, int64_t R, int n, int mode, double param, int exact_empties,
                      float* out /* [R] */);
 
+/* ------------------------------------------------------------------ policy surprise weighting (opt-in; with nothing of it called every kernel,
+ * record, file and launch is what it was).  In most self-play positions the search confirms the network's prior; in a few it overturns it.
+ * Every record becomes 8 examples, so the informative ones are diluted.  KataGo's remedy: a record's share of the training data is
+ * proportional to how far its policy target moved from the prior.
+ * The SURPRISE of a searched move, float64 without contraction, by square sq = 0 .. 63:
+ *     q      = the row that becomes the policy target: the recorded count row (the pruned one under forced playouts) at T = 1, (double)N[sq] /
+ *              pairwise_sum((double)N, 64), as k_expand_visits normalises it; with the Gumbel search the float32 improved-policy row, widened
+ *     p      = the root's STORED prior of the square (never the noised one), 0 off the legal set
+ *     term   = q > 0 ? q * (oz_log_cr(q) - oz_log_cr(max(p, DBL_MIN))) : 0          oz_log_cr: the same bits on host and device
+ *     s      = max(0, pairwise_sum(term, 64))                                         = KL(q || p)
+ * ONE definition, oz_surprise_term / oz_surprise_sum (csrc/oz_common.h), is what the move kernels and oz_policy_surprises evaluate.
+ * WEIGHTS: take one game's records; K = those with pad[0] == 0 (fully searched), S = pairwise_sum of their s by ply (zeros elsewhere, 64 terms):
+ *     w_i    = (float)((1 - frac) + frac * (s_i * (double)K / S))      fully searched;  1.0f where S == 0;  0 for a fast record
+ * so a game's weights sum to K: the amount of data is preserved.  frac in (0, 1]; KataGo uses 0.5.
+ * COPIES: d = oz_rng(weight_seed, game_id, ply, OZ_RNG_SURPRISE = 8);  c_i = (int)floor(8.0 * (double)w_i + oz_rng_unit(d)): the record becomes
+ * c_i examples instead of 8, E[c_i] = 8 w_i; the first of them is symmetry t0_i = d & 7 (oz_rng_unit reads d >> 11: independent bits), example
+ * k is symmetry (t0_i + k) & 7 of oz_sym_src.  ONE definition, oz_surprise_weight / oz_surprise_copies (csrc/oz_common.h), is what
+ * k_surprise_weights and the host functions evaluate.  KataGo's extra weight for surprising FAST moves is not built: a fast record gets 0. */
+typedef struct {
+    int64_t records;        /* records given a weight */
+    int64_t full_records;   /* of them, fully searched (pad[0] == 0) */
+    int64_t examples;       /* sum of c_i */
+    int64_t zero_copies;    /* fully searched records with c_i == 0 */
+    int64_t max_copies;     /* the largest c_i */
+} oz_surprise_weight_stats;
+/* the engine keeps the surprise of every searched move next to its record: lock-step rounds at any leaves_per_step, oz_selfplay_stagger and
+ * the free-running driver alike, with root noise, move sampling, forced playouts, a playout cap, recorded values and the Gumbel search; no
+ * record, no row and no statistic changes.  The surprise of a fast move is recorded and never used.  Before the first driver call (OZ_ERR_STATE
+ * afterwards).  Needs an engine that records a policy target: record_visits = 1 or oz_selfplay_set_gumbel before it (OZ_ERR_ARG).  512 B per
+ * slot + 8 B per record of device memory at the first enabling. */
+int oz_selfplay_set_record_surprise(oz_selfplay* sp, int enable);
+/* surprise i belongs to record i of oz_selfplay_records, the same ring order (OZ_ERR_ARG on an engine that does not record surprise) */
+int oz_selfplay_surprises(oz_selfplay* sp, double* out /* [max_records] */, int64_t max_records, int64_t* written);
+int oz_selfplay_surprises_device(oz_selfplay* sp, void* dst_device, int64_t max_records, int64_t* written);
+/* the surprise of `count` rows by square on the host (no device needed): N[count][64] int32 count rows (OZ_ERR_ARG: a negative count), or
+ * q[count][64] float32 policy rows; P[count][64] the priors. */
+int oz_policy_surprises(const int32_t* N, const double* P, int64_t count, double* out /* [count] */);
+int oz_policy_surprises_f32(const float* q, const double* P, int64_t count, double* out /* [count] */);
+/* weights, copy counts and first symmetries of the completed records [first_record, completed so far) into the engine's float32 weights,
+ * int32 copies and uint8 first_sym [record_cap] on the device (allocated by the first call), one wavefront per record; a game that lies
+ * partly before first_record is still normalised over all of its records.  Needs oz_selfplay_set_record_surprise.  Records are not touched.
+ * OZ_ERR_ARG: frac outside (0, 1] (NaN included), first_record < 0; OZ_ERR_STATE: a step is pending. */
+int oz_selfplay_surprise_weights(oz_selfplay* sp, int64_t first_record, double frac, uint64_t weight_seed,
+                                 oz_surprise_weight_stats* stats /* optional */);
+/* entry i belongs to record i (OZ_ERR_ARG before the first oz_selfplay_surprise_weights; entries below its first_record are 0 or stale) */
+int oz_selfplay_weights(oz_selfplay* sp, float* weights, int32_t* copies, uint8_t* first_sym /* [max_records] each */, int64_t max_records,
+                        int64_t* written);
+/* the same on the host (no device needed): R records in any order; records of one game_id are one game, taken in ply order (ply < 64).
+ * w[i], copies[i], first_sym[i] belong to records[i].  oz_surprise_copies: w in [0, 64] (the weights of oz_surprise_weights). */
+int oz_surprise_weights(const oz_record* records, const double* surprises, int64_t R, double frac, float* w /* [R] */);
+int oz_surprise_copies(const oz_record* records, const float* w, int64_t R, uint64_t weight_seed, int32_t* copies /* [R] */,
+                       uint8_t* first_sym /* [R] */);
+
 /* root visit counts of the last move round, counts[num_games][64] (parity tests) */
 int oz_selfplay_last_counts(oz_selfplay* sp, int32_t* counts);
 /* HIP-event time of the evaluator (NN) launches since creation, and their count */
@@ -1122,6 +1175,15 @@ int oz_replay_append_selfplay_targets(oz_replay* r, oz_selfplay* sp, int64_t fir
                                       int64_t* appended_records);
 int oz_replay_append_records_values(oz_replay* r, const oz_record* records, const int32_t* counts, const float* values, int64_t count,
                                     int alias_final, int target, double temperature);
+/* the engine append under POLICY SURPRISE WEIGHTING ("policy surprise weighting" above): record i becomes c_i examples instead of 8, the copy
+ * counts and first symmetries as the last oz_selfplay_surprise_weights left them (OZ_ERR_ARG before the first; the caller computes them for
+ * first_record or earlier).  Records in ascending (game_id, ply) as ever; example k < c_i of record i is symmetry (t0_i + k) & 7 and has the
+ * running index total + off_i + k, off = the exclusive prefix sum of c over that order (built on the host from 4 B per record; the example
+ * bytes stay on the device).  E = sum c_i examples: total advances by E, an append larger than the buffer keeps its last `capacity`.  A record
+ * with c_i == 0 writes nothing.  value_targets != 0: example z = the record's float32 value target, as oz_replay_append_selfplay_targets.
+ * *appended_records = the non-fast records considered, *appended_examples = E (both optional).  One wavefront per record, no atomics. */
+int oz_replay_append_selfplay_weighted(oz_replay* r, oz_selfplay* sp, int64_t first_record, int alias_final, int target, double temperature,
+                                       int value_targets, int64_t* appended_records, int64_t* appended_examples);
 /* finished examples from the host, in the given order (restoring a saved buffer, hand-made data) */
 int oz_replay_append_examples(oz_replay* r, const uint64_t* own, const uint64_t* opp, const float* pi /* [count][n*n] */,
                               const float* z, int64_t count);

@@ -82,6 +82,11 @@ class EndgameStats(C.Structure):                                                
     ]
 
 
+class SurpriseWeightStats(C.Structure):                                              # oz_surprise_weight_stats
+    _fields_ = [("records", C.c_int64), ("full_records", C.c_int64), ("examples", C.c_int64), ("zero_copies", C.c_int64),
+                ("max_copies", C.c_int64)]
+
+
 class ValueTargetStats(C.Structure):                                                 # oz_value_target_stats
     _fields_ = [("records", C.c_int64), ("exact", C.c_int64), ("sign_changed", C.c_int64)]
 
@@ -229,6 +234,13 @@ SIGNATURES = {
     "oz_selfplay_value_targets": [_vp, C.c_int64, C.c_int, C.c_double, C.c_int, C.POINTER(ValueTargetStats)],
     "oz_selfplay_targets": [_vp, _f32p, C.c_int64, _i64p], "oz_selfplay_targets_device": [_vp, _vp, C.c_int64, _i64p],
     "oz_value_targets": [_vp, _f64p, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int, _f32p],
+    "oz_selfplay_set_record_surprise": [_vp, C.c_int],
+    "oz_selfplay_surprises": [_vp, _f64p, C.c_int64, _i64p], "oz_selfplay_surprises_device": [_vp, _vp, C.c_int64, _i64p],
+    "oz_policy_surprises": [_i32p, _f64p, C.c_int64, _f64p], "oz_policy_surprises_f32": [_f32p, _f64p, C.c_int64, _f64p],
+    "oz_selfplay_surprise_weights": [_vp, C.c_int64, C.c_double, C.c_uint64, C.POINTER(SurpriseWeightStats)],
+    "oz_selfplay_weights": [_vp, _f32p, _i32p, _u8p, C.c_int64, _i64p],
+    "oz_surprise_weights": [_vp, _f64p, C.c_int64, C.c_double, _f32p],
+    "oz_surprise_copies": [_vp, _f32p, C.c_int64, C.c_uint64, _i32p, _u8p],
     "oz_selfplay_eval_time": [_vp, _f64p, _i64p, _i64p],
     "oz_comm_unique_id": [_u8p], "oz_comm_create": [C.POINTER(_vp), _u8p, C.c_int, C.c_int], "oz_comm_destroy": [_vp],
     "oz_selfplay_gather_records": [_vp, _vp, C.c_int64, _vp, C.c_int64, _i64p, _i64p],
@@ -282,6 +294,7 @@ SIGNATURES = {
     "oz_replay_append_selfplay": [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_double, _i64p],
     "oz_replay_append_records": [_vp, _vp, _i32p, C.c_int64, C.c_int, C.c_int, C.c_double],
     "oz_replay_append_selfplay_targets": [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_double, _i64p],
+    "oz_replay_append_selfplay_weighted": [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int, _i64p, _i64p],
     "oz_replay_append_records_values": [_vp, _vp, _i32p, _f32p, C.c_int64, C.c_int, C.c_int, C.c_double],
     "oz_replay_append_examples": [_vp, _u64p, _u64p, _f32p, _f32p, C.c_int64],
     "oz_replay_restore": [_vp, _u64p, _u64p, _f32p, _f32p, C.c_int64, C.c_int64],
@@ -627,6 +640,20 @@ def check_value_target(value_target, alias_final_boards=False):
         raise ValueError("value_target needs alias_final_boards=False: a search value belongs to the position of its move, not to the game's "
                          "final position")
     return VALUE_TARGET_MODES[value_target[0]], param
+
+
+def check_surprise_frac(frac, what="surprise_weight"):
+    """the frac of policy surprise weighting (include/othellozero_amd.h, "policy surprise weighting"): a number in (0, 1] -> float;
+    ValueError for anything else (NaN included)"""
+    if isinstance(frac, (bool, str, bytes)):
+        raise ValueError(f"{what}: frac must be a number in (0, 1], got {frac!r}")
+    try:
+        f = float(frac)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: frac must be a number in (0, 1], got {frac!r}") from None
+    if not 0.0 < f <= 1.0:
+        raise ValueError(f"{what}: frac must be in (0, 1] (got {f})")
+    return f
 
 
 def check_opponent(opponent):

@@ -173,6 +173,53 @@ def rules_gumbel_root(N, N0, Q, P, g, legal, vhat, gumbel, budget, with_scores=F
     return (pick, move, pi, score, gaps) if with_scores else (pick, move, pi)
 
 
+def rules_policy_surprise(target, P):
+    """oz_policy_surprises on the host (no GPU needed): the surprise s = KL(q || p) of searched moves from their rows by square.  target =
+    int32 (..., 64) count rows (the recorded, possibly pruned counts: normalised at T = 1) or float32 (..., 64) policy rows (the improved
+    policy of a Gumbel search: widened to float64); P float64 (..., 64) the root's stored priors, 0 off the legal set -> float64 (...).
+    The function the move kernels evaluate (include/othellozero_amd.h, "policy surprise weighting")."""
+    t = np.asarray(target)
+    p_ = np.ascontiguousarray(P, dtype=np.float64)
+    if t.shape != p_.shape or t.ndim < 1 or t.shape[-1] != 64:
+        raise ValueError(f"target and P must both have shape (..., 64) (got {t.shape} and {p_.shape})")
+    out = np.zeros(t.shape[:-1], np.float64)
+    if np.issubdtype(t.dtype, np.integer):
+        t = np.ascontiguousarray(t, dtype=np.int32)
+        _lib.check(_lib.load().oz_policy_surprises(_lib.p_i32(t), _lib.p_f64(p_), out.size, _lib.p_f64(out)))
+    elif t.dtype == np.float32:
+        t = np.ascontiguousarray(t)
+        _lib.check(_lib.load().oz_policy_surprises_f32(_lib.p_f32(t), _lib.p_f64(p_), out.size, _lib.p_f64(out)))
+    else:
+        raise ValueError(f"target must be int32 count rows or float32 policy rows (got dtype {t.dtype})")
+    return out
+
+
+def rules_surprise_weights(records, surprises, frac):
+    """oz_surprise_weights on the host (no GPU needed): the float32 weights (R,) of move records (_lib.RECORD_DTYPE, any order; records of one
+    game_id are one game) from their surprises (float64 (R,)): (1 - frac) + frac s K / S over the game's K fully searched records, 1 where
+    their surprises sum to 0, 0 for a fast record.  The function k_surprise_weights evaluates."""
+    frac = _lib.check_surprise_frac(frac, "rules_surprise_weights")
+    rec = np.ascontiguousarray(records, dtype=_lib.RECORD_DTYPE).ravel()
+    sur = np.ascontiguousarray(surprises, dtype=np.float64).ravel()
+    if sur.size != rec.size:
+        raise ValueError(f"{sur.size} surprises for {rec.size} records")
+    w = np.zeros(rec.size, np.float32)
+    _lib.check(_lib.load().oz_surprise_weights(rec.ctypes.data_as(C.c_void_p), _lib.p_f64(sur), rec.size, frac, _lib.p_f32(w)))
+    return w
+
+
+def rules_surprise_copies(records, weights, seed):
+    """oz_surprise_copies on the host (no GPU needed): (copies int32 (R,), first_sym uint8 (R,)) of move records from their float32 weights:
+    floor(8 w + u) examples, the first of them symmetry d & 7, d the draw of (seed, game id, ply).  The function k_surprise_weights evaluates."""
+    rec = np.ascontiguousarray(records, dtype=_lib.RECORD_DTYPE).ravel()
+    w = np.ascontiguousarray(weights, dtype=np.float32).ravel()
+    if w.size != rec.size:
+        raise ValueError(f"{w.size} weights for {rec.size} records")
+    c, t0 = np.zeros(rec.size, np.int32), np.zeros(rec.size, np.uint8)
+    _lib.check(_lib.load().oz_surprise_copies(rec.ctypes.data_as(C.c_void_p), _lib.p_f32(w), rec.size, int(seed) & (2 ** 64 - 1), _lib.p_i32(c), _lib.p_u8(t0)))
+    return c, t0
+
+
 def rules_eval_symmetries(own, opp, seed):
     """oz_eval_symmetries on the host (no GPU needed): the orientation t in 0..7 (int32) a network set to ("random", seed) evaluates each
     mover-canonical position (own[i], opp[i]) in -- the function the kernels evaluate"""

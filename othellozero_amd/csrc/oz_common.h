@@ -24,12 +24,14 @@ OZ_HD uint64_t oz_sm64(uint64_t z) {
 }
 OZ_HD uint64_t oz_rotl64(uint64_t x, int r) { return (x << r) | (x >> (64 - r)); }
 
-enum { OZ_RNG_COIN = 0, OZ_RNG_EXPLORE = 1, OZ_RNG_TIE = 2, OZ_RNG_NOISE = 3, OZ_RNG_SAMPLE = 4, OZ_RNG_OPENING = 5, OZ_RNG_PLAYOUT = 6, OZ_RNG_GUMBEL = 7 };
+enum { OZ_RNG_COIN = 0, OZ_RNG_EXPLORE = 1, OZ_RNG_TIE = 2, OZ_RNG_NOISE = 3, OZ_RNG_SAMPLE = 4, OZ_RNG_OPENING = 5, OZ_RNG_PLAYOUT = 6, OZ_RNG_GUMBEL = 7, OZ_RNG_SURPRISE = 8 };
 // GUMBEL: stream 7 + 256 * square, the Gumbel draw of a root's square (Gumbel search below).  7 + 256 sq is none of 0 .. 6 for sq >= 1 and is 7 for
 // sq == 0; it is none of 3 + 256 sq' + 65536 i either: that would need 4 == 256 (sq' - sq) + 65536 i, and the right side is a multiple of 256.
 // NOISE: stream 3 + 256 * square + 65536 * draw (root noise, oz_search.hip); SAMPLE: the one unit draw of a sampled move (move sampling,
 // oz_search.hip) -- 4 is none of 3 + 256 sq + 65536 i; OPENING: the move of an opening ply, keyed (opening seed, opening id, ply)
 // (oz_openings.h) -- nor is 5; PLAYOUT: the full / fast draw of a self-play move (playout cap, oz_playout_budget below) -- nor is 6
+// SURPRISE: the draw of a record's copy count and first symmetry (policy surprise weighting below), keyed (weight seed, game id, ply) -- 8 is
+// none of 3 + 256 sq + 65536 i, and 7 + 256 sq == 8 has no solution
 // counter-based stream replacing random.random / np.random.choice / random.choice
 // (training.py:51,56; othelo_mcts.py:59): keyed (seed, global game id, ply, purpose)
 OZ_HD uint64_t oz_rng(uint64_t seed, uint64_t game, uint64_t move, uint64_t stream) {
@@ -428,6 +430,41 @@ OZ_HD double oz_value_target_td_step(double pq, double b_next, double om, double
 #pragma clang fp contract(off)
     const double a = om * pq, b = lam * b_next;
     return a + b;
+}
+
+// ---------------------------------------------------------------- policy surprise weighting
+// (include/othellozero_amd.h, "policy surprise weighting").  The surprise of a searched move: s = KL(q || p), q the policy target row of the
+// search and p the root's stored priors, by square.  oz_surprise_term: one square's q (log q - log max(p, DBL_MIN)), 0 where q is not positive;
+// both logarithms are oz_log_cr (IEEE operations only: the same bits on host and device).  oz_surprise_sum: pairwise_sum of the 64 terms,
+// clamped at 0 (rounding can leave a tiny negative sum where q == p).  float64, no contraction.  The move (oz_search.hip: one lane per
+// square computes its term, the sum is taken over the wave's 64 terms) and the host's oz_policy_surprises evaluate these two functions.
+OZ_HD double oz_surprise_term(double q, double p) {
+#pragma clang fp contract(off)
+    if (!(q > 0.0)) return 0.0;
+    const double pp = p > 2.2250738585072014e-308 ? p : 2.2250738585072014e-308;
+    const double d = oz_log_cr(q) - oz_log_cr(pp);
+    return q * d;
+}
+__host__ __device__ inline double oz_surprise_sum(const double* term /* [64] */) {
+    const double s = pairwise_sum(term, 64);
+    return s > 0.0 ? s : 0.0;
+}
+// The weight of a fully searched record of a game with K such records whose surprises sum to S (pairwise, by ply): (1 - frac) + frac s K / S,
+// rounded once to float32; 1 where S == 0.  om = 1 - frac, computed once by the caller.  Its copy count: floor(8 w + u), u the unit draw of
+// d = oz_rng(weight seed, game id, ply, OZ_RNG_SURPRISE); its first symmetry: d & 7 (oz_rng_unit reads d >> 11: independent bits).
+// The one definition k_surprise_weights and the host's oz_surprise_weights / oz_surprise_copies share.
+OZ_HD float oz_surprise_weight(double s, int K, double S, double om, double frac) {
+#pragma clang fp contract(off)
+    if (S == 0.0) return 1.0f;
+    const double a = s * (double)K;
+    const double b = a / S;
+    const double c = frac * b;
+    return (float)(om + c);
+}
+OZ_HD int oz_surprise_copies(float w, uint64_t d) {
+#pragma clang fp contract(off)
+    const double a = 8.0 * (double)w;
+    return (int)floor(a + oz_rng_unit(d));
 }
 
 // ---------------------------------------------------------------- training examples

@@ -236,7 +236,11 @@ struct oz_replay {
     oz_record* st_rec = nullptr;
     int32_t *st_cnt = nullptr, *st_perm = nullptr;
     float* st_tgt = nullptr;               // the records' value targets (the *_targets / *_values appends), beside st_rec
-    int64_t st_rec_cap = 0, st_cnt_cap = 0, st_tgt_cap = 0;
+    // the weighted append: the records' copy counts and first symmetries beside st_rec, and the example offset of every permuted record
+    int32_t* st_cpy = nullptr;
+    uint8_t* st_sym = nullptr;
+    long long* st_off = nullptr;
+    int64_t st_rec_cap = 0, st_cnt_cap = 0, st_tgt_cap = 0, st_w_cap = 0;
     std::mutex mu;
     int64_t held() const { return total < capacity ? total : capacity; }
 };
@@ -244,3 +248,4 @@ struct oz_replay {
 int oz_selfplay_replay_facts(oz_selfplay* sp, int* n, int* device, int* record_visits, int64_t* completed);
 // ... and whether it runs the Gumbel search (keeps improved-policy rows beside its records)
 int oz_selfplay_has_gumbel(oz_selfplay* sp);
+int oz_selfplay_copies_device(oz_selfplay* sp, void* copies_device, void* first_sym_device, int64_t max_records, int64_t* written);

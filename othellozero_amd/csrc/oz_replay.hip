@@ -73,6 +73,75 @@ __global__ __launch_bounds__(64) void k_replay_append(const oz_record* __restric
     }
 }
 
+// The weighted append ("policy surprise weighting" in the header): record i of the permutation becomes copies[rix] examples instead of 8;
+// example k of them is symmetry (first_sym[rix] + k) & 7 and has the running index base + off[i] + k, off = the exclusive prefix sum of the
+// copy counts over the permutation.  The eight boards are made once, as above, and kept in LDS; the row of example k is computed for its
+// symmetry (copies beyond 8 repeat symmetries).  skip / capacity as above; the kept examples of a launch are at most `capacity` consecutive
+// running indices.  A record with no copy writes nothing.  One wavefront per record, no atomics, no scratch, fixed order.
+template <int N, bool VISITS, bool POLICY = false>
+__global__ __launch_bounds__(64) void k_replay_append_w(const oz_record* __restrict__ recs, const int32_t* __restrict__ counts,
+                                                        const int32_t* __restrict__ perm, int alias_final, double inv, int k, long long base,
+                                                        long long skip, long long capacity, uint64_t* __restrict__ own,
+                                                        uint64_t* __restrict__ opp, float* __restrict__ pi, float* __restrict__ z,
+                                                        const float* __restrict__ zt, const int32_t* __restrict__ copies,
+                                                        const uint8_t* __restrict__ first_sym, const long long* __restrict__ off) {
+    constexpr int N2 = N * N;
+    __shared__ double arr[64];
+    __shared__ double divisor;
+    __shared__ uint64_t s_own[8], s_opp[8];
+    const int lane = threadIdx.x;
+    const long long i = blockIdx.x;
+    const int rix = perm[i];
+    const int c = copies[rix], t0 = first_sym[rix] & 7;
+    if (c <= 0) return;                                      // (the same for every lane)
+    const long long e0 = off[i];
+    const oz_record rec = recs[rix];
+    const uint64_t b = alias_final ? rec.final_black : rec.black, w = alias_final ? rec.final_white : rec.white;
+    const int r8 = lane >> 3, c8 = lane & 7;                 // this lane as a square
+    const bool on_board = r8 < N && c8 < N;
+    const int rn = lane / N, cn = lane % N;                  // this lane as a cell of the (n, n) view
+    const bool is_cell = lane < N2;
+    float q32 = 0.f;
+    if constexpr (VISITS) {
+        arr[lane] = is_cell ? oz_count_pow(counts[(long long)rix * 64 + rn * 8 + cn], inv, k) : 0.0;     // counts are 0 off the legal set
+        __syncthreads();
+        if (lane == 0) {
+            const double sum = pairwise_sum(arr, N2);
+            divisor = sum == 0 ? 1.0 : sum;
+        }
+        __syncthreads();
+        q32 = (float)(arr[lane] / divisor);
+    }
+    if constexpr (POLICY) q32 = is_cell ? __int_as_float(counts[(long long)rix * 64 + rn * 8 + cn]) : 0.f;
+    const int action = (rec.action >> 3) * N + (rec.action & 7);
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+        const int s8 = on_board ? oz_sym_src(t, N, r8, c8) : 0;
+        const int sq = (s8 / N) * 8 + s8 % N;
+        const uint64_t bo = __ballot(on_board && ((b >> sq) & 1)), bw = __ballot(on_board && ((w >> sq) & 1));
+        if (lane == t) { s_own[t] = bo; s_opp[t] = bw; }
+    }
+    __syncthreads();
+    for (int kk = 0; kk < c; ++kk) {
+        const int t = (t0 + kk) & 7;
+        const int src = is_cell ? oz_sym_src(t, N, rn, cn) : 0;
+        float p;
+        if constexpr (VISITS || POLICY) p = __shfl(q32, src);
+        else p = src == action ? 1.0f : 0.0f;
+        const long long e = e0 + kk;
+        if (is_cell && e >= skip) pi[((base + e) % capacity) * N2 + lane] = p;
+    }
+    const float zv = zt ? zt[rix] : (float)rec.z;
+    for (int kk = lane; kk < c; kk += 64) {
+        const long long e = e0 + kk;
+        if (e >= skip) {
+            const int t = (t0 + kk) & 7;
+            const long long slot = (base + e) % capacity;
+            own[slot] = s_own[t]; opp[slot] = s_opp[t]; z[slot] = zv;
+        }
+    }
+}
+
 // ---------------------------------------------------------------- the object
 #define R_LOCK(r) std::lock_guard<std::mutex> rlock__((r)->mu)
 
@@ -102,7 +171,7 @@ OZ_API int oz_replay_destroy(oz_replay* r) {
     if (!r) return OZ_OK;
     hipSetDevice(r->device);
     if (r->s) hipStreamSynchronize(r->s);
-    for (void* q : {(void*)r->own, (void*)r->opp, (void*)r->pi, (void*)r->z, (void*)r->st_rec, (void*)r->st_cnt, (void*)r->st_perm, (void*)r->st_tgt}) if (q) hipFree(q);
+    for (void* q : {(void*)r->own, (void*)r->opp, (void*)r->pi, (void*)r->z, (void*)r->st_rec, (void*)r->st_cnt, (void*)r->st_perm, (void*)r->st_tgt, (void*)r->st_cpy, (void*)r->st_sym, (void*)r->st_off}) if (q) hipFree(q);
     if (r->s) hipStreamDestroy(r->s);
     delete r;
     return OZ_OK;
@@ -148,6 +217,18 @@ static int replay_reserve(oz_replay* r, int64_t records, int64_t count_rows, int
     return OZ_OK;
 }
 
+// room for the copy counts, first symmetries and example offsets of `records` staged records (the weighted append)
+static int replay_reserve_weighted(oz_replay* r, int64_t records) {
+    if (records <= r->st_w_cap) return OZ_OK;
+    for (void* q : {(void*)r->st_cpy, (void*)r->st_sym, (void*)r->st_off}) if (q) hipFree(q);
+    r->st_cpy = nullptr; r->st_sym = nullptr; r->st_off = nullptr; r->st_w_cap = 0;
+    OZ_HIP(hipMalloc((void**)&r->st_cpy, sizeof(int32_t) * records));
+    OZ_HIP(hipMalloc((void**)&r->st_sym, (size_t)records));
+    OZ_HIP(hipMalloc((void**)&r->st_off, sizeof(long long) * records));
+    r->st_w_cap = records;
+    return OZ_OK;
+}
+
 static int replay_check_target(const char* who, int alias_final, int target, double temperature, bool engine = false) {
     OZ_REQUIRE(alias_final == 0 || alias_final == 1, "%s: alias_final = %d (0 or 1)", who, alias_final);
     OZ_REQUIRE(target != OZ_REPLAY_TARGET_POLICY || engine, "%s: OZ_REPLAY_TARGET_POLICY is offered for an engine's records only (oz_replay_append_selfplay)", who);
@@ -170,11 +251,25 @@ template <int N> static void replay_launch(oz_replay* r, int64_t count, int alia
                            (long long)r->total, skip, (long long)r->capacity, r->own, r->opp, r->pi, r->z, zt);
 }
 
+template <int N> static void replay_launch_w(oz_replay* r, int64_t count, int alias_final, int target, double inv, int k, long long skip, const float* zt) {
+    const dim3 grid((unsigned)count), block(64);
+    if (target == OZ_REPLAY_TARGET_POLICY)
+        hipLaunchKernelGGL((k_replay_append_w<N, false, true>), grid, block, 0, r->s, r->st_rec, r->st_cnt, r->st_perm, alias_final, inv, k, (long long)r->total, skip,
+                           (long long)r->capacity, r->own, r->opp, r->pi, r->z, zt, r->st_cpy, r->st_sym, r->st_off);
+    else if (target == OZ_REPLAY_TARGET_VISITS)
+        hipLaunchKernelGGL((k_replay_append_w<N, true>), grid, block, 0, r->s, r->st_rec, r->st_cnt, r->st_perm, alias_final, inv, k, (long long)r->total, skip,
+                           (long long)r->capacity, r->own, r->opp, r->pi, r->z, zt, r->st_cpy, r->st_sym, r->st_off);
+    else
+        hipLaunchKernelGGL((k_replay_append_w<N, false>), grid, block, 0, r->s, r->st_rec, (const int32_t*)nullptr, r->st_perm, alias_final, inv, k,
+                           (long long)r->total, skip, (long long)r->capacity, r->own, r->opp, r->pi, r->z, zt, r->st_cpy, r->st_sym, r->st_off);
+}
+
 // the staged records [first, first + count) of r->st_rec (host copy: h[0 .. count)) -> 8 examples each, in ascending (game_id, ply).  The fast
 // records of a playout cap (pad[0] != 0) are no training examples: they stay out of the permutation, so the kernel never sees them;
 // *kept = the records appended.
 static int replay_append_staged(oz_replay* r, const oz_record* h, int64_t first, int64_t staged, int alias_final, int target, double temperature,
-                                int64_t* kept, const float* zt = nullptr) {
+                                int64_t* kept, const float* zt = nullptr, const int32_t* hc = nullptr, int64_t* examples = nullptr) {
+    // hc (the weighted append): the staged records' copy counts on the host, hc[0 .. staged), their device copy in r->st_cpy / r->st_sym
     std::vector<int32_t> perm;
     perm.reserve((size_t)staged);
     for (int64_t i = 0; i < staged; ++i)
@@ -188,9 +283,25 @@ static int replay_append_staged(oz_replay* r, const oz_record* h, int64_t first,
     for (int32_t& p : perm) p += (int32_t)first;
     const double inv = target == OZ_REPLAY_TARGET_VISITS ? 1.0 / temperature : 1.0;
     const int k = oz_count_pow_k(inv);
-    const long long E = 8 * (long long)count, skip = E > r->capacity ? E - r->capacity : 0;
+    std::vector<long long> off;
+    long long E = 8 * (long long)count;
+    if (hc) {                                                  // the exclusive prefix sum of the copy counts over the permutation
+        off.resize((size_t)count);
+        E = 0;
+        for (int64_t i = 0; i < count; ++i) { off[(size_t)i] = E; E += hc[perm[(size_t)i] - first] > 0 ? hc[perm[(size_t)i] - first] : 0; }
+    }
+    if (examples) *examples = E;
+    const long long skip = E > r->capacity ? E - r->capacity : 0;
     hipError_t e = hipMemcpyAsync(r->st_perm, perm.data(), sizeof(int32_t) * count, hipMemcpyHostToDevice, r->s);
-    if (e == hipSuccess) {
+    if (e == hipSuccess && hc) e = hipMemcpyAsync(r->st_off, off.data(), sizeof(long long) * count, hipMemcpyHostToDevice, r->s);
+    if (e == hipSuccess && hc) {
+        switch (r->n) {
+        case 4: replay_launch_w<4>(r, count, alias_final, target, inv, k, skip, zt); break;
+        case 6: replay_launch_w<6>(r, count, alias_final, target, inv, k, skip, zt); break;
+        default: replay_launch_w<8>(r, count, alias_final, target, inv, k, skip, zt);
+        }
+        e = hipGetLastError();
+    } else if (e == hipSuccess) {
         switch (r->n) {
         case 4: replay_launch<4>(r, count, alias_final, target, inv, k, skip, zt); break;
         case 6: replay_launch<6>(r, count, alias_final, target, inv, k, skip, zt); break;
@@ -206,7 +317,7 @@ static int replay_append_staged(oz_replay* r, const oz_record* h, int64_t first,
 }
 
 static int replay_append_selfplay(oz_replay* r, oz_selfplay* sp, int64_t first_record, int alias_final, int target, double temperature,
-                                  int64_t* appended_records, bool targets) {
+                                  int64_t* appended_records, bool targets, bool weighted = false, int64_t* appended_examples = nullptr) {
     OZ_REQUIRE(r && sp, "oz_replay_append_selfplay: null argument");
     if (int rc = replay_check_target("oz_replay_append_selfplay", alias_final, target, temperature, true)) return rc;
     OZ_REQUIRE(first_record >= 0, "oz_replay_append_selfplay: first_record %lld", (long long)first_record);
@@ -220,9 +331,11 @@ static int replay_append_selfplay(oz_replay* r, oz_selfplay* sp, int64_t first_r
     OZ_REQUIRE(!visits || record_visits, "oz_replay_append_selfplay: this engine does not record visit counts: create it with oz_selfplay_config.record_visits = 1");
     OZ_REQUIRE(!policy || oz_selfplay_has_gumbel(sp), "oz_replay_append_selfplay: target OZ_REPLAY_TARGET_POLICY needs an engine with the Gumbel search (oz_selfplay_set_gumbel)");
     if (appended_records) *appended_records = 0;
+    if (appended_examples) *appended_examples = 0;
     if (completed <= first_record) return OZ_OK;
     OZ_HIP(hipSetDevice(r->device));
     if (int rc = replay_reserve(r, completed, visits || policy ? completed : 0, targets ? completed : 0)) return rc;
+    if (weighted) { if (int rc = replay_reserve_weighted(r, completed)) return rc; }
     int64_t got = 0, got_rows = 0;
     if (int rc = oz_selfplay_records_device(sp, r->st_rec, completed, &got)) return rc;
     if (visits) {
@@ -237,16 +350,31 @@ static int replay_append_selfplay(oz_replay* r, oz_selfplay* sp, int64_t first_r
         if (int rc = oz_selfplay_targets_device(sp, r->st_tgt, got, &got_rows)) return rc;
         if (got_rows < got) got = got_rows;
     }
+    if (weighted) {
+        if (int rc = oz_selfplay_copies_device(sp, r->st_cpy, r->st_sym, got, &got_rows)) return rc;
+        if (got_rows < got) got = got_rows;
+    }
     OZ_HIP(hipStreamSynchronize(nullptr));       // the engine's device-to-device copies ran on the null stream
     const int64_t count = got - first_record;
     if (count <= 0) return OZ_OK;
     std::vector<oz_record> h((size_t)count);     // 48 B per record: 2 % of the example bytes; the examples never leave the device
     OZ_HIP(hipMemcpyAsync(h.data(), r->st_rec + first_record, sizeof(oz_record) * count, hipMemcpyDeviceToHost, r->s));
+    std::vector<int32_t> hc;                     // ... and, weighted, 4 B more: their copy counts, for the offsets
+    if (weighted) {
+        hc.resize((size_t)count);
+        OZ_HIP(hipMemcpyAsync(hc.data(), r->st_cpy + first_record, sizeof(int32_t) * count, hipMemcpyDeviceToHost, r->s));
+    }
     OZ_HIP(hipStreamSynchronize(r->s));
     int64_t kept = 0;
-    if (int rc = replay_append_staged(r, h.data(), first_record, count, alias_final, target, temperature, &kept, targets ? r->st_tgt : nullptr)) return rc;
+    if (int rc = replay_append_staged(r, h.data(), first_record, count, alias_final, target, temperature, &kept, targets ? r->st_tgt : nullptr,
+                                      weighted ? hc.data() : nullptr, appended_examples)) return rc;
     if (appended_records) *appended_records = kept;
     return OZ_OK;
+}
+OZ_API int oz_replay_append_selfplay_weighted(oz_replay* r, oz_selfplay* sp, int64_t first_record, int alias_final, int target, double temperature,
+                                              int value_targets, int64_t* appended_records, int64_t* appended_examples) {
+    OZ_REQUIRE(value_targets == 0 || value_targets == 1, "oz_replay_append_selfplay_weighted: value_targets = %d (0 or 1)", value_targets);
+    return replay_append_selfplay(r, sp, first_record, alias_final, target, temperature, appended_records, value_targets != 0, true, appended_examples);
 }
 OZ_API int oz_replay_append_selfplay(oz_replay* r, oz_selfplay* sp, int64_t first_record, int alias_final, int target, double temperature,
                                      int64_t* appended_records) {

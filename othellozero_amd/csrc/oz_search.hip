@@ -2500,9 +2500,23 @@ struct GumbelPlay {
     float* policies;                       // [record_cap][64]
     unsigned long long* moves;             // [1] moves picked by the Gumbel rule
 };
-template <bool NOISE = false, bool SAMPLE = false, bool CAP = false, bool FORCE = false, bool VALUES = false, bool GUMBEL = false>
+// SURPRISE (an engine that records policy surprise, oz_selfplay_set_record_surprise; "policy surprise weighting" in the header): s = KL(q || p)
+// of the move's search, q the row that becomes the policy target (the pruned count row at T = 1, normalised as k_expand_visits does; under GUMBEL
+// the float32 improved-policy row) and p the root's stored priors, goes into the move log and from there beside the game's records, as the
+// root value does.  Instantiations of its own (k_sp_move_fs / k_sp_move_gs, the *_xs advance): every other kernel stays the code it was.
+// Never in the arena.
+struct SurprisePlay {
+    double* log;                           // [G][64 plies]
+    double* rec;                           // [record_cap]
+};
+// (calls, not inlined code: a 64-term pairwise_sum of constant length is unrolled into 64 loads in flight, 128 VGPRs; inlined into the move
+// they cost the free-running advance a wave of occupancy for all of its simulations, and the sums run once per move)
+__device__ __noinline__ double surprise_row_sum(const double* a) { return pairwise_sum(a, 64); }
+__device__ __noinline__ double surprise_sum(const double* term) { return oz_surprise_sum(term); }
+template <bool NOISE = false, bool SAMPLE = false, bool CAP = false, bool FORCE = false, bool VALUES = false, bool GUMBEL = false, bool SURPRISE = false>
 __device__ __forceinline__ void sp_move_body(const GamesDev& gm, const MctsDev& t, int g, int lane, int arena, MoveSampling ms = MoveSampling{},
-                                             PlayoutCap pc = PlayoutCap{}, ForcedPlayouts fp = ForcedPlayouts{}, GumbelPlay gp = GumbelPlay{}) {
+                                             PlayoutCap pc = PlayoutCap{}, ForcedPlayouts fp = ForcedPlayouts{}, GumbelPlay gp = GumbelPlay{},
+                                             SurprisePlay su = SurprisePlay{}) {
     if (!t.active[g]) return;
     bool prune = false;
     (void)prune;
@@ -2558,6 +2572,27 @@ __device__ __forceinline__ void sp_move_body(const GamesDev& gm, const MctsDev& 
             const GumbelPick pk = gumbel_policy_lane(t, gp.gd, garr, g, node, lane, legal);
             gpi = pk.p; gmove = pk.move;
         }
+    }
+    // record_surprise: KL(target row || stored priors) of this search (oz_surprise_term / oz_surprise_sum, oz_common.h)
+    double surp = 0.0;
+    (void)surp;
+    if constexpr (SURPRISE) {
+        __shared__ double sterm[64];
+        double q;
+        if constexpr (GUMBEL) q = (double)gpi;
+        else {
+            sterm[lane] = (double)row;                            // oz_count_pow at T = 1 (k = 1: the count itself), then the sum and the one division of
+                                                                  // k_expand_visits / k_replay_append<VISITS>; spelled out: the call would compile pow() in
+            wave_sync();
+            const double sum = surprise_row_sum(sterm);
+            wave_sync();
+            q = sterm[lane] / (sum == 0 ? 1.0 : sum);
+            wave_sync();
+        }
+        sterm[lane] = oz_surprise_term(q, is_legal ? rec_edge(t, g, node, oz_popc(legal & ((1ULL << lane) - 1ULL)))->p : 0.0);
+        wave_sync();
+        surp = surprise_sum(sterm);
+        wave_sync();                                             // the next move of this wave (free-running loop) writes sterm[] again
     }
     int action, greedy = 1;
     if (arena || gm.temperature == 0.0) {
@@ -2646,10 +2681,14 @@ __device__ __forceinline__ void sp_move_body(const GamesDev& gm, const MctsDev& 
             if (gm.log_values && lane < nply && (long long)(base + lane) < gm.record_cap)
                 gm.values[base + lane] = lane == ply ? rootv : gm.log_values[lb + lane];
         }
+        if constexpr (SURPRISE) {                             // ... and its surprises, the same way
+            if (lane < nply && (long long)(base + lane) < gm.record_cap) su.rec[base + lane] = lane == ply ? surp : su.log[lb + lane];
+        }
     } else {
         if (gm.record_visits && ply < 64) gm.log_counts[(lb + ply) * 64 + lane] = row;
         if constexpr (VALUES) { if (gm.log_values && lane == 0 && ply < 64) gm.log_values[lb + ply] = rootv; }
         if constexpr (GUMBEL) { if (ply < 64) gp.log_pi[(lb + ply) * 64 + lane] = gpi; }
+        if constexpr (SURPRISE) { if (lane == 0 && ply < 64) su.log[lb + ply] = surp; }
     }
     if constexpr (GUMBEL) { if (lane == 0 && greedy == 3) atomicAdd(gp.moves, 1ULL); }
     if (lane == 0) atomicAdd(&gm.counters[2], 1ULL);
@@ -2683,6 +2722,13 @@ __global__ __launch_bounds__(64) void k_sp_move_f(GamesDev gm, MctsDev t, MoveSa
 __global__ __launch_bounds__(64) void k_sp_move_g(GamesDev gm, MctsDev t, GumbelPlay gp) {
     sp_move_body<false, false, false, false, true, true>(gm, t, blockIdx.x, threadIdx.x, 0, MoveSampling{}, PlayoutCap{}, ForcedPlayouts{}, gp);
 }
+// (the *s kernels: k_sp_move_f and k_sp_move_g whose move records its policy surprise, launched by engines with record_surprise)
+__global__ __launch_bounds__(64) void k_sp_move_fs(GamesDev gm, MctsDev t, MoveSampling ms, PlayoutCap pc, ForcedPlayouts fp, SurprisePlay su) {
+    sp_move_body<false, true, true, true, true, false, true>(gm, t, blockIdx.x, threadIdx.x, 0, ms, pc, fp, GumbelPlay{}, su);
+}
+__global__ __launch_bounds__(64) void k_sp_move_gs(GamesDev gm, MctsDev t, GumbelPlay gp, SurprisePlay su) {
+    sp_move_body<false, false, false, false, true, true, true>(gm, t, blockIdx.x, threadIdx.x, 0, MoveSampling{}, PlayoutCap{}, ForcedPlayouts{}, gp, su);
+}
 
 // ---------------------------------------------------------------- free-running self-play step
 // The lock-step driver gives every game one simulation per step; simulations that end on a finished board need no
@@ -2713,9 +2759,9 @@ __global__ __launch_bounds__(64) void k_sp_move_g(GamesDev gm, MctsDev t, Gumbel
 //   forced playouts: the descents force through t.forced_k, the move prunes its row while the root's noise is still armed (sp_move_body<.., FORCE>
 //   reads the flag before it clears it): a function of the root record and eta, the same rows again.
 struct SelfplayExtras { double alpha; uint64_t seed; MoveSampling sample; PlayoutCap cap; ForcedPlayouts forced; };
-template <bool EXTRAS = false, bool VALUES = EXTRAS>
+template <bool EXTRAS = false, bool VALUES = EXTRAS, bool SURPRISE = false>
 __device__ __forceinline__ void advance_body(const GamesDev& gm, const MctsDev& t, TreeLds& L, int g, int lane, int sims, int* __restrict__ sims_done, int cap,
-                                             SelfplayExtras xt = SelfplayExtras{}) {
+                                             SelfplayExtras xt = SelfplayExtras{}, SurprisePlay su = SurprisePlay{}) {
     if (unii(t.leaf_status[g]) == OZ_LEAF_WAIT) {          // batch cap: the leaf of the simulation in progress found no slot -- offer it again, unchanged
         if (lane == 0) t.leaf_status[g] = OZ_LEAF_EVAL;
         return;
@@ -2739,7 +2785,7 @@ __device__ __forceinline__ void advance_body(const GamesDev& gm, const MctsDev& 
                 budget = oz_playout_budget(gm.seed, uni64(gm.game_id[g]), (uint64_t)unii(gm.ply[g]), sims, xt.cap.fast_sims, xt.cap.full_prob, &fast);
         }
         if (done >= budget) {                              // training.py:42-67: the move after num_simulations simulations
-            sp_move_body<EXTRAS, EXTRAS, EXTRAS, EXTRAS, VALUES>(gm, t, g, lane, 0, xt.sample, xt.cap, xt.forced);
+            sp_move_body<EXTRAS, EXTRAS, EXTRAS, EXTRAS, VALUES, false, SURPRISE>(gm, t, g, lane, 0, xt.sample, xt.cap, xt.forced, GumbelPlay{}, su);
             done = 0;
             if (lane == 0) t.leaf_status[g] = OZ_LEAF_IDLE;    // the evaluated leaf is consumed: nothing pending if the cap ends the loop here
             wave_sync();
@@ -2787,6 +2833,21 @@ __global__ __launch_bounds__(64) void k_backup_advance_x(GamesDev gm, MctsDev t,
     wave_sync();
     __syncthreads();
     advance_body<true>(gm, t, L, blockIdx.x, threadIdx.x, sims, sims_done, cap, xt);
+}
+
+// (the *_xs kernels: the EXTRAS kernels whose move records its policy surprise, launched by engines with record_surprise -- with or without
+// any other extra: each is looked at when it runs)
+__global__ __launch_bounds__(64) void k_advance_xs(GamesDev gm, MctsDev t, int sims, int* __restrict__ sims_done, int cap, SelfplayExtras xt, SurprisePlay su) {
+    __shared__ TreeLds L;
+    advance_body<true, true, true>(gm, t, L, blockIdx.x, threadIdx.x, sims, sims_done, cap, xt, su);
+}
+__global__ __launch_bounds__(64) void k_backup_advance_xs(GamesDev gm, MctsDev t, int sims, int* __restrict__ sims_done, int cap, SelfplayExtras xt,
+                                                          SurprisePlay su) {
+    __shared__ TreeLds L;
+    expand_backup_body(t, L, blockIdx.x, threadIdx.x, 0);
+    wave_sync();
+    __syncthreads();
+    advance_body<true, true, true>(gm, t, L, blockIdx.x, threadIdx.x, sims, sims_done, cap, xt, su);
 }
 
 // (the *_v kernels: the plain kernels whose move records root values, launched by engines with record_values and no other extra)
@@ -2895,6 +2956,13 @@ struct oz_selfplay {
     double *val_log = nullptr, *val_rec = nullptr;
     float* targets = nullptr;        // oz_selfplay_value_targets: [record_cap], allocated by the first call
     long long* d_vt = nullptr;       // ... and its three counters
+    // oz_selfplay_set_record_surprise: the buffers stay once allocated; su points at them while the option is on
+    double *sur_log = nullptr, *sur_rec = nullptr;
+    SurprisePlay su{nullptr, nullptr};
+    float* weights = nullptr;        // oz_selfplay_surprise_weights: [record_cap] each, allocated by the first call
+    int32_t* copies = nullptr;
+    uint8_t* first_sym = nullptr;
+    long long* d_sw = nullptr;       // ... and its five counters
     template <typename T> int alloc(T** p, size_t count) {
         OZ_HIP(hipMalloc((void**)p, sizeof(T) * (count ? count : 1)));
         allocs.push_back(*p);
@@ -3020,7 +3088,9 @@ static int selfplay_round_async(oz_selfplay* sp, int sims, int stagger_round) {
         }
     } else if (int rc = mcts_steps_async(m, sp->net, sims, G, true, capped ? &ck : nullptr)) return rc;
     timed(m, TS_MOVE, m->profile, [&] {
-        if (sp->gumbel_on) hipLaunchKernelGGL(k_sp_move_g, dim3(G), dim3(64), 0, s, sp->gm, m->d, GumbelPlay{m->gd, sp->gumbel_log, sp->gumbel_rows, sp->gumbel_moves});
+        if (sp->su.log && sp->gumbel_on) hipLaunchKernelGGL(k_sp_move_gs, dim3(G), dim3(64), 0, s, sp->gm, m->d, GumbelPlay{m->gd, sp->gumbel_log, sp->gumbel_rows, sp->gumbel_moves}, sp->su);
+        else if (sp->su.log) hipLaunchKernelGGL(k_sp_move_fs, dim3(G), dim3(64), 0, s, sp->gm, m->d, sp->sample, capped ? sp->cap : PlayoutCap{0, 0.0, nullptr, nullptr}, sp->forced, sp->su);
+        else if (sp->gumbel_on) hipLaunchKernelGGL(k_sp_move_g, dim3(G), dim3(64), 0, s, sp->gm, m->d, GumbelPlay{m->gd, sp->gumbel_log, sp->gumbel_rows, sp->gumbel_moves});
         else if (sp->forced.k > 0.0 || sp->gm.log_values) hipLaunchKernelGGL(k_sp_move_f, dim3(G), dim3(64), 0, s, sp->gm, m->d, sp->sample, capped ? sp->cap : PlayoutCap{0, 0.0, nullptr, nullptr}, sp->forced);
         else if (capped) hipLaunchKernelGGL(k_sp_move_c, dim3(G), dim3(64), 0, s, sp->gm, m->d, sp->sample, sp->cap);
         else if (sp->sample.plies > 0) hipLaunchKernelGGL(k_sp_move_s, dim3(G), dim3(64), 0, s, sp->gm, m->d, sp->sample);
@@ -3353,7 +3423,11 @@ OZ_API int oz_selfplay_run_steps(oz_selfplay* sp, int steps) {
         const int adv_cap = (sp->batch_cap > 0 && sp->batch_cap < d.G ? 1 : OZ_ADVANCE_CAP);
         // (from the second batch of a call on, the previous batch's expand + backup rides in the same launch; one closing k_expand_backup per call)
         timed(m, TS_SELECT, all, [&] {
-            if (m->noise_ever || sp->sample.plies > 0 || sp->cap.fast_sims > 0) {
+            if (sp->su.log) {
+                const SelfplayExtras xt{sp->noise_alpha, sp->gm.seed, sp->sample, sp->cap, sp->forced};
+                if (fuse && i > 0) hipLaunchKernelGGL(k_backup_advance_xs, dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap, xt, sp->su);
+                else hipLaunchKernelGGL(k_advance_xs, dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap, xt, sp->su);
+            } else if (m->noise_ever || sp->sample.plies > 0 || sp->cap.fast_sims > 0) {
                 const SelfplayExtras xt{sp->noise_alpha, sp->gm.seed, sp->sample, sp->cap, sp->forced};
                 if (fuse && i > 0) hipLaunchKernelGGL(k_backup_advance_x, dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap, xt);
                 else hipLaunchKernelGGL(k_advance_x, dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap, xt);
@@ -3737,6 +3811,221 @@ OZ_API int oz_value_targets(const oz_record* records, const double* values, int6
             out[ix] = (float)t;
         }
         lo = hi;
+    }
+    return OZ_OK;
+}
+
+// ---------------------------------------------------------------- policy surprise weighting ("policy surprise weighting" in the header)
+// surprises of the engine's searched moves: [G][64 plies] of the games in progress and one double per record.  Before the first driver call.
+OZ_API int oz_selfplay_set_record_surprise(oz_selfplay* sp, int enable) {
+    OZ_REQUIRE(sp, "null selfplay");
+    OZ_REQUIRE(enable == 0 || enable == 1, "oz_selfplay_set_record_surprise: enable = %d (0 or 1)", enable);
+    std::lock_guard<std::mutex> lk(sp->mu);
+    if (sp->mode != 0) { oz_set_error("oz_selfplay_set_record_surprise: the engine has been driven already (set it before the first driver call)"); return OZ_ERR_STATE; }
+    OZ_REQUIRE(!enable || sp->gm.record_visits || sp->gumbel_on,
+               "oz_selfplay_set_record_surprise: the surprise is that of a recorded policy target: create the engine with oz_selfplay_config.record_visits = 1 or "
+               "switch the Gumbel search on first (oz_selfplay_set_gumbel)");
+    if (enable && !sp->sur_log) {
+        hipSetDevice(sp->m->device);
+        const size_t held = sp->allocs.size(), G = (size_t)sp->gm.G, cap = (size_t)sp->gm.record_cap;
+        double *sur_log = nullptr, *sur_rec = nullptr;
+        int rc = sp->alloc(&sur_log, G * 64);
+        if (!rc) rc = sp->alloc(&sur_rec, cap);
+        if (!rc && (hipMemset(sur_log, 0, 8 * G * 64) != hipSuccess || hipMemset(sur_rec, 0, 8 * (cap ? cap : 1)) != hipSuccess)) {
+            oz_set_error("oz_selfplay_set_record_surprise: clearing the buffers failed");
+            rc = OZ_ERR_HIP;
+        }
+        if (rc) {
+            for (size_t i = held; i < sp->allocs.size(); ++i) hipFree(sp->allocs[i]);
+            sp->allocs.resize(held);
+            return rc;
+        }
+        sp->sur_log = sur_log; sp->sur_rec = sur_rec;
+    }
+    sp->su = enable ? SurprisePlay{sp->sur_log, sp->sur_rec} : SurprisePlay{nullptr, nullptr};
+    return OZ_OK;
+}
+#define OZ_REQUIRE_SURPRISE(sp) OZ_REQUIRE((sp)->su.rec, "this engine does not record policy surprise: call oz_selfplay_set_record_surprise(sp, 1) before the first driver call")
+OZ_API int oz_selfplay_surprises(oz_selfplay* sp, double* out, int64_t max_records, int64_t* written) {
+    OZ_REQUIRE(sp, "null selfplay");
+    OZ_REQUIRE_SURPRISE(sp);
+    return selfplay_rows(sp, sp->su.rec, sizeof(double), out, max_records, written, hipMemcpyDeviceToHost);
+}
+OZ_API int oz_selfplay_surprises_device(oz_selfplay* sp, void* dst_device, int64_t max_records, int64_t* written) {
+    OZ_REQUIRE(sp, "null selfplay");
+    OZ_REQUIRE_SURPRISE(sp);
+    return selfplay_rows(sp, sp->su.rec, sizeof(double), dst_device, max_records, written, hipMemcpyDeviceToDevice);
+}
+// the same surprises on the host (no device needed): the count rows are normalised at T = 1 as the move does, the float32 rows are widened
+static int policy_surprises(const char* fn, const int32_t* N, const float* q32, const double* P, int64_t count, double* out) {
+    OZ_REQUIRE(count >= 0, "%s: count %lld", fn, (long long)count);
+    if (count == 0) return OZ_OK;
+    OZ_REQUIRE((N || q32) && P && out, "%s: null argument", fn);
+    if (N) for (int64_t i = 0; i < count * 64; ++i) OZ_REQUIRE(N[i] >= 0, "%s: N[%lld][%d] = %d", fn, (long long)(i / 64), (int)(i % 64), N[i]);
+    for (int64_t i = 0; i < count; ++i) {
+        double q[64], term[64];
+        if (N) {
+            for (int sq = 0; sq < 64; ++sq) q[sq] = (double)N[i * 64 + sq];
+            const double sum = pairwise_sum(q, 64), divisor = sum == 0 ? 1.0 : sum;
+            for (int sq = 0; sq < 64; ++sq) q[sq] = q[sq] / divisor;
+        } else
+            for (int sq = 0; sq < 64; ++sq) q[sq] = (double)q32[i * 64 + sq];
+        for (int sq = 0; sq < 64; ++sq) term[sq] = oz_surprise_term(q[sq], P[i * 64 + sq]);
+        out[i] = oz_surprise_sum(term);
+    }
+    return OZ_OK;
+}
+OZ_API int oz_policy_surprises(const int32_t* N, const double* P, int64_t count, double* out) {
+    return policy_surprises("oz_policy_surprises", N, nullptr, P, count, out);
+}
+OZ_API int oz_policy_surprises_f32(const float* q, const double* P, int64_t count, double* out) {
+    return policy_surprises("oz_policy_surprises_f32", nullptr, q, P, count, out);
+}
+
+// One wavefront per record i of [first, have).  The record's ply says where its game starts (a game's records are contiguous and ascending
+// in ply): lane l loads record i - ply + l and belongs to the game while its game id and ply fit (a game has at most 60 plies: all of it is
+// inside the wave; one cut off by record_cap ends there).  K = the game's fully searched records (pad[0] == 0), S = pairwise_sum of their
+// surprises by lane = ply, zeros elsewhere; the record's weight, copy count and first symmetry: oz_surprise_weight / oz_surprise_copies
+// (oz_common.h).  Lane ply stores.  acc: [0] records [1] fully searched [2] examples [3] fully searched with no copy [4] the largest count
+__global__ __launch_bounds__(64) void k_surprise_weights(const oz_record* __restrict__ recs, const double* __restrict__ surprises, long long first,
+                                                         long long have, double om, double frac, uint64_t weight_seed, float* __restrict__ weights,
+                                                         int32_t* __restrict__ copies, uint8_t* __restrict__ first_sym, long long* __restrict__ acc) {
+    __shared__ double arr[64];
+    const int lane = threadIdx.x;
+    const long long i = first + blockIdx.x;
+    const int ply0 = unii((int)recs[i].ply);
+    const uint64_t gid0 = uni64(recs[i].game_id);
+    const long long j = i - ply0 + lane;
+    bool in = j >= 0 && j < have, full = false;
+    double s = 0.0;
+    if (in) {
+        const oz_record* r = recs + j;
+        in = r->game_id == gid0 && (int)r->ply == lane;
+        full = in && r->pad[0] == 0;
+        if (full) s = surprises[j];
+    }
+    const int K = oz_popc(__ballot(full));
+    arr[lane] = s;
+    __syncthreads();
+    const double S = pairwise_sum(arr, 64);
+    if (lane != ply0) return;
+    const uint64_t d = oz_rng(weight_seed, gid0, (uint64_t)ply0, OZ_RNG_SURPRISE);
+    const float w = full ? oz_surprise_weight(s, K, S, om, frac) : 0.0f;
+    const int c = full ? oz_surprise_copies(w, d) : 0;
+    weights[i] = w; copies[i] = c; first_sym[i] = (uint8_t)(d & 7);
+    atomicAdd((unsigned long long*)&acc[0], 1ULL);
+    if (full) {
+        atomicAdd((unsigned long long*)&acc[1], 1ULL);
+        atomicAdd((unsigned long long*)&acc[2], (unsigned long long)c);
+        if (c == 0) atomicAdd((unsigned long long*)&acc[3], 1ULL);
+        atomicMax((unsigned long long*)&acc[4], (unsigned long long)c);
+    }
+}
+
+static int surprise_frac_check(const char* fn, double frac) {
+    OZ_REQUIRE(frac > 0.0 && frac <= 1.0, "%s: frac %g outside (0, 1]", fn, frac);          // (NaN fails both compares)
+    return OZ_OK;
+}
+
+OZ_API int oz_selfplay_surprise_weights(oz_selfplay* sp, int64_t first_record, double frac, uint64_t weight_seed, oz_surprise_weight_stats* stats) {
+    OZ_REQUIRE(sp, "null selfplay");
+    if (int rc = surprise_frac_check("oz_selfplay_surprise_weights", frac)) return rc;
+    OZ_REQUIRE(first_record >= 0, "oz_selfplay_surprise_weights: first_record %lld", (long long)first_record);
+    std::lock_guard<std::mutex> lk(sp->mu);
+    OZ_REQUIRE_SURPRISE(sp);
+    if (sp->m->selected) { oz_set_error("oz_selfplay_surprise_weights: a step is pending (oz_mcts_select without oz_mcts_backup)"); return OZ_ERR_STATE; }
+    hipSetDevice(sp->m->device);
+    hipStream_t s = sp->m->stream;
+    OZ_HIP(hipStreamSynchronize(s));
+    unsigned long long total = 0;
+    OZ_HIP(hipMemcpy(&total, sp->gm.counters, 8, hipMemcpyDeviceToHost));
+    const long long have = (long long)total > sp->gm.record_cap ? sp->gm.record_cap : (long long)total;
+    const long long count = have > first_record ? have - first_record : 0;
+    OZ_REQUIRE(count < (1ll << 31), "too many records in one call");
+    if (!sp->first_sym) {
+        const size_t cap = (size_t)(sp->gm.record_cap ? sp->gm.record_cap : 1);
+        if (!sp->weights) { if (int rc = sp->alloc(&sp->weights, cap)) return rc; }
+        if (!sp->copies) { if (int rc = sp->alloc(&sp->copies, cap)) return rc; }
+        if (int rc = sp->alloc(&sp->first_sym, cap)) return rc;
+        OZ_HIP(hipMemsetAsync(sp->weights, 0, sizeof(float) * cap, s));
+        OZ_HIP(hipMemsetAsync(sp->copies, 0, sizeof(int32_t) * cap, s));
+        OZ_HIP(hipMemsetAsync(sp->first_sym, 0, cap, s));
+    }
+    long long acc[5] = {0, 0, 0, 0, 0};
+    if (count > 0) {
+        if (!sp->d_sw) { if (int rc = sp->alloc(&sp->d_sw, 5)) return rc; }
+        OZ_HIP(hipMemsetAsync(sp->d_sw, 0, sizeof acc, s));
+        const double om = 1.0 - frac;
+        hipLaunchKernelGGL(k_surprise_weights, dim3((unsigned)count), dim3(64), 0, s, sp->gm.records, sp->su.rec, (long long)first_record, have, om, frac,
+                           weight_seed, sp->weights, sp->copies, sp->first_sym, sp->d_sw);
+        OZ_HIP(hipGetLastError());
+        OZ_HIP(hipMemcpyAsync(acc, sp->d_sw, sizeof acc, hipMemcpyDeviceToHost, s));
+    }
+    OZ_HIP(hipStreamSynchronize(s));
+    if (stats) { stats->records = acc[0]; stats->full_records = acc[1]; stats->examples = acc[2]; stats->zero_copies = acc[3]; stats->max_copies = acc[4]; }
+    return OZ_OK;
+}
+#define OZ_REQUIRE_WEIGHTS(sp) OZ_REQUIRE((sp)->first_sym, "this engine holds no surprise weights: call oz_selfplay_surprise_weights first")
+OZ_API int oz_selfplay_weights(oz_selfplay* sp, float* weights, int32_t* copies, uint8_t* first_sym, int64_t max_records, int64_t* written) {
+    OZ_REQUIRE(sp, "null selfplay");
+    OZ_REQUIRE_WEIGHTS(sp);
+    OZ_REQUIRE(weights && copies && first_sym, "oz_selfplay_weights: null argument");
+    if (int rc = selfplay_rows(sp, sp->weights, sizeof(float), weights, max_records, written, hipMemcpyDeviceToHost)) return rc;
+    if (int rc = selfplay_rows(sp, sp->copies, sizeof(int32_t), copies, max_records, written, hipMemcpyDeviceToHost)) return rc;
+    return selfplay_rows(sp, sp->first_sym, 1, first_sym, max_records, written, hipMemcpyDeviceToHost);
+}
+// (for the replay buffer's weighted append: the copy counts and first symmetries, device to device)
+int oz_selfplay_copies_device(oz_selfplay* sp, void* copies_device, void* first_sym_device, int64_t max_records, int64_t* written) {
+    OZ_REQUIRE(sp, "null selfplay");
+    OZ_REQUIRE_WEIGHTS(sp);
+    if (int rc = selfplay_rows(sp, sp->copies, sizeof(int32_t), copies_device, max_records, written, hipMemcpyDeviceToDevice)) return rc;
+    return selfplay_rows(sp, sp->first_sym, 1, first_sym_device, max_records, written, hipMemcpyDeviceToDevice);
+}
+// the same weights on the host (no device needed): records in any order, grouped by game id and sorted by ply
+static void surprise_order(const oz_record* records, int64_t R, std::vector<int64_t>& order) {
+    order.resize((size_t)R);
+    for (int64_t i = 0; i < R; ++i) order[(size_t)i] = i;
+    std::stable_sort(order.begin(), order.end(), [records](int64_t a, int64_t b) {
+        return records[a].game_id != records[b].game_id ? records[a].game_id < records[b].game_id : records[a].ply < records[b].ply;
+    });
+}
+OZ_API int oz_surprise_weights(const oz_record* records, const double* surprises, int64_t R, double frac, float* w) {
+    if (int rc = surprise_frac_check("oz_surprise_weights", frac)) return rc;
+    OZ_REQUIRE(R >= 0, "oz_surprise_weights: R %lld", (long long)R);
+    if (R == 0) return OZ_OK;
+    OZ_REQUIRE(records && surprises && w, "oz_surprise_weights: null argument");
+    for (int64_t i = 0; i < R; ++i) OZ_REQUIRE(records[i].ply < 64, "oz_surprise_weights: records[%lld].ply = %d", (long long)i, (int)records[i].ply);
+    std::vector<int64_t> order;
+    surprise_order(records, R, order);
+    const double om = 1.0 - frac;
+    for (int64_t lo = 0; lo < R;) {
+        int64_t hi = lo + 1;
+        while (hi < R && records[order[(size_t)hi]].game_id == records[order[(size_t)lo]].game_id) ++hi;
+        double arr[64];
+        for (int l = 0; l < 64; ++l) arr[l] = 0.0;
+        int K = 0;
+        for (int64_t k = lo; k < hi; ++k) {
+            const int64_t ix = order[(size_t)k];
+            if (records[ix].pad[0] == 0) { ++K; arr[records[ix].ply] = surprises[ix]; }
+        }
+        const double S = pairwise_sum(arr, 64);
+        for (int64_t k = lo; k < hi; ++k) {
+            const int64_t ix = order[(size_t)k];
+            w[ix] = records[ix].pad[0] == 0 ? oz_surprise_weight(surprises[ix], K, S, om, frac) : 0.0f;
+        }
+        lo = hi;
+    }
+    return OZ_OK;
+}
+OZ_API int oz_surprise_copies(const oz_record* records, const float* w, int64_t R, uint64_t weight_seed, int32_t* copies, uint8_t* first_sym) {
+    OZ_REQUIRE(R >= 0, "oz_surprise_copies: R %lld", (long long)R);
+    if (R == 0) return OZ_OK;
+    OZ_REQUIRE(records && w && copies && first_sym, "oz_surprise_copies: null argument");
+    for (int64_t i = 0; i < R; ++i) {
+        OZ_REQUIRE(w[i] >= 0.0f && w[i] <= 64.0f, "oz_surprise_copies: w[%lld] = %g outside [0, 64]", (long long)i, (double)w[i]);
+        const uint64_t d = oz_rng(weight_seed, records[i].game_id, (uint64_t)records[i].ply, OZ_RNG_SURPRISE);
+        copies[i] = oz_surprise_copies(w[i], d);
+        first_sym[i] = (uint8_t)(d & 7);
     }
     return OZ_OK;
 }

@@ -297,20 +297,23 @@ def self_play_match(board_size, neural_network, old_neural_network, total_games,
 def _selfplay_into_replay(replay, neural_network, board_size, num_episodes, num_simulations, degree_exploration, temperature, e_greedy, seed,
                           first_game_id, q_mode, visits, leaves_per_step, root_noise, sample_moves, alias_final_boards, policy_target,
                           target_temperature, endgame_targets=0, solve_leaves=0, playout_cap=None, forced_playouts=0.0, value_target="outcome",
-                          gumbel=None):
+                          gumbel=None, surprise_weight=None):
     """one iteration's games on the engine selfplay_batch would create, played to the end without reading a record, and their examples
     appended to the device buffer; -> (records appended, the endgame solver's statistics or None).  One-channel (BaseNN) examples are never
     aliased (examples_from_records).  endgame_targets > 0: SelfPlayEngine.solve_records before the append.  playout_cap: the engine's; the
     append leaves the fast records out and counts the fully searched ones.  forced_playouts: the engine's; its visit rows, which the append
     reads, are then the pruned ones.  value_target: the engine records root values and the append computes the value targets (after the
-    endgame solver, exact_empties = endgame_targets).  gumbel: the engine's; policy_target="improved" appends its improved-policy rows."""
+    endgame solver, exact_empties = endgame_targets).  gumbel: the engine's; policy_target="improved" appends its improved-policy rows.
+    surprise_weight=(frac, weight_seed): the engine records policy surprise and the append writes c_i examples per record
+    (ReplayBuffer.append_engine(surprise_weight=...)); training.surprise_stats then holds the iteration's dict(records, examples,
+    mean_copies, max_copies, mean_surprise)."""
     from .training import SelfPlayEngine
     vt_on = _lib.check_value_target(value_target)[0] != _lib.VALUE_TARGET_OUTCOME
     eng = SelfPlayEngine(neural_network, board_size, num_episodes, num_simulations, degree_exploration, temperature, e_greedy, seed,
                          first_game_id, q_mode=q_mode, record_visits=visits, leaves_per_step=leaves_per_step, root_noise=root_noise,
                          sample_moves=sample_moves, solve_leaves=solve_leaves, **({"playout_cap": playout_cap} if playout_cap is not None else {}),
                          **({"forced_playouts": forced_playouts} if forced_playouts else {}), **({"record_values": True} if vt_on else {}),
-                         **({"gumbel": gumbel} if gumbel is not None else {}))
+                         **({"gumbel": gumbel} if gumbel is not None else {}), **({"record_surprise": True} if surprise_weight is not None else {}))
     for _ in range(board_size * board_size):
         eng.run(4)
         if eng.stats()["live_games"] == 0:
@@ -318,9 +321,18 @@ def _selfplay_into_replay(replay, neural_network, board_size, num_episodes, num_
     endgame = eng.solve_records(endgame_targets) if endgame_targets else None
     if solve_leaves:
         training.rows_solved += eng.rows_solved()
-    return replay.append_engine(eng, alias_final=alias_final_boards and getattr(neural_network, "in_channels", 2) == 2,
-                                policy_target=policy_target, target_temperature=target_temperature,
-                                **({"value_target": value_target, "exact_empties": endgame_targets} if vt_on else {})), endgame
+    appended = replay.append_engine(eng, alias_final=alias_final_boards and getattr(neural_network, "in_channels", 2) == 2,
+                                    policy_target=policy_target, target_temperature=target_temperature,
+                                    **({"value_target": value_target, "exact_empties": endgame_targets} if vt_on else {}),
+                                    **({"surprise_weight": surprise_weight} if surprise_weight is not None else {}))
+    if surprise_weight is not None:
+        st = replay.last_weight_stats
+        rec, sur = eng.records(with_surprise=True)
+        full = _lib.record_fast(rec) == 0
+        training.surprise_stats = dict(records=st["full_records"], examples=st["examples"], max_copies=st["max_copies"],
+                                       mean_copies=st["examples"] / st["full_records"] if st["full_records"] else 0.0,
+                                       mean_surprise=float(sur[full].mean()) if full.any() else 0.0)
+    return appended, endgame
 
 
 def _log_endgame(i, num_iterations, stats):
@@ -335,8 +347,17 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
              distributed=False, batched_evaluation=False, policy_target="onehot", target_temperature=1.0, leaves_per_step=1,
              root_noise=None, sample_moves=None, replay="host", evaluation_opponent="random", endgame_targets=0,
              solve_leaves=0, match_openings=None, evaluation_openings=None, playout_cap=None, forced_playouts=None, eval_symmetry=None,
-             value_target="outcome", gumbel=None):
+             value_target="outcome", gumbel=None, surprise_weight=None):
     """main.py:56-259 on the GPU engines; returns `historic` = [(episodes done, win rate vs random), ...]
+
+    surprise_weight=frac in (0, 1] (None = off, the default; KataGo uses 0.5): policy surprise weighting of the SELF-PLAY records.  The engine
+    keeps every searched move's surprise KL(policy target || root prior) (SelfPlayEngine(record_surprise=True)); a fully searched record of a
+    game with K of them weighs (1 - frac) + frac s K / S and becomes floor(8 w + u) examples of the device buffer instead of 8, so the
+    positions where the search overturned the prior take a larger share of the same amount of data.  The weight seed of iteration i is
+    seed + i.  It needs replay="device" and policy_target "visits" or "improved" (ValueError otherwise: the host example path writes 8
+    examples per record, distributed=True has no device buffer, and a one-hot target has no surprise to speak of).  Logs the examples
+    written, the mean and maximum copies per record and the mean surprise per iteration; training.surprise_history keeps the dicts.
+    Playing strength is neither gated nor claimed ("Policy surprise weighting").
 
     gumbel=(max_considered, c_visit, c_scale) or True (None = off, the default): the root search of Gumbel AlphaZero for every searched
     SELF-PLAY move (SelfPlayEngine), with replay="host" and replay="device" alike; matches and evaluations stay on PUCT.  It replaces
@@ -449,6 +470,18 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
     alias_final_boards=False.  Playing strength is neither gated nor claimed ("Value targets")."""
     vt_on = _lib.check_value_target(value_target, alias_final_boards)[0] != _lib.VALUE_TARGET_OUTCOME
     vt_kw = {"value_target": value_target} if vt_on else {}
+    training.surprise_history = []
+    if surprise_weight is not None:
+        surprise_weight = _lib.check_surprise_frac(surprise_weight)
+        if distributed:
+            raise ValueError("surprise_weight is not offered with distributed=True: the weighted append writes into the device replay buffer, which "
+                             "is single-process")
+        if replay != "device":
+            raise ValueError("surprise_weight needs replay='device': the weighted append writes a variable number of examples per record into the "
+                             "device replay buffer; the host example path writes 8 per record")
+        if policy_target not in ("visits", "improved"):
+            raise ValueError("surprise_weight needs policy_target='visits' or 'improved': the surprise is that of the search's policy target, and "
+                             "a one-hot target does not carry it")
     if eval_symmetry is not None:
         try:
             es_mode, es_seed = (eval_symmetry, 0) if isinstance(eval_symmetry, str) and eval_symmetry == "mean" else eval_symmetry
@@ -560,7 +593,13 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
                                                       degree_exploration, temperature, e_greedy, seed, total_episodes_done, q_mode, visits,
                                                       leaves_per_step, root_noise, sample_moves, alias_final_boards, policy_target,
                                                       target_temperature, endgame_targets, solve_leaves, playout_cap, forced_playouts, **vt_kw,
-                                                      **gumbel_kw)
+                                                      **gumbel_kw,
+                                                      **({"surprise_weight": (surprise_weight, seed + i)} if surprise_weight is not None else {}))
+            if surprise_weight is not None:
+                st = training.surprise_stats
+                training.surprise_history.append(st)
+                logging.info('[%d/%d] surprise weighting: %d examples from %d records / mean_copies %.3f / max_copies %d / mean_surprise %.4f', i,
+                             num_iterations, st["examples"], st["records"], st["mean_copies"], st["max_copies"], st["mean_surprise"])
             if endgame is not None:
                 training.endgame_history.append(endgame)
                 _log_endgame(i, num_iterations, endgame)

@@ -65,7 +65,7 @@ class ReplayBuffer:
         _lib.check(_lib.load().oz_replay_clear(self._h))
 
     def append_engine(self, eng, first_record=0, alias_final=False, policy_target="onehot", target_temperature=1.0, value_target="outcome",
-                      exact_empties=0, target=None):
+                      exact_empties=0, target=None, surprise_weight=None):
         """the records [first_record, completed so far) of a SelfPlayEngine -> 8 examples each, in ascending (game_id, ply), device to
         device; returns the number of records appended.  policy_target="visits" needs an engine created with record_visits=True.
         policy_target="improved" (or target="improved") needs an engine created with gumbel=...: every example's pi is its record's float32
@@ -73,10 +73,29 @@ class ReplayBuffer:
         The fast records of a playout cap (_lib.record_fast) are left out and not counted.
         value_target=("blend", w) / ("td", lam) (an engine created with record_values=True; alias_final=False): the engine computes the
         value targets of those records (SelfPlayEngine.value_targets(value_target, exact_empties, first_record)) and every example's z is
-        its record's float32 target instead of the game outcome; "outcome" is the call without it."""
+        its record's float32 target instead of the game outcome; "outcome" is the call without it.
+        surprise_weight=(frac, seed) (an engine created with record_surprise=True): policy surprise weighting.  The engine computes the
+        records' weights (SelfPlayEngine.surprise_weights(frac, seed, first_record)) and record i becomes c_i = floor(8 w_i + u_i) examples
+        instead of 8, the symmetries (t0_i + k) & 7; `total` advances by the sum of c_i, which self.last_examples then holds.  The return
+        value stays the number of non-fast records considered.  Combines with every policy and value target and with alias_final."""
         target, T = _target(policy_target if target is None else target, target_temperature, engine=True)
         mode, _ = _lib.check_value_target(value_target, alias_final)
         done = C.c_int64()
+        if surprise_weight is not None:
+            try:
+                frac, seed = surprise_weight
+            except (TypeError, ValueError):
+                raise ValueError(f"surprise_weight must be (frac, seed), got {surprise_weight!r}") from None
+            frac = _lib.check_surprise_frac(frac)
+            vt = mode != _lib.VALUE_TARGET_OUTCOME
+            if vt:
+                eng.value_targets(value_target, exact_empties=exact_empties, first_record=first_record)
+            self.last_weight_stats = eng.surprise_weights(frac, seed, first_record=first_record)
+            examples = C.c_int64()
+            _lib.check(_lib.load().oz_replay_append_selfplay_weighted(self._h, eng._h, int(first_record), 1 if alias_final else 0, target, T,
+                                                                      1 if vt else 0, C.byref(done), C.byref(examples)))
+            self.last_examples = examples.value
+            return done.value
         if mode != _lib.VALUE_TARGET_OUTCOME:
             eng.value_targets(value_target, exact_empties=exact_empties, first_record=first_record)
             _lib.check(_lib.load().oz_replay_append_selfplay_targets(self._h, eng._h, int(first_record), 0, target, T, C.byref(done)))

@@ -188,7 +188,7 @@ class SelfPlayEngine:
                  policy_temperature=1.0, e_greedy=0.9, seed=1234, first_game_id=0, game_id_stride=0,
                  q_mode=_lib.QMODE_F64, refill=False, node_cap=0, record_cap=0, dedup=True, batch_cap=0, eval_cache=False,
                  record_visits=False, leaves_per_step=1, root_noise=None, sample_moves=None, solve_leaves=0, playout_cap=None,
-                 forced_playouts=None, record_values=False, gumbel=None):
+                 forced_playouts=None, record_values=False, gumbel=None, record_surprise=False):
         """dedup: cross-game leaf de-duplication (a board several games reach in one batch is evaluated once; no record changes);
         batch_cap: leaves per network batch of the free-running driver (0 = none; see preferred_batch_cap);
         eval_cache: take (pi, v) of boards the network has evaluated before from its persistent cache (NNetWrapper.set_eval_cache) --
@@ -230,7 +230,12 @@ class SelfPlayEngine:
         (greedy == 3 in its record; pure Gumbel: e_greedy = 1).  The engine keeps the float32 improved-policy row softmax(logit + sigma(completed
         Q)) of every searched move: records(with_policies=True), the targets of loop.examples_from_records(policies=...).  16 KB per slot +
         256 B per record.  It replaces root_noise, forced_playouts and sample_moves, and does not combine with playout_cap or
-        leaves_per_step > 1 (ValueError); run_steps() and stagger() then raise.  gumbel_stats() counts (DESIGN.md, "Gumbel search")."""
+        leaves_per_step > 1 (ValueError); run_steps() and stagger() then raise.  gumbel_stats() counts (DESIGN.md, "Gumbel search").
+        record_surprise=True (needs record_visits=True or gumbel=...): keep every recorded move's policy surprise KL(q || p), q the row that
+        becomes its policy target and p the root's stored priors (oz_selfplay_set_record_surprise), for records(with_surprise=True) and
+        surprise_weights(); 512 B per slot + 8 B per record, no record changes.  Every driver ("Policy surprise weighting")."""
+        if record_surprise and not (record_visits or gumbel):
+            raise ValueError("record_surprise needs record_visits=True or gumbel=...: the surprise is that of a recorded policy target")
         gumbel = _lib.check_gumbel_options(gumbel, root_noise=root_noise, forced_playouts=forced_playouts, sample_moves=sample_moves,
                                            playout_cap=playout_cap, leaves_per_step=leaves_per_step)
         playout_cap = _lib.check_playout_cap(playout_cap, num_simulations)
@@ -274,6 +279,20 @@ class SelfPlayEngine:
         self.gumbel = gumbel
         if gumbel is not None:
             _lib.check(lib.oz_selfplay_set_gumbel(self._h, gumbel[0], gumbel[1], gumbel[2]))
+        self.record_surprise = bool(record_surprise)
+        if record_surprise:
+            _lib.check(lib.oz_selfplay_set_record_surprise(self._h, 1))
+
+    def surprise_weights(self, frac, seed, first_record=0):
+        """oz_selfplay_surprise_weights: weights, copy counts and first symmetries of the completed records from `first_record` on, computed
+        on the device (records(with_weights=True), ReplayBuffer.append_engine(surprise_weight=...)); the records are not touched.  A fully
+        searched record of a game with K of them gets w = (1 - frac) + frac s K / S, a fast record 0; it becomes floor(8 w + u) examples,
+        u and the first symmetry drawn per (seed, game id, ply).  frac in (0, 1] (KataGo: 0.5).  Needs record_surprise=True.
+        -> dict(records, full_records, examples, zero_copies, max_copies)."""
+        frac = _lib.check_surprise_frac(frac, "surprise_weights")
+        s = _lib.SurpriseWeightStats()
+        _lib.check(_lib.load().oz_selfplay_surprise_weights(self._h, int(first_record), frac, int(seed) & (2 ** 64 - 1), C.byref(s)))
+        return {k: int(getattr(s, k)) for k, _ in s._fields_}
 
     def gumbel_stats(self):
         """dict(max_considered, c_visit, c_scale, moves): the Gumbel search that is set (max_considered 0 = off) and the moves the Gumbel rule
@@ -415,20 +434,24 @@ class SelfPlayEngine:
         _lib.check(_lib.load().oz_selfplay_last_counts(self._h, _lib.p_i32(c)))
         return c
 
-    def records(self, with_visits=False, with_values=False, with_targets=False, with_policies=False):
+    def records(self, with_visits=False, with_values=False, with_targets=False, with_policies=False, with_surprise=False, with_weights=False):
         """move records of the games completed so far (numpy structured array, _lib.RECORD_DTYPE),
         sorted by (game_id, ply).  with_visits=True (engine created with record_visits=True): (records, counts), counts =
         int32 (R, 64) root visit counts of each record's move by square row*8+col, in the same order.
         with_values=True (record_values=True): (records, [counts,] values), values = float64 (R,) root value of each record's search.
         with_targets=True (after value_targets()): the float32 (R,) value targets follow, (records, [counts,] [values,] targets).
-        with_policies=True (gumbel=...): the float32 (R, 64) improved-policy rows by square come last."""
+        with_policies=True (gumbel=...): the float32 (R, 64) improved-policy rows by square follow.
+        with_surprise=True (record_surprise=True): the float64 (R,) policy surprises follow.
+        with_weights=True (after surprise_weights()): the tuple (w float32 (R,), copies int32 (R,), first_sym uint8 (R,)) comes last."""
         total = self.stats()["records"]
         out = np.zeros(max(total, 1), dtype=_lib.RECORD_DTYPE)
         written = C.c_int64()
         _lib.check(_lib.load().oz_selfplay_records(self._h, out.ctypes.data_as(C.c_void_p), total, C.byref(written)))
         out = out[:written.value]
         order = np.lexsort((out["ply"], out["game_id"]))
-        if not (with_visits or with_values or with_targets or with_policies):
+        if with_surprise and not self.record_surprise:
+            raise ValueError("records(with_surprise=True) needs an engine created with record_surprise=True")
+        if not (with_visits or with_values or with_targets or with_policies or with_surprise or with_weights):
             return out[order]
         ret = [out[order]]
         got = C.c_int64()
@@ -452,6 +475,16 @@ class SelfPlayEngine:
             _lib.check(_lib.load().oz_selfplay_policies(self._h, _lib.p_f32(rows), out.size, C.byref(got)))
             assert got.value == out.size, (got.value, out.size)
             ret.append(rows[:out.size][order])
+        if with_surprise:
+            sur = np.zeros(max(out.size, 1), np.float64)
+            _lib.check(_lib.load().oz_selfplay_surprises(self._h, _lib.p_f64(sur), out.size, C.byref(got)))
+            assert got.value == out.size, (got.value, out.size)
+            ret.append(sur[:out.size][order])
+        if with_weights:
+            w, c, t0 = np.zeros(max(out.size, 1), np.float32), np.zeros(max(out.size, 1), np.int32), np.zeros(max(out.size, 1), np.uint8)
+            _lib.check(_lib.load().oz_selfplay_weights(self._h, _lib.p_f32(w), _lib.p_i32(c), _lib.p_u8(t0), out.size, C.byref(got)))
+            assert got.value == out.size, (got.value, out.size)
+            ret.append((w[:out.size][order], c[:out.size][order], t0[:out.size][order]))
         return tuple(ret)
 
     def solve_records(self, max_empties, first_record=0):
@@ -574,8 +607,14 @@ def expand_examples(records, board_size, alias_final=False, visits=None, target_
 def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations=100, degree_exploration=1.0,
                    policy_temperature=1.0, e_greedy=0.9, seed=1234, first_game_id=0, q_mode=_lib.QMODE_F64,
                    expand=False, alias_final=False, record_visits=False, target_temperature=1.0, leaves_per_step=1, root_noise=None,
-                   sample_moves=None, endgame_targets=0, solve_leaves=0, playout_cap=None, forced_playouts=None, value_target="outcome", gumbel=None):
+                   sample_moves=None, endgame_targets=0, solve_leaves=0, playout_cap=None, forced_playouts=None, value_target="outcome", gumbel=None,
+                   surprise_weight=None):
     """Play num_games complete games; returns the move records (or the expanded examples).
+    surprise_weight=(frac, weight_seed): policy surprise weighting (SelfPlayEngine(record_surprise=True).surprise_weights; needs
+    record_visits=True or gumbel).  Two more entries come back last of all -- (records, ..., surprises, (w, copies, first_sym)): the float64
+    policy surprise of every record and its float32 weight, int32 copy count and uint8 first symmetry, for the device replay buffer's
+    weighted append or a consumer of one's own; not with expand (ValueError: the host example path does not weight).
+    selfplay_batch.surprise_stats holds the last call's SelfPlayEngine.surprise_weights() statistics (None when off).
     gumbel=(max_considered, c_visit, c_scale) or True: the Gumbel root search in every searched move (SelfPlayEngine).  The float32 (R, 64)
     improved-policy rows come back last -- (records, [counts,] [targets,] policies) -- for loop.examples_from_records(policies=...); not with
     expand (ValueError).  selfplay_batch.gumbel_stats holds the last call's SelfPlayEngine.gumbel_stats() (None when off).
@@ -601,6 +640,16 @@ def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations
                                        playout_cap=playout_cap, leaves_per_step=leaves_per_step)
     if gumbel is not None and expand:
         raise ValueError("selfplay_batch: gumbel with expand=True is not offered; expand the rows with loop.examples_from_records(policies=...)")
+    if surprise_weight is not None:
+        try:
+            sw_frac, sw_seed = surprise_weight
+        except (TypeError, ValueError):
+            raise ValueError(f"surprise_weight must be (frac, weight_seed), got {surprise_weight!r}") from None
+        sw_frac = _lib.check_surprise_frac(sw_frac)
+        if expand:
+            raise ValueError("selfplay_batch: surprise_weight with expand=True is not offered: the host example path writes 8 examples per record")
+        if not (record_visits or gumbel is not None):
+            raise ValueError("selfplay_batch: surprise_weight needs record_visits=True or gumbel=...: the surprise is that of a recorded policy target")
     forced_playouts = _lib.check_forced_playouts(forced_playouts, _lib.check_root_noise(root_noise))
     playout_cap = _lib.check_playout_cap(playout_cap, num_simulations)
     solve_leaves = _lib.check_solve_leaves(solve_leaves)
@@ -609,7 +658,14 @@ def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations
                          e_greedy, seed, first_game_id, q_mode=q_mode, record_visits=record_visits, leaves_per_step=leaves_per_step,
                          root_noise=root_noise, sample_moves=sample_moves, solve_leaves=solve_leaves, playout_cap=playout_cap,
                          **({"forced_playouts": forced_playouts} if forced_playouts > 0.0 else {}), **({"record_values": True} if vt_on else {}),
-                         **({"gumbel": gumbel} if gumbel is not None else {}))
+                         **({"gumbel": gumbel} if gumbel is not None else {}), **({"record_surprise": True} if surprise_weight is not None else {}))
+    selfplay_batch.surprise_stats = None
+
+    def weighted(ret):
+        if surprise_weight is None:
+            return ret
+        selfplay_batch.surprise_stats = eng.surprise_weights(sw_frac, sw_seed)
+        return (ret if isinstance(ret, tuple) else (ret,)) + eng.records(with_surprise=True, with_weights=True)[1:]
     selfplay_batch.value_target_stats = None
     selfplay_batch.gumbel_stats = None
     if gumbel is not None:                                 # (the options' statistics as below; the rows come last)
@@ -619,7 +675,7 @@ def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations
         selfplay_batch.value_target_stats = getattr(eng, "value_target_stats", None)
         selfplay_batch.forced_playout_stats = selfplay_batch.playout_stats = None
         selfplay_batch.rows_solved = eng.rows_solved() if solve_leaves else None
-        return got
+        return weighted(got)
     if vt_on:
         got = eng.play_to_end(with_visits=record_visits, endgame_targets=endgame_targets, value_target=value_target)
         rec, counts, targets = got if record_visits else (got[0], None, got[1])
@@ -630,7 +686,7 @@ def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations
         selfplay_batch.rows_solved = eng.rows_solved() if solve_leaves else None
         if expand:
             return expand_examples(rec, board_size, alias_final, visits=counts, target_temperature=target_temperature, values=targets)
-        return (rec, counts, targets) if record_visits else (rec, targets)
+        return weighted((rec, counts, targets) if record_visits else (rec, targets))
     selfplay_batch.endgame_stats = selfplay_batch.rows_solved = selfplay_batch.playout_stats = selfplay_batch.forced_playout_stats = None
     if record_visits:
         rec, counts = eng.play_to_end(with_visits=True, endgame_targets=endgame_targets)
@@ -638,7 +694,7 @@ def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations
         selfplay_batch.playout_stats = eng.playout_stats() if playout_cap is not None else None
         selfplay_batch.rows_solved = eng.rows_solved() if solve_leaves else None
         selfplay_batch.endgame_stats = getattr(eng, "endgame_stats", None)
-        return expand_examples(rec, board_size, alias_final, visits=counts, target_temperature=target_temperature) if expand else (rec, counts)
+        return expand_examples(rec, board_size, alias_final, visits=counts, target_temperature=target_temperature) if expand else weighted((rec, counts))
     rec = eng.play_to_end(endgame_targets=endgame_targets)
     selfplay_batch.forced_playout_stats = eng.forced_playout_stats() if forced_playouts > 0.0 else None
     selfplay_batch.playout_stats = eng.playout_stats() if playout_cap is not None else None
