@@ -452,6 +452,48 @@ int oz_mcts_sample_moves(oz_mcts* m, double temperature, uint64_t seed, const ui
 int oz_playout_budgets(uint64_t seed, const uint64_t* game_ids, const int32_t* plies, int64_t count, int sims, int fast_sims,
                        double full_prob, int32_t* out /* [count] */);
 
+/* ---- resignation: stop a decided self-play game early, play a fixed share out regardless as an audit (opt-in, AlphaGo Zero's and KataGo's;
+ * off, every launch, record and row stays bit for bit).  A decided game otherwise keeps running full searches until the last disc is placed,
+ * and its last records carry the outcome of noise played after the game was decided.  With (v, r, min_ply, keep_prob), 0 < v <= 1,
+ * 1 <= r <= 8, 0 <= min_ply <= 64, 0 <= keep_prob <= 1, every game holds side in {-1, 0, +1} and streak, both 0 at its start.  After the
+ * search of the self-play move of (game id, ply i), mover p_i = +-1, root value q_i (oz_root_term / oz_root_mean over the RAW counts, "value
+ * targets" below), all in float64:
+ *     b = p_i * q_i                                                   the root value from BLACK's side
+ *     c = b >= v ? +1 : b <= -v ? -1 : 0                               NaN: 0
+ *     c == 0:    side = 0, streak = 0;   c == side:  streak = min(streak + 1, 255);   otherwise:  side = c, streak = 1
+ *     trigger_i = streak >= r && i >= min_ply
+ * ONE function, oz_resign_step (csrc/oz_common.h), is what the move kernels and oz_resign_scan evaluate.  Every searched self-play move
+ * updates the state: the fast moves of a playout cap and the moves of the explore branch too.
+ * A game is EXEMPT iff the unit draw of the library's stream (seed, game id, 0, OZ_RNG_RESIGN = 9) is < keep_prob -- stream 9 is none of
+ * 0 .. 8, none of the root-noise streams 3 + 256 sq + 65536 i and none of the Gumbel streams 7 + 256 sq (oz_resign_exempt).
+ *   * a game that is not exempt, at its first trigger, where move i does not end the game by itself: move i is chosen, logged and played as
+ *     ever, then the game ends as ADJUDICATED: winner = side, final_black / final_white = the board after move i, every record of the game
+ *     has z = +1 iff winner == player and pad[1] == 1 (the second spare byte of oz_record; the layout does not change).  games_completed,
+ *     moves, records, the visit, value, policy and surprise rows and the refill behave exactly as at a natural end.
+ *   * where move i ends the game by itself the natural result stands, pad[1] == 0, and the game is not counted as adjudicated.
+ *   * an exempt game remembers its first trigger (ply and side; one at the game's last move counts) and plays on; its records have
+ *     pad[1] == 0.  At its end it is counted in games_exempt, and where it triggered in exempt_triggered, its remembered ply added to
+ *     exempt_trigger_ply_sum, and in exempt_wrong iff the natural winner (a draw goes to BLACK, as in oz_record.z) is not the remembered
+ *     side: exempt_wrong / exempt_triggered is the rule's false-positive rate, the number v is tuned by.
+ *   * keep_prob == 1: every game is exempt -- the bytes of the engine without the option, and the counters still measure the rule.
+ *   * never touched: the arena, matches and evaluations, the bare oz_mcts.  pad[2] stays 0. */
+typedef struct {
+    int64_t games_adjudicated;      /* games ended by the rule */
+    int64_t adjudicated_plies_sum;  /* the plies those games were played for (their records) */
+    int64_t games_exempt;           /* exempt games completed */
+    int64_t exempt_triggered;       /* of them, games in which the rule triggered */
+    int64_t exempt_wrong;           /* of them, games whose natural winner is not the side the first trigger called */
+    int64_t exempt_trigger_ply_sum; /* the plies of those first triggers, summed over exempt_triggered */
+} oz_resign_stats;
+/* the first trigger of `games` sequences on the host (no device needed): game g is the next plies_per_game[g] entries of players (+-1) and
+ * values, ply 0 first; trigger_ply[g] = the ply, trigger_side[g] = the side it calls the game for, or -1 and 0 where the rule never
+ * triggers.  OZ_ERR_ARG: v outside (0, 1], r outside [1, 8], min_ply outside [0, 64] (NaN included), a negative length, a player not +-1. */
+int oz_resign_scan(const int8_t* players, const double* values, const int32_t* plies_per_game, int64_t games, double v, int r, int min_ply,
+                   int32_t* trigger_ply /* [games] */, int8_t* trigger_side /* [games] */);
+/* out[i] = 1 where the game with id game_ids[i] is exempt under (seed, keep_prob), else 0; on the host (no device needed).  OZ_ERR_ARG:
+ * keep_prob outside [0, 1] (NaN included). */
+int oz_resign_exempt(uint64_t seed, const uint64_t* game_ids, int64_t count, double keep_prob, uint8_t* out /* [count] */);
+
 /* ---- forced playouts: forced playouts and policy target pruning for the noisy root (opt-in, KataGo's; off, every launch, record and row stays
  * bit for bit).  At ~100 simulations a move the noise favours but the prior dismisses gets a visit or two and is dropped: if it is good the
  * search never finds out, if it is bad its visits stay in the row policy_target="visits" trains on.  With the forcing constant k (KataGo: 2.0;
@@ -609,7 +651,8 @@ typedef struct {
     uint8_t greedy;         /* 1 = greedy branch of the coin (arg-max), 0 = explore branch (uniform legal move), 2 = greedy branch, move
                              * drawn by move sampling (oz_selfplay_set_move_sampling; ply < plies) */
     uint8_t pad[3];         /* pad[0]: 0 = the move was searched on the full budget, 1 = on the fast one ("playout cap" above: not a training
-                             * example); always 0 without the option.  pad[1], pad[2]: 0 */
+                             * example); always 0 without the option.  pad[1]: 1 = the game was adjudicated ("resignation" above: z and the final board are those
+                             * of the stop), else 0.  pad[2]: 0 */
 } oz_record;
 
 typedef struct {
@@ -677,6 +720,17 @@ int oz_selfplay_set_forced_playouts(oz_selfplay* sp, double k);
 /* what is set and, since it was armed: the moves whose recorded row differs from the raw counts, and the visits before / after pruning summed
  * over every move pruning ran on (the moves with an armed root).  Every pointer may be NULL; reading a counter waits for the engine's stream. */
 int oz_selfplay_get_forced_playouts(oz_selfplay* sp, double* k, int64_t* moves_pruned, int64_t* visits_raw, int64_t* visits_kept);
+/* self-play with resignation ("resignation" above), keyed (cfg.seed, game id).  Holds for oz_selfplay_run at any leaves_per_step, with root
+ * noise, move sampling, a playout cap, forced playouts, record_visits, recorded surprise, solved leaves, oz_selfplay_solve_records and the
+ * value targets (the TD chain then ends in the adjudicated z).  Needs oz_selfplay_set_record_values(sp, 1) first -- the rule reads the root
+ * value the move computes for it -- and comes before the first driver call (OZ_ERR_STATE otherwise).  OZ_ERR_STATE also: together with
+ * the Gumbel search (whichever comes second is refused), and, once it is armed, oz_selfplay_run_steps, oz_selfplay_stagger and
+ * oz_selfplay_set_record_values(sp, 0).  r == 0 disarms (the other arguments are then not looked at).  OZ_ERR_ARG: v outside (0, 1], r
+ * outside [0, 8], min_ply outside [0, 64], keep_prob outside [0, 1] (NaN included).  The engine stays usable after a refusal.  4 B per slot
+ * + 48 B of device memory at the first arming. */
+int oz_selfplay_set_resign(oz_selfplay* sp, double v, int r, int min_ply, double keep_prob);
+/* what is set (r 0 = off) and the counters since the arming.  Every pointer may be NULL; reading the counters waits for the engine's stream. */
+int oz_selfplay_get_resign(oz_selfplay* sp, double* v, int* r, int* min_ply, double* keep_prob, oz_resign_stats* stats);
 int oz_selfplay_sync(oz_selfplay* sp);
 /* continuous self-play (cfg.refill): bring a fresh engine to the steady state of a long-running one before measuring it --
  * slot g is advanced (g * P) / num_games plies into its first game, P = n*n - 4, by searched self-play moves at `sims_pre`

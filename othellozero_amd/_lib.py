@@ -87,6 +87,11 @@ class SurpriseWeightStats(C.Structure):                                         
                 ("max_copies", C.c_int64)]
 
 
+class ResignStats(C.Structure):                                                      # oz_resign_stats
+    _fields_ = [("games_adjudicated", C.c_int64), ("adjudicated_plies_sum", C.c_int64), ("games_exempt", C.c_int64),
+                ("exempt_triggered", C.c_int64), ("exempt_wrong", C.c_int64), ("exempt_trigger_ply_sum", C.c_int64)]
+
+
 class ValueTargetStats(C.Structure):                                                 # oz_value_target_stats
     _fields_ = [("records", C.c_int64), ("exact", C.c_int64), ("sign_changed", C.c_int64)]
 
@@ -110,12 +115,19 @@ RECORD_DTYPE = np.dtype([
 ])
 assert RECORD_DTYPE.itemsize == 48
 RNG_PLAYOUT = 6                                                                      # OZ_RNG_PLAYOUT
+RNG_RESIGN = 9                                                                       # OZ_RNG_RESIGN
 
 
 def record_fast(records):
     """the playout-cap flag of move records (RECORD_DTYPE): uint8, 1 = the move was searched on the fast budget (no training example),
     0 = on the full one; the first spare byte of oz_record, always 0 without the option"""
     return np.asarray(records)["pad"][..., 0]
+
+
+def record_adjudicated(records):
+    """the resignation flag of move records (RECORD_DTYPE): uint8, 1 = the record's game was adjudicated (stopped by the resignation rule: z
+    and the final board are those of the stop), 0 = it was played to its end; the second spare byte of oz_record, always 0 without the option"""
+    return np.asarray(records)["pad"][..., 1]
 
 
 def full_records(records, visits=None):
@@ -205,6 +217,10 @@ SIGNATURES = {
     "oz_selfplay_set_forced_playouts": [_vp, C.c_double],
     "oz_selfplay_get_forced_playouts": [_vp, _f64p, _i64p, _i64p, _i64p],
     "oz_playout_budgets": [C.c_uint64, _u64p, _i32p, C.c_int64, C.c_int, C.c_int, C.c_double, _i32p],
+    "oz_selfplay_set_resign": [_vp, C.c_double, C.c_int, C.c_int, C.c_double],
+    "oz_selfplay_get_resign": [_vp, _f64p, C.POINTER(C.c_int), C.POINTER(C.c_int), _f64p, C.POINTER(ResignStats)],
+    "oz_resign_scan": [_i8p, _f64p, _i32p, C.c_int64, C.c_double, C.c_int, C.c_int, _i32p, _i8p],
+    "oz_resign_exempt": [C.c_uint64, _u64p, C.c_int64, C.c_double, _u8p],
     "oz_mcts_set_gumbel": [_vp, C.c_int, C.c_double, C.c_double, C.c_int, _f64p, _u8p],
     "oz_mcts_sample_gumbel": [_vp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_uint64, _u64p, _i32p],
     "oz_mcts_get_gumbel": [_vp, _f64p, _u8p, _i32p, _i32p, _f64p, _f64p, _i32p],
@@ -557,6 +573,38 @@ def check_playout_cap(playout_cap, num_simulations=None):
     if not 0.0 < full_prob <= 1.0:
         raise ValueError(f"playout_cap: full_prob must be in (0, 1] (got {full_prob})")
     return fast_sims, full_prob
+
+
+def check_resign(resign, gumbel=None, free_running=False):
+    """resign = None or (v, r, min_ply, keep_prob): resignation of decided self-play games with a played-out audit share
+    (include/othellozero_amd.h, "resignation").  A game whose root values, seen from BLACK, stayed at or beyond +-v for r searched moves in
+    a row is stopped from ply min_ply on and given to that side; a share keep_prob of the games, drawn per (seed, game id), is played out
+    regardless and measures the rule.  Returns None or (float, int, int, float); ValueError for anything the library would refuse: v in
+    (0, 1], r a whole number in [1, 8], min_ply a whole number in [0, 64], keep_prob in [0, 1] (NaN refused), and together with gumbel or the
+    free-running driver."""
+    if resign is None:
+        return None
+    bad = f"resign must be None or (v, r, min_ply, keep_prob), got {resign!r}"
+    try:
+        v, r, min_ply, keep_prob = resign
+        if any(isinstance(x, (bool, str, bytes)) for x in (v, r, min_ply, keep_prob)) or int(r) != r or int(min_ply) != min_ply:
+            raise ValueError
+        v, r, min_ply, keep_prob = float(v), int(r), int(min_ply), float(keep_prob)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(bad) from None
+    if not 0.0 < v <= 1.0:
+        raise ValueError(f"resign: v must be in (0, 1] (got {v})")
+    if not 1 <= r <= 8:
+        raise ValueError(f"resign: r must be in [1, 8] (got {r})")
+    if not 0 <= min_ply <= 64:
+        raise ValueError(f"resign: min_ply must be in [0, 64] (got {min_ply})")
+    if not 0.0 <= keep_prob <= 1.0:
+        raise ValueError(f"resign: keep_prob must be in [0, 1] (got {keep_prob})")
+    if gumbel is not None and gumbel is not False:
+        raise ValueError("resign does not combine with gumbel")
+    if free_running:
+        raise ValueError("resign holds for the lock-step rounds only (not the free-running driver, not stagger)")
+    return v, r, min_ply, keep_prob
 
 
 def playout_budgets(seed, game_ids, plies, num_simulations, playout_cap):

@@ -129,6 +129,35 @@ def rules_value_targets(records, values, n, value_target, exact_empties=0):
     return out
 
 
+def rules_resign_scan(players, values, plies_per_game, v, r, min_ply):
+    """oz_resign_scan: the first trigger of the resignation rule in each of several games, on the host (no GPU needed).  players int8 (+-1)
+    and values float64: the movers and root values of the games' searched moves, one game after the other, ply 0 first; plies_per_game int32
+    (games,): how many entries each game has; v, r, min_ply: the rule (the exemption is not looked at here).  -> (trigger_ply
+    int32 (games,), trigger_side int8 (games,)): the ply of the first trigger and the side it calls the game for, -1 and 0 where the rule
+    never triggers.  The function the move kernels evaluate (include/othellozero_amd.h, "resignation")."""
+    v, r, min_ply, _keep = _lib.check_resign((v, r, min_ply, 0.0))
+    p_ = np.ascontiguousarray(players, dtype=np.int8).ravel()
+    q_ = np.ascontiguousarray(values, dtype=np.float64).ravel()
+    n_ = np.ascontiguousarray(plies_per_game, dtype=np.int32).ravel()
+    if p_.size != q_.size or (n_ < 0).any() or int(n_.sum(dtype=np.int64)) != p_.size:
+        raise ValueError(f"{p_.size} players and {q_.size} values for games of {int(n_.sum(dtype=np.int64))} plies in all")
+    ply, side = np.full(n_.size, -1, np.int32), np.zeros(n_.size, np.int8)
+    _lib.check(_lib.load().oz_resign_scan(_lib.p_i8(p_), _lib.p_f64(q_), _lib.p_i32(n_), n_.size, v, r, min_ply, _lib.p_i32(ply), _lib.p_i8(side)))
+    return ply, side
+
+
+def rules_resign_exempt(seed, game_ids, keep_prob):
+    """oz_resign_exempt on the host (no GPU needed): bool (count,), True where the game with that id is played out regardless of the
+    resignation rule under (seed, keep_prob) -- the unit draw of stream (seed, game id, 0, OZ_RNG_RESIGN) is below keep_prob"""
+    keep_prob = float(keep_prob)
+    if not 0.0 <= keep_prob <= 1.0:
+        raise ValueError(f"resign: keep_prob must be in [0, 1] (got {keep_prob})")
+    ids = np.ascontiguousarray(game_ids, dtype=np.uint64).ravel()
+    out = np.zeros(ids.size, np.uint8)
+    _lib.check(_lib.load().oz_resign_exempt(int(seed) & (2 ** 64 - 1), _lib.p_u64(ids), ids.size, keep_prob, _lib.p_u8(out)))
+    return out.astype(bool)
+
+
 def rules_gumbel_considered_visits(m, n):
     """oz_gumbel_considered_visits on the host (no GPU needed): the sequential-halving schedule of a Gumbel root that considers m moves over n
     simulations -> int32 (n,): the visit count the pick of simulation t must match (include/othellozero_amd.h, "Gumbel search")"""

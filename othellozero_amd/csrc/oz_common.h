@@ -24,7 +24,7 @@ OZ_HD uint64_t oz_sm64(uint64_t z) {
 }
 OZ_HD uint64_t oz_rotl64(uint64_t x, int r) { return (x << r) | (x >> (64 - r)); }
 
-enum { OZ_RNG_COIN = 0, OZ_RNG_EXPLORE = 1, OZ_RNG_TIE = 2, OZ_RNG_NOISE = 3, OZ_RNG_SAMPLE = 4, OZ_RNG_OPENING = 5, OZ_RNG_PLAYOUT = 6, OZ_RNG_GUMBEL = 7, OZ_RNG_SURPRISE = 8 };
+enum { OZ_RNG_COIN = 0, OZ_RNG_EXPLORE = 1, OZ_RNG_TIE = 2, OZ_RNG_NOISE = 3, OZ_RNG_SAMPLE = 4, OZ_RNG_OPENING = 5, OZ_RNG_PLAYOUT = 6, OZ_RNG_GUMBEL = 7, OZ_RNG_SURPRISE = 8, OZ_RNG_RESIGN = 9 };
 // GUMBEL: stream 7 + 256 * square, the Gumbel draw of a root's square (Gumbel search below).  7 + 256 sq is none of 0 .. 6 for sq >= 1 and is 7 for
 // sq == 0; it is none of 3 + 256 sq' + 65536 i either: that would need 4 == 256 (sq' - sq) + 65536 i, and the right side is a multiple of 256.
 // NOISE: stream 3 + 256 * square + 65536 * draw (root noise, oz_search.hip); SAMPLE: the one unit draw of a sampled move (move sampling,
@@ -32,6 +32,10 @@ enum { OZ_RNG_COIN = 0, OZ_RNG_EXPLORE = 1, OZ_RNG_TIE = 2, OZ_RNG_NOISE = 3, OZ
 // (oz_openings.h) -- nor is 5; PLAYOUT: the full / fast draw of a self-play move (playout cap, oz_playout_budget below) -- nor is 6
 // SURPRISE: the draw of a record's copy count and first symmetry (policy surprise weighting below), keyed (weight seed, game id, ply) -- 8 is
 // none of 3 + 256 sq + 65536 i, and 7 + 256 sq == 8 has no solution
+// RESIGN: the one unit draw that exempts a game from resignation (resignation below), keyed (seed, game id, 0) -- 9 is none of 0 .. 8; it is none
+// of 3 + 256 sq + 65536 i (6 is no multiple of 256) and none of 7 + 256 sq (nor is 2)
+static_assert(OZ_RNG_RESIGN > OZ_RNG_SURPRISE && (OZ_RNG_RESIGN - OZ_RNG_NOISE) % 256 != 0 && (OZ_RNG_RESIGN - OZ_RNG_GUMBEL) % 256 != 0,
+              "OZ_RNG_RESIGN collides with another stream");
 // counter-based stream replacing random.random / np.random.choice / random.choice
 // (training.py:51,56; othelo_mcts.py:59): keyed (seed, global game id, ply, purpose)
 OZ_HD uint64_t oz_rng(uint64_t seed, uint64_t game, uint64_t move, uint64_t stream) {
@@ -431,6 +435,25 @@ OZ_HD double oz_value_target_td_step(double pq, double b_next, double om, double
     const double a = om * pq, b = lam * b_next;
     return a + b;
 }
+
+// ---------------------------------------------------------------- resignation
+// (include/othellozero_amd.h, "resignation").  The state of one game: side = whose win the last root values called (+1 BLACK, -1 WHITE, 0
+// nobody's), streak = how many searched moves in a row called it (saturating at 255).  oz_resign_step takes the state over the searched move of
+// ply `ply` with mover p = +-1 and root value q (oz_root_mean of the RAW counts, for the mover) and says whether the rule triggers there:
+// b = p q is the value from BLACK's side; c = +1 where b >= v, -1 where b <= -v, else 0 (NaN fails both compares: 0).  float64, no contraction.
+// oz_resign_is_exempt: the game is played out regardless (the audit share).  The one definition the move (oz_search.hip) and the host's
+// oz_resign_scan / oz_resign_exempt share.
+struct OzResign { int side, streak; };
+OZ_HD bool oz_resign_step(OzResign& st, int p, double q, double v, int r, int min_ply, int ply) {
+#pragma clang fp contract(off)
+    const double b = (double)p * q;
+    const int c = b >= v ? 1 : b <= -v ? -1 : 0;
+    if (c == 0) { st.side = 0; st.streak = 0; }
+    else if (c == st.side) st.streak = st.streak + 1 < 255 ? st.streak + 1 : 255;
+    else { st.side = c; st.streak = 1; }
+    return st.streak >= r && ply >= min_ply;
+}
+OZ_HD bool oz_resign_is_exempt(uint64_t seed, uint64_t game, double keep_prob) { return oz_rng_unit(oz_rng(seed, game, 0, OZ_RNG_RESIGN)) < keep_prob; }
 
 // ---------------------------------------------------------------- policy surprise weighting
 // (include/othellozero_amd.h, "policy surprise weighting").  The surprise of a searched move: s = KL(q || p), q the policy target row of the

@@ -2509,14 +2509,31 @@ struct SurprisePlay {
     double* log;                           // [G][64 plies]
     double* rec;                           // [record_cap]
 };
+// RESIGN (an engine with resignation, oz_selfplay_set_resign; "resignation" in the header; lock-step rounds only; rs.r > 0 where it is on): the
+// slot's (side, streak) take the move's root value -- the VALUES rootv, no second routine -- through oz_resign_step (oz_common.h).  At the first
+// trigger of a game that is not exempt, where the move does not end the game by itself, the game ends through the `fin` branch with the winner
+// overridden and pad[1] = 1 in its records; an exempt game remembers its first trigger and is counted at its natural end.  Lane 0 resets the
+// slot's state where the game ends.  Instantiations of its own (k_sp_move_r / k_sp_move_rs): every other kernel stays the code it was.  Never
+// in the arena.
+struct ResignPlay {
+    double v, keep_prob;
+    int r, min_ply;                        // r > 0 = on
+    int8_t* side;                          // [G] whose win the last root values called (+1 BLACK, -1 WHITE, 0 nobody's)
+    uint8_t* streak;                       // [G] for how many searched moves in a row
+    int8_t* ex_side;                       // [G] exempt game: the side of its first trigger, 0 = none yet
+    uint8_t* ex_ply;                       // [G] ... and its ply
+    unsigned long long* stat;              // [6] oz_resign_stats in its order
+};
 // (calls, not inlined code: a 64-term pairwise_sum of constant length is unrolled into 64 loads in flight, 128 VGPRs; inlined into the move
 // they cost the free-running advance a wave of occupancy for all of its simulations, and the sums run once per move)
 __device__ __noinline__ double surprise_row_sum(const double* a) { return pairwise_sum(a, 64); }
 __device__ __noinline__ double surprise_sum(const double* term) { return oz_surprise_sum(term); }
-template <bool NOISE = false, bool SAMPLE = false, bool CAP = false, bool FORCE = false, bool VALUES = false, bool GUMBEL = false, bool SURPRISE = false>
+template <bool NOISE = false, bool SAMPLE = false, bool CAP = false, bool FORCE = false, bool VALUES = false, bool GUMBEL = false, bool SURPRISE = false,
+          bool RESIGN = false>
 __device__ __forceinline__ void sp_move_body(const GamesDev& gm, const MctsDev& t, int g, int lane, int arena, MoveSampling ms = MoveSampling{},
                                              PlayoutCap pc = PlayoutCap{}, ForcedPlayouts fp = ForcedPlayouts{}, GumbelPlay gp = GumbelPlay{},
-                                             SurprisePlay su = SurprisePlay{}) {
+                                             SurprisePlay su = SurprisePlay{}, ResignPlay rs = ResignPlay{}) {
+    static_assert(!RESIGN || VALUES, "resignation reads the root value the VALUES move computes");
     if (!t.active[g]) return;
     bool prune = false;
     (void)prune;
@@ -2637,11 +2654,44 @@ __device__ __forceinline__ void sp_move_body(const GamesDev& gm, const MctsDev& 
             }
         }
     }
+    // resignation: the slot's state takes this move's root value (oz_resign_step, oz_common.h); every value below is wave-uniform
+    OzResign rst{0, 0};
+    bool rtrig = false, rexempt = false, adjudicated = false;
+    int rex_side = 0, rex_ply = 0;
+    (void)rst; (void)rtrig; (void)rexempt; (void)adjudicated; (void)rex_side; (void)rex_ply;
+    if constexpr (RESIGN) {
+        if (rs.r > 0) {
+            rst = OzResign{unii((int)rs.side[g]), unii((int)rs.streak[g])};
+            rtrig = oz_resign_step(rst, player, rootv, rs.v, rs.r, rs.min_ply, ply);
+            rexempt = oz_resign_is_exempt(gm.seed, gid, rs.keep_prob);
+            rex_side = unii((int)rs.ex_side[g]); rex_ply = unii((int)rs.ex_ply[g]);
+            if (rtrig && rexempt && rex_side == 0) { rex_side = rst.side; rex_ply = ply; }       // the first trigger of an exempt game
+        }
+    }
     oz_game_play(black, white, player, fin, action, gm.valid);
     const int nply = ply + 1;
+    if constexpr (RESIGN) {
+        if (rtrig && !rexempt && !fin) { adjudicated = true; fin = 1; }       // the move was played as ever; the game stops here
+    }
     if (fin) {
         // get_winning_player: draw -> BLACK; z = +1 if winner == mover else -1 (training.py:69-72)
-        const int winner = oz_popc(black) >= oz_popc(white) ? 1 : -1;
+        int winner = oz_popc(black) >= oz_popc(white) ? 1 : -1;
+        if constexpr (RESIGN) {
+            if (rs.r > 0 && lane == 0) {
+                if (adjudicated) {
+                    atomicAdd(&rs.stat[0], 1ULL);
+                    atomicAdd(&rs.stat[1], (unsigned long long)nply);
+                } else if (rexempt) {
+                    atomicAdd(&rs.stat[2], 1ULL);
+                    if (rex_side != 0) {
+                        atomicAdd(&rs.stat[3], 1ULL);
+                        if (winner != rex_side) atomicAdd(&rs.stat[4], 1ULL);
+                        atomicAdd(&rs.stat[5], (unsigned long long)rex_ply);
+                    }
+                }
+            }
+            if (adjudicated) winner = rst.side;
+        }
         unsigned long long base = 0;
         if (lane == 0) {
             base = atomicAdd(&gm.counters[0], (unsigned long long)nply);
@@ -2661,6 +2711,7 @@ __device__ __forceinline__ void sp_move_body(const GamesDev& gm, const MctsDev& 
                 r.greedy = cur ? (uint8_t)greedy : gm.log_greedy[lb + lane];
                 r.pad[0] = r.pad[1] = r.pad[2] = 0;
                 if constexpr (CAP) { if (pc.fast_sims > 0) r.pad[0] = cur ? (uint8_t)fast : pc.log_fast[lb + lane]; }
+                if constexpr (RESIGN) { if (adjudicated) r.pad[1] = 1; }
                 gm.records[base + lane] = r;
             } else atomicOr(t.error_flag, EF_RECORDS);
         }
@@ -2692,6 +2743,12 @@ __device__ __forceinline__ void sp_move_body(const GamesDev& gm, const MctsDev& 
     }
     if constexpr (GUMBEL) { if (lane == 0 && greedy == 3) atomicAdd(gp.moves, 1ULL); }
     if (lane == 0) atomicAdd(&gm.counters[2], 1ULL);
+    if constexpr (RESIGN) {                                // the slot's state: that of the game in progress, zero for the next game where this one ended
+        if (rs.r > 0 && lane == 0) {
+            rs.side[g] = (int8_t)(fin ? 0 : rst.side); rs.streak[g] = (uint8_t)(fin ? 0 : rst.streak);
+            rs.ex_side[g] = (int8_t)(fin ? 0 : rex_side); rs.ex_ply[g] = (uint8_t)(fin ? 0 : rex_ply);
+        }
+    }
     if (fin && gm.refill) {
         // a fresh OthelloGame + a fresh OthelloMCTS in the same slot (training.py:30-32)
         for (int i = lane; i < t.ht_cap; i += 64) t.ht[(size_t)g * t.ht_cap + i] = 0;
@@ -2728,6 +2785,13 @@ __global__ __launch_bounds__(64) void k_sp_move_fs(GamesDev gm, MctsDev t, MoveS
 }
 __global__ __launch_bounds__(64) void k_sp_move_gs(GamesDev gm, MctsDev t, GumbelPlay gp, SurprisePlay su) {
     sp_move_body<false, false, false, false, true, true, true>(gm, t, blockIdx.x, threadIdx.x, 0, MoveSampling{}, PlayoutCap{}, ForcedPlayouts{}, gp, su);
+}
+// (the *r kernels: k_sp_move_f and k_sp_move_fs whose move applies the resignation rule, launched by engines with oz_selfplay_set_resign)
+__global__ __launch_bounds__(64) void k_sp_move_r(GamesDev gm, MctsDev t, MoveSampling ms, PlayoutCap pc, ForcedPlayouts fp, ResignPlay rs) {
+    sp_move_body<false, true, true, true, true, false, false, true>(gm, t, blockIdx.x, threadIdx.x, 0, ms, pc, fp, GumbelPlay{}, SurprisePlay{}, rs);
+}
+__global__ __launch_bounds__(64) void k_sp_move_rs(GamesDev gm, MctsDev t, MoveSampling ms, PlayoutCap pc, ForcedPlayouts fp, SurprisePlay su, ResignPlay rs) {
+    sp_move_body<false, true, true, true, true, false, true, true>(gm, t, blockIdx.x, threadIdx.x, 0, ms, pc, fp, GumbelPlay{}, su, rs);
 }
 
 // ---------------------------------------------------------------- free-running self-play step
@@ -2963,6 +3027,7 @@ struct oz_selfplay {
     int32_t* copies = nullptr;
     uint8_t* first_sym = nullptr;
     long long* d_sw = nullptr;       // ... and its five counters
+    ResignPlay resign{0.0, 0.0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr};      // oz_selfplay_set_resign: r > 0 = on (the buffers stay once allocated)
     template <typename T> int alloc(T** p, size_t count) {
         OZ_HIP(hipMalloc((void**)p, sizeof(T) * (count ? count : 1)));
         allocs.push_back(*p);
@@ -3088,7 +3153,9 @@ static int selfplay_round_async(oz_selfplay* sp, int sims, int stagger_round) {
         }
     } else if (int rc = mcts_steps_async(m, sp->net, sims, G, true, capped ? &ck : nullptr)) return rc;
     timed(m, TS_MOVE, m->profile, [&] {
-        if (sp->su.log && sp->gumbel_on) hipLaunchKernelGGL(k_sp_move_gs, dim3(G), dim3(64), 0, s, sp->gm, m->d, GumbelPlay{m->gd, sp->gumbel_log, sp->gumbel_rows, sp->gumbel_moves}, sp->su);
+        if (sp->resign.r > 0 && sp->su.log) hipLaunchKernelGGL(k_sp_move_rs, dim3(G), dim3(64), 0, s, sp->gm, m->d, sp->sample, capped ? sp->cap : PlayoutCap{0, 0.0, nullptr, nullptr}, sp->forced, sp->su, sp->resign);
+        else if (sp->resign.r > 0) hipLaunchKernelGGL(k_sp_move_r, dim3(G), dim3(64), 0, s, sp->gm, m->d, sp->sample, capped ? sp->cap : PlayoutCap{0, 0.0, nullptr, nullptr}, sp->forced, sp->resign);
+        else if (sp->su.log && sp->gumbel_on) hipLaunchKernelGGL(k_sp_move_gs, dim3(G), dim3(64), 0, s, sp->gm, m->d, GumbelPlay{m->gd, sp->gumbel_log, sp->gumbel_rows, sp->gumbel_moves}, sp->su);
         else if (sp->su.log) hipLaunchKernelGGL(k_sp_move_fs, dim3(G), dim3(64), 0, s, sp->gm, m->d, sp->sample, capped ? sp->cap : PlayoutCap{0, 0.0, nullptr, nullptr}, sp->forced, sp->su);
         else if (sp->gumbel_on) hipLaunchKernelGGL(k_sp_move_g, dim3(G), dim3(64), 0, s, sp->gm, m->d, GumbelPlay{m->gd, sp->gumbel_log, sp->gumbel_rows, sp->gumbel_moves});
         else if (sp->forced.k > 0.0 || sp->gm.log_values) hipLaunchKernelGGL(k_sp_move_f, dim3(G), dim3(64), 0, s, sp->gm, m->d, sp->sample, capped ? sp->cap : PlayoutCap{0, 0.0, nullptr, nullptr}, sp->forced);
@@ -3129,6 +3196,7 @@ OZ_API int oz_selfplay_stagger(oz_selfplay* sp, int sims_pre) {
     hipSetDevice(sp->m->device);
     OZ_REQUIRE(sp->mode == 0, "oz_selfplay_stagger must be the first driver call on an engine");
     if (sp->gumbel_on) { oz_set_error("oz_selfplay_stagger: not with the Gumbel search (its budget is num_simulations; use oz_selfplay_run)"); return OZ_ERR_STATE; }
+    if (sp->resign.r > 0) { oz_set_error("oz_selfplay_stagger: not with resignation (its rounds search at sims_pre; use oz_selfplay_run)"); return OZ_ERR_STATE; }
     OZ_REQUIRE(sp->cfg.refill, "oz_selfplay_stagger is for continuous self-play (cfg.refill = 1)");
     sp->mode = 1;
     selfplay_attach_cache(sp);
@@ -3335,6 +3403,101 @@ OZ_API int oz_playout_budgets(uint64_t seed, const uint64_t* game_ids, const int
     }
     return OZ_OK;
 }
+// resignation for the self-play games of the engine (oz_selfplay_run at any leaves_per_step); after oz_selfplay_set_record_values(sp, 1), before
+// the first driver call.  r == 0 disarms.  4 B per slot + 48 B at the first arming.
+static int resign_check(const char* fn, double v, int r, int min_ply) {
+    OZ_REQUIRE(v > 0.0 && v <= 1.0, "%s: v %g outside (0, 1]", fn, v);                              // (NaN fails both compares)
+    OZ_REQUIRE(r >= 1 && r <= 8, "%s: r %d outside [1, 8]", fn, r);
+    OZ_REQUIRE(min_ply >= 0 && min_ply <= 64, "%s: min_ply %d outside [0, 64]", fn, min_ply);
+    return OZ_OK;
+}
+OZ_API int oz_selfplay_set_resign(oz_selfplay* sp, double v, int r, int min_ply, double keep_prob) {
+    OZ_REQUIRE(sp, "null selfplay");
+    if (r != 0) {
+        if (int rc = resign_check("oz_selfplay_set_resign", v, r, min_ply)) return rc;
+        OZ_REQUIRE(keep_prob >= 0.0 && keep_prob <= 1.0, "oz_selfplay_set_resign: keep_prob %g outside [0, 1]", keep_prob);
+    }
+    std::lock_guard<std::mutex> lk(sp->mu);
+    if (sp->mode != 0) { oz_set_error("oz_selfplay_set_resign: the engine has been driven already (set it before the first driver call)"); return OZ_ERR_STATE; }
+    if (r == 0) { sp->resign.r = 0; return OZ_OK; }
+    if (sp->gumbel_on) { oz_set_error("oz_selfplay_set_resign: not with the Gumbel search (the engine has it switched on)"); return OZ_ERR_STATE; }
+    if (!sp->gm.log_values) { oz_set_error("oz_selfplay_set_resign: the rule reads recorded root values (oz_selfplay_set_record_values(sp, 1) first)"); return OZ_ERR_STATE; }
+    if (!sp->resign.stat) {
+        hipSetDevice(sp->m->device);
+        const size_t held = sp->allocs.size(), G = (size_t)sp->gm.G;
+        uint8_t* state = nullptr; unsigned long long* stat = nullptr;
+        int rc = sp->alloc(&state, 4 * G);
+        if (!rc) rc = sp->alloc(&stat, 6);
+        if (!rc && (hipMemset(state, 0, 4 * G) != hipSuccess || hipMemset(stat, 0, 6 * sizeof(unsigned long long)) != hipSuccess)) {
+            oz_set_error("oz_selfplay_set_resign: clearing the buffers failed");
+            rc = OZ_ERR_HIP;
+        }
+        if (rc) {
+            for (size_t i = held; i < sp->allocs.size(); ++i) hipFree(sp->allocs[i]);
+            sp->allocs.resize(held);
+            return rc;
+        }
+        sp->resign.side = (int8_t*)state; sp->resign.streak = state + G;
+        sp->resign.ex_side = (int8_t*)(state + 2 * G); sp->resign.ex_ply = state + 3 * G;
+        sp->resign.stat = stat;
+    }
+    sp->resign.v = v; sp->resign.r = r; sp->resign.min_ply = min_ply; sp->resign.keep_prob = keep_prob;
+    return OZ_OK;
+}
+OZ_API int oz_selfplay_get_resign(oz_selfplay* sp, double* v, int* r, int* min_ply, double* keep_prob, oz_resign_stats* stats) {
+    OZ_REQUIRE(sp, "null selfplay");
+    std::lock_guard<std::mutex> lk(sp->mu);
+    const bool on = sp->resign.r > 0;
+    if (v) *v = on ? sp->resign.v : 0.0;
+    if (r) *r = sp->resign.r;
+    if (min_ply) *min_ply = on ? sp->resign.min_ply : 0;
+    if (keep_prob) *keep_prob = on ? sp->resign.keep_prob : 0.0;
+    if (stats) {
+        unsigned long long c[6] = {0, 0, 0, 0, 0, 0};
+        if (sp->resign.stat) {
+            hipSetDevice(sp->m->device);
+            OZ_HIP(hipStreamSynchronize(sp->m->stream));
+            OZ_HIP(hipMemcpy(c, sp->resign.stat, sizeof c, hipMemcpyDeviceToHost));
+        }
+        stats->games_adjudicated = (int64_t)c[0]; stats->adjudicated_plies_sum = (int64_t)c[1]; stats->games_exempt = (int64_t)c[2];
+        stats->exempt_triggered = (int64_t)c[3]; stats->exempt_wrong = (int64_t)c[4]; stats->exempt_trigger_ply_sum = (int64_t)c[5];
+    }
+    return OZ_OK;
+}
+// oz_resign_step over whole sequences, on the host: needs no device
+OZ_API int oz_resign_scan(const int8_t* players, const double* values, const int32_t* plies_per_game, int64_t games, double v, int r, int min_ply,
+                          int32_t* trigger_ply, int8_t* trigger_side) {
+    if (int rc = resign_check("oz_resign_scan", v, r, min_ply)) return rc;
+    OZ_REQUIRE(games >= 0, "oz_resign_scan: games %lld", (long long)games);
+    if (games == 0) return OZ_OK;
+    OZ_REQUIRE(plies_per_game && trigger_ply && trigger_side, "oz_resign_scan: null argument");
+    int64_t total = 0;
+    for (int64_t g = 0; g < games; ++g) {
+        OZ_REQUIRE(plies_per_game[g] >= 0, "oz_resign_scan: plies_per_game[%lld] = %d", (long long)g, plies_per_game[g]);
+        total += plies_per_game[g];
+    }
+    OZ_REQUIRE(total == 0 || (players && values), "oz_resign_scan: null argument");
+    for (int64_t i = 0; i < total; ++i) OZ_REQUIRE(players[i] == 1 || players[i] == -1, "oz_resign_scan: players[%lld] = %d", (long long)i, (int)players[i]);
+    int64_t at = 0;
+    for (int64_t g = 0; g < games; ++g) {
+        OzResign st{0, 0};
+        trigger_ply[g] = -1; trigger_side[g] = 0;
+        for (int i = 0; i < plies_per_game[g]; ++i) {
+            const bool trig = oz_resign_step(st, players[at + i], values[at + i], v, r, min_ply, i);
+            if (trig && trigger_ply[g] < 0) { trigger_ply[g] = i; trigger_side[g] = (int8_t)st.side; }
+        }
+        at += plies_per_game[g];
+    }
+    return OZ_OK;
+}
+OZ_API int oz_resign_exempt(uint64_t seed, const uint64_t* game_ids, int64_t count, double keep_prob, uint8_t* out) {
+    OZ_REQUIRE(keep_prob >= 0.0 && keep_prob <= 1.0, "oz_resign_exempt: keep_prob %g outside [0, 1]", keep_prob);
+    OZ_REQUIRE(count >= 0, "oz_resign_exempt: count %lld", (long long)count);
+    if (count == 0) return OZ_OK;
+    OZ_REQUIRE(game_ids && out, "oz_resign_exempt: null argument");
+    for (int64_t i = 0; i < count; ++i) out[i] = oz_resign_is_exempt(seed, game_ids[i], keep_prob) ? 1 : 0;
+    return OZ_OK;
+}
 // the Gumbel search for every searched move of the lock-step rounds of oz_selfplay_run; before the first driver call.  The budget is the
 // engine's num_simulations, the seed the engine's.  16 KB per slot + 256 B per record for the improved-policy rows at the first call.
 OZ_API int oz_selfplay_set_gumbel(oz_selfplay* sp, int max_considered, double c_visit, double c_scale) {
@@ -3345,6 +3508,7 @@ OZ_API int oz_selfplay_set_gumbel(oz_selfplay* sp, int max_considered, double c_
     if (sp->noise_on || sp->forced.k > 0.0) { oz_set_error("oz_selfplay_set_gumbel: the Gumbel search replaces root noise and forced playouts (the engine has them switched on)"); return OZ_ERR_STATE; }
     if (sp->sample.plies > 0) { oz_set_error("oz_selfplay_set_gumbel: the Gumbel search replaces move sampling (the engine has it switched on)"); return OZ_ERR_STATE; }
     if (sp->cap.fast_sims > 0) { oz_set_error("oz_selfplay_set_gumbel: not with a playout cap (it needs two budgets and two schedules)"); return OZ_ERR_STATE; }
+    if (sp->resign.r > 0) { oz_set_error("oz_selfplay_set_gumbel: not with resignation (the engine has it armed)"); return OZ_ERR_STATE; }
     std::lock_guard<std::mutex> lkm(sp->m->mu);
     hipSetDevice(sp->m->device);
     if (!sp->gumbel_log) {
@@ -3406,6 +3570,7 @@ OZ_API int oz_selfplay_run_steps(oz_selfplay* sp, int steps) {
         return OZ_ERR_STATE;
     }
     if (sp->gumbel_on) { oz_set_error("oz_selfplay_run_steps: the free-running driver does not run the Gumbel search; use oz_selfplay_run"); return OZ_ERR_STATE; }
+    if (sp->resign.r > 0) { oz_set_error("oz_selfplay_run_steps: the free-running driver does not resign games; use oz_selfplay_run"); return OZ_ERR_STATE; }
     std::lock_guard<std::mutex> lkn(sp->net->mu);
     oz_mcts* m = sp->m;
     hipSetDevice(m->device);
@@ -3650,6 +3815,7 @@ OZ_API int oz_selfplay_set_record_values(oz_selfplay* sp, int enable) {
     OZ_REQUIRE(enable == 0 || enable == 1, "oz_selfplay_set_record_values: enable = %d (0 or 1)", enable);
     std::lock_guard<std::mutex> lk(sp->mu);
     if (sp->mode != 0) { oz_set_error("oz_selfplay_set_record_values: the engine has been driven already (set it before the first driver call)"); return OZ_ERR_STATE; }
+    if (!enable && sp->resign.r > 0) { oz_set_error("oz_selfplay_set_record_values: resignation is armed and reads the root values (disarm it first)"); return OZ_ERR_STATE; }
     if (enable && !sp->val_log) {
         hipSetDevice(sp->m->device);
         const size_t held = sp->allocs.size(), G = (size_t)sp->gm.G, cap = (size_t)sp->gm.record_cap;

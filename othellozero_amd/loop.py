@@ -87,6 +87,8 @@ def examples_from_records(records, board_size, alias_final=True, in_channels=2, 
     visits (int32 (R, 64), the records' root visit counts): the policy of every example is the search's visit distribution at
     target_temperature (expand_examples) instead of the one-hot of the move played.
     The fast records of a playout cap (_lib.record_fast) are no training examples: they and their visit-count rows are dropped first.
+    The records of an adjudicated game (_lib.record_adjudicated, SelfPlayEngine(resign=...)) are examples like any other: z is the adjudicated
+    one, and with alias_final=True the "final board" of such a game is the board at the stop.
     values (float32 (R,), the records' value targets): the z of every example is its record's target, a float, instead of the int outcome.
     policies (float32 (R, 64) by square, the records' improved-policy rows of a Gumbel search, SelfPlayEngine.records(with_policies=True)): the
     policy of every example is its record's row under the example's symmetry, float32 (n, n), bit for bit (oz_examples_expand_policy, on the
@@ -297,7 +299,7 @@ def self_play_match(board_size, neural_network, old_neural_network, total_games,
 def _selfplay_into_replay(replay, neural_network, board_size, num_episodes, num_simulations, degree_exploration, temperature, e_greedy, seed,
                           first_game_id, q_mode, visits, leaves_per_step, root_noise, sample_moves, alias_final_boards, policy_target,
                           target_temperature, endgame_targets=0, solve_leaves=0, playout_cap=None, forced_playouts=0.0, value_target="outcome",
-                          gumbel=None, surprise_weight=None):
+                          gumbel=None, surprise_weight=None, resign=None):
     """one iteration's games on the engine selfplay_batch would create, played to the end without reading a record, and their examples
     appended to the device buffer; -> (records appended, the endgame solver's statistics or None).  One-channel (BaseNN) examples are never
     aliased (examples_from_records).  endgame_targets > 0: SelfPlayEngine.solve_records before the append.  playout_cap: the engine's; the
@@ -306,14 +308,16 @@ def _selfplay_into_replay(replay, neural_network, board_size, num_episodes, num_
     endgame solver, exact_empties = endgame_targets).  gumbel: the engine's; policy_target="improved" appends its improved-policy rows.
     surprise_weight=(frac, weight_seed): the engine records policy surprise and the append writes c_i examples per record
     (ReplayBuffer.append_engine(surprise_weight=...)); training.surprise_stats then holds the iteration's dict(records, examples,
-    mean_copies, max_copies, mean_surprise)."""
+    mean_copies, max_copies, mean_surprise).  resign: the engine's; an adjudicated record is appended like any other, and training.resign_stats
+    then holds the engine's resign_stats()."""
     from .training import SelfPlayEngine
     vt_on = _lib.check_value_target(value_target)[0] != _lib.VALUE_TARGET_OUTCOME
     eng = SelfPlayEngine(neural_network, board_size, num_episodes, num_simulations, degree_exploration, temperature, e_greedy, seed,
                          first_game_id, q_mode=q_mode, record_visits=visits, leaves_per_step=leaves_per_step, root_noise=root_noise,
                          sample_moves=sample_moves, solve_leaves=solve_leaves, **({"playout_cap": playout_cap} if playout_cap is not None else {}),
                          **({"forced_playouts": forced_playouts} if forced_playouts else {}), **({"record_values": True} if vt_on else {}),
-                         **({"gumbel": gumbel} if gumbel is not None else {}), **({"record_surprise": True} if surprise_weight is not None else {}))
+                         **({"gumbel": gumbel} if gumbel is not None else {}), **({"record_surprise": True} if surprise_weight is not None else {}),
+                         **({"resign": resign} if resign is not None else {}))
     for _ in range(board_size * board_size):
         eng.run(4)
         if eng.stats()["live_games"] == 0:
@@ -321,6 +325,8 @@ def _selfplay_into_replay(replay, neural_network, board_size, num_episodes, num_
     endgame = eng.solve_records(endgame_targets) if endgame_targets else None
     if solve_leaves:
         training.rows_solved += eng.rows_solved()
+    if resign is not None:
+        training.resign_stats = eng.resign_stats()
     appended = replay.append_engine(eng, alias_final=alias_final_boards and getattr(neural_network, "in_channels", 2) == 2,
                                     policy_target=policy_target, target_temperature=target_temperature,
                                     **({"value_target": value_target, "exact_empties": endgame_targets} if vt_on else {}),
@@ -335,6 +341,14 @@ def _selfplay_into_replay(replay, neural_network, board_size, num_episodes, num_
     return appended, endgame
 
 
+def _log_resign(i, num_iterations, stats):
+    logging.info('[%d/%d] resignation: %d games adjudicated after %.1f plies on average / audit: %d exempt games, %d triggered, %d wrongly '
+                 '(false-positive rate %s)', i, num_iterations, stats["games_adjudicated"],
+                 stats["adjudicated_plies_sum"] / stats["games_adjudicated"] if stats["games_adjudicated"] else 0.0, stats["games_exempt"],
+                 stats["exempt_triggered"], stats["exempt_wrong"],
+                 '%.3f' % (stats["exempt_wrong"] / stats["exempt_triggered"]) if stats["exempt_triggered"] else 'n/a')
+
+
 def _log_endgame(i, num_iterations, stats):
     logging.info('[%d/%d] endgame targets: solved %d / z_changed %d / mean_disc_loss %.3f', i, num_iterations, stats["solved"],
                  stats["z_changed"], stats["mean_disc_loss"])
@@ -347,8 +361,18 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
              distributed=False, batched_evaluation=False, policy_target="onehot", target_temperature=1.0, leaves_per_step=1,
              root_noise=None, sample_moves=None, replay="host", evaluation_opponent="random", endgame_targets=0,
              solve_leaves=0, match_openings=None, evaluation_openings=None, playout_cap=None, forced_playouts=None, eval_symmetry=None,
-             value_target="outcome", gumbel=None, surprise_weight=None):
+             value_target="outcome", gumbel=None, surprise_weight=None, resign=None):
     """main.py:56-259 on the GPU engines; returns `historic` = [(episodes done, win rate vs random), ...]
+
+    resign=(v, r, min_ply, keep_prob) (None = off, the default): resignation of decided SELF-PLAY games with a played-out audit share
+    (SelfPlayEngine), in the host path, the distributed path (the flag travels inside the 48-byte records through the all-gather) and with
+    replay="device" alike; matches and evaluations are never adjudicated.  A game whose root values, seen from BLACK, stayed at or beyond
+    +-v for r searched moves in a row stops from ply min_ply on and goes to that side: its records carry that z and train like any other
+    (with alias_final_boards=True the "final board" of such a game is the board at the stop), and the searches of a decided game's last
+    plies are saved.  A share keep_prob of the games is played out regardless.  Logs the adjudicated games and the audit counters per
+    iteration; training.resign_history keeps the engines' resign_stats() dicts (with distributed=True: this rank's), from which
+    exempt_wrong / exempt_triggered is the rule's false-positive rate -- tune v until it is a few per cent (AlphaGo Zero: below 5 %).
+    Not with gumbel (ValueError).  Playing strength is neither gated nor claimed ("Resignation").
 
     surprise_weight=frac in (0, 1] (None = off, the default; KataGo uses 0.5): policy surprise weighting of the SELF-PLAY records.  The engine
     keeps every searched move's surprise KL(policy target || root prior) (SelfPlayEngine(record_surprise=True)); a fully searched record of a
@@ -470,6 +494,9 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
     alias_final_boards=False.  Playing strength is neither gated nor claimed ("Value targets")."""
     vt_on = _lib.check_value_target(value_target, alias_final_boards)[0] != _lib.VALUE_TARGET_OUTCOME
     vt_kw = {"value_target": value_target} if vt_on else {}
+    resign = _lib.check_resign(resign, gumbel=gumbel)
+    resign_kw = {"resign": resign} if resign is not None else {}
+    training.resign_history = []
     training.surprise_history = []
     if surprise_weight is not None:
         surprise_weight = _lib.check_surprise_frac(surprise_weight)
@@ -593,8 +620,11 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
                                                       degree_exploration, temperature, e_greedy, seed, total_episodes_done, q_mode, visits,
                                                       leaves_per_step, root_noise, sample_moves, alias_final_boards, policy_target,
                                                       target_temperature, endgame_targets, solve_leaves, playout_cap, forced_playouts, **vt_kw,
-                                                      **gumbel_kw,
+                                                      **gumbel_kw, **resign_kw,
                                                       **({"surprise_weight": (surprise_weight, seed + i)} if surprise_weight is not None else {}))
+            if resign is not None:
+                training.resign_history.append(training.resign_stats)
+                _log_resign(i, num_iterations, training.resign_stats)
             if surprise_weight is not None:
                 st = training.surprise_stats
                 training.surprise_history.append(st)
@@ -614,9 +644,10 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
                 eng = SelfPlayEngine(neural_network, board_size, count, num_simulations, degree_exploration, temperature, e_greedy,
                                      seed=seed, first_game_id=total_episodes_done + first, q_mode=q_mode, record_visits=visits,
                                      leaves_per_step=leaves_per_step, root_noise=root_noise, sample_moves=sample_moves,
-                                     solve_leaves=solve_leaves, **cap_kw, **({"record_values": True} if vt_on else {}))
+                                     solve_leaves=solve_leaves, **cap_kw, **({"record_values": True} if vt_on else {}), **resign_kw)
                 eng.play_to_end(endgame_targets=endgame_targets, **vt_kw)               # each rank relabels its own records (and computes its targets)
                 training.rows_solved += eng.rows_solved() if solve_leaves else 0
+                resign_stats = eng.resign_stats() if resign is not None else None
                 records = pooled_selfplay_records(eng, device, with_visits=visits,      # the only exchange of the self-play phase
                                                   **({"with_values": True} if vt_on else {}))
                 endgame = getattr(eng, "endgame_stats", None)
@@ -627,10 +658,14 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
                                          seed=seed, first_game_id=total_episodes_done, q_mode=q_mode, record_visits=visits,
                                          leaves_per_step=leaves_per_step, root_noise=root_noise, sample_moves=sample_moves,
                                          **({"endgame_targets": endgame_targets} if endgame_targets else {}), **({"solve_leaves": solve_leaves} if solve_leaves else {}),
-                                         **cap_kw, **vt_kw, **gumbel_kw)
+                                         **cap_kw, **vt_kw, **gumbel_kw, **resign_kw)
                 training.rows_solved += selfplay_batch.rows_solved if solve_leaves else 0
+                resign_stats = selfplay_batch.resign_stats if resign is not None else None
                 endgame = getattr(selfplay_batch, "endgame_stats", None) if endgame_targets else None
             restore_eval_symmetry()
+            if resign is not None:
+                training.resign_history.append(resign_stats)
+                _log_resign(i, num_iterations, resign_stats)
             if endgame is not None:
                 training.endgame_history.append(endgame)
                 _log_endgame(i, num_iterations, endgame)

@@ -71,6 +71,8 @@ class ReplayBuffer:
         policy_target="improved" (or target="improved") needs an engine created with gumbel=...: every example's pi is its record's float32
         improved-policy row under the example's symmetry, staged device to device, bit for bit.
         The fast records of a playout cap (_lib.record_fast) are left out and not counted.
+        The records of an adjudicated game (_lib.record_adjudicated, an engine created with resign=...) are appended like any other: z is
+        the adjudicated one, and with alias_final=True the "final board" of such a game is the board at the stop.
         value_target=("blend", w) / ("td", lam) (an engine created with record_values=True; alias_final=False): the engine computes the
         value targets of those records (SelfPlayEngine.value_targets(value_target, exact_empties, first_record)) and every example's z is
         its record's float32 target instead of the game outcome; "outcome" is the call without it.

@@ -188,7 +188,7 @@ class SelfPlayEngine:
                  policy_temperature=1.0, e_greedy=0.9, seed=1234, first_game_id=0, game_id_stride=0,
                  q_mode=_lib.QMODE_F64, refill=False, node_cap=0, record_cap=0, dedup=True, batch_cap=0, eval_cache=False,
                  record_visits=False, leaves_per_step=1, root_noise=None, sample_moves=None, solve_leaves=0, playout_cap=None,
-                 forced_playouts=None, record_values=False, gumbel=None, record_surprise=False):
+                 forced_playouts=None, record_values=False, gumbel=None, record_surprise=False, resign=None):
         """dedup: cross-game leaf de-duplication (a board several games reach in one batch is evaluated once; no record changes);
         batch_cap: leaves per network batch of the free-running driver (0 = none; see preferred_batch_cap);
         eval_cache: take (pi, v) of boards the network has evaluated before from its persistent cache (NNetWrapper.set_eval_cache) --
@@ -233,7 +233,17 @@ class SelfPlayEngine:
         leaves_per_step > 1 (ValueError); run_steps() and stagger() then raise.  gumbel_stats() counts (DESIGN.md, "Gumbel search").
         record_surprise=True (needs record_visits=True or gumbel=...): keep every recorded move's policy surprise KL(q || p), q the row that
         becomes its policy target and p the root's stored priors (oz_selfplay_set_record_surprise), for records(with_surprise=True) and
-        surprise_weights(); 512 B per slot + 8 B per record, no record changes.  Every driver ("Policy surprise weighting")."""
+        surprise_weights(); 512 B per slot + 8 B per record, no record changes.  Every driver ("Policy surprise weighting").
+        resign=(v, r, min_ply, keep_prob): resignation with a played-out audit share (oz_selfplay_set_resign); switches record_values on.
+        After every searched move the root value, seen from BLACK, is held against +-v; once it has stayed at or beyond the same bound for r
+        moves in a row and the ply is at least min_ply, the game stops after that move and goes to that side: its records carry z for that
+        winner, the board at the stop as their final board and the flag _lib.record_adjudicated reads; a refilled slot starts its next game
+        at once.  A share keep_prob of the games, drawn per (seed, game id), is played out regardless: resign_stats() counts how often the
+        rule triggered in them and how often it was wrong.  The record consumers take an adjudicated record as any other (with
+        alias_final=True the "final board" of such a game is the board at the stop).  run() at any leaves_per_step, with every option but
+        gumbel (ValueError); run_steps() and stagger() then raise.  keep_prob = 1 plays the games of the engine without the option
+        (DESIGN.md, "Resignation")."""
+        resign = _lib.check_resign(resign, gumbel=gumbel)
         if record_surprise and not (record_visits or gumbel):
             raise ValueError("record_surprise needs record_visits=True or gumbel=...: the surprise is that of a recorded policy target")
         gumbel = _lib.check_gumbel_options(gumbel, root_noise=root_noise, forced_playouts=forced_playouts, sample_moves=sample_moves,
@@ -273,8 +283,8 @@ class SelfPlayEngine:
         self.forced_playouts = forced_playouts
         if forced_playouts > 0.0:
             _lib.check(lib.oz_selfplay_set_forced_playouts(self._h, forced_playouts))
-        self.record_values = bool(record_values)
-        if record_values:
+        self.record_values = bool(record_values) or resign is not None
+        if self.record_values:
             _lib.check(lib.oz_selfplay_set_record_values(self._h, 1))
         self.gumbel = gumbel
         if gumbel is not None:
@@ -282,6 +292,19 @@ class SelfPlayEngine:
         self.record_surprise = bool(record_surprise)
         if record_surprise:
             _lib.check(lib.oz_selfplay_set_record_surprise(self._h, 1))
+
+        self.resign = resign
+        if resign is not None:
+            _lib.check(lib.oz_selfplay_set_resign(self._h, *resign))
+
+    def resign_stats(self):
+        """dict(v, r, min_ply, keep_prob, games_adjudicated, adjudicated_plies_sum, games_exempt, exempt_triggered, exempt_wrong,
+        exempt_trigger_ply_sum): the resignation rule that is set (r 0 = off) and, since it was armed, the games it ended and the plies they
+        were played for, and of the exempt games completed how many triggered the rule, how many of those the natural winner proved wrong,
+        and the plies of their first triggers in sum.  exempt_wrong / exempt_triggered is the rule's false-positive rate."""
+        v, r, m, kp, s = C.c_double(), C.c_int(), C.c_int(), C.c_double(), _lib.ResignStats()
+        _lib.check(_lib.load().oz_selfplay_get_resign(self._h, C.byref(v), C.byref(r), C.byref(m), C.byref(kp), C.byref(s)))
+        return dict(v=v.value, r=r.value, min_ply=m.value, keep_prob=kp.value, **{k: int(getattr(s, k)) for k, _ in s._fields_})
 
     def surprise_weights(self, frac, seed, first_record=0):
         """oz_selfplay_surprise_weights: weights, copy counts and first symmetries of the completed records from `first_record` on, computed
@@ -572,7 +595,8 @@ def expand_examples(records, board_size, alias_final=False, visits=None, target_
     and the second array returned is pi (R*8, n, n) float64 (target_temperature > 0).
 
     The fast records of a playout cap (_lib.record_fast) are no training examples: they and their visit-count rows are dropped first, so R
-    counts the fully searched moves.
+    counts the fully searched moves.  The records of an adjudicated game (_lib.record_adjudicated) are examples like any other; with
+    alias_final=True the "final board" of such a game is the board at the stop.
 
     values = the records' value targets (float32 (R,), agents.rules_value_targets / SelfPlayEngine.records(with_targets=True)): each
     example takes its record's target, 8 per record, and z comes back as float32 (in that case only)."""
@@ -608,8 +632,12 @@ def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations
                    policy_temperature=1.0, e_greedy=0.9, seed=1234, first_game_id=0, q_mode=_lib.QMODE_F64,
                    expand=False, alias_final=False, record_visits=False, target_temperature=1.0, leaves_per_step=1, root_noise=None,
                    sample_moves=None, endgame_targets=0, solve_leaves=0, playout_cap=None, forced_playouts=None, value_target="outcome", gumbel=None,
-                   surprise_weight=None):
+                   surprise_weight=None, resign=None):
     """Play num_games complete games; returns the move records (or the expanded examples).
+    resign=(v, r, min_ply, keep_prob): resignation with a played-out audit share (SelfPlayEngine): a decided game stops early, its records
+    carry the adjudicated z, the board at the stop as their final board (what alias_final=True then shows) and the flag
+    _lib.record_adjudicated reads; nothing else about what comes back changes.  Not with gumbel (ValueError).  selfplay_batch.resign_stats
+    holds the last call's SelfPlayEngine.resign_stats() (None when off).
     surprise_weight=(frac, weight_seed): policy surprise weighting (SelfPlayEngine(record_surprise=True).surprise_weights; needs
     record_visits=True or gumbel).  Two more entries come back last of all -- (records, ..., surprises, (w, copies, first_sym)): the float64
     policy surprise of every record and its float32 weight, int32 copy count and uint8 first symmetry, for the device replay buffer's
@@ -654,11 +682,14 @@ def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations
     playout_cap = _lib.check_playout_cap(playout_cap, num_simulations)
     solve_leaves = _lib.check_solve_leaves(solve_leaves)
     endgame_targets = _lib.check_endgame_targets(endgame_targets, expand and alias_final)
+    resign = _lib.check_resign(resign, gumbel=gumbel)
+    selfplay_batch.resign_stats = None
     eng = SelfPlayEngine(neural_network, board_size, num_games, num_simulations, degree_exploration, policy_temperature,
                          e_greedy, seed, first_game_id, q_mode=q_mode, record_visits=record_visits, leaves_per_step=leaves_per_step,
                          root_noise=root_noise, sample_moves=sample_moves, solve_leaves=solve_leaves, playout_cap=playout_cap,
                          **({"forced_playouts": forced_playouts} if forced_playouts > 0.0 else {}), **({"record_values": True} if vt_on else {}),
-                         **({"gumbel": gumbel} if gumbel is not None else {}), **({"record_surprise": True} if surprise_weight is not None else {}))
+                         **({"gumbel": gumbel} if gumbel is not None else {}), **({"record_surprise": True} if surprise_weight is not None else {}),
+                         **({"resign": resign} if resign is not None else {}))
     selfplay_batch.surprise_stats = None
 
     def weighted(ret):
@@ -683,6 +714,7 @@ def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations
         selfplay_batch.value_target_stats = eng.value_target_stats
         selfplay_batch.forced_playout_stats = eng.forced_playout_stats() if forced_playouts > 0.0 else None
         selfplay_batch.playout_stats = eng.playout_stats() if playout_cap is not None else None
+        selfplay_batch.resign_stats = eng.resign_stats() if resign is not None else None
         selfplay_batch.rows_solved = eng.rows_solved() if solve_leaves else None
         if expand:
             return expand_examples(rec, board_size, alias_final, visits=counts, target_temperature=target_temperature, values=targets)
@@ -692,12 +724,14 @@ def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations
         rec, counts = eng.play_to_end(with_visits=True, endgame_targets=endgame_targets)
         selfplay_batch.forced_playout_stats = eng.forced_playout_stats() if forced_playouts > 0.0 else None
         selfplay_batch.playout_stats = eng.playout_stats() if playout_cap is not None else None
+        selfplay_batch.resign_stats = eng.resign_stats() if resign is not None else None
         selfplay_batch.rows_solved = eng.rows_solved() if solve_leaves else None
         selfplay_batch.endgame_stats = getattr(eng, "endgame_stats", None)
         return expand_examples(rec, board_size, alias_final, visits=counts, target_temperature=target_temperature) if expand else weighted((rec, counts))
     rec = eng.play_to_end(endgame_targets=endgame_targets)
     selfplay_batch.forced_playout_stats = eng.forced_playout_stats() if forced_playouts > 0.0 else None
     selfplay_batch.playout_stats = eng.playout_stats() if playout_cap is not None else None
+    selfplay_batch.resign_stats = eng.resign_stats() if resign is not None else None
     selfplay_batch.rows_solved = eng.rows_solved() if solve_leaves else None
     selfplay_batch.endgame_stats = getattr(eng, "endgame_stats", None)
     return expand_examples(rec, board_size, alias_final) if expand else rec
