@@ -1059,6 +1059,30 @@ int oz_trainer_apply(oz_trainer* t);                         /* Adam step + BN m
 int oz_trainer_set_dataset(oz_trainer* t, const uint64_t* own, const uint64_t* opp, const float* pi_target, const float* z_target, int64_t N);
 int oz_trainer_fit_epoch(oz_trainer* t, const int32_t* order, int64_t count, int batch, float* losses3);
 int oz_trainer_outputs(oz_trainer* t, int B, float* p /* [B][n*n] */, float* v /* [B] */);   /* of the last forward pass */
+/* Held-out evaluation in INFERENCE mode (keras Model.evaluate / validation_data): the network that will play -- the BN layers on their CURRENT
+ * moving statistics, no dropout -- on examples that are not trained on by the call.  The weights evaluated are the raw iterate (the trainer's
+ * parameters); the weight average of oz_optimizer.average_decay is NOT evaluated (it would need a second set of derived GEMM operands).
+ * The forward is the step's own: the same conv1 kernel and GEMM launches in the trainer's precision, the loss of the trainer's policy-loss mode.
+ * out[OZ_EVAL_FIELDS] float64:
+ *   out[0..2] = mean loss, policy loss, value loss (the definitions of losses3, in inference mode), float64 sums of the per-example float32 values;
+ *   out[3] = share of examples whose policy arg-max equals the target's (the lowest index among equal maxima on both sides);
+ *   out[4] = share of the examples with z != 0 whose v has z's sign (0 when there are none);
+ *   out[5] = examples; out[6] = examples with z != 0; out[7] = 0 (reserved).
+ * Batches of `batch` in [1, max_batch] in the given order, the last one may be short; the sums are added in an order that depends on the
+ * batch sizes alone (no atomics), so a repeated call returns the same doubles.
+ * oz_trainer_evaluate: N host examples, uploaded to arrays of the evaluation's own -- the resident data set of oz_trainer_set_dataset stays.
+ * oz_trainer_evaluate_dataset: `count` indices into the resident data set (any count >= 1; OZ_ERR_ARG while it is empty).
+ * oz_trainer_evaluate_replay (declared with the replay buffer below): `count` slot indices in [0, held).
+ * Left untouched: the weights, Adam moments, the weight average, the step count, the moving statistics and the ones a pending
+ * forward_backward has staged, the gradient arena, the losses of the last step, the resident data set and its order -- a forward_backward,
+ * an evaluation, then apply gives the weights it gives without the evaluation, bit for bit.  Overwritten: the pre-activations, activations,
+ * p / v and the staged batch, so oz_trainer_outputs / _get_activation (and get_preact) afterwards show the evaluation's LAST batch, and the
+ * plan rows' forward GEMM fields.  Errors: OZ_ERR_ARG for a batch outside [1, max_batch], an index out of range, another board size or
+ * device; in precision f16x2 the range guard acts as in a step (OZ_ERR_STATE, reported once).  Synchronous. */
+#define OZ_EVAL_FIELDS 8
+int oz_trainer_evaluate(oz_trainer* t, const uint64_t* own, const uint64_t* opp, const float* pi_target, const float* z_target, int64_t N,
+                        int batch, double* out);
+int oz_trainer_evaluate_dataset(oz_trainer* t, const int32_t* order, int64_t count, int batch, double* out);
 /* post-activation output of block `layer` (0-3 conv, 4-5 dense; [B][pixels][channels]) of the last forward pass -- inspection */
 int oz_trainer_get_activation(oz_trainer* t, int layer, int B, float* data, int64_t nelem);
 /* Diagnostics: read-only views of the last step, for judging every GEMM of the trainer on its own (no kernel is changed by them).
@@ -1249,6 +1273,8 @@ int oz_replay_read(oz_replay* r, int64_t first_slot, int64_t count, uint64_t* ow
 /* oz_trainer_fit_epoch with the replay buffer as the resident data set: order[i] = a slot index in [0, held); the same launches, steps and
  * losses as oz_trainer_fit_epoch on a data set with the slots' contents */
 int oz_trainer_fit_epoch_replay(oz_trainer* t, oz_replay* r, const int32_t* order, int64_t count, int batch, float* losses3);
+/* oz_trainer_evaluate_dataset with the replay buffer's slots as the data set (order[i] in [0, held)); locks the trainer, then the buffer */
+int oz_trainer_evaluate_replay(oz_trainer* t, oz_replay* r, const int32_t* order, int64_t count, int batch, double* out);
 
 /* ------------------------------------------------------------------ diagnostics
  * device arithmetic behind the PUCT / backup formulas (MCTS/__init__.py:68,168-170), for bit-exact

@@ -168,14 +168,16 @@ class NNetWrapper(_NetHandle):
             return self.train_precision
         return "f16x2" if self.precision == "f16x2" and self.num_channels % 256 == 0 else "f32"
 
-    def train(self, examples, verbose=None, seed=None, allreduce=None):
+    def train(self, examples, verbose=None, seed=None, allreduce=None, validation=None, validation_slots=None):
         """Net/NNet.py:53-68: model.fit(x=boards, y=[pis, vs], batch_size=self.batch_size, epochs=self.epochs) on the GPU
         (oz_trainer_*: MFMA forward / backward in the wrapper's precision -- "f16x2" runs the 3x3 layers' forward and data
         gradient on the fp16 matrix cores like the inference kernels (needs num_channels % 256 == 0, else fp32); train_precision="bf16x3"
         runs their forward and both gradients as three bf16 planes per fp32 value (fp32-class, no scaling, no guard) -- Adam
         lr=self.lr with clipvalue 0.5 for ONN / none for BNN, Dropout self.dropout, BN momentum 0.99; the wrapper's `optimizer` options act inside
         every step; with use_average the network receives the weight average after the fit).  Returns a History-like object (`.history['loss']`, ...).  The TensorBoard
-        callback of the reference is not reproduced.  Optimiser state persists across calls like the compiled Keras model's."""
+        callback of the reference is not reproduced.  Optimiser state persists across calls like the compiled Keras model's.
+        validation (example tuples) / validation_slots (slots of the ReplayBuffer passed as `examples`, held out of the fit: trainer.holdout_slots):
+        held-out examples evaluated in inference mode after every epoch, History.history gains the val_* lists (trainer.fit / fit_replay)."""
         from . import trainer as T
         from .replay import ReplayBuffer
         replay = examples if isinstance(examples, ReplayBuffer) else None
@@ -185,12 +187,51 @@ class NNetWrapper(_NetHandle):
                 raise ValueError("training from a ReplayBuffer is single-process: a data-parallel fit keeps the step-wise path (pass example tuples)")
             if replay.n != self.board_size_x:
                 raise ValueError(f"the ReplayBuffer holds {replay.n} x {replay.n} examples, this network plays {self.board_size_x} x {self.board_size_x}")
+            if validation is not None:
+                raise ValueError("a fit from a ReplayBuffer takes validation_slots= (slots of that buffer), not validation= example tuples")
             if len(replay) == 0:
                 return T.History()
+        elif validation_slots is not None:
+            raise ValueError("validation_slots= names slots of a ReplayBuffer: pass validation= example tuples with example tuples")
         elif not examples:
             return T.History()
         else:
             own, opp, pi, z = T.pack_examples(examples, self.board_size_x, self.in_channels)
+        self._sync_trainer(seed, allreduce)
+        shuffle_seed = 1000003 * self._fit_calls + (self._model_index if seed is None else seed)
+        if replay is not None:
+            hist = T.fit_replay(self._trainer, replay, batch_size=self.batch_size, epochs=self.epochs, shuffle_seed=shuffle_seed, verbose=verbose,
+                                validation_slots=validation_slots)
+        else:
+            val = T.pack_examples(validation, self.board_size_x, self.in_channels) if validation else None
+            hist = T.fit(self._trainer, own, opp, pi, z, batch_size=self.batch_size, epochs=self.epochs, shuffle_seed=shuffle_seed,
+                         allreduce=allreduce, verbose=verbose, validation=val)
+        return self._finish_fit(hist, allreduce)
+
+    def evaluate(self, examples_or_replay, slots=None):
+        """keras Model.evaluate on held-out examples, in inference mode on the device (trainer.Trainer.evaluate: moving BN statistics, no dropout, the
+        trainer's arithmetic and policy loss): example tuples, or a ReplayBuffer with `slots` (None: every held slot).  -> dict(loss,
+        pi-reshaped_loss, v_loss, policy_top1, value_sign, examples, decided).  The trainer is created as train() creates it and receives the
+        network's weights only when somebody else has set them since the trainer last exported (the weights version differs); nothing else
+        changes -- no step, no optimiser state, no commit.  What is evaluated is the trainer's raw iterate: with use_average the network plays the
+        weight average, which this does not measure."""
+        from . import trainer as T
+        from .replay import ReplayBuffer
+        self._sync_trainer(None, None, only_if_changed=True)
+        if isinstance(examples_or_replay, ReplayBuffer):
+            replay = examples_or_replay
+            if replay.n != self.board_size_x:
+                raise ValueError(f"the ReplayBuffer holds {replay.n} x {replay.n} examples, this network plays {self.board_size_x} x {self.board_size_x}")
+            slots = np.arange(len(replay), dtype=np.int32) if slots is None else np.ascontiguousarray(slots, dtype=np.int32)
+            return self._trainer.evaluate_replay(replay, slots, self.batch_size)
+        if slots is not None:
+            raise ValueError("slots= names slots of a ReplayBuffer")
+        own, opp, pi, z = T.pack_examples(examples_or_replay, self.board_size_x, self.in_channels)
+        return self._trainer.evaluate(own, opp, pi, z, batch_size=self.batch_size)
+
+    def _sync_trainer(self, seed, allreduce, only_if_changed=False):
+        """the trainer of train() / evaluate(): created at the first use, then given the network's weights where they are not its own"""
+        from . import trainer as T
         if getattr(self, "_trainer", None) is None:
             assert self.num_channels % 128 == 0, "the training kernels need num_channels % 128 == 0"
             # a GradientAllReduce owns the gradient arena (a torch tensor RCCL can reduce in place): the library writes into it
@@ -203,6 +244,11 @@ class NNetWrapper(_NetHandle):
             self._trainer_arena = getattr(allreduce, "ptr", None)
             self._fit_calls = 0
             self._exported_version = None
+        if only_if_changed:              # evaluate(): the weights go in only when the version differs, and the trainer then holds this version
+            if self._exported_version != self._weights_version:
+                self._trainer.set_weights(self.get_weights())
+                self._exported_version = self._weights_version
+            return
         assert getattr(allreduce, "ptr", None) == self._trainer_arena, "train() must keep using the GradientAllReduce it started with"
         if not self.optimizer or self._exported_version != self._weights_version:
             # (without options: as ever.)  Somebody else set the network's weights: the trainer (and its average) starts from them
@@ -213,12 +259,9 @@ class NNetWrapper(_NetHandle):
             for i in range(36):
                 if i % 6 in (4, 5):
                     _lib.check(_lib.load().oz_trainer_set_weight(self._trainer._h, i, _lib.p_f32(mine[i]), mine[i].size))
-        shuffle_seed = 1000003 * self._fit_calls + (self._model_index if seed is None else seed)
-        if replay is not None:
-            hist = T.fit_replay(self._trainer, replay, batch_size=self.batch_size, epochs=self.epochs, shuffle_seed=shuffle_seed, verbose=verbose)
-        else:
-            hist = T.fit(self._trainer, own, opp, pi, z, batch_size=self.batch_size, epochs=self.epochs, shuffle_seed=shuffle_seed,
-                         allreduce=allreduce, verbose=verbose)
+
+    def _finish_fit(self, hist, allreduce):
+        """the end of train(): the trained weights go to the network"""
         self._fit_calls += 1
         use_average = bool(self.optimizer and self.optimizer.get("use_average"))
         weights = self._trainer.get_weights(average=use_average)

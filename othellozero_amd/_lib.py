@@ -105,6 +105,7 @@ class Optimizer(C.Structure):                                                   
 
 
 LR_SCHEDULES = {"constant": 0, "linear": 1, "cosine": 2}                             # OZ_LR_*
+EVAL_FIELDS = 8                                                                      # OZ_EVAL_FIELDS
 SQSUM_KINDS = {"gradients": 0, "weights": 1}                                         # OZ_SQSUM_GRADIENTS / OZ_SQSUM_DECAYED_WEIGHTS
 
 
@@ -287,6 +288,8 @@ SIGNATURES = {
     "oz_trainer_apply": [_vp],
     "oz_trainer_set_dataset": [_vp, _u64p, _u64p, _f32p, _f32p, C.c_int64],
     "oz_trainer_fit_epoch": [_vp, _i32p, C.c_int64, C.c_int, _f32p],
+    "oz_trainer_evaluate": [_vp, _u64p, _u64p, _f32p, _f32p, C.c_int64, C.c_int, _f64p],
+    "oz_trainer_evaluate_dataset": [_vp, _i32p, C.c_int64, C.c_int, _f64p],
     "oz_trainer_outputs": [_vp, C.c_int, _f32p, _f32p],
     "oz_trainer_get_activation": [_vp, C.c_int, C.c_int, _f32p, C.c_int64],
     "oz_trainer_get_preact": [_vp, C.c_int, C.c_int, _f32p, C.c_int64], "oz_trainer_get_dz": [_vp, C.c_int, C.c_int, _f32p, C.c_int64],
@@ -316,6 +319,7 @@ SIGNATURES = {
     "oz_replay_restore": [_vp, _u64p, _u64p, _f32p, _f32p, C.c_int64, C.c_int64],
     "oz_replay_read": [_vp, C.c_int64, C.c_int64, _u64p, _u64p, _f32p, _f32p],
     "oz_trainer_fit_epoch_replay": [_vp, _vp, _i32p, C.c_int64, C.c_int, _f32p],
+    "oz_trainer_evaluate_replay": [_vp, _vp, _i32p, C.c_int64, C.c_int, _f64p],
 }
 
 _LIB = None

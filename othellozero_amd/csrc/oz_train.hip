@@ -231,6 +231,26 @@ __global__ __launch_bounds__(256) void k_t_bn_fwd(const float* __restrict__ z, c
     }
     *reinterpret_cast<f32x4*>(a + i) = out;
 }
+// inference mode (held-out evaluation): a = relu((z - moving_mean) * (1 / sqrtf(moving_var + eps)) * gamma + beta); 4 consecutive channels per
+// thread.  Writes nothing but `a`: no batch statistics, no staged moving statistics, no dropout
+__global__ __launch_bounds__(256) void k_t_bn_infer(const float* __restrict__ z, const float* __restrict__ mm, const float* __restrict__ mv,
+                                                    const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ a,
+                                                    const int* __restrict__ d_count, int P, int C) {
+    const long long total = (long long)(*d_count) * P * C;
+    const long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (i >= total) return;
+    const int c = (int)(i % C);
+    const f32x4 zv = *reinterpret_cast<const f32x4*>(z + i), mu = *reinterpret_cast<const f32x4*>(mm + c),
+                va = *reinterpret_cast<const f32x4*>(mv + c), ga = *reinterpret_cast<const f32x4*>(gamma + c),
+                be = *reinterpret_cast<const f32x4*>(beta + c);
+    f32x4 out;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float y = (zv[k] - mu[k]) * (1.0f / sqrtf(va[k] + BN_EPS)) * ga[k] + be[k];
+        out[k] = y > 0.f ? y : 0.f;
+    }
+    *reinterpret_cast<f32x4*>(a + i) = out;
+}
 // ---------------------------------------------------------------- heads: forward, losses, gradient wrt f2
 // one 64-thread block per sample (A = n*n <= 64 policy outputs, lane = action)
 // flat = 0 (OZ_POLICY_LOSS_ROWS): the reference's loss on the (n, n) view, every row renormalised and the rows averaged;
@@ -302,6 +322,102 @@ __global__ __launch_bounds__(64) void k_t_heads(const float* __restrict__ f2 /*[
         dvpre[b] = 2.0f * d / (float)B * (1.0f - v * v);
         loss[2 * b] = flat ? lpi : lpi / (float)n;          // per-sample mean over rows (ROWS)
         loss[2 * b + 1] = d * d;
+    }
+}
+// ---------------------------------------------------------------- held-out evaluation: heads without gradients, per-example metrics
+// k_t_heads' forward (the same logits, softmax, tanh and clipped cross entropy, flat as there) with no gradient stores; per example one row of
+// OZ_EVAL_ROW floats: [0] the policy loss of the mode, [1] (v - z)^2, [2] arg-max of p == arg-max of the target (lowest index among equal
+// maxima on both sides), [3] v z > 0, [4] z != 0
+#define OZ_EVAL_ROW 5
+__device__ __forceinline__ int t_argmax_lowest(float val, int lane) {      // wave reduction on (value, index): the larger value, the lower index on a tie
+    int idx = lane;
+    for (int o = 32; o; o >>= 1) {
+        const float ov = __shfl_xor(val, o);
+        const int oi = __shfl_xor(idx, o);
+        if (ov > val || (ov == val && oi < idx)) { val = ov; idx = oi; }
+    }
+    return idx;
+}
+__global__ __launch_bounds__(64) void k_t_eval_heads(const float* __restrict__ f2 /*[B][512]*/, const int* __restrict__ d_count, int n, int flat,
+                                                     const float* __restrict__ Wpi /*[512][A]*/, const float* __restrict__ bpi,
+                                                     const float* __restrict__ Wv /*[512]*/, const float* __restrict__ bv,
+                                                     const float* __restrict__ pit /*[B][A]*/, const float* __restrict__ zt /*[B]*/,
+                                                     float* __restrict__ p_out, float* __restrict__ v_out, float* __restrict__ rows /*[B][OZ_EVAL_ROW]*/) {
+    const int b = blockIdx.x, lane = threadIdx.x, A = n * n, B = *d_count;
+    if (b >= B) return;
+    const float* x = f2 + (size_t)b * 512;
+    float logit = -INFINITY, vacc = 0.f;
+    {   // (the weight loads of k_t_heads: 64 rows in flight, the fmaf chain in k order)
+        const auto wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Wpi), 0, 512 * A * 4, 0x00020000);
+        const int lo = (lane < A ? lane : 0) * 4;
+        float acc = 0.f;
+#pragma unroll 1
+        for (int k0 = 0; k0 < 512; k0 += 64) {
+            float wv[64];
+#pragma unroll
+            for (int j = 0; j < 64; ++j) wv[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(wrs, lo, (k0 + j) * A * 4, 0));
+#pragma unroll
+            for (int j = 0; j < 64; ++j) acc = fmaf(x[k0 + j], wv[j], acc);
+        }
+        if (lane < A) logit = acc + bpi[lane];
+    }
+    for (int k = lane; k < 512; k += 64) vacc = fmaf(x[k], Wv[k], vacc);
+    for (int o = 32; o; o >>= 1) vacc += __shfl_xor(vacc, o);
+    float mx = logit;
+    for (int o = 32; o; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    const float e = lane < A ? expf(logit - mx) : 0.f;
+    float se = e;
+    for (int o = 32; o; o >>= 1) se += __shfl_xor(se, o);
+    const float p = e / se;
+    const float v = tanhf(vacc + bv[0]);
+    const int row = flat ? 0 : lane / n, width = flat ? A : n;
+    const float t = lane < A ? pit[(size_t)b * A + lane] : 0.f;
+    float S = 0.f;
+    for (int c = 0; c < width; ++c) { const int src = row * n + c; S += __shfl(p, src < 63 ? src : 63); }
+    const float q = lane < A ? p / S : 0.5f;
+    const float qc = fminf(fmaxf(q, 1e-7f), 1.0f - 1e-7f);
+    float lpi = lane < A ? -t * logf(qc) : 0.f;
+    for (int o = 32; o; o >>= 1) lpi += __shfl_xor(lpi, o);
+    const int ap = t_argmax_lowest(lane < A ? p : -INFINITY, lane), at = t_argmax_lowest(lane < A ? t : -INFINITY, lane);      // idle lanes never win
+    if (lane < A) p_out[(size_t)b * A + lane] = p;
+    if (lane == 0) {
+        const float z = zt[b], d = v - z;
+        v_out[b] = v;
+        float* r = rows + (size_t)b * OZ_EVAL_ROW;
+        r[0] = flat ? lpi : lpi / (float)n;
+        r[1] = d * d;
+        r[2] = ap == at ? 1.f : 0.f;
+        r[3] = v * z > 0.f ? 1.f : 0.f;
+        r[4] = z != 0.f ? 1.f : 0.f;
+    }
+}
+// one block adds the B rows of a batch into the accumulator: thread i sums rows i, i + 256, ... in example order, then a fixed tree over the 256
+// partial sums -- the order depends on nothing but B (no atomics)
+struct TEvalAcc { double sum[2]; long long cnt[3]; long long examples; };
+__global__ __launch_bounds__(256) void k_t_acc_eval(const float* __restrict__ rows, int B, TEvalAcc* __restrict__ acc) {
+    __shared__ double sd[2][256];
+    __shared__ int sc[3][256];
+    const int i = threadIdx.x;
+    double d0 = 0.0, d1 = 0.0;
+    int c0 = 0, c1 = 0, c2 = 0;
+    for (int b = i; b < B; b += 256) {
+        const float* r = rows + (size_t)b * OZ_EVAL_ROW;
+        d0 += (double)r[0]; d1 += (double)r[1];
+        c0 += r[2] != 0.f; c1 += r[3] != 0.f; c2 += r[4] != 0.f;
+    }
+    sd[0][i] = d0; sd[1][i] = d1; sc[0][i] = c0; sc[1][i] = c1; sc[2][i] = c2;
+    __syncthreads();
+    for (int o = 128; o; o >>= 1) {
+        if (i < o) {
+            sd[0][i] += sd[0][i + o]; sd[1][i] += sd[1][i + o];
+            sc[0][i] += sc[0][i + o]; sc[1][i] += sc[1][i + o]; sc[2][i] += sc[2][i + o];
+        }
+        __syncthreads();
+    }
+    if (i == 0) {
+        acc->sum[0] += sd[0][0]; acc->sum[1] += sd[1][0];
+        acc->cnt[0] += sc[0][0]; acc->cnt[1] += sc[1][0]; acc->cnt[2] += sc[2][0];
+        acc->examples += B;
     }
 }
 // dWpi[k][a] = sum_b f2[b][k] dlogit[b][a];  dWv[k] = sum_b f2[b][k] dvpre[b]   (block = k, thread = a; a == A handles v)
@@ -1070,6 +1186,13 @@ struct oz_trainer {
     int* ds_order = nullptr;
     double* ds_acc = nullptr;
     int64_t ds_n = 0, ds_cap = 0, ds_order_cap = 0;
+    // held-out evaluation (oz_trainer_evaluate*): an order buffer, example arrays (the host-array entry point), per-example rows and an accumulator of
+    // its own -- the resident data set, ds_order and ds_acc of a fit are never touched
+    int* ev_order = nullptr;
+    uint64_t *ev_own = nullptr, *ev_opp = nullptr;
+    float *ev_pi = nullptr, *ev_z = nullptr, *ev_rows = nullptr;
+    TEvalAcc* ev_acc = nullptr;
+    int64_t ev_order_cap = 0, ev_cap = 0;
     // diagnostics (oz_trainer_set_capture / get_dgrad / get_plan): the raw data gradients of a step, copied out of the ping-pong buffers, and its launch plan
     bool capture = false, cap_valid = false, ran = false;      // ran: a step has been enqueued (the views below have something to show)
     float* cap[6] = {};                  // cap[l] = the gradient wrt a[l] as the heads / the data-gradient launch of layer l + 1 left it (allocated at the first capture)
@@ -1093,6 +1216,7 @@ struct oz_trainer {
         if (s) hipStreamSynchronize(s);
         for (void* q : allocs) hipFree(q);
         for (void* q : {(void*)ds_own, (void*)ds_opp, (void*)ds_pi, (void*)ds_z, (void*)ds_order, (void*)ds_acc}) if (q) hipFree(q);
+        for (void* q : {(void*)ev_order, (void*)ev_own, (void*)ev_opp, (void*)ev_pi, (void*)ev_z}) if (q) hipFree(q);
         if (h_in) hipHostFree(h_in);
         for (hipEvent_t e : ev_dz) if (e) hipEventDestroy(e);
         if (ev_w) hipEventDestroy(ev_w);
@@ -1470,6 +1594,16 @@ static int t_bn_forward(oz_trainer* t, int l, int B) {
     return OZ_OK;
 }
 
+// BN (inference mode: the moving statistics) + ReLU of layer l: z[l] -> a[l], nothing else written
+static int t_bn_infer(oz_trainer* t, int l, int B) {
+    const int Cc = t->L[l].Co, P = t->L[l].P;
+    const long long total = (long long)B * P * Cc;
+    hipLaunchKernelGGL(k_t_bn_infer, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, t->s, t->z[l], t->stats[6 * l + 4], t->stats[6 * l + 5],
+                       t->param(6 * l + 2), t->param(6 * l + 3), t->a[l], t->d_count, P, Cc);
+    OZ_HIP(hipGetLastError());
+    return OZ_OK;
+}
+
 // the main stream waits for an operand of t_refresh where it first reads it, once per refresh
 static int t_wait_once(hipStream_t s, hipEvent_t e, bool& pending) {
     if (pending) { OZ_HIP(hipStreamWaitEvent(s, e, 0)); pending = false; }
@@ -1480,15 +1614,16 @@ static int t_wait_once(hipStream_t s, hipEvent_t e, bool& pending) {
 // backward -> dgrad -> BN backward of the layer below -> ...) stays on the main stream; what only needs a[l - 1] and dz[l] -- the weight gradient
 // and the bias gradient's last sum -- runs on the second stream behind ev_dz[l], beside the chain, whose small-batch launches leave most CUs idle.
 
-// forward: boards -> conv1 .. fc2 (each with its BN) -> heads and losses
-static int t_forward(oz_trainer* t, int B) {
+// forward: boards -> conv1 .. fc2 (each with its BN) -> heads and losses.  infer (held-out evaluation): the same conv1 and GEMM launches, the BN
+// on the moving statistics without dropout (k_t_bn_infer), and k_t_eval_heads (metrics rows, no gradients) at the end
+static int t_forward(oz_trainer* t, int B, bool infer = false) {
     hipStream_t s = t->s;
     const int n = t->n, C = t->C, A = n * n;
     const long long tot = (long long)B * A * (C / 4);
     hipLaunchKernelGGL(k_t_conv1_fwd, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, t->d_own, t->d_opp, t->d_count, n, C, t->cin,
                        t->param(0), t->param(1), t->z[0]);
     OZ_HIP(hipGetLastError());
-    if (int rc = t_bn_forward(t, 0, B)) return rc;
+    if (int rc = infer ? t_bn_infer(t, 0, B) : t_bn_forward(t, 0, B)) return rc;
     for (int l = 1; l < 6; ++l) {
         const TLayer& L = t->L[l];
         const int Pin = t->L[l - 1].P;
@@ -1516,7 +1651,13 @@ static int t_forward(oz_trainer* t, int B) {
                                            L.Cin, 9, L.Co, 0, s, t->gpartial, t->gpartial_floats, t->zeros, 0, &t->plan[l - 1][OZ_TRAINER_PLAN_FWD_KSLICES])) return rc;
         }
         }
-        if (int rc = t_bn_forward(t, l, B)) return rc;
+        if (int rc = infer ? t_bn_infer(t, l, B) : t_bn_forward(t, l, B)) return rc;
+    }
+    if (infer) {
+        hipLaunchKernelGGL(k_t_eval_heads, dim3(B), dim3(64), 0, s, t->a[5], t->d_count, n, t->policy_loss, t->param(36), t->param(37), t->param(38),
+                           t->param(39), t->d_pit, t->d_zt, t->p, t->v, t->ev_rows);
+        OZ_HIP(hipGetLastError());
+        return OZ_OK;
     }
     hipLaunchKernelGGL(k_t_heads, dim3(B), dim3(64), 0, s, t->a[5], t->d_count, n, t->policy_loss, t->param(36), t->param(37), t->param(38), t->param(39),
                        t->d_pit, t->d_zt, t->p, t->v, t->dlogit, t->dvpre, t->loss);
@@ -1868,6 +2009,95 @@ OZ_API int oz_trainer_fit_epoch_replay(oz_trainer* t, oz_replay* r, const int32_
     for (int64_t i = 0; i < count; ++i)
         OZ_REQUIRE(order[i] >= 0 && order[i] < held, "oz_trainer_fit_epoch_replay: index %d outside the %lld examples the replay buffer holds", order[i], (long long)held);
     return t_fit_epoch_view(t, {r->own, r->opp, r->pi, r->z, held}, order, count, batch, losses3);
+}
+
+// ---------------------------------------------------------------- held-out evaluation in inference mode
+// `count` examples of `d` in the order `order` (validated by the caller's entry point), batches of `batch`: per batch the device-side gather, the
+// inference forward (the raw iterate t->P, the CURRENT moving statistics, no dropout) and the accumulation, back to back on the main stream; one
+// synchronisation and one read-back.  Leaves alone: the weights, Adam moments, the weight average, step, the staged moving statistics (stats_new),
+// the gradient arena, t->losses, the resident data set and ds_order.  Overwrites: z[l], a[l], p, v, the batch staging buffers (d_own .. d_count),
+// the packed activations of a split mode and the plan rows' forward fields
+static int t_evaluate_view(oz_trainer* t, const TDataView& d, const int32_t* order, int64_t count, int batch, double* out) {
+    OZ_HIP(hipSetDevice(t->device));
+    hipStream_t s = t->s;
+    const int A = t->n * t->n;
+    if (count > t->ev_order_cap) {
+        OZ_HIP(hipStreamSynchronize(s));
+        if (t->ev_order) hipFree(t->ev_order);
+        t->ev_order = nullptr; t->ev_order_cap = 0;
+        OZ_HIP(hipMalloc((void**)&t->ev_order, count * sizeof(int)));
+        t->ev_order_cap = count;
+    }
+    if (!t->ev_rows) T_ALLOC(t->ev_rows, (size_t)t->Bmax * OZ_EVAL_ROW);
+    if (!t->ev_acc) T_ALLOC(t->ev_acc, 1);
+    OZ_HIP(hipMemcpyAsync(t->ev_order, order, count * sizeof(int), hipMemcpyHostToDevice, s));
+    OZ_HIP(hipMemsetAsync(t->ev_acc, 0, sizeof(TEvalAcc), s));
+    if (t->dirty) if (int rc = t_refresh(t)) return rc;
+    for (int64_t first = 0; first < count; first += batch) {
+        const int B = (int)(count - first < batch ? count - first : batch);
+        hipLaunchKernelGGL(k_t_gather_batch, dim3((B * A + 255) / 256), dim3(256), 0, s, d.own, d.opp, d.pi, d.z, t->ev_order,
+                           (int)first, B, A, t->d_own, t->d_opp, t->d_pit, t->d_zt, t->d_count);
+        if (int rc = t_forward(t, B, /*infer=*/true)) return rc;
+        hipLaunchKernelGGL(k_t_acc_eval, dim3(1), dim3(256), 0, s, t->ev_rows, B, t->ev_acc);
+    }
+    OZ_HIP(hipGetLastError());
+    TEvalAcc h;
+    OZ_HIP(hipMemcpyAsync(&h, t->ev_acc, sizeof h, hipMemcpyDeviceToHost, s));
+    OZ_HIP(hipStreamSynchronize(s));
+    const double N = (double)h.examples;
+    out[1] = h.sum[0] / N; out[2] = h.sum[1] / N; out[0] = out[1] + out[2];
+    out[3] = (double)h.cnt[0] / N;
+    out[4] = h.cnt[2] > 0 ? (double)h.cnt[1] / (double)h.cnt[2] : 0.0;
+    out[5] = N; out[6] = (double)h.cnt[2]; out[7] = 0.0;
+    return t_check_range(t);
+}
+
+OZ_API int oz_trainer_evaluate(oz_trainer* t, const uint64_t* own, const uint64_t* opp, const float* pi, const float* z, int64_t N, int batch, double* out) {
+    OZ_REQUIRE(t && own && opp && pi && z && out && N >= 1 && N < (1ll << 31), "oz_trainer_evaluate: bad argument");
+    T_LOCK(t);
+    OZ_REQUIRE(batch >= 1 && batch <= t->Bmax, "oz_trainer_evaluate: batch %d outside [1, %d]", batch, t->Bmax);
+    OZ_HIP(hipSetDevice(t->device));
+    const int A = t->n * t->n;
+    if (N > t->ev_cap) {               // arrays of the evaluation's own: the resident data set of a fit stays what it is
+        OZ_HIP(hipStreamSynchronize(t->s));
+        for (void* q : {(void*)t->ev_own, (void*)t->ev_opp, (void*)t->ev_pi, (void*)t->ev_z}) if (q) hipFree(q);
+        t->ev_own = t->ev_opp = nullptr; t->ev_pi = t->ev_z = nullptr; t->ev_cap = 0;
+        OZ_HIP(hipMalloc((void**)&t->ev_own, N * sizeof(uint64_t))); OZ_HIP(hipMalloc((void**)&t->ev_opp, N * sizeof(uint64_t)));
+        OZ_HIP(hipMalloc((void**)&t->ev_pi, (size_t)N * A * sizeof(float))); OZ_HIP(hipMalloc((void**)&t->ev_z, N * sizeof(float)));
+        t->ev_cap = N;
+    }
+    OZ_HIP(hipMemcpyAsync(t->ev_own, own, N * sizeof(uint64_t), hipMemcpyHostToDevice, t->s));
+    OZ_HIP(hipMemcpyAsync(t->ev_opp, opp, N * sizeof(uint64_t), hipMemcpyHostToDevice, t->s));
+    OZ_HIP(hipMemcpyAsync(t->ev_pi, pi, (size_t)N * A * sizeof(float), hipMemcpyHostToDevice, t->s));
+    OZ_HIP(hipMemcpyAsync(t->ev_z, z, N * sizeof(float), hipMemcpyHostToDevice, t->s));
+    std::vector<int32_t> order((size_t)N);
+    for (int64_t i = 0; i < N; ++i) order[(size_t)i] = (int32_t)i;
+    const int rc = t_evaluate_view(t, {t->ev_own, t->ev_opp, t->ev_pi, t->ev_z, N}, order.data(), N, batch, out);
+    if (rc) hipStreamSynchronize(t->s);            // (a successful call has synchronised) the uploads out of the caller's arrays and `order` may still be in flight
+    return rc;
+}
+
+OZ_API int oz_trainer_evaluate_dataset(oz_trainer* t, const int32_t* order, int64_t count, int batch, double* out) {
+    OZ_REQUIRE(t && order && out && count >= 1 && count < (1ll << 31), "oz_trainer_evaluate_dataset: bad argument");
+    T_LOCK(t);
+    OZ_REQUIRE(t->ds_n > 0, "oz_trainer_evaluate_dataset: the resident data set is empty (oz_trainer_set_dataset first)");
+    OZ_REQUIRE(batch >= 1 && batch <= t->Bmax, "oz_trainer_evaluate_dataset: batch %d outside [1, %d]", batch, t->Bmax);
+    for (int64_t i = 0; i < count; ++i) OZ_REQUIRE(order[i] >= 0 && order[i] < t->ds_n, "oz_trainer_evaluate_dataset: index %d outside the data set", order[i]);
+    return t_evaluate_view(t, {t->ds_own, t->ds_opp, t->ds_pi, t->ds_z, t->ds_n}, order, count, batch, out);
+}
+
+// (trainer locked before the replay buffer, as in oz_trainer_fit_epoch_replay)
+OZ_API int oz_trainer_evaluate_replay(oz_trainer* t, oz_replay* r, const int32_t* order, int64_t count, int batch, double* out) {
+    OZ_REQUIRE(t && r && order && out && count >= 1 && count < (1ll << 31), "oz_trainer_evaluate_replay: bad argument");
+    T_LOCK(t);
+    std::lock_guard<std::mutex> rlock(r->mu);
+    OZ_REQUIRE(r->n == t->n, "oz_trainer_evaluate_replay: the trainer's boards are %d x %d, the replay buffer's %d x %d", t->n, t->n, r->n, r->n);
+    OZ_REQUIRE(r->device == t->device, "oz_trainer_evaluate_replay: the trainer lives on device %d, the replay buffer on device %d", t->device, r->device);
+    OZ_REQUIRE(batch >= 1 && batch <= t->Bmax, "oz_trainer_evaluate_replay: batch %d outside [1, %d]", batch, t->Bmax);
+    const int64_t held = r->held();
+    for (int64_t i = 0; i < count; ++i)
+        OZ_REQUIRE(order[i] >= 0 && order[i] < held, "oz_trainer_evaluate_replay: index %d outside the %lld examples the replay buffer holds", order[i], (long long)held);
+    return t_evaluate_view(t, {r->own, r->opp, r->pi, r->z, held}, order, count, batch, out);
 }
 
 // the two stages of the sum of squares of `X`'s arrays `sg` on the main stream -> norm_out[slot] (clipnorm > 0: the clip scale too)

@@ -349,6 +349,32 @@ def _log_resign(i, num_iterations, stats):
                  '%.3f' % (stats["exempt_wrong"] / stats["exempt_triggered"]) if stats["exempt_triggered"] else 'n/a')
 
 
+def _fit_with_holdout(i, num_iterations, neural_network, replay, total_before, share):
+    """the device fit of an iteration with the newest floor(share * E) of the E examples its append wrote held out (trainer.holdout_slots):
+    evaluated before the fit and after each epoch, logged, and recorded in training.validation_history"""
+    from .trainer import VAL_KEYS, holdout_slots
+    held, capacity, total = replay.info()
+    _, val_slots = holdout_slots(held, capacity, total, total - total_before, share)
+    before = neural_network.evaluate(replay, val_slots) if val_slots.size else None
+    hist = neural_network.train(replay, verbose=2 if logging.root.level <= logging.DEBUG else None, validation_slots=val_slots)
+    epochs = [{k: hist.history["val_" + k][ep] for k in VAL_KEYS} for ep in range(len(hist.history.get("val_loss", [])))]
+    stats = dict(examples=int(val_slots.size), decided=before["decided"] if before else 0, before=before, epochs=epochs)
+    training.validation_history.append(stats)
+    _log_validation(i, num_iterations, stats)
+    return hist
+
+
+def _log_validation(i, num_iterations, stats):
+    if not stats["epochs"]:
+        logging.info('[%d/%d] held-out evaluation: %d examples held out, nothing to report', i, num_iterations, stats["examples"])
+        return
+    b, e = stats["before"], stats["epochs"][-1]
+    logging.info('[%d/%d] held-out evaluation: %d newest examples (%d decided) / loss %.4f -> %.4f (pi %.4f -> %.4f, v %.4f -> %.4f) / '
+                 'policy_top1 %.3f -> %.3f / value_sign %.3f -> %.3f (before the fit -> after its last epoch)', i, num_iterations,
+                 stats["examples"], stats["decided"], b["loss"], e["loss"], b["pi-reshaped_loss"], e["pi-reshaped_loss"], b["v_loss"], e["v_loss"],
+                 b["policy_top1"], e["policy_top1"], b["value_sign"], e["value_sign"])
+
+
 def _log_endgame(i, num_iterations, stats):
     logging.info('[%d/%d] endgame targets: solved %d / z_changed %d / mean_disc_loss %.3f', i, num_iterations, stats["solved"],
                  stats["z_changed"], stats["mean_disc_loss"])
@@ -361,8 +387,18 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
              distributed=False, batched_evaluation=False, policy_target="onehot", target_temperature=1.0, leaves_per_step=1,
              root_noise=None, sample_moves=None, replay="host", evaluation_opponent="random", endgame_targets=0,
              solve_leaves=0, match_openings=None, evaluation_openings=None, playout_cap=None, forced_playouts=None, eval_symmetry=None,
-             value_target="outcome", gumbel=None, surprise_weight=None, resign=None):
+             value_target="outcome", gumbel=None, surprise_weight=None, resign=None, validation_share=None):
     """main.py:56-259 on the GPU engines; returns `historic` = [(episodes done, win rate vs random), ...]
+
+    validation_share=f in (0, 0.5] (None = off, the default: the loop is unchanged): held-out evaluation of every iteration's fit.  After an
+    iteration's append, the newest floor(f * E) of the E examples that append wrote (trainer.holdout_slots) are held out of THAT iteration's fit
+    and evaluated in inference mode -- moving BN statistics, no dropout (NNetWrapper.evaluate) -- before the fit and after each of its epochs:
+    one log line per iteration, and training.validation_history gains dict(examples, decided, before, epochs=[one dict per epoch]).  The
+    examples stay in the ring and are ordinary training data from the next iteration on: validation is always on the newest games, never
+    trained on at the time they are measured.  It needs replay="device" (ValueError otherwise).  Two known leaks: the cut may fall inside a
+    game or between the symmetric copies of one position, so a held-out example may have a sibling in the training part; and opening
+    positions recur in every game, so early-ply examples are in effect seen before.  The numbers bound nothing about playing strength, which is
+    neither gated nor claimed ("Held-out evaluation").
 
     resign=(v, r, min_ply, keep_prob) (None = off, the default): resignation of decided SELF-PLAY games with a played-out audit share
     (SelfPlayEngine), in the host path, the distributed path (the flag travels inside the 48-byte records through the all-gather) and with
@@ -498,6 +534,16 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
     resign_kw = {"resign": resign} if resign is not None else {}
     training.resign_history = []
     training.surprise_history = []
+    training.validation_history = []
+    if validation_share is not None:
+        if isinstance(validation_share, bool) or not isinstance(validation_share, (int, float)) or not 0.0 < validation_share <= 0.5:
+            raise ValueError(f"validation_share must be None or a share in (0, 0.5] of an iteration's new examples (got {validation_share!r})")
+        if distributed:
+            raise ValueError("validation_share is not offered with distributed=True: the held-out examples are slots of the device replay buffer, "
+                             "which is single-process")
+        if replay != "device":
+            raise ValueError("validation_share needs replay='device': the held-out examples are the newest slots of the device replay buffer; the "
+                             "host example path shuffles its buffer in place and has no newest part")
     if surprise_weight is not None:
         surprise_weight = _lib.check_surprise_frac(surprise_weight)
         if distributed:
@@ -616,6 +662,7 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
             if previous is not None:
                 net.set_eval_symmetry(*previous)
         if device_replay is not None:
+            total_before = device_replay.total if validation_share is not None else 0
             appended, endgame = _selfplay_into_replay(device_replay, neural_network, board_size, num_episodes, num_simulations,
                                                       degree_exploration, temperature, e_greedy, seed, total_episodes_done, q_mode, visits,
                                                       leaves_per_step, root_noise, sample_moves, alias_final_boards, policy_target,
@@ -637,7 +684,10 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
             logging.info('[%d/%d] self-play done: %d records, device buffer holds %d examples', i, num_iterations, appended, len(device_replay))
             restore_eval_symmetry()
             logging.info('[%d/%d] fit on the device buffer', i, num_iterations)
-            neural_network.train(device_replay, verbose=2 if logging.root.level <= logging.DEBUG else None)
+            if validation_share is not None:
+                _fit_with_holdout(i, num_iterations, neural_network, device_replay, total_before, validation_share)
+            else:
+                neural_network.train(device_replay, verbose=2 if logging.root.level <= logging.DEBUG else None)
         else:
             if distributed:
                 first, count = shard_games(num_episodes, rank, world)

@@ -212,6 +212,40 @@ class Trainer:
         _lib.check(_lib.load().oz_trainer_fit_epoch_replay(self._h, replay._h, _lib.p_i32(order), order.size, int(batch_size), _lib.p_f32(out)))
         return out
 
+    # ---- held-out evaluation in inference mode (oz_trainer_evaluate*): moving BN statistics, no dropout, the trainer's raw iterate; no state of
+    # a fit is touched (outputs() / activation() afterwards show the evaluation's last batch)
+    @staticmethod
+    def _eval_dict(out):
+        return {"loss": float(out[0]), "pi-reshaped_loss": float(out[1]), "v_loss": float(out[2]), "policy_top1": float(out[3]),
+                "value_sign": float(out[4]), "examples": int(out[5]), "decided": int(out[6])}
+
+    def evaluate(self, own, opp, pi, z, batch_size=None):
+        """keras Model.evaluate on host examples (the resident data set of a fit stays): dict(loss, pi-reshaped_loss, v_loss -- the fit's loss
+        definitions --, policy_top1 = share of examples whose policy arg-max is the target's (lowest index on ties), value_sign = share of the
+        `decided` examples (z != 0) whose v has z's sign, examples, decided).  batch_size None: max_batch"""
+        own = np.ascontiguousarray(own, dtype=np.uint64).ravel()
+        opp = np.ascontiguousarray(opp, dtype=np.uint64).ravel()
+        pi = np.ascontiguousarray(pi, dtype=np.float32).reshape(own.size, self.n * self.n)
+        z = np.ascontiguousarray(z, dtype=np.float32).reshape(own.size)
+        out = np.zeros(_lib.EVAL_FIELDS, np.float64)
+        _lib.check(_lib.load().oz_trainer_evaluate(self._h, _lib.p_u64(own), _lib.p_u64(opp), _lib.p_f32(pi), _lib.p_f32(z), own.size,
+                                                   int(self.max_batch if batch_size is None else batch_size), _lib.p_f64(out)))
+        return self._eval_dict(out)
+
+    def evaluate_dataset(self, order, batch_size):
+        """evaluate() on the examples `order` indexes in the resident data set (set_dataset)"""
+        order = np.ascontiguousarray(order, dtype=np.int32)
+        out = np.zeros(_lib.EVAL_FIELDS, np.float64)
+        _lib.check(_lib.load().oz_trainer_evaluate_dataset(self._h, _lib.p_i32(order), order.size, int(batch_size), _lib.p_f64(out)))
+        return self._eval_dict(out)
+
+    def evaluate_replay(self, replay, order, batch_size):
+        """evaluate() on a ReplayBuffer's slots `order` (indices in [0, len(replay))), read in place on the device"""
+        order = np.ascontiguousarray(order, dtype=np.int32)
+        out = np.zeros(_lib.EVAL_FIELDS, np.float64)
+        _lib.check(_lib.load().oz_trainer_evaluate_replay(self._h, replay._h, _lib.p_i32(order), order.size, int(batch_size), _lib.p_f64(out)))
+        return self._eval_dict(out)
+
     def apply(self):
         _lib.check(_lib.load().oz_trainer_apply(self._h))
 
@@ -319,9 +353,31 @@ def pack_examples(examples, board_size, in_channels=2):
     return own, opp, pi, z
 
 
-def _record_epoch(hist, ep, epochs, means, verbose, trainer=None):
-    for k, val in zip(("loss", "pi-reshaped_loss", "v_loss"), means):
-        hist.history[k].append(float(val))
+VAL_KEYS = ("loss", "pi-reshaped_loss", "v_loss", "policy_top1", "value_sign")      # History.history gains "val_" + each with validation data
+
+
+def holdout_slots(held, capacity, total, new_examples, share):
+    """the newest examples of a ReplayBuffer as a validation split: (train_slots, validation_slots), int32.  held / capacity / total: the buffer's
+    info() after an append that wrote `new_examples` examples; V = floor(share * min(new_examples, held)) validation examples, the running
+    indices [total - V, total) modulo capacity (the ring's slot rule); the training slots are every other held slot, ascending.  0 < share <= 0.5.
+    A pure function (no GPU)."""
+    if not 0.0 < share <= 0.5:
+        raise ValueError(f"share={share!r}: the held-out share of the new examples lies in (0, 0.5]")
+    held, capacity, total, new_examples = int(held), int(capacity), int(total), int(new_examples)
+    assert 0 <= held <= capacity and held == min(total, capacity) and new_examples >= 0, (held, capacity, total, new_examples)
+    V = int(np.floor(share * min(new_examples, held)))
+    val = (np.arange(total - V, total, dtype=np.int64) % max(capacity, 1)).astype(np.int32)
+    keep = np.ones(held, bool)
+    keep[val] = False
+    return np.flatnonzero(keep).astype(np.int32), val
+
+
+def _record_epoch(hist, ep, epochs, means, verbose, trainer=None, val=None):
+    for k, mean in zip(("loss", "pi-reshaped_loss", "v_loss"), means):
+        hist.history[k].append(float(mean))
+    if val is not None:
+        for k in VAL_KEYS:
+            hist.history.setdefault("val_" + k, []).append(float(val[k]))
     hist.epoch.append(ep)
     if hasattr(trainer, "step_info") and trainer.step > 0:
         info = trainer.step_info()
@@ -329,24 +385,39 @@ def _record_epoch(hist, ep, epochs, means, verbose, trainer=None):
         hist.grad_norm.append(info["grad_norm"] if trainer.optimizer()["global_clipnorm"] > 0 else None)
     if verbose:
         print(f"Epoch {ep + 1}/{epochs} - loss: {hist.history['loss'][-1]:.4f} - pi-reshaped_loss: "
-              f"{hist.history['pi-reshaped_loss'][-1]:.4f} - v_loss: {hist.history['v_loss'][-1]:.4f}")
+              f"{hist.history['pi-reshaped_loss'][-1]:.4f} - v_loss: {hist.history['v_loss'][-1]:.4f}"
+              + ("" if val is None else "".join(f" - val_{k}: {val[k]:.4f}" for k in VAL_KEYS)))
 
 
-def fit_replay(trainer, replay, batch_size=32, epochs=10, shuffle_seed=0, verbose=None):
+def fit_replay(trainer, replay, batch_size=32, epochs=10, shuffle_seed=0, verbose=None, validation_slots=None):
     """`fit(..., resident=True)` on the examples a ReplayBuffer holds, read in place on the device (oz_trainer_fit_epoch_replay): the same
     per-epoch order RandomState(shuffle_seed + ep).permutation(len(replay)) over the slots, the same batches, steps, weights and losses
-    as fit() on replay.read().  Single-process training."""
+    as fit() on replay.read().  Single-process training.
+
+    validation_slots (None: as ever): slots held out of the fit (holdout_slots) -- the epochs train on the other held slots, ascending, in the
+    order train_slots[RandomState(shuffle_seed + ep).permutation(len(train_slots))], and after every epoch the held-out slots are evaluated in
+    inference mode (Trainer.evaluate_replay): History.history gains val_loss, val_pi-reshaped_loss, val_v_loss, val_policy_top1, val_value_sign."""
     N = len(replay)
     hist = History()
+    train_slots = None
+    if validation_slots is not None:
+        validation_slots = np.ascontiguousarray(validation_slots, dtype=np.int32).ravel()
+        keep = np.ones(N, bool)
+        keep[validation_slots] = False
+        train_slots = np.flatnonzero(keep).astype(np.int32)
+        N = len(train_slots)
     for ep in range(epochs if N else 0):
         order = np.random.RandomState(shuffle_seed + ep).permutation(N)
+        if train_slots is not None:
+            order = train_slots[order]
         means = np.asarray(trainer.fit_epoch_replay(replay, order, batch_size), dtype=np.float64)
-        _record_epoch(hist, ep, epochs, means, verbose, trainer)
+        val = trainer.evaluate_replay(replay, validation_slots, batch_size) if validation_slots is not None and validation_slots.size else None
+        _record_epoch(hist, ep, epochs, means, verbose, trainer, val)
     trainer.sync()
     return hist
 
 
-def fit(trainer, own, opp, pi, z, batch_size=32, epochs=10, shuffle_seed=0, allreduce=None, verbose=None, resident=None):
+def fit(trainer, own, opp, pi, z, batch_size=32, epochs=10, shuffle_seed=0, allreduce=None, verbose=None, resident=None, validation=None):
     """keras Model.fit(x, y, batch_size, epochs) with shuffle=True (the default the reference relies on).
     `allreduce(trainer)` -- if given -- averages the gradient arena across ranks between backward and apply.
 
@@ -354,7 +425,11 @@ def fit(trainer, own, opp, pi, z, batch_size=32, epochs=10, shuffle_seed=0, allr
     epoch is one library call that runs its optimiser steps back to back on the device (oz_trainer_fit_epoch) -- the
     same shuffled order, batches, steps and weights as the step-wise loop, without a host copy or a synchronisation
     per step.  With an all-reduce (data-parallel training) the loop stays step-wise: the collective sits between
-    backward and apply."""
+    backward and apply.
+
+    validation (None: as ever): (own, opp, pi, z) of held-out examples, evaluated in inference mode after every epoch (Trainer.evaluate: moving BN
+    statistics, no dropout); History.history gains val_loss, val_pi-reshaped_loss, val_v_loss, val_policy_top1, val_value_sign (Keras' names).
+    With an all-reduce each rank evaluates its own validation examples: no collective is added."""
     N = len(z)
     hist = History()
     if resident is None:
@@ -385,6 +460,7 @@ def fit(trainer, own, opp, pi, z, batch_size=32, epochs=10, shuffle_seed=0, allr
                 tot += np.asarray(losses) * len(idx)            # keras reports the sample-weighted running mean
                 seen += len(idx)
             means = tot / max(seen, 1)
-        _record_epoch(hist, ep, epochs, means, verbose, trainer)
+        val = trainer.evaluate(*validation, batch_size=batch_size) if validation is not None and len(validation[3]) else None
+        _record_epoch(hist, ep, epochs, means, verbose, trainer, val)
     trainer.sync()
     return hist
