@@ -381,6 +381,31 @@ int oz_mcts_get_solve_leaves(oz_mcts* m, int* max_empties, int64_t* rows_solved 
 int oz_mcts_solve_leaves_profile(oz_mcts* m, int enable);
 int oz_mcts_solve_leaves_profile_read(oz_mcts* m, double* ms_total, int64_t* launches, int reset);
 
+/* ---- value signs: a backup whose signs are right across passes and finished boards (opt-in; OZ_VALUE_SIGNS_REFERENCE, the default, is the
+ * search above bit for bit).  The reference's rule (MCTS/__init__.py:39-40,68-71) negates the value once per level on the way up, and returns
+ * -reward of a finished board seen from channel 0.  Two things differ from a sound negamax: a finished child is not
+ * colour-swapped, so a move that wins the game on the spot stores Q = -1 in its parent (and a draw counts as channel 0's win); and after a
+ * pass the same side moves again, yet the value is negated there too, so every value that crosses a pass arrives above it with the wrong sign.
+ * With OZ_VALUE_SIGNS_SOUND, for a descent along the edges 0 .. depth-1, sigma_d = 1 where the sides swapped after edge d and 0 where the
+ * same side moves again (a pass, or the game is over), and V_L the leaf's value for the side to move at the leaf (the network's v, the solved
+ * sign, or sign(discs own - discs opp) in {-1, 0, +1} on a finished board, an integer value like the reference's):
+ *     edge d gets  V_L * (-1)^(sigma_d + .. + sigma_{depth-1}),   oz_mcts_last_value reports minus what edge 0 got (at depth 0: -V_L).
+ * Nothing else changes: the Q update and its type rule, N, Ns, PUCT, the tie rule, the virtual loss of the leaf-parallel search, the tables,
+ * de-duplication, the caches and the random streams.  It combines with every other option; root values, value targets, recorded surprise,
+ * the resign rule and Gumbel's completed Q read what the search stores.  One mismatch stays: a drawn game is 0 here and +-1 (draw -> BLACK)
+ * in the records' z.  OZ_ERR_STATE: the tree holds nodes (a tree mixes neither rule: right after create or after oz_mcts_reset(-1) only). */
+#define OZ_VALUE_SIGNS_REFERENCE 0
+#define OZ_VALUE_SIGNS_SOUND 1
+int oz_mcts_set_value_signs(oz_mcts* m, int mode);
+int oz_mcts_get_value_signs(oz_mcts* m, int* mode);
+/* the definition on the host, no device needed: out[d] = what edge d stores, d = 0 .. depth-1 (depth <= 64; bit d of swap_bits = sigma_d, read
+ * in sound mode only); *last_value (may be NULL) = what oz_mcts_last_value reports.  leaf_value = V_L above in BOTH modes: the reference's
+ * -v / -reward at the leaf is part of its rule. */
+int oz_search_backup_values(int mode, uint64_t swap_bits, int depth, double leaf_value, double* out, double* last_value);
+/* V_L of a finished board for `own`, the side the descent leaves to move: sound sign(discs own - discs opp); reference +1 unless own has fewer
+ * discs, -1 then (MCTS/__init__.py:39-40 returns its negation) */
+int oz_search_terminal_value(int mode, uint64_t own, uint64_t opp, int* value);
+
 /* ---- root noise: Dirichlet noise on the root prior, AlphaZero's exploration inside the search (opt-in; off, every result stays bit for bit)
  * P'(root, a) = (1 - eps) P(root, a) + eps eta_a, eta ~ Dir(alpha) over the root's legal moves, fresh for every searched move.
  * STORED PRIORS ARE NEVER MODIFIED: the node tables are transposition tables that persist across the moves of a game, so the noise is applied
@@ -689,6 +714,10 @@ int oz_selfplay_set_leaves_per_step(oz_selfplay* sp, int k);
 /* solved leaves of the engine's search (see oz_mcts_set_solve_leaves), for every driver; takes effect at the next step */
 int oz_selfplay_set_solve_leaves(oz_selfplay* sp, int max_empties);
 int oz_selfplay_get_solve_leaves(oz_selfplay* sp, int* max_empties, int64_t* rows_solved);
+/* value signs of the engine's search, for every driver (see oz_mcts_set_value_signs; the reference's rule, MCTS/__init__.py:39-40,68-71, is
+ * the default: sound mode differs on finished boards and across passes); OZ_ERR_STATE after the first driver call */
+int oz_selfplay_set_value_signs(oz_selfplay* sp, int mode);
+int oz_selfplay_get_value_signs(oz_selfplay* sp, int* mode);
 /* HIP-event timing of the engine's solving kernel (oz_mcts_solve_leaves_profile / _read on the engine's search) */
 int oz_selfplay_solve_leaves_profile(oz_selfplay* sp, int enable);
 int oz_selfplay_solve_leaves_profile_read(oz_selfplay* sp, double* ms_total, int64_t* launches, int reset);
@@ -955,6 +984,9 @@ int oz_arena_set_leaves_per_step(oz_arena* a, int k_black, int k_white);
  * oz_arena_set_leaves_per_step.  The read returns the rows each search has solved so far. */
 int oz_arena_set_solve_leaves(oz_arena* a, int black, int white); /* per agent, before the first run, like oz_arena_set_leaves_per_step */
 int oz_arena_get_solve_leaves(oz_arena* a, int64_t* rows_black, int64_t* rows_white);
+/* value signs of the BLACK (net_a) and WHITE (net_b) agent's search (see oz_mcts_set_value_signs; the reference's rule, MCTS/__init__.py:39-40,
+ * 68-71, is the default: sound mode differs on finished boards and across passes); per agent, before the first run */
+int oz_arena_set_value_signs(oz_arena* a, int black, int white);
 /* HIP-event timing of the two agents' tree kernels on the launch stream, slots of oz_selfplay_profile (0 select 1 leaf compaction 2 evaluator = all
  * network launches 3 expand + backup 4 move), summed over both searches; the networks' own kernels: oz_net_profile on net_a / net_b */
 int oz_arena_profile(oz_arena* a, int enable);

@@ -204,6 +204,11 @@ SIGNATURES = {
     "oz_selfplay_set_solve_leaves": [_vp, C.c_int], "oz_selfplay_get_solve_leaves": [_vp, C.POINTER(C.c_int), _i64p],
     "oz_selfplay_solve_leaves_profile": [_vp, C.c_int], "oz_selfplay_solve_leaves_profile_read": [_vp, _f64p, _i64p, C.c_int],
     "oz_arena_set_solve_leaves": [_vp, C.c_int, C.c_int], "oz_arena_get_solve_leaves": [_vp, _i64p, _i64p],
+    "oz_mcts_set_value_signs": [_vp, C.c_int], "oz_mcts_get_value_signs": [_vp, C.POINTER(C.c_int)],
+    "oz_selfplay_set_value_signs": [_vp, C.c_int], "oz_selfplay_get_value_signs": [_vp, C.POINTER(C.c_int)],
+    "oz_arena_set_value_signs": [_vp, C.c_int, C.c_int],
+    "oz_search_backup_values": [C.c_int, C.c_uint64, C.c_int, C.c_double, _f64p, _f64p],
+    "oz_search_terminal_value": [C.c_int, C.c_uint64, C.c_uint64, C.POINTER(C.c_int)],
     "oz_mcts_set_root_noise": [_vp, C.c_double, _f64p, _u8p],
     "oz_mcts_sample_root_noise": [_vp, C.c_double, C.c_double, C.c_uint64, _u64p, _i32p],
     "oz_mcts_get_root_noise": [_vp, _f64p, _u8p, _f64p],
@@ -658,6 +663,26 @@ def check_solve_leaves_pair(solve_leaves):
         return check_solve_leaves(solve_leaves[0], "solve_leaves[black]"), check_solve_leaves(solve_leaves[1], "solve_leaves[white]")
     e = check_solve_leaves(solve_leaves)
     return e, e
+
+
+VALUE_SIGNS = {"reference": 0, "sound": 1}     # OZ_VALUE_SIGNS_*
+
+
+def check_value_signs(value_signs, what="value_signs"):
+    """value_signs="reference" | "sound" of the searches (oz_mcts_set_value_signs) -> the library's mode number; ValueError otherwise"""
+    if not isinstance(value_signs, str) or value_signs not in VALUE_SIGNS:
+        raise ValueError(f"{what} must be 'reference' or 'sound' (got {value_signs!r})")
+    return VALUE_SIGNS[value_signs]
+
+
+def check_value_signs_pair(value_signs):
+    """arena_batch(value_signs=mode or (mode_black, mode_white)) -> (int, int)"""
+    if isinstance(value_signs, (tuple, list)):
+        if len(value_signs) != 2:
+            raise ValueError(f"value_signs must be one mode or (black, white) (got {value_signs!r})")
+        return check_value_signs(value_signs[0], "value_signs[black]"), check_value_signs(value_signs[1], "value_signs[white]")
+    m = check_value_signs(value_signs)
+    return m, m
 
 
 def check_endgame_targets(endgame_targets, alias_final_boards):

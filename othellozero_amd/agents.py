@@ -79,6 +79,31 @@ def rules_solve_sign(black, white, player, n, max_empties=_lib.SOLVE_MAX_EMPTIES
     return sign, solved
 
 
+def rules_backup_values(value_signs, swaps, leaf_value):
+    """oz_search_backup_values: what one backup stores, on the host (no GPU needed).  swaps = sigma_d of the descent's edges d = 0 .. depth-1, a
+    sequence of 0 / 1 (1: the sides swapped after the edge; 0: the same side moves again, a pass or the end of the game), leaf_value = the leaf's
+    value for the side to move there.  -> (values float64 (depth,), what edge d gets; last_value, what OthelloMCTS reports as the simulation's
+    value).  value_signs "reference" | "sound" (include/othellozero_amd.h, "value signs")."""
+    mode = _lib.check_value_signs(value_signs)
+    swaps = [int(bool(b)) for b in swaps]
+    depth = len(swaps)
+    if depth > 64:
+        raise ValueError(f"rules_backup_values: at most 64 levels (got {depth})")
+    bits = sum(b << d for d, b in enumerate(swaps))
+    out, last = np.zeros(max(depth, 1), np.float64), C.c_double()
+    _lib.check(_lib.load().oz_search_backup_values(mode, bits, depth, float(leaf_value), _lib.p_f64(out), C.byref(last)))
+    return out[:depth], last.value
+
+
+def rules_terminal_value(value_signs, own, opp):
+    """oz_search_terminal_value: a finished board's value for `own`, the side the descent leaves to move there (bitboards), on the host:
+    "sound" the sign of the disc difference (a draw is 0), "reference" +1 unless own has fewer discs (a draw is own's win)."""
+    mode = _lib.check_value_signs(value_signs)
+    v = C.c_int()
+    _lib.check(_lib.load().oz_search_terminal_value(mode, int(own), int(opp), C.byref(v)))
+    return v.value
+
+
 def rules_prune_counts(N, Q, P, eta, legal, Ns, c, epsilon, k):
     """oz_forced_playouts_prune, policy target pruning over a batch of root rows, on the host (no GPU needed): N int32, Q, P, eta float64
     (count, 64) by square row*8+col, legal uint64 (count,), Ns int32 (count,) = the roots' stored statistics, their noise and visits; c, epsilon =
@@ -322,15 +347,16 @@ class NeuralNetworkOthelloAgent(OthelloAgent):
     the first valid action with the largest policy entry."""
 
     def __init__(self, game, neural_network, num_simulations, degree_exploration, temperature=0,
-                 q_mode=_lib.QMODE_F64, leaves_per_step=1, solve_leaves=0):
+                 q_mode=_lib.QMODE_F64, leaves_per_step=1, solve_leaves=0, value_signs="reference"):
         solve_leaves = _lib.check_solve_leaves(solve_leaves)
+        _lib.check_value_signs(value_signs)
         super().__init__(game)
         self.neural_network, self.num_simulations, self.temperature = neural_network, num_simulations, 0
         side = game.board_size
         # an agent searches on its own turns only: about half the plies
         self.mcts = OthelloMCTS(side, neural_network, degree_exploration, q_mode=q_mode,
                                 node_cap=num_simulations * (side * side // 2) + 64, leaves_per_step=leaves_per_step,
-                                solve_leaves=solve_leaves)
+                                solve_leaves=solve_leaves, value_signs=value_signs)
 
     def play(self):
         game = self.game
@@ -360,7 +386,8 @@ def duel_between_agents(game, agent_1, agent_2):
 
 def arena_batch(net_a, net_b, board_size=8, num_games=512, num_simulations=800, degree_exploration=1.0, seed=0,
                 first_game_id=0, q_mode=_lib.QMODE_F64, node_cap=0, max_rounds=0, dedup=True, profile=False, eval_cache=False,
-                leaves_per_step=1, opponent=None, solve_leaves=0, openings=None, first_opening_id=0, opening_moves=None):
+                leaves_per_step=1, opponent=None, solve_leaves=0, openings=None, first_opening_id=0, opening_moves=None,
+                value_signs="reference"):
     """num_games games of net_a (BLACK) vs net_b (WHITE), temperature 0, max-visit ties broken by the RNG_TIE
     stream keyed (seed, game id, ply).  One of the two may be None: RandomOthelloAgent plays that colour, or with
     opponent=("minimax", depth) / ("minimax", depth, "discs" | "weighted") the fixed-depth minimax (oz_arena_set_opponent; ties between its
@@ -376,6 +403,8 @@ def arena_batch(net_a, net_b, board_size=8, num_games=512, num_simulations=800, 
     (oz_arena_set_leaves_per_step); an agent's network needs max_batch >= num_games * its k.
     solve_leaves = E or (E_black, E_white): the agent's search takes the exact win / draw / loss of a leaf with at most E empties in place of
     its network's value (oz_arena_set_solve_leaves; 0 = off); the result then carries rows_solved = (black, white).
+    value_signs = "reference" | "sound" or (black, white): the rule by which the agent's search backs its values up (oz_arena_set_value_signs;
+    OthelloMCTS, value_signs).
     openings = (plies, opening_seed): every game first plays a random opening of `plies` plies (at most 16) without any search
     (oz_arena_set_openings, rules_random_openings); game slot g plays opening first_opening_id + g whatever seed and first_game_id are, so two
     arenas given the same (openings, first_opening_id) start from the same positions.  opening_moves = (moves uint8 (num_games, 16), n_plies int32
@@ -384,6 +413,7 @@ def arena_batch(net_a, net_b, board_size=8, num_games=512, num_simulations=800, 
     than asked for where the game ended first)."""
     opening = _lib.check_openings(openings, first_opening_id, opening_moves, num_games)
     eb_, ew_ = _lib.check_solve_leaves_pair(solve_leaves)
+    vb_, vw_ = _lib.check_value_signs_pair(value_signs)
     kb, kw = (leaves_per_step, leaves_per_step) if np.isscalar(leaves_per_step) else leaves_per_step
     minimax = _lib.check_opponents(opponent, net_a is None, net_b is None)
     lib = _lib.require_gpu()
@@ -400,6 +430,8 @@ def arena_batch(net_a, net_b, board_size=8, num_games=512, num_simulations=800, 
             _lib.check(lib.oz_arena_set_leaves_per_step(h, int(kb), int(kw)))
         if not (np.isscalar(solve_leaves) and solve_leaves == 0):
             _lib.check(lib.oz_arena_set_solve_leaves(h, eb_, ew_))
+        if vb_ or vw_:
+            _lib.check(lib.oz_arena_set_value_signs(h, vb_, vw_))
         if opening is not None and opening[0] == "random":
             _lib.check(lib.oz_arena_set_openings(h, opening[1], opening[2], opening[3]))
         elif opening is not None:

@@ -395,6 +395,31 @@ __host__ __device__ inline double pairwise_sum(const double* a, int len) {
     return res;
 }
 
+// ---------------------------------------------------------------- value signs of the backup
+// (include/othellozero_amd.h, "value signs").  A descent took the edges 0 .. depth-1; bit d of `swaps` is sigma_d: 1 where the turn went to the
+// opponent after edge d (the descent swapped own and opp), 0 where the same side moves again (a pass, or the game is over).  `leaf` is the
+// leaf's value for the side to move there -- `own` as the descent leaves it: the network's v, the solved sign, or oz_terminal_value.
+//   sound:     edge d gets leaf * (-1)^(sigma_d + .. + sigma_{depth-1}): the leaf as the side that played edge d sees it.
+//   reference: edge d gets leaf * (-1)^(depth - d) (MCTS/__init__.py:68-71: one negation per level, whoever moves), and a finished board is
+//              worth +1 to `own` unless it has fewer discs (:39-40: a draw is own's win) -- so a move that ends the game in the mover's favour
+//              stores -1.  The sigma bits are not read.
+// Negations only: the values are exact in both modes.  oz_backup_last is what oz_mcts_last_value reports: minus what edge 0 got (at depth 0,
+// -leaf).  The one definition the tree kernels (descend_one / backup_one, oz_search.hip) and the host's oz_search_backup_values share.
+#define OZ_VSIGNS_REFERENCE 0
+#define OZ_VSIGNS_SOUND 1
+OZ_HD int oz_terminal_value(int mode, uint64_t own, uint64_t opp) {
+    const int a = oz_popc(own), b = oz_popc(opp);
+    if (mode == OZ_VSIGNS_SOUND) return (a > b) - (a < b);
+    return a >= b ? 1 : -1;
+}
+OZ_HD double oz_backup_value(int mode, uint64_t swaps, int depth, int d, double leaf) {
+    const int flips = mode == OZ_VSIGNS_SOUND ? oz_popc(swaps >> d) : depth - d;
+    return (flips & 1) ? -leaf : leaf;
+}
+OZ_HD double oz_backup_last(int mode, uint64_t swaps, int depth, double leaf) {
+    return -oz_backup_value(mode, depth > 0 ? swaps : 0, depth, 0, leaf);
+}
+
 // ---------------------------------------------------------------- root value and value targets
 // (include/othellozero_amd.h, "value targets").  The root value of a search: the visit-weighted mean of the root's Q, for the player to
 // move.  a[sq] = oz_root_term: (double)N * Q where N > 0, else 0 (counts are 0 off the legal set); oz_root_mean = pairwise_sum(a, 64) /

@@ -89,6 +89,10 @@ struct MctsDev {
     double noise_eps;          // the mixing weight (0: off)
     double forced_k;           // forced playouts ("forced playouts" below): the forcing constant k (0: off); needs noise, so the *_n kernels alone read it
 };
+// the frontier entries (node, edge rank): the rank is below 64; in the sound instantiations (VS, "value signs" in oz_common.h) bit 30 of .y keeps
+// sigma of the level -- the descent swapped sides after the edge.  The reference instantiations never set the bit and read .y as it is.
+#define OZ_PATH_SWAP (1 << 30)
+template <int VS> __device__ __forceinline__ int path_rank(int y) { return VS != OZ_VSIGNS_REFERENCE ? y & (OZ_PATH_SWAP - 1) : y; }
 
 // Gumbel search ("Gumbel search" below): what the *_g kernels get beside MctsDev.  An object without the option never fills or passes it.
 struct GumbelDev {
@@ -366,7 +370,8 @@ struct Descent {
 };
 // GUMBEL (the *_g kernels): gr = the slot's Gumbel view (gumbel_of_slot); on an armed root, depth 0 picks by the Gumbel rule instead of PUCT.
 struct GumbelRoot { bool armed; double g; int n0; const GumbelDev* gd; };
-template <bool NOISE, bool GUMBEL = false>
+// VS: the value signs the tree holds (oz_common.h), a template argument of every tree kernel: the default's code is the reference rule alone
+template <bool NOISE, bool GUMBEL = false, int VS = OZ_VSIGNS_REFERENCE>
 __device__ __forceinline__ Descent descend_one(const MctsDev& t, uint4* rec, int2* path, int g, int lane, uint64_t own, uint64_t opp, uint64_t legal,
                                                int& rootn, bool noisy, double eta, const InFlight fl, const GumbelRoot gr = GumbelRoot{false, 0.0, 0, nullptr}) {
     int depth = 0, status, tval = 0, err = 0, fs = -1;
@@ -375,8 +380,8 @@ __device__ __forceinline__ Descent descend_one(const MctsDev& t, uint4* rec, int
     for (;;) {
         // `legal` = the mover's legal set of the state we stand on (of the root above; below, the move that led here computed it)
         if (legal == 0 && oz_legal(opp, own, t.valid) == 0) {       // is_terminal_state, othelo_mcts.py:28-29
-            // get_state_reward: winner of the ch0 view, draw -> ch0; simulate returns -reward
-            tval = oz_popc(own) >= oz_popc(opp) ? -1 : 1;
+            // get_state_reward: winner of the ch0 view, draw -> ch0 (simulate returns -reward: the backup's reference rule); sound: the sign, a draw is 0
+            tval = oz_terminal_value(VS, own, opp);
             status = OZ_LEAF_TERMINAL;
             break;
         }
@@ -407,7 +412,7 @@ __device__ __forceinline__ Descent descend_one(const MctsDev& t, uint4* rec, int
         for (int i = 0; i < fl.n; ++i)
             if (fl.depth[i] > depth) {
                 const int2 pe = fl.path[i][depth];
-                if (pe.x == node) { ++ks; ke += pe.y == rank ? 1 : 0; }
+                if (pe.x == node) { ++ks; ke += path_rank<VS>(pe.y) == rank ? 1 : 0; }
             }
         double U = -INFINITY;
         int child = -1;
@@ -460,13 +465,14 @@ __device__ __forceinline__ Descent descend_one(const MctsDev& t, uint4* rec, int
         const double m = wave_max_f64(U);
         const int best = oz_ctz(__ballot(cand && U == m));                 // first maximum
         const int brank = oz_popc(legal & ((1ULL << best) - 1ULL));
-        if (lane == 0) path[depth] = make_int2(node, brank);
+        if constexpr (VS == OZ_VSIGNS_REFERENCE) { if (lane == 0) path[depth] = make_int2(node, brank); }
         ++depth;
         pnode = node; prank = brank;
         node = lane_get(child, best);
         oz_apply(own, opp, best);
         // swap only if the opponent can move (othelo_mcts.py:43-49); its legal set IS the next state's -- one flood per level, not two
         const uint64_t theirs = oz_legal(opp, own, t.valid);
+        if constexpr (VS != OZ_VSIGNS_REFERENCE) { if (lane == 0) path[depth - 1] = make_int2(pnode, brank | (theirs != 0 ? OZ_PATH_SWAP : 0)); }   // sigma rides along
         if (theirs != 0) { uint64_t s = own; own = opp; opp = s; legal = theirs; }
         else legal = oz_legal(own, opp, t.valid);                   // pass (or the game is over): the same side is to move again
     }
@@ -484,7 +490,7 @@ __device__ __forceinline__ GumbelRoot gumbel_of_slot(const GumbelDev& gd, int g,
     }
     return gr;
 }
-template <bool NOISE = false, bool GUMBEL = false>
+template <bool NOISE = false, bool GUMBEL = false, int VS = OZ_VSIGNS_REFERENCE>
 __device__ __forceinline__ int select_body(const MctsDev& t, TreeLds& L, int g, int lane, const GumbelDev* gd = nullptr) {
     if (!t.active[g]) {
         if (lane == 0) t.leaf_status[g] = OZ_LEAF_IDLE;
@@ -496,7 +502,7 @@ __device__ __forceinline__ int select_body(const MctsDev& t, TreeLds& L, int g, 
     int rootn = unii(t.root_node[g]);
     GumbelRoot gr{false, 0.0, 0, nullptr};
     if constexpr (GUMBEL) gr = gumbel_of_slot(*gd, g, lane);
-    const Descent e = descend_one<NOISE, GUMBEL>(t, L.rec, L.path, g, lane, own, opp, oz_legal(own, opp, t.valid), rootn, noisy, eta, InFlight{nullptr, nullptr, 0}, gr);
+    const Descent e = descend_one<NOISE, GUMBEL, VS>(t, L.rec, L.path, g, lane, own, opp, oz_legal(own, opp, t.valid), rootn, noisy, eta, InFlight{nullptr, nullptr, 0}, gr);
     __syncthreads();
     if (lane < e.depth) t.path[(size_t)g * OZ_MAX_DEPTH + lane] = L.path[lane];          // the frontier, one coalesced store
     if (lane == 0) {
@@ -510,19 +516,22 @@ __device__ __forceinline__ int select_body(const MctsDev& t, TreeLds& L, int g, 
     }
     return e.status;
 }
+template <int VS = OZ_VSIGNS_REFERENCE>
 __global__ __launch_bounds__(64) void k_select(MctsDev t) {
     __shared__ TreeLds L;
-    select_body(t, L, blockIdx.x, threadIdx.x);
+    select_body<false, false, VS>(t, L, blockIdx.x, threadIdx.x);
 }
 // (the *_n kernels: the same kernels over the NOISE = true bodies, launched by objects that have armed root noise)
+template <int VS = OZ_VSIGNS_REFERENCE>
 __global__ __launch_bounds__(64) void k_select_n(MctsDev t) {
     __shared__ TreeLds L;
-    select_body<true>(t, L, blockIdx.x, threadIdx.x);
+    select_body<true, false, VS>(t, L, blockIdx.x, threadIdx.x);
 }
 // (the *_g kernels: the same kernels over the GUMBEL = true bodies, launched by objects with the Gumbel search switched on)
+template <int VS = OZ_VSIGNS_REFERENCE>
 __global__ __launch_bounds__(64) void k_select_g(MctsDev t, GumbelDev gd) {
     __shared__ TreeLds L;
-    select_body<false, true>(t, L, blockIdx.x, threadIdx.x, &gd);
+    select_body<false, true, VS>(t, L, blockIdx.x, threadIdx.x, &gd);
 }
 
 // ---------------------------------------------------------------- K13: leaf compaction
@@ -772,23 +781,29 @@ struct LeafRef {
 };
 // backup (MCTS/__init__.py:68-71): the level-d caller sees the leaf value negated (depth-1-d) times; all levels in
 // parallel, one lane per level (a path never visits a node twice: every move adds a disc)
+// `value` = the leaf's value for the side to move there; what each level stores of it is oz_backup_value (oz_common.h) under VS: the
+// reference's one negation per level, or -- sound -- one per level at which the descent swapped sides (the sigma bits of the frontier)
+template <int VS>
 __device__ __forceinline__ void backup_one(const MctsDev& t, int g, int lane, int depth, const int2* __restrict__ path, double value, int vt) {
+    int2 pe = make_int2(0, 0);
+    if (lane < depth) pe = path[lane];
+    const uint64_t swaps = VS != OZ_VSIGNS_REFERENCE ? __ballot((pe.y & OZ_PATH_SWAP) != 0) : 0;          // (lanes at or above depth hold 0)
     if (lane < depth) {
-        const int2 pe = path[lane];
-        const double val = ((depth - 1 - lane) & 1) ? -value : value;
-        if ((unsigned)pe.x < (unsigned)t.node_cap && (unsigned)pe.y < (unsigned)t.row_cap) {
-            q_update(t, rec_edge(t, g, pe.x, pe.y), val, vt);
+        const int rank = path_rank<VS>(pe.y);
+        const double val = oz_backup_value(VS, swaps, depth, lane, value);
+        if ((unsigned)pe.x < (unsigned)t.node_cap && (unsigned)rank < (unsigned)t.row_cap) {
+            q_update(t, rec_edge(t, g, pe.x, rank), val, vt);
             *rec_Ns(t, g, pe.x) += 1;
         } else atomicOr(t.error_flag, EF_CORRUPT);
     }
     if (lane == 0) {
-        t.last_value[g] = (depth & 1) ? -value : value;
+        t.last_value[g] = oz_backup_last(VS, swaps, depth, value);
         t.last_vtype[g] = vt;
     }
 }
 // expand the leaf if it needs it, then back its value up along its path.  GUMBEL: the new node's header keeps the value the expansion backs
 // up, before negation (the network's v, or the exact one where solve_leaves replaced it) -- vhat of the completed-Q formula, in header word 3
-template <bool GUMBEL = false>
+template <bool GUMBEL = false, int VS = OZ_VSIGNS_REFERENCE>
 __device__ __forceinline__ void expand_backup_one(const MctsDev& t, TreeLds& L, int g, int lane, const LeafRef& lf) {
     const int status = lf.status;
     if (status == OZ_LEAF_IDLE || status == OZ_LEAF_WAIT) return;           // (WAIT: the leaf was not in the batch, nothing to expand yet)
@@ -833,7 +848,7 @@ __device__ __forceinline__ void expand_backup_one(const MctsDev& t, TreeLds& L, 
                 t.ht[(size_t)g * t.ht_cap + fs] = ht_entry(own, opp, node);
                 if (depth > 0) {
                     const int2 pe = lf.path[depth - 1];
-                    rec_edge(t, g, pe.x, pe.y)->child = node;
+                    rec_edge(t, g, pe.x, path_rank<VS>(pe.y))->child = node;
                 } else t.root_node[g] = node;
             }
         }
@@ -843,20 +858,21 @@ __device__ __forceinline__ void expand_backup_one(const MctsDev& t, TreeLds& L, 
             if (!(sum > 0)) st[ST_FALLBACK] += 1;
             if (!ok) atomicOr(t.error_flag, node >= t.node_cap || fs < 0 ? EF_NODES : EF_EDGES);
         }
-        value = -(double)t.v[slot];                                            // return -v (:57)
+        value = (double)t.v[slot];                                             // v for the leaf's mover (return -v, :57: the negation is the backup rule's)
         vt = t.qmode == OZ_QMODE_F64 ? VT_F64 : VT_F32;
     } else {
         value = (double)lf.tval;
         vt = VT_INT;
     }
-    backup_one(t, g, lane, lf.depth, lf.path, value, vt);
+    backup_one<VS>(t, g, lane, lf.depth, lf.path, value, vt);
 }
 // ... of the descent select_body stored in the per-game arrays.  slot_is_game != 0: pi / v are indexed by game (host evaluator path); else
 // by compacted slot.
+template <int VS>
 __device__ __forceinline__ void backup_body(const MctsDev& t, int g, int lane, double value, int vt) {
-    backup_one(t, g, lane, t.depth[g], t.path + (size_t)g * OZ_MAX_DEPTH, value, vt);
+    backup_one<VS>(t, g, lane, t.depth[g], t.path + (size_t)g * OZ_MAX_DEPTH, value, vt);
 }
-template <bool GUMBEL = false>
+template <bool GUMBEL = false, int VS = OZ_VSIGNS_REFERENCE>
 __device__ __forceinline__ void expand_backup_body(const MctsDev& t, TreeLds& L, int g, int lane, int slot_is_game) {
     LeafRef lf;
     lf.status = unii(t.leaf_status[g]);
@@ -865,38 +881,43 @@ __device__ __forceinline__ void expand_backup_body(const MctsDev& t, TreeLds& L,
     lf.fs = unii(t.leaf_fs[g]);
     lf.depth = unii(t.depth[g]); lf.tval = unii(t.term_value[g]);
     lf.path = t.path + (size_t)g * OZ_MAX_DEPTH;
-    expand_backup_one<GUMBEL>(t, L, g, lane, lf);
+    expand_backup_one<GUMBEL, VS>(t, L, g, lane, lf);
 }
+template <int VS = OZ_VSIGNS_REFERENCE>
 __global__ __launch_bounds__(64) void k_expand_backup(MctsDev t, int slot_is_game) {
     __shared__ TreeLds L;
-    expand_backup_body(t, L, blockIdx.x, threadIdx.x, slot_is_game);
+    expand_backup_body<false, VS>(t, L, blockIdx.x, threadIdx.x, slot_is_game);
 }
 // expand + backup of simulation s-1 and the descent of simulation s in ONE launch (same wave, same game): one kernel boundary
 // less per simulation step, and the records the backup has just written are re-read by the descent while still in the CU's cache
+template <int VS = OZ_VSIGNS_REFERENCE>
 __global__ __launch_bounds__(64) void k_backup_select(MctsDev t) {
     __shared__ TreeLds L;
-    expand_backup_body(t, L, blockIdx.x, threadIdx.x, 0);
+    expand_backup_body<false, VS>(t, L, blockIdx.x, threadIdx.x, 0);
     wave_sync();                                           // the wave's own stores (records, child indices, table entry, root index) before its loads
     __syncthreads();
-    select_body(t, L, blockIdx.x, threadIdx.x);
+    select_body<false, false, VS>(t, L, blockIdx.x, threadIdx.x);
 }
+template <int VS = OZ_VSIGNS_REFERENCE>
 __global__ __launch_bounds__(64) void k_backup_select_n(MctsDev t) {
     __shared__ TreeLds L;
-    expand_backup_body(t, L, blockIdx.x, threadIdx.x, 0);
+    expand_backup_body<false, VS>(t, L, blockIdx.x, threadIdx.x, 0);
     wave_sync();
     __syncthreads();
-    select_body<true>(t, L, blockIdx.x, threadIdx.x);
+    select_body<true, false, VS>(t, L, blockIdx.x, threadIdx.x);
 }
+template <int VS = OZ_VSIGNS_REFERENCE>
 __global__ __launch_bounds__(64) void k_expand_backup_g(MctsDev t, int slot_is_game) {
     __shared__ TreeLds L;
-    expand_backup_body<true>(t, L, blockIdx.x, threadIdx.x, slot_is_game);
+    expand_backup_body<true, VS>(t, L, blockIdx.x, threadIdx.x, slot_is_game);
 }
+template <int VS = OZ_VSIGNS_REFERENCE>
 __global__ __launch_bounds__(64) void k_backup_select_g(MctsDev t, GumbelDev gd) {
     __shared__ TreeLds L;
-    expand_backup_body<true>(t, L, blockIdx.x, threadIdx.x, 0);
+    expand_backup_body<true, VS>(t, L, blockIdx.x, threadIdx.x, 0);
     wave_sync();
     __syncthreads();
-    select_body<false, true>(t, L, blockIdx.x, threadIdx.x, &gd);
+    select_body<false, true, VS>(t, L, blockIdx.x, threadIdx.x, &gd);
 }
 
 
@@ -939,7 +960,7 @@ struct WideLds {
     int depth[OZ_WK], status[OZ_WK];
 };
 
-template <bool NOISE = false>
+template <bool NOISE = false, int VS = OZ_VSIGNS_REFERENCE>
 __device__ __forceinline__ void wide_select_body(const MctsDev& t, const WideDev& w, WideLds& L, int g, int lane) {
     const int left = t.active[g] ? unii(w.left[g]) : 0;
     const int nd = left < w.K ? left : w.K;
@@ -955,7 +976,7 @@ __device__ __forceinline__ void wide_select_body(const MctsDev& t, const WideDev
     int count = 0, coll = 0, leaves = 0, nterm = 0, visits = 0, err = 0;
     const size_t gb = (size_t)g * OZ_WK;
     for (int j = 0; j < nd; ++j) {
-        const Descent e = descend_one<NOISE>(t, L.t.rec, L.path[j], g, lane, rown, ropp, rlegal, rootn, noisy, eta, InFlight{L.path, L.depth, j});
+        const Descent e = descend_one<NOISE, false, VS>(t, L.t.rec, L.path[j], g, lane, rown, ropp, rlegal, rootn, noisy, eta, InFlight{L.path, L.depth, j});
         if (e.err) { err = e.err; break; }                                      // the step stops here for this game (nothing of this descent is stored)
         if (e.status == OZ_LEAF_EVAL) {
             bool same = false;
@@ -989,6 +1010,7 @@ __device__ __forceinline__ void wide_select_body(const MctsDev& t, const WideDev
 }
 
 // per game, j ascending: expand leaf j / take the terminal value, back it up along path j
+template <int VS = OZ_VSIGNS_REFERENCE>
 __device__ __forceinline__ void wide_expand_backup_body(const MctsDev& t, const WideDev& w, WideLds& L, int g, int lane) {
     const int count = unii(w.count[g]);
     if (count <= 0) return;
@@ -1007,7 +1029,7 @@ __device__ __forceinline__ void wide_expand_backup_body(const MctsDev& t, const 
             if (ht_find(t, g, lf.own, lf.opp, lane, &fs) >= 0) fs = -1;          // (cannot be in the table: the step holds a board once)
             lf.fs = fs;
         }
-        expand_backup_one(t, L.t, g, lane, lf);
+        expand_backup_one<false, VS>(t, L.t, g, lane, lf);
         wave_sync();                                                            // records, table entry, Q / N of this descent before the next one's loads
         __syncthreads();
     }
@@ -1017,32 +1039,37 @@ __device__ __forceinline__ void wide_expand_backup_body(const MctsDev& t, const 
         t.depth[g] = depth;                                                     // oz_mcts_last_value: of the last simulation backed up
     }
 }
+template <int VS = OZ_VSIGNS_REFERENCE>
 __global__ __launch_bounds__(64) void k_wide_select(MctsDev t, WideDev w) {
     __shared__ WideLds L;
-    wide_select_body(t, w, L, blockIdx.x, threadIdx.x);
+    wide_select_body<false, VS>(t, w, L, blockIdx.x, threadIdx.x);
 }
+template <int VS = OZ_VSIGNS_REFERENCE>
 __global__ __launch_bounds__(64) void k_wide_select_n(MctsDev t, WideDev w) {
     __shared__ WideLds L;
-    wide_select_body<true>(t, w, L, blockIdx.x, threadIdx.x);
+    wide_select_body<true, VS>(t, w, L, blockIdx.x, threadIdx.x);
 }
+template <int VS = OZ_VSIGNS_REFERENCE>
 __global__ __launch_bounds__(64) void k_wide_expand_backup(MctsDev t, WideDev w) {
     __shared__ WideLds L;
-    wide_expand_backup_body(t, w, L, blockIdx.x, threadIdx.x);
+    wide_expand_backup_body<VS>(t, w, L, blockIdx.x, threadIdx.x);
 }
 // expand + backup of step s-1 and the descents of step s in ONE launch (the wide counterpart of k_backup_select)
+template <int VS = OZ_VSIGNS_REFERENCE>
 __global__ __launch_bounds__(64) void k_wide_backup_select(MctsDev t, WideDev w) {
     __shared__ WideLds L;
-    wide_expand_backup_body(t, w, L, blockIdx.x, threadIdx.x);
+    wide_expand_backup_body<VS>(t, w, L, blockIdx.x, threadIdx.x);
     wave_sync();
     __syncthreads();
-    wide_select_body(t, w, L, blockIdx.x, threadIdx.x);
+    wide_select_body<false, VS>(t, w, L, blockIdx.x, threadIdx.x);
 }
+template <int VS = OZ_VSIGNS_REFERENCE>
 __global__ __launch_bounds__(64) void k_wide_backup_select_n(MctsDev t, WideDev w) {
     __shared__ WideLds L;
-    wide_expand_backup_body(t, w, L, blockIdx.x, threadIdx.x);
+    wide_expand_backup_body<VS>(t, w, L, blockIdx.x, threadIdx.x);
     wave_sync();
     __syncthreads();
-    wide_select_body<true>(t, w, L, blockIdx.x, threadIdx.x);
+    wide_select_body<true, VS>(t, w, L, blockIdx.x, threadIdx.x);
 }
 // dense batch in (game, j) order: prefix sum over the per-game leaf counts
 __global__ __launch_bounds__(1024) void k_wide_compact(MctsDev t, WideDev w) {
@@ -1166,6 +1193,8 @@ struct oz_mcts {
     float* gumbel_pi = nullptr; double* gumbel_score = nullptr;         // [G][64] each: what k_gumbel_policy wrote last
     // solved leaves (oz_mcts_set_solve_leaves): 0 = off, nothing allocated and nothing launched
     int solve_leaves = 0;
+    // value signs of the backup (oz_mcts_set_value_signs): which instantiation of the tree kernels the object launches
+    int vsigns = OZ_VSIGNS_REFERENCE;
     unsigned solve_stamp = 0;
     unsigned* solve_claim = nullptr; unsigned long long* solve_rows = nullptr;
     bool solve_profile = false;      // oz_mcts_solve_leaves_profile: HIP events around k_solve_leaves
@@ -1286,6 +1315,8 @@ static int check_error_flag(oz_mcts* m) {
     return OZ_OK;
 }
 
+// the tree kernel `K` of the object m's value signs (m in scope)
+#define OZ_VS(K) (m->vsigns != OZ_VSIGNS_REFERENCE ? K<OZ_VSIGNS_SOUND> : K<OZ_VSIGNS_REFERENCE>)
 enum { TS_SELECT = 0, TS_COMPACT = 1, TS_NN = 2, TS_BACKUP = 3, TS_MOVE = 4 };
 // the step's solved rows (k_solve_leaves): after the evaluator of EITHER kind of step has written the rows [0, cap) (and the cache has taken
 // them), before their expand + backup.  hits: the step may have rows served from the evaluation cache.  Off (the default), nothing is launched.
@@ -1389,8 +1420,8 @@ static int mcts_wide_steps(oz_mcts* m, oz_net* net, int nsims, int max_games, bo
         if (enqueued > (long long)nsims) { oz_set_error("leaf-parallel search: the simulation budget did not run out after %d steps (internal error)", nsims); return OZ_ERR_STATE; }
         for (int k = 0; k < steps; ++k) {
             timed(m, TS_SELECT, all, [&] {
-                if (k == 0) hipLaunchKernelGGL(m->noise_ever ? k_wide_select_n : k_wide_select, dim3(d.G), dim3(64), 0, s, d, w);
-                else hipLaunchKernelGGL(m->noise_ever ? k_wide_backup_select_n : k_wide_backup_select, dim3(d.G), dim3(64), 0, s, d, w);
+                if (k == 0) hipLaunchKernelGGL(m->noise_ever ? OZ_VS(k_wide_select_n) : OZ_VS(k_wide_select), dim3(d.G), dim3(64), 0, s, d, w);
+                else hipLaunchKernelGGL(m->noise_ever ? OZ_VS(k_wide_backup_select_n) : OZ_VS(k_wide_backup_select), dim3(d.G), dim3(64), 0, s, d, w);
             });
             timed(m, TS_COMPACT, all, [&] { hipLaunchKernelGGL(k_wide_compact, dim3(1), dim3(1024), 0, s, d, w); });
             const long long i = (time_eval || all) ? m->timer.begin(TS_NN, s) : -1;
@@ -1398,7 +1429,7 @@ static int mcts_wide_steps(oz_mcts* m, oz_net* net, int nsims, int max_games, bo
             m->timer.end(i, s);
             solve_leaves_async(m, cap, false);              // (no evaluation cache here: every leaf has a row of its own)
         }
-        timed(m, TS_BACKUP, all, [&] { hipLaunchKernelGGL(k_wide_expand_backup, dim3(d.G), dim3(64), 0, s, d, w); });
+        timed(m, TS_BACKUP, all, [&] { hipLaunchKernelGGL(OZ_VS(k_wide_expand_backup), dim3(d.G), dim3(64), 0, s, d, w); });
         OZ_HIP(hipGetLastError());
         int max_left = 0;
         OZ_HIP(hipMemsetAsync(w.max_left, 0, sizeof(int), s));
@@ -1430,15 +1461,15 @@ static int mcts_steps_async(oz_mcts* m, oz_net* net, int nsims, int max_games, b
     for (int k = 0; k < nsims; ++k) {
         timed(m, TS_SELECT, all, [&] {
             if (m->gumbel_ever) {
-                if (k == 0) hipLaunchKernelGGL(k_select_g, dim3(d.G), dim3(64), 0, s, d, m->gd);
-                else hipLaunchKernelGGL(k_backup_select_g, dim3(d.G), dim3(64), 0, s, d, m->gd);
-            } else if (k == 0) hipLaunchKernelGGL(m->noise_ever ? k_select_n : k_select, dim3(d.G), dim3(64), 0, s, d);
-            else hipLaunchKernelGGL(m->noise_ever ? k_backup_select_n : k_backup_select, dim3(d.G), dim3(64), 0, s, d);
+                if (k == 0) hipLaunchKernelGGL(OZ_VS(k_select_g), dim3(d.G), dim3(64), 0, s, d, m->gd);
+                else hipLaunchKernelGGL(OZ_VS(k_backup_select_g), dim3(d.G), dim3(64), 0, s, d, m->gd);
+            } else if (k == 0) hipLaunchKernelGGL(m->noise_ever ? OZ_VS(k_select_n) : OZ_VS(k_select), dim3(d.G), dim3(64), 0, s, d);
+            else hipLaunchKernelGGL(m->noise_ever ? OZ_VS(k_backup_select_n) : OZ_VS(k_backup_select), dim3(d.G), dim3(64), 0, s, d);
         });
         timed(m, TS_COMPACT, all, [&] { hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, s, d); });
         if (int rc = eval_batch_async(m, net, max_games, time_eval || all)) return rc;
     }
-    timed(m, TS_BACKUP, all, [&] { hipLaunchKernelGGL(m->gumbel_ever ? k_expand_backup_g : k_expand_backup, dim3(d.G), dim3(64), 0, s, d, 0); });
+    timed(m, TS_BACKUP, all, [&] { hipLaunchKernelGGL(m->gumbel_ever ? OZ_VS(k_expand_backup_g) : OZ_VS(k_expand_backup), dim3(d.G), dim3(64), 0, s, d, 0); });
     OZ_HIP(hipGetLastError());
     return OZ_OK;
 }
@@ -1585,6 +1616,52 @@ OZ_API int oz_mcts_solve_leaves_profile_read(oz_mcts* m, double* ms_total, int64
     if (ms_total) *ms_total = m->solve_timer.ms[0];
     if (launches) *launches = m->solve_timer.count[0];
     if (reset) m->solve_timer.reset();
+    return OZ_OK;
+}
+
+// ---- value signs: the option (a tree holds values of one rule only, so the mode changes on an empty tree alone)
+static_assert(OZ_VALUE_SIGNS_REFERENCE == OZ_VSIGNS_REFERENCE && OZ_VALUE_SIGNS_SOUND == OZ_VSIGNS_SOUND, "value signs: one numbering");
+static int value_signs_check(const char* fn, int mode) {
+    OZ_REQUIRE(mode == OZ_VALUE_SIGNS_REFERENCE || mode == OZ_VALUE_SIGNS_SOUND, "%s: unknown mode %d", fn, mode);
+    return OZ_OK;
+}
+static int value_signs_set_locked(oz_mcts* m, const char* fn, int mode) {
+    if (m->selected) { oz_set_error("%s: a step is pending (oz_mcts_select without oz_mcts_backup)", fn); return OZ_ERR_STATE; }
+    hipSetDevice(m->device);
+    std::vector<int> nodes((size_t)m->d.G);
+    OZ_HIP(hipMemcpyAsync(nodes.data(), m->d.node_count, sizeof(int) * nodes.size(), hipMemcpyDeviceToHost, m->stream));
+    OZ_HIP(hipStreamSynchronize(m->stream));
+    for (int n : nodes)
+        if (n != 0) { oz_set_error("%s: the tree holds nodes already (set the mode right after create or after oz_mcts_reset(-1))", fn); return OZ_ERR_STATE; }
+    m->vsigns = mode;
+    return OZ_OK;
+}
+OZ_API int oz_mcts_set_value_signs(oz_mcts* m, int mode) {
+    OZ_REQUIRE(m, "null mcts");
+    if (int rc = value_signs_check("oz_mcts_set_value_signs", mode)) return rc;
+    std::lock_guard<std::mutex> lk(m->mu);
+    return value_signs_set_locked(m, "oz_mcts_set_value_signs", mode);
+}
+OZ_API int oz_mcts_get_value_signs(oz_mcts* m, int* mode) {
+    OZ_REQUIRE(m && mode, "null argument");
+    std::lock_guard<std::mutex> lk(m->mu);
+    *mode = m->vsigns;
+    return OZ_OK;
+}
+// the definition on the host (oz_common.h), for tests and tools without a device
+OZ_API int oz_search_backup_values(int mode, uint64_t swap_bits, int depth, double leaf_value, double* out, double* last_value) {
+    if (int rc = value_signs_check("oz_search_backup_values", mode)) return rc;
+    OZ_REQUIRE(depth >= 0 && depth <= OZ_MAX_DEPTH, "oz_search_backup_values: depth %d outside 0 .. %d", depth, OZ_MAX_DEPTH);
+    OZ_REQUIRE(depth == 0 || out, "oz_search_backup_values: null argument");
+    if (depth < 64) swap_bits &= (1ULL << depth) - 1ULL;
+    for (int d = 0; d < depth; ++d) out[d] = oz_backup_value(mode, swap_bits, depth, d, leaf_value);
+    if (last_value) *last_value = oz_backup_last(mode, swap_bits, depth, leaf_value);
+    return OZ_OK;
+}
+OZ_API int oz_search_terminal_value(int mode, uint64_t own, uint64_t opp, int* value) {
+    if (int rc = value_signs_check("oz_search_terminal_value", mode)) return rc;
+    OZ_REQUIRE(value, "oz_search_terminal_value: null argument");
+    *value = oz_terminal_value(mode, own, opp);
     return OZ_OK;
 }
 
@@ -1753,8 +1830,8 @@ OZ_API int oz_mcts_select(oz_mcts* m) {
     OZ_REFUSE_WIDE(m, "oz_mcts_select");
     OZ_REFUSE_SOLVED(m, "oz_mcts_select");
     hipSetDevice(m->device);
-    if (m->gumbel_ever) hipLaunchKernelGGL(k_select_g, dim3(m->d.G), dim3(64), 0, m->stream, m->d, m->gd);
-    else hipLaunchKernelGGL(m->noise_ever ? k_select_n : k_select, dim3(m->d.G), dim3(64), 0, m->stream, m->d);
+    if (m->gumbel_ever) hipLaunchKernelGGL(OZ_VS(k_select_g), dim3(m->d.G), dim3(64), 0, m->stream, m->d, m->gd);
+    else hipLaunchKernelGGL(m->noise_ever ? OZ_VS(k_select_n) : OZ_VS(k_select), dim3(m->d.G), dim3(64), 0, m->stream, m->d);
     OZ_HIP(hipGetLastError());
     m->selected = true;
     return check_error_flag(m);
@@ -1784,7 +1861,7 @@ OZ_API int oz_mcts_backup(oz_mcts* m, const float* pi, const float* v) {
     const int G = m->d.G;
     OZ_HIP(hipMemcpyAsync(m->d.pi, pi, 4ull * G * m->d.n2, hipMemcpyHostToDevice, m->stream));
     OZ_HIP(hipMemcpyAsync(m->d.v, v, 4ull * G, hipMemcpyHostToDevice, m->stream));
-    hipLaunchKernelGGL(m->gumbel_ever ? k_expand_backup_g : k_expand_backup, dim3(G), dim3(64), 0, m->stream, m->d, 1);
+    hipLaunchKernelGGL(m->gumbel_ever ? OZ_VS(k_expand_backup_g) : OZ_VS(k_expand_backup), dim3(G), dim3(64), 0, m->stream, m->d, 1);
     OZ_HIP(hipGetLastError());
     m->selected = false;
     return check_error_flag(m);
@@ -2823,7 +2900,7 @@ __global__ __launch_bounds__(64) void k_sp_move_rs(GamesDev gm, MctsDev t, MoveS
 //   forced playouts: the descents force through t.forced_k, the move prunes its row while the root's noise is still armed (sp_move_body<.., FORCE>
 //   reads the flag before it clears it): a function of the root record and eta, the same rows again.
 struct SelfplayExtras { double alpha; uint64_t seed; MoveSampling sample; PlayoutCap cap; ForcedPlayouts forced; };
-template <bool EXTRAS = false, bool VALUES = EXTRAS, bool SURPRISE = false>
+template <bool EXTRAS = false, bool VALUES = EXTRAS, bool SURPRISE = false, int VS = OZ_VSIGNS_REFERENCE>
 __device__ __forceinline__ void advance_body(const GamesDev& gm, const MctsDev& t, TreeLds& L, int g, int lane, int sims, int* __restrict__ sims_done, int cap,
                                              SelfplayExtras xt = SelfplayExtras{}, SurprisePlay su = SurprisePlay{}) {
     if (unii(t.leaf_status[g]) == OZ_LEAF_WAIT) {          // batch cap: the leaf of the simulation in progress found no slot -- offer it again, unchanged
@@ -2861,10 +2938,10 @@ __device__ __forceinline__ void advance_body(const GamesDev& gm, const MctsDev& 
                 wave_sync();
             }
         }
-        status = select_body<EXTRAS>(t, L, g, lane);
+        status = select_body<EXTRAS, false, VS>(t, L, g, lane);
         if (status != OZ_LEAF_TERMINAL) break;             // EVAL: wait for the network; IDLE: error path
         wave_sync();
-        backup_body(t, g, lane, (double)t.term_value[g], VT_INT);
+        backup_body<VS>(t, g, lane, (double)t.term_value[g], VT_INT);
         ++done;
         status = OZ_LEAF_IDLE;
         if (lane == 0) t.leaf_status[g] = OZ_LEAF_IDLE;    // nothing pending if the cap ends the loop here
@@ -2872,59 +2949,67 @@ __device__ __forceinline__ void advance_body(const GamesDev& gm, const MctsDev& 
     }
     if (lane == 0) sims_done[g] = done;
 }
+template <int VS = OZ_VSIGNS_REFERENCE>
 __global__ __launch_bounds__(64) void k_advance(GamesDev gm, MctsDev t, int sims, int* __restrict__ sims_done, int cap) {
     __shared__ TreeLds L;
-    advance_body(gm, t, L, blockIdx.x, threadIdx.x, sims, sims_done, cap);
+    advance_body<false, false, false, VS>(gm, t, L, blockIdx.x, threadIdx.x, sims, sims_done, cap);
 }
 // expand + backup of the leaves the previous batch evaluated and the advance to the next batch's leaves in ONE launch (the free-running
 // counterpart of k_backup_select: one kernel boundary less per batch, the records just written are re-read from the CU's cache)
+template <int VS = OZ_VSIGNS_REFERENCE>
 __global__ __launch_bounds__(64) void k_backup_advance(GamesDev gm, MctsDev t, int sims, int* __restrict__ sims_done, int cap) {
     __shared__ TreeLds L;
-    expand_backup_body(t, L, blockIdx.x, threadIdx.x, 0);
+    expand_backup_body<false, VS>(t, L, blockIdx.x, threadIdx.x, 0);
     wave_sync();
     __syncthreads();
-    advance_body(gm, t, L, blockIdx.x, threadIdx.x, sims, sims_done, cap);
+    advance_body<false, false, false, VS>(gm, t, L, blockIdx.x, threadIdx.x, sims, sims_done, cap);
 }
 
 // (the *_x kernels: the same kernels over the EXTRAS = true bodies, launched by engines with root noise or move sampling)
+template <int VS = OZ_VSIGNS_REFERENCE>
 __global__ __launch_bounds__(64) void k_advance_x(GamesDev gm, MctsDev t, int sims, int* __restrict__ sims_done, int cap, SelfplayExtras xt) {
     __shared__ TreeLds L;
-    advance_body<true>(gm, t, L, blockIdx.x, threadIdx.x, sims, sims_done, cap, xt);
+    advance_body<true, true, false, VS>(gm, t, L, blockIdx.x, threadIdx.x, sims, sims_done, cap, xt);
 }
+template <int VS = OZ_VSIGNS_REFERENCE>
 __global__ __launch_bounds__(64) void k_backup_advance_x(GamesDev gm, MctsDev t, int sims, int* __restrict__ sims_done, int cap, SelfplayExtras xt) {
     __shared__ TreeLds L;
-    expand_backup_body(t, L, blockIdx.x, threadIdx.x, 0);
+    expand_backup_body<false, VS>(t, L, blockIdx.x, threadIdx.x, 0);
     wave_sync();
     __syncthreads();
-    advance_body<true>(gm, t, L, blockIdx.x, threadIdx.x, sims, sims_done, cap, xt);
+    advance_body<true, true, false, VS>(gm, t, L, blockIdx.x, threadIdx.x, sims, sims_done, cap, xt);
 }
 
 // (the *_xs kernels: the EXTRAS kernels whose move records its policy surprise, launched by engines with record_surprise -- with or without
 // any other extra: each is looked at when it runs)
+template <int VS = OZ_VSIGNS_REFERENCE>
 __global__ __launch_bounds__(64) void k_advance_xs(GamesDev gm, MctsDev t, int sims, int* __restrict__ sims_done, int cap, SelfplayExtras xt, SurprisePlay su) {
     __shared__ TreeLds L;
-    advance_body<true, true, true>(gm, t, L, blockIdx.x, threadIdx.x, sims, sims_done, cap, xt, su);
+    advance_body<true, true, true, VS>(gm, t, L, blockIdx.x, threadIdx.x, sims, sims_done, cap, xt, su);
 }
+template <int VS = OZ_VSIGNS_REFERENCE>
 __global__ __launch_bounds__(64) void k_backup_advance_xs(GamesDev gm, MctsDev t, int sims, int* __restrict__ sims_done, int cap, SelfplayExtras xt,
                                                           SurprisePlay su) {
     __shared__ TreeLds L;
-    expand_backup_body(t, L, blockIdx.x, threadIdx.x, 0);
+    expand_backup_body<false, VS>(t, L, blockIdx.x, threadIdx.x, 0);
     wave_sync();
     __syncthreads();
-    advance_body<true, true, true>(gm, t, L, blockIdx.x, threadIdx.x, sims, sims_done, cap, xt, su);
+    advance_body<true, true, true, VS>(gm, t, L, blockIdx.x, threadIdx.x, sims, sims_done, cap, xt, su);
 }
 
 // (the *_v kernels: the plain kernels whose move records root values, launched by engines with record_values and no other extra)
+template <int VS = OZ_VSIGNS_REFERENCE>
 __global__ __launch_bounds__(64) void k_advance_v(GamesDev gm, MctsDev t, int sims, int* __restrict__ sims_done, int cap) {
     __shared__ TreeLds L;
-    advance_body<false, true>(gm, t, L, blockIdx.x, threadIdx.x, sims, sims_done, cap);
+    advance_body<false, true, false, VS>(gm, t, L, blockIdx.x, threadIdx.x, sims, sims_done, cap);
 }
+template <int VS = OZ_VSIGNS_REFERENCE>
 __global__ __launch_bounds__(64) void k_backup_advance_v(GamesDev gm, MctsDev t, int sims, int* __restrict__ sims_done, int cap) {
     __shared__ TreeLds L;
-    expand_backup_body(t, L, blockIdx.x, threadIdx.x, 0);
+    expand_backup_body<false, VS>(t, L, blockIdx.x, threadIdx.x, 0);
     wave_sync();
     __syncthreads();
-    advance_body<false, true>(gm, t, L, blockIdx.x, threadIdx.x, sims, sims_done, cap);
+    advance_body<false, true, false, VS>(gm, t, L, blockIdx.x, threadIdx.x, sims, sims_done, cap);
 }
 
 // RandomOthelloAgent.play (agents.py:20-24) for every live game whose mover is `side`: random.choice over the valid
@@ -3251,6 +3336,20 @@ OZ_API int oz_selfplay_get_solve_leaves(oz_selfplay* sp, int* max_empties, int64
     OZ_REQUIRE(sp, "null selfplay");
     std::lock_guard<std::mutex> lk(sp->mu);
     return oz_mcts_get_solve_leaves(sp->m, max_empties, rows_solved);
+}
+// value signs of the engine's search (see oz_mcts_set_value_signs), for every driver; before the first driver call
+OZ_API int oz_selfplay_set_value_signs(oz_selfplay* sp, int mode) {
+    OZ_REQUIRE(sp, "null selfplay");
+    if (int rc = value_signs_check("oz_selfplay_set_value_signs", mode)) return rc;
+    std::lock_guard<std::mutex> lk(sp->mu);
+    if (sp->mode != 0) { oz_set_error("oz_selfplay_set_value_signs: the engine has been driven already (set it before the first driver call)"); return OZ_ERR_STATE; }
+    std::lock_guard<std::mutex> lkm(sp->m->mu);
+    return value_signs_set_locked(sp->m, "oz_selfplay_set_value_signs", mode);
+}
+OZ_API int oz_selfplay_get_value_signs(oz_selfplay* sp, int* mode) {
+    OZ_REQUIRE(sp, "null selfplay");
+    std::lock_guard<std::mutex> lk(sp->mu);
+    return oz_mcts_get_value_signs(sp->m, mode);
 }
 // HIP-event timing of the engine's k_solve_leaves launches (oz_mcts_solve_leaves_profile on the engine's search)
 OZ_API int oz_selfplay_solve_leaves_profile(oz_selfplay* sp, int enable) {
@@ -3590,17 +3689,17 @@ OZ_API int oz_selfplay_run_steps(oz_selfplay* sp, int steps) {
         timed(m, TS_SELECT, all, [&] {
             if (sp->su.log) {
                 const SelfplayExtras xt{sp->noise_alpha, sp->gm.seed, sp->sample, sp->cap, sp->forced};
-                if (fuse && i > 0) hipLaunchKernelGGL(k_backup_advance_xs, dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap, xt, sp->su);
-                else hipLaunchKernelGGL(k_advance_xs, dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap, xt, sp->su);
+                if (fuse && i > 0) hipLaunchKernelGGL(OZ_VS(k_backup_advance_xs), dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap, xt, sp->su);
+                else hipLaunchKernelGGL(OZ_VS(k_advance_xs), dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap, xt, sp->su);
             } else if (m->noise_ever || sp->sample.plies > 0 || sp->cap.fast_sims > 0) {
                 const SelfplayExtras xt{sp->noise_alpha, sp->gm.seed, sp->sample, sp->cap, sp->forced};
-                if (fuse && i > 0) hipLaunchKernelGGL(k_backup_advance_x, dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap, xt);
-                else hipLaunchKernelGGL(k_advance_x, dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap, xt);
+                if (fuse && i > 0) hipLaunchKernelGGL(OZ_VS(k_backup_advance_x), dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap, xt);
+                else hipLaunchKernelGGL(OZ_VS(k_advance_x), dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap, xt);
             } else if (sp->gm.log_values) {
-                if (fuse && i > 0) hipLaunchKernelGGL(k_backup_advance_v, dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap);
-                else hipLaunchKernelGGL(k_advance_v, dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap);
-            } else if (fuse && i > 0) hipLaunchKernelGGL(k_backup_advance, dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap);
-            else hipLaunchKernelGGL(k_advance, dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap);
+                if (fuse && i > 0) hipLaunchKernelGGL(OZ_VS(k_backup_advance_v), dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap);
+                else hipLaunchKernelGGL(OZ_VS(k_advance_v), dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap);
+            } else if (fuse && i > 0) hipLaunchKernelGGL(OZ_VS(k_backup_advance), dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap);
+            else hipLaunchKernelGGL(OZ_VS(k_advance), dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap);
         });
         MctsDev dc = d;                                    // this batch's cap and slot order (the kernels take the struct by value)
         const int cap = sp->batch_cap > 0 && sp->batch_cap < d.G ? sp->batch_cap : 0;
@@ -3610,7 +3709,7 @@ OZ_API int oz_selfplay_run_steps(oz_selfplay* sp, int steps) {
         timed(m, TS_COMPACT, all, [&] { hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, s, dc); });
         // (the network's launches are sized for the cap: it picks its tile shapes from the batch it is asked to hold)
         if (int rc = eval_batch_async(m, sp->net, cap ? cap : d.G, true)) return rc;
-        if (!fuse || i == steps - 1) timed(m, TS_BACKUP, all, [&] { hipLaunchKernelGGL(k_expand_backup, dim3(d.G), dim3(64), 0, s, d, 0); });
+        if (!fuse || i == steps - 1) timed(m, TS_BACKUP, all, [&] { hipLaunchKernelGGL(OZ_VS(k_expand_backup), dim3(d.G), dim3(64), 0, s, d, 0); });
         OZ_HIP(hipGetLastError());
         if (m->timer.backlog() > 4096) m->timer.drain();      // completed pairs only: never a host stall inside the enqueue loop
     }
@@ -4412,6 +4511,16 @@ OZ_API int oz_arena_set_solve_leaves(oz_arena* a, int black, int white) {
     if (a->started) { oz_set_error("oz_arena_set_solve_leaves: the arena has run already (set it before the first run)"); return OZ_ERR_STATE; }
     if (int rc = solve_leaves_set_locked(a->games.m, black)) return rc;
     return solve_leaves_set_locked(a->mb, white);
+}
+// value signs per agent (black for net_a's search, white for net_b's); before the first run
+OZ_API int oz_arena_set_value_signs(oz_arena* a, int black, int white) {
+    OZ_REQUIRE(a, "null arena");
+    if (int rc = value_signs_check("oz_arena_set_value_signs", black)) return rc;
+    if (int rc = value_signs_check("oz_arena_set_value_signs", white)) return rc;
+    std::lock_guard<std::mutex> lk(a->mu);
+    if (a->started) { oz_set_error("oz_arena_set_value_signs: the arena has run already (set it before the first run)"); return OZ_ERR_STATE; }
+    if (int rc = value_signs_set_locked(a->games.m, "oz_arena_set_value_signs", black)) return rc;
+    return value_signs_set_locked(a->mb, "oz_arena_set_value_signs", white);
 }
 OZ_API int oz_arena_get_solve_leaves(oz_arena* a, int64_t* rows_black, int64_t* rows_white) {
     OZ_REQUIRE(a && rows_black && rows_white, "null argument");

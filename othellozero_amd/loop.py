@@ -173,18 +173,20 @@ def evaluate_against_random(board_size, neural_network, games, num_simulations, 
 
 
 def evaluate_against_random_batch(board_size, neural_network, games, num_simulations, degree_exploration, seed=0, leaves_per_step=1,
-                                  opponent=None, solve_leaves=0, openings=None):
+                                  opponent=None, solve_leaves=0, openings=None, value_signs="reference"):
     """The same evaluation as `evaluate_against_random` played in lock step on the GPU (agents.arena_batch with a random
     mover): the network takes BLACK in the first games // 2 + games % 2 games and WHITE in the rest (the reference draws the
     colours with random.shuffle; the split here is fixed).  opponent: arena_batch's (None / "random", or ("minimax", depth[, evaluation])).
     solve_leaves=E > 0: the network's search takes exact values for leaves with at most E empties (arena_batch).
+    value_signs="sound": the network's search backs its values up with the signs right across passes and finished boards (arena_batch).
     openings=(plies, opening_seed): every game starts with a random opening (arena_batch); game k of the BLACK half and game k of the WHITE half
     play opening k, so the network meets every opening from both sides (with an odd `games` the BLACK half has one opening more).
     -> dict(wins, black_wins, black_games, white_wins, white_games)"""
     _lib.check_opponent(opponent)
     solve_leaves = _lib.check_solve_leaves(solve_leaves)
+    _lib.check_value_signs(value_signs)
     _lib.check_openings(openings)
-    opening_kw = {"openings": openings, "first_opening_id": 0} if openings is not None else {}
+    opening_kw = dict({"openings": openings, "first_opening_id": 0} if openings is not None else {}, **({"value_signs": value_signs} if value_signs != "reference" else {}))
     as_black, as_white = games // 2 + games % 2, games // 2
     r = dict(wins=0, black_wins=0, black_games=0, white_wins=0, white_games=0)
     if as_black:
@@ -208,12 +210,13 @@ def evaluate_against_opponent(board_size, neural_network, games, num_simulations
 
 
 def evaluate_against_opponent_batch(board_size, neural_network, games, num_simulations, degree_exploration, opponent, seed=0, leaves_per_step=1,
-                                    solve_leaves=0, openings=None):
+                                    solve_leaves=0, openings=None, value_signs="reference"):
     """`evaluate_against_random_batch` under the name that says what it does when the opponent is not the random agent"""
     solve_leaves = _lib.check_solve_leaves(solve_leaves)
+    _lib.check_value_signs(value_signs)
     return evaluate_against_random_batch(board_size, neural_network, games, num_simulations, degree_exploration, seed=seed,
                                          leaves_per_step=leaves_per_step, opponent=opponent, **({"solve_leaves": solve_leaves} if solve_leaves else {}),
-                                         **({"openings": openings} if openings is not None else {}))
+                                         **({"openings": openings} if openings is not None else {}), **({"value_signs": value_signs} if value_signs != "reference" else {}))
 
 
 def _discs(boards):
@@ -247,18 +250,20 @@ def pair_statistics(new_black_final_black, new_black_final_white, old_black_fina
 
 
 def paired_match(board_size, neural_network, old_neural_network, pairs, num_simulations, degree_exploration, openings, seed=0, leaves_per_step=1,
-                 solve_leaves=0):
+                 solve_leaves=0, value_signs="reference"):
     """A match over an opening suite, every opening played twice with the colours swapped -- NOT the reference's match (main.py:110-134 starts
     every game from the standard position).  Two arenas of `pairs` games: the new network as BLACK against the old one, then the old one as
     BLACK against the new; both get openings=(plies, opening_seed) and first_opening_id=0, so game i of either starts with opening i.  Game ids
     are 0 .. pairs - 1 and pairs .. 2 pairs - 1, as in self_play_match.  -> pair_statistics' dict, plus games = the two arena_batch results."""
     solve_leaves = _lib.check_solve_leaves(solve_leaves)
+    _lib.check_value_signs(value_signs)
     if openings is None:
         raise ValueError("paired_match needs openings=(plies, opening_seed): without them every pair is the same two games")
     _lib.check_openings(openings)
     if isinstance(pairs, bool) or not isinstance(pairs, (int, np.integer)) or pairs < 1:
         raise ValueError(f"paired_match: pairs must be a whole number >= 1 (got {pairs!r})")
-    kw = dict(leaves_per_step=leaves_per_step, openings=openings, first_opening_id=0, **({"solve_leaves": solve_leaves} if solve_leaves else {}))
+    kw = dict(leaves_per_step=leaves_per_step, openings=openings, first_opening_id=0, **({"solve_leaves": solve_leaves} if solve_leaves else {}),
+              **({"value_signs": value_signs} if value_signs != "reference" else {}))
     a = arena_batch(neural_network, old_neural_network, board_size, int(pairs), num_simulations, degree_exploration, seed=seed, **kw)
     b = arena_batch(old_neural_network, neural_network, board_size, int(pairs), num_simulations, degree_exploration, seed=seed,
                     first_game_id=int(pairs), **kw)
@@ -267,31 +272,34 @@ def paired_match(board_size, neural_network, old_neural_network, pairs, num_simu
 
 
 def self_play_match(board_size, neural_network, old_neural_network, total_games, num_simulations, degree_exploration, seed=0,
-                    leaves_per_step=1, solve_leaves=0, openings=None):
+                    leaves_per_step=1, solve_leaves=0, openings=None, value_signs="reference"):
     """main.py:110-134: total_games // 2 games with the new network as BLACK, the rest with it as WHITE.
     -> number of games the new network won (a drawn game goes to BLACK, like get_winning_player).
     solve_leaves=E > 0: both networks' searches take exact values for leaves with at most E empties (arena_batch).
+    value_signs="sound": both networks' searches back their values up with the signs right across passes and finished boards (arena_batch).
     openings=(plies, opening_seed): paired_match over total_games // 2 openings instead (total_games must be even: a pair is two games); the
     return value is its `wins`, counted by the same rule, and self_play_match.stats holds its dict (None after a match without openings)."""
     solve_leaves = _lib.check_solve_leaves(solve_leaves)
+    _lib.check_value_signs(value_signs)
     self_play_match.stats = None
     if openings is not None:
         _lib.check_openings(openings)
         if total_games % 2 or total_games < 2:
             raise ValueError(f"self_play_match with openings plays pairs of games: total_games must be even and >= 2 (got {total_games})")
         stats = paired_match(board_size, neural_network, old_neural_network, total_games // 2, num_simulations, degree_exploration, openings,
-                             seed=seed, leaves_per_step=leaves_per_step, solve_leaves=solve_leaves)
+                             seed=seed, leaves_per_step=leaves_per_step, solve_leaves=solve_leaves, **({"value_signs": value_signs} if value_signs != "reference" else {}))
         self_play_match.stats = {k: v for k, v in stats.items() if k != "games"}
         return stats["wins"]
     as_black, as_white = total_games // 2, total_games // 2 + total_games % 2
     wins = 0
     if as_black:
         res = arena_batch(neural_network, old_neural_network, board_size, as_black, num_simulations, degree_exploration, seed=seed,
-                          leaves_per_step=leaves_per_step, **({"solve_leaves": solve_leaves} if solve_leaves else {}))
+                          leaves_per_step=leaves_per_step, **({"solve_leaves": solve_leaves} if solve_leaves else {}), **({"value_signs": value_signs} if value_signs != "reference" else {}))
         wins += int((res["winner"] == 1).sum())
     if as_white:
         res = arena_batch(old_neural_network, neural_network, board_size, as_white, num_simulations, degree_exploration,
-                          seed=seed, first_game_id=as_black, leaves_per_step=leaves_per_step, **({"solve_leaves": solve_leaves} if solve_leaves else {}))
+                          seed=seed, first_game_id=as_black, leaves_per_step=leaves_per_step, **({"solve_leaves": solve_leaves} if solve_leaves else {}),
+                          **({"value_signs": value_signs} if value_signs != "reference" else {}))
         wins += int((res["winner"] == -1).sum())
     return wins
 
@@ -299,7 +307,7 @@ def self_play_match(board_size, neural_network, old_neural_network, total_games,
 def _selfplay_into_replay(replay, neural_network, board_size, num_episodes, num_simulations, degree_exploration, temperature, e_greedy, seed,
                           first_game_id, q_mode, visits, leaves_per_step, root_noise, sample_moves, alias_final_boards, policy_target,
                           target_temperature, endgame_targets=0, solve_leaves=0, playout_cap=None, forced_playouts=0.0, value_target="outcome",
-                          gumbel=None, surprise_weight=None, resign=None):
+                          gumbel=None, surprise_weight=None, resign=None, value_signs="reference"):
     """one iteration's games on the engine selfplay_batch would create, played to the end without reading a record, and their examples
     appended to the device buffer; -> (records appended, the endgame solver's statistics or None).  One-channel (BaseNN) examples are never
     aliased (examples_from_records).  endgame_targets > 0: SelfPlayEngine.solve_records before the append.  playout_cap: the engine's; the
@@ -317,7 +325,7 @@ def _selfplay_into_replay(replay, neural_network, board_size, num_episodes, num_
                          sample_moves=sample_moves, solve_leaves=solve_leaves, **({"playout_cap": playout_cap} if playout_cap is not None else {}),
                          **({"forced_playouts": forced_playouts} if forced_playouts else {}), **({"record_values": True} if vt_on else {}),
                          **({"gumbel": gumbel} if gumbel is not None else {}), **({"record_surprise": True} if surprise_weight is not None else {}),
-                         **({"resign": resign} if resign is not None else {}))
+                         **({"resign": resign} if resign is not None else {}), **({"value_signs": value_signs} if value_signs != "reference" else {}))
     for _ in range(board_size * board_size):
         eng.run(4)
         if eng.stats()["live_games"] == 0:
@@ -387,7 +395,7 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
              distributed=False, batched_evaluation=False, policy_target="onehot", target_temperature=1.0, leaves_per_step=1,
              root_noise=None, sample_moves=None, replay="host", evaluation_opponent="random", endgame_targets=0,
              solve_leaves=0, match_openings=None, evaluation_openings=None, playout_cap=None, forced_playouts=None, eval_symmetry=None,
-             value_target="outcome", gumbel=None, surprise_weight=None, resign=None, validation_share=None):
+             value_target="outcome", gumbel=None, surprise_weight=None, resign=None, validation_share=None, value_signs="reference"):
     """main.py:56-259 on the GPU engines; returns `historic` = [(episodes done, win rate vs random), ...]
 
     validation_share=f in (0, 0.5] (None = off, the default: the loop is unchanged): held-out evaluation of every iteration's fit.  After an
@@ -481,6 +489,13 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
     Use 6: on an MI355X at 4 096 games of 8x8 the solving kernel then takes 0.11 ms of a 3.8 ms network batch (174 leaves solved per batch), inside
     the run-to-run spread of the search without it; 8 costs 0.53 ms (a fifth more per batch), 10 costs 5.2 ms and more than doubles the batch
     (DESIGN.md, "Solved leaves"; tools/solve_leaves_bench.py, profiles/solve_leaves_bench.json).
+
+    value_signs="sound" ("reference" = off, the default): every search of the batched engines -- self-play, matches and batched evaluation --
+    backs its values up with the signs right across passes and finished boards: one negation per change of the side to move instead of one per
+    level, and a finished board worth the sign of its disc difference to the side to move there, a draw 0.  The reference's rule stores -1 for
+    a move that wins the game on the spot and flips every value that crosses a pass; the visit counts, root values, value
+    targets, surprise and the resign rule all read those numbers.  Combines with every other option.  A drawn game stays +-1 in the records'
+    z.  The drop-in evaluation agents stay without it ("Value signs"; tools/value_signs_bench.py).
 
     match_openings=(plies, opening_seed) / evaluation_openings=(plies, opening_seed) (None = off, the default): the games of the new-vs-old
     match / of the batched evaluation start with random openings of `plies` plies instead of the one standard position, every opening played
@@ -582,6 +597,8 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
         raise ValueError(f"match_openings plays pairs of games: self_play_total_games must be even and >= 2 (got {self_play_total_games})")
     training.match_history = []
     solve_leaves = _lib.check_solve_leaves(solve_leaves)
+    _lib.check_value_signs(value_signs)
+    vs_kw = {"value_signs": value_signs} if value_signs != "reference" else {}
     training.rows_solved = 0
     endgame_targets = _lib.check_endgame_targets(endgame_targets, alias_final_boards)
     training.endgame_history = []
@@ -667,7 +684,7 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
                                                       degree_exploration, temperature, e_greedy, seed, total_episodes_done, q_mode, visits,
                                                       leaves_per_step, root_noise, sample_moves, alias_final_boards, policy_target,
                                                       target_temperature, endgame_targets, solve_leaves, playout_cap, forced_playouts, **vt_kw,
-                                                      **gumbel_kw, **resign_kw,
+                                                      **gumbel_kw, **resign_kw, **vs_kw,
                                                       **({"surprise_weight": (surprise_weight, seed + i)} if surprise_weight is not None else {}))
             if resign is not None:
                 training.resign_history.append(training.resign_stats)
@@ -694,7 +711,7 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
                 eng = SelfPlayEngine(neural_network, board_size, count, num_simulations, degree_exploration, temperature, e_greedy,
                                      seed=seed, first_game_id=total_episodes_done + first, q_mode=q_mode, record_visits=visits,
                                      leaves_per_step=leaves_per_step, root_noise=root_noise, sample_moves=sample_moves,
-                                     solve_leaves=solve_leaves, **cap_kw, **({"record_values": True} if vt_on else {}), **resign_kw)
+                                     solve_leaves=solve_leaves, **cap_kw, **({"record_values": True} if vt_on else {}), **resign_kw, **vs_kw)
                 eng.play_to_end(endgame_targets=endgame_targets, **vt_kw)               # each rank relabels its own records (and computes its targets)
                 training.rows_solved += eng.rows_solved() if solve_leaves else 0
                 resign_stats = eng.resign_stats() if resign is not None else None
@@ -708,7 +725,7 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
                                          seed=seed, first_game_id=total_episodes_done, q_mode=q_mode, record_visits=visits,
                                          leaves_per_step=leaves_per_step, root_noise=root_noise, sample_moves=sample_moves,
                                          **({"endgame_targets": endgame_targets} if endgame_targets else {}), **({"solve_leaves": solve_leaves} if solve_leaves else {}),
-                                         **cap_kw, **vt_kw, **gumbel_kw, **resign_kw)
+                                         **cap_kw, **vt_kw, **gumbel_kw, **resign_kw, **vs_kw)
                 training.rows_solved += selfplay_batch.rows_solved if solve_leaves else 0
                 resign_stats = selfplay_batch.resign_stats if resign is not None else None
                 endgame = getattr(selfplay_batch, "endgame_stats", None) if endgame_targets else None
@@ -746,7 +763,7 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
             logging.info('[%d/%d] arena: trained network against the previous one', i, num_iterations)
             new_net_victories = self_play_match(board_size, neural_network, old_neural_network, self_play_total_games,
                                                 num_simulations, degree_exploration, seed=seed + i, leaves_per_step=leaves_per_step,
-                                                **({"solve_leaves": solve_leaves} if solve_leaves else {}),
+                                                **({"solve_leaves": solve_leaves} if solve_leaves else {}), **vs_kw,
                                                 **({"openings": match_openings} if match_openings is not None else {}))
             if match_openings is not None:
                 stats = self_play_match.stats
@@ -771,11 +788,11 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
             if batched_evaluation:
                 new = evaluate_against_random_batch(board_size, neural_network, evaluation_iterations, num_simulations,
                                                     degree_exploration, seed=seed + 7919 * i, leaves_per_step=leaves_per_step,
-                                                    opponent=evaluation_opponent, **({"solve_leaves": solve_leaves} if solve_leaves else {}),
+                                                    opponent=evaluation_opponent, **({"solve_leaves": solve_leaves} if solve_leaves else {}), **vs_kw,
                                                     **({"openings": evaluation_openings} if evaluation_openings is not None else {}))
                 old = evaluate_against_random_batch(board_size, old_neural_network, evaluation_iterations, num_simulations,
                                                     degree_exploration, seed=seed + 7919 * i + 1, leaves_per_step=leaves_per_step,
-                                                    opponent=evaluation_opponent, **({"solve_leaves": solve_leaves} if solve_leaves else {}),
+                                                    opponent=evaluation_opponent, **({"solve_leaves": solve_leaves} if solve_leaves else {}), **vs_kw,
                                                     **({"openings": evaluation_openings} if evaluation_openings is not None else {}))
             else:
                 new = evaluate_against_random(board_size, neural_network, evaluation_iterations, num_simulations, degree_exploration,

@@ -18,7 +18,7 @@ from .Othello import OthelloGame, OthelloPlayer
 
 class OthelloMCTS:
     def __init__(self, board_size, neural_network, degree_exploration, q_mode=_lib.QMODE_F64,
-                 node_cap=8192, leaves_per_step=1, solve_leaves=0, forced_playouts=None, gumbel=None):
+                 node_cap=8192, leaves_per_step=1, solve_leaves=0, forced_playouts=None, gumbel=None, value_signs="reference"):
         """q_mode: OZ_QMODE_F64 = the NumPy 1.18.5 promotion the reference pins (requirements.txt:19),
         OZ_QMODE_NEP50 = what NumPy >= 2 computes (SURVEY.md R-FP).
         leaves_per_step > 1 (native networks only, created with max_batch >= leaves_per_step): that many descents of the tree per
@@ -31,7 +31,13 @@ class OthelloMCTS:
         gumbel=(max_considered, c_visit, c_scale) or True: the search keeps every node's own value and is ready for the Gumbel root rule
         (include/othellozero_amd.h, "Gumbel search"): sample_gumbel / set_gumbel arm a root before its simulations, gumbel_policy gives the
         move and the improved policy afterwards.  It replaces root noise, forced playouts and move sampling; not with leaves_per_step > 1.
-        Not the reference's search."""
+        Not the reference's search.
+        value_signs="sound": the backup negates a value once per change of the side to move, not once per level, and a finished board is worth
+        the sign of its disc difference to the side to move there, a draw 0 (oz_mcts_set_value_signs; include/othellozero_amd.h, "value
+        signs").  "reference" (the default) is the reference's rule, which stores the wrong sign for a move that ends the game and across every
+        pass.  Not the reference's search."""
+        self.value_signs = value_signs
+        vs_mode = _lib.check_value_signs(value_signs)
         self.gumbel = _lib.check_gumbel_options(gumbel, forced_playouts=forced_playouts, leaves_per_step=leaves_per_step)
         self.forced_playouts = _lib.check_forced_playouts(forced_playouts, need_noise=False)
         self._forced_set = False
@@ -55,6 +61,8 @@ class OthelloMCTS:
         lib = _lib.require_gpu()
         _lib.check(lib.oz_mcts_create(C.byref(self._h), board_size, 1, node_cap, float(degree_exploration), q_mode))
         self._root = None
+        if vs_mode:
+            _lib.check(lib.oz_mcts_set_value_signs(self._h, vs_mode))
         if self.leaves_per_step != 1:
             _lib.check(lib.oz_mcts_set_leaves_per_step(self._h, self.leaves_per_step))
         if self.solve_leaves:

@@ -33,7 +33,7 @@ def training_example_symmetries(board, policy):
 def execute_episode(board_size, neural_network, degree_exploration, num_simulations, policy_temperature, e_greedy,
                     q_mode=_lib.QMODE_F64, snapshot_boards=False, policy_target="onehot", target_temperature=1.0,
                     leaves_per_step=1, root_noise=None, noise_seed=0, sample_moves=None, sample_seed=0, solve_leaves=0,
-                    forced_playouts=None, value_target="outcome", gumbel=None, gumbel_seed=0):
+                    forced_playouts=None, value_target="outcome", gumbel=None, gumbel_seed=0, value_signs="reference"):
     """training.py:26-72.  Returns [(board (n,n,2) bool, one-hot policy (n,n) float64, z int), ...], 8 per move.
 
     gumbel=(max_considered, c_visit, c_scale) or True: every move's search is a Gumbel root search of num_simulations simulations
@@ -67,7 +67,11 @@ def execute_episode(board_size, neural_network, degree_exploration, num_simulati
 
     value_target=("blend", w) / ("td", lam): every move's root value (OthelloMCTS.root_value) is recorded and z is the float value target of the
     move (agents.rules_value_targets) instead of the int outcome; needs snapshot_boards=True (a search value belongs to the position of its
-    move).  "outcome" is the function without it."""
+    move).  "outcome" is the function without it.
+
+    value_signs="sound": the search backs its values up with the signs right across passes and finished boards (OthelloMCTS); "reference" is
+    the function without it."""
+    _lib.check_value_signs(value_signs)
     vt_mode, _ = _lib.check_value_target(value_target, not snapshot_boards)
     root_values, movers, positions = [], [], []
     solve_leaves = _lib.check_solve_leaves(solve_leaves)
@@ -87,7 +91,8 @@ def execute_episode(board_size, neural_network, degree_exploration, num_simulati
     game = OthelloGame(board_size)
     mcts = OthelloMCTS(board_size, neural_network, degree_exploration, q_mode=q_mode,
                        node_cap=num_simulations * (board_size * board_size - 3) + 64, leaves_per_step=leaves_per_step,
-                       solve_leaves=solve_leaves, forced_playouts=forced_playouts, **({"gumbel": gumbel} if gumbel is not None else {}))
+                       solve_leaves=solve_leaves, forced_playouts=forced_playouts, **({"gumbel": gumbel} if gumbel is not None else {}),
+                       **({"value_signs": value_signs} if value_signs != "reference" else {}))
     # training.py:34-37 (BNN examples are one-channel boards, a fresh array per round: no aliasing for them)
     board_view_type = BoardView.ONE_CHANNEL if getattr(neural_network.network_type, "name", "") == "BNN" else BoardView.TWO_CHANNELS
 
@@ -188,7 +193,7 @@ class SelfPlayEngine:
                  policy_temperature=1.0, e_greedy=0.9, seed=1234, first_game_id=0, game_id_stride=0,
                  q_mode=_lib.QMODE_F64, refill=False, node_cap=0, record_cap=0, dedup=True, batch_cap=0, eval_cache=False,
                  record_visits=False, leaves_per_step=1, root_noise=None, sample_moves=None, solve_leaves=0, playout_cap=None,
-                 forced_playouts=None, record_values=False, gumbel=None, record_surprise=False, resign=None):
+                 forced_playouts=None, record_values=False, gumbel=None, record_surprise=False, resign=None, value_signs="reference"):
         """dedup: cross-game leaf de-duplication (a board several games reach in one batch is evaluated once; no record changes);
         batch_cap: leaves per network batch of the free-running driver (0 = none; see preferred_batch_cap);
         eval_cache: take (pi, v) of boards the network has evaluated before from its persistent cache (NNetWrapper.set_eval_cache) --
@@ -242,7 +247,13 @@ class SelfPlayEngine:
         rule triggered in them and how often it was wrong.  The record consumers take an adjudicated record as any other (with
         alias_final=True the "final board" of such a game is the board at the stop).  run() at any leaves_per_step, with every option but
         gumbel (ValueError); run_steps() and stagger() then raise.  keep_prob = 1 plays the games of the engine without the option
-        (DESIGN.md, "Resignation")."""
+        (DESIGN.md, "Resignation").
+        value_signs="sound": every search of the engine backs its values up with the signs right across passes and finished boards -- one
+        negation per change of the side to move, a finished board worth the sign of its disc difference to the side to move there, a draw 0
+        (oz_selfplay_set_value_signs).  "reference" (the default) is the reference's rule.  Every driver and every option; the root values,
+        value targets, recorded surprise and the resign rule read what the search stores.  A drawn game stays +-1 (draw -> BLACK) in the
+        records' z (DESIGN.md, "Value signs")."""
+        vs_mode = _lib.check_value_signs(value_signs)
         resign = _lib.check_resign(resign, gumbel=gumbel)
         if record_surprise and not (record_visits or gumbel):
             raise ValueError("record_surprise needs record_visits=True or gumbel=...: the surprise is that of a recorded policy target")
@@ -265,6 +276,9 @@ class SelfPlayEngine:
         self._h = C.c_void_p()
         _lib.check(lib.oz_selfplay_create(C.byref(self._h), C.byref(self.cfg), neural_network._h))
         self.n, self.num_games = board_size, num_games
+        self.value_signs = value_signs
+        if vs_mode:
+            _lib.check(lib.oz_selfplay_set_value_signs(self._h, vs_mode))
         self.leaves_per_step = int(leaves_per_step)
         if self.leaves_per_step != 1:
             _lib.check(lib.oz_selfplay_set_leaves_per_step(self._h, self.leaves_per_step))
@@ -632,8 +646,9 @@ def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations
                    policy_temperature=1.0, e_greedy=0.9, seed=1234, first_game_id=0, q_mode=_lib.QMODE_F64,
                    expand=False, alias_final=False, record_visits=False, target_temperature=1.0, leaves_per_step=1, root_noise=None,
                    sample_moves=None, endgame_targets=0, solve_leaves=0, playout_cap=None, forced_playouts=None, value_target="outcome", gumbel=None,
-                   surprise_weight=None, resign=None):
+                   surprise_weight=None, resign=None, value_signs="reference"):
     """Play num_games complete games; returns the move records (or the expanded examples).
+    value_signs="sound": the searches back their values up with the signs right across passes and finished boards (SelfPlayEngine).
     resign=(v, r, min_ply, keep_prob): resignation with a played-out audit share (SelfPlayEngine): a decided game stops early, its records
     carry the adjudicated z, the board at the stop as their final board (what alias_final=True then shows) and the flag
     _lib.record_adjudicated reads; nothing else about what comes back changes.  Not with gumbel (ValueError).  selfplay_batch.resign_stats
@@ -663,6 +678,7 @@ def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations
     targets, exact_empties = endgame_targets).  The float32 targets come back last -- (records, [counts,] targets) -- or, with expand, as
     the examples' float32 z; with expand it needs alias_final=False.  selfplay_batch.value_target_stats holds the last call's statistics
     (None when off)."""
+    _lib.check_value_signs(value_signs)
     vt_on = _lib.check_value_target(value_target, expand and alias_final)[0] != _lib.VALUE_TARGET_OUTCOME
     gumbel = _lib.check_gumbel_options(gumbel, root_noise=root_noise, forced_playouts=forced_playouts, sample_moves=sample_moves,
                                        playout_cap=playout_cap, leaves_per_step=leaves_per_step)
@@ -689,7 +705,7 @@ def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations
                          root_noise=root_noise, sample_moves=sample_moves, solve_leaves=solve_leaves, playout_cap=playout_cap,
                          **({"forced_playouts": forced_playouts} if forced_playouts > 0.0 else {}), **({"record_values": True} if vt_on else {}),
                          **({"gumbel": gumbel} if gumbel is not None else {}), **({"record_surprise": True} if surprise_weight is not None else {}),
-                         **({"resign": resign} if resign is not None else {}))
+                         **({"resign": resign} if resign is not None else {}), **({"value_signs": value_signs} if value_signs != "reference" else {}))
     selfplay_batch.surprise_stats = None
 
     def weighted(ret):
