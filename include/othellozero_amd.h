@@ -406,6 +406,50 @@ int oz_search_backup_values(int mode, uint64_t swap_bits, int depth, double leaf
  * discs, -1 then (MCTS/__init__.py:39-40 returns its negation) */
 int oz_search_terminal_value(int mode, uint64_t own, uint64_t opp, int* value);
 
+/* ---- proofs: exact values kept as proofs and backed up the tree (opt-in, on top of OZ_VALUE_SIGNS_SOUND; off, every result stays bit for
+ * bit).  The MCTS-Solver step (Winands et al. 2008; "certainty propagation").  Values are -1 / 0 / +1 or unknown (OZ_PROOF_UNKNOWN).
+ * States: an edge (S, a) may carry a proven value e(S, a) for the side to move at S; a node may carry an own proven value (set only where it
+ *   was expanded from a solved leaf).  val(S) = the own value if set; else +1 if any legal edge has e = +1; else max e if every legal edge is
+ *   known; else unknown.
+ * Exact results of a descent (V_L = the value for the side to move where the descent ends, as in "value signs"): (1) it ends on a finished
+ *   board; (2) it stops on a proof (below); (3) the leaf is expanded while solve_leaves = E > 0 and has <= E empties: v is the exact sign, and
+ *   the new node's own value is set to it.  Every other leaf proves nothing.
+ * Descent, at the node S at level d: the finished-board check and the table lookup come first.  If d > 0 and val(S) is known the descent ends
+ *   here like a finished board with V_L = val(S), no edge of S visited (the root never stops: a move must receive visits).  Candidates: the
+ *   legal edges with e == val(S) if that is known (the root only); else, and where that set is empty, the legal edges with e != -1; none of
+ *   those either: the legal set, and the search reports a corrupt table.  U is the search's formula (in-flight view, root noise, float64 left
+ *   to right) with Q = (double)e in place of the (adjusted) Q where e is known; the first maximum among the candidates is taken.  If the taken
+ *   edge's e is known the descent ends right after the move (depth d + 1, like a finished board) with V_L = sigma_d ? -e : e; the child is
+ *   not looked up.
+ * Backup: Q / N / Ns of every level exactly as in sound mode.  Then, for an exact result, from the bottom with x = V_L, for d = depth-1 .. 0:
+ *   x = sigma_d ? -x : x; e(path[d]) = x (a known, different value reports a corrupt table); stop if val(path[d].node) is unknown, else
+ *   x = that value.  With leaves_per_step = K the K backups of a step run in their order; proofs are read in selection, written in backup.
+ * Stored Q stays the running mean and oz_mcts_root_values / oz_mcts_root_counts / the move read the raw statistics as before.  Proofs live in
+ * 32 bytes per node beside the records, persist with the tree and go with oz_mcts_reset.  Supported: oz_mcts_simulate, oz_selfplay_run,
+ * the arena, any leaves_per_step, root noise, move sampling, playout cap, solve_leaves, the recorded rows and targets, resignation.
+ * OZ_ERR_STATE: the tree holds nodes; the signs are OZ_VALUE_SIGNS_REFERENCE; the Gumbel search or forced playouts are on (and those refuse
+ * an object with proofs); oz_selfplay_run_steps and oz_selfplay_stagger refuse an engine with proofs. */
+#define OZ_PROOF_UNKNOWN (-128)
+int oz_mcts_set_proofs(oz_mcts* m, int enable);
+int oz_mcts_get_proofs(oz_mcts* m, int* enabled);
+/* node `index` of game `game` (indices as oz_mcts_dump_node): edge[64] by square (OZ_PROOF_UNKNOWN off the legal set), *node_value the own
+ * value, *node_val val(S).  OZ_ERR_STATE on an object without the option. */
+int oz_mcts_dump_proofs(oz_mcts* m, int game, int index, int8_t* edge, int8_t* node_value, int8_t* node_val);
+/* the current roots: edge [G][64], val [G], rc [G] (0, or 1 where the game is idle or its root is not in the table) */
+int oz_mcts_root_proofs(oz_mcts* m, int8_t* edge, int8_t* val, int32_t* rc);
+/* summed over the games: [0] edges proven [1] descents ended on a proven edge [2] descents ended on a proven node [3] roots whose value became
+ * known (zeros on an object without the option) */
+int oz_mcts_proof_stats(oz_mcts* m, int64_t* out4);
+/* the rule on the host, no device needed.  A node's edge proofs are two masks by square: state = 2 * hi bit + lo bit, 0 unknown, 1 loss,
+ * 2 draw, 3 win.  oz_search_proof_value: val(S).  oz_search_proof_candidates: the candidate set of a node of value node_val (pass
+ * OZ_PROOF_UNKNOWN below the root), *inconsistent = 1 where it fell back to the legal set.  oz_search_proof_backup: the loop of the backup
+ * over a path of `depth` levels (level d: the node's legal[d], lo[d], hi[d], own_value[d], the square taken and sigma[d]); lo / hi are
+ * updated in place, out3 = levels marked, edges newly proven, 1 where level 0's value became known; *conflict = 1 where a known edge differed. */
+int oz_search_proof_value(uint64_t legal, uint64_t lo, uint64_t hi, int own_value, int* value);
+int oz_search_proof_candidates(uint64_t legal, uint64_t lo, uint64_t hi, int node_val, uint64_t* candidates, int* inconsistent);
+int oz_search_proof_backup(const uint8_t* sigma, const int32_t* square, int depth, int leaf_value, const uint64_t* legal, uint64_t* lo, uint64_t* hi,
+                           const int8_t* own_value, int32_t* out3, int* conflict);
+
 /* ---- root noise: Dirichlet noise on the root prior, AlphaZero's exploration inside the search (opt-in; off, every result stays bit for bit)
  * P'(root, a) = (1 - eps) P(root, a) + eps eta_a, eta ~ Dir(alpha) over the root's legal moves, fresh for every searched move.
  * STORED PRIORS ARE NEVER MODIFIED: the node tables are transposition tables that persist across the moves of a game, so the noise is applied
@@ -718,6 +762,10 @@ int oz_selfplay_get_solve_leaves(oz_selfplay* sp, int* max_empties, int64_t* row
  * the default: sound mode differs on finished boards and across passes); OZ_ERR_STATE after the first driver call */
 int oz_selfplay_set_value_signs(oz_selfplay* sp, int mode);
 int oz_selfplay_get_value_signs(oz_selfplay* sp, int* mode);
+/* proofs of the engine's search (see oz_mcts_set_proofs; after oz_selfplay_set_value_signs(sp, OZ_VALUE_SIGNS_SOUND)), for oz_selfplay_run;
+ * OZ_ERR_STATE after the first driver call.  oz_selfplay_proof_stats: as oz_mcts_proof_stats, over the engine's games so far. */
+int oz_selfplay_set_proofs(oz_selfplay* sp, int enable);
+int oz_selfplay_proof_stats(oz_selfplay* sp, int64_t* out4);
 /* HIP-event timing of the engine's solving kernel (oz_mcts_solve_leaves_profile / _read on the engine's search) */
 int oz_selfplay_solve_leaves_profile(oz_selfplay* sp, int enable);
 int oz_selfplay_solve_leaves_profile_read(oz_selfplay* sp, double* ms_total, int64_t* launches, int reset);
@@ -987,6 +1035,9 @@ int oz_arena_get_solve_leaves(oz_arena* a, int64_t* rows_black, int64_t* rows_wh
 /* value signs of the BLACK (net_a) and WHITE (net_b) agent's search (see oz_mcts_set_value_signs; the reference's rule, MCTS/__init__.py:39-40,
  * 68-71, is the default: sound mode differs on finished boards and across passes); per agent, before the first run */
 int oz_arena_set_value_signs(oz_arena* a, int black, int white);
+/* proofs of the BLACK (net_a) and WHITE (net_b) agent's search (see oz_mcts_set_proofs; an agent with proofs needs sound signs); before the
+ * first run */
+int oz_arena_set_proofs(oz_arena* a, int black, int white);
 /* HIP-event timing of the two agents' tree kernels on the launch stream, slots of oz_selfplay_profile (0 select 1 leaf compaction 2 evaluator = all
  * network launches 3 expand + backup 4 move), summed over both searches; the networks' own kernels: oz_net_profile on net_a / net_b */
 int oz_arena_profile(oz_arena* a, int enable);

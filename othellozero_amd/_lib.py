@@ -209,6 +209,13 @@ SIGNATURES = {
     "oz_arena_set_value_signs": [_vp, C.c_int, C.c_int],
     "oz_search_backup_values": [C.c_int, C.c_uint64, C.c_int, C.c_double, _f64p, _f64p],
     "oz_search_terminal_value": [C.c_int, C.c_uint64, C.c_uint64, C.POINTER(C.c_int)],
+    "oz_mcts_set_proofs": [_vp, C.c_int], "oz_mcts_get_proofs": [_vp, C.POINTER(C.c_int)],
+    "oz_mcts_dump_proofs": [_vp, C.c_int, C.c_int, _i8p, _i8p, _i8p], "oz_mcts_root_proofs": [_vp, _i8p, _i8p, _i32p],
+    "oz_mcts_proof_stats": [_vp, _i64p], "oz_selfplay_set_proofs": [_vp, C.c_int], "oz_selfplay_proof_stats": [_vp, _i64p],
+    "oz_arena_set_proofs": [_vp, C.c_int, C.c_int],
+    "oz_search_proof_value": [C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(C.c_int)],
+    "oz_search_proof_candidates": [C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, _u64p, C.POINTER(C.c_int)],
+    "oz_search_proof_backup": [_u8p, _i32p, C.c_int, C.c_int, _u64p, _u64p, _u64p, _i8p, _i32p, C.POINTER(C.c_int)],
     "oz_mcts_set_root_noise": [_vp, C.c_double, _f64p, _u8p],
     "oz_mcts_sample_root_noise": [_vp, C.c_double, C.c_double, C.c_uint64, _u64p, _i32p],
     "oz_mcts_get_root_noise": [_vp, _f64p, _u8p, _f64p],
@@ -683,6 +690,42 @@ def check_value_signs_pair(value_signs):
         return check_value_signs(value_signs[0], "value_signs[black]"), check_value_signs(value_signs[1], "value_signs[white]")
     m = check_value_signs(value_signs)
     return m, m
+
+
+PROOF_UNKNOWN = -128                            # OZ_PROOF_UNKNOWN
+PROOF_STATS = ("edges_proven", "edge_stops", "node_stops", "roots_proven")     # oz_mcts_proof_stats
+
+
+def check_proofs(proofs, value_signs, what="proofs", gumbel=None, forced_playouts=None):
+    """proofs=True | False of the searches (oz_mcts_set_proofs) -> bool; on needs value_signs="sound" and neither the Gumbel search nor
+    forced playouts: ValueError otherwise, before the library is touched"""
+    if not isinstance(proofs, (bool, int, np.bool_)) or proofs not in (0, 1):
+        raise ValueError(f"{what} must be True or False (got {proofs!r})")
+    if proofs and value_signs != "sound":
+        raise ValueError(f"{what}=True needs value_signs='sound' (got {value_signs!r}): a proof built on the reference's finished boards is wrong")
+    if proofs and gumbel is not None:
+        raise ValueError(f"{what}=True does not combine with the Gumbel search")
+    if proofs and forced_playouts:
+        raise ValueError(f"{what}=True does not combine with forced playouts")
+    return bool(proofs)
+
+
+def check_proofs_pair(proofs, value_signs):
+    """arena_batch(proofs=flag or (black, white)) with value_signs=mode or (black, white) -> (bool, bool)"""
+    vs = tuple(value_signs) if isinstance(value_signs, (tuple, list)) else (value_signs, value_signs)
+    if isinstance(proofs, (tuple, list)):
+        if len(proofs) != 2:
+            raise ValueError(f"proofs must be one flag or (black, white) (got {proofs!r})")
+        return check_proofs(proofs[0], vs[0], "proofs[black]"), check_proofs(proofs[1], vs[1], "proofs[white]")
+    if proofs and vs[0] != vs[1]:
+        raise ValueError("proofs=True with two value_signs: give proofs=(black, white)")
+    p = check_proofs(proofs, vs[0])
+    return p, p
+
+
+def proofs_kw(proofs):
+    """the keyword to pass on: nothing where the option is off, so that callers without it see the calls they always saw"""
+    return {"proofs": proofs} if (any(proofs) if isinstance(proofs, (tuple, list)) else proofs) else {}
 
 
 def check_endgame_targets(endgame_targets, alias_final_boards):

@@ -104,6 +104,69 @@ def rules_terminal_value(value_signs, own, opp):
     return v.value
 
 
+def _proof_masks(edge):
+    """edge proofs by square (-1 / 0 / +1, anything else = unknown) -> the two masks (lo, hi) of the library's entry: state = e + 2"""
+    lo = hi = 0
+    for sq, e in enumerate(edge):
+        if int(e) in (-1, 0, 1):
+            st = int(e) + 2
+            lo |= (st & 1) << sq
+            hi |= (st >> 1) << sq
+    return lo, hi
+
+
+def _proof_in(v):
+    return _lib.PROOF_UNKNOWN if v is None else int(v)
+
+
+def _proof_out(v):
+    return None if v == _lib.PROOF_UNKNOWN else int(v)
+
+
+def rules_proof_value(legal, edge, own_value=None):
+    """oz_search_proof_value: val(S) of a node, on the host (no GPU needed).  legal = the node's legal mask, edge = 64 proofs by square
+    (-1 / 0 / +1, None or _lib.PROOF_UNKNOWN = unknown), own_value = the node's own value or None.  -> -1 / 0 / +1 or None: the own value if
+    set; else +1 if a legal edge wins; else the maximum if every legal edge is known (include/othellozero_amd.h, "proofs")."""
+    lo, hi = _proof_masks([_proof_in(e) for e in edge])
+    v = C.c_int()
+    _lib.check(_lib.load().oz_search_proof_value(int(legal), lo, hi, _proof_in(own_value), C.byref(v)))
+    return _proof_out(v.value)
+
+
+def rules_proof_candidates(legal, edge, node_val=None):
+    """oz_search_proof_candidates: the edges a descent may take at a node whose val(S) is node_val (None below the root) -> (mask,
+    inconsistent): the legal edges proven node_val; else, and where there is none, those not proven lost; none either: the legal set and
+    inconsistent = True."""
+    lo, hi = _proof_masks([_proof_in(e) for e in edge])
+    cand, bad = C.c_uint64(), C.c_int()
+    _lib.check(_lib.load().oz_search_proof_candidates(int(legal), lo, hi, _proof_in(node_val), C.byref(cand), C.byref(bad)))
+    return cand.value, bool(bad.value)
+
+
+def rules_proof_backup(path, leaf_value):
+    """oz_search_proof_backup: the proof loop of one backup.  path = one dict per level d = 0 .. depth-1 with legal (mask), edge (64 proofs
+    by square, None = unknown), own_value (or None), square (the edge taken) and sigma (0 / 1); leaf_value = V_L in -1 / 0 / +1.  -> (edges:
+    the levels' proofs after the loop, a list of 64-lists; marked = levels marked from the bottom; fresh = edges newly proven; root = level 0's
+    value became known; conflict = a known edge differed)."""
+    depth = len(path)
+    if depth > 64:
+        raise ValueError(f"rules_proof_backup: at most 64 levels (got {depth})")
+    k = max(depth, 1)
+    sigma, square = np.zeros(k, np.uint8), np.zeros(k, np.int32)
+    legal, lo, hi, own = np.zeros(k, np.uint64), np.zeros(k, np.uint64), np.zeros(k, np.uint64), np.full(k, _lib.PROOF_UNKNOWN, np.int8)
+    for d, lv in enumerate(path):
+        sigma[d], square[d], legal[d], own[d] = int(bool(lv["sigma"])), int(lv["square"]), int(lv["legal"]), _proof_in(lv.get("own_value"))
+        lo[d], hi[d] = _proof_masks([_proof_in(e) for e in lv["edge"]])
+    out3, conflict = np.zeros(3, np.int32), C.c_int()
+    _lib.check(_lib.load().oz_search_proof_backup(_lib.p_u8(sigma), _lib.p_i32(square), depth, int(leaf_value), _lib.p_u64(legal), _lib.p_u64(lo),
+                                                  _lib.p_u64(hi), _lib.p_i8(own), _lib.p_i32(out3), C.byref(conflict)))
+    edges = []
+    for d in range(depth):
+        l, h = int(lo[d]), int(hi[d])
+        edges.append([(((h >> s) & 1) * 2 + ((l >> s) & 1) - 2) if ((l | h) >> s) & 1 else None for s in range(64)])
+    return edges, int(out3[0]), int(out3[1]), bool(out3[2]), bool(conflict.value)
+
+
 def rules_prune_counts(N, Q, P, eta, legal, Ns, c, epsilon, k):
     """oz_forced_playouts_prune, policy target pruning over a batch of root rows, on the host (no GPU needed): N int32, Q, P, eta float64
     (count, 64) by square row*8+col, legal uint64 (count,), Ns int32 (count,) = the roots' stored statistics, their noise and visits; c, epsilon =
@@ -347,16 +410,17 @@ class NeuralNetworkOthelloAgent(OthelloAgent):
     the first valid action with the largest policy entry."""
 
     def __init__(self, game, neural_network, num_simulations, degree_exploration, temperature=0,
-                 q_mode=_lib.QMODE_F64, leaves_per_step=1, solve_leaves=0, value_signs="reference"):
+                 q_mode=_lib.QMODE_F64, leaves_per_step=1, solve_leaves=0, value_signs="reference", proofs=False):
         solve_leaves = _lib.check_solve_leaves(solve_leaves)
         _lib.check_value_signs(value_signs)
+        _lib.check_proofs(proofs, value_signs)
         super().__init__(game)
         self.neural_network, self.num_simulations, self.temperature = neural_network, num_simulations, 0
         side = game.board_size
         # an agent searches on its own turns only: about half the plies
         self.mcts = OthelloMCTS(side, neural_network, degree_exploration, q_mode=q_mode,
                                 node_cap=num_simulations * (side * side // 2) + 64, leaves_per_step=leaves_per_step,
-                                solve_leaves=solve_leaves, value_signs=value_signs)
+                                solve_leaves=solve_leaves, value_signs=value_signs, **_lib.proofs_kw(proofs))
 
     def play(self):
         game = self.game
@@ -387,7 +451,7 @@ def duel_between_agents(game, agent_1, agent_2):
 def arena_batch(net_a, net_b, board_size=8, num_games=512, num_simulations=800, degree_exploration=1.0, seed=0,
                 first_game_id=0, q_mode=_lib.QMODE_F64, node_cap=0, max_rounds=0, dedup=True, profile=False, eval_cache=False,
                 leaves_per_step=1, opponent=None, solve_leaves=0, openings=None, first_opening_id=0, opening_moves=None,
-                value_signs="reference"):
+                value_signs="reference", proofs=False):
     """num_games games of net_a (BLACK) vs net_b (WHITE), temperature 0, max-visit ties broken by the RNG_TIE
     stream keyed (seed, game id, ply).  One of the two may be None: RandomOthelloAgent plays that colour, or with
     opponent=("minimax", depth) / ("minimax", depth, "discs" | "weighted") the fixed-depth minimax (oz_arena_set_opponent; ties between its
@@ -405,6 +469,8 @@ def arena_batch(net_a, net_b, board_size=8, num_games=512, num_simulations=800, 
     its network's value (oz_arena_set_solve_leaves; 0 = off); the result then carries rows_solved = (black, white).
     value_signs = "reference" | "sound" or (black, white): the rule by which the agent's search backs its values up (oz_arena_set_value_signs;
     OthelloMCTS, value_signs).
+    proofs = True | False or (black, white): the agent's search keeps exact values as proofs and backs them up the tree (oz_arena_set_proofs;
+    OthelloMCTS, proofs); an agent with proofs needs value_signs "sound".  The moves read the raw counts as before.
     openings = (plies, opening_seed): every game first plays a random opening of `plies` plies (at most 16) without any search
     (oz_arena_set_openings, rules_random_openings); game slot g plays opening first_opening_id + g whatever seed and first_game_id are, so two
     arenas given the same (openings, first_opening_id) start from the same positions.  opening_moves = (moves uint8 (num_games, 16), n_plies int32
@@ -414,6 +480,7 @@ def arena_batch(net_a, net_b, board_size=8, num_games=512, num_simulations=800, 
     opening = _lib.check_openings(openings, first_opening_id, opening_moves, num_games)
     eb_, ew_ = _lib.check_solve_leaves_pair(solve_leaves)
     vb_, vw_ = _lib.check_value_signs_pair(value_signs)
+    pb_, pw_ = _lib.check_proofs_pair(proofs, value_signs)
     kb, kw = (leaves_per_step, leaves_per_step) if np.isscalar(leaves_per_step) else leaves_per_step
     minimax = _lib.check_opponents(opponent, net_a is None, net_b is None)
     lib = _lib.require_gpu()
@@ -432,6 +499,8 @@ def arena_batch(net_a, net_b, board_size=8, num_games=512, num_simulations=800, 
             _lib.check(lib.oz_arena_set_solve_leaves(h, eb_, ew_))
         if vb_ or vw_:
             _lib.check(lib.oz_arena_set_value_signs(h, vb_, vw_))
+        if pb_ or pw_:
+            _lib.check(lib.oz_arena_set_proofs(h, int(pb_), int(pw_)))
         if opening is not None and opening[0] == "random":
             _lib.check(lib.oz_arena_set_openings(h, opening[1], opening[2], opening[3]))
         elif opening is not None:

@@ -420,6 +420,72 @@ OZ_HD double oz_backup_last(int mode, uint64_t swaps, int depth, double leaf) {
     return -oz_backup_value(mode, depth > 0 ? swaps : 0, depth, 0, leaf);
 }
 
+// ---------------------------------------------------------------- proofs: exact values kept and backed up the tree
+// (include/othellozero_amd.h, "proofs").  OZ_VSIGNS_PROVEN is the third, internal value of the tree kernels' VS argument: the sound rule plus
+// proofs (every `mode == OZ_VSIGNS_SOUND` test above reads it through oz_vsigns_rule).  A proof is -1 / 0 / +1 for the side to move at the
+// node, or OZ_PROOF_NONE.  One 32-byte entry per node beside its record: two masks by square (state of square sq = 2 * hi + lo: 0 unknown,
+// 1 loss, 2 draw, 3 win -- e = state - 2), the node's legal set and its own value (set where it was expanded from a solved leaf).
+#define OZ_VSIGNS_PROVEN 2
+#define OZ_PROOF_NONE (-128)
+struct OzProof { uint64_t lo, hi, legal; int32_t own, pad; };
+OZ_HD int oz_vsigns_rule(int vs) { return vs == OZ_VSIGNS_PROVEN ? OZ_VSIGNS_SOUND : vs; }
+OZ_HD int oz_proof_edge(uint64_t lo, uint64_t hi, int sq) {
+    const int st = (int)((hi >> sq) & 1) * 2 + (int)((lo >> sq) & 1);
+    return st ? st - 2 : OZ_PROOF_NONE;
+}
+// val(S): the own value if set; else +1 if a legal edge wins; else the maximum if every legal edge is known; else unknown
+OZ_HD int oz_proof_value(uint64_t legal, uint64_t lo, uint64_t hi, int own) {
+    if (own != OZ_PROOF_NONE) return own;
+    if (legal & lo & hi) return 1;
+    if (legal == 0 || (legal & ~(lo | hi)) != 0) return OZ_PROOF_NONE;
+    return (legal & hi) ? 0 : -1;
+}
+// the edges a descent may take at a node of value `val` (OZ_PROOF_NONE below the root, where a known node is never descended): those whose
+// proof equals a known val; else -- and where there is none -- those not proven lost; none of those either: the legal set, *inconsistent = 1
+OZ_HD uint64_t oz_proof_candidates(uint64_t legal, uint64_t lo, uint64_t hi, int val, int* inconsistent) {
+    *inconsistent = 0;
+    uint64_t c = 0;
+    if (val == 1) c = legal & lo & hi;
+    else if (val == 0) c = legal & hi & ~lo;
+    else if (val == -1) c = legal & lo & ~hi;
+    if (c) return c;
+    c = legal & ~(lo & ~hi);
+    if (c) return c;
+    *inconsistent = 1;
+    return legal;
+}
+// e(S, sq) = x: 1 newly proven, 0 known and equal, -1 known and different (the masks are left alone)
+OZ_HD int oz_proof_mark(uint64_t* lo, uint64_t* hi, int sq, int x) {
+    const int e = oz_proof_edge(*lo, *hi, sq);
+    if (e != OZ_PROOF_NONE) return e == x ? 0 : -1;
+    const int st = x + 2;
+    *lo |= (uint64_t)(st & 1) << sq;
+    *hi |= (uint64_t)(st >> 1) << sq;
+    return 1;
+}
+// the proof loop of the backup over the entries of a path (pr[d] = the entry of the node of level d, sq[d] / sigma[d] its edge and swap bit):
+// from the bottom, x = V_L; per level x = sigma_d ? -x : x, e(path[d]) = x, and on while the node's value is known with x = that value.
+// -> levels marked (counted from the bottom); *fresh = edges newly proven, *conflict = 1 where a known edge differed, *root = 1 where the
+// value of level 0's node went from unknown to known
+OZ_HD int oz_proof_backup(OzProof* const* pr, const int* sq, const unsigned char* sigma, int depth, int leaf, int* fresh, int* conflict, int* root) {
+    int x = leaf, levels = 0;
+    *fresh = 0; *conflict = 0; *root = 0;
+    for (int d = depth - 1; d >= 0; --d) {
+        OzProof* p = pr[d];
+        x = sigma[d] ? -x : x;
+        const int before = oz_proof_value(p->legal, p->lo, p->hi, p->own);
+        const int r = oz_proof_mark(&p->lo, &p->hi, sq[d], x);
+        ++levels;
+        if (r > 0) *fresh += 1;
+        if (r < 0) *conflict = 1;
+        const int v = oz_proof_value(p->legal, p->lo, p->hi, p->own);
+        if (v == OZ_PROOF_NONE) break;
+        if (d == 0 && before == OZ_PROOF_NONE) *root = 1;
+        x = v;
+    }
+    return levels;
+}
+
 // ---------------------------------------------------------------- root value and value targets
 // (include/othellozero_amd.h, "value targets").  The root value of a search: the visit-weighted mean of the root's Q, for the player to
 // move.  a[sq] = oz_root_term: (double)N * Q where N > 0, else 0 (counts are 0 off the legal set); oz_root_mean = pairwise_sum(a, 64) /

@@ -54,6 +54,13 @@ struct OzEdge { uint32_t n_tag; int32_t child; double q; double p; };
 #define OZ_HT_IDX_MASK ((1u << OZ_HT_IDX_BITS) - 1u)
 static_assert(sizeof(OzEdge) == OZ_EDGE_BYTES, "edge layout");
 
+// proofs ("proofs" in oz_common.h): what the OZ_VSIGNS_PROVEN instantiations of the tree kernels get beside the records
+enum { PS_EDGES = 0, PS_EDGE_STOPS = 1, PS_NODE_STOPS = 2, PS_ROOTS = 3, OZ_NPSTAT = 4 };
+struct ProofDev {
+    OzProof* entry;            // [G][node_cap] one entry per node record, written whole at expansion
+    unsigned long long* stat;  // [G][OZ_NPSTAT] edges proven, descents ended on a proven edge / on a proven node, roots whose value became known
+    int E;                     // the object's solve_leaves: a leaf expanded with <= E empties carries the exact sign in v (0: none does)
+};
 struct MctsDev {
     int G, n, n2, node_cap, row_cap, rec_bytes, ht_cap;
     uint64_t valid;
@@ -88,6 +95,7 @@ struct MctsDev {
     uint8_t* noise_armed;      // [G] the slot's CURRENT root carries noise
     double noise_eps;          // the mixing weight (0: off)
     double forced_k;           // forced playouts ("forced playouts" below): the forcing constant k (0: off); needs noise, so the *_n kernels alone read it
+    ProofDev pf;               // proofs ("proofs" below): null / 0 until oz_*_set_proofs; the OZ_VSIGNS_PROVEN instantiations alone read it
 };
 // the frontier entries (node, edge rank): the rank is below 64; in the sound instantiations (VS, "value signs" in oz_common.h) bit 30 of .y keeps
 // sigma of the level -- the descent swapped sides after the edge.  The reference instantiations never set the bit and read .y as it is.
@@ -381,7 +389,7 @@ __device__ __forceinline__ Descent descend_one(const MctsDev& t, uint4* rec, int
         // `legal` = the mover's legal set of the state we stand on (of the root above; below, the move that led here computed it)
         if (legal == 0 && oz_legal(opp, own, t.valid) == 0) {       // is_terminal_state, othelo_mcts.py:28-29
             // get_state_reward: winner of the ch0 view, draw -> ch0 (simulate returns -reward: the backup's reference rule); sound: the sign, a draw is 0
-            tval = oz_terminal_value(VS, own, opp);
+            tval = oz_terminal_value(oz_vsigns_rule(VS), own, opp);
             status = OZ_LEAF_TERMINAL;
             break;
         }
@@ -400,9 +408,29 @@ __device__ __forceinline__ Descent descend_one(const MctsDev& t, uint4* rec, int
         // stage the record: header + cnt edges, 16 bytes per lane
         const int cnt = oz_popc(legal);
         const int chunks = (OZ_REC_HDR + cnt * OZ_EDGE_BYTES + 15) >> 4;
+        // proofs: the node's entry, its address a function of the node index like the record's -- both loads are in flight together
+        uint64_t plo = 0, phi = 0, pcand = legal;
+        int pown = OZ_PROOF_NONE;
+        if constexpr (VS == OZ_VSIGNS_PROVEN) {
+            const OzProof* pp = t.pf.entry + (size_t)g * t.node_cap + node;
+            plo = pp->lo; phi = pp->hi; pown = pp->own;
+        }
         __syncthreads();                                            // the previous level's LDS reads are done
         if (lane < chunks) rec[lane] = reinterpret_cast<const uint4*>(rec_ptr(t, g, node))[lane];
         __syncthreads();
+        if constexpr (VS == OZ_VSIGNS_PROVEN) {
+            plo = uni64(plo); phi = uni64(phi); pown = unii(pown);
+            const int val = oz_proof_value(legal, plo, phi, pown);
+            if (depth > 0 && val != OZ_PROOF_NONE) {                // a proven position is not searched again (the root always is: a move needs visits)
+                tval = val;
+                status = OZ_LEAF_TERMINAL;
+                if (lane == 0) t.pf.stat[(size_t)g * OZ_NPSTAT + PS_NODE_STOPS] += 1;
+                break;
+            }
+            int bad;
+            pcand = oz_proof_candidates(legal, plo, phi, val, &bad);
+            if (bad && lane == 0) atomicOr(t.error_flag, EF_CORRUPT);
+        }
         const uint64_t* w = reinterpret_cast<const uint64_t*>(rec);
         const int Ns = unii((int)(uint32_t)w[2]);
         const bool is_legal = (legal >> lane) & 1;
@@ -426,6 +454,10 @@ __device__ __forceinline__ Descent descend_one(const MctsDev& t, uint4* rec, int
                 Q = ((double)N * Q - (double)ke) / (double)(N + ke);
                 N += ke;
             }
+            if constexpr (VS == OZ_VSIGNS_PROVEN) {                         // a proven edge is worth its proof, whatever was averaged into Q
+                const int e = oz_proof_edge(plo, phi, lane);
+                if (e != OZ_PROOF_NONE) Q = (double)e;
+            }
             const double bound = sqrt((double)(Ns + ks)) / (double)(1 + N);    // MCTS/__init__.py:169
             U = Q + (t.c * P) * bound;                                     // :170, left to right
             if constexpr (NOISE) {
@@ -438,6 +470,10 @@ __device__ __forceinline__ Descent descend_one(const MctsDev& t, uint4* rec, int
             }
         }
         bool cand = is_legal;
+        if constexpr (VS == OZ_VSIGNS_PROVEN) {
+            cand = (pcand >> lane) & 1;
+            if (!cand) U = -INFINITY;
+        }
         if constexpr (GUMBEL) {
             if (gr.armed && depth == 0) {                                   // (uniform: one branch per wave)
                 const GumbelDev& gd = *gr.gd;
@@ -475,6 +511,15 @@ __device__ __forceinline__ Descent descend_one(const MctsDev& t, uint4* rec, int
         if constexpr (VS != OZ_VSIGNS_REFERENCE) { if (lane == 0) path[depth - 1] = make_int2(pnode, brank | (theirs != 0 ? OZ_PATH_SWAP : 0)); }   // sigma rides along
         if (theirs != 0) { uint64_t s = own; own = opp; opp = s; legal = theirs; }
         else legal = oz_legal(own, opp, t.valid);                   // pass (or the game is over): the same side is to move again
+        if constexpr (VS == OZ_VSIGNS_PROVEN) {
+            const int e = oz_proof_edge(plo, phi, best);
+            if (e != OZ_PROOF_NONE) {                               // the edge is proven: its value for the side to move after it, no look at the child
+                tval = theirs != 0 ? -e : e;
+                status = OZ_LEAF_TERMINAL;
+                if (lane == 0) t.pf.stat[(size_t)g * OZ_NPSTAT + PS_EDGE_STOPS] += 1;
+                break;
+            }
+        }
     }
     return Descent{own, opp, legal, depth, status, tval, fs, err};
 }
@@ -783,22 +828,49 @@ struct LeafRef {
 // parallel, one lane per level (a path never visits a node twice: every move adds a disc)
 // `value` = the leaf's value for the side to move there; what each level stores of it is oz_backup_value (oz_common.h) under VS: the
 // reference's one negation per level, or -- sound -- one per level at which the descent swapped sides (the sigma bits of the frontier)
+// proofs: the loop of the backup, after the Q update (lane 0; one entry per level, and it usually ends after one or two).  leaf = V_L, exact.
+__device__ __forceinline__ void proof_backup(const MctsDev& t, int g, int depth, const int2* __restrict__ path, int leaf) {
+    unsigned long long* st = t.pf.stat + (size_t)g * OZ_NPSTAT;
+    int x = leaf;
+    for (int d = depth - 1; d >= 0; --d) {
+        const int2 pe = path[d];
+        if ((unsigned)pe.x >= (unsigned)t.node_cap) return;         // (backup_one has raised EF_CORRUPT)
+        OzProof* pp = t.pf.entry + (size_t)g * t.node_cap + pe.x;
+        OzProof p = *pp;
+        const int rank = pe.y & (OZ_PATH_SWAP - 1);
+        uint64_t rest = p.legal;                                    // the square of the edge: the rank-th legal one
+        for (int i = 0; i < rank; ++i) rest &= rest - 1;
+        if (rest == 0) { atomicOr(t.error_flag, EF_CORRUPT); return; }
+        x = (pe.y & OZ_PATH_SWAP) ? -x : x;
+        const int before = oz_proof_value(p.legal, p.lo, p.hi, p.own);
+        const int r = oz_proof_mark(&p.lo, &p.hi, oz_ctz(rest), x);
+        if (r < 0) atomicOr(t.error_flag, EF_CORRUPT);
+        if (r > 0) { pp->lo = p.lo; pp->hi = p.hi; st[PS_EDGES] += 1; }
+        const int v = oz_proof_value(p.legal, p.lo, p.hi, p.own);
+        if (v == OZ_PROOF_NONE) return;
+        if (d == 0 && before == OZ_PROOF_NONE) st[PS_ROOTS] += 1;
+        x = v;
+    }
+}
 template <int VS>
-__device__ __forceinline__ void backup_one(const MctsDev& t, int g, int lane, int depth, const int2* __restrict__ path, double value, int vt) {
+__device__ __forceinline__ void backup_one(const MctsDev& t, int g, int lane, int depth, const int2* __restrict__ path, double value, int vt, bool exact = false) {
     int2 pe = make_int2(0, 0);
     if (lane < depth) pe = path[lane];
     const uint64_t swaps = VS != OZ_VSIGNS_REFERENCE ? __ballot((pe.y & OZ_PATH_SWAP) != 0) : 0;          // (lanes at or above depth hold 0)
     if (lane < depth) {
         const int rank = path_rank<VS>(pe.y);
-        const double val = oz_backup_value(VS, swaps, depth, lane, value);
+        const double val = oz_backup_value(oz_vsigns_rule(VS), swaps, depth, lane, value);
         if ((unsigned)pe.x < (unsigned)t.node_cap && (unsigned)rank < (unsigned)t.row_cap) {
             q_update(t, rec_edge(t, g, pe.x, rank), val, vt);
             *rec_Ns(t, g, pe.x) += 1;
         } else atomicOr(t.error_flag, EF_CORRUPT);
     }
     if (lane == 0) {
-        t.last_value[g] = oz_backup_last(VS, swaps, depth, value);
+        t.last_value[g] = oz_backup_last(oz_vsigns_rule(VS), swaps, depth, value);
         t.last_vtype[g] = vt;
+    }
+    if constexpr (VS == OZ_VSIGNS_PROVEN) {
+        if (exact && lane == 0) proof_backup(t, g, depth, path, (int)value);
     }
 }
 // expand the leaf if it needs it, then back its value up along its path.  GUMBEL: the new node's header keeps the value the expansion backs
@@ -809,6 +881,7 @@ __device__ __forceinline__ void expand_backup_one(const MctsDev& t, TreeLds& L, 
     if (status == OZ_LEAF_IDLE || status == OZ_LEAF_WAIT) return;           // (WAIT: the leaf was not in the batch, nothing to expand yet)
     double value;
     int vt;
+    bool exact = false;
     if (status == OZ_LEAF_EVAL) {
         // first visit (MCTS/__init__.py:44-57): P = pi * mask, normalised; uniform over legal if the sum is 0
         const uint64_t own = lf.own, opp = lf.opp, legal = lf.legal;
@@ -843,6 +916,16 @@ __device__ __forceinline__ void expand_backup_one(const MctsDev& t, TreeLds& L, 
             __syncthreads();
             const int chunks = (OZ_REC_HDR + cnt * OZ_EDGE_BYTES + 15) >> 4;
             if (lane < chunks) reinterpret_cast<uint4*>(rec_ptr(t, g, node))[lane] = L.rec[lane];
+            if constexpr (VS == OZ_VSIGNS_PROVEN) {
+                // the node's proof entry, whole (a reused pool slot inherits nothing); a solved leaf's v is its exact sign: the node's own value
+                int ownv = OZ_PROOF_NONE;
+                if (t.pf.E > 0 && t.n2 - oz_popc(own | opp) <= t.pf.E) ownv = (int)t.v[slot];
+                exact = ownv != OZ_PROOF_NONE;
+                if (lane == 0) {
+                    t.pf.entry[(size_t)g * t.node_cap + node] = OzProof{0, 0, legal, ownv, 0};
+                    if (exact && depth == 0) t.pf.stat[(size_t)g * OZ_NPSTAT + PS_ROOTS] += 1;
+                }
+            }
             if (lane == 0) {
                 t.node_count[g] = node + 1;
                 t.ht[(size_t)g * t.ht_cap + fs] = ht_entry(own, opp, node);
@@ -863,8 +946,9 @@ __device__ __forceinline__ void expand_backup_one(const MctsDev& t, TreeLds& L, 
     } else {
         value = (double)lf.tval;
         vt = VT_INT;
+        exact = true;
     }
-    backup_one<VS>(t, g, lane, lf.depth, lf.path, value, vt);
+    backup_one<VS>(t, g, lane, lf.depth, lf.path, value, vt, exact);
 }
 // ... of the descent select_body stored in the per-game arrays.  slot_is_game != 0: pi / v are indexed by game (host evaluator path); else
 // by compacted slot.
@@ -1195,6 +1279,8 @@ struct oz_mcts {
     int solve_leaves = 0;
     // value signs of the backup (oz_mcts_set_value_signs): which instantiation of the tree kernels the object launches
     int vsigns = OZ_VSIGNS_REFERENCE;
+    // proofs (oz_mcts_set_proofs): on top of sound signs, the OZ_VSIGNS_PROVEN instantiations (d.pf's arrays are allocated at the first setting)
+    bool proofs = false;
     unsigned solve_stamp = 0;
     unsigned* solve_claim = nullptr; unsigned long long* solve_rows = nullptr;
     bool solve_profile = false;      // oz_mcts_solve_leaves_profile: HIP events around k_solve_leaves
@@ -1317,6 +1403,8 @@ static int check_error_flag(oz_mcts* m) {
 
 // the tree kernel `K` of the object m's value signs (m in scope)
 #define OZ_VS(K) (m->vsigns != OZ_VSIGNS_REFERENCE ? K<OZ_VSIGNS_SOUND> : K<OZ_VSIGNS_REFERENCE>)
+// ... of the kernels that have the proven instantiation (the plain and the wide search; the Gumbel and free-running families refuse the option)
+#define OZ_VSP(K) (m->proofs ? K<OZ_VSIGNS_PROVEN> : OZ_VS(K))
 enum { TS_SELECT = 0, TS_COMPACT = 1, TS_NN = 2, TS_BACKUP = 3, TS_MOVE = 4 };
 // the step's solved rows (k_solve_leaves): after the evaluator of EITHER kind of step has written the rows [0, cap) (and the cache has taken
 // them), before their expand + backup.  hits: the step may have rows served from the evaluation cache.  Off (the default), nothing is launched.
@@ -1420,8 +1508,8 @@ static int mcts_wide_steps(oz_mcts* m, oz_net* net, int nsims, int max_games, bo
         if (enqueued > (long long)nsims) { oz_set_error("leaf-parallel search: the simulation budget did not run out after %d steps (internal error)", nsims); return OZ_ERR_STATE; }
         for (int k = 0; k < steps; ++k) {
             timed(m, TS_SELECT, all, [&] {
-                if (k == 0) hipLaunchKernelGGL(m->noise_ever ? OZ_VS(k_wide_select_n) : OZ_VS(k_wide_select), dim3(d.G), dim3(64), 0, s, d, w);
-                else hipLaunchKernelGGL(m->noise_ever ? OZ_VS(k_wide_backup_select_n) : OZ_VS(k_wide_backup_select), dim3(d.G), dim3(64), 0, s, d, w);
+                if (k == 0) hipLaunchKernelGGL(m->noise_ever ? OZ_VSP(k_wide_select_n) : OZ_VSP(k_wide_select), dim3(d.G), dim3(64), 0, s, d, w);
+                else hipLaunchKernelGGL(m->noise_ever ? OZ_VSP(k_wide_backup_select_n) : OZ_VSP(k_wide_backup_select), dim3(d.G), dim3(64), 0, s, d, w);
             });
             timed(m, TS_COMPACT, all, [&] { hipLaunchKernelGGL(k_wide_compact, dim3(1), dim3(1024), 0, s, d, w); });
             const long long i = (time_eval || all) ? m->timer.begin(TS_NN, s) : -1;
@@ -1429,7 +1517,7 @@ static int mcts_wide_steps(oz_mcts* m, oz_net* net, int nsims, int max_games, bo
             m->timer.end(i, s);
             solve_leaves_async(m, cap, false);              // (no evaluation cache here: every leaf has a row of its own)
         }
-        timed(m, TS_BACKUP, all, [&] { hipLaunchKernelGGL(OZ_VS(k_wide_expand_backup), dim3(d.G), dim3(64), 0, s, d, w); });
+        timed(m, TS_BACKUP, all, [&] { hipLaunchKernelGGL(OZ_VSP(k_wide_expand_backup), dim3(d.G), dim3(64), 0, s, d, w); });
         OZ_HIP(hipGetLastError());
         int max_left = 0;
         OZ_HIP(hipMemsetAsync(w.max_left, 0, sizeof(int), s));
@@ -1463,13 +1551,13 @@ static int mcts_steps_async(oz_mcts* m, oz_net* net, int nsims, int max_games, b
             if (m->gumbel_ever) {
                 if (k == 0) hipLaunchKernelGGL(OZ_VS(k_select_g), dim3(d.G), dim3(64), 0, s, d, m->gd);
                 else hipLaunchKernelGGL(OZ_VS(k_backup_select_g), dim3(d.G), dim3(64), 0, s, d, m->gd);
-            } else if (k == 0) hipLaunchKernelGGL(m->noise_ever ? OZ_VS(k_select_n) : OZ_VS(k_select), dim3(d.G), dim3(64), 0, s, d);
-            else hipLaunchKernelGGL(m->noise_ever ? OZ_VS(k_backup_select_n) : OZ_VS(k_backup_select), dim3(d.G), dim3(64), 0, s, d);
+            } else if (k == 0) hipLaunchKernelGGL(m->noise_ever ? OZ_VSP(k_select_n) : OZ_VSP(k_select), dim3(d.G), dim3(64), 0, s, d);
+            else hipLaunchKernelGGL(m->noise_ever ? OZ_VSP(k_backup_select_n) : OZ_VSP(k_backup_select), dim3(d.G), dim3(64), 0, s, d);
         });
         timed(m, TS_COMPACT, all, [&] { hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, s, d); });
         if (int rc = eval_batch_async(m, net, max_games, time_eval || all)) return rc;
     }
-    timed(m, TS_BACKUP, all, [&] { hipLaunchKernelGGL(m->gumbel_ever ? OZ_VS(k_expand_backup_g) : OZ_VS(k_expand_backup), dim3(d.G), dim3(64), 0, s, d, 0); });
+    timed(m, TS_BACKUP, all, [&] { hipLaunchKernelGGL(m->gumbel_ever ? OZ_VS(k_expand_backup_g) : OZ_VSP(k_expand_backup), dim3(d.G), dim3(64), 0, s, d, 0); });
     OZ_HIP(hipGetLastError());
     return OZ_OK;
 }
@@ -1576,6 +1664,7 @@ static int solve_leaves_set_locked(oz_mcts* m, int e) {
         OZ_HIP(hipMemsetAsync(m->solve_rows, 0, sizeof(unsigned long long), m->stream));
     }
     m->solve_leaves = e;
+    m->d.pf.E = e;                                         // (proofs: a leaf expanded with <= e empties carries its exact sign)
     return OZ_OK;
 }
 static int solve_leaves_rows_locked(oz_mcts* m, int64_t* rows) {
@@ -1633,6 +1722,7 @@ static int value_signs_set_locked(oz_mcts* m, const char* fn, int mode) {
     OZ_HIP(hipStreamSynchronize(m->stream));
     for (int n : nodes)
         if (n != 0) { oz_set_error("%s: the tree holds nodes already (set the mode right after create or after oz_mcts_reset(-1))", fn); return OZ_ERR_STATE; }
+    if (m->proofs && mode != OZ_VSIGNS_SOUND) { oz_set_error("%s: proofs are on and need the sound signs (switch them off first)", fn); return OZ_ERR_STATE; }
     m->vsigns = mode;
     return OZ_OK;
 }
@@ -1662,6 +1752,170 @@ OZ_API int oz_search_terminal_value(int mode, uint64_t own, uint64_t opp, int* v
     if (int rc = value_signs_check("oz_search_terminal_value", mode)) return rc;
     OZ_REQUIRE(value, "oz_search_terminal_value: null argument");
     *value = oz_terminal_value(mode, own, opp);
+    return OZ_OK;
+}
+
+// ---- proofs: the option (include/othellozero_amd.h, "proofs").  Like the value signs it changes on an empty tree alone; it needs the sound
+// signs (the reference's finished boards carry the wrong sign) and refuses the kernel families without a proven instantiation.
+static_assert(OZ_PROOF_UNKNOWN == OZ_PROOF_NONE, "proofs: one numbering");
+static int proofs_set_locked(oz_mcts* m, const char* fn, int enable) {
+    if (m->selected) { oz_set_error("%s: a step is pending (oz_mcts_select without oz_mcts_backup)", fn); return OZ_ERR_STATE; }
+    hipSetDevice(m->device);
+    MctsDev& d = m->d;
+    std::vector<int> nodes((size_t)d.G);
+    OZ_HIP(hipMemcpyAsync(nodes.data(), d.node_count, sizeof(int) * nodes.size(), hipMemcpyDeviceToHost, m->stream));
+    OZ_HIP(hipStreamSynchronize(m->stream));
+    for (int n : nodes)
+        if (n != 0) { oz_set_error("%s: the tree holds nodes already (set the option right after create or after oz_mcts_reset(-1))", fn); return OZ_ERR_STATE; }
+    if (!enable) { m->proofs = false; return OZ_OK; }
+    if (m->vsigns != OZ_VSIGNS_SOUND) { oz_set_error("%s: proofs need value signs \"sound\" (a proof built on the reference's finished boards is wrong)", fn); return OZ_ERR_STATE; }
+    if (m->gumbel_ever) { oz_set_error("%s: not with the Gumbel search (its kernels have no proven instantiation)", fn); return OZ_ERR_STATE; }
+    if (d.forced_k > 0.0) { oz_set_error("%s: not with forced playouts (set k to 0 first)", fn); return OZ_ERR_STATE; }
+    if (!d.pf.entry) {
+        const size_t held = m->allocs.size();
+        int rc = m->alloc(&d.pf.entry, (size_t)d.G * d.node_cap);
+        if (!rc) rc = m->alloc(&d.pf.stat, (size_t)d.G * OZ_NPSTAT);
+        if (!rc && (hipMemsetAsync(d.pf.stat, 0, sizeof(unsigned long long) * OZ_NPSTAT * (size_t)d.G, m->stream) != hipSuccess ||
+                    hipStreamSynchronize(m->stream) != hipSuccess)) {
+            oz_set_error("%s: clearing the counters failed", fn);
+            rc = OZ_ERR_HIP;
+        }
+        if (rc) {
+            for (size_t i = held; i < m->allocs.size(); ++i) hipFree(m->allocs[i]);
+            m->allocs.resize(held);
+            d.pf.entry = nullptr; d.pf.stat = nullptr;
+            return rc;
+        }
+    }
+    d.pf.E = m->solve_leaves;
+    m->proofs = true;
+    return OZ_OK;
+}
+OZ_API int oz_mcts_set_proofs(oz_mcts* m, int enable) {
+    OZ_REQUIRE(m, "null mcts");
+    std::lock_guard<std::mutex> lk(m->mu);
+    return proofs_set_locked(m, "oz_mcts_set_proofs", enable);
+}
+OZ_API int oz_mcts_get_proofs(oz_mcts* m, int* enabled) {
+    OZ_REQUIRE(m && enabled, "null argument");
+    std::lock_guard<std::mutex> lk(m->mu);
+    *enabled = m->proofs ? 1 : 0;
+    return OZ_OK;
+}
+static int proof_stats_locked(oz_mcts* m, int64_t* out4) {
+    for (int k = 0; k < OZ_NPSTAT; ++k) out4[k] = 0;
+    if (!m->d.pf.stat) return OZ_OK;
+    const size_t cnt = (size_t)m->d.G * OZ_NPSTAT;
+    std::vector<unsigned long long> h(cnt);
+    hipSetDevice(m->device);
+    OZ_HIP(hipMemcpyAsync(h.data(), m->d.pf.stat, 8 * cnt, hipMemcpyDeviceToHost, m->stream));
+    OZ_HIP(hipStreamSynchronize(m->stream));
+    for (size_t i = 0; i < cnt; ++i) out4[i % OZ_NPSTAT] += (int64_t)h[i];
+    return OZ_OK;
+}
+OZ_API int oz_mcts_proof_stats(oz_mcts* m, int64_t* out4) {
+    OZ_REQUIRE(m && out4, "null argument");
+    std::lock_guard<std::mutex> lk(m->mu);
+    return proof_stats_locked(m, out4);
+}
+// the proof entry of node `index` of game `game` (indices as oz_mcts_dump_node) on the host; false: the object keeps none
+static int proof_entry_locked(oz_mcts* m, int game, int index, OzProof* p) {
+    MctsDev& d = m->d;
+    OZ_REQUIRE(game >= 0 && game < d.G, "game index out of range");
+    hipSetDevice(m->device);
+    OZ_HIP(hipStreamSynchronize(m->stream));
+    int nn = 0;
+    OZ_HIP(hipMemcpy(&nn, d.node_count + game, 4, hipMemcpyDeviceToHost));
+    OZ_REQUIRE(index >= 0 && index < nn, "node index %d out of range (%d nodes)", index, nn);
+    OZ_HIP(hipMemcpy(p, d.pf.entry + (size_t)game * d.node_cap + index, sizeof(OzProof), hipMemcpyDeviceToHost));
+    return OZ_OK;
+}
+static void proof_edges(const OzProof& p, int8_t* edge) {
+    for (int s = 0; s < 64; ++s) edge[s] = (int8_t)(((p.legal >> s) & 1) ? oz_proof_edge(p.lo, p.hi, s) : OZ_PROOF_NONE);
+}
+OZ_API int oz_mcts_dump_proofs(oz_mcts* m, int game, int index, int8_t* edge, int8_t* node_value, int8_t* node_val) {
+    OZ_REQUIRE(m && edge && node_value && node_val, "null argument");
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (!m->proofs) { oz_set_error("oz_mcts_dump_proofs: the object keeps no proofs (oz_mcts_set_proofs)"); return OZ_ERR_STATE; }
+    OzProof p;
+    if (int rc = proof_entry_locked(m, game, index, &p)) return rc;
+    proof_edges(p, edge);
+    *node_value = (int8_t)p.own;
+    *node_val = (int8_t)oz_proof_value(p.legal, p.lo, p.hi, p.own);
+    return OZ_OK;
+}
+// the proofs of the current roots: rc[g] = 0, or 1 where game g is idle or its root is not in the table (edge / val are then unknown)
+OZ_API int oz_mcts_root_proofs(oz_mcts* m, int8_t* edge, int8_t* val, int32_t* rc) {
+    OZ_REQUIRE(m && edge && val && rc, "null argument");
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (!m->proofs) { oz_set_error("oz_mcts_root_proofs: the object keeps no proofs (oz_mcts_set_proofs)"); return OZ_ERR_STATE; }
+    hipSetDevice(m->device);
+    MctsDev& d = m->d;
+    const int G = d.G;
+    std::vector<uint64_t> o(G), q(G);
+    std::vector<uint8_t> act(G);
+    std::vector<int> nn(G);
+    OZ_HIP(hipMemcpyAsync(o.data(), d.root_own, 8ull * G, hipMemcpyDeviceToHost, m->stream));
+    OZ_HIP(hipMemcpyAsync(q.data(), d.root_opp, 8ull * G, hipMemcpyDeviceToHost, m->stream));
+    OZ_HIP(hipMemcpyAsync(act.data(), d.active, G, hipMemcpyDeviceToHost, m->stream));
+    OZ_HIP(hipMemcpyAsync(nn.data(), d.node_count, 4ull * G, hipMemcpyDeviceToHost, m->stream));
+    OZ_HIP(hipStreamSynchronize(m->stream));
+    std::vector<uint64_t> keys;
+    std::vector<OzProof> pr;
+    for (int g = 0; g < G; ++g) {
+        for (int s = 0; s < 64; ++s) edge[(size_t)g * 64 + s] = OZ_PROOF_NONE;
+        val[g] = OZ_PROOF_NONE; rc[g] = 1;
+        if (!act[g] || nn[g] <= 0) continue;
+        // (the host has no view of the hash table: the node headers are searched -- a call per move on small trees, for tests and tools)
+        keys.resize((size_t)nn[g] * 2);
+        OZ_HIP(hipMemcpy2D(keys.data(), 16, d.recs + (size_t)g * d.node_cap * (size_t)d.rec_bytes, (size_t)d.rec_bytes, 16, (size_t)nn[g], hipMemcpyDeviceToHost));
+        for (int i = 0; i < nn[g]; ++i)
+            if (keys[2 * (size_t)i] == o[g] && keys[2 * (size_t)i + 1] == q[g]) {
+                OzProof p;
+                OZ_HIP(hipMemcpy(&p, d.pf.entry + (size_t)g * d.node_cap + i, sizeof(OzProof), hipMemcpyDeviceToHost));
+                proof_edges(p, edge + (size_t)g * 64);
+                val[g] = (int8_t)oz_proof_value(p.legal, p.lo, p.hi, p.own);
+                rc[g] = 0;
+                break;
+            }
+    }
+    return OZ_OK;
+}
+// the rule on the host (oz_common.h), for tests and tools without a device.  Values are -1 / 0 / +1 or OZ_PROOF_UNKNOWN.
+static bool proof_is_value(int v) { return v == OZ_PROOF_NONE || (v >= -1 && v <= 1); }
+OZ_API int oz_search_proof_value(uint64_t legal, uint64_t lo, uint64_t hi, int own_value, int* value) {
+    OZ_REQUIRE(value, "oz_search_proof_value: null argument");
+    OZ_REQUIRE(proof_is_value(own_value), "oz_search_proof_value: own_value %d", own_value);
+    *value = oz_proof_value(legal, lo, hi, own_value);
+    return OZ_OK;
+}
+OZ_API int oz_search_proof_candidates(uint64_t legal, uint64_t lo, uint64_t hi, int node_val, uint64_t* candidates, int* inconsistent) {
+    OZ_REQUIRE(candidates && inconsistent, "oz_search_proof_candidates: null argument");
+    OZ_REQUIRE(proof_is_value(node_val), "oz_search_proof_candidates: node_val %d", node_val);
+    *candidates = oz_proof_candidates(legal, lo, hi, node_val, inconsistent);
+    return OZ_OK;
+}
+// the proof loop over a path: level d's node has (legal[d], lo[d], hi[d], own_value[d]) and the descent took its square[d] with swap bit
+// sigma[d]; lo / hi are updated in place.  out3 = levels marked, edges newly proven, 1 where the root's value became known;
+// *conflict = 1 where a known edge differed.
+OZ_API int oz_search_proof_backup(const uint8_t* sigma, const int32_t* square, int depth, int leaf_value, const uint64_t* legal, uint64_t* lo, uint64_t* hi,
+                                  const int8_t* own_value, int32_t* out3, int* conflict) {
+    OZ_REQUIRE(depth >= 0 && depth <= OZ_MAX_DEPTH, "oz_search_proof_backup: depth %d outside 0 .. %d", depth, OZ_MAX_DEPTH);
+    OZ_REQUIRE(leaf_value >= -1 && leaf_value <= 1, "oz_search_proof_backup: leaf_value %d", leaf_value);
+    OZ_REQUIRE(out3 && conflict && (depth == 0 || (sigma && square && legal && lo && hi && own_value)), "oz_search_proof_backup: null argument");
+    OzProof pr[OZ_MAX_DEPTH];
+    OzProof* pp[OZ_MAX_DEPTH];
+    int sq[OZ_MAX_DEPTH];
+    for (int d = 0; d < depth; ++d) {
+        OZ_REQUIRE(square[d] >= 0 && square[d] < 64 && ((legal[d] >> square[d]) & 1), "oz_search_proof_backup: square[%d] = %d is not legal", d, square[d]);
+        OZ_REQUIRE(proof_is_value(own_value[d]), "oz_search_proof_backup: own_value[%d] = %d", d, own_value[d]);
+        pr[d] = OzProof{lo[d], hi[d], legal[d], own_value[d], 0};
+        pp[d] = &pr[d]; sq[d] = square[d];
+    }
+    int fresh = 0, root = 0;
+    out3[0] = oz_proof_backup(pp, sq, sigma, depth, leaf_value, &fresh, conflict, &root);
+    out3[1] = fresh; out3[2] = root;
+    for (int d = 0; d < depth; ++d) { lo[d] = pr[d].lo; hi[d] = pr[d].hi; }
     return OZ_OK;
 }
 
@@ -1831,7 +2085,7 @@ OZ_API int oz_mcts_select(oz_mcts* m) {
     OZ_REFUSE_SOLVED(m, "oz_mcts_select");
     hipSetDevice(m->device);
     if (m->gumbel_ever) hipLaunchKernelGGL(OZ_VS(k_select_g), dim3(m->d.G), dim3(64), 0, m->stream, m->d, m->gd);
-    else hipLaunchKernelGGL(m->noise_ever ? OZ_VS(k_select_n) : OZ_VS(k_select), dim3(m->d.G), dim3(64), 0, m->stream, m->d);
+    else hipLaunchKernelGGL(m->noise_ever ? OZ_VSP(k_select_n) : OZ_VSP(k_select), dim3(m->d.G), dim3(64), 0, m->stream, m->d);
     OZ_HIP(hipGetLastError());
     m->selected = true;
     return check_error_flag(m);
@@ -1861,7 +2115,7 @@ OZ_API int oz_mcts_backup(oz_mcts* m, const float* pi, const float* v) {
     const int G = m->d.G;
     OZ_HIP(hipMemcpyAsync(m->d.pi, pi, 4ull * G * m->d.n2, hipMemcpyHostToDevice, m->stream));
     OZ_HIP(hipMemcpyAsync(m->d.v, v, 4ull * G, hipMemcpyHostToDevice, m->stream));
-    hipLaunchKernelGGL(m->gumbel_ever ? OZ_VS(k_expand_backup_g) : OZ_VS(k_expand_backup), dim3(G), dim3(64), 0, m->stream, m->d, 1);
+    hipLaunchKernelGGL(m->gumbel_ever ? OZ_VS(k_expand_backup_g) : OZ_VSP(k_expand_backup), dim3(G), dim3(64), 0, m->stream, m->d, 1);
     OZ_HIP(hipGetLastError());
     m->selected = false;
     return check_error_flag(m);
@@ -2078,6 +2332,7 @@ static int gumbel_enable(oz_mcts* m, const char* fn, int max_considered, double 
     MctsDev& d = m->d;
     const int G = d.G;
     if (!m->gumbel_ever) {
+        if (m->proofs) { oz_set_error("%s: not with proofs (the Gumbel kernels have no proven instantiation)", fn); return OZ_ERR_STATE; }
         if (m->noise_ever) { oz_set_error("%s: the Gumbel search replaces root noise and forced playouts (the object has armed root noise)", fn); return OZ_ERR_STATE; }
         if (m->wide()) { oz_set_error("%s: the Gumbel search runs one leaf per game and step (leaves_per_step is %d)", fn, m->leaves_per_step); return OZ_ERR_STATE; }
         std::vector<int> nn(G);
@@ -2280,6 +2535,7 @@ static int forced_check(const char* fn, double k) {
 }
 // k > 0 needs root noise armed on the object (forcing is a rule of the noisy root); k == 0 switches off
 static int forced_set_locked(oz_mcts* m, const char* fn, double k) {
+    if (k > 0.0 && m->proofs) { oz_set_error("%s: not with proofs (forcing a proven loss would undo them)", fn); return OZ_ERR_STATE; }
     if (k > 0.0 && !(m->noise_ever && m->d.noise_eps > 0.0)) {
         oz_set_error("%s: forced playouts need root noise (arm it first)", fn);
         return OZ_ERR_STATE;
@@ -3280,6 +3536,7 @@ OZ_API int oz_selfplay_stagger(oz_selfplay* sp, int sims_pre) {
     std::lock_guard<std::mutex> lkn(sp->net->mu);
     hipSetDevice(sp->m->device);
     OZ_REQUIRE(sp->mode == 0, "oz_selfplay_stagger must be the first driver call on an engine");
+    if (sp->m->proofs) { oz_set_error("oz_selfplay_stagger: not with proofs (use oz_selfplay_run)"); return OZ_ERR_STATE; }
     if (sp->gumbel_on) { oz_set_error("oz_selfplay_stagger: not with the Gumbel search (its budget is num_simulations; use oz_selfplay_run)"); return OZ_ERR_STATE; }
     if (sp->resign.r > 0) { oz_set_error("oz_selfplay_stagger: not with resignation (its rounds search at sims_pre; use oz_selfplay_run)"); return OZ_ERR_STATE; }
     OZ_REQUIRE(sp->cfg.refill, "oz_selfplay_stagger is for continuous self-play (cfg.refill = 1)");
@@ -3345,6 +3602,20 @@ OZ_API int oz_selfplay_set_value_signs(oz_selfplay* sp, int mode) {
     if (sp->mode != 0) { oz_set_error("oz_selfplay_set_value_signs: the engine has been driven already (set it before the first driver call)"); return OZ_ERR_STATE; }
     std::lock_guard<std::mutex> lkm(sp->m->mu);
     return value_signs_set_locked(sp->m, "oz_selfplay_set_value_signs", mode);
+}
+// proofs of the engine's search (see oz_mcts_set_proofs), for oz_selfplay_run; before the first driver call
+OZ_API int oz_selfplay_set_proofs(oz_selfplay* sp, int enable) {
+    OZ_REQUIRE(sp, "null selfplay");
+    std::lock_guard<std::mutex> lk(sp->mu);
+    if (sp->mode != 0) { oz_set_error("oz_selfplay_set_proofs: the engine has been driven already (set it before the first driver call)"); return OZ_ERR_STATE; }
+    std::lock_guard<std::mutex> lkm(sp->m->mu);
+    return proofs_set_locked(sp->m, "oz_selfplay_set_proofs", enable);
+}
+OZ_API int oz_selfplay_proof_stats(oz_selfplay* sp, int64_t* out4) {
+    OZ_REQUIRE(sp && out4, "null argument");
+    std::lock_guard<std::mutex> lk(sp->mu);
+    std::lock_guard<std::mutex> lkm(sp->m->mu);
+    return proof_stats_locked(sp->m, out4);
 }
 OZ_API int oz_selfplay_get_value_signs(oz_selfplay* sp, int* mode) {
     OZ_REQUIRE(sp, "null selfplay");
@@ -3669,6 +3940,7 @@ OZ_API int oz_selfplay_run_steps(oz_selfplay* sp, int steps) {
         return OZ_ERR_STATE;
     }
     if (sp->gumbel_on) { oz_set_error("oz_selfplay_run_steps: the free-running driver does not run the Gumbel search; use oz_selfplay_run"); return OZ_ERR_STATE; }
+    if (sp->m->proofs) { oz_set_error("oz_selfplay_run_steps: the free-running driver keeps no proofs; use oz_selfplay_run"); return OZ_ERR_STATE; }
     if (sp->resign.r > 0) { oz_set_error("oz_selfplay_run_steps: the free-running driver does not resign games; use oz_selfplay_run"); return OZ_ERR_STATE; }
     std::lock_guard<std::mutex> lkn(sp->net->mu);
     oz_mcts* m = sp->m;
@@ -4521,6 +4793,14 @@ OZ_API int oz_arena_set_value_signs(oz_arena* a, int black, int white) {
     if (a->started) { oz_set_error("oz_arena_set_value_signs: the arena has run already (set it before the first run)"); return OZ_ERR_STATE; }
     if (int rc = value_signs_set_locked(a->games.m, "oz_arena_set_value_signs", black)) return rc;
     return value_signs_set_locked(a->mb, "oz_arena_set_value_signs", white);
+}
+// proofs per agent (black for net_a's search, white for net_b's), each on top of sound signs; before the first run
+OZ_API int oz_arena_set_proofs(oz_arena* a, int black, int white) {
+    OZ_REQUIRE(a, "null arena");
+    std::lock_guard<std::mutex> lk(a->mu);
+    if (a->started) { oz_set_error("oz_arena_set_proofs: the arena has run already (set it before the first run)"); return OZ_ERR_STATE; }
+    if (int rc = proofs_set_locked(a->games.m, "oz_arena_set_proofs", black)) return rc;
+    return proofs_set_locked(a->mb, "oz_arena_set_proofs", white);
 }
 OZ_API int oz_arena_get_solve_leaves(oz_arena* a, int64_t* rows_black, int64_t* rows_white) {
     OZ_REQUIRE(a && rows_black && rows_white, "null argument");

@@ -173,20 +173,22 @@ def evaluate_against_random(board_size, neural_network, games, num_simulations, 
 
 
 def evaluate_against_random_batch(board_size, neural_network, games, num_simulations, degree_exploration, seed=0, leaves_per_step=1,
-                                  opponent=None, solve_leaves=0, openings=None, value_signs="reference"):
+                                  opponent=None, solve_leaves=0, openings=None, value_signs="reference", proofs=False):
     """The same evaluation as `evaluate_against_random` played in lock step on the GPU (agents.arena_batch with a random
     mover): the network takes BLACK in the first games // 2 + games % 2 games and WHITE in the rest (the reference draws the
     colours with random.shuffle; the split here is fixed).  opponent: arena_batch's (None / "random", or ("minimax", depth[, evaluation])).
     solve_leaves=E > 0: the network's search takes exact values for leaves with at most E empties (arena_batch).
     value_signs="sound": the network's search backs its values up with the signs right across passes and finished boards (arena_batch).
+    proofs=True (needs value_signs="sound"): the network's search keeps exact values as proofs and backs them up the tree (arena_batch).
     openings=(plies, opening_seed): every game starts with a random opening (arena_batch); game k of the BLACK half and game k of the WHITE half
     play opening k, so the network meets every opening from both sides (with an odd `games` the BLACK half has one opening more).
     -> dict(wins, black_wins, black_games, white_wins, white_games)"""
     _lib.check_opponent(opponent)
     solve_leaves = _lib.check_solve_leaves(solve_leaves)
     _lib.check_value_signs(value_signs)
+    _lib.check_proofs(proofs, value_signs)
     _lib.check_openings(openings)
-    opening_kw = dict({"openings": openings, "first_opening_id": 0} if openings is not None else {}, **({"value_signs": value_signs} if value_signs != "reference" else {}))
+    opening_kw = dict({"openings": openings, "first_opening_id": 0} if openings is not None else {}, **({"value_signs": value_signs} if value_signs != "reference" else {}), **_lib.proofs_kw(proofs))
     as_black, as_white = games // 2 + games % 2, games // 2
     r = dict(wins=0, black_wins=0, black_games=0, white_wins=0, white_games=0)
     if as_black:
@@ -210,13 +212,14 @@ def evaluate_against_opponent(board_size, neural_network, games, num_simulations
 
 
 def evaluate_against_opponent_batch(board_size, neural_network, games, num_simulations, degree_exploration, opponent, seed=0, leaves_per_step=1,
-                                    solve_leaves=0, openings=None, value_signs="reference"):
+                                    solve_leaves=0, openings=None, value_signs="reference", proofs=False):
     """`evaluate_against_random_batch` under the name that says what it does when the opponent is not the random agent"""
     solve_leaves = _lib.check_solve_leaves(solve_leaves)
     _lib.check_value_signs(value_signs)
+    _lib.check_proofs(proofs, value_signs)
     return evaluate_against_random_batch(board_size, neural_network, games, num_simulations, degree_exploration, seed=seed,
                                          leaves_per_step=leaves_per_step, opponent=opponent, **({"solve_leaves": solve_leaves} if solve_leaves else {}),
-                                         **({"openings": openings} if openings is not None else {}), **({"value_signs": value_signs} if value_signs != "reference" else {}))
+                                         **({"openings": openings} if openings is not None else {}), **({"value_signs": value_signs} if value_signs != "reference" else {}), **_lib.proofs_kw(proofs))
 
 
 def _discs(boards):
@@ -250,20 +253,21 @@ def pair_statistics(new_black_final_black, new_black_final_white, old_black_fina
 
 
 def paired_match(board_size, neural_network, old_neural_network, pairs, num_simulations, degree_exploration, openings, seed=0, leaves_per_step=1,
-                 solve_leaves=0, value_signs="reference"):
+                 solve_leaves=0, value_signs="reference", proofs=False):
     """A match over an opening suite, every opening played twice with the colours swapped -- NOT the reference's match (main.py:110-134 starts
     every game from the standard position).  Two arenas of `pairs` games: the new network as BLACK against the old one, then the old one as
     BLACK against the new; both get openings=(plies, opening_seed) and first_opening_id=0, so game i of either starts with opening i.  Game ids
     are 0 .. pairs - 1 and pairs .. 2 pairs - 1, as in self_play_match.  -> pair_statistics' dict, plus games = the two arena_batch results."""
     solve_leaves = _lib.check_solve_leaves(solve_leaves)
     _lib.check_value_signs(value_signs)
+    _lib.check_proofs(proofs, value_signs)
     if openings is None:
         raise ValueError("paired_match needs openings=(plies, opening_seed): without them every pair is the same two games")
     _lib.check_openings(openings)
     if isinstance(pairs, bool) or not isinstance(pairs, (int, np.integer)) or pairs < 1:
         raise ValueError(f"paired_match: pairs must be a whole number >= 1 (got {pairs!r})")
     kw = dict(leaves_per_step=leaves_per_step, openings=openings, first_opening_id=0, **({"solve_leaves": solve_leaves} if solve_leaves else {}),
-              **({"value_signs": value_signs} if value_signs != "reference" else {}))
+              **({"value_signs": value_signs} if value_signs != "reference" else {}), **_lib.proofs_kw(proofs))
     a = arena_batch(neural_network, old_neural_network, board_size, int(pairs), num_simulations, degree_exploration, seed=seed, **kw)
     b = arena_batch(old_neural_network, neural_network, board_size, int(pairs), num_simulations, degree_exploration, seed=seed,
                     first_game_id=int(pairs), **kw)
@@ -272,34 +276,36 @@ def paired_match(board_size, neural_network, old_neural_network, pairs, num_simu
 
 
 def self_play_match(board_size, neural_network, old_neural_network, total_games, num_simulations, degree_exploration, seed=0,
-                    leaves_per_step=1, solve_leaves=0, openings=None, value_signs="reference"):
+                    leaves_per_step=1, solve_leaves=0, openings=None, value_signs="reference", proofs=False):
     """main.py:110-134: total_games // 2 games with the new network as BLACK, the rest with it as WHITE.
     -> number of games the new network won (a drawn game goes to BLACK, like get_winning_player).
     solve_leaves=E > 0: both networks' searches take exact values for leaves with at most E empties (arena_batch).
     value_signs="sound": both networks' searches back their values up with the signs right across passes and finished boards (arena_batch).
+    proofs=True (needs value_signs="sound"): both searches keep exact values as proofs and back them up the tree (arena_batch).
     openings=(plies, opening_seed): paired_match over total_games // 2 openings instead (total_games must be even: a pair is two games); the
     return value is its `wins`, counted by the same rule, and self_play_match.stats holds its dict (None after a match without openings)."""
     solve_leaves = _lib.check_solve_leaves(solve_leaves)
     _lib.check_value_signs(value_signs)
+    _lib.check_proofs(proofs, value_signs)
     self_play_match.stats = None
     if openings is not None:
         _lib.check_openings(openings)
         if total_games % 2 or total_games < 2:
             raise ValueError(f"self_play_match with openings plays pairs of games: total_games must be even and >= 2 (got {total_games})")
         stats = paired_match(board_size, neural_network, old_neural_network, total_games // 2, num_simulations, degree_exploration, openings,
-                             seed=seed, leaves_per_step=leaves_per_step, solve_leaves=solve_leaves, **({"value_signs": value_signs} if value_signs != "reference" else {}))
+                             seed=seed, leaves_per_step=leaves_per_step, solve_leaves=solve_leaves, **({"value_signs": value_signs} if value_signs != "reference" else {}), **_lib.proofs_kw(proofs))
         self_play_match.stats = {k: v for k, v in stats.items() if k != "games"}
         return stats["wins"]
     as_black, as_white = total_games // 2, total_games // 2 + total_games % 2
     wins = 0
     if as_black:
         res = arena_batch(neural_network, old_neural_network, board_size, as_black, num_simulations, degree_exploration, seed=seed,
-                          leaves_per_step=leaves_per_step, **({"solve_leaves": solve_leaves} if solve_leaves else {}), **({"value_signs": value_signs} if value_signs != "reference" else {}))
+                          leaves_per_step=leaves_per_step, **({"solve_leaves": solve_leaves} if solve_leaves else {}), **({"value_signs": value_signs} if value_signs != "reference" else {}), **_lib.proofs_kw(proofs))
         wins += int((res["winner"] == 1).sum())
     if as_white:
         res = arena_batch(old_neural_network, neural_network, board_size, as_white, num_simulations, degree_exploration,
                           seed=seed, first_game_id=as_black, leaves_per_step=leaves_per_step, **({"solve_leaves": solve_leaves} if solve_leaves else {}),
-                          **({"value_signs": value_signs} if value_signs != "reference" else {}))
+                          **({"value_signs": value_signs} if value_signs != "reference" else {}), **_lib.proofs_kw(proofs))
         wins += int((res["winner"] == -1).sum())
     return wins
 
@@ -307,7 +313,7 @@ def self_play_match(board_size, neural_network, old_neural_network, total_games,
 def _selfplay_into_replay(replay, neural_network, board_size, num_episodes, num_simulations, degree_exploration, temperature, e_greedy, seed,
                           first_game_id, q_mode, visits, leaves_per_step, root_noise, sample_moves, alias_final_boards, policy_target,
                           target_temperature, endgame_targets=0, solve_leaves=0, playout_cap=None, forced_playouts=0.0, value_target="outcome",
-                          gumbel=None, surprise_weight=None, resign=None, value_signs="reference"):
+                          gumbel=None, surprise_weight=None, resign=None, value_signs="reference", proofs=False):
     """one iteration's games on the engine selfplay_batch would create, played to the end without reading a record, and their examples
     appended to the device buffer; -> (records appended, the endgame solver's statistics or None).  One-channel (BaseNN) examples are never
     aliased (examples_from_records).  endgame_targets > 0: SelfPlayEngine.solve_records before the append.  playout_cap: the engine's; the
@@ -325,7 +331,7 @@ def _selfplay_into_replay(replay, neural_network, board_size, num_episodes, num_
                          sample_moves=sample_moves, solve_leaves=solve_leaves, **({"playout_cap": playout_cap} if playout_cap is not None else {}),
                          **({"forced_playouts": forced_playouts} if forced_playouts else {}), **({"record_values": True} if vt_on else {}),
                          **({"gumbel": gumbel} if gumbel is not None else {}), **({"record_surprise": True} if surprise_weight is not None else {}),
-                         **({"resign": resign} if resign is not None else {}), **({"value_signs": value_signs} if value_signs != "reference" else {}))
+                         **({"resign": resign} if resign is not None else {}), **({"value_signs": value_signs} if value_signs != "reference" else {}), **_lib.proofs_kw(proofs))
     for _ in range(board_size * board_size):
         eng.run(4)
         if eng.stats()["live_games"] == 0:
@@ -335,6 +341,7 @@ def _selfplay_into_replay(replay, neural_network, board_size, num_episodes, num_
         training.rows_solved += eng.rows_solved()
     if resign is not None:
         training.resign_stats = eng.resign_stats()
+    training.proof_stats = eng.proof_stats() if proofs else None
     appended = replay.append_engine(eng, alias_final=alias_final_boards and getattr(neural_network, "in_channels", 2) == 2,
                                     policy_target=policy_target, target_temperature=target_temperature,
                                     **({"value_target": value_target, "exact_empties": endgame_targets} if vt_on else {}),
@@ -355,6 +362,11 @@ def _log_resign(i, num_iterations, stats):
                  stats["adjudicated_plies_sum"] / stats["games_adjudicated"] if stats["games_adjudicated"] else 0.0, stats["games_exempt"],
                  stats["exempt_triggered"], stats["exempt_wrong"],
                  '%.3f' % (stats["exempt_wrong"] / stats["exempt_triggered"]) if stats["exempt_triggered"] else 'n/a')
+
+
+def _log_proofs(i, num_iterations, stats):
+    logging.info('[%d/%d] proofs: %d edges proven / descents ended on a proven edge %d, on a proven node %d / %d roots proven', i, num_iterations,
+                 stats["edges_proven"], stats["edge_stops"], stats["node_stops"], stats["roots_proven"])
 
 
 def _fit_with_holdout(i, num_iterations, neural_network, replay, total_before, share):
@@ -395,7 +407,7 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
              distributed=False, batched_evaluation=False, policy_target="onehot", target_temperature=1.0, leaves_per_step=1,
              root_noise=None, sample_moves=None, replay="host", evaluation_opponent="random", endgame_targets=0,
              solve_leaves=0, match_openings=None, evaluation_openings=None, playout_cap=None, forced_playouts=None, eval_symmetry=None,
-             value_target="outcome", gumbel=None, surprise_weight=None, resign=None, validation_share=None, value_signs="reference"):
+             value_target="outcome", gumbel=None, surprise_weight=None, resign=None, validation_share=None, value_signs="reference", proofs=False):
     """main.py:56-259 on the GPU engines; returns `historic` = [(episodes done, win rate vs random), ...]
 
     validation_share=f in (0, 0.5] (None = off, the default: the loop is unchanged): held-out evaluation of every iteration's fit.  After an
@@ -496,6 +508,13 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
     a move that wins the game on the spot and flips every value that crosses a pass; the visit counts, root values, value
     targets, surprise and the resign rule all read those numbers.  Combines with every other option.  A drawn game stays +-1 in the records'
     z.  The drop-in evaluation agents stay without it ("Value signs"; tools/value_signs_bench.py).
+
+    proofs=True (needs value_signs="sound"; False = off, the default): every search of the batched engines keeps the exact values it meets --
+    finished boards, solved leaves -- as proofs, combines them at the parent (any winning move proves a win, all moves known proves their
+    maximum) and backs them up the path; a descent never picks a proven loss while something else is left, takes the exact value in place of
+    the averaged Q and stops at a proven position.  One setting serves self-play, the match and the batched evaluation.  The moves, visit rows
+    and root values read the raw statistics as before.  Not with gumbel or forced_playouts (ValueError).  training.proof_history keeps the
+    self-play engines' proof_stats() per iteration (with distributed=True: this rank's) ("Proofs"; tools/proofs_bench.py).
 
     match_openings=(plies, opening_seed) / evaluation_openings=(plies, opening_seed) (None = off, the default): the games of the new-vs-old
     match / of the batched evaluation start with random openings of `plies` plies instead of the one standard position, every opening played
@@ -598,7 +617,9 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
     training.match_history = []
     solve_leaves = _lib.check_solve_leaves(solve_leaves)
     _lib.check_value_signs(value_signs)
-    vs_kw = {"value_signs": value_signs} if value_signs != "reference" else {}
+    _lib.check_proofs(proofs, value_signs, gumbel=gumbel, forced_playouts=forced_playouts)
+    training.proof_history = []
+    vs_kw = dict({"value_signs": value_signs} if value_signs != "reference" else {}, **_lib.proofs_kw(proofs))
     training.rows_solved = 0
     endgame_targets = _lib.check_endgame_targets(endgame_targets, alias_final_boards)
     training.endgame_history = []
@@ -689,6 +710,9 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
             if resign is not None:
                 training.resign_history.append(training.resign_stats)
                 _log_resign(i, num_iterations, training.resign_stats)
+            if proofs:
+                training.proof_history.append(training.proof_stats)
+                _log_proofs(i, num_iterations, training.proof_stats)
             if surprise_weight is not None:
                 st = training.surprise_stats
                 training.surprise_history.append(st)
@@ -715,6 +739,7 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
                 eng.play_to_end(endgame_targets=endgame_targets, **vt_kw)               # each rank relabels its own records (and computes its targets)
                 training.rows_solved += eng.rows_solved() if solve_leaves else 0
                 resign_stats = eng.resign_stats() if resign is not None else None
+                proof_stats = eng.proof_stats() if proofs else None
                 records = pooled_selfplay_records(eng, device, with_visits=visits,      # the only exchange of the self-play phase
                                                   **({"with_values": True} if vt_on else {}))
                 endgame = getattr(eng, "endgame_stats", None)
@@ -728,11 +753,15 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
                                          **cap_kw, **vt_kw, **gumbel_kw, **resign_kw, **vs_kw)
                 training.rows_solved += selfplay_batch.rows_solved if solve_leaves else 0
                 resign_stats = selfplay_batch.resign_stats if resign is not None else None
+                proof_stats = selfplay_batch.proof_stats if proofs else None
                 endgame = getattr(selfplay_batch, "endgame_stats", None) if endgame_targets else None
             restore_eval_symmetry()
             if resign is not None:
                 training.resign_history.append(resign_stats)
                 _log_resign(i, num_iterations, resign_stats)
+            if proofs:
+                training.proof_history.append(proof_stats)
+                _log_proofs(i, num_iterations, proof_stats)
             if endgame is not None:
                 training.endgame_history.append(endgame)
                 _log_endgame(i, num_iterations, endgame)

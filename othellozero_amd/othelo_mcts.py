@@ -18,7 +18,7 @@ from .Othello import OthelloGame, OthelloPlayer
 
 class OthelloMCTS:
     def __init__(self, board_size, neural_network, degree_exploration, q_mode=_lib.QMODE_F64,
-                 node_cap=8192, leaves_per_step=1, solve_leaves=0, forced_playouts=None, gumbel=None, value_signs="reference"):
+                 node_cap=8192, leaves_per_step=1, solve_leaves=0, forced_playouts=None, gumbel=None, value_signs="reference", proofs=False):
         """q_mode: OZ_QMODE_F64 = the NumPy 1.18.5 promotion the reference pins (requirements.txt:19),
         OZ_QMODE_NEP50 = what NumPy >= 2 computes (SURVEY.md R-FP).
         leaves_per_step > 1 (native networks only, created with max_batch >= leaves_per_step): that many descents of the tree per
@@ -35,9 +35,14 @@ class OthelloMCTS:
         value_signs="sound": the backup negates a value once per change of the side to move, not once per level, and a finished board is worth
         the sign of its disc difference to the side to move there, a draw 0 (oz_mcts_set_value_signs; include/othellozero_amd.h, "value
         signs").  "reference" (the default) is the reference's rule, which stores the wrong sign for a move that ends the game and across every
-        pass.  Not the reference's search."""
+        pass.  Not the reference's search.
+        proofs=True (needs value_signs="sound"; native networks only): exact values -- finished boards, solved leaves -- are kept as proofs
+        and backed up the tree; the descent never picks a proven loss while something else is left, takes the exact value in place of the
+        averaged Q and stops at a proven position (oz_mcts_set_proofs; include/othellozero_amd.h, "proofs").  root_proof / dump_proofs /
+        proof_stats read them.  Not with gumbel or forced_playouts."""
         self.value_signs = value_signs
         vs_mode = _lib.check_value_signs(value_signs)
+        self.proofs = _lib.check_proofs(proofs, value_signs, gumbel=gumbel, forced_playouts=forced_playouts)
         self.gumbel = _lib.check_gumbel_options(gumbel, forced_playouts=forced_playouts, leaves_per_step=leaves_per_step)
         self.forced_playouts = _lib.check_forced_playouts(forced_playouts, need_noise=False)
         self._forced_set = False
@@ -56,6 +61,8 @@ class OthelloMCTS:
             raise ValueError(f"leaves_per_step must be 1 .. {_lib.MAX_LEAVES_PER_STEP} (got {leaves_per_step})")
         if self.leaves_per_step != 1 and not self._native:
             raise ValueError("leaves_per_step > 1 needs a native NNetWrapper / StubNetWrapper (the leaves are evaluated on the device)")
+        if self.proofs and not self._native:
+            raise ValueError("proofs=True needs a native NNetWrapper / StubNetWrapper (the leaves are evaluated on the device)")
         if self.solve_leaves and not self._native:
             raise ValueError("solve_leaves > 0 needs a native NNetWrapper / StubNetWrapper (the leaves are evaluated and solved on the device)")
         lib = _lib.require_gpu()
@@ -63,6 +70,8 @@ class OthelloMCTS:
         self._root = None
         if vs_mode:
             _lib.check(lib.oz_mcts_set_value_signs(self._h, vs_mode))
+        if self.proofs:
+            _lib.check(lib.oz_mcts_set_proofs(self._h, 1))
         if self.leaves_per_step != 1:
             _lib.check(lib.oz_mcts_set_leaves_per_step(self._h, self.leaves_per_step))
         if self.solve_leaves:
@@ -390,7 +399,45 @@ class OthelloMCTS:
             _lib.check(lib.oz_mcts_dump_node(self._h, 0, i, C.byref(own), C.byref(opp), C.byref(Ns), C.byref(legal),
                                              _lib.p_i32(N), _lib.p_f64(Q), _lib.p_u8(qt), _lib.p_f64(P)))
             out.append(dict(k0=own.value, k1=opp.value, Ns=Ns.value, legal=legal.value, N=N, Q=Q, qtag=qt, P=P))
+        if self.proofs:
+            for node, pr in zip(out, self.dump_proofs()):
+                node["proofs"] = pr
         return out
+
+    # ---- proofs (include/othellozero_amd.h, "proofs")
+    def _need_proofs(self):
+        if not self.proofs:
+            raise ValueError("this search was created without proofs=True")
+
+    def root_proof(self, state):
+        """(val, edge) of the mover-canonical `state`: val = its proven value -1 / 0 / +1 for the player to move or None, edge = int8 (64,) by
+        square with _lib.PROOF_UNKNOWN where nothing is proven.  KeyError if the state is unknown to the search."""
+        self._need_proofs()
+        own, opp = _lib.pack_board(state)
+        self._set_root(own, opp)
+        edge, val, rc = np.zeros((1, 64), np.int8), np.zeros(1, np.int8), np.zeros(1, np.int32)
+        _lib.check(_lib.load().oz_mcts_root_proofs(self._h, _lib.p_i8(edge), _lib.p_i8(val), _lib.p_i32(rc)))
+        if rc[0] != 0:
+            raise KeyError("state is unknown to the search")
+        return (None if val[0] == _lib.PROOF_UNKNOWN else int(val[0])), edge[0]
+
+    def dump_proofs(self):
+        """per node, in dump()'s order: dict(edge int8 (64,), value = the node's own value, val = val(S); _lib.PROOF_UNKNOWN = unknown)"""
+        self._need_proofs()
+        lib = _lib.load()
+        nn = np.zeros(1, np.int32)
+        _lib.check(lib.oz_mcts_num_nodes(self._h, _lib.p_i32(nn)))
+        out = []
+        for i in range(int(nn[0])):
+            edge, value, val = np.zeros(64, np.int8), C.c_int8(), C.c_int8()
+            _lib.check(lib.oz_mcts_dump_proofs(self._h, 0, i, _lib.p_i8(edge), C.byref(value), C.byref(val)))
+            out.append(dict(edge=edge, value=value.value, val=val.value))
+        return out
+
+    def proof_stats(self):
+        s = np.zeros(4, np.int64)
+        _lib.check(_lib.load().oz_mcts_proof_stats(self._h, _lib.p_i64(s)))
+        return dict(zip(_lib.PROOF_STATS, (int(x) for x in s)))
 
     def wide_stats(self):
         s = np.zeros(3, np.int64)

@@ -33,7 +33,7 @@ def training_example_symmetries(board, policy):
 def execute_episode(board_size, neural_network, degree_exploration, num_simulations, policy_temperature, e_greedy,
                     q_mode=_lib.QMODE_F64, snapshot_boards=False, policy_target="onehot", target_temperature=1.0,
                     leaves_per_step=1, root_noise=None, noise_seed=0, sample_moves=None, sample_seed=0, solve_leaves=0,
-                    forced_playouts=None, value_target="outcome", gumbel=None, gumbel_seed=0, value_signs="reference"):
+                    forced_playouts=None, value_target="outcome", gumbel=None, gumbel_seed=0, value_signs="reference", proofs=False):
     """training.py:26-72.  Returns [(board (n,n,2) bool, one-hot policy (n,n) float64, z int), ...], 8 per move.
 
     gumbel=(max_considered, c_visit, c_scale) or True: every move's search is a Gumbel root search of num_simulations simulations
@@ -70,8 +70,12 @@ def execute_episode(board_size, neural_network, degree_exploration, num_simulati
     move).  "outcome" is the function without it.
 
     value_signs="sound": the search backs its values up with the signs right across passes and finished boards (OthelloMCTS); "reference" is
-    the function without it."""
+    the function without it.
+
+    proofs=True (needs value_signs="sound"): the search keeps exact values as proofs and backs them up the tree (OthelloMCTS); not with
+    gumbel or forced_playouts."""
     _lib.check_value_signs(value_signs)
+    _lib.check_proofs(proofs, value_signs, gumbel=gumbel, forced_playouts=forced_playouts)
     vt_mode, _ = _lib.check_value_target(value_target, not snapshot_boards)
     root_values, movers, positions = [], [], []
     solve_leaves = _lib.check_solve_leaves(solve_leaves)
@@ -92,7 +96,7 @@ def execute_episode(board_size, neural_network, degree_exploration, num_simulati
     mcts = OthelloMCTS(board_size, neural_network, degree_exploration, q_mode=q_mode,
                        node_cap=num_simulations * (board_size * board_size - 3) + 64, leaves_per_step=leaves_per_step,
                        solve_leaves=solve_leaves, forced_playouts=forced_playouts, **({"gumbel": gumbel} if gumbel is not None else {}),
-                       **({"value_signs": value_signs} if value_signs != "reference" else {}))
+                       **({"value_signs": value_signs} if value_signs != "reference" else {}), **_lib.proofs_kw(proofs))
     # training.py:34-37 (BNN examples are one-channel boards, a fresh array per round: no aliasing for them)
     board_view_type = BoardView.ONE_CHANNEL if getattr(neural_network.network_type, "name", "") == "BNN" else BoardView.TWO_CHANNELS
 
@@ -193,7 +197,7 @@ class SelfPlayEngine:
                  policy_temperature=1.0, e_greedy=0.9, seed=1234, first_game_id=0, game_id_stride=0,
                  q_mode=_lib.QMODE_F64, refill=False, node_cap=0, record_cap=0, dedup=True, batch_cap=0, eval_cache=False,
                  record_visits=False, leaves_per_step=1, root_noise=None, sample_moves=None, solve_leaves=0, playout_cap=None,
-                 forced_playouts=None, record_values=False, gumbel=None, record_surprise=False, resign=None, value_signs="reference"):
+                 forced_playouts=None, record_values=False, gumbel=None, record_surprise=False, resign=None, value_signs="reference", proofs=False):
         """dedup: cross-game leaf de-duplication (a board several games reach in one batch is evaluated once; no record changes);
         batch_cap: leaves per network batch of the free-running driver (0 = none; see preferred_batch_cap);
         eval_cache: take (pi, v) of boards the network has evaluated before from its persistent cache (NNetWrapper.set_eval_cache) --
@@ -252,8 +256,14 @@ class SelfPlayEngine:
         negation per change of the side to move, a finished board worth the sign of its disc difference to the side to move there, a draw 0
         (oz_selfplay_set_value_signs).  "reference" (the default) is the reference's rule.  Every driver and every option; the root values,
         value targets, recorded surprise and the resign rule read what the search stores.  A drawn game stays +-1 (draw -> BLACK) in the
-        records' z (DESIGN.md, "Value signs")."""
+        records' z (DESIGN.md, "Value signs").
+        proofs=True (needs value_signs="sound"): every search keeps exact values -- finished boards, solved leaves, what was proven from
+        them -- as proofs and backs them up the tree; a descent never picks a proven loss while something else is left, takes the exact
+        value in place of the averaged Q and stops at a proven position (oz_selfplay_set_proofs).  run() / play_to_end() at any
+        leaves_per_step with every option but gumbel and forced_playouts (ValueError); run_steps() and stagger() then raise.  The moves, the
+        visit rows and the root values read the raw statistics as before.  proof_stats() counts ("Proofs")."""
         vs_mode = _lib.check_value_signs(value_signs)
+        proofs = _lib.check_proofs(proofs, value_signs, gumbel=gumbel, forced_playouts=forced_playouts)
         resign = _lib.check_resign(resign, gumbel=gumbel)
         if record_surprise and not (record_visits or gumbel):
             raise ValueError("record_surprise needs record_visits=True or gumbel=...: the surprise is that of a recorded policy target")
@@ -279,6 +289,9 @@ class SelfPlayEngine:
         self.value_signs = value_signs
         if vs_mode:
             _lib.check(lib.oz_selfplay_set_value_signs(self._h, vs_mode))
+        self.proofs = proofs
+        if proofs:
+            _lib.check(lib.oz_selfplay_set_proofs(self._h, 1))
         self.leaves_per_step = int(leaves_per_step)
         if self.leaves_per_step != 1:
             _lib.check(lib.oz_selfplay_set_leaves_per_step(self._h, self.leaves_per_step))
@@ -310,6 +323,13 @@ class SelfPlayEngine:
         self.resign = resign
         if resign is not None:
             _lib.check(lib.oz_selfplay_set_resign(self._h, *resign))
+
+    def proof_stats(self):
+        """dict(edges_proven, edge_stops, node_stops, roots_proven) over the engine's games so far: edges given a proof, descents ended on a
+        proven edge / on a proven node, roots whose value became known (zeros without proofs=True)"""
+        s = np.zeros(4, np.int64)
+        _lib.check(_lib.load().oz_selfplay_proof_stats(self._h, _lib.p_i64(s)))
+        return dict(zip(_lib.PROOF_STATS, (int(x) for x in s)))
 
     def resign_stats(self):
         """dict(v, r, min_ply, keep_prob, games_adjudicated, adjudicated_plies_sum, games_exempt, exempt_triggered, exempt_wrong,
@@ -646,8 +666,10 @@ def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations
                    policy_temperature=1.0, e_greedy=0.9, seed=1234, first_game_id=0, q_mode=_lib.QMODE_F64,
                    expand=False, alias_final=False, record_visits=False, target_temperature=1.0, leaves_per_step=1, root_noise=None,
                    sample_moves=None, endgame_targets=0, solve_leaves=0, playout_cap=None, forced_playouts=None, value_target="outcome", gumbel=None,
-                   surprise_weight=None, resign=None, value_signs="reference"):
+                   surprise_weight=None, resign=None, value_signs="reference", proofs=False):
     """Play num_games complete games; returns the move records (or the expanded examples).
+    proofs=True (needs value_signs="sound"): the searches keep exact values as proofs and back them up the tree (SelfPlayEngine);
+    selfplay_batch.proof_stats holds the last call's SelfPlayEngine.proof_stats() (None when off).
     value_signs="sound": the searches back their values up with the signs right across passes and finished boards (SelfPlayEngine).
     resign=(v, r, min_ply, keep_prob): resignation with a played-out audit share (SelfPlayEngine): a decided game stops early, its records
     carry the adjudicated z, the board at the stop as their final board (what alias_final=True then shows) and the flag
@@ -679,6 +701,8 @@ def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations
     the examples' float32 z; with expand it needs alias_final=False.  selfplay_batch.value_target_stats holds the last call's statistics
     (None when off)."""
     _lib.check_value_signs(value_signs)
+    _lib.check_proofs(proofs, value_signs, gumbel=gumbel, forced_playouts=forced_playouts)
+    selfplay_batch.proof_stats = None
     vt_on = _lib.check_value_target(value_target, expand and alias_final)[0] != _lib.VALUE_TARGET_OUTCOME
     gumbel = _lib.check_gumbel_options(gumbel, root_noise=root_noise, forced_playouts=forced_playouts, sample_moves=sample_moves,
                                        playout_cap=playout_cap, leaves_per_step=leaves_per_step)
@@ -705,7 +729,8 @@ def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations
                          root_noise=root_noise, sample_moves=sample_moves, solve_leaves=solve_leaves, playout_cap=playout_cap,
                          **({"forced_playouts": forced_playouts} if forced_playouts > 0.0 else {}), **({"record_values": True} if vt_on else {}),
                          **({"gumbel": gumbel} if gumbel is not None else {}), **({"record_surprise": True} if surprise_weight is not None else {}),
-                         **({"resign": resign} if resign is not None else {}), **({"value_signs": value_signs} if value_signs != "reference" else {}))
+                         **({"resign": resign} if resign is not None else {}), **({"value_signs": value_signs} if value_signs != "reference" else {}),
+                         **_lib.proofs_kw(proofs))
     selfplay_batch.surprise_stats = None
 
     def weighted(ret):
@@ -722,6 +747,7 @@ def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations
         selfplay_batch.value_target_stats = getattr(eng, "value_target_stats", None)
         selfplay_batch.forced_playout_stats = selfplay_batch.playout_stats = None
         selfplay_batch.rows_solved = eng.rows_solved() if solve_leaves else None
+        selfplay_batch.proof_stats = eng.proof_stats() if proofs else None
         return weighted(got)
     if vt_on:
         got = eng.play_to_end(with_visits=record_visits, endgame_targets=endgame_targets, value_target=value_target)
@@ -732,6 +758,7 @@ def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations
         selfplay_batch.playout_stats = eng.playout_stats() if playout_cap is not None else None
         selfplay_batch.resign_stats = eng.resign_stats() if resign is not None else None
         selfplay_batch.rows_solved = eng.rows_solved() if solve_leaves else None
+        selfplay_batch.proof_stats = eng.proof_stats() if proofs else None
         if expand:
             return expand_examples(rec, board_size, alias_final, visits=counts, target_temperature=target_temperature, values=targets)
         return weighted((rec, counts, targets) if record_visits else (rec, targets))
@@ -742,6 +769,7 @@ def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations
         selfplay_batch.playout_stats = eng.playout_stats() if playout_cap is not None else None
         selfplay_batch.resign_stats = eng.resign_stats() if resign is not None else None
         selfplay_batch.rows_solved = eng.rows_solved() if solve_leaves else None
+        selfplay_batch.proof_stats = eng.proof_stats() if proofs else None
         selfplay_batch.endgame_stats = getattr(eng, "endgame_stats", None)
         return expand_examples(rec, board_size, alias_final, visits=counts, target_temperature=target_temperature) if expand else weighted((rec, counts))
     rec = eng.play_to_end(endgame_targets=endgame_targets)
@@ -749,5 +777,6 @@ def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations
     selfplay_batch.playout_stats = eng.playout_stats() if playout_cap is not None else None
     selfplay_batch.resign_stats = eng.resign_stats() if resign is not None else None
     selfplay_batch.rows_solved = eng.rows_solved() if solve_leaves else None
+    selfplay_batch.proof_stats = eng.proof_stats() if proofs else None
     selfplay_batch.endgame_stats = getattr(eng, "endgame_stats", None)
     return expand_examples(rec, board_size, alias_final) if expand else rec
