@@ -545,7 +545,7 @@ int oz_playout_budgets(uint64_t seed, const uint64_t* game_ids, const int32_t* p
  *     exempt_trigger_ply_sum, and in exempt_wrong iff the natural winner (a draw goes to BLACK, as in oz_record.z) is not the remembered
  *     side: exempt_wrong / exempt_triggered is the rule's false-positive rate, the number v is tuned by.
  *   * keep_prob == 1: every game is exempt -- the bytes of the engine without the option, and the counters still measure the rule.
- *   * never touched: the arena, matches and evaluations, the bare oz_mcts.  pad[2] stays 0. */
+ *   * never touched: the arena, matches and evaluations, the bare oz_mcts.  pad[2] stays 0 (it is proof play's). */
 typedef struct {
     int64_t games_adjudicated;      /* games ended by the rule */
     int64_t adjudicated_plies_sum;  /* the plies those games were played for (their records) */
@@ -721,7 +721,8 @@ typedef struct {
                              * drawn by move sampling (oz_selfplay_set_move_sampling; ply < plies) */
     uint8_t pad[3];         /* pad[0]: 0 = the move was searched on the full budget, 1 = on the fast one ("playout cap" above: not a training
                              * example); always 0 without the option.  pad[1]: 1 = the game was adjudicated ("resignation" above: z and the final board are those
-                             * of the stop), else 0.  pad[2]: 0 */
+                             * of the stop), else 0.  pad[2]: the proof code of the move's root ("proof play" below: 1 loss, 2 draw, 3 win, for
+                             * the mover), 0 = unknown; always 0 without the option */
 } oz_record;
 
 typedef struct {
@@ -1038,6 +1039,57 @@ int oz_arena_set_value_signs(oz_arena* a, int black, int white);
 /* proofs of the BLACK (net_a) and WHITE (net_b) agent's search (see oz_mcts_set_proofs; an agent with proofs needs sound signs); before the
  * first run */
 int oz_arena_set_proofs(oz_arena* a, int black, int white);
+
+/* ------------------------------------------------------------------ proof play: play and record what a proven root knows (opt-in, on top of
+ * proofs; with nothing of it called every kernel, record, file and launch is what it was).  The search proves wins, draws and losses; without
+ * this option the move, the visit row and the root value still read the raw counts and the stored Q -- a move proven lost after it took most
+ * of the visits is played, trained towards and averaged in.  The rule, one definition for host and device (oz_proof_play, csrc/oz_common.h),
+ * over the root's proof entry (legal, lo, hi, own) and its raw counts cnt[64]:
+ *   val  = val(root) ("proofs" above); C = the candidates the descent picks from at the root: the edges that prove a known val, else the
+ *          edges not proven lost, else the legal set.
+ *   keep = C where a square of C has cnt > 0; else the legal set, counted as a fallback.  A root proven a loss keeps its whole row.
+ *   row[a] = cnt[a] on keep, 0 elsewhere: the recorded visit row, and what record_surprise measures.
+ *   move:  every branch that reads counts -- the arena's and temperature 0's arg-max with its tie draw, the first maximum, move sampling --
+ *          reads row and its maximum.  The explore branch of the e-greedy coin stays uniform over the legal set.
+ *   root value = (double)val where val is known, else the raw visit-weighted mean: what record_values logs and resignation reads.
+ *   proof code of a searched move = val + 2 (1 loss, 2 draw, 3 win, for the mover), 0 where unknown: byte pad[2] of the move's record.
+ * oz_selfplay_last_counts stays raw.  The option inherits the support matrix and the refusals of proofs and adds none but this: it needs
+ * proofs (OZ_ERR_STATE without them; switching proofs off under it is refused too). */
+/* the engine's moves, for oz_selfplay_run; before the first driver call (OZ_ERR_STATE afterwards) */
+int oz_selfplay_set_proof_play(oz_selfplay* sp, int enable);
+/* [0] searched moves on a proven root [1] moves whose row differs from the raw counts [2] moves whose action differs from the one the raw
+ * counts give (greedy and sampled moves; both are evaluated) [3] fallbacks.  Zeros on an engine without the option. */
+int oz_selfplay_proof_play_stats(oz_selfplay* sp, int64_t* out4);
+/* per agent (black for net_a's search, white for net_b's); needs that agent's proofs; before the first run */
+int oz_arena_set_proof_play(oz_arena* a, int black, int white);
+/* the bare search: oz_mcts_root_counts / oz_mcts_root_values with the rule's row and value (same shapes and rc); OZ_ERR_STATE on an object
+ * without proofs.  oz_mcts_root_counts and oz_mcts_root_values stay the raw ones. */
+int oz_mcts_proven_counts(oz_mcts* m, int32_t* counts /* [G][64] */, uint64_t* legal /* [G] */, int32_t* rc /* [G] */);
+int oz_mcts_proven_root_values(oz_mcts* m, double* value /* [G] */, int32_t* rc /* [G] */);
+/* oz_mcts_sample_moves over the rule's row and its maximum (same arguments, keys and rc) */
+int oz_mcts_proven_sample_moves(oz_mcts* m, double temperature, uint64_t seed, const uint64_t* game_ids, const int32_t* plies, int32_t* action,
+                                int32_t* rc);
+/* proof targets: the completed records [first_record, completed so far), in place, one wavefront per record: a record with pad[2] != 0 gets
+ * z = the proven sign for its mover; a proven draw follows z's convention (BLACK's win).  Idempotent.  Run it before
+ * oz_selfplay_solve_records, the value targets and the replay appends.  oz_proof_targets: the same pass over R records on the host. */
+typedef struct {
+    int64_t records;        /* records looked at */
+    int64_t proven;         /* of them, with a proof code */
+    int64_t z_changed;      /* of those, whose z was another sign */
+} oz_proof_target_stats;
+int oz_selfplay_proof_targets(oz_selfplay* sp, int64_t first_record, oz_proof_target_stats* stats /* optional */);
+int oz_proof_targets(oz_record* records, int64_t R, oz_proof_target_stats* stats /* optional */);
+/* oz_selfplay_value_targets / oz_value_targets with one more flag: exact_proven = 1 makes a record with a proof code exact like one with
+ * <= exact_empties empties (it restarts the TD chain; BLEND keeps its z).  The entries without the flag are these with 0, the same code. */
+int oz_selfplay_value_targets_x(oz_selfplay* sp, int64_t first_record, int mode, double param, int exact_empties, int exact_proven,
+                                oz_value_target_stats* stats /* optional */);
+int oz_value_targets_x(const oz_record* records, const double* values, int64_t R, int n, int mode, double param, int exact_empties,
+                       int exact_proven, float* out /* [R] */);
+/* the rule on the host, no device needed: edge[64] and own_value as oz_mcts_root_proofs / oz_mcts_dump_proofs give them (read on the legal
+ * squares; OZ_PROOF_UNKNOWN = none), counts[64] the raw counts (0 off the legal set).  Every output may be NULL. */
+int oz_search_proof_play(uint64_t legal, const int8_t* edge, int own_value, const int32_t* counts, int8_t* val, uint64_t* keep,
+                         int32_t* row /* [64] */, int* fallback, int* inconsistent);
+
 /* HIP-event timing of the two agents' tree kernels on the launch stream, slots of oz_selfplay_profile (0 select 1 leaf compaction 2 evaluator = all
  * network launches 3 expand + backup 4 move), summed over both searches; the networks' own kernels: oz_net_profile on net_a / net_b */
 int oz_arena_profile(oz_arena* a, int enable);

@@ -96,7 +96,11 @@ class ValueTargetStats(C.Structure):                                            
     _fields_ = [("records", C.c_int64), ("exact", C.c_int64), ("sign_changed", C.c_int64)]
 
 
-class Optimizer(C.Structure):                                                        # oz_optimizer
+class ProofTargetStats(C.Structure):                                                 # oz_proof_target_stats
+    _fields_ = [("records", C.c_int64), ("proven", C.c_int64), ("z_changed", C.c_int64)]
+
+
+class Optimizer(C.Structure):                                                       # oz_optimizer
     _fields_ = [
         ("l2", C.c_double), ("weight_decay", C.c_double), ("decay_mask", C.c_uint64), ("global_clipnorm", C.c_double),
         ("average_decay", C.c_double), ("schedule", C.c_int32), ("reserved", C.c_int32), ("warmup_steps", C.c_int64),
@@ -213,6 +217,14 @@ SIGNATURES = {
     "oz_mcts_dump_proofs": [_vp, C.c_int, C.c_int, _i8p, _i8p, _i8p], "oz_mcts_root_proofs": [_vp, _i8p, _i8p, _i32p],
     "oz_mcts_proof_stats": [_vp, _i64p], "oz_selfplay_set_proofs": [_vp, C.c_int], "oz_selfplay_proof_stats": [_vp, _i64p],
     "oz_arena_set_proofs": [_vp, C.c_int, C.c_int],
+    "oz_selfplay_set_proof_play": [_vp, C.c_int], "oz_selfplay_proof_play_stats": [_vp, _i64p],
+    "oz_selfplay_proof_targets": [_vp, C.c_int64, C.POINTER(ProofTargetStats)], "oz_proof_targets": [_vp, C.c_int64, C.POINTER(ProofTargetStats)],
+    "oz_arena_set_proof_play": [_vp, C.c_int, C.c_int],
+    "oz_mcts_proven_sample_moves": [_vp, C.c_double, C.c_uint64, _u64p, _i32p, _i32p, _i32p],
+    "oz_mcts_proven_counts": [_vp, _i32p, _u64p, _i32p],"oz_mcts_proven_root_values": [_vp, _f64p, _i32p],
+    "oz_selfplay_value_targets_x": [_vp, C.c_int64, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(ValueTargetStats)],
+    "oz_value_targets_x": [_vp, _f64p, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, _f32p],
+    "oz_search_proof_play": [C.c_uint64, _i8p, C.c_int, _i32p, _i8p, _u64p, _i32p, C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "oz_search_proof_value": [C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(C.c_int)],
     "oz_search_proof_candidates": [C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, _u64p, C.POINTER(C.c_int)],
     "oz_search_proof_backup": [_u8p, _i32p, C.c_int, C.c_int, _u64p, _u64p, _u64p, _i8p, _i32p, C.POINTER(C.c_int)],
@@ -726,6 +738,62 @@ def check_proofs_pair(proofs, value_signs):
 def proofs_kw(proofs):
     """the keyword to pass on: nothing where the option is off, so that callers without it see the calls they always saw"""
     return {"proofs": proofs} if (any(proofs) if isinstance(proofs, (tuple, list)) else proofs) else {}
+
+
+PROOF_PLAY_STATS = ("proven_roots", "rows_changed", "moves_changed", "fallbacks")     # oz_selfplay_proof_play_stats
+
+
+def check_proof_play(proof_play, proofs, what="proof_play"):
+    """proof_play=True | False (include/othellozero_amd.h, "proof play") -> bool; on needs proofs=True: ValueError otherwise, before the
+    library is touched"""
+    if not isinstance(proof_play, (bool, int, np.bool_)) or proof_play not in (0, 1):
+        raise ValueError(f"{what} must be True or False (got {proof_play!r})")
+    if proof_play and not proofs:
+        raise ValueError(f"{what}=True needs proofs=True: it plays and records what the proofs know")
+    return bool(proof_play)
+
+
+def check_proof_play_pair(proof_play, proofs):
+    """arena_batch(proof_play=flag or (black, white)) with proofs = the checked (black, white) pair -> (bool, bool)"""
+    if isinstance(proof_play, (tuple, list)):
+        if len(proof_play) != 2:
+            raise ValueError(f"proof_play must be one flag or (black, white) (got {proof_play!r})")
+        return check_proof_play(proof_play[0], proofs[0], "proof_play[black]"), check_proof_play(proof_play[1], proofs[1], "proof_play[white]")
+    if proof_play and proofs[0] != proofs[1]:
+        raise ValueError("proof_play=True with proofs on one agent: give proof_play=(black, white)")
+    p = check_proof_play(proof_play, proofs[0])
+    return p, p
+
+
+def check_proof_targets(proof_targets, proof_play):
+    """proof_targets=True | False -> bool; on needs proof_play=True (the records carry no proof code without it)"""
+    if not isinstance(proof_targets, (bool, int, np.bool_)) or proof_targets not in (0, 1):
+        raise ValueError(f"proof_targets must be True or False (got {proof_targets!r})")
+    if proof_targets and not proof_play:
+        raise ValueError("proof_targets=True needs proof_play=True: the records carry no proof code without it")
+    return bool(proof_targets)
+
+
+def proof_play_kw(proof_play):
+    """the keyword to pass on: nothing where the option is off, so that callers without it see the calls they always saw"""
+    return {"proof_play": proof_play} if (any(proof_play) if isinstance(proof_play, (tuple, list)) else proof_play) else {}
+
+
+def record_proven(records):
+    """the proven value of move records (RECORD_DTYPE) for the mover: int8 -1 / 0 / +1, PROOF_UNKNOWN where the record carries no proof
+    code (pad[2] == 0: the third spare byte of oz_record, always 0 without proof play)"""
+    code = np.asarray(records)["pad"][..., 2].astype(np.int16)
+    return np.where(code == 0, PROOF_UNKNOWN, code - 2).astype(np.int8)
+
+
+def proof_targets(records):
+    """oz_proof_targets on the host, in place: z of every record with a proof code becomes the proven sign -> dict(records, proven, z_changed)"""
+    records = np.asarray(records)
+    if records.dtype != RECORD_DTYPE or not records.flags.c_contiguous or not records.flags.writeable:
+        raise ValueError("proof_targets: a writeable contiguous RECORD_DTYPE array")
+    st = ProofTargetStats()
+    check(load().oz_proof_targets(records.ctypes.data_as(_vp), int(records.size), C.byref(st)))
+    return {"records": st.records, "proven": st.proven, "z_changed": st.z_changed}
 
 
 def check_endgame_targets(endgame_targets, alias_final_boards):

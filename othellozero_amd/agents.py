@@ -167,6 +167,22 @@ def rules_proof_backup(path, leaf_value):
     return edges, int(out3[0]), int(out3[1]), bool(out3[2]), bool(conflict.value)
 
 
+def rules_proof_play(legal, edge, own_value, counts):
+    """oz_search_proof_play: what a root's proofs leave of its raw counts, on the host (no GPU needed).  legal = the root's legal mask,
+    edge = 64 proofs by square (-1 / 0 / +1, None or _lib.PROOF_UNKNOWN = unknown), own_value = the root's own value or None, counts = its 64
+    raw visit counts (0 off the legal set).  -> dict(val: -1 / 0 / +1 or None; keep: the mask of the squares whose counts stay -- the
+    candidates of the descent at the root, or the legal set where none of them was visited; row: int32 (64,) the counts on keep, 0
+    elsewhere; fallback; inconsistent).  The rule the move kernels apply (include/othellozero_amd.h, "proof play")."""
+    e = np.array([_proof_in(None if x is None else x) for x in edge], np.int8)
+    cnt = np.ascontiguousarray(counts, dtype=np.int32).ravel()
+    if e.size != 64 or cnt.size != 64:
+        raise ValueError(f"rules_proof_play: 64 proofs and 64 counts (got {e.size} and {cnt.size})")
+    val, keep, row, fall, bad = C.c_int8(), C.c_uint64(), np.zeros(64, np.int32), C.c_int(), C.c_int()
+    _lib.check(_lib.load().oz_search_proof_play(int(legal), _lib.p_i8(e), _proof_in(own_value), _lib.p_i32(cnt), C.byref(val), C.byref(keep),
+                                                _lib.p_i32(row), C.byref(fall), C.byref(bad)))
+    return dict(val=_proof_out(val.value), keep=keep.value, row=row, fallback=bool(fall.value), inconsistent=bool(bad.value))
+
+
 def rules_prune_counts(N, Q, P, eta, legal, Ns, c, epsilon, k):
     """oz_forced_playouts_prune, policy target pruning over a batch of root rows, on the host (no GPU needed): N int32, Q, P, eta float64
     (count, 64) by square row*8+col, legal uint64 (count,), Ns int32 (count,) = the roots' stored statistics, their noise and visits; c, epsilon =
@@ -200,11 +216,12 @@ def rules_root_values(N, Q):
     return out
 
 
-def rules_value_targets(records, values, n, value_target, exact_empties=0):
+def rules_value_targets(records, values, n, value_target, exact_empties=0, exact_proven=False):
     """oz_value_targets: the value targets of move records (_lib.RECORD_DTYPE, any order; records of one game_id are one game) with their
     root values (float64 (R,)), on the host (no GPU needed) -> float32 (R,), target i for record i.  value_target = "outcome", ("blend", w)
     or ("td", lam); exact_empties=E > 0: a record with at most E empties keeps its z (an exact value of SelfPlayEngine.solve_records(E)) and
-    restarts the TD chain.  The function k_value_targets evaluates (include/othellozero_amd.h, "value targets")."""
+    restarts the TD chain.  exact_proven=True: a record with a proof code (_lib.record_proven; after _lib.proof_targets) does the same
+    (oz_value_targets_x).  The function k_value_targets evaluates (include/othellozero_amd.h, "value targets")."""
     mode, param = _lib.check_value_target(value_target)
     exact_empties = _lib.check_solve_empties(exact_empties, 0, "exact_empties")
     rec = np.ascontiguousarray(records, dtype=_lib.RECORD_DTYPE).ravel()
@@ -212,6 +229,10 @@ def rules_value_targets(records, values, n, value_target, exact_empties=0):
     if val.size != rec.size:
         raise ValueError(f"{val.size} root values for {rec.size} records")
     out = np.zeros(rec.size, np.float32)
+    if exact_proven:
+        _lib.check(_lib.load().oz_value_targets_x(rec.ctypes.data_as(C.c_void_p), _lib.p_f64(val), rec.size, int(n), mode, param, exact_empties,
+                                                  1, _lib.p_f32(out)))
+        return out
     _lib.check(_lib.load().oz_value_targets(rec.ctypes.data_as(C.c_void_p), _lib.p_f64(val), rec.size, int(n), mode, param, exact_empties,
                                             _lib.p_f32(out)))
     return out
@@ -410,17 +431,20 @@ class NeuralNetworkOthelloAgent(OthelloAgent):
     the first valid action with the largest policy entry."""
 
     def __init__(self, game, neural_network, num_simulations, degree_exploration, temperature=0,
-                 q_mode=_lib.QMODE_F64, leaves_per_step=1, solve_leaves=0, value_signs="reference", proofs=False):
+                 q_mode=_lib.QMODE_F64, leaves_per_step=1, solve_leaves=0, value_signs="reference", proofs=False, proof_play=False):
+        """proof_play=True (needs proofs=True): the move is the arg-max of the row the root's proofs keep (OthelloMCTS.proven_counts)"""
         solve_leaves = _lib.check_solve_leaves(solve_leaves)
         _lib.check_value_signs(value_signs)
         _lib.check_proofs(proofs, value_signs)
+        self.proof_play = _lib.check_proof_play(proof_play, proofs)
         super().__init__(game)
         self.neural_network, self.num_simulations, self.temperature = neural_network, num_simulations, 0
         side = game.board_size
         # an agent searches on its own turns only: about half the plies
         self.mcts = OthelloMCTS(side, neural_network, degree_exploration, q_mode=q_mode,
                                 node_cap=num_simulations * (side * side // 2) + 64, leaves_per_step=leaves_per_step,
-                                solve_leaves=solve_leaves, value_signs=value_signs, **_lib.proofs_kw(proofs))
+                                solve_leaves=solve_leaves, value_signs=value_signs, **_lib.proofs_kw(proofs),
+                                **_lib.proof_play_kw(self.proof_play))
 
     def play(self):
         game = self.game
@@ -428,7 +452,7 @@ class NeuralNetworkOthelloAgent(OthelloAgent):
         board = game.board(BoardView.TWO_CHANNELS)
         self.mcts.simulate_n(board, mover, self.num_simulations)
         canonical = board if mover == OthelloPlayer.BLACK else OthelloGame.invert_board(board)
-        policy = self.mcts.get_policy_action_probabilities(canonical, self.temperature)
+        policy = self.mcts.get_policy_action_probabilities(canonical, self.temperature, **({"proven": True} if self.proof_play else {}))
         best = None
         for action in game.get_valid_actions():               # max() keeps the FIRST maximum: strict '>' below
             if best is None or policy[tuple(action)] > policy[tuple(best)]:
@@ -451,7 +475,7 @@ def duel_between_agents(game, agent_1, agent_2):
 def arena_batch(net_a, net_b, board_size=8, num_games=512, num_simulations=800, degree_exploration=1.0, seed=0,
                 first_game_id=0, q_mode=_lib.QMODE_F64, node_cap=0, max_rounds=0, dedup=True, profile=False, eval_cache=False,
                 leaves_per_step=1, opponent=None, solve_leaves=0, openings=None, first_opening_id=0, opening_moves=None,
-                value_signs="reference", proofs=False):
+                value_signs="reference", proofs=False, proof_play=False):
     """num_games games of net_a (BLACK) vs net_b (WHITE), temperature 0, max-visit ties broken by the RNG_TIE
     stream keyed (seed, game id, ply).  One of the two may be None: RandomOthelloAgent plays that colour, or with
     opponent=("minimax", depth) / ("minimax", depth, "discs" | "weighted") the fixed-depth minimax (oz_arena_set_opponent; ties between its
@@ -471,6 +495,8 @@ def arena_batch(net_a, net_b, board_size=8, num_games=512, num_simulations=800, 
     OthelloMCTS, value_signs).
     proofs = True | False or (black, white): the agent's search keeps exact values as proofs and backs them up the tree (oz_arena_set_proofs;
     OthelloMCTS, proofs); an agent with proofs needs value_signs "sound".  The moves read the raw counts as before.
+    proof_play = True | False or (black, white): the agent's move is the arg-max -- ties as ever -- of the row its root's proofs keep
+    (oz_arena_set_proof_play; include/othellozero_amd.h, "proof play"); needs that agent's proofs.
     openings = (plies, opening_seed): every game first plays a random opening of `plies` plies (at most 16) without any search
     (oz_arena_set_openings, rules_random_openings); game slot g plays opening first_opening_id + g whatever seed and first_game_id are, so two
     arenas given the same (openings, first_opening_id) start from the same positions.  opening_moves = (moves uint8 (num_games, 16), n_plies int32
@@ -481,6 +507,7 @@ def arena_batch(net_a, net_b, board_size=8, num_games=512, num_simulations=800, 
     eb_, ew_ = _lib.check_solve_leaves_pair(solve_leaves)
     vb_, vw_ = _lib.check_value_signs_pair(value_signs)
     pb_, pw_ = _lib.check_proofs_pair(proofs, value_signs)
+    ppb_, ppw_ = _lib.check_proof_play_pair(proof_play, (pb_, pw_))
     kb, kw = (leaves_per_step, leaves_per_step) if np.isscalar(leaves_per_step) else leaves_per_step
     minimax = _lib.check_opponents(opponent, net_a is None, net_b is None)
     lib = _lib.require_gpu()
@@ -501,6 +528,8 @@ def arena_batch(net_a, net_b, board_size=8, num_games=512, num_simulations=800, 
             _lib.check(lib.oz_arena_set_value_signs(h, vb_, vw_))
         if pb_ or pw_:
             _lib.check(lib.oz_arena_set_proofs(h, int(pb_), int(pw_)))
+        if ppb_ or ppw_:
+            _lib.check(lib.oz_arena_set_proof_play(h, int(ppb_), int(ppw_)))
         if opening is not None and opening[0] == "random":
             _lib.check(lib.oz_arena_set_openings(h, opening[1], opening[2], opening[3]))
         elif opening is not None:

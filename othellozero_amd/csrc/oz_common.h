@@ -485,6 +485,21 @@ OZ_HD int oz_proof_backup(OzProof* const* pr, const int* sq, const unsigned char
     }
     return levels;
 }
+// proof play (include/othellozero_amd.h, "proof play"): what a root's proofs leave of its raw counts for the move, the policy row and the root
+// value.  `visited` = the squares with a raw count > 0.  -> val = oz_proof_value of the entry; *keep = the candidates the descent picks from at
+// the root (oz_proof_candidates of val) where one of them was visited, else the legal set with *fallback = 1.  The row is the raw count on
+// *keep and 0 elsewhere; the root value is (double)val where val is known; the proof code of the move is oz_proof_code(val).  A root proven
+// a loss keeps its whole row: every edge is a candidate.
+OZ_HD int oz_proof_play(uint64_t legal, uint64_t lo, uint64_t hi, int own, uint64_t visited, uint64_t* keep, int* fallback, int* inconsistent) {
+    const int val = oz_proof_value(legal, lo, hi, own);
+    const uint64_t c = oz_proof_candidates(legal, lo, hi, val, inconsistent);
+    *fallback = (c & visited) == 0;
+    *keep = *fallback ? legal : c;
+    return val;
+}
+OZ_HD int oz_proof_code(int val) { return val == OZ_PROOF_NONE ? 0 : val + 2; }       // 0 unknown, 1 loss, 2 draw, 3 win: for the mover
+// the sign a proof code gives oz_record.z (a draw follows z's convention: BLACK's win); code != 0
+OZ_HD int oz_proof_code_z(int code, int player) { return code == 3 ? 1 : code == 1 ? -1 : player == 1 ? 1 : -1; }
 
 // ---------------------------------------------------------------- root value and value targets
 // (include/othellozero_amd.h, "value targets").  The root value of a search: the visit-weighted mean of the root's Q, for the player to

@@ -2587,6 +2587,157 @@ OZ_API int oz_mcts_pruned_counts(oz_mcts* m, int32_t* counts, uint64_t* legal, i
     OZ_HIP(hipStreamSynchronize(m->stream));
     return OZ_OK;
 }
+// ---- proof play on the bare search ("proof play" in the header): the rows and root values a proven root leaves (oz_proof_play, oz_common.h)
+// k_root_counts with the rule's row: the raw count on the kept squares, 0 elsewhere
+__global__ __launch_bounds__(64) void k_proven_counts(MctsDev t, int32_t* counts, uint64_t* legal_out, int32_t* rc_out) {
+    const int g = blockIdx.x, lane = threadIdx.x;
+    const uint64_t own = uni64(t.root_own[g]), opp = uni64(t.root_opp[g]);
+    const uint64_t legal = oz_legal(own, opp, t.valid);
+    const int node = root_lookup(t, g, own, opp, lane);
+    int cnt = 0, rc = 0;
+    if (node < 0) rc = 1;
+    else if (*rec_Ns(t, g, node) == 0) rc = 2;
+    else if ((legal >> lane) & 1)
+        cnt = (int)(rec_edge(t, g, node, oz_popc(legal & ((1ULL << lane) - 1ULL)))->n_tag & ~OZ_TAG_F32);
+    rc = unii(rc);
+    if (rc == 0) {
+        const OzProof* pe = t.pf.entry + (size_t)g * t.node_cap + node;
+        uint64_t keep;
+        int fall, bad;
+        oz_proof_play(uni64(pe->legal), uni64(pe->lo), uni64(pe->hi), unii(pe->own), __ballot(cnt > 0), &keep, &fall, &bad);
+        if (!((keep >> lane) & 1)) cnt = 0;
+    }
+    counts[(size_t)g * 64 + lane] = cnt;
+    if (lane == 0) { legal_out[g] = legal; rc_out[g] = rc; }
+}
+// k_root_values with the rule's value: the exact one where the root's value is known, else the raw mean
+__global__ __launch_bounds__(64) void k_proven_root_values(MctsDev t, double* value_out, int32_t* rc_out) {
+    __shared__ double terms[64];
+    const int g = blockIdx.x, lane = threadIdx.x;
+    const uint64_t own = uni64(t.root_own[g]), opp = uni64(t.root_opp[g]);
+    const uint64_t legal = oz_legal(own, opp, t.valid);
+    const int node = root_lookup(t, g, own, opp, lane);
+    int cnt = 0, rc = 0;
+    double q = 0.0;
+    if (node < 0) rc = 1;
+    else if (*rec_Ns(t, g, node) == 0) rc = 2;
+    else if ((legal >> lane) & 1) {
+        const OzEdge* e = rec_edge(t, g, node, oz_popc(legal & ((1ULL << lane) - 1ULL)));
+        cnt = (int)(e->n_tag & ~OZ_TAG_F32);
+        q = e->q;
+    }
+    rc = unii(rc);
+    terms[lane] = oz_root_term(cnt, q);
+    const int total = wave_sum_i32(cnt);
+    wave_sync();
+    int vrc = 0;
+    double v = oz_root_mean(terms, (long long)total, &vrc);
+    if (rc == 0) {
+        const OzProof* pe = t.pf.entry + (size_t)g * t.node_cap + node;
+        const int val = oz_proof_value(uni64(pe->legal), uni64(pe->lo), uni64(pe->hi), unii(pe->own));
+        if (val != OZ_PROOF_NONE) { v = (double)val; vrc = 0; }
+    }
+    if (lane == 0) { value_out[g] = rc == 0 ? v : 0.0; rc_out[g] = rc == 0 ? vrc : rc; }
+}
+// k_sample_moves over the rule's row and its maximum (the drop-in path's sampled move under proof play)
+static int sample_check(const char* fn, double temperature);
+__global__ __launch_bounds__(64) void k_proven_sample_moves(MctsDev t, double temperature, uint64_t seed, const uint64_t* __restrict__ game_ids,
+                                                            const int* __restrict__ plies, int32_t* action_out, int32_t* rc_out) {
+    const int g = blockIdx.x, lane = threadIdx.x;
+    const uint64_t own = uni64(t.root_own[g]), opp = uni64(t.root_opp[g]);
+    const uint64_t legal = oz_legal(own, opp, t.valid);
+    const int node = root_lookup(t, g, own, opp, lane);
+    int cnt = 0, rc = 0, action = -1;
+    if (node < 0) rc = 1;
+    else if (*rec_Ns(t, g, node) == 0) rc = 2;
+    else if ((legal >> lane) & 1)
+        cnt = (int)(rec_edge(t, g, node, oz_popc(legal & ((1ULL << lane) - 1ULL)))->n_tag & ~OZ_TAG_F32);
+    rc = unii(rc);
+    if (rc == 0) {
+        const OzProof* pe = t.pf.entry + (size_t)g * t.node_cap + node;
+        uint64_t keep;
+        int fall, bad;
+        oz_proof_play(uni64(pe->legal), uni64(pe->lo), uni64(pe->hi), unii(pe->own), __ballot(cnt > 0), &keep, &fall, &bad);
+        if (!((keep >> lane) & 1)) cnt = 0;
+    }
+    const int mx = unii(wave_max_i32(cnt));
+    if (rc == 0 && mx >= 1 && t.active[g])
+        action = sample_move(cnt, legal, mx, temperature, oz_rng_unit(oz_rng(seed, uni64(game_ids[g]), (uint64_t)unii(plies[g]), OZ_RNG_SAMPLE)), lane);
+    if (lane == 0) { action_out[g] = action; rc_out[g] = rc; }
+}
+OZ_API int oz_mcts_proven_sample_moves(oz_mcts* m, double temperature, uint64_t seed, const uint64_t* game_ids, const int32_t* plies, int32_t* action, int32_t* rc) {
+    OZ_REQUIRE(m && game_ids && plies && action && rc, "null argument");
+    if (int r = sample_check("oz_mcts_proven_sample_moves", temperature)) return r;
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (!m->proofs) { oz_set_error("oz_mcts_proven_sample_moves: the object keeps no proofs (oz_mcts_set_proofs)"); return OZ_ERR_STATE; }
+    hipSetDevice(m->device);
+    const int G = m->d.G;
+    for (int i = 0; i < G; ++i) OZ_REQUIRE(plies[i] >= 0, "oz_mcts_proven_sample_moves: plies[%d] = %d", i, plies[i]);
+    if (int r = stage_keys(m, game_ids, plies)) return r;
+    int32_t* da = m->rc_counts; int32_t* dr = m->rc_rc;           // (the staging of oz_mcts_root_counts: [G][64] and [G])
+    hipLaunchKernelGGL(k_proven_sample_moves, dim3(G), dim3(64), 0, m->stream, m->d, temperature, seed, (const uint64_t*)m->noise_ids, (const int*)m->noise_plies, da, dr);
+    OZ_HIP(hipGetLastError());
+    OZ_HIP(hipMemcpyAsync(action, da, 4ull * G, hipMemcpyDeviceToHost, m->stream));
+    OZ_HIP(hipMemcpyAsync(rc, dr, 4ull * G, hipMemcpyDeviceToHost, m->stream));
+    OZ_HIP(hipStreamSynchronize(m->stream));
+    return OZ_OK;
+}
+OZ_API int oz_mcts_proven_counts(oz_mcts* m, int32_t* counts, uint64_t* legal, int32_t* rc) {
+    OZ_REQUIRE(m && counts && legal && rc, "null argument");
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (!m->proofs) { oz_set_error("oz_mcts_proven_counts: the object keeps no proofs (oz_mcts_set_proofs)"); return OZ_ERR_STATE; }
+    hipSetDevice(m->device);
+    const int G = m->d.G;
+    int32_t* dc = m->rc_counts; uint64_t* dl = m->rc_legal; int32_t* dr = m->rc_rc;
+    hipLaunchKernelGGL(k_proven_counts, dim3(G), dim3(64), 0, m->stream, m->d, dc, dl, dr);
+    OZ_HIP(hipGetLastError());
+    OZ_HIP(hipMemcpyAsync(counts, dc, 4ull * G * 64, hipMemcpyDeviceToHost, m->stream));
+    OZ_HIP(hipMemcpyAsync(legal, dl, 8ull * G, hipMemcpyDeviceToHost, m->stream));
+    OZ_HIP(hipMemcpyAsync(rc, dr, 4ull * G, hipMemcpyDeviceToHost, m->stream));
+    OZ_HIP(hipStreamSynchronize(m->stream));
+    return OZ_OK;
+}
+OZ_API int oz_mcts_proven_root_values(oz_mcts* m, double* value, int32_t* rc) {
+    OZ_REQUIRE(m && value && rc, "null argument");
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (!m->proofs) { oz_set_error("oz_mcts_proven_root_values: the object keeps no proofs (oz_mcts_set_proofs)"); return OZ_ERR_STATE; }
+    hipSetDevice(m->device);
+    const int G = m->d.G;
+    double* dv = reinterpret_cast<double*>(m->rc_legal);          // (the staging of oz_mcts_root_counts: [G] 8-byte words and [G] codes)
+    int32_t* dr = m->rc_rc;
+    hipLaunchKernelGGL(k_proven_root_values, dim3(G), dim3(64), 0, m->stream, m->d, dv, dr);
+    OZ_HIP(hipGetLastError());
+    OZ_HIP(hipMemcpyAsync(value, dv, 8ull * G, hipMemcpyDeviceToHost, m->stream));
+    OZ_HIP(hipMemcpyAsync(rc, dr, 4ull * G, hipMemcpyDeviceToHost, m->stream));
+    OZ_HIP(hipStreamSynchronize(m->stream));
+    return OZ_OK;
+}
+// oz_proof_play of one root, on the host: needs no device.  edge[sq] = -1 / 0 / +1 or OZ_PROOF_UNKNOWN as oz_mcts_root_proofs gives them
+// (read on the legal squares), own_value likewise; counts = the root's 64 raw counts.
+OZ_API int oz_search_proof_play(uint64_t legal, const int8_t* edge, int own_value, const int32_t* counts, int8_t* val, uint64_t* keep, int32_t* row,
+                                int* fallback, int* inconsistent) {
+    OZ_REQUIRE(edge && counts, "oz_search_proof_play: null argument");
+    OZ_REQUIRE(own_value == OZ_PROOF_NONE || (own_value >= -1 && own_value <= 1), "oz_search_proof_play: own_value = %d", own_value);
+    uint64_t lo = 0, hi = 0, visited = 0;
+    for (int sq = 0; sq < 64; ++sq) {
+        OZ_REQUIRE(counts[sq] >= 0, "oz_search_proof_play: counts[%d] = %d", sq, counts[sq]);
+        if (counts[sq] > 0) visited |= 1ULL << sq;
+        if (!((legal >> sq) & 1) || edge[sq] == OZ_PROOF_NONE) continue;
+        OZ_REQUIRE(edge[sq] >= -1 && edge[sq] <= 1, "oz_search_proof_play: edge[%d] = %d", sq, (int)edge[sq]);
+        oz_proof_mark(&lo, &hi, sq, edge[sq]);
+    }
+    OZ_REQUIRE((visited & ~legal) == 0, "oz_search_proof_play: a count off the legal set");
+    uint64_t k;
+    int f, bad;
+    const int v = oz_proof_play(legal, lo, hi, own_value, visited, &k, &f, &bad);
+    if (val) *val = (int8_t)v;
+    if (keep) *keep = k;
+    if (fallback) *fallback = f;
+    if (inconsistent) *inconsistent = bad;
+    if (row) for (int sq = 0; sq < 64; ++sq) row[sq] = ((k >> sq) & 1) ? counts[sq] : 0;
+    return OZ_OK;
+}
+
 // oz_forced_prune over `count` rows, on the host: needs no device
 OZ_API int oz_forced_playouts_prune(const int32_t* N, const double* Q, const double* P, const double* eta, const uint64_t* legal, const int32_t* Ns,
                                     int64_t count, double c, double eps, double k, int32_t* pruned) {
@@ -2860,13 +3011,24 @@ struct ResignPlay {
 // (calls, not inlined code: a 64-term pairwise_sum of constant length is unrolled into 64 loads in flight, 128 VGPRs; inlined into the move
 // they cost the free-running advance a wave of occupancy for all of its simulations, and the sums run once per move)
 __device__ __noinline__ double surprise_row_sum(const double* a) { return pairwise_sum(a, 64); }
+// PROVEN (an engine or an arena agent with proof play, oz_selfplay_set_proof_play / oz_arena_set_proof_play; "proof play" in the header; on top
+// of proofs, lock-step rounds only): the move loads the root's proof entry -- one 32-byte wave-uniform load -- and applies oz_proof_play
+// (oz_common.h): `row` is the raw count on the kept squares, and everything that reads `row` -- log_counts / visits, SURPRISE, and here every
+// branch of the move that reads counts -- reads it and its maximum; rootv is the exact value where it is known (VALUES logs it, RESIGN reads it);
+// the proof code goes into the move log and from there into byte pad[2] of the game's records.  The explore branch of the coin stays uniform
+// over the legal set and last_counts stays raw.  Instantiations of its own (k_sp_move_p*): every other kernel stays the code it was.
+struct ProofPlay {
+    uint8_t* log;                          // [G][64 plies] the proof code of every ply of the game in progress; null in the arena
+    unsigned long long* stat;              // [4] proven roots, rows changed, moves changed, fallbacks; null in the arena
+};
 __device__ __noinline__ double surprise_sum(const double* term) { return oz_surprise_sum(term); }
 template <bool NOISE = false, bool SAMPLE = false, bool CAP = false, bool FORCE = false, bool VALUES = false, bool GUMBEL = false, bool SURPRISE = false,
-          bool RESIGN = false>
+          bool RESIGN = false, bool PROVEN = false>
 __device__ __forceinline__ void sp_move_body(const GamesDev& gm, const MctsDev& t, int g, int lane, int arena, MoveSampling ms = MoveSampling{},
                                              PlayoutCap pc = PlayoutCap{}, ForcedPlayouts fp = ForcedPlayouts{}, GumbelPlay gp = GumbelPlay{},
-                                             SurprisePlay su = SurprisePlay{}, ResignPlay rs = ResignPlay{}) {
+                                             SurprisePlay su = SurprisePlay{}, ResignPlay rs = ResignPlay{}, ProofPlay pp = ProofPlay{}) {
     static_assert(!RESIGN || VALUES, "resignation reads the root value the VALUES move computes");
+    static_assert(!PROVEN || !GUMBEL, "proofs and the Gumbel search exclude each other");
     if (!t.active[g]) return;
     bool prune = false;
     (void)prune;
@@ -2883,6 +3045,15 @@ __device__ __forceinline__ void sp_move_body(const GamesDev& gm, const MctsDev& 
     int cnt = 0;
     if (is_legal) cnt = (int)(rec_edge(t, g, node, oz_popc(legal & ((1ULL << lane) - 1ULL)))->n_tag & ~OZ_TAG_F32);
     gm.last_counts[(size_t)g * 64 + lane] = cnt;
+    // proof play: the root's proof entry and what it keeps of the counts (oz_proof_play, oz_common.h); every value is wave-uniform
+    int pval = OZ_PROOF_NONE, pfall = 0;
+    uint64_t pkeep = legal;
+    (void)pval; (void)pfall; (void)pkeep;
+    if constexpr (PROVEN) {
+        const OzProof* pe = t.pf.entry + (size_t)g * t.node_cap + node;
+        int pbad;
+        pval = oz_proof_play(uni64(pe->legal), uni64(pe->lo), uni64(pe->hi), unii(pe->own), __ballot(cnt > 0), &pkeep, &pfall, &pbad);
+    }
     // record_values: the root value of this search from the RAW counts and the stored Q (oz_root_term / oz_root_mean, oz_common.h)
     double rootv = 0.0;
     (void)rootv;
@@ -2895,6 +3066,7 @@ __device__ __forceinline__ void sp_move_body(const GamesDev& gm, const MctsDev& 
             int vrc;
             rootv = oz_root_mean(terms, (long long)total, &vrc);
             wave_sync();                                         // the next move of this wave (free-running loop) writes terms[] again
+            if constexpr (PROVEN) { if (pval != OZ_PROOF_NONE) rootv = (double)pval; }
         }
     }
     const int ply = unii(gm.ply[g]);
@@ -2912,6 +3084,11 @@ __device__ __forceinline__ void sp_move_body(const GamesDev& gm, const MctsDev& 
                 atomicAdd(&fp.stat[2], (unsigned long long)kept);
             }
         }
+    }
+    int mcnt = cnt, mmx = mx;                                    // what the move reads: the raw counts, or under PROVEN the row and its maximum
+    if constexpr (PROVEN) {
+        row = ((pkeep >> lane) & 1) ? cnt : 0;
+        mcnt = row; mmx = unii(wave_max_i32(row));
     }
     float gpi = 0.0f;                                            // this lane's entry of the improved policy row
     int gmove = -1;
@@ -2947,12 +3124,12 @@ __device__ __forceinline__ void sp_move_body(const GamesDev& gm, const MctsDev& 
     int action, greedy = 1;
     if (arena || gm.temperature == 0.0) {
         // bests = argwhere(p == p.max()) over the whole board; random.choice(bests) -> RNG_TIE stream
-        const uint64_t bests = __ballot(is_legal && cnt == mx);
+        const uint64_t bests = __ballot(is_legal && mcnt == mmx);
         const int nbests = oz_popc(bests);
         action = oz_kth_bit(bests, (int)(oz_rng(gm.seed, gid, (uint64_t)ply, OZ_RNG_TIE) % (uint64_t)nbests));
     } else {
         // N**(1/T) / sum is monotone in N: argwhere(policy == policy.max())[0] = first max-visit square
-        action = oz_ctz(__ballot(is_legal && cnt == mx));
+        action = oz_ctz(__ballot(is_legal && mcnt == mmx));
     }
     if constexpr (GUMBEL) {
         if (gmove >= 0) { action = gmove; greedy = 3; }
@@ -2965,8 +3142,31 @@ __device__ __forceinline__ void sp_move_body(const GamesDev& gm, const MctsDev& 
         } else if constexpr (SAMPLE) {
             if (ply < ms.plies) {
                 greedy = 2;
-                action = sample_move(cnt, legal, mx, ms.temperature, oz_rng_unit(oz_rng(gm.seed, gid, (uint64_t)ply, OZ_RNG_SAMPLE)), lane);
+                action = sample_move(mcnt, legal, mmx, ms.temperature, oz_rng_unit(oz_rng(gm.seed, gid, (uint64_t)ply, OZ_RNG_SAMPLE)), lane);
             }
+        }
+    }
+    // proof play: the proof code of the move, and the counters -- the move the raw counts give is evaluated beside the one played
+    int pcode = 0;
+    (void)pcode;
+    if constexpr (PROVEN) {
+        pcode = oz_proof_code(pval);
+        const bool row_changed = __ballot(row != cnt) != 0;
+        bool move_changed = false;
+        if (row_changed && greedy != 0) {
+            int raw;
+            if (greedy == 2) raw = sample_move(cnt, legal, mx, ms.temperature, oz_rng_unit(oz_rng(gm.seed, gid, (uint64_t)ply, OZ_RNG_SAMPLE)), lane);
+            else if (arena || gm.temperature == 0.0) {
+                const uint64_t bests = __ballot(is_legal && cnt == mx);
+                raw = oz_kth_bit(bests, (int)(oz_rng(gm.seed, gid, (uint64_t)ply, OZ_RNG_TIE) % (uint64_t)oz_popc(bests)));
+            } else raw = oz_ctz(__ballot(is_legal && cnt == mx));
+            move_changed = raw != action;
+        }
+        if (lane == 0 && pp.stat) {
+            if (pcode) atomicAdd(&pp.stat[0], 1ULL);
+            if (row_changed) atomicAdd(&pp.stat[1], 1ULL);
+            if (move_changed) atomicAdd(&pp.stat[2], 1ULL);
+            if (pfall) atomicAdd(&pp.stat[3], 1ULL);
         }
     }
     uint64_t black = uni64(gm.black[g]), white = uni64(gm.white[g]);
@@ -2975,6 +3175,7 @@ __device__ __forceinline__ void sp_move_body(const GamesDev& gm, const MctsDev& 
         gm.log_black[lb + ply] = black; gm.log_white[lb + ply] = white;
         gm.log_action[lb + ply] = (uint8_t)action; gm.log_player[lb + ply] = (int8_t)player;
         gm.log_greedy[lb + ply] = (uint8_t)greedy;
+        if constexpr (PROVEN) { if (pp.log) pp.log[lb + ply] = (uint8_t)pcode; }
     }
     int fast = 0;
     (void)fast;
@@ -3045,6 +3246,7 @@ __device__ __forceinline__ void sp_move_body(const GamesDev& gm, const MctsDev& 
                 r.pad[0] = r.pad[1] = r.pad[2] = 0;
                 if constexpr (CAP) { if (pc.fast_sims > 0) r.pad[0] = cur ? (uint8_t)fast : pc.log_fast[lb + lane]; }
                 if constexpr (RESIGN) { if (adjudicated) r.pad[1] = 1; }
+                if constexpr (PROVEN) { if (pp.log) r.pad[2] = cur ? (uint8_t)pcode : pp.log[lb + lane]; }
                 gm.records[base + lane] = r;
             } else atomicOr(t.error_flag, EF_RECORDS);
         }
@@ -3125,6 +3327,23 @@ __global__ __launch_bounds__(64) void k_sp_move_r(GamesDev gm, MctsDev t, MoveSa
 }
 __global__ __launch_bounds__(64) void k_sp_move_rs(GamesDev gm, MctsDev t, MoveSampling ms, PlayoutCap pc, ForcedPlayouts fp, SurprisePlay su, ResignPlay rs) {
     sp_move_body<false, true, true, true, true, false, true, true>(gm, t, blockIdx.x, threadIdx.x, 0, ms, pc, fp, GumbelPlay{}, su, rs);
+}
+// (the *p kernels: k_sp_move_f, _fs, _r and _rs whose move plays and records what a proven root knows, launched by engines with
+// oz_selfplay_set_proof_play; k_sp_move_pa: k_sp_move of an arena agent with oz_arena_set_proof_play)
+__global__ __launch_bounds__(64) void k_sp_move_p(GamesDev gm, MctsDev t, MoveSampling ms, PlayoutCap pc, ForcedPlayouts fp, ProofPlay pp) {
+    sp_move_body<false, true, true, true, true, false, false, false, true>(gm, t, blockIdx.x, threadIdx.x, 0, ms, pc, fp, GumbelPlay{}, SurprisePlay{}, ResignPlay{}, pp);
+}
+__global__ __launch_bounds__(64) void k_sp_move_ps(GamesDev gm, MctsDev t, MoveSampling ms, PlayoutCap pc, ForcedPlayouts fp, SurprisePlay su, ProofPlay pp) {
+    sp_move_body<false, true, true, true, true, false, true, false, true>(gm, t, blockIdx.x, threadIdx.x, 0, ms, pc, fp, GumbelPlay{}, su, ResignPlay{}, pp);
+}
+__global__ __launch_bounds__(64) void k_sp_move_pr(GamesDev gm, MctsDev t, MoveSampling ms, PlayoutCap pc, ForcedPlayouts fp, ResignPlay rs, ProofPlay pp) {
+    sp_move_body<false, true, true, true, true, false, false, true, true>(gm, t, blockIdx.x, threadIdx.x, 0, ms, pc, fp, GumbelPlay{}, SurprisePlay{}, rs, pp);
+}
+__global__ __launch_bounds__(64) void k_sp_move_prs(GamesDev gm, MctsDev t, MoveSampling ms, PlayoutCap pc, ForcedPlayouts fp, SurprisePlay su, ResignPlay rs, ProofPlay pp) {
+    sp_move_body<false, true, true, true, true, false, true, true, true>(gm, t, blockIdx.x, threadIdx.x, 0, ms, pc, fp, GumbelPlay{}, su, rs, pp);
+}
+__global__ __launch_bounds__(64) void k_sp_move_pa(GamesDev gm, MctsDev t) {
+    sp_move_body<false, false, false, false, false, false, false, false, true>(gm, t, blockIdx.x, threadIdx.x, 1);
 }
 
 // ---------------------------------------------------------------- free-running self-play step
@@ -3369,6 +3588,10 @@ struct oz_selfplay {
     uint8_t* first_sym = nullptr;
     long long* d_sw = nullptr;       // ... and its five counters
     ResignPlay resign{0.0, 0.0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr};      // oz_selfplay_set_resign: r > 0 = on (the buffers stay once allocated)
+    // oz_selfplay_set_proof_play (the arena: oz_arena_set_proof_play, [0] BLACK's agent, [1] WHITE's): the buffers stay once allocated
+    bool proof_play = false, arena_proof_play[2] = {false, false};
+    ProofPlay pplay{nullptr, nullptr};
+    long long* d_pt = nullptr;       // oz_selfplay_proof_targets: its three counters (allocated by the first call)
     template <typename T> int alloc(T** p, size_t count) {
         OZ_HIP(hipMalloc((void**)p, sizeof(T) * (count ? count : 1)));
         allocs.push_back(*p);
@@ -3494,7 +3717,13 @@ static int selfplay_round_async(oz_selfplay* sp, int sims, int stagger_round) {
         }
     } else if (int rc = mcts_steps_async(m, sp->net, sims, G, true, capped ? &ck : nullptr)) return rc;
     timed(m, TS_MOVE, m->profile, [&] {
-        if (sp->resign.r > 0 && sp->su.log) hipLaunchKernelGGL(k_sp_move_rs, dim3(G), dim3(64), 0, s, sp->gm, m->d, sp->sample, capped ? sp->cap : PlayoutCap{0, 0.0, nullptr, nullptr}, sp->forced, sp->su, sp->resign);
+        const PlayoutCap pcap = capped ? sp->cap : PlayoutCap{0, 0.0, nullptr, nullptr};
+        const bool pplay = sp->proof_play && m->proofs;
+        if (pplay && sp->resign.r > 0 && sp->su.log) hipLaunchKernelGGL(k_sp_move_prs, dim3(G), dim3(64), 0, s, sp->gm, m->d, sp->sample, pcap, sp->forced, sp->su, sp->resign, sp->pplay);
+        else if (pplay && sp->resign.r > 0) hipLaunchKernelGGL(k_sp_move_pr, dim3(G), dim3(64), 0, s, sp->gm, m->d, sp->sample, pcap, sp->forced, sp->resign, sp->pplay);
+        else if (pplay && sp->su.log) hipLaunchKernelGGL(k_sp_move_ps, dim3(G), dim3(64), 0, s, sp->gm, m->d, sp->sample, pcap, sp->forced, sp->su, sp->pplay);
+        else if (pplay) hipLaunchKernelGGL(k_sp_move_p, dim3(G), dim3(64), 0, s, sp->gm, m->d, sp->sample, pcap, sp->forced, sp->pplay);
+        else if (sp->resign.r > 0 && sp->su.log) hipLaunchKernelGGL(k_sp_move_rs, dim3(G), dim3(64), 0, s, sp->gm, m->d, sp->sample, capped ? sp->cap : PlayoutCap{0, 0.0, nullptr, nullptr}, sp->forced, sp->su, sp->resign);
         else if (sp->resign.r > 0) hipLaunchKernelGGL(k_sp_move_r, dim3(G), dim3(64), 0, s, sp->gm, m->d, sp->sample, capped ? sp->cap : PlayoutCap{0, 0.0, nullptr, nullptr}, sp->forced, sp->resign);
         else if (sp->su.log && sp->gumbel_on) hipLaunchKernelGGL(k_sp_move_gs, dim3(G), dim3(64), 0, s, sp->gm, m->d, GumbelPlay{m->gd, sp->gumbel_log, sp->gumbel_rows, sp->gumbel_moves}, sp->su);
         else if (sp->su.log) hipLaunchKernelGGL(k_sp_move_fs, dim3(G), dim3(64), 0, s, sp->gm, m->d, sp->sample, capped ? sp->cap : PlayoutCap{0, 0.0, nullptr, nullptr}, sp->forced, sp->su);
@@ -3608,6 +3837,7 @@ OZ_API int oz_selfplay_set_proofs(oz_selfplay* sp, int enable) {
     OZ_REQUIRE(sp, "null selfplay");
     std::lock_guard<std::mutex> lk(sp->mu);
     if (sp->mode != 0) { oz_set_error("oz_selfplay_set_proofs: the engine has been driven already (set it before the first driver call)"); return OZ_ERR_STATE; }
+    if (!enable && sp->proof_play) { oz_set_error("oz_selfplay_set_proofs: proof play is on and reads the proofs (oz_selfplay_set_proof_play(sp, 0) first)"); return OZ_ERR_STATE; }
     std::lock_guard<std::mutex> lkm(sp->m->mu);
     return proofs_set_locked(sp->m, "oz_selfplay_set_proofs", enable);
 }
@@ -3616,6 +3846,47 @@ OZ_API int oz_selfplay_proof_stats(oz_selfplay* sp, int64_t* out4) {
     std::lock_guard<std::mutex> lk(sp->mu);
     std::lock_guard<std::mutex> lkm(sp->m->mu);
     return proof_stats_locked(sp->m, out4);
+}
+// proof play of the engine's moves ("proof play" in the header), for oz_selfplay_run; on top of proofs; before the first driver call
+OZ_API int oz_selfplay_set_proof_play(oz_selfplay* sp, int enable) {
+    OZ_REQUIRE(sp, "null selfplay");
+    OZ_REQUIRE(enable == 0 || enable == 1, "oz_selfplay_set_proof_play: enable = %d (0 or 1)", enable);
+    std::lock_guard<std::mutex> lk(sp->mu);
+    if (sp->mode != 0) { oz_set_error("oz_selfplay_set_proof_play: the engine has been driven already (set it before the first driver call)"); return OZ_ERR_STATE; }
+    if (!enable) { sp->proof_play = false; return OZ_OK; }
+    if (!sp->m->proofs) { oz_set_error("oz_selfplay_set_proof_play: the engine keeps no proofs (oz_selfplay_set_proofs first)"); return OZ_ERR_STATE; }
+    if (!sp->pplay.stat) {
+        hipSetDevice(sp->m->device);
+        const size_t held = sp->allocs.size(), G = (size_t)sp->gm.G;
+        uint8_t* log = nullptr; unsigned long long* stat = nullptr;
+        int rc = sp->alloc(&log, G * 64);
+        if (!rc) rc = sp->alloc(&stat, 4);
+        if (!rc && (hipMemset(log, 0, G * 64) != hipSuccess || hipMemset(stat, 0, 4 * sizeof(unsigned long long)) != hipSuccess)) {
+            oz_set_error("oz_selfplay_set_proof_play: clearing the buffers failed");
+            rc = OZ_ERR_HIP;
+        }
+        if (rc) {
+            for (size_t i = held; i < sp->allocs.size(); ++i) hipFree(sp->allocs[i]);
+            sp->allocs.resize(held);
+            return rc;
+        }
+        sp->pplay.log = log; sp->pplay.stat = stat;
+    }
+    sp->proof_play = true;
+    return OZ_OK;
+}
+// out4: searched moves on a proven root, moves whose row differs from the raw counts, moves whose action does, fallbacks
+OZ_API int oz_selfplay_proof_play_stats(oz_selfplay* sp, int64_t* out4) {
+    OZ_REQUIRE(sp && out4, "null argument");
+    std::lock_guard<std::mutex> lk(sp->mu);
+    unsigned long long c[4] = {0, 0, 0, 0};
+    if (sp->pplay.stat) {
+        hipSetDevice(sp->m->device);
+        OZ_HIP(hipStreamSynchronize(sp->m->stream));
+        OZ_HIP(hipMemcpy(c, sp->pplay.stat, sizeof c, hipMemcpyDeviceToHost));
+    }
+    for (int i = 0; i < 4; ++i) out4[i] = (int64_t)c[i];
+    return OZ_OK;
 }
 OZ_API int oz_selfplay_get_value_signs(oz_selfplay* sp, int* mode) {
     OZ_REQUIRE(sp, "null selfplay");
@@ -4223,25 +4494,26 @@ OZ_API int oz_selfplay_values_device(oz_selfplay* sp, void* dst_device, int64_t 
 // One wavefront per record i of [first, have).  Lane l loads record i + l: a game's records are contiguous and ascending in ply, so the
 // game ends before the first lane l >= 1 whose record has ply 0 or another game id, or lies past the range (a game has at most 60 plies:
 // the end is always inside the wave).  TD: the recurrence runs backwards from there over the lanes' (p z, p q, exact), every lane the
-// same steps (oz_value_target_td_step); lane 0 stores.  acc: [0] records [1] exact [2] sign(t) != z
+// same steps (oz_value_target_td_step); lane 0 stores.  acc: [0] records [1] exact [2] sign(t) != z.  exact_proven: a record with a proof
+// code (pad[2] != 0, "proof play" in the header) is exact too -- its z is the proven sign once oz_selfplay_proof_targets has run.
 __global__ __launch_bounds__(64) void k_value_targets(const oz_record* __restrict__ recs, const double* __restrict__ values, long long first, long long have,
-                                                      int n2, int mode, double om, double param, int exact_empties, float* __restrict__ targets,
-                                                      long long* __restrict__ acc) {
+                                                      int n2, int mode, double om, double param, int exact_empties, int exact_proven,
+                                                      float* __restrict__ targets, long long* __restrict__ acc) {
     const int lane = threadIdx.x;
     const long long i = first + blockIdx.x, j = i + lane;
     const bool in = j < have;
     uint64_t gid = 0, black = 0, white = 0;
-    int ply = 0, p = 1, z = 1;
+    int ply = 0, p = 1, z = 1, code = 0;
     double q = 0.0;
     if (in) {
         const oz_record* r = recs + j;
-        gid = r->game_id; black = r->black; white = r->white; ply = r->ply; p = r->player; z = r->z;
+        gid = r->game_id; black = r->black; white = r->white; ply = r->ply; p = r->player; z = r->z; code = r->pad[2];
         q = values[j];
     }
     const uint64_t gid0 = uni64(gid);
     const uint64_t stop = __ballot(lane >= 1 && (!in || ply == 0 || gid != gid0));
     const int T = stop ? oz_ctz(stop) : 64;                       // records from i to the end of its game
-    const bool exact = oz_value_target_exact(black, white, n2, exact_empties);
+    const bool exact = oz_value_target_exact(black, white, n2, exact_empties) || (exact_proven && code != 0);
     const double pz = (double)(p * z), pq = (double)p * q;
     double t;
     if (mode == OZ_VALUE_TARGET_TD) {
@@ -4271,13 +4543,15 @@ static int value_target_check(const char* fn, int mode, double param, int exact_
     return OZ_OK;
 }
 
-OZ_API int oz_selfplay_value_targets(oz_selfplay* sp, int64_t first_record, int mode, double param, int exact_empties, oz_value_target_stats* stats) {
+static int selfplay_value_targets(const char* fn, oz_selfplay* sp, int64_t first_record, int mode, double param, int exact_empties, int exact_proven,
+                                  oz_value_target_stats* stats) {
     OZ_REQUIRE(sp, "null selfplay");
-    if (int rc = value_target_check("oz_selfplay_value_targets", mode, param, exact_empties)) return rc;
-    OZ_REQUIRE(first_record >= 0, "oz_selfplay_value_targets: first_record %lld", (long long)first_record);
+    if (int rc = value_target_check(fn, mode, param, exact_empties)) return rc;
+    OZ_REQUIRE(exact_proven == 0 || exact_proven == 1, "%s: exact_proven = %d (0 or 1)", fn, exact_proven);
+    OZ_REQUIRE(first_record >= 0, "%s: first_record %lld", fn, (long long)first_record);
     std::lock_guard<std::mutex> lk(sp->mu);
     OZ_REQUIRE_VALUES(sp);
-    if (sp->m->selected) { oz_set_error("oz_selfplay_value_targets: a step is pending (oz_mcts_select without oz_mcts_backup)"); return OZ_ERR_STATE; }
+    if (sp->m->selected) { oz_set_error("%s: a step is pending (oz_mcts_select without oz_mcts_backup)", fn); return OZ_ERR_STATE; }
     hipSetDevice(sp->m->device);
     hipStream_t s = sp->m->stream;
     OZ_HIP(hipStreamSynchronize(s));
@@ -4297,13 +4571,21 @@ OZ_API int oz_selfplay_value_targets(oz_selfplay* sp, int64_t first_record, int 
         const int n = sp->gm.n;
         const double om = 1.0 - param;
         hipLaunchKernelGGL(k_value_targets, dim3((unsigned)count), dim3(64), 0, s, sp->gm.records, sp->gm.values, (long long)first_record, have, n * n, mode, om,
-                           param, exact_empties, sp->targets, sp->d_vt);
+                           param, exact_empties, exact_proven, sp->targets, sp->d_vt);
         OZ_HIP(hipGetLastError());
         OZ_HIP(hipMemcpyAsync(acc, sp->d_vt, sizeof acc, hipMemcpyDeviceToHost, s));
     }
     OZ_HIP(hipStreamSynchronize(s));
     if (stats) { stats->records = acc[0]; stats->exact = acc[1]; stats->sign_changed = acc[2]; }
     return OZ_OK;
+}
+OZ_API int oz_selfplay_value_targets(oz_selfplay* sp, int64_t first_record, int mode, double param, int exact_empties, oz_value_target_stats* stats) {
+    return selfplay_value_targets("oz_selfplay_value_targets", sp, first_record, mode, param, exact_empties, 0, stats);
+}
+// ... with exact_proven = 1 a record that carries a proof code is exact as well (run oz_selfplay_proof_targets first: z is then the proven sign)
+OZ_API int oz_selfplay_value_targets_x(oz_selfplay* sp, int64_t first_record, int mode, double param, int exact_empties, int exact_proven,
+                                       oz_value_target_stats* stats) {
+    return selfplay_value_targets("oz_selfplay_value_targets_x", sp, first_record, mode, param, exact_empties, exact_proven, stats);
 }
 #define OZ_REQUIRE_TARGETS(sp) OZ_REQUIRE((sp)->targets, "this engine holds no value targets: call oz_selfplay_value_targets first")
 OZ_API int oz_selfplay_targets(oz_selfplay* sp, float* out, int64_t max_records, int64_t* written) {
@@ -4317,12 +4599,14 @@ OZ_API int oz_selfplay_targets_device(oz_selfplay* sp, void* dst_device, int64_t
     return selfplay_rows(sp, sp->targets, sizeof(float), dst_device, max_records, written, hipMemcpyDeviceToDevice);
 }
 // the same targets on the host (no device needed): records in any order, grouped by game id and sorted by ply
-OZ_API int oz_value_targets(const oz_record* records, const double* values, int64_t R, int n, int mode, double param, int exact_empties, float* out) {
-    if (int rc = value_target_check("oz_value_targets", mode, param, exact_empties)) return rc;
-    OZ_REQUIRE(n == 4 || n == 6 || n == 8, "oz_value_targets: board size must be 4, 6 or 8 (got %d)", n);
-    OZ_REQUIRE(R >= 0, "oz_value_targets: R %lld", (long long)R);
+static int host_value_targets(const char* fn, const oz_record* records, const double* values, int64_t R, int n, int mode, double param, int exact_empties,
+                              int exact_proven, float* out) {
+    if (int rc = value_target_check(fn, mode, param, exact_empties)) return rc;
+    OZ_REQUIRE(exact_proven == 0 || exact_proven == 1, "%s: exact_proven = %d (0 or 1)", fn, exact_proven);
+    OZ_REQUIRE(n == 4 || n == 6 || n == 8, "%s: board size must be 4, 6 or 8 (got %d)", fn, n);
+    OZ_REQUIRE(R >= 0, "%s: R %lld", fn, (long long)R);
     if (R == 0) return OZ_OK;
-    OZ_REQUIRE(records && values && out, "oz_value_targets: null argument");
+    OZ_REQUIRE(records && values && out, "%s: null argument", fn);
     std::vector<int64_t> order((size_t)R);
     for (int64_t i = 0; i < R; ++i) order[(size_t)i] = i;
     std::stable_sort(order.begin(), order.end(), [records](int64_t a, int64_t b) {
@@ -4338,7 +4622,7 @@ OZ_API int oz_value_targets(const oz_record* records, const double* values, int6
         for (int64_t k = hi - 1; k >= lo; --k) {
             const int64_t ix = order[(size_t)k];
             const oz_record& r = records[ix];
-            const bool exact = oz_value_target_exact(r.black, r.white, n2, exact_empties);
+            const bool exact = oz_value_target_exact(r.black, r.white, n2, exact_empties) || (exact_proven && r.pad[2] != 0);
             const double z = (double)r.z, p = (double)r.player, q = values[ix];
             double t = z;
             if (mode == OZ_VALUE_TARGET_TD) {
@@ -4349,6 +4633,70 @@ OZ_API int oz_value_targets(const oz_record* records, const double* values, int6
         }
         lo = hi;
     }
+    return OZ_OK;
+}
+OZ_API int oz_value_targets(const oz_record* records, const double* values, int64_t R, int n, int mode, double param, int exact_empties, float* out) {
+    return host_value_targets("oz_value_targets", records, values, R, n, mode, param, exact_empties, 0, out);
+}
+OZ_API int oz_value_targets_x(const oz_record* records, const double* values, int64_t R, int n, int mode, double param, int exact_empties,
+                              int exact_proven, float* out) {
+    return host_value_targets("oz_value_targets_x", records, values, R, n, mode, param, exact_empties, exact_proven, out);
+}
+
+// ---------------------------------------------------------------- proof targets ("proof play" in the header)
+// one 64-lane block per record, in place, like k_solve_records: a record with a proof code gets z = the proven sign for its mover (a draw: BLACK's
+// win, as oz_record.z has it).  Idempotent.  acc: [0] records seen [1] proven [2] z changed
+__global__ __launch_bounds__(64) void k_proof_targets(oz_record* __restrict__ recs, long long* __restrict__ acc) {
+    if (threadIdx.x != 0) return;
+    oz_record* rec = recs + blockIdx.x;
+    const int code = rec->pad[2], player = rec->player, z_old = rec->z;
+    atomicAdd((unsigned long long*)&acc[0], 1ULL);
+    if (code == 0) return;
+    const int z = oz_proof_code_z(code, player);
+    if (z != z_old) rec->z = (int8_t)z;
+    atomicAdd((unsigned long long*)&acc[1], 1ULL);
+    if (z != z_old) atomicAdd((unsigned long long*)&acc[2], 1ULL);
+}
+OZ_API int oz_selfplay_proof_targets(oz_selfplay* sp, int64_t first_record, oz_proof_target_stats* stats) {
+    OZ_REQUIRE(sp, "null selfplay");
+    OZ_REQUIRE(first_record >= 0, "oz_selfplay_proof_targets: first_record %lld", (long long)first_record);
+    std::lock_guard<std::mutex> lk(sp->mu);
+    if (sp->m->selected) { oz_set_error("oz_selfplay_proof_targets: a step is pending (oz_mcts_select without oz_mcts_backup)"); return OZ_ERR_STATE; }
+    hipSetDevice(sp->m->device);
+    hipStream_t s = sp->m->stream;
+    OZ_HIP(hipStreamSynchronize(s));
+    unsigned long long total = 0;
+    OZ_HIP(hipMemcpy(&total, sp->gm.counters, 8, hipMemcpyDeviceToHost));
+    const long long have = (long long)total > sp->gm.record_cap ? sp->gm.record_cap : (long long)total;
+    const long long count = have > first_record ? have - first_record : 0;
+    OZ_REQUIRE(count < (1ll << 31), "too many records in one call");
+    long long acc[3] = {0, 0, 0};
+    if (count > 0) {
+        if (!sp->d_pt) { if (int rc = sp->alloc(&sp->d_pt, 3)) return rc; }
+        OZ_HIP(hipMemsetAsync(sp->d_pt, 0, sizeof acc, s));
+        hipLaunchKernelGGL(k_proof_targets, dim3((unsigned)count), dim3(64), 0, s, sp->gm.records + first_record, sp->d_pt);
+        OZ_HIP(hipGetLastError());
+        OZ_HIP(hipMemcpyAsync(acc, sp->d_pt, sizeof acc, hipMemcpyDeviceToHost, s));
+        OZ_HIP(hipStreamSynchronize(s));
+    }
+    if (stats) { stats->records = acc[0]; stats->proven = acc[1]; stats->z_changed = acc[2]; }
+    return OZ_OK;
+}
+// the same pass on the host (no device needed), in place -> stats
+OZ_API int oz_proof_targets(oz_record* records, int64_t R, oz_proof_target_stats* stats) {
+    OZ_REQUIRE(R >= 0, "oz_proof_targets: R %lld", (long long)R);
+    OZ_REQUIRE(R == 0 || records, "oz_proof_targets: null argument");
+    oz_proof_target_stats st = {0, 0, 0};
+    for (int64_t i = 0; i < R; ++i) {
+        oz_record& r = records[i];
+        st.records += 1;
+        if (r.pad[2] == 0) continue;
+        OZ_REQUIRE(r.pad[2] <= 3, "oz_proof_targets: record %lld has proof code %d", (long long)i, (int)r.pad[2]);
+        const int z = oz_proof_code_z(r.pad[2], r.player);
+        st.proven += 1;
+        if (z != r.z) { r.z = (int8_t)z; st.z_changed += 1; }
+    }
+    if (stats) *stats = st;
     return OZ_OK;
 }
 
@@ -4799,8 +5147,26 @@ OZ_API int oz_arena_set_proofs(oz_arena* a, int black, int white) {
     OZ_REQUIRE(a, "null arena");
     std::lock_guard<std::mutex> lk(a->mu);
     if (a->started) { oz_set_error("oz_arena_set_proofs: the arena has run already (set it before the first run)"); return OZ_ERR_STATE; }
+    if ((!black && a->games.arena_proof_play[0]) || (!white && a->games.arena_proof_play[1])) {
+        oz_set_error("oz_arena_set_proofs: proof play is on for that agent and reads the proofs (oz_arena_set_proof_play first)");
+        return OZ_ERR_STATE;
+    }
     if (int rc = proofs_set_locked(a->games.m, "oz_arena_set_proofs", black)) return rc;
     return proofs_set_locked(a->mb, "oz_arena_set_proofs", white);
+}
+// proof play per agent ("proof play" in the header): the agent's move is the arg-max of the row its root's proofs keep; needs that agent's
+// proofs; before the first run
+OZ_API int oz_arena_set_proof_play(oz_arena* a, int black, int white) {
+    OZ_REQUIRE(a, "null arena");
+    OZ_REQUIRE((black == 0 || black == 1) && (white == 0 || white == 1), "oz_arena_set_proof_play: black = %d, white = %d (0 or 1)", black, white);
+    std::lock_guard<std::mutex> lk(a->mu);
+    if (a->started) { oz_set_error("oz_arena_set_proof_play: the arena has run already (set it before the first run)"); return OZ_ERR_STATE; }
+    if ((black && !a->games.m->proofs) || (white && !a->mb->proofs)) {
+        oz_set_error("oz_arena_set_proof_play: the agent keeps no proofs (oz_arena_set_proofs first)");
+        return OZ_ERR_STATE;
+    }
+    a->games.arena_proof_play[0] = black != 0; a->games.arena_proof_play[1] = white != 0;
+    return OZ_OK;
 }
 OZ_API int oz_arena_get_solve_leaves(oz_arena* a, int64_t* rows_black, int64_t* rows_white) {
     OZ_REQUIRE(a && rows_black && rows_white, "null argument");
@@ -4970,8 +5336,14 @@ OZ_API int oz_arena_run_rounds(oz_arena* a, int max_rounds_arg) {
             rc = mcts_steps_async(mb, a->nb, a->sims, movers[1], false);
         }
         if (rc) break;
-        if (run_a) timed(ma, TS_MOVE, ma->profile, [&] { hipLaunchKernelGGL(k_sp_move, dim3(G), dim3(64), 0, s, sp->gm, ma->d, 1); });
-        if (run_b) timed(mb, TS_MOVE, mb->profile, [&] { hipLaunchKernelGGL(k_sp_move, dim3(G), dim3(64), 0, s, sp->gm, mb->d, 1); });
+        if (run_a) timed(ma, TS_MOVE, ma->profile, [&] {
+            if (sp->arena_proof_play[0]) hipLaunchKernelGGL(k_sp_move_pa, dim3(G), dim3(64), 0, s, sp->gm, ma->d);
+            else hipLaunchKernelGGL(k_sp_move, dim3(G), dim3(64), 0, s, sp->gm, ma->d, 1);
+        });
+        if (run_b) timed(mb, TS_MOVE, mb->profile, [&] {
+            if (sp->arena_proof_play[1]) hipLaunchKernelGGL(k_sp_move_pa, dim3(G), dim3(64), 0, s, sp->gm, mb->d);
+            else hipLaunchKernelGGL(k_sp_move, dim3(G), dim3(64), 0, s, sp->gm, mb->d, 1);
+        });
         if (hipGetLastError() != hipSuccess) { oz_set_error("arena kernel launch failed"); rc = OZ_ERR_HIP; break; }
         if ((round & 3) == 3 || round + 1 == max_rounds) {
             if ((rc = check_error_flag(ma))) break;

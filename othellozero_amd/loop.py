@@ -173,13 +173,15 @@ def evaluate_against_random(board_size, neural_network, games, num_simulations, 
 
 
 def evaluate_against_random_batch(board_size, neural_network, games, num_simulations, degree_exploration, seed=0, leaves_per_step=1,
-                                  opponent=None, solve_leaves=0, openings=None, value_signs="reference", proofs=False):
+                                  opponent=None, solve_leaves=0, openings=None, value_signs="reference", proofs=False,
+                                  proof_play=False):
     """The same evaluation as `evaluate_against_random` played in lock step on the GPU (agents.arena_batch with a random
     mover): the network takes BLACK in the first games // 2 + games % 2 games and WHITE in the rest (the reference draws the
     colours with random.shuffle; the split here is fixed).  opponent: arena_batch's (None / "random", or ("minimax", depth[, evaluation])).
     solve_leaves=E > 0: the network's search takes exact values for leaves with at most E empties (arena_batch).
     value_signs="sound": the network's search backs its values up with the signs right across passes and finished boards (arena_batch).
     proofs=True (needs value_signs="sound"): the network's search keeps exact values as proofs and backs them up the tree (arena_batch).
+    proof_play=True (needs proofs=True): the network's move is the arg-max of the row its root's proofs keep (arena_batch).
     openings=(plies, opening_seed): every game starts with a random opening (arena_batch); game k of the BLACK half and game k of the WHITE half
     play opening k, so the network meets every opening from both sides (with an odd `games` the BLACK half has one opening more).
     -> dict(wins, black_wins, black_games, white_wins, white_games)"""
@@ -187,8 +189,10 @@ def evaluate_against_random_batch(board_size, neural_network, games, num_simulat
     solve_leaves = _lib.check_solve_leaves(solve_leaves)
     _lib.check_value_signs(value_signs)
     _lib.check_proofs(proofs, value_signs)
+    _lib.check_proof_play(proof_play, proofs)
     _lib.check_openings(openings)
-    opening_kw = dict({"openings": openings, "first_opening_id": 0} if openings is not None else {}, **({"value_signs": value_signs} if value_signs != "reference" else {}), **_lib.proofs_kw(proofs))
+    opening_kw = dict({"openings": openings, "first_opening_id": 0} if openings is not None else {}, **({"value_signs": value_signs} if value_signs != "reference" else {}), **_lib.proofs_kw(proofs),
+                      **_lib.proof_play_kw(proof_play))
     as_black, as_white = games // 2 + games % 2, games // 2
     r = dict(wins=0, black_wins=0, black_games=0, white_wins=0, white_games=0)
     if as_black:
@@ -212,14 +216,16 @@ def evaluate_against_opponent(board_size, neural_network, games, num_simulations
 
 
 def evaluate_against_opponent_batch(board_size, neural_network, games, num_simulations, degree_exploration, opponent, seed=0, leaves_per_step=1,
-                                    solve_leaves=0, openings=None, value_signs="reference", proofs=False):
+                                    solve_leaves=0, openings=None, value_signs="reference", proofs=False, proof_play=False):
     """`evaluate_against_random_batch` under the name that says what it does when the opponent is not the random agent"""
     solve_leaves = _lib.check_solve_leaves(solve_leaves)
     _lib.check_value_signs(value_signs)
     _lib.check_proofs(proofs, value_signs)
+    _lib.check_proof_play(proof_play, proofs)
     return evaluate_against_random_batch(board_size, neural_network, games, num_simulations, degree_exploration, seed=seed,
                                          leaves_per_step=leaves_per_step, opponent=opponent, **({"solve_leaves": solve_leaves} if solve_leaves else {}),
-                                         **({"openings": openings} if openings is not None else {}), **({"value_signs": value_signs} if value_signs != "reference" else {}), **_lib.proofs_kw(proofs))
+                                         **({"openings": openings} if openings is not None else {}), **({"value_signs": value_signs} if value_signs != "reference" else {}), **_lib.proofs_kw(proofs),
+                                         **_lib.proof_play_kw(proof_play))
 
 
 def _discs(boards):
@@ -253,7 +259,7 @@ def pair_statistics(new_black_final_black, new_black_final_white, old_black_fina
 
 
 def paired_match(board_size, neural_network, old_neural_network, pairs, num_simulations, degree_exploration, openings, seed=0, leaves_per_step=1,
-                 solve_leaves=0, value_signs="reference", proofs=False):
+                 solve_leaves=0, value_signs="reference", proofs=False, proof_play=False):
     """A match over an opening suite, every opening played twice with the colours swapped -- NOT the reference's match (main.py:110-134 starts
     every game from the standard position).  Two arenas of `pairs` games: the new network as BLACK against the old one, then the old one as
     BLACK against the new; both get openings=(plies, opening_seed) and first_opening_id=0, so game i of either starts with opening i.  Game ids
@@ -261,13 +267,14 @@ def paired_match(board_size, neural_network, old_neural_network, pairs, num_simu
     solve_leaves = _lib.check_solve_leaves(solve_leaves)
     _lib.check_value_signs(value_signs)
     _lib.check_proofs(proofs, value_signs)
+    _lib.check_proof_play(proof_play, proofs)
     if openings is None:
         raise ValueError("paired_match needs openings=(plies, opening_seed): without them every pair is the same two games")
     _lib.check_openings(openings)
     if isinstance(pairs, bool) or not isinstance(pairs, (int, np.integer)) or pairs < 1:
         raise ValueError(f"paired_match: pairs must be a whole number >= 1 (got {pairs!r})")
     kw = dict(leaves_per_step=leaves_per_step, openings=openings, first_opening_id=0, **({"solve_leaves": solve_leaves} if solve_leaves else {}),
-              **({"value_signs": value_signs} if value_signs != "reference" else {}), **_lib.proofs_kw(proofs))
+              **({"value_signs": value_signs} if value_signs != "reference" else {}), **_lib.proofs_kw(proofs), **_lib.proof_play_kw(proof_play))
     a = arena_batch(neural_network, old_neural_network, board_size, int(pairs), num_simulations, degree_exploration, seed=seed, **kw)
     b = arena_batch(old_neural_network, neural_network, board_size, int(pairs), num_simulations, degree_exploration, seed=seed,
                     first_game_id=int(pairs), **kw)
@@ -276,36 +283,40 @@ def paired_match(board_size, neural_network, old_neural_network, pairs, num_simu
 
 
 def self_play_match(board_size, neural_network, old_neural_network, total_games, num_simulations, degree_exploration, seed=0,
-                    leaves_per_step=1, solve_leaves=0, openings=None, value_signs="reference", proofs=False):
+                    leaves_per_step=1, solve_leaves=0, openings=None, value_signs="reference", proofs=False, proof_play=False):
     """main.py:110-134: total_games // 2 games with the new network as BLACK, the rest with it as WHITE.
     -> number of games the new network won (a drawn game goes to BLACK, like get_winning_player).
     solve_leaves=E > 0: both networks' searches take exact values for leaves with at most E empties (arena_batch).
     value_signs="sound": both networks' searches back their values up with the signs right across passes and finished boards (arena_batch).
     proofs=True (needs value_signs="sound"): both searches keep exact values as proofs and back them up the tree (arena_batch).
+    proof_play=True (needs proofs=True): both agents' moves are the arg-max of the row their root's proofs keep (arena_batch).
     openings=(plies, opening_seed): paired_match over total_games // 2 openings instead (total_games must be even: a pair is two games); the
     return value is its `wins`, counted by the same rule, and self_play_match.stats holds its dict (None after a match without openings)."""
     solve_leaves = _lib.check_solve_leaves(solve_leaves)
     _lib.check_value_signs(value_signs)
     _lib.check_proofs(proofs, value_signs)
+    _lib.check_proof_play(proof_play, proofs)
     self_play_match.stats = None
     if openings is not None:
         _lib.check_openings(openings)
         if total_games % 2 or total_games < 2:
             raise ValueError(f"self_play_match with openings plays pairs of games: total_games must be even and >= 2 (got {total_games})")
         stats = paired_match(board_size, neural_network, old_neural_network, total_games // 2, num_simulations, degree_exploration, openings,
-                             seed=seed, leaves_per_step=leaves_per_step, solve_leaves=solve_leaves, **({"value_signs": value_signs} if value_signs != "reference" else {}), **_lib.proofs_kw(proofs))
+                             seed=seed, leaves_per_step=leaves_per_step, solve_leaves=solve_leaves, **({"value_signs": value_signs} if value_signs != "reference" else {}), **_lib.proofs_kw(proofs),
+                             **_lib.proof_play_kw(proof_play))
         self_play_match.stats = {k: v for k, v in stats.items() if k != "games"}
         return stats["wins"]
     as_black, as_white = total_games // 2, total_games // 2 + total_games % 2
     wins = 0
     if as_black:
         res = arena_batch(neural_network, old_neural_network, board_size, as_black, num_simulations, degree_exploration, seed=seed,
-                          leaves_per_step=leaves_per_step, **({"solve_leaves": solve_leaves} if solve_leaves else {}), **({"value_signs": value_signs} if value_signs != "reference" else {}), **_lib.proofs_kw(proofs))
+                          leaves_per_step=leaves_per_step, **({"solve_leaves": solve_leaves} if solve_leaves else {}), **({"value_signs": value_signs} if value_signs != "reference" else {}), **_lib.proofs_kw(proofs),
+                          **_lib.proof_play_kw(proof_play))
         wins += int((res["winner"] == 1).sum())
     if as_white:
         res = arena_batch(old_neural_network, neural_network, board_size, as_white, num_simulations, degree_exploration,
                           seed=seed, first_game_id=as_black, leaves_per_step=leaves_per_step, **({"solve_leaves": solve_leaves} if solve_leaves else {}),
-                          **({"value_signs": value_signs} if value_signs != "reference" else {}), **_lib.proofs_kw(proofs))
+                          **({"value_signs": value_signs} if value_signs != "reference" else {}), **_lib.proofs_kw(proofs), **_lib.proof_play_kw(proof_play))
         wins += int((res["winner"] == -1).sum())
     return wins
 
@@ -313,7 +324,8 @@ def self_play_match(board_size, neural_network, old_neural_network, total_games,
 def _selfplay_into_replay(replay, neural_network, board_size, num_episodes, num_simulations, degree_exploration, temperature, e_greedy, seed,
                           first_game_id, q_mode, visits, leaves_per_step, root_noise, sample_moves, alias_final_boards, policy_target,
                           target_temperature, endgame_targets=0, solve_leaves=0, playout_cap=None, forced_playouts=0.0, value_target="outcome",
-                          gumbel=None, surprise_weight=None, resign=None, value_signs="reference", proofs=False):
+                          gumbel=None, surprise_weight=None, resign=None, value_signs="reference", proofs=False, proof_play=False,
+                          proof_targets=False):
     """one iteration's games on the engine selfplay_batch would create, played to the end without reading a record, and their examples
     appended to the device buffer; -> (records appended, the endgame solver's statistics or None).  One-channel (BaseNN) examples are never
     aliased (examples_from_records).  endgame_targets > 0: SelfPlayEngine.solve_records before the append.  playout_cap: the engine's; the
@@ -323,7 +335,9 @@ def _selfplay_into_replay(replay, neural_network, board_size, num_episodes, num_
     surprise_weight=(frac, weight_seed): the engine records policy surprise and the append writes c_i examples per record
     (ReplayBuffer.append_engine(surprise_weight=...)); training.surprise_stats then holds the iteration's dict(records, examples,
     mean_copies, max_copies, mean_surprise).  resign: the engine's; an adjudicated record is appended like any other, and training.resign_stats
-    then holds the engine's resign_stats()."""
+    then holds the engine's resign_stats().  proof_play: the engine's; training.proof_play_stats then holds its proof_play_stats().
+    proof_targets: SelfPlayEngine.proof_targets before the endgame solver and the append, whose value targets then take a proven record as
+    exact; training.proof_target_stats holds its statistics."""
     from .training import SelfPlayEngine
     vt_on = _lib.check_value_target(value_target)[0] != _lib.VALUE_TARGET_OUTCOME
     eng = SelfPlayEngine(neural_network, board_size, num_episodes, num_simulations, degree_exploration, temperature, e_greedy, seed,
@@ -331,20 +345,24 @@ def _selfplay_into_replay(replay, neural_network, board_size, num_episodes, num_
                          sample_moves=sample_moves, solve_leaves=solve_leaves, **({"playout_cap": playout_cap} if playout_cap is not None else {}),
                          **({"forced_playouts": forced_playouts} if forced_playouts else {}), **({"record_values": True} if vt_on else {}),
                          **({"gumbel": gumbel} if gumbel is not None else {}), **({"record_surprise": True} if surprise_weight is not None else {}),
-                         **({"resign": resign} if resign is not None else {}), **({"value_signs": value_signs} if value_signs != "reference" else {}), **_lib.proofs_kw(proofs))
+                         **({"resign": resign} if resign is not None else {}), **({"value_signs": value_signs} if value_signs != "reference" else {}), **_lib.proofs_kw(proofs),
+                         **_lib.proof_play_kw(proof_play))
     for _ in range(board_size * board_size):
         eng.run(4)
         if eng.stats()["live_games"] == 0:
             break
+    training.proof_target_stats = eng.proof_targets() if proof_targets else None
     endgame = eng.solve_records(endgame_targets) if endgame_targets else None
     if solve_leaves:
         training.rows_solved += eng.rows_solved()
     if resign is not None:
         training.resign_stats = eng.resign_stats()
     training.proof_stats = eng.proof_stats() if proofs else None
+    training.proof_play_stats = eng.proof_play_stats() if proof_play else None
     appended = replay.append_engine(eng, alias_final=alias_final_boards and getattr(neural_network, "in_channels", 2) == 2,
                                     policy_target=policy_target, target_temperature=target_temperature,
                                     **({"value_target": value_target, "exact_empties": endgame_targets} if vt_on else {}),
+                                    **({"exact_proven": True} if vt_on and proof_targets else {}),
                                     **({"surprise_weight": surprise_weight} if surprise_weight is not None else {}))
     if surprise_weight is not None:
         st = replay.last_weight_stats
@@ -367,6 +385,13 @@ def _log_resign(i, num_iterations, stats):
 def _log_proofs(i, num_iterations, stats):
     logging.info('[%d/%d] proofs: %d edges proven / descents ended on a proven edge %d, on a proven node %d / %d roots proven', i, num_iterations,
                  stats["edges_proven"], stats["edge_stops"], stats["node_stops"], stats["roots_proven"])
+
+
+def _log_proof_play(i, num_iterations, stats, targets):
+    logging.info('[%d/%d] proof play: %d moves on a proven root / %d rows changed, %d moves changed, %d fallbacks%s', i, num_iterations,
+                 stats["proven_roots"], stats["rows_changed"], stats["moves_changed"], stats["fallbacks"],
+                 '' if targets is None else ' / proof targets: %d of %d records proven, z changed in %d' % (
+                     targets["proven"], targets["records"], targets["z_changed"]))
 
 
 def _fit_with_holdout(i, num_iterations, neural_network, replay, total_before, share):
@@ -407,7 +432,8 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
              distributed=False, batched_evaluation=False, policy_target="onehot", target_temperature=1.0, leaves_per_step=1,
              root_noise=None, sample_moves=None, replay="host", evaluation_opponent="random", endgame_targets=0,
              solve_leaves=0, match_openings=None, evaluation_openings=None, playout_cap=None, forced_playouts=None, eval_symmetry=None,
-             value_target="outcome", gumbel=None, surprise_weight=None, resign=None, validation_share=None, value_signs="reference", proofs=False):
+             value_target="outcome", gumbel=None, surprise_weight=None, resign=None, validation_share=None, value_signs="reference", proofs=False,
+             proof_play=False, proof_targets=False):
     """main.py:56-259 on the GPU engines; returns `historic` = [(episodes done, win rate vs random), ...]
 
     validation_share=f in (0, 0.5] (None = off, the default: the loop is unchanged): held-out evaluation of every iteration's fit.  After an
@@ -516,6 +542,16 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
     and root values read the raw statistics as before.  Not with gumbel or forced_playouts (ValueError).  training.proof_history keeps the
     self-play engines' proof_stats() per iteration (with distributed=True: this rank's) ("Proofs"; tools/proofs_bench.py).
 
+    proof_play=True (needs proofs=True; False = off, the default): the searches' exact knowledge reaches the three hand-overs it stopped short
+    of.  The recorded visit row keeps the raw counts of the moves the descent would still pick at the root -- those that prove a known
+    value, else those not proven lost -- and every move rule that reads counts reads that row, so a move proven lost after it took most of
+    the visits is neither played nor trained towards; the recorded root value (value targets, resignation) is the exact one where it is
+    known; the record carries the proof code (_lib.record_proven).  The explore branch of the coin stays uniform.  One setting serves
+    self-play, the match and the batched evaluation.  training.proof_play_history keeps the self-play engines' proof_play_stats() per
+    iteration.  proof_targets=True (needs proof_play=True): before the endgame targets, the value targets and the appends, z of every
+    proven record becomes the proven sign (SelfPlayEngine.proof_targets), and the value targets take such a record as exact.  Playing
+    strength is neither gated nor claimed ("Proof play"; tools/proof_play_bench.py).
+
     match_openings=(plies, opening_seed) / evaluation_openings=(plies, opening_seed) (None = off, the default): the games of the new-vs-old
     match / of the batched evaluation start with random openings of `plies` plies instead of the one standard position, every opening played
     from both sides (self_play_match / evaluate_against_random_batch with openings=; DESIGN.md, "Openings").  At temperature 0 the reference's
@@ -618,8 +654,11 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
     solve_leaves = _lib.check_solve_leaves(solve_leaves)
     _lib.check_value_signs(value_signs)
     _lib.check_proofs(proofs, value_signs, gumbel=gumbel, forced_playouts=forced_playouts)
+    proof_play = _lib.check_proof_play(proof_play, proofs)
+    pt_kw = {"proof_targets": True} if _lib.check_proof_targets(proof_targets, proof_play) else {}
     training.proof_history = []
-    vs_kw = dict({"value_signs": value_signs} if value_signs != "reference" else {}, **_lib.proofs_kw(proofs))
+    training.proof_play_history = []
+    vs_kw = dict({"value_signs": value_signs} if value_signs != "reference" else {}, **_lib.proofs_kw(proofs), **_lib.proof_play_kw(proof_play))
     training.rows_solved = 0
     endgame_targets = _lib.check_endgame_targets(endgame_targets, alias_final_boards)
     training.endgame_history = []
@@ -705,7 +744,7 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
                                                       degree_exploration, temperature, e_greedy, seed, total_episodes_done, q_mode, visits,
                                                       leaves_per_step, root_noise, sample_moves, alias_final_boards, policy_target,
                                                       target_temperature, endgame_targets, solve_leaves, playout_cap, forced_playouts, **vt_kw,
-                                                      **gumbel_kw, **resign_kw, **vs_kw,
+                                                      **gumbel_kw, **resign_kw, **vs_kw, **pt_kw,
                                                       **({"surprise_weight": (surprise_weight, seed + i)} if surprise_weight is not None else {}))
             if resign is not None:
                 training.resign_history.append(training.resign_stats)
@@ -713,6 +752,9 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
             if proofs:
                 training.proof_history.append(training.proof_stats)
                 _log_proofs(i, num_iterations, training.proof_stats)
+            if proof_play:
+                training.proof_play_history.append(dict(training.proof_play_stats, targets=training.proof_target_stats))
+                _log_proof_play(i, num_iterations, training.proof_play_stats, training.proof_target_stats)
             if surprise_weight is not None:
                 st = training.surprise_stats
                 training.surprise_history.append(st)
@@ -736,10 +778,12 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
                                      seed=seed, first_game_id=total_episodes_done + first, q_mode=q_mode, record_visits=visits,
                                      leaves_per_step=leaves_per_step, root_noise=root_noise, sample_moves=sample_moves,
                                      solve_leaves=solve_leaves, **cap_kw, **({"record_values": True} if vt_on else {}), **resign_kw, **vs_kw)
-                eng.play_to_end(endgame_targets=endgame_targets, **vt_kw)               # each rank relabels its own records (and computes its targets)
+                eng.play_to_end(endgame_targets=endgame_targets, **vt_kw, **pt_kw)               # each rank relabels its own records (and computes its targets)
                 training.rows_solved += eng.rows_solved() if solve_leaves else 0
                 resign_stats = eng.resign_stats() if resign is not None else None
                 proof_stats = eng.proof_stats() if proofs else None
+                proof_play_stats = eng.proof_play_stats() if proof_play else None
+                proof_target_stats = getattr(eng, "proof_target_stats", None)
                 records = pooled_selfplay_records(eng, device, with_visits=visits,      # the only exchange of the self-play phase
                                                   **({"with_values": True} if vt_on else {}))
                 endgame = getattr(eng, "endgame_stats", None)
@@ -750,10 +794,12 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
                                          seed=seed, first_game_id=total_episodes_done, q_mode=q_mode, record_visits=visits,
                                          leaves_per_step=leaves_per_step, root_noise=root_noise, sample_moves=sample_moves,
                                          **({"endgame_targets": endgame_targets} if endgame_targets else {}), **({"solve_leaves": solve_leaves} if solve_leaves else {}),
-                                         **cap_kw, **vt_kw, **gumbel_kw, **resign_kw, **vs_kw)
+                                         **cap_kw, **vt_kw, **gumbel_kw, **resign_kw, **vs_kw, **pt_kw)
                 training.rows_solved += selfplay_batch.rows_solved if solve_leaves else 0
                 resign_stats = selfplay_batch.resign_stats if resign is not None else None
                 proof_stats = selfplay_batch.proof_stats if proofs else None
+                proof_play_stats = selfplay_batch.proof_play_stats if proof_play else None
+                proof_target_stats = getattr(selfplay_batch, "proof_target_stats", None)
                 endgame = getattr(selfplay_batch, "endgame_stats", None) if endgame_targets else None
             restore_eval_symmetry()
             if resign is not None:
@@ -762,6 +808,9 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
             if proofs:
                 training.proof_history.append(proof_stats)
                 _log_proofs(i, num_iterations, proof_stats)
+            if proof_play:
+                training.proof_play_history.append(dict(proof_play_stats, targets=proof_target_stats))
+                _log_proof_play(i, num_iterations, proof_play_stats, proof_target_stats)
             if endgame is not None:
                 training.endgame_history.append(endgame)
                 _log_endgame(i, num_iterations, endgame)

@@ -18,7 +18,8 @@ from .Othello import OthelloGame, OthelloPlayer
 
 class OthelloMCTS:
     def __init__(self, board_size, neural_network, degree_exploration, q_mode=_lib.QMODE_F64,
-                 node_cap=8192, leaves_per_step=1, solve_leaves=0, forced_playouts=None, gumbel=None, value_signs="reference", proofs=False):
+                 node_cap=8192, leaves_per_step=1, solve_leaves=0, forced_playouts=None, gumbel=None, value_signs="reference", proofs=False,
+                 proof_play=False):
         """q_mode: OZ_QMODE_F64 = the NumPy 1.18.5 promotion the reference pins (requirements.txt:19),
         OZ_QMODE_NEP50 = what NumPy >= 2 computes (SURVEY.md R-FP).
         leaves_per_step > 1 (native networks only, created with max_batch >= leaves_per_step): that many descents of the tree per
@@ -39,10 +40,14 @@ class OthelloMCTS:
         proofs=True (needs value_signs="sound"; native networks only): exact values -- finished boards, solved leaves -- are kept as proofs
         and backed up the tree; the descent never picks a proven loss while something else is left, takes the exact value in place of the
         averaged Q and stops at a proven position (oz_mcts_set_proofs; include/othellozero_amd.h, "proofs").  root_proof / dump_proofs /
-        proof_stats read them.  Not with gumbel or forced_playouts."""
+        proof_stats read them.  Not with gumbel or forced_playouts.
+        proof_play=True (needs proofs=True): proven_counts / get_policy_action_probabilities(..., proven=True) / root_value(..., proven=True) /
+        sample_action(..., proven=True) give the row, the policy, the value and the sampled move the root's proofs leave
+        (include/othellozero_amd.h, "proof play"); the flag itself changes no call -- callers (execute_episode, the agents) read it."""
         self.value_signs = value_signs
         vs_mode = _lib.check_value_signs(value_signs)
         self.proofs = _lib.check_proofs(proofs, value_signs, gumbel=gumbel, forced_playouts=forced_playouts)
+        self.proof_play = _lib.check_proof_play(proof_play, self.proofs)
         self.gumbel = _lib.check_gumbel_options(gumbel, forced_playouts=forced_playouts, leaves_per_step=leaves_per_step)
         self.forced_playouts = _lib.check_forced_playouts(forced_playouts, need_noise=False)
         self._forced_set = False
@@ -215,17 +220,18 @@ class OthelloMCTS:
         return eta[0], bool(armed[0]), eps.value
 
     # ---- move sampling (include/othellozero_amd.h, "move sampling"): the engines' move rule for the opening plies, on the bare search
-    def sample_action(self, state, temperature, seed, game_id, ply):
+    def sample_action(self, state, temperature, seed, game_id, ply, proven=False):
         """the move drawn in proportion to N ** (1 / temperature) over the visit counts of the mover-canonical `state` (as
         get_policy_action_probabilities takes it), keyed (seed, game_id, ply): (row, col).  KeyError if the state is unknown or was never
-        selected from."""
+        selected from.  proven=True (proofs=True): over proven_counts(state)."""
         temperature, _ = _lib.check_sample_moves((temperature, 0))
         own, opp = _lib.pack_board(state)
         self._set_root(own, opp)
         gid, pl = np.array([int(game_id)], np.uint64), np.array([int(ply)], np.int32)
         action, rc = np.zeros(1, np.int32), np.zeros(1, np.int32)
-        _lib.check(_lib.load().oz_mcts_sample_moves(self._h, temperature, int(seed), _lib.p_u64(gid), _lib.p_i32(pl), _lib.p_i32(action),
-                                                    _lib.p_i32(rc)))
+        fn = _lib.load().oz_mcts_proven_sample_moves if proven else _lib.load().oz_mcts_sample_moves
+        _lib.check(fn(self._h, temperature, int(seed), _lib.p_u64(gid), _lib.p_i32(pl), _lib.p_i32(action),
+              _lib.p_i32(rc)))
         if rc[0] != 0 or action[0] < 0:
             raise KeyError("state is unknown to the search or was never selected from")
         return int(action[0]) >> 3, int(action[0]) & 7
@@ -259,12 +265,13 @@ class OthelloMCTS:
             _lib.check(lib.oz_mcts_backup(self._h, _lib.p_f32(pi), _lib.p_f32(v)))
         return self._last_value()
 
-    def _counts(self, state, pruned=False):
-        """visit counts of a mover-canonical state: (rc, counts[64], legal mask); pruned: the policy target's row (oz_mcts_pruned_counts)"""
+    def _counts(self, state, pruned=False, proven=False):
+        """visit counts of a mover-canonical state: (rc, counts[64], legal mask); pruned: the policy target's row (oz_mcts_pruned_counts);
+        proven: the row the root's proofs keep (oz_mcts_proven_counts)"""
         own, opp = _lib.pack_board(state)
         self._set_root(own, opp)
         cnt, legal, rc = np.zeros(64, np.int32), np.zeros(1, np.uint64), np.zeros(1, np.int32)
-        fn = _lib.load().oz_mcts_pruned_counts if pruned else _lib.load().oz_mcts_root_counts
+        fn = _lib.load().oz_mcts_proven_counts if proven else _lib.load().oz_mcts_pruned_counts if pruned else _lib.load().oz_mcts_root_counts
         _lib.check(fn(self._h, _lib.p_i32(cnt), _lib.p_u64(legal), _lib.p_i32(rc)))
         return int(rc[0]), cnt, int(legal[0])
 
@@ -277,14 +284,24 @@ class OthelloMCTS:
             raise KeyError("state is unknown to the search or was never selected from")
         return cnt
 
-    def root_value(self, state):
+    def proven_counts(self, state):
+        """int32 (64,) by square: the visit counts of the mover-canonical `state` as its proofs keep them (include/othellozero_amd.h, "proof
+        play"): the raw counts of the moves the descent would still pick at the root, 0 elsewhere.  Needs proofs=True.  KeyError if the
+        state is unknown or was never selected from."""
+        rc, cnt, _ = self._counts(state, proven=True)
+        if rc != 0:
+            raise KeyError("state is unknown to the search or was never selected from")
+        return cnt
+
+    def root_value(self, state, proven=False):
         """the search's value of the mover-canonical `state` for the player to move: the visit-weighted mean of its edges' Q over the raw
         visit counts (include/othellozero_amd.h, "value targets"; agents.rules_root_values of the node's dump).  KeyError if the state is
-        unknown or was never selected from."""
+        unknown or was never selected from.  proven=True (proofs=True): the exact value where the state's value is proven."""
         own, opp = _lib.pack_board(state)
         self._set_root(own, opp)
         val, rc = np.zeros(1, np.float64), np.zeros(1, np.int32)
-        _lib.check(_lib.load().oz_mcts_root_values(self._h, _lib.p_f64(val), _lib.p_i32(rc)))
+        fn = _lib.load().oz_mcts_proven_root_values if proven else _lib.load().oz_mcts_root_values
+        _lib.check(fn(self._h, _lib.p_f64(val), _lib.p_i32(rc)))
         if rc[0] != 0:
             raise KeyError("state is unknown to the search or was never selected from")
         return float(val[0])
@@ -306,11 +323,11 @@ class OthelloMCTS:
         """othelo_mcts.py:40-41: legal actions of BLACK (= channel 0) as tuples, ascending row-major."""
         return [tuple(int(x) for x in a) for a in OthelloGame.get_player_valid_actions(state, OthelloPlayer.BLACK)]
 
-    def get_policy_action_probabilities(self, state, temperature, pruned=False):
+    def get_policy_action_probabilities(self, state, temperature, pruned=False, proven=False):
         """othelo_mcts.py:51-67, evaluated with the same NumPy / random calls as the reference.  pruned=True: over pruned_counts(state), the
-        policy target of a search with forced playouts."""
+        policy target of a search with forced playouts.  proven=True: over proven_counts(state)."""
         n = self._board_size
-        rc, cnt, legal = self._counts(state, pruned)
+        rc, cnt, legal = self._counts(state, pruned, proven)
         if rc == 2:
             raise KeyError("state was expanded but never selected from (num_simulations < 2)")
         probabilities = np.zeros((n, n))

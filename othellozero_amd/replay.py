@@ -65,7 +65,7 @@ class ReplayBuffer:
         _lib.check(_lib.load().oz_replay_clear(self._h))
 
     def append_engine(self, eng, first_record=0, alias_final=False, policy_target="onehot", target_temperature=1.0, value_target="outcome",
-                      exact_empties=0, target=None, surprise_weight=None):
+                      exact_empties=0, target=None, surprise_weight=None, exact_proven=False):
         """the records [first_record, completed so far) of a SelfPlayEngine -> 8 examples each, in ascending (game_id, ply), device to
         device; returns the number of records appended.  policy_target="visits" needs an engine created with record_visits=True.
         policy_target="improved" (or target="improved") needs an engine created with gumbel=...: every example's pi is its record's float32
@@ -75,13 +75,15 @@ class ReplayBuffer:
         the adjudicated one, and with alias_final=True the "final board" of such a game is the board at the stop.
         value_target=("blend", w) / ("td", lam) (an engine created with record_values=True; alias_final=False): the engine computes the
         value targets of those records (SelfPlayEngine.value_targets(value_target, exact_empties, first_record)) and every example's z is
-        its record's float32 target instead of the game outcome; "outcome" is the call without it.
+        its record's float32 target instead of the game outcome; "outcome" is the call without it.  exact_proven=True (after
+        SelfPlayEngine.proof_targets()): a record with a proof code is exact for those targets, like one within exact_empties.
         surprise_weight=(frac, seed) (an engine created with record_surprise=True): policy surprise weighting.  The engine computes the
         records' weights (SelfPlayEngine.surprise_weights(frac, seed, first_record)) and record i becomes c_i = floor(8 w_i + u_i) examples
         instead of 8, the symmetries (t0_i + k) & 7; `total` advances by the sum of c_i, which self.last_examples then holds.  The return
         value stays the number of non-fast records considered.  Combines with every policy and value target and with alias_final."""
         target, T = _target(policy_target if target is None else target, target_temperature, engine=True)
         mode, _ = _lib.check_value_target(value_target, alias_final)
+        xp = {"exact_proven": True} if exact_proven else {}
         done = C.c_int64()
         if surprise_weight is not None:
             try:
@@ -91,7 +93,7 @@ class ReplayBuffer:
             frac = _lib.check_surprise_frac(frac)
             vt = mode != _lib.VALUE_TARGET_OUTCOME
             if vt:
-                eng.value_targets(value_target, exact_empties=exact_empties, first_record=first_record)
+                eng.value_targets(value_target, exact_empties=exact_empties, first_record=first_record, **xp)
             self.last_weight_stats = eng.surprise_weights(frac, seed, first_record=first_record)
             examples = C.c_int64()
             _lib.check(_lib.load().oz_replay_append_selfplay_weighted(self._h, eng._h, int(first_record), 1 if alias_final else 0, target, T,
@@ -99,7 +101,7 @@ class ReplayBuffer:
             self.last_examples = examples.value
             return done.value
         if mode != _lib.VALUE_TARGET_OUTCOME:
-            eng.value_targets(value_target, exact_empties=exact_empties, first_record=first_record)
+            eng.value_targets(value_target, exact_empties=exact_empties, first_record=first_record, **xp)
             _lib.check(_lib.load().oz_replay_append_selfplay_targets(self._h, eng._h, int(first_record), 0, target, T, C.byref(done)))
             return done.value
         _lib.check(_lib.load().oz_replay_append_selfplay(self._h, eng._h, int(first_record), 1 if alias_final else 0, target, T, C.byref(done)))

@@ -33,7 +33,8 @@ def training_example_symmetries(board, policy):
 def execute_episode(board_size, neural_network, degree_exploration, num_simulations, policy_temperature, e_greedy,
                     q_mode=_lib.QMODE_F64, snapshot_boards=False, policy_target="onehot", target_temperature=1.0,
                     leaves_per_step=1, root_noise=None, noise_seed=0, sample_moves=None, sample_seed=0, solve_leaves=0,
-                    forced_playouts=None, value_target="outcome", gumbel=None, gumbel_seed=0, value_signs="reference", proofs=False):
+                    forced_playouts=None, value_target="outcome", gumbel=None, gumbel_seed=0, value_signs="reference", proofs=False,
+                    proof_play=False):
     """training.py:26-72.  Returns [(board (n,n,2) bool, one-hot policy (n,n) float64, z int), ...], 8 per move.
 
     gumbel=(max_considered, c_visit, c_scale) or True: every move's search is a Gumbel root search of num_simulations simulations
@@ -73,9 +74,14 @@ def execute_episode(board_size, neural_network, degree_exploration, num_simulati
     the function without it.
 
     proofs=True (needs value_signs="sound"): the search keeps exact values as proofs and backs them up the tree (OthelloMCTS); not with
-    gumbel or forced_playouts."""
+    gumbel or forced_playouts.
+
+    proof_play=True (needs proofs=True): the policy the move is taken from, the sampled move, the "visits" target and the recorded root
+    value are those the root's proofs leave (OthelloMCTS.proven_counts / root_value(proven=True)); the explore branch is unchanged."""
     _lib.check_value_signs(value_signs)
     _lib.check_proofs(proofs, value_signs, gumbel=gumbel, forced_playouts=forced_playouts)
+    proof_play = _lib.check_proof_play(proof_play, proofs)
+    pp = {"proven": True} if proof_play else {}
     vt_mode, _ = _lib.check_value_target(value_target, not snapshot_boards)
     root_values, movers, positions = [], [], []
     solve_leaves = _lib.check_solve_leaves(solve_leaves)
@@ -96,7 +102,7 @@ def execute_episode(board_size, neural_network, degree_exploration, num_simulati
     mcts = OthelloMCTS(board_size, neural_network, degree_exploration, q_mode=q_mode,
                        node_cap=num_simulations * (board_size * board_size - 3) + 64, leaves_per_step=leaves_per_step,
                        solve_leaves=solve_leaves, forced_playouts=forced_playouts, **({"gumbel": gumbel} if gumbel is not None else {}),
-                       **({"value_signs": value_signs} if value_signs != "reference" else {}), **_lib.proofs_kw(proofs))
+                       **({"value_signs": value_signs} if value_signs != "reference" else {}), **_lib.proofs_kw(proofs), **_lib.proof_play_kw(proof_play))
     # training.py:34-37 (BNN examples are one-channel boards, a fresh array per round: no aliasing for them)
     board_view_type = BoardView.ONE_CHANNEL if getattr(neural_network.network_type, "name", "") == "BNN" else BoardView.TWO_CHANNELS
 
@@ -109,9 +115,9 @@ def execute_episode(board_size, neural_network, degree_exploration, num_simulati
         mcts.simulate_n(state, game.current_player, num_simulations)
         if game.current_player == OthelloPlayer.WHITE:
             state = OthelloGame.invert_board(state)
-        policy = mcts.get_policy_action_probabilities(state, policy_temperature)
+        policy = mcts.get_policy_action_probabilities(state, policy_temperature, **pp)
         if vt_mode != _lib.VALUE_TARGET_OUTCOME:
-            root_values.append(mcts.root_value(state))
+            root_values.append(mcts.root_value(state, **pp))
             movers.append(game.current_player.value)
             positions.append(_lib.pack_board(game.board(BoardView.TWO_CHANNELS)))
 
@@ -121,7 +127,7 @@ def execute_episode(board_size, neural_network, degree_exploration, num_simulati
             if gumbel is not None:
                 action = mcts.gumbel_policy(state)[0]
             if sample_moves is not None and len(examples) // 8 < sample_moves[1]:
-                action = mcts.sample_action(state, sample_moves[0], sample_seed, 0, len(examples) // 8)
+                action = mcts.sample_action(state, sample_moves[0], sample_seed, 0, len(examples) // 8, **pp)
         else:
             actions = mcts.get_state_actions(state)
             action = actions[np.random.choice(len(actions))]
@@ -131,7 +137,7 @@ def execute_episode(board_size, neural_network, degree_exploration, num_simulati
         if policy_target == "improved":
             action_choosed = mcts.gumbel_policy(state)[1]
         if policy_target == "visits":
-            action_choosed = mcts.get_policy_action_probabilities(state, target_temperature, pruned=forced_playouts > 0.0)
+            action_choosed = mcts.get_policy_action_probabilities(state, target_temperature, pruned=forced_playouts > 0.0, **pp)
         board_now = game.board(board_view_type)
         if snapshot_boards:
             board_now = np.copy(board_now)
@@ -197,7 +203,8 @@ class SelfPlayEngine:
                  policy_temperature=1.0, e_greedy=0.9, seed=1234, first_game_id=0, game_id_stride=0,
                  q_mode=_lib.QMODE_F64, refill=False, node_cap=0, record_cap=0, dedup=True, batch_cap=0, eval_cache=False,
                  record_visits=False, leaves_per_step=1, root_noise=None, sample_moves=None, solve_leaves=0, playout_cap=None,
-                 forced_playouts=None, record_values=False, gumbel=None, record_surprise=False, resign=None, value_signs="reference", proofs=False):
+                 forced_playouts=None, record_values=False, gumbel=None, record_surprise=False, resign=None, value_signs="reference", proofs=False,
+                 proof_play=False):
         """dedup: cross-game leaf de-duplication (a board several games reach in one batch is evaluated once; no record changes);
         batch_cap: leaves per network batch of the free-running driver (0 = none; see preferred_batch_cap);
         eval_cache: take (pi, v) of boards the network has evaluated before from its persistent cache (NNetWrapper.set_eval_cache) --
@@ -261,9 +268,15 @@ class SelfPlayEngine:
         them -- as proofs and backs them up the tree; a descent never picks a proven loss while something else is left, takes the exact
         value in place of the averaged Q and stops at a proven position (oz_selfplay_set_proofs).  run() / play_to_end() at any
         leaves_per_step with every option but gumbel and forced_playouts (ValueError); run_steps() and stagger() then raise.  The moves, the
-        visit rows and the root values read the raw statistics as before.  proof_stats() counts ("Proofs")."""
+        visit rows and the root values read the raw statistics as before.  proof_stats() counts ("Proofs").
+        proof_play=True (needs proofs=True): the move, the recorded visit row and the recorded root value take what the root's proofs know
+        (oz_selfplay_set_proof_play): the row keeps the raw counts of the moves the descent would still pick at the root -- those that prove
+        a known value, else those not proven lost -- and every move rule that reads counts reads that row; the root value is the exact one
+        where it is known; the record carries the proof code _lib.record_proven reads.  The explore branch of the coin and last_counts()
+        stay as they are.  proof_play_stats() counts; proof_targets() makes z of the proven records exact ("Proof play")."""
         vs_mode = _lib.check_value_signs(value_signs)
         proofs = _lib.check_proofs(proofs, value_signs, gumbel=gumbel, forced_playouts=forced_playouts)
+        proof_play = _lib.check_proof_play(proof_play, proofs)
         resign = _lib.check_resign(resign, gumbel=gumbel)
         if record_surprise and not (record_visits or gumbel):
             raise ValueError("record_surprise needs record_visits=True or gumbel=...: the surprise is that of a recorded policy target")
@@ -292,6 +305,9 @@ class SelfPlayEngine:
         self.proofs = proofs
         if proofs:
             _lib.check(lib.oz_selfplay_set_proofs(self._h, 1))
+        self.proof_play = proof_play
+        if proof_play:
+            _lib.check(lib.oz_selfplay_set_proof_play(self._h, 1))
         self.leaves_per_step = int(leaves_per_step)
         if self.leaves_per_step != 1:
             _lib.check(lib.oz_selfplay_set_leaves_per_step(self._h, self.leaves_per_step))
@@ -331,6 +347,22 @@ class SelfPlayEngine:
         _lib.check(_lib.load().oz_selfplay_proof_stats(self._h, _lib.p_i64(s)))
         return dict(zip(_lib.PROOF_STATS, (int(x) for x in s)))
 
+    def proof_play_stats(self):
+        """dict(proven_roots, rows_changed, moves_changed, fallbacks) over the engine's searched moves so far: those on a root whose value
+        is known, those whose recorded row differs from the raw counts, those whose greedy or sampled action differs from the one the raw
+        counts give, and those whose candidates were all unvisited (zeros without proof_play=True)"""
+        s = np.zeros(4, np.int64)
+        _lib.check(_lib.load().oz_selfplay_proof_play_stats(self._h, _lib.p_i64(s)))
+        return dict(zip(_lib.PROOF_PLAY_STATS, (int(x) for x in s)))
+
+    def proof_targets(self, first_record=0):
+        """oz_selfplay_proof_targets: the completed records from `first_record` on that carry a proof code get z = the proven sign for their
+        mover (a proven draw follows z's convention: BLACK's win), in place on the device; idempotent.  Run it before solve_records(),
+        value_targets() and the replay appends.  -> dict(records, proven, z_changed)."""
+        s = _lib.ProofTargetStats()
+        _lib.check(_lib.load().oz_selfplay_proof_targets(self._h, int(first_record), C.byref(s)))
+        return {k: int(getattr(s, k)) for k, _ in s._fields_}
+
     def resign_stats(self):
         """dict(v, r, min_ply, keep_prob, games_adjudicated, adjudicated_plies_sum, games_exempt, exempt_triggered, exempt_wrong,
         exempt_trigger_ply_sum): the resignation rule that is set (r 0 = off) and, since it was armed, the games it ended and the plies they
@@ -365,16 +397,20 @@ class SelfPlayEngine:
         _lib.check(_lib.load().oz_selfplay_gumbel(self._h, _lib.p_f64(g), _lib.p_u8(armed), _lib.p_i32(n0)))
         return g, armed, n0
 
-    def value_targets(self, value_target, exact_empties=0, first_record=0):
+    def value_targets(self, value_target, exact_empties=0, first_record=0, exact_proven=False):
         """oz_selfplay_value_targets: the value targets of the completed records from `first_record` on, computed on the device into the
         engine's float32 targets (records(with_targets=True), ReplayBuffer.append_engine(value_target=...)); the records are not touched.
         value_target = "outcome", ("blend", w): (1 - w) z + w q, or ("td", lam): TD(lam) over the root values of the following plies, ending
         in the outcome.  exact_empties=E > 0 (after solve_records(E)): a record with at most E empties keeps its exact z and restarts the
-        chain.  Needs record_values=True.  -> dict(records, exact, sign_changed)."""
+        chain.  exact_proven=True (after proof_targets()): a record with a proof code does the same (oz_selfplay_value_targets_x).  Needs
+        record_values=True.  -> dict(records, exact, sign_changed)."""
         mode, param = _lib.check_value_target(value_target)
         exact_empties = _lib.check_solve_empties(exact_empties, 0, "exact_empties")
         s = _lib.ValueTargetStats()
-        _lib.check(_lib.load().oz_selfplay_value_targets(self._h, int(first_record), mode, param, exact_empties, C.byref(s)))
+        if exact_proven:
+            _lib.check(_lib.load().oz_selfplay_value_targets_x(self._h, int(first_record), mode, param, exact_empties, 1, C.byref(s)))
+        else:
+            _lib.check(_lib.load().oz_selfplay_value_targets(self._h, int(first_record), mode, param, exact_empties, C.byref(s)))
         return {k: int(getattr(s, k)) for k, _ in s._fields_}
 
     def forced_playout_stats(self):
@@ -586,20 +622,25 @@ class SelfPlayEngine:
         _lib.check(_lib.load().oz_selfplay_eval_time(self._h, C.byref(ms), C.byref(launches), C.byref(leaves)))
         return dict(ms=ms.value, launches=launches.value, leaves=leaves.value)
 
-    def play_to_end(self, max_rounds=None, with_visits=False, endgame_targets=0, value_target="outcome", with_policies=False):
+    def play_to_end(self, max_rounds=None, with_visits=False, endgame_targets=0, value_target="outcome", with_policies=False,
+                    proof_targets=False):
         """endgame_targets=E > 0: solve_records(E) once the games are over, before the records are read (its stats: self.endgame_stats).
         value_target other than "outcome": value_targets(value_target, exact_empties=endgame_targets) after that (its stats:
         self.value_target_stats), and the targets come back too: (records, [counts,] targets).  with_policies=True (gumbel=...): the
-        improved-policy rows come last"""
+        improved-policy rows come last.  proof_targets=True (proof_play=True): proof_targets() before all of that (its stats:
+        self.proof_target_stats), and the value targets take a proven record as exact"""
+        proof_targets = _lib.check_proof_targets(proof_targets, self.proof_play)
         max_rounds = max_rounds or self.n * self.n
         for _ in range(max_rounds):
             self.run(4)
             if self.stats()["live_games"] == 0:
                 break
+        if proof_targets:
+            self.proof_target_stats = self.proof_targets()
         if endgame_targets:
             self.endgame_stats = self.solve_records(endgame_targets)
         if _lib.check_value_target(value_target)[0] != _lib.VALUE_TARGET_OUTCOME:
-            self.value_target_stats = self.value_targets(value_target, exact_empties=endgame_targets)
+            self.value_target_stats = self.value_targets(value_target, exact_empties=endgame_targets, exact_proven=proof_targets)
             return self.records(with_visits=with_visits, with_targets=True, with_policies=with_policies)
         return self.records(with_visits=with_visits, with_policies=with_policies)
 
@@ -666,8 +707,13 @@ def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations
                    policy_temperature=1.0, e_greedy=0.9, seed=1234, first_game_id=0, q_mode=_lib.QMODE_F64,
                    expand=False, alias_final=False, record_visits=False, target_temperature=1.0, leaves_per_step=1, root_noise=None,
                    sample_moves=None, endgame_targets=0, solve_leaves=0, playout_cap=None, forced_playouts=None, value_target="outcome", gumbel=None,
-                   surprise_weight=None, resign=None, value_signs="reference", proofs=False):
+                   surprise_weight=None, resign=None, value_signs="reference", proofs=False, proof_play=False, proof_targets=False):
     """Play num_games complete games; returns the move records (or the expanded examples).
+    proof_play=True (needs proofs=True): moves, visit rows, root values and the records' proof codes take what the roots' proofs know
+    (SelfPlayEngine); selfplay_batch.proof_play_stats holds the last call's SelfPlayEngine.proof_play_stats() (None when off).
+    proof_targets=True (needs proof_play=True): z of every proven record becomes the proven sign (SelfPlayEngine.proof_targets) before the
+    endgame targets, the value targets -- which then take a proven record as exact -- and the expansion; selfplay_batch.proof_target_stats
+    holds the last call's statistics (None when off).
     proofs=True (needs value_signs="sound"): the searches keep exact values as proofs and back them up the tree (SelfPlayEngine);
     selfplay_batch.proof_stats holds the last call's SelfPlayEngine.proof_stats() (None when off).
     value_signs="sound": the searches back their values up with the signs right across passes and finished boards (SelfPlayEngine).
@@ -702,7 +748,9 @@ def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations
     (None when off)."""
     _lib.check_value_signs(value_signs)
     _lib.check_proofs(proofs, value_signs, gumbel=gumbel, forced_playouts=forced_playouts)
-    selfplay_batch.proof_stats = None
+    proof_play = _lib.check_proof_play(proof_play, proofs)
+    pt_kw = {"proof_targets": True} if _lib.check_proof_targets(proof_targets, proof_play) else {}
+    selfplay_batch.proof_stats = selfplay_batch.proof_play_stats = selfplay_batch.proof_target_stats = None
     vt_on = _lib.check_value_target(value_target, expand and alias_final)[0] != _lib.VALUE_TARGET_OUTCOME
     gumbel = _lib.check_gumbel_options(gumbel, root_noise=root_noise, forced_playouts=forced_playouts, sample_moves=sample_moves,
                                        playout_cap=playout_cap, leaves_per_step=leaves_per_step)
@@ -730,7 +778,7 @@ def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations
                          **({"forced_playouts": forced_playouts} if forced_playouts > 0.0 else {}), **({"record_values": True} if vt_on else {}),
                          **({"gumbel": gumbel} if gumbel is not None else {}), **({"record_surprise": True} if surprise_weight is not None else {}),
                          **({"resign": resign} if resign is not None else {}), **({"value_signs": value_signs} if value_signs != "reference" else {}),
-                         **_lib.proofs_kw(proofs))
+                         **_lib.proofs_kw(proofs), **_lib.proof_play_kw(proof_play))
     selfplay_batch.surprise_stats = None
 
     def weighted(ret):
@@ -741,16 +789,18 @@ def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations
     selfplay_batch.value_target_stats = None
     selfplay_batch.gumbel_stats = None
     if gumbel is not None:                                 # (the options' statistics as below; the rows come last)
-        got = eng.play_to_end(with_visits=record_visits, endgame_targets=endgame_targets, value_target=value_target, with_policies=True)
+        got = eng.play_to_end(with_visits=record_visits, endgame_targets=endgame_targets, value_target=value_target, with_policies=True, **pt_kw)
         selfplay_batch.gumbel_stats = eng.gumbel_stats()
         selfplay_batch.endgame_stats = getattr(eng, "endgame_stats", None)
         selfplay_batch.value_target_stats = getattr(eng, "value_target_stats", None)
         selfplay_batch.forced_playout_stats = selfplay_batch.playout_stats = None
         selfplay_batch.rows_solved = eng.rows_solved() if solve_leaves else None
         selfplay_batch.proof_stats = eng.proof_stats() if proofs else None
+        selfplay_batch.proof_play_stats = eng.proof_play_stats() if proof_play else None
+        selfplay_batch.proof_target_stats = getattr(eng, "proof_target_stats", None)
         return weighted(got)
     if vt_on:
-        got = eng.play_to_end(with_visits=record_visits, endgame_targets=endgame_targets, value_target=value_target)
+        got = eng.play_to_end(with_visits=record_visits, endgame_targets=endgame_targets, value_target=value_target, **pt_kw)
         rec, counts, targets = got if record_visits else (got[0], None, got[1])
         selfplay_batch.endgame_stats = getattr(eng, "endgame_stats", None)
         selfplay_batch.value_target_stats = eng.value_target_stats
@@ -759,24 +809,30 @@ def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations
         selfplay_batch.resign_stats = eng.resign_stats() if resign is not None else None
         selfplay_batch.rows_solved = eng.rows_solved() if solve_leaves else None
         selfplay_batch.proof_stats = eng.proof_stats() if proofs else None
+        selfplay_batch.proof_play_stats = eng.proof_play_stats() if proof_play else None
+        selfplay_batch.proof_target_stats = getattr(eng, "proof_target_stats", None)
         if expand:
             return expand_examples(rec, board_size, alias_final, visits=counts, target_temperature=target_temperature, values=targets)
         return weighted((rec, counts, targets) if record_visits else (rec, targets))
     selfplay_batch.endgame_stats = selfplay_batch.rows_solved = selfplay_batch.playout_stats = selfplay_batch.forced_playout_stats = None
     if record_visits:
-        rec, counts = eng.play_to_end(with_visits=True, endgame_targets=endgame_targets)
+        rec, counts = eng.play_to_end(with_visits=True, endgame_targets=endgame_targets, **pt_kw)
         selfplay_batch.forced_playout_stats = eng.forced_playout_stats() if forced_playouts > 0.0 else None
         selfplay_batch.playout_stats = eng.playout_stats() if playout_cap is not None else None
         selfplay_batch.resign_stats = eng.resign_stats() if resign is not None else None
         selfplay_batch.rows_solved = eng.rows_solved() if solve_leaves else None
         selfplay_batch.proof_stats = eng.proof_stats() if proofs else None
+        selfplay_batch.proof_play_stats = eng.proof_play_stats() if proof_play else None
+        selfplay_batch.proof_target_stats = getattr(eng, "proof_target_stats", None)
         selfplay_batch.endgame_stats = getattr(eng, "endgame_stats", None)
         return expand_examples(rec, board_size, alias_final, visits=counts, target_temperature=target_temperature) if expand else weighted((rec, counts))
-    rec = eng.play_to_end(endgame_targets=endgame_targets)
+    rec = eng.play_to_end(endgame_targets=endgame_targets, **pt_kw)
     selfplay_batch.forced_playout_stats = eng.forced_playout_stats() if forced_playouts > 0.0 else None
     selfplay_batch.playout_stats = eng.playout_stats() if playout_cap is not None else None
     selfplay_batch.resign_stats = eng.resign_stats() if resign is not None else None
     selfplay_batch.rows_solved = eng.rows_solved() if solve_leaves else None
     selfplay_batch.proof_stats = eng.proof_stats() if proofs else None
+    selfplay_batch.proof_play_stats = eng.proof_play_stats() if proof_play else None
+    selfplay_batch.proof_target_stats = getattr(eng, "proof_target_stats", None)
     selfplay_batch.endgame_stats = getattr(eng, "endgame_stats", None)
     return expand_examples(rec, board_size, alias_final) if expand else rec
