@@ -450,6 +450,49 @@ int oz_search_proof_candidates(uint64_t legal, uint64_t lo, uint64_t hi, int nod
 int oz_search_proof_backup(const uint8_t* sigma, const int32_t* square, int depth, int leaf_value, const uint64_t* legal, uint64_t* lo, uint64_t* hi,
                            const int8_t* own_value, int32_t* out3, int* conflict);
 
+/* ---- selection: first-play urgency (FPU) reduction, a visit-scaled exploration constant and a prior-first first visit (opt-in; with every
+ * part off, the default, every kernel, table, record and launch is the search above).  The reference's rule U = Q + c P sqrt(Ns) / (1 + N)
+ * values an unvisited move at Q = 0, keeps c constant, and sends the first visit of a fresh node (sqrt(0) = 0: all U equal) to the first legal
+ * square.  Three parts, each switchable on its own (KataGo / Leela Chess Zero's FPU; AlphaZero's and Lc0's c(s)).
+ * At a node S at level d of a descent, for a legal square a:
+ *   N'_a, Q'_a = the statistics as selection sees them today: the stored bits where no descent of this step is in flight on the edge, else
+ *     the virtual-loss view N + k, ((double)N * Q - (double)k) / (double)(N + k);  n = Ns + k(S), the node's visits in the same view;
+ *   P_a = the prior selection uses today: the stored P, or Pn = (1 - eps) * P + eps * eta at depth 0 of an armed noisy root;
+ *   vhat(S) = the value the node's expansion backed up, for the side to move at S: the network's v, or the solved sign under solve_leaves
+ *     (header word 3 of the node, what the Gumbel kernels keep there; oz_mcts_node_value reads it).
+ * float64, no contraction, every product, sum and quotient rounded on its own in the order written:
+ *   OZ_SELECT_GROWTH (cpuct_base > 0, cpuct_factor >= 0):  c_S = c + cpuct_factor * log(((1.0 + (double)n) + cpuct_base) / cpuct_base), the
+ *     logarithm the library's correctly rounded one (error below 2^-85);  off: c_S = c.  AlphaZero: (19652, 1); Lc0 about (38739, 3.9).
+ *   OZ_SELECT_PRIOR_FIRST:  r = n > 0 ? sqrt((double)n) : 1.0;  off: r = sqrt((double)n).  A fresh node's first visit then goes to the first
+ *     maximum of c_S * P_a (of F + c_S * P_a under FPU; F is the same for all squares).
+ *   OZ_SELECT_FPU (both reductions in [0, 4]):  f = fpu_root_reduction at d == 0, else fpu_reduction (KataGo: 0.2, and 0.1 or 0 at the
+ *     root).  With visited(a) := N'_a > 0:  SN = the integer sum of N'_a;  SQ = tree-sum over the 64 squares of
+ *     (visited ? (double)N'_a * Q'_a : 0.0);  SP = tree-sum of (visited ? P_a : 0.0);  V = (vhat + SQ) / (1.0 + (double)SN);
+ *     F = V - f * sqrt(SP), then F = -1.0 where F < -1.0.  Every legal edge with N'_a == 0 takes Q'_a := F; edges with visits keep theirs.
+ *     tree-sum = the balanced binary tree over the squares 0 .. 63 (zeros off the legal set): x_i <- x_{2i} + x_{2i+1}, six rounds.
+ *   U_a = Q'_a + (c_S * P_a) * (r / (double)(1 + N'_a)).
+ * Under proofs a known edge value replaces Q'_a after the FPU step, as before.  First-maximum tie break, the candidate sets of the proofs,
+ * the in-flight view, the stored Q / N / Ns, the backup and the move rules do not change.
+ * Supported: oz_mcts_simulate at any leaves_per_step, oz_mcts_select / leaves / backup, oz_selfplay_run, the arena, both value signs, proofs
+ * and proof play, root noise, move sampling, playout cap, solve_leaves, every recorded row and target, resignation.
+ * OZ_ERR_ARG: a value outside the ranges above (NaN included) of a part that is on, unknown flag bits.  OZ_ERR_STATE: the tree holds nodes
+ * (every node of such a tree keeps vhat: right after create or after oz_mcts_reset(-1) only) or a step is pending; the Gumbel search or
+ * forced playouts are on (their quota and pruning restate PUCT with the constant c) -- and those refuse an object with the option, whichever
+ * is set second; oz_selfplay_run_steps and oz_selfplay_stagger refuse an engine with it (the free-running kernels stay as they are).
+ * flags == 0 switches the option off; a part that is off keeps no parameters (the getter reports 0 for them). */
+#define OZ_SELECT_FPU 1
+#define OZ_SELECT_GROWTH 2
+#define OZ_SELECT_PRIOR_FIRST 4
+int oz_mcts_set_selection(oz_mcts* m, int flags, double fpu_reduction, double fpu_root_reduction, double cpuct_base, double cpuct_factor);
+int oz_mcts_get_selection(oz_mcts* m, int* flags, double* fpu_reduction, double* fpu_root_reduction, double* cpuct_base, double* cpuct_factor);
+/* the rule on the host, no device needed.  oz_search_select_c: c_S of a node with n visits.  oz_search_select_scores: one node from its rows by
+ * square -- N, Q = N', Q' above (the caller's view), P = the prior in use, Ns = n, level = d -> U[64] (-inf off the legal set); F, V (0 with
+ * FPU off), c_S and pick (the first maximum; -1 without a legal square) may be NULL. */
+int oz_search_select_c(double c, double cpuct_base, double cpuct_factor, int n, double* out);
+int oz_search_select_scores(const int32_t* N, const double* Q, const double* P, uint64_t legal, int Ns, double vhat, int level, double c, int flags,
+                            double fpu_reduction, double fpu_root_reduction, double cpuct_base, double cpuct_factor, double* U, double* F, double* V,
+                            double* c_S, int32_t* pick);
+
 /* ---- root noise: Dirichlet noise on the root prior, AlphaZero's exploration inside the search (opt-in; off, every result stays bit for bit)
  * P'(root, a) = (1 - eps) P(root, a) + eps eta_a, eta ~ Dir(alpha) over the root's legal moves, fresh for every searched move.
  * STORED PRIORS ARE NEVER MODIFIED: the node tables are transposition tables that persist across the moves of a game, so the noise is applied
@@ -664,7 +707,8 @@ int oz_mcts_get_gumbel(oz_mcts* m, double* g /* [num_games][64] */, uint8_t* arm
 int oz_mcts_gumbel_policy(oz_mcts* m, float* pi /* [num_games][64] */, int32_t* action /* [num_games] */, int32_t* rc /* [num_games] */);
 /* the scores the last oz_mcts_gumbel_policy evaluated, -inf off the legal set (inspection) */
 int oz_mcts_gumbel_scores(oz_mcts* m, double* score /* [num_games][64] */);
-/* header word 3 of a node (indices as oz_mcts_dump_node): its own value where it was expanded under the option, 0.0 elsewhere */
+/* header word 3 of a node (indices as oz_mcts_dump_node): its own value where it was expanded under the option -- or under the selection
+ * option ("selection": vhat) --, 0.0 elsewhere */
 int oz_mcts_node_value(oz_mcts* m, int game, int index, double* value);
 /* the host-only twins (no device needed).  oz_gumbel_considered_visits: out[n], m in [1, 64].  oz_gumbel_draws: g[count][64] of `count` roots from
  * their keys and legal sets.  oz_gumbel_from_units: g of given unit draws u in [0, 1) (the endpoint mapping above).  oz_gumbel_root: pick, move and
@@ -763,6 +807,9 @@ int oz_selfplay_get_solve_leaves(oz_selfplay* sp, int* max_empties, int64_t* row
  * the default: sound mode differs on finished boards and across passes); OZ_ERR_STATE after the first driver call */
 int oz_selfplay_set_value_signs(oz_selfplay* sp, int mode);
 int oz_selfplay_get_value_signs(oz_selfplay* sp, int* mode);
+/* the selection rule of the engine's search (see oz_mcts_set_selection), for oz_selfplay_run; OZ_ERR_STATE after the first driver call */
+int oz_selfplay_set_selection(oz_selfplay* sp, int flags, double fpu_reduction, double fpu_root_reduction, double cpuct_base, double cpuct_factor);
+int oz_selfplay_get_selection(oz_selfplay* sp, int* flags, double* fpu_reduction, double* fpu_root_reduction, double* cpuct_base, double* cpuct_factor);
 /* proofs of the engine's search (see oz_mcts_set_proofs; after oz_selfplay_set_value_signs(sp, OZ_VALUE_SIGNS_SOUND)), for oz_selfplay_run;
  * OZ_ERR_STATE after the first driver call.  oz_selfplay_proof_stats: as oz_mcts_proof_stats, over the engine's games so far. */
 int oz_selfplay_set_proofs(oz_selfplay* sp, int enable);
@@ -1062,6 +1109,8 @@ int oz_selfplay_set_proof_play(oz_selfplay* sp, int enable);
 int oz_selfplay_proof_play_stats(oz_selfplay* sp, int64_t* out4);
 /* per agent (black for net_a's search, white for net_b's); needs that agent's proofs; before the first run */
 int oz_arena_set_proof_play(oz_arena* a, int black, int white);
+/* the selection rule of one agent's search (see oz_mcts_set_selection): agent +1 = BLACK (net_a), -1 = WHITE (net_b); before the first run */
+int oz_arena_set_selection(oz_arena* a, int agent, int flags, double fpu_reduction, double fpu_root_reduction, double cpuct_base, double cpuct_factor);
 /* the bare search: oz_mcts_root_counts / oz_mcts_root_values with the rule's row and value (same shapes and rc); OZ_ERR_STATE on an object
  * without proofs.  oz_mcts_root_counts and oz_mcts_root_values stay the raw ones. */
 int oz_mcts_proven_counts(oz_mcts* m, int32_t* counts /* [G][64] */, uint64_t* legal /* [G] */, int32_t* rc /* [G] */);

@@ -213,6 +213,14 @@ SIGNATURES = {
     "oz_arena_set_value_signs": [_vp, C.c_int, C.c_int],
     "oz_search_backup_values": [C.c_int, C.c_uint64, C.c_int, C.c_double, _f64p, _f64p],
     "oz_search_terminal_value": [C.c_int, C.c_uint64, C.c_uint64, C.POINTER(C.c_int)],
+    "oz_mcts_set_selection": [_vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double],
+    "oz_mcts_get_selection": [_vp, C.POINTER(C.c_int), _f64p, _f64p, _f64p, _f64p],
+    "oz_selfplay_set_selection": [_vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double],
+    "oz_selfplay_get_selection": [_vp, C.POINTER(C.c_int), _f64p, _f64p, _f64p, _f64p],
+    "oz_arena_set_selection": [_vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double],
+    "oz_search_select_c": [C.c_double, C.c_double, C.c_double, C.c_int, _f64p],
+    "oz_search_select_scores": [_i32p, _f64p, _f64p, C.c_uint64, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int, C.c_double, C.c_double, C.c_double,
+                                C.c_double, _f64p, _f64p, _f64p, _f64p, _i32p],
     "oz_mcts_set_proofs": [_vp, C.c_int], "oz_mcts_get_proofs": [_vp, C.POINTER(C.c_int)],
     "oz_mcts_dump_proofs": [_vp, C.c_int, C.c_int, _i8p, _i8p, _i8p], "oz_mcts_root_proofs": [_vp, _i8p, _i8p, _i32p],
     "oz_mcts_proof_stats": [_vp, _i64p], "oz_selfplay_set_proofs": [_vp, C.c_int], "oz_selfplay_proof_stats": [_vp, _i64p],
@@ -702,6 +710,85 @@ def check_value_signs_pair(value_signs):
         return check_value_signs(value_signs[0], "value_signs[black]"), check_value_signs(value_signs[1], "value_signs[white]")
     m = check_value_signs(value_signs)
     return m, m
+
+
+SELECT_FPU, SELECT_GROWTH, SELECT_PRIOR_FIRST = 1, 2, 4     # OZ_SELECT_*
+SELECTION_KEYS = ("fpu", "cpuct_growth", "prior_first")
+
+
+def _selection_pair(value, what, lo_open, hi):
+    """two finite floats; the first in (0, inf) where lo_open, else both in [0, hi]"""
+    if isinstance(value, (str, bytes)) or not hasattr(value, "__len__") or len(value) != 2:
+        raise ValueError(f"{what} must be a pair of numbers (got {value!r})")
+    out = []
+    for i, x in enumerate(value):
+        if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)):
+            raise ValueError(f"{what}[{i}] must be a number (got {x!r})")
+        x = float(x)
+        low_ok = x > 0.0 if (lo_open and i == 0) else x >= 0.0
+        if not (low_ok and x <= hi and x != float("inf")):              # (NaN fails the compares)
+            raise ValueError(f"{what}[{i}] = {x!r} outside the range the library takes")
+        out.append(x)
+    return tuple(out)
+
+
+def check_selection(selection, what="selection", gumbel=None, forced_playouts=None):
+    """selection=None | dict(fpu=(reduction, root_reduction), cpuct_growth=(base, factor), prior_first=bool) of the searches
+    (oz_mcts_set_selection; include/othellozero_amd.h, "selection") -> (flags, fpu_reduction, fpu_root_reduction, cpuct_base, cpuct_factor),
+    flags == 0 where every part is off.  ValueError for anything the library would refuse -- both reductions in [0, 4], base > 0, factor >= 0,
+    all finite -- and for the Gumbel search or forced playouts beside it, before the library is touched."""
+    if selection is None:
+        return (0, 0.0, 0.0, 0.0, 0.0)
+    if not isinstance(selection, dict):
+        raise ValueError(f"{what} must be None or a dict with the keys {SELECTION_KEYS} (got {selection!r})")
+    unknown = [k for k in selection if k not in SELECTION_KEYS]
+    if unknown:
+        raise ValueError(f"{what}: unknown key(s) {unknown!r} (known: {SELECTION_KEYS})")
+    flags, fpu, growth = 0, (0.0, 0.0), (0.0, 0.0)
+    if selection.get("fpu") is not None:
+        fpu = _selection_pair(selection["fpu"], f"{what}['fpu']", False, 4.0)
+        flags |= SELECT_FPU
+    if selection.get("cpuct_growth") is not None:
+        growth = _selection_pair(selection["cpuct_growth"], f"{what}['cpuct_growth']", True, float("inf"))
+        flags |= SELECT_GROWTH
+    pf = selection.get("prior_first", False)
+    if not isinstance(pf, (bool, np.bool_)):
+        raise ValueError(f"{what}['prior_first'] must be True or False (got {pf!r})")
+    if pf:
+        flags |= SELECT_PRIOR_FIRST
+    if flags and gumbel is not None:
+        raise ValueError(f"{what} does not combine with the Gumbel search (its root rule is not PUCT)")
+    if flags and forced_playouts:
+        raise ValueError(f"{what} does not combine with forced playouts (their quota and pruning restate PUCT with the constant c)")
+    return (flags, fpu[0], fpu[1], growth[0], growth[1])
+
+
+def check_selection_pair(selection):
+    """arena_batch(selection=one value or (black, white)) -> (checked, checked)"""
+    if isinstance(selection, (tuple, list)):
+        if len(selection) != 2:
+            raise ValueError(f"selection must be one value or (black, white) (got {selection!r})")
+        return check_selection(selection[0], "selection[black]"), check_selection(selection[1], "selection[white]")
+    s = check_selection(selection)
+    return s, s
+
+
+def selection_dict(checked):
+    """the keyword's form of a checked selection (what OthelloMCTS.selection reads back): None where the option is off"""
+    flags, f, fr, b, k = checked
+    if not flags:
+        return None
+    return dict(fpu=(f, fr) if flags & SELECT_FPU else None, cpuct_growth=(b, k) if flags & SELECT_GROWTH else None,
+                prior_first=bool(flags & SELECT_PRIOR_FIRST))
+
+
+def selection_kw(selection):
+    """the keyword to pass on: nothing where the option is off, so that callers without it see the calls they always saw"""
+    if isinstance(selection, (tuple, list)):
+        on = any(check_selection(x)[0] for x in selection)
+    else:
+        on = check_selection(selection)[0]
+    return {"selection": selection} if on else {}
 
 
 PROOF_UNKNOWN = -128                            # OZ_PROOF_UNKNOWN

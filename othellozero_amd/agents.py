@@ -104,6 +104,31 @@ def rules_terminal_value(value_signs, own, opp):
     return v.value
 
 
+def rules_select_c(c, base, factor, n):
+    """oz_search_select_c: the visit-scaled exploration constant of a node with n visits, on the host (no GPU needed):
+    c + factor * log(((1.0 + n) + base) / base) with the library's correctly rounded logarithm (include/othellozero_amd.h, "selection")"""
+    out = C.c_double()
+    _lib.check(_lib.load().oz_search_select_c(float(c), float(base), float(factor), int(n), C.byref(out)))
+    return out.value
+
+
+def rules_select_scores(N, Q, P, legal, Ns, vhat, level, c, selection):
+    """oz_search_select_scores: the selection rule at one node, on the host (no GPU needed).  N, Q, P = 64 entries by square as selection sees
+    them (the caller's in-flight view and noisy prior), legal = the mask, Ns = the node's visits in that view, vhat = the value its expansion
+    backed up, level = its depth in the descent, c = the exploration constant, selection = the keyword's dict (or None).
+    -> dict(U float64 (64,) with -inf off the legal set, F, V (0.0 with FPU off), c_S, pick = the first maximum or -1)"""
+    flags, f, fr, b, k = _lib.check_selection(selection)
+    N = np.ascontiguousarray(N, dtype=np.int32).ravel()
+    Q = np.ascontiguousarray(Q, dtype=np.float64).ravel()
+    P = np.ascontiguousarray(P, dtype=np.float64).ravel()
+    if not (N.size == Q.size == P.size == 64):
+        raise ValueError("rules_select_scores: N, Q and P take 64 entries by square")
+    U, F, V, cS, pick = np.zeros(64, np.float64), C.c_double(), C.c_double(), C.c_double(), C.c_int32()
+    _lib.check(_lib.load().oz_search_select_scores(_lib.p_i32(N), _lib.p_f64(Q), _lib.p_f64(P), int(legal), int(Ns), float(vhat), int(level), float(c),
+                                                   flags, f, fr, b, k, _lib.p_f64(U), C.byref(F), C.byref(V), C.byref(cS), C.byref(pick)))
+    return dict(U=U, F=F.value, V=V.value, c_S=cS.value, pick=pick.value)
+
+
 def _proof_masks(edge):
     """edge proofs by square (-1 / 0 / +1, anything else = unknown) -> the two masks (lo, hi) of the library's entry: state = e + 2"""
     lo = hi = 0
@@ -431,9 +456,12 @@ class NeuralNetworkOthelloAgent(OthelloAgent):
     the first valid action with the largest policy entry."""
 
     def __init__(self, game, neural_network, num_simulations, degree_exploration, temperature=0,
-                 q_mode=_lib.QMODE_F64, leaves_per_step=1, solve_leaves=0, value_signs="reference", proofs=False, proof_play=False):
-        """proof_play=True (needs proofs=True): the move is the arg-max of the row the root's proofs keep (OthelloMCTS.proven_counts)"""
+                 q_mode=_lib.QMODE_F64, leaves_per_step=1, solve_leaves=0, value_signs="reference", proofs=False, proof_play=False,
+                 selection=None):
+        """proof_play=True (needs proofs=True): the move is the arg-max of the row the root's proofs keep (OthelloMCTS.proven_counts)
+        selection: the selection rule of the agent's search (OthelloMCTS, selection)"""
         solve_leaves = _lib.check_solve_leaves(solve_leaves)
+        _lib.check_selection(selection)
         _lib.check_value_signs(value_signs)
         _lib.check_proofs(proofs, value_signs)
         self.proof_play = _lib.check_proof_play(proof_play, proofs)
@@ -444,7 +472,7 @@ class NeuralNetworkOthelloAgent(OthelloAgent):
         self.mcts = OthelloMCTS(side, neural_network, degree_exploration, q_mode=q_mode,
                                 node_cap=num_simulations * (side * side // 2) + 64, leaves_per_step=leaves_per_step,
                                 solve_leaves=solve_leaves, value_signs=value_signs, **_lib.proofs_kw(proofs),
-                                **_lib.proof_play_kw(self.proof_play))
+                                **_lib.proof_play_kw(self.proof_play), **_lib.selection_kw(selection))
 
     def play(self):
         game = self.game
@@ -475,7 +503,7 @@ def duel_between_agents(game, agent_1, agent_2):
 def arena_batch(net_a, net_b, board_size=8, num_games=512, num_simulations=800, degree_exploration=1.0, seed=0,
                 first_game_id=0, q_mode=_lib.QMODE_F64, node_cap=0, max_rounds=0, dedup=True, profile=False, eval_cache=False,
                 leaves_per_step=1, opponent=None, solve_leaves=0, openings=None, first_opening_id=0, opening_moves=None,
-                value_signs="reference", proofs=False, proof_play=False):
+                value_signs="reference", proofs=False, proof_play=False, selection=None):
     """num_games games of net_a (BLACK) vs net_b (WHITE), temperature 0, max-visit ties broken by the RNG_TIE
     stream keyed (seed, game id, ply).  One of the two may be None: RandomOthelloAgent plays that colour, or with
     opponent=("minimax", depth) / ("minimax", depth, "discs" | "weighted") the fixed-depth minimax (oz_arena_set_opponent; ties between its
@@ -497,6 +525,8 @@ def arena_batch(net_a, net_b, board_size=8, num_games=512, num_simulations=800, 
     OthelloMCTS, proofs); an agent with proofs needs value_signs "sound".  The moves read the raw counts as before.
     proof_play = True | False or (black, white): the agent's move is the arg-max -- ties as ever -- of the row its root's proofs keep
     (oz_arena_set_proof_play; include/othellozero_amd.h, "proof play"); needs that agent's proofs.
+    selection = None | dict(fpu=, cpuct_growth=, prior_first=) or (black, white): the selection rule of the agent's search
+    (oz_arena_set_selection; OthelloMCTS, selection); an agent without a network searches nothing.
     openings = (plies, opening_seed): every game first plays a random opening of `plies` plies (at most 16) without any search
     (oz_arena_set_openings, rules_random_openings); game slot g plays opening first_opening_id + g whatever seed and first_game_id are, so two
     arenas given the same (openings, first_opening_id) start from the same positions.  opening_moves = (moves uint8 (num_games, 16), n_plies int32
@@ -508,6 +538,7 @@ def arena_batch(net_a, net_b, board_size=8, num_games=512, num_simulations=800, 
     vb_, vw_ = _lib.check_value_signs_pair(value_signs)
     pb_, pw_ = _lib.check_proofs_pair(proofs, value_signs)
     ppb_, ppw_ = _lib.check_proof_play_pair(proof_play, (pb_, pw_))
+    sel_pair = _lib.check_selection_pair(selection)
     kb, kw = (leaves_per_step, leaves_per_step) if np.isscalar(leaves_per_step) else leaves_per_step
     minimax = _lib.check_opponents(opponent, net_a is None, net_b is None)
     lib = _lib.require_gpu()
@@ -530,6 +561,9 @@ def arena_batch(net_a, net_b, board_size=8, num_games=512, num_simulations=800, 
             _lib.check(lib.oz_arena_set_proofs(h, int(pb_), int(pw_)))
         if ppb_ or ppw_:
             _lib.check(lib.oz_arena_set_proof_play(h, int(ppb_), int(ppw_)))
+        for side, sel in zip((1, -1), sel_pair):
+            if sel[0]:
+                _lib.check(lib.oz_arena_set_selection(h, side, *sel))
         if opening is not None and opening[0] == "random":
             _lib.check(lib.oz_arena_set_openings(h, opening[1], opening[2], opening[3]))
         elif opening is not None:

@@ -501,6 +501,56 @@ OZ_HD int oz_proof_code(int val) { return val == OZ_PROOF_NONE ? 0 : val + 2; } 
 // the sign a proof code gives oz_record.z (a draw follows z's convention: BLACK's win); code != 0
 OZ_HD int oz_proof_code_z(int code, int player) { return code == 3 ? 1 : code == 1 ? -1 : player == 1 ? 1 : -1; }
 
+// ---------------------------------------------------------------- selection: FPU reduction, visit-scaled c_puct, prior-first (opt-in)
+// (include/othellozero_amd.h, "selection").  At a node S at level d of a descent, for a legal square a: N', Q' = the statistics as selection sees
+// them (stored, or the virtual-loss view), n = Ns + k(S) the node's visits in that view, P the prior selection uses (the noisy one at an armed
+// root), vhat the value the node's expansion backed up (header word 3).  float64, no contraction, every product, sum and quotient rounded on
+// its own in the order written:
+//     growth:      c_S = c + factor * oz_log_cr(((1.0 + (double)n) + base) / base)                     off: c_S = c
+//     prior-first: r = n > 0 ? sqrt((double)n) : 1.0                                                    off: r = sqrt((double)n)
+//     FPU:         f = d == 0 ? root_reduction : reduction;  visited(a) := N'_a > 0;  SN = the integer sum of N'_a,
+//                  SQ = tree-sum of (visited ? (double)N'_a * Q'_a : 0.0),  SP = tree-sum of (visited ? P_a : 0.0),
+//                  V = (vhat + SQ) / (1.0 + (double)SN),  F = V - f * sqrt(SP), and F = -1.0 where F < -1.0;
+//                  a legal edge with N'_a == 0 takes Q'_a := F
+//     U_a = Q'_a + (c_S * P_a) * (r / (double)(1 + N'_a))
+// tree-sum: the balanced binary tree over the squares 0 .. 63 (x_i <- x_{2i} + x_{2i+1}, six rounds), zeros off the legal set -- one xor
+// butterfly of the wave (wave_tree_sum_f64, oz_search.hip; addition commutes, so every lane ends with the same bits), oz_tree_sum64 on the host.
+// The one definition the SEL instantiations of descend_one and the host's oz_search_select_c / oz_search_select_scores share.
+#define OZ_SEL_FPU 1
+#define OZ_SEL_GROWTH 2
+#define OZ_SEL_PRIOR_FIRST 4
+struct OzSelection { int flags; double fpu, fpu_root, base, factor; };    // flags == 0: off
+OZ_HD double oz_select_c(double c, double base, double factor, int n) {
+#pragma clang fp contract(off)
+    return c + factor * oz_log_cr(((1.0 + (double)n) + base) / base);
+}
+OZ_HD double oz_select_r(int prior_first, int n) {
+#pragma clang fp contract(off)
+    return prior_first && n <= 0 ? 1.0 : sqrt((double)n);
+}
+OZ_HD double oz_select_fpu_q(int N, double Q) {
+#pragma clang fp contract(off)
+    return N > 0 ? (double)N * Q : 0.0;
+}
+OZ_HD double oz_select_fpu(double vhat, double SQ, double SP, int SN, double f, double* V) {
+#pragma clang fp contract(off)
+    *V = (vhat + SQ) / (1.0 + (double)SN);
+    const double F = *V - f * sqrt(SP);
+    return F < -1.0 ? -1.0 : F;
+}
+OZ_HD double oz_select_u(double Q, double cS, double P, double r, int N) {
+#pragma clang fp contract(off)
+    return Q + (cS * P) * (r / (double)(1 + N));
+}
+__host__ __device__ inline double oz_tree_sum64(const double* x /* [64] */) {
+#pragma clang fp contract(off)
+    double s[64];
+    for (int i = 0; i < 64; ++i) s[i] = x[i];
+    for (int w = 32; w >= 1; w >>= 1)
+        for (int i = 0; i < w; ++i) s[i] = s[2 * i] + s[2 * i + 1];
+    return s[0];
+}
+
 // ---------------------------------------------------------------- root value and value targets
 // (include/othellozero_amd.h, "value targets").  The root value of a search: the visit-weighted mean of the root's Q, for the player to
 // move.  a[sq] = oz_root_term: (double)N * Q where N > 0, else 0 (counts are 0 off the legal set); oz_root_mean = pairwise_sum(a, 64) /

@@ -96,6 +96,7 @@ struct MctsDev {
     double noise_eps;          // the mixing weight (0: off)
     double forced_k;           // forced playouts ("forced playouts" below): the forcing constant k (0: off); needs noise, so the *_n kernels alone read it
     ProofDev pf;               // proofs ("proofs" below): null / 0 until oz_*_set_proofs; the OZ_VSIGNS_PROVEN instantiations alone read it
+    OzSelection sel;           // selection ("selection" in oz_common.h): flags == 0 until oz_*_set_selection; the *_sel kernels alone read it
 };
 // the frontier entries (node, edge rank): the rank is below 64; in the sound instantiations (VS, "value signs" in oz_common.h) bit 30 of .y keeps
 // sigma of the level -- the descent swapped sides after the edge.  The reference instantiations never set the bit and read .y as it is.
@@ -136,6 +137,13 @@ __device__ __forceinline__ double wave_max_f64(double x) {
         double y = __shfl_xor(x, off, 64);
         x = y > x ? y : x;
     }
+    return x;
+}
+// the balanced binary tree sum over the lanes 0 .. 63 (oz_tree_sum64, oz_common.h): round r adds the partner lane ^ (1 << r); addition
+// commutes, so every lane ends with the same bits
+__device__ __forceinline__ double wave_tree_sum_f64(double x) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) x += __shfl_xor(x, off, 64);
     return x;
 }
 __device__ __forceinline__ int wave_max_i32(int x) {
@@ -379,7 +387,8 @@ struct Descent {
 // GUMBEL (the *_g kernels): gr = the slot's Gumbel view (gumbel_of_slot); on an armed root, depth 0 picks by the Gumbel rule instead of PUCT.
 struct GumbelRoot { bool armed; double g; int n0; const GumbelDev* gd; };
 // VS: the value signs the tree holds (oz_common.h), a template argument of every tree kernel: the default's code is the reference rule alone
-template <bool NOISE, bool GUMBEL = false, int VS = OZ_VSIGNS_REFERENCE>
+// SEL (the *_sel kernels): U by the selection rule of oz_common.h ("selection"); t.sel is uniform: one branch per part and wave
+template <bool NOISE, bool GUMBEL = false, int VS = OZ_VSIGNS_REFERENCE, bool SEL = false>
 __device__ __forceinline__ Descent descend_one(const MctsDev& t, uint4* rec, int2* path, int g, int lane, uint64_t own, uint64_t opp, uint64_t legal,
                                                int& rootn, bool noisy, double eta, const InFlight fl, const GumbelRoot gr = GumbelRoot{false, 0.0, 0, nullptr}) {
     int depth = 0, status, tval = 0, err = 0, fs = -1;
@@ -469,6 +478,41 @@ __device__ __forceinline__ Descent descend_one(const MctsDev& t, uint4* rec, int
                 }
             }
         }
+        if constexpr (SEL) {
+            int N = 0;
+            double Q = 0.0, P = 0.0;
+            if (is_legal) {
+                N = (int)((uint32_t)w[4 + 3 * rank] & ~OZ_TAG_F32);
+                Q = __longlong_as_double((long long)w[5 + 3 * rank]);
+                P = __longlong_as_double((long long)w[6 + 3 * rank]);
+                if (ke) {
+                    Q = ((double)N * Q - (double)ke) / (double)(N + ke);
+                    N += ke;
+                }
+                if constexpr (NOISE) {
+                    if (noisy && depth == 0) P = (1.0 - t.noise_eps) * P + t.noise_eps * eta;
+                }
+            }
+            const int nv = Ns + ks;
+            const double cS = (t.sel.flags & OZ_SEL_GROWTH) ? oz_select_c(t.c, t.sel.base, t.sel.factor, nv) : t.c;
+            const double r = oz_select_r(t.sel.flags & OZ_SEL_PRIOR_FIRST, nv);
+            if (t.sel.flags & OZ_SEL_FPU) {
+                const bool vis = is_legal && N > 0;
+                const int SN = wave_sum_i32(is_legal ? N : 0);
+                const double SQ = wave_tree_sum_f64(vis ? oz_select_fpu_q(N, Q) : 0.0);
+                const double SP = wave_tree_sum_f64(vis ? P : 0.0);
+                double V;
+                const double F = oz_select_fpu(__longlong_as_double((long long)w[3]), SQ, SP, SN, depth == 0 ? t.sel.fpu_root : t.sel.fpu, &V);
+                if (!vis) Q = F;
+            }
+            if (is_legal) {
+                if constexpr (VS == OZ_VSIGNS_PROVEN) {
+                    const int e = oz_proof_edge(plo, phi, lane);
+                    if (e != OZ_PROOF_NONE) Q = (double)e;
+                }
+                U = oz_select_u(Q, cS, P, r, N);
+            }
+        }
         bool cand = is_legal;
         if constexpr (VS == OZ_VSIGNS_PROVEN) {
             cand = (pcand >> lane) & 1;
@@ -535,7 +579,7 @@ __device__ __forceinline__ GumbelRoot gumbel_of_slot(const GumbelDev& gd, int g,
     }
     return gr;
 }
-template <bool NOISE = false, bool GUMBEL = false, int VS = OZ_VSIGNS_REFERENCE>
+template <bool NOISE = false, bool GUMBEL = false, int VS = OZ_VSIGNS_REFERENCE, bool SEL = false>
 __device__ __forceinline__ int select_body(const MctsDev& t, TreeLds& L, int g, int lane, const GumbelDev* gd = nullptr) {
     if (!t.active[g]) {
         if (lane == 0) t.leaf_status[g] = OZ_LEAF_IDLE;
@@ -547,7 +591,7 @@ __device__ __forceinline__ int select_body(const MctsDev& t, TreeLds& L, int g, 
     int rootn = unii(t.root_node[g]);
     GumbelRoot gr{false, 0.0, 0, nullptr};
     if constexpr (GUMBEL) gr = gumbel_of_slot(*gd, g, lane);
-    const Descent e = descend_one<NOISE, GUMBEL, VS>(t, L.rec, L.path, g, lane, own, opp, oz_legal(own, opp, t.valid), rootn, noisy, eta, InFlight{nullptr, nullptr, 0}, gr);
+    const Descent e = descend_one<NOISE, GUMBEL, VS, SEL>(t, L.rec, L.path, g, lane, own, opp, oz_legal(own, opp, t.valid), rootn, noisy, eta, InFlight{nullptr, nullptr, 0}, gr);
     __syncthreads();
     if (lane < e.depth) t.path[(size_t)g * OZ_MAX_DEPTH + lane] = L.path[lane];          // the frontier, one coalesced store
     if (lane == 0) {
@@ -571,6 +615,17 @@ template <int VS = OZ_VSIGNS_REFERENCE>
 __global__ __launch_bounds__(64) void k_select_n(MctsDev t) {
     __shared__ TreeLds L;
     select_body<true, false, VS>(t, L, blockIdx.x, threadIdx.x);
+}
+// (the *_sel kernels: the same kernels over the SEL = true bodies, launched by objects with the selection option)
+template <int VS = OZ_VSIGNS_REFERENCE>
+__global__ __launch_bounds__(64) void k_select_sel(MctsDev t) {
+    __shared__ TreeLds L;
+    select_body<false, false, VS, true>(t, L, blockIdx.x, threadIdx.x);
+}
+template <int VS = OZ_VSIGNS_REFERENCE>
+__global__ __launch_bounds__(64) void k_select_n_sel(MctsDev t) {
+    __shared__ TreeLds L;
+    select_body<true, false, VS, true>(t, L, blockIdx.x, threadIdx.x);
 }
 // (the *_g kernels: the same kernels over the GUMBEL = true bodies, launched by objects with the Gumbel search switched on)
 template <int VS = OZ_VSIGNS_REFERENCE>
@@ -874,8 +929,9 @@ __device__ __forceinline__ void backup_one(const MctsDev& t, int g, int lane, in
     }
 }
 // expand the leaf if it needs it, then back its value up along its path.  GUMBEL: the new node's header keeps the value the expansion backs
-// up, before negation (the network's v, or the exact one where solve_leaves replaced it) -- vhat of the completed-Q formula, in header word 3
-template <bool GUMBEL = false, int VS = OZ_VSIGNS_REFERENCE>
+// up, before negation (the network's v, or the exact one where solve_leaves replaced it) -- vhat of the completed-Q formula, in header word 3.
+// SEL: the same word, vhat of the selection rule's FPU
+template <bool GUMBEL = false, int VS = OZ_VSIGNS_REFERENCE, bool SEL = false>
 __device__ __forceinline__ void expand_backup_one(const MctsDev& t, TreeLds& L, int g, int lane, const LeafRef& lf) {
     const int status = lf.status;
     if (status == OZ_LEAF_IDLE || status == OZ_LEAF_WAIT) return;           // (WAIT: the leaf was not in the batch, nothing to expand yet)
@@ -904,7 +960,7 @@ __device__ __forceinline__ void expand_backup_one(const MctsDev& t, TreeLds& L, 
             uint64_t* w = reinterpret_cast<uint64_t*>(L.rec);
             if (lane == 0) {
                 w[0] = own; w[1] = opp; w[2] = (uint64_t)(uint32_t)cnt << 32; w[3] = 0;
-                if constexpr (GUMBEL) w[3] = (uint64_t)__double_as_longlong((double)t.v[slot]);
+                if constexpr (GUMBEL || SEL) w[3] = (uint64_t)__double_as_longlong((double)t.v[slot]);
             }
             if (is_legal) {
                 const int rank = oz_popc(legal & ((1ULL << lane) - 1ULL));
@@ -956,7 +1012,7 @@ template <int VS>
 __device__ __forceinline__ void backup_body(const MctsDev& t, int g, int lane, double value, int vt) {
     backup_one<VS>(t, g, lane, t.depth[g], t.path + (size_t)g * OZ_MAX_DEPTH, value, vt);
 }
-template <bool GUMBEL = false, int VS = OZ_VSIGNS_REFERENCE>
+template <bool GUMBEL = false, int VS = OZ_VSIGNS_REFERENCE, bool SEL = false>
 __device__ __forceinline__ void expand_backup_body(const MctsDev& t, TreeLds& L, int g, int lane, int slot_is_game) {
     LeafRef lf;
     lf.status = unii(t.leaf_status[g]);
@@ -965,7 +1021,7 @@ __device__ __forceinline__ void expand_backup_body(const MctsDev& t, TreeLds& L,
     lf.fs = unii(t.leaf_fs[g]);
     lf.depth = unii(t.depth[g]); lf.tval = unii(t.term_value[g]);
     lf.path = t.path + (size_t)g * OZ_MAX_DEPTH;
-    expand_backup_one<GUMBEL, VS>(t, L, g, lane, lf);
+    expand_backup_one<GUMBEL, VS, SEL>(t, L, g, lane, lf);
 }
 template <int VS = OZ_VSIGNS_REFERENCE>
 __global__ __launch_bounds__(64) void k_expand_backup(MctsDev t, int slot_is_game) {
@@ -989,6 +1045,27 @@ __global__ __launch_bounds__(64) void k_backup_select_n(MctsDev t) {
     wave_sync();
     __syncthreads();
     select_body<true, false, VS>(t, L, blockIdx.x, threadIdx.x);
+}
+template <int VS = OZ_VSIGNS_REFERENCE>
+__global__ __launch_bounds__(64) void k_expand_backup_sel(MctsDev t, int slot_is_game) {
+    __shared__ TreeLds L;
+    expand_backup_body<false, VS, true>(t, L, blockIdx.x, threadIdx.x, slot_is_game);
+}
+template <int VS = OZ_VSIGNS_REFERENCE>
+__global__ __launch_bounds__(64) void k_backup_select_sel(MctsDev t) {
+    __shared__ TreeLds L;
+    expand_backup_body<false, VS, true>(t, L, blockIdx.x, threadIdx.x, 0);
+    wave_sync();
+    __syncthreads();
+    select_body<false, false, VS, true>(t, L, blockIdx.x, threadIdx.x);
+}
+template <int VS = OZ_VSIGNS_REFERENCE>
+__global__ __launch_bounds__(64) void k_backup_select_n_sel(MctsDev t) {
+    __shared__ TreeLds L;
+    expand_backup_body<false, VS, true>(t, L, blockIdx.x, threadIdx.x, 0);
+    wave_sync();
+    __syncthreads();
+    select_body<true, false, VS, true>(t, L, blockIdx.x, threadIdx.x);
 }
 template <int VS = OZ_VSIGNS_REFERENCE>
 __global__ __launch_bounds__(64) void k_expand_backup_g(MctsDev t, int slot_is_game) {
@@ -1044,7 +1121,7 @@ struct WideLds {
     int depth[OZ_WK], status[OZ_WK];
 };
 
-template <bool NOISE = false, int VS = OZ_VSIGNS_REFERENCE>
+template <bool NOISE = false, int VS = OZ_VSIGNS_REFERENCE, bool SEL = false>
 __device__ __forceinline__ void wide_select_body(const MctsDev& t, const WideDev& w, WideLds& L, int g, int lane) {
     const int left = t.active[g] ? unii(w.left[g]) : 0;
     const int nd = left < w.K ? left : w.K;
@@ -1060,7 +1137,7 @@ __device__ __forceinline__ void wide_select_body(const MctsDev& t, const WideDev
     int count = 0, coll = 0, leaves = 0, nterm = 0, visits = 0, err = 0;
     const size_t gb = (size_t)g * OZ_WK;
     for (int j = 0; j < nd; ++j) {
-        const Descent e = descend_one<NOISE, false, VS>(t, L.t.rec, L.path[j], g, lane, rown, ropp, rlegal, rootn, noisy, eta, InFlight{L.path, L.depth, j});
+        const Descent e = descend_one<NOISE, false, VS, SEL>(t, L.t.rec, L.path[j], g, lane, rown, ropp, rlegal, rootn, noisy, eta, InFlight{L.path, L.depth, j});
         if (e.err) { err = e.err; break; }                                      // the step stops here for this game (nothing of this descent is stored)
         if (e.status == OZ_LEAF_EVAL) {
             bool same = false;
@@ -1094,7 +1171,7 @@ __device__ __forceinline__ void wide_select_body(const MctsDev& t, const WideDev
 }
 
 // per game, j ascending: expand leaf j / take the terminal value, back it up along path j
-template <int VS = OZ_VSIGNS_REFERENCE>
+template <int VS = OZ_VSIGNS_REFERENCE, bool SEL = false>
 __device__ __forceinline__ void wide_expand_backup_body(const MctsDev& t, const WideDev& w, WideLds& L, int g, int lane) {
     const int count = unii(w.count[g]);
     if (count <= 0) return;
@@ -1113,7 +1190,7 @@ __device__ __forceinline__ void wide_expand_backup_body(const MctsDev& t, const 
             if (ht_find(t, g, lf.own, lf.opp, lane, &fs) >= 0) fs = -1;          // (cannot be in the table: the step holds a board once)
             lf.fs = fs;
         }
-        expand_backup_one<false, VS>(t, L.t, g, lane, lf);
+        expand_backup_one<false, VS, SEL>(t, L.t, g, lane, lf);
         wave_sync();                                                            // records, table entry, Q / N of this descent before the next one's loads
         __syncthreads();
     }
@@ -1154,6 +1231,38 @@ __global__ __launch_bounds__(64) void k_wide_backup_select_n(MctsDev t, WideDev 
     wave_sync();
     __syncthreads();
     wide_select_body<true, VS>(t, w, L, blockIdx.x, threadIdx.x);
+}
+// (the *_sel kernels of the leaf-parallel search: the SEL = true bodies)
+template <int VS = OZ_VSIGNS_REFERENCE>
+__global__ __launch_bounds__(64) void k_wide_select_sel(MctsDev t, WideDev w) {
+    __shared__ WideLds L;
+    wide_select_body<false, VS, true>(t, w, L, blockIdx.x, threadIdx.x);
+}
+template <int VS = OZ_VSIGNS_REFERENCE>
+__global__ __launch_bounds__(64) void k_wide_select_n_sel(MctsDev t, WideDev w) {
+    __shared__ WideLds L;
+    wide_select_body<true, VS, true>(t, w, L, blockIdx.x, threadIdx.x);
+}
+template <int VS = OZ_VSIGNS_REFERENCE>
+__global__ __launch_bounds__(64) void k_wide_expand_backup_sel(MctsDev t, WideDev w) {
+    __shared__ WideLds L;
+    wide_expand_backup_body<VS, true>(t, w, L, blockIdx.x, threadIdx.x);
+}
+template <int VS = OZ_VSIGNS_REFERENCE>
+__global__ __launch_bounds__(64) void k_wide_backup_select_sel(MctsDev t, WideDev w) {
+    __shared__ WideLds L;
+    wide_expand_backup_body<VS, true>(t, w, L, blockIdx.x, threadIdx.x);
+    wave_sync();
+    __syncthreads();
+    wide_select_body<false, VS, true>(t, w, L, blockIdx.x, threadIdx.x);
+}
+template <int VS = OZ_VSIGNS_REFERENCE>
+__global__ __launch_bounds__(64) void k_wide_backup_select_n_sel(MctsDev t, WideDev w) {
+    __shared__ WideLds L;
+    wide_expand_backup_body<VS, true>(t, w, L, blockIdx.x, threadIdx.x);
+    wave_sync();
+    __syncthreads();
+    wide_select_body<true, VS, true>(t, w, L, blockIdx.x, threadIdx.x);
 }
 // dense batch in (game, j) order: prefix sum over the per-game leaf counts
 __global__ __launch_bounds__(1024) void k_wide_compact(MctsDev t, WideDev w) {
@@ -1405,6 +1514,8 @@ static int check_error_flag(oz_mcts* m) {
 #define OZ_VS(K) (m->vsigns != OZ_VSIGNS_REFERENCE ? K<OZ_VSIGNS_SOUND> : K<OZ_VSIGNS_REFERENCE>)
 // ... of the kernels that have the proven instantiation (the plain and the wide search; the Gumbel and free-running families refuse the option)
 #define OZ_VSP(K) (m->proofs ? K<OZ_VSIGNS_PROVEN> : OZ_VS(K))
+// ... of the kernels that have the selection instantiation too (the same two families; the Gumbel and free-running ones refuse the option)
+#define OZ_VSPS(K) (m->d.sel.flags ? OZ_VSP(K##_sel) : OZ_VSP(K))
 enum { TS_SELECT = 0, TS_COMPACT = 1, TS_NN = 2, TS_BACKUP = 3, TS_MOVE = 4 };
 // the step's solved rows (k_solve_leaves): after the evaluator of EITHER kind of step has written the rows [0, cap) (and the cache has taken
 // them), before their expand + backup.  hits: the step may have rows served from the evaluation cache.  Off (the default), nothing is launched.
@@ -1508,8 +1619,8 @@ static int mcts_wide_steps(oz_mcts* m, oz_net* net, int nsims, int max_games, bo
         if (enqueued > (long long)nsims) { oz_set_error("leaf-parallel search: the simulation budget did not run out after %d steps (internal error)", nsims); return OZ_ERR_STATE; }
         for (int k = 0; k < steps; ++k) {
             timed(m, TS_SELECT, all, [&] {
-                if (k == 0) hipLaunchKernelGGL(m->noise_ever ? OZ_VSP(k_wide_select_n) : OZ_VSP(k_wide_select), dim3(d.G), dim3(64), 0, s, d, w);
-                else hipLaunchKernelGGL(m->noise_ever ? OZ_VSP(k_wide_backup_select_n) : OZ_VSP(k_wide_backup_select), dim3(d.G), dim3(64), 0, s, d, w);
+                if (k == 0) hipLaunchKernelGGL(m->noise_ever ? OZ_VSPS(k_wide_select_n) : OZ_VSPS(k_wide_select), dim3(d.G), dim3(64), 0, s, d, w);
+                else hipLaunchKernelGGL(m->noise_ever ? OZ_VSPS(k_wide_backup_select_n) : OZ_VSPS(k_wide_backup_select), dim3(d.G), dim3(64), 0, s, d, w);
             });
             timed(m, TS_COMPACT, all, [&] { hipLaunchKernelGGL(k_wide_compact, dim3(1), dim3(1024), 0, s, d, w); });
             const long long i = (time_eval || all) ? m->timer.begin(TS_NN, s) : -1;
@@ -1517,7 +1628,7 @@ static int mcts_wide_steps(oz_mcts* m, oz_net* net, int nsims, int max_games, bo
             m->timer.end(i, s);
             solve_leaves_async(m, cap, false);              // (no evaluation cache here: every leaf has a row of its own)
         }
-        timed(m, TS_BACKUP, all, [&] { hipLaunchKernelGGL(OZ_VSP(k_wide_expand_backup), dim3(d.G), dim3(64), 0, s, d, w); });
+        timed(m, TS_BACKUP, all, [&] { hipLaunchKernelGGL(OZ_VSPS(k_wide_expand_backup), dim3(d.G), dim3(64), 0, s, d, w); });
         OZ_HIP(hipGetLastError());
         int max_left = 0;
         OZ_HIP(hipMemsetAsync(w.max_left, 0, sizeof(int), s));
@@ -1551,13 +1662,13 @@ static int mcts_steps_async(oz_mcts* m, oz_net* net, int nsims, int max_games, b
             if (m->gumbel_ever) {
                 if (k == 0) hipLaunchKernelGGL(OZ_VS(k_select_g), dim3(d.G), dim3(64), 0, s, d, m->gd);
                 else hipLaunchKernelGGL(OZ_VS(k_backup_select_g), dim3(d.G), dim3(64), 0, s, d, m->gd);
-            } else if (k == 0) hipLaunchKernelGGL(m->noise_ever ? OZ_VSP(k_select_n) : OZ_VSP(k_select), dim3(d.G), dim3(64), 0, s, d);
-            else hipLaunchKernelGGL(m->noise_ever ? OZ_VSP(k_backup_select_n) : OZ_VSP(k_backup_select), dim3(d.G), dim3(64), 0, s, d);
+            } else if (k == 0) hipLaunchKernelGGL(m->noise_ever ? OZ_VSPS(k_select_n) : OZ_VSPS(k_select), dim3(d.G), dim3(64), 0, s, d);
+            else hipLaunchKernelGGL(m->noise_ever ? OZ_VSPS(k_backup_select_n) : OZ_VSPS(k_backup_select), dim3(d.G), dim3(64), 0, s, d);
         });
         timed(m, TS_COMPACT, all, [&] { hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, s, d); });
         if (int rc = eval_batch_async(m, net, max_games, time_eval || all)) return rc;
     }
-    timed(m, TS_BACKUP, all, [&] { hipLaunchKernelGGL(m->gumbel_ever ? OZ_VS(k_expand_backup_g) : OZ_VSP(k_expand_backup), dim3(d.G), dim3(64), 0, s, d, 0); });
+    timed(m, TS_BACKUP, all, [&] { hipLaunchKernelGGL(m->gumbel_ever ? OZ_VS(k_expand_backup_g) : OZ_VSPS(k_expand_backup), dim3(d.G), dim3(64), 0, s, d, 0); });
     OZ_HIP(hipGetLastError());
     return OZ_OK;
 }
@@ -1800,6 +1911,105 @@ OZ_API int oz_mcts_get_proofs(oz_mcts* m, int* enabled) {
     OZ_REQUIRE(m && enabled, "null argument");
     std::lock_guard<std::mutex> lk(m->mu);
     *enabled = m->proofs ? 1 : 0;
+    return OZ_OK;
+}
+// ---- selection: the option (include/othellozero_amd.h, "selection").  Every node of such a tree keeps vhat in header word 3, so like the value
+// signs it changes on an empty tree alone; it refuses the kernel families without a selection instantiation and forced playouts.
+static_assert(OZ_SELECT_FPU == OZ_SEL_FPU && OZ_SELECT_GROWTH == OZ_SEL_GROWTH && OZ_SELECT_PRIOR_FIRST == OZ_SEL_PRIOR_FIRST, "selection: one numbering");
+static int selection_check(const char* fn, int flags, double fpu, double fpu_root, double base, double factor) {
+    OZ_REQUIRE((flags & ~(OZ_SEL_FPU | OZ_SEL_GROWTH | OZ_SEL_PRIOR_FIRST)) == 0, "%s: unknown flag bits %d", fn, flags);
+    if (flags & OZ_SEL_FPU) {                                                                                  // (NaN fails both compares)
+        OZ_REQUIRE(fpu >= 0.0 && fpu <= 4.0, "%s: fpu_reduction %g outside [0, 4]", fn, fpu);
+        OZ_REQUIRE(fpu_root >= 0.0 && fpu_root <= 4.0, "%s: fpu_root_reduction %g outside [0, 4]", fn, fpu_root);
+    }
+    if (flags & OZ_SEL_GROWTH) {
+        OZ_REQUIRE(base > 0.0 && base < INFINITY, "%s: cpuct_base %g must be positive and finite", fn, base);
+        OZ_REQUIRE(factor >= 0.0 && factor < INFINITY, "%s: cpuct_factor %g must be >= 0 and finite", fn, factor);
+    }
+    return OZ_OK;
+}
+// a part that is off keeps no parameters: what the getter reports is what the kernels read
+static OzSelection selection_of(int flags, double fpu, double fpu_root, double base, double factor) {
+    OzSelection s{flags, 0.0, 0.0, 0.0, 0.0};
+    if (flags & OZ_SEL_FPU) { s.fpu = fpu; s.fpu_root = fpu_root; }
+    if (flags & OZ_SEL_GROWTH) { s.base = base; s.factor = factor; }
+    return s;
+}
+static int selection_set_locked(oz_mcts* m, const char* fn, const OzSelection& sel) {
+    if (m->selected) { oz_set_error("%s: a step is pending (oz_mcts_select without oz_mcts_backup)", fn); return OZ_ERR_STATE; }
+    hipSetDevice(m->device);
+    MctsDev& d = m->d;
+    std::vector<int> nodes((size_t)d.G);
+    OZ_HIP(hipMemcpyAsync(nodes.data(), d.node_count, sizeof(int) * nodes.size(), hipMemcpyDeviceToHost, m->stream));
+    OZ_HIP(hipStreamSynchronize(m->stream));
+    for (int n : nodes)
+        if (n != 0) { oz_set_error("%s: the tree holds nodes already (set the option right after create or after oz_mcts_reset(-1))", fn); return OZ_ERR_STATE; }
+    if (sel.flags) {
+        if (m->gumbel_ever) { oz_set_error("%s: not with the Gumbel search (its kernels have no selection instantiation)", fn); return OZ_ERR_STATE; }
+        if (d.forced_k > 0.0) { oz_set_error("%s: not with forced playouts (their quota and pruning restate PUCT with the constant c; set k to 0 first)", fn); return OZ_ERR_STATE; }
+    }
+    d.sel = sel;
+    return OZ_OK;
+}
+OZ_API int oz_mcts_set_selection(oz_mcts* m, int flags, double fpu_reduction, double fpu_root_reduction, double cpuct_base, double cpuct_factor) {
+    OZ_REQUIRE(m, "null mcts");
+    if (int rc = selection_check("oz_mcts_set_selection", flags, fpu_reduction, fpu_root_reduction, cpuct_base, cpuct_factor)) return rc;
+    std::lock_guard<std::mutex> lk(m->mu);
+    return selection_set_locked(m, "oz_mcts_set_selection", selection_of(flags, fpu_reduction, fpu_root_reduction, cpuct_base, cpuct_factor));
+}
+OZ_API int oz_mcts_get_selection(oz_mcts* m, int* flags, double* fpu_reduction, double* fpu_root_reduction, double* cpuct_base, double* cpuct_factor) {
+    OZ_REQUIRE(m, "null mcts");
+    std::lock_guard<std::mutex> lk(m->mu);
+    const OzSelection& s = m->d.sel;
+    if (flags) *flags = s.flags;
+    if (fpu_reduction) *fpu_reduction = s.fpu;
+    if (fpu_root_reduction) *fpu_root_reduction = s.fpu_root;
+    if (cpuct_base) *cpuct_base = s.base;
+    if (cpuct_factor) *cpuct_factor = s.factor;
+    return OZ_OK;
+}
+// the definition on the host (oz_common.h), for tests and tools without a device
+OZ_API int oz_search_select_c(double c, double base, double factor, int n, double* out) {
+    OZ_REQUIRE(out, "oz_search_select_c: null argument");
+    if (int rc = selection_check("oz_search_select_c", OZ_SEL_GROWTH, 0.0, 0.0, base, factor)) return rc;
+    OZ_REQUIRE(n >= 0, "oz_search_select_c: n %d", n);
+    *out = oz_select_c(c, base, factor, n);
+    return OZ_OK;
+}
+OZ_API int oz_search_select_scores(const int32_t* N, const double* Q, const double* P, uint64_t legal, int Ns, double vhat, int level, double c, int flags,
+                                   double fpu_reduction, double fpu_root_reduction, double cpuct_base, double cpuct_factor, double* U, double* F,
+                                   double* V, double* c_S, int32_t* pick) {
+    OZ_REQUIRE(N && Q && P && U, "oz_search_select_scores: null argument");
+    if (int rc = selection_check("oz_search_select_scores", flags, fpu_reduction, fpu_root_reduction, cpuct_base, cpuct_factor)) return rc;
+    OZ_REQUIRE(Ns >= 0 && level >= 0, "oz_search_select_scores: Ns %d, level %d", Ns, level);
+    for (int sq = 0; sq < 64; ++sq) OZ_REQUIRE(!((legal >> sq) & 1) || N[sq] >= 0, "oz_search_select_scores: N[%d] = %d", sq, N[sq]);
+    const OzSelection s = selection_of(flags, fpu_reduction, fpu_root_reduction, cpuct_base, cpuct_factor);
+    const double cS = (s.flags & OZ_SEL_GROWTH) ? oz_select_c(c, s.base, s.factor, Ns) : c;
+    const double r = oz_select_r(s.flags & OZ_SEL_PRIOR_FIRST, Ns);
+    double f = 0.0, v = 0.0;
+    if (s.flags & OZ_SEL_FPU) {
+        double aq[64], ap[64];
+        int SN = 0;
+        for (int sq = 0; sq < 64; ++sq) {
+            const bool vis = ((legal >> sq) & 1) && N[sq] > 0;
+            if ((legal >> sq) & 1) SN += N[sq];
+            aq[sq] = vis ? oz_select_fpu_q(N[sq], Q[sq]) : 0.0;
+            ap[sq] = vis ? P[sq] : 0.0;
+        }
+        f = oz_select_fpu(vhat, oz_tree_sum64(aq), oz_tree_sum64(ap), SN, level == 0 ? s.fpu_root : s.fpu, &v);
+    }
+    int best = -1;
+    for (int sq = 0; sq < 64; ++sq) {
+        U[sq] = -INFINITY;
+        if (!((legal >> sq) & 1)) continue;
+        const double q = (s.flags & OZ_SEL_FPU) && N[sq] == 0 ? f : Q[sq];
+        U[sq] = oz_select_u(q, cS, P[sq], r, N[sq]);
+        if (best < 0 || U[sq] > U[best]) best = sq;                        // the first maximum
+    }
+    if (F) *F = f;
+    if (V) *V = v;
+    if (c_S) *c_S = cS;
+    if (pick) *pick = best;
     return OZ_OK;
 }
 static int proof_stats_locked(oz_mcts* m, int64_t* out4) {
@@ -2085,7 +2295,7 @@ OZ_API int oz_mcts_select(oz_mcts* m) {
     OZ_REFUSE_SOLVED(m, "oz_mcts_select");
     hipSetDevice(m->device);
     if (m->gumbel_ever) hipLaunchKernelGGL(OZ_VS(k_select_g), dim3(m->d.G), dim3(64), 0, m->stream, m->d, m->gd);
-    else hipLaunchKernelGGL(m->noise_ever ? OZ_VSP(k_select_n) : OZ_VSP(k_select), dim3(m->d.G), dim3(64), 0, m->stream, m->d);
+    else hipLaunchKernelGGL(m->noise_ever ? OZ_VSPS(k_select_n) : OZ_VSPS(k_select), dim3(m->d.G), dim3(64), 0, m->stream, m->d);
     OZ_HIP(hipGetLastError());
     m->selected = true;
     return check_error_flag(m);
@@ -2115,7 +2325,7 @@ OZ_API int oz_mcts_backup(oz_mcts* m, const float* pi, const float* v) {
     const int G = m->d.G;
     OZ_HIP(hipMemcpyAsync(m->d.pi, pi, 4ull * G * m->d.n2, hipMemcpyHostToDevice, m->stream));
     OZ_HIP(hipMemcpyAsync(m->d.v, v, 4ull * G, hipMemcpyHostToDevice, m->stream));
-    hipLaunchKernelGGL(m->gumbel_ever ? OZ_VS(k_expand_backup_g) : OZ_VSP(k_expand_backup), dim3(G), dim3(64), 0, m->stream, m->d, 1);
+    hipLaunchKernelGGL(m->gumbel_ever ? OZ_VS(k_expand_backup_g) : OZ_VSPS(k_expand_backup), dim3(G), dim3(64), 0, m->stream, m->d, 1);
     OZ_HIP(hipGetLastError());
     m->selected = false;
     return check_error_flag(m);
@@ -2333,6 +2543,7 @@ static int gumbel_enable(oz_mcts* m, const char* fn, int max_considered, double 
     const int G = d.G;
     if (!m->gumbel_ever) {
         if (m->proofs) { oz_set_error("%s: not with proofs (the Gumbel kernels have no proven instantiation)", fn); return OZ_ERR_STATE; }
+        if (m->d.sel.flags) { oz_set_error("%s: not with the selection option (the Gumbel kernels have no selection instantiation)", fn); return OZ_ERR_STATE; }
         if (m->noise_ever) { oz_set_error("%s: the Gumbel search replaces root noise and forced playouts (the object has armed root noise)", fn); return OZ_ERR_STATE; }
         if (m->wide()) { oz_set_error("%s: the Gumbel search runs one leaf per game and step (leaves_per_step is %d)", fn, m->leaves_per_step); return OZ_ERR_STATE; }
         std::vector<int> nn(G);
@@ -2470,7 +2681,8 @@ OZ_API int oz_mcts_gumbel_scores(oz_mcts* m, double* score) {
     OZ_HIP(hipStreamSynchronize(m->stream));
     return OZ_OK;
 }
-// header word 3 of node `index` of game `game`: the node's own value where it was expanded under the Gumbel search, 0.0 elsewhere
+// header word 3 of node `index` of game `game`: the node's own value (vhat) where it was expanded under the Gumbel search or under the
+// selection option, 0.0 elsewhere
 OZ_API int oz_mcts_node_value(oz_mcts* m, int game, int index, double* value) {
     OZ_REQUIRE(m && value, "null argument");
     std::lock_guard<std::mutex> lk(m->mu);
@@ -2536,6 +2748,7 @@ static int forced_check(const char* fn, double k) {
 // k > 0 needs root noise armed on the object (forcing is a rule of the noisy root); k == 0 switches off
 static int forced_set_locked(oz_mcts* m, const char* fn, double k) {
     if (k > 0.0 && m->proofs) { oz_set_error("%s: not with proofs (forcing a proven loss would undo them)", fn); return OZ_ERR_STATE; }
+    if (k > 0.0 && m->d.sel.flags) { oz_set_error("%s: not with the selection option (the quota and the pruning restate PUCT with the constant c)", fn); return OZ_ERR_STATE; }
     if (k > 0.0 && !(m->noise_ever && m->d.noise_eps > 0.0)) {
         oz_set_error("%s: forced playouts need root noise (arm it first)", fn);
         return OZ_ERR_STATE;
@@ -3766,6 +3979,7 @@ OZ_API int oz_selfplay_stagger(oz_selfplay* sp, int sims_pre) {
     hipSetDevice(sp->m->device);
     OZ_REQUIRE(sp->mode == 0, "oz_selfplay_stagger must be the first driver call on an engine");
     if (sp->m->proofs) { oz_set_error("oz_selfplay_stagger: not with proofs (use oz_selfplay_run)"); return OZ_ERR_STATE; }
+    if (sp->m->d.sel.flags) { oz_set_error("oz_selfplay_stagger: not with the selection option (it continues on the free-running kernels; use oz_selfplay_run)"); return OZ_ERR_STATE; }
     if (sp->gumbel_on) { oz_set_error("oz_selfplay_stagger: not with the Gumbel search (its budget is num_simulations; use oz_selfplay_run)"); return OZ_ERR_STATE; }
     if (sp->resign.r > 0) { oz_set_error("oz_selfplay_stagger: not with resignation (its rounds search at sims_pre; use oz_selfplay_run)"); return OZ_ERR_STATE; }
     OZ_REQUIRE(sp->cfg.refill, "oz_selfplay_stagger is for continuous self-play (cfg.refill = 1)");
@@ -3831,6 +4045,20 @@ OZ_API int oz_selfplay_set_value_signs(oz_selfplay* sp, int mode) {
     if (sp->mode != 0) { oz_set_error("oz_selfplay_set_value_signs: the engine has been driven already (set it before the first driver call)"); return OZ_ERR_STATE; }
     std::lock_guard<std::mutex> lkm(sp->m->mu);
     return value_signs_set_locked(sp->m, "oz_selfplay_set_value_signs", mode);
+}
+// the selection rule of the engine's search (see oz_mcts_set_selection), for oz_selfplay_run; before the first driver call
+OZ_API int oz_selfplay_set_selection(oz_selfplay* sp, int flags, double fpu_reduction, double fpu_root_reduction, double cpuct_base, double cpuct_factor) {
+    OZ_REQUIRE(sp, "null selfplay");
+    if (int rc = selection_check("oz_selfplay_set_selection", flags, fpu_reduction, fpu_root_reduction, cpuct_base, cpuct_factor)) return rc;
+    std::lock_guard<std::mutex> lk(sp->mu);
+    if (sp->mode != 0) { oz_set_error("oz_selfplay_set_selection: the engine has been driven already (set it before the first driver call)"); return OZ_ERR_STATE; }
+    std::lock_guard<std::mutex> lkm(sp->m->mu);
+    return selection_set_locked(sp->m, "oz_selfplay_set_selection", selection_of(flags, fpu_reduction, fpu_root_reduction, cpuct_base, cpuct_factor));
+}
+OZ_API int oz_selfplay_get_selection(oz_selfplay* sp, int* flags, double* fpu_reduction, double* fpu_root_reduction, double* cpuct_base, double* cpuct_factor) {
+    OZ_REQUIRE(sp, "null selfplay");
+    std::lock_guard<std::mutex> lk(sp->mu);
+    return oz_mcts_get_selection(sp->m, flags, fpu_reduction, fpu_root_reduction, cpuct_base, cpuct_factor);
 }
 // proofs of the engine's search (see oz_mcts_set_proofs), for oz_selfplay_run; before the first driver call
 OZ_API int oz_selfplay_set_proofs(oz_selfplay* sp, int enable) {
@@ -4212,6 +4440,7 @@ OZ_API int oz_selfplay_run_steps(oz_selfplay* sp, int steps) {
     }
     if (sp->gumbel_on) { oz_set_error("oz_selfplay_run_steps: the free-running driver does not run the Gumbel search; use oz_selfplay_run"); return OZ_ERR_STATE; }
     if (sp->m->proofs) { oz_set_error("oz_selfplay_run_steps: the free-running driver keeps no proofs; use oz_selfplay_run"); return OZ_ERR_STATE; }
+    if (sp->m->d.sel.flags) { oz_set_error("oz_selfplay_run_steps: the free-running kernels have no selection instantiation; use oz_selfplay_run"); return OZ_ERR_STATE; }
     if (sp->resign.r > 0) { oz_set_error("oz_selfplay_run_steps: the free-running driver does not resign games; use oz_selfplay_run"); return OZ_ERR_STATE; }
     std::lock_guard<std::mutex> lkn(sp->net->mu);
     oz_mcts* m = sp->m;
@@ -5141,6 +5370,17 @@ OZ_API int oz_arena_set_value_signs(oz_arena* a, int black, int white) {
     if (a->started) { oz_set_error("oz_arena_set_value_signs: the arena has run already (set it before the first run)"); return OZ_ERR_STATE; }
     if (int rc = value_signs_set_locked(a->games.m, "oz_arena_set_value_signs", black)) return rc;
     return value_signs_set_locked(a->mb, "oz_arena_set_value_signs", white);
+}
+// the selection rule of one agent's search (agent +1: BLACK, net_a's; -1: WHITE, net_b's); before the first run
+OZ_API int oz_arena_set_selection(oz_arena* a, int agent, int flags, double fpu_reduction, double fpu_root_reduction, double cpuct_base, double cpuct_factor) {
+    OZ_REQUIRE(a, "null arena");
+    OZ_REQUIRE(agent == 1 || agent == -1, "oz_arena_set_selection: agent must be +1 (BLACK) or -1 (WHITE), got %d", agent);
+    if (int rc = selection_check("oz_arena_set_selection", flags, fpu_reduction, fpu_root_reduction, cpuct_base, cpuct_factor)) return rc;
+    std::lock_guard<std::mutex> lk(a->mu);
+    if (a->started) { oz_set_error("oz_arena_set_selection: the arena has run already (set it before the first run)"); return OZ_ERR_STATE; }
+    oz_mcts* m = agent == 1 ? a->games.m : a->mb;
+    std::lock_guard<std::mutex> lkm(m->mu);
+    return selection_set_locked(m, "oz_arena_set_selection", selection_of(flags, fpu_reduction, fpu_root_reduction, cpuct_base, cpuct_factor));
 }
 // proofs per agent (black for net_a's search, white for net_b's), each on top of sound signs; before the first run
 OZ_API int oz_arena_set_proofs(oz_arena* a, int black, int white) {

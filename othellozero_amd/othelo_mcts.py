@@ -19,7 +19,7 @@ from .Othello import OthelloGame, OthelloPlayer
 class OthelloMCTS:
     def __init__(self, board_size, neural_network, degree_exploration, q_mode=_lib.QMODE_F64,
                  node_cap=8192, leaves_per_step=1, solve_leaves=0, forced_playouts=None, gumbel=None, value_signs="reference", proofs=False,
-                 proof_play=False):
+                 proof_play=False, selection=None):
         """q_mode: OZ_QMODE_F64 = the NumPy 1.18.5 promotion the reference pins (requirements.txt:19),
         OZ_QMODE_NEP50 = what NumPy >= 2 computes (SURVEY.md R-FP).
         leaves_per_step > 1 (native networks only, created with max_batch >= leaves_per_step): that many descents of the tree per
@@ -43,7 +43,13 @@ class OthelloMCTS:
         proof_stats read them.  Not with gumbel or forced_playouts.
         proof_play=True (needs proofs=True): proven_counts / get_policy_action_probabilities(..., proven=True) / root_value(..., proven=True) /
         sample_action(..., proven=True) give the row, the policy, the value and the sampled move the root's proofs leave
-        (include/othellozero_amd.h, "proof play"); the flag itself changes no call -- callers (execute_episode, the agents) read it."""
+        (include/othellozero_amd.h, "proof play"); the flag itself changes no call -- callers (execute_episode, the agents) read it.
+        selection=dict(fpu=(reduction, root_reduction), cpuct_growth=(base, factor), prior_first=bool), every key optional: the descent's
+        U = Q + c P sqrt(Ns) / (1 + N) with an unvisited move valued at the node's running value minus a reduction (first-play urgency)
+        in place of 0, an exploration constant that grows with the node's visits, and a first visit that follows the prior
+        (oz_mcts_set_selection; include/othellozero_amd.h, "selection").  None, or every part off, is the search as it was.  Every node then
+        keeps the value its expansion backed up (node_values).  Not with gumbel or forced_playouts.  Not the reference's search."""
+        self._selection = _lib.check_selection(selection, gumbel=gumbel, forced_playouts=forced_playouts)
         self.value_signs = value_signs
         vs_mode = _lib.check_value_signs(value_signs)
         self.proofs = _lib.check_proofs(proofs, value_signs, gumbel=gumbel, forced_playouts=forced_playouts)
@@ -77,12 +83,33 @@ class OthelloMCTS:
             _lib.check(lib.oz_mcts_set_value_signs(self._h, vs_mode))
         if self.proofs:
             _lib.check(lib.oz_mcts_set_proofs(self._h, 1))
+        if self._selection[0]:
+            _lib.check(lib.oz_mcts_set_selection(self._h, *self._selection))
         if self.leaves_per_step != 1:
             _lib.check(lib.oz_mcts_set_leaves_per_step(self._h, self.leaves_per_step))
         if self.solve_leaves:
             _lib.check(lib.oz_mcts_set_solve_leaves(self._h, self.solve_leaves))
         if self.gumbel is not None:                        # over the empty tree: the parameters, no root armed yet (the budget comes with the arming)
             _lib.check(lib.oz_mcts_set_gumbel(self._h, self.gumbel[0], self.gumbel[1], self.gumbel[2], 1, None, None))
+
+    # ---- selection (include/othellozero_amd.h, "selection")
+    @property
+    def selection(self):
+        """the selection rule the library runs, as the keyword takes it (None: the default rule)"""
+        flags, vals = C.c_int(), [C.c_double() for _ in range(4)]
+        _lib.check(_lib.load().oz_mcts_get_selection(self._h, C.byref(flags), *(C.byref(v) for v in vals)))
+        return _lib.selection_dict((flags.value, *(v.value for v in vals)))
+
+    def node_values(self):
+        """per node, in dump()'s order: the value its expansion backed up (vhat; kept under selection= and gumbel=, 0.0 otherwise)"""
+        lib = _lib.load()
+        nn = np.zeros(1, np.int32)
+        _lib.check(lib.oz_mcts_num_nodes(self._h, _lib.p_i32(nn)))
+        out, v = [], C.c_double()
+        for i in range(int(nn[0])):
+            _lib.check(lib.oz_mcts_node_value(self._h, 0, i, C.byref(v)))
+            out.append(v.value)
+        return out
 
     # ---- Gumbel search (include/othellozero_amd.h, "Gumbel search")
     def _need_gumbel(self):

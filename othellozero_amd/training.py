@@ -34,7 +34,7 @@ def execute_episode(board_size, neural_network, degree_exploration, num_simulati
                     q_mode=_lib.QMODE_F64, snapshot_boards=False, policy_target="onehot", target_temperature=1.0,
                     leaves_per_step=1, root_noise=None, noise_seed=0, sample_moves=None, sample_seed=0, solve_leaves=0,
                     forced_playouts=None, value_target="outcome", gumbel=None, gumbel_seed=0, value_signs="reference", proofs=False,
-                    proof_play=False):
+                    proof_play=False, selection=None):
     """training.py:26-72.  Returns [(board (n,n,2) bool, one-hot policy (n,n) float64, z int), ...], 8 per move.
 
     gumbel=(max_considered, c_visit, c_scale) or True: every move's search is a Gumbel root search of num_simulations simulations
@@ -77,7 +77,10 @@ def execute_episode(board_size, neural_network, degree_exploration, num_simulati
     gumbel or forced_playouts.
 
     proof_play=True (needs proofs=True): the policy the move is taken from, the sampled move, the "visits" target and the recorded root
-    value are those the root's proofs leave (OthelloMCTS.proven_counts / root_value(proven=True)); the explore branch is unchanged."""
+    value are those the root's proofs leave (OthelloMCTS.proven_counts / root_value(proven=True)); the explore branch is unchanged.
+
+    selection=dict(fpu=, cpuct_growth=, prior_first=): the selection rule of the search (OthelloMCTS); not with gumbel or forced_playouts."""
+    _lib.check_selection(selection, gumbel=gumbel, forced_playouts=forced_playouts)
     _lib.check_value_signs(value_signs)
     _lib.check_proofs(proofs, value_signs, gumbel=gumbel, forced_playouts=forced_playouts)
     proof_play = _lib.check_proof_play(proof_play, proofs)
@@ -102,7 +105,8 @@ def execute_episode(board_size, neural_network, degree_exploration, num_simulati
     mcts = OthelloMCTS(board_size, neural_network, degree_exploration, q_mode=q_mode,
                        node_cap=num_simulations * (board_size * board_size - 3) + 64, leaves_per_step=leaves_per_step,
                        solve_leaves=solve_leaves, forced_playouts=forced_playouts, **({"gumbel": gumbel} if gumbel is not None else {}),
-                       **({"value_signs": value_signs} if value_signs != "reference" else {}), **_lib.proofs_kw(proofs), **_lib.proof_play_kw(proof_play))
+                       **({"value_signs": value_signs} if value_signs != "reference" else {}), **_lib.proofs_kw(proofs), **_lib.proof_play_kw(proof_play),
+                       **_lib.selection_kw(selection))
     # training.py:34-37 (BNN examples are one-channel boards, a fresh array per round: no aliasing for them)
     board_view_type = BoardView.ONE_CHANNEL if getattr(neural_network.network_type, "name", "") == "BNN" else BoardView.TWO_CHANNELS
 
@@ -204,7 +208,7 @@ class SelfPlayEngine:
                  q_mode=_lib.QMODE_F64, refill=False, node_cap=0, record_cap=0, dedup=True, batch_cap=0, eval_cache=False,
                  record_visits=False, leaves_per_step=1, root_noise=None, sample_moves=None, solve_leaves=0, playout_cap=None,
                  forced_playouts=None, record_values=False, gumbel=None, record_surprise=False, resign=None, value_signs="reference", proofs=False,
-                 proof_play=False):
+                 proof_play=False, selection=None):
         """dedup: cross-game leaf de-duplication (a board several games reach in one batch is evaluated once; no record changes);
         batch_cap: leaves per network batch of the free-running driver (0 = none; see preferred_batch_cap);
         eval_cache: take (pi, v) of boards the network has evaluated before from its persistent cache (NNetWrapper.set_eval_cache) --
@@ -273,7 +277,14 @@ class SelfPlayEngine:
         (oz_selfplay_set_proof_play): the row keeps the raw counts of the moves the descent would still pick at the root -- those that prove
         a known value, else those not proven lost -- and every move rule that reads counts reads that row; the root value is the exact one
         where it is known; the record carries the proof code _lib.record_proven reads.  The explore branch of the coin and last_counts()
-        stay as they are.  proof_play_stats() counts; proof_targets() makes z of the proven records exact ("Proof play")."""
+        stay as they are.  proof_play_stats() counts; proof_targets() makes z of the proven records exact ("Proof play").
+        selection=dict(fpu=(reduction, root_reduction), cpuct_growth=(base, factor), prior_first=bool), every key optional: every search
+        of the engine values an unvisited move at the node's running value minus a reduction in place of 0, lets the exploration constant
+        grow with the node's visits and sends a fresh node's first visit where the prior points (oz_selfplay_set_selection;
+        include/othellozero_amd.h, "selection").  run() / play_to_end() at any leaves_per_step with every option but gumbel and
+        forced_playouts (ValueError); run_steps() and stagger() then raise.  Records, rows and targets read what the search stores
+        (DESIGN.md, "Selection")."""
+        selection = _lib.check_selection(selection, gumbel=gumbel, forced_playouts=forced_playouts)
         vs_mode = _lib.check_value_signs(value_signs)
         proofs = _lib.check_proofs(proofs, value_signs, gumbel=gumbel, forced_playouts=forced_playouts)
         proof_play = _lib.check_proof_play(proof_play, proofs)
@@ -308,6 +319,9 @@ class SelfPlayEngine:
         self.proof_play = proof_play
         if proof_play:
             _lib.check(lib.oz_selfplay_set_proof_play(self._h, 1))
+        self.selection = _lib.selection_dict(selection)
+        if selection[0]:
+            _lib.check(lib.oz_selfplay_set_selection(self._h, *selection))
         self.leaves_per_step = int(leaves_per_step)
         if self.leaves_per_step != 1:
             _lib.check(lib.oz_selfplay_set_leaves_per_step(self._h, self.leaves_per_step))
@@ -707,8 +721,10 @@ def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations
                    policy_temperature=1.0, e_greedy=0.9, seed=1234, first_game_id=0, q_mode=_lib.QMODE_F64,
                    expand=False, alias_final=False, record_visits=False, target_temperature=1.0, leaves_per_step=1, root_noise=None,
                    sample_moves=None, endgame_targets=0, solve_leaves=0, playout_cap=None, forced_playouts=None, value_target="outcome", gumbel=None,
-                   surprise_weight=None, resign=None, value_signs="reference", proofs=False, proof_play=False, proof_targets=False):
+                   surprise_weight=None, resign=None, value_signs="reference", proofs=False, proof_play=False, proof_targets=False,
+                   selection=None):
     """Play num_games complete games; returns the move records (or the expanded examples).
+    selection=dict(fpu=, cpuct_growth=, prior_first=): the selection rule of the searches (SelfPlayEngine); not with gumbel or forced_playouts.
     proof_play=True (needs proofs=True): moves, visit rows, root values and the records' proof codes take what the roots' proofs know
     (SelfPlayEngine); selfplay_batch.proof_play_stats holds the last call's SelfPlayEngine.proof_play_stats() (None when off).
     proof_targets=True (needs proof_play=True): z of every proven record becomes the proven sign (SelfPlayEngine.proof_targets) before the
@@ -746,6 +762,7 @@ def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations
     targets, exact_empties = endgame_targets).  The float32 targets come back last -- (records, [counts,] targets) -- or, with expand, as
     the examples' float32 z; with expand it needs alias_final=False.  selfplay_batch.value_target_stats holds the last call's statistics
     (None when off)."""
+    _lib.check_selection(selection, gumbel=gumbel, forced_playouts=forced_playouts)
     _lib.check_value_signs(value_signs)
     _lib.check_proofs(proofs, value_signs, gumbel=gumbel, forced_playouts=forced_playouts)
     proof_play = _lib.check_proof_play(proof_play, proofs)
@@ -778,7 +795,7 @@ def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations
                          **({"forced_playouts": forced_playouts} if forced_playouts > 0.0 else {}), **({"record_values": True} if vt_on else {}),
                          **({"gumbel": gumbel} if gumbel is not None else {}), **({"record_surprise": True} if surprise_weight is not None else {}),
                          **({"resign": resign} if resign is not None else {}), **({"value_signs": value_signs} if value_signs != "reference" else {}),
-                         **_lib.proofs_kw(proofs), **_lib.proof_play_kw(proof_play))
+                         **_lib.proofs_kw(proofs), **_lib.proof_play_kw(proof_play), **_lib.selection_kw(selection))
     selfplay_batch.surprise_stats = None
 
     def weighted(ret):
