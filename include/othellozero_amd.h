@@ -1111,6 +1111,50 @@ int oz_selfplay_proof_play_stats(oz_selfplay* sp, int64_t* out4);
 int oz_arena_set_proof_play(oz_arena* a, int black, int white);
 /* the selection rule of one agent's search (see oz_mcts_set_selection): agent +1 = BLACK (net_a), -1 = WHITE (net_b); before the first run */
 int oz_arena_set_selection(oz_arena* a, int agent, int flags, double fpu_reduction, double fpu_root_reduction, double cpuct_base, double cpuct_factor);
+
+/* ---- tree collection: drop the stored nodes a slot's game has passed (opt-in; off, every kernel, table, record and launch is what it was)
+ * A slot's node table only grows until the slot is refilled or reset, so node_cap has to hold a whole game.  Every move adds exactly one disc
+ * and a pass creates no node, so once a slot's root holds D discs a stored node that is not the root and holds <= D discs can never be looked
+ * up again; every node with more than D discs keeps its statistics.  A collection drops exactly those dead nodes: the kept records move to
+ * the front of the slot's pool in expansion order (stable), every edge's cached child index is renumbered, the node's proof entry moves with
+ * it, the slot's hash table is rebuilt.  No result bit changes -- counts, values, moves, records, rows are those of the object without the
+ * option -- only records are freed, so a smaller node_cap suffices.  node_cap keeps its meaning and its defaults; overflow after a
+ * collection is OZ_ERR_CAPACITY as ever.
+ * The identity holds while a slot's roots never lose discs: a root set to an EARLIER position finds its dropped nodes gone and expands them
+ * afresh (a loss of statistics, never an error).
+ * oz_search_tree_keep: the rule on the host, no device needed.  keep[i] = node i stays under the root (root_own, root_opp): it IS the root, or
+ * popcount(own | opp) > popcount(root_own | root_opp); new_index[i] = the number of kept j < i, -1 where dropped; *kept = their number.
+ * oz_mcts_collect: collects the active slots against their current roots (inactive slots are untouched byte for byte; nothing happens on an
+ * object whose roots were never set).  out2 (may be NULL) = nodes before, nodes kept, summed over the active slots.  OZ_ERR_STATE while a step
+ * is pending (oz_mcts_select without oz_mcts_backup).  The first call allocates the scratch map, 4 B per node of capacity.
+ * Engine and arena: k_tree_collect runs behind the round's roots kernel, before anything looks the new roots up.
+ *   OZ_TREE_GC_ON_DEMAND   decided per game on the device: collect iff node_count + num_simulations > node_cap (a simulation expands at most
+ *                          one node, at any leaves_per_step)
+ *   OZ_TREE_GC_EVERY_MOVE  every active slot every round (the diagnostic mode: small tests exercise the kernel on every move)
+ * Before the first driver call / the first run (OZ_ERR_STATE afterwards); OZ_ERR_ARG for an unknown mode.  It combines with every option of
+ * oz_selfplay_run and the arena.  oz_selfplay_run_steps and oz_selfplay_stagger refuse an engine with the option (OZ_ERR_STATE): the
+ * free-running kernels move inside the kernel and would need the collection as a device call there.
+ * oz_tree_gc_stats, per-game counters reduced at the read: collections, the node counts before and after them summed, peak_nodes = the largest
+ * node count a slot had at the start of a round since arming, peak_kept = the largest count after a collection -- peak_kept + num_simulations
+ * is the node_cap a game of that kind needs under OZ_TREE_GC_ON_DEMAND.  Zeros on an object that never armed the option. */
+#define OZ_TREE_GC_OFF 0
+#define OZ_TREE_GC_ON_DEMAND 1
+#define OZ_TREE_GC_EVERY_MOVE 2
+typedef struct oz_tree_gc_stats {
+    int64_t collections, nodes_before_sum, nodes_kept_sum, peak_nodes, peak_kept;
+} oz_tree_gc_stats;
+int oz_search_tree_keep(uint64_t root_own, uint64_t root_opp, const uint64_t* own, const uint64_t* opp, int64_t count,
+                        uint8_t* keep /* [count] */, int32_t* new_index /* [count], -1 where dropped */, int64_t* kept);
+int oz_mcts_collect(oz_mcts* m, int64_t* out2);
+int oz_mcts_tree_gc_stats(oz_mcts* m, oz_tree_gc_stats* stats);
+int oz_selfplay_set_tree_gc(oz_selfplay* sp, int mode);
+int oz_selfplay_get_tree_gc(oz_selfplay* sp, int* mode, oz_tree_gc_stats* stats);
+/* HIP-event timing of the engine's collection launches (one pair per launch); off, nothing is recorded */
+int oz_selfplay_tree_gc_profile(oz_selfplay* sp, int enable);
+int oz_selfplay_tree_gc_profile_read(oz_selfplay* sp, double* ms_total, int64_t* launches, int reset);
+/* per agent: agent +1 = BLACK (net_a), -1 = WHITE (net_b); before the first run */
+int oz_arena_set_tree_gc(oz_arena* a, int agent, int mode);
+int oz_arena_get_tree_gc(oz_arena* a, int agent, int* mode, oz_tree_gc_stats* stats);
 /* the bare search: oz_mcts_root_counts / oz_mcts_root_values with the rule's row and value (same shapes and rc); OZ_ERR_STATE on an object
  * without proofs.  oz_mcts_root_counts and oz_mcts_root_values stay the raw ones. */
 int oz_mcts_proven_counts(oz_mcts* m, int32_t* counts /* [G][64] */, uint64_t* legal /* [G] */, int32_t* rc /* [G] */);

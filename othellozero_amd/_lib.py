@@ -100,6 +100,11 @@ class ProofTargetStats(C.Structure):                                            
     _fields_ = [("records", C.c_int64), ("proven", C.c_int64), ("z_changed", C.c_int64)]
 
 
+class TreeGcStats(C.Structure):                                                      # oz_tree_gc_stats
+    _fields_ = [("collections", C.c_int64), ("nodes_before_sum", C.c_int64), ("nodes_kept_sum", C.c_int64), ("peak_nodes", C.c_int64),
+                ("peak_kept", C.c_int64)]
+
+
 class Optimizer(C.Structure):                                                       # oz_optimizer
     _fields_ = [
         ("l2", C.c_double), ("weight_decay", C.c_double), ("decay_mask", C.c_uint64), ("global_clipnorm", C.c_double),
@@ -221,6 +226,11 @@ SIGNATURES = {
     "oz_search_select_c": [C.c_double, C.c_double, C.c_double, C.c_int, _f64p],
     "oz_search_select_scores": [_i32p, _f64p, _f64p, C.c_uint64, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int, C.c_double, C.c_double, C.c_double,
                                 C.c_double, _f64p, _f64p, _f64p, _f64p, _i32p],
+    "oz_search_tree_keep": [C.c_uint64, C.c_uint64, _u64p, _u64p, C.c_int64, _u8p, _i32p, _i64p],
+    "oz_mcts_collect": [_vp, _i64p], "oz_mcts_tree_gc_stats": [_vp, C.POINTER(TreeGcStats)],
+    "oz_selfplay_set_tree_gc": [_vp, C.c_int], "oz_selfplay_get_tree_gc": [_vp, C.POINTER(C.c_int), C.POINTER(TreeGcStats)],
+    "oz_selfplay_tree_gc_profile": [_vp, C.c_int], "oz_selfplay_tree_gc_profile_read": [_vp, _f64p, _i64p, C.c_int],
+    "oz_arena_set_tree_gc": [_vp, C.c_int, C.c_int], "oz_arena_get_tree_gc": [_vp, C.c_int, C.POINTER(C.c_int), C.POINTER(TreeGcStats)],
     "oz_mcts_set_proofs": [_vp, C.c_int], "oz_mcts_get_proofs": [_vp, C.POINTER(C.c_int)],
     "oz_mcts_dump_proofs": [_vp, C.c_int, C.c_int, _i8p, _i8p, _i8p], "oz_mcts_root_proofs": [_vp, _i8p, _i8p, _i32p],
     "oz_mcts_proof_stats": [_vp, _i64p], "oz_selfplay_set_proofs": [_vp, C.c_int], "oz_selfplay_proof_stats": [_vp, _i64p],
@@ -789,6 +799,52 @@ def selection_kw(selection):
     else:
         on = check_selection(selection)[0]
     return {"selection": selection} if on else {}
+
+
+TREE_GC = {"off": 0, "demand": 1, "every": 2}   # OZ_TREE_GC_*
+TREE_GC_STATS = ("collections", "nodes_before_sum", "nodes_kept_sum", "peak_nodes", "peak_kept")     # oz_tree_gc_stats
+
+
+def check_tree_gc(tree_gc, what="tree_gc"):
+    """tree_gc="off" | "demand" | "every" of the searches (include/othellozero_amd.h, "tree collection") -> the library's mode number;
+    ValueError otherwise, before the library is touched"""
+    if not isinstance(tree_gc, str) or tree_gc not in TREE_GC:
+        raise ValueError(f"{what} must be 'off', 'demand' or 'every' (got {tree_gc!r})")
+    return TREE_GC[tree_gc]
+
+
+def check_tree_gc_pair(tree_gc):
+    """arena_batch(tree_gc=mode or (mode_black, mode_white)) -> (int, int)"""
+    if isinstance(tree_gc, (tuple, list)):
+        if len(tree_gc) != 2:
+            raise ValueError(f"tree_gc must be one mode or (black, white) (got {tree_gc!r})")
+        return check_tree_gc(tree_gc[0], "tree_gc[black]"), check_tree_gc(tree_gc[1], "tree_gc[white]")
+    m = check_tree_gc(tree_gc)
+    return m, m
+
+
+def tree_gc_kw(tree_gc):
+    """the keyword to pass on: nothing where the option is off, so that callers without it see the calls they always saw"""
+    on = any(check_tree_gc_pair(tree_gc))
+    return {"tree_gc": tree_gc} if on else {}
+
+
+def tree_gc_stats_dict(st):
+    return {k: int(getattr(st, k)) for k in TREE_GC_STATS}
+
+
+def search_tree_keep(root_own, root_opp, own, opp):
+    """oz_search_tree_keep on the host: (keep uint8[count], new_index int32[count], kept)"""
+    own = np.ascontiguousarray(own, dtype=np.uint64).ravel()
+    opp = np.ascontiguousarray(opp, dtype=np.uint64).ravel()
+    if own.size != opp.size:
+        raise ValueError("own and opp must have the same length")
+    keep = np.zeros(own.size, dtype=np.uint8)
+    new_index = np.zeros(own.size, dtype=np.int32)
+    kept = C.c_int64(0)
+    check(load().oz_search_tree_keep(int(root_own), int(root_opp), own.ctypes.data_as(_u64p), opp.ctypes.data_as(_u64p), own.size,
+                                     keep.ctypes.data_as(_u8p), new_index.ctypes.data_as(_i32p), C.byref(kept)))
+    return keep, new_index, int(kept.value)
 
 
 PROOF_UNKNOWN = -128                            # OZ_PROOF_UNKNOWN

@@ -457,9 +457,11 @@ class NeuralNetworkOthelloAgent(OthelloAgent):
 
     def __init__(self, game, neural_network, num_simulations, degree_exploration, temperature=0,
                  q_mode=_lib.QMODE_F64, leaves_per_step=1, solve_leaves=0, value_signs="reference", proofs=False, proof_play=False,
-                 selection=None):
+                 selection=None, tree_gc="off", node_cap=0):
         """proof_play=True (needs proofs=True): the move is the arg-max of the row the root's proofs keep (OthelloMCTS.proven_counts)
-        selection: the selection rule of the agent's search (OthelloMCTS, selection)"""
+        selection: the selection rule of the agent's search (OthelloMCTS, selection)
+        tree_gc: the agent's search drops the nodes the game has passed (OthelloMCTS, tree_gc); node_cap > 0: its capacity in place of the default"""
+        _lib.check_tree_gc(tree_gc)
         solve_leaves = _lib.check_solve_leaves(solve_leaves)
         _lib.check_selection(selection)
         _lib.check_value_signs(value_signs)
@@ -470,9 +472,9 @@ class NeuralNetworkOthelloAgent(OthelloAgent):
         side = game.board_size
         # an agent searches on its own turns only: about half the plies
         self.mcts = OthelloMCTS(side, neural_network, degree_exploration, q_mode=q_mode,
-                                node_cap=num_simulations * (side * side // 2) + 64, leaves_per_step=leaves_per_step,
+                                node_cap=int(node_cap) if node_cap else num_simulations * (side * side // 2) + 64, leaves_per_step=leaves_per_step,
                                 solve_leaves=solve_leaves, value_signs=value_signs, **_lib.proofs_kw(proofs),
-                                **_lib.proof_play_kw(self.proof_play), **_lib.selection_kw(selection))
+                                **_lib.proof_play_kw(self.proof_play), **_lib.selection_kw(selection), **_lib.tree_gc_kw(tree_gc))
 
     def play(self):
         game = self.game
@@ -503,7 +505,7 @@ def duel_between_agents(game, agent_1, agent_2):
 def arena_batch(net_a, net_b, board_size=8, num_games=512, num_simulations=800, degree_exploration=1.0, seed=0,
                 first_game_id=0, q_mode=_lib.QMODE_F64, node_cap=0, max_rounds=0, dedup=True, profile=False, eval_cache=False,
                 leaves_per_step=1, opponent=None, solve_leaves=0, openings=None, first_opening_id=0, opening_moves=None,
-                value_signs="reference", proofs=False, proof_play=False, selection=None):
+                value_signs="reference", proofs=False, proof_play=False, selection=None, tree_gc="off"):
     """num_games games of net_a (BLACK) vs net_b (WHITE), temperature 0, max-visit ties broken by the RNG_TIE
     stream keyed (seed, game id, ply).  One of the two may be None: RandomOthelloAgent plays that colour, or with
     opponent=("minimax", depth) / ("minimax", depth, "discs" | "weighted") the fixed-depth minimax (oz_arena_set_opponent; ties between its
@@ -527,6 +529,9 @@ def arena_batch(net_a, net_b, board_size=8, num_games=512, num_simulations=800, 
     (oz_arena_set_proof_play; include/othellozero_amd.h, "proof play"); needs that agent's proofs.
     selection = None | dict(fpu=, cpuct_growth=, prior_first=) or (black, white): the selection rule of the agent's search
     (oz_arena_set_selection; OthelloMCTS, selection); an agent without a network searches nothing.
+    tree_gc = "off" | "demand" | "every" or (black, white): the agent's search drops the stored nodes its games have passed, right after its
+    roots are set (oz_arena_set_tree_gc; include/othellozero_amd.h, "tree collection"); no result changes, a smaller node_cap suffices.  The
+    result then carries tree_gc_stats = (black, white), each dict(collections, nodes_before_sum, nodes_kept_sum, peak_nodes, peak_kept).
     openings = (plies, opening_seed): every game first plays a random opening of `plies` plies (at most 16) without any search
     (oz_arena_set_openings, rules_random_openings); game slot g plays opening first_opening_id + g whatever seed and first_game_id are, so two
     arenas given the same (openings, first_opening_id) start from the same positions.  opening_moves = (moves uint8 (num_games, 16), n_plies int32
@@ -539,6 +544,7 @@ def arena_batch(net_a, net_b, board_size=8, num_games=512, num_simulations=800, 
     pb_, pw_ = _lib.check_proofs_pair(proofs, value_signs)
     ppb_, ppw_ = _lib.check_proof_play_pair(proof_play, (pb_, pw_))
     sel_pair = _lib.check_selection_pair(selection)
+    gc_pair = _lib.check_tree_gc_pair(tree_gc)
     kb, kw = (leaves_per_step, leaves_per_step) if np.isscalar(leaves_per_step) else leaves_per_step
     minimax = _lib.check_opponents(opponent, net_a is None, net_b is None)
     lib = _lib.require_gpu()
@@ -564,6 +570,9 @@ def arena_batch(net_a, net_b, board_size=8, num_games=512, num_simulations=800, 
         for side, sel in zip((1, -1), sel_pair):
             if sel[0]:
                 _lib.check(lib.oz_arena_set_selection(h, side, *sel))
+        for side, net, mode in zip((1, -1), (net_a, net_b), gc_pair):
+            if mode and net is not None:
+                _lib.check(lib.oz_arena_set_tree_gc(h, side, mode))
         if opening is not None and opening[0] == "random":
             _lib.check(lib.oz_arena_set_openings(h, opening[1], opening[2], opening[3]))
         elif opening is not None:
@@ -579,6 +588,14 @@ def arena_batch(net_a, net_b, board_size=8, num_games=512, num_simulations=800, 
             rb, rw = C.c_int64(), C.c_int64()
             _lib.check(lib.oz_arena_get_solve_leaves(h, C.byref(rb), C.byref(rw)))
             rows = (rb.value, rw.value)
+        gc_stats = None
+        if any(gc_pair):
+            gc_stats = []
+            for side in (1, -1):
+                st = _lib.TreeGcStats()
+                _lib.check(lib.oz_arena_get_tree_gc(h, side, None, C.byref(st)))
+                gc_stats.append(_lib.tree_gc_stats_dict(st))
+            gc_stats = tuple(gc_stats)
         tree = opp_kernel = None
         if profile and any(minimax):
             ms1, cnt1 = C.c_double(), C.c_int64()
@@ -607,4 +624,5 @@ def arena_batch(net_a, net_b, board_size=8, num_games=512, num_simulations=800, 
     return dict(winner=winner, points=points, n_moves=nm, actions=acts, players=pls, final_black=fb, final_white=fw,
                 stats_black=sa, stats_white=sb, leaves_evaluated=ea.value + eb.value, tree_kernels=tree,
                 **({"opponent_kernel": opp_kernel} if any(minimax) else {}), **({"rows_solved": rows} if rows is not None else {}),
-                **({"opening_plies": opening_plies} if opening is not None else {}))
+                **({"opening_plies": opening_plies} if opening is not None else {}),
+                **({"tree_gc_stats": gc_stats} if gc_stats is not None else {}))

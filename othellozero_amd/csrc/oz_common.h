@@ -551,6 +551,16 @@ __host__ __device__ inline double oz_tree_sum64(const double* x /* [64] */) {
     return s[0];
 }
 
+// ---------------------------------------------------------------- tree collection: which stored nodes a slot can still look up
+// (include/othellozero_amd.h, "tree collection").  Every move adds exactly one disc and a pass creates no node (the child is stored as
+// OthelloGame.play leaves it), so a descent from a root with D discs looks up the root itself and positions with more than D discs, nothing
+// else: a stored node that is not the root and holds <= D discs is dead, every other node keeps its statistics.  (Reachability through the
+// `child` indices would be the wrong rule: a transposed child that IS in the table reads -1 on an edge until that edge is descended.)
+// The one definition k_tree_collect (oz_search.hip) and the host's oz_search_tree_keep share.
+OZ_HD bool oz_tree_keep(uint64_t root_own, uint64_t root_opp, uint64_t own, uint64_t opp) {
+    return (own == root_own && opp == root_opp) || oz_popc(own | opp) > oz_popc(root_own | root_opp);
+}
+
 // ---------------------------------------------------------------- root value and value targets
 // (include/othellozero_amd.h, "value targets").  The root value of a search: the visit-weighted mean of the root's Q, for the player to
 // move.  a[sq] = oz_root_term: (double)N * Q where N > 0, else 0 (counts are 0 off the legal set); oz_root_mean = pairwise_sum(a, 64) /

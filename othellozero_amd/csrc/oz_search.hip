@@ -1355,6 +1355,16 @@ __global__ void k_wide_left(MctsDev t, WideDev w) {
     if ((threadIdx.x & 63) == 0 && m > 0) atomicMax(w.max_left, m);
 }
 
+// tree collection ("tree collection" below): what k_tree_collect gets beside MctsDev.  An object that never arms it allocates and passes nothing.
+enum { GC_COLLECTIONS = 0, GC_BEFORE = 1, GC_KEPT = 2, GC_PEAK_NODES = 3, GC_PEAK_KEPT = 4, OZ_NGCSTAT = 5 };
+struct TreeGcDev {
+    int* map;                  // [G][node_cap] old index -> new index, -1 where dropped (scratch of one launch)
+    long long* stat;           // [G][OZ_NGCSTAT] per game, no atomics: summed / maximised at the read
+    long long* last;           // [G][2] nodes before, nodes kept of the LAST launch (0, 0 where the slot was not collected)
+    int mode;                  // OZ_TREE_GC_ON_DEMAND: only where node_count + sims > node_cap; OZ_TREE_GC_EVERY_MOVE: every active slot
+    int sims;
+};
+
 // ---------------------------------------------------------------- host object
 struct oz_mcts {
     MctsDev d;
@@ -1394,6 +1404,10 @@ struct oz_mcts {
     unsigned* solve_claim = nullptr; unsigned long long* solve_rows = nullptr;
     bool solve_profile = false;      // oz_mcts_solve_leaves_profile: HIP events around k_solve_leaves
     OzTimer solve_timer{1};
+    // tree collection (oz_mcts_collect, oz_*_set_tree_gc): gc.map == nullptr until the object's first arming
+    TreeGcDev gc{};
+    bool gc_profile = false;         // oz_selfplay_tree_gc_profile: HIP events around k_tree_collect
+    OzTimer gc_timer{1};
 
     template <typename T> int alloc(T** p, size_t count) {
         OZ_HIP(hipMalloc((void**)p, sizeof(T) * (count ? count : 1)));
@@ -1488,6 +1502,7 @@ static void mcts_destroy(oz_mcts* m) {
     hipStreamSynchronize(m->stream);
     m->timer.destroy();
     m->solve_timer.destroy();
+    m->gc_timer.destroy();
     for (void* p : m->allocs) hipFree(p);
     hipStreamDestroy(m->stream);
     delete m;
@@ -3110,6 +3125,206 @@ OZ_API int oz_mcts_stats(oz_mcts* m, int64_t* out5) {
     return mcts_stats_locked(m, out5);
 }
 
+// ---------------------------------------------------------------- tree collection: drop the nodes a slot's game has passed (opt-in)
+// (the semantics are stated in include/othellozero_amd.h, "tree collection"; the rule is oz_tree_keep, oz_common.h.)
+// One wave per game, active slots only, against the slot's current root.  What holds a record index across move rounds, and what becomes of it:
+//   * every edge's `child`: -1 stays, anything else becomes map[child] (a kept node's child holds more discs than the root: kept too);
+//   * root_node[g]: set to -1, whoever needs the root looks it up again (the descents, root_lookup);
+//   * the OzProof entry of a node (an array parallel to the records): moves with its record;
+//   * the hash table: zeroed and refilled from the kept records.
+// path / the per-(game, j) arrays of the leaf-parallel search / leaf_* / hit_entry live inside a step and no step is pending here; Gumbel's n0,
+// the noise eta are by square; vhat (header word 3) travels inside the record.  An expansion writes every byte of a record (and of its proof
+// entry) that any reader reads -- the header whole, popcount(legal) edges, the unused half of the last 16-byte chunk -- so the freed tail is
+// left as it is: the next expansion into a freed index overwrites what will be read of it.
+// A kernel of its own with arguments of its own (MctsDev is untouched): an object that never arms the option launches and allocates nothing.
+__global__ __launch_bounds__(64) void k_tree_collect(MctsDev t, TreeGcDev gc) {
+    const int g = blockIdx.x, lane = threadIdx.x;
+    if (lane == 0) { gc.last[(size_t)g * 2] = 0; gc.last[(size_t)g * 2 + 1] = 0; }
+    if (!unii((int)t.active[g])) return;
+    const int nc = unii(t.node_count[g]);
+    long long* st = gc.stat + (size_t)g * OZ_NGCSTAT;
+    if (lane == 0 && (long long)nc > st[GC_PEAK_NODES]) st[GC_PEAK_NODES] = nc;
+    if (nc < 0 || nc > t.node_cap) { if (lane == 0) atomicOr(t.error_flag, EF_CORRUPT); return; }
+    if (gc.mode == OZ_TREE_GC_ON_DEMAND && (long long)nc + (long long)gc.sims <= (long long)t.node_cap) return;     // (uniform: a simulation expands at most one node)
+    const uint64_t ro = uni64(t.root_own[g]), rp = uni64(t.root_opp[g]);
+    int* __restrict__ map = gc.map + (size_t)g * t.node_cap;
+    // pass 1, the plan: a lane per record header, ballot + prefix popcount per 64 = the stable old -> new map
+    int kept = 0;
+    for (int base = 0; base < nc; base += 64) {
+        const int i = base + lane;
+        bool keep = false;
+        if (i < nc) {
+            const uint64_t* h = reinterpret_cast<const uint64_t*>(rec_ptr(t, g, i));
+            keep = oz_tree_keep(ro, rp, h[0], h[1]);
+        }
+        const uint64_t kb = __ballot(keep);
+        if (i < nc) map[i] = keep ? kept + oz_popc(kb & ((1ULL << lane) - 1ULL)) : -1;
+        kept += oz_popc(kb);
+    }
+    __threadfence();
+    __syncthreads();
+    // pass 2, the move: kept records to their new index in ascending order, in place (dst <= src and records are disjoint strides: a forward
+    // sweep never overwrites a record it has yet to read).  One wave-wide 16-byte load per record, as the descent's; every byte as it was
+    // except the edges' child words.
+    const int rec_chunks = t.rec_bytes >> 4;                       // <= 64
+    bool bad = false;
+    for (int base = 0; base < nc; base += 64) {
+        const int mi = base + lane < nc ? map[base + lane] : -1;
+        uint64_t kb = __ballot(mi >= 0);
+        while (kb) {
+            const int l = oz_ctz(kb);
+            kb &= kb - 1;
+            const int src = base + l, dst = lane_get(mi, l);
+            uint4 v = make_uint4(0, 0, 0, 0);
+            if (lane < rec_chunks) v = reinterpret_cast<const uint4*>(rec_ptr(t, g, src))[lane];
+            int cnt = lane_get((int)v.y, 1);                       // header word 2 = Ns | cnt << 32: the high half is lane 1's .y
+            if (cnt < 0 || cnt > t.row_cap) { bad = true; cnt = 0; }
+            const int chunks = (OZ_REC_HDR + cnt * OZ_EDGE_BYTES + 15) >> 4;
+            uint32_t x[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int w = 4 * lane + j - 9;                    // the child of edge r is 32-bit word 9 + 6 r of the record
+                if (w >= 0 && w % 6 == 0 && w / 6 < cnt && (int)x[j] != -1) {
+                    const int c = (int)x[j];
+                    int nm = -1;
+                    if ((unsigned)c < (unsigned)nc) nm = map[c];
+                    if (nm < 0) bad = true;                        // never a dangling index: the edge forgets its child (and the error is raised)
+                    x[j] = (uint32_t)nm;
+                }
+            }
+            if (lane < chunks) reinterpret_cast<uint4*>(rec_ptr(t, g, dst))[lane] = make_uint4(x[0], x[1], x[2], x[3]);
+            if (t.pf.entry != nullptr && dst != src) {
+                uint4 pv = make_uint4(0, 0, 0, 0);
+                if (lane < 2) pv = reinterpret_cast<const uint4*>(t.pf.entry + (size_t)g * t.node_cap + src)[lane];
+                if (lane < 2) reinterpret_cast<uint4*>(t.pf.entry + (size_t)g * t.node_cap + dst)[lane] = pv;
+            }
+        }
+    }
+    if (__ballot(bad) && lane == 0) atomicOr(t.error_flag, EF_CORRUPT);
+    // pass 3, the hash table: empty the game's window, then the kept nodes 64 at a time, each by linear probing from its key's base slot --
+    // a slot only ever goes from empty to taken, so every slot between a key's base and its entry is taken: what ht_find relies on
+    uint32_t* ht = t.ht + (size_t)g * t.ht_cap;
+    const int mask = t.ht_cap - 1;
+    for (int i = lane; i < t.ht_cap; i += 64) ht[i] = 0;
+    __threadfence();
+    __syncthreads();
+    for (int base = 0; base < kept; base += 64) {
+        const int i = base + lane;
+        if (i < kept) {
+            const uint64_t* h = reinterpret_cast<const uint64_t*>(rec_ptr(t, g, i));
+            const uint64_t own = h[0], opp = h[1];
+            const uint32_t e = ht_entry(own, opp, i);
+            int slot = (int)((uint32_t)(key_hash64(own, opp) >> 17) & (uint32_t)mask);
+            for (int probed = 0; probed < t.ht_cap; ++probed, slot = (slot + 1) & mask)     // (ht_cap >= 2 node_cap: a free slot exists)
+                if (atomicCAS(&ht[slot], 0u, e) == 0u) break;
+        }
+    }
+    // pass 4, the counters
+    if (lane == 0) {
+        t.node_count[g] = kept;
+        t.root_node[g] = -1;
+        st[GC_COLLECTIONS] += 1; st[GC_BEFORE] += nc; st[GC_KEPT] += kept;
+        if ((long long)kept > st[GC_PEAK_KEPT]) st[GC_PEAK_KEPT] = kept;
+        gc.last[(size_t)g * 2] = nc; gc.last[(size_t)g * 2 + 1] = kept;
+    }
+}
+
+static int tree_gc_check(const char* fn, int mode) {
+    OZ_REQUIRE(mode == OZ_TREE_GC_OFF || mode == OZ_TREE_GC_ON_DEMAND || mode == OZ_TREE_GC_EVERY_MOVE, "%s: unknown tree_gc mode %d", fn, mode);
+    return OZ_OK;
+}
+// the scratch map and the counters, at the object's first arming
+static int tree_gc_alloc(oz_mcts* m) {
+    if (m->gc.map) return OZ_OK;
+    hipSetDevice(m->device);
+    const MctsDev& d = m->d;
+    const size_t held = m->allocs.size();
+    TreeGcDev gc{};
+    int rc = m->alloc(&gc.map, (size_t)d.G * d.node_cap);
+    if (!rc) rc = m->alloc(&gc.stat, (size_t)d.G * OZ_NGCSTAT);
+    if (!rc) rc = m->alloc(&gc.last, (size_t)d.G * 2);
+    if (rc) {
+        for (size_t i = held; i < m->allocs.size(); ++i) hipFree(m->allocs[i]);
+        m->allocs.resize(held);
+        return rc;
+    }
+    OZ_HIP(hipMemsetAsync(gc.stat, 0, sizeof(long long) * (size_t)d.G * OZ_NGCSTAT, m->stream));
+    OZ_HIP(hipMemsetAsync(gc.last, 0, sizeof(long long) * (size_t)d.G * 2, m->stream));
+    m->gc = gc;
+    return OZ_OK;
+}
+// one launch on m->stream (the object is armed: tree_gc_alloc has run); sims = the budget ON_DEMAND makes room for
+static void tree_collect_async(oz_mcts* m, int mode, int sims) {
+    TreeGcDev gc = m->gc;
+    gc.mode = mode; gc.sims = sims;
+    const long long ti = m->gc_profile ? m->gc_timer.begin(0, m->stream) : -1;
+    hipLaunchKernelGGL(k_tree_collect, dim3(m->d.G), dim3(64), 0, m->stream, m->d, gc);
+    m->gc_timer.end(ti, m->stream);
+    if (m->gc_profile && m->gc_timer.backlog() > 4096) m->gc_timer.drain();
+}
+static int tree_gc_stats_locked(oz_mcts* m, oz_tree_gc_stats* out) {
+    memset(out, 0, sizeof *out);
+    if (!m->gc.stat) return OZ_OK;
+    hipSetDevice(m->device);
+    const size_t cnt = (size_t)m->d.G * OZ_NGCSTAT;
+    std::vector<long long> h(cnt);
+    OZ_HIP(hipMemcpyAsync(h.data(), m->gc.stat, sizeof(long long) * cnt, hipMemcpyDeviceToHost, m->stream));
+    OZ_HIP(hipStreamSynchronize(m->stream));
+    for (int g = 0; g < m->d.G; ++g) {
+        const long long* s = h.data() + (size_t)g * OZ_NGCSTAT;
+        out->collections += s[GC_COLLECTIONS]; out->nodes_before_sum += s[GC_BEFORE]; out->nodes_kept_sum += s[GC_KEPT];
+        if (s[GC_PEAK_NODES] > out->peak_nodes) out->peak_nodes = s[GC_PEAK_NODES];
+        if (s[GC_PEAK_KEPT] > out->peak_kept) out->peak_kept = s[GC_PEAK_KEPT];
+    }
+    return OZ_OK;
+}
+static int tree_gc_profile_read_locked(oz_mcts* m, double* ms_total, int64_t* launches, int reset) {
+    hipSetDevice(m->device);
+    if (m->gc_timer.collect() != OZ_OK) { oz_set_error("HIP event timing failed"); return OZ_ERR_HIP; }
+    if (ms_total) *ms_total = m->gc_timer.ms[0];
+    if (launches) *launches = m->gc_timer.count[0];
+    if (reset) m->gc_timer.reset();
+    return OZ_OK;
+}
+
+OZ_API int oz_mcts_collect(oz_mcts* m, int64_t* out2) {
+    OZ_REQUIRE(m, "null mcts");
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (m->selected) { oz_set_error("oz_mcts_collect: a host-evaluated step is pending (oz_mcts_select without oz_mcts_backup)"); return OZ_ERR_STATE; }
+    hipSetDevice(m->device);
+    if (int rc = tree_gc_alloc(m)) return rc;
+    tree_collect_async(m, OZ_TREE_GC_EVERY_MOVE, 0);
+    OZ_HIP(hipGetLastError());
+    std::vector<long long> last((size_t)m->d.G * 2);
+    OZ_HIP(hipMemcpyAsync(last.data(), m->gc.last, sizeof(long long) * last.size(), hipMemcpyDeviceToHost, m->stream));
+    OZ_HIP(hipStreamSynchronize(m->stream));
+    if (out2) {
+        out2[0] = out2[1] = 0;
+        for (int g = 0; g < m->d.G; ++g) { out2[0] += last[(size_t)g * 2]; out2[1] += last[(size_t)g * 2 + 1]; }
+    }
+    return check_error_flag(m);
+}
+OZ_API int oz_mcts_tree_gc_stats(oz_mcts* m, oz_tree_gc_stats* stats) {
+    OZ_REQUIRE(m && stats, "null argument");
+    std::lock_guard<std::mutex> lk(m->mu);
+    return tree_gc_stats_locked(m, stats);
+}
+// the rule on the host, no device needed
+OZ_API int oz_search_tree_keep(uint64_t root_own, uint64_t root_opp, const uint64_t* own, const uint64_t* opp, int64_t count, uint8_t* keep,
+                               int32_t* new_index, int64_t* kept) {
+    OZ_REQUIRE(count >= 0 && (count == 0 || (own && opp && keep && new_index)) && kept, "oz_search_tree_keep: null argument or count %lld < 0", (long long)count);
+    OZ_REQUIRE(count <= 0x7FFFFFFFLL, "oz_search_tree_keep: count %lld does not fit a node index", (long long)count);
+    int64_t k = 0;
+    for (int64_t i = 0; i < count; ++i) {
+        const bool kp = oz_tree_keep(root_own, root_opp, own[i], opp[i]);
+        keep[i] = kp ? 1 : 0;
+        new_index[i] = kp ? (int32_t)k : -1;
+        k += kp ? 1 : 0;
+    }
+    *kept = k;
+    return OZ_OK;
+}
+
 // ================================================================ self-play driver
 struct GamesDev {
     int G, n;
@@ -3805,6 +4020,8 @@ struct oz_selfplay {
     bool proof_play = false, arena_proof_play[2] = {false, false};
     ProofPlay pplay{nullptr, nullptr};
     long long* d_pt = nullptr;       // oz_selfplay_proof_targets: its three counters (allocated by the first call)
+    // oz_selfplay_set_tree_gc (the arena: oz_arena_set_tree_gc, [0] BLACK's agent, [1] WHITE's): k_tree_collect after the round's roots kernel
+    int tree_gc = OZ_TREE_GC_OFF, arena_tree_gc[2] = {OZ_TREE_GC_OFF, OZ_TREE_GC_OFF};
     template <typename T> int alloc(T** p, size_t count) {
         OZ_HIP(hipMalloc((void**)p, sizeof(T) * (count ? count : 1)));
         allocs.push_back(*p);
@@ -3914,6 +4131,7 @@ static int selfplay_round_async(oz_selfplay* sp, int sims, int stagger_round) {
     timed(m, TS_MOVE, m->profile, [&] {
         if (stagger_round >= 0) hipLaunchKernelGGL(k_sp_roots_stagger, gg, dim3(256), 0, s, sp->gm, m->d, stagger_round, sp->stagger_period);
         else hipLaunchKernelGGL(k_sp_roots, gg, dim3(256), 0, s, sp->gm, m->d, 0);
+        if (sp->tree_gc != OZ_TREE_GC_OFF) tree_collect_async(m, sp->tree_gc, sims);      // before whoever looks the new roots up (Gumbel arming, the descents)
         if (sp->gumbel_on) hipLaunchKernelGGL(k_gumbel_arm, dim3(G), dim3(64), 0, s, m->d, m->gd, 1, sp->gm.seed, (const uint64_t*)sp->gm.game_id, (const int*)sp->gm.ply, (const uint8_t*)nullptr);
         if (sp->noise_on && capped) hipLaunchKernelGGL(k_root_noise_c, dim3(G), dim3(64), 0, s, m->d, sp->noise_alpha, ck);
         else if (sp->noise_on) hipLaunchKernelGGL(k_root_noise, dim3(G), dim3(64), 0, s, m->d, sp->noise_alpha, sp->gm.seed, (const uint64_t*)sp->gm.game_id, (const int*)sp->gm.ply);
@@ -3982,6 +4200,7 @@ OZ_API int oz_selfplay_stagger(oz_selfplay* sp, int sims_pre) {
     if (sp->m->d.sel.flags) { oz_set_error("oz_selfplay_stagger: not with the selection option (it continues on the free-running kernels; use oz_selfplay_run)"); return OZ_ERR_STATE; }
     if (sp->gumbel_on) { oz_set_error("oz_selfplay_stagger: not with the Gumbel search (its budget is num_simulations; use oz_selfplay_run)"); return OZ_ERR_STATE; }
     if (sp->resign.r > 0) { oz_set_error("oz_selfplay_stagger: not with resignation (its rounds search at sims_pre; use oz_selfplay_run)"); return OZ_ERR_STATE; }
+    if (sp->tree_gc != OZ_TREE_GC_OFF) { oz_set_error("oz_selfplay_stagger: not with tree collection (it continues on the free-running kernels; use oz_selfplay_run)"); return OZ_ERR_STATE; }
     OZ_REQUIRE(sp->cfg.refill, "oz_selfplay_stagger is for continuous self-play (cfg.refill = 1)");
     sp->mode = 1;
     selfplay_attach_cache(sp);
@@ -4131,6 +4350,41 @@ OZ_API int oz_selfplay_solve_leaves_profile_read(oz_selfplay* sp, double* ms_tot
     OZ_REQUIRE(sp, "null selfplay");
     std::lock_guard<std::mutex> lk(sp->mu);
     return oz_mcts_solve_leaves_profile_read(sp->m, ms_total, launches, reset);
+}
+
+// tree collection for the rounds of oz_selfplay_run (see oz_mcts_collect); before the first driver call.  The free-running k_advance* family
+// moves inside the kernel and would need the collection as a device call there: oz_selfplay_run_steps / oz_selfplay_stagger refuse the option.
+OZ_API int oz_selfplay_set_tree_gc(oz_selfplay* sp, int mode) {
+    OZ_REQUIRE(sp, "null selfplay");
+    if (int rc = tree_gc_check("oz_selfplay_set_tree_gc", mode)) return rc;
+    std::lock_guard<std::mutex> lk(sp->mu);
+    if (sp->mode != 0) { oz_set_error("oz_selfplay_set_tree_gc: the engine has been driven already (set it before the first driver call)"); return OZ_ERR_STATE; }
+    std::lock_guard<std::mutex> lkm(sp->m->mu);
+    if (mode != OZ_TREE_GC_OFF) if (int rc = tree_gc_alloc(sp->m)) return rc;
+    sp->tree_gc = mode;
+    return OZ_OK;
+}
+OZ_API int oz_selfplay_get_tree_gc(oz_selfplay* sp, int* mode, oz_tree_gc_stats* stats) {
+    OZ_REQUIRE(sp, "null selfplay");
+    std::lock_guard<std::mutex> lk(sp->mu);
+    std::lock_guard<std::mutex> lkm(sp->m->mu);
+    if (mode) *mode = sp->tree_gc;
+    if (stats) return tree_gc_stats_locked(sp->m, stats);
+    return OZ_OK;
+}
+// HIP-event timing of the engine's collection launches; off, nothing is recorded
+OZ_API int oz_selfplay_tree_gc_profile(oz_selfplay* sp, int enable) {
+    OZ_REQUIRE(sp, "null selfplay");
+    std::lock_guard<std::mutex> lk(sp->mu);
+    std::lock_guard<std::mutex> lkm(sp->m->mu);
+    sp->m->gc_profile = enable != 0;
+    return OZ_OK;
+}
+OZ_API int oz_selfplay_tree_gc_profile_read(oz_selfplay* sp, double* ms_total, int64_t* launches, int reset) {
+    OZ_REQUIRE(sp, "null selfplay");
+    std::lock_guard<std::mutex> lk(sp->mu);
+    std::lock_guard<std::mutex> lkm(sp->m->mu);
+    return tree_gc_profile_read_locked(sp->m, ms_total, launches, reset);
 }
 
 // root noise for every searched move of the engine (the lock-step rounds, oz_selfplay_stagger's included, and the free-running driver); before
@@ -4442,6 +4696,7 @@ OZ_API int oz_selfplay_run_steps(oz_selfplay* sp, int steps) {
     if (sp->m->proofs) { oz_set_error("oz_selfplay_run_steps: the free-running driver keeps no proofs; use oz_selfplay_run"); return OZ_ERR_STATE; }
     if (sp->m->d.sel.flags) { oz_set_error("oz_selfplay_run_steps: the free-running kernels have no selection instantiation; use oz_selfplay_run"); return OZ_ERR_STATE; }
     if (sp->resign.r > 0) { oz_set_error("oz_selfplay_run_steps: the free-running driver does not resign games; use oz_selfplay_run"); return OZ_ERR_STATE; }
+    if (sp->tree_gc != OZ_TREE_GC_OFF) { oz_set_error("oz_selfplay_run_steps: the free-running driver moves inside its kernels and does not collect the tree; use oz_selfplay_run"); return OZ_ERR_STATE; }
     std::lock_guard<std::mutex> lkn(sp->net->mu);
     oz_mcts* m = sp->m;
     hipSetDevice(m->device);
@@ -5408,6 +5663,29 @@ OZ_API int oz_arena_set_proof_play(oz_arena* a, int black, int white) {
     a->games.arena_proof_play[0] = black != 0; a->games.arena_proof_play[1] = white != 0;
     return OZ_OK;
 }
+// tree collection of one agent's search (see oz_mcts_collect): agent +1 = BLACK (net_a), -1 = WHITE (net_b); before the first run
+OZ_API int oz_arena_set_tree_gc(oz_arena* a, int agent, int mode) {
+    OZ_REQUIRE(a, "null arena");
+    OZ_REQUIRE(agent == 1 || agent == -1, "oz_arena_set_tree_gc: agent %d (+1 BLACK, -1 WHITE)", agent);
+    if (int rc = tree_gc_check("oz_arena_set_tree_gc", mode)) return rc;
+    std::lock_guard<std::mutex> lk(a->mu);
+    if (a->started) { oz_set_error("oz_arena_set_tree_gc: the arena has run already (set it before the first run)"); return OZ_ERR_STATE; }
+    oz_mcts* m = agent == 1 ? a->games.m : a->mb;
+    std::lock_guard<std::mutex> lkm(m->mu);
+    if (mode != OZ_TREE_GC_OFF) if (int rc = tree_gc_alloc(m)) return rc;
+    a->games.arena_tree_gc[agent == 1 ? 0 : 1] = mode;
+    return OZ_OK;
+}
+OZ_API int oz_arena_get_tree_gc(oz_arena* a, int agent, int* mode, oz_tree_gc_stats* stats) {
+    OZ_REQUIRE(a, "null arena");
+    OZ_REQUIRE(agent == 1 || agent == -1, "oz_arena_get_tree_gc: agent %d (+1 BLACK, -1 WHITE)", agent);
+    std::lock_guard<std::mutex> lk(a->mu);
+    oz_mcts* m = agent == 1 ? a->games.m : a->mb;
+    std::lock_guard<std::mutex> lkm(m->mu);
+    if (mode) *mode = a->games.arena_tree_gc[agent == 1 ? 0 : 1];
+    if (stats) return tree_gc_stats_locked(m, stats);
+    return OZ_OK;
+}
 OZ_API int oz_arena_get_solve_leaves(oz_arena* a, int64_t* rows_black, int64_t* rows_white) {
     OZ_REQUIRE(a && rows_black && rows_white, "null argument");
     std::lock_guard<std::mutex> lk(a->mu);
@@ -5565,7 +5843,9 @@ OZ_API int oz_arena_run_rounds(oz_arena* a, int max_rounds_arg) {
         if (movers[0] + movers[1] == 0) break;               // every game is over
         const bool run_a = a->na && movers[0] > 0, run_b = a->nb && movers[1] > 0;
         if (run_a) hipLaunchKernelGGL(k_sp_roots, dim3((G + 255) / 256), dim3(256), 0, s, sp->gm, ma->d, 1);
+        if (run_a && sp->arena_tree_gc[0] != OZ_TREE_GC_OFF) tree_collect_async(ma, sp->arena_tree_gc[0], a->sims);
         if (run_b) hipLaunchKernelGGL(k_sp_roots, dim3((G + 255) / 256), dim3(256), 0, s, sp->gm, mb->d, -1);
+        if (run_b && sp->arena_tree_gc[1] != OZ_TREE_GC_OFF) tree_collect_async(mb, sp->arena_tree_gc[1], a->sims);
         // the evaluator's launches are made for the movers of the round (an upper bound of the leaves a batch can hold), not for all G slots
         if (run_a) {
             std::lock_guard<std::mutex> la(a->na->mu);

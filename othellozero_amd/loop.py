@@ -174,7 +174,7 @@ def evaluate_against_random(board_size, neural_network, games, num_simulations, 
 
 def evaluate_against_random_batch(board_size, neural_network, games, num_simulations, degree_exploration, seed=0, leaves_per_step=1,
                                   opponent=None, solve_leaves=0, openings=None, value_signs="reference", proofs=False,
-                                  proof_play=False, selection=None):
+                                  proof_play=False, selection=None, tree_gc="off"):
     """The same evaluation as `evaluate_against_random` played in lock step on the GPU (agents.arena_batch with a random
     mover): the network takes BLACK in the first games // 2 + games % 2 games and WHITE in the rest (the reference draws the
     colours with random.shuffle; the split here is fixed).  opponent: arena_batch's (None / "random", or ("minimax", depth[, evaluation])).
@@ -190,10 +190,11 @@ def evaluate_against_random_batch(board_size, neural_network, games, num_simulat
     _lib.check_value_signs(value_signs)
     _lib.check_proofs(proofs, value_signs)
     _lib.check_proof_play(proof_play, proofs)
+    _lib.check_tree_gc(tree_gc)
     _lib.check_selection(selection)
     _lib.check_openings(openings)
     opening_kw = dict({"openings": openings, "first_opening_id": 0} if openings is not None else {}, **({"value_signs": value_signs} if value_signs != "reference" else {}), **_lib.proofs_kw(proofs),
-                      **_lib.proof_play_kw(proof_play), **_lib.selection_kw(selection))
+                      **_lib.proof_play_kw(proof_play), **_lib.selection_kw(selection), **_lib.tree_gc_kw(tree_gc))
     as_black, as_white = games // 2 + games % 2, games // 2
     r = dict(wins=0, black_wins=0, black_games=0, white_wins=0, white_games=0)
     if as_black:
@@ -217,17 +218,18 @@ def evaluate_against_opponent(board_size, neural_network, games, num_simulations
 
 
 def evaluate_against_opponent_batch(board_size, neural_network, games, num_simulations, degree_exploration, opponent, seed=0, leaves_per_step=1,
-                                    solve_leaves=0, openings=None, value_signs="reference", proofs=False, proof_play=False, selection=None):
+                                    solve_leaves=0, openings=None, value_signs="reference", proofs=False, proof_play=False, selection=None, tree_gc="off"):
     """`evaluate_against_random_batch` under the name that says what it does when the opponent is not the random agent"""
     solve_leaves = _lib.check_solve_leaves(solve_leaves)
     _lib.check_value_signs(value_signs)
     _lib.check_proofs(proofs, value_signs)
     _lib.check_proof_play(proof_play, proofs)
+    _lib.check_tree_gc(tree_gc)
     _lib.check_selection(selection)
     return evaluate_against_random_batch(board_size, neural_network, games, num_simulations, degree_exploration, seed=seed,
                                          leaves_per_step=leaves_per_step, opponent=opponent, **({"solve_leaves": solve_leaves} if solve_leaves else {}),
                                          **({"openings": openings} if openings is not None else {}), **({"value_signs": value_signs} if value_signs != "reference" else {}), **_lib.proofs_kw(proofs),
-                                         **_lib.proof_play_kw(proof_play), **_lib.selection_kw(selection))
+                                         **_lib.proof_play_kw(proof_play), **_lib.selection_kw(selection), **_lib.tree_gc_kw(tree_gc))
 
 
 def _discs(boards):
@@ -261,7 +263,7 @@ def pair_statistics(new_black_final_black, new_black_final_white, old_black_fina
 
 
 def paired_match(board_size, neural_network, old_neural_network, pairs, num_simulations, degree_exploration, openings, seed=0, leaves_per_step=1,
-                 solve_leaves=0, value_signs="reference", proofs=False, proof_play=False, selection=None):
+                 solve_leaves=0, value_signs="reference", proofs=False, proof_play=False, selection=None, tree_gc="off"):
     """A match over an opening suite, every opening played twice with the colours swapped -- NOT the reference's match (main.py:110-134 starts
     every game from the standard position).  Two arenas of `pairs` games: the new network as BLACK against the old one, then the old one as
     BLACK against the new; both get openings=(plies, opening_seed) and first_opening_id=0, so game i of either starts with opening i.  Game ids
@@ -270,6 +272,7 @@ def paired_match(board_size, neural_network, old_neural_network, pairs, num_simu
     _lib.check_value_signs(value_signs)
     _lib.check_proofs(proofs, value_signs)
     _lib.check_proof_play(proof_play, proofs)
+    _lib.check_tree_gc(tree_gc)
     _lib.check_selection(selection)
     if openings is None:
         raise ValueError("paired_match needs openings=(plies, opening_seed): without them every pair is the same two games")
@@ -277,7 +280,7 @@ def paired_match(board_size, neural_network, old_neural_network, pairs, num_simu
     if isinstance(pairs, bool) or not isinstance(pairs, (int, np.integer)) or pairs < 1:
         raise ValueError(f"paired_match: pairs must be a whole number >= 1 (got {pairs!r})")
     kw = dict(leaves_per_step=leaves_per_step, openings=openings, first_opening_id=0, **({"solve_leaves": solve_leaves} if solve_leaves else {}),
-              **({"value_signs": value_signs} if value_signs != "reference" else {}), **_lib.proofs_kw(proofs), **_lib.proof_play_kw(proof_play), **_lib.selection_kw(selection))
+              **({"value_signs": value_signs} if value_signs != "reference" else {}), **_lib.proofs_kw(proofs), **_lib.proof_play_kw(proof_play), **_lib.selection_kw(selection), **_lib.tree_gc_kw(tree_gc))
     a = arena_batch(neural_network, old_neural_network, board_size, int(pairs), num_simulations, degree_exploration, seed=seed, **kw)
     b = arena_batch(old_neural_network, neural_network, board_size, int(pairs), num_simulations, degree_exploration, seed=seed,
                     first_game_id=int(pairs), **kw)
@@ -286,7 +289,7 @@ def paired_match(board_size, neural_network, old_neural_network, pairs, num_simu
 
 
 def self_play_match(board_size, neural_network, old_neural_network, total_games, num_simulations, degree_exploration, seed=0,
-                    leaves_per_step=1, solve_leaves=0, openings=None, value_signs="reference", proofs=False, proof_play=False, selection=None):
+                    leaves_per_step=1, solve_leaves=0, openings=None, value_signs="reference", proofs=False, proof_play=False, selection=None, tree_gc="off"):
     """main.py:110-134: total_games // 2 games with the new network as BLACK, the rest with it as WHITE.
     -> number of games the new network won (a drawn game goes to BLACK, like get_winning_player).
     solve_leaves=E > 0: both networks' searches take exact values for leaves with at most E empties (arena_batch).
@@ -299,6 +302,7 @@ def self_play_match(board_size, neural_network, old_neural_network, total_games,
     _lib.check_value_signs(value_signs)
     _lib.check_proofs(proofs, value_signs)
     _lib.check_proof_play(proof_play, proofs)
+    _lib.check_tree_gc(tree_gc)
     _lib.check_selection(selection)
     self_play_match.stats = None
     if openings is not None:
@@ -307,7 +311,7 @@ def self_play_match(board_size, neural_network, old_neural_network, total_games,
             raise ValueError(f"self_play_match with openings plays pairs of games: total_games must be even and >= 2 (got {total_games})")
         stats = paired_match(board_size, neural_network, old_neural_network, total_games // 2, num_simulations, degree_exploration, openings,
                              seed=seed, leaves_per_step=leaves_per_step, solve_leaves=solve_leaves, **({"value_signs": value_signs} if value_signs != "reference" else {}), **_lib.proofs_kw(proofs),
-                             **_lib.proof_play_kw(proof_play), **_lib.selection_kw(selection))
+                             **_lib.proof_play_kw(proof_play), **_lib.selection_kw(selection), **_lib.tree_gc_kw(tree_gc))
         self_play_match.stats = {k: v for k, v in stats.items() if k != "games"}
         return stats["wins"]
     as_black, as_white = total_games // 2, total_games // 2 + total_games % 2
@@ -315,12 +319,12 @@ def self_play_match(board_size, neural_network, old_neural_network, total_games,
     if as_black:
         res = arena_batch(neural_network, old_neural_network, board_size, as_black, num_simulations, degree_exploration, seed=seed,
                           leaves_per_step=leaves_per_step, **({"solve_leaves": solve_leaves} if solve_leaves else {}), **({"value_signs": value_signs} if value_signs != "reference" else {}), **_lib.proofs_kw(proofs),
-                          **_lib.proof_play_kw(proof_play), **_lib.selection_kw(selection))
+                          **_lib.proof_play_kw(proof_play), **_lib.selection_kw(selection), **_lib.tree_gc_kw(tree_gc))
         wins += int((res["winner"] == 1).sum())
     if as_white:
         res = arena_batch(old_neural_network, neural_network, board_size, as_white, num_simulations, degree_exploration,
                           seed=seed, first_game_id=as_black, leaves_per_step=leaves_per_step, **({"solve_leaves": solve_leaves} if solve_leaves else {}),
-                          **({"value_signs": value_signs} if value_signs != "reference" else {}), **_lib.proofs_kw(proofs), **_lib.proof_play_kw(proof_play), **_lib.selection_kw(selection))
+                          **({"value_signs": value_signs} if value_signs != "reference" else {}), **_lib.proofs_kw(proofs), **_lib.proof_play_kw(proof_play), **_lib.selection_kw(selection), **_lib.tree_gc_kw(tree_gc))
         wins += int((res["winner"] == -1).sum())
     return wins
 
@@ -329,7 +333,7 @@ def _selfplay_into_replay(replay, neural_network, board_size, num_episodes, num_
                           first_game_id, q_mode, visits, leaves_per_step, root_noise, sample_moves, alias_final_boards, policy_target,
                           target_temperature, endgame_targets=0, solve_leaves=0, playout_cap=None, forced_playouts=0.0, value_target="outcome",
                           gumbel=None, surprise_weight=None, resign=None, value_signs="reference", proofs=False, proof_play=False,
-                          proof_targets=False, selection=None):
+                          proof_targets=False, selection=None, tree_gc="off"):
     """one iteration's games on the engine selfplay_batch would create, played to the end without reading a record, and their examples
     appended to the device buffer; -> (records appended, the endgame solver's statistics or None).  One-channel (BaseNN) examples are never
     aliased (examples_from_records).  endgame_targets > 0: SelfPlayEngine.solve_records before the append.  playout_cap: the engine's; the
@@ -350,7 +354,7 @@ def _selfplay_into_replay(replay, neural_network, board_size, num_episodes, num_
                          **({"forced_playouts": forced_playouts} if forced_playouts else {}), **({"record_values": True} if vt_on else {}),
                          **({"gumbel": gumbel} if gumbel is not None else {}), **({"record_surprise": True} if surprise_weight is not None else {}),
                          **({"resign": resign} if resign is not None else {}), **({"value_signs": value_signs} if value_signs != "reference" else {}), **_lib.proofs_kw(proofs),
-                         **_lib.proof_play_kw(proof_play), **_lib.selection_kw(selection))
+                         **_lib.proof_play_kw(proof_play), **_lib.selection_kw(selection), **_lib.tree_gc_kw(tree_gc))
     for _ in range(board_size * board_size):
         eng.run(4)
         if eng.stats()["live_games"] == 0:
@@ -437,7 +441,7 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
              root_noise=None, sample_moves=None, replay="host", evaluation_opponent="random", endgame_targets=0,
              solve_leaves=0, match_openings=None, evaluation_openings=None, playout_cap=None, forced_playouts=None, eval_symmetry=None,
              value_target="outcome", gumbel=None, surprise_weight=None, resign=None, validation_share=None, value_signs="reference", proofs=False,
-             proof_play=False, proof_targets=False, selection=None):
+             proof_play=False, proof_targets=False, selection=None, tree_gc="off"):
     """main.py:56-259 on the GPU engines; returns `historic` = [(episodes done, win rate vs random), ...]
 
     validation_share=f in (0, 0.5] (None = off, the default: the loop is unchanged): held-out evaluation of every iteration's fit.  After an
@@ -551,6 +555,9 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
     and a prior-first first visit, each part on its own (OthelloMCTS, selection; include/othellozero_amd.h, "selection").  Not with gumbel or
     forced_playouts (ValueError).  The drop-in evaluation agents stay without it.  Playing strength is neither gated nor claimed (DESIGN.md,
     "Selection"; tools/selection_bench.py).
+    tree_gc="demand" | "every" ("off" = the default): every search of the batched engines -- self-play, matches and batched evaluation --
+    drops the stored nodes its games have passed (SelfPlayEngine, tree_gc; include/othellozero_amd.h, "tree collection").  No record, move
+    or result changes: the option only lets a smaller node capacity suffice ("Tree collection").
     proof_play=True (needs proofs=True; False = off, the default): the searches' exact knowledge reaches the three hand-overs it stopped short
     of.  The recorded visit row keeps the raw counts of the moves the descent would still pick at the root -- those that prove a known
     value, else those not proven lost -- and every move rule that reads counts reads that row, so a move proven lost after it took most of
@@ -664,11 +671,12 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
     _lib.check_value_signs(value_signs)
     _lib.check_proofs(proofs, value_signs, gumbel=gumbel, forced_playouts=forced_playouts)
     proof_play = _lib.check_proof_play(proof_play, proofs)
+    _lib.check_tree_gc(tree_gc)
     _lib.check_selection(selection, gumbel=gumbel, forced_playouts=forced_playouts)
     pt_kw = {"proof_targets": True} if _lib.check_proof_targets(proof_targets, proof_play) else {}
     training.proof_history = []
     training.proof_play_history = []
-    vs_kw = dict({"value_signs": value_signs} if value_signs != "reference" else {}, **_lib.proofs_kw(proofs), **_lib.proof_play_kw(proof_play), **_lib.selection_kw(selection))
+    vs_kw = dict({"value_signs": value_signs} if value_signs != "reference" else {}, **_lib.proofs_kw(proofs), **_lib.proof_play_kw(proof_play), **_lib.selection_kw(selection), **_lib.tree_gc_kw(tree_gc))
     training.rows_solved = 0
     endgame_targets = _lib.check_endgame_targets(endgame_targets, alias_final_boards)
     training.endgame_history = []

@@ -19,7 +19,7 @@ from .Othello import OthelloGame, OthelloPlayer
 class OthelloMCTS:
     def __init__(self, board_size, neural_network, degree_exploration, q_mode=_lib.QMODE_F64,
                  node_cap=8192, leaves_per_step=1, solve_leaves=0, forced_playouts=None, gumbel=None, value_signs="reference", proofs=False,
-                 proof_play=False, selection=None):
+                 proof_play=False, selection=None, tree_gc="off"):
         """q_mode: OZ_QMODE_F64 = the NumPy 1.18.5 promotion the reference pins (requirements.txt:19),
         OZ_QMODE_NEP50 = what NumPy >= 2 computes (SURVEY.md R-FP).
         leaves_per_step > 1 (native networks only, created with max_batch >= leaves_per_step): that many descents of the tree per
@@ -48,7 +48,16 @@ class OthelloMCTS:
         U = Q + c P sqrt(Ns) / (1 + N) with an unvisited move valued at the node's running value minus a reduction (first-play urgency)
         in place of 0, an exploration constant that grows with the node's visits, and a first visit that follows the prior
         (oz_mcts_set_selection; include/othellozero_amd.h, "selection").  None, or every part off, is the search as it was.  Every node then
-        keeps the value its expansion backed up (node_values).  Not with gumbel or forced_playouts.  Not the reference's search."""
+        keeps the value its expansion backed up (node_values).  Not with gumbel or forced_playouts.  Not the reference's search.
+        tree_gc="demand" | "every" ("off" is the default): collect() on the wrapper's own account (include/othellozero_amd.h, "tree
+        collection") -- "every": before a simulate / simulate_n call whose root differs from the previous call's; "demand": when the node
+        count at the last read plus the simulations since says the call may not fit node_cap (no read-back per simulation).  Counts, values
+        and policies are those of the object without the option as long as the roots' disc counts never decrease: a root set to an EARLIER
+        position finds its dropped nodes gone and expands them afresh -- a loss of statistics, never an error.  node_cap keeps its meaning
+        and default; the option makes a smaller one sufficient."""
+        self._gc_mode = _lib.check_tree_gc(tree_gc)
+        self.tree_gc = tree_gc
+        self._sim_root, self._gc_bound = None, 0
         self._selection = _lib.check_selection(selection, gumbel=gumbel, forced_playouts=forced_playouts)
         self.value_signs = value_signs
         vs_mode = _lib.check_value_signs(value_signs)
@@ -91,6 +100,16 @@ class OthelloMCTS:
             _lib.check(lib.oz_mcts_set_solve_leaves(self._h, self.solve_leaves))
         if self.gumbel is not None:                        # over the empty tree: the parameters, no root armed yet (the budget comes with the arming)
             _lib.check(lib.oz_mcts_set_gumbel(self._h, self.gumbel[0], self.gumbel[1], self.gumbel[2], 1, None, None))
+
+    # ---- tree collection (include/othellozero_amd.h, "tree collection")
+    def collect(self):
+        """drop the stored nodes the current root has passed (oz_mcts_collect): those that are not the root and hold no more discs than it.
+        -> (nodes before, nodes kept); (0, 0) before the first root is set.  No statistic of a kept node changes."""
+        out = np.zeros(2, np.int64)
+        _lib.check(_lib.load().oz_mcts_collect(self._h, _lib.p_i64(out)))
+        if self._root is not None:
+            self._gc_bound = int(out[1])
+        return int(out[0]), int(out[1])
 
     # ---- selection (include/othellozero_amd.h, "selection")
     @property
@@ -273,6 +292,12 @@ class OthelloMCTS:
         lib = _lib.load()
         own, opp = self._canonical(state, player)
         self._set_root(own, opp)
+        if self._gc_mode == _lib.TREE_GC["every"] and self._sim_root not in (None, (own, opp)):
+            self.collect()
+        elif self._gc_mode == _lib.TREE_GC["demand"] and self._gc_bound + int(count) > self._node_cap:
+            self.collect()
+        self._sim_root = (own, opp)
+        self._gc_bound += int(count)                       # a simulation expands at most one node
         n = self._board_size
         if self._native:
             _lib.check(lib.oz_mcts_simulate(self._h, self._neural_network._h, int(count)))

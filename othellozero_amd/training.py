@@ -34,7 +34,7 @@ def execute_episode(board_size, neural_network, degree_exploration, num_simulati
                     q_mode=_lib.QMODE_F64, snapshot_boards=False, policy_target="onehot", target_temperature=1.0,
                     leaves_per_step=1, root_noise=None, noise_seed=0, sample_moves=None, sample_seed=0, solve_leaves=0,
                     forced_playouts=None, value_target="outcome", gumbel=None, gumbel_seed=0, value_signs="reference", proofs=False,
-                    proof_play=False, selection=None):
+                    proof_play=False, selection=None, tree_gc="off", node_cap=0):
     """training.py:26-72.  Returns [(board (n,n,2) bool, one-hot policy (n,n) float64, z int), ...], 8 per move.
 
     gumbel=(max_considered, c_visit, c_scale) or True: every move's search is a Gumbel root search of num_simulations simulations
@@ -79,7 +79,11 @@ def execute_episode(board_size, neural_network, degree_exploration, num_simulati
     proof_play=True (needs proofs=True): the policy the move is taken from, the sampled move, the "visits" target and the recorded root
     value are those the root's proofs leave (OthelloMCTS.proven_counts / root_value(proven=True)); the explore branch is unchanged.
 
-    selection=dict(fpu=, cpuct_growth=, prior_first=): the selection rule of the search (OthelloMCTS); not with gumbel or forced_playouts."""
+    selection=dict(fpu=, cpuct_growth=, prior_first=): the selection rule of the search (OthelloMCTS); not with gumbel or forced_playouts.
+
+    tree_gc="demand" | "every": the search drops the nodes the game has passed (OthelloMCTS); the examples are those of "off".  node_cap > 0:
+    the search's node capacity in place of a whole game's nodes -- what the option makes sufficient."""
+    _lib.check_tree_gc(tree_gc)
     _lib.check_selection(selection, gumbel=gumbel, forced_playouts=forced_playouts)
     _lib.check_value_signs(value_signs)
     _lib.check_proofs(proofs, value_signs, gumbel=gumbel, forced_playouts=forced_playouts)
@@ -103,10 +107,10 @@ def execute_episode(board_size, neural_network, degree_exploration, num_simulati
     examples = []
     game = OthelloGame(board_size)
     mcts = OthelloMCTS(board_size, neural_network, degree_exploration, q_mode=q_mode,
-                       node_cap=num_simulations * (board_size * board_size - 3) + 64, leaves_per_step=leaves_per_step,
+                       node_cap=int(node_cap) if node_cap else num_simulations * (board_size * board_size - 3) + 64, leaves_per_step=leaves_per_step,
                        solve_leaves=solve_leaves, forced_playouts=forced_playouts, **({"gumbel": gumbel} if gumbel is not None else {}),
                        **({"value_signs": value_signs} if value_signs != "reference" else {}), **_lib.proofs_kw(proofs), **_lib.proof_play_kw(proof_play),
-                       **_lib.selection_kw(selection))
+                       **_lib.selection_kw(selection), **_lib.tree_gc_kw(tree_gc))
     # training.py:34-37 (BNN examples are one-channel boards, a fresh array per round: no aliasing for them)
     board_view_type = BoardView.ONE_CHANNEL if getattr(neural_network.network_type, "name", "") == "BNN" else BoardView.TWO_CHANNELS
 
@@ -208,7 +212,7 @@ class SelfPlayEngine:
                  q_mode=_lib.QMODE_F64, refill=False, node_cap=0, record_cap=0, dedup=True, batch_cap=0, eval_cache=False,
                  record_visits=False, leaves_per_step=1, root_noise=None, sample_moves=None, solve_leaves=0, playout_cap=None,
                  forced_playouts=None, record_values=False, gumbel=None, record_surprise=False, resign=None, value_signs="reference", proofs=False,
-                 proof_play=False, selection=None):
+                 proof_play=False, selection=None, tree_gc="off"):
         """dedup: cross-game leaf de-duplication (a board several games reach in one batch is evaluated once; no record changes);
         batch_cap: leaves per network batch of the free-running driver (0 = none; see preferred_batch_cap);
         eval_cache: take (pi, v) of boards the network has evaluated before from its persistent cache (NNetWrapper.set_eval_cache) --
@@ -283,7 +287,13 @@ class SelfPlayEngine:
         grow with the node's visits and sends a fresh node's first visit where the prior points (oz_selfplay_set_selection;
         include/othellozero_amd.h, "selection").  run() / play_to_end() at any leaves_per_step with every option but gumbel and
         forced_playouts (ValueError); run_steps() and stagger() then raise.  Records, rows and targets read what the search stores
-        (DESIGN.md, "Selection")."""
+        (DESIGN.md, "Selection").
+        tree_gc="demand" | "every" ("off" is the default): drop the stored nodes a slot's game has passed -- those that are not the root and
+        hold no more discs than it, which no descent can reach again -- right after the round's roots are set (oz_selfplay_set_tree_gc;
+        include/othellozero_amd.h, "tree collection").  No record, row or counter changes; node_cap can be far below a whole game's nodes.
+        "demand" collects a slot only when num_simulations more nodes might not fit, "every" every slot every round (diagnostic).  run() /
+        play_to_end() with every option; run_steps() and stagger() then raise.  tree_gc_stats() counts ("Tree collection")."""
+        tree_gc_mode = _lib.check_tree_gc(tree_gc)
         selection = _lib.check_selection(selection, gumbel=gumbel, forced_playouts=forced_playouts)
         vs_mode = _lib.check_value_signs(value_signs)
         proofs = _lib.check_proofs(proofs, value_signs, gumbel=gumbel, forced_playouts=forced_playouts)
@@ -353,6 +363,28 @@ class SelfPlayEngine:
         self.resign = resign
         if resign is not None:
             _lib.check(lib.oz_selfplay_set_resign(self._h, *resign))
+        self.tree_gc = tree_gc
+        if tree_gc_mode:
+            _lib.check(lib.oz_selfplay_set_tree_gc(self._h, tree_gc_mode))
+
+    def tree_gc_stats(self):
+        """dict(mode, collections, nodes_before_sum, nodes_kept_sum, peak_nodes, peak_kept): the tree collection that is set and, since it was
+        armed, the collections run, the node counts before and after them in sum, the largest node count a slot had at the start of a
+        round and the largest it had after a collection -- peak_kept + num_simulations is the node_cap these games need under "demand"
+        (zeros without tree_gc)"""
+        mode, st = C.c_int(), _lib.TreeGcStats()
+        _lib.check(_lib.load().oz_selfplay_get_tree_gc(self._h, C.byref(mode), C.byref(st)))
+        return dict(mode={v: k for k, v in _lib.TREE_GC.items()}[mode.value], **_lib.tree_gc_stats_dict(st))
+
+    def tree_gc_profile(self, enable=True):
+        """HIP-event timing of the collection launches on / off (tree_gc_profile_read)"""
+        _lib.check(_lib.load().oz_selfplay_tree_gc_profile(self._h, 1 if enable else 0))
+
+    def tree_gc_profile_read(self, reset=False):
+        """(milliseconds in total, launches) of the collection launches timed so far; waits for the stream"""
+        ms, cnt = C.c_double(), C.c_int64()
+        _lib.check(_lib.load().oz_selfplay_tree_gc_profile_read(self._h, C.byref(ms), C.byref(cnt), 1 if reset else 0))
+        return ms.value, cnt.value
 
     def proof_stats(self):
         """dict(edges_proven, edge_stops, node_stops, roots_proven) over the engine's games so far: edges given a proof, descents ended on a
@@ -722,8 +754,10 @@ def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations
                    expand=False, alias_final=False, record_visits=False, target_temperature=1.0, leaves_per_step=1, root_noise=None,
                    sample_moves=None, endgame_targets=0, solve_leaves=0, playout_cap=None, forced_playouts=None, value_target="outcome", gumbel=None,
                    surprise_weight=None, resign=None, value_signs="reference", proofs=False, proof_play=False, proof_targets=False,
-                   selection=None):
+                   selection=None, tree_gc="off", node_cap=0):
     """Play num_games complete games; returns the move records (or the expanded examples).
+    tree_gc="demand" | "every": drop the tree nodes a game has passed (SelfPlayEngine); no record changes, a smaller node_cap (0 = the
+    default, a whole game's nodes) suffices; selfplay_batch.tree_gc_stats holds the last call's SelfPlayEngine.tree_gc_stats() (None when off).
     selection=dict(fpu=, cpuct_growth=, prior_first=): the selection rule of the searches (SelfPlayEngine); not with gumbel or forced_playouts.
     proof_play=True (needs proofs=True): moves, visit rows, root values and the records' proof codes take what the roots' proofs know
     (SelfPlayEngine); selfplay_batch.proof_play_stats holds the last call's SelfPlayEngine.proof_play_stats() (None when off).
@@ -762,6 +796,7 @@ def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations
     targets, exact_empties = endgame_targets).  The float32 targets come back last -- (records, [counts,] targets) -- or, with expand, as
     the examples' float32 z; with expand it needs alias_final=False.  selfplay_batch.value_target_stats holds the last call's statistics
     (None when off)."""
+    _lib.check_tree_gc(tree_gc)
     _lib.check_selection(selection, gumbel=gumbel, forced_playouts=forced_playouts)
     _lib.check_value_signs(value_signs)
     _lib.check_proofs(proofs, value_signs, gumbel=gumbel, forced_playouts=forced_playouts)
@@ -795,8 +830,14 @@ def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations
                          **({"forced_playouts": forced_playouts} if forced_playouts > 0.0 else {}), **({"record_values": True} if vt_on else {}),
                          **({"gumbel": gumbel} if gumbel is not None else {}), **({"record_surprise": True} if surprise_weight is not None else {}),
                          **({"resign": resign} if resign is not None else {}), **({"value_signs": value_signs} if value_signs != "reference" else {}),
-                         **_lib.proofs_kw(proofs), **_lib.proof_play_kw(proof_play), **_lib.selection_kw(selection))
+                         **_lib.proofs_kw(proofs), **_lib.proof_play_kw(proof_play), **_lib.selection_kw(selection), **_lib.tree_gc_kw(tree_gc),
+                         **({"node_cap": int(node_cap)} if node_cap else {}))
     selfplay_batch.surprise_stats = None
+    selfplay_batch.tree_gc_stats = None
+
+    def collected(ret):
+        selfplay_batch.tree_gc_stats = eng.tree_gc_stats() if tree_gc != "off" else None
+        return ret
 
     def weighted(ret):
         if surprise_weight is None:
@@ -815,7 +856,7 @@ def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations
         selfplay_batch.proof_stats = eng.proof_stats() if proofs else None
         selfplay_batch.proof_play_stats = eng.proof_play_stats() if proof_play else None
         selfplay_batch.proof_target_stats = getattr(eng, "proof_target_stats", None)
-        return weighted(got)
+        return collected(weighted(got))
     if vt_on:
         got = eng.play_to_end(with_visits=record_visits, endgame_targets=endgame_targets, value_target=value_target, **pt_kw)
         rec, counts, targets = got if record_visits else (got[0], None, got[1])
@@ -829,8 +870,8 @@ def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations
         selfplay_batch.proof_play_stats = eng.proof_play_stats() if proof_play else None
         selfplay_batch.proof_target_stats = getattr(eng, "proof_target_stats", None)
         if expand:
-            return expand_examples(rec, board_size, alias_final, visits=counts, target_temperature=target_temperature, values=targets)
-        return weighted((rec, counts, targets) if record_visits else (rec, targets))
+            return collected(expand_examples(rec, board_size, alias_final, visits=counts, target_temperature=target_temperature, values=targets))
+        return collected(weighted((rec, counts, targets) if record_visits else (rec, targets)))
     selfplay_batch.endgame_stats = selfplay_batch.rows_solved = selfplay_batch.playout_stats = selfplay_batch.forced_playout_stats = None
     if record_visits:
         rec, counts = eng.play_to_end(with_visits=True, endgame_targets=endgame_targets, **pt_kw)
@@ -842,7 +883,7 @@ def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations
         selfplay_batch.proof_play_stats = eng.proof_play_stats() if proof_play else None
         selfplay_batch.proof_target_stats = getattr(eng, "proof_target_stats", None)
         selfplay_batch.endgame_stats = getattr(eng, "endgame_stats", None)
-        return expand_examples(rec, board_size, alias_final, visits=counts, target_temperature=target_temperature) if expand else weighted((rec, counts))
+        return collected(expand_examples(rec, board_size, alias_final, visits=counts, target_temperature=target_temperature) if expand else weighted((rec, counts)))
     rec = eng.play_to_end(endgame_targets=endgame_targets, **pt_kw)
     selfplay_batch.forced_playout_stats = eng.forced_playout_stats() if forced_playouts > 0.0 else None
     selfplay_batch.playout_stats = eng.playout_stats() if playout_cap is not None else None
@@ -852,4 +893,4 @@ def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations
     selfplay_batch.proof_play_stats = eng.proof_play_stats() if proof_play else None
     selfplay_batch.proof_target_stats = getattr(eng, "proof_target_stats", None)
     selfplay_batch.endgame_stats = getattr(eng, "endgame_stats", None)
-    return expand_examples(rec, board_size, alias_final) if expand else rec
+    return collected(expand_examples(rec, board_size, alias_final) if expand else rec)
