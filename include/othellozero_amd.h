@@ -250,6 +250,13 @@ int oz_sym_boards(const int32_t* t, int n, const uint64_t* boards, int64_t count
 /* diagnostics switch, per network (default 0), precision bf16x3: the tile of conv3 / conv4 -- 0 = the launcher picks (256 x 256 where the network's
  * capacity fills the chip on it, else 128 x 256), 128 / 256 = that tile.  Bit-identical results: the screen of the two tiles. */
 #define OZ_NET_OPT_B3_TILE 10
+/* diagnostics switch, per network (default 0), precision bf16x3: the mixed plan of conv3 / conv4 -- the layer's leading rows on 256 x 256 tiles, the rows
+ * behind them on 128 x 256 tiles, two launches.  0 = the launcher picks (from the network's capacity: the big tile for whole rounds of the 256 CUs, the small
+ * one for what is left, where that is at least one big round plus at most one small round and prices below either tile alone -- an 8x8 network of 4096
+ * boards: conv3's first 131072 rows), negative = never mix, a positive multiple of 256 = that many leading rows of conv3 and conv4 on the big tile whatever
+ * the pricing and the k split say (ignored where it does not lie inside the layer's capacity rows) -- lets a small network put the boundary anywhere.
+ * OZ_NET_OPT_B3_TILE 128 / 256 overrides it: that tile for the whole launch.  Bit-identical results.  Takes effect at the next forward. */
+#define OZ_NET_OPT_B3_MIX_ROWS 11
 int oz_net_set_option(oz_net* net, int option, int value);
 int oz_net_self_check(oz_net* net, double* max_dpi, double* max_dv, int* positions);
 /* precision f16x2: the exponents chosen at the last commit.  which = 0 .. 4: per-channel activation exponents of the conv1, conv2, conv3,
@@ -258,6 +265,8 @@ int oz_net_get_scaling(oz_net* net, int which, int32_t* out, int64_t nelem);
 /* launch facts of the last forward: OZ_NET_INFO_CONV3_TILE_ROWS = the row-tile height conv3 ran on.  Precision f16x2: 256 / 192 / 128, chosen per call
  * from the capacity the caller launches with (256 at bench.py's batch cap of 3640 leaves; 128 when the call fits one grid round on that tile, e.g.
  * an arena's ~430-leaf batches), 128 x 128 tiles on the latency path (max_batch <= 32).
+ * Precision bf16x3: 256 where the whole layer ran on the 256 x 256 tile, else 128 -- a layer on the mixed plan (OZ_NET_KERNEL_B3_MIXED) reports the SMALLEST
+ * row tile of the plan that ran, 128; how many of its rows went to the 256-row tile is OZ_NET_INFO_LAYER_BIG_ROWS.
  * Precision f32: what oz_gemm_f32_launch really launched -- 256 (GmBig: a 3x3 convolution whose 256 x 256 tiles fill the chip, e.g. every call
  * of a max_batch = 4096 network), 128 (GmStd: smaller networks, or OZ_NET_OPT_F32_STD_TILE), 64 (the weight-stream kernel of layers with at
  * most 64 rows: one-position networks). */
@@ -272,10 +281,13 @@ int oz_net_get_scaling(oz_net* net, int which, int32_t* out, int64_t nelem);
 /* the launch plan of the last forward, per layer l = 1 .. 5 (conv2, conv3, conv4, fc1, fc2): the row-tile height of the kernel that ran the layer
  * (64 / 128 / 192 / 256; 0 = no row tiles: the table gather), the number of k-slices its k loop was cut into (1 = unsplit; slices of layers
  * 1 .. 4 are added by the precision's fixed-order reduce kernel, those of fc2 by the heads kernel), and which kernel / main loop it was
- * (OZ_NET_KERNEL_*).  What a test matrix needs to show that it ran the configuration it names. */
+ * (OZ_NET_KERNEL_*).  What a test matrix needs to show that it ran the configuration it names.  OZ_NET_INFO_LAYER_BIG_ROWS: precision bf16x3, how
+ * many leading rows of the layer's capacity belong to 256-row tiles -- 0 for OZ_NET_KERNEL_B3, every row for OZ_NET_KERNEL_B3_BIG, the boundary of the two
+ * launches for OZ_NET_KERNEL_B3_MIXED (whose OZ_NET_INFO_LAYER_TILE_ROWS is 128, the smaller tile); 0 in the other precisions. */
 #define OZ_NET_INFO_LAYER_TILE_ROWS(l) (16 + (l))
 #define OZ_NET_INFO_LAYER_KSLICES(l) (32 + (l))
 #define OZ_NET_INFO_LAYER_KERNEL(l) (48 + (l))
+#define OZ_NET_INFO_LAYER_BIG_ROWS(l) (64 + (l))
 enum {
     OZ_NET_KERNEL_NONE = 0,
     OZ_NET_KERNEL_F32_SKINNY = 1,        /* k_gemm_f32_skinny: the weight stream of layers with at most 64 rows */
@@ -289,9 +301,15 @@ enum {
     OZ_NET_KERNEL_H2_MIDPP = 14, OZ_NET_KERNEL_H2_LOWPP1 = 15, OZ_NET_KERNEL_H2_LOWPP = 16, OZ_NET_KERNEL_H2_BIG = 17, OZ_NET_KERNEL_H2_MID = 18,
     OZ_NET_KERNEL_H2_THIN2 = 19, OZ_NET_KERNEL_H2_THIN = 20, OZ_NET_KERNEL_H2_THIN4W = 21,     /* k_gemm_h2 on the tile configuration of that name */
     OZ_NET_KERNEL_B3 = 30,               /* k_gemm_b3 (128 x 256) */
-    OZ_NET_KERNEL_B3_BIG = 31            /* k_gemm_b3_big (256 x 256) */
+    OZ_NET_KERNEL_B3_BIG = 31,           /* k_gemm_b3_big (256 x 256) */
+    OZ_NET_KERNEL_B3_MIXED = 32          /* k_gemm_b3_big over the layer's leading rows, then k_gemm_b3 over the rest (OZ_NET_OPT_B3_MIX_ROWS) */
 };
 int oz_net_get_info(oz_net* net, int what, int* value);
+/* host only, no GPU needed: the plan a precision-bf16x3 network of board size n (6 / 8), `channels` filters and capacity max_batch makes for its layer
+ * 1 .. 5 (conv2 .. fc2) when the layer's k loop has `kslices` slices, under OZ_NET_OPT_B3_TILE = tile_opt and OZ_NET_OPT_B3_MIX_ROWS = mix_rows_opt: *kernel =
+ * OZ_NET_KERNEL_B3 / _B3_BIG / _B3_MIXED, *big_rows as OZ_NET_INFO_LAYER_BIG_ROWS reports them, *small_tiles = the 128-row tiles of the capacity's remaining
+ * rows.  The function the forward itself asks. */
+int oz_net_b3_plan(int n, int channels, int max_batch, int layer, int kslices, int tile_opt, int mix_rows_opt, int* kernel, int64_t* big_rows, int64_t* small_tiles);
 /* Diagnostics: a read-only view of the last forward (the inference side's counterpart of oz_trainer_get_activation).  layer 0 .. 3 = the outputs
  * of conv1 .. conv4, 4 / 5 = fc1 / fc2 (the trainer's numbering); a row is a (board, pixel) index of the last forward -- oz_net_predict's boards in
  * call order -- and out[rows][channels] receives rows first_row .. first_row + rows - 1 as float64: EXACTLY the numbers the consuming kernel

@@ -36,6 +36,16 @@ class _NetHandle:
 PRECISION_MODES = {"f32": 0, "f16x2": 1, "bf16x3": 2}      # oz_net_set_precision
 
 
+def b3_plan(n, channels, max_batch, layer, kslices=1, tile=0, mix_rows=0):
+    """host only, no GPU: the plan a precision-bf16x3 network of that shape and capacity makes for `layer` (1 .. 5 = conv2 .. fc2) with `kslices`
+    k-slices under NET_OPT_B3_TILE = tile and NET_OPT_B3_MIX_ROWS = mix_rows -- dict(kernel="b3" / "b3_big" / "b3_mixed", big_rows=the layer's
+    leading rows on 256-row tiles, small_tiles=the 128-row tiles of the capacity's other rows) (oz_net_b3_plan: the function the forward asks)"""
+    kernel, big_rows, small_tiles = C.c_int(), C.c_int64(), C.c_int64()
+    _lib.check(_lib.load().oz_net_b3_plan(int(n), int(channels), int(max_batch), int(layer), int(kslices), int(tile), int(mix_rows),
+                                          C.byref(kernel), C.byref(big_rows), C.byref(small_tiles)))
+    return dict(kernel=_lib.NET_KERNEL_NAMES[kernel.value], big_rows=big_rows.value, small_tiles=small_tiles.value)
+
+
 class NNetWrapper(_NetHandle):
     _models_built = 0          # Keras numbers layer names per process (conv2d, ..., conv2d_4, ...); checkpoints keep that
 
@@ -420,7 +430,8 @@ class NNetWrapper(_NetHandle):
 
     def conv3_tile_rows(self):
         """row-tile height the LAST forward ran conv3 on (f16x2: 256 at bench.py's batch cap, 192 for full 4096-leaf launches, 128 on the latency path;
-        f32: 256 = the 256 x 256 tile of large batches, 128 = the standard tile, 64 = the weight-stream kernel of one-position networks)"""
+        f32: 256 = the 256 x 256 tile of large batches, 128 = the standard tile, 64 = the weight-stream kernel of one-position networks; bf16x3: 256 where every row ran on the 256 x 256 tile, else 128 --
+        the smallest row tile of the plan, so 128 too for layer_plan()'s "b3_mixed")"""
         v = C.c_int()
         _lib.check(_lib.load().oz_net_get_info(self._h, _lib.NET_INFO_CONV3_TILE_ROWS, C.byref(v)))
         return v.value
@@ -433,15 +444,16 @@ class NNetWrapper(_NetHandle):
 
     def layer_plan(self):
         """the launch plan of the LAST forward: {layer 1 .. 5 (conv2, conv3, conv4, fc1, fc2): dict(tile_rows=row-tile height (0: the table gather),
-        kslices=k-slices of the layer's k loop, kernel=_lib.NET_KERNEL_NAMES name of the kernel / main loop)} -- what a test reads to show that it ran
-        the configuration it names (oz_net_get_info, OZ_NET_INFO_LAYER_*)"""
+        kslices=k-slices of the layer's k loop, kernel=_lib.NET_KERNEL_NAMES name of the kernel / main loop, big_rows=precision bf16x3: the layer's
+        leading rows on 256-row tiles -- for kernel "b3_mixed" the boundary between its two launches, with tile_rows = 128)} -- what a test reads to
+        show that it ran the configuration it names (oz_net_get_info, OZ_NET_INFO_LAYER_*)"""
         lib, v, plan = _lib.load(), C.c_int(), {}
         for layer in range(1, 6):
             row = []
-            for base in (_lib.NET_INFO_LAYER_TILE_ROWS, _lib.NET_INFO_LAYER_KSLICES, _lib.NET_INFO_LAYER_KERNEL):
+            for base in (_lib.NET_INFO_LAYER_TILE_ROWS, _lib.NET_INFO_LAYER_KSLICES, _lib.NET_INFO_LAYER_KERNEL, _lib.NET_INFO_LAYER_BIG_ROWS):
                 _lib.check(lib.oz_net_get_info(self._h, base + layer, C.byref(v)))
                 row.append(v.value)
-            plan[layer] = dict(tile_rows=row[0], kslices=row[1], kernel=_lib.NET_KERNEL_NAMES[row[2]])
+            plan[layer] = dict(tile_rows=row[0], kslices=row[1], kernel=_lib.NET_KERNEL_NAMES[row[2]], big_rows=row[3])
         return plan
 
     def activation(self, layer, first_row=0, rows=None):

@@ -19,11 +19,13 @@ NET_OPT_SIMPLE_LOOP, NET_OPT_ACT_TARGET_LOG2, NET_OPT_LOW_GUARD_LOG2, NET_OPT_SE
 NET_OPT_CONV3_TILE = 8
 NET_OPT_LOW_LOOP_PHASES = 9
 NET_OPT_B3_TILE = 10
+NET_OPT_B3_MIX_ROWS = 11
 NET_INFO_CONV3_TILE_ROWS, NET_INFO_SELF_CHECK_GUARD, NET_INFO_ARITHMETIC = 1, 2, 3                                                          # oz_net_get_info
+NET_INFO_LAYER_BIG_ROWS = 64       # + layer: bf16x3, the leading rows on 256-row tiles
 NET_INFO_LAYER_TILE_ROWS, NET_INFO_LAYER_KSLICES, NET_INFO_LAYER_KERNEL = 16, 32, 48      # + layer 1 .. 5 (conv2 .. fc2): the launch plan of the last forward
 NET_KERNEL_NAMES = {0: "none", 1: "f32_skinny", 2: "f32_std", 3: "f32_std_pixmajor", 4: "f32_big", 5: "lut", 6: "lut_xcd", 7: "lut_xcd_inline",
                     10: "h2_small2", 11: "h2_small", 12: "h2_bigpp", 13: "h2_bigpp_lut", 14: "h2_midpp", 15: "h2_lowpp1", 16: "h2_lowpp", 17: "h2_big",
-                    18: "h2_mid", 19: "h2_thin2", 20: "h2_thin", 21: "h2_thin4w", 30: "b3", 31: "b3_big"}      # OZ_NET_KERNEL_* of the header
+                    18: "h2_mid", 19: "h2_thin2", 20: "h2_thin", 21: "h2_thin4w", 30: "b3", 31: "b3_big", 32: "b3_mixed"}      # OZ_NET_KERNEL_* of the header
 LEAF_IDLE, LEAF_TERMINAL, LEAF_EVAL = 0, 1, 2
 VT_INT, VT_F32, VT_F64 = 0, 1, 2
 MAX_LEAVES_PER_STEP = 16                                                             # OZ_MCTS_MAX_LEAVES_PER_STEP
@@ -191,6 +193,7 @@ SIGNATURES = {
     "oz_eval_symmetries": [C.c_uint64, _u64p, _u64p, C.c_int64, _i32p], "oz_sym_boards": [_i32p, C.c_int, _u64p, C.c_int64, _u64p],
     "oz_net_set_option": [_vp, C.c_int, C.c_int], "oz_net_get_info": [_vp, C.c_int, C.POINTER(C.c_int)],
     "oz_net_get_scaling": [_vp, C.c_int, _i32p, C.c_int64],
+    "oz_net_b3_plan": [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), _i64p, _i64p],
     "oz_net_get_activation": [_vp, C.c_int, C.c_int64, C.c_int64, _f64p],
     "oz_net_self_check": [_vp, _f64p, _f64p, C.POINTER(C.c_int)],
     "oz_mcts_create": [C.POINTER(_vp), C.c_int, C.c_int, C.c_int, C.c_double, C.c_int],

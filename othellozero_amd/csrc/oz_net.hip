@@ -531,25 +531,36 @@ static int launch_h2(const OzLayerShape& L, const void* in, const uint4* W, cons
     return OZ_OK;
 }
 
-// big: the 256 x 256 tile (k_gemm_b3_big; ksplit must be 1), else the 128 x 256 tile
+// big_rows: the leading rows of the layer that run on the 256 x 256 tile (k_gemm_b3_big; 'valid' layers only), the rows behind them on the
+// 128 x 256 tile: 0 = one launch of 128-row tiles, >= max_count's rows = one launch of 256-row tiles, in between (a multiple of 256) = the mixed
+// plan, two launches back to back -- the second one's row tiles start at big_rows (B3Geom::mt0) and its grid covers what the call has beyond them.
+// Both tiles add every output element's products in the same order: which launch a row falls into changes no bit of it.
 template <int TAG>
 static int launch_b3(const OzLayerShape& L, const uint4* in, const uint4* W, const float* scale, const float* shift, void* out, int packed, OzDeferredReduce* defer,
-                     const int* d_count, int max_count, bool big, int ksplit, float* slabs, long long slab, const uint4* zero_line, hipStream_t s, int relu = 1) {
+                     const int* d_count, int max_count, long long big_rows, int ksplit, float* slabs, long long slab, const uint4* zero_line, hipStream_t s, int relu = 1) {
     OZ_REQUIRE(L.N % B3_BN == 0 && L.Cin % B3_BK == 0, "gemm_b3: N %% 256 and Cin %% 32 must be 0 (N=%d Cin=%d)", L.N, L.Cin);
     if (defer) *defer = OzDeferredReduce();
     B3Geom g;
     oz_geom_set_shape(g, L);
     g.out_b3 = packed; g.relu = relu; g.ksplit = ksplit; g.slab = slab;
-    const int P = L.pixels(), N = L.N, BM = big ? B3B_BM : B3_BM;
-    const int num_mt = (int)(((long long)max_count * P + BM - 1) / BM);
-    const dim3 grid(gemm_grid(num_mt, (N / B3_BN) * ksplit));
+    const int P = L.pixels(), N = L.N;
+    const long long rows = (long long)max_count * P;
+    OZ_REQUIRE(big_rows == 0 || L.pad == 0, "gemm_b3: the 256-row tile needs a 'valid' layer (pad=%d)", L.pad);
+    OZ_REQUIRE(big_rows >= rows || big_rows % B3B_BM == 0, "gemm_b3: a mixed plan's 256-row part must be whole tiles (%lld rows)", big_rows);
     void* dst = ksplit > 1 ? (void*)slabs : out;
-    if (big) {
+    if (big_rows > 0) {
+        const int num_mt = (int)(((big_rows < rows ? big_rows : rows) + B3B_BM - 1) / B3B_BM);
+        g.mt0 = 0;
         if (int rc = set_max_lds_once<k_gemm_b3_big<TAG>>(B3B_LDS)) return rc;
-        hipLaunchKernelGGL((k_gemm_b3_big<TAG>), grid, dim3(B3_NT), B3B_LDS, s, in, W, scale, shift, dst, d_count, g, num_mt, zero_line);
-    } else {
+        hipLaunchKernelGGL((k_gemm_b3_big<TAG>), dim3(gemm_grid(num_mt, (N / B3_BN) * ksplit)), dim3(B3_NT), B3B_LDS, s, in, W, scale, shift, dst, d_count, g, num_mt,
+                           zero_line);
+    }
+    if (big_rows == 0 || big_rows < rows) {
+        g.mt0 =(int)(big_rows / B3_BM);
+        const int num_mt = (int)((rows + B3_BM - 1) / B3_BM) - g.mt0;
         if (int rc = set_max_lds_once<k_gemm_b3<TAG>>(B3_LDS)) return rc;
-        hipLaunchKernelGGL((k_gemm_b3<TAG>), grid, dim3(B3_NT), B3_LDS, s, in, W, scale, shift, dst, d_count, g, num_mt, zero_line);
+        hipLaunchKernelGGL((k_gemm_b3<TAG>), dim3(gemm_grid(num_mt, (N / B3_BN) * ksplit)), dim3(B3_NT), B3_LDS, s, in, W, scale, shift, dst, d_count, g, num_mt,
+                           zero_line);
     }
     if (ksplit > 1 && packed) {                               // the consumer reads the b3 layout: fixed-order reduce + BN + ReLU + split
         const long long threads = (long long)max_count * P * (N / 8);
@@ -561,13 +572,48 @@ static int launch_b3(const OzLayerShape& L, const uint4* in, const uint4* W, con
     return OZ_OK;
 }
 
-// the price of the two b3 tiles for `rows` x N outputs (tile_cost), the 256-row tile at 0.96 of its rows (measured at equal fill: 3.59 us per k-tile
-// against 2 x 1.87): true when a grid of 256 x 256 tiles fills the chip and pays no more than one of 128 x 256 tiles.  Callers add their own
-// conditions ('valid' padding, no k split, the screen option).
-static bool b3_big_tile_pays(long long rows, int N) {
-    auto paid = [&](int bm) { return (double)tile_cost(rows, N, bm); };
-    const long long big_blocks = ((rows + B3B_BM - 1) / B3B_BM) * (N / B3B_BN);
-    return big_blocks >= 192 && 0.96 * paid(B3B_BM) <= paid(B3_BM);
+// what a round of 256 x 256 tiles costs against two rounds of 128 x 256 tiles -- the ONE relative price of the big tile.  Measured on conv3 itself
+// (8x8, 512 filters, max_batch 4096) at 3640 leaves, where both grids are whole rounds -- 4.0 big, 8.0 small: 1915 .. 1941 us against 2065 .. 2107 us
+// per launch in three alternating passes of net.profile_kernels on one box, ratios 0.921 / 0.936 / 0.927.  (Round 6 had 0.96 from k-tile times at
+// equal fill, 3.59 us against 2 x 1.87; conv4 at 3916 leaves gives 974 / 1048 = 0.93.)
+#define B3_BIG_ROUND_COST 0.93
+// the whole-round prefix of a mixed plan: the rows of as many 256-row tiles as fill whole rounds of the 256 CUs (0: not even one round)
+static long long b3_whole_round_rows(long long rows, int N) {
+    const int nnt = N / B3B_BN;
+    if (256 % nnt) return 0;
+    const long long big_blocks = ((rows + B3B_BM - 1) / B3B_BM) * nnt;
+    return big_blocks / 256 * 256 / nnt * B3B_BM;
+}
+// how many LEADING rows of `rows` x N outputs run on the 256-row tile, the rest on the 128-row tile: the cheapest of three plans priced with tile_cost
+// and B3_BIG_ROUND_COST --
+//   0                  every row on 128 x 256 tiles
+//   rows               every row on 256 x 256 tiles, if their grid fills the chip (>= 192 blocks) and pays no more than the small tiles'
+//   the whole rounds   (may_mix) the big tile for as many tiles as fill whole rounds of the chip, the small tile for what is left, if that is
+//                      at least one whole big round and at most one small round: no round of either tile is paid for and left partly idle
+//                      (4096 boards of 8x8 conv3: 4 x 256 big blocks + 256 small ones against 9.0 small rounds or 4.5 big ones paid as 5)
+// Callers add their own conditions ('valid' padding, no k split, the screen options).
+static long long b3_big_rows(long long rows, int N, bool may_mix) {
+    const int nnt = N / B3B_BN;
+    const long long big_blocks = ((rows + B3B_BM - 1) / B3B_BM) * nnt;
+    double best = (double)tile_cost(rows, N, B3_BM);
+    long long pick = 0;
+    if (big_blocks >= 192 && B3_BIG_ROUND_COST * tile_cost(rows, N, B3B_BM) <= best) { best = B3_BIG_ROUND_COST * tile_cost(rows, N, B3B_BM); pick = rows; }
+    const long long head = may_mix ? b3_whole_round_rows(rows, N) : 0;
+    if (head > 0 && head < rows && ((rows - head + B3_BM - 1) / B3_BM) * nnt <= 256 &&
+        B3_BIG_ROUND_COST * tile_cost(head, N, B3B_BM) + tile_cost(rows - head, N, B3_BM) < best) pick = head;
+    return pick;
+}
+// the network object's plan for one b3 layer of capacity rows_cap x N (OnnNet::launch_gemm_b3; oz_net_b3_plan shows it without a device):
+// tile_opt = OZ_NET_OPT_B3_TILE (128 / 256: that tile for the whole launch), mix_opt = OZ_NET_OPT_B3_MIX_ROWS (< 0: never mix; > 0: that many leading
+// rows of a 'valid' 3x3 layer on the big tile whatever it costs, whatever the k split -- a test switch: only what the kernels need is asked of it)
+static long long b3_plan_rows(const OzLayerShape& L, long long rows_cap, int ksplit, int tile_opt, int mix_opt) {
+    if (tile_opt == 128 || L.pad != 0) return 0;
+    if (tile_opt == 256) return ksplit == 1 ? rows_cap : 0;
+    if (mix_opt > 0 && L.taps == 9) return mix_opt % B3B_BM == 0 && mix_opt < rows_cap ? mix_opt : ksplit == 1 ? b3_big_rows(rows_cap, L.N, false) : 0;
+    return ksplit == 1 ? b3_big_rows(rows_cap, L.N, mix_opt == 0) : 0;
+}
+static int b3_plan_kernel(long long big_rows, long long rows_cap) {
+    return big_rows <= 0 ? OZ_NET_KERNEL_B3 : big_rows >= rows_cap ? OZ_NET_KERNEL_B3_BIG : OZ_NET_KERNEL_B3_MIXED;
 }
 
 // k_gemm_h2 for callers outside the network object (the trainer's f16x2 mode): out[M][N] fp32 rows = (A . Wh^T) * scale + shift, A and Wh
@@ -603,7 +649,7 @@ int oz_gemm_h2_launch(const void* in_h2, const void* Wh, const float* scale, con
 // k_gemm_b3 for callers outside the network object (the trainer's bf16x3 mode): out[M][N] fp32 rows = act((A . Wb^T) * scale + shift), A and
 // Wb in the b3 layout, relu 0 or 1.  Tile and k-split are chosen from `max_count` (the caller's capacity -- a constant of the trainer, so a row's
 // result does not depend on the size of one call): the 256 x 256 tile for unsplit 'valid' layers whose grid fills the chip on it (the network
-// object's pricing, b3_big_tile_pays), else the 128 x 256 tile with the k loop split until every CU has a block (raw slabs in `partial`, then the
+// object's pricing without its mixed plan, b3_big_rows), else the 128 x 256 tile with the k loop split until every CU has a block (raw slabs in `partial`, then the
 // fixed-order fp32 reduce with scale / shift / act).  `tag` 0 / 1 only names the kernel in a profile (forward / data gradient).  The inference
 // forward launches through the same launch_b3 with its own tiles and splits (OnnNet::launch_gemm_b3).
 int oz_gemm_b3_launch(const void* in_b3, const void* Wb, const float* scale, const float* shift, float* out, const int* d_count, int max_count,
@@ -611,11 +657,11 @@ int oz_gemm_b3_launch(const void* in_b3, const void* Wb, const float* scale, con
                       const void* zero_line, int tag, int* plan_out) {
     const OzLayerShape L = {Hin, Hout, pad, Cin, taps, N};
     const long long Mmax = (long long)max_count * L.pixels();
-    const bool big = pad == 0 && b3_big_tile_pays(Mmax, N);
+    const bool big = pad == 0 && b3_big_rows(Mmax, N, false) > 0;     // (one tile per launch here: the trainer does not mix)
     // (one 144 KB block per CU)
     const int ksplit = !big && partial ? trainer_ksplit(((Mmax + B3_BM - 1) / B3_BM) * (N / B3_BN), L.K() / B3_BK, Mmax * N, partial_floats) : 1;
     auto go = [&](auto t) {
-        return launch_b3<decltype(t)::value>(L, (const uint4*)in_b3, (const uint4*)Wb, scale, shift, out, 0, nullptr, d_count, max_count, big, ksplit, partial,
+        return launch_b3<decltype(t)::value>(L, (const uint4*)in_b3, (const uint4*)Wb, scale, shift, out, 0, nullptr, d_count, max_count, big ? Mmax : 0, ksplit, partial,
                                              Mmax * N, (const uint4*)zero_line, s, relu);
     };
     // plan_out (optional): [0] = the k-slices of this launch, [1] = the kernel (OZ_NET_KERNEL_B3 / OZ_NET_KERNEL_B3_BIG)
@@ -973,11 +1019,12 @@ struct OnnNet : oz_net {
     bool f32_std_tile = false;       // oz_net_set_option(OZ_NET_OPT_F32_STD_TILE): precision f32 never takes the 256 x 256 tile (bit-identity screen)
     bool simple_loop = false;        // oz_net_set_option(OZ_NET_OPT_SIMPLE_LOOP): one-barrier-per-k-tile loop for the 3x3 layers (race screen)
     int b3_tile = 0;                 // oz_net_set_option(OZ_NET_OPT_B3_TILE): 0 = the launcher picks (256 x 256 where its grid fills the chip), 128 / 256 = that tile (bit-identity screen)
+    int b3_mix_rows = 0;             // oz_net_set_option(OZ_NET_OPT_B3_MIX_ROWS): 0 = the launcher picks, < 0 = never the mixed plan, > 0 = that many leading rows of conv3 / conv4 on the 256-row tile
     int low_loop_phases = 1;         // oz_net_set_option(OZ_NET_OPT_LOW_LOOP_PHASES): main loop of the 128 x 256 tile -- 1 (default) = one phase per k-tile, three LDS stages; 2 = round 5's 2-phase loop
     float* d_t2rows = nullptr;       // commit staging: one tap's T2 rows [OZ_LUT_PATTERNS][C] before the slice-major re-layout
     int last_conv3_rows = 0;         // row-tile height the last forward ran conv3 on (oz_net_get_info)
     // the launch plan of the last forward (oz_net_get_info, OZ_NET_INFO_LAYER_*): index = layer 1 .. 5 (conv2 .. fc2), written by the launch wrappers
-    struct LayerPlan { int tile_rows = 0, ksplit = 0, kernel = OZ_NET_KERNEL_NONE; };
+    struct LayerPlan { int tile_rows = 0, ksplit = 0, kernel = OZ_NET_KERNEL_NONE; long long big_rows = 0; };      // big_rows: bf16x3, the layer's leading rows on 256-row tiles
     LayerPlan plan[6];
     // where the last forward left the output of conv1 .. fc2 (oz_net_get_activation; index = its `layer`), written at the end of the three forwards.
     // fmt: -1 not materialised, 0 fp32 rows, 1 the h2 layout (aexp: the tensor's exponents on the device), 2 the b3 layout, 3 k-slices left to the heads kernel (last_defer)
@@ -1659,14 +1706,21 @@ struct OnnNet : oz_net {
         // the 256 x 256 tile (two thirds of the operand bytes per MFMA: the small tile is bound by its LDS-DMA stream out of the L2s) for unsplit 'valid'
         // layers whose grid fills the chip on it -- keyed on the CAPACITY of the network (max_batch), like every tile / split choice, so that a position's
         // bits do not depend on the call (they would not anyway: both tiles add the same products in the same order; OZ_NET_OPT_B3_TILE screens that)
-        // Which tile: the one whose grid pays fewer tile-rows at the network's capacity (b3_big_tile_pays).  4096 positions of 8x8: conv3 = 9 rounds of 128
-        // rows against 5 (4.5 paid as 5) of 256 -> the small tile; conv4 = 4 rounds of 128 against 2.0 of 256 -> the big one (974 against 1048 us at 3916
-        // leaves).  The tile does not dissolve the kernel's real bound, which turned out to be the clock under load, not the L2 stream (docs/HISTORY.md, round 6).
+        // Which tile: the plan whose grids pay the fewest tile-rows at the network's capacity (b3_big_rows).  4096 positions of 8x8: conv4 = 4 rounds of 128
+        // rows against 2.0 of 256 -> the big tile (974 against 1048 us at 3916 leaves); conv3 = 9 rounds of 128 rows against 5 (4.5 paid as 5) of 256 -> neither:
+        // the MIXED plan, the first four whole rounds (1024 blocks, 131072 rows, 3640.9 boards) on the big tile and the remaining <= 16384 rows on one round of
+        // small tiles, two launches inside the layer's timed slot.  The boundary is a constant of the network (a multiple of 256 rows of its capacity); the
+        // second launch's grid is sized from the call and its blocks return at once where the batch ends before them.  Reported as OZ_NET_KERNEL_B3_MIXED with
+        // the big part's rows; the row tile reported for a mixed layer is the smaller one, 128.
+        // Measured on one box (profiles/b3_mixed_conv3_ab.txt): conv3 per launch 2270 - 2307 -> 2131 - 2170 us at 3916 leaves, 2330 - 2343 -> 2140 - 2185 us at 4096;
+        // bench.py's ms_per_step 416.6 -> 401.0 in three alternating runs each.  A call far below the capacity pays a 256-row round where a 128-row one would do.
+        // The tile does not dissolve the kernel's real bound, which turned out to be the clock under load, not the L2 stream (docs/HISTORY.md, round 6).
         const long long rows_cap = (long long)max_batch * L.pixels();
-        const bool big = b3_tile != 128 && L.pad == 0 && ksplit == 1 && (b3_tile == 256 || b3_big_tile_pays(rows_cap, L.N));
-        if (layer == 2) last_conv3_rows = big ? B3B_BM : B3_BM;
-        plan[layer] = LayerPlan{big ? B3B_BM : B3_BM, ksplit, big ? OZ_NET_KERNEL_B3_BIG : OZ_NET_KERNEL_B3};
-        return launch_b3<TAG>(L, in, d_wb[layer - 1], d_scale[layer], d_shift[layer], out, out_b3, layer == 5 ? &fc2_defer : nullptr, d_count, max_count, big,
+        const long long big_rows = b3_plan_rows(L, rows_cap, ksplit, b3_tile, b3_mix_rows);
+        const int kernel = b3_plan_kernel(big_rows, rows_cap), tile_rows = kernel == OZ_NET_KERNEL_B3_BIG ? B3B_BM : B3_BM;
+        if (layer == 2) last_conv3_rows = tile_rows;
+        plan[layer] = LayerPlan{tile_rows, ksplit, kernel, kernel == OZ_NET_KERNEL_B3 ? 0 : big_rows};
+        return launch_b3<TAG>(L, in, d_wb[layer - 1], d_scale[layer], d_shift[layer], out, out_b3, layer == 5 ? &fc2_defer : nullptr, d_count, max_count, big_rows,
                               ksplit, d_part_b3, rows_cap * L.N, d_zero, s);
     }
 
@@ -2322,12 +2376,17 @@ OZ_API int oz_net_set_option(oz_net* net, int option, int value) {
     OZ_REQUIRE(o, "not an OthelloNN network");
     OZ_REQUIRE(option == OZ_NET_OPT_SIMPLE_LOOP || option == OZ_NET_OPT_ACT_TARGET_LOG2 || option == OZ_NET_OPT_LOW_GUARD_LOG2 ||
                option == OZ_NET_OPT_SELF_CHECK || option == OZ_NET_OPT_W_TARGET_LOG2 || option == OZ_NET_OPT_F32_STD_TILE ||
-               option == OZ_NET_OPT_LATENCY_SPLITS || option == OZ_NET_OPT_CONV3_TILE || option == OZ_NET_OPT_LOW_LOOP_PHASES || option == OZ_NET_OPT_B3_TILE, "unknown network option %d", option);
+               option == OZ_NET_OPT_LATENCY_SPLITS || option == OZ_NET_OPT_CONV3_TILE || option == OZ_NET_OPT_LOW_LOOP_PHASES || option == OZ_NET_OPT_B3_TILE ||
+               option == OZ_NET_OPT_B3_MIX_ROWS, "unknown network option %d", option);
     std::lock_guard<std::mutex> lk(o->mu);
     if (option == OZ_NET_OPT_SIMPLE_LOOP) o->simple_loop = value != 0;
     else if (option == OZ_NET_OPT_B3_TILE) {
         OZ_REQUIRE(value == 0 || value == 128 || value == 256, "OZ_NET_OPT_B3_TILE must be 0, 128 or 256 (got %d)", value);
         o->b3_tile = value;
+    }
+    else if (option == OZ_NET_OPT_B3_MIX_ROWS) {
+        OZ_REQUIRE(value <= 0 || value % B3B_BM == 0, "OZ_NET_OPT_B3_MIX_ROWS must be 0, negative or a positive multiple of 256 (got %d)", value);
+        o->b3_mix_rows = value;
     }
     else if (option == OZ_NET_OPT_LOW_LOOP_PHASES) {
         OZ_REQUIRE(value == 1 || value == 2, "OZ_NET_OPT_LOW_LOOP_PHASES must be 1 or 2 (got %d)", value);
@@ -2389,9 +2448,28 @@ OZ_API int oz_net_get_info(oz_net* net, int what, int* value) {
         if (what == OZ_NET_INFO_LAYER_TILE_ROWS(l)) { *value = p.tile_rows; return OZ_OK; }
         if (what == OZ_NET_INFO_LAYER_KSLICES(l)) { *value = p.ksplit; return OZ_OK; }
         if (what == OZ_NET_INFO_LAYER_KERNEL(l)) { *value = p.kernel; return OZ_OK; }
+        if (what == OZ_NET_INFO_LAYER_BIG_ROWS(l)) { *value = (int)p.big_rows; return OZ_OK; }
     }
     OZ_REQUIRE(what == OZ_NET_INFO_CONV3_TILE_ROWS || what == OZ_NET_INFO_SELF_CHECK_GUARD || what == OZ_NET_INFO_ARITHMETIC, "unknown network info %d", what);
     *value = what == OZ_NET_INFO_CONV3_TILE_ROWS ? o->last_conv3_rows : what == OZ_NET_INFO_ARITHMETIC ? (o->precision == 2 && !o->use_b3() ? 0 : o->precision) : o->sc_guard;
+    return OZ_OK;
+}
+
+// host only: the plan OnnNet::launch_gemm_b3 makes for layer 1 .. 5 of an n x n network of `channels` filters and capacity max_batch in precision
+// bf16x3, under the two screen options -- the same b3_plan_rows, no device touched
+OZ_API int oz_net_b3_plan(int n, int channels, int max_batch, int layer, int kslices, int tile_opt, int mix_rows_opt, int* kernel, int64_t* big_rows,
+                          int64_t* small_tiles) {
+    OZ_REQUIRE((n == 6 || n == 8) && channels > 0 && channels % B3_BN == 0 && max_batch >= 1 && layer >= 1 && layer <= 5 && kslices >= 1,
+               "oz_net_b3_plan: bad shape (n=%d channels=%d max_batch=%d layer=%d kslices=%d)", n, channels, max_batch, layer, kslices);
+    OZ_REQUIRE(tile_opt == 0 || tile_opt == 128 || tile_opt == 256, "OZ_NET_OPT_B3_TILE must be 0, 128 or 256 (got %d)", tile_opt);
+    OZ_REQUIRE(mix_rows_opt <= 0 || mix_rows_opt % B3B_BM == 0, "OZ_NET_OPT_B3_MIX_ROWS must be 0, negative or a positive multiple of 256 (got %d)", mix_rows_opt);
+    const OzLayerShape L = oz_onn_layers(n, channels)[layer - 1];
+    const long long rows_cap = (long long)max_batch * L.pixels();
+    const long long head = b3_plan_rows(L, rows_cap, kslices, tile_opt, mix_rows_opt);
+    const int k = b3_plan_kernel(head, rows_cap);
+    if (kernel) *kernel = k;
+    if (big_rows) *big_rows = k == OZ_NET_KERNEL_B3 ? 0 : head;
+    if (small_tiles) *small_tiles = k == OZ_NET_KERNEL_B3_BIG ? 0 : (rows_cap + B3_BM - 1) / B3_BM - (k == OZ_NET_KERNEL_B3 ? 0 : head / B3_BM);
     return OZ_OK;
 }
 

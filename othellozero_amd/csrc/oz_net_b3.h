@@ -30,6 +30,13 @@
 // quad -- r, r + 4, r + 8, r + 12 -- need four different chunk slots: {a ^ g0, a ^ 1 ^ g1, a ^ 1 ^ g2, a ^ g3} = all four for g = (0, 3, 2, 1).
 // Every output element receives its products in one fixed order (k-tile by k-tile, the six plane products in the order above), so
 // a position's result does not depend on its place in the batch or on the batch size.
+//
+// Two tiles, one layer: k_gemm_b3 (128 x 256) and k_gemm_b3_big (256 x 256, below) add the same products in the same order, so a layer may be cut
+// by rows between them -- the mixed plan of launch_b3 (oz_net.hip): k_gemm_b3_big over the leading rows that fill whole rounds of the 256 CUs, then
+// k_gemm_b3 over the rest with B3Geom::mt0 = the first row tile behind them.  Inside a kernel mt0 only shifts the block's row tile (once, right after
+// the block mapping): staging addresses and masks, the m < M tests and the three epilogues all work on the layer's rows; main loops, LDS regions,
+// wait counts and barriers do not know of it.  Where such a layer reports ONE row-tile height (OZ_NET_INFO_CONV3_TILE_ROWS, the layer plan's
+// tile_rows) it is the smallest of the plan that ran, 128; the plan's kernel id (OZ_NET_KERNEL_B3_MIXED) and its big rows say the rest.
 #pragma once
 
 #define B3_BK 32
@@ -51,6 +58,8 @@ struct B3Geom {
     int relu;
     int ksplit;                                   // > 1: raw fp32 partial sums to slab[ks] (no scale / shift); a fixed-order reduce finishes the layer
     long long slab;                               // floats between two partial slabs
+    int mt0 = 0;                                  // first row tile of this launch, in tiles of the kernel's own height: a layer cut into a 256-row and a
+                                                  // 128-row launch (launch_b3) starts the second one behind the first one's rows
 };
 
 // b3_split, b3_store8 and the layout's definition live in oz_common.h: the trainer converts its operands with the same functions
@@ -133,7 +142,9 @@ __global__ __launch_bounds__(B3_NT, 2) void k_gemm_b3(const uint4* __restrict__ 
     }
     const int P = g.Hout * g.Hout;
     const long long M = (long long)(*d_count) * P;
-    if (mt >= num_mt || (long long)mt * BM >= M) return;
+    if (mt >= num_mt) return;
+    mt += g.mt0;                                             // from here on mt is the row tile of the layer, not of the launch
+    if ((long long)mt * BM >= M) return;
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -407,7 +418,9 @@ __global__ __launch_bounds__(B3_NT, 2) void k_gemm_b3_big(const uint4* __restric
     }
     const int P = g.Hout * g.Hout;
     const long long M = (long long)(*d_count) * P;
-    if (mt >= num_mt || (long long)mt * BM >= M) return;
+    if (mt >= num_mt) return;
+    mt += g.mt0;                                             // from here on mt is the row tile of the layer, not of the launch
+    if ((long long)mt * BM >= M) return;
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);

@@ -1,0 +1,114 @@
+"""The row plan of the bf16x3 GEMM layers (oz_net.hip: b3_big_rows / b3_plan_rows, shown without a device by oz_net_b3_plan): which leading rows of
+a layer run on 256 x 256 tiles and which on 128 x 256 tiles, as a function of the network's CAPACITY alone.  No GPU.
+
+The mixed plan exists where the big part is at least one whole round of the 256 CUs and the rest at most one round of small tiles; everywhere else the
+plan is what it was before the mixed plan existed (one tile for the whole layer)."""
+import pytest
+
+from othellozero_amd.NNet import b3_plan
+
+CONV3, CONV4 = 2, 3
+
+
+def _blocks(rows, bm, channels):
+    return -(-rows // bm) * (channels // 256)
+
+
+def test_bench_network_conv3_is_four_big_rounds_and_one_small():
+    p = b3_plan(8, 512, 4096, CONV3)
+    assert p == dict(kernel="b3_mixed", big_rows=131072, small_tiles=128), p
+    # 131072 rows of 256-row tiles x 2 column tiles = 4 whole rounds; 128 row tiles x 2 = one round: nothing is paid for and left idle
+    assert _blocks(p["big_rows"], 256, 512) == 4 * 256 and p["small_tiles"] * 2 == 256
+    assert p["big_rows"] + p["small_tiles"] * 128 == 4096 * 36
+
+
+@pytest.mark.parametrize("n,layer", [(8, CONV4), (6, CONV3)])
+def test_layers_of_exactly_two_big_rounds_stay_all_big(n, layer):
+    p = b3_plan(n, 512, 4096, layer)
+    assert p == dict(kernel="b3_big", big_rows=65536, small_tiles=0), p
+
+
+@pytest.mark.parametrize("capacity", [160, 192, 384, 512])
+def test_small_and_medium_networks_never_mix(capacity):
+    for n in (8, 6):
+        for layer in (1, 2, 3, 4, 5):
+            for kslices in (1, 2, 4, 8):
+                p = b3_plan(n, 512, capacity, layer, kslices=kslices)
+                assert p["kernel"] == "b3" and p["big_rows"] == 0, (n, layer, kslices, p)
+            assert b3_plan(n, 256, capacity, layer)["kernel"] == "b3"
+
+
+def test_mixing_becomes_possible_at_911_boards():
+    # 8x8 conv3 at 512 filters: 910 boards = 32760 rows = 128 big row tiles, the last one short of rows: not one whole round AND something left over
+    assert b3_plan(8, 512, 910, CONV3)["kernel"] != "b3_mixed"
+    p = b3_plan(8, 512, 911, CONV3)
+    assert p == dict(kernel="b3_mixed", big_rows=32768, small_tiles=1), p
+    for capacity in range(1, 911):
+        for layer in (CONV3, CONV4):
+            assert b3_plan(8, 512, capacity, layer)["kernel"] != "b3_mixed", (capacity, layer)
+
+
+def test_a_remainder_of_more_than_one_small_round_is_not_mixed():
+    # 1466 boards of 8x8 conv3 = 52776 rows: one whole big round (32768 rows) and 20008 rows = 157 small row tiles x 2 = 314 blocks > 256
+    p = b3_plan(8, 512, 1466, CONV3)
+    assert p["kernel"] == "b3_big" and p["big_rows"] == 52776, p
+    # every capacity: a mixed plan is whole big rounds plus at most one small round, and the rows add up
+    for n, pixels in ((8, {CONV3: 36, CONV4: 16}), (6, {CONV3: 16, CONV4: 4})):
+        for capacity in list(range(128, 6000, 7)) + [4096, 8192]:
+            for layer in (CONV3, CONV4):
+                p, rows = b3_plan(n, 512, capacity, layer), capacity * pixels[layer]
+                if p["kernel"] == "b3_mixed":
+                    assert 0 < p["big_rows"] < rows and _blocks(p["big_rows"], 256, 512) % 256 == 0 and p["big_rows"] % 256 == 0, (n, capacity, layer, p)
+                    assert 0 < p["small_tiles"] * 2 <= 256 and p["small_tiles"] == -(-(rows - p["big_rows"]) // 128), (n, capacity, layer, p)
+                elif p["kernel"] == "b3_big":
+                    assert p["big_rows"] == rows and p["small_tiles"] == 0 and _blocks(rows, 256, 512) >= 192
+                else:
+                    assert p["big_rows"] == 0 and p["small_tiles"] == -(-rows // 128)
+
+
+def test_preconditions_and_switches():
+    # a split k loop, 'same' padding and the dense layers never mix on their own
+    assert b3_plan(8, 512, 4096, CONV3, kslices=2)["kernel"] == "b3"
+    assert b3_plan(8, 512, 4096, 1)["kernel"] == "b3"                       # conv2: pad 1
+    for layer in (4, 5):
+        assert b3_plan(8, 512, 4096, layer)["kernel"] != "b3_mixed"
+    # never mix: the plan of the single tiles -- 9 small rounds against 4.5 big ones paid as 5
+    assert b3_plan(8, 512, 4096, CONV3, mix_rows=-1) == dict(kernel="b3", big_rows=0, small_tiles=1152)
+    assert b3_plan(8, 512, 4096, CONV4, mix_rows=-1)["kernel"] == "b3_big"
+    # a forced tile is that tile for the whole launch, whatever the mix option says
+    for mix in (0, -1, 512):
+        assert b3_plan(8, 512, 4096, CONV3, tile=128, mix_rows=mix) == dict(kernel="b3", big_rows=0, small_tiles=1152)
+        assert b3_plan(8, 512, 4096, CONV3, tile=256, mix_rows=mix) == dict(kernel="b3_big", big_rows=147456, small_tiles=0)
+    # forced rows: conv3 and conv4 of any capacity and k split, the boundary where the caller puts it
+    assert b3_plan(8, 512, 160, CONV3, kslices=4, mix_rows=256) == dict(kernel="b3_mixed", big_rows=256, small_tiles=43)
+    assert b3_plan(8, 512, 160, CONV4, kslices=8, mix_rows=512) == dict(kernel="b3_mixed", big_rows=512, small_tiles=16)
+    assert b3_plan(6, 512, 160, CONV3, kslices=8, mix_rows=256) == dict(kernel="b3_mixed", big_rows=256, small_tiles=18)
+    # ... but only 'valid' 3x3 layers, and only a boundary inside the capacity's rows
+    assert b3_plan(8, 512, 160, 1, kslices=2, mix_rows=256)["kernel"] == "b3"
+    assert b3_plan(8, 512, 160, 4, kslices=8, mix_rows=256)["kernel"] == "b3"
+    assert b3_plan(6, 512, 160, CONV4, kslices=8, mix_rows=1024)["kernel"] == "b3"        # 640 rows
+    from othellozero_amd import _lib
+    for bad in dict(mix_rows=100), dict(tile=192), dict(layer=6):
+        args = dict(n=8, channels=512, max_batch=160, layer=CONV3)
+        args.update(bad)
+        with pytest.raises(_lib.OzError):
+            b3_plan(**args)
+
+
+def test_profile_summary_counts_the_two_launches_of_a_mixed_layer_as_one_layer():
+    """tools/summarize_prof.py labels layers by launch order: k_gemm_b3_big<3> followed by k_gemm_b3<3> is conv3 twice, and conv4 / fc1 / fc2 keep their names"""
+    import importlib.util
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("summarize_prof", os.path.join(root, "tools", "summarize_prof.py"))
+    sp = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(sp)
+    head, tail = ["k_backup_advance", "k_compact", "k_lut_ids", "k_conv2_lut_xcd<8, 2, false>"], ["k_gemm_b3_big<4>", "k_gemm_b3<5>", "k_splitk_reduce_b3", "k_gemm_b3<6>", "k_heads_lds"]
+    mixed = sp.label_layers(head + ["k_gemm_b3_big<3>", "k_gemm_b3<3>"] + tail)
+    assert [l for l in mixed if l] == ["conv1+conv2 (table gather)", "conv3", "conv3", "conv4", "fc1", "fc2"]
+    plain = sp.label_layers(head + ["k_gemm_b3<3>"] + tail)
+    assert [l for l in plain if l] == ["conv1+conv2 (table gather)", "conv3", "conv4", "fc1", "fc2"]
+    both = sp.label_layers(head + ["k_gemm_b3_big<3>", "k_gemm_b3<3>", "k_gemm_b3_big<4>", "k_gemm_b3<4>"] + tail[1:])
+    assert [l for l in both if l] == ["conv1+conv2 (table gather)", "conv3", "conv3", "conv4", "conv4", "fc1", "fc2"]
+    # the trainer's launches share one tag per direction: consecutive layers stay consecutive layers
+    assert sp.label_layers(["k_conv1", "k_gemm_b3<7>", "k_gemm_b3_big<7>", "k_gemm_b3<7>"])[1:] == ["conv2", "conv3", "conv4"]

@@ -53,12 +53,14 @@ def label_layers(records):
     """records: dispatch-ordered (kernel, ...) tuples.  Returns one layer name (or "") per record: a forward starts at k_lut_ids / k_conv1*,
     whether it uses the table gather decides which GEMM comes first, and the n-th k_gemm launch after the start is the n-th layer of
     OthelloNN -- launch ORDER, not grid size, so every batch size, tile choice and board is labelled the same way.  The table build at
-    oz_net_commit (nine GEMMs in a row without a forward start) stays unlabelled."""
+    oz_net_commit (nine GEMMs in a row without a forward start) stays unlabelled.  One exception to "a launch = a layer": the bf16x3 mixed plan
+    runs a layer as k_gemm_b3_big<TAG> over its leading rows and then k_gemm_b3<TAG> over the rest -- a k_gemm_b3 right behind a k_gemm_b3_big
+    of the same TAG belongs to that launch's layer."""
     out = [""] * len(records)
-    order, idx, open_fw = None, 0, False
+    order, idx, open_fw, prev_tag = None, 0, False, None
     for i, k in enumerate(records):
         if k.startswith("k_lut_ids") or k.startswith("k_conv1"):
-            open_fw, idx = True, 0
+            open_fw, idx, prev_tag = True, 0, None
             order = None if k.startswith("k_lut_ids") else NET_ORDER_GEMM      # k_lut_ids: decided by what follows
             continue
         if not open_fw:
@@ -70,6 +72,12 @@ def label_layers(records):
         if k.startswith("k_gemm"):
             if order is None:
                 order = NET_ORDER_GEMM                        # k_lut_ids followed by a GEMM: conv1 from its table inside conv2's gather
+            tag = re.match(r"k_gemm_b3(_big)?<([2-6])>", k)       # (TAG 2 .. 6: the network object's layers, one tag each; the trainer's 7 / 8 repeat)
+            if tag and not tag.group(1) and prev_tag == tag.group(2) and idx > 0:     # the second launch of a mixed layer
+                out[i] = order[idx - 1]
+                prev_tag = None
+                continue
+            prev_tag = tag.group(2) if tag and tag.group(1) else None
             if idx < len(order):
                 out[i] = order[idx]
             idx += 1
