@@ -94,16 +94,16 @@ struct MctsDev {
     double* noise_eta;         // [G][64] eta by square, 0 off the legal set of the root it was drawn for
     uint8_t* noise_armed;      // [G] the slot's CURRENT root carries noise
     double noise_eps;          // the mixing weight (0: off)
-    double forced_k;           // forced playouts ("forced playouts" below): the forcing constant k (0: off); needs noise, so the *_n kernels alone read it
+    double forced_k;           // forced playouts ("forced playouts" below): the forcing constant k (0: off); needs noise, so the TV_NOISE kernels alone read it
     ProofDev pf;               // proofs ("proofs" below): null / 0 until oz_*_set_proofs; the OZ_VSIGNS_PROVEN instantiations alone read it
-    OzSelection sel;           // selection ("selection" in oz_common.h): flags == 0 until oz_*_set_selection; the *_sel kernels alone read it
+    OzSelection sel;           // selection ("selection" in oz_common.h): flags == 0 until oz_*_set_selection; the TV_SEL kernels alone read it
 };
 // the frontier entries (node, edge rank): the rank is below 64; in the sound instantiations (VS, "value signs" in oz_common.h) bit 30 of .y keeps
 // sigma of the level -- the descent swapped sides after the edge.  The reference instantiations never set the bit and read .y as it is.
 #define OZ_PATH_SWAP (1 << 30)
 template <int VS> __device__ __forceinline__ int path_rank(int y) { return VS != OZ_VSIGNS_REFERENCE ? y & (OZ_PATH_SWAP - 1) : y; }
 
-// Gumbel search ("Gumbel search" below): what the *_g kernels get beside MctsDev.  An object without the option never fills or passes it.
+// Gumbel search ("Gumbel search" below): what the tree kernels get beside MctsDev; the TV_GUMBEL ones alone read it.  An object without the option never fills it.
 struct GumbelDev {
     double* g;                 // [G][64] the Gumbel draw by square, 0 off the legal set of the root it was drawn for
     int* n0;                   // [G][64] the root's stored N when the slot was armed (0: the root was not in the table)
@@ -384,10 +384,10 @@ struct Descent {
     int fs;                    // free table slot of the probe that left the known tree (-1: none)
     int err;                   // EF_* bit of an error exit (status is then OZ_LEAF_IDLE), 0: none
 };
-// GUMBEL (the *_g kernels): gr = the slot's Gumbel view (gumbel_of_slot); on an armed root, depth 0 picks by the Gumbel rule instead of PUCT.
+// GUMBEL (the TV_GUMBEL kernels): gr = the slot's Gumbel view (gumbel_of_slot); on an armed root, depth 0 picks by the Gumbel rule instead of PUCT.
 struct GumbelRoot { bool armed; double g; int n0; const GumbelDev* gd; };
 // VS: the value signs the tree holds (oz_common.h), a template argument of every tree kernel: the default's code is the reference rule alone
-// SEL (the *_sel kernels): U by the selection rule of oz_common.h ("selection"); t.sel is uniform: one branch per part and wave
+// SEL (the TV_SEL kernels): U by the selection rule of oz_common.h ("selection"); t.sel is uniform: one branch per part and wave
 template <bool NOISE, bool GUMBEL = false, int VS = OZ_VSIGNS_REFERENCE, bool SEL = false>
 __device__ __forceinline__ Descent descend_one(const MctsDev& t, uint4* rec, int2* path, int g, int lane, uint64_t own, uint64_t opp, uint64_t legal,
                                                int& rootn, bool noisy, double eta, const InFlight fl, const GumbelRoot gr = GumbelRoot{false, 0.0, 0, nullptr}) {
@@ -604,34 +604,6 @@ __device__ __forceinline__ int select_body(const MctsDev& t, TreeLds& L, int g, 
         if (e.err) atomicOr(t.error_flag, e.err);
     }
     return e.status;
-}
-template <int VS = OZ_VSIGNS_REFERENCE>
-__global__ __launch_bounds__(64) void k_select(MctsDev t) {
-    __shared__ TreeLds L;
-    select_body<false, false, VS>(t, L, blockIdx.x, threadIdx.x);
-}
-// (the *_n kernels: the same kernels over the NOISE = true bodies, launched by objects that have armed root noise)
-template <int VS = OZ_VSIGNS_REFERENCE>
-__global__ __launch_bounds__(64) void k_select_n(MctsDev t) {
-    __shared__ TreeLds L;
-    select_body<true, false, VS>(t, L, blockIdx.x, threadIdx.x);
-}
-// (the *_sel kernels: the same kernels over the SEL = true bodies, launched by objects with the selection option)
-template <int VS = OZ_VSIGNS_REFERENCE>
-__global__ __launch_bounds__(64) void k_select_sel(MctsDev t) {
-    __shared__ TreeLds L;
-    select_body<false, false, VS, true>(t, L, blockIdx.x, threadIdx.x);
-}
-template <int VS = OZ_VSIGNS_REFERENCE>
-__global__ __launch_bounds__(64) void k_select_n_sel(MctsDev t) {
-    __shared__ TreeLds L;
-    select_body<true, false, VS, true>(t, L, blockIdx.x, threadIdx.x);
-}
-// (the *_g kernels: the same kernels over the GUMBEL = true bodies, launched by objects with the Gumbel search switched on)
-template <int VS = OZ_VSIGNS_REFERENCE>
-__global__ __launch_bounds__(64) void k_select_g(MctsDev t, GumbelDev gd) {
-    __shared__ TreeLds L;
-    select_body<false, true, VS>(t, L, blockIdx.x, threadIdx.x, &gd);
 }
 
 // ---------------------------------------------------------------- K13: leaf compaction
@@ -1023,62 +995,45 @@ __device__ __forceinline__ void expand_backup_body(const MctsDev& t, TreeLds& L,
     lf.path = t.path + (size_t)g * OZ_MAX_DEPTH;
     expand_backup_one<GUMBEL, VS, SEL>(t, L, g, lane, lf);
 }
-template <int VS = OZ_VSIGNS_REFERENCE>
-__global__ __launch_bounds__(64) void k_expand_backup(MctsDev t, int slot_is_game) {
+// ---- the tree kernels: one template per phase, instantiated per variant.  V is a mask of TV_* flags; tree_kernels() (host side) computes it
+// from the object's state and is the one place that says which masks have a kernel.  An object without an option launches the instantiations
+// without its flag, which are the code they were before the option existed, register for register.
+//   flag        option (what sets it)                                   what the bodies do with it
+//   TV_SIGNS    the low two bits ARE the OZ_VSIGNS_* value:             VS of every body: the backup's signs, sigma riding in the path entries;
+//               value signs (oz_*_set_value_signs: SOUND), proofs       PROVEN also keeps, backs up and descends by the proof entries (t.pf)
+//               (oz_*_set_proofs: PROVEN); 0 = the reference's rule
+//   TV_NOISE    root noise, from the object's first arming on           NOISE of the descent: an armed slot's depth 0 sees (1 - eps) P + eps eta;
+//               (oz_mcts::noise_ever)                                   the expansion and the backup never look at it (k_*expand_backup: never set)
+//   TV_SEL      selection (oz_*_set_selection, t.sel.flags != 0)        SEL: U by the selection rule of oz_common.h; a new node keeps vhat for its FPU
+//   TV_GUMBEL   the Gumbel search, from its first setting on            GUMBEL: an armed root picks by the Gumbel rule (reads gd; nobody else does);
+//               (oz_mcts::gumbel_ever); one descent per step only       a new node keeps vhat for the completed Q
+enum : unsigned { TV_SIGNS = 3, TV_NOISE = 4, TV_SEL = 8, TV_GUMBEL = 16 };
+constexpr bool has(unsigned v, unsigned flag) { return (v & flag) != 0; }
+// between the expand + backup of one step and what the same wave does next in the same launch: the wave's own stores (records, child indices,
+// table entry, root index) before its loads, and the LDS stage free again
+__device__ __forceinline__ void backup_fence() {
+    wave_sync();
+    __syncthreads();
+}
+template <unsigned V>
+__global__ __launch_bounds__(64) void k_select(MctsDev t, GumbelDev gd) {
     __shared__ TreeLds L;
-    expand_backup_body<false, VS>(t, L, blockIdx.x, threadIdx.x, slot_is_game);
+    select_body<has(V, TV_NOISE), has(V, TV_GUMBEL), int(V & TV_SIGNS), has(V, TV_SEL)>(t, L, blockIdx.x, threadIdx.x, &gd);
+}
+template <unsigned V>
+__global__ __launch_bounds__(64) void k_expand_backup(MctsDev t, int slot_is_game) {
+    static_assert(!has(V, TV_NOISE), "root noise is the descent's alone: one expand + backup for both");
+    __shared__ TreeLds L;
+    expand_backup_body<has(V, TV_GUMBEL), int(V & TV_SIGNS), has(V, TV_SEL)>(t, L, blockIdx.x, threadIdx.x, slot_is_game);
 }
 // expand + backup of simulation s-1 and the descent of simulation s in ONE launch (same wave, same game): one kernel boundary
 // less per simulation step, and the records the backup has just written are re-read by the descent while still in the CU's cache
-template <int VS = OZ_VSIGNS_REFERENCE>
-__global__ __launch_bounds__(64) void k_backup_select(MctsDev t) {
+template <unsigned V>
+__global__ __launch_bounds__(64) void k_backup_select(MctsDev t, GumbelDev gd) {
     __shared__ TreeLds L;
-    expand_backup_body<false, VS>(t, L, blockIdx.x, threadIdx.x, 0);
-    wave_sync();                                           // the wave's own stores (records, child indices, table entry, root index) before its loads
-    __syncthreads();
-    select_body<false, false, VS>(t, L, blockIdx.x, threadIdx.x);
-}
-template <int VS = OZ_VSIGNS_REFERENCE>
-__global__ __launch_bounds__(64) void k_backup_select_n(MctsDev t) {
-    __shared__ TreeLds L;
-    expand_backup_body<false, VS>(t, L, blockIdx.x, threadIdx.x, 0);
-    wave_sync();
-    __syncthreads();
-    select_body<true, false, VS>(t, L, blockIdx.x, threadIdx.x);
-}
-template <int VS = OZ_VSIGNS_REFERENCE>
-__global__ __launch_bounds__(64) void k_expand_backup_sel(MctsDev t, int slot_is_game) {
-    __shared__ TreeLds L;
-    expand_backup_body<false, VS, true>(t, L, blockIdx.x, threadIdx.x, slot_is_game);
-}
-template <int VS = OZ_VSIGNS_REFERENCE>
-__global__ __launch_bounds__(64) void k_backup_select_sel(MctsDev t) {
-    __shared__ TreeLds L;
-    expand_backup_body<false, VS, true>(t, L, blockIdx.x, threadIdx.x, 0);
-    wave_sync();
-    __syncthreads();
-    select_body<false, false, VS, true>(t, L, blockIdx.x, threadIdx.x);
-}
-template <int VS = OZ_VSIGNS_REFERENCE>
-__global__ __launch_bounds__(64) void k_backup_select_n_sel(MctsDev t) {
-    __shared__ TreeLds L;
-    expand_backup_body<false, VS, true>(t, L, blockIdx.x, threadIdx.x, 0);
-    wave_sync();
-    __syncthreads();
-    select_body<true, false, VS, true>(t, L, blockIdx.x, threadIdx.x);
-}
-template <int VS = OZ_VSIGNS_REFERENCE>
-__global__ __launch_bounds__(64) void k_expand_backup_g(MctsDev t, int slot_is_game) {
-    __shared__ TreeLds L;
-    expand_backup_body<true, VS>(t, L, blockIdx.x, threadIdx.x, slot_is_game);
-}
-template <int VS = OZ_VSIGNS_REFERENCE>
-__global__ __launch_bounds__(64) void k_backup_select_g(MctsDev t, GumbelDev gd) {
-    __shared__ TreeLds L;
-    expand_backup_body<true, VS>(t, L, blockIdx.x, threadIdx.x, 0);
-    wave_sync();
-    __syncthreads();
-    select_body<false, true, VS>(t, L, blockIdx.x, threadIdx.x, &gd);
+    expand_backup_body<has(V, TV_GUMBEL), int(V & TV_SIGNS), has(V, TV_SEL)>(t, L, blockIdx.x, threadIdx.x, 0);
+    backup_fence();
+    select_body<has(V, TV_NOISE), has(V, TV_GUMBEL), int(V & TV_SIGNS), has(V, TV_SEL)>(t, L, blockIdx.x, threadIdx.x, &gd);
 }
 
 
@@ -1200,69 +1155,28 @@ __device__ __forceinline__ void wide_expand_backup_body(const MctsDev& t, const 
         t.depth[g] = depth;                                                     // oz_mcts_last_value: of the last simulation backed up
     }
 }
-template <int VS = OZ_VSIGNS_REFERENCE>
+// the leaf-parallel tree kernels: V as above (no TV_GUMBEL: the Gumbel search runs one descent per step)
+template <unsigned V>
 __global__ __launch_bounds__(64) void k_wide_select(MctsDev t, WideDev w) {
+    static_assert(!has(V, TV_GUMBEL), "the Gumbel search has no leaf-parallel kernels");
     __shared__ WideLds L;
-    wide_select_body<false, VS>(t, w, L, blockIdx.x, threadIdx.x);
+    wide_select_body<has(V, TV_NOISE), int(V & TV_SIGNS), has(V, TV_SEL)>(t, w, L, blockIdx.x, threadIdx.x);
 }
-template <int VS = OZ_VSIGNS_REFERENCE>
-__global__ __launch_bounds__(64) void k_wide_select_n(MctsDev t, WideDev w) {
-    __shared__ WideLds L;
-    wide_select_body<true, VS>(t, w, L, blockIdx.x, threadIdx.x);
-}
-template <int VS = OZ_VSIGNS_REFERENCE>
+template <unsigned V>
 __global__ __launch_bounds__(64) void k_wide_expand_backup(MctsDev t, WideDev w) {
+    static_assert(!has(V, TV_GUMBEL), "the Gumbel search has no leaf-parallel kernels");
+    static_assert(!has(V, TV_NOISE), "root noise is the descent's alone: one expand + backup for both");
     __shared__ WideLds L;
-    wide_expand_backup_body<VS>(t, w, L, blockIdx.x, threadIdx.x);
+    wide_expand_backup_body<int(V & TV_SIGNS), has(V, TV_SEL)>(t, w, L, blockIdx.x, threadIdx.x);
 }
 // expand + backup of step s-1 and the descents of step s in ONE launch (the wide counterpart of k_backup_select)
-template <int VS = OZ_VSIGNS_REFERENCE>
+template <unsigned V>
 __global__ __launch_bounds__(64) void k_wide_backup_select(MctsDev t, WideDev w) {
+    static_assert(!has(V, TV_GUMBEL), "the Gumbel search has no leaf-parallel kernels");
     __shared__ WideLds L;
-    wide_expand_backup_body<VS>(t, w, L, blockIdx.x, threadIdx.x);
-    wave_sync();
-    __syncthreads();
-    wide_select_body<false, VS>(t, w, L, blockIdx.x, threadIdx.x);
-}
-template <int VS = OZ_VSIGNS_REFERENCE>
-__global__ __launch_bounds__(64) void k_wide_backup_select_n(MctsDev t, WideDev w) {
-    __shared__ WideLds L;
-    wide_expand_backup_body<VS>(t, w, L, blockIdx.x, threadIdx.x);
-    wave_sync();
-    __syncthreads();
-    wide_select_body<true, VS>(t, w, L, blockIdx.x, threadIdx.x);
-}
-// (the *_sel kernels of the leaf-parallel search: the SEL = true bodies)
-template <int VS = OZ_VSIGNS_REFERENCE>
-__global__ __launch_bounds__(64) void k_wide_select_sel(MctsDev t, WideDev w) {
-    __shared__ WideLds L;
-    wide_select_body<false, VS, true>(t, w, L, blockIdx.x, threadIdx.x);
-}
-template <int VS = OZ_VSIGNS_REFERENCE>
-__global__ __launch_bounds__(64) void k_wide_select_n_sel(MctsDev t, WideDev w) {
-    __shared__ WideLds L;
-    wide_select_body<true, VS, true>(t, w, L, blockIdx.x, threadIdx.x);
-}
-template <int VS = OZ_VSIGNS_REFERENCE>
-__global__ __launch_bounds__(64) void k_wide_expand_backup_sel(MctsDev t, WideDev w) {
-    __shared__ WideLds L;
-    wide_expand_backup_body<VS, true>(t, w, L, blockIdx.x, threadIdx.x);
-}
-template <int VS = OZ_VSIGNS_REFERENCE>
-__global__ __launch_bounds__(64) void k_wide_backup_select_sel(MctsDev t, WideDev w) {
-    __shared__ WideLds L;
-    wide_expand_backup_body<VS, true>(t, w, L, blockIdx.x, threadIdx.x);
-    wave_sync();
-    __syncthreads();
-    wide_select_body<false, VS, true>(t, w, L, blockIdx.x, threadIdx.x);
-}
-template <int VS = OZ_VSIGNS_REFERENCE>
-__global__ __launch_bounds__(64) void k_wide_backup_select_n_sel(MctsDev t, WideDev w) {
-    __shared__ WideLds L;
-    wide_expand_backup_body<VS, true>(t, w, L, blockIdx.x, threadIdx.x);
-    wave_sync();
-    __syncthreads();
-    wide_select_body<true, VS, true>(t, w, L, blockIdx.x, threadIdx.x);
+    wide_expand_backup_body<int(V & TV_SIGNS), has(V, TV_SEL)>(t, w, L, blockIdx.x, threadIdx.x);
+    backup_fence();
+    wide_select_body<has(V, TV_NOISE), int(V & TV_SIGNS), has(V, TV_SEL)>(t, w, L, blockIdx.x, threadIdx.x);
 }
 // dense batch in (game, j) order: prefix sum over the per-game leaf counts
 __global__ __launch_bounds__(1024) void k_wide_compact(MctsDev t, WideDev w) {
@@ -1385,10 +1299,10 @@ struct oz_mcts {
     int leaves_per_step = 1;
     bool use_wide = false;           // oz_mcts_use_wide_kernels: K = 1 through the wide kernels
     bool wide() const { return leaves_per_step > 1 || use_wide; }
-    // root noise: true from the first arming on (d.noise_eta / d.noise_armed are then allocated): the descents run on the *_n kernels
+    // root noise: true from the first arming on (d.noise_eta / d.noise_armed are then allocated): the descents run on the TV_NOISE kernels
     bool noise_ever = false;
     uint64_t* noise_ids = nullptr; int32_t* noise_plies = nullptr;      // staging of the keys of oz_mcts_sample_root_noise / oz_mcts_sample_moves, [G] each
-    // Gumbel search: true from the first oz_mcts_set_gumbel / oz_mcts_sample_gumbel on (gd's arrays are then allocated): the object runs on the *_g kernels
+    // Gumbel search: true from the first oz_mcts_set_gumbel / oz_mcts_sample_gumbel on (gd's arrays are then allocated): the object runs on the TV_GUMBEL kernels
     bool gumbel_ever = false;
     GumbelDev gd{};
     int* gumbel_table = nullptr; size_t gumbel_table_len = 0;           // the device copy of the schedule gd.table points to
@@ -1525,12 +1439,41 @@ static int check_error_flag(oz_mcts* m) {
     return OZ_OK;
 }
 
-// the tree kernel `K` of the object m's value signs (m in scope)
-#define OZ_VS(K) (m->vsigns != OZ_VSIGNS_REFERENCE ? K<OZ_VSIGNS_SOUND> : K<OZ_VSIGNS_REFERENCE>)
-// ... of the kernels that have the proven instantiation (the plain and the wide search; the Gumbel and free-running families refuse the option)
-#define OZ_VSP(K) (m->proofs ? K<OZ_VSIGNS_PROVEN> : OZ_VS(K))
-// ... of the kernels that have the selection instantiation too (the same two families; the Gumbel and free-running ones refuse the option)
-#define OZ_VSPS(K) (m->d.sel.flags ? OZ_VSP(K##_sel) : OZ_VSP(K))
+// the tree kernels of one variant: a call's first descents, every further step's (the step before backed up in the same launch), the closing
+// expand + backup; one descent per game and step, and K of them (null where the variant has none)
+struct TreeKernels {
+    void (*select)(MctsDev, GumbelDev);
+    void (*backup_select)(MctsDev, GumbelDev);
+    void (*expand_backup)(MctsDev, int);
+    void (*wide_select)(MctsDev, WideDev);
+    void (*wide_backup_select)(MctsDev, WideDev);
+    void (*wide_expand_backup)(MctsDev, WideDev);
+};
+template <unsigned V> static TreeKernels tree_kernels_of() {
+    constexpr unsigned B = V & ~TV_NOISE;                    // root noise is the descent's alone
+    if constexpr (has(V, TV_GUMBEL)) return {k_select<V>, k_backup_select<V>, k_expand_backup<B>, nullptr, nullptr, nullptr};
+    else return {k_select<V>, k_backup_select<V>, k_expand_backup<B>, k_wide_select<V>, k_wide_backup_select<V>, k_wide_expand_backup<B>};
+}
+// the tree kernels of the object as it is now.  THE list of the variants that exist: every value signs with and without root noise and the
+// selection rule, and the Gumbel search under the reference's and the sound signs alone, one descent per step (the setters refuse the rest)
+static int tree_kernels(const oz_mcts* m, TreeKernels* k) {
+    const unsigned v = (m->proofs ? OZ_VSIGNS_PROVEN : m->vsigns != OZ_VSIGNS_REFERENCE ? OZ_VSIGNS_SOUND : OZ_VSIGNS_REFERENCE) | (m->noise_ever ? TV_NOISE : 0) |
+                       (m->d.sel.flags ? TV_SEL : 0) | (m->gumbel_ever ? TV_GUMBEL : 0);
+    switch (v) {
+#define OZ_V(...) case (__VA_ARGS__): *k = tree_kernels_of<(__VA_ARGS__)>(); break
+        OZ_V(OZ_VSIGNS_REFERENCE); OZ_V(OZ_VSIGNS_REFERENCE | TV_NOISE); OZ_V(OZ_VSIGNS_REFERENCE | TV_SEL); OZ_V(OZ_VSIGNS_REFERENCE | TV_NOISE | TV_SEL);
+        OZ_V(OZ_VSIGNS_SOUND); OZ_V(OZ_VSIGNS_SOUND | TV_NOISE); OZ_V(OZ_VSIGNS_SOUND | TV_SEL); OZ_V(OZ_VSIGNS_SOUND | TV_NOISE | TV_SEL);
+        OZ_V(OZ_VSIGNS_PROVEN); OZ_V(OZ_VSIGNS_PROVEN | TV_NOISE); OZ_V(OZ_VSIGNS_PROVEN | TV_SEL); OZ_V(OZ_VSIGNS_PROVEN | TV_NOISE | TV_SEL);
+        OZ_V(OZ_VSIGNS_REFERENCE | TV_GUMBEL); OZ_V(OZ_VSIGNS_SOUND | TV_GUMBEL);
+#undef OZ_V
+        default:
+            oz_set_error("the search has no tree kernels for value signs %u%s%s%s", v & TV_SIGNS, has(v, TV_NOISE) ? " + root noise" : "",
+                         has(v, TV_SEL) ? " + selection" : "", has(v, TV_GUMBEL) ? " + the Gumbel search" : "");
+            return OZ_ERR_STATE;
+    }
+    if (m->wide() && !k->wide_select) { oz_set_error("the Gumbel search runs one leaf per game and step: it has no leaf-parallel kernels"); return OZ_ERR_STATE; }
+    return OZ_OK;
+}
 enum { TS_SELECT = 0, TS_COMPACT = 1, TS_NN = 2, TS_BACKUP = 3, TS_MOVE = 4 };
 // the step's solved rows (k_solve_leaves): after the evaluator of EITHER kind of step has written the rows [0, cap) (and the cache has taken
 // them), before their expand + backup.  hits: the step may have rows served from the evaluation cache.  Off (the default), nothing is launched.
@@ -1619,6 +1562,8 @@ static int wide_set_k(oz_mcts* m, int k) {
 static int mcts_wide_steps(oz_mcts* m, oz_net* net, int nsims, int max_games, bool time_eval, const CapKeys* ck = nullptr) {
     MctsDev& d = m->d;
     if (int rc = wide_alloc(m)) return rc;
+    TreeKernels tk;
+    if (int rc = tree_kernels(m, &tk)) return rc;
     WideDev w = m->w;
     w.K = m->leaves_per_step;
     hipStream_t s = m->stream;
@@ -1633,17 +1578,14 @@ static int mcts_wide_steps(oz_mcts* m, oz_net* net, int nsims, int max_games, bo
         enqueued += steps;
         if (enqueued > (long long)nsims) { oz_set_error("leaf-parallel search: the simulation budget did not run out after %d steps (internal error)", nsims); return OZ_ERR_STATE; }
         for (int k = 0; k < steps; ++k) {
-            timed(m, TS_SELECT, all, [&] {
-                if (k == 0) hipLaunchKernelGGL(m->noise_ever ? OZ_VSPS(k_wide_select_n) : OZ_VSPS(k_wide_select), dim3(d.G), dim3(64), 0, s, d, w);
-                else hipLaunchKernelGGL(m->noise_ever ? OZ_VSPS(k_wide_backup_select_n) : OZ_VSPS(k_wide_backup_select), dim3(d.G), dim3(64), 0, s, d, w);
-            });
+            timed(m, TS_SELECT, all, [&] { hipLaunchKernelGGL(k == 0 ? tk.wide_select : tk.wide_backup_select, dim3(d.G), dim3(64), 0, s, d, w); });
             timed(m, TS_COMPACT, all, [&] { hipLaunchKernelGGL(k_wide_compact, dim3(1), dim3(1024), 0, s, d, w); });
             const long long i = (time_eval || all) ? m->timer.begin(TS_NN, s) : -1;
             if (int rc = oz_net_forward_device(net, d.batch_own, d.batch_opp, d.batch_count, cap, d.pi, d.v, s)) { m->timer.cancel(i); return rc; }
             m->timer.end(i, s);
             solve_leaves_async(m, cap, false);              // (no evaluation cache here: every leaf has a row of its own)
         }
-        timed(m, TS_BACKUP, all, [&] { hipLaunchKernelGGL(OZ_VSPS(k_wide_expand_backup), dim3(d.G), dim3(64), 0, s, d, w); });
+        timed(m, TS_BACKUP, all, [&] { hipLaunchKernelGGL(tk.wide_expand_backup, dim3(d.G), dim3(64), 0, s, d, w); });
         OZ_HIP(hipGetLastError());
         int max_left = 0;
         OZ_HIP(hipMemsetAsync(w.max_left, 0, sizeof(int), s));
@@ -1669,21 +1611,17 @@ static int mcts_collect_eval_time(oz_mcts* m) {
 static int mcts_steps_async(oz_mcts* m, oz_net* net, int nsims, int max_games, bool time_eval, const CapKeys* ck = nullptr) {
     if (m->wide()) return mcts_wide_steps(m, net, nsims, max_games, time_eval, ck);
     if (nsims <= 0) return OZ_OK;
+    TreeKernels tk;
+    if (int rc = tree_kernels(m, &tk)) return rc;
     MctsDev& d = m->d;
     hipStream_t s = m->stream;
     const bool all = m->profile;
     for (int k = 0; k < nsims; ++k) {
-        timed(m, TS_SELECT, all, [&] {
-            if (m->gumbel_ever) {
-                if (k == 0) hipLaunchKernelGGL(OZ_VS(k_select_g), dim3(d.G), dim3(64), 0, s, d, m->gd);
-                else hipLaunchKernelGGL(OZ_VS(k_backup_select_g), dim3(d.G), dim3(64), 0, s, d, m->gd);
-            } else if (k == 0) hipLaunchKernelGGL(m->noise_ever ? OZ_VSPS(k_select_n) : OZ_VSPS(k_select), dim3(d.G), dim3(64), 0, s, d);
-            else hipLaunchKernelGGL(m->noise_ever ? OZ_VSPS(k_backup_select_n) : OZ_VSPS(k_backup_select), dim3(d.G), dim3(64), 0, s, d);
-        });
+        timed(m, TS_SELECT, all, [&] { hipLaunchKernelGGL(k == 0 ? tk.select : tk.backup_select, dim3(d.G), dim3(64), 0, s, d, m->gd); });
         timed(m, TS_COMPACT, all, [&] { hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, s, d); });
         if (int rc = eval_batch_async(m, net, max_games, time_eval || all)) return rc;
     }
-    timed(m, TS_BACKUP, all, [&] { hipLaunchKernelGGL(m->gumbel_ever ? OZ_VS(k_expand_backup_g) : OZ_VSPS(k_expand_backup), dim3(d.G), dim3(64), 0, s, d, 0); });
+    timed(m, TS_BACKUP, all, [&] { hipLaunchKernelGGL(tk.expand_backup, dim3(d.G), dim3(64), 0, s, d, 0); });
     OZ_HIP(hipGetLastError());
     return OZ_OK;
 }
@@ -2308,9 +2246,10 @@ OZ_API int oz_mcts_select(oz_mcts* m) {
     std::lock_guard<std::mutex> lk(m->mu);
     OZ_REFUSE_WIDE(m, "oz_mcts_select");
     OZ_REFUSE_SOLVED(m, "oz_mcts_select");
+    TreeKernels tk;
+    if (int rc = tree_kernels(m, &tk)) return rc;
     hipSetDevice(m->device);
-    if (m->gumbel_ever) hipLaunchKernelGGL(OZ_VS(k_select_g), dim3(m->d.G), dim3(64), 0, m->stream, m->d, m->gd);
-    else hipLaunchKernelGGL(m->noise_ever ? OZ_VSPS(k_select_n) : OZ_VSPS(k_select), dim3(m->d.G), dim3(64), 0, m->stream, m->d);
+    hipLaunchKernelGGL(tk.select, dim3(m->d.G), dim3(64), 0, m->stream, m->d, m->gd);
     OZ_HIP(hipGetLastError());
     m->selected = true;
     return check_error_flag(m);
@@ -2336,11 +2275,13 @@ OZ_API int oz_mcts_backup(oz_mcts* m, const float* pi, const float* v) {
     OZ_REFUSE_WIDE(m, "oz_mcts_backup");
     OZ_REFUSE_SOLVED(m, "oz_mcts_backup");
     if (!m->selected) { oz_set_error("oz_mcts_backup: call oz_mcts_select first"); return OZ_ERR_STATE; }
+    TreeKernels tk;
+    if (int rc = tree_kernels(m, &tk)) return rc;
     hipSetDevice(m->device);
     const int G = m->d.G;
     OZ_HIP(hipMemcpyAsync(m->d.pi, pi, 4ull * G * m->d.n2, hipMemcpyHostToDevice, m->stream));
     OZ_HIP(hipMemcpyAsync(m->d.v, v, 4ull * G, hipMemcpyHostToDevice, m->stream));
-    hipLaunchKernelGGL(m->gumbel_ever ? OZ_VS(k_expand_backup_g) : OZ_VSPS(k_expand_backup), dim3(G), dim3(64), 0, m->stream, m->d, 1);
+    hipLaunchKernelGGL(tk.expand_backup, dim3(G), dim3(64), 0, m->stream, m->d, 1);
     OZ_HIP(hipGetLastError());
     m->selected = false;
     return check_error_flag(m);
@@ -2449,7 +2390,7 @@ OZ_API int oz_root_values(const int32_t* N, const double* Q, int64_t count, doub
 // (the semantics are stated in include/othellozero_amd.h, "Gumbel search"; the restatement the tests hold this against is tests/gumbel_ref.py.)
 //   * a view at depth 0, like root noise: the stored statistics are what PUCT stores, the Gumbel rule only decides which root edge a descent takes
 //     (descend_one<.., GUMBEL>), on the root the slot was armed for; deeper levels and unarmed roots are PUCT;
-//   * the one thing stored differently: the *_g expansion keeps the node's own value in header word 3 (expand_backup_one<GUMBEL>), which the
+//   * the one thing stored differently: the TV_GUMBEL expansion keeps the node's own value in header word 3 (expand_backup_one<GUMBEL>), which the
 //     completed-Q formula needs at the root -- so the option is switched on over an empty tree only;
 //   * a compile-time variant: an object that never switched it on launches the kernels it launched before this section existed.
 // arm the CURRENT roots: one wave per slot, one lane per square.  draw != 0: g from the streams (seed, ids[g], plies[g]); else g is the host's, already
@@ -3400,7 +3341,7 @@ __global__ void k_sp_roots_stagger(GamesDev gm, MctsDev t, int round, int period
 // that chooses the move keeps reading the raw counts.  A fast move of a playout cap is unarmed: never pruned.  Never in the arena.
 // VALUES (an engine that records root values, oz_selfplay_set_record_values; gm.log_values != null where it is on): the visit-weighted mean of
 // the root's Q over the raw counts goes into the move log next to the counts and from there beside the game's records.  Such an engine launches
-// instantiations of its own (k_sp_move_f in a lock-step round; the EXTRAS advance or, with no other option, k_advance_v), so the kernels of an
+// instantiations of its own (MV_FULL in a lock-step round; the AV_EXTRAS advance or, with no other option, AV_VALUES alone), so the kernels of an
 // engine without it stay the code they were, register for register.  Never in the arena.
 // GUMBEL (an engine with the Gumbel search, oz_selfplay_set_gumbel; lock-step rounds only): the round's roots kernel is followed by k_gumbel_arm,
 // so the root of every active slot with a legal move is armed.  Where the coin falls on its greedy branch the move is the Gumbel root's
@@ -3415,7 +3356,7 @@ struct GumbelPlay {
 // SURPRISE (an engine that records policy surprise, oz_selfplay_set_record_surprise; "policy surprise weighting" in the header): s = KL(q || p)
 // of the move's search, q the row that becomes the policy target (the pruned count row at T = 1, normalised as k_expand_visits does; under GUMBEL
 // the float32 improved-policy row) and p the root's stored priors, goes into the move log and from there beside the game's records, as the
-// root value does.  Instantiations of its own (k_sp_move_fs / k_sp_move_gs, the *_xs advance): every other kernel stays the code it was.
+// root value does.  Instantiations of its own (MV_SURPRISE, AV_SURPRISE): every other kernel stays the code it was.
 // Never in the arena.
 struct SurprisePlay {
     double* log;                           // [G][64 plies]
@@ -3425,7 +3366,7 @@ struct SurprisePlay {
 // slot's (side, streak) take the move's root value -- the VALUES rootv, no second routine -- through oz_resign_step (oz_common.h).  At the first
 // trigger of a game that is not exempt, where the move does not end the game by itself, the game ends through the `fin` branch with the winner
 // overridden and pad[1] = 1 in its records; an exempt game remembers its first trigger and is counted at its natural end.  Lane 0 resets the
-// slot's state where the game ends.  Instantiations of its own (k_sp_move_r / k_sp_move_rs): every other kernel stays the code it was.  Never
+// slot's state where the game ends.  Instantiations of its own (MV_RESIGN): every other kernel stays the code it was.  Never
 // in the arena.
 struct ResignPlay {
     double v, keep_prob;
@@ -3444,7 +3385,7 @@ __device__ __noinline__ double surprise_row_sum(const double* a) { return pairwi
 // (oz_common.h): `row` is the raw count on the kept squares, and everything that reads `row` -- log_counts / visits, SURPRISE, and here every
 // branch of the move that reads counts -- reads it and its maximum; rootv is the exact value where it is known (VALUES logs it, RESIGN reads it);
 // the proof code goes into the move log and from there into byte pad[2] of the game's records.  The explore branch of the coin stays uniform
-// over the legal set and last_counts stays raw.  Instantiations of its own (k_sp_move_p*): every other kernel stays the code it was.
+// over the legal set and last_counts stays raw.  Instantiations of its own (MV_PROVEN): every other kernel stays the code it was.
 struct ProofPlay {
     uint8_t* log;                          // [G][64 plies] the proof code of every ply of the game in progress; null in the arena
     unsigned long long* stat;              // [4] proven roots, rows changed, moves changed, fallbacks; null in the arena
@@ -3726,52 +3667,33 @@ __device__ __forceinline__ void sp_move_body(const GamesDev& gm, const MctsDev& 
         t.root_node[g] = -1;                               // the position changed: the next descent looks its root up again
     }
 }
-__global__ __launch_bounds__(64) void k_sp_move(GamesDev gm, MctsDev t, int arena) { sp_move_body(gm, t, blockIdx.x, threadIdx.x, arena); }
-// the self-play move of an engine with move sampling (lock-step rounds; the arena keeps k_sp_move)
-__global__ __launch_bounds__(64) void k_sp_move_s(GamesDev gm, MctsDev t, MoveSampling ms) { sp_move_body<false, true>(gm, t, blockIdx.x, threadIdx.x, 0, ms); }
-// the self-play move of a lock-step round under a playout cap (with or without move sampling: ms.plies says)
-__global__ __launch_bounds__(64) void k_sp_move_c(GamesDev gm, MctsDev t, MoveSampling ms, PlayoutCap pc) {
-    sp_move_body<false, true, true>(gm, t, blockIdx.x, threadIdx.x, 0, ms, pc);
-}
-// the self-play move of a lock-step round of an engine with forced playouts or recorded root values (with or without move sampling and a
-// playout cap: ms.plies and pc.fast_sims say; a staggered round passes a cap that is off; fp.k == 0: no forcing)
-__global__ __launch_bounds__(64) void k_sp_move_f(GamesDev gm, MctsDev t, MoveSampling ms, PlayoutCap pc, ForcedPlayouts fp) {
-    sp_move_body<false, true, true, true, true>(gm, t, blockIdx.x, threadIdx.x, 0, ms, pc, fp);
-}
-// the self-play move of a lock-step round of an engine with the Gumbel search (with or without recorded root values: gm.log_values says)
-__global__ __launch_bounds__(64) void k_sp_move_g(GamesDev gm, MctsDev t, GumbelPlay gp) {
-    sp_move_body<false, false, false, false, true, true>(gm, t, blockIdx.x, threadIdx.x, 0, MoveSampling{}, PlayoutCap{}, ForcedPlayouts{}, gp);
-}
-// (the *s kernels: k_sp_move_f and k_sp_move_g whose move records its policy surprise, launched by engines with record_surprise)
-__global__ __launch_bounds__(64) void k_sp_move_fs(GamesDev gm, MctsDev t, MoveSampling ms, PlayoutCap pc, ForcedPlayouts fp, SurprisePlay su) {
-    sp_move_body<false, true, true, true, true, false, true>(gm, t, blockIdx.x, threadIdx.x, 0, ms, pc, fp, GumbelPlay{}, su);
-}
-__global__ __launch_bounds__(64) void k_sp_move_gs(GamesDev gm, MctsDev t, GumbelPlay gp, SurprisePlay su) {
-    sp_move_body<false, false, false, false, true, true, true>(gm, t, blockIdx.x, threadIdx.x, 0, MoveSampling{}, PlayoutCap{}, ForcedPlayouts{}, gp, su);
-}
-// (the *r kernels: k_sp_move_f and k_sp_move_fs whose move applies the resignation rule, launched by engines with oz_selfplay_set_resign)
-__global__ __launch_bounds__(64) void k_sp_move_r(GamesDev gm, MctsDev t, MoveSampling ms, PlayoutCap pc, ForcedPlayouts fp, ResignPlay rs) {
-    sp_move_body<false, true, true, true, true, false, false, true>(gm, t, blockIdx.x, threadIdx.x, 0, ms, pc, fp, GumbelPlay{}, SurprisePlay{}, rs);
-}
-__global__ __launch_bounds__(64) void k_sp_move_rs(GamesDev gm, MctsDev t, MoveSampling ms, PlayoutCap pc, ForcedPlayouts fp, SurprisePlay su, ResignPlay rs) {
-    sp_move_body<false, true, true, true, true, false, true, true>(gm, t, blockIdx.x, threadIdx.x, 0, ms, pc, fp, GumbelPlay{}, su, rs);
-}
-// (the *p kernels: k_sp_move_f, _fs, _r and _rs whose move plays and records what a proven root knows, launched by engines with
-// oz_selfplay_set_proof_play; k_sp_move_pa: k_sp_move of an arena agent with oz_arena_set_proof_play)
-__global__ __launch_bounds__(64) void k_sp_move_p(GamesDev gm, MctsDev t, MoveSampling ms, PlayoutCap pc, ForcedPlayouts fp, ProofPlay pp) {
-    sp_move_body<false, true, true, true, true, false, false, false, true>(gm, t, blockIdx.x, threadIdx.x, 0, ms, pc, fp, GumbelPlay{}, SurprisePlay{}, ResignPlay{}, pp);
-}
-__global__ __launch_bounds__(64) void k_sp_move_ps(GamesDev gm, MctsDev t, MoveSampling ms, PlayoutCap pc, ForcedPlayouts fp, SurprisePlay su, ProofPlay pp) {
-    sp_move_body<false, true, true, true, true, false, true, false, true>(gm, t, blockIdx.x, threadIdx.x, 0, ms, pc, fp, GumbelPlay{}, su, ResignPlay{}, pp);
-}
-__global__ __launch_bounds__(64) void k_sp_move_pr(GamesDev gm, MctsDev t, MoveSampling ms, PlayoutCap pc, ForcedPlayouts fp, ResignPlay rs, ProofPlay pp) {
-    sp_move_body<false, true, true, true, true, false, false, true, true>(gm, t, blockIdx.x, threadIdx.x, 0, ms, pc, fp, GumbelPlay{}, SurprisePlay{}, rs, pp);
-}
-__global__ __launch_bounds__(64) void k_sp_move_prs(GamesDev gm, MctsDev t, MoveSampling ms, PlayoutCap pc, ForcedPlayouts fp, SurprisePlay su, ResignPlay rs, ProofPlay pp) {
-    sp_move_body<false, true, true, true, true, false, true, true, true>(gm, t, blockIdx.x, threadIdx.x, 0, ms, pc, fp, GumbelPlay{}, su, rs, pp);
-}
-__global__ __launch_bounds__(64) void k_sp_move_pa(GamesDev gm, MctsDev t) {
-    sp_move_body<false, false, false, false, false, false, false, false, true>(gm, t, blockIdx.x, threadIdx.x, 1);
+// ---- the move kernel of the lock-step rounds and the arena: one template, instantiated per variant.  M is a mask of MV_* flags; move_kernel()
+// (host side) computes it from the engine's state, fills the arguments and is the one place that says which masks have a kernel.
+//   flag          option (what sets it)                                              template argument of sp_move_body (described above it)
+//   MV_SAMPLE     move sampling (oz_selfplay_set_move_sampling); a.ms.plies == 0: off     SAMPLE
+//   MV_CAP        a playout cap (oz_selfplay_set_playout_cap); a.pc.fast_sims == 0: off   CAP     (a staggered round passes a cap that is off)
+//   MV_FORCE      forced playouts (oz_selfplay_set_forced_playouts); a.fp.k == 0: off     FORCE
+//   MV_VALUES     recorded root values (oz_selfplay_set_record_values); gm.log_values     VALUES
+//   MV_GUMBEL     the Gumbel search (oz_selfplay_set_gumbel): a.gp                        GUMBEL
+//   MV_SURPRISE   recorded policy surprise (oz_selfplay_set_record_surprise): a.su        SURPRISE
+//   MV_RESIGN     resignation (oz_selfplay_set_resign): a.rs                              RESIGN  (reads the VALUES root value)
+//   MV_PROVEN     proof play (oz_selfplay_set_proof_play / oz_arena_set_proof_play): a.pp PROVEN  (a.pp is null in the arena)
+// MV_FULL is what every self-play engine with forced playouts, recorded values, recorded surprise, resignation or proof play launches: those
+// options are looked at when the move runs, so their combinations need no kernels of their own.  NOISE is the free-running advance's alone.
+enum : unsigned { MV_SAMPLE = 1, MV_CAP = 2, MV_FORCE = 4, MV_VALUES = 8, MV_GUMBEL = 16, MV_SURPRISE = 32, MV_RESIGN = 64, MV_PROVEN = 128,
+                  MV_FULL = MV_SAMPLE | MV_CAP | MV_FORCE | MV_VALUES };
+// a default-constructed member is an option that is off.  (What MV_FULL and its combinations read comes first and packed, as those kernels
+// always took it, the Gumbel state behind: the order at which every instantiation keeps the registers of the kernel it replaced.)
+struct MoveArgs {
+    MoveSampling ms; PlayoutCap pc; ForcedPlayouts fp; SurprisePlay su; ResignPlay rs; ProofPlay pp; GumbelPlay gp;
+    int arena;                             // != 0: agents.py semantics
+};
+template <unsigned M>
+__global__ __launch_bounds__(64) void k_sp_move(GamesDev gm, MctsDev t, MoveArgs a) {
+    // (the plain move alone serves self-play and the arena; MV_PROVEN by itself is the arena's, everything else self-play's: the flag folds away)
+    const int arena = M == 0 ? a.arena : M == MV_PROVEN ? 1 : 0;
+    sp_move_body<false, has(M, MV_SAMPLE), has(M, MV_CAP), has(M, MV_FORCE), has(M, MV_VALUES), has(M, MV_GUMBEL), has(M, MV_SURPRISE), has(M, MV_RESIGN),
+                 has(M, MV_PROVEN)>(gm, t, blockIdx.x, threadIdx.x, arena, a.ms, a.pc, a.fp, a.gp, a.su, a.rs, a.pp);
 }
 
 // ---------------------------------------------------------------- free-running self-play step
@@ -3792,7 +3714,7 @@ __global__ __launch_bounds__(64) void k_sp_move_pa(GamesDev gm, MctsDev t) {
 // EXTRAS: the one instantiation for engines with root noise, move sampling, a playout cap or any of them together; which of them is on is looked
 // at when it runs (t.noise_eps > 0, xt.sample.plies > 0, xt.cap.fast_sims > 0).  An engine with none launches the EXTRAS = false kernels, which
 // are the code they were before.  VALUES: the move records root values where gm.log_values is set (sp_move_body<.., VALUES>); part of EXTRAS,
-// and on its own the instantiation of an engine whose only option it is (k_advance_v: the plain kernels plus the move's value, not the
+// and on its own the instantiation of an engine whose only option it is (AV_VALUES alone: the plain kernels plus the move's value, not the
 // registers of every extra).
 //   playout cap: the move is played once `done` reaches the budget of the slot's current (game id, ply) instead of `sims`; a fast root draws no
 //   noise.  Both are oz_playout_budget of the key, evaluated again at every pass of the loop: noise_armed[g] == 0 keeps meaning "no noise on this
@@ -3852,67 +3774,29 @@ __device__ __forceinline__ void advance_body(const GamesDev& gm, const MctsDev& 
     }
     if (lane == 0) sims_done[g] = done;
 }
-template <int VS = OZ_VSIGNS_REFERENCE>
-__global__ __launch_bounds__(64) void k_advance(GamesDev gm, MctsDev t, int sims, int* __restrict__ sims_done, int cap) {
+// ---- the free-running kernels: one template per phase, instantiated per variant.  A is a mask of AV_* flags; advance_kernels() (host side)
+// computes it from the engine's state, fills the arguments and is the one place that says which masks have a kernel.
+//   flag          option (what sets it)                                                    template argument of advance_body (described above it)
+//   AV_SIGNS      the low two bits ARE the OZ_VSIGNS_* value (REFERENCE or SOUND: no proofs)   VS
+//   AV_EXTRAS     root noise, move sampling, a playout cap, recorded surprise: any of them     EXTRAS (each is looked at when it runs: a.xt)
+//   AV_VALUES     recorded root values; every AV_EXTRAS kernel has it                          VALUES (gm.log_values says whether it records)
+//   AV_SURPRISE   recorded policy surprise; on top of AV_EXTRAS                                SURPRISE (a.su)
+enum : unsigned { AV_SIGNS = 3, AV_EXTRAS = 4, AV_VALUES = 8, AV_SURPRISE = 16 };
+// a default-constructed xt / su is an option that is off
+struct AdvanceArgs { SelfplayExtras xt; SurprisePlay su; };
+template <unsigned A>
+__global__ __launch_bounds__(64) void k_advance(GamesDev gm, MctsDev t, int sims, int* __restrict__ sims_done, int cap, AdvanceArgs a) {
     __shared__ TreeLds L;
-    advance_body<false, false, false, VS>(gm, t, L, blockIdx.x, threadIdx.x, sims, sims_done, cap);
+    advance_body<has(A, AV_EXTRAS), has(A, AV_VALUES), has(A, AV_SURPRISE), int(A & AV_SIGNS)>(gm, t, L, blockIdx.x, threadIdx.x, sims, sims_done, cap, a.xt, a.su);
 }
 // expand + backup of the leaves the previous batch evaluated and the advance to the next batch's leaves in ONE launch (the free-running
 // counterpart of k_backup_select: one kernel boundary less per batch, the records just written are re-read from the CU's cache)
-template <int VS = OZ_VSIGNS_REFERENCE>
-__global__ __launch_bounds__(64) void k_backup_advance(GamesDev gm, MctsDev t, int sims, int* __restrict__ sims_done, int cap) {
+template <unsigned A>
+__global__ __launch_bounds__(64) void k_backup_advance(GamesDev gm, MctsDev t, int sims, int* __restrict__ sims_done, int cap, AdvanceArgs a) {
     __shared__ TreeLds L;
-    expand_backup_body<false, VS>(t, L, blockIdx.x, threadIdx.x, 0);
-    wave_sync();
-    __syncthreads();
-    advance_body<false, false, false, VS>(gm, t, L, blockIdx.x, threadIdx.x, sims, sims_done, cap);
-}
-
-// (the *_x kernels: the same kernels over the EXTRAS = true bodies, launched by engines with root noise or move sampling)
-template <int VS = OZ_VSIGNS_REFERENCE>
-__global__ __launch_bounds__(64) void k_advance_x(GamesDev gm, MctsDev t, int sims, int* __restrict__ sims_done, int cap, SelfplayExtras xt) {
-    __shared__ TreeLds L;
-    advance_body<true, true, false, VS>(gm, t, L, blockIdx.x, threadIdx.x, sims, sims_done, cap, xt);
-}
-template <int VS = OZ_VSIGNS_REFERENCE>
-__global__ __launch_bounds__(64) void k_backup_advance_x(GamesDev gm, MctsDev t, int sims, int* __restrict__ sims_done, int cap, SelfplayExtras xt) {
-    __shared__ TreeLds L;
-    expand_backup_body<false, VS>(t, L, blockIdx.x, threadIdx.x, 0);
-    wave_sync();
-    __syncthreads();
-    advance_body<true, true, false, VS>(gm, t, L, blockIdx.x, threadIdx.x, sims, sims_done, cap, xt);
-}
-
-// (the *_xs kernels: the EXTRAS kernels whose move records its policy surprise, launched by engines with record_surprise -- with or without
-// any other extra: each is looked at when it runs)
-template <int VS = OZ_VSIGNS_REFERENCE>
-__global__ __launch_bounds__(64) void k_advance_xs(GamesDev gm, MctsDev t, int sims, int* __restrict__ sims_done, int cap, SelfplayExtras xt, SurprisePlay su) {
-    __shared__ TreeLds L;
-    advance_body<true, true, true, VS>(gm, t, L, blockIdx.x, threadIdx.x, sims, sims_done, cap, xt, su);
-}
-template <int VS = OZ_VSIGNS_REFERENCE>
-__global__ __launch_bounds__(64) void k_backup_advance_xs(GamesDev gm, MctsDev t, int sims, int* __restrict__ sims_done, int cap, SelfplayExtras xt,
-                                                          SurprisePlay su) {
-    __shared__ TreeLds L;
-    expand_backup_body<false, VS>(t, L, blockIdx.x, threadIdx.x, 0);
-    wave_sync();
-    __syncthreads();
-    advance_body<true, true, true, VS>(gm, t, L, blockIdx.x, threadIdx.x, sims, sims_done, cap, xt, su);
-}
-
-// (the *_v kernels: the plain kernels whose move records root values, launched by engines with record_values and no other extra)
-template <int VS = OZ_VSIGNS_REFERENCE>
-__global__ __launch_bounds__(64) void k_advance_v(GamesDev gm, MctsDev t, int sims, int* __restrict__ sims_done, int cap) {
-    __shared__ TreeLds L;
-    advance_body<false, true, false, VS>(gm, t, L, blockIdx.x, threadIdx.x, sims, sims_done, cap);
-}
-template <int VS = OZ_VSIGNS_REFERENCE>
-__global__ __launch_bounds__(64) void k_backup_advance_v(GamesDev gm, MctsDev t, int sims, int* __restrict__ sims_done, int cap) {
-    __shared__ TreeLds L;
-    expand_backup_body<false, VS>(t, L, blockIdx.x, threadIdx.x, 0);
-    wave_sync();
-    __syncthreads();
-    advance_body<false, true, false, VS>(gm, t, L, blockIdx.x, threadIdx.x, sims, sims_done, cap);
+    expand_backup_body<false, int(A & AV_SIGNS)>(t, L, blockIdx.x, threadIdx.x, 0);
+    backup_fence();
+    advance_body<has(A, AV_EXTRAS), has(A, AV_VALUES), has(A, AV_SURPRISE), int(A & AV_SIGNS)>(gm, t, L, blockIdx.x, threadIdx.x, sims, sims_done, cap, a.xt, a.su);
 }
 
 // RandomOthelloAgent.play (agents.py:20-24) for every live game whose mover is `side`: random.choice over the valid
@@ -4117,6 +4001,38 @@ static void selfplay_attach_cache(oz_selfplay* sp) {
     sp->m->d.ec = (sp->cfg.eval_cache && sp->net->ec.buckets && sp->net->ec.n2 == sp->m->d.n2) ? sp->net->ec : EvalCacheDev();
 }
 
+// the move kernel of the engine as it is now, with its arguments.  agent < 0: a self-play round (capped: under the engine's playout cap; a
+// staggered round is not); agent 0 / 1: that agent's move in the arena (agents.py semantics, no option but proof play).  THE list of the
+// variants that exist.
+typedef void (*MoveKernel)(GamesDev, MctsDev, MoveArgs);
+static int move_kernel(const oz_selfplay* sp, const oz_mcts* m, int agent, bool capped, MoveKernel* k, MoveArgs* a) {
+    unsigned v = 0;
+    *a = MoveArgs{};
+    if (agent >= 0) {
+        a->arena = 1;
+        v = sp->arena_proof_play[agent] ? MV_PROVEN : 0;
+    } else {
+        a->ms = sp->sample; a->pc = capped ? sp->cap : PlayoutCap{}; a->fp = sp->forced; a->su = sp->su; a->rs = sp->resign; a->pp = sp->pplay;
+        if (sp->gumbel_on) a->gp = GumbelPlay{m->gd, sp->gumbel_log, sp->gumbel_rows, sp->gumbel_moves};
+        v = (sp->proof_play && m->proofs ? MV_PROVEN : 0) | (sp->resign.r > 0 ? MV_RESIGN : 0) | (sp->su.log ? MV_SURPRISE : 0);
+        if (sp->gumbel_on) v |= MV_VALUES | MV_GUMBEL;                                  // (it replaces move sampling, forced playouts and the cap)
+        else if (v || sp->forced.k > 0.0 || sp->gm.log_values) v |= MV_FULL;
+        else if (capped) v = MV_SAMPLE | MV_CAP;                                        // (with or without move sampling: ms.plies says)
+        else if (sp->sample.plies > 0) v = MV_SAMPLE;
+    }
+    switch (v) {
+#define OZ_M(...) case (__VA_ARGS__): *k = k_sp_move<(__VA_ARGS__)>; return OZ_OK
+        OZ_M(0); OZ_M(MV_SAMPLE); OZ_M(MV_SAMPLE | MV_CAP); OZ_M(MV_FULL);
+        OZ_M(MV_FULL | MV_SURPRISE); OZ_M(MV_FULL | MV_RESIGN); OZ_M(MV_FULL | MV_SURPRISE | MV_RESIGN);
+        OZ_M(MV_FULL | MV_PROVEN); OZ_M(MV_FULL | MV_SURPRISE | MV_PROVEN); OZ_M(MV_FULL | MV_RESIGN | MV_PROVEN); OZ_M(MV_FULL | MV_SURPRISE | MV_RESIGN | MV_PROVEN);
+        OZ_M(MV_VALUES | MV_GUMBEL); OZ_M(MV_VALUES | MV_GUMBEL | MV_SURPRISE);
+        OZ_M(MV_PROVEN);                                                                // (the arena's)
+#undef OZ_M
+    }
+    oz_set_error("no move kernel for this combination of options (variant 0x%x)", v);
+    return OZ_ERR_STATE;
+}
+
 // one move round on m->stream: roots, `sims` lock-step simulations, move.  stagger_round >= 0: only slots whose start
 // offset (oz_selfplay_stagger) is still ahead of that round take part.  With leaves_per_step > 1 the round synchronises the stream once (the
 // 4-byte budget read-back of mcts_wide_steps): the lock-step drivers are then no longer asynchronous.
@@ -4147,23 +4063,10 @@ static int selfplay_round_async(oz_selfplay* sp, int sims, int stagger_round) {
             hipLaunchKernelGGL(k_cap_resume, gg, dim3(256), 0, s, m->d, (const uint8_t*)sp->gm.finished);
         }
     } else if (int rc = mcts_steps_async(m, sp->net, sims, G, true, capped ? &ck : nullptr)) return rc;
-    timed(m, TS_MOVE, m->profile, [&] {
-        const PlayoutCap pcap = capped ? sp->cap : PlayoutCap{0, 0.0, nullptr, nullptr};
-        const bool pplay = sp->proof_play && m->proofs;
-        if (pplay && sp->resign.r > 0 && sp->su.log) hipLaunchKernelGGL(k_sp_move_prs, dim3(G), dim3(64), 0, s, sp->gm, m->d, sp->sample, pcap, sp->forced, sp->su, sp->resign, sp->pplay);
-        else if (pplay && sp->resign.r > 0) hipLaunchKernelGGL(k_sp_move_pr, dim3(G), dim3(64), 0, s, sp->gm, m->d, sp->sample, pcap, sp->forced, sp->resign, sp->pplay);
-        else if (pplay && sp->su.log) hipLaunchKernelGGL(k_sp_move_ps, dim3(G), dim3(64), 0, s, sp->gm, m->d, sp->sample, pcap, sp->forced, sp->su, sp->pplay);
-        else if (pplay) hipLaunchKernelGGL(k_sp_move_p, dim3(G), dim3(64), 0, s, sp->gm, m->d, sp->sample, pcap, sp->forced, sp->pplay);
-        else if (sp->resign.r > 0 && sp->su.log) hipLaunchKernelGGL(k_sp_move_rs, dim3(G), dim3(64), 0, s, sp->gm, m->d, sp->sample, capped ? sp->cap : PlayoutCap{0, 0.0, nullptr, nullptr}, sp->forced, sp->su, sp->resign);
-        else if (sp->resign.r > 0) hipLaunchKernelGGL(k_sp_move_r, dim3(G), dim3(64), 0, s, sp->gm, m->d, sp->sample, capped ? sp->cap : PlayoutCap{0, 0.0, nullptr, nullptr}, sp->forced, sp->resign);
-        else if (sp->su.log && sp->gumbel_on) hipLaunchKernelGGL(k_sp_move_gs, dim3(G), dim3(64), 0, s, sp->gm, m->d, GumbelPlay{m->gd, sp->gumbel_log, sp->gumbel_rows, sp->gumbel_moves}, sp->su);
-        else if (sp->su.log) hipLaunchKernelGGL(k_sp_move_fs, dim3(G), dim3(64), 0, s, sp->gm, m->d, sp->sample, capped ? sp->cap : PlayoutCap{0, 0.0, nullptr, nullptr}, sp->forced, sp->su);
-        else if (sp->gumbel_on) hipLaunchKernelGGL(k_sp_move_g, dim3(G), dim3(64), 0, s, sp->gm, m->d, GumbelPlay{m->gd, sp->gumbel_log, sp->gumbel_rows, sp->gumbel_moves});
-        else if (sp->forced.k > 0.0 || sp->gm.log_values) hipLaunchKernelGGL(k_sp_move_f, dim3(G), dim3(64), 0, s, sp->gm, m->d, sp->sample, capped ? sp->cap : PlayoutCap{0, 0.0, nullptr, nullptr}, sp->forced);
-        else if (capped) hipLaunchKernelGGL(k_sp_move_c, dim3(G), dim3(64), 0, s, sp->gm, m->d, sp->sample, sp->cap);
-        else if (sp->sample.plies > 0) hipLaunchKernelGGL(k_sp_move_s, dim3(G), dim3(64), 0, s, sp->gm, m->d, sp->sample);
-        else hipLaunchKernelGGL(k_sp_move, dim3(G), dim3(64), 0, s, sp->gm, m->d, 0);
-    });
+    MoveKernel move;
+    MoveArgs margs;
+    if (int rc = move_kernel(sp, m, -1, capped, &move, &margs)) return rc;
+    timed(m, TS_MOVE, m->profile, [&] { hipLaunchKernelGGL(move, dim3(G), dim3(64), 0, s, sp->gm, m->d, margs); });
     OZ_HIP(hipGetLastError());
     if (m->timer.backlog() > 4096) m->timer.drain();      // completed pairs only: never a host stall inside the enqueue loop
     return OZ_OK;
@@ -4685,6 +4588,37 @@ OZ_API int oz_selfplay_root_noise(oz_selfplay* sp, double* eta, uint8_t* armed) 
     return noise_read_locked(sp->m, eta, armed);
 }
 
+// the free-running kernels of the engine as it is now -- a call's first advance, every further batch's (the batch before backed up in the same
+// launch), the closing expand + backup -- with the arguments that do not change from batch to batch.  THE list of the variants that exist:
+// plain, recorded values alone, the extras, the extras with recorded surprise, each under the reference's and the sound signs; what the
+// free-running driver does not run at all, oz_selfplay_run_steps refuses by name before it gets here.
+struct AdvanceKernels {
+    void (*advance)(GamesDev, MctsDev, int, int*, int, AdvanceArgs);
+    void (*backup_advance)(GamesDev, MctsDev, int, int*, int, AdvanceArgs);
+    void (*expand_backup)(MctsDev, int);
+};
+static int advance_kernels(const oz_selfplay* sp, AdvanceKernels* k, AdvanceArgs* a) {
+    const oz_mcts* m = sp->m;
+    const bool surprise = sp->su.log != nullptr;
+    const bool extras = surprise || m->noise_ever || sp->sample.plies > 0 || sp->cap.fast_sims > 0;
+    *a = AdvanceArgs{};
+    if (extras) a->xt = SelfplayExtras{sp->noise_alpha, sp->gm.seed, sp->sample, sp->cap, sp->forced};
+    if (surprise) a->su = sp->su;
+    const unsigned signs = m->proofs ? OZ_VSIGNS_PROVEN : m->vsigns != OZ_VSIGNS_REFERENCE ? OZ_VSIGNS_SOUND : OZ_VSIGNS_REFERENCE;
+    const unsigned v = signs | (extras ? AV_EXTRAS : 0) | (extras || sp->gm.log_values ? AV_VALUES : 0) | (surprise ? AV_SURPRISE : 0);
+    switch (v) {
+#define OZ_A(...) \
+    case (__VA_ARGS__): *k = AdvanceKernels{k_advance<(__VA_ARGS__)>, k_backup_advance<(__VA_ARGS__)>, k_expand_backup<(__VA_ARGS__) & AV_SIGNS>}; return OZ_OK
+        OZ_A(OZ_VSIGNS_REFERENCE); OZ_A(OZ_VSIGNS_REFERENCE | AV_VALUES); OZ_A(OZ_VSIGNS_REFERENCE | AV_EXTRAS | AV_VALUES);
+        OZ_A(OZ_VSIGNS_REFERENCE | AV_EXTRAS | AV_VALUES | AV_SURPRISE);
+        OZ_A(OZ_VSIGNS_SOUND); OZ_A(OZ_VSIGNS_SOUND | AV_VALUES); OZ_A(OZ_VSIGNS_SOUND | AV_EXTRAS | AV_VALUES);
+        OZ_A(OZ_VSIGNS_SOUND | AV_EXTRAS | AV_VALUES | AV_SURPRISE);
+#undef OZ_A
+    }
+    oz_set_error("oz_selfplay_run_steps: the free-running driver has no kernels for this combination of options (variant 0x%x); use oz_selfplay_run", v);
+    return OZ_ERR_STATE;
+}
+
 OZ_API int oz_selfplay_run_steps(oz_selfplay* sp, int steps) {
     OZ_REQUIRE(sp, "null selfplay");
     std::lock_guard<std::mutex> lk(sp->mu);
@@ -4705,7 +4639,9 @@ OZ_API int oz_selfplay_run_steps(oz_selfplay* sp, int steps) {
     if (sp->mode == 1 && m->noise_ever) OZ_HIP(hipMemsetAsync(d.noise_armed, 0, (size_t)d.G, m->stream));     // ... and the last round's noise is that of the roots before its moves
     sp->mode = 2;
     selfplay_attach_cache(sp);
-    const bool fuse = true;
+    AdvanceKernels ak;
+    AdvanceArgs aargs;
+    if (int rc = advance_kernels(sp, &ak, &aargs)) return rc;
     for (int i = 0; i < steps; ++i) {
         const bool all = m->profile;
         hipStream_t s = m->stream;
@@ -4713,21 +4649,7 @@ OZ_API int oz_selfplay_run_steps(oz_selfplay* sp, int steps) {
         // enough to keep the batches full and the launch is as short as the lock-step one (measured: +1.2 % expansions/s, +3 % games/s over 2)
         const int adv_cap = (sp->batch_cap > 0 && sp->batch_cap < d.G ? 1 : OZ_ADVANCE_CAP);
         // (from the second batch of a call on, the previous batch's expand + backup rides in the same launch; one closing k_expand_backup per call)
-        timed(m, TS_SELECT, all, [&] {
-            if (sp->su.log) {
-                const SelfplayExtras xt{sp->noise_alpha, sp->gm.seed, sp->sample, sp->cap, sp->forced};
-                if (fuse && i > 0) hipLaunchKernelGGL(OZ_VS(k_backup_advance_xs), dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap, xt, sp->su);
-                else hipLaunchKernelGGL(OZ_VS(k_advance_xs), dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap, xt, sp->su);
-            } else if (m->noise_ever || sp->sample.plies > 0 || sp->cap.fast_sims > 0) {
-                const SelfplayExtras xt{sp->noise_alpha, sp->gm.seed, sp->sample, sp->cap, sp->forced};
-                if (fuse && i > 0) hipLaunchKernelGGL(OZ_VS(k_backup_advance_x), dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap, xt);
-                else hipLaunchKernelGGL(OZ_VS(k_advance_x), dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap, xt);
-            } else if (sp->gm.log_values) {
-                if (fuse && i > 0) hipLaunchKernelGGL(OZ_VS(k_backup_advance_v), dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap);
-                else hipLaunchKernelGGL(OZ_VS(k_advance_v), dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap);
-            } else if (fuse && i > 0) hipLaunchKernelGGL(OZ_VS(k_backup_advance), dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap);
-            else hipLaunchKernelGGL(OZ_VS(k_advance), dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap);
-        });
+        timed(m, TS_SELECT, all, [&] { hipLaunchKernelGGL(i == 0 ? ak.advance : ak.backup_advance, dim3(d.G), dim3(64), 0, s, sp->gm, d, sp->cfg.sims, sp->d_sims_done, adv_cap, aargs); });
         MctsDev dc = d;                                    // this batch's cap and slot order (the kernels take the struct by value)
         const int cap = sp->batch_cap > 0 && sp->batch_cap < d.G ? sp->batch_cap : 0;
         dc.batch_cap = cap;
@@ -4736,7 +4658,7 @@ OZ_API int oz_selfplay_run_steps(oz_selfplay* sp, int steps) {
         timed(m, TS_COMPACT, all, [&] { hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, s, dc); });
         // (the network's launches are sized for the cap: it picks its tile shapes from the batch it is asked to hold)
         if (int rc = eval_batch_async(m, sp->net, cap ? cap : d.G, true)) return rc;
-        if (!fuse || i == steps - 1) timed(m, TS_BACKUP, all, [&] { hipLaunchKernelGGL(OZ_VS(k_expand_backup), dim3(d.G), dim3(64), 0, s, d, 0); });
+        if (i == steps - 1) timed(m, TS_BACKUP, all, [&] { hipLaunchKernelGGL(ak.expand_backup, dim3(d.G), dim3(64), 0, s, d, 0); });
         OZ_HIP(hipGetLastError());
         if (m->timer.backlog() > 4096) m->timer.drain();      // completed pairs only: never a host stall inside the enqueue loop
     }
@@ -5856,14 +5778,15 @@ OZ_API int oz_arena_run_rounds(oz_arena* a, int max_rounds_arg) {
             rc = mcts_steps_async(mb, a->nb, a->sims, movers[1], false);
         }
         if (rc) break;
-        if (run_a) timed(ma, TS_MOVE, ma->profile, [&] {
-            if (sp->arena_proof_play[0]) hipLaunchKernelGGL(k_sp_move_pa, dim3(G), dim3(64), 0, s, sp->gm, ma->d);
-            else hipLaunchKernelGGL(k_sp_move, dim3(G), dim3(64), 0, s, sp->gm, ma->d, 1);
-        });
-        if (run_b) timed(mb, TS_MOVE, mb->profile, [&] {
-            if (sp->arena_proof_play[1]) hipLaunchKernelGGL(k_sp_move_pa, dim3(G), dim3(64), 0, s, sp->gm, mb->d);
-            else hipLaunchKernelGGL(k_sp_move, dim3(G), dim3(64), 0, s, sp->gm, mb->d, 1);
-        });
+        oz_mcts* const movers_m[2] = {run_a ? ma : nullptr, run_b ? mb : nullptr};
+        for (int agent = 0; agent < 2 && !rc; ++agent) {
+            oz_mcts* mm = movers_m[agent];
+            MoveKernel move;
+            MoveArgs margs;
+            if (!mm || (rc = move_kernel(sp, mm, agent, false, &move, &margs))) continue;
+            timed(mm, TS_MOVE, mm->profile, [&] { hipLaunchKernelGGL(move, dim3(G), dim3(64), 0, s, sp->gm, mm->d, margs); });
+        }
+        if (rc) break;
         if (hipGetLastError() != hipSuccess) { oz_set_error("arena kernel launch failed"); rc = OZ_ERR_HIP; break; }
         if ((round & 3) == 3 || round + 1 == max_rounds) {
             if ((rc = check_error_flag(ma))) break;

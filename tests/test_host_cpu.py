@@ -425,12 +425,14 @@ def test_profile_summaries_label_layers_by_launch_order(tmp_path):
     sp = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(sp)
     commit = ["k_gemm_h2<H2BigPP>"] * 9
-    stagger = ["k_select", "k_compact", "k_lut_ids", "k_conv2_lut_xcd<8, true>", "k_gemm_h2<H2MidPP>", "k_gemm_h2<H2BigPP>", "k_gemm_h2<H2BigPP>",
+    stagger = ["k_select<0u>", "k_compact", "k_lut_ids", "k_conv2_lut_xcd<8, true>", "k_gemm_h2<H2MidPP>", "k_gemm_h2<H2BigPP>", "k_gemm_h2<H2BigPP>",
                "k_splitk_reduce_h2", "k_gemm_h2<H2Thin4w>", "k_heads_lds"]
-    timed = ["k_backup_advance", "k_compact", "k_lut_ids", "k_conv2_lut_xcd<8, true>", "k_gemm_h2<H2BigPP>", "k_gemm_h2<H2BigPP>", "k_gemm_h2<H2BigPP>",
+    timed = ["k_backup_advance<0u>", "k_compact", "k_lut_ids", "k_conv2_lut_xcd<8, true>", "k_gemm_h2<H2BigPP>", "k_gemm_h2<H2BigPP>", "k_gemm_h2<H2BigPP>",
              "k_splitk_reduce_h2", "k_gemm_h2<H2Thin4w>", "k_heads_lds"]
     seq = commit + stagger * 5 + timed * 3
     lab = sp.label_layers(seq)
+    bid = sp.batch_ids(seq)                                               # (the tree kernels are templates: a batch opens at the name before "<")
+    assert bid[:9] == [0] * 9 and bid[-1] == 8 and sorted(set(bid[-len(timed) * 3:])) == [6, 7, 8]        # the timed window: three batches
     assert lab[:9] == [""] * 9                                            # the table build at commit is not a forward
     assert [l for l in lab[9:19] if l] == ["conv1+conv2 (table gather)", "conv3", "conv4", "fc1", "fc2"]
     assert sp.label_layers(["k_conv1_h2", "k_gemm_h2<H2BigPP>", "k_gemm_h2<H2MidPP>"])[1:] == ["conv2", "conv3"]

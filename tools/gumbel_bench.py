@@ -5,7 +5,7 @@
 
 Per setting (option off / on, taking turns, --reps engines each): a continuous engine (refill) is warmed up, then `rounds` move rounds of
 oz_selfplay_run are timed on the wall clock with the HIP-event profile of the tree kernels on (oz_selfplay_profile_read).  The two kernels the
-option adds to a round, k_gumbel_arm (after the roots kernel) and the Gumbel move (k_sp_move_g with the improved policy, in place of
+option adds to a round, k_gumbel_arm (after the roots kernel) and the Gumbel move (k_sp_move<VALUES+GUMBEL> with the improved policy, in place of
 k_sp_move), are both timed in the roots_move slot: their cost is that slot's difference; the depth-0 pick sits in the select slot (the fused
 expand + backup + descent launches).  One JSON line per engine, and a summary -- moves/s per setting, the on-over-off ratio per repetition with
 its spread -- printed and written to --out.  Playing strength is not measured.

@@ -91,11 +91,16 @@ def label_layers(records):
 DESCENT = ("k_select", "k_backup_select", "k_advance", "k_backup_advance")      # the tree launch that opens a batch
 
 
+def family(name):
+    """the kernel's name before its template arguments: the tree kernels are templates on their variant (k_backup_advance<1u>)"""
+    return name.split("<", 1)[0]
+
+
 def batch_ids(kernels):
     """dispatch-ordered kernel names -> the running number of the network batch each launch belongs to (a batch opens with its descent kernel)"""
     out, b = [], 0
     for k in kernels:
-        if k in DESCENT:
+        if family(k) in DESCENT:
             b += 1
         out.append(b)
     return out
@@ -188,7 +193,7 @@ def tree(src, out, games):
     vals = defaultdict(dict)
     with open(src) as f:
         for r in csv.DictReader(l for l in f if not l.startswith("#")):
-            vals[r["kernel"]][r["counter"]] = float(r["avg_per_launch"])
+            vals[family(r["kernel"])][r["counter"]] = float(r["avg_per_launch"])
     j = {"round": 6, "simulations_per_launch": float(games), "algorithmic_bytes_per_sim": 1300, "source": src, "kernels": {}}
     tot_raw = tot_w = 0.0
     # (k_backup_select = expand + backup of the previous simulation fused with the descent: 99 of the 100 launches of a round;
