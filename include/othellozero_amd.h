@@ -159,6 +159,12 @@ int oz_net_commit(oz_net* net);
 int oz_net_predict(oz_net* net, const uint64_t* own, const uint64_t* opp, int count, float* pi, float* v);
 /* the same on boards in the reference's layout (Net/NNet.py:80-84): count x (n, n, 2) bytes NHWC, channel 0 = the mover, non-zero = a disc */
 int oz_net_predict_boards(oz_net* net, const uint8_t* boards_nhwc, int count, float* pi, float* v);
+/* Test entry: one forward launched the way the searches launch it -- grid and launch plan of `launch` positions, `count` of them live.  own / opp
+ * hold `launch` boards; pi[launch][n*n] and v[launch] are in/out: uploaded before the forward, all `launch` rows downloaded after it (rows from
+ * `count` on come back as they went in).  0 <= count <= launch, 1 <= launch <= max_batch (evaluation symmetry "mean": 8 * launch <= max_batch), else
+ * OZ_ERR_ARG with nothing launched; count == 0 runs the launch.  Rows [0, count) equal oz_net_predict's bit for bit; the guard flag is reported as
+ * oz_net_predict reports it.  Works for the stub network too. */
+int oz_net_forward_launched(oz_net* net, const uint64_t* own, const uint64_t* opp, int count, int launch, float* pi, float* v);
 /* timing hook for bench.py: run the forward `iters` times on `count` resident boards, return avg ms per forward (HIP events) */
 int oz_net_time_forward(oz_net* net, int count, int iters, float* ms_avg);
 /* HIP-event timing of the dominant launch on the stream it is launched on: the conv3 implicit GEMM when conv1 + conv2

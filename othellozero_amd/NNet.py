@@ -164,6 +164,23 @@ class NNetWrapper(_NetHandle):
                                           _lib.p_f32(pi[s:e]), _lib.p_f32(v[s:e])))
         return pi, v
 
+    def forward_launched(self, own, opp, count, pi=None, v=None):
+        """test entry (oz_net_forward_launched): ONE forward launched for len(own) positions -- their grid, their launch plan -- of which the first
+        `count` are live, the way a search calls the network.  pi (launch, n, n) / v (launch,) float32 are uploaded before the forward (zeros when
+        None) and come back whole: rows [0, count) as predict_batch gives them, rows from `count` on as they went in.  activation() and
+        layer_plan() then describe this forward (rows of boards beyond `count` are whatever the buffers held)."""
+        own = np.ascontiguousarray(own, dtype=np.uint64).ravel()
+        opp = np.ascontiguousarray(opp, dtype=np.uint64).ravel()
+        launch, n = own.size, self.board_size_x
+        assert opp.size == launch
+        pi = np.zeros((launch, n, n), np.float32) if pi is None else np.array(pi, dtype=np.float32, order="C").reshape(launch, n, n)
+        v = np.zeros(launch, np.float32) if v is None else np.array(v, dtype=np.float32, order="C").reshape(launch)
+        rc = _lib.load().oz_net_forward_launched(self._h, _lib.p_u64(own), _lib.p_u64(opp), int(count), launch, _lib.p_f32(pi), _lib.p_f32(v))
+        if rc != _lib.OZ_ERR_ARG:
+            self._last_call_boards = launch
+        _lib.check(rc)
+        return pi, v
+
     def predict(self, board):
         """Net/NNet.py:70-87: board (n,n,2) [ONN] or one-channel (n,n) with +1 / -1 [BNN] -> (pi.reshape(n,n), v[0][0])"""
         if self.in_channels == 1:
@@ -493,6 +510,7 @@ class StubNetWrapper(_NetHandle):
 
     predict_batch = NNetWrapper.predict_batch
     predict = NNetWrapper.predict
+    forward_launched = NNetWrapper.forward_launched
     set_eval_cache = NNetWrapper.set_eval_cache
     eval_cache_stats = NNetWrapper.eval_cache_stats
     set_eval_symmetry = NNetWrapper.set_eval_symmetry

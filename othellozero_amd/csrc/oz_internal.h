@@ -160,6 +160,13 @@ struct oz_net {
                        float* d_pi, float* d_v, hipStream_t s);
 };
 
+// The contract of a launch (what the searches rely on; tests/test_gpu_short_batches.py holds every kernel configuration to it through
+// oz_net_forward_launched):
+//   - the launch plan -- tiles, k-slices, kernels -- is a function of max_count and the network only, never of *d_count;
+//   - rows [0, *d_count) of d_pi / d_v equal, bit for bit, what a call of exactly those positions returns;
+//   - rows at or beyond *d_count of d_pi / d_v are NOT written (the searches place evaluation-cache hits there before the network runs);
+//   - the f16x2 range guards look at live rows only: whatever an earlier, larger batch left beyond *d_count in the activation buffers raises nothing;
+//   - *d_count == 0 is legal: every kernel is launched and returns.
 int oz_net_forward_device(oz_net* net, const uint64_t* d_own, const uint64_t* d_opp, const int* d_count,
                           int max_count, float* d_pi, float* d_v, hipStream_t s);
 

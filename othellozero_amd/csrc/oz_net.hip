@@ -2250,6 +2250,49 @@ OZ_API int oz_net_predict_boards(oz_net* net, const uint8_t* boards, int count, 
     return oz_net_predict(net, own.data(), opp.data(), count, pi, v);
 }
 
+// Test entry: ONE forward launched the way the searches launch it -- the grid and the plan of `launch` positions, `count` of them live (a device
+// int), on the null stream.  own / opp hold `launch` boards (rows from `count` on: what a search's batch arrays still hold from earlier steps);
+// pi[launch][n*n] and v[launch] are in/out: uploaded before the forward, all `launch` rows downloaded after it, so that a caller sees which rows the
+// forward wrote.  count == 0 runs the launch too.  The guard flag is reported exactly as oz_net_predict reports it.
+OZ_API int oz_net_forward_launched(oz_net* net, const uint64_t* own, const uint64_t* opp, int count, int launch, float* pi, float* v) {
+    OZ_REQUIRE(net && own && opp && pi && v, "null argument");
+    OZ_REQUIRE(launch >= 1 && launch <= net->max_batch, "launch %d outside [1, max_batch=%d]", launch, net->max_batch);
+    OZ_REQUIRE(count >= 0 && count <= launch, "count %d outside [0, launch=%d]", count, launch);
+    OZ_REQUIRE(net->es_mode != OZ_EVAL_SYM_MEAN || 8ll * launch <= net->max_batch,
+               "evaluation symmetry \"mean\" evaluates 8 boards per position: 8 x launch %d exceeds max_batch %d", launch, net->max_batch);
+    std::lock_guard<std::mutex> lk(net->mu);
+    hipSetDevice(net->device);
+    const size_t n2 = (size_t)net->n * net->n, L = (size_t)launch;
+    uint64_t* d_in = nullptr;                                // own[launch] | opp[launch] | count
+    float* d_out = nullptr;                                  // pi[launch][n2] | v[launch]
+    hipError_t e;
+    if ((e = hipMalloc((void**)&d_in, 8 * (2 * L + 1))) != hipSuccess || (e = hipMalloc((void**)&d_out, 4 * L * (n2 + 1))) != hipSuccess) {
+        hipFree(d_in); hipFree(d_out);
+        oz_set_error("hipMalloc failed: %s", hipGetErrorString(e));
+        return OZ_ERR_HIP;
+    }
+    const uint64_t count_word = (uint64_t)(uint32_t)count;
+    int rc = OZ_OK, flag = 0;
+    if ((e = hipMemcpy(d_in, own, 8 * L, hipMemcpyHostToDevice)) != hipSuccess || (e = hipMemcpy(d_in + L, opp, 8 * L, hipMemcpyHostToDevice)) != hipSuccess ||
+        (e = hipMemcpy(d_in + 2 * L, &count_word, 8, hipMemcpyHostToDevice)) != hipSuccess ||
+        (e = hipMemcpy(d_out, pi, 4 * L * n2, hipMemcpyHostToDevice)) != hipSuccess || (e = hipMemcpy(d_out + L * n2, v, 4 * L, hipMemcpyHostToDevice)) != hipSuccess) {
+        oz_set_error("upload failed: %s", hipGetErrorString(e));
+        rc = OZ_ERR_HIP;
+    }
+    if (!rc) rc = net->forward_device(d_in, d_in + L, reinterpret_cast<const int*>(d_in + 2 * L), launch, d_out, d_out + L * n2, 0);
+    if (!rc) {
+        const int* fd = net->flag_device();
+        if ((fd && (e = hipMemcpyAsync(&flag, fd, sizeof(int), hipMemcpyDeviceToHost, 0)) != hipSuccess) || (e = hipStreamSynchronize(0)) != hipSuccess ||
+            (e = hipMemcpy(pi, d_out, 4 * L * n2, hipMemcpyDeviceToHost)) != hipSuccess || (e = hipMemcpy(v, d_out + L * n2, 4 * L, hipMemcpyDeviceToHost)) != hipSuccess) {
+            oz_set_error("forward failed: %s", hipGetErrorString(e));
+            rc = OZ_ERR_HIP;
+        }
+    } else hipStreamSynchronize(0);
+    hipFree(d_in); hipFree(d_out);
+    if (rc) return rc;
+    return flag ? net->check() : OZ_OK;
+}
+
 __global__ void k_fill_boards(uint64_t* own, uint64_t* opp, int count, uint64_t valid) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
