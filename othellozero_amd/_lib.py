@@ -796,15 +796,6 @@ def selection_dict(checked):
                 prior_first=bool(flags & SELECT_PRIOR_FIRST))
 
 
-def selection_kw(selection):
-    """the keyword to pass on: nothing where the option is off, so that callers without it see the calls they always saw"""
-    if isinstance(selection, (tuple, list)):
-        on = any(check_selection(x)[0] for x in selection)
-    else:
-        on = check_selection(selection)[0]
-    return {"selection": selection} if on else {}
-
-
 TREE_GC = {"off": 0, "demand": 1, "every": 2}   # OZ_TREE_GC_*
 TREE_GC_STATS = ("collections", "nodes_before_sum", "nodes_kept_sum", "peak_nodes", "peak_kept")     # oz_tree_gc_stats
 
@@ -825,12 +816,6 @@ def check_tree_gc_pair(tree_gc):
         return check_tree_gc(tree_gc[0], "tree_gc[black]"), check_tree_gc(tree_gc[1], "tree_gc[white]")
     m = check_tree_gc(tree_gc)
     return m, m
-
-
-def tree_gc_kw(tree_gc):
-    """the keyword to pass on: nothing where the option is off, so that callers without it see the calls they always saw"""
-    on = any(check_tree_gc_pair(tree_gc))
-    return {"tree_gc": tree_gc} if on else {}
 
 
 def tree_gc_stats_dict(st):
@@ -882,11 +867,6 @@ def check_proofs_pair(proofs, value_signs):
     return p, p
 
 
-def proofs_kw(proofs):
-    """the keyword to pass on: nothing where the option is off, so that callers without it see the calls they always saw"""
-    return {"proofs": proofs} if (any(proofs) if isinstance(proofs, (tuple, list)) else proofs) else {}
-
-
 PROOF_PLAY_STATS = ("proven_roots", "rows_changed", "moves_changed", "fallbacks")     # oz_selfplay_proof_play_stats
 
 
@@ -919,11 +899,6 @@ def check_proof_targets(proof_targets, proof_play):
     if proof_targets and not proof_play:
         raise ValueError("proof_targets=True needs proof_play=True: the records carry no proof code without it")
     return bool(proof_targets)
-
-
-def proof_play_kw(proof_play):
-    """the keyword to pass on: nothing where the option is off, so that callers without it see the calls they always saw"""
-    return {"proof_play": proof_play} if (any(proof_play) if isinstance(proof_play, (tuple, list)) else proof_play) else {}
 
 
 def record_proven(records):
@@ -989,6 +964,73 @@ def check_surprise_frac(frac, what="surprise_weight"):
     if not 0.0 < f <= 1.0:
         raise ValueError(f"{what}: frac must be in (0, 1] (got {f})")
     return f
+
+
+def check_search_options(solve_leaves=0, value_signs="reference", proofs=False, proof_play=False, selection=None, tree_gc="off", gumbel=None,
+                         forced_playouts=None, pairs=False):
+    """The six options every batched search takes -- engines, arenas and the wrappers above them -- checked once, rules between them
+    included (proofs need sound signs, proof play needs proofs; selection and proofs stand beside neither `gumbel` nor `forced_playouts`,
+    which a self-play caller passes along).  pairs=True: each may also be a (black, white) pair, as arena_batch takes them.  -> the dict of
+    the six in the form a keyword carries them (solve_leaves an int, proofs and proof_play bools where they are not pairs); it is its own
+    valid input.  ValueError for anything else, in the order SelfPlayEngine has always looked."""
+    if pairs:
+        check_tree_gc_pair(tree_gc)
+        check_selection_pair(selection)
+        check_value_signs_pair(value_signs)
+        check_proof_play_pair(proof_play, check_proofs_pair(proofs, value_signs))
+        check_solve_leaves_pair(solve_leaves)
+    else:
+        check_tree_gc(tree_gc)
+        check_selection(selection, gumbel=gumbel, forced_playouts=forced_playouts)
+        check_value_signs(value_signs)
+        proofs = check_proofs(proofs, value_signs, gumbel=gumbel, forced_playouts=forced_playouts)
+        proof_play = check_proof_play(proof_play, proofs)
+        solve_leaves = check_solve_leaves(solve_leaves)
+    return dict(solve_leaves=solve_leaves, value_signs=value_signs, proofs=proofs, proof_play=proof_play, selection=selection, tree_gc=tree_gc)
+
+
+def check_selfplay_options(num_simulations, record_visits=False, leaves_per_step=1, root_noise=None, sample_moves=None, solve_leaves=0,
+                           playout_cap=None, forced_playouts=None, record_values=False, gumbel=None, record_surprise=False, resign=None,
+                           value_signs="reference", proofs=False, proof_play=False, selection=None, tree_gc="off"):
+    """Everything SelfPlayEngine takes beyond its plain configuration, checked once and in the engine's order: check_search_options, then
+    resign (not with gumbel), recorded surprise (needs visit rows or gumbel), gumbel (replaces noise, forcing and sampling; no cap, one
+    leaf per step), the playout cap against num_simulations, solve_leaves, root noise, forced playouts (need noise) and move sampling.
+    -> the dict of all sixteen with the checked values; it is its own valid input, so a wrapper hands its result on.  ValueError otherwise,
+    before the network or the library is touched."""
+    o = check_search_options(0, value_signs, proofs, proof_play, selection, tree_gc, gumbel=gumbel, forced_playouts=forced_playouts)
+    resign = check_resign(resign, gumbel=gumbel)
+    if record_surprise and not (record_visits or gumbel):
+        raise ValueError("record_surprise needs record_visits=True or gumbel=...: the surprise is that of a recorded policy target")
+    gumbel = check_gumbel_options(gumbel, root_noise=root_noise, forced_playouts=forced_playouts, sample_moves=sample_moves,
+                                  playout_cap=playout_cap, leaves_per_step=leaves_per_step)
+    playout_cap = check_playout_cap(playout_cap, num_simulations)
+    o["solve_leaves"] = check_solve_leaves(solve_leaves)                # (here, not above: where the engine has always checked it)
+    root_noise = check_root_noise(root_noise)
+    return dict(o, record_visits=record_visits, leaves_per_step=leaves_per_step, root_noise=root_noise, sample_moves=check_sample_moves(sample_moves),
+                playout_cap=playout_cap, forced_playouts=check_forced_playouts(forced_playouts, root_noise), record_values=bool(record_values),
+                gumbel=gumbel, record_surprise=bool(record_surprise), resign=resign)
+
+
+def _given(value):
+    return value is not None
+
+
+_SEARCH_ON = dict(solve_leaves=lambda e: e != 0, value_signs=lambda mode: mode != "reference", proofs=bool, proof_play=bool,
+                  selection=lambda s: check_selection(s)[0] != 0, tree_gc=lambda mode: mode != "off")
+_ENGINE_ON = dict(_SEARCH_ON, record_visits=bool, leaves_per_step=lambda k: int(k) != 1, root_noise=_given, sample_moves=_given,
+                  playout_cap=_given, forced_playouts=bool, record_values=bool, gumbel=_given, record_surprise=bool, resign=_given)
+
+
+def search_kw(checked):
+    """the keywords to pass on from check_search_options' dict (or the six of them in check_selfplay_options'): those of the options that
+    are on (for a pair: on for either colour), with the caller's value -- nothing for an option that is off, so that callers without it
+    see the calls they always saw"""
+    return {k: v for k, v in checked.items() if k in _SEARCH_ON and any(_SEARCH_ON[k](x) for x in (v if isinstance(v, (tuple, list)) else (v,)))}
+
+
+def engine_kw(checked, always=()):
+    """search_kw for check_selfplay_options' dict; the names in `always` are passed on whatever their value"""
+    return {k: v for k, v in checked.items() if k in always or _ENGINE_ON[k](v)}
 
 
 def check_opponent(opponent):

@@ -473,8 +473,8 @@ class NeuralNetworkOthelloAgent(OthelloAgent):
         # an agent searches on its own turns only: about half the plies
         self.mcts = OthelloMCTS(side, neural_network, degree_exploration, q_mode=q_mode,
                                 node_cap=int(node_cap) if node_cap else num_simulations * (side * side // 2) + 64, leaves_per_step=leaves_per_step,
-                                solve_leaves=solve_leaves, value_signs=value_signs, **_lib.proofs_kw(proofs),
-                                **_lib.proof_play_kw(self.proof_play), **_lib.selection_kw(selection), **_lib.tree_gc_kw(tree_gc))
+                                solve_leaves=solve_leaves, value_signs=value_signs,
+                                **_lib.search_kw(dict(proofs=proofs, proof_play=self.proof_play, selection=selection, tree_gc=tree_gc)))
 
     def play(self):
         game = self.game

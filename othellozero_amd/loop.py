@@ -186,24 +186,17 @@ def evaluate_against_random_batch(board_size, neural_network, games, num_simulat
     play opening k, so the network meets every opening from both sides (with an odd `games` the BLACK half has one opening more).
     -> dict(wins, black_wins, black_games, white_wins, white_games)"""
     _lib.check_opponent(opponent)
-    solve_leaves = _lib.check_solve_leaves(solve_leaves)
-    _lib.check_value_signs(value_signs)
-    _lib.check_proofs(proofs, value_signs)
-    _lib.check_proof_play(proof_play, proofs)
-    _lib.check_tree_gc(tree_gc)
-    _lib.check_selection(selection)
+    search = _lib.search_kw(_lib.check_search_options(solve_leaves, value_signs, proofs, proof_play, selection, tree_gc))
     _lib.check_openings(openings)
-    opening_kw = dict({"openings": openings, "first_opening_id": 0} if openings is not None else {}, **({"value_signs": value_signs} if value_signs != "reference" else {}), **_lib.proofs_kw(proofs),
-                      **_lib.proof_play_kw(proof_play), **_lib.selection_kw(selection), **_lib.tree_gc_kw(tree_gc))
+    kw = dict(search, seed=seed, leaves_per_step=leaves_per_step, opponent=opponent,
+              **({"openings": openings, "first_opening_id": 0} if openings is not None else {}))
     as_black, as_white = games // 2 + games % 2, games // 2
     r = dict(wins=0, black_wins=0, black_games=0, white_wins=0, white_games=0)
     if as_black:
-        res = arena_batch(neural_network, None, board_size, as_black, num_simulations, degree_exploration, seed=seed,
-                          leaves_per_step=leaves_per_step, opponent=opponent, **({"solve_leaves": solve_leaves} if solve_leaves else {}), **opening_kw)
+        res = arena_batch(neural_network, None, board_size, as_black, num_simulations, degree_exploration, **kw)
         r["black_wins"] = int((res["winner"] == 1).sum())
     if as_white:
-        res = arena_batch(None, neural_network, board_size, as_white, num_simulations, degree_exploration, seed=seed, first_game_id=as_black,
-                          leaves_per_step=leaves_per_step, opponent=opponent, **({"solve_leaves": solve_leaves} if solve_leaves else {}), **opening_kw)
+        res = arena_batch(None, neural_network, board_size, as_white, num_simulations, degree_exploration, first_game_id=as_black, **kw)
         r["white_wins"] = int((res["winner"] == -1).sum())
         r["black_games"] = as_white - r["white_wins"]              # games BLACK (the random agent) won
     r["white_games"] = r["white_wins"] + (as_black - r["black_wins"])
@@ -220,16 +213,9 @@ def evaluate_against_opponent(board_size, neural_network, games, num_simulations
 def evaluate_against_opponent_batch(board_size, neural_network, games, num_simulations, degree_exploration, opponent, seed=0, leaves_per_step=1,
                                     solve_leaves=0, openings=None, value_signs="reference", proofs=False, proof_play=False, selection=None, tree_gc="off"):
     """`evaluate_against_random_batch` under the name that says what it does when the opponent is not the random agent"""
-    solve_leaves = _lib.check_solve_leaves(solve_leaves)
-    _lib.check_value_signs(value_signs)
-    _lib.check_proofs(proofs, value_signs)
-    _lib.check_proof_play(proof_play, proofs)
-    _lib.check_tree_gc(tree_gc)
-    _lib.check_selection(selection)
     return evaluate_against_random_batch(board_size, neural_network, games, num_simulations, degree_exploration, seed=seed,
-                                         leaves_per_step=leaves_per_step, opponent=opponent, **({"solve_leaves": solve_leaves} if solve_leaves else {}),
-                                         **({"openings": openings} if openings is not None else {}), **({"value_signs": value_signs} if value_signs != "reference" else {}), **_lib.proofs_kw(proofs),
-                                         **_lib.proof_play_kw(proof_play), **_lib.selection_kw(selection), **_lib.tree_gc_kw(tree_gc))
+                                         leaves_per_step=leaves_per_step, opponent=opponent, solve_leaves=solve_leaves, openings=openings,
+                                         value_signs=value_signs, proofs=proofs, proof_play=proof_play, selection=selection, tree_gc=tree_gc)
 
 
 def _discs(boards):
@@ -268,19 +254,13 @@ def paired_match(board_size, neural_network, old_neural_network, pairs, num_simu
     every game from the standard position).  Two arenas of `pairs` games: the new network as BLACK against the old one, then the old one as
     BLACK against the new; both get openings=(plies, opening_seed) and first_opening_id=0, so game i of either starts with opening i.  Game ids
     are 0 .. pairs - 1 and pairs .. 2 pairs - 1, as in self_play_match.  -> pair_statistics' dict, plus games = the two arena_batch results."""
-    solve_leaves = _lib.check_solve_leaves(solve_leaves)
-    _lib.check_value_signs(value_signs)
-    _lib.check_proofs(proofs, value_signs)
-    _lib.check_proof_play(proof_play, proofs)
-    _lib.check_tree_gc(tree_gc)
-    _lib.check_selection(selection)
+    search = _lib.search_kw(_lib.check_search_options(solve_leaves, value_signs, proofs, proof_play, selection, tree_gc))
     if openings is None:
         raise ValueError("paired_match needs openings=(plies, opening_seed): without them every pair is the same two games")
     _lib.check_openings(openings)
     if isinstance(pairs, bool) or not isinstance(pairs, (int, np.integer)) or pairs < 1:
         raise ValueError(f"paired_match: pairs must be a whole number >= 1 (got {pairs!r})")
-    kw = dict(leaves_per_step=leaves_per_step, openings=openings, first_opening_id=0, **({"solve_leaves": solve_leaves} if solve_leaves else {}),
-              **({"value_signs": value_signs} if value_signs != "reference" else {}), **_lib.proofs_kw(proofs), **_lib.proof_play_kw(proof_play), **_lib.selection_kw(selection), **_lib.tree_gc_kw(tree_gc))
+    kw = dict(search, leaves_per_step=leaves_per_step, openings=openings, first_opening_id=0)
     a = arena_batch(neural_network, old_neural_network, board_size, int(pairs), num_simulations, degree_exploration, seed=seed, **kw)
     b = arena_batch(old_neural_network, neural_network, board_size, int(pairs), num_simulations, degree_exploration, seed=seed,
                     first_game_id=int(pairs), **kw)
@@ -298,35 +278,30 @@ def self_play_match(board_size, neural_network, old_neural_network, total_games,
     proof_play=True (needs proofs=True): both agents' moves are the arg-max of the row their root's proofs keep (arena_batch).
     openings=(plies, opening_seed): paired_match over total_games // 2 openings instead (total_games must be even: a pair is two games); the
     return value is its `wins`, counted by the same rule, and self_play_match.stats holds its dict (None after a match without openings)."""
-    solve_leaves = _lib.check_solve_leaves(solve_leaves)
-    _lib.check_value_signs(value_signs)
-    _lib.check_proofs(proofs, value_signs)
-    _lib.check_proof_play(proof_play, proofs)
-    _lib.check_tree_gc(tree_gc)
-    _lib.check_selection(selection)
+    search = _lib.search_kw(_lib.check_search_options(solve_leaves, value_signs, proofs, proof_play, selection, tree_gc))
     self_play_match.stats = None
     if openings is not None:
         _lib.check_openings(openings)
         if total_games % 2 or total_games < 2:
             raise ValueError(f"self_play_match with openings plays pairs of games: total_games must be even and >= 2 (got {total_games})")
         stats = paired_match(board_size, neural_network, old_neural_network, total_games // 2, num_simulations, degree_exploration, openings,
-                             seed=seed, leaves_per_step=leaves_per_step, solve_leaves=solve_leaves, **({"value_signs": value_signs} if value_signs != "reference" else {}), **_lib.proofs_kw(proofs),
-                             **_lib.proof_play_kw(proof_play), **_lib.selection_kw(selection), **_lib.tree_gc_kw(tree_gc))
+                             seed=seed, leaves_per_step=leaves_per_step, **search)
         self_play_match.stats = {k: v for k, v in stats.items() if k != "games"}
         return stats["wins"]
     as_black, as_white = total_games // 2, total_games // 2 + total_games % 2
+    kw = dict(search, seed=seed, leaves_per_step=leaves_per_step)
     wins = 0
     if as_black:
-        res = arena_batch(neural_network, old_neural_network, board_size, as_black, num_simulations, degree_exploration, seed=seed,
-                          leaves_per_step=leaves_per_step, **({"solve_leaves": solve_leaves} if solve_leaves else {}), **({"value_signs": value_signs} if value_signs != "reference" else {}), **_lib.proofs_kw(proofs),
-                          **_lib.proof_play_kw(proof_play), **_lib.selection_kw(selection), **_lib.tree_gc_kw(tree_gc))
+        res = arena_batch(neural_network, old_neural_network, board_size, as_black, num_simulations, degree_exploration, **kw)
         wins += int((res["winner"] == 1).sum())
     if as_white:
-        res = arena_batch(old_neural_network, neural_network, board_size, as_white, num_simulations, degree_exploration,
-                          seed=seed, first_game_id=as_black, leaves_per_step=leaves_per_step, **({"solve_leaves": solve_leaves} if solve_leaves else {}),
-                          **({"value_signs": value_signs} if value_signs != "reference" else {}), **_lib.proofs_kw(proofs), **_lib.proof_play_kw(proof_play), **_lib.selection_kw(selection), **_lib.tree_gc_kw(tree_gc))
+        res = arena_batch(old_neural_network, neural_network, board_size, as_white, num_simulations, degree_exploration, first_game_id=as_black, **kw)
         wins += int((res["winner"] == -1).sum())
     return wins
+
+
+_ENGINE_ALWAYS = ("record_visits", "leaves_per_step", "root_noise", "sample_moves", "solve_leaves")    # the loop's engines get these, on or off
+_STATS_PUBLISHED = ("resign_stats", "surprise_stats", "proof_stats", "proof_play_stats", "proof_target_stats")      # training.<name> of an iteration
 
 
 def _selfplay_into_replay(replay, neural_network, board_size, num_episodes, num_simulations, degree_exploration, temperature, e_greedy, seed,
@@ -335,8 +310,8 @@ def _selfplay_into_replay(replay, neural_network, board_size, num_episodes, num_
                           gumbel=None, surprise_weight=None, resign=None, value_signs="reference", proofs=False, proof_play=False,
                           proof_targets=False, selection=None, tree_gc="off"):
     """one iteration's games on the engine selfplay_batch would create, played to the end without reading a record, and their examples
-    appended to the device buffer; -> (records appended, the endgame solver's statistics or None).  One-channel (BaseNN) examples are never
-    aliased (examples_from_records).  endgame_targets > 0: SelfPlayEngine.solve_records before the append.  playout_cap: the engine's; the
+    appended to the device buffer; -> (records appended, the engine's option_stats() plus surprise_stats: what _publish_selfplay_stats
+    takes).  One-channel (BaseNN) examples are never aliased (examples_from_records).  endgame_targets > 0: SelfPlayEngine.solve_records before the append.  playout_cap: the engine's; the
     append leaves the fast records out and counts the fully searched ones.  forced_playouts: the engine's; its visit rows, which the append
     reads, are then the pruned ones.  value_target: the engine records root values and the append computes the value targets (after the
     endgame solver, exact_empties = endgame_targets).  gumbel: the engine's; policy_target="improved" appends its improved-policy rows.
@@ -348,38 +323,55 @@ def _selfplay_into_replay(replay, neural_network, board_size, num_episodes, num_
     exact; training.proof_target_stats holds its statistics."""
     from .training import SelfPlayEngine
     vt_on = _lib.check_value_target(value_target)[0] != _lib.VALUE_TARGET_OUTCOME
+    o = _lib.check_selfplay_options(num_simulations, visits, leaves_per_step, root_noise, sample_moves, solve_leaves, playout_cap, forced_playouts,
+                                    vt_on, gumbel, surprise_weight is not None, resign, value_signs, proofs, proof_play, selection, tree_gc)
     eng = SelfPlayEngine(neural_network, board_size, num_episodes, num_simulations, degree_exploration, temperature, e_greedy, seed,
-                         first_game_id, q_mode=q_mode, record_visits=visits, leaves_per_step=leaves_per_step, root_noise=root_noise,
-                         sample_moves=sample_moves, solve_leaves=solve_leaves, **({"playout_cap": playout_cap} if playout_cap is not None else {}),
-                         **({"forced_playouts": forced_playouts} if forced_playouts else {}), **({"record_values": True} if vt_on else {}),
-                         **({"gumbel": gumbel} if gumbel is not None else {}), **({"record_surprise": True} if surprise_weight is not None else {}),
-                         **({"resign": resign} if resign is not None else {}), **({"value_signs": value_signs} if value_signs != "reference" else {}), **_lib.proofs_kw(proofs),
-                         **_lib.proof_play_kw(proof_play), **_lib.selection_kw(selection), **_lib.tree_gc_kw(tree_gc))
+                         first_game_id, q_mode=q_mode, **_lib.engine_kw(o, always=_ENGINE_ALWAYS))
     for _ in range(board_size * board_size):
         eng.run(4)
         if eng.stats()["live_games"] == 0:
             break
-    training.proof_target_stats = eng.proof_targets() if proof_targets else None
-    endgame = eng.solve_records(endgame_targets) if endgame_targets else None
-    if solve_leaves:
-        training.rows_solved += eng.rows_solved()
-    if resign is not None:
-        training.resign_stats = eng.resign_stats()
-    training.proof_stats = eng.proof_stats() if proofs else None
-    training.proof_play_stats = eng.proof_play_stats() if proof_play else None
+    if proof_targets:
+        eng.proof_target_stats = eng.proof_targets()
+    if endgame_targets:
+        eng.endgame_stats = eng.solve_records(endgame_targets)
+    stats = dict(eng.option_stats(), surprise_stats=None)
     appended = replay.append_engine(eng, alias_final=alias_final_boards and getattr(neural_network, "in_channels", 2) == 2,
-                                    policy_target=policy_target, target_temperature=target_temperature,
-                                    **({"value_target": value_target, "exact_empties": endgame_targets} if vt_on else {}),
-                                    **({"exact_proven": True} if vt_on and proof_targets else {}),
-                                    **({"surprise_weight": surprise_weight} if surprise_weight is not None else {}))
+                                    policy_target=policy_target, target_temperature=target_temperature, surprise_weight=surprise_weight,
+                                    **({"value_target": value_target, "exact_empties": endgame_targets, "exact_proven": bool(proof_targets)} if vt_on else {}))
     if surprise_weight is not None:
         st = replay.last_weight_stats
         rec, sur = eng.records(with_surprise=True)
         full = _lib.record_fast(rec) == 0
-        training.surprise_stats = dict(records=st["full_records"], examples=st["examples"], max_copies=st["max_copies"],
+        stats["surprise_stats"] = dict(records=st["full_records"], examples=st["examples"], max_copies=st["max_copies"],
                                        mean_copies=st["examples"] / st["full_records"] if st["full_records"] else 0.0,
                                        mean_surprise=float(sur[full].mean()) if full.any() else 0.0)
-    return appended, endgame
+    return appended, stats
+
+
+def _publish_selfplay_stats(i, num_iterations, stats):
+    """an iteration's self-play statistics (SelfPlayEngine.option_stats(), and surprise_stats where the device path weighted) -> the
+    training.* attributes of their names, training.rows_solved, the histories and the log lines of the options that are on"""
+    training.rows_solved += stats["rows_solved"] or 0
+    for name in _STATS_PUBLISHED:
+        setattr(training, name, stats.get(name))
+    if stats["resign_stats"] is not None:
+        training.resign_history.append(stats["resign_stats"])
+        _log_resign(i, num_iterations, stats["resign_stats"])
+    if stats["proof_stats"] is not None:
+        training.proof_history.append(stats["proof_stats"])
+        _log_proofs(i, num_iterations, stats["proof_stats"])
+    if stats["proof_play_stats"] is not None:
+        training.proof_play_history.append(dict(stats["proof_play_stats"], targets=stats["proof_target_stats"]))
+        _log_proof_play(i, num_iterations, stats["proof_play_stats"], stats["proof_target_stats"])
+    if stats.get("surprise_stats") is not None:
+        st = stats["surprise_stats"]
+        training.surprise_history.append(st)
+        logging.info('[%d/%d] surprise weighting: %d examples from %d records / mean_copies %.3f / max_copies %d / mean_surprise %.4f', i,
+                     num_iterations, st["examples"], st["records"], st["mean_copies"], st["max_copies"], st["mean_surprise"])
+    if stats["endgame_stats"] is not None:
+        training.endgame_history.append(stats["endgame_stats"])
+        _log_endgame(i, num_iterations, stats["endgame_stats"])
 
 
 def _log_resign(i, num_iterations, stats):
@@ -615,9 +607,6 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
     replay="device" (the append reads the engine's targets on the device) alike; the examples' z is then a float.  It needs
     alias_final_boards=False.  Playing strength is neither gated nor claimed ("Value targets")."""
     vt_on = _lib.check_value_target(value_target, alias_final_boards)[0] != _lib.VALUE_TARGET_OUTCOME
-    vt_kw = {"value_target": value_target} if vt_on else {}
-    resign = _lib.check_resign(resign, gumbel=gumbel)
-    resign_kw = {"resign": resign} if resign is not None else {}
     training.resign_history = []
     training.surprise_history = []
     training.validation_history = []
@@ -654,11 +643,6 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
         _lib.check_eval_symmetry(es_mode, es_seed)
         _lib.check_eval_symmetry(es_mode, es_seed + num_iterations)
         eval_symmetry = (es_mode, int(es_seed))
-    playout_cap = _lib.check_playout_cap(playout_cap, num_simulations)
-    cap_kw = {"playout_cap": playout_cap} if playout_cap is not None else {}
-    forced_playouts = _lib.check_forced_playouts(forced_playouts, _lib.check_root_noise(root_noise))
-    if forced_playouts:
-        cap_kw["forced_playouts"] = forced_playouts
     _lib.check_opponent(evaluation_opponent)
     _lib.check_openings(match_openings)
     _lib.check_openings(evaluation_openings)
@@ -667,16 +651,8 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
     if match_openings is not None and self_play_training and (self_play_total_games % 2 or self_play_total_games < 2):
         raise ValueError(f"match_openings plays pairs of games: self_play_total_games must be even and >= 2 (got {self_play_total_games})")
     training.match_history = []
-    solve_leaves = _lib.check_solve_leaves(solve_leaves)
-    _lib.check_value_signs(value_signs)
-    _lib.check_proofs(proofs, value_signs, gumbel=gumbel, forced_playouts=forced_playouts)
-    proof_play = _lib.check_proof_play(proof_play, proofs)
-    _lib.check_tree_gc(tree_gc)
-    _lib.check_selection(selection, gumbel=gumbel, forced_playouts=forced_playouts)
-    pt_kw = {"proof_targets": True} if _lib.check_proof_targets(proof_targets, proof_play) else {}
     training.proof_history = []
     training.proof_play_history = []
-    vs_kw = dict({"value_signs": value_signs} if value_signs != "reference" else {}, **_lib.proofs_kw(proofs), **_lib.proof_play_kw(proof_play), **_lib.selection_kw(selection), **_lib.tree_gc_kw(tree_gc))
     training.rows_solved = 0
     endgame_targets = _lib.check_endgame_targets(endgame_targets, alias_final_boards)
     training.endgame_history = []
@@ -687,11 +663,14 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
                          "(use replay='host' with distributed=True)")
     if replay == "device" and dump_examples:
         raise ValueError("replay='device' keeps no example tuples to dump: use replay='host' with dump_examples=True, or ReplayBuffer.save")
-    root_noise = _lib.check_root_noise(root_noise)
-    sample_moves = _lib.check_sample_moves(sample_moves)
-    gumbel = _lib.check_gumbel_options(gumbel, root_noise=root_noise, forced_playouts=forced_playouts, sample_moves=sample_moves,
-                                       playout_cap=playout_cap, leaves_per_step=leaves_per_step, distributed=distributed)
-    gumbel_kw = {"gumbel": gumbel} if gumbel is not None else {}
+    visits = policy_target == "visits"
+    o = _lib.check_selfplay_options(num_simulations, visits, leaves_per_step, root_noise, sample_moves, solve_leaves, playout_cap, forced_playouts,
+                                    vt_on, gumbel, False, resign, value_signs, proofs, proof_play, selection, tree_gc)
+    o["record_surprise"] = surprise_weight is not None     # (past the engine's rule for it: the loop's own, above, say what it needs here)
+    gumbel = _lib.check_gumbel_options(o["gumbel"], distributed=distributed)
+    proof_targets = _lib.check_proof_targets(proof_targets, o["proof_play"])
+    search = _lib.search_kw(o)                              # what the match and the batched evaluation share with self-play
+    engine_options = {k: v for k, v in o.items() if not k.startswith("record_")}       # (the record_* flags: the two wrappers set them)
     if policy_target not in ("onehot", "visits", "improved"):
         raise ValueError(f"policy_target must be 'onehot', 'visits' or 'improved' (got {policy_target!r})")
     improved = policy_target == "improved"
@@ -703,7 +682,6 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
     if improved and getattr(neural_network, "policy_loss", "rows") != "flat":
         raise ValueError("policy_target='improved' needs a network trained with the flat policy loss: create it with "
                          "NNetWrapper(..., policy_loss='flat')")
-    visits = policy_target == "visits"
     if visits and alias_final_boards:
         raise ValueError("policy_target='visits' needs alias_final_boards=False: a visit distribution belongs to the position of its "
                          "move, not to the game's final position")
@@ -758,29 +736,14 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
                 net.set_eval_symmetry(*previous)
         if device_replay is not None:
             total_before = device_replay.total if validation_share is not None else 0
-            appended, endgame = _selfplay_into_replay(device_replay, neural_network, board_size, num_episodes, num_simulations,
-                                                      degree_exploration, temperature, e_greedy, seed, total_episodes_done, q_mode, visits,
-                                                      leaves_per_step, root_noise, sample_moves, alias_final_boards, policy_target,
-                                                      target_temperature, endgame_targets, solve_leaves, playout_cap, forced_playouts, **vt_kw,
-                                                      **gumbel_kw, **resign_kw, **vs_kw, **pt_kw,
-                                                      **({"surprise_weight": (surprise_weight, seed + i)} if surprise_weight is not None else {}))
-            if resign is not None:
-                training.resign_history.append(training.resign_stats)
-                _log_resign(i, num_iterations, training.resign_stats)
-            if proofs:
-                training.proof_history.append(training.proof_stats)
-                _log_proofs(i, num_iterations, training.proof_stats)
-            if proof_play:
-                training.proof_play_history.append(dict(training.proof_play_stats, targets=training.proof_target_stats))
-                _log_proof_play(i, num_iterations, training.proof_play_stats, training.proof_target_stats)
-            if surprise_weight is not None:
-                st = training.surprise_stats
-                training.surprise_history.append(st)
-                logging.info('[%d/%d] surprise weighting: %d examples from %d records / mean_copies %.3f / max_copies %d / mean_surprise %.4f', i,
-                             num_iterations, st["examples"], st["records"], st["mean_copies"], st["max_copies"], st["mean_surprise"])
-            if endgame is not None:
-                training.endgame_history.append(endgame)
-                _log_endgame(i, num_iterations, endgame)
+            appended, stats = _selfplay_into_replay(device_replay, neural_network, board_size, num_episodes, num_simulations,
+                                                    degree_exploration, temperature, e_greedy, seed, total_episodes_done, q_mode, visits,
+                                                    alias_final_boards=alias_final_boards, policy_target=policy_target,
+                                                    target_temperature=target_temperature, endgame_targets=endgame_targets,
+                                                    value_target=value_target, proof_targets=proof_targets,
+                                                    surprise_weight=None if surprise_weight is None else (surprise_weight, seed + i),
+                                                    **engine_options)
+            _publish_selfplay_stats(i, num_iterations, stats)
             total_episodes_done += num_episodes
             logging.info('[%d/%d] self-play done: %d records, device buffer holds %d examples', i, num_iterations, appended, len(device_replay))
             restore_eval_symmetry()
@@ -793,45 +756,21 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
             if distributed:
                 first, count = shard_games(num_episodes, rank, world)
                 eng = SelfPlayEngine(neural_network, board_size, count, num_simulations, degree_exploration, temperature, e_greedy,
-                                     seed=seed, first_game_id=total_episodes_done + first, q_mode=q_mode, record_visits=visits,
-                                     leaves_per_step=leaves_per_step, root_noise=root_noise, sample_moves=sample_moves,
-                                     solve_leaves=solve_leaves, **cap_kw, **({"record_values": True} if vt_on else {}), **resign_kw, **vs_kw)
-                eng.play_to_end(endgame_targets=endgame_targets, **vt_kw, **pt_kw)               # each rank relabels its own records (and computes its targets)
-                training.rows_solved += eng.rows_solved() if solve_leaves else 0
-                resign_stats = eng.resign_stats() if resign is not None else None
-                proof_stats = eng.proof_stats() if proofs else None
-                proof_play_stats = eng.proof_play_stats() if proof_play else None
-                proof_target_stats = getattr(eng, "proof_target_stats", None)
-                records = pooled_selfplay_records(eng, device, with_visits=visits,      # the only exchange of the self-play phase
-                                                  **({"with_values": True} if vt_on else {}))
-                endgame = getattr(eng, "endgame_stats", None)
+                                     seed=seed, first_game_id=total_episodes_done + first, q_mode=q_mode,
+                                     **_lib.engine_kw(o, always=_ENGINE_ALWAYS))
+                eng.play_to_end(endgame_targets=endgame_targets, value_target=value_target,      # each rank relabels its own records (and
+                                proof_targets=proof_targets)                                       # computes its targets)
+                stats = eng.option_stats()
+                records = pooled_selfplay_records(eng, device, with_visits=visits, with_values=vt_on)   # the only exchange of the self-play phase
                 del eng
             else:
                 records = selfplay_batch(neural_network, board_size, num_games=num_episodes, num_simulations=num_simulations,
                                          degree_exploration=degree_exploration, policy_temperature=temperature, e_greedy=e_greedy,
                                          seed=seed, first_game_id=total_episodes_done, q_mode=q_mode, record_visits=visits,
-                                         leaves_per_step=leaves_per_step, root_noise=root_noise, sample_moves=sample_moves,
-                                         **({"endgame_targets": endgame_targets} if endgame_targets else {}), **({"solve_leaves": solve_leaves} if solve_leaves else {}),
-                                         **cap_kw, **vt_kw, **gumbel_kw, **resign_kw, **vs_kw, **pt_kw)
-                training.rows_solved += selfplay_batch.rows_solved if solve_leaves else 0
-                resign_stats = selfplay_batch.resign_stats if resign is not None else None
-                proof_stats = selfplay_batch.proof_stats if proofs else None
-                proof_play_stats = selfplay_batch.proof_play_stats if proof_play else None
-                proof_target_stats = getattr(selfplay_batch, "proof_target_stats", None)
-                endgame = getattr(selfplay_batch, "endgame_stats", None) if endgame_targets else None
+                                         endgame_targets=endgame_targets, value_target=value_target, proof_targets=proof_targets, **engine_options)
+                stats = {name: getattr(selfplay_batch, name, None) for name in ("rows_solved", "endgame_stats") + _STATS_PUBLISHED}
             restore_eval_symmetry()
-            if resign is not None:
-                training.resign_history.append(resign_stats)
-                _log_resign(i, num_iterations, resign_stats)
-            if proofs:
-                training.proof_history.append(proof_stats)
-                _log_proofs(i, num_iterations, proof_stats)
-            if proof_play:
-                training.proof_play_history.append(dict(proof_play_stats, targets=proof_target_stats))
-                _log_proof_play(i, num_iterations, proof_play_stats, proof_target_stats)
-            if endgame is not None:
-                training.endgame_history.append(endgame)
-                _log_endgame(i, num_iterations, endgame)
+            _publish_selfplay_stats(i, num_iterations, stats)
             counts = targets = policies = None
             if gumbel is not None:                             # the improved-policy rows come last
                 policies, records = records[-1], (records[0] if len(records) == 2 else records[:-1])
@@ -859,8 +798,7 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
             logging.info('[%d/%d] arena: trained network against the previous one', i, num_iterations)
             new_net_victories = self_play_match(board_size, neural_network, old_neural_network, self_play_total_games,
                                                 num_simulations, degree_exploration, seed=seed + i, leaves_per_step=leaves_per_step,
-                                                **({"solve_leaves": solve_leaves} if solve_leaves else {}), **vs_kw,
-                                                **({"openings": match_openings} if match_openings is not None else {}))
+                                                **search, **({"openings": match_openings} if match_openings is not None else {}))
             if match_openings is not None:
                 stats = self_play_match.stats
                 training.match_history.append(stats)
@@ -884,11 +822,11 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
             if batched_evaluation:
                 new = evaluate_against_random_batch(board_size, neural_network, evaluation_iterations, num_simulations,
                                                     degree_exploration, seed=seed + 7919 * i, leaves_per_step=leaves_per_step,
-                                                    opponent=evaluation_opponent, **({"solve_leaves": solve_leaves} if solve_leaves else {}), **vs_kw,
+                                                    opponent=evaluation_opponent, **search,
                                                     **({"openings": evaluation_openings} if evaluation_openings is not None else {}))
                 old = evaluate_against_random_batch(board_size, old_neural_network, evaluation_iterations, num_simulations,
                                                     degree_exploration, seed=seed + 7919 * i + 1, leaves_per_step=leaves_per_step,
-                                                    opponent=evaluation_opponent, **({"solve_leaves": solve_leaves} if solve_leaves else {}), **vs_kw,
+                                                    opponent=evaluation_opponent, **search,
                                                     **({"openings": evaluation_openings} if evaluation_openings is not None else {}))
             else:
                 new = evaluate_against_random(board_size, neural_network, evaluation_iterations, num_simulations, degree_exploration,

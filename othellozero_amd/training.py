@@ -109,8 +109,7 @@ def execute_episode(board_size, neural_network, degree_exploration, num_simulati
     mcts = OthelloMCTS(board_size, neural_network, degree_exploration, q_mode=q_mode,
                        node_cap=int(node_cap) if node_cap else num_simulations * (board_size * board_size - 3) + 64, leaves_per_step=leaves_per_step,
                        solve_leaves=solve_leaves, forced_playouts=forced_playouts, **({"gumbel": gumbel} if gumbel is not None else {}),
-                       **({"value_signs": value_signs} if value_signs != "reference" else {}), **_lib.proofs_kw(proofs), **_lib.proof_play_kw(proof_play),
-                       **_lib.selection_kw(selection), **_lib.tree_gc_kw(tree_gc))
+                       **_lib.search_kw(dict(value_signs=value_signs, proofs=proofs, proof_play=proof_play, selection=selection, tree_gc=tree_gc)))
     # training.py:34-37 (BNN examples are one-channel boards, a fresh array per round: no aliasing for them)
     board_view_type = BoardView.ONE_CHANNEL if getattr(neural_network.network_type, "name", "") == "BNN" else BoardView.TWO_CHANNELS
 
@@ -204,6 +203,15 @@ def evaluate_neural_network(board_size, total_iterations, neural_network, num_si
 
 
 # ---------------------------------------------------------------- batched engine
+# SelfPlayEngine.records(): flag, C entry, dtype of each array the entry fills, shape of a row -- the weights are the one entry that fills
+# three arrays, which come back as one tuple
+_RECORD_ROWS = (("with_visits", "oz_selfplay_visits", (np.int32,), (64,)), ("with_values", "oz_selfplay_values", (np.float64,), ()),
+                ("with_targets", "oz_selfplay_targets", (np.float32,), ()), ("with_policies", "oz_selfplay_policies", (np.float32,), (64,)),
+                ("with_surprise", "oz_selfplay_surprises", (np.float64,), ()),
+                ("with_weights", "oz_selfplay_weights", (np.float32, np.int32, np.uint8), ()))
+_POINTER = {np.int32: _lib.p_i32, np.float32: _lib.p_f32, np.float64: _lib.p_f64, np.uint8: _lib.p_u8}
+
+
 class SelfPlayEngine:
     """num_games concurrent execute_episode instances on one GPU (C ABI: oz_selfplay_*)."""
 
@@ -293,21 +301,9 @@ class SelfPlayEngine:
         include/othellozero_amd.h, "tree collection").  No record, row or counter changes; node_cap can be far below a whole game's nodes.
         "demand" collects a slot only when num_simulations more nodes might not fit, "every" every slot every round (diagnostic).  run() /
         play_to_end() with every option; run_steps() and stagger() then raise.  tree_gc_stats() counts ("Tree collection")."""
-        tree_gc_mode = _lib.check_tree_gc(tree_gc)
-        selection = _lib.check_selection(selection, gumbel=gumbel, forced_playouts=forced_playouts)
-        vs_mode = _lib.check_value_signs(value_signs)
-        proofs = _lib.check_proofs(proofs, value_signs, gumbel=gumbel, forced_playouts=forced_playouts)
-        proof_play = _lib.check_proof_play(proof_play, proofs)
-        resign = _lib.check_resign(resign, gumbel=gumbel)
-        if record_surprise and not (record_visits or gumbel):
-            raise ValueError("record_surprise needs record_visits=True or gumbel=...: the surprise is that of a recorded policy target")
-        gumbel = _lib.check_gumbel_options(gumbel, root_noise=root_noise, forced_playouts=forced_playouts, sample_moves=sample_moves,
-                                           playout_cap=playout_cap, leaves_per_step=leaves_per_step)
-        playout_cap = _lib.check_playout_cap(playout_cap, num_simulations)
-        solve_leaves = _lib.check_solve_leaves(solve_leaves)
-        root_noise = _lib.check_root_noise(root_noise)
-        forced_playouts = _lib.check_forced_playouts(forced_playouts, root_noise)
-        sample_moves = _lib.check_sample_moves(sample_moves)
+        o = _lib.check_selfplay_options(num_simulations, record_visits, leaves_per_step, root_noise, sample_moves, solve_leaves, playout_cap,
+                                        forced_playouts, record_values, gumbel, record_surprise, resign, value_signs, proofs, proof_play, selection,
+                                        tree_gc)
         lib = _lib.require_gpu()
         assert getattr(neural_network, "_h", None) is not None, "SelfPlayEngine needs a native NNetWrapper / StubNetWrapper"
         self.net = neural_network
@@ -320,52 +316,44 @@ class SelfPlayEngine:
         self._h = C.c_void_p()
         _lib.check(lib.oz_selfplay_create(C.byref(self._h), C.byref(self.cfg), neural_network._h))
         self.n, self.num_games = board_size, num_games
-        self.value_signs = value_signs
-        if vs_mode:
-            _lib.check(lib.oz_selfplay_set_value_signs(self._h, vs_mode))
-        self.proofs = proofs
-        if proofs:
-            _lib.check(lib.oz_selfplay_set_proofs(self._h, 1))
-        self.proof_play = proof_play
-        if proof_play:
-            _lib.check(lib.oz_selfplay_set_proof_play(self._h, 1))
+        self.value_signs, self.proofs, self.proof_play, self.tree_gc = o["value_signs"], o["proofs"], o["proof_play"], o["tree_gc"]
+        selection = _lib.check_selection(o["selection"])                  # (the library's form of it: flags and four numbers)
         self.selection = _lib.selection_dict(selection)
-        if selection[0]:
-            _lib.check(lib.oz_selfplay_set_selection(self._h, *selection))
         self.leaves_per_step = int(leaves_per_step)
-        if self.leaves_per_step != 1:
-            _lib.check(lib.oz_selfplay_set_leaves_per_step(self._h, self.leaves_per_step))
-        self.root_noise = root_noise
-        if root_noise is not None:
-            _lib.check(lib.oz_selfplay_set_root_noise(self._h, root_noise[0], root_noise[1]))
-        self.sample_moves = sample_moves
-        if sample_moves is not None:
-            _lib.check(lib.oz_selfplay_set_move_sampling(self._h, sample_moves[0], sample_moves[1]))
-        self.solve_leaves = solve_leaves
-        if solve_leaves:
-            _lib.check(lib.oz_selfplay_set_solve_leaves(self._h, solve_leaves))
-        self.playout_cap = playout_cap
-        if playout_cap is not None:
-            _lib.check(lib.oz_selfplay_set_playout_cap(self._h, playout_cap[0], playout_cap[1]))
-        self.forced_playouts = forced_playouts
-        if forced_playouts > 0.0:
-            _lib.check(lib.oz_selfplay_set_forced_playouts(self._h, forced_playouts))
-        self.record_values = bool(record_values) or resign is not None
-        if self.record_values:
-            _lib.check(lib.oz_selfplay_set_record_values(self._h, 1))
-        self.gumbel = gumbel
-        if gumbel is not None:
-            _lib.check(lib.oz_selfplay_set_gumbel(self._h, gumbel[0], gumbel[1], gumbel[2]))
-        self.record_surprise = bool(record_surprise)
-        if record_surprise:
-            _lib.check(lib.oz_selfplay_set_record_surprise(self._h, 1))
+        self.root_noise, self.sample_moves, self.solve_leaves, self.playout_cap = o["root_noise"], o["sample_moves"], o["solve_leaves"], o["playout_cap"]
+        self.forced_playouts, self.gumbel, self.resign = o["forced_playouts"], o["gumbel"], o["resign"]
+        self.record_values = o["record_values"] or self.resign is not None
+        self.record_surprise = o["record_surprise"]
+        self.endgame_stats = self.value_target_stats = self.proof_target_stats = None       # play_to_end's, where it ran them
+        for armed, setter, args in (                                      # (the library sees the options in this order)
+                (self.value_signs != "reference", lib.oz_selfplay_set_value_signs, (_lib.VALUE_SIGNS[self.value_signs],)),
+                (self.proofs, lib.oz_selfplay_set_proofs, (1,)),
+                (self.proof_play, lib.oz_selfplay_set_proof_play, (1,)),
+                (selection[0], lib.oz_selfplay_set_selection, selection),
+                (self.leaves_per_step != 1, lib.oz_selfplay_set_leaves_per_step, (self.leaves_per_step,)),
+                (self.root_noise is not None, lib.oz_selfplay_set_root_noise, self.root_noise),
+                (self.sample_moves is not None, lib.oz_selfplay_set_move_sampling, self.sample_moves),
+                (self.solve_leaves, lib.oz_selfplay_set_solve_leaves, (self.solve_leaves,)),
+                (self.playout_cap is not None, lib.oz_selfplay_set_playout_cap, self.playout_cap),
+                (self.forced_playouts > 0.0, lib.oz_selfplay_set_forced_playouts, (self.forced_playouts,)),
+                (self.record_values, lib.oz_selfplay_set_record_values, (1,)),
+                (self.gumbel is not None, lib.oz_selfplay_set_gumbel, self.gumbel),
+                (self.record_surprise, lib.oz_selfplay_set_record_surprise, (1,)),
+                (self.resign is not None, lib.oz_selfplay_set_resign, self.resign),
+                (self.tree_gc != "off", lib.oz_selfplay_set_tree_gc, (_lib.TREE_GC[self.tree_gc],))):
+            if armed:
+                _lib.check(setter(self._h, *args))
 
-        self.resign = resign
-        if resign is not None:
-            _lib.check(lib.oz_selfplay_set_resign(self._h, *resign))
-        self.tree_gc = tree_gc
-        if tree_gc_mode:
-            _lib.check(lib.oz_selfplay_set_tree_gc(self._h, tree_gc_mode))
+    def option_stats(self):
+        """The statistics of the options this engine was created with, under the names selfplay_batch and loop.training publish them by:
+        rows_solved, playout_stats, forced_playout_stats, resign_stats, gumbel_stats, proof_stats, proof_play_stats and tree_gc_stats are
+        what the methods of those names return now; endgame_stats, value_target_stats and proof_target_stats what play_to_end's
+        solve_records(), value_targets() and proof_targets() returned.  None for an option that is off."""
+        on = dict(rows_solved=self.solve_leaves, playout_stats=self.playout_cap is not None, forced_playout_stats=self.forced_playouts > 0.0,
+                  resign_stats=self.resign is not None, gumbel_stats=self.gumbel is not None, proof_stats=self.proofs,
+                  proof_play_stats=self.proof_play, tree_gc_stats=self.tree_gc != "off")
+        return dict({name: getattr(self, name)() if armed else None for name, armed in on.items()}, endgame_stats=self.endgame_stats,
+                    value_target_stats=self.value_target_stats, proof_target_stats=self.proof_target_stats)
 
     def tree_gc_stats(self):
         """dict(mode, collections, nodes_before_sum, nodes_kept_sum, peak_nodes, peak_kept): the tree collection that is set and, since it was
@@ -590,41 +578,17 @@ class SelfPlayEngine:
         order = np.lexsort((out["ply"], out["game_id"]))
         if with_surprise and not self.record_surprise:
             raise ValueError("records(with_surprise=True) needs an engine created with record_surprise=True")
-        if not (with_visits or with_values or with_targets or with_policies or with_surprise or with_weights):
-            return out[order]
-        ret = [out[order]]
-        got = C.c_int64()
-        if with_visits:
-            counts = np.zeros((max(out.size, 1), 64), np.int32)
-            _lib.check(_lib.load().oz_selfplay_visits(self._h, _lib.p_i32(counts), out.size, C.byref(got)))
-            assert got.value == out.size, (got.value, out.size)
-            ret.append(counts[:out.size][order])
-        if with_values:
-            values = np.zeros(max(out.size, 1), np.float64)
-            _lib.check(_lib.load().oz_selfplay_values(self._h, _lib.p_f64(values), out.size, C.byref(got)))
-            assert got.value == out.size, (got.value, out.size)
-            ret.append(values[:out.size][order])
-        if with_targets:
-            targets = np.zeros(max(out.size, 1), np.float32)
-            _lib.check(_lib.load().oz_selfplay_targets(self._h, _lib.p_f32(targets), out.size, C.byref(got)))
-            assert got.value == out.size, (got.value, out.size)
-            ret.append(targets[:out.size][order])
-        if with_policies:
-            rows = np.zeros((max(out.size, 1), 64), np.float32)
-            _lib.check(_lib.load().oz_selfplay_policies(self._h, _lib.p_f32(rows), out.size, C.byref(got)))
-            assert got.value == out.size, (got.value, out.size)
-            ret.append(rows[:out.size][order])
-        if with_surprise:
-            sur = np.zeros(max(out.size, 1), np.float64)
-            _lib.check(_lib.load().oz_selfplay_surprises(self._h, _lib.p_f64(sur), out.size, C.byref(got)))
-            assert got.value == out.size, (got.value, out.size)
-            ret.append(sur[:out.size][order])
-        if with_weights:
-            w, c, t0 = np.zeros(max(out.size, 1), np.float32), np.zeros(max(out.size, 1), np.int32), np.zeros(max(out.size, 1), np.uint8)
-            _lib.check(_lib.load().oz_selfplay_weights(self._h, _lib.p_f32(w), _lib.p_i32(c), _lib.p_u8(t0), out.size, C.byref(got)))
-            assert got.value == out.size, (got.value, out.size)
-            ret.append((w[:out.size][order], c[:out.size][order], t0[:out.size][order]))
-        return tuple(ret)
+        want = dict(with_visits=with_visits, with_values=with_values, with_targets=with_targets, with_policies=with_policies,
+                    with_surprise=with_surprise, with_weights=with_weights)
+        ret, got, rows = [out[order]], C.c_int64(), max(out.size, 1)
+        for flag, entry, dtypes, row in _RECORD_ROWS:
+            if want[flag]:
+                arrays = [np.zeros((rows,) + row, dtype) for dtype in dtypes]
+                _lib.check(getattr(_lib.load(), entry)(self._h, *(_POINTER[a.dtype.type](a) for a in arrays), out.size, C.byref(got)))
+                assert got.value == out.size, (got.value, out.size)
+                arrays = [a[:out.size][order] for a in arrays]
+                ret.append(arrays[0] if len(arrays) == 1 else tuple(arrays))
+        return tuple(ret) if len(ret) > 1 else ret[0]
 
     def solve_records(self, max_empties, first_record=0):
         """oz_selfplay_solve_records: the completed records from `first_record` on whose position has at most max_empties empties get the
@@ -796,17 +760,11 @@ def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations
     targets, exact_empties = endgame_targets).  The float32 targets come back last -- (records, [counts,] targets) -- or, with expand, as
     the examples' float32 z; with expand it needs alias_final=False.  selfplay_batch.value_target_stats holds the last call's statistics
     (None when off)."""
-    _lib.check_tree_gc(tree_gc)
-    _lib.check_selection(selection, gumbel=gumbel, forced_playouts=forced_playouts)
-    _lib.check_value_signs(value_signs)
-    _lib.check_proofs(proofs, value_signs, gumbel=gumbel, forced_playouts=forced_playouts)
-    proof_play = _lib.check_proof_play(proof_play, proofs)
-    pt_kw = {"proof_targets": True} if _lib.check_proof_targets(proof_targets, proof_play) else {}
-    selfplay_batch.proof_stats = selfplay_batch.proof_play_stats = selfplay_batch.proof_target_stats = None
     vt_on = _lib.check_value_target(value_target, expand and alias_final)[0] != _lib.VALUE_TARGET_OUTCOME
-    gumbel = _lib.check_gumbel_options(gumbel, root_noise=root_noise, forced_playouts=forced_playouts, sample_moves=sample_moves,
-                                       playout_cap=playout_cap, leaves_per_step=leaves_per_step)
-    if gumbel is not None and expand:
+    o = _lib.check_selfplay_options(num_simulations, record_visits, leaves_per_step, root_noise, sample_moves, solve_leaves, playout_cap,
+                                    forced_playouts, vt_on, gumbel, False, resign, value_signs, proofs, proof_play, selection, tree_gc)
+    proof_targets = _lib.check_proof_targets(proof_targets, o["proof_play"])
+    if o["gumbel"] is not None and expand:
         raise ValueError("selfplay_batch: gumbel with expand=True is not offered; expand the rows with loop.examples_from_records(policies=...)")
     if surprise_weight is not None:
         try:
@@ -816,81 +774,24 @@ def selfplay_batch(neural_network, board_size=8, num_games=4096, num_simulations
         sw_frac = _lib.check_surprise_frac(sw_frac)
         if expand:
             raise ValueError("selfplay_batch: surprise_weight with expand=True is not offered: the host example path writes 8 examples per record")
-        if not (record_visits or gumbel is not None):
+        if not (record_visits or o["gumbel"] is not None):
             raise ValueError("selfplay_batch: surprise_weight needs record_visits=True or gumbel=...: the surprise is that of a recorded policy target")
-    forced_playouts = _lib.check_forced_playouts(forced_playouts, _lib.check_root_noise(root_noise))
-    playout_cap = _lib.check_playout_cap(playout_cap, num_simulations)
-    solve_leaves = _lib.check_solve_leaves(solve_leaves)
+        o["record_surprise"] = True                        # (past the engine's rule for it, in this function's words just above)
     endgame_targets = _lib.check_endgame_targets(endgame_targets, expand and alias_final)
-    resign = _lib.check_resign(resign, gumbel=gumbel)
-    selfplay_batch.resign_stats = None
     eng = SelfPlayEngine(neural_network, board_size, num_games, num_simulations, degree_exploration, policy_temperature,
-                         e_greedy, seed, first_game_id, q_mode=q_mode, record_visits=record_visits, leaves_per_step=leaves_per_step,
-                         root_noise=root_noise, sample_moves=sample_moves, solve_leaves=solve_leaves, playout_cap=playout_cap,
-                         **({"forced_playouts": forced_playouts} if forced_playouts > 0.0 else {}), **({"record_values": True} if vt_on else {}),
-                         **({"gumbel": gumbel} if gumbel is not None else {}), **({"record_surprise": True} if surprise_weight is not None else {}),
-                         **({"resign": resign} if resign is not None else {}), **({"value_signs": value_signs} if value_signs != "reference" else {}),
-                         **_lib.proofs_kw(proofs), **_lib.proof_play_kw(proof_play), **_lib.selection_kw(selection), **_lib.tree_gc_kw(tree_gc),
+                         e_greedy, seed, first_game_id, q_mode=q_mode,
+                         **_lib.engine_kw(o, always=("record_visits", "leaves_per_step", "root_noise", "sample_moves", "solve_leaves", "playout_cap")),
                          **({"node_cap": int(node_cap)} if node_cap else {}))
+    got = eng.play_to_end(with_visits=record_visits, endgame_targets=endgame_targets, value_target=value_target,
+                          with_policies=o["gumbel"] is not None, proof_targets=proof_targets)
+    got = got if isinstance(got, tuple) else (got,)        # records, [counts,] [targets,] [policies]
     selfplay_batch.surprise_stats = None
-    selfplay_batch.tree_gc_stats = None
-
-    def collected(ret):
-        selfplay_batch.tree_gc_stats = eng.tree_gc_stats() if tree_gc != "off" else None
-        return ret
-
-    def weighted(ret):
-        if surprise_weight is None:
-            return ret
+    if surprise_weight is not None:
         selfplay_batch.surprise_stats = eng.surprise_weights(sw_frac, sw_seed)
-        return (ret if isinstance(ret, tuple) else (ret,)) + eng.records(with_surprise=True, with_weights=True)[1:]
-    selfplay_batch.value_target_stats = None
-    selfplay_batch.gumbel_stats = None
-    if gumbel is not None:                                 # (the options' statistics as below; the rows come last)
-        got = eng.play_to_end(with_visits=record_visits, endgame_targets=endgame_targets, value_target=value_target, with_policies=True, **pt_kw)
-        selfplay_batch.gumbel_stats = eng.gumbel_stats()
-        selfplay_batch.endgame_stats = getattr(eng, "endgame_stats", None)
-        selfplay_batch.value_target_stats = getattr(eng, "value_target_stats", None)
-        selfplay_batch.forced_playout_stats = selfplay_batch.playout_stats = None
-        selfplay_batch.rows_solved = eng.rows_solved() if solve_leaves else None
-        selfplay_batch.proof_stats = eng.proof_stats() if proofs else None
-        selfplay_batch.proof_play_stats = eng.proof_play_stats() if proof_play else None
-        selfplay_batch.proof_target_stats = getattr(eng, "proof_target_stats", None)
-        return collected(weighted(got))
-    if vt_on:
-        got = eng.play_to_end(with_visits=record_visits, endgame_targets=endgame_targets, value_target=value_target, **pt_kw)
-        rec, counts, targets = got if record_visits else (got[0], None, got[1])
-        selfplay_batch.endgame_stats = getattr(eng, "endgame_stats", None)
-        selfplay_batch.value_target_stats = eng.value_target_stats
-        selfplay_batch.forced_playout_stats = eng.forced_playout_stats() if forced_playouts > 0.0 else None
-        selfplay_batch.playout_stats = eng.playout_stats() if playout_cap is not None else None
-        selfplay_batch.resign_stats = eng.resign_stats() if resign is not None else None
-        selfplay_batch.rows_solved = eng.rows_solved() if solve_leaves else None
-        selfplay_batch.proof_stats = eng.proof_stats() if proofs else None
-        selfplay_batch.proof_play_stats = eng.proof_play_stats() if proof_play else None
-        selfplay_batch.proof_target_stats = getattr(eng, "proof_target_stats", None)
-        if expand:
-            return collected(expand_examples(rec, board_size, alias_final, visits=counts, target_temperature=target_temperature, values=targets))
-        return collected(weighted((rec, counts, targets) if record_visits else (rec, targets)))
-    selfplay_batch.endgame_stats = selfplay_batch.rows_solved = selfplay_batch.playout_stats = selfplay_batch.forced_playout_stats = None
-    if record_visits:
-        rec, counts = eng.play_to_end(with_visits=True, endgame_targets=endgame_targets, **pt_kw)
-        selfplay_batch.forced_playout_stats = eng.forced_playout_stats() if forced_playouts > 0.0 else None
-        selfplay_batch.playout_stats = eng.playout_stats() if playout_cap is not None else None
-        selfplay_batch.resign_stats = eng.resign_stats() if resign is not None else None
-        selfplay_batch.rows_solved = eng.rows_solved() if solve_leaves else None
-        selfplay_batch.proof_stats = eng.proof_stats() if proofs else None
-        selfplay_batch.proof_play_stats = eng.proof_play_stats() if proof_play else None
-        selfplay_batch.proof_target_stats = getattr(eng, "proof_target_stats", None)
-        selfplay_batch.endgame_stats = getattr(eng, "endgame_stats", None)
-        return collected(expand_examples(rec, board_size, alias_final, visits=counts, target_temperature=target_temperature) if expand else weighted((rec, counts)))
-    rec = eng.play_to_end(endgame_targets=endgame_targets, **pt_kw)
-    selfplay_batch.forced_playout_stats = eng.forced_playout_stats() if forced_playouts > 0.0 else None
-    selfplay_batch.playout_stats = eng.playout_stats() if playout_cap is not None else None
-    selfplay_batch.resign_stats = eng.resign_stats() if resign is not None else None
-    selfplay_batch.rows_solved = eng.rows_solved() if solve_leaves else None
-    selfplay_batch.proof_stats = eng.proof_stats() if proofs else None
-    selfplay_batch.proof_play_stats = eng.proof_play_stats() if proof_play else None
-    selfplay_batch.proof_target_stats = getattr(eng, "proof_target_stats", None)
-    selfplay_batch.endgame_stats = getattr(eng, "endgame_stats", None)
-    return collected(expand_examples(rec, board_size, alias_final) if expand else rec)
+        got += eng.records(with_surprise=True, with_weights=True)[1:]
+    for name, stats in eng.option_stats().items():
+        setattr(selfplay_batch, name, stats)
+    if expand:
+        return expand_examples(got[0], board_size, alias_final, visits=got[1] if record_visits else None, target_temperature=target_temperature,
+                               values=got[-1] if vt_on else None)
+    return got if len(got) > 1 else got[0]

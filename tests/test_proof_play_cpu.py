@@ -283,4 +283,5 @@ def test_refusals_before_the_library_is_touched(monkeypatch):
         loop.training(proof_play=True, **kw)
     with pytest.raises(ValueError, match="proof_play=True"):
         loop.training(value_signs="sound", proofs=True, proof_targets=True, **kw)
-    assert _lib.proof_play_kw(False) == {} and _lib.proof_play_kw((False, False)) == {} and _lib.proof_play_kw((True, False)) == {"proof_play": (True, False)}
+    kw = lambda proof_play: _lib.search_kw(_lib.check_search_options(value_signs="sound", proofs=True, proof_play=proof_play, pairs=True))
+    assert "proof_play" not in kw(False) and "proof_play" not in kw((False, False)) and kw((True, False))["proof_play"] == (True, False)

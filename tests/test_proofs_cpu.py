@@ -263,4 +263,5 @@ def test_python_surface_refuses_before_the_library_is_touched(monkeypatch):
         loop.evaluate_against_opponent_batch(6, net, 4, 12, 1.0, ("minimax", 1), proofs=True)
     assert _lib.check_proofs_pair((True, False), ("sound", "reference")) == (True, False)
     assert _lib.check_proofs_pair(False, ("sound", "reference")) == (False, False)
-    assert _lib.proofs_kw(False) == {} and _lib.proofs_kw((False, False)) == {} and _lib.proofs_kw((True, False)) == {"proofs": (True, False)}
+    kw = lambda proofs: _lib.search_kw(_lib.check_search_options(value_signs="sound", proofs=proofs, pairs=True))
+    assert "proofs" not in kw(False) and "proofs" not in kw((False, False)) and kw((True, False))["proofs"] == (True, False)

@@ -211,9 +211,10 @@ def test_check_selection_arguments():
     assert ck(SETTINGS["all"]) == (7, 0.2, 0.1, 20.0, 2.0)
     assert ck(dict(fpu=(0.0, 4.0), cpuct_growth=(1e-9, 0.0)))[0] == 3
     assert _lib.selection_dict(ck(SETTINGS["all"])) == dict(fpu=(0.2, 0.1), cpuct_growth=(20.0, 2.0), prior_first=True)
-    assert _lib.selection_dict(ck(None)) is None and _lib.selection_kw(None) == {} and _lib.selection_kw({}) == {}
-    assert _lib.selection_kw(SETTINGS["fpu"]) == {"selection": SETTINGS["fpu"]}
-    assert _lib.selection_kw((None, SETTINGS["fpu"])) == {"selection": (None, SETTINGS["fpu"])} and _lib.selection_kw((None, None)) == {}
+    kw = lambda selection: _lib.search_kw(_lib.check_search_options(selection=selection, pairs=True))
+    assert _lib.selection_dict(ck(None)) is None and kw(None) == {} and kw({}) == {}
+    assert kw(SETTINGS["fpu"]) == {"selection": SETTINGS["fpu"]}
+    assert kw((None, SETTINGS["fpu"])) == {"selection": (None, SETTINGS["fpu"])} and kw((None, None)) == {}
     nan, inf = float("nan"), float("inf")
     for bad in ("fpu", 1, (0.2, 0.1), dict(fpu=0.2), dict(fpu=(0.2,)), dict(fpu=(0.2, 0.1, 0.0)), dict(fpu=(-0.1, 0.1)), dict(fpu=(0.2, 4.5)),
                 dict(fpu=(nan, 0.1)), dict(fpu=(0.2, nan)), dict(fpu=("a", 0.1)), dict(fpu=(True, 0.1)), dict(cpuct_growth=(0.0, 1.0)),

@@ -124,7 +124,8 @@ def test_unknown_modes_raise_before_the_library_is_touched(monkeypatch):
         agents.arena_batch(object(), object(), 6, 4, 8, tree_gc=("every", "off", "off"))
     assert [_lib.check_tree_gc(m) for m in ("off", "demand", "every")] == [0, 1, 2]
     assert _lib.check_tree_gc_pair("demand") == (1, 1) and _lib.check_tree_gc_pair(("off", "every")) == (0, 2)
-    assert _lib.tree_gc_kw("off") == {} and _lib.tree_gc_kw(("off", "off")) == {} and _lib.tree_gc_kw("every") == {"tree_gc": "every"}
+    kw = lambda tree_gc: _lib.search_kw(_lib.check_search_options(tree_gc=tree_gc, pairs=True))
+    assert kw("off") == {} and kw(("off", "off")) == {} and kw("every") == {"tree_gc": "every"}
 
 
 def test_keyword_is_on_every_surface_and_defaults_to_off():
