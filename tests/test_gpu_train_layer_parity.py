@@ -17,14 +17,35 @@ exactly 0.0 on the device); confirmed on the CPU with oracle/train_ref.py before
 dz columns of fc1 / fc2 (units dead or dropped in both rows) and every column of the 3x3 layers, 5 boards 0.93.
 
 Shapes: the smallest that reach each path, read off the launchers (oz_gemm_f32_launch, oz_gemm_h2_launch, oz_gemm_b3_launch, t_wgrad) and proven from
-the plan.  Left out, with the reason:
-  * f16x2 H2BigPP / H2MidPP (the 256 / 192-row ping-pong tiles) and the bf16x3 256-row tile need ceil(M / 256) x (N / 256) >= 192 row tiles: at 512
-    filters more than 24320 rows = 381 boards of 8x8 (conv2; conv3's data gradient) or 676 of 6x6, the same 50 MB per full-size tensor either
-    way -- a trainer of about 1.4 GB, above the 1 GB this file allows itself, and a whole-tensor float64 weight-gradient reference of more than
-    100 GFLOP per layer.  The forward and the data gradient of such a case could be checked on the sampled boards alone, without that reference;
-    that is not done here, so the trainer's big-tile data gradient through the zero-bordered buffer stays untested (the inference matrix,
-    test_gpu_layer_parity.py, runs the same tile configurations on the forward).
+the plan.
+
+The chip-filling tiles (the `chip` cases: 8x8, 512 filters, 383 .. 1598 boards).  f16x2 H2MidPP / H2BigPP (the 192 / 256-row ping-pong tiles) and
+bf16x3's k_gemm_b3_big (256 rows, 'valid' layers only) need ceil(M / 256) x (N / 256) >= 192 blocks: at 512 filters more than 24320 rows = 381
+boards of 64 pixels (conv2; conv3's data gradient), 676 of 36 (conv3; conv4's data gradient), 1521 of 16 (conv4).  What is particular to the
+trainer on them is the fp32-row epilogue with relu = 0, scale = wscale[l] / dscale[l], and the gather over the zero-bordered dz with pad = 0.
+The cases reach H2MidPP and H2BigPP on every forward and every data gradient of the 3x3 layers (h2-b1023-mid36 and h2-b1598-big16 add what the
+sizes shared with bf16x3 leave: H2MidPP on the 36-pixel launches, H2BigPP on conv4's forward, which takes H2MidPP from 1521 to 1536 boards and
+H2BigPP from 1537 on) and k_gemm_b3_big on the forward of conv3 / conv4 and the data gradients of conv3 / conv4 -- every launch it can serve,
+conv2 and its data gradient being 'same' -- each with a partly filled last row tile (but H2MidPP at 684 boards: 228 whole tiles; 383 boards
+have the partly filled one).  b3-b37-of-684 runs the 684-board launches on 37 live boards of a trainer that has done a full step.
+Which B reaches which kernel is train_layer_ref.tile_rule, asserted without a device by test_train_layer_parity_cpu.py and here against the
+plan.  The k-slices are asserted exactly: 1 on the mid / big tiles, trainer_kslices on the 128-row tile -- which is 1 as well once that launch
+has more than 128 blocks (more than 8192 rows: the split must fit one round of the chip), so at these sizes H2LowPP and k_gemm_b3 run unsplit too.
+Forward and data gradient: the sharp margins, on the sampled boards (three runs: every row position of a 256-row tile; the first, a middle and the
+last tile) -- per-row properties of an 8-term sum, the same at any batch.  Weight gradients of the 3x3 layers: every 16th input channel, all taps
+and output columns, ALL rows (train_layer_ref.sampled_ci), at the coarse bound; what that bound sees over 24 000 rows and more is rows, octets
+and slabs that go missing, not a lost plane product (test_chip_wgrad_bound_sees_lost_rows).  Kept columns, confirmed with oracle/train_ref.py on
+this network before the sizes were fixed: at 37 and at 383 boards every dz column of every layer is alive (1.00).
+Budget: one layer's tensors at a time on the host (of each downloaded tensor only the sampled boards stay), the trainer deleted before the next
+case.  Measured: a bf16x3 trainer of 1535 boards holds 7.3 GB on the device (3.8 GB at 684, 2.5 GB at 383), the test process 1.7 GB on the host
+at its peak, a case takes 1 .. 2.2 s; the cases below 383 boards stay within 1 GB.
+
+Left out, with the reason:
   * H2Small cannot be reached from the trainer: oz_gemm_h2_launch takes it only without a split-K buffer, and the trainer always passes one.
+  * H2MidPP / H2BigPP from a short call on a large f16x2 trainer: that launcher is keyed on the call's boards, so a short call IS a small case.
+  * k_gemm_b3_big with k-slices > 1 or on a 'same' layer, and the network object's mixed plan (b3_big_rows with may_mix): oz_gemm_b3_launch asks
+    for neither (test_gpu_layer_parity.py and test_b3_mix_plan_cpu.py hold them on the inference side).
+  * 6x6 on the chip-filling tiles: the same kernels and the same gather at other strides, 676 boards and more; not run.
 One line per (case, tensor, layer) is printed: the worst step's err, E32 and ratio (the table of one run: profiles/train_layer_parity_ratios.txt)."""
 import numpy as np
 import pytest
@@ -73,18 +94,24 @@ def _sel(B, pixels):
     return np.concatenate([np.arange(b0, b0 + nb) for b0, nb in R.sample_runs(B, pixels)])
 
 
-def measure(tr, w, n, C, B, batch):
-    """one step; -> (sampled records [(tensor, layer, gpu, ref32, ref64)], weight-gradient rows [(layer, err, e32, kept)], plan)"""
+def measure(tr, w, n, C, B, batch, sampled_wgrad=False):
+    """one step; -> (sampled records [(tensor, layer, gpu, ref32, ref64)], weight-gradient rows [(layer, err, e32, kept)], plan).
+    One layer at a time: of every downloaded tensor only the sampled boards are kept (and, with sampled_wgrad, every 16th input channel of the 3x3
+    layers' inputs for the weight gradient: train_layer_ref.sampled_ci) before the next one is fetched"""
     tr.forward_backward(*batch)                                    # raises on an f16x2 range refusal
     plan = tr.plan()
-    acts = [tr.activation(l, B) for l in range(6)]
     sampled, wrows = [], []
+    x = tr.activation(0, B)
     for l in range(1, 6):
         g = T.geometry(n, C, l)
-        x = acts[l - 1] if l <= 3 else acts[l - 1].reshape(B, -1)
+        if l > 3:
+            x = x.reshape(B, -1)
         dz = tr.dz(l, B)
         assert dz.shape == (B, g["Hz"], g["Hz"], g["Co"])
         dzi = dz[:, g["zoff"]:g["zoff"] + g["Hout"], g["zoff"]:g["zoff"] + g["Hout"], :]
+        if g["zoff"]:
+            dzi = np.ascontiguousarray(dzi)                        # (the bordered buffer goes)
+        del dz
         s = _sel(B, g["Hout"] ** 2)
         z = tr.preact(l, B)[s]
         sampled.append(("fwd", l, z, T.forward_z(w, l, x[s], np.float32), T.forward_z(w, l, x[s], np.float64)))
@@ -92,9 +119,14 @@ def measure(tr, w, n, C, B, batch):
         da = tr.dgrad(l - 1, B)[s]
         r64 = T.dgrad(w, l, dzi[s], np.float64)
         sampled.append(("dgrad", l, da.reshape(r64.shape), T.dgrad(w, l, dzi[s], np.float32), r64))
+        got = tr.get_grad(6 * l)
+        if sampled_wgrad and l <= 3:
+            x, got = T.sampled_ci(x, 3), T.sampled_ci(got, 2)
         r64 = T.wgrad(l, x, dzi, np.float64)
-        err, kept = T.statistic(tr.get_grad(6 * l), r64)
+        err, kept = T.statistic(got, r64)
         wrows.append((l, err, T.statistic(T.wgrad(l, x, dzi, np.float32), r64)[0], kept))
+        del x, dzi, r64, got
+        x = tr.activation(l, B) if l < 5 else None
     dl, dv = tr.head_grads(B)
     r64 = T.heads_dgrad(w, dl, dv, np.float64)
     sampled.append(("heads", 5, tr.dgrad(5, B).reshape(r64.shape), T.heads_dgrad(w, dl, dv, np.float32), r64))
@@ -135,8 +167,16 @@ def evaluate(steps, precision, n, C, B, kind):
 
 # ------------------------------------------------------------------ the matrix
 # expect: layer -> the plan fields the case exists for.  f32 runs 128 filters, the split modes 256 (their minimum).
-def _case(name, precision, n, C, B, expect, Bmax=None, kind="bisparse", sharp_wgrad=()):
-    return dict(name=name, precision=precision, n=n, C=C, B=B, Bmax=Bmax or B, kind=kind, expect=expect, sharp_wgrad=sharp_wgrad)
+def _case(name, precision, n, C, B, expect, Bmax=None, kind="bisparse", sharp_wgrad=(), chip=False):
+    """chip: a case of the chip-filling tiles (8x8, 512 filters, 383 boards and more) -- the 3x3 layers' weight gradients on the sampled input
+    channels, and a full Bmax-board step first where the call is shorter (a used trainer: stale packed operands lie behind the live rows)"""
+    return dict(name=name, precision=precision, n=n, C=C, B=B, Bmax=Bmax or B, kind=kind, expect=expect, sharp_wgrad=sharp_wgrad, chip=chip)
+
+
+def _chip(name, precision, B, tiles, Bmax=None):
+    """tiles: {layer: (forward kernel, data-gradient kernel)}; the weight gradients run on the octet kernels, split 8 (f16x2: 32 tiles) / 4 (bf16x3: 64)"""
+    wg = dict(wgrad_kernel="oct_h2", wgrad_msplit=8) if precision == "f16x2" else dict(wgrad_kernel="oct_b3", wgrad_msplit=4)
+    return _case(name, precision, 8, 512, B, {l: dict(wg, fwd_kernel=f, dgrad_kernel=d) for l, (f, d) in tiles.items()}, Bmax=Bmax, chip=True)
 
 
 _PIX = dict(dgrad_kernel="f32_std_pixmajor", dgrad_tap_skip=True, dgrad_kslices=1)
@@ -176,6 +216,23 @@ CASES = [
     # a call below the capacity: the b3 launches are sized for Bmax (grid, k split), the rows beyond the call must not enter
     _case("b3-b37-of-64", "bf16x3", 8, 256, 37, {l: dict(fwd_kernel="b3", dgrad_kernel="b3", wgrad_kernel="oct_b3") for l in (1, 2, 3)}, Bmax=64),
     _case("b3-dense-net", "bf16x3", 6, 256, 32, {1: dict(fwd_kernel="b3", wgrad_kernel="oct_b3")}, kind="dense"),
+    # ---- the chip-filling tiles: 8x8, 512 filters, B chosen so that the last row tile of the named launches is partly filled (train_layer_ref.tile_rule,
+    # asserted on the CPU by test_train_layer_parity_cpu.py).  f16x2: H2MidPP (192 rows) / H2BigPP (256 rows); conv3's data gradient reads the zero-bordered dz
+    _chip("h2-b383-mid", "f16x2", 383, {1: ("h2_midpp", "h2_midpp"), 2: ("h2_lowpp", "h2_midpp"), 3: ("h2_lowpp", "h2_lowpp")}),
+    _chip("h2-b447-big", "f16x2", 447, {1: ("h2_bigpp", "h2_bigpp"), 2: ("h2_lowpp", "h2_bigpp"), 3: ("h2_lowpp", "h2_lowpp")}),
+    _chip("h2-b684", "f16x2", 684, {1: ("h2_midpp", "h2_midpp"), 2: ("h2_bigpp", "h2_midpp"), 3: ("h2_lowpp", "h2_bigpp")}),
+    # (what the sizes shared with bf16x3 leave to H2MidPP: the 36-pixel launches -- conv3's forward, conv4's data gradient)
+    _chip("h2-b1023-mid36", "f16x2", 1023, {1: ("h2_bigpp", "h2_bigpp"), 2: ("h2_midpp", "h2_bigpp"), 3: ("h2_lowpp", "h2_midpp")}),
+    _chip("h2-b1535", "f16x2", 1535, {1: ("h2_bigpp", "h2_bigpp"), 2: ("h2_bigpp", "h2_bigpp"), 3: ("h2_midpp", "h2_bigpp")}),
+    # (and to H2BigPP: conv4's forward, 1537 boards and more)
+    _chip("h2-b1598-big16", "f16x2", 1598, {1: ("h2_midpp", "h2_midpp"), 2: ("h2_bigpp", "h2_midpp"), 3: ("h2_bigpp", "h2_bigpp")}),
+    # bf16x3: k_gemm_b3_big on the 'valid' layers only (conv2 and its data gradient stay on the 128-row tile at every size)
+    _chip("b3-b383-big", "bf16x3", 383, {1: ("b3", "b3"), 2: ("b3", "b3_big"), 3: ("b3", "b3")}),
+    _chip("b3-b684-big", "bf16x3", 684, {1: ("b3", "b3"), 2: ("b3_big", "b3"), 3: ("b3", "b3_big")}),
+    _chip("b3-b1535-big", "bf16x3", 1535, {1: ("b3", "b3"), 2: ("b3_big", "b3_big"), 3: ("b3_big", "b3_big")}),
+    # 37 boards on a trainer of 684 that has done a full step: 1332 rows of conv3's forward = five whole 256-row tiles, one partly filled, 91 dead.
+    # (No f16x2 twin: that launcher is keyed on the call's boards, so a short call is one of the small cases above)
+    _chip("b3-b37-of-684", "bf16x3", 37, {1: ("b3", "b3"), 2: ("b3_big", "b3"), 3: ("b3", "b3_big")}, Bmax=684),
 ]
 CASE_BY_NAME = {c["name"]: c for c in CASES}
 _results = {}
@@ -187,8 +244,11 @@ def run_case(case):
         precision, n, C, B, kind = (case[k] for k in ("precision", "n", "C", "B", "kind"))
         w = R.network_weights(n, C, kind)
         tr = _trainer(precision, n, C, case["Bmax"], kind)
+        if case["chip"] and B < case["Bmax"]:
+            tr.forward_backward(*_batch(n, case["Bmax"], 899))       # a used trainer: every packed operand filled up to its capacity
         count = 1 if B >= T.ROWS_FOR_NORM else -(-T.ROWS_FOR_NORM // B)
-        steps = [measure(tr, w, n, C, B, _batch(n, B, 900 + 17 * k)) for k in range(count)]
+        steps = [measure(tr, w, n, C, B, _batch(n, B, 900 + 17 * k), sampled_wgrad=case["chip"]) for k in range(count)]
+        del tr                                                       # (the device memory goes before the next case)
         rows, plan = evaluate(steps, precision, n, C, B, kind)
         worst = {}
         for r in rows:
@@ -213,9 +273,19 @@ def test_train_layer_parity(oz, name):
     precision = case["precision"]
     if precision != "f32":
         want = {"f16x2": "h2_", "bf16x3": "b3"}[precision]
+        # the launchers' rule restated (train_layer_ref.tile_plan): f16x2 is keyed on the call's boards, bf16x3 on the trainer's capacity
+        rule = T.tile_plan(precision, case["n"], case["C"], case["B"] if precision == "f16x2" else case["Bmax"])
         for l in (1, 2, 3):
             assert plan[l]["fwd_kernel"].startswith(want) and plan[l]["dgrad_kernel"].startswith(want), plan[l]
-            assert plan[l]["fwd_kslices"] > 1 and plan[l]["dgrad_kslices"] > 1, plan[l]           # below the big grid the trainer always splits the k loop
+            for side in ("fwd", "dgrad"):
+                kernel, split = plan[l][side + "_kernel"], plan[l][side + "_kslices"]
+                assert (kernel, split) == (rule[l][side + "_kernel"], rule[l][side + "_kslices"]), (l, side, plan[l], rule[l])
+                if kernel in T.UNSPLIT_KERNELS:
+                    assert split == 1, plan[l]                       # the mid / big tiles never split the k loop
+                else:
+                    # the 128-row tile: split until one round of the chip is full -- always > 1 below the chip-filling sizes; at those, a launch
+                    # of more than 128 blocks of 128 rows has no room for a second slice (trainer_kslices)
+                    assert kernel in ("h2_lowpp", "b3") and (split > 1 or case["chip"]), plan[l]
     for l in (4, 5):
         assert plan[l]["fwd_kernel"].startswith("f32_") and plan[l]["dgrad_kernel"].startswith("f32_") and plan[l]["wgrad_kernel"] == "taps_f32", plan[l]
     assert len(rows) == count * (5 * 3 + 1)

@@ -30,7 +30,12 @@ k-step holds 32 non-zero products whose summation inside the instruction is unsp
 holds about one, and nothing is left out there.  The second bracket (every product rounded into the fp32 accumulator on its own: the least exact an
 fp32 accumulator can be) gives 1.1 .. 2.1, and the margin is now taken from it.
 So the issue's expectation that a weight gradient over 72 .. 512 rows separates a lost bf16x3 term does not hold under this yardstick: such a term
-costs 9 .. 17 x E32 there, inside the coarse bound."""
+costs 9 .. 17 x E32 there, inside the coarse bound.
+The chip-filling tiles (the GPU matrix's `chip` cases, 383 boards and more at 8x8 / 512 filters): the launchers' tile and k-split rule is restated
+in train_layer_ref (tile_rule, trainer_kslices) and every case's batch is shown here to reach the kernels it names, 64 boards fewer not to.  Their
+weight gradients sum 6000 .. 100 000 rows; the coarse bound cannot see a lost plane product there.  What it does see is lost ROWS: on conv3 at 383
+boards (13788 rows, a block of 32 x 64 channels) the complete models give 1.7 (bf16x3) and 1.2 (f16x2) x E32, one octet of boards skipped 4 x 10^5,
+one slab of the octet split never added 9 x 10^5 and more."""
 import numpy as np
 import pytest
 
@@ -240,6 +245,117 @@ def test_dense_weight_gradients_and_long_sums_are_coarse():
     assert T.wgrad_class("f32", 4, 32) == "coarse" and T.wgrad_class("f32", 5, 32) == "coarse"
     assert T.wgrad_class("bf16x3", 1, 72) == "coarse" and T.wgrad_class("bf16x3", 2, 32) == "coarse" and T.wgrad_class("bf16x3", 3, 64) == "coarse"
     assert T.wgrad_class("f16x2", 1, 8192) == "coarse"               # beyond what the model was evaluated on
+
+
+# ------------------------------------------------------------------ the chip-filling tiles: which batch reaches which kernel
+# the GPU matrix's chip cases (8x8, 512 filters): boards -> {layer: (forward kernel, data-gradient kernel)} of the 3x3 layers.  f16x2 is keyed on
+# the call's boards, bf16x3 on the trainer's capacity
+CHIP_PLANS = {
+    ("f16x2", 383): {1: ("h2_midpp", "h2_midpp"), 2: ("h2_lowpp", "h2_midpp"), 3: ("h2_lowpp", "h2_lowpp")},
+    ("f16x2", 447): {1: ("h2_bigpp", "h2_bigpp"), 2: ("h2_lowpp", "h2_bigpp"), 3: ("h2_lowpp", "h2_lowpp")},
+    ("f16x2", 684): {1: ("h2_midpp", "h2_midpp"), 2: ("h2_bigpp", "h2_midpp"), 3: ("h2_lowpp", "h2_bigpp")},
+    ("f16x2", 1023): {1: ("h2_bigpp", "h2_bigpp"), 2: ("h2_midpp", "h2_bigpp"), 3: ("h2_lowpp", "h2_midpp")},
+    ("f16x2", 1535): {1: ("h2_bigpp", "h2_bigpp"), 2: ("h2_bigpp", "h2_bigpp"), 3: ("h2_midpp", "h2_bigpp")},
+    ("f16x2", 1598): {1: ("h2_midpp", "h2_midpp"), 2: ("h2_bigpp", "h2_midpp"), 3: ("h2_bigpp", "h2_bigpp")},
+    ("bf16x3", 383): {1: ("b3", "b3"), 2: ("b3", "b3_big"), 3: ("b3", "b3")},
+    ("bf16x3", 684): {1: ("b3", "b3"), 2: ("b3_big", "b3"), 3: ("b3", "b3_big")},
+    ("bf16x3", 1535): {1: ("b3", "b3"), 2: ("b3_big", "b3_big"), 3: ("b3_big", "b3_big")},
+}
+# what each of the three smallest exists for: (layer, side, kernel) that 64 boards fewer must NOT reach
+CHIP_FIRST = {
+    ("f16x2", 383): [(1, 0, "h2_midpp"), (1, 1, "h2_midpp"), (2, 1, "h2_midpp")],
+    ("f16x2", 447): [(1, 0, "h2_bigpp"), (1, 1, "h2_bigpp"), (2, 1, "h2_bigpp")],
+    ("f16x2", 684): [(2, 0, "h2_bigpp"), (3, 1, "h2_bigpp")],
+    ("bf16x3", 383): [(2, 1, "b3_big")],
+    ("bf16x3", 684): [(2, 0, "b3_big"), (3, 1, "b3_big")],
+}
+TILE_ROWS = {"h2_lowpp": 128, "h2_midpp": 192, "h2_bigpp": 256, "b3": 128, "b3_big": 256}
+
+
+def _kernels(arith, B):
+    p = T.tile_plan(arith, 8, 512, B)
+    return {l: (p[l]["fwd_kernel"], p[l]["dgrad_kernel"]) for l in p}, p
+
+
+@pytest.mark.parametrize("arith,B", sorted(CHIP_PLANS))
+def test_chip_cases_reach_their_tiles(arith, B):
+    """the launchers' tile rule restated (train_layer_ref.tile_rule / trainer_kslices): every chip case of the GPU matrix reaches the kernels it
+    names, with one k-slice on the mid / big tiles and a partly filled last row tile; 64 boards fewer do not reach them"""
+    kernels, plan = _kernels(arith, B)
+    assert kernels == CHIP_PLANS[arith, B]
+    for l in (1, 2, 3):
+        g = T.geometry(8, 512, l)
+        for side, rows in (("fwd", B * g["Hout"] ** 2), ("dgrad", B * g["Hin"] ** 2)):
+            kernel, split = plan[l][side + "_kernel"], plan[l][side + "_kslices"]
+            blocks128 = -(-rows // 128) * 2
+            assert split == 1 if kernel in T.UNSPLIT_KERNELS else (split > 1) == (2 * blocks128 <= 256), (l, side, kernel, split)
+            # the last row tile is partly filled -- but for 684 boards x 64 pixels = 228 whole 192-row tiles (conv2 and the data gradients of conv2 /
+            # conv3 on H2MidPP, which 383 boards run with a partly filled one); what 684 exists for, H2BigPP on 36-pixel layers, is partly filled
+            if kernel in T.UNSPLIT_KERNELS and (arith, B, kernel) != ("f16x2", 684, "h2_midpp"):
+                assert rows % TILE_ROWS[kernel] != 0, (l, side, kernel, rows)
+    for l, side, kernel in CHIP_FIRST.get((arith, B), []):
+        assert kernels[l][side] == kernel and _kernels(arith, B - 64)[0][l][side] != kernel, (l, side, kernel)
+
+
+def test_tile_rule_thresholds():
+    """the rule at its edges, 512 columns: 192 blocks of 256 rows = more than 95 row tiles = 24321 rows and more; bf16x3 needs a 'valid' layer and a grid
+    that costs no more than the 128-row tiles' at 0.93 a round"""
+    assert T.tile_cost(36864, 512, 256) == 2 * 256 and T.tile_cost(36864, 512, 192) == 2 * 192          # oz_net.hip's own example: 1024 boards of conv3
+    assert T.tile_rule("f16x2", 24320, 512, 0) == "low" and T.tile_rule("f16x2", 24321, 512, 1) == "mid"
+    assert T.tile_rule("f16x2", 447 * 64, 512, 1) == "big"                                               # 224 blocks in one round; 192-row tiles would need a second
+    assert T.tile_rule("bf16x3", 24320, 512, 0) == "low" and T.tile_rule("bf16x3", 24321, 512, 0) == "big" and T.tile_rule("bf16x3", 24321, 512, 1) == "low"
+    assert T.tile_rule("bf16x3", 684 * 64, 512, 0) == "low"                                              # 342 big blocks pay two rounds of 256 rows, 684 small ones three of 128
+    assert T.trainer_kslices("bf16x3", 8192, 512, 9 * 512, 0) == 2 and T.trainer_kslices("bf16x3", 8193, 512, 9 * 512, 0) == 1
+    assert T.trainer_kslices("f16x2", 64 * 16, 256, 9 * 256, 0) == 9                                     # at least 8 k-tiles a slice: 72 // 9
+    assert T.wgrad_msplit(383, 64, "bf16x3") == 4 and T.wgrad_msplit(383, 32, "f16x2") == 8 and T.wgrad_msplit(37, 64, "bf16x3") == 4
+
+
+# ------------------------------------------------------------------ the chip cases' weight gradient: what the coarse bound still sees
+CHIP_WGRAD_TILES = {"bf16x3": 64, "f16x2": 32}                                            # (Cin / CI) x (Co / CO) at 512 filters
+_chip_wgrad_cache = {}
+
+
+def _chip_wgrad_block():
+    """conv3 at 383 boards (13788 rows, 48 octets), a block of 32 input channels x 64 output columns, one tap, synthetic rows"""
+    if not _chip_wgrad_cache:
+        B, hout = 383, 6
+        rs = np.random.RandomState(383)
+        x, z = T.act_like(rs, B * hout * hout, 32), T.dz_like(rs, B * hout * hout, 64)
+        ref = x.astype(np.float64).T @ z.astype(np.float64)
+        _chip_wgrad_cache["v"] = (B, hout, x, z, ref, _stat(x.T @ z, ref))
+    return _chip_wgrad_cache["v"]
+
+
+@pytest.mark.parametrize("arith", ["bf16x3", "f16x2"])
+def test_chip_wgrad_bound_sees_lost_rows(arith):
+    """over 13788 rows E32 has grown to where a lost plane product hides inside the coarse bound (the module docstring: 9 .. 17 x E32 at 72 .. 512 rows
+    already); what MARGIN_COARSE does catch at the chip cases' sizes is BOOKKEEPING: an octet of 8 boards whose k-steps are skipped, or a slab
+    of the octet split that is never added -- each must exceed the bound at least fourfold, while the complete model stays within it"""
+    B, hout, x, z, ref, E32 = _chip_wgrad_block()
+    ms = T.wgrad_msplit(B, CHIP_WGRAD_TILES[arith], arith)
+    noct = (B + 7) // 8
+    full = _stat(T.model_wgrad(x, z, B, hout, arith, ms), ref) / E32
+    octets = {o: _stat(T.model_wgrad(x, z, B, hout, arith, ms, drop_octet=o), ref) / E32 for o in (0, noct // 2, noct - 1)}     # (the last one holds 7 boards)
+    slabs = {s: _stat(T.model_wgrad(x, z, B, hout, arith, ms, drop_slab=s), ref) / E32 for s in range(ms)}
+    print(f"wgrad {arith:6s} conv3 B={B} rows={B * hout * hout} msplit={ms}: E32 {E32:.3g}  complete {full:.2f}  octet lost {min(octets.values()):.0f} .. "
+          f"{max(octets.values()):.0f}  slab lost {min(slabs.values()):.0f} .. {max(slabs.values()):.0f}  -> coarse, margin {T.MARGIN_COARSE:g}")
+    assert T.wgrad_class(arith, 2, B * hout * hout) == "coarse"
+    assert full <= T.MARGIN_COARSE
+    assert min(octets.values()) >= 4 * T.MARGIN_COARSE and min(slabs.values()) >= 4 * T.MARGIN_COARSE
+
+
+def test_sampled_weight_gradient_is_a_slice_of_the_whole():
+    """the chip cases' weight-gradient reference (every 16th input channel) is the same slice of the whole tensor's reference (float64, to the
+    order of the sums), and its norm_c is at most the whole one's"""
+    rs = np.random.RandomState(2)
+    for layer, hin in ((1, 4), (2, 6)):
+        hout = hin if layer == 1 else hin - 2
+        x, dz = rs.standard_normal((3, hin, hin, 64)), rs.standard_normal((3, hout, hout, 8))
+        whole = T.wgrad(layer, x, dz, np.float64)
+        part = T.wgrad(layer, T.sampled_ci(x, 3), dz, np.float64)
+        assert part.shape == (3, 3, 64 // T.WGRAD_CI_STRIDE, 8) and np.allclose(part, T.sampled_ci(whole, 2), rtol=1e-12, atol=1e-12)
+        assert np.all(T.column_norm(part) <= T.column_norm(whole) * (1 + 1e-12))
+    assert T.WGRAD_CI_STRIDE <= 32                                       # at least one sampled channel in every 32-wide input-channel tile
 
 
 # ------------------------------------------------------------------ few-row samples

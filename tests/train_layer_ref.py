@@ -23,7 +23,9 @@ asserts that the model agrees, and names the shapes that cannot separate (they a
 written are in that test's docstring.
 Few-row samples: a dense layer of a B-board step has B rows; under the norm of a few rows the statistic is an element's relative error (layer_ref's
 docstring).  A case of fewer than ROWS_FOR_NORM boards therefore runs several steps on fresh batches (same weights) and takes norm_c over the rows of
-all of them; every element of every step is still compared."""
+all of them; every element of every step is still compared.
+The launchers' choice of row tile and k-split for a trainer GEMM is restated below (tile_rule, trainer_kslices, tile_plan), so that the batch sizes
+which reach the 192 / 256-row tiles are asserted on the CPU and a moved threshold shows without a device; the GPU matrix compares it with Trainer.plan."""
 import numpy as np
 
 import layer_ref as R
@@ -53,6 +55,61 @@ def geometry(n, C, layer):
     hin, hout, same, taps, K, N = R.layer_geometry(n, C, layer)
     zoff = 2 if layer in (2, 3) else 0
     return dict(Hin=hin, Hout=hout, same=same, taps=taps, Cin=K // taps, Co=N, zoff=zoff, Hz=hout + 2 * zoff)
+
+
+# ------------------------------------------------------------------ the launchers' tile rule (oz_gemm_h2_launch, oz_gemm_b3_launch), restated
+B3_BIG_ROUND_COST = 0.93               # oz_net.hip: a round of 256 x 256 tiles against two rounds of 128 x 256 tiles
+BIG_GRID_BLOCKS = 192                  # the 256-row tiles' grid must have at least this many blocks (of the chip's 256 CUs)
+
+
+def tile_cost(rows, N, bm):
+    """oz_net.hip's tile_cost: rounds of the 256 CUs x tile height that a grid of bm-row tiles (256 columns each) pays for rows x N outputs"""
+    return -(-(-(-rows // bm) * (N // 256)) // 256) * bm
+
+
+def tile_rule(arith, rows, N, pad):
+    """'low' / 'mid' / 'big': the row tile (128 / 192 / 256 rows) of a trainer GEMM of `rows` x N outputs -- rows = the launch's boards (f16x2: the
+    call's, bf16x3: the trainer's capacity) x output pixels; pad: 1 for a 'same' layer.  f16x2 (oz_gemm_h2_launch): the ping-pong tiles once
+    ceil(rows / 256) x (N / 256) >= 192, of the two the one whose grid pays fewer tile-rows (H2MidPP only if strictly fewer).  bf16x3
+    (oz_gemm_b3_launch: b3_big_rows(rows, N, false)): the 256-row tile for a 'valid' layer with that many blocks whose grid costs, at
+    B3_BIG_ROUND_COST, no more than the 128-row tiles'; there is no mid tile"""
+    big = -(-rows // 256) * (N // 256) >= BIG_GRID_BLOCKS
+    if arith == "f16x2":
+        return "low" if not big else "mid" if tile_cost(rows, N, 192) < tile_cost(rows, N, 256) else "big"
+    assert arith == "bf16x3"
+    return "big" if pad == 0 and big and B3_BIG_ROUND_COST * tile_cost(rows, N, 256) <= tile_cost(rows, N, 128) else "low"
+
+
+TILE_KERNEL = {("f16x2", "low"): "h2_lowpp", ("f16x2", "mid"): "h2_midpp", ("f16x2", "big"): "h2_bigpp", ("bf16x3", "low"): "b3", ("bf16x3", "big"): "b3_big"}
+UNSPLIT_KERNELS = ("h2_midpp", "h2_bigpp", "b3_big")        # one k-slice; h2_lowpp / b3 always split the k loop in the trainer
+
+
+PARTIAL_FLOATS = 40 << 20              # oz_train.hip: the trainer's split-K buffer (gpartial_floats)
+
+
+def trainer_kslices(arith, rows, N, K, pad):
+    """the k-slices of that launch: 1 on the mid / big tiles; on the 128-row tile oz_net.hip's trainer_ksplit -- the largest split <= 16 that keeps
+    the grid within one round of the 256 CUs, at least 8 k-tiles of 32 per slice, the slabs within the buffer.  So a 128-row launch of more than
+    128 blocks (more than 8192 rows at 512 filters) is not split either"""
+    if tile_rule(arith, rows, N, pad) != "low":
+        return 1
+    blocks, nk, ksplit = -(-rows // 128) * (N // 256), K // 32, 1
+    while ksplit < 16 and blocks * (ksplit + 1) <= 256 and nk // (ksplit + 1) >= 8 and (ksplit + 1) * rows * N <= PARTIAL_FLOATS:
+        ksplit += 1
+    return ksplit
+
+
+def tile_plan(arith, n, C, B):
+    """{layer 1 .. 3: dict(fwd_kernel, fwd_kslices, dgrad_kernel, dgrad_kslices)} of a launch of B boards as tile_rule / trainer_kslices have it:
+    the forward's rows are B x Hout^2, the data gradient's B x Hin^2 (its output is the layer's input; 'same' exactly where the layer is)"""
+    out = {}
+    for l in (1, 2, 3):
+        g = geometry(n, C, l)
+        pad = int(g["same"])
+        fwd, dg = (B * g["Hout"] ** 2, g["Co"], pad), (B * g["Hin"] ** 2, g["Cin"], pad)
+        out[l] = dict(fwd_kernel=TILE_KERNEL[arith, tile_rule(arith, *fwd)], fwd_kslices=trainer_kslices(arith, fwd[0], fwd[1], 9 * g["Cin"], pad),
+                      dgrad_kernel=TILE_KERNEL[arith, tile_rule(arith, *dg)], dgrad_kslices=trainer_kslices(arith, dg[0], dg[1], 9 * g["Co"], pad))
+    return out
 
 
 # ------------------------------------------------------------------ the three contractions of a layer, in any dtype
@@ -101,6 +158,17 @@ def wgrad(layer, x_in, dz_int, dtype):
             out[ty, tx] = win.T @ flat
     assert out.dtype == dtype
     return out
+
+
+WGRAD_CI_STRIDE = 16                   # the sampled weight gradient: every 16th input channel -- one or more in every 32- and 64-wide input-channel tile
+
+
+def sampled_ci(a, axis):
+    """every WGRAD_CI_STRIDE-th input channel of an activation (axis 3) or of a 3x3 weight gradient (axis 2), as a copy.  The sampled weight-gradient
+    reference of a 3x3 layer is wgrad(layer, sampled_ci(x, 3), dz, dtype) against sampled_ci(device's dW, 2): all nine taps, all output columns and
+    ALL rows -- every element is a sum over every (board, pixel) of the step, so rows, octets and slabs that go missing show as in the whole
+    tensor; norm_c over the sampled (tap, ci) is at most the whole tensor's, so the statistic is no looser"""
+    return np.ascontiguousarray(a[(slice(None),) * axis + (slice(None, None, WGRAD_CI_STRIDE),)])
 
 
 def heads_dgrad(weights, dlogit, dvpre, dtype):
@@ -204,7 +272,7 @@ def wgrad_msplit(B, tiles, arith):
     return msplit
 
 
-def model_wgrad(x_rows, dz_rows, B, hout, arith, msplit=1, drop=None, inner="exact"):
+def model_wgrad(x_rows, dz_rows, B, hout, arith, msplit=1, drop=None, inner="exact", drop_octet=None, drop_slab=None):
     """one tap of the octet weight gradient on x_rows (B hout^2, Ci), dz_rows (B hout^2, Co): per k-step (wgrad_groups) one MFMA per kept plane
     product, in mac()'s order (small terms first: R.B3_TERMS / R.H2_TERMS read as (plane of x, plane of dz)), each adding its exact products to the
     fp32 accumulator; octets split over `msplit` slabs that are summed in fp32 in slab order (k_t_sum_partials).  f16x2: dz moved by the power of
@@ -212,7 +280,9 @@ def model_wgrad(x_rows, dz_rows, B, hout, arith, msplit=1, drop=None, inner="exa
     inner: how one MFMA adds its (up to) 32 products to the accumulator, which the instruction set does not specify -- "exact": their exact sum,
     rounded to fp32 once (the most a 16-bit matrix core can do); "sequential": one by one in k order, each sum rounded to fp32 (the least an
     fp32 accumulator can do).  The hardware lies between the two; in the sparse forward / data-gradient models an MFMA holds about one non-zero
-    product, so the two coincide there"""
+    product, so the two coincide there.
+    drop_octet / drop_slab: a model that loses the k-steps of that octet of 8 boards / never adds that slab of the split (defects of the row
+    bookkeeping, not of the arithmetic: what the coarse bound of a long sum can still see)"""
     x, z = np.asarray(x_rows, np.float32), np.asarray(dz_rows, np.float32)
     if arith == "bf16x3":
         xp, zp, terms, back = R.b3_planes(x), R.b3_planes(z), R.B3_TERMS, 0
@@ -224,6 +294,8 @@ def model_wgrad(x_rows, dz_rows, B, hout, arith, msplit=1, drop=None, inner="exa
     per = -(-noct // msplit)
     slabs = [np.zeros((x.shape[1], z.shape[1]), np.float32) for _ in range(msplit)]
     for oct_, rows in wgrad_groups(B, hout):
+        if oct_ == drop_octet:
+            continue
         s = oct_ // per
         for (i, j) in terms:
             if (i, j) != drop:
@@ -236,6 +308,7 @@ def model_wgrad(x_rows, dz_rows, B, hout, arith, msplit=1, drop=None, inner="exa
         acc = slabs[0]
     else:
         acc = np.zeros_like(slabs[0])
-        for s in slabs:
-            acc = acc + s
+        for k, s in enumerate(slabs):
+            if k != drop_slab:
+                acc = acc + s
     return np.ldexp(acc, back).astype(np.float32)
