@@ -122,6 +122,11 @@ __device__ __forceinline__ OzEdge* rec_edge(const MctsDev& t, int g, int node, i
 __device__ __forceinline__ int* rec_Ns(const MctsDev& t, int g, int node) {
     return reinterpret_cast<int*>(rec_ptr(t, g, node) + 16);
 }
+// a record holds one edge per legal square, in square order: the rank of square sq under `legal`, and this lane's edge of `node` (lane = square)
+__device__ __forceinline__ int edge_rank(uint64_t legal, int sq) { return oz_popc(legal & ((1ULL << sq) - 1ULL)); }
+__device__ __forceinline__ OzEdge* lane_edge(const MctsDev& t, int g, int node, uint64_t legal, int lane) {
+    return rec_edge(t, g, node, edge_rank(legal, lane));
+}
 
 // per-wavefront LDS working set of the tree kernels (one wave = one game = one block of 64)
 struct TreeLds {
@@ -338,7 +343,7 @@ __device__ __forceinline__ int sample_move(int cnt, uint64_t legal, int mx, doub
 //   * forcing lives in descend_one<true>, at depth 0 of a descent from an armed root: a child tried at least once whose count (in-flight descents
 //     included) is below sqrt((k * Pn) * Ns) gets U = +inf.  MctsDev.forced_k is uniform, and so are `noisy` and `depth`: the wave takes one
 //     branch, only the compare is per lane.  k == 0 leaves the expression the noise kernels evaluated before.
-//   * pruning lives in the move (sp_move_body<.., FORCE>) and in k_pruned_counts: one lane per square computes oz_forced_prune (oz_common.h) of
+//   * pruning lives in the move (sp_move_body<.., FORCE>) and in k_root_read<RO_PRUNED>: one lane per square computes oz_forced_prune (oz_common.h) of
 //     its own (N, Q, P, eta) and of star's, fetched with lane_get.  Only the row that becomes the policy target is pruned; last_counts, the
 //     arg-max, the tie rule, sample_move and the e-greedy branch read the raw counts.
 struct ForcedPlayouts {
@@ -356,7 +361,7 @@ __device__ __forceinline__ int forced_prune_lane(const MctsDev& t, int g, int no
     const bool is_legal = (legal >> lane) & 1;
     double Q = 0.0, P = 0.0;
     if (is_legal) {
-        const OzEdge* e = rec_edge(t, g, node, oz_popc(legal & ((1ULL << lane) - 1ULL)));
+        const OzEdge* e = lane_edge(t, g, node, legal, lane);
         Q = e->q; P = e->p;
     }
     const double eta = t.noise_eta[(size_t)g * 64 + lane];
@@ -443,7 +448,7 @@ __device__ __forceinline__ Descent descend_one(const MctsDev& t, uint4* rec, int
         const uint64_t* w = reinterpret_cast<const uint64_t*>(rec);
         const int Ns = unii((int)(uint32_t)w[2]);
         const bool is_legal = (legal >> lane) & 1;
-        const int rank = oz_popc(legal & ((1ULL << lane) - 1ULL));
+        const int rank = edge_rank(legal, lane);
         // the in-flight descents of this step that stand on this node at this level, and those that took this lane's edge from it
         int ks = 0, ke = 0;
         for (int i = 0; i < fl.n; ++i)
@@ -544,7 +549,7 @@ __device__ __forceinline__ Descent descend_one(const MctsDev& t, uint4* rec, int
         }
         const double m = wave_max_f64(U);
         const int best = oz_ctz(__ballot(cand && U == m));                 // first maximum
-        const int brank = oz_popc(legal & ((1ULL << best) - 1ULL));
+        const int brank = edge_rank(legal, best);
         if constexpr (VS == OZ_VSIGNS_REFERENCE) { if (lane == 0) path[depth] = make_int2(node, brank); }
         ++depth;
         pnode = node; prank = brank;
@@ -935,7 +940,7 @@ __device__ __forceinline__ void expand_backup_one(const MctsDev& t, TreeLds& L, 
                 if constexpr (GUMBEL || SEL) w[3] = (uint64_t)__double_as_longlong((double)t.v[slot]);
             }
             if (is_legal) {
-                const int rank = oz_popc(legal & ((1ULL << lane) - 1ULL));
+                const int rank = edge_rank(legal, lane);
                 w[4 + 3 * rank] = 0xFFFFFFFF00000000ULL;                       // N|tag = 0, child = -1
                 w[5 + 3 * rank] = 0;                                           // Q = 0.0
                 w[6 + 3 * rank] = (uint64_t)__double_as_longlong(p);
@@ -1656,30 +1661,23 @@ OZ_API int oz_mcts_set_roots(oz_mcts* m, const uint64_t* own, const uint64_t* op
     const int G = m->d.G;
     for (int i = 0; i < G; ++i)
         OZ_REQUIRE((own[i] & opp[i]) == 0 && ((own[i] | opp[i]) & ~m->d.valid) == 0, "root %d is not a valid %dx%d board", i, m->d.n, m->d.n);
-    if (m->noise_ever) {                                   // root noise belongs to one board: a slot that gets another one loses it
+    auto disarm_moved = [&](uint8_t* armed_dev) -> int {  // what was armed for one board: a slot that gets another one loses it
         std::vector<uint64_t> o(G), p(G);
         std::vector<uint8_t> armed(G);
         OZ_HIP(hipMemcpyAsync(o.data(), m->d.root_own, 8ull * G, hipMemcpyDeviceToHost, m->stream));
         OZ_HIP(hipMemcpyAsync(p.data(), m->d.root_opp, 8ull * G, hipMemcpyDeviceToHost, m->stream));
-        OZ_HIP(hipMemcpyAsync(armed.data(), m->d.noise_armed, G, hipMemcpyDeviceToHost, m->stream));
+        OZ_HIP(hipMemcpyAsync(armed.data(), armed_dev, G, hipMemcpyDeviceToHost, m->stream));
         OZ_HIP(hipStreamSynchronize(m->stream));
         for (int i = 0; i < G; ++i)
             if (o[i] != own[i] || p[i] != opp[i]) armed[i] = 0;
-        OZ_HIP(hipMemcpyAsync(m->d.noise_armed, armed.data(), G, hipMemcpyHostToDevice, m->stream));
+        OZ_HIP(hipMemcpyAsync(armed_dev, armed.data(), G, hipMemcpyHostToDevice, m->stream));
         OZ_HIP(hipStreamSynchronize(m->stream));           // (`armed` is a local: the copy must be done before it goes)
-    }
-    if (m->gumbel_ever) {                                  // so do the Gumbel draw and the snapshot of the root's counts
-        std::vector<uint64_t> o(G), p(G);
-        std::vector<uint8_t> armed(G);
-        OZ_HIP(hipMemcpyAsync(o.data(), m->d.root_own, 8ull * G, hipMemcpyDeviceToHost, m->stream));
-        OZ_HIP(hipMemcpyAsync(p.data(), m->d.root_opp, 8ull * G, hipMemcpyDeviceToHost, m->stream));
-        OZ_HIP(hipMemcpyAsync(armed.data(), m->gd.armed, G, hipMemcpyDeviceToHost, m->stream));
-        OZ_HIP(hipStreamSynchronize(m->stream));
-        for (int i = 0; i < G; ++i)
-            if (o[i] != own[i] || p[i] != opp[i]) armed[i] = 0;
-        OZ_HIP(hipMemcpyAsync(m->gd.armed, armed.data(), G, hipMemcpyHostToDevice, m->stream));
-        OZ_HIP(hipStreamSynchronize(m->stream));
-    }
+        return OZ_OK;
+    };
+    if (m->noise_ever)                                     // root noise ...
+        if (int rc = disarm_moved(m->d.noise_armed)) return rc;
+    if (m->gumbel_ever)                                    // ... and the Gumbel draw with its snapshot of the root's counts
+        if (int rc = disarm_moved(m->gd.armed)) return rc;
     OZ_HIP(hipMemcpyAsync(m->d.root_own, own, 8ull * G, hipMemcpyHostToDevice, m->stream));
     OZ_HIP(hipMemcpyAsync(m->d.root_opp, opp, 8ull * G, hipMemcpyHostToDevice, m->stream));
     if (active) OZ_HIP(hipMemcpyAsync(m->d.active, active, G, hipMemcpyHostToDevice, m->stream));
@@ -2165,7 +2163,7 @@ static int noise_disarm(oz_mcts* m) {
     return OZ_OK;
 }
 #define OZ_REFUSE_GUMBEL(m, fn, what) \
-    do { if ((m)->gumbel_ever) { oz_set_error(fn ": the Gumbel search replaces " what " (the object has it switched on)"); return OZ_ERR_STATE; } } while (0)
+    do { if ((m)->gumbel_ever) { oz_set_error("%s: the Gumbel search replaces " what " (the object has it switched on)", fn); return OZ_ERR_STATE; } } while (0)
 #define OZ_REFUSE_PENDING(m, fn) \
     do { if ((m)->selected) { oz_set_error(fn ": a step is pending (oz_mcts_select without oz_mcts_backup)"); return OZ_ERR_STATE; } } while (0)
 
@@ -2299,79 +2297,161 @@ OZ_API int oz_mcts_last_value(oz_mcts* m, double* value, int32_t* vtype, int32_t
     return OZ_OK;
 }
 
-// N(state, action) for the root of every slot (MCTS/__init__.py:73-84,172-175)
+// ---------------------------------------------------------------- root read-outs: what the search knows of the root of every slot
 // record index of the root of slot g (cached by the descent, else looked up); -1 = not in the table
 __device__ __forceinline__ int root_lookup(const MctsDev& t, int g, uint64_t own, uint64_t opp, int lane) {
     int node = unii(t.root_node[g]);
     if (node < 0) { int fs; node = ht_find(t, g, own, opp, lane, &fs); }
     return node;
 }
-__global__ __launch_bounds__(64) void k_root_counts(MctsDev t, int32_t* counts, uint64_t* legal_out, int32_t* rc_out) {
-    const int g = blockIdx.x, lane = threadIdx.x;
+// the root's row, N(state, action) of MCTS/__init__.py:73-84,172-175: one wave per slot, lane = square.  rc (wave-uniform): 0; 1 = the root is not
+// in the table; 2 = it is and was never selected from (_Nsa[hash] still empty -> KeyError in the reference).  cnt = this lane's raw count and,
+// with Q, q = its stored Q: 0 off the legal set and where rc != 0
+struct RootRow { uint64_t legal; int node, rc, cnt; double q; };
+template <bool Q = false>
+__device__ __forceinline__ RootRow root_row(const MctsDev& t, int g, int lane) {
     const uint64_t own = uni64(t.root_own[g]), opp = uni64(t.root_opp[g]);
-    const uint64_t legal = oz_legal(own, opp, t.valid);
-    const int node = root_lookup(t, g, own, opp, lane);
-    int cnt = 0, rc = 0;
-    if (node < 0) rc = 1;
-    else if (*rec_Ns(t, g, node) == 0) rc = 2;          // _Nsa[hash] still empty -> KeyError in the reference
-    else if ((legal >> lane) & 1)
-        cnt = (int)(rec_edge(t, g, node, oz_popc(legal & ((1ULL << lane) - 1ULL)))->n_tag & ~OZ_TAG_F32);
-    counts[(size_t)g * 64 + lane] = cnt;
-    if (lane == 0) { legal_out[g] = legal; rc_out[g] = rc; }
-}
-
-OZ_API int oz_mcts_root_counts(oz_mcts* m, int32_t* counts, uint64_t* legal, int32_t* rc) {
-    OZ_REQUIRE(m && counts && legal && rc, "null argument");
-    std::lock_guard<std::mutex> lk(m->mu);
-    hipSetDevice(m->device);
-    const int G = m->d.G;
-    int32_t* dc = m->rc_counts; uint64_t* dl = m->rc_legal; int32_t* dr = m->rc_rc;
-    hipLaunchKernelGGL(k_root_counts, dim3(G), dim3(64), 0, m->stream, m->d, dc, dl, dr);
-    OZ_HIP(hipMemcpyAsync(counts, dc, 4ull * G * 64, hipMemcpyDeviceToHost, m->stream));
-    OZ_HIP(hipMemcpyAsync(legal, dl, 8ull * G, hipMemcpyDeviceToHost, m->stream));
-    OZ_HIP(hipMemcpyAsync(rc, dr, 4ull * G, hipMemcpyDeviceToHost, m->stream));
-    OZ_HIP(hipStreamSynchronize(m->stream));
-    return OZ_OK;
-}
-
-// the root value of every slot's search ("value targets" in the header): the visit-weighted mean of the root's stored Q over the raw counts.
-// One wave per game, lane = square: a[lane] = oz_root_term of the lane's edge, the wave sums N, oz_root_mean divides.  rc as k_root_counts
-__global__ __launch_bounds__(64) void k_root_values(MctsDev t, double* value_out, int32_t* rc_out) {
-    __shared__ double terms[64];
-    const int g = blockIdx.x, lane = threadIdx.x;
-    const uint64_t own = uni64(t.root_own[g]), opp = uni64(t.root_opp[g]);
-    const uint64_t legal = oz_legal(own, opp, t.valid);
-    const int node = root_lookup(t, g, own, opp, lane);
-    int cnt = 0, rc = 0;
-    double q = 0.0;
-    if (node < 0) rc = 1;
-    else if (*rec_Ns(t, g, node) == 0) rc = 2;
-    else if ((legal >> lane) & 1) {
-        const OzEdge* e = rec_edge(t, g, node, oz_popc(legal & ((1ULL << lane) - 1ULL)));
-        cnt = (int)(e->n_tag & ~OZ_TAG_F32);
-        q = e->q;
+    RootRow r{oz_legal(own, opp, t.valid), root_lookup(t, g, own, opp, lane), 0, 0, 0.0};
+    if (r.node < 0) r.rc = 1;
+    else if (*rec_Ns(t, g, r.node) == 0) r.rc = 2;
+    else if ((r.legal >> lane) & 1) {
+        const OzEdge* e = lane_edge(t, g, r.node, r.legal, lane);
+        r.cnt = (int)(e->n_tag & ~OZ_TAG_F32);
+        if constexpr (Q) r.q = e->q;
     }
-    rc = unii(rc);
+    r.rc = unii(r.rc);
+    return r;
+}
+// proof play of the root record `node` ("proof play" in the header): its proof entry -- one 32-byte wave-uniform load -- and what oz_proof_play
+// (oz_common.h) keeps of the raw counts cnt.  The rule's row is cnt on the squares of `keep` and 0 elsewhere; every member is wave-uniform
+struct ProofRow { uint64_t keep; int val, fall; };
+__device__ __forceinline__ ProofRow proof_row(const MctsDev& t, int g, int node, int cnt) {
+    const OzProof* pe = t.pf.entry + (size_t)g * t.node_cap + node;
+    ProofRow p;
+    int bad;
+    p.val = oz_proof_play(uni64(pe->legal), uni64(pe->lo), uni64(pe->hi), unii(pe->own), __ballot(cnt > 0), &p.keep, &p.fall, &bad);
+    return p;
+}
+// the root value of a search ("value targets" in the header): the visit-weighted mean of the stored Q over the raw counts.  terms = 64 doubles
+// of LDS: terms[lane] = oz_root_term of the lane's edge, the wave sums N, oz_root_mean divides (rc 2: no visit at all)
+struct RootValue { double v; int rc; };
+__device__ __forceinline__ RootValue root_value(double* terms, int cnt, double q, int lane) {
     terms[lane] = oz_root_term(cnt, q);
     const int total = wave_sum_i32(cnt);
     wave_sync();
-    int vrc = 0;
-    const double v = oz_root_mean(terms, (long long)total, &vrc);
-    if (lane == 0) { value_out[g] = rc == 0 ? v : 0.0; rc_out[g] = rc == 0 ? vrc : rc; }
+    RootValue r;
+    r.v = oz_root_mean(terms, (long long)total, &r.rc);
+    return r;
+}
+// ---- the read-out kernel of the bare search: one template, instantiated per entry.  R is a mask of RO_* flags: which row, and what is written
+// into the staging (ReadArgs).  Neither RO_VALUE nor RO_SAMPLE: the [G][64] row, the legal sets and rc.
+//   flag          what it does                                                                                    entries (oz_mcts_*)
+//   (none)        the raw row                                                                                     root_counts
+//   RO_PRUNED     the policy target's row: pruned where the slot's noise is armed (and k > 0), raw elsewhere      pruned_counts
+//   RO_PROVEN     the rule's row: the raw count on the squares proof play keeps, 0 elsewhere                      proven_counts
+//   RO_VALUE      writes the root value of the RAW row; with RO_PROVEN the exact one where the proofs know it     root_values, proven_root_values
+//   RO_SAMPLE     writes the move sampled from the row and its maximum (the engine's sample_move, the same        sample_moves, proven_sample_moves
+//                 keys); -1 where rc != 0 and on an idle slot
+enum : unsigned { RO_PRUNED = 1, RO_PROVEN = 2, RO_VALUE = 4, RO_SAMPLE = 8 };
+// the staging by what lies there: row = [G][64] counts (RO_SAMPLE: [G] actions), word = [G] 8-byte words (legal sets; RO_VALUE: the values'
+// bits), code = [G] rc.  The keys are the samplers' alone.
+struct ReadArgs {
+    int32_t* row; uint64_t* word; int32_t* code;
+    double temperature; uint64_t seed; const uint64_t* game_ids; const int* plies;
+};
+template <unsigned R>
+__global__ __launch_bounds__(64) void k_root_read(MctsDev t, ReadArgs a) {
+    static_assert(R < 16 && !(has(R, RO_PRUNED) && R != RO_PRUNED) && !(has(R, RO_VALUE) && has(R, RO_SAMPLE)), "no entry reads this out");
+    const int g = blockIdx.x, lane = threadIdx.x;
+    const RootRow r = root_row<has(R, RO_VALUE)>(t, g, lane);
+    int cnt = r.cnt, pval = OZ_PROOF_NONE;
+    if constexpr (has(R, RO_PROVEN)) {
+        if (r.rc == 0) {
+            const ProofRow p = proof_row(t, g, r.node, cnt);
+            pval = p.val;
+            if (!has(R, RO_VALUE) && !((p.keep >> lane) & 1)) cnt = 0;
+        }
+    }
+    if constexpr (has(R, RO_PRUNED)) {
+        if (r.rc == 0 && t.forced_k > 0.0 && t.noise_eps > 0.0 && t.noise_armed && unii((int)t.noise_armed[g]) != 0)
+            cnt = forced_prune_lane(t, g, r.node, lane, r.legal, cnt, unii(wave_max_i32(cnt)), t.forced_k);
+    }
+    if constexpr (has(R, RO_VALUE)) {
+        __shared__ double terms[64];
+        RootValue v = root_value(terms, cnt, r.q, lane);
+        if (pval != OZ_PROOF_NONE) v = RootValue{(double)pval, 0};
+        if (lane == 0) { a.word[g] = (uint64_t)__double_as_longlong(r.rc == 0 ? v.v : 0.0); a.code[g] = r.rc == 0 ? v.rc : r.rc; }
+    } else if constexpr (has(R, RO_SAMPLE)) {
+        const int mx = unii(wave_max_i32(cnt));
+        int action = -1;
+        if (r.rc == 0 && mx >= 1 && t.active[g])
+            action = sample_move(cnt, r.legal, mx, a.temperature, oz_rng_unit(oz_rng(a.seed, uni64(a.game_ids[g]), (uint64_t)unii(a.plies[g]), OZ_RNG_SAMPLE)), lane);
+        if (lane == 0) { a.row[g] = action; a.code[g] = r.rc; }
+    } else {
+        a.row[(size_t)g * 64 + lane] = cnt;
+        if (lane == 0) { a.word[g] = r.legal; a.code[g] = r.rc; }
+    }
+}
+static int sample_check(const char* fn, double temperature) {
+    OZ_REQUIRE(temperature >= 0.01 && temperature <= 100.0, "%s: temperature %g outside [0.01, 100]", fn, temperature);     // (NaN fails both compares)
+    return OZ_OK;
+}
+// one read-out, from the lock to the synchronised copies: `out` = the rows, the values or the actions (what k_root_read<R> writes), legal =
+// the rows' legal sets.  The samplers bring their keys; RO_PROVEN needs an object that keeps proofs, the raw sampler one without the Gumbel search.
+struct ReadKeys { double temperature; uint64_t seed; const uint64_t* game_ids; const int32_t* plies; };
+template <unsigned R>
+static int root_read(oz_mcts* m, const char* fn, void* out, uint64_t* legal, int32_t* rc, ReadKeys k = ReadKeys{}) {
+    constexpr bool rows = !has(R, RO_VALUE | RO_SAMPLE);
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (has(R, RO_PROVEN) && !m->proofs) { oz_set_error("%s: the object keeps no proofs (oz_mcts_set_proofs)", fn); return OZ_ERR_STATE; }
+    if (R == RO_SAMPLE) OZ_REFUSE_GUMBEL(m, fn, "move sampling");
+    hipSetDevice(m->device);
+    const int G = m->d.G;
+    ReadArgs a{m->rc_counts, m->rc_legal, m->rc_rc, k.temperature, k.seed, nullptr, nullptr};
+    if (has(R, RO_SAMPLE)) {
+        for (int i = 0; i < G; ++i) OZ_REQUIRE(k.plies[i] >= 0, "%s: plies[%d] = %d", fn, i, k.plies[i]);
+        if (int r = stage_keys(m, k.game_ids, k.plies)) return r;
+        a.game_ids = (const uint64_t*)m->noise_ids; a.plies = (const int*)m->noise_plies;
+    }
+    hipLaunchKernelGGL(k_root_read<R>, dim3(G), dim3(64), 0, m->stream, m->d, a);
+    OZ_HIP(hipGetLastError());
+    if (has(R, RO_VALUE)) OZ_HIP(hipMemcpyAsync(out, a.word, 8ull * G, hipMemcpyDeviceToHost, m->stream));
+    else OZ_HIP(hipMemcpyAsync(out, a.row, 4ull * G * (rows ? 64 : 1), hipMemcpyDeviceToHost, m->stream));
+    if (rows) OZ_HIP(hipMemcpyAsync(legal, a.word, 8ull * G, hipMemcpyDeviceToHost, m->stream));
+    OZ_HIP(hipMemcpyAsync(rc, a.code, 4ull * G, hipMemcpyDeviceToHost, m->stream));
+    OZ_HIP(hipStreamSynchronize(m->stream));
+    return OZ_OK;
+}
+OZ_API int oz_mcts_root_counts(oz_mcts* m, int32_t* counts, uint64_t* legal, int32_t* rc) {
+    OZ_REQUIRE(m && counts && legal && rc, "null argument");
+    return root_read<0>(m, "oz_mcts_root_counts", counts, legal, rc);
+}
+OZ_API int oz_mcts_pruned_counts(oz_mcts* m, int32_t* counts, uint64_t* legal, int32_t* rc) {
+    OZ_REQUIRE(m && counts && legal && rc, "null argument");
+    return root_read<RO_PRUNED>(m, "oz_mcts_pruned_counts", counts, legal, rc);
+}
+OZ_API int oz_mcts_proven_counts(oz_mcts* m, int32_t* counts, uint64_t* legal, int32_t* rc) {
+    OZ_REQUIRE(m && counts && legal && rc, "null argument");
+    return root_read<RO_PROVEN>(m, "oz_mcts_proven_counts", counts, legal, rc);
 }
 OZ_API int oz_mcts_root_values(oz_mcts* m, double* value, int32_t* rc) {
     OZ_REQUIRE(m && value && rc, "null argument");
-    std::lock_guard<std::mutex> lk(m->mu);
-    hipSetDevice(m->device);
-    const int G = m->d.G;
-    double* dv = reinterpret_cast<double*>(m->rc_legal);          // (the staging of oz_mcts_root_counts: [G] 8-byte words and [G] codes)
-    int32_t* dr = m->rc_rc;
-    hipLaunchKernelGGL(k_root_values, dim3(G), dim3(64), 0, m->stream, m->d, dv, dr);
-    OZ_HIP(hipGetLastError());
-    OZ_HIP(hipMemcpyAsync(value, dv, 8ull * G, hipMemcpyDeviceToHost, m->stream));
-    OZ_HIP(hipMemcpyAsync(rc, dr, 4ull * G, hipMemcpyDeviceToHost, m->stream));
-    OZ_HIP(hipStreamSynchronize(m->stream));
-    return OZ_OK;
+    return root_read<RO_VALUE>(m, "oz_mcts_root_values", value, nullptr, rc);
+}
+OZ_API int oz_mcts_proven_root_values(oz_mcts* m, double* value, int32_t* rc) {
+    OZ_REQUIRE(m && value && rc, "null argument");
+    return root_read<RO_PROVEN | RO_VALUE>(m, "oz_mcts_proven_root_values", value, nullptr, rc);
+}
+// move sampling on the current roots of the active slots: the drop-in path's move rule, under proof play over the rule's row
+OZ_API int oz_mcts_sample_moves(oz_mcts* m, double temperature, uint64_t seed, const uint64_t* game_ids, const int32_t* plies, int32_t* action, int32_t* rc) {
+    OZ_REQUIRE(m && game_ids && plies && action && rc, "null argument");
+    if (int r = sample_check("oz_mcts_sample_moves", temperature)) return r;
+    return root_read<RO_SAMPLE>(m, "oz_mcts_sample_moves", action, nullptr, rc, ReadKeys{temperature, seed, game_ids, plies});
+}
+OZ_API int oz_mcts_proven_sample_moves(oz_mcts* m, double temperature, uint64_t seed, const uint64_t* game_ids, const int32_t* plies, int32_t* action, int32_t* rc) {
+    OZ_REQUIRE(m && game_ids && plies && action && rc, "null argument");
+    if (int r = sample_check("oz_mcts_proven_sample_moves", temperature)) return r;
+    return root_read<RO_PROVEN | RO_SAMPLE>(m, "oz_mcts_proven_sample_moves", action, nullptr, rc, ReadKeys{temperature, seed, game_ids, plies});
 }
 // oz_root_value over `count` rows, on the host: needs no device
 OZ_API int oz_root_values(const int32_t* N, const double* Q, int64_t count, double* out) {
@@ -2409,7 +2489,7 @@ __global__ __launch_bounds__(64) void k_gumbel_arm(MctsDev t, GumbelDev gd, int 
     if (draw) gd.g[(size_t)g * 64 + lane] = is_legal ? oz_gumbel_draw(seed, uni64(ids[g]), (uint64_t)unii(plies[g]), lane) : 0.0;
     const int node = root_lookup(t, g, own, opp, lane);
     int n0 = 0;
-    if (node >= 0 && node < t.node_cap && is_legal) n0 = (int)(rec_edge(t, g, node, oz_popc(legal & ((1ULL << lane) - 1ULL)))->n_tag & ~OZ_TAG_F32);
+    if (node >= 0 && node < t.node_cap && is_legal) n0 = (int)(lane_edge(t, g, node, legal, lane)->n_tag & ~OZ_TAG_F32);
     gd.n0[(size_t)g * 64 + lane] = n0;
     if (lane == 0) gd.armed[g] = 1;
 }
@@ -2422,7 +2502,7 @@ __device__ __forceinline__ GumbelPick gumbel_policy_lane(const MctsDev& t, const
     int N = 0;
     double Q = 0.0, P = 0.0;
     if (is_legal) {
-        const OzEdge* e = rec_edge(t, g, node, oz_popc(legal & ((1ULL << lane) - 1ULL)));
+        const OzEdge* e = lane_edge(t, g, node, legal, lane);
         N = (int)(e->n_tag & ~OZ_TAG_F32); Q = e->q; P = e->p;
     }
     const int nv = is_legal ? N - gd.n0[(size_t)g * 64 + lane] : 0;
@@ -2725,162 +2805,6 @@ OZ_API int oz_mcts_get_forced_playouts(oz_mcts* m, double* k) {
     *k = m->d.forced_k;
     return OZ_OK;
 }
-// k_root_counts with the policy target's row: pruned where the slot's noise is armed (and k > 0), raw elsewhere
-__global__ __launch_bounds__(64) void k_pruned_counts(MctsDev t, int32_t* counts, uint64_t* legal_out, int32_t* rc_out) {
-    const int g = blockIdx.x, lane = threadIdx.x;
-    const uint64_t own = uni64(t.root_own[g]), opp = uni64(t.root_opp[g]);
-    const uint64_t legal = oz_legal(own, opp, t.valid);
-    const int node = root_lookup(t, g, own, opp, lane);
-    int cnt = 0, rc = 0;
-    if (node < 0) rc = 1;
-    else if (*rec_Ns(t, g, node) == 0) rc = 2;
-    else if ((legal >> lane) & 1)
-        cnt = (int)(rec_edge(t, g, node, oz_popc(legal & ((1ULL << lane) - 1ULL)))->n_tag & ~OZ_TAG_F32);
-    rc = unii(rc);
-    if (rc == 0 && t.forced_k > 0.0 && t.noise_eps > 0.0 && t.noise_armed && unii((int)t.noise_armed[g]) != 0)
-        cnt = forced_prune_lane(t, g, node, lane, legal, cnt, unii(wave_max_i32(cnt)), t.forced_k);
-    counts[(size_t)g * 64 + lane] = cnt;
-    if (lane == 0) { legal_out[g] = legal; rc_out[g] = rc; }
-}
-OZ_API int oz_mcts_pruned_counts(oz_mcts* m, int32_t* counts, uint64_t* legal, int32_t* rc) {
-    OZ_REQUIRE(m && counts && legal && rc, "null argument");
-    std::lock_guard<std::mutex> lk(m->mu);
-    hipSetDevice(m->device);
-    const int G = m->d.G;
-    int32_t* dc = m->rc_counts; uint64_t* dl = m->rc_legal; int32_t* dr = m->rc_rc;
-    hipLaunchKernelGGL(k_pruned_counts, dim3(G), dim3(64), 0, m->stream, m->d, dc, dl, dr);
-    OZ_HIP(hipGetLastError());
-    OZ_HIP(hipMemcpyAsync(counts, dc, 4ull * G * 64, hipMemcpyDeviceToHost, m->stream));
-    OZ_HIP(hipMemcpyAsync(legal, dl, 8ull * G, hipMemcpyDeviceToHost, m->stream));
-    OZ_HIP(hipMemcpyAsync(rc, dr, 4ull * G, hipMemcpyDeviceToHost, m->stream));
-    OZ_HIP(hipStreamSynchronize(m->stream));
-    return OZ_OK;
-}
-// ---- proof play on the bare search ("proof play" in the header): the rows and root values a proven root leaves (oz_proof_play, oz_common.h)
-// k_root_counts with the rule's row: the raw count on the kept squares, 0 elsewhere
-__global__ __launch_bounds__(64) void k_proven_counts(MctsDev t, int32_t* counts, uint64_t* legal_out, int32_t* rc_out) {
-    const int g = blockIdx.x, lane = threadIdx.x;
-    const uint64_t own = uni64(t.root_own[g]), opp = uni64(t.root_opp[g]);
-    const uint64_t legal = oz_legal(own, opp, t.valid);
-    const int node = root_lookup(t, g, own, opp, lane);
-    int cnt = 0, rc = 0;
-    if (node < 0) rc = 1;
-    else if (*rec_Ns(t, g, node) == 0) rc = 2;
-    else if ((legal >> lane) & 1)
-        cnt = (int)(rec_edge(t, g, node, oz_popc(legal & ((1ULL << lane) - 1ULL)))->n_tag & ~OZ_TAG_F32);
-    rc = unii(rc);
-    if (rc == 0) {
-        const OzProof* pe = t.pf.entry + (size_t)g * t.node_cap + node;
-        uint64_t keep;
-        int fall, bad;
-        oz_proof_play(uni64(pe->legal), uni64(pe->lo), uni64(pe->hi), unii(pe->own), __ballot(cnt > 0), &keep, &fall, &bad);
-        if (!((keep >> lane) & 1)) cnt = 0;
-    }
-    counts[(size_t)g * 64 + lane] = cnt;
-    if (lane == 0) { legal_out[g] = legal; rc_out[g] = rc; }
-}
-// k_root_values with the rule's value: the exact one where the root's value is known, else the raw mean
-__global__ __launch_bounds__(64) void k_proven_root_values(MctsDev t, double* value_out, int32_t* rc_out) {
-    __shared__ double terms[64];
-    const int g = blockIdx.x, lane = threadIdx.x;
-    const uint64_t own = uni64(t.root_own[g]), opp = uni64(t.root_opp[g]);
-    const uint64_t legal = oz_legal(own, opp, t.valid);
-    const int node = root_lookup(t, g, own, opp, lane);
-    int cnt = 0, rc = 0;
-    double q = 0.0;
-    if (node < 0) rc = 1;
-    else if (*rec_Ns(t, g, node) == 0) rc = 2;
-    else if ((legal >> lane) & 1) {
-        const OzEdge* e = rec_edge(t, g, node, oz_popc(legal & ((1ULL << lane) - 1ULL)));
-        cnt = (int)(e->n_tag & ~OZ_TAG_F32);
-        q = e->q;
-    }
-    rc = unii(rc);
-    terms[lane] = oz_root_term(cnt, q);
-    const int total = wave_sum_i32(cnt);
-    wave_sync();
-    int vrc = 0;
-    double v = oz_root_mean(terms, (long long)total, &vrc);
-    if (rc == 0) {
-        const OzProof* pe = t.pf.entry + (size_t)g * t.node_cap + node;
-        const int val = oz_proof_value(uni64(pe->legal), uni64(pe->lo), uni64(pe->hi), unii(pe->own));
-        if (val != OZ_PROOF_NONE) { v = (double)val; vrc = 0; }
-    }
-    if (lane == 0) { value_out[g] = rc == 0 ? v : 0.0; rc_out[g] = rc == 0 ? vrc : rc; }
-}
-// k_sample_moves over the rule's row and its maximum (the drop-in path's sampled move under proof play)
-static int sample_check(const char* fn, double temperature);
-__global__ __launch_bounds__(64) void k_proven_sample_moves(MctsDev t, double temperature, uint64_t seed, const uint64_t* __restrict__ game_ids,
-                                                            const int* __restrict__ plies, int32_t* action_out, int32_t* rc_out) {
-    const int g = blockIdx.x, lane = threadIdx.x;
-    const uint64_t own = uni64(t.root_own[g]), opp = uni64(t.root_opp[g]);
-    const uint64_t legal = oz_legal(own, opp, t.valid);
-    const int node = root_lookup(t, g, own, opp, lane);
-    int cnt = 0, rc = 0, action = -1;
-    if (node < 0) rc = 1;
-    else if (*rec_Ns(t, g, node) == 0) rc = 2;
-    else if ((legal >> lane) & 1)
-        cnt = (int)(rec_edge(t, g, node, oz_popc(legal & ((1ULL << lane) - 1ULL)))->n_tag & ~OZ_TAG_F32);
-    rc = unii(rc);
-    if (rc == 0) {
-        const OzProof* pe = t.pf.entry + (size_t)g * t.node_cap + node;
-        uint64_t keep;
-        int fall, bad;
-        oz_proof_play(uni64(pe->legal), uni64(pe->lo), uni64(pe->hi), unii(pe->own), __ballot(cnt > 0), &keep, &fall, &bad);
-        if (!((keep >> lane) & 1)) cnt = 0;
-    }
-    const int mx = unii(wave_max_i32(cnt));
-    if (rc == 0 && mx >= 1 && t.active[g])
-        action = sample_move(cnt, legal, mx, temperature, oz_rng_unit(oz_rng(seed, uni64(game_ids[g]), (uint64_t)unii(plies[g]), OZ_RNG_SAMPLE)), lane);
-    if (lane == 0) { action_out[g] = action; rc_out[g] = rc; }
-}
-OZ_API int oz_mcts_proven_sample_moves(oz_mcts* m, double temperature, uint64_t seed, const uint64_t* game_ids, const int32_t* plies, int32_t* action, int32_t* rc) {
-    OZ_REQUIRE(m && game_ids && plies && action && rc, "null argument");
-    if (int r = sample_check("oz_mcts_proven_sample_moves", temperature)) return r;
-    std::lock_guard<std::mutex> lk(m->mu);
-    if (!m->proofs) { oz_set_error("oz_mcts_proven_sample_moves: the object keeps no proofs (oz_mcts_set_proofs)"); return OZ_ERR_STATE; }
-    hipSetDevice(m->device);
-    const int G = m->d.G;
-    for (int i = 0; i < G; ++i) OZ_REQUIRE(plies[i] >= 0, "oz_mcts_proven_sample_moves: plies[%d] = %d", i, plies[i]);
-    if (int r = stage_keys(m, game_ids, plies)) return r;
-    int32_t* da = m->rc_counts; int32_t* dr = m->rc_rc;           // (the staging of oz_mcts_root_counts: [G][64] and [G])
-    hipLaunchKernelGGL(k_proven_sample_moves, dim3(G), dim3(64), 0, m->stream, m->d, temperature, seed, (const uint64_t*)m->noise_ids, (const int*)m->noise_plies, da, dr);
-    OZ_HIP(hipGetLastError());
-    OZ_HIP(hipMemcpyAsync(action, da, 4ull * G, hipMemcpyDeviceToHost, m->stream));
-    OZ_HIP(hipMemcpyAsync(rc, dr, 4ull * G, hipMemcpyDeviceToHost, m->stream));
-    OZ_HIP(hipStreamSynchronize(m->stream));
-    return OZ_OK;
-}
-OZ_API int oz_mcts_proven_counts(oz_mcts* m, int32_t* counts, uint64_t* legal, int32_t* rc) {
-    OZ_REQUIRE(m && counts && legal && rc, "null argument");
-    std::lock_guard<std::mutex> lk(m->mu);
-    if (!m->proofs) { oz_set_error("oz_mcts_proven_counts: the object keeps no proofs (oz_mcts_set_proofs)"); return OZ_ERR_STATE; }
-    hipSetDevice(m->device);
-    const int G = m->d.G;
-    int32_t* dc = m->rc_counts; uint64_t* dl = m->rc_legal; int32_t* dr = m->rc_rc;
-    hipLaunchKernelGGL(k_proven_counts, dim3(G), dim3(64), 0, m->stream, m->d, dc, dl, dr);
-    OZ_HIP(hipGetLastError());
-    OZ_HIP(hipMemcpyAsync(counts, dc, 4ull * G * 64, hipMemcpyDeviceToHost, m->stream));
-    OZ_HIP(hipMemcpyAsync(legal, dl, 8ull * G, hipMemcpyDeviceToHost, m->stream));
-    OZ_HIP(hipMemcpyAsync(rc, dr, 4ull * G, hipMemcpyDeviceToHost, m->stream));
-    OZ_HIP(hipStreamSynchronize(m->stream));
-    return OZ_OK;
-}
-OZ_API int oz_mcts_proven_root_values(oz_mcts* m, double* value, int32_t* rc) {
-    OZ_REQUIRE(m && value && rc, "null argument");
-    std::lock_guard<std::mutex> lk(m->mu);
-    if (!m->proofs) { oz_set_error("oz_mcts_proven_root_values: the object keeps no proofs (oz_mcts_set_proofs)"); return OZ_ERR_STATE; }
-    hipSetDevice(m->device);
-    const int G = m->d.G;
-    double* dv = reinterpret_cast<double*>(m->rc_legal);          // (the staging of oz_mcts_root_counts: [G] 8-byte words and [G] codes)
-    int32_t* dr = m->rc_rc;
-    hipLaunchKernelGGL(k_proven_root_values, dim3(G), dim3(64), 0, m->stream, m->d, dv, dr);
-    OZ_HIP(hipGetLastError());
-    OZ_HIP(hipMemcpyAsync(value, dv, 8ull * G, hipMemcpyDeviceToHost, m->stream));
-    OZ_HIP(hipMemcpyAsync(rc, dr, 4ull * G, hipMemcpyDeviceToHost, m->stream));
-    OZ_HIP(hipStreamSynchronize(m->stream));
-    return OZ_OK;
-}
 // oz_proof_play of one root, on the host: needs no device.  edge[sq] = -1 / 0 / +1 or OZ_PROOF_UNKNOWN as oz_mcts_root_proofs gives them
 // (read on the legal squares), own_value likewise; counts = the root's 64 raw counts.
 OZ_API int oz_search_proof_play(uint64_t legal, const int8_t* edge, int own_value, const int32_t* counts, int8_t* val, uint64_t* keep, int32_t* row,
@@ -2931,47 +2855,6 @@ OZ_API int oz_forced_playouts_prune(const int32_t* N, const double* Q, const dou
         for (int sq = 0; sq < 64; ++sq)
             out[sq] = ((legal[i] >> sq) & 1) ? oz_forced_prune(n[sq], q[sq], p[sq], e[sq], n[star], q[star], p[star], e[star], sq == star, Ns[i], c, eps, k) : 0;
     }
-    return OZ_OK;
-}
-
-// move sampling on the current roots of the active slots (the drop-in path's move rule: the engine's sample_move, the same keys).
-// action[g] = the sampled square; -1 where rc[g] != 0 (rc as k_root_counts) and on an idle slot.
-__global__ __launch_bounds__(64) void k_sample_moves(MctsDev t, double temperature, uint64_t seed, const uint64_t* __restrict__ game_ids,
-                                                     const int* __restrict__ plies, int32_t* action_out, int32_t* rc_out) {
-    const int g = blockIdx.x, lane = threadIdx.x;
-    const uint64_t own = uni64(t.root_own[g]), opp = uni64(t.root_opp[g]);
-    const uint64_t legal = oz_legal(own, opp, t.valid);
-    const int node = root_lookup(t, g, own, opp, lane);
-    int cnt = 0, rc = 0, action = -1;
-    if (node < 0) rc = 1;
-    else if (*rec_Ns(t, g, node) == 0) rc = 2;
-    else if ((legal >> lane) & 1)
-        cnt = (int)(rec_edge(t, g, node, oz_popc(legal & ((1ULL << lane) - 1ULL)))->n_tag & ~OZ_TAG_F32);
-    rc = unii(rc);
-    const int mx = unii(wave_max_i32(cnt));
-    if (rc == 0 && mx >= 1 && t.active[g])
-        action = sample_move(cnt, legal, mx, temperature, oz_rng_unit(oz_rng(seed, uni64(game_ids[g]), (uint64_t)unii(plies[g]), OZ_RNG_SAMPLE)), lane);
-    if (lane == 0) { action_out[g] = action; rc_out[g] = rc; }
-}
-static int sample_check(const char* fn, double temperature) {
-    OZ_REQUIRE(temperature >= 0.01 && temperature <= 100.0, "%s: temperature %g outside [0.01, 100]", fn, temperature);     // (NaN fails both compares)
-    return OZ_OK;
-}
-OZ_API int oz_mcts_sample_moves(oz_mcts* m, double temperature, uint64_t seed, const uint64_t* game_ids, const int32_t* plies, int32_t* action, int32_t* rc) {
-    OZ_REQUIRE(m && game_ids && plies && action && rc, "null argument");
-    if (int r = sample_check("oz_mcts_sample_moves", temperature)) return r;
-    std::lock_guard<std::mutex> lk(m->mu);
-    OZ_REFUSE_GUMBEL(m, "oz_mcts_sample_moves", "move sampling");
-    hipSetDevice(m->device);
-    const int G = m->d.G;
-    for (int i = 0; i < G; ++i) OZ_REQUIRE(plies[i] >= 0, "oz_mcts_sample_moves: plies[%d] = %d", i, plies[i]);
-    if (int r = stage_keys(m, game_ids, plies)) return r;
-    int32_t* da = m->rc_counts; int32_t* dr = m->rc_rc;           // (the staging of oz_mcts_root_counts: [G][64] and [G])
-    hipLaunchKernelGGL(k_sample_moves, dim3(G), dim3(64), 0, m->stream, m->d, temperature, seed, (const uint64_t*)m->noise_ids, (const int*)m->noise_plies, da, dr);
-    OZ_HIP(hipGetLastError());
-    OZ_HIP(hipMemcpyAsync(action, da, 4ull * G, hipMemcpyDeviceToHost, m->stream));
-    OZ_HIP(hipMemcpyAsync(rc, dr, 4ull * G, hipMemcpyDeviceToHost, m->stream));
-    OZ_HIP(hipStreamSynchronize(m->stream));
     return OZ_OK;
 }
 
@@ -3412,28 +3295,23 @@ __device__ __forceinline__ void sp_move_body(const GamesDev& gm, const MctsDev& 
     }
     const bool is_legal = (legal >> lane) & 1;
     int cnt = 0;
-    if (is_legal) cnt = (int)(rec_edge(t, g, node, oz_popc(legal & ((1ULL << lane) - 1ULL)))->n_tag & ~OZ_TAG_F32);
+    if (is_legal) cnt = (int)(lane_edge(t, g, node, legal, lane)->n_tag & ~OZ_TAG_F32);
     gm.last_counts[(size_t)g * 64 + lane] = cnt;
-    // proof play: the root's proof entry and what it keeps of the counts (oz_proof_play, oz_common.h); every value is wave-uniform
+    // proof play: what the root's proof entry keeps of the counts (proof_row); every value is wave-uniform
     int pval = OZ_PROOF_NONE, pfall = 0;
     uint64_t pkeep = legal;
     (void)pval; (void)pfall; (void)pkeep;
     if constexpr (PROVEN) {
-        const OzProof* pe = t.pf.entry + (size_t)g * t.node_cap + node;
-        int pbad;
-        pval = oz_proof_play(uni64(pe->legal), uni64(pe->lo), uni64(pe->hi), unii(pe->own), __ballot(cnt > 0), &pkeep, &pfall, &pbad);
+        const ProofRow p = proof_row(t, g, node, cnt);
+        pval = p.val; pkeep = p.keep; pfall = p.fall;
     }
-    // record_values: the root value of this search from the RAW counts and the stored Q (oz_root_term / oz_root_mean, oz_common.h)
+    // record_values: the root value of this search from the RAW counts and the stored Q (root_value)
     double rootv = 0.0;
     (void)rootv;
     if constexpr (VALUES) {
         if (gm.log_values) {
             __shared__ double terms[64];
-            terms[lane] = oz_root_term(cnt, is_legal ? rec_edge(t, g, node, oz_popc(legal & ((1ULL << lane) - 1ULL)))->q : 0.0);
-            const int total = wave_sum_i32(cnt);
-            wave_sync();
-            int vrc;
-            rootv = oz_root_mean(terms, (long long)total, &vrc);
+            rootv = root_value(terms, cnt, is_legal ? lane_edge(t, g, node, legal, lane)->q : 0.0, lane).v;
             wave_sync();                                         // the next move of this wave (free-running loop) writes terms[] again
             if constexpr (PROVEN) { if (pval != OZ_PROOF_NONE) rootv = (double)pval; }
         }
@@ -3485,7 +3363,7 @@ __device__ __forceinline__ void sp_move_body(const GamesDev& gm, const MctsDev& 
             q = sterm[lane] / (sum == 0 ? 1.0 : sum);
             wave_sync();
         }
-        sterm[lane] = oz_surprise_term(q, is_legal ? rec_edge(t, g, node, oz_popc(legal & ((1ULL << lane) - 1ULL)))->p : 0.0);
+        sterm[lane] = oz_surprise_term(q, is_legal ? lane_edge(t, g, node, legal, lane)->p : 0.0);
         wave_sync();
         surp = surprise_sum(sterm);
         wave_sync();                                             // the next move of this wave (free-running loop) writes sterm[] again

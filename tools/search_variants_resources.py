@@ -16,9 +16,10 @@ FIELDS = ("VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "LDS Size [bytes/block]"
 TREE = {"": 0, "_n": 4, "_sel": 8, "_n_sel": 12, "_g": 16}                                   # TV_NOISE, TV_SEL, TV_GUMBEL
 ADVANCE = {"": 0, "_v": 8, "_x": 12, "_xs": 28}                                               # AV_EXTRAS, AV_VALUES, AV_SURPRISE
 MOVE = {"": 0, "_s": 1, "_c": 3, "_f": 15, "_g": 24, "_fs": 47, "_gs": 56, "_r": 79, "_rs": 111, "_p": 143, "_ps": 175, "_pr": 207, "_prs": 239, "_pa": 128}
+READ = {"root_counts": 0, "pruned_counts": 1, "proven_counts": 2, "root_values": 4, "proven_root_values": 6, "sample_moves": 8, "proven_sample_moves": 10}
 FAMILIES = [("k_wide_backup_select", TREE), ("k_wide_expand_backup", TREE), ("k_wide_select", TREE), ("k_backup_select", TREE), ("k_expand_backup", TREE),
-            ("k_select", TREE), ("k_backup_advance", ADVANCE), ("k_advance", ADVANCE), ("k_sp_move", MOVE)]
-PER_STEP = {f for f, table in FAMILIES if table is not MOVE}
+            ("k_select", TREE), ("k_backup_advance", ADVANCE), ("k_advance", ADVANCE), ("k_sp_move", MOVE), ("k_", READ)]
+PER_STEP = {f for f, table in FAMILIES if table is not MOVE and table is not READ}
 
 
 def parse(path):
@@ -35,11 +36,11 @@ def parse(path):
 
 def successor(sig):
     """demangled signature of a parent kernel -> (family, 'family<mask>') of this commit's kernel, or (None, None)"""
-    m = re.match(r"(?:void )?(\w+?)(?:<(\d+)>)?\(", sig)
+    m = re.match(r"(?:void )?(\w+?)(?:<(\d+)u?>)?\(", sig)
     name, signs = m.group(1), int(m.group(2) or 0)
     for family, table in FAMILIES:
         if name.startswith(family) and name[len(family):] in table:
-            return family, "%s<%du>" % (family, table[name[len(family):]] | signs)
+            return family, "%s<%du>" % ("k_root_read" if table is READ else family, table[name[len(family):]] | signs)
     return None, None
 
 
