@@ -531,6 +531,13 @@ static int launch_h2(const OzLayerShape& L, const void* in, const uint4* W, cons
     return OZ_OK;
 }
 
+// k_gemm_b3_big keeps the offsets of its A rows in 32 bits (uint4 units, ~0u = a row beyond M); k_gemm_b3 keeps them in 64.  The largest offset the
+// big tile forms over the boards its `rows` leading rows touch: the last pixel row of the last board plus a tap offset, boards x Hin^2 x rowq +
+// 9 x Hin x rowq with rowq = Cin / 32 x 12 (at most 87380 boards of 8x8 conv3 at 2048 filters).  Beyond it the layer runs on the 128-row tile.
+static bool b3_big_offsets_fit(const OzLayerShape& L, long long rows) {
+    const long long rowq = L.Cin / 32 * 12, boards = (rows + L.pixels() - 1) / L.pixels();
+    return boards * L.Hin * L.Hin * rowq + 9ll * L.Hin * rowq < 0xFFFFFFFFll;
+}
 // big_rows: the leading rows of the layer that run on the 256 x 256 tile (k_gemm_b3_big; 'valid' layers only), the rows behind them on the
 // 128 x 256 tile: 0 = one launch of 128-row tiles, >= max_count's rows = one launch of 256-row tiles, in between (a multiple of 256) = the mixed
 // plan, two launches back to back -- the second one's row tiles start at big_rows (B3Geom::mt0) and its grid covers what the call has beyond them.
@@ -547,6 +554,7 @@ static int launch_b3(const OzLayerShape& L, const uint4* in, const uint4* W, con
     const long long rows = (long long)max_count * P;
     OZ_REQUIRE(big_rows == 0 || L.pad == 0, "gemm_b3: the 256-row tile needs a 'valid' layer (pad=%d)", L.pad);
     OZ_REQUIRE(big_rows >= rows || big_rows % B3B_BM == 0, "gemm_b3: a mixed plan's 256-row part must be whole tiles (%lld rows)", big_rows);
+    OZ_REQUIRE(big_rows == 0 || b3_big_offsets_fit(L, big_rows < rows ? big_rows : rows), "gemm_b3: %lld rows are beyond the 256-row tile's 32-bit row offsets", big_rows);
     void* dst = ksplit > 1 ? (void*)slabs : out;
     if (big_rows > 0) {
         const int num_mt = (int)(((big_rows < rows ? big_rows : rows) + B3B_BM - 1) / B3B_BM);
@@ -608,9 +616,11 @@ static long long b3_big_rows(long long rows, int N, bool may_mix) {
 // rows of a 'valid' 3x3 layer on the big tile whatever it costs, whatever the k split -- a test switch: only what the kernels need is asked of it)
 static long long b3_plan_rows(const OzLayerShape& L, long long rows_cap, int ksplit, int tile_opt, int mix_opt) {
     if (tile_opt == 128 || L.pad != 0) return 0;
-    if (tile_opt == 256) return ksplit == 1 ? rows_cap : 0;
-    if (mix_opt > 0 && L.taps == 9) return mix_opt % B3B_BM == 0 && mix_opt < rows_cap ? mix_opt : ksplit == 1 ? b3_big_rows(rows_cap, L.N, false) : 0;
-    return ksplit == 1 ? b3_big_rows(rows_cap, L.N, mix_opt == 0) : 0;
+    const long long big = tile_opt == 256 ? (ksplit == 1 ? rows_cap : 0)
+                        : mix_opt > 0 && L.taps == 9 ? (mix_opt % B3B_BM == 0 && mix_opt < rows_cap ? mix_opt : ksplit == 1 ? b3_big_rows(rows_cap, L.N, false) : 0)
+                        : ksplit == 1 ? b3_big_rows(rows_cap, L.N, mix_opt == 0) : 0;
+    // (whatever asked for the big tile, a forced tile included: its 32-bit row offsets must reach the rows it is given)
+    return big > 0 && b3_big_offsets_fit(L, big < rows_cap ? big : rows_cap) ? big : 0;
 }
 static int b3_plan_kernel(long long big_rows, long long rows_cap) {
     return big_rows <= 0 ? OZ_NET_KERNEL_B3 : big_rows >= rows_cap ? OZ_NET_KERNEL_B3_BIG : OZ_NET_KERNEL_B3_MIXED;
@@ -657,7 +667,7 @@ int oz_gemm_b3_launch(const void* in_b3, const void* Wb, const float* scale, con
                       const void* zero_line, int tag, int* plan_out) {
     const OzLayerShape L = {Hin, Hout, pad, Cin, taps, N};
     const long long Mmax = (long long)max_count * L.pixels();
-    const bool big = pad == 0 && b3_big_rows(Mmax, N, false) > 0;     // (one tile per launch here: the trainer does not mix)
+    const bool big = pad == 0 && b3_big_rows(Mmax, N, false) > 0 && b3_big_offsets_fit(L, Mmax);     // (one tile per launch here: the trainer does not mix)
     // (one 144 KB block per CU)
     const int ksplit = !big && partial ? trainer_ksplit(((Mmax + B3_BM - 1) / B3_BM) * (N / B3_BN), L.K() / B3_BK, Mmax * N, partial_floats) : 1;
     auto go = [&](auto t) {
@@ -1182,7 +1192,7 @@ struct OnnNet : oz_net {
         return sizing() > 32 && sizing() <= 1024 && ((rows + 127) / 128) * (C / 256) <= 256;
     }
     size_t partial_floats() const {
-        if (max_batch <= 32) return (size_t)16 * max_batch * 64 * 1024;
+        if (max_batch <= 32) return (size_t)16 * max_batch * 64 * (C > 1024 ? C : 1024);      // 16 slabs of the widest layer: fc1's 1024 columns, or C over <= 64 pixels
         size_t need = (size_t)(sizing() >= 1024 ? 4 : 16) * max_batch * 1024;        // fc1 (forward_h2: kfc1)
         const OzLayers L = layers();
         const int bm[3] = {256, 192, conv4_low() ? 128 : 256};

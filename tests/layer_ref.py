@@ -12,6 +12,8 @@ evaluated by tests/test_layer_parity_cpu.py on every run, never from what a kern
   E32 2.2e-7 .. 3.4e-7 on the five shapes of that test
   bf16x3, complete six-term product 1.2 .. 1.6 x E32, any single kept term removed >= 24 x E32   -> MARGIN_B3 = MARGIN_F32 = 6
   f16x2, complete three-term product 2.8 .. 3.5 x E32, any single term removed >= 1500 x E32      -> MARGIN_H2 = 16
+  (at the five shapes of 384 / 768 / 1024 filters added later, K = 3072 .. 12288, still 8 terms a column: E32 2.3e-7 .. 2.7e-7, bf16x3 complete
+   1.3 .. 2.2 x, weakest term removed >= 25 x; f16x2 complete 3.2 .. 4.0 x, weakest >= 1900 x -- the same margins hold)
 (a margin is a few times the modelled healthy value and at least four times below the weakest single-term defect; the exact-fp32 kernels are
 held to the bf16x3 margin: bf16x3 claims fp32's accuracy)
 Few-row samples.  norm_c is the SCALE of channel c; taken over one row (a dense layer of a one-board call) it is |z64| of that single element, the
@@ -60,7 +62,8 @@ def sparse_columns(kernel, rs, nnz=SPARSE_NNZ):
 def _biregular(rows, cols, per_row, per_col, rs):
     """a random 0/1 pattern (rows, cols) with exactly per_row ones in every row and per_col in every column: the row stubs against a random
     permutation of the column stubs, a stub pair that repeats an earlier (row, col) re-dealt by swapping its column with a random other stub's"""
-    assert rows * per_row == cols * per_col and per_row <= cols and per_col <= rows
+    assert rows * per_row == cols * per_col and per_row <= cols and per_col <= rows, \
+        f"no biregular pattern for a kernel of shape ({rows}, {cols}): {per_row} entries a row are {rows * per_row / cols:g} a column"
     r = np.repeat(np.arange(rows), per_row)
     c = rs.permutation(np.repeat(np.arange(cols), per_col))
     for _ in range(1000):
@@ -78,11 +81,20 @@ def _biregular(rows, cols, per_row, per_col, rs):
     return keep
 
 
+def dense_per_row(K, N, nnz=SPARSE_NNZ):
+    """entries per input row of a bisparse dense kernel (K, N): max(2, N nnz / K), lowered (never below 2) until the entries per column, per_row K / N,
+    are whole -- fc1 of 6x6 at 384 filters, (1536, 1024): 5 a row would be 7.5 a column, 4 a row are 6.  Every kernel whose first value is whole keeps it"""
+    per_row = max(2, N * nnz // K)
+    while per_row > 2 and per_row * K % N:
+        per_row -= 1
+    return per_row
+
+
 def bisparse_kernel(kernel, rs, nnz=SPARSE_NNZ):
     """`kernel` thinned in BOTH directions, so that the forward sum (over k, for an output column) and the data-gradient sum (over (tap, co), for
     an input channel) are both short.  3x3 kernels (3, 3, Cin, Co): exactly nnz entries per output channel and exactly nnz per input channel, each
-    at a random tap (the (ci, co) pairs are a biregular pattern, so no position repeats).  Dense kernels (K, N): exactly `per_row` = max(2, N nnz / K)
-    entries per input row and per_row K / N per output column (= nnz wherever N nnz / K >= 2).  Kept entries are scaled by sqrt(K / entries per
+    at a random tap (the (ci, co) pairs are a biregular pattern, so no position repeats).  Dense kernels (K, N): exactly `per_row` = dense_per_row(K, N)
+    = max(2, N nnz / K) entries per input row and per_row K / N per output column (= nnz wherever N nnz / K >= 2 and divides).  Kept entries are scaled by sqrt(K / entries per
     column), as sparse_columns does"""
     w = np.asarray(kernel)
     if w.ndim == 4:
@@ -94,7 +106,7 @@ def bisparse_kernel(kernel, rs, nnz=SPARSE_NNZ):
         K, per_col = 9 * ci, nnz
     else:
         K, N = w.shape
-        per_row = max(2, N * nnz // K)
+        per_row = dense_per_row(K, N, nnz)
         per_col = per_row * K // N
         keep = _biregular(K, N, per_row, per_col, rs)
     out = (np.where(keep, w, np.float32(0)) * np.float32(np.sqrt(K / per_col))).astype(np.float32)

@@ -95,6 +95,49 @@ def test_preconditions_and_switches():
             b3_plan(**args)
 
 
+def test_three_column_tiles_never_mix():
+    """768 filters: 256 CUs are no whole number of rounds of three column tiles (b3_whole_round_rows returns 0 when 256 % (N / 256) != 0), so the plan
+    is one tile for the whole layer at every capacity -- also where 512 filters mix"""
+    mixed_512 = 0
+    for n in (8, 6):
+        for capacity in list(range(128, 6000, 7)) + [911, 4096, 8192]:
+            for layer in (CONV3, CONV4):
+                p = b3_plan(n, 768, capacity, layer)
+                assert p["kernel"] in ("b3", "b3_big"), (n, capacity, layer, p)
+                if p["kernel"] == "b3_big":
+                    rows = capacity * (n - 2 * (layer - 1)) ** 2
+                    assert p["big_rows"] == rows and _blocks(rows, 256, 768) >= 192
+                mixed_512 += b3_plan(n, 512, capacity, layer)["kernel"] == "b3_mixed"
+    assert mixed_512 > 100
+    assert b3_plan(8, 512, 4096, CONV3)["kernel"] == "b3_mixed" and b3_plan(8, 768, 4096, CONV3) == dict(kernel="b3_big", big_rows=147456, small_tiles=0)
+    # four column tiles (1024 filters) do mix: 256 % 4 == 0
+    assert any(b3_plan(8, 1024, capacity, CONV3)["kernel"] == "b3_mixed" for capacity in range(456, 4097, 8))
+    # a forced boundary is still honoured at 768 (the switch asks only what the kernels need)
+    assert b3_plan(8, 768, 225, CONV3, kslices=1, mix_rows=256) == dict(kernel="b3_mixed", big_rows=256, small_tiles=62)
+
+
+def test_the_big_tile_stops_at_its_32_bit_row_offsets():
+    """k_gemm_b3_big keeps the offsets of its A rows in 32 bits (uint4 units: an input pixel row is Cin / 32 x 12 of them, ~0u marks a row beyond M);
+    k_gemm_b3 keeps them in 64.  The big tile may cover boards x Hin^2 x rowq + 9 x Hin x rowq < 2^32 - 1 only: 8x8 conv3 at 2048 filters, rowq = 768,
+    64 pixel rows a board -> 87380 boards; beyond, the plan is the 128-row tile, whatever asked for the big one.  Host only: nothing is allocated"""
+    rowq, hin = 2048 // 32 * 12, 8
+    fits = lambda boards: boards * hin * hin * rowq + 9 * hin * rowq < 2 ** 32 - 1
+    last = (2 ** 32 - 2 - 9 * hin * rowq) // (hin * hin * rowq)
+    assert last == 87380 and fits(last) and not fits(last + 1)
+    for tile in (0, 256):
+        below, above = b3_plan(8, 2048, last, CONV3, tile=tile), b3_plan(8, 2048, last + 1, CONV3, tile=tile)
+        assert below["kernel"] in ("b3_big", "b3_mixed") and below["big_rows"] > 0, (tile, below)
+        assert above == dict(kernel="b3", big_rows=0, small_tiles=-(-(last + 1) * 36 // 128)), (tile, above)
+    assert b3_plan(8, 2048, last, CONV3, tile=256) == dict(kernel="b3_big", big_rows=last * 36, small_tiles=0)
+    # conv4 reads 6x6 inputs: its limit lies 64 / 36 further out, and a mixed plan is judged on the rows its big part covers
+    assert b3_plan(8, 2048, last + 1, CONV4, tile=256)["kernel"] == "b3_big"
+    last4 = (2 ** 32 - 2 - 9 * 6 * rowq) // (36 * rowq)
+    assert b3_plan(8, 2048, last4, CONV4, tile=256)["kernel"] == "b3_big" and b3_plan(8, 2048, last4 + 1, CONV4, tile=256)["kernel"] == "b3"
+    assert b3_plan(8, 2048, last + 1, CONV3, kslices=2, mix_rows=256) == dict(kernel="b3_mixed", big_rows=256, small_tiles=-(-(last + 1) * 36 // 128) - 2)
+    # every shape the suite runs is far inside: the plans of the other tests in this file are unchanged
+    assert b3_plan(8, 512, 4096, CONV3) == dict(kernel="b3_mixed", big_rows=131072, small_tiles=128)
+
+
 def test_profile_summary_counts_the_two_launches_of_a_mixed_layer_as_one_layer():
     """tools/summarize_prof.py labels layers by launch order: k_gemm_b3_big<3> followed by k_gemm_b3<3> is conv3 twice, and conv4 / fc1 / fc2 keep their names"""
     import importlib.util

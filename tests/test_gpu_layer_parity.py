@@ -11,8 +11,12 @@ the CPU test the demonstration).  The ratio under the call's own norm is printed
 
 The matrix runs every tile / split-K / reduce / main-loop configuration the three forwards can select, each at three call sizes (full capacity, an
 odd size that is no multiple of a tile height, one board), and proves which kernel ran from NNetWrapper.layer_plan(); the last test asserts that
-the configurations seen are exactly the list REQUIRED.  One line per (precision, case, layer, network kind, call size) is printed: err, E32, ratio
-(the table of one run: profiles/layer_parity_ratios.txt)."""
+the configurations seen are exactly the list REQUIRED.  WIDTH_CASES repeat the matrix at 384 (f32), 768 (all three) and 1024 filters, where only the
+index arithmetic differs -- odd column-tile counts in both block mappings, k splits that do not divide the k-tiles, fc1 at K = 12288 -- under the
+same margins; REQUIRED_WIDTHS names every (precision, kernel, filters) they must reach.  One line per (precision, case, layer, network kind, call
+size) is printed: err, E32, ratio, and one per case with its time (the table of one run: profiles/layer_parity_ratios.txt)."""
+import time
+
 import numpy as np
 import pytest
 
@@ -186,6 +190,35 @@ CASES = [
     _case("b3-k1-k2", "bf16x3", 8, 512, 384, (384, 317, 1), {1: ("lut_xcd", 1), 2: ("b3", 1), 3: ("b3", 2), 4: ("b3", 8), 5: ("b3", 4)}),
     _case("b3-big", "bf16x3", 8, 512, 384, (384, 317, 1), {2: ("b3_big", 1)}, b3_tile=256),
 ]
+# ---- widths other than 256 and 512: the same kernels under other index arithmetic -- 384 filters (f32: three 128-column tiles, never the 256 x 256
+# tile) and 768 (the split precisions: three 256-column tiles, 216 k-tiles per 3x3 layer, fc1 with K = 12288 on 8x8), one case at 1024 (four column
+# tiles).  Capacities as above: the smallest at which the launcher's own condition selects the configuration at THAT width.
+WIDTH_CASES = [
+    # ---- f32, 384 filters
+    # the weight streams: kb must divide Cin = 384 -- 256 does not, 128 leaves 3 x 27 = 81 blocks, so the loop ends on 64 (54 slices of conv3 / conv4)
+    _case("f32-c384-skinny", "f32", 6, 384, 4, (4, 3, 1), {1: ("lut", 1), 2: ("f32_skinny", 54), 3: ("f32_skinny", 54), 4: ("f32_skinny", 24), 5: ("f32_skinny", 16)}),
+    # GmStd with the k loop split + k_splitk_reduce_f32: 108 k-tiles; conv4's eight slices do not divide them (13.5 each).  The generic gather at 384
+    _case("f32-c384-splitk", "f32", 8, 384, 96, (96, 85, 1), {1: ("lut", 1), 2: ("f32_std", 4), 3: ("f32_std", 8), 4: ("f32_std", 16), 5: ("f32_std", 4)}),
+    _case("f32-c384-pixmajor", "f32", 8, 384, 256, (256, 203, 1), {1: ("f32_std_pixmajor", 1), 2: ("f32_std", 2), 3: ("f32_std", 4)}, tables=0),
+    # 1359 boards: conv3's 48924 rows are 192 tiles of 256 rows, where 256 and 512 filters move to the 256 x 256 tile; N % 256 keeps 384 on GmStd, unsplit
+    _case("f32-c384-unsplit", "f32", 8, 384, 1359, (1359, 1201, 1), {1: ("lut", 1), 2: ("f32_std", 1), 3: ("f32_std", 1), 4: ("f32_std", 1), 5: ("f32_std", 1)}),
+    # ---- f16x2, 768 filters
+    # the small-capacity tiles: 16 slices of 216 k-tiles (13.5 each); fc1 with K = 12288
+    _case("h2-c768-small2", "f16x2", 8, 768, 8, (8, 7, 1), {1: ("lut", 1), 2: ("h2_small2", 16), 3: ("h2_small2", 16), 4: ("h2_small2", 16), 5: ("h2_thin2", 8)}),
+    # capacity 128: conv_ksplit with three column tiles stops at 4 slices (72 x 3 blocks want 8 at 256 filters)
+    _case("h2-c768-lowpp1", "f16x2", 8, 768, 128, (128, 101, 1), {1: ("lut", 1), 2: ("h2_lowpp1", 4), 3: ("h2_lowpp1", 4), 4: ("h2_lowpp1", 16), 5: ("h2_thin", 8)}),
+    _case("h2-c768-lowpp", "f16x2", 8, 768, 128, (128, 101, 1), {2: ("h2_lowpp", 4), 3: ("h2_lowpp", 4), 4: ("h2_lowpp", 16)}, low_loop_phases=2),
+    _case("h2-c768-midpp", "f16x2", 8, 768, 128, (128, 101, 1), {2: ("h2_midpp", 4)}, conv3_tile=192),
+    # ---- bf16x3, 768 filters (capacity >= B3_MIN_BATCH: k_gemm_b3 runs)
+    _case("b3-c768-split", "bf16x3", 8, 768, 128, (128, 101, 1), {1: ("lut", 1), 2: ("b3", 2), 3: ("b3", 4), 4: ("b3", 8), 5: ("b3", 4)}),
+    # conv_b3_ksplit stops splitting conv3 where ceil(36 mb / 128) x 3 >= 192 blocks: 64 row tiles, 225 boards (224 boards are 63 tiles)
+    _case("b3-c768-unsplit", "bf16x3", 8, 768, 225, (225, 187, 1), {1: ("lut", 1), 2: ("b3", 1), 3: ("b3", 4), 4: ("b3", 8), 5: ("b3", 4)}),
+    _case("b3-c768-conv2-gemm", "bf16x3", 8, 768, 225, (225, 187, 1), {1: ("b3", 1)}, tables=0),
+    _case("b3-c768-big", "bf16x3", 8, 768, 225, (225, 187, 1), {2: ("b3_big", 1)}, b3_tile=256),
+    # ---- 1024 filters, 6x6 (the weights stay at 126 MB): four column tiles, 288 k-tiles
+    _case("h2-c1024-6x6", "f16x2", 6, 1024, 128, (128, 101, 1), {1: ("lut", 1), 2: ("h2_bigpp", 8), 3: ("h2_lowpp1", 8), 4: ("h2_lowpp1", 16), 5: ("h2_thin", 8)}),
+]
+CASES += WIDTH_CASES
 CASE_BY_NAME = {c["name"]: c for c in CASES}
 
 
@@ -227,8 +260,24 @@ REQUIRED = {
     "f16x2:h2_mid", "f16x2:fc1_bigpp_4_slices", "f16x2:h2_thin2", "f16x2:h2_thin", "f16x2:h2_thin4w", "f16x2:splitk_reduce_h2",
     "f16x2:gather", "f16x2:fc2_reduce_by_heads",      # not named by the list, run by every default f16x2 case: the gather writing h2 rows, fc2's slices left to the heads
     "bf16x3:b3_k1", "bf16x3:b3_k2", "bf16x3:b3_k4", "bf16x3:b3_k8", "bf16x3:splitk_reduce_b3", "bf16x3:b3_big", "bf16x3:conv2_gemm", "bf16x3:fc1_split",
-    "bf16x3:fc2_4_slices_by_heads", "bf16x3:gather_c256", "bf16x3:gather_c512",
+    "bf16x3:fc2_4_slices_by_heads", "bf16x3:gather_c256", "bf16x3:gather_c512", "bf16x3:gather_c768",
 }
+
+
+def width_ids(precision, C, layer, p):
+    """the width tag of a configuration: (precision, kernel, filters) of conv2 .. fc1 -- the layers whose N or K is the filter count (fc2 is 1024 x 512
+    at every width)"""
+    return {(precision, p["kernel"], C)} if layer <= 4 else set()
+
+
+# every (precision, kernel) the WIDTH_CASES exist for, at its width: required like REQUIRED, no more, no fewer
+REQUIRED_WIDTHS = {
+    ("f32", "lut", 384), ("f32", "f32_skinny", 384), ("f32", "f32_std", 384), ("f32", "f32_std_pixmajor", 384),
+    ("f16x2", "lut", 768), ("f16x2", "h2_small2", 768), ("f16x2", "h2_lowpp1", 768), ("f16x2", "h2_lowpp", 768), ("f16x2", "h2_midpp", 768),
+    ("bf16x3", "lut", 768), ("bf16x3", "b3", 768), ("bf16x3", "b3_big", 768),
+    ("f16x2", "lut", 1024), ("f16x2", "h2_bigpp", 1024), ("f16x2", "h2_lowpp1", 1024),
+}
+BASE_WIDTHS = (256, 512)            # the widths of the cases above WIDTH_CASES
 
 _results = {}
 
@@ -237,7 +286,7 @@ def run_case(oz, case):
     """every (network kind, call size, layer) of a case, measured once per session: list of dict(kind, count, layer, err, e32, plan)"""
     name = case["name"]
     if name not in _results:
-        rows = []
+        rows, t0 = [], time.perf_counter()
         n, C, mb, precision = case["n"], case["C"], case["mb"], case["precision"]
         for kind in ("sparse", "dense"):
             net = _net(oz, precision, n, C, mb, kind)
@@ -257,6 +306,7 @@ def run_case(oz, case):
                 r["kind"] = kind
                 rows.append(r)
                 print(_line(precision, name, r))
+        print(f"layer-parity {precision:7s} {name:16s} {C} filters, capacity {mb}: {time.perf_counter() - t0:.2f} s (networks built and committed on first use)")
         _results[name] = rows
     return _results[name]
 
@@ -387,8 +437,43 @@ def test_latency_splits(oz):
 
 def test_every_configuration_ran(oz):
     """the union of the cases runs every configuration of the list, as reported by layer_plan() -- no more, no fewer"""
-    seen = set()
+    seen, widths = set(), set()
     for case in CASES:
         for r in run_case(oz, case):
             seen |= config_ids(case["precision"], case["C"], r["layer"], r["plan"], r["count"])
+            widths |= width_ids(case["precision"], case["C"], r["layer"], r["plan"])
     assert seen == REQUIRED, f"missing {sorted(REQUIRED - seen)}, not in the list {sorted(seen - REQUIRED)}"
+    # ... and the widths outside 256 / 512: every (precision, kernel, filters) of REQUIRED_WIDTHS, required and not merely tolerated
+    widths = {w for w in widths if w[2] not in BASE_WIDTHS}
+    assert widths == REQUIRED_WIDTHS, f"missing {sorted(REQUIRED_WIDTHS - widths)}, not in the list {sorted(widths - REQUIRED_WIDTHS)}"
+
+
+def _row_tiles(case, r):
+    """row tiles of the launch that produced row r: the call's boards x output pixels over the plan's tile rows (pixel-major tiles hold one pixel of
+    128 consecutive boards each)"""
+    pix = R.layer_geometry(case["n"], case["C"], r["layer"])[1] ** 2
+    T = r["plan"]["tile_rows"]
+    return -(-r["count"] // T) * pix if r["plan"]["kernel"] == "f32_std_pixmajor" else -(-r["count"] * pix // T)
+
+
+def test_both_block_mappings_ran_at_an_odd_column_tile_count(oz):
+    """k_gemm_h2, k_gemm_b3 and k_gemm_b3_big map a block to (row tile, column tile, k-slice) in two ways: launches of fewer than 8 row tiles send
+    the blocks of one row tile round the XCDs (q = (jb / num_mt) * 8 + xcd, blocks with q >= per_mt return), the others send the row tiles round
+    (mt = (jb / per_mt) * 8 + xcd).  Read from the plan's tile rows and the call's rows, not from the case list: at 768 filters -- three column tiles,
+    per_mt = 3 x k-slices -- each family ran both, the one-board call the first and the full call the second; likewise k_gemm_f32 at 384 filters, whose
+    grid pads the row tiles to a multiple of 8.  And a k split that does not divide the k-tiles ran in f32 and f16x2 (bf16x3's are in the trainer matrix)"""
+    family = lambda k: "h2" if k.startswith("h2_") else k if k in ("b3", "b3_big") else "f32" if k.startswith("f32_std") else None
+    ran, ragged = set(), set()
+    for case in WIDTH_CASES:
+        C = case["C"]
+        for r in run_case(oz, case):
+            fam = family(r["plan"]["kernel"])
+            if fam is None or r["layer"] > 3:
+                continue
+            ran.add((fam, C, _row_tiles(case, r) >= 8))
+            if (9 * C // 32) % r["plan"]["kslices"]:
+                ragged.add(fam)
+    for fam, C, column_tile in (("h2", 768, 256), ("b3", 768, 256), ("b3_big", 768, 256), ("f32", 384, 128)):
+        assert (C // column_tile) % 2 == 1
+        assert {(fam, C, False), (fam, C, True)} <= ran, (fam, C, sorted(ran))
+    assert {"f32", "h2"} <= ragged, ragged

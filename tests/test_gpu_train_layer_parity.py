@@ -40,13 +40,20 @@ Budget: one layer's tensors at a time on the host (of each downloaded tensor onl
 case.  Measured: a bf16x3 trainer of 1535 boards holds 7.3 GB on the device (3.8 GB at 684, 2.5 GB at 383), the test process 1.7 GB on the host
 at its peak, a case takes 1 .. 2.2 s; the cases below 383 boards stay within 1 GB.
 
+Other widths (WIDTH_CASES): f32 at 384 filters, both split modes at 768, bf16x3 at 1024 -- the same kernels where the column tiles are three or four,
+the 216 / 288 k-tiles are cut into slices that do not divide them (8x8, 768 filters, 64 boards: 2 / 4 / 10 forward slices; 6x6, 32 boards: 9 / 16 / 16;
+1024 filters: 7 / 16 / 16) and the slabs sit three tiles apart; same margins, same classes (wgrad_class), plans asserted against tile_plan.  Kept
+columns on these shapes: tests/test_train_layer_parity_cpu.py (the float64 oracle, every shape before its batch was fixed).
+
 Left out, with the reason:
   * H2Small cannot be reached from the trainer: oz_gemm_h2_launch takes it only without a split-K buffer, and the trainer always passes one.
   * H2MidPP / H2BigPP from a short call on a large f16x2 trainer: that launcher is keyed on the call's boards, so a short call IS a small case.
   * k_gemm_b3_big with k-slices > 1 or on a 'same' layer, and the network object's mixed plan (b3_big_rows with may_mix): oz_gemm_b3_launch asks
     for neither (test_gpu_layer_parity.py and test_b3_mix_plan_cpu.py hold them on the inference side).
   * 6x6 on the chip-filling tiles: the same kernels and the same gather at other strides, 676 boards and more; not run.
-One line per (case, tensor, layer) is printed: the worst step's err, E32 and ratio (the table of one run: profiles/train_layer_parity_ratios.txt)."""
+One line per (case, tensor, layer) is printed: the worst step's err, E32 and ratio, and one per case with its time (the table of one run: profiles/train_layer_parity_ratios.txt)."""
+import time
+
 import numpy as np
 import pytest
 
@@ -234,6 +241,37 @@ CASES = [
     # (No f16x2 twin: that launcher is keyed on the call's boards, so a short call is one of the small cases above)
     _chip("b3-b37-of-684", "bf16x3", 37, {1: ("b3", "b3"), 2: ("b3_big", "b3"), 3: ("b3", "b3_big")}, Bmax=684),
 ]
+
+
+# ---- widths other than 128 / 256 / 512: 384 filters (f32) and 768 (the split modes: three
+# column tiles, 216 k-tiles that trainer_ksplit cuts into 2 .. 16 slices, 9 / 10 / 16 of which do not divide them), one case at 1024 (288 k-tiles in 7).
+# The forward k-slices are named here as well as taken from train_layer_ref.tile_plan; the octet split: 72 (f16x2) / 144 (bf16x3) tiles at 768 filters
+def _width(name, precision, n, C, B, fwd_slices, wgrad, msplit, Bmax=None, sharp_wgrad=()):
+    tile = "h2_lowpp" if precision == "f16x2" else "b3"
+    return _case(name, precision, n, C, B, {l: dict(fwd_kernel=tile, dgrad_kernel=tile, fwd_kslices=fwd_slices[l - 1], wgrad_kernel=wgrad, wgrad_msplit=msplit)
+                                            for l in (1, 2, 3)}, Bmax=Bmax, sharp_wgrad=sharp_wgrad)
+
+
+_TAPS1 = dict(wgrad_kernel="taps_f32", wgrad_msplit=1)
+WIDTH_CASES = [
+    # ---- f32, 384 filters: three 128-column tiles, 108 k-tiles
+    # (6x6: conv4 sums 32 rows, the sharp class; fc1 is (1536, 1024), thinned to 4 entries a row: layer_ref.dense_per_row)
+    _case("f32-c384-b8", "f32", 6, 384, 8, {l: _TAPS1 for l in (1, 2, 3)}, sharp_wgrad=(3,)),
+    _case("f32-c384-b192-wconv", "f32", 8, 384, 192, {l: dict(wgrad_kernel="boards_f32", wgrad_msplit=16) for l in (1, 2, 3)}),      # 6 x 3 tiles
+    _case("f32-c384-b65-dense-std", "f32", 8, 384, 65, {4: dict(fwd_kernel="f32_std", dgrad_kernel="f32_std"), 5: dict(fwd_kernel="f32_std", dgrad_kernel="f32_std")}),
+    _case("f32-c384-b64-dense-skinny", "f32", 8, 384, 64, {4: dict(fwd_kernel="f32_skinny", dgrad_kernel="f32_skinny"), 5: dict(fwd_kernel="f32_skinny", dgrad_kernel="f32_skinny")}),
+    # ---- f16x2, 768 filters
+    _width("h2-c768-b64", "f16x2", 8, 768, 64, (2, 4, 10), "oct_h2", 4, sharp_wgrad=(1, 2, 3)),
+    _width("h2-c768-b32-6x6", "f16x2", 6, 768, 32, (9, 16, 16), "oct_h2", 4, sharp_wgrad=(1, 2, 3)),
+    # ---- bf16x3, 768 filters
+    _width("b3-c768-b64", "bf16x3", 8, 768, 64, (2, 4, 10), "oct_b3", 2),
+    _width("b3-c768-b32-6x6", "bf16x3", 6, 768, 32, (9, 16, 16), "oct_b3", 2),
+    _width("b3-c768-b9-second-octet", "bf16x3", 6, 768, 9, (16, 16, 16), "oct_b3", 2, sharp_wgrad=(3,)),
+    _width("b3-c768-b37-of-64", "bf16x3", 8, 768, 37, (2, 4, 10), "oct_b3", 2, Bmax=64),
+    # ---- 1024 filters, 6x6: four column tiles; 256 octet tiles leave the weight gradient unsplit
+    _width("b3-c1024-b32-6x6", "bf16x3", 6, 1024, 32, (7, 16, 16), "oct_b3", 1),
+]
+CASES += WIDTH_CASES
 CASE_BY_NAME = {c["name"]: c for c in CASES}
 _results = {}
 
@@ -242,6 +280,7 @@ def run_case(case):
     name = case["name"]
     if name not in _results:
         precision, n, C, B, kind = (case[k] for k in ("precision", "n", "C", "B", "kind"))
+        t0 = time.perf_counter()
         w = R.network_weights(n, C, kind)
         tr = _trainer(precision, n, C, case["Bmax"], kind)
         if case["chip"] and B < case["Bmax"]:
@@ -258,6 +297,7 @@ def run_case(case):
         for r in worst.values():
             print(f"train-parity {precision:7s} {name:22s} {r['tensor']:5s} layer {r['layer']} {kind:8s} B {B:4d} steps {count:2d} {r['kernel']:16s} split {r['split']:2d} "
                   f"{r['cls']:6s} err {r['err']:.3e}  E32 {r['e32']:.3e}  ratio {r['err'] / r['e32']:6.2f}  margin {r['margin']:4.1f}  kept {r['kept']:.2f}")
+        print(f"train-parity {precision:7s} {name:22s} {C} filters, B {B}, {count} step(s): {time.perf_counter() - t0:.2f} s")
         _results[name] = (rows, plan, count)
     return _results[name]
 

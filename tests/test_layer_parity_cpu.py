@@ -12,6 +12,9 @@ import layer_ref as R
 ROWS = 96
 # (board, filters, layer): K = 2304 and 4608 for the convolutions, 4096 and 8192 for fc1, 1024 for fc2
 SHAPES = [(8, 256, 2, 2304), (8, 512, 2, 4608), (8, 256, 4, 4096), (8, 512, 4, 8192), (8, 256, 5, 1024)]
+# ... and the widths of the GPU matrix's WIDTH_CASES: K = 3456 (384 filters), 6912 (768), 9216 (1024) for the convolutions, fc1 at 12288 (8x8, 768) and 3072
+# (6x6, 768).  The sums are still 8 terms long, so the margins separate as they do above (the figures are printed on every run)
+SHAPES += [(8, 384, 2, 3456), (8, 768, 2, 6912), (6, 1024, 2, 9216), (8, 768, 4, 12288), (6, 768, 4, 3072)]
 _case_cache = {}
 
 
