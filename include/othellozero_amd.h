@@ -1455,6 +1455,49 @@ int oz_trainer_sqsum(oz_trainer* t, int what, double* out);
  * weights, moments and average move as under `iters` steps on the arena as it stands (the step count does not) -- for a scratch trainer. */
 int oz_trainer_time_optimizer(oz_trainer* t, int iters, double* ms3);
 
+/* ---- auxiliary heads (opt-in; without them every kernel, launch, arena size, file and result is unchanged)
+ * KataGo's auxiliary targets from the END of the game: an ownership head and a score head on f2 (the 512 post-dropout features the policy and
+ * value heads read), trained with the trunk and then thrown away -- the search, predict and the inference network never see them.
+ * The target, one definition (oz_aux_target, csrc/oz_common.h; on the host oz_aux_targets): a record's final board from the mover's side,
+ * (fin_own, fin_opp) = (final_black, final_white) for player == +1, swapped otherwise; both words 0 = "no auxiliary target" for a record of
+ * an adjudicated game (pad[1] == 1: its board at the stop is no final board) and for the fast record of a playout cap (pad[0] == 1).  A real
+ * final board is never empty: fin_own | fin_opp == 0 is the mask m = 0.  With A = n*n: ownership target t_a = +1 / -1 / 0 for a square of
+ * fin_own / of fin_opp / empty, score target s* = (popcount(fin_own) - popcount(fin_opp)) / A.  A symmetry acts on the pair as on the boards.
+ * Heads and losses (fp32 in every trainer precision):  o_a = tanh(f2 . Wown[:, a] + bown[a]),  s = tanh(f2 . Wsc + bsc),
+ *   L_own = (1/B) sum_b m_b (1/A) sum_a (o_a - t_a)^2,   L_sc = (1/B) sum_b m_b (s - s*)^2      (B = the batch, as the value loss divides)
+ *   total loss = policy + value + w_own L_own + w_score L_sc   (losses[0]; the policy and value numbers stay what they were).
+ * Weights: four arrays behind the forty -- 40 Wown [512][A], 41 bown [A], 42 Wsc [512], 43 bsc [1] -- at the end of the parameter, gradient
+ * and Adam arenas (the forty keep their offsets; the arena then ends with bsc, without padding: oz_trainer_arena_size_aux =
+ * oz_trainer_arena_size + 512 A + A + 512 + 1).  oz_trainer_set_weight / get_weight / get_grad / get_adam_state / get_weight_average take the
+ * indices 40 .. 43; the optimiser options and the weight average act on the larger arena (the default decay mask gains
+ * the two kernels 40 and 42; an explicit decay_mask names arrays 0 .. 39 only).  A fresh head is Glorot-uniform from the trainer's seed, biases 0.
+ * oz_trainer_set_aux_heads: before the first step (OZ_ERR_STATE later); OZ_ERR_ARG for a negative or non-finite weight; again before the first
+ * step it only replaces the two weights.  OZ_ERR_ARG for a trainer created on an external gradient arena (a data-parallel fit): the library
+ * cannot see the size of a caller's arena, one sized for the forty arrays would be written past its end, and the final pairs do not travel
+ * through the pooled rows anyway; the heads' arenas are always library-owned (oz_trainer_arena_size_aux says how large they are).
+ * Both weights 0: the heads' forward and losses run, no backward kernel is launched, and the forty gradients and three losses are those of a
+ * trainer without the heads, bit for bit.
+ * Data: _forward_backward_aux / _set_dataset_aux take the examples' pairs; the entry points without them feed every mask 0.  An epoch from a
+ * replay buffer needs one that keeps the pairs (oz_replay_create_aux; OZ_ERR_ARG otherwise).  losses5 = {total, policy, value, L_own, L_sc}.
+ * oz_trainer_evaluate* do not run the heads. */
+int oz_aux_targets(const oz_record* records, int64_t R, uint64_t* fin_own /* [R] */, uint64_t* fin_opp /* [R] */);      /* host only, no GPU needed */
+int oz_trainer_arena_size_aux(int n, int channels, int in_channels, int64_t* nelem);
+int oz_trainer_set_aux_heads(oz_trainer* t, float w_own, float w_score);
+int oz_trainer_get_aux_heads(oz_trainer* t, int* on, float* w_own, float* w_score);
+int oz_trainer_forward_backward_aux(oz_trainer* t, const uint64_t* own, const uint64_t* opp, const float* pi_target, const float* z_target,
+                                    const uint64_t* fin_own, const uint64_t* fin_opp, int B, float* losses5);
+int oz_trainer_set_dataset_aux(oz_trainer* t, const uint64_t* own, const uint64_t* opp, const float* pi_target, const float* z_target,
+                               const uint64_t* fin_own, const uint64_t* fin_opp, int64_t N);
+/* of the last forward pass: o [B][A], s [B] (each may be NULL) */
+int oz_trainer_aux_outputs(oz_trainer* t, int B, float* own, float* score);
+/* step2 (optional): the last step's {L_own, L_sc}; epoch2 (optional): the sample-weighted float64 means of the last oz_trainer_fit_epoch /
+ * _replay call, accumulated on the device in step order like its three losses */
+int oz_trainer_get_aux_losses(oz_trainer* t, float* step2, double* epoch2);
+/* diagnostics: the last step's gradients wrt the two pre-activations, the loss weights included (dopre [B][A], dspre [B]); df2_before
+ * (optional, [B][512]): the gradient wrt f2 as the policy and value heads left it, before the auxiliary term was added -- needs
+ * oz_trainer_set_capture and a weight on (OZ_ERR_STATE otherwise); oz_trainer_get_dgrad(5) then shows the sum */
+int oz_trainer_get_aux_head_grads(oz_trainer* t, int B, float* dopre, float* dspre, float* df2_before);
+
 /* ------------------------------------------------------------------ replay buffer (opt-in; without it every result, record and file is unchanged)
  * Finished training examples RESIDENT on the device, between the self-play engines that produce them and the trainer that consumes them:
  * the replacement, for callers that ask for it, of the host's list of example tuples (main.py:21-53 CircularArray, training.py:58-72).
@@ -1527,6 +1570,19 @@ int oz_replay_read(oz_replay* r, int64_t first_slot, int64_t count, uint64_t* ow
 int oz_trainer_fit_epoch_replay(oz_trainer* t, oz_replay* r, const int32_t* order, int64_t count, int batch, float* losses3);
 /* oz_trainer_evaluate_dataset with the replay buffer's slots as the data set (order[i] in [0, held)); locks the trainer, then the buffer */
 int oz_trainer_evaluate_replay(oz_trainer* t, oz_replay* r, const int32_t* order, int64_t count, int batch, double* out);
+/* A buffer that also keeps every slot's FINAL PAIR for the trainer's auxiliary heads ("auxiliary heads" above): two more uint64 per slot,
+ * fin_own[s], fin_opp[s] = oz_aux_target of the example's record under the example's symmetry (0 / 0: no auxiliary target).  Every append
+ * fills them: the record appends (plain, with value targets, weighted) through AUX instantiations of the two append kernels -- the same
+ * ballots as the boards, lane t stores example t's pair, no atomics -- and the example appends through the _aux entry points below; the
+ * entry points without the pair write zeros into such a buffer.  own / opp / pi / z of a slot are what a plain buffer holds for the same
+ * appends.  The _aux example entry points on a plain buffer ignore the pair; oz_replay_read_aux on one is OZ_ERR_STATE. */
+int oz_replay_create_aux(oz_replay** out, int n, int64_t capacity);
+int oz_replay_has_aux(oz_replay* r, int* aux);
+int oz_replay_append_examples_aux(oz_replay* r, const uint64_t* own, const uint64_t* opp, const float* pi, const float* z, const uint64_t* fin_own,
+                                  const uint64_t* fin_opp, int64_t count);
+int oz_replay_restore_aux(oz_replay* r, const uint64_t* own, const uint64_t* opp, const float* pi, const float* z, const uint64_t* fin_own,
+                          const uint64_t* fin_opp, int64_t count, int64_t total);
+int oz_replay_read_aux(oz_replay* r, int64_t first_slot, int64_t count, uint64_t* fin_own, uint64_t* fin_opp);
 
 /* ------------------------------------------------------------------ diagnostics
  * device arithmetic behind the PUCT / backup formulas (MCTS/__init__.py:68,168-170), for bit-exact

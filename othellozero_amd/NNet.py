@@ -51,7 +51,7 @@ class NNetWrapper(_NetHandle):
 
     def __init__(self, board_size=(8, 8), batch_size=32, epochs=10, num_channels_1=512, num_channels_2=256,
                  lr=0.001, dropout=0.3, network=NeuralNets.ONN, max_batch=1, seed=0, weights=None, precision="f32", train_precision=None,
-                 policy_loss="rows", optimizer=None):
+                 policy_loss="rows", optimizer=None, aux_heads=None):
         super().__init__()
         self._model_index = NNetWrapper._models_built
         NNetWrapper._models_built += 1
@@ -92,6 +92,11 @@ class NNetWrapper(_NetHandle):
             unknown = set(self.optimizer) - set(OPTIMIZER_KEYS) - {"use_average"}
             assert not unknown, f"optimizer: unknown option(s) {sorted(unknown)}"
             assert not self.optimizer.get("use_average") or self.optimizer.get("average_decay", 0) > 0, "use_average needs average_decay in (0, 1)"
+        # aux_heads: None or dict(ownership=w, score=w) -- train() then also trains an ownership and a score head on the games' final boards
+        # (Trainer(aux_heads=...): fed by a ReplayBuffer(aux=True)).  The four arrays live with the trainer and in checkpoints; the inference
+        # network, predict and the search never see them
+        self.aux_heads = dict(aux_heads) if _lib.check_aux_heads(aux_heads) is not None else None
+        self._aux_weights = None                      # the heads' four arrays as the last fit / load_checkpoint left them (None: the trainer's fresh ones)
         self._weights_version = 0                     # counts set_weights / init_random: train() re-seeds its trainer when somebody else set the weights
         self._exported_version = None                 # the version train() itself left behind
         self.requested_precision = precision          # what the caller asked for: a refused f16x2 commit falls back for THAT set of weights only
@@ -207,6 +212,9 @@ class NNetWrapper(_NetHandle):
         held-out examples evaluated in inference mode after every epoch, History.history gains the val_* lists (trainer.fit / fit_replay)."""
         from . import trainer as T
         from .replay import ReplayBuffer
+        if getattr(self, "aux_heads", None) and allreduce is not None:
+            raise ValueError("a network with aux_heads does not train data-parallel: the all-reduce's gradient arena is sized for the forty arrays "
+                             "and the host example tuples carry no final pairs (train from a ReplayBuffer(aux=True), single-process)")
         replay = examples if isinstance(examples, ReplayBuffer) else None
         if replay is not None:
             # a device-resident replay buffer in place of the tuple list: the fit reads its slots in place (trainer.fit_replay)
@@ -259,6 +267,8 @@ class NNetWrapper(_NetHandle):
     def _sync_trainer(self, seed, allreduce, only_if_changed=False):
         """the trainer of train() / evaluate(): created at the first use, then given the network's weights where they are not its own"""
         from . import trainer as T
+        if getattr(self, "aux_heads", None) and allreduce is not None:
+            raise ValueError("a network with aux_heads does not train data-parallel (its gradient arena is the library's own)")
         if getattr(self, "_trainer", None) is None:
             assert self.num_channels % 128 == 0, "the training kernels need num_channels % 128 == 0"
             # a GradientAllReduce owns the gradient arena (a torch tensor RCCL can reduce in place): the library writes into it
@@ -267,7 +277,9 @@ class NNetWrapper(_NetHandle):
                                       seed=self._model_index if seed is None else seed,
                                       external_grads_ptr=getattr(allreduce, "ptr", None),
                                       precision=self._train_arithmetic(), policy_loss=self.policy_loss,
-                                      optimizer={k: v for k, v in (self.optimizer or {}).items() if k != "use_average"})
+                                      optimizer={k: v for k, v in (self.optimizer or {}).items() if k != "use_average"},
+                                      aux_heads=self.aux_heads)
+            self._push_aux_weights()
             self._trainer_arena = getattr(allreduce, "ptr", None)
             self._fit_calls = 0
             self._exported_version = None
@@ -287,11 +299,41 @@ class NNetWrapper(_NetHandle):
                 if i % 6 in (4, 5):
                     _lib.check(_lib.load().oz_trainer_set_weight(self._trainer._h, i, _lib.p_f32(mine[i]), mine[i].size))
 
+    def _push_aux_weights(self):
+        """the auxiliary heads' arrays a checkpoint brought go to the trainer, if there is one (else they wait for it)"""
+        if self.aux_heads and self._aux_weights is not None and getattr(self, "_trainer", None) is not None:
+            for i, a in zip(range(40, 44), self._aux_weights):
+                a = np.ascontiguousarray(a, dtype=np.float32)
+                _lib.check(_lib.load().oz_trainer_set_weight(self._trainer._h, i, _lib.p_f32(a), a.size))
+
+    def set_aux_heads(self, aux_heads):
+        """switch the auxiliary heads on (or change their weights) before the first train() / evaluate(): the trainer is created with them"""
+        new = dict(aux_heads) if _lib.check_aux_heads(aux_heads) is not None else None
+        if _lib.check_aux_heads(new) != _lib.check_aux_heads(self.aux_heads) and getattr(self, "_trainer", None) is not None:
+            raise ValueError("aux_heads: this network's trainer exists already (the heads are switched on before the first step); create the "
+                             "network with NNetWrapper(..., aux_heads=...)")
+        self.aux_heads = new
+
+    def aux_weights(self):
+        """the four arrays of the auxiliary heads (Wown (512, n*n), bown, Wsc (512, 1), bsc): always the trainer's RAW iterate, with
+        use_average too -- the trainer's own (created as train() creates it, if need be), or before there is one what the last fit, a copy() or
+        a loaded checkpoint left; checkpoints store these.  None without aux_heads"""
+        if not self.aux_heads:
+            return None
+        if getattr(self, "_trainer", None) is None and self._aux_weights is not None:      # (a copy(), a loaded checkpoint: no trainer needed to know them)
+            return [np.array(a, dtype=np.float32) for a in self._aux_weights]
+        self._sync_trainer(None, None, only_if_changed=True)
+        return self._trainer.get_weights()[40:]
+
     def _finish_fit(self, hist, allreduce):
         """the end of train(): the trained weights go to the network"""
         self._fit_calls += 1
         use_average = bool(self.optimizer and self.optimizer.get("use_average"))
         weights = self._trainer.get_weights(average=use_average)
+        if self.aux_heads:                              # the auxiliary heads stay with the trainer; a copy() of this network starts its own from them:
+            # always the RAW iterate, what aux_weights() reports (use_average concerns the network that plays, which has no such heads)
+            self._aux_weights = self._trainer.get_weights()[40:] if use_average else weights[40:]
+        weights = weights[:40]
         if allreduce is not None:                       # BN moving statistics are per replica: average them
             from .distributed import average_moving_statistics
             weights = average_moving_statistics(weights, getattr(allreduce, "group", None))
@@ -317,21 +359,39 @@ class NNetWrapper(_NetHandle):
     # NumPy archive of the same 40 arrays instead (an extension of this build).
     def save_checkpoint(self, filepath):
         """model.save_weights(filepath, save_format='h5')"""
+        aux = self.aux_weights()          # with aux_heads: two more Dense layers, `ownership` and `score` (arrays 40 .. 43)
         if filepath.endswith(".npz"):
-            np.savez(filepath, *self.get_weights())
+            np.savez(filepath, *(self.get_weights() + (aux or [])))
             return
-        layers = keras_h5.keras_layer_table(self.get_weights(), self._model_index, self.network_type.name)
+        layers = keras_h5.keras_layer_table(self.get_weights(), self._model_index, self.network_type.name, aux=aux)
         keras_h5.save_keras_weights(filepath, layers)
+
+    def _load_aux(self, arrays):
+        """the auxiliary heads' four arrays of a checkpoint: restored into a network with aux_heads, ignored by any other"""
+        if not self.aux_heads:
+            return
+        from .trainer import aux_shapes
+        for i, (a, shp) in enumerate(zip(arrays, aux_shapes(self.board_size_x))):
+            if tuple(np.shape(a)) != tuple(shp):
+                raise ValueError(f"weight {40 + i} of the file has shape {tuple(np.shape(a))}, the auxiliary heads expect {tuple(shp)}")
+        self._aux_weights = [np.array(a, dtype=np.float32) for a in arrays]
+        self._push_aux_weights()
 
     def load_checkpoint(self, filepath):
         """model.load_weights(filepath): layers with weights are matched BY ORDER, as Keras does; a file whose
         weighted-layer count or shapes differ from this network raises ValueError."""
         if filepath.endswith(".npz"):
             with np.load(filepath) as z:
-                self.set_weights([z[f"arr_{i}"] for i in range(len(z.files))])
+                arrays = [z[f"arr_{i}"] for i in range(len(z.files))]
+            self.set_weights(arrays[:40] if len(arrays) == 44 else arrays)
+            if len(arrays) == 44:
+                self._load_aux(arrays[40:])
             return
         assert filepath.endswith('.h5'), 'Expecting a file with .h5 as extension'
         layers = [(name, ws) for name, ws in keras_h5.load_keras_weights(filepath) if ws]
+        aux = None
+        if len(layers) == 16 and tuple(name for name, _ in layers[14:]) == keras_h5.AUX_LAYERS:      # a file with the auxiliary heads' two layers
+            aux, layers = keras_h5.flat_weights(layers[14:]), layers[:14]
         if len(layers) != 14:
             raise ValueError(f"You are trying to load a weight file containing {len(layers)} layers into a model with 14 layers.")
         flat = keras_h5.flat_weights(layers)
@@ -342,12 +402,15 @@ class NNetWrapper(_NetHandle):
             if tuple(a.shape) != tuple(shp):
                 raise ValueError(f"weight {i} of the file has shape {tuple(a.shape)}, this network expects {tuple(shp)}")
         self.set_weights(flat)
+        if aux is not None:
+            self._load_aux(aux)
 
     def copy(self):
         net = NNetWrapper((self.board_size_x, self.board_size_y), network=self.network_type,
                           num_channels_1=self.num_channels, max_batch=self.max_batch, weights=self.get_weights(),
                           precision=self.precision, train_precision=self.train_precision, policy_loss=self.policy_loss,
-                          optimizer=self.optimizer)
+                          optimizer=self.optimizer, aux_heads=self.aux_heads)
+        net._aux_weights = self._aux_weights
         mode, seed = self.eval_symmetry()
         if mode != "off" or seed:
             net.set_eval_symmetry(mode, seed)          # the evaluation symmetry is part of the network

@@ -366,6 +366,20 @@ SIGNATURES = {
     "oz_replay_read": [_vp, C.c_int64, C.c_int64, _u64p, _u64p, _f32p, _f32p],
     "oz_trainer_fit_epoch_replay": [_vp, _vp, _i32p, C.c_int64, C.c_int, _f32p],
     "oz_trainer_evaluate_replay": [_vp, _vp, _i32p, C.c_int64, C.c_int, _f64p],
+    # auxiliary heads
+    "oz_aux_targets": [_vp, C.c_int64, _u64p, _u64p],
+    "oz_trainer_arena_size_aux": [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)],
+    "oz_trainer_set_aux_heads": [_vp, C.c_float, C.c_float],
+    "oz_trainer_get_aux_heads": [_vp, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float)],
+    "oz_trainer_forward_backward_aux": [_vp, _u64p, _u64p, _f32p, _f32p, _u64p, _u64p, C.c_int, _f32p],
+    "oz_trainer_set_dataset_aux": [_vp, _u64p, _u64p, _f32p, _f32p, _u64p, _u64p, C.c_int64],
+    "oz_trainer_aux_outputs": [_vp, C.c_int, _f32p, _f32p],
+    "oz_trainer_get_aux_losses": [_vp, _f32p, _f64p],
+    "oz_trainer_get_aux_head_grads": [_vp, C.c_int, _f32p, _f32p, _f32p],
+    "oz_replay_create_aux": [C.POINTER(_vp), C.c_int, C.c_int64], "oz_replay_has_aux": [_vp, C.POINTER(C.c_int)],
+    "oz_replay_append_examples_aux": [_vp, _u64p, _u64p, _f32p, _f32p, _u64p, _u64p, C.c_int64],
+    "oz_replay_restore_aux": [_vp, _u64p, _u64p, _f32p, _f32p, _u64p, _u64p, C.c_int64, C.c_int64],
+    "oz_replay_read_aux": [_vp, C.c_int64, C.c_int64, _u64p, _u64p],
 }
 
 _LIB = None
@@ -950,6 +964,51 @@ def check_value_target(value_target, alias_final_boards=False):
         raise ValueError("value_target needs alias_final_boards=False: a search value belongs to the position of its move, not to the game's "
                          "final position")
     return VALUE_TARGET_MODES[value_target[0]], param
+
+
+def check_aux_heads(aux_heads, what="aux_heads"):
+    """aux_heads = None / False (off) or dict(ownership=w, score=w): the loss weights of the trainer's auxiliary heads (include/othellozero_amd.h,
+    "auxiliary heads"), finite and >= 0, a missing key 0.  -> None or (w_own, w_score); ValueError for anything else.  The one check of the
+    option: Trainer, NNetWrapper and loop.training call it; no GPU needed"""
+    if aux_heads is None or aux_heads is False:
+        return None
+    bad = f"{what} must be None or dict(ownership=weight, score=weight) with finite weights >= 0, got {aux_heads!r}"
+    if not isinstance(aux_heads, dict) or set(aux_heads) - {"ownership", "score"}:
+        raise ValueError(bad)
+    w = []
+    for key in ("ownership", "score"):
+        x = aux_heads.get(key, 0.0)
+        if isinstance(x, (bool, str, bytes)):
+            raise ValueError(bad)
+        try:
+            x = float(x)
+        except (TypeError, ValueError):
+            raise ValueError(bad) from None
+        if not (x >= 0.0 and x < float("inf")):
+            raise ValueError(bad)
+        w.append(x)
+    return tuple(w)
+
+
+def check_aux_heads_loop(aux_heads, replay="host", distributed=False, alias_final_boards=False, in_channels=2):
+    """training(aux_heads=...) -> None (off) or the dict to hand to the network.  The final pairs travel in the slots of the device replay buffer
+    alone: replay="host" and distributed=True are refused (the host example tuples and the pooled rows do not carry them).  With
+    alias_final_boards=True a two-plane network's examples SHOW the final board (the reference's aliased view): the ownership target would be
+    the input itself, so that is refused too; a one-plane network's examples are the positions at the move whatever alias_final_boards says
+    (examples_from_records), and pass."""
+    w = check_aux_heads(aux_heads)
+    if w is None:
+        return None
+    if distributed:
+        raise ValueError("aux_heads is not offered with distributed=True: the pooled rows of the all-gather do not carry the final pairs, and the "
+                         "device replay buffer that does is single-process")
+    if replay != "device":
+        raise ValueError("aux_heads needs replay='device': the final pairs are slots of the device replay buffer (ReplayBuffer(aux=True)); the "
+                         "host example tuples do not carry them")
+    if alias_final_boards and in_channels == 2:
+        raise ValueError("aux_heads needs alias_final_boards=False for a two-plane network: the aliased view shows every example as the game's "
+                         "final board, which is the ownership target itself")
+    return dict(ownership=w[0], score=w[1])
 
 
 def check_surprise_frac(frac, what="surprise_weight"):

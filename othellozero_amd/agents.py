@@ -406,6 +406,16 @@ def rules_sym_boards(boards, n, t):
     return out.reshape(b.shape)
 
 
+def rules_aux_targets(records):
+    """oz_aux_targets on the host (no GPU needed): (fin_own, fin_opp) uint64 (R,) of move records (_lib.RECORD_DTYPE) -- the game's final board
+    from the mover's side, the target of the trainer's auxiliary heads; 0 / 0 ("no auxiliary target") for a record of an adjudicated game and
+    for a fast record of a playout cap.  The function the replay buffer's append kernels evaluate."""
+    rec = np.ascontiguousarray(records, dtype=_lib.RECORD_DTYPE).ravel()
+    fo, fp = np.zeros(rec.size, np.uint64), np.zeros(rec.size, np.uint64)
+    _lib.check(_lib.load().oz_aux_targets(rec.ctypes.data_as(C.c_void_p), rec.size, _lib.p_u64(fo), _lib.p_u64(fp)))
+    return fo, fp
+
+
 def rules_random_openings(n, count, plies, seed, first_opening_id=0):
     """oz_rules_random_openings: the random openings first_opening_id .. first_opening_id + count - 1 of (plies, seed) on the n x n board, what
     arena_batch(openings=(plies, seed), first_opening_id=...) lets its games start with.  -> dict(black, white uint64 (count,) = the position

@@ -683,6 +683,21 @@ OZ_HD uint64_t oz_sym_board(int t, int n, uint64_t b) {
     return out;
 }
 
+// ---------------------------------------------------------------- auxiliary targets (include/othellozero_amd.h, "auxiliary heads")
+// The final board of a record's game from the mover's side: (final_black, final_white) for BLACK to move, swapped for WHITE.  Both words are 0
+// ("no auxiliary target") for a record of an adjudicated game (pad[1] == 1: the board at the stop is no final board) and for the fast record
+// of a playout cap (pad[0] == 1).  A real final board is never empty, so fin_own | fin_opp == 0 IS the mask.  The one definition the append
+// kernels (oz_replay.hip) and the host's oz_aux_targets share; Rec = oz_record.
+template <typename Rec> OZ_HD void oz_aux_target(const Rec& rec, uint64_t& fin_own, uint64_t& fin_opp) {
+    const bool none = rec.pad[0] == 1 || rec.pad[1] == 1, black = rec.player == 1;
+    fin_own = none ? 0 : black ? rec.final_black : rec.final_white;
+    fin_opp = none ? 0 : black ? rec.final_white : rec.final_black;
+}
+// the ownership target of square sq = row*8+col: +1 / -1 / 0 for a square of fin_own / of fin_opp / empty
+OZ_HD float oz_aux_own_target(uint64_t fin_own, uint64_t fin_opp, int sq) { return (float)((fin_own >> sq) & 1) - (float)((fin_opp >> sq) & 1); }
+// the score target: the final disc margin for the mover over the A = n*n squares (both counts are exact in float32, one division)
+OZ_HD float oz_aux_score_target(uint64_t fin_own, uint64_t fin_opp, int A) { return (float)(oz_popc(fin_own) - oz_popc(fin_opp)) / (float)A; }
+
 // N ** (1 / T) of get_policy_action_probabilities (othelo_mcts.py:59-60) for a visit count.  k = 1 / T where that is an integer (else 0):
 // the product of k factors is exact while it stays <= 2^53 (every partial product is then an integer below it), so it equals the
 // correctly rounded power the host computes; beyond that, and for any other exponent, the device's pow.

@@ -237,6 +237,7 @@ struct oz_replay {
     int64_t capacity = 0, total = 0;
     uint64_t *own = nullptr, *opp = nullptr;
     float *pi = nullptr, *z = nullptr;
+    uint64_t *fo = nullptr, *fp = nullptr;   // oz_replay_create_aux: every slot's final pair for the trainer's auxiliary heads (oz_aux_target), else NULL
     hipStream_t s = nullptr;
     // staging of an append, grown on demand and kept: the records (and visit-count rows) as the engine / the host holds them, and the
     // permutation that puts them in (game_id, ply) order

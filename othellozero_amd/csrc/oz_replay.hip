@@ -21,12 +21,14 @@
 // own / opp / z of example t are written by lane t: one 8-lane store each per record.  z = the record's z, or with zt (the records' value
 // targets, indexed like recs) the record's float32 target.
 // No atomics, no scratch, fixed order.
-template <int N, bool VISITS, bool POLICY = false>
+// AUX (a buffer of oz_replay_create_aux): the record's final pair (oz_aux_target: the final board from the mover's side, 0 / 0 without one) goes
+// through the same ballots as the boards, and lane t stores example t's pair into fo / fp.  The other instantiations never touch fo / fp.
+template <int N, bool VISITS, bool POLICY = false, bool AUX = false>
 __global__ __launch_bounds__(64) void k_replay_append(const oz_record* __restrict__ recs, const int32_t* __restrict__ counts,
                                                       const int32_t* __restrict__ perm, int alias_final, double inv, int k, long long base,
                                                       long long skip, long long capacity, uint64_t* __restrict__ own,
                                                       uint64_t* __restrict__ opp, float* __restrict__ pi, float* __restrict__ z,
-                                                      const float* __restrict__ zt) {
+                                                      const float* __restrict__ zt, uint64_t* __restrict__ fo, uint64_t* __restrict__ fp) {
     constexpr int N2 = N * N;
     __shared__ double arr[64];
     __shared__ double divisor;
@@ -52,13 +54,18 @@ __global__ __launch_bounds__(64) void k_replay_append(const oz_record* __restric
     }
     if constexpr (POLICY) q32 = is_cell ? __int_as_float(counts[(long long)rix * 64 + rn * 8 + cn]) : 0.f;
     const int action = (rec.action >> 3) * N + (rec.action & 7);
-    uint64_t my_own = 0, my_opp = 0;
+    uint64_t my_own = 0, my_opp = 0, fin_o = 0, fin_p = 0, my_fo = 0, my_fp = 0;
+    if constexpr (AUX) oz_aux_target(rec, fin_o, fin_p);
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
         const int s8 = on_board ? oz_sym_src(t, N, r8, c8) : 0;
         const int sq = (s8 / N) * 8 + s8 % N;
         const uint64_t bo = __ballot(on_board && ((b >> sq) & 1)), bw = __ballot(on_board && ((w >> sq) & 1));
         if (lane == t) { my_own = bo; my_opp = bw; }
+        if constexpr (AUX) {
+            const uint64_t ao = __ballot(on_board && ((fin_o >> sq) & 1)), aw = __ballot(on_board && ((fin_p >> sq) & 1));
+            if (lane == t) { my_fo = ao; my_fp = aw; }
+        }
         const int src = is_cell ? oz_sym_src(t, N, rn, cn) : 0;
         float p;
         if constexpr (VISITS || POLICY) p = __shfl(q32, src);
@@ -70,6 +77,7 @@ __global__ __launch_bounds__(64) void k_replay_append(const oz_record* __restric
     if (lane < 8 && e >= skip) {
         const long long slot = (base + e) % capacity;
         own[slot] = my_own; opp[slot] = my_opp; z[slot] = zt ? zt[rix] : (float)rec.z;
+        if constexpr (AUX) { fo[slot] = my_fo; fp[slot] = my_fp; }
     }
 }
 
@@ -77,14 +85,16 @@ __global__ __launch_bounds__(64) void k_replay_append(const oz_record* __restric
 // example k of them is symmetry (first_sym[rix] + k) & 7 and has the running index base + off[i] + k, off = the exclusive prefix sum of the
 // copy counts over the permutation.  The eight boards are made once, as above, and kept in LDS; the row of example k is computed for its
 // symmetry (copies beyond 8 repeat symmetries).  skip / capacity as above; the kept examples of a launch are at most `capacity` consecutive
-// running indices.  A record with no copy writes nothing.  One wavefront per record, no atomics, no scratch, fixed order.
-template <int N, bool VISITS, bool POLICY = false>
+// running indices.  A record with no copy writes nothing.  One wavefront per record, no atomics, no scratch, fixed order.  AUX: as above, the
+// eight final pairs kept in LDS beside the boards.
+template <int N, bool VISITS, bool POLICY = false, bool AUX = false>
 __global__ __launch_bounds__(64) void k_replay_append_w(const oz_record* __restrict__ recs, const int32_t* __restrict__ counts,
                                                         const int32_t* __restrict__ perm, int alias_final, double inv, int k, long long base,
                                                         long long skip, long long capacity, uint64_t* __restrict__ own,
                                                         uint64_t* __restrict__ opp, float* __restrict__ pi, float* __restrict__ z,
                                                         const float* __restrict__ zt, const int32_t* __restrict__ copies,
-                                                        const uint8_t* __restrict__ first_sym, const long long* __restrict__ off) {
+                                                        const uint8_t* __restrict__ first_sym, const long long* __restrict__ off,
+                                                        uint64_t* __restrict__ fo, uint64_t* __restrict__ fp) {
     constexpr int N2 = N * N;
     __shared__ double arr[64];
     __shared__ double divisor;
@@ -114,12 +124,23 @@ __global__ __launch_bounds__(64) void k_replay_append_w(const oz_record* __restr
     }
     if constexpr (POLICY) q32 = is_cell ? __int_as_float(counts[(long long)rix * 64 + rn * 8 + cn]) : 0.f;
     const int action = (rec.action >> 3) * N + (rec.action & 7);
+    uint64_t* s_fin = nullptr;                               // AUX: [0 .. 7] fin_own, [8 .. 15] fin_opp of the eight symmetries
+    uint64_t fin_o = 0, fin_p = 0;
+    if constexpr (AUX) {
+        __shared__ uint64_t s_fin_buf[16];
+        s_fin = s_fin_buf;
+        oz_aux_target(rec, fin_o, fin_p);
+    }
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
         const int s8 = on_board ? oz_sym_src(t, N, r8, c8) : 0;
         const int sq = (s8 / N) * 8 + s8 % N;
         const uint64_t bo = __ballot(on_board && ((b >> sq) & 1)), bw = __ballot(on_board && ((w >> sq) & 1));
         if (lane == t) { s_own[t] = bo; s_opp[t] = bw; }
+        if constexpr (AUX) {
+            const uint64_t ao = __ballot(on_board && ((fin_o >> sq) & 1)), aw = __ballot(on_board && ((fin_p >> sq) & 1));
+            if (lane == t) { s_fin[t] = ao; s_fin[8 + t] = aw; }
+        }
     }
     __syncthreads();
     for (int kk = 0; kk < c; ++kk) {
@@ -138,6 +159,7 @@ __global__ __launch_bounds__(64) void k_replay_append_w(const oz_record* __restr
             const int t = (t0 + kk) & 7;
             const long long slot = (base + e) % capacity;
             own[slot] = s_own[t]; opp[slot] = s_opp[t]; z[slot] = zv;
+            if constexpr (AUX) { fo[slot] = s_fin[t]; fp[slot] = s_fin[8 + t]; }
         }
     }
 }
@@ -145,7 +167,7 @@ __global__ __launch_bounds__(64) void k_replay_append_w(const oz_record* __restr
 // ---------------------------------------------------------------- the object
 #define R_LOCK(r) std::lock_guard<std::mutex> rlock__((r)->mu)
 
-OZ_API int oz_replay_create(oz_replay** out, int n, int64_t capacity) {
+static int replay_create(oz_replay** out, int n, int64_t capacity, bool aux) {
     OZ_REQUIRE(out, "oz_replay_create: null argument");
     OZ_REQUIRE(n == 4 || n == 6 || n == 8, "oz_replay_create: board size must be 4, 6 or 8 (got %d)", n);
     OZ_REQUIRE(capacity >= 1 && capacity < (1ll << 31), "oz_replay_create: capacity %lld outside [1, 2^31 - 1] examples", (long long)capacity);
@@ -163,7 +185,18 @@ OZ_API int oz_replay_create(oz_replay** out, int n, int64_t capacity) {
     if ((e = hipMalloc((void**)&r->opp, sizeof(uint64_t) * capacity)) != hipSuccess) return fail(e);
     if ((e = hipMalloc((void**)&r->pi, sizeof(float) * capacity * n * n)) != hipSuccess) return fail(e);
     if ((e = hipMalloc((void**)&r->z, sizeof(float) * capacity)) != hipSuccess) return fail(e);
+    if (aux) {
+        if ((e = hipMalloc((void**)&r->fo, sizeof(uint64_t) * capacity)) != hipSuccess) return fail(e);
+        if ((e = hipMalloc((void**)&r->fp, sizeof(uint64_t) * capacity)) != hipSuccess) return fail(e);
+    }
     *out = r;
+    return OZ_OK;
+}
+OZ_API int oz_replay_create(oz_replay** out, int n, int64_t capacity) { return replay_create(out, n, capacity, false); }
+OZ_API int oz_replay_create_aux(oz_replay** out, int n, int64_t capacity) { return replay_create(out, n, capacity, true); }
+OZ_API int oz_replay_has_aux(oz_replay* r, int* aux) {
+    OZ_REQUIRE(r && aux, "oz_replay_has_aux: null argument");
+    *aux = r->fo ? 1 : 0;
     return OZ_OK;
 }
 
@@ -171,7 +204,7 @@ OZ_API int oz_replay_destroy(oz_replay* r) {
     if (!r) return OZ_OK;
     hipSetDevice(r->device);
     if (r->s) hipStreamSynchronize(r->s);
-    for (void* q : {(void*)r->own, (void*)r->opp, (void*)r->pi, (void*)r->z, (void*)r->st_rec, (void*)r->st_cnt, (void*)r->st_perm, (void*)r->st_tgt, (void*)r->st_cpy, (void*)r->st_sym, (void*)r->st_off}) if (q) hipFree(q);
+    for (void* q : {(void*)r->own, (void*)r->opp, (void*)r->pi, (void*)r->z, (void*)r->fo, (void*)r->fp, (void*)r->st_rec, (void*)r->st_cnt, (void*)r->st_perm, (void*)r->st_tgt, (void*)r->st_cpy, (void*)r->st_sym, (void*)r->st_off}) if (q) hipFree(q);
     if (r->s) hipStreamDestroy(r->s);
     delete r;
     return OZ_OK;
@@ -238,30 +271,30 @@ static int replay_check_target(const char* who, int alias_final, int target, dou
     return OZ_OK;
 }
 
-template <int N> static void replay_launch(oz_replay* r, int64_t count, int alias_final, int target, double inv, int k, long long skip, const float* zt) {
+template <int N, bool AUX> static void replay_launch(oz_replay* r, int64_t count, int alias_final, int target, double inv, int k, long long skip, const float* zt) {
     const dim3 grid((unsigned)count), block(64);
     if (target == OZ_REPLAY_TARGET_POLICY)
-        hipLaunchKernelGGL((k_replay_append<N, false, true>), grid, block, 0, r->s, r->st_rec, r->st_cnt, r->st_perm, alias_final, inv, k, (long long)r->total, skip,
-                           (long long)r->capacity, r->own, r->opp, r->pi, r->z, zt);
+        hipLaunchKernelGGL((k_replay_append<N, false, true, AUX>), grid, block, 0, r->s, r->st_rec, r->st_cnt, r->st_perm, alias_final, inv, k, (long long)r->total, skip,
+                           (long long)r->capacity, r->own, r->opp, r->pi, r->z, zt, r->fo, r->fp);
     else if (target == OZ_REPLAY_TARGET_VISITS)
-        hipLaunchKernelGGL((k_replay_append<N, true>), grid, block, 0, r->s, r->st_rec, r->st_cnt, r->st_perm, alias_final, inv, k, (long long)r->total, skip,
-                           (long long)r->capacity, r->own, r->opp, r->pi, r->z, zt);
+        hipLaunchKernelGGL((k_replay_append<N, true, false, AUX>), grid, block, 0, r->s, r->st_rec, r->st_cnt, r->st_perm, alias_final, inv, k, (long long)r->total, skip,
+                           (long long)r->capacity, r->own, r->opp, r->pi, r->z, zt, r->fo, r->fp);
     else
-        hipLaunchKernelGGL((k_replay_append<N, false>), grid, block, 0, r->s, r->st_rec, (const int32_t*)nullptr, r->st_perm, alias_final, inv, k,
-                           (long long)r->total, skip, (long long)r->capacity, r->own, r->opp, r->pi, r->z, zt);
+        hipLaunchKernelGGL((k_replay_append<N, false, false, AUX>), grid, block, 0, r->s, r->st_rec, (const int32_t*)nullptr, r->st_perm, alias_final, inv, k,
+                           (long long)r->total, skip, (long long)r->capacity, r->own, r->opp, r->pi, r->z, zt, r->fo, r->fp);
 }
 
-template <int N> static void replay_launch_w(oz_replay* r, int64_t count, int alias_final, int target, double inv, int k, long long skip, const float* zt) {
+template <int N, bool AUX> static void replay_launch_w(oz_replay* r, int64_t count, int alias_final, int target, double inv, int k, long long skip, const float* zt) {
     const dim3 grid((unsigned)count), block(64);
     if (target == OZ_REPLAY_TARGET_POLICY)
-        hipLaunchKernelGGL((k_replay_append_w<N, false, true>), grid, block, 0, r->s, r->st_rec, r->st_cnt, r->st_perm, alias_final, inv, k, (long long)r->total, skip,
-                           (long long)r->capacity, r->own, r->opp, r->pi, r->z, zt, r->st_cpy, r->st_sym, r->st_off);
+        hipLaunchKernelGGL((k_replay_append_w<N, false, true, AUX>), grid, block, 0, r->s, r->st_rec, r->st_cnt, r->st_perm, alias_final, inv, k, (long long)r->total, skip,
+                           (long long)r->capacity, r->own, r->opp, r->pi, r->z, zt, r->st_cpy, r->st_sym, r->st_off, r->fo, r->fp);
     else if (target == OZ_REPLAY_TARGET_VISITS)
-        hipLaunchKernelGGL((k_replay_append_w<N, true>), grid, block, 0, r->s, r->st_rec, r->st_cnt, r->st_perm, alias_final, inv, k, (long long)r->total, skip,
-                           (long long)r->capacity, r->own, r->opp, r->pi, r->z, zt, r->st_cpy, r->st_sym, r->st_off);
+        hipLaunchKernelGGL((k_replay_append_w<N, true, false, AUX>), grid, block, 0, r->s, r->st_rec, r->st_cnt, r->st_perm, alias_final, inv, k, (long long)r->total, skip,
+                           (long long)r->capacity, r->own, r->opp, r->pi, r->z, zt, r->st_cpy, r->st_sym, r->st_off, r->fo, r->fp);
     else
-        hipLaunchKernelGGL((k_replay_append_w<N, false>), grid, block, 0, r->s, r->st_rec, (const int32_t*)nullptr, r->st_perm, alias_final, inv, k,
-                           (long long)r->total, skip, (long long)r->capacity, r->own, r->opp, r->pi, r->z, zt, r->st_cpy, r->st_sym, r->st_off);
+        hipLaunchKernelGGL((k_replay_append_w<N, false, false, AUX>), grid, block, 0, r->s, r->st_rec, (const int32_t*)nullptr, r->st_perm, alias_final, inv, k,
+                           (long long)r->total, skip, (long long)r->capacity, r->own, r->opp, r->pi, r->z, zt, r->st_cpy, r->st_sym, r->st_off, r->fo, r->fp);
 }
 
 // the staged records [first, first + count) of r->st_rec (host copy: h[0 .. count)) -> 8 examples each, in ascending (game_id, ply).  The fast
@@ -295,17 +328,23 @@ static int replay_append_staged(oz_replay* r, const oz_record* h, int64_t first,
     hipError_t e = hipMemcpyAsync(r->st_perm, perm.data(), sizeof(int32_t) * count, hipMemcpyHostToDevice, r->s);
     if (e == hipSuccess && hc) e = hipMemcpyAsync(r->st_off, off.data(), sizeof(long long) * count, hipMemcpyHostToDevice, r->s);
     if (e == hipSuccess && hc) {
-        switch (r->n) {
-        case 4: replay_launch_w<4>(r, count, alias_final, target, inv, k, skip, zt); break;
-        case 6: replay_launch_w<6>(r, count, alias_final, target, inv, k, skip, zt); break;
-        default: replay_launch_w<8>(r, count, alias_final, target, inv, k, skip, zt);
+        switch (r->n * 2 + (r->fo ? 1 : 0)) {
+        case 8: replay_launch_w<4, false>(r, count, alias_final, target, inv, k, skip, zt); break;
+        case 9: replay_launch_w<4, true>(r, count, alias_final, target, inv, k, skip, zt); break;
+        case 12: replay_launch_w<6, false>(r, count, alias_final, target, inv, k, skip, zt); break;
+        case 13: replay_launch_w<6, true>(r, count, alias_final, target, inv, k, skip, zt); break;
+        case 16: replay_launch_w<8, false>(r, count, alias_final, target, inv, k, skip, zt); break;
+        default: replay_launch_w<8, true>(r, count, alias_final, target, inv, k, skip, zt);
         }
         e = hipGetLastError();
     } else if (e == hipSuccess) {
-        switch (r->n) {
-        case 4: replay_launch<4>(r, count, alias_final, target, inv, k, skip, zt); break;
-        case 6: replay_launch<6>(r, count, alias_final, target, inv, k, skip, zt); break;
-        default: replay_launch<8>(r, count, alias_final, target, inv, k, skip, zt);
+        switch (r->n * 2 + (r->fo ? 1 : 0)) {
+        case 8: replay_launch<4, false>(r, count, alias_final, target, inv, k, skip, zt); break;
+        case 9: replay_launch<4, true>(r, count, alias_final, target, inv, k, skip, zt); break;
+        case 12: replay_launch<6, false>(r, count, alias_final, target, inv, k, skip, zt); break;
+        case 13: replay_launch<6, true>(r, count, alias_final, target, inv, k, skip, zt); break;
+        case 16: replay_launch<8, false>(r, count, alias_final, target, inv, k, skip, zt); break;
+        default: replay_launch<8, true>(r, count, alias_final, target, inv, k, skip, zt);
         }
         e = hipGetLastError();
     }
@@ -425,7 +464,17 @@ static int replay_ring_upload(oz_replay* r, void* dst, const void* src, size_t w
     return OZ_OK;
 }
 
-static int replay_append_examples_locked(oz_replay* r, const uint64_t* own, const uint64_t* opp, const float* pi, const float* z, int64_t count) {
+// `count` rows of `width` zero bytes into the ring at running index `k0` (count <= capacity)
+static int replay_ring_zero(oz_replay* r, void* dst, size_t width, int64_t k0, int64_t count) {
+    const int64_t s0 = k0 % r->capacity, head = std::min(count, r->capacity - s0);
+    OZ_HIP(hipMemsetAsync((char*)dst + width * s0, 0, width * head, r->s));
+    if (count > head) OZ_HIP(hipMemsetAsync(dst, 0, width * (count - head), r->s));
+    return OZ_OK;
+}
+
+// fin_own / fin_opp: the examples' final pairs for a buffer that keeps them (NULL: zero pairs, "no auxiliary target"); a plain buffer ignores them
+static int replay_append_examples_locked(oz_replay* r, const uint64_t* own, const uint64_t* opp, const float* pi, const float* z, int64_t count,
+                                         const uint64_t* fin_own = nullptr, const uint64_t* fin_opp = nullptr) {
     OZ_HIP(hipSetDevice(r->device));
     const int64_t skip = count > r->capacity ? count - r->capacity : 0, kept = count - skip, k0 = r->total + skip;
     const size_t A = (size_t)r->n * r->n;
@@ -433,6 +482,13 @@ static int replay_append_examples_locked(oz_replay* r, const uint64_t* own, cons
     if (!rc) rc = replay_ring_upload(r, r->opp, opp + skip, sizeof(uint64_t), k0, kept);
     if (!rc) rc = replay_ring_upload(r, r->pi, pi + skip * A, sizeof(float) * A, k0, kept);
     if (!rc) rc = replay_ring_upload(r, r->z, z + skip, sizeof(float), k0, kept);
+    if (!rc && r->fo && fin_own) {
+        rc = replay_ring_upload(r, r->fo, fin_own + skip, sizeof(uint64_t), k0, kept);
+        if (!rc) rc = replay_ring_upload(r, r->fp, fin_opp + skip, sizeof(uint64_t), k0, kept);
+    } else if (!rc && r->fo) {
+        rc = replay_ring_zero(r, r->fo, sizeof(uint64_t), k0, kept);
+        if (!rc) rc = replay_ring_zero(r, r->fp, sizeof(uint64_t), k0, kept);
+    }
     hipError_t e = hipStreamSynchronize(r->s);   // the host arrays may go away, whatever happened
     if (rc) return rc;
     OZ_HIP(e);
@@ -449,7 +505,18 @@ OZ_API int oz_replay_append_examples(oz_replay* r, const uint64_t* own, const ui
     return replay_append_examples_locked(r, own, opp, pi, z, count);
 }
 
-OZ_API int oz_replay_restore(oz_replay* r, const uint64_t* own, const uint64_t* opp, const float* pi, const float* z, int64_t count, int64_t total) {
+OZ_API int oz_replay_append_examples_aux(oz_replay* r, const uint64_t* own, const uint64_t* opp, const float* pi, const float* z,
+                                         const uint64_t* fin_own, const uint64_t* fin_opp, int64_t count) {
+    OZ_REQUIRE(r, "oz_replay_append_examples_aux: null replay buffer");
+    OZ_REQUIRE(count >= 0, "oz_replay_append_examples_aux: count %lld", (long long)count);
+    if (count == 0) return OZ_OK;
+    OZ_REQUIRE(own && opp && pi && z && fin_own && fin_opp, "oz_replay_append_examples_aux: null argument");
+    R_LOCK(r);
+    return replay_append_examples_locked(r, own, opp, pi, z, count, fin_own, fin_opp);
+}
+
+static int replay_restore(oz_replay* r, const uint64_t* own, const uint64_t* opp, const float* pi, const float* z, const uint64_t* fin_own,
+                          const uint64_t* fin_opp, int64_t count, int64_t total) {
     OZ_REQUIRE(r, "oz_replay_restore: null replay buffer");
     R_LOCK(r);
     OZ_REQUIRE(total >= 0 && count == (total < r->capacity ? total : r->capacity),
@@ -458,8 +525,16 @@ OZ_API int oz_replay_restore(oz_replay* r, const uint64_t* own, const uint64_t* 
     OZ_REQUIRE(count == 0 || (own && opp && pi && z), "oz_replay_restore: null argument");
     r->total = total - count;
     if (count == 0) return OZ_OK;
-    if (int rc = replay_append_examples_locked(r, own, opp, pi, z, count)) { r->total = 0; return rc; }
+    if (int rc = replay_append_examples_locked(r, own, opp, pi, z, count, fin_own, fin_opp)) { r->total = 0; return rc; }
     return OZ_OK;
+}
+OZ_API int oz_replay_restore(oz_replay* r, const uint64_t* own, const uint64_t* opp, const float* pi, const float* z, int64_t count, int64_t total) {
+    return replay_restore(r, own, opp, pi, z, nullptr, nullptr, count, total);
+}
+OZ_API int oz_replay_restore_aux(oz_replay* r, const uint64_t* own, const uint64_t* opp, const float* pi, const float* z, const uint64_t* fin_own,
+                                 const uint64_t* fin_opp, int64_t count, int64_t total) {
+    OZ_REQUIRE(count == 0 || (fin_own && fin_opp), "oz_replay_restore_aux: null argument");
+    return replay_restore(r, own, opp, pi, z, fin_own, fin_opp, count, total);
 }
 
 OZ_API int oz_replay_read(oz_replay* r, int64_t first_slot, int64_t count, uint64_t* own, uint64_t* opp, float* pi, float* z) {
@@ -474,6 +549,21 @@ OZ_API int oz_replay_read(oz_replay* r, int64_t first_slot, int64_t count, uint6
     if (opp) OZ_HIP(hipMemcpyAsync(opp, r->opp + first_slot, sizeof(uint64_t) * count, hipMemcpyDeviceToHost, r->s));
     if (pi) OZ_HIP(hipMemcpyAsync(pi, r->pi + first_slot * A, sizeof(float) * A * count, hipMemcpyDeviceToHost, r->s));
     if (z) OZ_HIP(hipMemcpyAsync(z, r->z + first_slot, sizeof(float) * count, hipMemcpyDeviceToHost, r->s));
+    OZ_HIP(hipStreamSynchronize(r->s));
+    return OZ_OK;
+}
+
+// the final pairs of `count` slots from `first_slot` on, of a buffer that keeps them (oz_replay_create_aux; OZ_ERR_STATE otherwise)
+OZ_API int oz_replay_read_aux(oz_replay* r, int64_t first_slot, int64_t count, uint64_t* fin_own, uint64_t* fin_opp) {
+    OZ_REQUIRE(r, "oz_replay_read_aux: null replay buffer");
+    R_LOCK(r);
+    if (!r->fo) { oz_set_error("oz_replay_read_aux: this replay buffer keeps no final pairs (oz_replay_create_aux)"); return OZ_ERR_STATE; }
+    OZ_REQUIRE(first_slot >= 0 && count >= 0 && first_slot + count <= r->held(), "oz_replay_read_aux: slots [%lld, %lld) but the buffer holds %lld examples",
+               (long long)first_slot, (long long)(first_slot + count), (long long)r->held());
+    if (count == 0) return OZ_OK;
+    OZ_HIP(hipSetDevice(r->device));
+    if (fin_own) OZ_HIP(hipMemcpyAsync(fin_own, r->fo + first_slot, sizeof(uint64_t) * count, hipMemcpyDeviceToHost, r->s));
+    if (fin_opp) OZ_HIP(hipMemcpyAsync(fin_opp, r->fp + first_slot, sizeof(uint64_t) * count, hipMemcpyDeviceToHost, r->s));
     OZ_HIP(hipStreamSynchronize(r->s));
     return OZ_OK;
 }

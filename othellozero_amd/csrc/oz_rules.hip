@@ -530,3 +530,11 @@ OZ_API int oz_examples_expand_policy(const oz_record* records, const float* rows
     }
     return OZ_OK;
 }
+
+// the auxiliary targets of `R` records (oz_aux_target, oz_common.h: the definition the replay buffer's append kernels evaluate): on the host,
+// no device needed
+OZ_API int oz_aux_targets(const oz_record* records, int64_t R, uint64_t* fin_own, uint64_t* fin_opp) {
+    OZ_REQUIRE(R >= 0 && (R == 0 || (records && fin_own && fin_opp)), "oz_aux_targets: null argument or negative count");
+    for (int64_t i = 0; i < R; ++i) oz_aux_target(records[i], fin_own[i], fin_opp[i]);
+    return OZ_OK;
+}

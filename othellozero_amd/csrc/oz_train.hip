@@ -421,6 +421,8 @@ __global__ __launch_bounds__(256) void k_t_acc_eval(const float* __restrict__ ro
     }
 }
 // dWpi[k][a] = sum_b f2[b][k] dlogit[b][a];  dWv[k] = sum_b f2[b][k] dvpre[b]   (block = k, thread = a; a == A handles v)
+// TWO callers: t_heads_backward launches it for the policy / value heads and, with the auxiliary heads on, a second time on their tensors
+// (dopre, dspre -> dWown, dWsc): a change of its sums or its argument order changes both
 __global__ __launch_bounds__(128) void k_t_heads_wgrad(const float* __restrict__ f2, const float* __restrict__ dlogit, const float* __restrict__ dvpre,
                                                        const int* __restrict__ d_count, int A, float* __restrict__ dWpi, float* __restrict__ dWv) {
     const int k = blockIdx.x, a = threadIdx.x, B = *d_count;
@@ -453,6 +455,90 @@ __global__ __launch_bounds__(256) void k_t_heads_dgrad(const float* __restrict__
     float acc = dvpre[b] * Wv[k];
     for (int a = 0; a < A; ++a) acc = fmaf(dlogit[(size_t)b * A + a], Wpi[(size_t)k * A + a], acc);
     df2[i] = acc;
+}
+
+// ---------------------------------------------------------------- auxiliary heads (oz_trainer_set_aux_heads): ownership and score from the final boards
+// Two more heads on f2, trained and then thrown away: o[a] = tanh(f2 . Wown[:, a] + bown[a]) against who owns square a at the end of the game
+// (+1 mover / -1 opponent / 0 empty), s = tanh(f2 . Wsc + bsc) against the final disc margin / A, both from the mover's side (oz_aux_target,
+// oz_common.h).  m = (fin_own | fin_opp) != 0 masks an example without a final board; the batch means divide by B as the value loss does:
+//   L_own = (1/B) sum_b m_b (1/A) sum_a (o - t)^2        L_sc = (1/B) sum_b m_b (s - s_target)^2
+// fp32 in every trainer precision.  The loss weights are folded into the pre-activation gradients, so the three backward kernels know nothing of
+// them; with both weights 0 the backward kernels are not launched at all (forward and losses only: the 40 gradients keep their bits).
+// k_t_aux_heads: one 64-thread block per sample, lane = cell a = row*n+col, the weight-row loads of k_t_heads (64 rows in flight, the fmaf
+// chain in k order).  Every sum over lanes is the xor-shuffle tree: a fixed order
+__global__ __launch_bounds__(64) void k_t_aux_heads(const float* __restrict__ f2 /*[B][512]*/, const int* __restrict__ d_count, int n,
+                                                    const float* __restrict__ Wown /*[512][A]*/, const float* __restrict__ bown,
+                                                    const float* __restrict__ Wsc /*[512]*/, const float* __restrict__ bsc,
+                                                    const uint64_t* __restrict__ fin_own, const uint64_t* __restrict__ fin_opp, float w_own, float w_sc,
+                                                    float* __restrict__ o_out /*[B][A]*/, float* __restrict__ s_out /*[B]*/,
+                                                    float* __restrict__ dopre /*[B][A]*/, float* __restrict__ dspre /*[B]*/,
+                                                    float* __restrict__ loss /*[B][2]*/) {
+    const int b = blockIdx.x, lane = threadIdx.x, A = n * n, B = *d_count;
+    if (b >= B) return;
+    const float* x = f2 + (size_t)b * 512;
+    float opre = 0.f, sacc = 0.f;
+    {
+        const auto wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Wown), 0, 512 * A * 4, 0x00020000);
+        const int lo = (lane < A ? lane : 0) * 4;
+        float acc = 0.f;
+#pragma unroll 1
+        for (int k0 = 0; k0 < 512; k0 += 64) {
+            float wv[64];
+#pragma unroll
+            for (int j = 0; j < 64; ++j) wv[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(wrs, lo, (k0 + j) * A * 4, 0));
+#pragma unroll
+            for (int j = 0; j < 64; ++j) acc = fmaf(x[k0 + j], wv[j], acc);
+        }
+        if (lane < A) opre = acc + bown[lane];
+    }
+    for (int k = lane; k < 512; k += 64) sacc = fmaf(x[k], Wsc[k], sacc);
+    for (int off = 32; off; off >>= 1) sacc += __shfl_xor(sacc, off);
+    const uint64_t fo = fin_own[b], fp = fin_opp[b];
+    const bool live = (fo | fp) != 0;
+    const float o = tanhf(opre), s = tanhf(sacc + bsc[0]);
+    const float d = lane < A ? o - oz_aux_own_target(fo, fp, (lane / n) * 8 + lane % n) : 0.f;
+    float lo_ = d * d;
+    for (int off = 32; off; off >>= 1) lo_ += __shfl_xor(lo_, off);
+    if (lane < A) {
+        o_out[(size_t)b * A + lane] = o;
+        dopre[(size_t)b * A + lane] = live ? w_own * (2.0f * d / ((float)B * (float)A)) * (1.0f - o * o) : 0.f;
+    }
+    if (lane == 0) {
+        const float ds = s - oz_aux_score_target(fo, fp, A);
+        s_out[b] = s;
+        dspre[b] = live ? w_sc * (2.0f * ds / (float)B) * (1.0f - s * s) : 0.f;
+        loss[2 * b] = live ? lo_ / (float)A : 0.f;
+        loss[2 * b + 1] = live ? ds * ds : 0.f;
+    }
+}
+// aux[0..1] = L_own, L_sc (batch means, sums in batch order); with a weight on, losses[0] (k_t_heads_bias' total) gains w_own L_own + w_sc L_sc
+__global__ __launch_bounds__(64) void k_t_aux_losses(const float* __restrict__ loss, const int* __restrict__ d_count, float w_own, float w_sc,
+                                                     float* __restrict__ aux /*[2]*/, float* __restrict__ losses) {
+    if (threadIdx.x != 0) return;
+    const int B = *d_count;
+    float lo = 0.f, ls = 0.f;
+    _Pragma("unroll 8") for (int b = 0; b < B; ++b) { lo += loss[2 * b]; ls += loss[2 * b + 1]; }
+    lo /= (float)B; ls /= (float)B;
+    aux[0] = lo; aux[1] = ls;
+    if (w_own > 0.f || w_sc > 0.f) losses[0] = losses[0] + (w_own * lo + w_sc * ls);
+}
+// (the weight gradients dWown[k][a] = sum_b f2[b][k] dopre[b][a], dWsc[k] = sum_b f2[b][k] dspre[b] ARE k_t_heads_wgrad's sums: a second launch of it)
+// dbown[a] = sum_b dopre[b][a]; dbsc = sum_b dspre[b]; sums in batch order
+__global__ __launch_bounds__(128) void k_t_aux_bias(const float* __restrict__ dopre, const float* __restrict__ dspre, const int* __restrict__ d_count, int A,
+                                                    float* __restrict__ dbown, float* __restrict__ dbsc) {
+    const int a = threadIdx.x, B = *d_count;
+    if (a < A) { float s = 0.f; _Pragma("unroll 8") for (int b = 0; b < B; ++b) s += dopre[(size_t)b * A + a]; dbown[a] = s; }
+    if (a == A) { float s = 0.f; _Pragma("unroll 8") for (int b = 0; b < B; ++b) s += dspre[b]; dbsc[0] = s; }
+}
+// df2[b][k] += sum_a dopre[b][a] Wown[k][a] + dspre[b] Wsc[k]: behind k_t_heads_dgrad, one thread per element, the sum in k_t_heads_dgrad's order
+__global__ __launch_bounds__(256) void k_t_aux_dgrad(const float* __restrict__ dopre, const float* __restrict__ dspre, const float* __restrict__ Wown,
+                                                     const float* __restrict__ Wsc, const int* __restrict__ d_count, int A, float* __restrict__ df2) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long long)(*d_count) * 512) return;
+    const int b = (int)(i / 512), k = (int)(i % 512);
+    float acc = dspre[b] * Wsc[k];
+    for (int a = 0; a < A; ++a) acc = fmaf(dopre[(size_t)b * A + a], Wown[(size_t)k * A + a], acc);
+    df2[i] += acc;
 }
 
 // ---------------------------------------------------------------- weight gradient: TN implicit GEMM on fp32 MFMA
@@ -1058,8 +1144,9 @@ __global__ __launch_bounds__(256) void k_t_adam(float* __restrict__ P, const flo
 // so the bounds are scalar loads and the test costs two compares per range and unit (eight ranges under the default mask) beside nine 16-byte
 // streams -- no table in memory, no per-lane indexing of the arguments (which would go to scratch).
 #define T_OPT_SEGS 28                        // trainable arrays of the network
+#define T_OPT_ARRAYS (T_OPT_SEGS + 4)        // ... and of a trainer with the auxiliary heads (the norm's table alone: decayed arrays that follow each other merge into one range)
 struct TUnitRanges { int n; int lo[T_OPT_SEGS], hi[T_OPT_SEGS]; };             // units [lo, hi)
-struct TSegs { int n; long long off[T_OPT_SEGS], len[T_OPT_SEGS]; };           // arrays: offset in the arena (floats, a multiple of 4) and ELEMENT count
+struct TSegs { int n; long long off[T_OPT_ARRAYS], len[T_OPT_ARRAYS]; };       // arrays: offset in the arena (floats, a multiple of 4) and ELEMENT count
 struct TAdamX { float lr_t, clip, c2 /* 2 c */, lam /* lr_s lambda */, d, omd /* 1 - d */; };
 struct TNormOut { double sumsq, norm, scale; float scale32, pad; };
 #define T_OPT_ADAM_BLOCKS 2048               // grid caps: the rest is grid-stride
@@ -1150,8 +1237,19 @@ struct oz_trainer {
     int64_t step = 0;
     int policy_loss = OZ_POLICY_LOSS_ROWS;   // oz_trainer_set_policy_loss
     hipStream_t s = nullptr;
-    int64_t size[40], toff[40];          // element counts; offset in the trainable arena (-1: moving statistic)
+    int64_t size[44], toff[44];          // element counts; offset in the trainable arena (-1: moving statistic); 40 .. 43: the auxiliary heads
     int64_t total = 0;
+    // auxiliary heads (oz_trainer_set_aux_heads): nw = 44 arrays, the four new ones at the end of the arenas; the staged batch's final pairs
+    // (pinned mirror h_fin), the heads' outputs, pre-activation gradients, per-sample losses and the two batch means; the resident data set's pairs
+    bool aux = false;
+    int nw = 40;
+    float w_own = 0.f, w_sc = 0.f;
+    uint64_t *d_fin = nullptr, *h_fin = nullptr;         // [2][Bmax]: fin_own, fin_opp
+    float *ao = nullptr, *as = nullptr, *dopre = nullptr, *dspre = nullptr, *aux_loss = nullptr, *aux_losses = nullptr;
+    float* cap_f2 = nullptr;             // capture: the gradient wrt f2 as k_t_heads_dgrad left it, before k_t_aux_dgrad's add
+    uint64_t *ds_fo = nullptr, *ds_fp = nullptr;
+    int64_t ds_fin_cap = 0;
+    double epoch_aux[2] = {0.0, 0.0};    // the last fit epoch's sample-weighted means of the two losses
     float *P = nullptr, *G = nullptr, *M1 = nullptr, *V2 = nullptr;
     bool own_grads = true;
     float *stats[40] = {}, *stats_new[40] = {};
@@ -1216,8 +1314,9 @@ struct oz_trainer {
         if (s) hipStreamSynchronize(s);
         for (void* q : allocs) hipFree(q);
         for (void* q : {(void*)ds_own, (void*)ds_opp, (void*)ds_pi, (void*)ds_z, (void*)ds_order, (void*)ds_acc}) if (q) hipFree(q);
-        for (void* q : {(void*)ev_order, (void*)ev_own, (void*)ev_opp, (void*)ev_pi, (void*)ev_z}) if (q) hipFree(q);
+        for (void* q : {(void*)ev_order, (void*)ev_own, (void*)ev_opp, (void*)ev_pi, (void*)ev_z, (void*)ds_fo, (void*)ds_fp}) if (q) hipFree(q);
         if (h_in) hipHostFree(h_in);
+        if (h_fin) hipHostFree(h_fin);
         for (hipEvent_t e : ev_dz) if (e) hipEventDestroy(e);
         if (ev_w) hipEventDestroy(ev_w);
         for (hipEvent_t e : {ev_pre, ev_wt, ev_wd, ev_wl[1], ev_wl[2], ev_wl[3]}) if (e) hipEventDestroy(e);
@@ -1229,8 +1328,9 @@ struct oz_trainer {
 };
 
 // element counts of the 40 get_weights() arrays and their offsets in the trainable arena (-1: moving statistic);
-// every array starts 16-byte aligned.  Returns the arena size in floats.
-static int64_t t_layout(int n, int C, int cin, int64_t* size, int64_t* toff) {
+// every array starts 16-byte aligned.  Returns the arena size in floats.  aux: the four arrays of the auxiliary heads (40 Wown [512][A],
+// 41 bown [A], 42 Wsc [512], 43 bsc [1]) follow the forty, so the forty keep their offsets
+static int64_t t_layout(int n, int C, int cin, int64_t* size, int64_t* toff, bool aux = false) {
     const int64_t A = n * n;
     const OzLayers net = oz_onn_layers(n, C);
     for (int l = 0; l < 6; ++l) {          // kernel [K][N], then bias, gamma, beta and the two moving statistics [N]
@@ -1245,8 +1345,14 @@ static int64_t t_layout(int n, int C, int cin, int64_t* size, int64_t* toff) {
         toff[i] = stat ? -1 : total;
         if (!stat) total += (size[i] + 3) / 4 * 4;
     }
+    if (aux) {
+        size[40] = 512 * A; size[41] = A; size[42] = 512; size[43] = 1;
+        for (int i = 40; i < 44; ++i) { toff[i] = total; total += i < 43 ? (size[i] + 3) / 4 * 4 : size[i]; }     // (the arena ends with bsc: no padding behind it)
+    }
     return total;
 }
+// what a library-owned arena of `total` floats is allocated with: whole 16-byte units (an arena with the auxiliary heads ends inside one)
+static int64_t t_arena_alloc(int64_t total) { return (total + 3) / 4 * 4; }
 
 static int t_alloc(oz_trainer* t, void** out, size_t bytes, bool zero = true) {
     OZ_HIP(hipMalloc(out, bytes ? bytes : 16));
@@ -1259,10 +1365,11 @@ static int t_alloc(oz_trainer* t, void** out, size_t bytes, bool zero = true) {
 
 // ---------------------------------------------------------------- optimiser options: validation, the schedule (host only), the segment tables
 static bool t_is_stat(int i) { return i < 36 && (i % 6 == 4 || i % 6 == 5); }
-static uint64_t t_decay_mask(const oz_optimizer& o) {            // 0 = the default: the eight kernels
+static uint64_t t_decay_mask(const oz_optimizer& o, bool aux = false) {      // 0 = the default: the eight kernels (with the auxiliary heads: and their two)
     if (o.decay_mask) return o.decay_mask;
     uint64_t m = (1ull << 36) | (1ull << 38);
     for (int l = 0; l < 6; ++l) m |= 1ull << (6 * l);
+    if (aux) m |= (1ull << 40) | (1ull << 42);
     return m;
 }
 static int t_opt_check(const oz_optimizer* o, const char* who) {
@@ -1304,9 +1411,9 @@ OZ_API int oz_lr_schedule_at(const oz_optimizer* opt, float lr, int64_t step, do
 // the segment tables of the current options: every trainable array (the norm), the decayed ones (oz_trainer_sqsum), and the decayed ones as
 // merged 16-byte-unit ranges (k_t_adam_x)
 static void t_opt_tables(oz_trainer* t) {
-    const uint64_t mask = t_decay_mask(t->opt);
+    const uint64_t mask = t_decay_mask(t->opt, t->aux);
     t->seg_all.n = t->seg_dec.n = t->dec_units.n = 0;
-    for (int i = 0; i < 40; ++i) {
+    for (int i = 0; i < t->nw; ++i) {
         if (t->toff[i] < 0) continue;
         TSegs& a = t->seg_all;
         a.off[a.n] = t->toff[i]; a.len[a.n] = t->size[i]; a.n += 1;
@@ -1450,7 +1557,7 @@ OZ_API int oz_trainer_set_precision(oz_trainer* t, int mode) {
 }
 
 OZ_API int oz_trainer_set_weight(oz_trainer* t, int index, const float* data, int64_t nelem) {
-    OZ_REQUIRE(t && data && index >= 0 && index < 40, "oz_trainer_set_weight: bad argument");
+    OZ_REQUIRE(t && data && index >= 0 && index < t->nw, "oz_trainer_set_weight: bad argument");
     T_LOCK(t);
     OZ_REQUIRE(nelem == t->size[index], "oz_trainer_set_weight: weight %d has %lld elements, got %lld", index, (long long)t->size[index], (long long)nelem);
     OZ_HIP(hipSetDevice(t->device));
@@ -1462,7 +1569,7 @@ OZ_API int oz_trainer_set_weight(oz_trainer* t, int index, const float* data, in
     return OZ_OK;
 }
 OZ_API int oz_trainer_get_weight(oz_trainer* t, int index, float* data, int64_t nelem) {
-    OZ_REQUIRE(t && data && index >= 0 && index < 40 && nelem == t->size[index], "oz_trainer_get_weight: bad argument");
+    OZ_REQUIRE(t && data && index >= 0 && index < t->nw && nelem == t->size[index], "oz_trainer_get_weight: bad argument");
     T_LOCK(t);
     OZ_HIP(hipSetDevice(t->device));
     OZ_HIP(hipMemcpyAsync(data, t->param(index), nelem * sizeof(float), hipMemcpyDeviceToHost, t->s));
@@ -1470,7 +1577,7 @@ OZ_API int oz_trainer_get_weight(oz_trainer* t, int index, float* data, int64_t 
     return OZ_OK;
 }
 OZ_API int oz_trainer_get_grad(oz_trainer* t, int index, float* data, int64_t nelem) {
-    OZ_REQUIRE(t && data && index >= 0 && index < 40 && nelem == t->size[index] && t->toff[index] >= 0, "oz_trainer_get_grad: bad argument");
+    OZ_REQUIRE(t && data && index >= 0 && index < t->nw && nelem == t->size[index] && t->toff[index] >= 0, "oz_trainer_get_grad: bad argument");
     T_LOCK(t);
     OZ_HIP(hipSetDevice(t->device));
     OZ_HIP(hipMemcpyAsync(data, t->grad(index), nelem * sizeof(float), hipMemcpyDeviceToHost, t->s));
@@ -1488,6 +1595,73 @@ OZ_API int oz_trainer_arena_size(int n, int channels, int in_channels, int64_t* 
     int64_t size[40], toff[40];
     const int64_t tot = t_layout(n, channels, in_channels, size, toff);
     *nelem = tot;
+    return OZ_OK;
+}
+OZ_API int oz_trainer_arena_size_aux(int n, int channels, int in_channels, int64_t* nelem) {
+    OZ_REQUIRE(nelem, "oz_trainer_arena_size_aux: bad argument");
+    int64_t size[44], toff[44];
+    *nelem = t_layout(n, channels, in_channels, size, toff, true);
+    return OZ_OK;
+}
+
+// ---------------------------------------------------------------- auxiliary heads: switching them on
+// Glorot-uniform array of `count` floats from (seed, stream): limit sqrt(6 / (fan_in + fan_out)), the unit draws of oz_rng
+static void t_glorot(std::vector<float>& w, int64_t count, int fan_in, int fan_out, uint64_t seed, uint64_t stream) {
+    const double lim = sqrt(6.0 / (double)(fan_in + fan_out));
+    w.resize((size_t)count);
+    for (int64_t i = 0; i < count; ++i) w[(size_t)i] = (float)((2.0 * oz_rng_unit(oz_rng(seed, (uint64_t)i, stream, 0x617578ULL)) - 1.0) * lim);
+}
+OZ_API int oz_trainer_set_aux_heads(oz_trainer* t, float w_own, float w_score) {
+    OZ_REQUIRE(t, "oz_trainer_set_aux_heads: NULL");
+    OZ_REQUIRE(w_own >= 0.f && w_score >= 0.f && std::isfinite(w_own) && std::isfinite(w_score),
+               "oz_trainer_set_aux_heads: weights (%g, %g) must be finite and >= 0", (double)w_own, (double)w_score);
+    T_LOCK(t);
+    if (t->ran || t->step > 0) { oz_set_error("oz_trainer_set_aux_heads: a step has run on this trainer (the heads are switched on before the first one)"); return OZ_ERR_STATE; }
+    // (the library cannot see how large a caller's arena is, and the four gradients would be written behind a forty-array one)
+    OZ_REQUIRE(t->own_grads, "oz_trainer_set_aux_heads: not offered for a trainer created on an external gradient arena (a data-parallel fit): the arena was sized for the forty arrays");
+    OZ_HIP(hipSetDevice(t->device));
+    if (t->aux) { t->w_own = w_own; t->w_sc = w_score; return OZ_OK; }      // (again before the first step: the weights alone)
+    OZ_HIP(hipStreamSynchronize(t->s));
+    const int64_t old_total = t->total, A = t->n * t->n;
+    const int64_t total = t_layout(t->n, t->C, t->cin, t->size, t->toff, true);
+    // the three (four, five) arenas grow by the aux arrays: new allocations, the forty's contents carried over, the old ones freed
+    auto grow = [&](float*& arena) -> int {
+        float* neu = nullptr;
+        if (int rc = t_alloc(t, (void**)&neu, (size_t)t_arena_alloc(total) * sizeof(float))) return rc;
+        OZ_HIP(hipMemcpyAsync(neu, arena, old_total * sizeof(float), hipMemcpyDeviceToDevice, t->s));
+        OZ_HIP(hipStreamSynchronize(t->s));
+        for (void*& q : t->allocs) if (q == (void*)arena) { q = t->allocs.back(); t->allocs.pop_back(); break; }
+        hipFree(arena);
+        arena = neu;
+        return OZ_OK;
+    };
+    if (int rc = grow(t->P)) return rc;
+    if (int rc = grow(t->M1)) return rc;
+    if (int rc = grow(t->V2)) return rc;
+    if (int rc = grow(t->G)) return rc;
+    if (t->E) { if (int rc = grow(t->E)) return rc; }
+    t->total = total; t->nw = 44; t->aux = true; t->w_own = w_own; t->w_sc = w_score;
+    const size_t Bm = (size_t)t->Bmax;
+    T_ALLOC(t->d_fin, 2 * Bm);
+    OZ_HIP(hipHostMalloc((void**)&t->h_fin, 2 * Bm * sizeof(uint64_t), hipHostMallocDefault));
+    T_ALLOC(t->ao, Bm * A); T_ALLOC(t->as, Bm); T_ALLOC(t->dopre, Bm * A); T_ALLOC(t->dspre, Bm); T_ALLOC(t->aux_loss, 2 * Bm); T_ALLOC(t->aux_losses, 2);
+    if (t->capture) T_ALLOC(t->cap_f2, Bm * 512);
+    std::vector<float> w;
+    t_glorot(w, 512 * A, 512, (int)A, t->seed, 40);
+    OZ_HIP(hipMemcpyAsync(t->param(40), w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice, t->s));
+    if (t->E) OZ_HIP(hipMemcpyAsync(t->E + t->toff[40], w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice, t->s));
+    OZ_HIP(hipStreamSynchronize(t->s));
+    t_glorot(w, 512, 512, 1, t->seed, 42);
+    OZ_HIP(hipMemcpyAsync(t->param(42), w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice, t->s));
+    if (t->E) OZ_HIP(hipMemcpyAsync(t->E + t->toff[42], w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice, t->s));
+    OZ_HIP(hipStreamSynchronize(t->s));
+    t_opt_tables(t);
+    return OZ_OK;
+}
+OZ_API int oz_trainer_get_aux_heads(oz_trainer* t, int* on, float* w_own, float* w_score) {
+    OZ_REQUIRE(t && on && w_own && w_score, "oz_trainer_get_aux_heads: bad argument");
+    T_LOCK(t);
+    *on = t->aux ? 1 : 0; *w_own = t->w_own; *w_score = t->w_sc;
     return OZ_OK;
 }
 OZ_API int oz_trainer_sync(oz_trainer* t) {
@@ -1661,6 +1835,9 @@ static int t_forward(oz_trainer* t, int B, bool infer = false) {
     }
     hipLaunchKernelGGL(k_t_heads, dim3(B), dim3(64), 0, s, t->a[5], t->d_count, n, t->policy_loss, t->param(36), t->param(37), t->param(38), t->param(39),
                        t->d_pit, t->d_zt, t->p, t->v, t->dlogit, t->dvpre, t->loss);
+    if (t->aux)
+        hipLaunchKernelGGL(k_t_aux_heads, dim3(B), dim3(64), 0, s, t->a[5], t->d_count, n, t->param(40), t->param(41), t->param(42), t->param(43),
+                           t->d_fin, t->d_fin + t->Bmax, t->w_own, t->w_sc, t->ao, t->as, t->dopre, t->dspre, t->aux_loss);
     OZ_HIP(hipGetLastError());
     return OZ_OK;
 }
@@ -1681,6 +1858,18 @@ static int t_heads_backward(oz_trainer* t, int B, float* dA) {
                        t->mode == 1 ? t->dzmax : (unsigned*)nullptr);
     hipLaunchKernelGGL(k_t_heads_dgrad, dim3((unsigned)(((long long)B * 512 + 255) / 256)), dim3(256), 0, s, t->dlogit, t->dvpre, t->param(36),
                        t->param(38), t->d_count, A, dA);
+    OZ_HIP(hipGetLastError());
+    if (!t->aux) return t_capture(t, 5, B, dA);
+    // auxiliary heads: their batch-mean losses behind k_t_heads_bias (whose total they join); with a weight on, their weight and bias gradients
+    // and their term of dA behind k_t_heads_dgrad.  Both weights 0: nothing more is launched (adding a signed zero into dA would change bits)
+    hipLaunchKernelGGL(k_t_aux_losses, dim3(1), dim3(64), 0, s, t->aux_loss, t->d_count, t->w_own, t->w_sc, t->aux_losses, t->losses);
+    if (t->w_own > 0.f || t->w_sc > 0.f) {
+        if (t->capture) OZ_HIP(hipMemcpyAsync(t->cap_f2, dA, (size_t)B * 512 * sizeof(float), hipMemcpyDeviceToDevice, s));
+        hipLaunchKernelGGL(k_t_heads_wgrad, dim3(512), dim3(128), 0, s, t->a[5], t->dopre, t->dspre, t->d_count, A, t->grad(40), t->grad(42));
+        hipLaunchKernelGGL(k_t_aux_bias, dim3(1), dim3(128), 0, s, t->dopre, t->dspre, t->d_count, A, t->grad(41), t->grad(43));
+        hipLaunchKernelGGL(k_t_aux_dgrad, dim3((unsigned)(((long long)B * 512 + 255) / 256)), dim3(256), 0, s, t->dopre, t->dspre, t->param(40),
+                           t->param(42), t->d_count, A, dA);
+    }
     OZ_HIP(hipGetLastError());
     return t_capture(t, 5, B, dA);
 }
@@ -1876,14 +2065,23 @@ static int t_forward_backward_async(oz_trainer* t, int B) {
     return OZ_OK;
 }
 
-OZ_API int oz_trainer_forward_backward(oz_trainer* t, const uint64_t* own, const uint64_t* opp, const float* pi_target, const float* z_target,
-                                       int B, float* losses3) {
-    OZ_REQUIRE(t && own && opp && pi_target && z_target, "oz_trainer_forward_backward: NULL argument");
-    T_LOCK(t);
+// the staged batch's final pairs of a trainer with the auxiliary heads, from the host (fin_own == NULL: every mask 0), on the main stream
+static int t_stage_fin(oz_trainer* t, const uint64_t* fin_own, const uint64_t* fin_opp, int B) {
+    if (!fin_own) { OZ_HIP(hipMemsetAsync(t->d_fin, 0, 2 * (size_t)t->Bmax * sizeof(uint64_t), t->s)); return OZ_OK; }
+    memcpy(t->h_fin, fin_own, B * sizeof(uint64_t));
+    memcpy(t->h_fin + t->Bmax, fin_opp, B * sizeof(uint64_t));
+    OZ_HIP(hipMemcpyAsync(t->d_fin, t->h_fin, 2 * (size_t)t->Bmax * sizeof(uint64_t), hipMemcpyHostToDevice, t->s));
+    return OZ_OK;
+}
+
+// losses: {total, policy, value} and, aux5, {ownership, score} behind them
+static int t_forward_backward_host(oz_trainer* t, const uint64_t* own, const uint64_t* opp, const float* pi_target, const float* z_target,
+                                   const uint64_t* fin_own, const uint64_t* fin_opp, int B, float* losses3, bool aux5) {
     OZ_REQUIRE(B >= 1 && B <= t->Bmax, "oz_trainer_forward_backward: batch %d outside [1, %d]", B, t->Bmax);
     OZ_HIP(hipSetDevice(t->device));
     hipStream_t s = t->s;
     const int A = t->n * t->n;
+    if (t->aux) if (int rc = t_stage_fin(t, fin_own, fin_opp, B)) { hipStreamSynchronize(s); return rc; }
     {   // one upload (the call synchronises before it returns, so the pinned block is free again at the next call)
         unsigned char* h = t->h_in;
         memcpy(h + ((unsigned char*)t->d_own - t->d_in), own, B * sizeof(uint64_t));
@@ -1897,11 +2095,31 @@ OZ_API int oz_trainer_forward_backward(oz_trainer* t, const uint64_t* own, const
         hipStreamSynchronize(s);                   // the upload out of h_in may still be in flight: a retrying caller's next memcpy into it must not race with that DMA
         return rc;
     }
-    float h[4];
+    float h[4], ha[2] = {0.f, 0.f};
     OZ_HIP(hipMemcpyAsync(h, t->losses, 3 * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (aux5) OZ_HIP(hipMemcpyAsync(ha, t->aux_losses, 2 * sizeof(float), hipMemcpyDeviceToHost, s));
     OZ_HIP(hipStreamSynchronize(s));
     if (losses3) { losses3[0] = h[0]; losses3[1] = h[1]; losses3[2] = h[2]; }
+    if (losses3 && aux5) { losses3[3] = ha[0]; losses3[4] = ha[1]; }
     return t_check_range(t);
+}
+OZ_API int oz_trainer_forward_backward(oz_trainer* t, const uint64_t* own, const uint64_t* opp, const float* pi_target, const float* z_target,
+                                       int B, float* losses3) {
+    OZ_REQUIRE(t && own && opp && pi_target && z_target, "oz_trainer_forward_backward: NULL argument");
+    T_LOCK(t);
+    return t_forward_backward_host(t, own, opp, pi_target, z_target, nullptr, nullptr, B, losses3, false);
+}
+static int t_need_aux(oz_trainer* t, const char* who) {
+    if (t->aux) return OZ_OK;
+    oz_set_error("%s: this trainer has no auxiliary heads (oz_trainer_set_aux_heads)", who);
+    return OZ_ERR_STATE;
+}
+OZ_API int oz_trainer_forward_backward_aux(oz_trainer* t, const uint64_t* own, const uint64_t* opp, const float* pi_target, const float* z_target,
+                                           const uint64_t* fin_own, const uint64_t* fin_opp, int B, float* losses5) {
+    OZ_REQUIRE(t && own && opp && pi_target && z_target && fin_own && fin_opp, "oz_trainer_forward_backward_aux: NULL argument");
+    T_LOCK(t);
+    if (int rc = t_need_aux(t, "oz_trainer_forward_backward_aux")) return rc;
+    return t_forward_backward_host(t, own, opp, pi_target, z_target, fin_own, fin_opp, B, losses5, true);
 }
 
 // ---------------------------------------------------------------- HBM-resident data set: one upload per fit, one read-back per epoch
@@ -1923,12 +2141,39 @@ __global__ void k_t_acc_losses(const float* __restrict__ losses, int B, double* 
     if (threadIdx.x < 3) acc[threadIdx.x] += (double)losses[threadIdx.x] * (double)B;
     if (threadIdx.x == 3) acc[3] += (double)B;
 }
+// the aux siblings of the two kernels above: the batch's final pairs by index, and the two auxiliary losses into acc[4], acc[5]
+__global__ void k_t_gather_batch_aux(const uint64_t* __restrict__ ds_fo, const uint64_t* __restrict__ ds_fp, const int* __restrict__ order, int first, int B,
+                                     uint64_t* __restrict__ fo, uint64_t* __restrict__ fp) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const int src = order[first + b];
+    fo[b] = ds_fo[src]; fp[b] = ds_fp[src];
+}
+__global__ void k_t_acc_aux_losses(const float* __restrict__ aux, int B, double* __restrict__ acc) {
+    if (threadIdx.x < 2) acc[4 + threadIdx.x] += (double)aux[threadIdx.x] * (double)B;
+}
+#define T_DS_ACC 6                       // doubles of ds_acc: 3 weighted loss sums, the samples, the two auxiliary sums
 
-OZ_API int oz_trainer_set_dataset(oz_trainer* t, const uint64_t* own, const uint64_t* opp, const float* pi_target, const float* z_target, int64_t N) {
-    OZ_REQUIRE(t && own && opp && pi_target && z_target && N >= 1 && N < (1ll << 31), "oz_trainer_set_dataset: bad argument");
-    T_LOCK(t);
+static int t_set_dataset(oz_trainer* t, const uint64_t* own, const uint64_t* opp, const float* pi_target, const float* z_target,
+                         const uint64_t* fin_own, const uint64_t* fin_opp, int64_t N) {
     OZ_HIP(hipSetDevice(t->device));
     const int A = t->n * t->n;
+    if (t->aux) {                      // the pairs beside the data set (no arrays given: every mask 0)
+        if (N > t->ds_fin_cap) {
+            OZ_HIP(hipStreamSynchronize(t->s));
+            if (t->ds_fo) { hipFree(t->ds_fo); hipFree(t->ds_fp); }
+            t->ds_fo = t->ds_fp = nullptr; t->ds_fin_cap = 0;
+            OZ_HIP(hipMalloc((void**)&t->ds_fo, N * sizeof(uint64_t))); OZ_HIP(hipMalloc((void**)&t->ds_fp, N * sizeof(uint64_t)));
+            t->ds_fin_cap = N;
+        }
+        if (fin_own) {
+            OZ_HIP(hipMemcpyAsync(t->ds_fo, fin_own, N * sizeof(uint64_t), hipMemcpyHostToDevice, t->s));
+            OZ_HIP(hipMemcpyAsync(t->ds_fp, fin_opp, N * sizeof(uint64_t), hipMemcpyHostToDevice, t->s));
+        } else {
+            OZ_HIP(hipMemsetAsync(t->ds_fo, 0, N * sizeof(uint64_t), t->s));
+            OZ_HIP(hipMemsetAsync(t->ds_fp, 0, N * sizeof(uint64_t), t->s));
+        }
+    }
     if (N > t->ds_cap) {
         OZ_HIP(hipStreamSynchronize(t->s));
         if (t->ds_own) { hipFree(t->ds_own); hipFree(t->ds_opp); hipFree(t->ds_pi); hipFree(t->ds_z); }
@@ -1939,7 +2184,7 @@ OZ_API int oz_trainer_set_dataset(oz_trainer* t, const uint64_t* own, const uint
         OZ_HIP(hipMalloc((void**)&t->ds_order, N * sizeof(int)));
         t->ds_cap = N; t->ds_order_cap = N;
     }
-    if (!t->ds_acc) OZ_HIP(hipMalloc((void**)&t->ds_acc, 4 * sizeof(double)));
+    if (!t->ds_acc) OZ_HIP(hipMalloc((void**)&t->ds_acc, T_DS_ACC * sizeof(double)));
     OZ_HIP(hipMemcpyAsync(t->ds_own, own, N * sizeof(uint64_t), hipMemcpyHostToDevice, t->s));
     OZ_HIP(hipMemcpyAsync(t->ds_opp, opp, N * sizeof(uint64_t), hipMemcpyHostToDevice, t->s));
     OZ_HIP(hipMemcpyAsync(t->ds_pi, pi_target, (size_t)N * A * sizeof(float), hipMemcpyHostToDevice, t->s));
@@ -1948,12 +2193,24 @@ OZ_API int oz_trainer_set_dataset(oz_trainer* t, const uint64_t* own, const uint
     t->ds_n = N;
     return OZ_OK;
 }
+OZ_API int oz_trainer_set_dataset(oz_trainer* t, const uint64_t* own, const uint64_t* opp, const float* pi_target, const float* z_target, int64_t N) {
+    OZ_REQUIRE(t && own && opp && pi_target && z_target && N >= 1 && N < (1ll << 31), "oz_trainer_set_dataset: bad argument");
+    T_LOCK(t);
+    return t_set_dataset(t, own, opp, pi_target, z_target, nullptr, nullptr, N);
+}
+OZ_API int oz_trainer_set_dataset_aux(oz_trainer* t, const uint64_t* own, const uint64_t* opp, const float* pi_target, const float* z_target,
+                                      const uint64_t* fin_own, const uint64_t* fin_opp, int64_t N) {
+    OZ_REQUIRE(t && own && opp && pi_target && z_target && fin_own && fin_opp && N >= 1 && N < (1ll << 31), "oz_trainer_set_dataset_aux: bad argument");
+    T_LOCK(t);
+    if (int rc = t_need_aux(t, "oz_trainer_set_dataset_aux")) return rc;
+    return t_set_dataset(t, own, opp, pi_target, z_target, fin_own, fin_opp, N);
+}
 
 static int t_apply_locked(oz_trainer* t);
 
 // What an epoch reads its examples from: the trainer's own resident data set (oz_trainer_set_dataset) or a replay buffer's slots
-// (oz_replay.hip) -- `n` examples in the same four arrays.
-struct TDataView { const uint64_t *own, *opp; const float *pi, *z; int64_t n; };
+// (oz_replay.hip) -- `n` examples in the same four arrays; fo / fp: their final pairs for the auxiliary heads (NULL: none, every mask 0).
+struct TDataView { const uint64_t *own, *opp; const float *pi, *z; int64_t n; const uint64_t *fo = nullptr, *fp = nullptr; };
 
 // the optimiser steps of one epoch over `d` in the order `order` (validated by the caller's entry point): per step one device-side gather of
 // the batch, forward + backward, the loss accumulation and Adam, back to back on the stream; one read-back at the end
@@ -1968,21 +2225,26 @@ static int t_fit_epoch_view(oz_trainer* t, const TDataView& d, const int32_t* or
         OZ_HIP(hipMalloc((void**)&t->ds_order, count * sizeof(int)));
         t->ds_order_cap = count;
     }
-    if (!t->ds_acc) OZ_HIP(hipMalloc((void**)&t->ds_acc, 4 * sizeof(double)));
+    if (!t->ds_acc) OZ_HIP(hipMalloc((void**)&t->ds_acc, T_DS_ACC * sizeof(double)));
     OZ_HIP(hipMemcpyAsync(t->ds_order, order, count * sizeof(int), hipMemcpyHostToDevice, s));
-    OZ_HIP(hipMemsetAsync(t->ds_acc, 0, 4 * sizeof(double), s));
+    OZ_HIP(hipMemsetAsync(t->ds_acc, 0, T_DS_ACC * sizeof(double), s));
+    if (t->aux && !d.fo) OZ_HIP(hipMemsetAsync(t->d_fin, 0, 2 * (size_t)t->Bmax * sizeof(uint64_t), s));      // no pairs: every mask 0, for the whole epoch
     for (int64_t first = 0; first < count; first += batch) {
         const int B = (int)(count - first < batch ? count - first : batch);            // the last batch may be short, as in keras
         hipLaunchKernelGGL(k_t_gather_batch, dim3((B * A + 255) / 256), dim3(256), 0, s, d.own, d.opp, d.pi, d.z, t->ds_order,
                            (int)first, B, A, t->d_own, t->d_opp, t->d_pit, t->d_zt, t->d_count);
+        if (t->aux && d.fo)
+            hipLaunchKernelGGL(k_t_gather_batch_aux, dim3((B + 255) / 256), dim3(256), 0, s, d.fo, d.fp, t->ds_order, (int)first, B, t->d_fin, t->d_fin + t->Bmax);
         if (int rc = t_forward_backward_async(t, B)) return rc;
         hipLaunchKernelGGL(k_t_acc_losses, dim3(1), dim3(64), 0, s, t->losses, B, t->ds_acc);
+        if (t->aux) hipLaunchKernelGGL(k_t_acc_aux_losses, dim3(1), dim3(64), 0, s, t->aux_losses, B, t->ds_acc);
         if (int rc = t_apply_locked(t)) return rc;
     }
-    double h[4];
+    double h[T_DS_ACC];
     OZ_HIP(hipMemcpyAsync(h, t->ds_acc, sizeof h, hipMemcpyDeviceToHost, s));
     OZ_HIP(hipStreamSynchronize(s));
     if (losses3) for (int k = 0; k < 3; ++k) losses3[k] = (float)(h[k] / (h[3] > 0 ? h[3] : 1.0));
+    for (int k = 0; k < 2; ++k) t->epoch_aux[k] = h[4 + k] / (h[3] > 0 ? h[3] : 1.0);
     return t_check_range(t);
 }
 
@@ -1993,7 +2255,7 @@ OZ_API int oz_trainer_fit_epoch(oz_trainer* t, const int32_t* order, int64_t cou
                (long long)count, (long long)t->ds_n);
     OZ_REQUIRE(batch >= 1 && batch <= t->Bmax, "oz_trainer_fit_epoch: batch %d outside [1, %d]", batch, t->Bmax);
     for (int64_t i = 0; i < count; ++i) OZ_REQUIRE(order[i] >= 0 && order[i] < t->ds_n, "oz_trainer_fit_epoch: index %d outside the data set", order[i]);
-    return t_fit_epoch_view(t, {t->ds_own, t->ds_opp, t->ds_pi, t->ds_z, t->ds_n}, order, count, batch, losses3);
+    return t_fit_epoch_view(t, {t->ds_own, t->ds_opp, t->ds_pi, t->ds_z, t->ds_n, t->aux ? t->ds_fo : nullptr, t->aux ? t->ds_fp : nullptr}, order, count, batch, losses3);
 }
 
 // the same epoch with a replay buffer's slots as the resident data set (trainer locked before the replay buffer; the appends are synchronous,
@@ -2008,7 +2270,8 @@ OZ_API int oz_trainer_fit_epoch_replay(oz_trainer* t, oz_replay* r, const int32_
     const int64_t held = r->held();
     for (int64_t i = 0; i < count; ++i)
         OZ_REQUIRE(order[i] >= 0 && order[i] < held, "oz_trainer_fit_epoch_replay: index %d outside the %lld examples the replay buffer holds", order[i], (long long)held);
-    return t_fit_epoch_view(t, {r->own, r->opp, r->pi, r->z, held}, order, count, batch, losses3);
+    OZ_REQUIRE(!t->aux || r->fo, "oz_trainer_fit_epoch_replay: a trainer with the auxiliary heads needs a replay buffer that keeps the final pairs (oz_replay_create_aux)");
+    return t_fit_epoch_view(t, {r->own, r->opp, r->pi, r->z, held, t->aux ? r->fo : nullptr, t->aux ? r->fp : nullptr}, order, count, batch, losses3);
 }
 
 // ---------------------------------------------------------------- held-out evaluation in inference mode
@@ -2128,7 +2391,7 @@ static int t_launch_optimizer(oz_trainer* t, double lr_s, float lr_t, bool with_
             t->last_clipped = true;
         }
         const TAdamX a = {lr_t, t->clip, (float)(2.0 * o.l2), (float)(lr_s * o.weight_decay), (float)o.average_decay, (float)(1.0 - o.average_decay)};
-        const int units = (int)(t->total / 4);
+        const int units = (int)(t_arena_alloc(t->total) / 4);      // (whole units: only an arena with the auxiliary heads ends inside one, and that one is always library-owned)
         const int blocks = (units + 255) / 256 < T_OPT_ADAM_BLOCKS ? (units + 255) / 256 : T_OPT_ADAM_BLOCKS;
         hipLaunchKernelGGL(k_t_adam_x, dim3(blocks), dim3(256), 0, t->s, (float4*)t->P, (const float4*)t->G, (float4*)t->M1, (float4*)t->V2,
                            avg ? (float4*)t->E : (float4*)nullptr, units, a, clipped ? &t->norm_out[0].scale32 : (const float*)nullptr, t->dec_units);
@@ -2168,7 +2431,7 @@ OZ_API int oz_trainer_set_optimizer(oz_trainer* t, const oz_optimizer* opt) {
     OZ_REQUIRE(!fused || ((uintptr_t)t->G & 15) == 0, "oz_trainer_set_optimizer: the external gradient arena is not 16-byte aligned");
     OZ_HIP(hipSetDevice(t->device));
     if (o.average_decay > 0.0 && !(t->opt.average_decay > 0.0)) {        // switched on: E = the weights as they are now (stream order)
-        if (!t->E) T_ALLOC(t->E, t->total);
+        if (!t->E) T_ALLOC(t->E, t_arena_alloc(t->total));
         OZ_HIP(hipMemcpyAsync(t->E, t->P, t->total * sizeof(float), hipMemcpyDeviceToDevice, t->s));
         OZ_HIP(hipStreamSynchronize(t->s));
     }
@@ -2204,7 +2467,7 @@ OZ_API int oz_trainer_get_step_info(oz_trainer* t, double* lr_s, double* grad_no
     return OZ_OK;
 }
 OZ_API int oz_trainer_get_weight_average(oz_trainer* t, int index, float* data, int64_t nelem) {
-    OZ_REQUIRE(t && data && index >= 0 && index < 40, "oz_trainer_get_weight_average: bad argument");
+    OZ_REQUIRE(t && data && index >= 0 && index < t->nw, "oz_trainer_get_weight_average: bad argument");
     T_LOCK(t);
     OZ_REQUIRE(nelem == t->size[index], "oz_trainer_get_weight_average: weight %d has %lld elements, got %lld", index, (long long)t->size[index], (long long)nelem);
     if (!(t->opt.average_decay > 0.0)) { oz_set_error("oz_trainer_get_weight_average: the weight average is off (oz_optimizer.average_decay)"); return OZ_ERR_STATE; }
@@ -2323,6 +2586,10 @@ OZ_API int oz_trainer_set_capture(oz_trainer* t, int on) {
         for (int l = 0; l < 6; ++l) T_ALLOC(t->cap[l], (size_t)t->Bmax * t->L[l].P * t->L[l].Co);
         OZ_HIP(hipStreamSynchronize(t->s));
     }
+    if (on && t->aux && !t->cap_f2) {
+        T_ALLOC(t->cap_f2, (size_t)t->Bmax * 512);
+        OZ_HIP(hipStreamSynchronize(t->s));
+    }
     t->capture = on != 0;
     t->cap_valid = false;                 // what an earlier step captured is not the next reader's step
     return OZ_OK;
@@ -2345,6 +2612,41 @@ OZ_API int oz_trainer_get_head_grads(oz_trainer* t, int B, float* dlogit, float*
     if (int rc = t_read(t, t->dlogit, dlogit, (int64_t)B * t->n * t->n)) return rc;
     return t_read(t, t->dvpre, dvpre, B);
 }
+// ---------------------------------------------------------------- auxiliary heads: read-outs of the last step
+OZ_API int oz_trainer_aux_outputs(oz_trainer* t, int B, float* own, float* score) {
+    OZ_REQUIRE(t && B >= 1 && B <= t->Bmax, "oz_trainer_aux_outputs: bad argument");
+    T_LOCK(t);
+    if (int rc = t_need_aux(t, "oz_trainer_aux_outputs")) return rc;
+    if (int rc = t_need_step(t, "oz_trainer_aux_outputs")) return rc;
+    if (own) if (int rc = t_read(t, t->ao, own, (int64_t)B * t->n * t->n)) return rc;
+    if (score) if (int rc = t_read(t, t->as, score, B)) return rc;
+    return OZ_OK;
+}
+OZ_API int oz_trainer_get_aux_losses(oz_trainer* t, float* step2, double* epoch2) {
+    OZ_REQUIRE(t, "oz_trainer_get_aux_losses: NULL");
+    T_LOCK(t);
+    if (int rc = t_need_aux(t, "oz_trainer_get_aux_losses")) return rc;
+    if (step2) {
+        if (int rc = t_need_step(t, "oz_trainer_get_aux_losses")) return rc;
+        if (int rc = t_read(t, t->aux_losses, step2, 2)) return rc;
+    }
+    if (epoch2) { epoch2[0] = t->epoch_aux[0]; epoch2[1] = t->epoch_aux[1]; }
+    return OZ_OK;
+}
+OZ_API int oz_trainer_get_aux_head_grads(oz_trainer* t, int B, float* dopre, float* dspre, float* df2_before) {
+    OZ_REQUIRE(t && dopre && dspre && B >= 1 && B <= t->Bmax, "oz_trainer_get_aux_head_grads: bad argument");
+    T_LOCK(t);
+    if (int rc = t_need_aux(t, "oz_trainer_get_aux_head_grads")) return rc;
+    if (int rc = t_need_step(t, "oz_trainer_get_aux_head_grads")) return rc;
+    if (int rc = t_read(t, t->dopre, dopre, (int64_t)B * t->n * t->n)) return rc;
+    if (int rc = t_read(t, t->dspre, dspre, B)) return rc;
+    if (!df2_before) return OZ_OK;
+    if (!t->capture || !t->cap_valid || !(t->w_own > 0.f || t->w_sc > 0.f)) {
+        oz_set_error("oz_trainer_get_aux_head_grads: no captured step with an auxiliary weight on (oz_trainer_set_capture(t, 1), then a step)");
+        return OZ_ERR_STATE;
+    }
+    return t_read(t, t->cap_f2, df2_before, (int64_t)B * 512);
+}
 OZ_API int oz_trainer_get_plan(oz_trainer* t, int* plan, int n) {
     OZ_REQUIRE(t && plan && n == OZ_TRAINER_PLAN_ROWS * OZ_TRAINER_PLAN_FIELDS, "oz_trainer_get_plan: plan holds OZ_TRAINER_PLAN_ROWS x OZ_TRAINER_PLAN_FIELDS ints");
     T_LOCK(t);
@@ -2359,7 +2661,7 @@ OZ_API int oz_trainer_get_bn_stats(oz_trainer* t, int layer, float* mean, float*
     return t_read(t, t->rstd[layer], rstd, t->L[layer].Co);
 }
 OZ_API int oz_trainer_get_adam_state(oz_trainer* t, int index, float* m, float* v) {
-    OZ_REQUIRE(t && m && v && index >= 0 && index < 40, "oz_trainer_get_adam_state: bad argument");
+    OZ_REQUIRE(t && m && v && index >= 0 && index < t->nw, "oz_trainer_get_adam_state: bad argument");
     T_LOCK(t);
     OZ_REQUIRE(t->toff[index] >= 0, "oz_trainer_get_adam_state: array %d is a moving statistic, it has no moments", index);
     if (int rc = t_read(t, t->M1 + t->toff[index], m, t->size[index])) return rc;

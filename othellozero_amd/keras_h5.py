@@ -545,11 +545,15 @@ def write_h5(path, root_attrs, groups):
 # =====================================================================================================================
 # Keras weight-file layer on top
 # =====================================================================================================================
-def keras_layer_table(weights, model_index=0, network="ONN"):
+AUX_LAYERS = ("ownership", "score")     # the two Dense layers of the trainer's auxiliary heads, behind `v` in a file that carries them
+
+
+def keras_layer_table(weights, model_index=0, network="ONN", aux=None):
     """The `model.layers` of OthelloNN / BaseNN (Net/OthelloNN.py:42-54, Net/BaseNN.py:41-54) with Keras' automatic
     names, for the `model_index`-th such model built in a process (the reference builds several: main.py:275-300),
     paired with the 40 get_weights() arrays.  -> [(layer name, [(weight name, array)])], weightless layers included.
-    BaseNN has an unnamed Reshape after the input and another after `pi` where OthelloNN has `pi-reshaped`."""
+    BaseNN has an unnamed Reshape after the input and another after `pi` where OthelloNN has `pi-reshaped`.
+    aux: None or the four arrays of the auxiliary heads (Wown, bown, Wsc, bsc): two more Dense layers, `ownership` and `score`, at the end."""
     assert len(weights) == 40, "expected the 40 arrays of get_weights()"
     m = model_index
     sfx = lambda base, k: base if k == 0 else f"{base}_{k}"
@@ -567,6 +571,10 @@ def keras_layer_table(weights, model_index=0, network="ONN"):
                    (sfx("dropout", 2 * m + i), [])]
     layers += [take("pi", ("kernel:0", "bias:0")), (sfx("reshape", 2 * m + 1) if network == "BNN" else "pi-reshaped", []),
                take("v", ("kernel:0", "bias:0"))]
+    if aux is not None:
+        assert len(aux) == 4, "expected the four arrays of the auxiliary heads"
+        it = iter(aux)
+        layers += [take(name, ("kernel:0", "bias:0")) for name in AUX_LAYERS]
     return layers
 
 

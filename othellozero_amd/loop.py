@@ -433,8 +433,15 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
              root_noise=None, sample_moves=None, replay="host", evaluation_opponent="random", endgame_targets=0,
              solve_leaves=0, match_openings=None, evaluation_openings=None, playout_cap=None, forced_playouts=None, eval_symmetry=None,
              value_target="outcome", gumbel=None, surprise_weight=None, resign=None, validation_share=None, value_signs="reference", proofs=False,
-             proof_play=False, proof_targets=False, selection=None, tree_gc="off"):
+             proof_play=False, proof_targets=False, selection=None, tree_gc="off", aux_heads=None):
     """main.py:56-259 on the GPU engines; returns `historic` = [(episodes done, win rate vs random), ...]
+
+    aux_heads=dict(ownership=w, score=w) (None = off, the default: the loop is unchanged): KataGo's auxiliary targets from the end of the game.
+    The trainer gains an ownership and a score head (Trainer(aux_heads=...): who owns each square on the game's final board, and the final disc
+    margin, both for the mover; trained with the trunk, never used at play time), the device replay buffer keeps every example's final pair
+    (ReplayBuffer(aux=True): zero for the records of adjudicated games and for fast records), and the two losses are logged per iteration;
+    training.aux_history keeps them.  It needs replay="device", not distributed=True, and alias_final_boards=False for a two-plane network
+    (ValueError otherwise: _lib.check_aux_heads_loop).  Playing strength is neither gated nor claimed ("Auxiliary heads").
 
     validation_share=f in (0, 0.5] (None = off, the default: the loop is unchanged): held-out evaluation of every iteration's fit.  After an
     iteration's append, the newest floor(f * E) of the E examples that append wrote (trainer.holdout_slots) are held out of THAT iteration's fit
@@ -610,6 +617,12 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
     training.resign_history = []
     training.surprise_history = []
     training.validation_history = []
+    training.aux_history = []
+    aux_heads = _lib.check_aux_heads_loop(aux_heads, replay, distributed, alias_final_boards, getattr(neural_network, "in_channels", 2))
+    if aux_heads is not None:
+        if not hasattr(neural_network, "set_aux_heads"):
+            raise ValueError(f"aux_heads needs a network that trains auxiliary heads (NNetWrapper); {type(neural_network).__name__} has none")
+        neural_network.set_aux_heads(aux_heads)
     if validation_share is not None:
         if isinstance(validation_share, bool) or not isinstance(validation_share, (int, float)) or not 0.0 < validation_share <= 0.5:
             raise ValueError(f"validation_share must be None or a share in (0, 0.5] of an iteration's new examples (got {validation_share!r})")
@@ -717,7 +730,7 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
     device_replay = None
     if replay == "device":
         from .replay import ReplayBuffer
-        device_replay = ReplayBuffer(board_size, training_buffer_size)
+        device_replay = ReplayBuffer(board_size, training_buffer_size, aux=True) if aux_heads is not None else ReplayBuffer(board_size, training_buffer_size)
     old_neural_network = neural_network.copy()
     for i in range(1, num_iterations + 1):
         logging.info('[%d/%d] begin', i, num_iterations)
@@ -749,9 +762,13 @@ def training(board_size, num_iterations, num_episodes, num_simulations, degree_e
             restore_eval_symmetry()
             logging.info('[%d/%d] fit on the device buffer', i, num_iterations)
             if validation_share is not None:
-                _fit_with_holdout(i, num_iterations, neural_network, device_replay, total_before, validation_share)
+                hist = _fit_with_holdout(i, num_iterations, neural_network, device_replay, total_before, validation_share)
             else:
-                neural_network.train(device_replay, verbose=2 if logging.root.level <= logging.DEBUG else None)
+                hist = neural_network.train(device_replay, verbose=2 if logging.root.level <= logging.DEBUG else None)
+            if aux_heads is not None and hist is not None and hist.history.get("ownership_loss"):
+                training.aux_history.append({k: hist.history[k][-1] for k in ("ownership_loss", "score_loss")})
+                logging.info('[%d/%d] auxiliary heads: ownership_loss %.4f score_loss %.4f', i, num_iterations,
+                             hist.history["ownership_loss"][-1], hist.history["score_loss"][-1])
         else:
             if distributed:
                 first, count = shard_games(num_episodes, rank, world)

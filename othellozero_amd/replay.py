@@ -1,6 +1,6 @@
 """Device-resident replay buffer -- C ABI: oz_replay_*.
 
-`ReplayBuffer(board_size, capacity)` holds finished training examples in HBM, in the layout of the trainer's resident data set
+`ReplayBuffer(board_size, capacity, aux=False)` holds finished training examples in HBM, in the layout of the trainer's resident data set
 (own / opp bitboards, one float32 pi row, one float32 z per slot).  It is filled device to device from a `SelfPlayEngine`
 (`append_engine`), from move records the host holds (`append_records`: pooled records of a multi-GPU run, saved games) or from finished
 examples (`append_examples`), and `trainer.fit_replay` / `NNetWrapper.train(replay)` train from it in place: no example tuples, no
@@ -29,12 +29,15 @@ def _target(policy_target, target_temperature, engine=False):
 
 
 class ReplayBuffer:
-    def __init__(self, board_size, capacity):
-        """room for `capacity` examples (1 .. 2^31 - 1) of board_size x board_size boards on the current device: 24 + 4 n^2 bytes each"""
+    def __init__(self, board_size, capacity, aux=False):
+        """room for `capacity` examples (1 .. 2^31 - 1) of board_size x board_size boards on the current device: 24 + 4 n^2 bytes each.
+        aux=True: every slot also keeps its FINAL PAIR (fin_own, fin_opp: the game's final board from the mover's side under the example's
+        symmetry, 0 / 0 for "no auxiliary target"; 16 bytes more), the targets of a Trainer(..., aux_heads=...).  Every append fills it; the
+        four arrays of read() are what a plain buffer holds"""
         lib = _lib.require_gpu()
-        self.n = int(board_size)
+        self.n, self.aux = int(board_size), bool(aux)
         self._h = C.c_void_p()
-        _lib.check(lib.oz_replay_create(C.byref(self._h), self.n, int(capacity)))
+        _lib.check((lib.oz_replay_create_aux if self.aux else lib.oz_replay_create)(C.byref(self._h), self.n, int(capacity)))
 
     def __del__(self):
         try:
@@ -133,14 +136,23 @@ class ReplayBuffer:
                                                         rec.size, 1 if alias_final else 0, target, T))
         return int((_lib.record_fast(rec) == 0).sum())
 
-    def append_examples(self, own, opp, pi, z):
-        """finished examples in the given order: own / opp uint64 (N,), pi float32 (N, n*n), z float32 (N,) -- what read() returns"""
+    def append_examples(self, own, opp, pi, z, fin_own=None, fin_opp=None):
+        """finished examples in the given order: own / opp uint64 (N,), pi float32 (N, n*n), z float32 (N,) -- what read() returns.
+        fin_own / fin_opp uint64 (N,): their final pairs (read_aux()); without them a buffer with aux=True stores zero pairs, and a plain
+        buffer ignores them"""
         own = np.ascontiguousarray(own, dtype=np.uint64).ravel()
         opp = np.ascontiguousarray(opp, dtype=np.uint64).ravel()
         N = own.size
         pi = np.ascontiguousarray(pi, dtype=np.float32).reshape(N, self.n * self.n)
         z = np.ascontiguousarray(z, dtype=np.float32).reshape(N)
         assert opp.size == N, (opp.size, N)
+        if fin_own is not None:
+            fo = np.ascontiguousarray(fin_own, dtype=np.uint64).ravel()
+            fp = np.ascontiguousarray(fin_opp, dtype=np.uint64).ravel()
+            assert fo.size == N and fp.size == N, (fo.size, fp.size, N)
+            _lib.check(_lib.load().oz_replay_append_examples_aux(self._h, _lib.p_u64(own), _lib.p_u64(opp), _lib.p_f32(pi), _lib.p_f32(z),
+                                                                 _lib.p_u64(fo), _lib.p_u64(fp), N))
+            return
         _lib.check(_lib.load().oz_replay_append_examples(self._h, _lib.p_u64(own), _lib.p_u64(opp), _lib.p_f32(pi), _lib.p_f32(z), N))
 
     def read(self, first=0, count=None):
@@ -153,24 +165,41 @@ class ReplayBuffer:
         _lib.check(_lib.load().oz_replay_read(self._h, first, count, _lib.p_u64(own), _lib.p_u64(opp), _lib.p_f32(pi), _lib.p_f32(z)))
         return own, opp, pi, z
 
+    def read_aux(self, first=0, count=None):
+        """the final pairs of slots [first, first + count) (default: every held slot from `first` on) -> (fin_own, fin_opp) uint64; a buffer
+        with aux=True only (OzError OZ_ERR_STATE otherwise)"""
+        first = int(first)
+        count = len(self) - first if count is None else int(count)
+        k = max(count, 0)
+        fo, fp = np.zeros(k, np.uint64), np.zeros(k, np.uint64)
+        _lib.check(_lib.load().oz_replay_read_aux(self._h, first, count, _lib.p_u64(fo), _lib.p_u64(fp)))
+        return fo, fp
+
     def save(self, path):
-        """one .npz: the held examples in AGE order (oldest first) plus board size, capacity and total"""
+        """one .npz: the held examples in AGE order (oldest first) plus board size, capacity and total; a buffer with aux=True adds the
+        arrays fin_own / fin_opp"""
         held, cap, total = self.info()
         own, opp, pi, z = self.read(0, held)
         age = (np.arange(total - held, total) % cap).astype(np.int64)          # slot of the i-th oldest held example
+        extra = {}
+        if self.aux:
+            fo, fp = self.read_aux(0, held)
+            extra = dict(fin_own=fo[age], fin_opp=fp[age])
         with open(path, "wb") as f:
             np.savez(f, own=own[age], opp=opp[age], pi=pi[age], z=z[age], board_size=np.int64(self.n), capacity=np.int64(cap),
-                     total=np.int64(total))
+                     total=np.int64(total), **extra)
 
     @classmethod
-    def load(cls, path, capacity=None):
+    def load(cls, path, capacity=None, aux=False):
         """a buffer with the slot layout, contents and `total` of the saved one.  capacity: the saved one's unless given -- a smaller one
         keeps the newest examples; a larger one than a buffer that had already wrapped restarts the running index at the number kept
-        (the overwritten examples are gone)"""
+        (the overwritten examples are gone).  aux=True: a buffer that keeps the final pairs -- the file's, or zero pairs for a file saved
+        without them; aux=False ignores the file's pairs"""
         with np.load(path, allow_pickle=False) as f:
             own, opp, pi, z = (np.ascontiguousarray(f[k]) for k in ("own", "opp", "pi", "z"))
             n, cap, total = int(f["board_size"]), int(f["capacity"]), int(f["total"])
-        buf = cls(n, cap if capacity is None else capacity)
+            fin = (np.ascontiguousarray(f["fin_own"]), np.ascontiguousarray(f["fin_opp"])) if aux and "fin_own" in f.files else None
+        buf = cls(n, cap if capacity is None else capacity, aux=True) if aux else cls(n, cap if capacity is None else capacity)
         keep = min(own.size, buf.capacity)
         if keep < min(total, buf.capacity):
             total = keep
@@ -179,5 +208,11 @@ class ReplayBuffer:
         opp = np.ascontiguousarray(opp[first:], dtype=np.uint64)
         pi = np.ascontiguousarray(pi.reshape(-1, n * n)[first:], dtype=np.float32)
         z = np.ascontiguousarray(z[first:], dtype=np.float32)
+        if fin is not None:
+            fo = np.ascontiguousarray(fin[0][first:], dtype=np.uint64)
+            fp = np.ascontiguousarray(fin[1][first:], dtype=np.uint64)
+            _lib.check(_lib.load().oz_replay_restore_aux(buf._h, _lib.p_u64(own), _lib.p_u64(opp), _lib.p_f32(pi), _lib.p_f32(z), _lib.p_u64(fo),
+                                                         _lib.p_u64(fp), keep, total))
+            return buf
         _lib.check(_lib.load().oz_replay_restore(buf._h, _lib.p_u64(own), _lib.p_u64(opp), _lib.p_f32(pi), _lib.p_f32(z), keep, total))
         return buf

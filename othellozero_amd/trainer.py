@@ -13,6 +13,8 @@ from . import _lib
 from .weights import onn_shapes
 
 TRAINABLE = [i for i in range(40) if i >= 36 or i % 6 not in (4, 5)]
+AUX_ARRAYS = (40, 41, 42, 43)          # get_weights() indices of the auxiliary heads: Wown (512, n*n), bown (n*n,), Wsc (512, 1), bsc (1,)
+AUX_KEYS = ("ownership_loss", "score_loss")      # History.history gains these two with the auxiliary heads on
 PRECISION_MODES = {"f32": 0, "f16x2": 1, "bf16x3": 2}      # oz_trainer_set_precision
 POLICY_LOSSES = {"rows": _lib.POLICY_LOSS_ROWS, "flat": _lib.POLICY_LOSS_FLAT}      # oz_trainer_set_policy_loss
 
@@ -21,8 +23,10 @@ class History:
     """what keras Model.fit returns, as far as the reference uses it (main.py:108: kept, never read).  `lr` / `grad_norm`: the scheduled rate and the
     gradient's global norm (None with global_clipnorm off) of each epoch's LAST step -- attributes, Keras' history holds the three losses only"""
 
-    def __init__(self):
+    def __init__(self, aux=False):
         self.history = {"loss": [], "pi-reshaped_loss": [], "v_loss": []}
+        if aux:
+            self.history.update({k: [] for k in AUX_KEYS})
         self.epoch = []
         self.lr, self.grad_norm = [], []
 
@@ -50,6 +54,12 @@ def make_optimizer(l2=0.0, weight_decay=0.0, decay_mask=None, global_clipnorm=0.
     return o
 
 
+def aux_shapes(board_size):
+    """shapes of the four arrays of the auxiliary heads, get_weights() indices 40 .. 43"""
+    A = board_size * board_size
+    return [(512, A), (A,), (512, 1), (1,)]
+
+
 def lr_schedule_at(lr, step, schedule=None, **options):
     """lr_s of optimiser step `step` (1-based) under `schedule` (oz_lr_schedule_at: the library's one definition; no GPU needed)"""
     out = C.c_double()
@@ -59,8 +69,11 @@ def lr_schedule_at(lr, step, schedule=None, **options):
 
 class Trainer:
     def __init__(self, board_size=8, channels=512, in_channels=2, max_batch=32, lr=1e-3, clipvalue=0.5, dropout=0.3,
-                 bn_momentum=0.99, seed=0, external_grads_ptr=None, precision="f32", policy_loss="rows", optimizer=None):
+                 bn_momentum=0.99, seed=0, external_grads_ptr=None, precision="f32", policy_loss="rows", optimizer=None, aux_heads=None):
         """optimizer: None or a dict of set_optimizer's keyword arguments
+        aux_heads: None or dict(ownership=w, score=w) -- an ownership and a score head trained on the games' final boards beside the policy and
+        value heads (oz_trainer_set_aux_heads): four more arrays behind the forty, two more losses; fed through forward_backward / set_dataset's
+        fin_own / fin_opp or a ReplayBuffer(aux=True)
         precision: arithmetic of the 3x3 layers -- "f32" (fp32 matrix cores), "f16x2" (forward / data-gradient GEMMs: fp32 values
         as two fp16 planes on the fp16 matrix cores, per-step power-of-two scaling and a range guard; channels % 256 == 0) or "bf16x3"
         (forward, data gradient and weight gradient: every fp32 value exactly as three bf16 planes on the bf16 matrix cores, no scaling,
@@ -69,6 +82,10 @@ class Trainer:
         averaged); "flat" -- on the whole (n*n,) softmax, the loss for dense visit-distribution targets"""
         assert precision in PRECISION_MODES, precision
         assert policy_loss in POLICY_LOSSES, policy_loss
+        aux = _lib.check_aux_heads(aux_heads)
+        if aux is not None and external_grads_ptr:
+            raise ValueError("aux_heads is not offered with external_grads_ptr (a data-parallel fit): the external gradient arena is sized for the "
+                             "forty arrays -- the heads' four gradients would be written past its end -- and the pooled rows carry no final pairs")
         lib = _lib.require_gpu()
         self.n, self.channels, self.in_channels, self.max_batch = board_size, channels, in_channels, int(max_batch)
         self._h = C.c_void_p()
@@ -82,6 +99,10 @@ class Trainer:
         self.policy_loss = policy_loss
         if policy_loss != "rows":
             _lib.check(lib.oz_trainer_set_policy_loss(self._h, POLICY_LOSSES[policy_loss]))
+        self.aux = aux is not None
+        if self.aux:
+            _lib.check(lib.oz_trainer_set_aux_heads(self._h, aux[0], aux[1]))
+            self.shapes = list(self.shapes) + aux_shapes(board_size)
         if optimizer:
             self.set_optimizer(**optimizer)
 
@@ -94,22 +115,24 @@ class Trainer:
             pass
 
     @staticmethod
-    def arena_size(board_size, channels, in_channels=2):
-        n = C.c_int64()
-        _lib.check(_lib.load().oz_trainer_arena_size(board_size, channels, in_channels, C.byref(n)))
+    def arena_size(board_size, channels, in_channels=2, aux=False):
+        """floats of the parameter / gradient / Adam arenas (aux: of a trainer with the auxiliary heads)"""
+        n, lib = C.c_int64(), _lib.load()
+        _lib.check((lib.oz_trainer_arena_size_aux if aux else lib.oz_trainer_arena_size)(board_size, channels, in_channels, C.byref(n)))
         return n.value
 
     def set_weights(self, weights):
+        """the 40 arrays (the auxiliary heads, if any, keep theirs) or, with the auxiliary heads, all 44"""
         lib = _lib.load()
-        assert len(weights) == 40
+        assert len(weights) in (40, len(self.shapes)), len(weights)
         for i, (w, shp) in enumerate(zip(weights, self.shapes)):
             a = np.ascontiguousarray(w, dtype=np.float32)
             assert a.shape == tuple(shp), f"weight {i}: shape {a.shape} != {shp}"
             _lib.check(lib.oz_trainer_set_weight(self._h, i, _lib.p_f32(a), a.size))
 
     def get_weights(self, average=False):
-        """the 40 arrays; average=True: the weight average E in place of every trainable array (the BN moving statistics as they are);
-        OzError(OZ_ERR_STATE) with average_decay off"""
+        """the 40 arrays (44 with the auxiliary heads); average=True: the weight average E in place of every trainable array (the BN moving
+        statistics as they are); OzError(OZ_ERR_STATE) with average_decay off"""
         lib, out = _lib.load(), []
         get = lib.oz_trainer_get_weight_average if average else lib.oz_trainer_get_weight
         for i, shp in enumerate(self.shapes):
@@ -161,7 +184,7 @@ class Trainer:
     def get_grads(self):
         """{index: gradient} of the trainable arrays after forward_backward"""
         lib, out = _lib.load(), {}
-        for i in TRAINABLE:
+        for i in TRAINABLE + (list(AUX_ARRAYS) if self.aux else []):
             a = np.zeros(self.shapes[i], dtype=np.float32)
             _lib.check(lib.oz_trainer_get_grad(self._h, i, _lib.p_f32(a), a.size))
             out[i] = a
@@ -178,24 +201,75 @@ class Trainer:
         _lib.check(_lib.load().oz_trainer_grad_arena(self._h, C.byref(ptr), C.byref(n)))
         return ptr.value, n.value
 
-    def forward_backward(self, own, opp, pi_target, z_target):
-        """-> (loss, pi loss, v loss) of the batch; gradients of the batch-mean loss are left in the arena"""
+    def _fin(self, fin_own, fin_opp, count):
+        """the examples' final pairs as two uint64 arrays, or None without them"""
+        if fin_own is None and fin_opp is None:
+            return None
+        assert self.aux, "fin_own / fin_opp feed the auxiliary heads: Trainer(..., aux_heads=dict(ownership=w, score=w))"
+        fo = np.ascontiguousarray(fin_own, dtype=np.uint64).ravel()
+        fp = np.ascontiguousarray(fin_opp, dtype=np.uint64).ravel()
+        assert fo.size == count and fp.size == count, (fo.size, fp.size, count)
+        return fo, fp
+
+    def forward_backward(self, own, opp, pi_target, z_target, fin_own=None, fin_opp=None):
+        """-> (loss, pi loss, v loss) of the batch; gradients of the batch-mean loss are left in the arena.  With the auxiliary heads:
+        -> (loss, pi loss, v loss, ownership loss, score loss); fin_own / fin_opp: the examples' final pairs (rules_aux_targets; without them
+        every mask is 0)"""
         own = np.ascontiguousarray(own, dtype=np.uint64).ravel()
         opp = np.ascontiguousarray(opp, dtype=np.uint64).ravel()
         B = own.size
         pit = np.ascontiguousarray(pi_target, dtype=np.float32).reshape(B, self.n * self.n)
         zt = np.ascontiguousarray(z_target, dtype=np.float32).reshape(B)
-        losses = np.zeros(3, np.float32)
-        _lib.check(_lib.load().oz_trainer_forward_backward(self._h, _lib.p_u64(own), _lib.p_u64(opp), _lib.p_f32(pit),
-                                                           _lib.p_f32(zt), B, _lib.p_f32(losses)))
-        return float(losses[0]), float(losses[1]), float(losses[2])
+        fin = self._fin(fin_own, fin_opp, B)
+        losses = np.zeros(5, np.float32)
+        if fin is not None:
+            _lib.check(_lib.load().oz_trainer_forward_backward_aux(self._h, _lib.p_u64(own), _lib.p_u64(opp), _lib.p_f32(pit), _lib.p_f32(zt),
+                                                                   _lib.p_u64(fin[0]), _lib.p_u64(fin[1]), B, _lib.p_f32(losses)))
+        else:
+            _lib.check(_lib.load().oz_trainer_forward_backward(self._h, _lib.p_u64(own), _lib.p_u64(opp), _lib.p_f32(pit),
+                                                               _lib.p_f32(zt), B, _lib.p_f32(losses)))
+            if self.aux:
+                losses[3:] = self.aux_losses()
+        return tuple(float(x) for x in losses[:5 if self.aux else 3])
 
-    def set_dataset(self, own, opp, pi, z):
-        """upload the examples of a fit once; they stay in HBM until the next set_dataset"""
+    def set_dataset(self, own, opp, pi, z, fin_own=None, fin_opp=None):
+        """upload the examples of a fit once; they stay in HBM until the next set_dataset.  fin_own / fin_opp: their final pairs for the
+        auxiliary heads (without them every mask is 0)"""
         own = np.ascontiguousarray(own, dtype=np.uint64); opp = np.ascontiguousarray(opp, dtype=np.uint64)
         pi = np.ascontiguousarray(pi, dtype=np.float32).reshape(own.size, self.n * self.n)
         z = np.ascontiguousarray(z, dtype=np.float32)
+        fin = self._fin(fin_own, fin_opp, own.size)
+        if fin is not None:
+            _lib.check(_lib.load().oz_trainer_set_dataset_aux(self._h, _lib.p_u64(own), _lib.p_u64(opp), _lib.p_f32(pi), _lib.p_f32(z),
+                                                              _lib.p_u64(fin[0]), _lib.p_u64(fin[1]), own.size))
+            return
         _lib.check(_lib.load().oz_trainer_set_dataset(self._h, _lib.p_u64(own), _lib.p_u64(opp), _lib.p_f32(pi), _lib.p_f32(z), own.size))
+
+    # ---- auxiliary heads: read-outs of the last step / epoch
+    def aux_outputs(self, B):
+        """(ownership (B, n*n) in [-1, 1] for the mover, score (B,)) of the last forward pass"""
+        o, s = np.zeros((B, self.n * self.n), np.float32), np.zeros(B, np.float32)
+        _lib.check(_lib.load().oz_trainer_aux_outputs(self._h, B, _lib.p_f32(o), _lib.p_f32(s)))
+        return o, s
+
+    def aux_losses(self, epoch=False):
+        """(ownership loss, score loss): the last step's batch means (float32), or with epoch=True the float64 sample-weighted means of the last
+        fit_epoch / fit_epoch_replay call"""
+        if epoch:
+            out = np.zeros(2, np.float64)
+            _lib.check(_lib.load().oz_trainer_get_aux_losses(self._h, None, _lib.p_f64(out)))
+        else:
+            out = np.zeros(2, np.float32)
+            _lib.check(_lib.load().oz_trainer_get_aux_losses(self._h, _lib.p_f32(out), None))
+        return out
+
+    def aux_head_grads(self, B, before=False):
+        """(dopre (B, n*n), dspre (B,)) of the last step: the gradients wrt the two heads' pre-activations, loss weights included; before=True
+        adds the gradient wrt f2 (B, 512) as the policy and value heads left it, before the auxiliary term (needs set_capture(True))"""
+        do, ds = np.zeros((B, self.n * self.n), np.float32), np.zeros(B, np.float32)
+        d0 = np.zeros((B, 512), np.float32) if before else None
+        _lib.check(_lib.load().oz_trainer_get_aux_head_grads(self._h, B, _lib.p_f32(do), _lib.p_f32(ds), _lib.p_f32(d0) if before else None))
+        return (do, ds, d0) if before else (do, ds)
 
     def fit_epoch(self, order, batch_size):
         """the optimiser steps of one epoch over the resident examples in `order` (batches of batch_size, last one short);
@@ -372,9 +446,12 @@ def holdout_slots(held, capacity, total, new_examples, share):
     return np.flatnonzero(keep).astype(np.int32), val
 
 
-def _record_epoch(hist, ep, epochs, means, verbose, trainer=None, val=None):
+def _record_epoch(hist, ep, epochs, means, verbose, trainer=None, val=None, aux_means=None):
     for k, mean in zip(("loss", "pi-reshaped_loss", "v_loss"), means):
         hist.history[k].append(float(mean))
+    if aux_means is not None:
+        for k, mean in zip(AUX_KEYS, aux_means):
+            hist.history[k].append(float(mean))
     if val is not None:
         for k in VAL_KEYS:
             hist.history.setdefault("val_" + k, []).append(float(val[k]))
@@ -386,6 +463,7 @@ def _record_epoch(hist, ep, epochs, means, verbose, trainer=None, val=None):
     if verbose:
         print(f"Epoch {ep + 1}/{epochs} - loss: {hist.history['loss'][-1]:.4f} - pi-reshaped_loss: "
               f"{hist.history['pi-reshaped_loss'][-1]:.4f} - v_loss: {hist.history['v_loss'][-1]:.4f}"
+              + ("" if aux_means is None else "".join(f" - {k}: {m:.4f}" for k, m in zip(AUX_KEYS, aux_means)))
               + ("" if val is None else "".join(f" - val_{k}: {val[k]:.4f}" for k in VAL_KEYS)))
 
 
@@ -398,7 +476,10 @@ def fit_replay(trainer, replay, batch_size=32, epochs=10, shuffle_seed=0, verbos
     order train_slots[RandomState(shuffle_seed + ep).permutation(len(train_slots))], and after every epoch the held-out slots are evaluated in
     inference mode (Trainer.evaluate_replay): History.history gains val_loss, val_pi-reshaped_loss, val_v_loss, val_policy_top1, val_value_sign."""
     N = len(replay)
-    hist = History()
+    aux = bool(getattr(trainer, "aux", False))
+    if aux and not getattr(replay, "aux", False):
+        raise ValueError("fit_replay: a trainer with auxiliary heads needs a replay buffer that keeps the final pairs: ReplayBuffer(..., aux=True)")
+    hist = History(aux)
     train_slots = None
     if validation_slots is not None:
         validation_slots = np.ascontiguousarray(validation_slots, dtype=np.int32).ravel()
@@ -412,12 +493,13 @@ def fit_replay(trainer, replay, batch_size=32, epochs=10, shuffle_seed=0, verbos
             order = train_slots[order]
         means = np.asarray(trainer.fit_epoch_replay(replay, order, batch_size), dtype=np.float64)
         val = trainer.evaluate_replay(replay, validation_slots, batch_size) if validation_slots is not None and validation_slots.size else None
-        _record_epoch(hist, ep, epochs, means, verbose, trainer, val)
+        _record_epoch(hist, ep, epochs, means, verbose, trainer, val, trainer.aux_losses(epoch=True) if aux else None)
     trainer.sync()
     return hist
 
 
-def fit(trainer, own, opp, pi, z, batch_size=32, epochs=10, shuffle_seed=0, allreduce=None, verbose=None, resident=None, validation=None):
+def fit(trainer, own, opp, pi, z, batch_size=32, epochs=10, shuffle_seed=0, allreduce=None, verbose=None, resident=None, validation=None,
+        fin_own=None, fin_opp=None):
     """keras Model.fit(x, y, batch_size, epochs) with shuffle=True (the default the reference relies on).
     `allreduce(trainer)` -- if given -- averages the gradient arena across ranks between backward and apply.
 
@@ -429,29 +511,46 @@ def fit(trainer, own, opp, pi, z, batch_size=32, epochs=10, shuffle_seed=0, allr
 
     validation (None: as ever): (own, opp, pi, z) of held-out examples, evaluated in inference mode after every epoch (Trainer.evaluate: moving BN
     statistics, no dropout); History.history gains val_loss, val_pi-reshaped_loss, val_v_loss, val_policy_top1, val_value_sign (Keras' names).
-    With an all-reduce each rank evaluates its own validation examples: no collective is added."""
+    With an all-reduce each rank evaluates its own validation examples: no collective is added.
+
+    fin_own / fin_opp (a trainer with auxiliary heads): the examples' final pairs; History.history gains ownership_loss and score_loss,
+    accumulated per epoch in float64 in example order like the three losses.  Without them such a trainer trains with every mask 0."""
     N = len(z)
-    hist = History()
+    aux = bool(getattr(trainer, "aux", False))
+    assert aux or (fin_own is None and fin_opp is None), "fin_own / fin_opp feed the auxiliary heads (Trainer(..., aux_heads=...))"
+    fin = None
+    if fin_own is not None:
+        fin = (np.ascontiguousarray(fin_own, dtype=np.uint64).ravel(), np.ascontiguousarray(fin_opp, dtype=np.uint64).ravel())
+    hist = History(aux)
     if resident is None:
         resident = allreduce is None
     assert not (resident and allreduce is not None), "the resident path has no room for a per-step all-reduce"
     if resident:
-        trainer.set_dataset(own, opp, pi, z)
+        if fin is not None:
+            trainer.set_dataset(own, opp, pi, z, fin[0], fin[1])
+        else:
+            trainer.set_dataset(own, opp, pi, z)
     for ep in range(epochs):
         order = np.random.RandomState(shuffle_seed + ep).permutation(N)
+        aux_means = None
         if resident:
             means = np.asarray(trainer.fit_epoch(order, batch_size), dtype=np.float64)
+            if aux:
+                aux_means = trainer.aux_losses(epoch=True)
         else:
-            tot, seen = np.zeros(3), 0
+            tot, seen = np.zeros(5 if aux else 3), 0
             for s in range(0, N, batch_size):
                 idx = order[s:s + batch_size]
                 failed = None
                 try:
-                    losses = trainer.forward_backward(own[idx], opp[idx], pi[idx], z[idx])
+                    if fin is not None:
+                        losses = trainer.forward_backward(own[idx], opp[idx], pi[idx], z[idx], fin[0][idx], fin[1][idx])
+                    else:
+                        losses = trainer.forward_backward(own[idx], opp[idx], pi[idx], z[idx])
                 except Exception as e:                           # the f16x2 range guard, a bad batch shape, an out-of-memory: this rank's step is invalid
                     if allreduce is None:
                         raise
-                    failed, losses = e, np.zeros(3)
+                    failed, losses = e, np.zeros(5 if aux else 3)
                 if allreduce is not None:
                     # a rank that failed still joins the collective (with a poisoned arena), so no peer blocks in the all-reduce and
                     # EVERY rank raises together
@@ -460,7 +559,9 @@ def fit(trainer, own, opp, pi, z, batch_size=32, epochs=10, shuffle_seed=0, allr
                 tot += np.asarray(losses) * len(idx)            # keras reports the sample-weighted running mean
                 seen += len(idx)
             means = tot / max(seen, 1)
+            if aux:
+                means, aux_means = means[:3], means[3:]
         val = trainer.evaluate(*validation, batch_size=batch_size) if validation is not None and len(validation[3]) else None
-        _record_epoch(hist, ep, epochs, means, verbose, trainer, val)
+        _record_epoch(hist, ep, epochs, means, verbose, trainer, val, aux_means)
     trainer.sync()
     return hist
