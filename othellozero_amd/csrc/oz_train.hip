@@ -252,9 +252,58 @@ __global__ __launch_bounds__(256) void k_t_bn_infer(const float* __restrict__ z,
     *reinterpret_cast<f32x4*>(a + i) = out;
 }
 // ---------------------------------------------------------------- heads: forward, losses, gradient wrt f2
-// one 64-thread block per sample (A = n*n <= 64 policy outputs, lane = action)
+// The two matvecs of a head pair on one sample's f2 row x[512], one 64-lane wave per sample; k_t_heads, k_t_eval_heads and k_t_aux_heads all
+// run these bodies, so their sums have one order.
+// t_head_cols: lane a's column of W[512][A], sum_k x[k] W[k][a] (lanes >= A read column 0; the caller adds the bias and drops them).
+// 64 weight rows in flight per batch (buffer loads: one per-lane offset register + a scalar row offset each), the fmaf chain stays in k order:
+// the loop is a chain of L2 round trips, 32 of them with 16 rows in flight = 19 us per launch at the reference's batch (round 5)
+__device__ __forceinline__ float t_head_cols(const float* __restrict__ x, const float* __restrict__ W, int A, int lane) {
+    const auto wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(W), 0, 512 * A * 4, 0x00020000);
+    const int lo = (lane < A ? lane : 0) * 4;
+    float acc = 0.f;
+#pragma unroll 1
+    for (int k0 = 0; k0 < 512; k0 += 64) {
+        float wv[64];
+#pragma unroll
+        for (int j = 0; j < 64; ++j) wv[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(wrs, lo, (k0 + j) * A * 4, 0));
+#pragma unroll
+        for (int j = 0; j < 64; ++j) acc = fmaf(x[k0 + j], wv[j], acc);
+    }
+    return acc;
+}
+// t_head_dot: x . w[512] for the scalar head, every lane a strided fmaf chain, then the xor-shuffle tree (every lane holds the sum)
+__device__ __forceinline__ float t_head_dot(const float* __restrict__ x, const float* __restrict__ w, int lane) {
+    float acc = 0.f;
+    for (int k = lane; k < 512; k += 64) acc = fmaf(x[k], w[k], acc);
+    for (int o = 32; o; o >>= 1) acc += __shfl_xor(acc, o);
+    return acc;
+}
+// The policy loss of one sample from its logits (lane = action, -inf on lanes >= A): softmax p, the renormalised q = p / S, the clipped cross
+// entropy summed over the lanes.  k_t_heads adds the gradient, k_t_eval_heads the arg-max metrics.
 // flat = 0 (OZ_POLICY_LOSS_ROWS): the reference's loss on the (n, n) view, every row renormalised and the rows averaged;
 // flat = 1 (OZ_POLICY_LOSS_FLAT): the same clipped cross entropy with ONE group of A lanes -- whole-board sums, no mean over rows
+struct TPolicyLoss { float p, t, S, q, lpi; int row, width; };     // lpi: the sum over the lanes (ROWS: the caller divides by n)
+__device__ __forceinline__ TPolicyLoss t_policy_loss(float logit, const float* __restrict__ pit_b /*[A]*/, int n, int A, int flat, int lane) {
+    TPolicyLoss r;
+    float mx = logit;
+    for (int o = 32; o; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    const float e = lane < A ? expf(logit - mx) : 0.f;
+    float se = e;
+    for (int o = 32; o; o >>= 1) se += __shfl_xor(se, o);
+    r.p = e / se;
+    // row-normalised, clipped cross entropy on the (n, n) view; the lanes of one board row are n consecutive lanes
+    // (every lane runs the shuffles; lanes >= A read a clamped source and their results are unused).  flat: one group of A lanes
+    r.row = flat ? 0 : lane / n; r.width = flat ? A : n;
+    r.t = lane < A ? pit_b[lane] : 0.f;
+    r.S = 0.f;
+    for (int c = 0; c < r.width; ++c) { const int src = r.row * n + c; r.S += __shfl(r.p, src < 63 ? src : 63); }
+    r.q = lane < A ? r.p / r.S : 0.5f;
+    const float qc = fminf(fmaxf(r.q, 1e-7f), 1.0f - 1e-7f);
+    r.lpi = lane < A ? -r.t * logf(qc) : 0.f;
+    for (int o = 32; o; o >>= 1) r.lpi += __shfl_xor(r.lpi, o);
+    return r;
+}
+// one 64-thread block per sample (A = n*n <= 64 policy outputs, lane = action)
 __global__ __launch_bounds__(64) void k_t_heads(const float* __restrict__ f2 /*[B][512]*/, const int* __restrict__ d_count, int n, int flat,
                                                 const float* __restrict__ Wpi /*[512][A]*/, const float* __restrict__ bpi,
                                                 const float* __restrict__ Wv /*[512]*/, const float* __restrict__ bv,
@@ -265,48 +314,18 @@ __global__ __launch_bounds__(64) void k_t_heads(const float* __restrict__ f2 /*[
     const int b = blockIdx.x, lane = threadIdx.x, A = n * n, B = *d_count;
     if (b >= B) return;
     const float* x = f2 + (size_t)b * 512;
-    float logit = -INFINITY, vacc = 0.f;
-    {
-        // 64 weight rows in flight per batch (buffer loads: one per-lane offset register + a scalar row offset each), the fmaf chain stays in k order:
-        // the loop is a chain of L2 round trips, 32 of them with 16 rows in flight = 19 us per launch at the reference's batch (round 5)
-        const auto wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Wpi), 0, 512 * A * 4, 0x00020000);
-        const int lo = (lane < A ? lane : 0) * 4;
-        float acc = 0.f;
-#pragma unroll 1
-        for (int k0 = 0; k0 < 512; k0 += 64) {
-            float wv[64];
-#pragma unroll
-            for (int j = 0; j < 64; ++j) wv[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(wrs, lo, (k0 + j) * A * 4, 0));
-#pragma unroll
-            for (int j = 0; j < 64; ++j) acc = fmaf(x[k0 + j], wv[j], acc);
-        }
-        if (lane < A) logit = acc + bpi[lane];
-    }
-    for (int k = lane; k < 512; k += 64) vacc = fmaf(x[k], Wv[k], vacc);
-    for (int o = 32; o; o >>= 1) vacc += __shfl_xor(vacc, o);
-    float mx = logit;
-    for (int o = 32; o; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-    const float e = lane < A ? expf(logit - mx) : 0.f;
-    float se = e;
-    for (int o = 32; o; o >>= 1) se += __shfl_xor(se, o);
-    const float p = e / se;
+    const float acc = t_head_cols(x, Wpi, A, lane);
+    const float logit = lane < A ? acc + bpi[lane] : -INFINITY;
+    const float vacc = t_head_dot(x, Wv, lane);
+    const TPolicyLoss pl = t_policy_loss(logit, pit + (size_t)b * A, n, A, flat, lane);
+    const float p = pl.p, t = pl.t, S = pl.S, q = pl.q, lpi = pl.lpi;
     const float v = tanhf(vacc + bv[0]);
-    // row-normalised, clipped cross entropy on the (n, n) view; the lanes of one board row are n consecutive lanes
-    // (every lane runs the shuffles; lanes >= A read a clamped source and their results are unused).  flat: one group of A lanes
-    const int row = flat ? 0 : lane / n, width = flat ? A : n;
-    const float t = lane < A ? pit[(size_t)b * A + lane] : 0.f;
-    float S = 0.f;
-    for (int c = 0; c < width; ++c) { const int src = row * n + c; S += __shfl(p, src < 63 ? src : 63); }
-    const float q = lane < A ? p / S : 0.5f;
-    const bool inside = q >= 1e-7f && q <= 1.0f - 1e-7f;
-    const float qc = fminf(fmaxf(q, 1e-7f), 1.0f - 1e-7f);
-    float lpi = lane < A ? -t * logf(qc) : 0.f;
-    for (int o = 32; o; o >>= 1) lpi += __shfl_xor(lpi, o);
     // dL/dq = -t/q inside the clip range (0 outside); q = p / S  =>  dL/dp_j = g_j / S - (sum_{c in row} g_c q_c) / S
+    const bool inside = q >= 1e-7f && q <= 1.0f - 1e-7f;
     const float gq = (lane < A && inside) ? -t / q : 0.f;
     const float gqq = gq * q;
     float rowdot = 0.f;
-    for (int c = 0; c < width; ++c) { const int src = row * n + c; rowdot += __shfl(gqq, src < 63 ? src : 63); }
+    for (int c = 0; c < pl.width; ++c) { const int src = pl.row * n + c; rowdot += __shfl(gqq, src < 63 ? src : 63); }
     const float normp = flat ? 1.0f / (float)B : 1.0f / ((float)B * (float)n);
     const float gp = lane < A ? (gq - rowdot) / S * normp : 0.f;
     // softmax backward: dlogit_j = p_j (gp_j - sum_k gp_k p_k)
@@ -325,7 +344,7 @@ __global__ __launch_bounds__(64) void k_t_heads(const float* __restrict__ f2 /*[
     }
 }
 // ---------------------------------------------------------------- held-out evaluation: heads without gradients, per-example metrics
-// k_t_heads' forward (the same logits, softmax, tanh and clipped cross entropy, flat as there) with no gradient stores; per example one row of
+// k_t_heads' forward (t_head_cols, t_head_dot and t_policy_loss as there, flat as there) with no gradient stores; per example one row of
 // OZ_EVAL_ROW floats: [0] the policy loss of the mode, [1] (v - z)^2, [2] arg-max of p == arg-max of the target (lowest index among equal
 // maxima on both sides), [3] v z > 0, [4] z != 0
 #define OZ_EVAL_ROW 5
@@ -346,38 +365,12 @@ __global__ __launch_bounds__(64) void k_t_eval_heads(const float* __restrict__ f
     const int b = blockIdx.x, lane = threadIdx.x, A = n * n, B = *d_count;
     if (b >= B) return;
     const float* x = f2 + (size_t)b * 512;
-    float logit = -INFINITY, vacc = 0.f;
-    {   // (the weight loads of k_t_heads: 64 rows in flight, the fmaf chain in k order)
-        const auto wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Wpi), 0, 512 * A * 4, 0x00020000);
-        const int lo = (lane < A ? lane : 0) * 4;
-        float acc = 0.f;
-#pragma unroll 1
-        for (int k0 = 0; k0 < 512; k0 += 64) {
-            float wv[64];
-#pragma unroll
-            for (int j = 0; j < 64; ++j) wv[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(wrs, lo, (k0 + j) * A * 4, 0));
-#pragma unroll
-            for (int j = 0; j < 64; ++j) acc = fmaf(x[k0 + j], wv[j], acc);
-        }
-        if (lane < A) logit = acc + bpi[lane];
-    }
-    for (int k = lane; k < 512; k += 64) vacc = fmaf(x[k], Wv[k], vacc);
-    for (int o = 32; o; o >>= 1) vacc += __shfl_xor(vacc, o);
-    float mx = logit;
-    for (int o = 32; o; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-    const float e = lane < A ? expf(logit - mx) : 0.f;
-    float se = e;
-    for (int o = 32; o; o >>= 1) se += __shfl_xor(se, o);
-    const float p = e / se;
+    const float acc = t_head_cols(x, Wpi, A, lane);
+    const float logit = lane < A ? acc + bpi[lane] : -INFINITY;
+    const float vacc = t_head_dot(x, Wv, lane);
+    const TPolicyLoss pl = t_policy_loss(logit, pit + (size_t)b * A, n, A, flat, lane);
+    const float p = pl.p, t = pl.t, lpi = pl.lpi;
     const float v = tanhf(vacc + bv[0]);
-    const int row = flat ? 0 : lane / n, width = flat ? A : n;
-    const float t = lane < A ? pit[(size_t)b * A + lane] : 0.f;
-    float S = 0.f;
-    for (int c = 0; c < width; ++c) { const int src = row * n + c; S += __shfl(p, src < 63 ? src : 63); }
-    const float q = lane < A ? p / S : 0.5f;
-    const float qc = fminf(fmaxf(q, 1e-7f), 1.0f - 1e-7f);
-    float lpi = lane < A ? -t * logf(qc) : 0.f;
-    for (int o = 32; o; o >>= 1) lpi += __shfl_xor(lpi, o);
     const int ap = t_argmax_lowest(lane < A ? p : -INFINITY, lane), at = t_argmax_lowest(lane < A ? t : -INFINITY, lane);      // idle lanes never win
     if (lane < A) p_out[(size_t)b * A + lane] = p;
     if (lane == 0) {
@@ -420,9 +413,9 @@ __global__ __launch_bounds__(256) void k_t_acc_eval(const float* __restrict__ ro
         acc->examples += B;
     }
 }
+// The three backward kernels of a head pair (t_head_pair_backward): the policy / value heads and, with the auxiliary heads on, theirs
+// (dopre, dspre, Wown, Wsc in the places of dlogit, dvpre, Wpi, Wv).
 // dWpi[k][a] = sum_b f2[b][k] dlogit[b][a];  dWv[k] = sum_b f2[b][k] dvpre[b]   (block = k, thread = a; a == A handles v)
-// TWO callers: t_heads_backward launches it for the policy / value heads and, with the auxiliary heads on, a second time on their tensors
-// (dopre, dspre -> dWown, dWsc): a change of its sums or its argument order changes both
 __global__ __launch_bounds__(128) void k_t_heads_wgrad(const float* __restrict__ f2, const float* __restrict__ dlogit, const float* __restrict__ dvpre,
                                                        const int* __restrict__ d_count, int A, float* __restrict__ dWpi, float* __restrict__ dWv) {
     const int k = blockIdx.x, a = threadIdx.x, B = *d_count;
@@ -431,7 +424,8 @@ __global__ __launch_bounds__(128) void k_t_heads_wgrad(const float* __restrict__
     _Pragma("unroll 8") for (int b = 0; b < B; ++b) acc = fmaf(f2[(size_t)b * 512 + k], a < A ? dlogit[(size_t)b * A + a] : dvpre[b], acc);    // 8 loads in flight, sums in batch order
     if (a < A) dWpi[(size_t)k * A + a] = acc; else dWv[k] = acc;
 }
-// dbpi[a] = sum_b dlogit[b][a]; dbv = sum_b dvpre[b]; losses[0..2] = total, pi, v (batch means)
+// dbpi[a] = sum_b dlogit[b][a]; dbv = sum_b dvpre[b]; sums in batch order.  loss (nullable, with losses: the auxiliary pair has k_t_aux_losses):
+// losses[0..2] = total, pi, v (batch means)
 __global__ __launch_bounds__(128) void k_t_heads_bias(const float* __restrict__ dlogit, const float* __restrict__ dvpre, const float* __restrict__ loss,
                                                       const int* __restrict__ d_count, int A, float* __restrict__ dbpi, float* __restrict__ dbv,
                                                       float* __restrict__ losses, unsigned* __restrict__ zero6 /* nullable: six words cleared here */) {
@@ -439,22 +433,23 @@ __global__ __launch_bounds__(128) void k_t_heads_bias(const float* __restrict__ 
     if (zero6 && a >= 120 && a < 126) zero6[a - 120] = 0u;   // the per-layer |dz| maxima of the f16x2 mode (a 24-byte memset was two fill launches on the chain)
     if (a < A) { float s = 0.f; _Pragma("unroll 8") for (int b = 0; b < B; ++b) s += dlogit[(size_t)b * A + a]; dbpi[a] = s; }
     if (a == A) { float s = 0.f; _Pragma("unroll 8") for (int b = 0; b < B; ++b) s += dvpre[b]; dbv[0] = s; }
-    if (a == A + 1) {
+    if (loss && a == A + 1) {
         float lp = 0.f, lv = 0.f;
         _Pragma("unroll 8") for (int b = 0; b < B; ++b) { lp += loss[2 * b]; lv += loss[2 * b + 1]; }
         lp /= (float)B; lv /= (float)B;
         losses[0] = lp + lv; losses[1] = lp; losses[2] = lv;
     }
 }
-// df2[b][k] = sum_a dlogit[b][a] Wpi[k][a] + dvpre[b] Wv[k]
+// df2[b][k] = sum_a dlogit[b][a] Wpi[k][a] + dvpre[b] Wv[k]; add (the auxiliary pair, behind the first launch): the same sum, then df2 += it.
+// One launch per pair: a single sum over both pairs would round differently and could not leave df2's bits alone with both weights 0
 __global__ __launch_bounds__(256) void k_t_heads_dgrad(const float* __restrict__ dlogit, const float* __restrict__ dvpre, const float* __restrict__ Wpi,
-                                                       const float* __restrict__ Wv, const int* __restrict__ d_count, int A, float* __restrict__ df2) {
+                                                       const float* __restrict__ Wv, const int* __restrict__ d_count, int A, int add, float* __restrict__ df2) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long long)(*d_count) * 512) return;
     const int b = (int)(i / 512), k = (int)(i % 512);
     float acc = dvpre[b] * Wv[k];
     for (int a = 0; a < A; ++a) acc = fmaf(dlogit[(size_t)b * A + a], Wpi[(size_t)k * A + a], acc);
-    df2[i] = acc;
+    df2[i] = add ? df2[i] + acc : acc;
 }
 
 // ---------------------------------------------------------------- auxiliary heads (oz_trainer_set_aux_heads): ownership and score from the final boards
@@ -464,8 +459,8 @@ __global__ __launch_bounds__(256) void k_t_heads_dgrad(const float* __restrict__
 //   L_own = (1/B) sum_b m_b (1/A) sum_a (o - t)^2        L_sc = (1/B) sum_b m_b (s - s_target)^2
 // fp32 in every trainer precision.  The loss weights are folded into the pre-activation gradients, so the three backward kernels know nothing of
 // them; with both weights 0 the backward kernels are not launched at all (forward and losses only: the 40 gradients keep their bits).
-// k_t_aux_heads: one 64-thread block per sample, lane = cell a = row*n+col, the weight-row loads of k_t_heads (64 rows in flight, the fmaf
-// chain in k order).  Every sum over lanes is the xor-shuffle tree: a fixed order
+// k_t_aux_heads: one 64-thread block per sample, lane = cell a = row*n+col, k_t_heads' matvecs (t_head_cols, t_head_dot).  Every sum over
+// lanes is the xor-shuffle tree: a fixed order
 __global__ __launch_bounds__(64) void k_t_aux_heads(const float* __restrict__ f2 /*[B][512]*/, const int* __restrict__ d_count, int n,
                                                     const float* __restrict__ Wown /*[512][A]*/, const float* __restrict__ bown,
                                                     const float* __restrict__ Wsc /*[512]*/, const float* __restrict__ bsc,
@@ -476,23 +471,9 @@ __global__ __launch_bounds__(64) void k_t_aux_heads(const float* __restrict__ f2
     const int b = blockIdx.x, lane = threadIdx.x, A = n * n, B = *d_count;
     if (b >= B) return;
     const float* x = f2 + (size_t)b * 512;
-    float opre = 0.f, sacc = 0.f;
-    {
-        const auto wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Wown), 0, 512 * A * 4, 0x00020000);
-        const int lo = (lane < A ? lane : 0) * 4;
-        float acc = 0.f;
-#pragma unroll 1
-        for (int k0 = 0; k0 < 512; k0 += 64) {
-            float wv[64];
-#pragma unroll
-            for (int j = 0; j < 64; ++j) wv[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(wrs, lo, (k0 + j) * A * 4, 0));
-#pragma unroll
-            for (int j = 0; j < 64; ++j) acc = fmaf(x[k0 + j], wv[j], acc);
-        }
-        if (lane < A) opre = acc + bown[lane];
-    }
-    for (int k = lane; k < 512; k += 64) sacc = fmaf(x[k], Wsc[k], sacc);
-    for (int off = 32; off; off >>= 1) sacc += __shfl_xor(sacc, off);
+    const float acc = t_head_cols(x, Wown, A, lane);
+    const float opre = lane < A ? acc + bown[lane] : 0.f;
+    const float sacc = t_head_dot(x, Wsc, lane);
     const uint64_t fo = fin_own[b], fp = fin_opp[b];
     const bool live = (fo | fp) != 0;
     const float o = tanhf(opre), s = tanhf(sacc + bsc[0]);
@@ -511,7 +492,9 @@ __global__ __launch_bounds__(64) void k_t_aux_heads(const float* __restrict__ f2
         loss[2 * b + 1] = live ? ds * ds : 0.f;
     }
 }
-// aux[0..1] = L_own, L_sc (batch means, sums in batch order); with a weight on, losses[0] (k_t_heads_bias' total) gains w_own L_own + w_sc L_sc
+// aux[0..1] = L_own, L_sc (batch means, sums in batch order); with a weight on, losses[0] (k_t_heads_bias' total) gains w_own L_own + w_sc L_sc.
+// A kernel of its own, not a part of k_t_heads_bias' second launch: it runs with both weights 0 too, when the pair's backward is not launched,
+// and it adds into losses[0] only after the first k_t_heads_bias has written it
 __global__ __launch_bounds__(64) void k_t_aux_losses(const float* __restrict__ loss, const int* __restrict__ d_count, float w_own, float w_sc,
                                                      float* __restrict__ aux /*[2]*/, float* __restrict__ losses) {
     if (threadIdx.x != 0) return;
@@ -522,24 +505,7 @@ __global__ __launch_bounds__(64) void k_t_aux_losses(const float* __restrict__ l
     aux[0] = lo; aux[1] = ls;
     if (w_own > 0.f || w_sc > 0.f) losses[0] = losses[0] + (w_own * lo + w_sc * ls);
 }
-// (the weight gradients dWown[k][a] = sum_b f2[b][k] dopre[b][a], dWsc[k] = sum_b f2[b][k] dspre[b] ARE k_t_heads_wgrad's sums: a second launch of it)
-// dbown[a] = sum_b dopre[b][a]; dbsc = sum_b dspre[b]; sums in batch order
-__global__ __launch_bounds__(128) void k_t_aux_bias(const float* __restrict__ dopre, const float* __restrict__ dspre, const int* __restrict__ d_count, int A,
-                                                    float* __restrict__ dbown, float* __restrict__ dbsc) {
-    const int a = threadIdx.x, B = *d_count;
-    if (a < A) { float s = 0.f; _Pragma("unroll 8") for (int b = 0; b < B; ++b) s += dopre[(size_t)b * A + a]; dbown[a] = s; }
-    if (a == A) { float s = 0.f; _Pragma("unroll 8") for (int b = 0; b < B; ++b) s += dspre[b]; dbsc[0] = s; }
-}
-// df2[b][k] += sum_a dopre[b][a] Wown[k][a] + dspre[b] Wsc[k]: behind k_t_heads_dgrad, one thread per element, the sum in k_t_heads_dgrad's order
-__global__ __launch_bounds__(256) void k_t_aux_dgrad(const float* __restrict__ dopre, const float* __restrict__ dspre, const float* __restrict__ Wown,
-                                                     const float* __restrict__ Wsc, const int* __restrict__ d_count, int A, float* __restrict__ df2) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long long)(*d_count) * 512) return;
-    const int b = (int)(i / 512), k = (int)(i % 512);
-    float acc = dspre[b] * Wsc[k];
-    for (int a = 0; a < A; ++a) acc = fmaf(dopre[(size_t)b * A + a], Wown[(size_t)k * A + a], acc);
-    df2[i] += acc;
-}
+// (the pair's weight, bias and f2 gradients are a second launch each of k_t_heads_wgrad, k_t_heads_bias and k_t_heads_dgrad)
 
 // ---------------------------------------------------------------- weight gradient: TN implicit GEMM on fp32 MFMA
 // dW[t][ci][co] = sum_m Xs_t[m][ci] * dZ[m][co], m = (b, oy, ox).  Block tile 128 ci x 128 co for one tap, 4 waves of
@@ -1246,7 +1212,7 @@ struct oz_trainer {
     float w_own = 0.f, w_sc = 0.f;
     uint64_t *d_fin = nullptr, *h_fin = nullptr;         // [2][Bmax]: fin_own, fin_opp
     float *ao = nullptr, *as = nullptr, *dopre = nullptr, *dspre = nullptr, *aux_loss = nullptr, *aux_losses = nullptr;
-    float* cap_f2 = nullptr;             // capture: the gradient wrt f2 as k_t_heads_dgrad left it, before k_t_aux_dgrad's add
+    float* cap_f2 = nullptr;             // capture: the gradient wrt f2 as k_t_heads_dgrad left it, before its second launch's add
     uint64_t *ds_fo = nullptr, *ds_fp = nullptr;
     int64_t ds_fin_cap = 0;
     double epoch_aux[2] = {0.0, 0.0};    // the last fit epoch's sample-weighted means of the two losses
@@ -1853,11 +1819,16 @@ static int t_capture(oz_trainer* t, int l, int B, const float* dA) {
 static int t_heads_backward(oz_trainer* t, int B, float* dA) {
     hipStream_t s = t->s;
     const int A = t->n * t->n;
-    hipLaunchKernelGGL(k_t_heads_wgrad, dim3(512), dim3(128), 0, s, t->a[5], t->dlogit, t->dvpre, t->d_count, A, t->grad(36), t->grad(38));
-    hipLaunchKernelGGL(k_t_heads_bias, dim3(1), dim3(128), 0, s, t->dlogit, t->dvpre, t->loss, t->d_count, A, t->grad(37), t->grad(39), t->losses,
-                       t->mode == 1 ? t->dzmax : (unsigned*)nullptr);
-    hipLaunchKernelGGL(k_t_heads_dgrad, dim3((unsigned)(((long long)B * 512 + 255) / 256)), dim3(256), 0, s, t->dlogit, t->dvpre, t->param(36),
-                       t->param(38), t->d_count, A, dA);
+    // one head pair: arrays p .. p + 3 of the arena are its W[512][A], b[A], w[512], b[1]; dcol / dsc the gradients wrt its pre-activations.
+    // aux: the second pair adds into dA and leaves the losses and the |dz| maxima to the first
+    auto pair_backward = [&](int p, const float* dcol, const float* dsc, bool aux) {
+        hipLaunchKernelGGL(k_t_heads_wgrad, dim3(512), dim3(128), 0, s, t->a[5], dcol, dsc, t->d_count, A, t->grad(p), t->grad(p + 2));
+        hipLaunchKernelGGL(k_t_heads_bias, dim3(1), dim3(128), 0, s, dcol, dsc, aux ? (const float*)nullptr : t->loss, t->d_count, A, t->grad(p + 1),
+                           t->grad(p + 3), aux ? (float*)nullptr : t->losses, !aux && t->mode == 1 ? t->dzmax : (unsigned*)nullptr);
+        hipLaunchKernelGGL(k_t_heads_dgrad, dim3((unsigned)(((long long)B * 512 + 255) / 256)), dim3(256), 0, s, dcol, dsc, t->param(p), t->param(p + 2),
+                           t->d_count, A, (int)aux, dA);
+    };
+    pair_backward(36, t->dlogit, t->dvpre, false);
     OZ_HIP(hipGetLastError());
     if (!t->aux) return t_capture(t, 5, B, dA);
     // auxiliary heads: their batch-mean losses behind k_t_heads_bias (whose total they join); with a weight on, their weight and bias gradients
@@ -1865,10 +1836,7 @@ static int t_heads_backward(oz_trainer* t, int B, float* dA) {
     hipLaunchKernelGGL(k_t_aux_losses, dim3(1), dim3(64), 0, s, t->aux_loss, t->d_count, t->w_own, t->w_sc, t->aux_losses, t->losses);
     if (t->w_own > 0.f || t->w_sc > 0.f) {
         if (t->capture) OZ_HIP(hipMemcpyAsync(t->cap_f2, dA, (size_t)B * 512 * sizeof(float), hipMemcpyDeviceToDevice, s));
-        hipLaunchKernelGGL(k_t_heads_wgrad, dim3(512), dim3(128), 0, s, t->a[5], t->dopre, t->dspre, t->d_count, A, t->grad(40), t->grad(42));
-        hipLaunchKernelGGL(k_t_aux_bias, dim3(1), dim3(128), 0, s, t->dopre, t->dspre, t->d_count, A, t->grad(41), t->grad(43));
-        hipLaunchKernelGGL(k_t_aux_dgrad, dim3((unsigned)(((long long)B * 512 + 255) / 256)), dim3(256), 0, s, t->dopre, t->dspre, t->param(40),
-                           t->param(42), t->d_count, A, dA);
+        pair_backward(40, t->dopre, t->dspre, true);
     }
     OZ_HIP(hipGetLastError());
     return t_capture(t, 5, B, dA);
@@ -2126,46 +2094,49 @@ OZ_API int oz_trainer_forward_backward_aux(oz_trainer* t, const uint64_t* own, c
 // keras Model.fit (Net/NNet.py:67) walks the examples in shuffled batches; here the examples live on the device for the
 // whole fit, a step gathers its batch by index on the device, and the optimiser steps of an epoch are enqueued back to back
 // (no host copy, no synchronisation per step); the sample-weighted loss sums are accumulated on the device.
+// ds_fo / ds_fp (nullable, with fo / fp): the examples' final pairs for the auxiliary heads, gathered beside the boards
 __global__ void k_t_gather_batch(const uint64_t* __restrict__ ds_own, const uint64_t* __restrict__ ds_opp, const float* __restrict__ ds_pi,
-                                 const float* __restrict__ ds_z, const int* __restrict__ order, int first, int B, int A,
+                                 const float* __restrict__ ds_z, const uint64_t* __restrict__ ds_fo, const uint64_t* __restrict__ ds_fp,
+                                 const int* __restrict__ order, int first, int B, int A,
                                  uint64_t* __restrict__ own, uint64_t* __restrict__ opp, float* __restrict__ pit, float* __restrict__ zt,
-                                 int* __restrict__ d_count) {
+                                 uint64_t* __restrict__ fo, uint64_t* __restrict__ fp, int* __restrict__ d_count) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i == 0) *d_count = B;
     if (i >= B * A) return;
     const int b = i / A, a = i % A, src = order[first + b];
     pit[i] = ds_pi[(size_t)src * A + a];
-    if (a == 0) { own[b] = ds_own[src]; opp[b] = ds_opp[src]; zt[b] = ds_z[src]; }
-}
-__global__ void k_t_acc_losses(const float* __restrict__ losses, int B, double* __restrict__ acc /*[4]: 3 weighted sums + samples*/) {
-    if (threadIdx.x < 3) acc[threadIdx.x] += (double)losses[threadIdx.x] * (double)B;
-    if (threadIdx.x == 3) acc[3] += (double)B;
-}
-// the aux siblings of the two kernels above: the batch's final pairs by index, and the two auxiliary losses into acc[4], acc[5]
-__global__ void k_t_gather_batch_aux(const uint64_t* __restrict__ ds_fo, const uint64_t* __restrict__ ds_fp, const int* __restrict__ order, int first, int B,
-                                     uint64_t* __restrict__ fo, uint64_t* __restrict__ fp) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    const int src = order[first + b];
-    fo[b] = ds_fo[src]; fp[b] = ds_fp[src];
-}
-__global__ void k_t_acc_aux_losses(const float* __restrict__ aux, int B, double* __restrict__ acc) {
-    if (threadIdx.x < 2) acc[4 + threadIdx.x] += (double)aux[threadIdx.x] * (double)B;
+    if (a == 0) {
+        own[b] = ds_own[src]; opp[b] = ds_opp[src]; zt[b] = ds_z[src];
+        if (ds_fo) { fo[b] = ds_fo[src]; fp[b] = ds_fp[src]; }
+    }
 }
 #define T_DS_ACC 6                       // doubles of ds_acc: 3 weighted loss sums, the samples, the two auxiliary sums
+__global__ void k_t_acc_losses(const float* __restrict__ losses, const float* __restrict__ aux /*nullable*/, int B, double* __restrict__ acc /*[T_DS_ACC]*/) {
+    if (threadIdx.x < 3) acc[threadIdx.x] += (double)losses[threadIdx.x] * (double)B;
+    if (threadIdx.x == 3) acc[3] += (double)B;
+    if (aux && (threadIdx.x == 4 || threadIdx.x == 5)) acc[threadIdx.x] += (double)aux[threadIdx.x - 4] * (double)B;
+}
+
+// Device arrays that grow with what a caller brings (`per` elements each per example, `cap` examples so far): when n exceeds cap, wait for the
+// stream, free them, null the pointers and zero cap BEFORE allocating (a failed hipMalloc leaves no dangling pointer), then cap = n
+struct TGrowArray { void** p; size_t bytes_per; };
+#define T_GROW(ptr, per) TGrowArray{(void**)&(ptr), (size_t)(per) * sizeof(*(ptr))}
+static int t_grow(oz_trainer* t, int64_t n, int64_t& cap, std::initializer_list<TGrowArray> arrays) {
+    if (n <= cap) return OZ_OK;
+    OZ_HIP(hipStreamSynchronize(t->s));
+    for (const TGrowArray& a : arrays) { if (*a.p) hipFree(*a.p); *a.p = nullptr; }
+    cap = 0;
+    for (const TGrowArray& a : arrays) OZ_HIP(hipMalloc(a.p, (size_t)n * a.bytes_per));
+    cap = n;
+    return OZ_OK;
+}
 
 static int t_set_dataset(oz_trainer* t, const uint64_t* own, const uint64_t* opp, const float* pi_target, const float* z_target,
                          const uint64_t* fin_own, const uint64_t* fin_opp, int64_t N) {
     OZ_HIP(hipSetDevice(t->device));
     const int A = t->n * t->n;
     if (t->aux) {                      // the pairs beside the data set (no arrays given: every mask 0)
-        if (N > t->ds_fin_cap) {
-            OZ_HIP(hipStreamSynchronize(t->s));
-            if (t->ds_fo) { hipFree(t->ds_fo); hipFree(t->ds_fp); }
-            t->ds_fo = t->ds_fp = nullptr; t->ds_fin_cap = 0;
-            OZ_HIP(hipMalloc((void**)&t->ds_fo, N * sizeof(uint64_t))); OZ_HIP(hipMalloc((void**)&t->ds_fp, N * sizeof(uint64_t)));
-            t->ds_fin_cap = N;
-        }
+        if (int rc = t_grow(t, N, t->ds_fin_cap, {T_GROW(t->ds_fo, 1), T_GROW(t->ds_fp, 1)})) return rc;
         if (fin_own) {
             OZ_HIP(hipMemcpyAsync(t->ds_fo, fin_own, N * sizeof(uint64_t), hipMemcpyHostToDevice, t->s));
             OZ_HIP(hipMemcpyAsync(t->ds_fp, fin_opp, N * sizeof(uint64_t), hipMemcpyHostToDevice, t->s));
@@ -2174,16 +2145,8 @@ static int t_set_dataset(oz_trainer* t, const uint64_t* own, const uint64_t* opp
             OZ_HIP(hipMemsetAsync(t->ds_fp, 0, N * sizeof(uint64_t), t->s));
         }
     }
-    if (N > t->ds_cap) {
-        OZ_HIP(hipStreamSynchronize(t->s));
-        if (t->ds_own) { hipFree(t->ds_own); hipFree(t->ds_opp); hipFree(t->ds_pi); hipFree(t->ds_z); }
-        if (t->ds_order) hipFree(t->ds_order);          // (an epoch from a replay buffer may have sized it before any data set)
-        t->ds_own = t->ds_opp = nullptr; t->ds_pi = t->ds_z = nullptr; t->ds_order = nullptr; t->ds_cap = 0; t->ds_order_cap = 0;
-        OZ_HIP(hipMalloc((void**)&t->ds_own, N * sizeof(uint64_t))); OZ_HIP(hipMalloc((void**)&t->ds_opp, N * sizeof(uint64_t)));
-        OZ_HIP(hipMalloc((void**)&t->ds_pi, (size_t)N * A * sizeof(float))); OZ_HIP(hipMalloc((void**)&t->ds_z, N * sizeof(float)));
-        OZ_HIP(hipMalloc((void**)&t->ds_order, N * sizeof(int)));
-        t->ds_cap = N; t->ds_order_cap = N;
-    }
+    if (int rc = t_grow(t, N, t->ds_cap, {T_GROW(t->ds_own, 1), T_GROW(t->ds_opp, 1), T_GROW(t->ds_pi, A), T_GROW(t->ds_z, 1)})) return rc;
+    if (int rc = t_grow(t, N, t->ds_order_cap, {T_GROW(t->ds_order, 1)})) return rc;      // (an epoch from a replay buffer may have sized it already)
     if (!t->ds_acc) OZ_HIP(hipMalloc((void**)&t->ds_acc, T_DS_ACC * sizeof(double)));
     OZ_HIP(hipMemcpyAsync(t->ds_own, own, N * sizeof(uint64_t), hipMemcpyHostToDevice, t->s));
     OZ_HIP(hipMemcpyAsync(t->ds_opp, opp, N * sizeof(uint64_t), hipMemcpyHostToDevice, t->s));
@@ -2212,32 +2175,43 @@ static int t_apply_locked(oz_trainer* t);
 // (oz_replay.hip) -- `n` examples in the same four arrays; fo / fp: their final pairs for the auxiliary heads (NULL: none, every mask 0).
 struct TDataView { const uint64_t *own, *opp; const float *pi, *z; int64_t n; const uint64_t *fo = nullptr, *fp = nullptr; };
 
+// What the epoch and evaluation entry points (`who`) check alike: the batch in [1, Bmax] and every index of `order` inside the resident data
+// set or, r given (and locked), inside what the replay buffer holds -- then also r's board size and device and, need_fo, that it keeps the final pairs
+static int t_check_batches(oz_trainer* t, const char* who, oz_replay* r, bool need_fo, const int32_t* order, int64_t count, int batch) {
+    if (r) {
+        OZ_REQUIRE(r->n == t->n, "%s: the trainer's boards are %d x %d, the replay buffer's %d x %d", who, t->n, t->n, r->n, r->n);
+        OZ_REQUIRE(r->device == t->device, "%s: the trainer lives on device %d, the replay buffer on device %d", who, t->device, r->device);
+    }
+    OZ_REQUIRE(batch >= 1 && batch <= t->Bmax, "%s: batch %d outside [1, %d]", who, batch, t->Bmax);
+    const int64_t limit = r ? r->held() : t->ds_n;
+    for (int64_t i = 0; i < count; ++i) {
+        if (order[i] >= 0 && order[i] < limit) continue;
+        if (r) oz_set_error("%s: index %d outside the %lld examples the replay buffer holds", who, order[i], (long long)limit);
+        else oz_set_error("%s: index %d outside the data set", who, order[i]);
+        return OZ_ERR_ARG;
+    }
+    OZ_REQUIRE(!need_fo || r->fo, "%s: a trainer with the auxiliary heads needs a replay buffer that keeps the final pairs (oz_replay_create_aux)", who);
+    return OZ_OK;
+}
+
 // the optimiser steps of one epoch over `d` in the order `order` (validated by the caller's entry point): per step one device-side gather of
 // the batch, forward + backward, the loss accumulation and Adam, back to back on the stream; one read-back at the end
 static int t_fit_epoch_view(oz_trainer* t, const TDataView& d, const int32_t* order, int64_t count, int batch, float* losses3) {
     OZ_HIP(hipSetDevice(t->device));
     hipStream_t s = t->s;
     const int A = t->n * t->n;
-    if (count > t->ds_order_cap) {             // (never on the resident path: oz_trainer_set_dataset sized it for the data set)
-        OZ_HIP(hipStreamSynchronize(s));
-        if (t->ds_order) hipFree(t->ds_order);
-        t->ds_order = nullptr; t->ds_order_cap = 0;
-        OZ_HIP(hipMalloc((void**)&t->ds_order, count * sizeof(int)));
-        t->ds_order_cap = count;
-    }
+    if (int rc = t_grow(t, count, t->ds_order_cap, {T_GROW(t->ds_order, 1)})) return rc;      // (never on the resident path: oz_trainer_set_dataset sized it)
     if (!t->ds_acc) OZ_HIP(hipMalloc((void**)&t->ds_acc, T_DS_ACC * sizeof(double)));
     OZ_HIP(hipMemcpyAsync(t->ds_order, order, count * sizeof(int), hipMemcpyHostToDevice, s));
     OZ_HIP(hipMemsetAsync(t->ds_acc, 0, T_DS_ACC * sizeof(double), s));
     if (t->aux && !d.fo) OZ_HIP(hipMemsetAsync(t->d_fin, 0, 2 * (size_t)t->Bmax * sizeof(uint64_t), s));      // no pairs: every mask 0, for the whole epoch
+    uint64_t* const fin_own = d.fo ? t->d_fin : nullptr, * const fin_opp = d.fo ? t->d_fin + t->Bmax : nullptr;      // (d.fo only with the auxiliary heads)
     for (int64_t first = 0; first < count; first += batch) {
         const int B = (int)(count - first < batch ? count - first : batch);            // the last batch may be short, as in keras
-        hipLaunchKernelGGL(k_t_gather_batch, dim3((B * A + 255) / 256), dim3(256), 0, s, d.own, d.opp, d.pi, d.z, t->ds_order,
-                           (int)first, B, A, t->d_own, t->d_opp, t->d_pit, t->d_zt, t->d_count);
-        if (t->aux && d.fo)
-            hipLaunchKernelGGL(k_t_gather_batch_aux, dim3((B + 255) / 256), dim3(256), 0, s, d.fo, d.fp, t->ds_order, (int)first, B, t->d_fin, t->d_fin + t->Bmax);
+        hipLaunchKernelGGL(k_t_gather_batch, dim3((B * A + 255) / 256), dim3(256), 0, s, d.own, d.opp, d.pi, d.z, d.fo, d.fp, t->ds_order,
+                           (int)first, B, A, t->d_own, t->d_opp, t->d_pit, t->d_zt, fin_own, fin_opp, t->d_count);
         if (int rc = t_forward_backward_async(t, B)) return rc;
-        hipLaunchKernelGGL(k_t_acc_losses, dim3(1), dim3(64), 0, s, t->losses, B, t->ds_acc);
-        if (t->aux) hipLaunchKernelGGL(k_t_acc_aux_losses, dim3(1), dim3(64), 0, s, t->aux_losses, B, t->ds_acc);
+        hipLaunchKernelGGL(k_t_acc_losses, dim3(1), dim3(64), 0, s, t->losses, t->aux ? t->aux_losses : (const float*)nullptr, B, t->ds_acc);
         if (int rc = t_apply_locked(t)) return rc;
     }
     double h[T_DS_ACC];
@@ -2253,8 +2227,7 @@ OZ_API int oz_trainer_fit_epoch(oz_trainer* t, const int32_t* order, int64_t cou
     T_LOCK(t);
     OZ_REQUIRE(t->ds_n > 0 && count <= t->ds_n, "oz_trainer_fit_epoch: %lld indices but the resident data set holds %lld examples (oz_trainer_set_dataset first)",
                (long long)count, (long long)t->ds_n);
-    OZ_REQUIRE(batch >= 1 && batch <= t->Bmax, "oz_trainer_fit_epoch: batch %d outside [1, %d]", batch, t->Bmax);
-    for (int64_t i = 0; i < count; ++i) OZ_REQUIRE(order[i] >= 0 && order[i] < t->ds_n, "oz_trainer_fit_epoch: index %d outside the data set", order[i]);
+    if (int rc = t_check_batches(t, "oz_trainer_fit_epoch", nullptr, false, order, count, batch)) return rc;
     return t_fit_epoch_view(t, {t->ds_own, t->ds_opp, t->ds_pi, t->ds_z, t->ds_n, t->aux ? t->ds_fo : nullptr, t->aux ? t->ds_fp : nullptr}, order, count, batch, losses3);
 }
 
@@ -2264,14 +2237,8 @@ OZ_API int oz_trainer_fit_epoch_replay(oz_trainer* t, oz_replay* r, const int32_
     OZ_REQUIRE(t && r && order && count >= 1 && count < (1ll << 31), "oz_trainer_fit_epoch_replay: bad argument");
     T_LOCK(t);
     std::lock_guard<std::mutex> rlock(r->mu);
-    OZ_REQUIRE(r->n == t->n, "oz_trainer_fit_epoch_replay: the trainer's boards are %d x %d, the replay buffer's %d x %d", t->n, t->n, r->n, r->n);
-    OZ_REQUIRE(r->device == t->device, "oz_trainer_fit_epoch_replay: the trainer lives on device %d, the replay buffer on device %d", t->device, r->device);
-    OZ_REQUIRE(batch >= 1 && batch <= t->Bmax, "oz_trainer_fit_epoch_replay: batch %d outside [1, %d]", batch, t->Bmax);
-    const int64_t held = r->held();
-    for (int64_t i = 0; i < count; ++i)
-        OZ_REQUIRE(order[i] >= 0 && order[i] < held, "oz_trainer_fit_epoch_replay: index %d outside the %lld examples the replay buffer holds", order[i], (long long)held);
-    OZ_REQUIRE(!t->aux || r->fo, "oz_trainer_fit_epoch_replay: a trainer with the auxiliary heads needs a replay buffer that keeps the final pairs (oz_replay_create_aux)");
-    return t_fit_epoch_view(t, {r->own, r->opp, r->pi, r->z, held, t->aux ? r->fo : nullptr, t->aux ? r->fp : nullptr}, order, count, batch, losses3);
+    if (int rc = t_check_batches(t, "oz_trainer_fit_epoch_replay", r, t->aux, order, count, batch)) return rc;
+    return t_fit_epoch_view(t, {r->own, r->opp, r->pi, r->z, r->held(), t->aux ? r->fo : nullptr, t->aux ? r->fp : nullptr}, order, count, batch, losses3);
 }
 
 // ---------------------------------------------------------------- held-out evaluation in inference mode
@@ -2284,13 +2251,7 @@ static int t_evaluate_view(oz_trainer* t, const TDataView& d, const int32_t* ord
     OZ_HIP(hipSetDevice(t->device));
     hipStream_t s = t->s;
     const int A = t->n * t->n;
-    if (count > t->ev_order_cap) {
-        OZ_HIP(hipStreamSynchronize(s));
-        if (t->ev_order) hipFree(t->ev_order);
-        t->ev_order = nullptr; t->ev_order_cap = 0;
-        OZ_HIP(hipMalloc((void**)&t->ev_order, count * sizeof(int)));
-        t->ev_order_cap = count;
-    }
+    if (int rc = t_grow(t, count, t->ev_order_cap, {T_GROW(t->ev_order, 1)})) return rc;
     if (!t->ev_rows) T_ALLOC(t->ev_rows, (size_t)t->Bmax * OZ_EVAL_ROW);
     if (!t->ev_acc) T_ALLOC(t->ev_acc, 1);
     OZ_HIP(hipMemcpyAsync(t->ev_order, order, count * sizeof(int), hipMemcpyHostToDevice, s));
@@ -2298,8 +2259,8 @@ static int t_evaluate_view(oz_trainer* t, const TDataView& d, const int32_t* ord
     if (t->dirty) if (int rc = t_refresh(t)) return rc;
     for (int64_t first = 0; first < count; first += batch) {
         const int B = (int)(count - first < batch ? count - first : batch);
-        hipLaunchKernelGGL(k_t_gather_batch, dim3((B * A + 255) / 256), dim3(256), 0, s, d.own, d.opp, d.pi, d.z, t->ev_order,
-                           (int)first, B, A, t->d_own, t->d_opp, t->d_pit, t->d_zt, t->d_count);
+        hipLaunchKernelGGL(k_t_gather_batch, dim3((B * A + 255) / 256), dim3(256), 0, s, d.own, d.opp, d.pi, d.z, nullptr, nullptr, t->ev_order,
+                           (int)first, B, A, t->d_own, t->d_opp, t->d_pit, t->d_zt, nullptr, nullptr, t->d_count);
         if (int rc = t_forward(t, B, /*infer=*/true)) return rc;
         hipLaunchKernelGGL(k_t_acc_eval, dim3(1), dim3(256), 0, s, t->ev_rows, B, t->ev_acc);
     }
@@ -2318,17 +2279,11 @@ static int t_evaluate_view(oz_trainer* t, const TDataView& d, const int32_t* ord
 OZ_API int oz_trainer_evaluate(oz_trainer* t, const uint64_t* own, const uint64_t* opp, const float* pi, const float* z, int64_t N, int batch, double* out) {
     OZ_REQUIRE(t && own && opp && pi && z && out && N >= 1 && N < (1ll << 31), "oz_trainer_evaluate: bad argument");
     T_LOCK(t);
-    OZ_REQUIRE(batch >= 1 && batch <= t->Bmax, "oz_trainer_evaluate: batch %d outside [1, %d]", batch, t->Bmax);
+    if (int rc = t_check_batches(t, "oz_trainer_evaluate", nullptr, false, nullptr, 0, batch)) return rc;      // (the order is the identity)
     OZ_HIP(hipSetDevice(t->device));
     const int A = t->n * t->n;
-    if (N > t->ev_cap) {               // arrays of the evaluation's own: the resident data set of a fit stays what it is
-        OZ_HIP(hipStreamSynchronize(t->s));
-        for (void* q : {(void*)t->ev_own, (void*)t->ev_opp, (void*)t->ev_pi, (void*)t->ev_z}) if (q) hipFree(q);
-        t->ev_own = t->ev_opp = nullptr; t->ev_pi = t->ev_z = nullptr; t->ev_cap = 0;
-        OZ_HIP(hipMalloc((void**)&t->ev_own, N * sizeof(uint64_t))); OZ_HIP(hipMalloc((void**)&t->ev_opp, N * sizeof(uint64_t)));
-        OZ_HIP(hipMalloc((void**)&t->ev_pi, (size_t)N * A * sizeof(float))); OZ_HIP(hipMalloc((void**)&t->ev_z, N * sizeof(float)));
-        t->ev_cap = N;
-    }
+    // arrays of the evaluation's own: the resident data set of a fit stays what it is
+    if (int rc = t_grow(t, N, t->ev_cap, {T_GROW(t->ev_own, 1), T_GROW(t->ev_opp, 1), T_GROW(t->ev_pi, A), T_GROW(t->ev_z, 1)})) return rc;
     OZ_HIP(hipMemcpyAsync(t->ev_own, own, N * sizeof(uint64_t), hipMemcpyHostToDevice, t->s));
     OZ_HIP(hipMemcpyAsync(t->ev_opp, opp, N * sizeof(uint64_t), hipMemcpyHostToDevice, t->s));
     OZ_HIP(hipMemcpyAsync(t->ev_pi, pi, (size_t)N * A * sizeof(float), hipMemcpyHostToDevice, t->s));
@@ -2344,8 +2299,7 @@ OZ_API int oz_trainer_evaluate_dataset(oz_trainer* t, const int32_t* order, int6
     OZ_REQUIRE(t && order && out && count >= 1 && count < (1ll << 31), "oz_trainer_evaluate_dataset: bad argument");
     T_LOCK(t);
     OZ_REQUIRE(t->ds_n > 0, "oz_trainer_evaluate_dataset: the resident data set is empty (oz_trainer_set_dataset first)");
-    OZ_REQUIRE(batch >= 1 && batch <= t->Bmax, "oz_trainer_evaluate_dataset: batch %d outside [1, %d]", batch, t->Bmax);
-    for (int64_t i = 0; i < count; ++i) OZ_REQUIRE(order[i] >= 0 && order[i] < t->ds_n, "oz_trainer_evaluate_dataset: index %d outside the data set", order[i]);
+    if (int rc = t_check_batches(t, "oz_trainer_evaluate_dataset", nullptr, false, order, count, batch)) return rc;
     return t_evaluate_view(t, {t->ds_own, t->ds_opp, t->ds_pi, t->ds_z, t->ds_n}, order, count, batch, out);
 }
 
@@ -2354,13 +2308,8 @@ OZ_API int oz_trainer_evaluate_replay(oz_trainer* t, oz_replay* r, const int32_t
     OZ_REQUIRE(t && r && order && out && count >= 1 && count < (1ll << 31), "oz_trainer_evaluate_replay: bad argument");
     T_LOCK(t);
     std::lock_guard<std::mutex> rlock(r->mu);
-    OZ_REQUIRE(r->n == t->n, "oz_trainer_evaluate_replay: the trainer's boards are %d x %d, the replay buffer's %d x %d", t->n, t->n, r->n, r->n);
-    OZ_REQUIRE(r->device == t->device, "oz_trainer_evaluate_replay: the trainer lives on device %d, the replay buffer on device %d", t->device, r->device);
-    OZ_REQUIRE(batch >= 1 && batch <= t->Bmax, "oz_trainer_evaluate_replay: batch %d outside [1, %d]", batch, t->Bmax);
-    const int64_t held = r->held();
-    for (int64_t i = 0; i < count; ++i)
-        OZ_REQUIRE(order[i] >= 0 && order[i] < held, "oz_trainer_evaluate_replay: index %d outside the %lld examples the replay buffer holds", order[i], (long long)held);
-    return t_evaluate_view(t, {r->own, r->opp, r->pi, r->z, held}, order, count, batch, out);
+    if (int rc = t_check_batches(t, "oz_trainer_evaluate_replay", r, false, order, count, batch)) return rc;
+    return t_evaluate_view(t, {r->own, r->opp, r->pi, r->z, r->held()}, order, count, batch, out);
 }
 
 // the two stages of the sum of squares of `X`'s arrays `sg` on the main stream -> norm_out[slot] (clipnorm > 0: the clip scale too)

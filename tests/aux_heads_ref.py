@@ -6,7 +6,7 @@ Three groups:
   * AuxTrainRef: the float64 torch-autograd restatement of a training step WITH the two heads.  oracle/train_ref.py's forward_backward is one
     block, so the forward is restated here with the two heads and the two loss terms behind it; _bn_train, _relu, dropout_keep, planes and apply
     are the oracle's own;
-  * per-kernel references of k_t_aux_heads / the weight and bias gradients / k_t_aux_dgrad in a `dtype` (float64: the reference, float32: the
+  * per-kernel references of k_t_aux_heads / the weight and bias gradients / k_t_heads_dgrad's adding launch in a `dtype` (float64: the reference, float32: the
     yardstick E32, as in train_kernel_ref), and float32 models in the kernels' own summation order with switches for single defects.
 
 Margins (x E32) of the per-kernel tests: the arithmetic has the shape of the policy / value heads', so they start from train_kernel_ref's heads
@@ -23,7 +23,7 @@ AUX = (40, 41, 42, 43)                 # Wown (512, A), bown (A,), Wsc (512, 1),
 MARGIN = {
     "aux_o": 8.0, "aux_s": 8.0, "aux_dopre": 8.0, "aux_dspre": 8.0, "aux_loss": 8.0,      # k_t_aux_heads (+ k_t_aux_losses' batch means)
     "aux_dwown": 6.0, "aux_dwsc": 6.0, "aux_dbown": 6.0, "aux_dbsc": 6.0,                 # weight and bias gradients, sums in batch order
-    "aux_df2": 8.0,                                                                       # k_t_aux_dgrad's term of the gradient wrt f2
+    "aux_df2": 8.0,                                                                       # the heads' term of the gradient wrt f2 (k_t_heads_dgrad, add)
 }
 
 
@@ -230,7 +230,7 @@ def aux_reduce(a5, dopre, dspre, dtype):
 
 
 def aux_dgrad(dopre, dspre, wown, wsc, dtype):
-    """k_t_aux_dgrad's term: (B, 512) = dopre Wown^T + dspre Wsc^T"""
+    """the term k_t_heads_dgrad's second launch adds: (B, 512) = dopre Wown^T + dspre Wsc^T"""
     return np.asarray(dopre, dtype) @ np.asarray(wown, dtype).T + np.outer(np.asarray(dspre, dtype).reshape(-1), np.asarray(wsc, dtype).reshape(-1))
 
 
@@ -262,14 +262,14 @@ def model_aux_forward(a5, wown, bown, wsc, bsc, defect=None):
 
 
 def model_aux_reduce(a5, dopre, dspre, lost_board=False):
-    """the weight and bias gradients in batch order (k_t_heads_wgrad's sums on the heads' tensors, k_t_aux_bias)"""
+    """the weight and bias gradients in batch order (k_t_heads_wgrad's and k_t_heads_bias' sums on the heads' tensors)"""
     sl = slice(None, -1) if lost_board else slice(None)
     r = K.model_heads_reduce(np.asarray(a5)[sl], np.asarray(dopre)[sl], np.asarray(dspre)[sl])
     return dict(dwown=r["dwpi"], dwsc=r["dwv"], dbown=r["dbpi"], dbsc=r["dbv"])
 
 
 def model_aux_dgrad(dopre, dspre, wown, wsc, df2_before, defect=None):
-    """k_t_aux_dgrad: acc = dspre[b] Wsc[k] (rounded), fmaf over a ascending, df2 += acc.  defect: None | 'no_score' | 'lost_a' (the last square left out)"""
+    """k_t_heads_dgrad with add set: acc = dspre[b] Wsc[k] (rounded), fmaf over a ascending, df2 += acc.  defect: None | 'no_score' | 'lost_a' (the last square left out)"""
     do, ds = np.asarray(dopre, F32), np.asarray(dspre, F32).reshape(-1)
     W, w = np.asarray(wown, F32), np.asarray(wsc, F32).reshape(-1)
     acc = np.zeros((do.shape[0], 512), F32) if defect == "no_score" else (ds[:, None] * w[None, :]).astype(F32)

@@ -11,7 +11,7 @@ defect).  What the models print -- 6x6 and 8x8 at 9 boards, 8x8 at 33, weights (
       dspre: a dead sample >= 1.7e6, the factor 2 >= 1.1e6, tanh' >= 4.4e6, the pair swapped >= 1.9e6
       the two batch means in batch order (k_t_aux_losses; floor 2^-24) 0.51 .. 2.95; the mean over the live samples instead of B >= 6.3e6  -> MARGIN 8
   weight and bias gradients in batch order: dWown 1.00 .. 1.12, dWsc 1.00, dbown 1.00, dbsc 0.51 .. 0.63; a lost board >= 9.2e5 -> MARGIN 6 (the heads')
-  k_t_aux_dgrad: df2 + (dspre Wsc, then fmaf over a ascending) 1.00 .. 2.22; the score term missing >= 3.0e6, the last square >= 1.3e5 -> MARGIN 8
+  k_t_heads_dgrad, add set: df2 + (dspre Wsc, then fmaf over a ascending) 1.00 .. 2.22; the score term missing >= 3.0e6, the last square >= 1.3e5 -> MARGIN 8
 Every tensor separates at the heads' margins: none is changed."""
 import numpy as np
 import pytest

@@ -95,7 +95,7 @@ def _stat(kind, got, r32, r64):
 
 @pytest.mark.parametrize("n,B", [(6, 5), (8, 5), (8, 32)])
 def test_aux_kernel_parity(oz, n, B):
-    """k_t_aux_heads, the weight and bias gradients, k_t_aux_dgrad and the batch means, each from the device's own inputs of the step"""
+    """k_t_aux_heads, the weight and bias gradients, k_t_heads_dgrad's adding launch and the batch means, each from the device's own inputs of the step"""
     C = 128
     w = _weights(n, C, 2, 5)
     gpu = _gpu(n, C, 2, B, w)
@@ -159,7 +159,7 @@ def test_zero_weights_leave_the_forty_gradients_alone(oz):
 
 def test_dead_masks_train_nothing(oz):
     """weights (1, 1) and every mask 0 (given as zero pairs, and not given at all): zero aux losses and gradients, and the 40 gradients of an
-    aux-off trainer.  k_t_aux_dgrad then adds a signed zero into every element of df2, and (-0) + (+0) = +0 is another bit pattern than -0 with
+    aux-off trainer.  k_t_heads_dgrad's second launch then adds a signed zero into every element of df2, and (-0) + (+0) = +0 is another bit pattern than -0 with
     the same value: the comparison of the forty is by value (np.array_equal), which is exact for everything but the sign of a zero"""
     n, C, B = 6, 128, 7
     w = _weights(n, C, 2, 9)
